@@ -13,7 +13,12 @@ Extra objects on the JSON line:
                ((4*K*nu noise + 4 cost) bytes x rollouts on this GPU) / its mean duration measured
                with HIP events on the launch stream; peak = 8 TB/s HBM3E.
   cpu_baseline the fp64 oracle (oracle/, kind "port": MuJoCo itself is not installable here) rolling out a bounded
-               sample of the same workload on all host cores, rank 0 at N=1 only.
+               sample of the same workload on all host cores, rank 0 at N=1 only (--full).
+
+A plain run sets up, warms up, times --steps plan steps and prints the line.  --full adds, after the timed steps, the
+measurements that run further plan steps or CPU work of their own: benchmark_100 / steady_state, plan_step_ms_with_traces,
+cube_only, recorded_inputs and cpu_baseline (each still switched off by its --no-* option).
+--dump-outputs DIR writes what the last timed step returned to its caller as DIR/<name>.npy (float32 / float64).
 """
 
 from __future__ import annotations
@@ -41,6 +46,27 @@ WORKLOADS = {
 }
 HBM_PEAK_GBS = 8000.0
 TRAFFIC_FILE = "r06_traffic.json"
+DUMP_ROWS_MAX = 1 << 20  # --dump-outputs: larger arrays are cut to a fixed, seeded sample of this many rows (dump_outputs)
+DUMP_BYTES_MAX = 64 << 20
+
+
+def dump_outputs(out_dir: str, arrays: dict, rows_max: int = DUMP_ROWS_MAX) -> None:
+    """Write every array as <out_dir>/<name>.npy, float32 kept, any other dtype as float64.  An array of more than `rows_max` rows is replaced by the
+    rows of a fixed sample (seed 0, ascending), whose indices go to <name>_rows.npy: the same arguments dump the same rows from run to run."""
+    out = {}
+    for name, a in arrays.items():
+        a = np.asarray(a)
+        if a.shape and a.shape[0] > rows_max:
+            rows = np.sort(np.random.default_rng(0).choice(a.shape[0], rows_max, replace=False))
+            a = a[rows]
+            out[name + "_rows"] = rows.astype(np.float64)
+        out[name] = a if a.dtype in (np.float32, np.float64) else a.astype(np.float64)
+    total = sum(a.nbytes for a in out.values())
+    if total > DUMP_BYTES_MAX:
+        raise SystemExit(f"bench.py: --dump-outputs would write {total} bytes, more than {DUMP_BYTES_MAX}")
+    os.makedirs(out_dir, exist_ok=True)
+    for name, a in out.items():
+        np.save(os.path.join(out_dir, name + ".npy"), a)
 
 
 def usable_cpus() -> int:
@@ -162,7 +188,7 @@ def materialize_line(args, torch, world: int, rank: int) -> None:
     t0 = time.perf_counter()
     ev0.record()
     for _ in range(args.steps):
-        be.rollout_device(x0, U)
+        out = be.rollout_device(x0, U)
     ev1.record()
     torch.cuda.synchronize()
     if world > 1:
@@ -172,6 +198,8 @@ def materialize_line(args, torch, world: int, rank: int) -> None:
         t = torch.tensor([elapsed], dtype=torch.float64, device="cpu" if SHARED_GPU_TEST else "cuda")
         torch.distributed.all_reduce(t, op=torch.distributed.ReduceOp.MAX)
         elapsed = float(t.item())
+    if args.dump_outputs and rank == 0:  # (N, H, nx) states are GBs at the default sizes: 1024 sampled rollouts of rank 0's shard
+        dump_outputs(args.dump_outputs, {"states": out[0].cpu().numpy(), "sensors": out[1].cpu().numpy()}, rows_max=1024)
     kern_ms = ev0.elapsed_time(ev1) / args.steps
     alg = 4 * n_local * H * (gm.nx + gm.ns + gm.nu)
     achieved = alg / (kern_ms * 1e-3) / 1e9
@@ -234,7 +262,15 @@ def main() -> None:
     ap.add_argument("--no-replay", action="store_true", help="skip the replay of the recorded plan inputs (the deterministic, round-to-round comparable figure) after the timed region")
     ap.add_argument("--mode", default="fused", choices=["fused", "materialize"],
                     help="fused = the plan step (headline); materialize = drop-in RolloutBackend.rollout writing every state/sensor (the HBM-bound exhibit, SURVEY 8d)")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps, also run the measurements the headline does not need: benchmark_100 / steady_state, traces cost, cube_only, "
+                         "recorded inputs, CPU baseline")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step returned (plan step: nominal_knots, times, rewards, traces when read in the step; materialize: sampled "
+                         "states / sensors) as DIR/<name>.npy")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
 
     world = int(os.environ.get("WORLD_SIZE", "1"))
     rank = int(os.environ.get("RANK", "0"))
@@ -357,12 +393,15 @@ def main() -> None:
         t = torch.tensor([elapsed], dtype=torch.float64, device="cpu" if SHARED_GPU_TEST else "cuda")
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         elapsed = float(t.item())
+    if args.dump_outputs and rank == 0:  # the plan the caller of update_action gets, the last iteration's rewards (this rank's shard) and the traces the step read
+        dump_outputs(args.dump_outputs, dict(nominal_knots=ctrl.nominal_knots, times=ctrl.times, rewards=ctrl.rewards,
+                                             **({"traces": ctrl.traces} if traces_in_step else {})))
     kern_ms = float(np.mean([a.elapsed_time(b) for a, b in ctrl.kernel_events])) if ctrl.kernel_events else float("nan")
     # The timed steps start from rest, the cheap end of the closed loop.  The reference's own statistic (judo/app/benchmark.py:19,96-107) is 100 timed plan steps after 10
     # warm-ups, summarised as mean / std / median / IQR / min / max: when --steps < 100 that loop is run here as well -- restarted from the same state and seed, outside
     # `value` -- so that the tail of the distribution is in the driver's line and not only under profiles/.  `steady_state` = its last 20 plan steps.
     steady, bench100 = None, None
-    if world == 1 and not is_policy and not args.no_steady_state and args.steps < 100:
+    if args.full and world == 1 and not is_policy and not args.no_steady_state and args.steps < 100:
         n_warm, n_timed, n_last = 10, 100, 20
         n_ev = len(ctrl.kernel_events)
         ctrl.reserve_timing_events(4 * (n_warm + n_timed) * max(1, ctrl.max_opt_iters) + 8)
@@ -420,7 +459,7 @@ def main() -> None:
     # the reference's plan time includes update_traces (judo/controller/controller.py:299).  Since round 3 the fused kernels write every rollout's trace sensors and the
     # elites' rows are gathered on the device, so reading `Controller.traces` is part of the timed steps above; what it costs on its own is measured here, on further steps
     with_traces = None
-    if not is_policy and ctrl.trace_sensors and not args.no_with_traces:
+    if args.full and not is_policy and ctrl.trace_sensors and not args.no_with_traces:
         # (the plan keeps moving, and with it the cost of a plan step: the extra steps are not compared with the timed ones as wholes -- what is measured is the
         # time reading `Controller.traces` adds to each of them, which is then put on top of the timed steps' mean)
         n_extra, tq, t_tr = min(args.steps, 10), t_plan, 0.0
@@ -441,7 +480,7 @@ def main() -> None:
                                "steps; in_value: the timed steps read the traces themselves, as the reference's update_action does"}
     # leap_cube: the same measurement restarted with the hand's own contacts switched off (the model round 1 measured), outside the timed region
     cube_only = None
-    if args.task == "leap_cube" and world == 1 and ctrl.model is not None and ctrl.model.self_collision and not args.no_cube_only:
+    if args.full and args.task == "leap_cube" and world == 1 and ctrl.model is not None and ctrl.model.self_collision and not args.no_cube_only:
         ctrl.model.set_self_collision(False)
         ctrl.reset()
         ctrl.current_state = ctrl.task.default_state()
@@ -465,7 +504,7 @@ def main() -> None:
     # from round to round: the plan inputs of 40 consecutive plan steps recorded once in round 2 (tools/diag/ab_fixed_inputs.py record), replayed with fixed per-step seeds.
     replay = None
     rfile = os.path.join(ROOT, "tools", "diag", {"leap_cube": "ab_inputs_leap.npz", "fr3_pick": "ab_inputs_fr3.npz"}.get(args.task, "-"))
-    if world == 1 and not is_policy and not args.no_replay and os.path.exists(rfile) and (N, H) == WORKLOADS[args.task][1:] and args.optimizer is None:
+    if args.full and world == 1 and not is_policy and not args.no_replay and os.path.exists(rfile) and (N, H) == WORKLOADS[args.task][1:] and args.optimizer is None:
         rec = np.load(rfile)
         ctrl.reset()
         ctrl.current_state = ctrl.task.default_state()
@@ -560,7 +599,7 @@ def main() -> None:
             line["steady_state"] = steady
         if replay:
             line["recorded_inputs"] = replay
-        if world == 1 and not args.no_cpu_baseline:
+        if args.full and world == 1 and not args.no_cpu_baseline:
             line["cpu_baseline"] = cpu_baseline_policy(ctrl) if is_policy else cpu_baseline(args.task, ctrl)
         print(json.dumps(line))
     if world > 1 or rccl_one:

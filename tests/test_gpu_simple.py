@@ -382,6 +382,35 @@ def test_benchmark_sweep_reports_every_pair(gpu):
             assert 0 < r["min"] <= r["median"] <= r["max"] and r["iqr25"] <= r["iqr75"]
 
 
+def test_bench_dumps_the_last_timed_step_and_runs_its_extras_only_with_full(gpu, tmp_path):
+    """`bench.py --dump-outputs DIR` writes the last timed plan step's plan, rewards and traces, the same from run to run (the extras of --full run after the
+    dump); a plain line carries none of the after-the-timed-steps measurements, a --full line does."""
+    import json
+    import subprocess
+    import sys
+
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    cmd = [sys.executable, os.path.join(root, "bench.py"), "--task", "cartpole", "--rollouts", "256", "--steps", "3", "--warmup", "1", "--settle", "0"]
+    lines = []
+    for i, extra in enumerate(([], ["--full", "--no-cpu-baseline"])):
+        r = subprocess.run(cmd + extra + ["--dump-outputs", str(tmp_path / f"run{i}")], capture_output=True, text=True, timeout=600, cwd=root)
+        assert r.returncode == 0, r.stderr[-2000:]
+        js = [ln for ln in r.stdout.splitlines() if ln.startswith("{")]
+        assert len(js) == 1, r.stdout[-2000:]
+        lines.append(json.loads(js[0]))
+    plain, full = lines
+    assert plain["steps"] == 3 and plain["ms_per_step"] > 0 and plain["unit"] == "rollouts/s" and plain["higher_is_better"] and plain["dtype"] == "f32"
+    assert not {"benchmark_100", "steady_state", "plan_step_ms_with_traces", "recorded_inputs", "cpu_baseline"} & set(plain)
+    assert {"benchmark_100", "steady_state", "plan_step_ms_with_traces"} <= set(full)
+    names = sorted(os.listdir(tmp_path / "run0"))
+    assert names == ["nominal_knots.npy", "rewards.npy", "times.npy", "traces.npy"] and sorted(os.listdir(tmp_path / "run1")) == names
+    for name in names:
+        a, b = np.load(tmp_path / "run0" / name), np.load(tmp_path / "run1" / name)
+        assert a.dtype in (np.float32, np.float64) and np.isfinite(a).all(), name
+        np.testing.assert_array_equal(a, b)
+    assert np.load(tmp_path / "run0" / "rewards.npy").shape == (256,) and np.load(tmp_path / "run0" / "nominal_knots.npy").shape[0] == full["config"]["num_nodes"]
+
+
 @pytest.mark.parametrize("nu,K,N", [(1, 4, 70), (2, 5, 129), (16, 4, 33)])
 def test_knot_moments_kernel(gpu, nu, K, N):
     """jh_knot_moments: sum and sum of squares of (candidate knot - center) per actuator, from the recomputed or the explicit knots."""

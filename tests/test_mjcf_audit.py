@@ -1,15 +1,30 @@
 """The model compiler may not silently drop a physics attribute of the reference's MJCF files (rounds 1-3 dropped `euler` on nine geoms of the Spot arm -- wrong in the
-oracle AND in the kernel, every parity test green).  Build container only: needs /root/reference (the GPU box has none; the compiled models are committed JSON)."""
+oracle AND in the kernel, every parity test green).  The MJCF files are not part of this repository: the audit reads their attribute census
+(tests/golden/mjcf_attributes.json, tools/diag/mjcf_attribute_audit.py --write-census), the refusals are shown on a small model of our own (STAND_IN)."""
 import importlib.util
+import json
 import os
 import sys
-import xml.etree.ElementTree as ET
 
 import pytest
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-REF = "/root/reference/judo/models/xml"
-pytestmark = pytest.mark.skipif(not os.path.isdir(REF), reason="needs the reference's MJCF files")
+
+# one body on a hinge with a sphere and a motor: it compiles as it stands, so every refusal below is the patched attribute's
+STAND_IN = """<mujoco model="stand_in">
+  <compiler angle="radian"/>
+  <option timestep="0.01"/>
+  <worldbody>
+    <body name="pole" pos="0 0 1">
+      <joint name="hinge" type="hinge" axis="0 1 0"/>
+      <geom name="bob" type="sphere" size="0.1"/>
+    </body>
+  </worldbody>
+  <actuator>
+    <motor name="torque" joint="hinge"/>
+  </actuator>
+</mujoco>
+"""
 
 
 def _load(path, name):
@@ -25,7 +40,10 @@ def _load(path, name):
 
 def test_every_non_visual_attribute_of_the_shipped_mjcf_is_read_by_the_compiler():
     audit = _load(os.path.join(ROOT, "tools", "diag", "mjcf_attribute_audit.py"), "mjcf_attribute_audit")
-    assert audit.unread_non_visual() == {}, "tools/compile_mjcf.py never reads these attributes: implement them or raise on a non-default value"
+    with open(audit.CENSUS) as f:
+        seen = json.load(f)
+    assert set(seen) >= {"body", "geom", "joint", "option", "compiler", "position", "framepos"} and "euler" in seen["geom"]  # the census covers the seven models
+    assert audit.unread_non_visual(seen) == {}, "tools/compile_mjcf.py never reads these attributes: implement them or raise on a non-default value"
 
 
 @pytest.mark.parametrize("xml_name,tag,attr,value", [
@@ -36,8 +54,12 @@ def test_every_non_visual_attribute_of_the_shipped_mjcf_is_read_by_the_compiler(
     ("leap_cube.xml", "body", "zaxis", "0 0 1"),
     ("spot_primitive/robot.xml", "geom", "contype", "2"),  # mixed collision masks: the pair lists apply MuJoCo's body-level filters only
 ])
-def test_a_value_the_engines_do_not_model_is_refused(monkeypatch, xml_name, tag, attr, value):
+def test_a_value_the_engines_do_not_model_is_refused(monkeypatch, tmp_path, xml_name, tag, attr, value):
     C = _load(os.path.join(ROOT, "tools", "compile_mjcf.py"), "compile_mjcf_audit")
+    (tmp_path / xml_name).parent.mkdir(parents=True, exist_ok=True)
+    (tmp_path / xml_name).write_text(STAND_IN)
+    monkeypatch.setattr(C, "REF_XML", str(tmp_path))
+    assert C.compile_model(xml_name, "x")["joints"][0]["name"] == "hinge"
     load = C.load_xml
 
     def patched(path):
@@ -49,16 +71,3 @@ def test_a_value_the_engines_do_not_model_is_refused(monkeypatch, xml_name, tag,
     monkeypatch.setattr(C, "load_xml", patched)
     with pytest.raises(NotImplementedError):
         C.compile_model(xml_name, "x")
-
-
-def test_the_committed_models_are_what_the_compiler_produces_today():
-    import json
-
-    C = _load(os.path.join(ROOT, "tools", "compile_mjcf.py"), "compile_mjcf_regen")
-    for xml_name, task in (("cartpole.xml", "cartpole"), ("cylinder_push.xml", "cylinder_push"), ("leap_cube.xml", "leap_cube"), ("fr3_pick.xml", "fr3_pick"),
-                           ("leap_cube_palm_down.xml", "leap_cube_down"), ("caltech_leap_cube.xml", "caltech_leap_cube"), ("spot_primitive/robot.xml", "spot")):
-        m = C.compile_model(xml_name, task)
-        if task in ("leap_cube_down", "caltech_leap_cube"):
-            m["family"] = "leap_cube"
-        committed = json.load(open(os.path.join(ROOT, "judo_amd", "models", task + ".json")))
-        assert json.loads(json.dumps(m)) == committed, task
