@@ -62,7 +62,7 @@ int jh_model_dims(const jh_model* m, int* dims /* HOST */);
  * Newton iteration cap, out[2] Newton iterations (summed over rollouts), out[3] physics steps (summed over rollouts); leap_cube kernel generation 3 also:
  * out[4] Newton iterations executed by wavefronts (four rollouts advance in lock step: per step the maximum over the four), out[5] physics steps
  * summed over wavefronts; out[6] launches that ran without their overflow rows because the device's memory pool refused the scratch block (the contact capacity was then what
- * the LDS pool holds), out[7] reserved (0).  The counters are 32-bit and wrap: reset them at least every ~10^9 rollout-steps.  HOST pointer. */
+ * the LDS pool holds); out[7] plan steps of jh_plan_step / jh_plan_step_shard that ran as one launch (cartpole, cylinder_push; counted on the host, no device work).  The counters are 32-bit and wrap: reset them at least every ~10^9 rollout-steps.  HOST pointer. */
 int jh_model_stats(jh_model* m, int* out /* HOST, 8 ints */, int reset);
 
 /* (The cross-check kernel generations of the parity tests and their registration hook are NOT part of this interface: include/judo_amd_xcheck.h.) */
@@ -105,6 +105,14 @@ int jh_model_limits(const jh_model* m, int* out /* HOST, 4 ints */);
  * steps (>= 0), or a negative jh_status.  A Controller asks before every plan step and takes the materialise path above it (a live num_nodes / horizon
  * edit, judo/optimizers/base.py:15-21, must not raise out of update_action). */
 int jh_model_max_fused_knots(const jh_model* m, int H);
+/* The closed-form models (cartpole, cylinder_push) run a plan step of jh_plan_step as ONE launch (rollout + cost + update tail) when the knots of a workgroup of 256
+ * rollouts and W fit its 48 KiB LDS staging: this returns the largest such K at horizon H (<= jh_model_max_fused_knots; 0 for the other models), or a negative jh_status.
+ * Above it the plan step takes two launches, the fused rollout kernel and then the update tail; both forms give the same bits. */
+int jh_model_one_launch_max_knots(const jh_model* m, int H);
+/* How jh_plan_step / jh_plan_step_shard run a closed-form model's plan step: 0 = one launch up to jh_model_one_launch_max_knots, two above (the default), 1 = always one
+ * launch (a plan step it cannot hold -- K above the limit, or knots_out requested -- fails with JH_ERR_INVALID), 2 = always two.  The environment variable
+ * JUDO_AMD_PLAN_STEP_LAUNCHES=2 makes 2 the default of every model created after it is set.  1 is refused for the articulated models, which always take two. */
+int jh_model_set_plan_step_launches(jh_model* m, int launches);
 
 /* Plan-step I/O in one call each (the two transfers of a plan step: < 2 KB down, the new nominal knots up): an asynchronous copy of `nbytes` from
  * pinned HOST memory to the device on `stream`; and an asynchronous copy from the device to pinned HOST memory followed by a wait for `stream`
@@ -158,7 +166,8 @@ int jh_sample_knots(const float* nominal, const float* noise, int ldn, const flo
 /* Candidate control trajectories of the materialise path (judo/controller/controller.py:239-249: the candidate splines evaluated at
  * the rollout times): controls[n,h,u] = sum_k W[h,k] * knot(n,k,u), (N,H,nu) row-major, ready for jh_rollout_materialize.
  * W is the (H,K) interpolation matrix of the spline kind (linear in the knots for zero/linear/cubic interp1d); knots come from
- * `knots_nku` or, when it is NULL, are recomputed as clip(nominal + sigma*noise) exactly like jh_rollout_cost does. */
+ * `knots_nku` or, when it is NULL, are recomputed as clip(nominal + sigma*noise) exactly like jh_rollout_cost does.  Every K * nu <= JH_MAX_KNOT_DIM and every H:
+ * W and the knots are staged in LDS where they fit and read from global memory where they do not (same bits). */
 int jh_spline_controls(const float* W, const float* knots_nku, const float* nominal, const float* noise, int ldn, const float* sigma,
                        const float* ctrl_lo_hi, int N, int n_offset, int H, int K, int nu, float* controls, void* stream);
 
@@ -191,7 +200,11 @@ int jh_topk_partial(const float* costs, const float* knots_nku, const float* nom
  * (mode 0) or jh_topk_partial + jh_elite_merge (mode 1: k elites, raw population std into sigma_out, which may be NULL) compute, plus -- when E > 0 -- the records
  * [cost, global index (bits), trace row] of the E best rollouts (ties: higher index first) that jh_topk_partial + jh_trace_gather produce, into trace_out (E x (2 + row_floats)).
  * Every workgroup writes its partial records to `scratch` and the last one to finish merges them: same arithmetic in the same order as the separate calls, bit-identical
- * outputs.  `scratch`: jh_update_fused_scratch_floats(N, K, nu) floats, ZERO before its first use (it holds the ticket counter, which every launch leaves at zero). */
+ * outputs.  `scratch`: jh_update_fused_scratch_floats(N, K, nu) floats, ZERO before its first use (it holds the ticket counter, which every launch leaves at zero).
+ * NaN costs (a diverged rollout) deviate from the reference on purpose: the update takes a NaN cost for +inf -- MPPI weight zero, ranked behind every finite cost
+ * for the CEM / PS elites and the trace elites -- where numpy would let it poison the weighted mean, win np.argmax and sort first in flip(argsort).  A trace record whose
+ * rollout's cost is +inf or NaN (>= 3e38), or that lies past the last rollout (E > N), is empty: cost +inf, index -1, zero row.  With no finite cost at all the MPPI
+ * mean is NaN, as the reference's is. */
 size_t jh_update_fused_scratch_floats(int N, int K, int nu);
 int jh_update_fused(const float* costs, const float* knots_nku, const float* nominal, const float* noise, int ldn, const float* sigma, const float* ctrl_lo_hi, int N,
                     int n_offset, int K, int nu, int mode, float lambda, int k, int tie_high, int E, const float* trace, int row_floats, int colmajor, float* scratch,

@@ -27,6 +27,8 @@ _SIGNATURES = {
     "jh_model_limits": (C.c_int, [C.c_void_p, C.POINTER(C.c_int)]),
     "jh_register_xcheck": (C.c_int, [C.c_void_p]),
     "jh_model_max_fused_knots": (C.c_int, [C.c_void_p, C.c_int]),
+    "jh_model_one_launch_max_knots": (C.c_int, [C.c_void_p, C.c_int]),
+    "jh_model_set_plan_step_launches": (C.c_int, [C.c_void_p, C.c_int]),
     "jh_model_set_self_collision": (C.c_int, [C.c_void_p, C.c_int]),
     "jh_model_set_contact_capacity": (C.c_int, [C.c_void_p, C.c_int]),
     "jh_model_trace_layout": (C.c_int, [C.c_void_p, C.POINTER(C.c_int)]),

@@ -33,6 +33,7 @@ extern "C" int jh_model_create(const void* blob, size_t nbytes, int device, jh_m
   jh_model* m = new jh_model();
   m->device = device; m->kind = (int)h.kind; m->nq = h.nq; m->nv = h.nv; m->nu = h.nu; m->ns = h.ns; m->ntaskparam = h.ntaskparam;
   m->nf = h.nfloat; m->ni = h.nint; m->d_f = nullptr; m->d_i = nullptr; m->d_stats = nullptr; m->kernel_gen = (h.kind == JH_TASK_LEAP_CUBE || h.kind == JH_TASK_FR3_PICK) ? 3 : 2; m->self_collision = 1; m->contact_capacity = 48;
+  { const char* e = getenv("JUDO_AMD_PLAN_STEP_LAUNCHES"); m->plan_step_launches = (e && e[0] == '2') ? 2 : 0; }  // (the environment sets the default; jh_model_set_plan_step_launches changes it per model)
   const char* p = (const char*)blob + sizeof(h);
   m->h_f.assign((const float*)p, (const float*)p + h.nfloat);
   m->h_i.assign((const int*)(p + 4 * (size_t)h.nfloat), (const int*)(p + 4 * (size_t)h.nfloat) + h.nint);
@@ -80,7 +81,8 @@ extern "C" int jh_model_stats(jh_model* m, int* out, int reset) {
   JH_REQUIRE(m && out, "model_stats: null pointer");
   JH_HIP(hipMemcpy(out, m->d_stats, 4 * sizeof(int), hipMemcpyDeviceToHost));
   JH_HIP(hipMemcpy(out + 4, m->d_stats + 20, 2 * sizeof(int), hipMemcpyDeviceToHost));
-  out[6] = reset ? __atomic_exchange_n(&m->ovf_fallbacks, 0, __ATOMIC_RELAXED) : __atomic_load_n(&m->ovf_fallbacks, __ATOMIC_RELAXED); out[7] = 0;
+  out[6] = reset ? __atomic_exchange_n(&m->ovf_fallbacks, 0, __ATOMIC_RELAXED) : __atomic_load_n(&m->ovf_fallbacks, __ATOMIC_RELAXED);
+  out[7] = reset ? __atomic_exchange_n(&m->one_launch_steps, 0, __ATOMIC_RELAXED) : __atomic_load_n(&m->one_launch_steps, __ATOMIC_RELAXED);
   if (reset) JH_HIP(hipMemset(m->d_stats, 0, JH_NSTATS * sizeof(int)));
   return JH_OK;
 }
@@ -178,6 +180,19 @@ extern "C" int jh_model_limits(const jh_model* m, int* out) {
 extern "C" int jh_model_max_fused_knots(const jh_model* m, int H) {
   JH_REQUIRE(m != nullptr && H >= 1, "model_max_fused_knots: null model or H < 1");
   return max_fused_knots(m, H);
+}
+
+extern "C" int jh_model_one_launch_max_knots(const jh_model* m, int H) {
+  JH_REQUIRE(m != nullptr && H >= 1, "model_one_launch_max_knots: null model or H < 1");
+  const int k = JH_MAX_KNOT_DIM / (m->nu > 0 ? m->nu : 1), lds_k = jh_simple_one_launch_max_knots(m, H);
+  return k < lds_k ? k : lds_k;
+}
+
+extern "C" int jh_model_set_plan_step_launches(jh_model* m, int launches) {
+  JH_REQUIRE(m != nullptr && launches >= 0 && launches <= 2, "model_set_plan_step_launches: launches must be 0 (automatic), 1 or 2");
+  JH_REQUIRE(launches != 1 || m->kind == JH_TASK_CARTPOLE || m->kind == JH_TASK_CYLINDER_PUSH, "model_set_plan_step_launches: only the closed-form models have a one-launch plan step");
+  m->plan_step_launches = launches;
+  return JH_OK;
 }
 
 extern "C" int jh_upload_async(void* dst, const void* src, size_t nbytes, void* stream) {
@@ -280,11 +295,20 @@ extern "C" int jh_rollout_cost_traced(const jh_model* m, const float* x0, const 
 }
 
 // Closed-form models (cartpole, cylinder_push): the rollout kernels are ~50 us, so a second launch and the gap in front of it are a fifth of the plan step -- the two run as
-// one launch (jh_simple.hip).  JUDO_AMD_PLAN_STEP_LAUNCHES=2 keeps the two launches (A/B, tests/test_gpu_simple.py compares the two forms bit for bit).
-static bool one_launch_plan_step(const jh_model* m, int N, int H, int K, const float* costs, const float* knots_out, const float* W, const float* noise, int ldn) {
-  static const bool two = [] { const char* e = getenv("JUDO_AMD_PLAN_STEP_LAUNCHES"); return e && e[0] == '2'; }();
-  if (two || !(m->kind == JH_TASK_CARTPOLE || m->kind == JH_TASK_CYLINDER_PUSH) || knots_out || !costs || !W || !noise) return false;
-  return N > 0 && H > 0 && K >= 1 && ldn >= N && K * m->nu <= JH_MAX_KNOT_DIM && jh_simple_plan_step_fits(m, H, K);
+// one launch (jh_simple.hip) wherever its LDS staging fits (K <= jh_model_one_launch_max_knots).  jh_model_set_plan_step_launches forces either form (2: the rollout kernel,
+// then k_update_tail), so that tests/test_gpu_plan_edges.py compares the two bit for bit in one process; JUDO_AMD_PLAN_STEP_LAUNCHES=2 sets that for every new model.
+// Forced one launch where it cannot run (knots_out requested, or K above the limit) is an error, not a quiet switch.
+static int plan_step_launches(const jh_model* m, int N, int H, int K, const float* costs, const float* knots_out, const float* W, const float* noise, int ldn, bool* one) {
+  *one = false;
+  if (m->plan_step_launches == 2 || !(m->kind == JH_TASK_CARTPOLE || m->kind == JH_TASK_CYLINDER_PUSH)) return JH_OK;
+  const bool fits = costs && W && noise && N > 0 && H > 0 && K >= 1 && ldn >= N && K * m->nu <= JH_MAX_KNOT_DIM && jh_simple_plan_step_fits(m, H, K);
+  if (m->plan_step_launches == 1) {
+    JH_REQUIRE(!knots_out, "plan_step: the one-launch plan step writes no candidate knots (knots_out), and one launch is forced (jh_model_set_plan_step_launches)");
+    JH_REQUIRE(fits, "plan_step: one launch is forced but K = %d exceeds its LDS staging at H = %d (jh_model_one_launch_max_knots)", K, H);
+  }
+  *one = fits && !knots_out;
+  if (*one) __atomic_fetch_add(&m->one_launch_steps, 1, __ATOMIC_RELAXED);
+  return JH_OK;
 }
 
 // One plan-step iteration on one GPU as ONE call (Controller.update_action's loop body, judo/controller/controller.py:250-299): the packed host block
@@ -305,7 +329,9 @@ extern "C" int jh_plan_step(const jh_model* m, void* blk_dev, const void* blk_ho
   // polls it instead of waiting for the stream's event
   unsigned* flag = (out_host_mark && out_host_mark != (void*)out) ? (unsigned*)out_host_mark : nullptr;
   const unsigned expect = flag ? __atomic_load_n(flag, __ATOMIC_RELAXED) + 1u : 0u;
-  if (rc == JH_OK && one_launch_plan_step(m, N, H, K, costs, knots_out, W, noise, ldn)) {
+  bool one = false;
+  if (rc == JH_OK) rc = plan_step_launches(m, N, H, K, costs, knots_out, W, noise, ldn, &one);
+  if (rc == JH_OK && one) {
     // closed-form models: rollout + cost + the update's tail in ONE launch (jh_simple.hip k_plan_step); the rollout / update split of the timing events collapses
     jh_upd::TailArgs a;
     rc = jh_update_tail_args("plan_step", costs, nullptr, b + o_nominal, noise, ldn, b + o_sigma, b + o_lohi, N, n_offset, K, m->nu, mode, lambda, k, tie_high, trace ? E : 0, trace, row_floats,
@@ -342,7 +368,9 @@ extern "C" int jh_plan_step_shard(const jh_model* m, void* blk_dev, const void* 
   hipStream_t st = (hipStream_t)stream;
   int rc = blk_dev == blk_host ? JH_OK : jh_upload_async(blk_dev, blk_host, blk_bytes, stream);
   if (rc == JH_OK && timing) JH_HIP(hipEventRecord((hipEvent_t)timing[0], st));
-  if (rc == JH_OK && one_launch_plan_step(m, N, H, K, costs, knots_out, W, noise, ldn)) {
+  bool one = false;
+  if (rc == JH_OK) rc = plan_step_launches(m, N, H, K, costs, knots_out, W, noise, ldn, &one);
+  if (rc == JH_OK && one) {
     jh_upd::TailArgs a;
     rc = jh_update_tail_args("plan_step_shard", costs, nullptr, b + o_nominal, noise, ldn, b + o_sigma, b + o_lohi, N, n_offset, K, m->nu, mode, lambda, k, tie_high, trace ? E : 0, trace,
                              row_floats, colmajor, scratch, nullptr, nullptr, nullptr, rec_out, &a);

@@ -29,6 +29,8 @@ struct jh_model {
   int kernel_gen;  // articulated engine kernel: 3 = cooperative 16-lanes-per-rollout, two waves per SIMD (leap_cube: v5; fr3_pick: v6, matrix-free contact Jacobian), 2 = cooperative, one wave per SIMD (leap_cube: v2, fr3_pick: v3), 1 = one lane per rollout
   int contact_capacity;  // leap_cube generation 3: 48 (all in LDS, jh_engine_v5.hip) or 64 (jh_engine_v5_cap64.hip); jh_model_set_contact_capacity
   int self_collision;  // leap_cube on jh_engine_v5.hip: model the hand's own contacts (finger-finger, finger-palm) as MuJoCo does; 0 = the cube's contacts only
+  int plan_step_launches;  // closed-form models' plan step: 0 = one launch where it fits (the default), 1 = always one launch, 2 = always two (jh_model_set_plan_step_launches)
+  mutable int one_launch_steps = 0;  // plan steps that ran as one launch (jh_model_stats out[7]); __atomic builtins, as ovf_fallbacks
   mutable int ovf_fallbacks = 0;  // launches that ran without their overflow rows (jh_launch_scratch); updated with __atomic builtins: a planner thread may launch while another polls jh_model_stats
   int* d_stats;  // JH_NSTATS diagnostic counters: [0..3] contact-cap overflows, Newton iteration-cap hits, Newton iterations, steps; [20..21] wave-level iterations, steps; the rest: diagnostic builds
   std::vector<float> h_f;
@@ -98,6 +100,7 @@ int jh_simple_rollout_cost(const jh_model* m, const float* x0, const float* nomi
 // solves in every step.  Returns the largest shift (<= log2 rpw) that still leaves every wave of the launch a SIMD of its own; JUDO_AMD_LATENCY_SHIFT=0..2 overrides.
 int jh_latency_shift(int N, int rpw);
 int jh_simple_max_knots(const jh_model* m, int H);  // largest fused K at horizon H (LDS staging budget of the launcher)
+int jh_simple_one_launch_max_knots(const jh_model* m, int H);  // largest K of the one-launch plan step at horizon H (its 48 KiB LDS staging)
 int jh_engine_max_knots(const jh_model* m, int H);
 int jh_simple_materialize(const jh_model* m, const float* x0, int x0_batched, const float* controls, int N, int H, float* states,
                           float* sensors, hipStream_t st);

@@ -368,12 +368,13 @@ int launch_plan_step(const jh_model* m, const float* x0, const float* W, const f
 }  // namespace
 
 // can the plan step of this model run as one launch?  (closed-form models; the knots of a workgroup of 256 rollouts must fit the LDS staging next to the update's own 9 KB)
-bool jh_simple_plan_step_fits(const jh_model* m, int H, int K) {
-  if (m->kind != JH_TASK_CARTPOLE && m->kind != JH_TASK_CYLINDER_PUSH) return false;
-  const int nu = m->kind == JH_TASK_CARTPOLE ? Cartpole::NU : CylinderPush::NU;
-  const int np = m->kind == JH_TASK_CARTPOLE ? Cartpole::NP + Cartpole::NTP + Cartpole::NX : CylinderPush::NP + CylinderPush::NTP + CylinderPush::NX;
-  return sizeof(float) * ((size_t)H * K + (size_t)K * nu * jh_upd::kUB + np) <= 48 * 1024;
+template <class T>
+static int one_launch_max_knots(int H) { return (int)((12 * 1024 - T::NP - T::NTP - T::NX) / ((size_t)H + (size_t)T::NU * jh_upd::kUB)); }  // launch_plan_step's 48 KiB, in floats
+int jh_simple_one_launch_max_knots(const jh_model* m, int H) {
+  if (m->kind != JH_TASK_CARTPOLE && m->kind != JH_TASK_CYLINDER_PUSH) return 0;
+  return m->kind == JH_TASK_CARTPOLE ? one_launch_max_knots<Cartpole>(H) : one_launch_max_knots<CylinderPush>(H);
 }
+bool jh_simple_plan_step_fits(const jh_model* m, int H, int K) { return K <= jh_simple_one_launch_max_knots(m, H); }
 
 #ifdef JH_TAIL_TICKS
 extern "C" int jh_debug_tail_ticks(long long* out) { return hipMemcpyFromSymbol(out, HIP_SYMBOL(jh_upd::g_tail_ticks), 16 * sizeof(long long)) == hipSuccess ? 0 : -2; }

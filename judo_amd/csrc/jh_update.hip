@@ -42,6 +42,19 @@ __global__ __launch_bounds__(64) void k_spline_controls(KnotSrc src, const float
   }
 }
 
+// The same sum where W and 64 rollouts' knots do not fit the LDS (K * nu >= 256, or a long horizon): one thread per output element reads W and the knots from global
+// memory (the knots recomputed by KnotSrc where they are not given).  Same products in the same order as k_spline_controls: the same bits.  Only K * nu and H*K above the
+// LDS staging take it -- the materialise path above the fused kernels' knot limit (include/judo_amd.h: a live num_nodes edit must not raise).
+__global__ __launch_bounds__(kUB) void k_spline_controls_global(KnotSrc src, const float* __restrict__ W, int N, int H, int K, float* __restrict__ out) {
+  const int nu = src.nu, row = H * nu;
+  const size_t f = (size_t)blockIdx.x * kUB + threadIdx.x;
+  if (f >= (size_t)N * row) return;
+  const int r = (int)(f / row), i = (int)(f - (size_t)r * row), h = i / nu, u = i - h * nu;
+  float v = 0.f;
+  for (int k = 0; k < K; k++) v = fmaf(W[(size_t)h * K + k], src.get(r, k * nu + u), v);
+  out[f] = v;
+}
+
 // Moments of the candidate knots per actuator for the running action normaliser (judo/utils/normalization.py:176-200 on
 // `candidate_knots`): out[u] += sum_{n,k} (x - center[u]), out[nu+u] += sum_{n,k} (x - center[u])^2.  One wave per 64 rollouts, wave
 // butterflies, one atomic per (block, actuator, moment).
@@ -171,10 +184,14 @@ extern "C" int jh_spline_controls(const float* W, const float* knots_nku, const 
   JH_REQUIRE(knots_nku || (nominal && noise && sigma), "spline_controls: need either knots_nku or nominal+noise+sigma");
   JH_REQUIRE(knots_nku || ldn >= N, "spline_controls: ldn (%d) < N (%d)", ldn, N);
   JH_REQUIRE(H > 0, "spline_controls: H must be positive");
-  size_t lds = sizeof(float) * ((size_t)H * K + 64 * (size_t)((K * nu) | 1));
-  JH_REQUIRE(lds <= 64 * 1024, "spline_controls: H*K too large for the LDS staging (%zu bytes)", lds);
+  const size_t lds = sizeof(float) * ((size_t)H * K + 64 * (size_t)((K * nu) | 1));
   KnotSrc src{knots_nku, nominal, noise, sigma, lohi, ldn, n_offset, K * nu, nu};
-  hipLaunchKernelGGL(k_spline_controls, dim3((N + 63) / 64), dim3(64), lds, (hipStream_t)stream, src, W, N, H, K, controls);
+  if (lds <= 64 * 1024) hipLaunchKernelGGL(k_spline_controls, dim3((N + 63) / 64), dim3(64), lds, (hipStream_t)stream, src, W, N, H, K, controls);
+  else {  // (no LDS staging: every K * nu <= JH_MAX_KNOT_DIM and every horizon)
+    const size_t total = (size_t)N * H * nu;
+    JH_REQUIRE(total / kUB < 0x7fffffffu, "spline_controls: N * H * nu = %zu too large for one launch", total);
+    hipLaunchKernelGGL(k_spline_controls_global, dim3((unsigned)((total + kUB - 1) / kUB)), dim3(kUB), 0, (hipStream_t)stream, src, W, N, H, K, controls);
+  }
   JH_HIP(hipGetLastError());
   return JH_OK;
 }

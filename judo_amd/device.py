@@ -149,12 +149,23 @@ class GpuModel:
             self._max_knots_cache[H] = k
         return k
 
+    def one_launch_max_knots_at(self, H: int) -> int:
+        """Largest K whose plan step runs as one launch at horizon H (`jh_model_one_launch_max_knots`; 0: the model has no one-launch form)."""
+        k = int(_lib.lib().jh_model_one_launch_max_knots(self.handle, int(H)))
+        if k < 0:
+            _lib.check(k, "jh_model_one_launch_max_knots")
+        return k
+
+    def set_plan_step_launches(self, launches: int) -> None:
+        """0: one launch where it fits (default), 1: always one launch, 2: always two (`jh_model_set_plan_step_launches`)."""
+        _lib.check(_lib.lib().jh_model_set_plan_step_launches(self.handle, int(launches)), "jh_model_set_plan_step_launches")
+
     def stats(self, reset: bool = True) -> dict:
         """Diagnostic counters of the articulated-body kernels (synchronises)."""
         out = (C.c_int * 8)()
         _lib.check(_lib.lib().jh_model_stats(self.handle, out, int(reset)), "jh_model_stats")
         u = [v & 0xFFFFFFFF for v in out]  # 32-bit counters: unsigned
-        return {"contact_overflow": u[0], "newton_cap_hits": u[1], "newton_iters": u[2], "steps": u[3], "wave_newton_iters": u[4], "wave_steps": u[5], "overflow_pool_fallbacks": u[6]}
+        return {"contact_overflow": u[0], "newton_cap_hits": u[1], "newton_iters": u[2], "steps": u[3], "wave_newton_iters": u[4], "wave_steps": u[5], "overflow_pool_fallbacks": u[6], "one_launch_plan_steps": u[7]}
 
     def __del__(self) -> None:
         try:
