@@ -267,8 +267,9 @@ int jh_policy_step(const jh_policy* p, const float* states, int ld, int nq, int 
 
 /* ---- physics half of the Spot policy rollout (System::rollout's inner mj_step loop, mujoco_extensions/system/system_class.cpp:300-318): advance
  * N rollouts of a floating-base robot on a ground plane by `substeps` engine steps with the control held.  The model image is what
- * judo_amd/tree_model.py packs (free base + 19 hinges in 5 chains, plane contacts, pyramidal cones, implicitfast).  state_in / state_out are
- * (N x 51) rows [qpos(26), qvel(25)] and may alias; ctrl is (N x 19) joint position targets; warmstart (N x 25, may be NULL) is the solver's
+ * judo_amd/tree_model.py packs (free base + 19 hinges in 5 chains, plane contacts, pyramidal cones, implicitfast; optionally ONE free box, spot_box).  state_in / state_out are
+ * (N x (nq + nv)) rows [qpos(nq), qvel(nv)] and may alias -- nq / nv = 26 / 25, with the box 33 / 31 (its qpos / qvel after the robot's; jh_tree_dims);
+ * ctrl is (N x 19) joint position targets; warmstart (N x nv, may be NULL) is the solver's
  * starting acceleration, read and overwritten with this call's last constraint-consistent acceleration (mjData.qacc_warmstart).  sensors_out (N x nsensordata,
  * may be NULL): mjData.sensordata as mj_step leaves it after the last step, i.e. the site positions / frame axes of that step's forward pass.
  * jh_tree_stats: [contacts dropped over capacity, steps at the iteration cap, Newton iterations, steps]. */
@@ -284,8 +285,8 @@ int jh_tree_substeps(const jh_tree* t, const float* state_in, const float* ctrl,
                      void* stream);
 
 /* ---- the whole of threaded_rollout (mujoco_extensions/system/system_class.cpp:277-367; pybind entry mujoco_extensions/policy_rollout/pybind/policy_rollout.cpp:65)
- * in the reference's array layouts: x0 is one (51) state (x0_batched = 0) or (N x 51); commands (N x T x 25); states (N x T x 51), row [n][i] = the state after
- * command row i's policy step and `substeps` engine steps, sensors (N x T x nsensordata, may be NULL) the sensordata of the same row; policy_out (N x 12) in/out (last_policy_output -> policy_outputs).  warmstart (N x 25, may be NULL)
+ * in the reference's array layouts: x0 is one (nq + nv) state (x0_batched = 0) or (N x (nq + nv)); commands (N x T x 25); states (N x T x (nq + nv)), row [n][i] = the state after
+ * command row i's policy step and `substeps` engine steps, sensors (N x T x nsensordata, may be NULL) the sensordata of the same row; policy_out (N x 12) in/out (last_policy_output -> policy_outputs).  warmstart (N x nv, may be NULL)
  * carries mjData.qacc_warmstart from call to call as the reference's per-thread mjData does; reset_warmstart != 0 zeroes it before every control step instead.
  * cutoff_seconds >= 0: the rollout stops issuing command rows once that much DEVICE time has passed since the call started (checked against the control
  * step two back) and the remaining rows repeat the last computed state, as System::rollout does with its wall clock; < 0: no deadline.  *steps_done = rows

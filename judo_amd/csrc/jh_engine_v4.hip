@@ -21,6 +21,14 @@
 // between two different chains (leg against leg, arm against leg) needs a second chain block (J2, at most NX2 such contacts per rollout and step) and couples the two
 // chains in the Hessian: the fill-in-free tree factorisation does not apply, and the rollouts that have such a contact in a step take a dense 25 x 25 Cholesky
 // (dense_cholesky_solve: one row per lane in registers, pivot rows broadcast through LDS) for that step's Newton systems.
+//
+// spot_box (judo/models/xml/spot_box/robot.xml): ONE free box besides the robot, template parameter OBJ.  Its six dofs sit on the idle lanes 26..31 (world-frame
+// translation, body-frame rotation, centre of mass at the body origin: a diagonal, constant inertia block).  Contacts: the box against the plane (PlaneBox, lane 31) and
+// against every robot geom (jh_coop.h's box-sphere / box-capsule / box-box, one pair per lane; the normal points from the robot geom to the box).  A robot-box contact row
+// moves the box, the base and ONE chain, a box-plane row the box alone.  Newton: the box block of the Hessian (6 x 6, dense) is eliminated first (Schur complement through
+// its Cholesky factor, every robot row and the right-hand side updated by the lanes that own them), the robot system keeps its size and -- as long as the box touches at most
+// one chain in the step -- its tree structure; a rollout whose box touches two chains takes the dense 25 x 25 path for that step.  The box part of the solution follows from
+// the robot part.  State rows: nq = 33 (robot 26, box 7), nv = 31 (robot 25, box 6), stride 64.
 #include <cstddef>
 #include "jh_coop.h"
 
@@ -33,6 +41,8 @@ namespace {
 
 constexpr int G = 32, RPW = 2, WAVE = 64;
 constexpr int NJ = 19, NVT = 25, NQ = 26, NX = 51, NB = 20, MAXD = 7;
+constexpr int NQO = NQ + 7, NVO = NVT + 6, NXO = NQO + NVO;  // with the free box (OBJ): its qpos after the robot's, its qvel after the robot's
+constexpr int TO_F = 48, TO_I = 4, OB_G = 20;               // object records (judo_amd/tree_model.py); OB_G: where the box's geom record sits in the float record
 constexpr int NCP = 32, RAW_F = 8, NR = NVT + 1;  // NR: row registers
 // Contact Jacobian row (contact frame x dofs), compact: a ground contact moves with the base and ONE chain.  [3 b + r] base dof b, [JC + 3 m + r] position m of
 // the contact's chain (zero beyond the owner link), rows padded to float4s.
@@ -61,7 +71,7 @@ constexpr int MAXHIT4 = 64;  // robot-robot geom pairs that survive the broad ph
 constexpr int MAXPP = 9;     // robot-robot geom pairs per lane (32 lanes: 288 pairs; Spot has 287): the lane's share of the pair list is read once per launch and kept in registers
 
 template <bool SELF>
-struct __attribute__((aligned(16))) RS4T {  // per-rollout shared state; positions are relative to the base origin
+struct __attribute__((aligned(16))) RS4Core {  // per-rollout shared state; positions are relative to the base origin
   float vec[3][G];                        // broadcast vectors (read as float4)
   float Lb[7][LBW];                       // base rows (6 = the rhs) pushed through the chain factors: [0..18] chain columns
   float LbT[NJ][8];                       // the same, transposed: per joint the six base-row entries and the rhs entry
@@ -84,8 +94,20 @@ struct __attribute__((aligned(16))) RS4T {  // per-rollout shared state; positio
   int xc[SELF ? NX2 : 1];                    // contact index of cross contact x
   int ncon, nx2;
 };
-using RS4 = RS4T<false>;
-static_assert(offsetof(RS4T<true>, Hc) % 16 == 0 && offsetof(RS4T<false>, Hc) % 16 == 0 && sizeof(RS4T<true>) % 16 == 0 && sizeof(RS4T<false>) % 16 == 0, "Hc rows are moved as 16-byte vectors");
+static_assert(offsetof(RS4Core<true>, Hc) % 16 == 0 && offsetof(RS4Core<false>, Hc) % 16 == 0 && sizeof(RS4Core<true>) % 16 == 0 && sizeof(RS4Core<false>) % 16 == 0, "Hc rows are moved as 16-byte vectors");
+// the kernel's shared state; with the free box (OBJ) the contact bookkeeping of SELF (cinfo) is always on and the box's own arrays follow
+template <bool SELF, bool OBJ>
+struct RS4T : RS4Core<SELF> {};
+template <bool SELF>
+struct RS4T<SELF, true> : RS4Core<true> {
+  float Jo[NCP][20];   // box columns of the contact rows: [3 d + r] box dof d
+  float Cb[6][8];      // the box block of the Newton Hessian, row d = box dof d
+  float Yo[G][8];      // per robot dof lane (and lane 25, the rhs): its box-coupling row pushed through the box block's factor
+  float xr[G];         // robot part of a Newton direction, dof order
+  float zb[8];         // right-hand side of the box part
+  float opos[4], oR[12];  // box pose: origin relative to the base origin, rotation
+  float oacc[8];       // box acceleration of the integration step
+};
 // cinfo: bits 0-2 side B's chain (0 = the base body, 1 + chain otherwise), 3-5 its depth in the chain, 6-8 / 9-11 the same for side A, 12 side A is a robot geom (a
 // robot-robot contact; else the plane), 13-16 cross index + 1 (0: both sides move with the base and at most one chain), 17 dead (a cross contact above NX2: dropped)
 __device__ __forceinline__ int ci_chB(int ci) { return ci & 7; }
@@ -95,6 +117,7 @@ __device__ __forceinline__ int ci_depA(int ci) { return (ci >> 9) & 7; }
 __device__ __forceinline__ bool ci_self(int ci) { return (ci >> 12) & 1; }
 __device__ __forceinline__ int ci_x(int ci) { return (ci >> 13) & 15; }
 __device__ __forceinline__ int ci_P(int ci) { return ci_chB(ci) > 0 ? ci_chB(ci) : (ci_self(ci) ? ci_chA(ci) : 0); }                                   // primary chain (1 + id), 0 = none
+__device__ __forceinline__ bool ci_obj(int ci) { return (ci >> 18) & 1; }  // side B is the free box (OBJ): bit 18
 __device__ __forceinline__ int ci_Q(int ci) { return (ci_self(ci) && ci_chA(ci) > 0 && ci_chB(ci) > 0 && ci_chA(ci) != ci_chB(ci)) ? ci_chA(ci) : 0; }  // second chain of a cross contact
 
 // Sum over the 32 lanes (two DPP rows) of a rollout, bit-identical in every lane.  The row exchange is gfx950's v_permlane16_swap: with both
@@ -428,6 +451,12 @@ __device__ __forceinline__ void jac_mul(float* o, const float* Jc, const float* 
   for (int m = 0; m < 7; m++) { const float w = vc[m]; o[0] = fmaf(Jc[JC + 3 * m], w, o[0]); o[1] = fmaf(Jc[JC + 3 * m + 1], w, o[1]); o[2] = fmaf(Jc[JC + 3 * m + 2], w, o[2]); }
 }
 
+// the box part of a contact row (OBJ) times the box dofs of a lane-indexed vector (entries 26..31), added to o
+__device__ __forceinline__ void jac_mul_o(float* o, const float* Jo, const float* v) {
+#pragma unroll
+  for (int d = 0; d < 6; d++) { const float w = v[NVT + 1 + d]; o[0] = fmaf(Jo[3 * d], w, o[0]); o[1] = fmaf(Jo[3 * d + 1], w, o[1]); o[2] = fmaf(Jo[3 * d + 2], w, o[2]); }
+}
+
 // the second chain block of a contact between two chains (7 x 3 in RS4::J2), added to o
 __device__ __forceinline__ void jac_mul2(float* o, const float* J2x, const float* v, int csq) {
   const float* vc = v + 6 + csq;
@@ -444,11 +473,13 @@ __device__ __forceinline__ float dot_row(const float* Mrow, const float* v) {
 }
 
 
-template <bool SELF>
+template <bool SELF, bool OBJ = false>
 __global__ __launch_bounds__(WAVE, 1) void k_tree_v4(const float* __restrict__ gF, const int* __restrict__ gI, int nF, int nI, const float* state_in, int ld_in,
                                                     const float* __restrict__ ctrl, float* __restrict__ warm, int N, int substeps, float* state_out, int ld_out,
                                                     float* __restrict__ sensors_out, int ld_sens, int* __restrict__ stats, int dshift) {
-  using RS = RS4T<SELF>;
+  using RS = RS4T<SELF, OBJ>;
+  constexpr bool CI = SELF || OBJ;                          // per-contact side bookkeeping (cinfo) in shared memory
+  constexpr int NQ_ = OBJ ? NQO : NQ, NV_ = OBJ ? NVO : NVT;  // state row: qpos (robot [, box]), qvel (robot [, box])
   __shared__ RS sRS[RPW];
   __shared__ __attribute__((aligned(16))) float sF[SF_MAX];  // the model image, shared by the rollouts of the wave
   __shared__ int sI[SI_MAX];
@@ -457,6 +488,12 @@ __global__ __launch_bounds__(WAVE, 1) void k_tree_v4(const float* __restrict__ g
   for (int i = lane; i < nF && i < SF_MAX; i += WAVE) sF[i] = gF[i];  // (the sensor records at the end of the image are read from global memory, once per launch)
   for (int i = lane; i < nI && i < SI_MAX; i += WAVE) sI[i] = gI[i];
   __syncthreads();
+  if constexpr (OBJ) {  // the box's geom record goes where geom ng's would be: geom index ng names the box in the contact records (owner -3)
+    const int og = TH_F + NJ * TD_F + sI[1] * TG_F, oo = gI[9];
+    for (int i = lane; i < TG_F; i += WAVE) sF[og + i] = gF[oo + OB_G + i];
+    if (lane == 0) { sI[TH_I + NJ * TD_I + sI[1] * TG_I] = -3; sI[TH_I + NJ * TD_I + sI[1] * TG_I + 1] = 6; }
+    __syncthreads();
+  }
   // (latency mode, jh_internal.h: with dshift = 1 both rows of the wave compute the same rollout and the first writes -- the shipped 24-rollout plans)
   const int n = (blockIdx.x << (1 - dshift)) + (r >> dshift);
   const bool live = n < N && (r & ((1 << dshift) - 1)) == 0;
@@ -473,6 +510,18 @@ __global__ __launch_bounds__(WAVE, 1) void k_tree_v4(const float* __restrict__ g
   R.cid = R.cstart < 12 ? R.cstart / 3 : 4; R.clen = R.cid < 4 ? 3 : 7;
   R.bl = l < 6 ? l : (l == NVT ? 6 : -1);
   const int cstart = R.cstart, cdepth = R.cdepth;
+  const bool isobj = OBJ && l > NVT;                    // box dof lanes 26..31
+  const bool hasdofx = hasdof || isobj;
+  const int od = isobj ? l - NVT - 1 : 0;               // own box dof
+  float Mdd = 1.f, oI[3] = {0.f, 0.f, 0.f}, omass = 0.f;  // the box's (diagonal) inertia
+  int opk = -1;                                         // this lane's robot geom of the robot-box pairs
+  if constexpr (OBJ) {
+    const float* ob = gF + gI[9];
+    omass = ob[0]; oI[0] = ob[13]; oI[1] = ob[14]; oI[2] = ob[15];
+    Mdd = od < 3 ? omass : (od == 3 ? oI[0] : (od == 4 ? oI[1] : oI[2]));
+    const int* oi = gI + gI[10];
+    opk = l < oi[1] ? oi[TO_I + l] : -1;
+  }
   const int oGF = TH_F + nj * TD_F, oGI = TH_I + nj * TD_I;
   const float h = sF[TF_DT], impratio = sF[TF_IMPRATIO], tol = sF[TF_TOL], lstol = sF[TF_LSTOL]; const int cap = (int)sF[TF_MAXITER];
   const float grav[3] = {sF[TF_GRAV], sF[TF_GRAV + 1], sF[TF_GRAV + 2]};
@@ -486,12 +535,19 @@ __global__ __launch_bounds__(WAVE, 1) void k_tree_v4(const float* __restrict__ g
   const float c_flim = hasact ? jf[JF_FLIM] : 0.f, c_flo = jf[JF_FLO], c_fhi = jf[JF_FHI];
   // ---- state: replicated base + own joint
   float qb[7], vb[6], q = 0.f, qd = 0.f, qws = 0.f;
+  float qo[7] = {1.f, 0.f, 0.f, 0.f, 1.f, 0.f, 0.f}, vo[6] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f};  // free box (OBJ): replicated in every lane, as the base
   {
     const float* xi = state_in + (size_t)nc * ld_in;  // ld_in = 0: one state for every rollout
     for (int i = 0; i < 7; i++) qb[i] = xi[i];
-    for (int i = 0; i < 6; i++) vb[i] = xi[NQ + i];
-    if (isjoint) { q = xi[7 + k]; qd = xi[NQ + 6 + k]; }
-    if (hasdof && warm) qws = warm[(size_t)nc * NVT + l];
+    for (int i = 0; i < 6; i++) vb[i] = xi[NQ_ + i];
+    if (isjoint) { q = xi[7 + k]; qd = xi[NQ_ + 6 + k]; }
+    if constexpr (OBJ) {
+      for (int i = 0; i < 7; i++) qo[i] = xi[NQ + i];
+      for (int i = 0; i < 6; i++) vo[i] = xi[NQ_ + NVT + i];
+      if (hasdofx && warm) qws = warm[(size_t)nc * NV_ + (isobj ? l - 1 : l)];
+    } else {
+      if (hasdof && warm) qws = warm[(size_t)nc * NVT + l];
+    }
   }
   const float u = hasact ? ctrl[(size_t)nc * NJ + k] : 0.f;
   int n_iters = 0, n_maxed = 0;
@@ -515,6 +571,7 @@ __global__ __launch_bounds__(WAVE, 1) void k_tree_v4(const float* __restrict__ g
 #pragma unroll
       for (int i = 0; i < 6; i++) if (i == l) myqd = vb[i];
       if (hasdof) S.qd[l] = myqd;
+      if constexpr (OBJ) { float v = vo[0]; for (int i = 1; i < 6; i++) v = od == i ? vo[i] : v; if (isobj) S.qd[l] = v; }
       if (l == 0) { S.ncon = 0; S.nx2 = 0; }
     }
     __syncthreads();
@@ -549,6 +606,17 @@ __global__ __launch_bounds__(WAVE, 1) void k_tree_v4(const float* __restrict__ g
       else if (l < 6) { Sown[0] = Rb[l - 3]; Sown[1] = Rb[3 + l - 3]; Sown[2] = Rb[6 + l - 3]; }
       if (hasdof) for (int i = 0; i < 6; i++) S.Sax[l][i] = Sown[i];
       if (isbody) { for (int i = 0; i < 3; i++) S.xpos[bidx][i] = pown[i]; for (int i = 0; i < 9; i++) S.xR[bidx][i] = Rown[i]; }
+      if constexpr (OBJ) {  // the box: pose relative to the base origin; a box lane's spatial axis about the base origin (rotation about the box origin: c x axis)
+        const float no = rsqrtf(qo[3] * qo[3] + qo[4] * qo[4] + qo[5] * qo[5] + qo[6] * qo[6]);
+        qo[3] *= no; qo[4] *= no; qo[5] *= no; qo[6] *= no;
+        float Ro[9]; quat2mat(Ro, qo + 3);
+        const float c[3] = {qo[0] - qb[0], qo[1] - qb[1], qo[2] - qb[2]};
+        if (isobj) {
+          if (od < 3) { for (int i = 0; i < 6; i++) Sown[i] = 0.f; Sown[3 + od] = 1.f; }
+          else { float ax[3]; col3(ax, Ro, od - 3); float lin[3]; cross3(lin, c, ax); for (int i = 0; i < 3; i++) { Sown[i] = ax[i]; Sown[3 + i] = lin[i]; } }
+        }
+        if (l == NVT + 1) { for (int i = 0; i < 3; i++) S.opos[i] = c[i]; for (int i = 0; i < 9; i++) S.oR[i] = Ro[i]; }
+      }
     }
     PH(0)
     // ================================================================ body spatial inertia; composite inertias = suffix sums along the chains
@@ -584,6 +652,13 @@ __global__ __launch_bounds__(WAVE, 1) void k_tree_v4(const float* __restrict__ g
         float Rs[9]; for (int i = 0; i < 9; i++) Rs[i] = S.xR[b][i];
         if (kind == 0) { float w[3]; mulMV(w, Rs, o); for (int i = 0; i < 3; i++) o[i] = w[i] + S.xpos[b][i] + qb[i]; }
         else col3(o, Rs, kind - 1);
+      }
+      if constexpr (OBJ) {
+        if (owner == -3) {  // a site on the box
+          float Rs[9]; for (int i = 0; i < 9; i++) Rs[i] = S.oR[i];
+          if (kind == 0) { float w[3]; mulMV(w, Rs, o); for (int i = 0; i < 3; i++) o[i] = w[i] + qo[i]; }
+          else col3(o, Rs, kind - 1);
+        }
       }
       if (hasref) {  // position in the frame of a world-fixed reference site: R_ref' (p - p_ref)
         const float dv[3] = {o[0] - sf[3], o[1] - sf[4], o[2] - sf[5]};
@@ -691,6 +766,15 @@ __global__ __launch_bounds__(WAVE, 1) void k_tree_v4(const float* __restrict__ g
       float row[NR], xb[6];
       load_row(row, Mrow, R, k, S.vec[0], 0.f);
       a0_own = tree_cholesky_solve(row, S, R, k, xb PA_ARG);
+      if constexpr (OBJ) {  // the box: gravity on the translation, -w x I w on the body-frame rotation; its inertia block is diagonal and apart from the robot's
+        const float Iw[3] = {oI[0] * vo[3], oI[1] * vo[4], oI[2] * vo[5]};
+        float gy[3]; cross3(gy, vo + 3, Iw);
+        if (isobj) {
+          float f = omass * grav[0]; f = od == 1 ? omass * grav[1] : f; f = od == 2 ? omass * grav[2] : f;
+          f = od == 3 ? -gy[0] : f; f = od == 4 ? -gy[1] : f; f = od == 5 ? -gy[2] : f;
+          fs_own = f; Md_own = Mdd; a0_own = f / Mdd;
+        }
+      }
     }
     PH(2)
     // ================================================================ collision: every robot geom against the plane
@@ -864,6 +948,62 @@ __global__ __launch_bounds__(WAVE, 1) void k_tree_v4(const float* __restrict__ g
       }
       PH(15)
     }
+    if constexpr (OBJ) {
+      // ================================================================ the box against the plane (lane 31) and against the robot geoms (one robot-box pair per lane)
+      const float* bf = sF + oGF + ng * TG_F;
+      float bp[3], bR[9];
+      {
+        float Ro[9], c[3]; for (int i = 0; i < 9; i++) Ro[i] = S.oR[i]; for (int i = 0; i < 3; i++) c[i] = S.opos[i];
+        mulMV(bp, Ro, bf + GF4_POS); for (int i = 0; i < 3; i++) bp[i] += c[i];
+        mulMM(bR, Ro, bf + GF4_R);
+      }
+      if (l == G - 1) {  // PlaneBox: corners in MuJoCo's order, at most 4 contacts; [4] = the box (geom B = ng), the plane as geom A
+        const float pr[3] = {plp[0] - qb[0], plp[1] - qb[1], plp[2] - qb[2]};
+        const float hs[3] = {bf[GF4_SIZE], bf[GF4_SIZE + 1], bf[GF4_SIZE + 2]};
+        const float dif[3] = {bp[0] - pr[0], bp[1] - pr[1], bp[2] - pr[2]};
+        const float dist0 = dot3(dif, pln);
+        int cnt = 0;
+        for (int i = 0; i < 8; i++) {
+          const float vl[3] = {(i & 1) ? hs[0] : -hs[0], (i & 2) ? hs[1] : -hs[1], (i & 4) ? hs[2] : -hs[2]};
+          float vec3[3]; mulMV(vec3, bR, vl);
+          const float d = dist0 + dot3(pln, vec3);
+          if (d <= 0.f && cnt < 4) {
+            const int ic = atomicAdd(&S.ncon, 1);
+            if (ic >= NCP) { if (stats && live) atomicAdd(stats, 1); }
+            else {
+              float* e = S.raw[ic];
+              e[0] = bp[0] + vec3[0] - pln[0] * 0.5f * d; e[1] = bp[1] + vec3[1] - pln[1] * 0.5f * d; e[2] = bp[2] + vec3[2] - pln[2] * 0.5f * d;
+              e[3] = d; e[4] = __int_as_float(ng); e[5] = e[6] = e[7] = 0.f;
+            }
+            cnt++;
+          }
+        }
+      }
+      struct ObjSink {
+        RS* S; int* stats; int pk; bool flip;
+        __device__ __forceinline__ void push(const float* pos, const float* n, float dist) {
+          const int i = atomicAdd(&S->ncon, 1);
+          if (i >= NCP) { if (stats) atomicAdd(stats, 1); return; }
+          float* e = S->raw[i];
+          e[0] = pos[0]; e[1] = pos[1]; e[2] = pos[2]; e[3] = dist; e[4] = __int_as_float((pk >> 8) | (((pk & 255) + 1) << 8));
+          e[5] = flip ? -n[0] : n[0]; e[6] = flip ? -n[1] : n[1]; e[7] = flip ? -n[2] : n[2];
+        }
+      };
+      if (opk >= 0) {  // robot geom opk (geom 1) against the box (geom 2): the normal points from the robot geom to the box, as the oracle orders these pairs
+        const int g = opk;
+        const float* gf = sF + oGF + g * TG_F; const int owner = sI[oGI + g * TG_I], gt = sI[oGI + g * TG_I + 1]; const int gb = owner < 0 ? 0 : 1 + owner;
+        float gp[3], gR[9], xR[9]; for (int i = 0; i < 9; i++) xR[i] = S.xR[gb][i];
+        mulMV(gp, xR, gf + GF4_POS); for (int i = 0; i < 3; i++) gp[i] += S.xpos[gb][i];
+        mulMM(gR, xR, gf + GF4_R);
+        const float d[3] = {bp[0] - gp[0], bp[1] - gp[1], bp[2] - gp[2]}, rs = gf[GF4_RBOUND] + bf[GF4_RBOUND];
+        if (dot3(d, d) <= rs * rs) {  // (mj_collideGeoms' bounding-sphere filter)
+          ObjSink sk{&S, live ? stats : nullptr, g | (ng << 8), false};
+          if (gt == 6) collide_box_box(sk, gp, gR, gf + GF4_SIZE, bp, bR, bf + GF4_SIZE);
+          else if (gt == 2) { sk.flip = true; collide_box_sphere(sk, bp, bR, bf + GF4_SIZE, gp, gf[GF4_SIZE]); }
+          else { sk.flip = true; collide_box_capsule(sk, bp, bR, bf + GF4_SIZE, gp, gR, gf[GF4_SIZE], gf[GF4_SIZE + 1]); }
+        }
+      }
+    }
     __syncthreads();
     // ================================================================ constraint rows
     const int ncon = S.ncon < NCP ? S.ncon : NCP;
@@ -881,12 +1021,13 @@ __global__ __launch_bounds__(WAVE, 1) void k_tree_v4(const float* __restrict__ g
           if (owner < 0) { ch = 0; dep = 0; } else { const int cs_ = sI[TH_I + owner * TD_I + 1]; ch = 1 + (cs_ < 12 ? cs_ / 3 : 4); dep = sI[TH_I + owner * TD_I + 2]; }
         };
         int chB, depB, chA = 0, depA = 0; side(gB, chB, depB);
-        const bool selfc = SELF && gA1 != 0;
+        const bool selfc = CI && gA1 != 0;
         if (selfc) side(gA1 - 1, chA, depA);
         my_ci = chB | (depB << 3) | (chA << 6) | (depA << 9) | ((selfc ? 1 : 0) << 12);
+        if (OBJ && gB == ng) my_ci |= 1 << 18;  // side B is the box
         cross = ci_Q(my_ci) != 0;
       }
-      if constexpr (SELF) {
+      if constexpr (CI) {
         const unsigned xm = (unsigned)(__ballot(cross) >> (32 * r));
         if (cross) {
           const int x = __popc(xm & ((1u << l) - 1u));
@@ -904,9 +1045,9 @@ __global__ __launch_bounds__(WAVE, 1) void k_tree_v4(const float* __restrict__ g
     if (l < ncon) {  // contact frame.  Plane contacts: plane normal (from the plane, geom 1, to the robot geom), second axis along a capsule's axis; robot-robot: the narrow phase's normal
       const float* e = S.raw[l];
       float fr[9] = {pln[0], pln[1], pln[2], 0, 0, 0, 0, 0, 0};
-      if (SELF && ci_self(my_ci)) { fr[0] = e[5]; fr[1] = e[6]; fr[2] = e[7]; }
+      if (CI && ci_self(my_ci)) { fr[0] = e[5]; fr[1] = e[6]; fr[2] = e[7]; }
       make_frame(fr);
-      if (!(SELF && ci_self(my_ci))) {
+      if (!(CI && ci_self(my_ci))) {
         float y[3] = {e[5], e[6], e[7]};
         const float dp = dot3(fr, y); y[0] -= fr[0] * dp; y[1] -= fr[1] * dp; y[2] -= fr[2] * dp;
         const float nn = sqrtf(dot3(y, y));
@@ -919,7 +1060,7 @@ __global__ __launch_bounds__(WAVE, 1) void k_tree_v4(const float* __restrict__ g
     for (int c = 0; c < ncon; c++) {  // Jacobian: every dof lane its own column, side B minus side A (the plane is static); the spare lanes clear the padding
       const float* e = S.raw[c];
       int ci;
-      if constexpr (SELF) ci = S.cinfo[c];
+      if constexpr (CI) ci = S.cinfo[c];
       else { const int owner = sI[oGI + (__float_as_int(e[4]) & 255) * TG_I]; ci = owner < 0 ? 0 : ((1 + (sI[TH_I + owner * TD_I + 1] < 12 ? sI[TH_I + owner * TD_I + 1] / 3 : 4)) | (sI[TH_I + owner * TD_I + 2] << 3)); }
       const int P = ci_P(ci), Q = SELF ? ci_Q(ci) : 0, xq = ci_x(ci) > 0 ? ci_x(ci) - 1 : 0;
       const bool dead = SELF && ((ci >> 17) & 1);
@@ -931,6 +1072,7 @@ __global__ __launch_bounds__(WAVE, 1) void k_tree_v4(const float* __restrict__ g
           if (ci_chB(ci) == 1 + R.cid && cdepth <= ci_depB(ci)) sgn += 1.f;
           if (ci_self(ci) && ci_chA(ci) == 1 + R.cid && cdepth <= ci_depA(ci)) sgn -= 1.f;
         }
+        if (OBJ && isbase && ci_obj(ci)) sgn = ci_self(ci) ? -1.f : 0.f;  // box against a robot geom: the base carries side A; box against the plane: the base is not involved
         const float pos[3] = {e[0], e[1], e[2]};
         float v[3]; cross3(v, Sown, pos); for (int i = 0; i < 3; i++) v[i] += Sown[3 + i];
         const float* fr = S.fW[c];
@@ -942,6 +1084,16 @@ __global__ __launch_bounds__(WAVE, 1) void k_tree_v4(const float* __restrict__ g
         if (m >= len) { float* o = S.J[c] + JC + 3 * m; o[0] = o[1] = o[2] = 0.f; }
         if (SELF && Q != 0 && !dead && m >= (Q < 5 ? 3 : 7)) { float* o = S.J2[xq] + 3 * m; o[0] = o[1] = o[2] = 0.f; }
       }
+      if constexpr (OBJ) {  // the box columns: side B when the contact names the box, else zero
+        if (isobj) {
+          const float sgn = ci_obj(ci) ? 1.f : 0.f;
+          const float pos[3] = {e[0], e[1], e[2]};
+          float v[3]; cross3(v, Sown, pos); for (int i = 0; i < 3; i++) v[i] += Sown[3 + i];
+          const float* fr = S.fW[c];
+          float* o = S.Jo[c] + 3 * od;
+          o[0] = sgn * dot3(fr, v); o[1] = sgn * dot3(fr + 3, v); o[2] = sgn * dot3(fr + 6, v);
+        }
+      }
     }
     __syncthreads();
     if (sl.valid) {
@@ -949,7 +1101,7 @@ __global__ __launch_bounds__(WAVE, 1) void k_tree_v4(const float* __restrict__ g
       const float* gf = sF + oGF + gid * TG_F;
       float si[5]; for (int w = 0; w < 5; w++) si[w] = gf[GF4_SOLIMP + w];
       float mu = gf[GF4_MU], tran = gf[GF4_TRAN];
-      if (SELF && ci_self(my_ci)) {  // robot against robot: mj_contactParam with equal priorities -- the larger friction; the two bodies' inverse weights
+      if (CI && ci_self(my_ci)) {  // robot against robot (or against the box): mj_contactParam with equal priorities -- the larger friction; the two bodies' inverse weights
         const float* ga = sF + oGF + (((__float_as_int(e[4]) >> 8) & 255) - 1) * TG_F;
         mu = fmaxf(gf[GF4_MUOWN], ga[GF4_MUOWN]); tran = gf[GF4_TRAN] + ga[GF4_TRAN];
       }
@@ -960,6 +1112,7 @@ __global__ __launch_bounds__(WAVE, 1) void k_tree_v4(const float* __restrict__ g
       float vel[3];
       jac_mul(vel, S.J[l], S.qd, my_cs);
       if (SELF && my_Q != 0) jac_mul2(vel, S.J2[my_x], S.qd, my_csq);
+      if constexpr (OBJ) jac_mul_o(vel, S.Jo[l], S.qd);
       sl.aref[0] = -gf[GF4_B] * vel[0] - gf[GF4_K] * imp * dist; sl.aref[1] = -gf[GF4_B] * vel[1]; sl.aref[2] = -gf[GF4_B] * vel[2];
     }
     DofRows4 dr;
@@ -975,33 +1128,42 @@ __global__ __launch_bounds__(WAVE, 1) void k_tree_v4(const float* __restrict__ g
     // ================================================================ Newton solver (tree-structured Hessian, one row per lane)
     float a_own = a0_own;
     unsigned involved = 0;  // bit c: contact c moves with this lane's dof (base lanes: every contact; joint lanes: contacts on their chain)
+    if constexpr (OBJ) { if (isobj) for (int c = 0; c < ncon; c++) involved |= ci_obj(S.cinfo[c]) ? (1u << c) : 0u; }
     if (hasdof) for (int c = 0; c < ncon; c++) {
       int P;
-      if constexpr (SELF) P = ci_P(S.cinfo[c]);
+      if constexpr (CI) P = ci_P(S.cinfo[c]);
       else { const int owner = sI[oGI + (__float_as_int(S.raw[c][4]) & 255) * TG_I]; P = owner < 0 ? 0 : 1 + (sI[TH_I + owner * TD_I + 1] < 12 ? sI[TH_I + owner * TD_I + 1] / 3 : 4); }
       involved |= (isbase || P == 1 + R.cid) ? (1u << c) : 0u;
     }
     // contacts between two chains (SELF): which of them have this lane's chain as their second chain, and the wave-uniform question whether a rollout has any
     unsigned involved2 = 0;
     if constexpr (SELF) { if (isjoint) for (int x = 0; x < nx2; x++) involved2 |= ci_Q(S.cinfo[S.xc[x]]) == 1 + R.cid ? (1u << x) : 0u; }
-    const bool dense_step = SELF && __any(nx2 > 0);
+    bool two_chains = false;  // OBJ: the box touches two different chains in this step -- the Schur complement couples them, no tree structure
+    if constexpr (OBJ) {
+      unsigned chm = 0;
+      for (int c = 0; c < ncon; c++) { const int ci = S.cinfo[c]; chm |= (ci_obj(ci) && ci_self(ci) && ci_P(ci) > 0) ? (1u << ci_P(ci)) : 0u; }
+      two_chains = __popc(chm) > 1;
+    }
+    const bool dense_step = (SELF && __any(nx2 > 0)) || (OBJ && __any(two_chains));
     const int cd3 = 3 * (cdepth < 0 ? 0 : cdepth);
     const int own_col = isbase ? 3 * l : JC + 3 * (cdepth < 0 ? 0 : cdepth);  // own column in a compact Jacobian row
+    const int own_o = 3 * od;                                                   // a box lane's own column in the box part of a row
     const float iMd = 1.f / Md_own;
-    const float snorm = gsum32(hasdof ? fs_own * fs_own * iMd : 0.f);
+    const float snorm = gsum32(hasdofx ? fs_own * fs_own * iMd : 0.f);
     int iters_this = 0;
     {
       // ---- warm start: the better of last step's acceleration and the unconstrained one
-      if (hasdof) { S.vec[0][l] = qws; S.vec[1][l] = a0_own; S.vec[2][l] = qws - a0_own; }
+      if (hasdofx) { S.vec[0][l] = qws; S.vec[1][l] = a0_own; S.vec[2][l] = qws - a0_own; }
       __syncthreads();
       float jar_ws[3] = {0.f, 0.f, 0.f};
-      if (sl.valid) { float o[3]; jac_mul(o, S.J[l], S.vec[0], my_cs); if (SELF && my_Q != 0) jac_mul2(o, S.J2[my_x], S.vec[0], my_csq); for (int w = 0; w < 3; w++) sl.jar[w] = o[w] - sl.aref[w]; }
+      if (sl.valid) { float o[3]; jac_mul(o, S.J[l], S.vec[0], my_cs); if (SELF && my_Q != 0) jac_mul2(o, S.J2[my_x], S.vec[0], my_csq); if constexpr (OBJ) jac_mul_o(o, S.Jo[l], S.vec[0]); for (int w = 0; w < 3; w++) sl.jar[w] = o[w] - sl.aref[w]; }
       dr.jf = qws - dr.faref; dr.jl = dr.lims * qws - dr.laref;
-      const float mdw = dot_row(Mrow, S.vec[2]);
-      const float cost_ws = gsum32(lane_cost4(sl, dr) + (hasdof ? 0.5f * (qws - a0_own) * mdw : 0.f));
+      float mdw = dot_row(Mrow, S.vec[2]);
+      if constexpr (OBJ) mdw = isobj ? Mdd * S.vec[2][l] : mdw;
+      const float cost_ws = gsum32(lane_cost4(sl, dr) + (hasdofx ? 0.5f * (qws - a0_own) * mdw : 0.f));
       for (int w = 0; w < 3; w++) jar_ws[w] = sl.jar[w];
       const float jf_ws = dr.jf, jl_ws = dr.jl;
-      if (sl.valid) { float o[3]; jac_mul(o, S.J[l], S.vec[1], my_cs); if (SELF && my_Q != 0) jac_mul2(o, S.J2[my_x], S.vec[1], my_csq); for (int w = 0; w < 3; w++) sl.jar[w] = o[w] - sl.aref[w]; }
+      if (sl.valid) { float o[3]; jac_mul(o, S.J[l], S.vec[1], my_cs); if (SELF && my_Q != 0) jac_mul2(o, S.J2[my_x], S.vec[1], my_csq); if constexpr (OBJ) jac_mul_o(o, S.Jo[l], S.vec[1]); for (int w = 0; w < 3; w++) sl.jar[w] = o[w] - sl.aref[w]; }
       dr.jf = a0_own - dr.faref; dr.jl = dr.lims * a0_own - dr.laref;
       const float cost_0 = gsum32(lane_cost4(sl, dr));
       if (cost_ws < cost_0) { a_own = qws; for (int w = 0; w < 3; w++) sl.jar[w] = jar_ws[w]; dr.jf = jf_ws; dr.jl = jl_ws; }
@@ -1012,7 +1174,7 @@ __global__ __launch_bounds__(WAVE, 1) void k_tree_v4(const float* __restrict__ g
         PH(4)
         // ---- (1) gradient row
         const float da_own = a_own - a0_own;
-        if (hasdof) S.vec[0][l] = da_own;
+        if (hasdofx) S.vec[0][l] = da_own;
         if (l < ncon) {  // (a dropped contact -- above the capacity for contacts between two chains -- keeps its row with zero force and weight)
           float f[3] = {0.f, 0.f, 0.f}, Wm[6] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
           if (sl.valid) pyramid_eval(sl.jar, sl.D, sl.mu, f, Wm);
@@ -1020,6 +1182,7 @@ __global__ __launch_bounds__(WAVE, 1) void k_tree_v4(const float* __restrict__ g
         }
         __syncthreads();
         float g_own = dot_row(Mrow, S.vec[0]), hd = 0.f;
+        if constexpr (OBJ) g_own = isobj ? Mdd * S.vec[0][l] : g_own;
         if (dr.fl > 0.f) {
           const float x = dr.jf, fl = dr.fl, lim = dr.fR * fl;
           if (x <= -lim) g_own -= fl; else if (x >= lim) g_own += fl; else { g_own += dr.fD * x; hd += dr.fD; }
@@ -1027,6 +1190,7 @@ __global__ __launch_bounds__(WAVE, 1) void k_tree_v4(const float* __restrict__ g
         if (dr.lims != 0.f && dr.jl < 0.f) { g_own += dr.lims * dr.lD * dr.jl; hd += dr.lD; }
         for (int c = 0; c < ncon; c++) {  // branch-free: a lane the contact does not move reads some other column and multiplies it by zero
           const float* jc = S.J[c] + own_col; const float* fc = S.fW[c];
+          if constexpr (OBJ) jc = isobj ? S.Jo[c] + own_o : jc;
           const float on = (involved >> c) & 1u ? 1.f : 0.f;
           g_own -= on * (jc[0] * fc[0] + jc[1] * fc[1] + jc[2] * fc[2]);
         }
@@ -1038,28 +1202,40 @@ __global__ __launch_bounds__(WAVE, 1) void k_tree_v4(const float* __restrict__ g
           }
         }
         // ---- (2) convergence; leave before any Hessian work once both rollouts of the wave are done
-        const float gn = gsum32(hasdof ? g_own * g_own * iMd : 0.f);
+        const float gn = gsum32(hasdofx ? g_own * g_own * iMd : 0.f);
         if (act && gn <= tol * tol * fmaxf(snorm, 1e-12f)) act = false;
         if (!__any(act)) break;
         if (act) iters_this++;
         PH(5)
         // ---- (3) Hessian row in the factorisation layout; the rhs lane takes -g
-        if (hasdof) S.vec[1][l] = -g_own;
+        if (hasdofx) S.vec[1][l] = -g_own;
         __syncthreads();
         float row[NR];
         load_row(row, Mrow, R, k, S.vec[1], hd);
+        float rowo[6] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f};  // OBJ: the row's box columns (robot lanes: the coupling; box lanes: the box block; lane 25: the rhs's box part)
+        if constexpr (OBJ) {
+#pragma unroll
+          for (int d = 0; d < 6; d++) rowo[d] = R.bl == 6 ? S.vec[1][NVT + 1 + d] : ((isobj && od == d) ? Mdd + hd : 0.f);
+        }
         for (int c = 0; c < ncon; c++) {  // branch-free accumulation of J' W J: the row of the compact Jacobian is the same for every lane
           const float* fc = S.fW[c]; const float* Jc = S.J[c];
           const float on = (involved >> c) & 1u ? 1.f : 0.f;
-          const float j0 = on * Jc[own_col], j1 = on * Jc[own_col + 1], j2 = on * Jc[own_col + 2];
+          float j0, j1, j2;
+          if constexpr (OBJ) { const float* jown = isobj ? S.Jo[c] + own_o : Jc + own_col; j0 = on * jown[0]; j1 = on * jown[1]; j2 = on * jown[2]; }
+          else { j0 = on * Jc[own_col]; j1 = on * Jc[own_col + 1]; j2 = on * Jc[own_col + 2]; }
           const float G0 = fc[4] * j0 + fc[5] * j1 + fc[7] * j2, G1 = fc[5] * j0 + fc[6] * j1 + fc[8] * j2, G2 = fc[7] * j0 + fc[8] * j1 + fc[9] * j2;
           float dch[7], dba[6];
 #pragma unroll
           for (int m = 0; m < 7; m++) dch[m] = Jc[JC + 3 * m] * G0 + Jc[JC + 3 * m + 1] * G1 + Jc[JC + 3 * m + 2] * G2;
 #pragma unroll
           for (int m = 0; m < 6; m++) dba[m] = Jc[3 * m] * G0 + Jc[3 * m + 1] * G1 + Jc[3 * m + 2] * G2;
+          if constexpr (OBJ) {
+            const float* Jo = S.Jo[c];
+#pragma unroll
+            for (int d = 0; d < 6; d++) rowo[d] += Jo[3 * d] * G0 + Jo[3 * d + 1] * G1 + Jo[3 * d + 2] * G2;
+          }
           int och;  // 0: both sides sit on the base (the chain part is zero), else 1 + the contact's (primary) chain
-          if constexpr (SELF) och = ci_P(S.cinfo[c]);
+          if constexpr (CI) och = ci_P(S.cinfo[c]);
           else { const int owner = sI[oGI + (__float_as_int(S.raw[c][4]) & 255) * TG_I]; och = owner < 0 ? 0 : 1 + (sI[TH_I + owner * TD_I + 1] < 12 ? sI[TH_I + owner * TD_I + 1] / 3 : 4); }
 #pragma unroll
           for (int ch = 0; ch < NCH; ch++) {
@@ -1098,15 +1274,85 @@ __global__ __launch_bounds__(WAVE, 1) void k_tree_v4(const float* __restrict__ g
         // ---- (4) factorise and solve; the direction goes back through LDS
         float xb[6];
         // (a rollout with a contact between two chains has no tree-structured Hessian: the wave then factorises densely -- valid for its other rollout too)
-        const float p_own = dense_step ? dense_cholesky_solve(row, S, R, k, xb) : tree_cholesky_solve(row, S, R, k, xb PA_ARG);
-        if (hasdof) S.vec[2][l] = p_own;
+        float p_own;
+        if constexpr (OBJ) {
+          // eliminate the box block C first: y_i = L_C^-1 B_i for every robot row i and the rhs, then row_i -= y_i . y_j over the 25 robot columns (the robot system's Schur
+          // complement; only the base and the chains the box touches change), solve the robot system, and C x_box = r_box - B' x_robot
+          if (isobj) {
+#pragma unroll
+            for (int d = 0; d < 6; d++) S.Cb[od][d] = rowo[d];
+          }
+          __syncthreads();
+          {
+            float Lc[21];
+#pragma unroll
+            for (int pp = 0; pp < 6; pp++) {
+#pragma unroll
+              for (int m = 0; m <= pp; m++) Lc[tri4(pp, m)] = S.Cb[pp][m];
+            }
+            chol_packed<6>(Lc);
+            fwd_packed<6>(rowo, Lc);
+          }
+          if (hasdof || R.bl == 6) {
+            float4* o = reinterpret_cast<float4*>(S.Yo[l]);
+            o[0] = make_float4(rowo[0], rowo[1], rowo[2], rowo[3]); o[1] = make_float4(rowo[4], rowo[5], 0.f, 0.f);
+          }
+          __syncthreads();
+          if (hasdof || R.bl == 6) {
+#pragma unroll
+            for (int j = 0; j < NVT; j++) {
+              const float* yj = S.Yo[j < NJ ? 6 + j : j - NJ];
+              float d = 0.f;
+#pragma unroll
+              for (int e = 0; e < 6; e++) d = fmaf(rowo[e], yj[e], d);
+              row[j] -= d;
+            }
+          }
+          p_own = dense_step ? dense_cholesky_solve(row, S, R, k, xb) : tree_cholesky_solve(row, S, R, k, xb PA_ARG);
+          if (hasdof) S.xr[l] = p_own;
+          __syncthreads();
+          if (isobj) {
+            float z = -g_own;
+#pragma unroll
+            for (int j = 0; j < NVT; j++) z = fmaf(-row[j], S.xr[j < NJ ? 6 + j : j - NJ], z);
+            S.zb[od] = z;
+          }
+          __syncthreads();
+          if (isobj) {
+            float Lc[21], zz[6];
+#pragma unroll
+            for (int pp = 0; pp < 6; pp++) {
+#pragma unroll
+              for (int m = 0; m <= pp; m++) Lc[tri4(pp, m)] = S.Cb[pp][m];
+              zz[pp] = S.zb[pp];
+            }
+            chol_packed<6>(Lc);
+            fwd_packed<6>(zz, Lc);
+            float xo[6];
+#pragma unroll
+            for (int m = 5; m >= 0; m--) {
+              float sx = zz[m];
+#pragma unroll
+              for (int q2 = m + 1; q2 < 6; q2++) sx -= Lc[tri4(q2, m)] * xo[q2];
+              xo[m] = sx * Lc[tri4(m, m)];
+            }
+            float v = xo[0];
+#pragma unroll
+            for (int d = 1; d < 6; d++) v = od == d ? xo[d] : v;
+            p_own = v;
+          }
+        } else {
+          p_own = dense_step ? dense_cholesky_solve(row, S, R, k, xb) : tree_cholesky_solve(row, S, R, k, xb PA_ARG);
+        }
+        if (hasdofx) S.vec[2][l] = p_own;
         __syncthreads();
         PH(7)
         // ---- (5) exact line search
-        const float Mp_own = dot_row(Mrow, S.vec[2]);
-        const float pMp = gsum32(hasdof ? p_own * Mp_own : 0.f), pMd = gsum32(hasdof ? Mp_own * da_own : 0.f), gp = gsum32(hasdof ? g_own * p_own : 0.f);
+        float Mp_own = dot_row(Mrow, S.vec[2]);
+        if constexpr (OBJ) Mp_own = isobj ? Mdd * p_own : Mp_own;
+        const float pMp = gsum32(hasdofx ? p_own * Mp_own : 0.f), pMd = gsum32(hasdofx ? Mp_own * da_own : 0.f), gp = gsum32(hasdofx ? g_own * p_own : 0.f);
         if (act && !(gp < 0.f)) act = false;
-        if (sl.valid) { jac_mul(sl.jp, S.J[l], S.vec[2], my_cs); if (SELF && my_Q != 0) jac_mul2(sl.jp, S.J2[my_x], S.vec[2], my_csq); }
+        if (sl.valid) { jac_mul(sl.jp, S.J[l], S.vec[2], my_cs); if (SELF && my_Q != 0) jac_mul2(sl.jp, S.J2[my_x], S.vec[2], my_csq); if constexpr (OBJ) jac_mul_o(sl.jp, S.Jo[l], S.vec[2]); }
         dr.pf = p_own; dr.pl = dr.lims * p_own;
         float lo = 0.f, hi = -1.f, alpha = 1.f; bool lsact = act;
         for (int ls = 0; ls < 12 && __any(lsact); ls++) {
@@ -1147,6 +1393,7 @@ __global__ __launch_bounds__(WAVE, 1) void k_tree_v4(const float* __restrict__ g
       __syncthreads();
       float row[NR], x[6];
       load_row(row, Mrow, R, k, S.vec[1], h * (c_damp + kv_eff));
+      if constexpr (OBJ) { if (isobj) S.oacc[od] = (fs_own + Mdd * da_own) / Mdd; }  // the box: no damping, no servo -- its own diagonal block (read after the solve's barriers)
       const float qacc = tree_cholesky_solve(row, S, R, k, x PA_ARG);
       if (isjoint) { qd = fmaf(h, qacc, qd); q = fmaf(h, qd, q); }
       qws = a_own;
@@ -1164,6 +1411,22 @@ __global__ __launch_bounds__(WAVE, 1) void k_tree_v4(const float* __restrict__ g
       }
       const float nn = rsqrtf(qb[3] * qb[3] + qb[4] * qb[4] + qb[5] * qb[5] + qb[6] * qb[6]);
       qb[3] *= nn; qb[4] *= nn; qb[5] *= nn; qb[6] *= nn;
+      if constexpr (OBJ) {  // the free box, as the base: world-frame translation, body-frame rotation (mju_quatIntegrate)
+        for (int i = 0; i < 6; i++) vo[i] = fmaf(h, S.oacc[i], vo[i]);
+        for (int i = 0; i < 3; i++) qo[i] = fmaf(h, vo[i], qo[i]);
+        const float won = sqrtf(vo[3] * vo[3] + vo[4] * vo[4] + vo[5] * vo[5]), oang = won * h;
+        if (oang > 0.f) {
+          float sn, cs; sincosf(0.5f * oang, &sn, &cs); const float kk = sn / won;
+          float dq[4] = {cs, vo[3] * kk, vo[4] * kk, vo[5] * kk}, *qq = qo + 3;
+          const float r0 = qq[0] * dq[0] - qq[1] * dq[1] - qq[2] * dq[2] - qq[3] * dq[3];
+          const float r1 = qq[0] * dq[1] + qq[1] * dq[0] + qq[2] * dq[3] - qq[3] * dq[2];
+          const float r2 = qq[0] * dq[2] - qq[1] * dq[3] + qq[2] * dq[0] + qq[3] * dq[1];
+          const float r3 = qq[0] * dq[3] + qq[1] * dq[2] - qq[2] * dq[1] + qq[3] * dq[0];
+          qq[0] = r0; qq[1] = r1; qq[2] = r2; qq[3] = r3;
+        }
+        const float no = rsqrtf(qo[3] * qo[3] + qo[4] * qo[4] + qo[5] * qo[5] + qo[6] * qo[6]);
+        qo[3] *= no; qo[4] *= no; qo[5] *= no; qo[6] *= no;
+      }
     }
     __syncthreads();
     PH(9)
@@ -1171,17 +1434,44 @@ __global__ __launch_bounds__(WAVE, 1) void k_tree_v4(const float* __restrict__ g
   PH_FLUSH
   if (live) {
     float* o = state_out + (size_t)n * ld_out;
-    if (isjoint) { o[7 + k] = q; o[NQ + 6 + k] = qd; }
+    if (isjoint) { o[7 + k] = q; o[NQ_ + 6 + k] = qd; }
     if (l < 7) o[l] = qb[l];
-    if (l < 6) o[NQ + l] = vb[l];
-    if (hasdof && warm) warm[(size_t)n * NVT + l] = qws;
+    if (l < 6) o[NQ_ + l] = vb[l];
+    if constexpr (OBJ) {
+      float v = qo[0];
+      for (int i = 1; i < 7; i++) v = (l - NVT) == i ? qo[i] : v;
+      if (l >= NVT) o[NQ + l - NVT] = v;                     // lanes 25..31: the box's qpos
+      float w = vo[0];
+      for (int i = 1; i < 6; i++) w = od == i ? vo[i] : w;
+      if (isobj) o[NQ_ + NVT + od] = w;                      // lanes 26..31: the box's qvel
+      if (hasdofx && warm) warm[(size_t)n * NV_ + (isobj ? l - 1 : l)] = qws;
+    } else {
+      if (hasdof && warm) warm[(size_t)n * NVT + l] = qws;
+    }
     if (stats && l == 0) { if (n_maxed) atomicAdd(stats + 1, n_maxed); atomicAdd(stats + 2, n_iters); atomicAdd(stats + 3, substeps); }
   }
 }
 
 }  // namespace
 
-struct jh_tree { float* d_f; int* d_i; int* d_stats; int nj, ng, nq, nv, nf, ni, ns, npair, self_collision; std::vector<hipEvent_t> events; };
+struct jh_tree { float* d_f; int* d_i; int* d_stats; int nj, ng, nq, nv, nf, ni, ns, npair, self_collision, nobj; std::vector<hipEvent_t> events; };
+
+namespace {
+// the instantiation for the image (a free box or not) and the self-collision switch; states rows of nq + nv floats
+void launch_tree(const jh_tree* t, hipStream_t st, const float* xin, int ld_in, const float* ctrl, float* warm, int N, int substeps, float* xout, int ld_out, float* sens, int ld_sens) {
+  const int dshift = jh_latency_shift(N, RPW), per_wave = RPW >> dshift;
+  const dim3 grid((N + per_wave - 1) / per_wave), block(WAVE);
+  if (t->nobj) {
+    if (t->self_collision)
+      hipLaunchKernelGGL((k_tree_v4<true, true>), grid, block, 0, st, t->d_f, t->d_i, t->nf, t->ni, xin, ld_in, ctrl, warm, N, substeps, xout, ld_out, sens, ld_sens, t->d_stats, dshift);
+    else
+      hipLaunchKernelGGL((k_tree_v4<false, true>), grid, block, 0, st, t->d_f, t->d_i, t->nf, t->ni, xin, ld_in, ctrl, warm, N, substeps, xout, ld_out, sens, ld_sens, t->d_stats, dshift);
+  } else if (t->self_collision)
+    hipLaunchKernelGGL(k_tree_v4<true>, grid, block, 0, st, t->d_f, t->d_i, t->nf, t->ni, xin, ld_in, ctrl, warm, N, substeps, xout, ld_out, sens, ld_sens, t->d_stats, dshift);
+  else
+    hipLaunchKernelGGL(k_tree_v4<false>, grid, block, 0, st, t->d_f, t->d_i, t->nf, t->ni, xin, ld_in, ctrl, warm, N, substeps, xout, ld_out, sens, ld_sens, t->d_stats, dshift);
+}
+}  // namespace
 
 extern "C" int jh_tree_create(const void* blob, size_t nbytes, jh_tree** out) {
   JH_REQUIRE(blob && out && nbytes >= 16, "tree_create: null or short blob");
@@ -1190,12 +1480,26 @@ extern "C" int jh_tree_create(const void* blob, size_t nbytes, jh_tree** out) {
   const size_t nf = hd[1], ni = hd[2];
   JH_REQUIRE(nbytes == 16 + 4 * (nf + ni), "tree_create: blob size mismatch");
   const float* f = (const float*)(hd + 4); const int* ii = (const int*)(f + nf);
-  JH_REQUIRE(ii[0] == NJ && ii[2] == NQ && ii[3] == NVT && ii[1] <= G - 1, "tree_create: the kernel is instantiated for a free base + 19 hinges (got %d joints, nq %d, nv %d, %d geoms)", ii[0], ii[2], ii[3], ii[1]);
-  JH_REQUIRE((size_t)(TH_F + ii[0] * TD_F + ii[1] * TG_F) <= (size_t)SF_MAX && (size_t)(TH_I + ii[0] * TD_I + ii[1] * TG_I) <= (size_t)SI_MAX,
+  const int nobj = ii[8];
+  JH_REQUIRE(nobj == 0 || nobj == 1, "tree_create: the kernel carries at most one free object besides the robot (the image has %d)", nobj);
+  JH_REQUIRE(ii[0] == NJ && ii[2] == (nobj ? NQO : NQ) && ii[3] == (nobj ? NVO : NVT) && ii[1] <= G - 1 - nobj,
+             "tree_create: the kernel is instantiated for a free base + 19 hinges [+ one free box] (got %d joints, nq %d, nv %d, %d geoms, %d objects)", ii[0], ii[2], ii[3], ii[1], nobj);
+  JH_REQUIRE((size_t)(TH_F + ii[0] * TD_F + (ii[1] + nobj) * TG_F) <= (size_t)SF_MAX && (size_t)(TH_I + ii[0] * TD_I + (ii[1] + nobj) * TG_I) <= (size_t)SI_MAX,
              "tree_create: model image too large for the kernel's LDS copy");
-  JH_REQUIRE(ii[4] >= 0 && ii[4] <= G && ii[6] >= 0 && nf == (size_t)(TH_F + ii[0] * TD_F + ii[1] * TG_F + ii[4] * TS_F) &&
-             ni == (size_t)(TH_I + ii[0] * TD_I + ii[1] * TG_I + ii[4] * TS_I + ii[6]) && (ii[6] == 0 || ii[7] == TH_I + ii[0] * TD_I + ii[1] * TG_I + ii[4] * TS_I),
+  const size_t nf0 = (size_t)(TH_F + ii[0] * TD_F + ii[1] * TG_F + ii[4] * TS_F), ni0 = (size_t)(TH_I + ii[0] * TD_I + ii[1] * TG_I + ii[4] * TS_I + ii[6]);
+  JH_REQUIRE(ii[4] >= 0 && ii[4] <= G && ii[6] >= 0 && nf == nf0 + (nobj ? TO_F : 0) && ni >= ni0 + (nobj ? TO_I : 0) && (nobj || ni == ni0) &&
+             (ii[6] == 0 || ii[7] == TH_I + ii[0] * TD_I + ii[1] * TG_I + ii[4] * TS_I),
              "tree_create: image sizes do not match the counts in its header (or more than 32 sensors)");
+  if (nobj) {  // the object section (judo_amd/tree_model.py): where the header says, one box geom, inertia at the body origin along its frame, robot-box pairs
+    JH_REQUIRE((size_t)ii[9] == nf0 && (size_t)ii[10] == ni0 && ni == ni0 + TO_I + (size_t)ii[ni0 + 1], "tree_create: object section not where the header puts it");
+    const float* of = f + nf0; const int* oi = ii + ni0;
+    JH_REQUIRE(oi[0] == 6, "tree_create: the free object must collide through one box geom (got geom type %d)", oi[0]);
+    JH_REQUIRE(of[1] == 0.f && of[2] == 0.f && of[3] == 0.f && of[4] == 1.f && of[5] == 0.f && of[6] == 0.f && of[7] == 0.f && of[8] == 1.f && of[9] == 0.f && of[10] == 0.f &&
+               of[11] == 0.f && of[12] == 1.f && of[0] > 0.f && of[13] > 0.f && of[14] > 0.f && of[15] > 0.f,
+               "tree_create: the free object needs a positive mass and inertia, its centre of mass at its origin and its principal axes along its frame");
+    JH_REQUIRE(oi[1] >= 0 && oi[1] <= G, "tree_create: %d robot-box pairs, the kernel holds %d", oi[1], G);
+    for (int p = 0; p < oi[1]; p++) JH_REQUIRE(oi[TO_I + p] >= 0 && oi[TO_I + p] < ii[1], "tree_create: bad robot-box pair %d (geom %d)", p, oi[TO_I + p]);
+  }
   JH_REQUIRE(ii[6] <= MAXPP * G, "tree_create: %d robot-robot geom pairs, the kernel holds %d", ii[6], MAXPP * G);
   for (int p = 0; p < ii[6]; p++) {  // robot-robot geom pairs: g1 | g2 << 8 with g1 < g2 < number of geoms
     const int pk = ii[ii[7] + p], g1 = pk & 255, g2 = pk >> 8;
@@ -1209,7 +1513,7 @@ extern "C" int jh_tree_create(const void* blob, size_t nbytes, jh_tree** out) {
   jh_tree* t = new jh_tree();
   t->nf = (int)nf; t->ni = (int)ni; t->ns = ii[5];
   t->nj = ii[0]; t->ng = ii[1]; t->nq = ii[2]; t->nv = ii[3];
-  t->npair = ii[6]; t->self_collision = ii[6] > 0 ? 1 : 0;  // the robot collides with itself when the image lists pairs, as MuJoCo does (jh_tree_set_self_collision)
+  t->npair = ii[6]; t->self_collision = ii[6] > 0 ? 1 : 0; t->nobj = nobj;  // the robot collides with itself when the image lists pairs, as MuJoCo does (jh_tree_set_self_collision)
   JH_HIP(hipMalloc(&t->d_f, 4 * nf)); JH_HIP(hipMalloc(&t->d_i, 4 * ni)); JH_HIP(hipMalloc(&t->d_stats, 64 * sizeof(int)));
   JH_HIP(hipMemcpy(t->d_f, f, 4 * nf, hipMemcpyHostToDevice)); JH_HIP(hipMemcpy(t->d_i, ii, 4 * ni, hipMemcpyHostToDevice));
   JH_HIP(hipMemset(t->d_stats, 0, 64 * sizeof(int)));
@@ -1262,13 +1566,8 @@ extern "C" int jh_tree_substeps(const jh_tree* t, const float* state_in, const f
                                 void* stream) {
   JH_REQUIRE(t && state_in && ctrl && state_out, "tree_substeps: null pointer");
   JH_REQUIRE(N > 0 && substeps > 0, "tree_substeps: need at least one rollout and one step");
-  const int dshift = jh_latency_shift(N, RPW), per_wave = RPW >> dshift;
-  if (t->self_collision)
-    hipLaunchKernelGGL(k_tree_v4<true>, dim3((N + per_wave - 1) / per_wave), dim3(WAVE), 0, (hipStream_t)stream, t->d_f, t->d_i, t->nf, t->ni, state_in, NX, ctrl, warmstart, N, substeps, state_out, NX,
-                       sensors_out, t->ns, t->d_stats, dshift);
-  else
-    hipLaunchKernelGGL(k_tree_v4<false>, dim3((N + per_wave - 1) / per_wave), dim3(WAVE), 0, (hipStream_t)stream, t->d_f, t->d_i, t->nf, t->ni, state_in, NX, ctrl, warmstart, N, substeps, state_out, NX,
-                       sensors_out, t->ns, t->d_stats, dshift);
+  const int nx = t->nq + t->nv;
+  launch_tree(t, (hipStream_t)stream, state_in, nx, ctrl, warmstart, N, substeps, state_out, nx, sensors_out, t->ns);
   JH_HIP(hipGetLastError());
   return JH_OK;
 }
@@ -1292,6 +1591,7 @@ extern "C" int jh_policy_rollout(const jh_policy* p, jh_tree* t, const float* x0
   JH_REQUIRE(!reset_warmstart || warmstart, "policy_rollout: reset_warmstart needs a warmstart buffer");
   hipStream_t st = (hipStream_t)stream;
   float* control = scratch + jh_policy_scratch_floats(N);
+  const int NX = t->nq + t->nv, NQ = t->nq, NVT = t->nv;  // the state row of the image's model (robot [+ free box]): the policy reads the robot's part at its offsets
   const bool deadline = cutoff_seconds >= 0.0;
   if (deadline) {
     while ((int)t->events.size() < T + 1) { hipEvent_t e; JH_HIP(hipEventCreate(&e)); t->events.push_back(e); }
@@ -1309,13 +1609,7 @@ extern "C" int jh_policy_rollout(const jh_policy* p, jh_tree* t, const float* x0
     const int rc = jh_policy_step_strided(p, xin, ld, NQ, 0, 0, 7, 6, commands + (size_t)i * 25, T * 25, policy_out, control, scratch, N, st);
     if (rc != JH_OK) return rc;
     if (reset_warmstart) JH_HIP(hipMemsetAsync(warmstart, 0, (size_t)N * NVT * sizeof(float), st));
-    const int dshift = jh_latency_shift(N, RPW), per_wave = RPW >> dshift;
-    if (t->self_collision)
-      hipLaunchKernelGGL(k_tree_v4<true>, dim3((N + per_wave - 1) / per_wave), dim3(WAVE), 0, st, t->d_f, t->d_i, t->nf, t->ni, xin, ld, control, warmstart, N, substeps, states + (size_t)i * NX, T * NX,
-                         sensors ? sensors + (size_t)i * t->ns : nullptr, T * t->ns, t->d_stats, dshift);
-    else
-      hipLaunchKernelGGL(k_tree_v4<false>, dim3((N + per_wave - 1) / per_wave), dim3(WAVE), 0, st, t->d_f, t->d_i, t->nf, t->ni, xin, ld, control, warmstart, N, substeps, states + (size_t)i * NX, T * NX,
-                         sensors ? sensors + (size_t)i * t->ns : nullptr, T * t->ns, t->d_stats, dshift);
+    launch_tree(t, st, xin, ld, control, warmstart, N, substeps, states + (size_t)i * NX, T * NX, sensors ? sensors + (size_t)i * t->ns : nullptr, T * t->ns);
     if (deadline) JH_HIP(hipEventRecord(t->events[i + 1], st));
   }
   JH_HIP(hipGetLastError());

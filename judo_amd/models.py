@@ -26,11 +26,61 @@ MINMU = 1e-5
 
 
 def load_description(task: str) -> dict:
+    if task in DERIVED_DESCRIPTIONS:
+        return DERIVED_DESCRIPTIONS[task]()
     path = os.path.join(MODEL_DIR, task + ".json")
     if not os.path.exists(path):
         raise ValueError(f"unknown task {task!r}: no model description at {path}")
     with open(path) as f:
         return json.load(f)
+
+
+def spot_box_description() -> dict:
+    """The Spot robot with a free box (judo/models/xml/spot_box/robot.xml), derived from `spot.json` rather than transcribed into a file of its own.
+
+    spot_box/robot.xml includes the same spot_primitive/{default,body,legs,arm,actuator,contact}.xml as spot_primitive/robot.xml, so the robot's
+    bodies, joints, geoms, actuators and excludes are spot.json's.  What differs:
+      * the robot's body sits at z = 0.52 (robot.xml:16; spot_primitive: 0.7).  This moves qpos0 only: the inverse weights at qpos0 of the free base
+        (and of every body) do not depend on where the whole robot stands, the mass matrix being expressed about the base;
+      * a body `box_body` (robot.xml:22) with a free joint `box_joint` (:23), inertia at its origin (:24: mass 1.5, diaginertia 0.1445 x 3), a box geom
+        `box_collision` (:25: half size 0.254, class "collision" -> friction 0.15 and MuJoCo's default solref / solimp, the values every robot geom carries,
+        spot_primitive/default.xml:14-17; priority 4), and the site `site_object` (:27) that spot_primitive declares in the world body;
+      * the sensor list of robot.xml:36-50 (13 world-frame site sensors, 39 floats; no reference frames).
+    Bodies and geoms are in the order the MJCF compiler gives them (tools/compile_mjcf.py transcribes the XML to the same description): the box body
+    before the static fixtures that hold the plane, the box geom before the plane."""
+    d = load_description("spot")
+    bodies, geoms, sites = d["bodies"], d["geoms"], d["sites"]
+    fix = next(i for i, b in enumerate(bodies) if b["name"] == "world_fixtures")
+    assert fix == len(bodies) - 1 and all(b["parent"] != fix for b in bodies)
+    box = fix                                                   # the box takes the fixtures' index, the fixtures move one up
+    for g in geoms:
+        g["body"] = g["body"] + 1 if g["body"] == fix else g["body"]
+    for st in sites:
+        st["body"] = st["body"] + 1 if st["body"] == fix else st["body"]
+    bodies[1] = dict(bodies[1], pos=[0.0, 0.0, 0.52])                                                         # robot.xml:16
+    bodies.insert(box, dict(name="box_body", parent=0, pos=[2.0, 0.0, 0.254], quat=[1.0, 0.0, 0.0, 0.0], mocap=False,   # :22
+                            mass=1.5, ipos=[0.0, 0.0, 0.0], iquat=[1.0, 0.0, 0.0, 0.0], inertia=[0.1445, 0.1445, 0.1445]))   # :24
+    base = next(j for j in d["joints"] if j["type"] == "free")
+    d["joints"].append(dict(base, name="box_joint", body=box))                                               # :23 (a free joint's defaults, as the base's)
+    robot = next(g for g in geoms if g["type"] != "plane")      # class "collision": the contact parameters every robot geom carries
+    plane = next(i for i, g in enumerate(geoms) if g["type"] == "plane")
+    geoms.insert(plane, dict(name="box_collision", body=box, type="box", condim=robot["condim"], friction=list(robot["friction"]), solref=list(robot["solref"]),   # :25
+                             solimp=list(robot["solimp"]), margin=robot["margin"], gap=robot["gap"], solmix=robot["solmix"], priority=4, pos=[0.0, 0.0, 0.0],
+                             quat=[1.0, 0.0, 0.0, 0.0], size=[0.254, 0.254, 0.254]))
+    obj = next(i for i, st in enumerate(sites) if st["name"] == "site_object")
+    sites[obj] = dict(sites[obj], body=box, pos=[0.0, 0.0, 0.0])                                              # :27
+    site = {st["name"]: i for i, st in enumerate(sites)}
+    sens = [("sensor_body", "framepos", "site_body"), ("body_x_axis", "framexaxis", "site_body"), ("object_x_axis", "framexaxis", "site_object"),   # :37-39
+            ("object_y_axis", "frameyaxis", "site_object"), ("object_z_axis", "framezaxis", "site_object"), ("trace_fngr_site", "framepos", "site_arm_link_fngr"),   # :40-42
+            ("gripper_x_axis", "framexaxis", "site_arm_link_wr1"), ("gripper_y_axis", "frameyaxis", "site_arm_link_wr1"), ("finger_x_axis", "framexaxis", "site_arm_link_fngr"),   # :43-45
+            ("fl_pos", "framepos", "site_front_left"), ("fr_pos", "framepos", "site_front_right"), ("hl_pos", "framepos", "site_rear_left"), ("hr_pos", "framepos", "site_rear_right")]   # :46-49
+    d["sensors"] = [dict(name=n, type=t, adr=3 * k, objtype="site", obj=site[s], dim=3) for k, (n, t, s) in enumerate(sens)]
+    d["nsensordata"] = 3 * len(sens)
+    d["task"], d["family"], d["source"] = "spot_box", "spot", "judo v0.0.7 judo/models/xml/spot_box/robot.xml (derived from spot.json)"
+    return d
+
+
+DERIVED_DESCRIPTIONS = {"spot_box": spot_box_description}
 
 
 # ----------------------------------------------------------------------------------------- small rigid-body helpers

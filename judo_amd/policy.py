@@ -92,7 +92,8 @@ class SpotLocomotionPolicy:
 
 
 class SpotTreeEngine:
-    """The Spot model on the ground plane as a device engine: `substeps(states, ctrl, warmstart, n)` = n x mj_step with the control held."""
+    """The Spot model on the ground plane as a device engine: `substeps(states, ctrl, warmstart, n)` = n x mj_step with the control held.
+    `nq` / `nv` are the image's (jh_tree_dims): 26 / 25 for `spot`, 33 / 31 for `spot_box` (the robot's, then the free box's); the class constants are the robot's."""
 
     NQ, NV, NU = 26, 25, 19
 
@@ -109,20 +110,20 @@ class SpotTreeEngine:
         self.timestep = float(self.desc["option"]["timestep"])
         dims = (C.c_int * 4)()
         _lib.check(_lib.lib().jh_tree_dims(self.handle, dims), "jh_tree_dims")
-        self.nsensordata = int(dims[3])
+        self.nq, self.nv, self.nsensordata = int(dims[0]), int(dims[1]), int(dims[3])
         self.self_collision = bool(self_collision)
         _lib.check(_lib.lib().jh_tree_set_self_collision(self.handle, int(self.self_collision)), "jh_tree_set_self_collision")
 
     def substeps(self, states: torch.Tensor, ctrl: torch.Tensor, warmstart: torch.Tensor | None, n: int, out: torch.Tensor | None = None,
                  sensors: torch.Tensor | None = None) -> torch.Tensor:
-        nx = self.NQ + self.NV
+        nx = self.nq + self.nv
         if states.ndim != 2 or states.shape[1] != nx or not states.is_contiguous() or states.dtype != torch.float32:
             raise ValueError(f"states must be a contiguous float32 (N, {nx}) tensor")
         N = int(states.shape[0])
         if tuple(ctrl.shape) != (N, self.NU) or not ctrl.is_contiguous():
             raise ValueError(f"ctrl must be a contiguous (N, {self.NU}) tensor")
-        if warmstart is not None and (tuple(warmstart.shape) != (N, self.NV) or not warmstart.is_contiguous()):
-            raise ValueError(f"warmstart must be a contiguous (N, {self.NV}) tensor")
+        if warmstart is not None and (tuple(warmstart.shape) != (N, self.nv) or not warmstart.is_contiguous()):
+            raise ValueError(f"warmstart must be a contiguous (N, {self.nv}) tensor")
         if out is None:
             out = torch.empty_like(states)
         if sensors is not None and (tuple(sensors.shape) != (N, self.nsensordata) or not sensors.is_contiguous() or sensors.dtype != torch.float32):
@@ -157,14 +158,14 @@ class PolicyRolloutBackend(RolloutBackend):
         self.device = device or require_gpu()
         self.engine = SpotTreeEngine(desc, self.device)
         self.policy = SpotLocomotionPolicy(policy_path, self.device)
-        self.layout = SpotStateLayout(nq=SpotTreeEngine.NQ, nv=SpotTreeEngine.NV)
+        self.layout = SpotStateLayout(nq=self.engine.nq, nv=self.engine.nv)
         self.physics_substeps = int(physics_substeps)
         self.carry_warmstart = carry_warmstart
         self.update(num_threads)
 
     def update(self, num_threads: int) -> None:
         self.num_threads = int(num_threads)
-        self._warm = torch.zeros((self.num_threads, SpotTreeEngine.NV), dtype=torch.float32, device=self.device)
+        self._warm = torch.zeros((self.num_threads, self.engine.nv), dtype=torch.float32, device=self.device)
         self._scratch = None
 
     def rollout(self, x0, controls, last_policy_output=None, cutoff_time: float | None = None):
@@ -182,7 +183,7 @@ class PolicyRolloutBackend(RolloutBackend):
             raise ValueError(f"controls must be ({self.num_threads}, T, 25), got {tuple(cmd.shape)}")
         N, T = int(cmd.shape[0]), int(cmd.shape[1])
         x = f32(x0, self.device) if not isinstance(x0, torch.Tensor) else x0.to(torch.float32)
-        nx = SpotTreeEngine.NQ + SpotTreeEngine.NV
+        nx = self.engine.nq + self.engine.nv
         if tuple(x.shape) not in ((nx,), (N, nx)):
             raise ValueError(f"x0 must be ({nx},) or ({N}, {nx}), got {tuple(x.shape)}")
         x = x.contiguous()

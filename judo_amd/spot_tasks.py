@@ -4,8 +4,9 @@ A Spot task optimises a compact command vector (base velocity, optionally arm / 
 to the 25-d command of the locomotion policy, and the rollout runs policy + plant (`judo_amd.policy.PolicyRolloutBackend`).  Everything
 here accepts numpy arrays (host, float64, what the reference passes) or torch tensors (device, what the controller's materialise path passes).
 
-Scope this round: the robot alone on the ground plane (`spot_base`, `spot_navigate`).  The object tasks (`spot_box_push`, `spot_tire_roll`,
-`spot_tire_upright`) add free bodies the tree kernel does not carry yet.
+Scope: the robot alone on the ground plane (`spot_base`, `spot_navigate`) and the robot with a free box (`spot_box_push`, model `spot_box`: the tree kernel's
+object instantiation, csrc/jh_engine_v4.hip).  The tire tasks (`spot_tire_roll`, `spot_tire_upright`) collide a mesh tire that the reference does not ship
+(DESIGN.md section 8).
 """
 
 from __future__ import annotations
@@ -27,6 +28,8 @@ ARM_STOWED_POS = np.array([0, -3.11, 3.13, 1.56, 0, -1.56, GRIPPER_CLOSED_POS]) 
 ARM_UNSTOWED_POS = np.array([0, -0.9, 1.8, 0, -0.9, 0, GRIPPER_CLOSED_POS])         # :92
 STANDING_HEIGHT = 0.52                     # :95
 STANDING_HEIGHT_CMD = STANDING_HEIGHT      # :96
+Z_AXIS = np.array([0.0, 0.0, 1.0])         # :120
+BOX_HALF_LENGTH = 0.254                    # :127
 LEG_SOFT_LOWER_JOINT_LIMITS = np.array([-0.6, -0.8, -2.7] * 4)    # :99
 LEG_SOFT_UPPER_JOINT_LIMITS = np.array([0.6, 1.65, -0.3] * 4)     # :100
 ARM_SOFT_LOWER_JOINT_LIMITS = ARM_UNSTOWED_POS - np.array([1.0, 1.0, 0.8, np.pi / 2, 0.7, np.pi / 4, 0])   # :101
@@ -247,5 +250,73 @@ class SpotNavigate(SpotBase):
         return np.array([0, 0, STANDING_HEIGHT, 1, 0, 0, 0, *LEGS_STANDING_POS, *self.reset_arm_pos])
 
 
+# ---- judo/tasks/spot/spot_box_push.py ---------------------------------------------------------------------------------
+RADIUS_MIN, RADIUS_MAX = 1.0, 2.0           # :21-22
+
+
+@dataclass
+class SpotBoxPushConfig(SpotBaseConfig):    # spot_box_push.py:25-45
+    w_goal: float = 60.0
+    w_orientation: float = 15.0
+    w_torso_proximity: float = 0.1
+    w_gripper_proximity: float = 4.0
+    orientation_threshold: float = 0.5
+    fall_penalty: float = 2500.0
+    w_controls: float = 0.0
+    goal_position: np.ndarray = field(default_factory=lambda: np.array([0.0, 0.0, BOX_HALF_LENGTH]))
+
+
+class SpotBoxPush(SpotBase):
+    """spot_box_push.py:48-127: push the box to a goal position with the arm unstowed.  The model is `spot_box` (judo_amd.models.spot_box_description)."""
+
+    name = "spot_box_push"
+    model_name = "spot_box"
+    config_t = SpotBoxPushConfig
+
+    def __init__(self, config: SpotBoxPushConfig | None = None) -> None:
+        super().__init__(use_arm=True, config=config)
+        self.body_pose_idx = self.get_joint_position_start_index("base")
+        self.object_pose_idx = self.get_joint_position_start_index("box_joint")
+        self.object_y_axis_idx = self.get_sensor_start_index("object_y_axis")
+        self.gripper_pos_idx = self.get_sensor_start_index("trace_fngr_site")
+
+    def reward(self, states, sensors, controls, system_metadata: dict[str, Any] | None = None):   # :70-115
+        """As the reference computes it: the torso term enters with a POSITIVE sign, the orientation term counts the steps whose object y axis points up
+        (y . z > threshold), every other term is a mean over time."""
+        cfg = self.config
+        b, o, y, gi = self.body_pose_idx, self.object_pose_idx, self.object_y_axis_idx, self.gripper_pos_idx
+        body_height, body_pos, object_pos = states[..., b + 2], states[..., b : b + 3], states[..., o : o + 3]
+        object_y_axis, gripper_pos = sensors[..., y : y + 3], sensors[..., gi : gi + 3]
+        if _is_torch(states):
+            import torch
+
+            goal = torch.as_tensor(np.asarray(cfg.goal_position), dtype=states.dtype, device=states.device)
+            fallen = -cfg.fall_penalty * (body_height <= cfg.spot_fallen_threshold).any(dim=-1).to(states.dtype)
+            r = fallen - cfg.w_goal * torch.linalg.norm(object_pos - goal, dim=-1).mean(-1)
+            r = r - cfg.w_orientation * (object_y_axis[..., 2] > cfg.orientation_threshold).to(states.dtype).sum(-1)
+            r = r + cfg.w_torso_proximity * torch.linalg.norm(body_pos - object_pos, dim=-1).mean(-1)
+            r = r - cfg.w_gripper_proximity * torch.linalg.norm(gripper_pos - object_pos, dim=-1).mean(-1)
+            return r - cfg.w_controls * torch.linalg.norm(controls, dim=-1).mean(-1)
+        fallen = -cfg.fall_penalty * (body_height <= cfg.spot_fallen_threshold).any(axis=-1)
+        r = fallen - cfg.w_goal * np.linalg.norm(object_pos - np.asarray(cfg.goal_position)[None, None], axis=-1).mean(-1)
+        r = r - cfg.w_orientation * np.abs(np.dot(object_y_axis, Z_AXIS) > cfg.orientation_threshold).sum(axis=-1)
+        r = r + cfg.w_torso_proximity * np.linalg.norm(body_pos - object_pos, axis=-1).mean(-1)
+        r = r - cfg.w_gripper_proximity * np.linalg.norm(gripper_pos - object_pos, axis=-1).mean(-1)
+        return r - cfg.w_controls * np.linalg.norm(controls, axis=-1).mean(-1)
+
+    def default_state(self) -> np.ndarray:
+        """Deterministic x0 for the benchmark / parity harness: the robot standing at the origin with the arm unstowed, the box 1.5 m ahead, at rest."""
+        return np.concatenate([[0, 0, STANDING_HEIGHT, 1, 0, 0, 0], LEGS_STANDING_POS, self.reset_arm_pos, [1.5, 0, BOX_HALF_LENGTH, 1, 0, 0, 0], np.zeros(self.nv)])
+
+    @property
+    def reset_pose(self) -> np.ndarray:     # :117-127: base at randn(2), the box at radius 1..2 in a random direction plus randn(2)
+        radius = RADIUS_MIN + (RADIUS_MAX - RADIUS_MIN) * np.random.rand()
+        theta = 2 * np.pi * np.random.rand()
+        object_xy = np.array([radius * np.cos(theta), radius * np.sin(theta)]) + np.random.randn(2)
+        reset_object_pose = np.array([*object_xy, BOX_HALF_LENGTH, 1, 0, 0, 0])
+        return np.array([*np.random.randn(2), STANDING_HEIGHT, 1, 0, 0, 0, *LEGS_STANDING_POS, *self.reset_arm_pos, *reset_object_pose])
+
+
 register_task(SpotBase.name, SpotBase, SpotBaseConfig)
 register_task(SpotNavigate.name, SpotNavigate, SpotNavigateConfig)
+register_task(SpotBoxPush.name, SpotBoxPush, SpotBoxPushConfig)

@@ -8,6 +8,12 @@ listed in the image; pyramidal cones.  Contact parameters are mixed on the host:
 friction / solref / solimp apply to plane contacts (mj_contactParam); the robot geoms all carry the same solref / solimp / priority (checked), so a
 robot-robot pair takes the larger of the two frictions and the stored solref / solimp.
 
+Optional object section (judo/models/xml/spot_box/robot.xml): ONE free body hanging off the world, with its centre of mass at its origin, principal axes along its
+frame and ONE box collision geom, its dofs after the robot's.  The box collides with the plane (the plane's parameters, by priority, as for the robot geoms) and with every
+robot geom (equal priorities: mixed like a robot-robot pair; the box must carry the robot geoms' solref / solimp); a sensor site on the box has owner code -3.  Header
+I[8] = number of objects (0 or 1), I[9] / I[10] = where the object's float / int records start; both come after everything else, so the image of a model without an
+object is the same as before the section existed.
+
 Float image F / int image I (little-endian fp32 / int32), see the enums at the top of jh_engine_v4.hip.
 """
 
@@ -21,22 +27,38 @@ TH_F, TH_I = 32, 16           # header sizes
 TD_F, TD_I = 56, 4            # per joint dof
 TG_F, TG_I = 28, 2            # per geom
 TS_F, TS_I = 16, 4            # per sensor
+TO_F, TO_I = 48, 4            # object: body record (mass, ipos 3, iR 9, inertia 3, invweight0 2, pad 2) + its box geom in the geom record's layout; type, number of robot-box pairs, pad
 SOLVER_TOL, SOLVER_MAX_ITER, SOLVER_LS_TOL = 1e-4, 20, 1e-2
 GTYPE = {"sphere": 2, "capsule": 3, "box": 6}
 MAX_JOINTS, MAX_GEOMS, MAX_DEPTH = 25, 31, 7
 
 
+def object_joints(desc: dict) -> list[int]:
+    """Free joints after the first (the robot's base): the free objects of the model."""
+    return [j for j, jn in enumerate(desc["joints"]) if jn["type"] == "free"][1:]
+
+
 def tree_structure(desc: dict) -> dict:
-    """Base body, joint bodies in dof order, per-joint (parent joint, chain start, depth)."""
+    """Base body, joint bodies in dof order, per-joint (parent joint, chain start, depth); free objects (their bodies) after the robot."""
     lay = layout(desc)
     bodies, joints = desc["bodies"], desc["joints"]
     free = [j for j, jn in enumerate(joints) if jn["type"] == "free"]
-    if len(free) != 1 or lay.jnt_dofadr[free[0]] != 0:
+    if not free or lay.jnt_dofadr[free[0]] != 0:
         raise NotImplementedError("tree kernel: exactly one free joint, first in the dof order")
+    objs = object_joints(desc)
+    if len(objs) > 1:
+        raise NotImplementedError("tree kernel: at most one free object besides the robot")
+    objects = []
+    for j in objs:
+        b = joints[j]["body"]
+        if bodies[b]["parent"] != 0 or len(lay.body_joints[b]) != 1 or any(x["parent"] == b for x in bodies) or lay.jnt_dofadr[j] != lay.nv - 6:
+            raise NotImplementedError("tree kernel: a free object is one body hanging off the world, without children, its dofs last")
+        objects.append(b)
+    joints = [dict(jn, type="_object") if j in objs else jn for j, jn in enumerate(joints)]
     base = joints[free[0]]["body"]
     if bodies[base]["parent"] != 0 and any(len(lay.body_joints[b]) for b in [bodies[base]["parent"]]):
         raise NotImplementedError("tree kernel: the free body must hang off the world")
-    hinges = [j for j, jn in enumerate(joints) if jn["type"] != "free"]
+    hinges = [j for j, jn in enumerate(joints) if jn["type"] not in ("free", "_object")]
     body_of = {}
     info = []
     for k, j in enumerate(hinges):
@@ -58,7 +80,7 @@ def tree_structure(desc: dict) -> dict:
             raise NotImplementedError("tree kernel: every jointed body must hang off the base or off another jointed body")
     if len(hinges) > MAX_JOINTS or max(i["depth"] for i in info) >= MAX_DEPTH:
         raise NotImplementedError("tree kernel: at most 25 joints in chains of at most 7")
-    return dict(layout=lay, base=base, hinges=hinges, body_of=body_of, info=info)
+    return dict(layout=lay, base=base, hinges=hinges, body_of=body_of, info=info, objects=objects)
 
 
 def robot_pairs(desc: dict, robot_geoms: list) -> list[tuple[int, int]]:
@@ -83,9 +105,20 @@ def bounding_radius(g: dict) -> float:
     return {"sphere": size[0], "capsule": size[0] + size[1], "box": float(np.linalg.norm(size[:3]))}[g["type"]]
 
 
+def _mix_with_plane(g: dict, plane: dict):
+    """mj_contactParam for a geom against the plane: the higher priority wins, equal priorities mix (max friction, mean solref / solimp)."""
+    pri_p, pri_g = plane.get("priority", 0), g.get("priority", 0)
+    if pri_p > pri_g:
+        return plane["friction"][0], plane["solref"], plane["solimp"]
+    if pri_g > pri_p:
+        return g["friction"][0], g["solref"], g["solimp"]
+    return (max(plane["friction"][0], g["friction"][0]), [0.5 * (plane["solref"][i] + g["solref"][i]) for i in range(2)],
+            [0.5 * (plane["solimp"][i] + g["solimp"][i]) for i in range(5)])
+
+
 def pack_tree_model(desc: dict) -> tuple[np.ndarray, np.ndarray]:
     st = tree_structure(desc)
-    lay, base, hinges, body_of, info = st["layout"], st["base"], st["hinges"], st["body_of"], st["info"]
+    lay, base, hinges, body_of, info, objects = st["layout"], st["base"], st["hinges"], st["body_of"], st["info"], st["objects"]
     bodies, joints, geoms, o = desc["bodies"], desc["joints"], desc["geoms"], desc["option"]
     if o["cone"] != "pyramidal" or o["integrator"] != "implicitfast":
         raise NotImplementedError("tree kernel: pyramidal cones, implicitfast integrator")
@@ -98,7 +131,8 @@ def pack_tree_model(desc: dict) -> tuple[np.ndarray, np.ndarray]:
     pb = bodies[plane["body"]]
     Rp = quat_to_mat(pb["quat"]) @ quat_to_mat(plane["quat"])
     ppos = np.array(pb["pos"]) + quat_to_mat(pb["quat"]) @ np.array(plane["pos"])
-    robot_geoms = [g for g in geoms if g is not plane]
+    robot_geoms = [g for g in geoms if g is not plane and g["body"] not in objects]
+    obj_geoms = [g for g in geoms if g["body"] in objects]
     if len(robot_geoms) > MAX_GEOMS:
         raise NotImplementedError("tree kernel: too many collision geoms")
     act_of = {a["joint"]: a for a in desc["actuators"]}
@@ -114,8 +148,17 @@ def pack_tree_model(desc: dict) -> tuple[np.ndarray, np.ndarray]:
                 raise NotImplementedError("tree kernel: robot geoms with different solref / solimp / priority / solmix")
         if np.abs(bodyw[plane["body"]]).max() != 0:
             raise NotImplementedError("tree kernel: the plane must sit on a static body (zero inverse weight)")
-    F = np.zeros(TH_F + nj * TD_F + len(robot_geoms) * TG_F + len(sensors) * TS_F, dtype=np.float32)
-    I = np.zeros(TH_I + nj * TD_I + len(robot_geoms) * TG_I + len(sensors) * TS_I + len(pairs), dtype=np.int32)
+    opairs = []
+    if objects:
+        if len(obj_geoms) != 1 or obj_geoms[0]["type"] != "box":
+            raise NotImplementedError("tree kernel: a free object carries exactly one box collision geom")
+        ob, og = bodies[objects[0]], obj_geoms[0]
+        if np.abs(ob["ipos"]).max() > 0 or list(ob["iquat"]) != [1.0, 0.0, 0.0, 0.0]:
+            raise NotImplementedError("tree kernel: a free object has its centre of mass at its origin and its principal axes along its frame")
+        excl = {tuple(sorted(e)) for e in desc.get("excludes", [])}
+        opairs = [i for i, g in enumerate(robot_geoms) if tuple(sorted((g["body"], og["body"]))) not in excl]
+    F = np.zeros(TH_F + nj * TD_F + len(robot_geoms) * TG_F + len(sensors) * TS_F + (TO_F if objects else 0), dtype=np.float32)
+    I = np.zeros(TH_I + nj * TD_I + len(robot_geoms) * TG_I + len(sensors) * TS_I + len(pairs) + (TO_I + len(opairs) if objects else 0), dtype=np.int32)
     bb = bodies[base]
     F[0:8] = [o["timestep"], o["impratio"], SOLVER_TOL, SOLVER_MAX_ITER, SOLVER_LS_TOL, *o["gravity"]]
     F[8:14] = [*ppos, *Rp[:, 2]]                       # plane point, plane normal
@@ -155,7 +198,6 @@ def pack_tree_model(desc: dict) -> tuple[np.ndarray, np.ndarray]:
             raise NotImplementedError("tree kernel: joint-level actuatorfrcrange")
         I[TH_I + k * TD_I: TH_I + (k + 1) * TD_I] = [info[k]["parent"], info[k]["start"], info[k]["depth"], 1 if a is not None else 0]
     og_f, og_i = TH_F + nj * TD_F, TH_I + nj * TD_I
-    pri_p = plane.get("priority", 0)
     for gi, g in enumerate(robot_geoms):
         if g["type"] not in GTYPE or g["condim"] != 3 or g["margin"] != 0 or g["gap"] != 0:
             raise NotImplementedError(f"tree kernel: geom {g['name']} ({g['type']})")
@@ -163,15 +205,7 @@ def pack_tree_model(desc: dict) -> tuple[np.ndarray, np.ndarray]:
         owner = -1 if gb == base else body_of.get(gb)
         if owner is None:
             raise NotImplementedError("tree kernel: collision geoms must sit on the base or on a jointed body")
-        pri_g = g.get("priority", 0)
-        if pri_p > pri_g:
-            mu, solref, solimp = plane["friction"][0], plane["solref"], plane["solimp"]
-        elif pri_g > pri_p:
-            mu, solref, solimp = g["friction"][0], g["solref"], g["solimp"]
-        else:
-            mu = max(plane["friction"][0], g["friction"][0])
-            solref = [0.5 * (plane["solref"][i] + g["solref"][i]) for i in range(2)]
-            solimp = [0.5 * (plane["solimp"][i] + g["solimp"][i]) for i in range(5)]
+        mu, solref, solimp = _mix_with_plane(g, plane)
         cK, cB = solref_to_kb(solref, solimp, o["timestep"])
         size = (list(g["size"]) + [0, 0, 0])[:3]
         f = F[og_f + gi * TG_F: og_f + (gi + 1) * TG_F]
@@ -202,6 +236,8 @@ def pack_tree_model(desc: dict) -> tuple[np.ndarray, np.ndarray]:
             return -1, np.array(st["pos"], dtype=np.float64), np.eye(3)
         if b in body_of:
             return body_of[b], np.array(st["pos"], dtype=np.float64), np.eye(3)
+        if b in objects:
+            return -3, np.array(st["pos"], dtype=np.float64), np.eye(3)
         if len(lay.body_joints[b]) == 0 and (bodies[b]["parent"] == 0 or b == 0):   # world-fixed: fold the body pose into the site
             Rw = quat_to_mat(bodies[b]["quat"]) if b != 0 else np.eye(3)
             pw = (np.array(bodies[b]["pos"]) if b != 0 else np.zeros(3)) + Rw @ np.array(st["pos"])
@@ -232,6 +268,32 @@ def pack_tree_model(desc: dict) -> tuple[np.ndarray, np.ndarray]:
     I[6:8] = [len(pairs), op]
     for k, (a, b) in enumerate(pairs):
         I[op + k] = a | (b << 8)
+    if objects:  # the object section (module docstring)
+        oof, ooi = os_f + len(sensors) * TS_F, op + len(pairs)
+        I[8:11] = [1, oof, ooi]
+        f = F[oof: oof + TO_F]
+        f[0], f[1:4], f[4:13], f[13:16] = ob["mass"], ob["ipos"], quat_to_mat(ob["iquat"]).reshape(-1), ob["inertia"]
+        f[16:18] = bodyw[objects[0]]
+        mu, solref, solimp = _mix_with_plane(og, plane)  # the box against the plane
+        cK, cB = solref_to_kb(solref, solimp, o["timestep"])
+        own_k, own_b = solref_to_kb(og["solref"], og["solimp"], o["timestep"])
+        ref = robot_geoms[0]
+        if og["condim"] != 3 or og["margin"] != 0 or og["gap"] != 0 or og.get("priority", 0) != ref.get("priority", 0) or og.get("solmix", 1.0) != ref.get("solmix", 1.0) or \
+                list(og["solref"]) != list(ref["solref"]) or list(og["solimp"]) != list(ref["solimp"]) or \
+                not (np.isclose(own_k, cK) and np.isclose(own_b, cB) and np.allclose(clamp_solimp(og["solimp"]), clamp_solimp(solimp))):
+            raise NotImplementedError("tree kernel: the object's box needs condim 3, no margin / gap and the robot geoms' priority / solmix / solref / solimp")
+        g = f[20: 20 + TG_F]
+        g[0:3] = og["size"][:3]
+        g[3:6] = og["pos"]
+        g[6:15] = quat_to_mat(og["quat"]).reshape(-1)
+        g[15] = max(1e-5, mu)
+        g[16:18] = [cK, cB]
+        g[18:23] = clamp_solimp(solimp)
+        g[23] = bodyw[objects[0]][0] + bodyw[plane["body"]][0]
+        g[24] = bounding_radius(og)
+        g[25] = max(1e-5, og["friction"][0])
+        I[ooi: ooi + TO_I] = [GTYPE[og["type"]], len(opairs), 0, 0]
+        I[ooi + TO_I: ooi + TO_I + len(opairs)] = opairs
     return F, I
 
 

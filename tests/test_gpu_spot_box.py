@@ -1,0 +1,251 @@
+"""spot_box on the GPU: the tree kernel's free-box instantiation (csrc/jh_engine_v4.hip, `k_tree_v4<SELF, true>`) against the oracle engine with the `spot_box`
+description (judo_amd.models.spot_box_description; oracle.collision_pairs(desc, "all"): the robot's 287 own pairs, 27 robot-box pairs and box-plane), the policy
+rollout of the spot_box model against `oracle.policy.policy_rollout`, the task's device reward against its numpy reward, and a short closed loop of the controller.
+
+Floating point as in tests/test_gpu_spot.py (fp32 kernel stopping at 1e-4, fp64 oracle at 1e-10); tolerances are 5x the largest error observed (tests/conftest.py::bounded)."""
+
+import numpy as np
+import pytest
+
+from tests.conftest import bounded
+
+pytestmark = pytest.mark.gpu
+
+NQ, NV = 33, 31
+# state columns: robot base position / quaternion, joints, box position / quaternion; robot base velocities, joint velocities, box velocities
+SL = dict(pos=slice(0, 3), quat=slice(3, 7), q=slice(7, 26), opos=slice(26, 29), oquat=slice(29, 33), vlin=slice(33, 36), vang=slice(36, 39), qd=slice(39, 58),
+          ovlin=slice(58, 61), ovang=slice(61, 64))
+# 5 x the largest error observed over the tests below (per unit of `scale`): 6.1e-8, 8e-8, 3.0e-7, 1.2e-7, 7.7e-8, 8.8e-7, 4.7e-6, 1.7e-5, 1.5e-6, 6.4e-6 -- the level of
+# test_gpu_spot.py's TOL; the largest box errors come from the tilted box dropped onto the plane, the robot-box contacts stay below them
+TOL = dict(pos=3e-7, quat=4e-7, q=1.5e-6, opos=6e-7, oquat=4e-7, vlin=4.5e-6, vang=2.5e-5, qd=8.5e-5, ovlin=7.5e-6, ovang=3.2e-5)
+
+
+def _check(what, got, ref, tol, scale=1.0):
+    for name, sl in SL.items():
+        err = np.abs(got[..., sl] - ref[..., sl]).max()
+        assert bounded(f"spot_box {what}: {name} error / scale", err / scale, tol[name]), f"{what} {name}: {err:.3e} > {tol[name] * scale:.1e}"
+
+
+@pytest.fixture(scope="module")
+def box(gpu):
+    from judo_amd.models import load_description
+    from judo_amd.policy import SpotTreeEngine
+    from oracle import oracle as O
+    from oracle import policy as P
+
+    desc = load_description("spot_box")
+    om = O.Model("spot_box", desc=desc, pairs=O.collision_pairs(desc, "all"))
+    eng = SpotTreeEngine(desc)
+    assert (om.nq, om.nv, eng.nq, eng.nv, eng.nsensordata) == (NQ, NV, NQ, NV, 39)
+    return P, O, om, eng, desc
+
+
+def _reset_state(P, box_xy=(2.0, 0.0)):
+    """SpotBoxPush's layout: the robot's reset state, the box 4 mm into the plane (resting exactly at its half size would put the corners at the fp32 contact threshold)."""
+    x = P.spot_reset_state()
+    return np.concatenate([x[:26], [box_xy[0], box_xy[1], 0.25, 1, 0, 0, 0], x[26:], np.zeros(6)])
+
+
+def _oracle_steps(om, X, U, k, with_sensors=False):
+    res = [om.rollout(X[i], np.repeat(U[i][None], k, axis=0)[None], nthread=1) for i in range(X.shape[0])]
+    st = np.stack([r[0][0, -1] for r in res])
+    return (st, np.stack([r[1][0, -1] for r in res])) if with_sensors else st
+
+
+def _run(eng, om, X, U, tol, what, steps=(1, 2, 5)):
+    import torch
+
+    xs = torch.as_tensor(X, dtype=torch.float32, device="cuda")
+    us = torch.as_tensor(U, dtype=torch.float32, device="cuda")
+    eng.stats()
+    for k in steps:
+        warm = torch.zeros((len(X), NV), dtype=torch.float32, device="cuda")
+        got = eng.substeps(xs, us, warm, k).cpu().numpy()
+        assert np.isfinite(got).all()
+        _check(f"{what}, {k} steps", got, _oracle_steps(om, X, U, k), tol, scale=1.0 + 0.5 * (k - 1))
+    st = eng.stats()
+    assert st["contacts_dropped"] == 0, st
+    return st
+
+
+def _box_contact_states(P, om, desc, n_want, seed):
+    """Robot standing, the box placed against it at random: classified by what the robot-box contacts couple -- the base alone, the base and one chain (arm or a leg), two
+    different chains (the dense path)."""
+    from judo_amd.tree_model import tree_structure
+
+    st = tree_structure(desc)
+    gs = desc["geoms"]
+    boxg = next(i for i, g in enumerate(gs) if g["name"] == "box_collision")
+
+    def chain(g):
+        b = gs[g]["body"]
+        if b not in st["body_of"]:
+            return 0
+        c0 = st["info"][st["body_of"][b]]["start"]
+        return 1 + (c0 // 3 if c0 < 12 else 4)
+
+    rng = np.random.default_rng(seed)
+    out = {"base": [], "one": [], "two": []}
+    for _ in range(4000):
+        if all(len(v) >= n_want for v in out.values()):
+            break
+        x = _reset_state(P)
+        x[7:19] += rng.standard_normal(12) * 0.05
+        if rng.random() < 0.5:
+            x[19:26] = [0, -0.9, 1.8, 0, -0.9, 0, 0] + rng.standard_normal(7) * 0.3   # the arm out in front
+        ang = rng.uniform(-np.pi, np.pi)
+        r = rng.uniform(0.35, 0.9)
+        x[26:28] = [r * np.cos(ang), r * np.sin(ang)]
+        x[28] = 0.25 + rng.uniform(0.0, 0.35)
+        qq = np.array([1.0, *rng.standard_normal(3) * 0.2])
+        x[29:33] = qq / np.linalg.norm(qq)
+        x[NQ + 25: NQ + 31] = rng.standard_normal(6) * 0.2
+        f = om.forward(x[:NQ], x[NQ:], x[7:26])
+        cs = f["contacts"]
+        rbc = [c for c in cs if boxg in (int(c[13]), int(c[14])) and gs[int(c[13]) if int(c[14]) == boxg else int(c[14])]["type"] != "plane"]
+        rb = [int(c[13]) if int(c[14]) == boxg else int(c[14]) for c in rbc]
+        if not rb or f["ncon"] > 28 or min(c[0] for c in rbc) < -0.02:
+            continue  # (deep interpenetration of a random placement: stiff, and nothing a rollout visits)
+        chains = {chain(g) for g in rb} - {0}
+        kind = "base" if not chains else ("one" if len(chains) == 1 else "two")
+        if len(out[kind]) < n_want:
+            out[kind].append(x)
+    return out
+
+
+def test_box_resting_robot_in_the_air(box):
+    """No robot-box contact: the box's own rows (box-plane, four corners) next to the robot's articulated dynamics, joint friction and limits."""
+    P, O, om, eng, desc = box
+    rng = np.random.default_rng(0)
+    N = 6
+    X = np.tile(_reset_state(P), (N, 1))
+    X[:, 2] = 1.0
+    X[:, 7:26] += rng.standard_normal((N, 19)) * 0.1
+    X[:, NQ:NQ + 25] = rng.standard_normal((N, 25)) * 0.3
+    U = np.tile(P.DEFAULT_JOINT_POS, (N, 1))
+    _run(eng, om, X, U, TOL, "resting box")
+    import torch
+
+    # sensordata: the box site's frame axes (object_x / y / z_axis) and the robot's sites, from the last step's forward pass
+    sens = torch.full((N, 39), float("nan"), dtype=torch.float32, device="cuda")
+    eng.substeps(torch.as_tensor(X, dtype=torch.float32, device="cuda"), torch.as_tensor(U, dtype=torch.float32, device="cuda"), None, 3, sensors=sens)
+    _, sref = _oracle_steps(om, X, U, 3, with_sensors=True)
+    np.testing.assert_allclose(sens.cpu().numpy(), sref, rtol=0, atol=1.5e-6)
+
+
+def test_box_dropped_tilted_onto_the_plane(box):
+    """A tilted, spinning box dropped onto the plane: one to four corner contacts (PlaneBox), box rows only."""
+    P, O, om, eng, desc = box
+    rng = np.random.default_rng(1)
+    N = 8
+    X = np.tile(_reset_state(P), (N, 1))
+    X[:, 7:19] += rng.standard_normal((N, 12)) * 0.02
+    q = rng.standard_normal((N, 4)) * np.array([[0.0, 0.5, 0.5, 0.5]])
+    q[:, 0] = 1.0
+    X[:, 29:33] = q / np.linalg.norm(q, axis=1, keepdims=True)
+    X[:, 28] = 0.25 + rng.uniform(-0.02, 0.1, N)
+    X[:, NQ + 25: NQ + 31] = rng.standard_normal((N, 6)) * 0.5
+    U = np.tile(P.DEFAULT_JOINT_POS, (N, 1))
+    boxg = next(j for j, g in enumerate(desc["geoms"]) if g["name"] == "box_collision")
+    ncorner = [int(sum(boxg in (int(c[13]), int(c[14])) for c in om.forward(X[i, :NQ], X[i, NQ:], U[i])["contacts"])) for i in range(N)]
+    assert max(ncorner) >= 2 and min(ncorner) >= 1, ncorner
+    _run(eng, om, X, U, TOL, "dropped box")
+
+
+@pytest.mark.parametrize("kind", ["base", "one", "two"])
+def test_robot_pushing_the_box(box, kind):
+    """Robot-box contacts: with the base alone and with one chain (the box block eliminated by its Schur complement, the robot system still a tree), and with two chains at
+    once (the dense 25 x 25 path)."""
+    P, O, om, eng, desc = box
+    groups = _box_contact_states(P, om, desc, 4, seed=11)
+    X = np.stack(groups[kind])
+    assert len(X) >= 2, {k: len(v) for k, v in groups.items()}
+    U = X[:, 7:26].copy()
+    _run(eng, om, X, U, TOL, f"robot-box contact ({kind})", steps=(1, 2, 5))
+    # the contacts matter: the same states without the robot-box pairs move the box differently
+    import torch
+    from judo_amd.policy import SpotTreeEngine
+
+    xs = torch.as_tensor(X, dtype=torch.float32, device="cuda")
+    us = torch.as_tensor(U, dtype=torch.float32, device="cuda")
+    a = eng.substeps(xs, us, None, 1).cpu().numpy()
+    om_free = O.Model("spot_box", desc=desc, pairs=[p for p in O.collision_pairs(desc, "all") if not (desc["geoms"][p[1]]["name"] == "box_collision" and desc["geoms"][p[0]]["type"] != "plane")])
+    b = _oracle_steps(om_free, X, U, 1)
+    assert np.abs(a[:, 58:64] - b[:, 58:64]).max() > 1e-3
+    del SpotTreeEngine
+
+
+def test_policy_rollout_with_the_box_matches_oracle(box):
+    """jh_policy_rollout on the spot_box image (state stride 64): 24 rollouts x a few command rows, states and the 39 sensor floats, against oracle.policy.policy_rollout."""
+    from judo_amd.policy import PolicyRolloutBackend
+
+    P, O, om, eng, desc = box
+    Ws, bs = P.load_actor()
+    N, T = 24, 5
+    x0 = _reset_state(P, box_xy=(0.95, 0.0))     # the box right in front of the robot: the unstowed arm and the body reach it
+    rng = np.random.default_rng(3)
+    cmds = np.tile(P.DEFAULT_POLICY_COMMAND, (N, T, 1))
+    cmds[:, :, :3] = rng.uniform(-0.5, 0.5, (N, 1, 3))
+    cmds[:, :, 3:10] = np.array([0, -0.9, 1.8, 0, -0.9, 0, 0]) + rng.standard_normal((N, 1, 7)) * 0.3
+    be = PolicyRolloutBackend(N, desc=desc, carry_warmstart=False)
+    states, sensors, outs = be.rollout(x0, cmds, np.zeros((N, 12)))
+    assert states.shape == (N, T, 64) and sensors.shape == (N, T, 39) and outs.shape == (N, 12)
+    assert be.engine.stats()["contacts_dropped"] == 0
+    for i in range(N):
+        ref, sref, o = P.policy_rollout(om, Ws, bs, x0, cmds[i], with_sensors=True)
+        _check(f"policy rollout {i}", states[i], ref, TOL, scale=4.0)
+        assert bounded("spot_box policy rollout: sensor error", np.abs(sensors[i] - sref).max(), 5e-6)               # observed <= 9.8e-7
+        assert bounded("spot_box policy rollout: policy output error", np.abs(outs[i] - o).max(), 3.5e-5)          # observed <= 6.7e-6
+
+
+def test_device_reward_matches_numpy_reward_of_oracle_states(box):
+    """SpotBoxPush.reward on the device tensors of a policy rollout equals its numpy reward on the oracle's states and sensors of the same rollouts."""
+    import torch
+    from judo_amd.policy import PolicyRolloutBackend
+    from judo_amd.spot_tasks import SpotBoxPush
+
+    P, O, om, eng, desc = box
+    task = SpotBoxPush()
+    Ws, bs = P.load_actor()
+    N, T = 6, 4
+    x0 = _reset_state(P, box_xy=(1.2, 0.3))
+    cmds = np.tile(P.DEFAULT_POLICY_COMMAND, (N, T, 1))
+    cmds[:, :, 0] = np.linspace(-0.5, 0.5, N)[:, None]
+    be = PolicyRolloutBackend(N, desc=desc, carry_warmstart=False)
+    st, se, _ = be.rollout(x0, torch.as_tensor(cmds, dtype=torch.float32, device="cuda"), torch.zeros((N, 12), dtype=torch.float32, device="cuda"))
+    ctl = torch.zeros((N, T, task.nu), dtype=torch.float32, device="cuda")
+    r_dev = task.reward(st, se, ctl).cpu().numpy()
+    ref = [P.policy_rollout(om, Ws, bs, x0, cmds[i], with_sensors=True) for i in range(N)]
+    r_np = task.reward(np.stack([r[0] for r in ref]), np.stack([r[1] for r in ref]), np.zeros((N, T, task.nu)))
+    assert bounded("spot_box_push device reward vs numpy reward of oracle states, relative", np.abs(r_dev - r_np).max() / np.abs(r_np).max(), 6e-7)  # observed 1.3e-7
+
+
+def test_spot_box_push_controller_closed_loop(box):
+    """make_controller("spot_box_push", "mppi"): plan steps on the box model, the plan's first action applied to a one-rollout plant; finite, and the box moves."""
+    import torch
+    from judo_amd.controller import make_controller
+    from judo_amd.policy import PolicyRolloutBackend
+
+    P, O, om, eng, desc = box
+    np.random.seed(0)
+    ctrl = make_controller("spot_box_push", "mppi")
+    ctrl.rollout_cutoff_time = None
+    ctrl.optimizer.seed(2)
+    task = ctrl.task
+    x = _reset_state(P, box_xy=(0.66, 0.0))         # the box 14 mm into the robot's body box: pushed away from the first step on
+    x0 = x.copy()
+    x[19:26] = [0, -0.9, 1.8, 0, -0.9, 0, 0]
+    plant = PolicyRolloutBackend(1, physics_substeps=task.physics_substeps, desc=task.desc)
+    last = np.zeros((1, 12))
+    t = 0.0
+    for _ in range(5):
+        ctrl.update_states(x[:NQ], x[NQ:], time=t)
+        ctrl.update_action()
+        assert np.isfinite(ctrl.nominal_knots).all() and np.isfinite(ctrl.rewards).all()
+        cmd = np.asarray(task.task_to_sim_ctrl(ctrl.action(t)), dtype=np.float64).reshape(1, 1, 25)
+        st, _, last = plant.rollout(x, cmd, last)
+        x = st[0, -1]
+        t += task.dt
+    assert np.isfinite(x).all() and x[2] > 0.3
+    assert np.linalg.norm(x[26:28] - x0[26:28]) > 1e-3
+    torch.cuda.synchronize()

@@ -460,6 +460,14 @@ def compile_model(xml_name: str, task: str) -> dict:
     return model
 
 
+def transcribe_spot_box() -> dict:
+    """judo/models/xml/spot_box/robot.xml as a description: a CROSS-CHECK only.  The product derives `spot_box` from spot.json in code
+    (judo_amd/models.py::spot_box_description) and no spot_box.json is written; tests/test_spot_box_host.py compares the two."""
+    m = compile_model("spot_box/robot.xml", "spot_box")
+    m["family"] = "spot"
+    return m
+
+
 def main() -> None:
     os.makedirs(OUT_DIR, exist_ok=True)
     for xml_name, task in (("cartpole.xml", "cartpole"), ("cylinder_push.xml", "cylinder_push"), ("leap_cube.xml", "leap_cube"), ("fr3_pick.xml", "fr3_pick"),
