@@ -129,10 +129,7 @@ class Controller:
         self._side_events, self._side_flip = None, 0
         self.noise_events: list = []  # (start, end) of the side-stream noise draws when record_kernel_events is set
         self.prefetch_noise = True  # draw the next iteration's noise behind this iteration's download
-        self.zero_copy_out = True  # jh_update_fused writes nominal | sigma | trace records into the pinned host block itself (no download command)
         self.force_shard_path = False  # tests: take launch -> all-gather -> merge with ONE rank as well (the RCCL branch of the exchange on a one-GPU box)
-        self.poll_completion = True  # one GPU, closed-form models (plan steps of ~0.1 ms): wait for the completion word the update's last workgroup writes behind its results instead of the stream's event (jh_plan_step, out_host_mark); the articulated models' 7-50 ms plan steps keep the event
-        self.host_block_in_place = True  # closed-form models: the plan-step kernel reads x0 | nominal | sigma | task params | bounds from the pinned host block (no copy in front of the launch)
         self.fused_update = True  # one GPU: the whole update (block partials, merge, trace elites) in one launch and one download (jh_update_fused); False: the separate kernels
         self._prefetch_args = None
         self.keep_candidates = False
@@ -485,7 +482,7 @@ class Controller:
             _lib.check(_lib.lib().jh_upload_async(b.blk.data_ptr(), b.host_ptr, b.nblk_bytes, self._stream), "jh_upload_async")
 
     def _ensure_block(self, b: _PlanBuffers) -> None:
-        """The device copy of the plan block holds what the pinned host block holds.  A plan step whose kernel read the host block in place (`host_block_in_place`)
+        """The device copy of the plan block holds what the pinned host block holds.  A plan step whose kernel read the host block in place (closed-form models)
         leaves the device copy behind; the few consumers of the device views outside the plan step (`candidate_knots`, the knot-record form of the trace stage) bring it up first."""
         if getattr(b, "blk_stale", False):
             _lib.check(_lib.lib().jh_upload_async(b.blk.data_ptr(), b.host_ptr, b.nblk_bytes, current_stream_ptr()), "jh_upload_async")
@@ -507,36 +504,62 @@ class Controller:
             lohi = np.where(np.isnan(lohi), np.concatenate([ctrl_lo, ctrl_hi]), lohi)
         return np.nan_to_num(lohi.astype(np.float32), posinf=3.0e38, neginf=-3.0e38)
 
-    def _fetch(self, b: _PlanBuffers, n: int, behind=None, in_place: bool = False, n_float: int | None = None) -> np.ndarray:
-        """Device result -> pinned host memory, one wait: the only synchronisation of an iteration.  `behind` enqueues work that may run after the
-        copy (the trace records): it is launched while the copy is in flight and is not waited for.  `in_place`: the update kernel wrote the pinned host
-        block itself (jh_update_fused with host pointers): no copy, the completion mark alone."""
+    def _fetch(self, b: _PlanBuffers, n: int = 0, behind=None, begun: bool = False) -> None:
+        """Wait for the iteration's result in the pinned output block: the only synchronisation of an iteration.  `n` floats are copied there from the device
+        block first; 0: the update kernel wrote the pinned block itself (a completion mark alone).  `begun`: jh_plan_step / jh_plan_merge set the mark already.
+        `behind` enqueues work that may run after the result (the trace records), and so is the next iteration's noise draw: launched while the kernels run,
+        not waited for."""
         L = _lib.lib()
-        _lib.check(L.jh_download_begin(b.out_host_ptr, b.out.data_ptr(), 0 if in_place else 4 * n, self._stream), "jh_download_begin")
-        try:  # (the mark set by `begin` must be consumed whatever happens in between: `end` pops the oldest mark of this thread)
+        if not begun:
+            _lib.check(L.jh_download_begin(b.out_host_ptr, b.out.data_ptr(), 4 * n, self._stream), "jh_download_begin")
+        try:  # (the mark must be consumed whatever happens in between: `end` pops the oldest mark of this thread)
             if behind is not None:
                 behind()
             if self._prefetch_args is not None:
                 self._prefetch_noise(*self._prefetch_args)
         finally:
             _lib.check(L.jh_download_end(), "jh_download_end")
-        # only nominal | sigma are floats to be widened: the trace records behind them carry an index column of int bit patterns (they are consumed as the raw fp32 copy)
-        return b.out_np[: n if n_float is None else n_float].astype(np.float64)
+
+    def _event(self) -> HipEvent | None:
+        """A timing event recorded now on the launch stream while `record_kernel_events` is on."""
+        if not self.record_kernel_events:
+            return None
+        ev = self._timing_event()
+        ev.record()
+        return ev
+
+    def _trace_buffer(self, b: _PlanBuffers, n_local: int, H: int) -> tuple[torch.Tensor, int] | None:
+        """(buffer, floats per rollout) into which the fused kernel writes the trace sensors of every rollout, so that `traces` becomes a gather of the elites' rows
+        instead of a second rollout; None when it writes none."""
+        nfl = self._fused_trace_floats()
+        if not nfl:
+            return None
+        if b.trace_buf is None or b.trace_buf.numel() != n_local * H * nfl:
+            b.trace_buf = torch.empty(n_local * H * nfl, dtype=torch.float32, device=self.device)
+        return b.trace_buf, H * nfl
+
+    def _iteration_shape(self, world: int, nrm: Normalizer) -> str:
+        """How an iteration of a `FusedOptimizer` runs:
+          "plan_step"        one GPU, shipped cost: ONE library call (jh_plan_step) and one wait;
+          "plan_step_shard"  the same on several ranks (or `force_shard_path`): jh_plan_step_shard -> one all-gather of the ranks' records -> jh_plan_merge;
+          "update_fused"     one GPU otherwise (plugin costs, the materialise path, running normaliser statistics): rollout, then jh_update_fused;
+          "separate"         rollout, then the separate partial / all-gather / merge kernels (several ranks outside "plan_step_shard", or `fused_update` off)."""
+        fused_update = self.fused_update and hasattr(self.optimizer, "fused_update_args")
+        if fused_update and not nrm.needs_moments and self.uses_fused_cost:
+            return "plan_step" if world == 1 and not self.force_shard_path else "plan_step_shard"
+        return "update_fused" if fused_update and world == 1 else "separate"
 
     def _fused_iteration(self, lib, b: _PlanBuffers, nrm: Normalizer, nominal_n: np.ndarray, W, shard: Shard, world: int, H: int, K: int, nu: int, N: int,
                          stream, state: dict) -> np.ndarray:
-        opt, task = self.optimizer, self.task
+        opt = self.optimizer
         sigma_n = np.asarray(opt.knot_sigma(), dtype=np.float64)  # normalised units; may advance CEM state
         # every shipped normaliser is affine per actuator: raw = center + scale * normalised (judo_amd/normalization.py)
         scale, center = nrm.noise_scale(), nrm.denormalize(np.zeros(nu))
         nominal_raw = nrm.denormalize(nominal_n)
         sigma_raw = sigma_n * scale[None, :]
-        fused_cost = self.uses_fused_cost
-        one_call = world == 1 and not self.force_shard_path and fused_cost and self.fused_update and self.zero_copy_out and hasattr(opt, "fused_update_args") and not nrm.needs_moments
-        # several ranks, same conditions: the same shape -- launch (rollout + this rank's record) -> ONE all-gather -> merge -- instead of the chain of separate partial /
-        # gather / merge / trace-gather launches with two collectives, which remains for the cases below (plugin costs, running normaliser statistics)
-        shard_call = (world > 1 or self.force_shard_path) and fused_cost and self.fused_update and self.zero_copy_out and hasattr(opt, "fused_update_args") and not nrm.needs_moments
-        self._pack_block(b, nominal_raw, sigma_raw, self._raw_bounds(nrm), upload=not (one_call or shard_call))
+        shape = self._iteration_shape(world, nrm)
+        one_call = shape in ("plan_step", "plan_step_shard")
+        self._pack_block(b, nominal_raw, sigma_raw, self._raw_bounds(nrm), upload=not one_call)  # (the plan-step calls upload the block themselves or read it in place)
         noise = self._draw_noise(shard.count, shard.offset)  # (K, nu, shard.count), possibly a view into the full draw
         self._prefetch_args = (shard.count, shard.offset)
         ldn, noise_p = int(noise.stride(1)), noise.data_ptr()
@@ -548,94 +571,92 @@ class Controller:
             if b.knots_out is None or b.knots_out.shape[2] != ldn:
                 b.knots_out = torch.empty((K, nu, ldn), dtype=torch.float32, device=self.device)
             knots_out = b.knots_out[:, :, : shard.count]
-        state["trace_buf"] = None
-        is_cem = hasattr(opt, "sigma") and isinstance(getattr(opt, "sigma"), np.ndarray)
-        if one_call or shard_call:
-            # ---- one GPU, shipped cost: the whole iteration is ONE library call (jh_plan_step: upload, rollout + cost kernel, one-launch update with the trace elites'
-            # records, results written straight into the pinned host block) and one wait
-            nfl = self._fused_trace_floats()
-            staging = state.get("stage") is not None
-            if nfl and (b.trace_buf is None or b.trace_buf.numel() != shard.count * H * nfl):
-                b.trace_buf = torch.empty(shard.count * H * nfl, dtype=torch.float32, device=self.device)
-            E_t = min(int(state.get("E", 0)), _lib.MAX_ELITES) if (staging and nfl) else 0
-            row = H * nfl if E_t else 0
-            n_out = 2 * K * nu + E_t * (2 + row)
-            b.size_out(n_out)
-            mode, lam, k_el, tie = opt.fused_update_args()
-            timing = None
-            if self.record_kernel_events:
-                evs = [self._timing_event() for _ in range(3)]
-                timing = (C.c_void_p * 3)(*[e.handle for e in evs])
-                self.kernel_events.append((evs[0], evs[1]))
-                self.exchange_events.append((evs[1], evs[2]))
-            off = b.offsets
-            if one_call:
-                in_place = self.host_block_in_place and self.model.closed_form and knots_out is None
-                blk_dev = b.host_ptr if in_place else b.blk.data_ptr()
-                b.blk_stale = in_place  # (jh_plan_step uploads the block itself unless it is read in place)
-                st = lib.jh_plan_step(self.model.handle, blk_dev, b.host_ptr, b.nblk_bytes, int(off[1]), int(off[2]), int(off[3]), int(off[4]), noise_p, ldn, _lib.ptr(W), int(task.phase),
-                                      shard.count, shard.offset, H, K, _lib.ptr(b.costs), _lib.ptr(knots_out), _lib.ptr(b.trace_buf) if nfl else None, mode, lam, k_el, tie, E_t, row,
-                                      int(self._trace_colmajor) if nfl else 0, _lib.ptr(b.fused_scratch), b.out_host_ptr, b.done_ptr if (self.poll_completion and self.model.closed_form) else b.out_host_ptr, timing, stream)
-                what = "jh_plan_step"
-            else:
-                # ---- several ranks: launch (rollout + cost + this rank's record [update record | E trace records]) -> one all-gather -> merge on every rank into
-                # the same pinned output block; everything behind this branch is the one-GPU code
-                b.blk_stale = False  # (jh_plan_step_shard uploads the block)
-                L = int(lib.jh_shard_record_floats(K, nu, mode, k_el, E_t, row))
-                if b.shard_rec is None or b.shard_rec.numel() != L:
-                    b.shard_rec = torch.empty(L, dtype=torch.float32, device=self.device)
-                st = lib.jh_plan_step_shard(self.model.handle, b.blk.data_ptr(), b.host_ptr, b.nblk_bytes, int(off[1]), int(off[2]), int(off[3]), int(off[4]), noise_p, ldn, _lib.ptr(W),
-                                            int(task.phase), shard.count, shard.offset, H, K, _lib.ptr(b.costs), _lib.ptr(knots_out), _lib.ptr(b.trace_buf) if nfl else None, mode, lam, k_el,
-                                            tie, E_t, row, int(self._trace_colmajor) if nfl else 0, _lib.ptr(b.fused_scratch), _lib.ptr(b.shard_rec), timing, stream)
-                _lib.check(st, "jh_plan_step_shard")
-                if self._prefetch_args is not None:  # the next iteration's noise on the side stream, enqueued in front of the collective: it overlaps the exchange
-                    self._prefetch_noise(*self._prefetch_args, side=True)
-                    self._prefetch_args = None
-                b.shard_all = all_gather_records(b.shard_rec, self.group, force=self.force_shard_path)  # (world * L,), rank-major; kept alive until the merge has run
-                done = None
-                if self.record_kernel_events:
-                    done = self._timing_event()
-                    self.exchange_events[-1] = (evs[1], done)  # exchange = this rank's record + the all-gather + the merge
-                st = lib.jh_plan_merge(_lib.ptr(b.shard_all), world, K, nu, mode, lam, k_el, tie, E_t, row, b.out_host_ptr, b.out_host_ptr, done.handle if done is not None else None, stream)
-                what = "jh_plan_merge"
-            try:
-                _lib.check(st, what)
-                if self._prefetch_args is not None:
-                    self._prefetch_noise(*self._prefetch_args)
-            finally:
-                if st == 0:
-                    _lib.check(lib.jh_download_end(), "jh_download_end")
-            res = b.out_np[: 2 * K * nu if is_cem else K * nu].astype(np.float64)  # (not the trace records: their index column is an int bit pattern)
-            if nfl:
-                state["trace_buf"] = (b.trace_buf, H * nfl)
-            state.update(costs=b.costs, knots_out=knots_out, noise_p=noise_p, ldn=ldn, knots_nku=None)
-            if E_t:
-                self._traces = None
-                self._trace_stage = dict(kind="sensors", recs=b.out_np[2 * K * nu : n_out].copy(), stride=2 + row, E=int(state["E"]), x0=state["x0"], times=np.array(state["new_times"]),
-                                         order=self.spline_order, H=H, K=K, nu=nu, index_is_bits=True, sorted=True)
-            elif staging:
-                state["stage"]()  # (no trace buffer: the elites' knots, re-rolled when the traces are read)
-            nominal_n = (res[: K * nu].reshape(K, nu) - center[None, :]) / scale[None, :]
-            if is_cem:
-                opt.sigma = np.clip(res[K * nu : 2 * K * nu].reshape(K, nu) / scale[None, :], opt.sigma_min, opt.sigma_max)
-            self._rewards, self._candidate_knots = None, None
-            self._last_fused = dict(b=b, noise=noise, noise_p=noise_p, ldn=ldn, shard=shard, K=K, nu=nu)
-            return nominal_n
-        if self.record_kernel_events:
-            ev0, ev1 = self._timing_event(), self._timing_event()
-            ev0.record()
-        if fused_cost:
-            nfl = self._fused_trace_floats()
-            if nfl:  # the kernel also writes the trace sensors of every rollout: `traces` becomes a gather of the elites' rows instead of a second rollout
-                if b.trace_buf is None or b.trace_buf.numel() != shard.count * H * nfl:
-                    b.trace_buf = torch.empty(shard.count * H * nfl, dtype=torch.float32, device=self.device)
+        state.update(knots_out=knots_out, noise_p=noise_p, ldn=ldn, knots_nku=None, trace_buf=None)
+        is_cem = isinstance(getattr(opt, "sigma", None), np.ndarray)
+        n_res = 2 * K * nu if is_cem else K * nu  # nominal (| sigma); the trace records behind them carry an index column of int bit patterns and are not widened
+        if one_call:
+            E_t = self._plan_step(lib, b, shape, noise_p, ldn, knots_out, W, shard, world, H, K, nu, stream, state)
+        else:
+            E_t = self._rollout_update(lib, b, shape, nrm, noise_p, ldn, knots_out, W, shard, world, H, K, nu, N, n_res, stream, state)
+        res = b.out_np[:n_res].astype(np.float64)
+        if E_t:  # the update wrote the trace elites' records behind nominal | sigma, best first
+            stride = 2 + state["trace_buf"][1]
+            self._traces = None
+            self._trace_stage = dict(kind="sensors", recs=b.out_np[2 * K * nu : 2 * K * nu + E_t * stride].copy(), stride=stride, E=int(state["E"]), x0=state["x0"],
+                                     times=np.array(state["new_times"]), order=self.spline_order, H=H, K=K, nu=nu, index_is_bits=True, sorted=True)
+        nominal_n = (res[: K * nu].reshape(K, nu) - center[None, :]) / scale[None, :]  # the update acted on the normalised candidates
+        if is_cem:  # CEM: refit in normalised units
+            opt.sigma = np.clip(res[K * nu : 2 * K * nu].reshape(K, nu) / scale[None, :], opt.sigma_min, opt.sigma_max)
+        self._rewards, self._candidate_knots = None, None
+        self._last_fused = dict(b=b, noise=noise, noise_p=noise_p, ldn=ldn, shard=shard, K=K, nu=nu)
+        return nominal_n
+
+    def _trace_records(self, b: _PlanBuffers, state: dict, K: int, nu: int) -> tuple[int, int]:
+        """(count, row floats) of the trace elites' records the update writes behind nominal | sigma -- in the iteration that stages the traces, when the rollout
+        kernel wrote the trace buffer -- with the output block sized for them."""
+        tb = state["trace_buf"]
+        E_t = min(int(state.get("E", 0)), _lib.MAX_ELITES) if (state.get("stage") is not None and tb is not None) else 0
+        row = tb[1] if E_t else 0
+        b.size_out(2 * K * nu + E_t * (2 + row))
+        return E_t, row
+
+    def _plan_step(self, lib, b: _PlanBuffers, shape: str, noise_p: int, ldn: int, knots_out, W, shard: Shard, world: int, H: int, K: int, nu: int, stream,
+                   state: dict) -> int:
+        """Shapes "plan_step" / "plan_step_shard": upload, rollout + cost kernel and the update with the trace elites' records in one library call, the results
+        written straight into the pinned output block -- on several ranks through this rank's record, one all-gather and the merge.  Returns the trace records written."""
+        opt = self.optimizer
+        tb = state["trace_buf"] = self._trace_buffer(b, shard.count, H)
+        E_t, row = self._trace_records(b, state, K, nu)
+        mode, lam, k_el, tie = opt.fused_update_args()
+        evs = [self._timing_event() for _ in range(3)] if self.record_kernel_events else None  # recorded inside the call: before the rollout, before the update, behind it
+        timing = (C.c_void_p * 3)(*[e.handle for e in evs]) if evs else None
+        off = b.offsets
+        args = (b.host_ptr, b.nblk_bytes, int(off[1]), int(off[2]), int(off[3]), int(off[4]), noise_p, ldn, _lib.ptr(W), int(self.task.phase), shard.count, shard.offset, H, K,
+                _lib.ptr(b.costs), _lib.ptr(knots_out), _lib.ptr(tb[0]) if tb else None, mode, lam, k_el, tie, E_t, row, int(self._trace_colmajor) if tb else 0,
+                _lib.ptr(b.fused_scratch))
+        state["costs"] = b.costs
+        exchange_end = evs[2] if evs else None
+        if shape == "plan_step":
+            # closed-form models (plan steps of ~0.1 ms): the kernel reads the host block in place, and the host polls the completion word the update's last workgroup
+            # writes behind its results; the articulated models' 7-50 ms plan steps upload the block and keep the stream's event
+            in_place = b.blk_stale = self.model.closed_form and knots_out is None
+            mark = b.done_ptr if self.model.closed_form else b.out_host_ptr
+            _lib.check(lib.jh_plan_step(self.model.handle, b.host_ptr if in_place else b.blk.data_ptr(), *args, b.out_host_ptr, mark, timing, stream), "jh_plan_step")
+        else:
+            b.blk_stale = False  # (jh_plan_step_shard uploads the block)
+            L = int(lib.jh_shard_record_floats(K, nu, mode, k_el, E_t, row))
+            if b.shard_rec is None or b.shard_rec.numel() != L:
+                b.shard_rec = torch.empty(L, dtype=torch.float32, device=self.device)
+            _lib.check(lib.jh_plan_step_shard(self.model.handle, b.blk.data_ptr(), *args, _lib.ptr(b.shard_rec), timing, stream), "jh_plan_step_shard")
+            if self._prefetch_args is not None:  # the next iteration's noise on the side stream, enqueued in front of the collective: it overlaps the exchange
+                self._prefetch_noise(*self._prefetch_args, side=True)
+                self._prefetch_args = None
+            b.shard_all = all_gather_records(b.shard_rec, self.group, force=self.force_shard_path)  # (world * L,), rank-major; kept alive until the merge has run
+            exchange_end = self._timing_event() if evs else None  # exchange = this rank's record + the all-gather + the merge
+            st = lib.jh_plan_merge(_lib.ptr(b.shard_all), world, K, nu, mode, lam, k_el, tie, E_t, row, b.out_host_ptr, b.out_host_ptr,
+                                   exchange_end.handle if exchange_end else None, stream)
+            _lib.check(st, "jh_plan_merge")
+        if evs:
+            self.kernel_events.append((evs[0], evs[1]))
+            self.exchange_events.append((evs[1], exchange_end))
+        self._fetch(b, begun=True)
+        if not E_t and state.get("stage") is not None:
+            state["stage"]()  # (no trace buffer: the elites' knots, re-rolled when the traces are read)
+        return E_t
+
+    def _rollout_update(self, lib, b: _PlanBuffers, shape: str, nrm: Normalizer, noise_p: int, ldn: int, knots_out, W, shard: Shard, world: int, H: int, K: int,
+                        nu: int, N: int, n_res: int, stream, state: dict) -> int:
+        """Shapes "update_fused" / "separate": the rollout (the fused rollout + cost kernel, or the materialise path), then the update, then -- for the running
+        normaliser -- the moments of this iteration's candidates.  Returns the trace records written behind nominal | sigma."""
+        opt, task = self.optimizer, self.task
+        ev0 = self._event()
+        if self.uses_fused_cost:
+            tb = state["trace_buf"] = self._trace_buffer(b, shard.count, H)
             st = lib.jh_rollout_cost_traced(self.model.handle, _lib.ptr(b.x0), _lib.ptr(b.nominal), noise_p, ldn, _lib.ptr(b.sigma), _lib.ptr(W),
                                             _lib.ptr(b.lohi), _lib.ptr(b.tp), int(task.phase), shard.count, shard.offset, H, K, _lib.ptr(b.costs),
-                                            _lib.ptr(knots_out), _lib.ptr(b.trace_buf) if nfl else None, stream)
+                                            _lib.ptr(knots_out), _lib.ptr(tb[0]) if tb else None, stream)
             _lib.check(st, "jh_rollout_cost")
             costs = b.costs
-            if nfl:
-                state["trace_buf"] = (b.trace_buf, H * nfl)
         else:
             costs = self._materialised_costs(b.x0, b.nominal, noise_p, ldn, b.sigma, b.lohi, None, W, shard, H, K, stream)
             if knots_out is not None:  # the materialise path never wrote the candidates: sample them into the (K, nu, N) layout the fused kernel uses
@@ -643,54 +664,32 @@ class Controller:
                 st = lib.jh_sample_knots(_lib.ptr(b.nominal), noise_p, ldn, _lib.ptr(b.sigma), _lib.ptr(b.lohi), shard.count, shard.offset, K, nu, _lib.ptr(tmp), stream)
                 _lib.check(st, "jh_sample_knots")
                 knots_out.copy_(tmp.permute(1, 2, 0))
-        if self.record_kernel_events:
-            ev1.record()
-            self.kernel_events.append((ev0, ev1))
-        is_cem = hasattr(opt, "sigma") and isinstance(getattr(opt, "sigma"), np.ndarray)
-        state.update(costs=costs, knots_out=knots_out, noise_p=noise_p, ldn=ldn, knots_nku=None)
-        tail = world == 1 and self.fused_update and hasattr(opt, "fused_update_args")
-        if tail:
+        if ev0 is not None:
+            self.kernel_events.append((ev0, self._event()))
+        state["costs"] = costs
+        if shape == "update_fused":
             # one GPU: block partials, merge and -- in the last iteration, when the rollout kernel wrote the trace buffer -- the trace elites' records in ONE launch,
-            # nominal | sigma | records in one output block, one download (controller.py:288-299 without the seven-launch chain)
-            tb, staging = state.get("trace_buf"), state.get("stage") is not None
-            E_t = min(int(state.get("E", 0)), _lib.MAX_ELITES) if (staging and tb is not None) else 0
-            row = tb[1] if E_t else 0
-            n_out = 2 * K * nu + E_t * (2 + row)
-            b.size_out(n_out)
+            # nominal | sigma | records written straight into the pinned host block (device-visible: hipHostMalloc) by the last workgroup (controller.py:288-299
+            # without the seven-launch chain)
+            E_t, row = self._trace_records(b, state, K, nu)
             mode, lam, k_el, tie = opt.fused_update_args()
-            if self.record_kernel_events:
-                ex0, ex1 = self._timing_event(), self._timing_event()
-                ex0.record()
-            # the results go straight into the pinned host block (device-visible: hipHostMalloc): a few KB of stores from the last workgroup instead of a copy command
-            o = b.out_host_ptr if self.zero_copy_out else b.out.data_ptr()
+            ex0 = self._event()
+            o = b.out_host_ptr
             st = lib.jh_update_fused(_lib.ptr(costs), None, _lib.ptr(b.nominal), noise_p, ldn, _lib.ptr(b.sigma), _lib.ptr(b.lohi), shard.count, shard.offset, K, nu, mode, lam,
-                                     k_el, tie, E_t, _lib.ptr(tb[0]) if E_t else None, row, int(self._trace_colmajor) if E_t else 0, _lib.ptr(b.fused_scratch),
+                                     k_el, tie, E_t, _lib.ptr(state["trace_buf"][0]) if E_t else None, row, int(self._trace_colmajor) if E_t else 0, _lib.ptr(b.fused_scratch),
                                      o, o + 4 * K * nu, (o + 8 * K * nu) if E_t else None, stream)
             _lib.check(st, "jh_update_fused")
-            if self.record_kernel_events:
-                ex1.record()
-                self.exchange_events.append((ex0, ex1))
-            if staging and E_t:
-                res = self._fetch(b, n_out, in_place=self.zero_copy_out, n_float=2 * K * nu if is_cem else K * nu)
-                self._traces = None
-                self._trace_stage = dict(kind="sensors", recs=b.out_np[2 * K * nu : n_out].copy(), stride=2 + row, E=int(state["E"]), x0=state["x0"], times=np.array(state["new_times"]),
-                                         order=self.spline_order, H=H, K=K, nu=nu, index_is_bits=True, sorted=True)
-            else:
-                res = self._fetch(b, 2 * K * nu if is_cem else K * nu, behind=state.get("stage"), in_place=self.zero_copy_out)
+            n_copy = 0
         else:
+            E_t = 0
             opt.device_partial(costs, None, b.nominal, noise_p, b.sigma, b.lohi, shard.count, shard.offset, b.scratch, b.rec, ldn=ldn, stream=stream)
-            if self.record_kernel_events:  # the exchange of the per-rank records and the merge (bench.py attributes the plan step: kernel / exchange / host)
-                ex0, ex1 = self._timing_event(), self._timing_event()
-                ex0.record()
+            ex0 = self._event()  # the exchange of the per-rank records and the merge (bench.py attributes the plan step: kernel / exchange / host)
             recs = all_gather_records(b.rec, self.group)
             opt.device_merge(recs, world, b.out.data_ptr(), b.out.data_ptr() + 4 * K * nu, clip_sigma=False, stream=stream)
-            if self.record_kernel_events:
-                ex1.record()
-                self.exchange_events.append((ex0, ex1))
-            res = self._fetch(b, 2 * K * nu if is_cem else K * nu, behind=state.get("stage"))
-        nominal_n = (res[: K * nu].reshape(K, nu) - center[None, :]) / scale[None, :]  # the update acted on the normalised candidates
-        if is_cem:  # CEM: refit in normalised units
-            opt.sigma = np.clip(res[K * nu : 2 * K * nu].reshape(K, nu) / scale[None, :], opt.sigma_min, opt.sigma_max)
+            n_copy = n_res
+        if ex0 is not None:
+            self.exchange_events.append((ex0, self._event()))
+        self._fetch(b, n_copy, behind=None if E_t else state.get("stage"))
         if nrm.needs_moments:  # running statistics over this iteration's raw candidates, all ranks (controller.py:290-291)
             if b.mom is None:
                 b.mom = torch.empty(2 * nu, dtype=torch.float32, device=self.device)
@@ -705,10 +704,7 @@ class Controller:
             s1 = m[0] + cnt * dm
             s2 = m[1] + 2 * dm * m[0] + cnt * dm * dm
             nrm.update_from_moments(cnt, s1, s2)
-        state.update(costs=costs, knots_out=knots_out, noise_p=noise_p, ldn=ldn, knots_nku=None)
-        self._rewards, self._candidate_knots = None, None
-        self._last_fused = dict(b=b, noise=noise, noise_p=noise_p, ldn=ldn, shard=shard, K=K, nu=nu)
-        return nominal_n
+        return E_t
 
     def _candidates_iteration(self, lib, b: _PlanBuffers, nrm: Normalizer, nominal_n: np.ndarray, W, shard: Shard, H: int, K: int, nu: int, N: int,
                               stream, state: dict) -> np.ndarray:

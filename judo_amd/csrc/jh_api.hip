@@ -311,79 +311,62 @@ static int plan_step_launches(const jh_model* m, int N, int H, int K, const floa
   return JH_OK;
 }
 
-// One plan-step iteration on one GPU as ONE call (Controller.update_action's loop body, judo/controller/controller.py:250-299): the packed host block
-// x0 | nominal | sigma | task params | bounds goes up, the fused rollout + cost kernel runs, jh_update_fused reduces the costs to nominal | sigma | trace
-// records -- written where `out` points, normally the pinned host block itself -- and the completion mark of jh_download_begin is set: jh_download_end waits for
-// it.  Everything is enqueued on `stream`; nothing is waited for here.  Five ctypes calls less per plan step than the separate entry points: a tenth of a small one.
-extern "C" int jh_plan_step(const jh_model* m, void* blk_dev, const void* blk_host, size_t blk_bytes, int o_nominal, int o_sigma, int o_tp, int o_lohi, const float* noise, int ldn,
-                            const float* W, int phase, int N, int n_offset, int H, int K, float* costs, float* knots_out, float* trace, int mode, float lambda, int k, int tie_high, int E,
-                            int row_floats, int colmajor, float* scratch, float* out, void* out_host_mark, void* const* timing /* 3 events of jh_event_create, or NULL */, void* stream) {
-  JH_REQUIRE(m && blk_dev && blk_host && out && scratch, "plan_step: null pointer");
+// One plan-step iteration as ONE call (Controller.update_action's loop body, judo/controller/controller.py:250-299): the packed host block x0 | nominal | sigma |
+// task params | bounds goes up, the fused rollout + cost kernel runs, and the update's tail reduces the costs.  Everything is enqueued on `stream`; nothing is waited for
+// here.  Five ctypes calls less per plan step than the separate entry points: a tenth of a small one.  The tail writes one of two destinations:
+//  - `out` (jh_plan_step): nominal | sigma | trace records, normally the pinned host block itself, then the completion mark of jh_download_begin, which
+//    jh_download_end waits for.  `flag` non-null: a 4-byte word in device-visible pinned host memory -- the update's last workgroup stores its old value + 1 there
+//    behind the results and jh_download_end polls it instead of waiting for the stream's event;
+//  - `rec_out` (jh_plan_step_shard): this rank's RECORD (jh_update_shard's) instead of the nominal, and no mark: the caller all-gathers the G records and
+//    jh_plan_merge finishes the update.
+static int plan_step(const char* who, const jh_model* m, void* blk_dev, const void* blk_host, size_t blk_bytes, int o_nominal, int o_sigma, int o_tp, int o_lohi,
+                     const float* noise, int ldn, const float* W, int phase, int N, int n_offset, int H, int K, float* costs, float* knots_out, float* trace, int mode,
+                     float lambda, int k, int tie_high, int E, int row_floats, int colmajor, float* scratch, float* out, unsigned* flag, float* rec_out,
+                     void* const* timing, void* stream) {
+  JH_REQUIRE(m && blk_dev && blk_host && (out || rec_out) && scratch, "%s: null pointer", who);
   const float* b = (const float*)blk_dev;
   hipStream_t st = (hipStream_t)stream;
   // blk_dev == blk_host: a device-visible pinned host block the kernels read in place (the closed-form models: a few hundred bytes read once per workgroup cost less than the copy in front of the launch)
   int rc = blk_dev == blk_host ? JH_OK : jh_upload_async(blk_dev, blk_host, blk_bytes, stream);
   if (rc == JH_OK && timing) JH_HIP(hipEventRecord((hipEvent_t)timing[0], st));
   const int KU = K * m->nu;
-  // out_host_mark != out: a 4-byte word in device-visible pinned host memory -- the update's last workgroup stores its old value + 1 there behind the results and jh_download_end
-  // polls it instead of waiting for the stream's event
-  unsigned* flag = (out_host_mark && out_host_mark != (void*)out) ? (unsigned*)out_host_mark : nullptr;
   const unsigned expect = flag ? __atomic_load_n(flag, __ATOMIC_RELAXED) + 1u : 0u;
   bool one = false;
   if (rc == JH_OK) rc = plan_step_launches(m, N, H, K, costs, knots_out, W, noise, ldn, &one);
-  if (rc == JH_OK && one) {
-    // closed-form models: rollout + cost + the update's tail in ONE launch (jh_simple.hip k_plan_step); the rollout / update split of the timing events collapses
-    jh_upd::TailArgs a;
-    rc = jh_update_tail_args("plan_step", costs, nullptr, b + o_nominal, noise, ldn, b + o_sigma, b + o_lohi, N, n_offset, K, m->nu, mode, lambda, k, tie_high, trace ? E : 0, trace, row_floats,
-                             colmajor, scratch, out, out + KU, (trace && E > 0) ? out + 2 * KU : nullptr, nullptr, &a);
-    a.done_flag = flag; a.done_value = expect;
-    if (rc == JH_OK) rc = jh_simple_plan_step(m, b, W, b + o_tp, H, K, a, st);
-    if (rc == JH_OK && timing) { JH_HIP(hipEventRecord((hipEvent_t)timing[1], st)); JH_HIP(hipEventRecord((hipEvent_t)timing[2], st)); }
-    if (rc == JH_OK) rc = download_begin(out, out, 0, stream, flag, expect);
-    return rc;
-  }
-  if (rc == JH_OK) rc = jh_rollout_cost_traced(m, b, b + o_nominal, noise, ldn, b + o_sigma, W, b + o_lohi, b + o_tp, phase, N, n_offset, H, K, costs, knots_out, trace, stream);
-  if (rc == JH_OK && timing) JH_HIP(hipEventRecord((hipEvent_t)timing[1], st));
-  if (rc == JH_OK) {
-    jh_upd::TailArgs a;
-    rc = jh_update_tail_args("plan_step", costs, nullptr, b + o_nominal, noise, ldn, b + o_sigma, b + o_lohi, N, n_offset, K, m->nu, mode, lambda, k, tie_high, trace ? E : 0, trace, row_floats,
-                             colmajor, scratch, out, out + KU, (trace && E > 0) ? out + 2 * KU : nullptr, nullptr, &a);
-    a.done_flag = flag; a.done_value = expect;
-    if (rc == JH_OK) rc = jh_update_tail_launch(a, st);
-  }
+  // two launches: the rollout kernel, then k_update_tail; one (closed-form models): rollout + cost + the update's tail in jh_simple.hip's k_plan_step, where the
+  // rollout / update split of the timing events collapses
+  if (rc == JH_OK && !one) rc = jh_rollout_cost_traced(m, b, b + o_nominal, noise, ldn, b + o_sigma, W, b + o_lohi, b + o_tp, phase, N, n_offset, H, K, costs, knots_out, trace, stream);
+  if (rc == JH_OK && !one && timing) JH_HIP(hipEventRecord((hipEvent_t)timing[1], st));
+  jh_upd::TailArgs a;
+  if (rc == JH_OK)
+    rc = jh_update_tail_args(who, costs, nullptr, b + o_nominal, noise, ldn, b + o_sigma, b + o_lohi, N, n_offset, K, m->nu, mode, lambda, k, tie_high, trace ? E : 0, trace, row_floats,
+                             colmajor, scratch, out, out ? out + KU : nullptr, (out && trace && E > 0) ? out + 2 * KU : nullptr, rec_out, &a);
+  a.done_flag = flag; a.done_value = expect;
+  if (rc == JH_OK) rc = one ? jh_simple_plan_step(m, b, W, b + o_tp, H, K, a, st) : jh_update_tail_launch(a, st);
+  if (rc == JH_OK && one && timing) JH_HIP(hipEventRecord((hipEvent_t)timing[1], st));
   if (rc == JH_OK && timing) JH_HIP(hipEventRecord((hipEvent_t)timing[2], st));
-  if (rc == JH_OK) rc = download_begin(out, out, 0, stream, flag, expect);
+  if (rc == JH_OK && out) rc = download_begin(out, out, 0, stream, flag, expect);
   return rc;
 }
 
-// The same iteration when the rollouts are sharded over G ranks: launch -> all-gather -> merge.  jh_plan_step_shard is jh_plan_step with the update's
-// last stage left out: the tail launch writes this rank's RECORD (jh_update_shard) instead of the nominal; the caller all-gathers the G records (RCCL: one collective
-// of <= a few KB) and hands them to jh_plan_merge, which finishes the update on every rank (jh_shard_merge: identical nominal everywhere, no broadcast) into the same
-// output block jh_plan_step fills and sets the same completion mark.
+extern "C" int jh_plan_step(const jh_model* m, void* blk_dev, const void* blk_host, size_t blk_bytes, int o_nominal, int o_sigma, int o_tp, int o_lohi, const float* noise, int ldn,
+                            const float* W, int phase, int N, int n_offset, int H, int K, float* costs, float* knots_out, float* trace, int mode, float lambda, int k, int tie_high, int E,
+                            int row_floats, int colmajor, float* scratch, float* out, void* out_host_mark, void* const* timing /* 3 events of jh_event_create, or NULL */, void* stream) {
+  JH_REQUIRE(out, "plan_step: null pointer");
+  unsigned* flag = (out_host_mark && out_host_mark != (void*)out) ? (unsigned*)out_host_mark : nullptr;  // (out_host_mark == out: the stream's event)
+  return plan_step("plan_step", m, blk_dev, blk_host, blk_bytes, o_nominal, o_sigma, o_tp, o_lohi, noise, ldn, W, phase, N, n_offset, H, K, costs, knots_out, trace, mode, lambda, k,
+                   tie_high, E, row_floats, colmajor, scratch, out, flag, nullptr, timing, stream);
+}
+
+// The same iteration when the rollouts are sharded over G ranks: launch -> all-gather -> merge.  The tail writes this rank's record; jh_plan_merge
+// finishes the update on every rank (jh_shard_merge: identical nominal everywhere, no broadcast) into the same output block jh_plan_step fills and sets the same
+// completion mark.
 extern "C" int jh_plan_step_shard(const jh_model* m, void* blk_dev, const void* blk_host, size_t blk_bytes, int o_nominal, int o_sigma, int o_tp, int o_lohi, const float* noise,
                                   int ldn, const float* W, int phase, int N, int n_offset, int H, int K, float* costs, float* knots_out, float* trace, int mode, float lambda, int k,
                                   int tie_high, int E, int row_floats, int colmajor, float* scratch, float* rec_out, void* const* timing /* 3 events, or NULL */, void* stream) {
-  JH_REQUIRE(m && blk_dev && blk_host && rec_out && scratch, "plan_step_shard: null pointer");
-  const float* b = (const float*)blk_dev;
-  hipStream_t st = (hipStream_t)stream;
-  int rc = blk_dev == blk_host ? JH_OK : jh_upload_async(blk_dev, blk_host, blk_bytes, stream);
-  if (rc == JH_OK && timing) JH_HIP(hipEventRecord((hipEvent_t)timing[0], st));
-  bool one = false;
-  if (rc == JH_OK) rc = plan_step_launches(m, N, H, K, costs, knots_out, W, noise, ldn, &one);
-  if (rc == JH_OK && one) {
-    jh_upd::TailArgs a;
-    rc = jh_update_tail_args("plan_step_shard", costs, nullptr, b + o_nominal, noise, ldn, b + o_sigma, b + o_lohi, N, n_offset, K, m->nu, mode, lambda, k, tie_high, trace ? E : 0, trace,
-                             row_floats, colmajor, scratch, nullptr, nullptr, nullptr, rec_out, &a);
-    if (rc == JH_OK) rc = jh_simple_plan_step(m, b, W, b + o_tp, H, K, a, st);
-    if (rc == JH_OK && timing) { JH_HIP(hipEventRecord((hipEvent_t)timing[1], st)); JH_HIP(hipEventRecord((hipEvent_t)timing[2], st)); }
-    return rc;
-  }
-  if (rc == JH_OK) rc = jh_rollout_cost_traced(m, b, b + o_nominal, noise, ldn, b + o_sigma, W, b + o_lohi, b + o_tp, phase, N, n_offset, H, K, costs, knots_out, trace, stream);
-  if (rc == JH_OK && timing) JH_HIP(hipEventRecord((hipEvent_t)timing[1], st));
-  if (rc == JH_OK) rc = jh_update_shard(costs, nullptr, b + o_nominal, noise, ldn, b + o_sigma, b + o_lohi, N, n_offset, K, m->nu, mode, lambda, k, tie_high, trace ? E : 0, trace, row_floats,
-                                        colmajor, scratch, rec_out, stream);
-  if (rc == JH_OK && timing) JH_HIP(hipEventRecord((hipEvent_t)timing[2], st));
-  return rc;
+  JH_REQUIRE(rec_out, "plan_step_shard: null pointer");
+  return plan_step("plan_step_shard", m, blk_dev, blk_host, blk_bytes, o_nominal, o_sigma, o_tp, o_lohi, noise, ldn, W, phase, N, n_offset, H, K, costs, knots_out, trace, mode,
+                   lambda, k, tie_high, E, row_floats, colmajor, scratch, nullptr, nullptr, rec_out, timing, stream);
 }
 
 extern "C" int jh_plan_merge(const float* recs, int G, int K, int nu, int mode, float lambda, int k, int tie_high, int E, int row_floats, float* out, void* out_host_mark,

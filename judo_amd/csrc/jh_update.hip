@@ -308,10 +308,7 @@ extern "C" int jh_update_fused(const float* costs, const float* knots_nku, const
   TailArgs a;
   if (int e = jh_update_tail_args("update_fused", costs, knots_nku, nominal, noise, ldn, sigma, lohi, N, n_offset, K, nu, mode, lambda, k, tie_high, E, trace, row_floats, colmajor, scratch,
                                   nominal_out, sigma_out, trace_out, nullptr, &a)) return e;
-  const int nb = (N + kUB - 1) / kUB;
-  hipLaunchKernelGGL(k_update_tail, dim3(nb), dim3(kUB), 0, (hipStream_t)stream, a);
-  JH_HIP(hipGetLastError());
-  return JH_OK;
+  return jh_update_tail_launch(a, (hipStream_t)stream);
 }
 
 // ------------------------------------------------------------------------------------------------ the sharded plan step: launch -> all-gather -> merge
@@ -364,10 +361,7 @@ extern "C" int jh_update_shard(const float* costs, const float* knots_nku, const
   TailArgs a;
   if (int e = jh_update_tail_args("update_shard", costs, knots_nku, nominal, noise, ldn, sigma, lohi, N, n_offset, K, nu, mode, lambda, k, tie_high, E, trace, row_floats, colmajor, scratch,
                                   nullptr, nullptr, nullptr, rec_out, &a)) return e;
-  const int nb = (N + kUB - 1) / kUB;
-  hipLaunchKernelGGL(k_update_tail, dim3(nb), dim3(kUB), 0, (hipStream_t)stream, a);
-  JH_HIP(hipGetLastError());
-  return JH_OK;
+  return jh_update_tail_launch(a, (hipStream_t)stream);
 }
 
 extern "C" int jh_shard_merge(const float* recs, int G, int K, int nu, int mode, float lambda, int k, int tie_high, int E, int row_floats, float* nominal_out,

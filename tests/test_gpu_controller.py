@@ -341,24 +341,22 @@ def test_full_size_configs_properties(gpu, task_name, opt_name, N, H):
 @pytest.mark.parametrize("task_name,opt_name,N", [("cartpole", "mppi", 4096), ("cylinder_push", "mppi", 1000), ("cartpole", "ps", 300), ("fr3_pick", "cem", 257), ("leap_cube", "mppi", 64),
                                                   ("cartpole", "cem", 3)])
 def test_fused_update_is_bit_identical_to_the_separate_kernels(gpu, task_name, opt_name, N):
-    """jh_update_fused (one launch: block partials, merge, trace elites; one download) against jh_mppi_partial / jh_topk_partial + merge + jh_trace_gather: three consecutive
-    plan steps give the same nominal, sigma, costs and trace segments bit for bit (ragged last workgroup, fewer rollouts than trace elites, every optimizer)."""
+    """jh_update_fused (one launch: block partials, merge, trace elites; one wait) against jh_mppi_partial / jh_topk_partial + merge + jh_trace_gather: three consecutive
+    plan steps give the same nominal, sigma, costs and trace segments bit for bit (ragged last workgroup, fewer rollouts than trace elites, every optimizer).  Twice: the
+    default path (jh_plan_step, one call, results written into the pinned host block; cartpole / cylinder_push: ONE launch that reads its host block in place, completion
+    word polled) against the separate kernels, and the materialise path's rollout followed by jh_update_fused against the same rollout followed by the separate kernels."""
     import torch
 
     from judo_amd.controller import make_controller
 
-    outs = []
-    # jh_plan_step (one call, results written into the pinned host block; cartpole / cylinder_push: ONE launch that reads its host block in place; completion word polled) /
-    # the same call with the uploaded block and the stream's event / jh_update_fused + download / separate kernels
-    for fused, zero_copy, lean in ((True, True, True), (True, True, False), (True, False, False), (False, False, False)):
+    def run(fused: bool, materialize: bool) -> list:
         ctrl = make_controller(task_name, opt_name)
-        ctrl.poll_completion = ctrl.host_block_in_place = lean
         ctrl.optimizer.config.num_rollouts = N
         ctrl.reset()
         ctrl.current_state = ctrl.task.default_state()
         ctrl.optimizer.seed(21)
-        ctrl.fused_update, ctrl.zero_copy_out = fused, zero_copy
-        ctrl.record_kernel_events = fused and zero_copy  # (the timing events recorded inside the one-call path)
+        ctrl.fused_update, ctrl.force_materialize = fused, materialize
+        ctrl.record_kernel_events = fused  # (the timing events recorded inside the one-call path, and around the rollout and jh_update_fused)
         rec = []
         for step in range(3):
             ctrl.time = 0.05 * step
@@ -366,11 +364,12 @@ def test_fused_update_is_bit_identical_to_the_separate_kernels(gpu, task_name, o
             tr = ctrl.traces
             rec.append((ctrl.nominal_knots.copy(), np.array(getattr(ctrl.optimizer, "sigma", 0.0)).copy(), ctrl.costs_device.cpu().numpy().copy(), None if tr is None else tr.copy()))
         torch.cuda.synchronize()
-        outs.append(rec)
         if ctrl.record_kernel_events:
-            assert len(ctrl.kernel_events) == 3 and all(0.0 < a.elapsed_time(b) < 1e4 for a, b in ctrl.kernel_events)
-    for other in outs[1:]:
-        for a, b in zip(outs[0], other):
+            assert len(ctrl.kernel_events) == len(ctrl.exchange_events) == 3 and all(0.0 < a.elapsed_time(b) < 1e4 for a, b in ctrl.kernel_events)
+        return rec
+
+    for materialize in (False, True):
+        for a, b in zip(run(True, materialize), run(False, materialize)):
             assert np.array_equal(a[0], b[0]) and np.array_equal(a[1], b[1]) and np.array_equal(a[2], b[2])
             assert (a[3] is None) == (b[3] is None) and (a[3] is None or (a[3].shape == b[3].shape and np.array_equal(a[3], b[3])))
             assert np.isfinite(a[0]).all()
