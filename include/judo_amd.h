@@ -267,8 +267,9 @@ int jh_policy_step(const jh_policy* p, const float* states, int ld, int nq, int 
 
 /* ---- physics half of the Spot policy rollout (System::rollout's inner mj_step loop, mujoco_extensions/system/system_class.cpp:300-318): advance
  * N rollouts of a floating-base robot on a ground plane by `substeps` engine steps with the control held.  The model image is what
- * judo_amd/tree_model.py packs (free base + 19 hinges in 5 chains, plane contacts, pyramidal cones, implicitfast; optionally ONE free box, spot_box).  state_in / state_out are
- * (N x (nq + nv)) rows [qpos(nq), qvel(nv)] and may alias -- nq / nv = 26 / 25, with the box 33 / 31 (its qpos / qvel after the robot's; jh_tree_dims);
+ * judo_amd/tree_model.py packs (free base + 19 hinges in 5 chains, plane contacts, pyramidal cones, implicitfast; optionally ONE free object: a box, spot_box, or a
+ * cylinder, spot_tire; jh_tree_create refuses any other object shape).  state_in / state_out are
+ * (N x (nq + nv)) rows [qpos(nq), qvel(nv)] and may alias -- nq / nv = 26 / 25, with the object 33 / 31 (its qpos / qvel after the robot's; jh_tree_dims);
  * ctrl is (N x 19) joint position targets; warmstart (N x nv, may be NULL) is the solver's
  * starting acceleration, read and overwritten with this call's last constraint-consistent acceleration (mjData.qacc_warmstart).  sensors_out (N x nsensordata,
  * may be NULL): mjData.sensordata as mj_step leaves it after the last step, i.e. the site positions / frame axes of that step's forward pass.

@@ -313,6 +313,213 @@ __device__ __forceinline__ void collide_box_capsule(Sink& sk, const float* pb, c
   }
 }
 
+// ---- a cylinder (radius r, half length L along the local z of Rc) against the robot's geoms: the spot_tire object (csrc/jh_engine_v4.hip, k_tree_v4<SELF, true, true>)
+
+// sphere against cylinder (MuJoCo's primitive mjc_SphereCylinder, as the oracle restates it in collide_cylinder_sphere): the closest point of the solid cylinder to the
+// centre (side, cap or rim), the normal from the cylinder to the sphere along that line, position midway through the overlap; a centre inside leaves through the nearer
+// of side and cap
+template <class Sink>
+__device__ __forceinline__ void collide_cylinder_sphere(Sink& sk, const float* pc, const float* Rc, float r, float L, const float* ps, float rs) {
+  float ax[3]; col3(ax, Rc, 2);
+  const float v[3] = {ps[0] - pc[0], ps[1] - pc[1], ps[2] - pc[2]};
+  const float x = dot3(v, ax);
+  const float rad[3] = {v[0] - x * ax[0], v[1] - x * ax[1], v[2] - x * ax[2]};
+  const float rl = sqrtf(dot3(rad, rad));
+  float er[3];
+  if (rl > 1e-7f) { er[0] = rad[0] / rl; er[1] = rad[1] / rl; er[2] = rad[2] / rl; }
+  else {  // centre on the axis: any radial direction
+    const float t[3] = {fabsf(ax[0]) > 0.9f ? 0.f : 1.f, fabsf(ax[0]) > 0.9f ? 1.f : 0.f, 0.f};
+    cross3(er, ax, t); const float l = sqrtf(dot3(er, er)); er[0] /= l; er[1] /= l; er[2] /= l;
+  }
+  const float sx = x >= 0.f ? 1.f : -1.f;
+  float n[3], cp[3], dist;
+  if (fabsf(x) <= L && rl <= r) {  // centre inside
+    const float dside = r - rl, dcap = L - fabsf(x);
+    if (dside <= dcap) { for (int k = 0; k < 3; k++) { n[k] = er[k]; cp[k] = pc[k] + x * ax[k] + r * er[k]; } dist = -dside - rs; }
+    else { for (int k = 0; k < 3; k++) { n[k] = sx * ax[k]; cp[k] = pc[k] + sx * L * ax[k] + rl * er[k]; } dist = -dcap - rs; }
+  } else {
+    const float cx = fabsf(x) > L ? sx * L : x, cr = rl > r ? r : rl;
+    for (int k = 0; k < 3; k++) cp[k] = pc[k] + cx * ax[k] + cr * er[k];
+    const float dv[3] = {ps[0] - cp[0], ps[1] - cp[1], ps[2] - cp[2]};
+    const float l = sqrtf(dot3(dv, dv));
+    if (l < 1e-7f) return;
+    for (int k = 0; k < 3; k++) n[k] = dv[k] / l;
+    dist = l - rs;
+  }
+  if (dist >= 0.f) return;
+  const float pos[3] = {cp[0] + n[0] * 0.5f * dist, cp[1] + n[1] * 0.5f * dist, cp[2] + n[2] * 0.5f * dist};
+  sk.push(pos, n, dist);
+}
+
+// A capsule (type 3) or a box (type 6) against the cylinder: MuJoCo sends these pairs through its general convex collider (mjc_Convex, GJK + EPA), which gives ONE contact
+// of minimum translation -- depth, normal from geom 1 to geom 2, position midway between the two witness points.  The oracle restates it in double precision
+// (collide_convex, oracle/jo_engine.c).  This is the same algorithm in fp32 with a BOUNDED polytope, chosen over exact special cases because box-cylinder has no closed form
+// (its minimum translation can lie along a curved face of the Minkowski difference) and capsule-cylinder would need one per feature pair.  Worst case per lane: GJK at most
+// CVX_GJK_IT = 48 support steps; EPA at most CVX_MAXV - 4 = 36 expansions of a polytope of at most CVX_MAXV = 40 vertices and 2 CVX_MAXV = 80 faces (a closed
+// triangulation of V vertices has 2V - 4), each expansion O(faces).  The polytope lives in the lane's private memory (about 2.6 KB, scratch), not in LDS.  It stops when
+// the closest face is a supporting plane within CVX_TOL = 1e-6 (m); a curved contact that needs more than 36 expansions keeps the closest face found so far, whose
+// depth is then below the true one by less than the last expansion's growth.  Where the closest feature is not unique (parallel faces or edges) the witness points --
+// and so the position -- may differ from the oracle's within that feature; depth and normal do not.
+constexpr int CVX_MAXV = 40, CVX_MAXF = 2 * CVX_MAXV, CVX_GJK_IT = 48;
+constexpr float CVX_TOL = 1e-6f;
+struct CvxShape { int type; float s0, s1, s2; float p[3], R[9]; };
+__device__ __forceinline__ void cvx_support(const CvxShape& s, const float* d, float* out) {
+  out[0] = s.p[0]; out[1] = s.p[1]; out[2] = s.p[2];
+  if (s.type == 6) {
+    const float h[3] = {s.s0, s.s1, s.s2};
+#pragma unroll
+    for (int k = 0; k < 3; k++) {
+      float ax[3]; col3(ax, s.R, k); const float e = dot3(d, ax) >= 0.f ? h[k] : -h[k];
+      out[0] = fmaf(ax[0], e, out[0]); out[1] = fmaf(ax[1], e, out[1]); out[2] = fmaf(ax[2], e, out[2]);
+    }
+  } else {  // capsule or cylinder: the end of the axis segment that faces d, then the radius -- all of it (capsule) or its part across the axis (cylinder)
+    float ax[3]; col3(ax, s.R, 2);
+    const float da = dot3(d, ax), e = da >= 0.f ? s.s1 : -s.s1;
+    out[0] = fmaf(ax[0], e, out[0]); out[1] = fmaf(ax[1], e, out[1]); out[2] = fmaf(ax[2], e, out[2]);
+    float r[3] = {d[0], d[1], d[2]};
+    if (s.type == 5) { r[0] -= da * ax[0]; r[1] -= da * ax[1]; r[2] -= da * ax[2]; }
+    const float l = sqrtf(dot3(r, r));
+    if (l > 1e-7f * (fabsf(da) + l)) { const float k = s.s0 / l; out[0] = fmaf(r[0], k, out[0]); out[1] = fmaf(r[1], k, out[1]); out[2] = fmaf(r[2], k, out[2]); }
+  }
+}
+struct CvxVert { float w[3], a[3]; };  // w = a - b on the Minkowski difference A - B; a the support point of A (b follows)
+__device__ __forceinline__ void cvx_vertex(const CvxShape& A, const CvxShape& B, const float* d, CvxVert& v) {
+  const float nd[3] = {-d[0], -d[1], -d[2]};
+  float b[3];
+  cvx_support(A, d, v.a); cvx_support(B, nd, b);
+  v.w[0] = v.a[0] - b[0]; v.w[1] = v.a[1] - b[1]; v.w[2] = v.a[2] - b[2];
+}
+struct CvxFace { float n[3], dist; int v; };  // v: vertex indices 0-7 / 8-15 / 16-23, bit 31 dead
+__device__ __forceinline__ bool cvx_face(const CvxVert* V, int i, int j, int k, CvxFace& f) {
+  const float e1[3] = {V[j].w[0] - V[i].w[0], V[j].w[1] - V[i].w[1], V[j].w[2] - V[i].w[2]}, e2[3] = {V[k].w[0] - V[i].w[0], V[k].w[1] - V[i].w[1], V[k].w[2] - V[i].w[2]};
+  cross3(f.n, e1, e2);
+  const float l = sqrtf(dot3(f.n, f.n));
+  if (!(l > 1e-18f)) return false;
+  f.n[0] /= l; f.n[1] /= l; f.n[2] /= l;
+  f.dist = dot3(f.n, V[i].w);
+  f.v = i | (j << 8) | (k << 16);
+  if (f.dist < 0.f) { f.dist = -f.dist; f.n[0] = -f.n[0]; f.n[1] = -f.n[1]; f.n[2] = -f.n[2]; f.v = i | (k << 8) | (j << 16); }
+  return true;
+}
+// GJK on A - B, overlap only (the oracle's ccd_gjk): true with four vertices around the origin in sx[0..3]
+__device__ __forceinline__ bool cvx_gjk(const CvxShape& A, const CvxShape& B, CvxVert* sx) {
+  float d[3] = {B.p[0] - A.p[0], B.p[1] - A.p[1], B.p[2] - A.p[2]};
+  if (dot3(d, d) < 1e-20f) { d[0] = 1.f; d[1] = 0.f; d[2] = 0.f; }
+  int n = 1;
+  cvx_vertex(A, B, d, sx[0]);
+  d[0] = -sx[0].w[0]; d[1] = -sx[0].w[1]; d[2] = -sx[0].w[2];
+  for (int it = 0; it < CVX_GJK_IT; it++) {
+    if (dot3(d, d) < 1e-24f) {  // the origin lies on the simplex: any direction that grows it
+      float e[3] = {1.f, 0.f, 0.f};
+      if (n >= 2) {
+        const float ab[3] = {sx[1].w[0] - sx[0].w[0], sx[1].w[1] - sx[0].w[1], sx[1].w[2] - sx[0].w[2]};
+        float t[3] = {0.f, 1.f, 0.f}; cross3(e, ab, t);
+        if (dot3(e, e) < 1e-20f) { t[1] = 0.f; t[2] = 1.f; cross3(e, ab, t); }
+      }
+      d[0] = e[0]; d[1] = e[1]; d[2] = e[2];
+    }
+    CvxVert nv; cvx_vertex(A, B, d, nv);
+    if (dot3(nv.w, d) < 0.f) return false;  // the new support point did not pass the origin: separated
+    sx[3] = sx[2]; sx[2] = sx[1]; sx[1] = sx[0]; sx[0] = nv; n++;
+    const float* a = sx[0].w; const float* b = sx[1].w;
+    const float ao[3] = {-a[0], -a[1], -a[2]}, ab[3] = {b[0] - a[0], b[1] - a[1], b[2] - a[2]};
+    if (n == 2) {
+      if (dot3(ab, ao) > 0.f) { float t[3]; cross3(t, ab, ao); cross3(d, t, ab); } else { n = 1; d[0] = ao[0]; d[1] = ao[1]; d[2] = ao[2]; }
+    } else if (n == 3) {
+      const float* c = sx[2].w;
+      const float ac[3] = {c[0] - a[0], c[1] - a[1], c[2] - a[2]};
+      float abc[3], t[3]; cross3(abc, ab, ac); cross3(t, abc, ac);
+      if (dot3(t, ao) > 0.f) {
+        if (dot3(ac, ao) > 0.f) { sx[1] = sx[2]; n = 2; float u[3]; cross3(u, ac, ao); cross3(d, u, ac); }
+        else if (dot3(ab, ao) > 0.f) { n = 2; float u[3]; cross3(u, ab, ao); cross3(d, u, ab); }
+        else { n = 1; d[0] = ao[0]; d[1] = ao[1]; d[2] = ao[2]; }
+      } else {
+        cross3(t, ab, abc);
+        if (dot3(t, ao) > 0.f) {
+          if (dot3(ab, ao) > 0.f) { n = 2; float u[3]; cross3(u, ab, ao); cross3(d, u, ab); } else { n = 1; d[0] = ao[0]; d[1] = ao[1]; d[2] = ao[2]; }
+        } else if (dot3(abc, ao) > 0.f) { d[0] = abc[0]; d[1] = abc[1]; d[2] = abc[2]; }
+        else { const CvxVert tmp = sx[1]; sx[1] = sx[2]; sx[2] = tmp; d[0] = -abc[0]; d[1] = -abc[1]; d[2] = -abc[2]; }
+      }
+    } else {  // tetrahedron: which face through the new vertex, if any, sees the origin
+      const float* c = sx[2].w; const float* dd = sx[3].w;
+      const float ac[3] = {c[0] - a[0], c[1] - a[1], c[2] - a[2]}, ad[3] = {dd[0] - a[0], dd[1] - a[1], dd[2] - a[2]};
+      float abc[3], acd[3], adb[3]; cross3(abc, ab, ac); cross3(acd, ac, ad); cross3(adb, ad, ab);
+      if (dot3(abc, ad) > 0.f) { abc[0] = -abc[0]; abc[1] = -abc[1]; abc[2] = -abc[2]; }
+      if (dot3(acd, ab) > 0.f) { acd[0] = -acd[0]; acd[1] = -acd[1]; acd[2] = -acd[2]; }
+      if (dot3(adb, ac) > 0.f) { adb[0] = -adb[0]; adb[1] = -adb[1]; adb[2] = -adb[2]; }
+      if (dot3(abc, ao) > 0.f) { n = 3; d[0] = abc[0]; d[1] = abc[1]; d[2] = abc[2]; }
+      else if (dot3(acd, ao) > 0.f) { sx[1] = sx[2]; sx[2] = sx[3]; n = 3; d[0] = acd[0]; d[1] = acd[1]; d[2] = acd[2]; }
+      else if (dot3(adb, ao) > 0.f) { sx[2] = sx[1]; sx[1] = sx[3]; n = 3; d[0] = adb[0]; d[1] = adb[1]; d[2] = adb[2]; }
+      else return true;
+    }
+  }
+  return false;
+}
+// geom A (capsule / box) against geom B (the cylinder): at most one contact, normal from A to B
+template <class Sink>
+__device__ __noinline__ void collide_convex_cylinder(Sink& sk, const CvxShape& A, const CvxShape& B) {
+  CvxVert V[CVX_MAXV];
+  CvxFace F[CVX_MAXF];
+  int ed[CVX_MAXF];
+  if (!cvx_gjk(A, B, V)) return;
+  int nv = 4, nf = 0;
+  {
+    const int idx[4][3] = {{0, 1, 2}, {0, 2, 3}, {0, 3, 1}, {1, 3, 2}};
+    for (int f = 0; f < 4; f++) {
+      if (!cvx_face(V, idx[f][0], idx[f][1], idx[f][2], F[nf])) return;  // a flat simplex: touching without volume
+      const int opp = 6 - idx[f][0] - idx[f][1] - idx[f][2];
+      if (dot3(F[nf].n, V[opp].w) - F[nf].dist > 0.f) {  // the opposite vertex must lie behind the face
+        F[nf].n[0] = -F[nf].n[0]; F[nf].n[1] = -F[nf].n[1]; F[nf].n[2] = -F[nf].n[2]; F[nf].dist = -F[nf].dist;
+        F[nf].v = idx[f][0] | (idx[f][2] << 8) | (idx[f][1] << 16);
+      }
+      nf++;
+    }
+  }
+  int best = -1;
+  for (int it = 0; it < CVX_MAXV; it++) {
+    best = -1;
+    for (int f = 0; f < nf; f++) if (F[f].v >= 0 && (best < 0 || F[f].dist < F[best].dist)) best = f;
+    if (best < 0) return;
+    CvxVert nw; cvx_vertex(A, B, F[best].n, nw);
+    if (dot3(nw.w, F[best].n) - F[best].dist < CVX_TOL || nv >= CVX_MAXV) break;
+    int ne = 0;  // the faces the new point sees go; their unshared edges form the horizon
+    for (int f = 0; f < nf; f++) {
+      if (F[f].v < 0 || dot3(F[f].n, nw.w) - F[f].dist <= 0.f) continue;
+      const int fv = F[f].v;
+      F[f].v = fv | (1 << 31);
+      for (int e = 0; e < 3; e++) {
+        const int a = (fv >> (8 * e)) & 255, b = (fv >> (8 * ((e + 1) % 3))) & 255;
+        int found = -1;
+        for (int q = 0; q < ne; q++) if (ed[q] == (b | (a << 8))) { found = q; break; }
+        if (found >= 0) ed[found] = ed[--ne];
+        else if (ne < CVX_MAXF) ed[ne++] = a | (b << 8);
+      }
+    }
+    if (ne == 0) break;  // numerically on the surface already
+    V[nv] = nw;
+    int k = 0;
+    for (int f = 0; f < nf; f++) if (F[f].v >= 0) { if (k != f) F[k] = F[f]; k++; }
+    nf = k;
+    for (int e = 0; e < ne && nf < CVX_MAXF; e++) if (cvx_face(V, ed[e] & 255, ed[e] >> 8, nv, F[nf])) nf++;
+    nv++;
+    best = -1;
+  }
+  if (best < 0) return;
+  const CvxFace f = F[best];
+  const CvxVert& a = V[f.v & 255]; const CvxVert& b = V[(f.v >> 8) & 255]; const CvxVert& c = V[(f.v >> 16) & 255];
+  const float pr[3] = {f.n[0] * f.dist, f.n[1] * f.dist, f.n[2] * f.dist};
+  float v0[3], v1[3], v2[3];
+  for (int k = 0; k < 3; k++) { v0[k] = b.w[k] - a.w[k]; v1[k] = c.w[k] - a.w[k]; v2[k] = pr[k] - a.w[k]; }
+  const float d00 = dot3(v0, v0), d01 = dot3(v0, v1), d11 = dot3(v1, v1), d20 = dot3(v2, v0), d21 = dot3(v2, v1), den = d00 * d11 - d01 * d01;
+  const float bv = den > 1e-30f ? (d11 * d20 - d01 * d21) / den : 0.f, bw = den > 1e-30f ? (d00 * d21 - d01 * d20) / den : 0.f, bu = 1.f - bv - bw;
+  float pos[3];
+  for (int k = 0; k < 3; k++) {  // midway between the witness points wa = sum a, wb = wa - sum w
+    const float wa = bu * a.a[k] + bv * b.a[k] + bw * c.a[k], ww = bu * a.w[k] + bv * b.w[k] + bw * c.w[k];
+    pos[k] = wa - 0.5f * ww;
+  }
+  sk.push(pos, f.n, -f.dist);
+}
+
 // signed box-box distance = largest separation over the 15 SAT axes (exact when a face or an edge pair is closest; see the oracle)
 __device__ __forceinline__ float box_box_distance(const float* p1, const float* R1, const float* h1, const float* p2, const float* R2, const float* h2) {
   float A[3][3], B[3][3], dv[3], best = -1e30f;

@@ -29,6 +29,11 @@
 // its Cholesky factor, every robot row and the right-hand side updated by the lanes that own them), the robot system keeps its size and -- as long as the box touches at most
 // one chain in the step -- its tree structure; a rollout whose box touches two chains takes the dense 25 x 25 path for that step.  The box part of the solution follows from
 // the robot part.  State rows: nq = 33 (robot 26, box 7), nv = 31 (robot 25, box 6), stride 64.
+//
+// spot_tire (judo/models/xml/spot_tire/robot.xml, the tire's meshes standing in as the reference's own cylinder): the same free object with a CYLINDER geom, template
+// parameter CYL (its own instantiation: the box and robot-only ones compile as before).  Only the narrow phase differs: PlaneCylinder on lane 31, and per robot geom
+// jh_coop.h's cylinder-sphere (MuJoCo's primitive) or the bounded fp32 GJK + EPA for capsules and boxes (MuJoCo's general convex collider); normals from the robot geom
+// to the tire, as for the box.
 #include <cstddef>
 #include "jh_coop.h"
 
@@ -473,7 +478,7 @@ __device__ __forceinline__ float dot_row(const float* Mrow, const float* v) {
 }
 
 
-template <bool SELF, bool OBJ = false>
+template <bool SELF, bool OBJ = false, bool CYL = false>
 __global__ __launch_bounds__(WAVE, 1) void k_tree_v4(const float* __restrict__ gF, const int* __restrict__ gI, int nF, int nI, const float* state_in, int ld_in,
                                                     const float* __restrict__ ctrl, float* __restrict__ warm, int N, int substeps, float* state_out, int ld_out,
                                                     float* __restrict__ sensors_out, int ld_sens, int* __restrict__ stats, int dshift) {
@@ -491,7 +496,7 @@ __global__ __launch_bounds__(WAVE, 1) void k_tree_v4(const float* __restrict__ g
   if constexpr (OBJ) {  // the box's geom record goes where geom ng's would be: geom index ng names the box in the contact records (owner -3)
     const int og = TH_F + NJ * TD_F + sI[1] * TG_F, oo = gI[9];
     for (int i = lane; i < TG_F; i += WAVE) sF[og + i] = gF[oo + OB_G + i];
-    if (lane == 0) { sI[TH_I + NJ * TD_I + sI[1] * TG_I] = -3; sI[TH_I + NJ * TD_I + sI[1] * TG_I + 1] = 6; }
+    if (lane == 0) { sI[TH_I + NJ * TD_I + sI[1] * TG_I] = -3; sI[TH_I + NJ * TD_I + sI[1] * TG_I + 1] = CYL ? 5 : 6; }
     __syncthreads();
   }
   // (latency mode, jh_internal.h: with dshift = 1 both rows of the wave compute the same rollout and the first writes -- the shipped 24-rollout plans)
@@ -957,25 +962,27 @@ __global__ __launch_bounds__(WAVE, 1) void k_tree_v4(const float* __restrict__ g
         mulMV(bp, Ro, bf + GF4_POS); for (int i = 0; i < 3; i++) bp[i] += c[i];
         mulMM(bR, Ro, bf + GF4_R);
       }
-      if (l == G - 1) {  // PlaneBox: corners in MuJoCo's order, at most 4 contacts; [4] = the box (geom B = ng), the plane as geom A
-        const float pr[3] = {plp[0] - qb[0], plp[1] - qb[1], plp[2] - qb[2]};
-        const float hs[3] = {bf[GF4_SIZE], bf[GF4_SIZE + 1], bf[GF4_SIZE + 2]};
-        const float dif[3] = {bp[0] - pr[0], bp[1] - pr[1], bp[2] - pr[2]};
-        const float dist0 = dot3(dif, pln);
-        int cnt = 0;
-        for (int i = 0; i < 8; i++) {
-          const float vl[3] = {(i & 1) ? hs[0] : -hs[0], (i & 2) ? hs[1] : -hs[1], (i & 4) ? hs[2] : -hs[2]};
-          float vec3[3]; mulMV(vec3, bR, vl);
-          const float d = dist0 + dot3(pln, vec3);
-          if (d <= 0.f && cnt < 4) {
-            const int ic = atomicAdd(&S.ncon, 1);
-            if (ic >= NCP) { if (stats && live) atomicAdd(stats, 1); }
-            else {
-              float* e = S.raw[ic];
-              e[0] = bp[0] + vec3[0] - pln[0] * 0.5f * d; e[1] = bp[1] + vec3[1] - pln[1] * 0.5f * d; e[2] = bp[2] + vec3[2] - pln[2] * 0.5f * d;
-              e[3] = d; e[4] = __int_as_float(ng); e[5] = e[6] = e[7] = 0.f;
+      if constexpr (!CYL) {
+        if (l == G - 1) {  // PlaneBox: corners in MuJoCo's order, at most 4 contacts; [4] = the box (geom B = ng), the plane as geom A
+          const float pr[3] = {plp[0] - qb[0], plp[1] - qb[1], plp[2] - qb[2]};
+          const float hs[3] = {bf[GF4_SIZE], bf[GF4_SIZE + 1], bf[GF4_SIZE + 2]};
+          const float dif[3] = {bp[0] - pr[0], bp[1] - pr[1], bp[2] - pr[2]};
+          const float dist0 = dot3(dif, pln);
+          int cnt = 0;
+          for (int i = 0; i < 8; i++) {
+            const float vl[3] = {(i & 1) ? hs[0] : -hs[0], (i & 2) ? hs[1] : -hs[1], (i & 4) ? hs[2] : -hs[2]};
+            float vec3[3]; mulMV(vec3, bR, vl);
+            const float d = dist0 + dot3(pln, vec3);
+            if (d <= 0.f && cnt < 4) {
+              const int ic = atomicAdd(&S.ncon, 1);
+              if (ic >= NCP) { if (stats && live) atomicAdd(stats, 1); }
+              else {
+                float* e = S.raw[ic];
+                e[0] = bp[0] + vec3[0] - pln[0] * 0.5f * d; e[1] = bp[1] + vec3[1] - pln[1] * 0.5f * d; e[2] = bp[2] + vec3[2] - pln[2] * 0.5f * d;
+                e[3] = d; e[4] = __int_as_float(ng); e[5] = e[6] = e[7] = 0.f;
+              }
+              cnt++;
             }
-            cnt++;
           }
         }
       }
@@ -998,9 +1005,58 @@ __global__ __launch_bounds__(WAVE, 1) void k_tree_v4(const float* __restrict__ g
         const float d[3] = {bp[0] - gp[0], bp[1] - gp[1], bp[2] - gp[2]}, rs = gf[GF4_RBOUND] + bf[GF4_RBOUND];
         if (dot3(d, d) <= rs * rs) {  // (mj_collideGeoms' bounding-sphere filter)
           ObjSink sk{&S, live ? stats : nullptr, g | (ng << 8), false};
-          if (gt == 6) collide_box_box(sk, gp, gR, gf + GF4_SIZE, bp, bR, bf + GF4_SIZE);
-          else if (gt == 2) { sk.flip = true; collide_box_sphere(sk, bp, bR, bf + GF4_SIZE, gp, gf[GF4_SIZE]); }
-          else { sk.flip = true; collide_box_capsule(sk, bp, bR, bf + GF4_SIZE, gp, gR, gf[GF4_SIZE], gf[GF4_SIZE + 1]); }
+          if constexpr (CYL) {
+            if (gt == 2) { sk.flip = true; collide_cylinder_sphere(sk, bp, bR, bf[GF4_SIZE], bf[GF4_SIZE + 1], gp, gf[GF4_SIZE]); }
+            else {
+              CvxShape A{gt, gf[GF4_SIZE], gf[GF4_SIZE + 1], gf[GF4_SIZE + 2], {gp[0], gp[1], gp[2]}, {}}, B{5, bf[GF4_SIZE], bf[GF4_SIZE + 1], 0.f, {bp[0], bp[1], bp[2]}, {}};
+              for (int i = 0; i < 9; i++) { A.R[i] = gR[i]; B.R[i] = bR[i]; }
+              collide_convex_cylinder(sk, A, B);
+            }
+          } else {
+            if (gt == 6) collide_box_box(sk, gp, gR, gf + GF4_SIZE, bp, bR, bf + GF4_SIZE);
+            else if (gt == 2) { sk.flip = true; collide_box_sphere(sk, bp, bR, bf + GF4_SIZE, gp, gf[GF4_SIZE]); }
+            else { sk.flip = true; collide_box_capsule(sk, bp, bR, bf + GF4_SIZE, gp, gR, gf[GF4_SIZE], gf[GF4_SIZE + 1]); }
+          }
+        }
+      }
+      if constexpr (CYL) {
+        if (l == G - 1) {  // PlaneCylinder (MuJoCo's mjc_PlaneCylinder), the plane as geom A, at most 4 contacts: the deepest rim point, the other end of its generator line,
+                           // then -- when the near disk touches -- the two other corners of an equilateral triangle inscribed in that disk's rim
+          const float pr[3] = {plp[0] - qb[0], plp[1] - qb[1], plp[2] - qb[2]};
+          const float rad = bf[GF4_SIZE], hl = bf[GF4_SIZE + 1];
+          float ax[3] = {bR[2], bR[5], bR[8]};
+          float prjaxis = dot3(pln, ax);
+          if (prjaxis > 0.f) { ax[0] = -ax[0]; ax[1] = -ax[1]; ax[2] = -ax[2]; prjaxis = -prjaxis; }  // the axis points toward the plane
+          const float dif[3] = {bp[0] - pr[0], bp[1] - pr[1], bp[2] - pr[2]};
+          const float dist0 = dot3(dif, pln);
+          float vec[3] = {ax[0] * prjaxis - pln[0], ax[1] * prjaxis - pln[1], ax[2] * prjaxis - pln[2]};  // -normal without its part along the axis
+          const float lsq = dot3(vec, vec);
+          if (lsq >= 1e-12f) { const float k = rad * rsqrtf(lsq); vec[0] *= k; vec[1] *= k; vec[2] *= k; }
+          else { vec[0] = bR[0] * rad; vec[1] = bR[3] * rad; vec[2] = bR[6] * rad; }  // disk parallel to the plane: the cylinder's x axis
+          const float prjvec = dot3(vec, pln);
+          ax[0] *= hl; ax[1] *= hl; ax[2] *= hl; prjaxis *= hl;
+          const float zero[3] = {0.f, 0.f, 0.f};
+          auto emit = [&](float d, const float* o1, float s1, const float* o2, float s2) {
+            const float pos[3] = {bp[0] + vec[0] * s1 + o1[0] + o2[0] * s2 - pln[0] * 0.5f * d, bp[1] + vec[1] * s1 + o1[1] + o2[1] * s2 - pln[1] * 0.5f * d,
+                                  bp[2] + vec[2] * s1 + o1[2] + o2[2] * s2 - pln[2] * 0.5f * d};
+            const int i = atomicAdd(&S.ncon, 1);
+            if (i >= NCP) { if (stats && live) atomicAdd(stats, 1); return; }
+            float* e = S.raw[i];
+            e[0] = pos[0]; e[1] = pos[1]; e[2] = pos[2]; e[3] = d; e[4] = __int_as_float(ng); e[5] = e[6] = e[7] = 0.f;
+          };
+          const float d1 = dist0 + prjaxis + prjvec;
+          if (d1 <= 0.f) {
+            emit(d1, ax, 1.f, zero, 0.f);
+            const float d2 = dist0 - prjaxis + prjvec;
+            if (d2 <= 0.f) { const float nax[3] = {-ax[0], -ax[1], -ax[2]}; emit(d2, nax, 1.f, zero, 0.f); }
+            const float d3 = dist0 + prjaxis - 0.5f * prjvec;
+            if (d3 <= 0.f) {
+              float v1[3]; cross3(v1, vec, ax);
+              const float k = rad * 0.8660254037844386f * rsqrtf(dot3(v1, v1)); v1[0] *= k; v1[1] *= k; v1[2] *= k;
+              emit(d3, ax, -0.5f, v1, 1.f);
+              emit(d3, ax, -0.5f, v1, -1.f);
+            }
+          }
         }
       }
     }
@@ -1454,14 +1510,19 @@ __global__ __launch_bounds__(WAVE, 1) void k_tree_v4(const float* __restrict__ g
 
 }  // namespace
 
-struct jh_tree { float* d_f; int* d_i; int* d_stats; int nj, ng, nq, nv, nf, ni, ns, npair, self_collision, nobj; std::vector<hipEvent_t> events; };
+struct jh_tree { float* d_f; int* d_i; int* d_stats; int nj, ng, nq, nv, nf, ni, ns, npair, self_collision, nobj, ocyl; std::vector<hipEvent_t> events; };
 
 namespace {
-// the instantiation for the image (a free box or not) and the self-collision switch; states rows of nq + nv floats
+// the instantiation for the image (a free box, a free cylinder or neither) and the self-collision switch; states rows of nq + nv floats
 void launch_tree(const jh_tree* t, hipStream_t st, const float* xin, int ld_in, const float* ctrl, float* warm, int N, int substeps, float* xout, int ld_out, float* sens, int ld_sens) {
   const int dshift = jh_latency_shift(N, RPW), per_wave = RPW >> dshift;
   const dim3 grid((N + per_wave - 1) / per_wave), block(WAVE);
-  if (t->nobj) {
+  if (t->nobj && t->ocyl) {
+    if (t->self_collision)
+      hipLaunchKernelGGL((k_tree_v4<true, true, true>), grid, block, 0, st, t->d_f, t->d_i, t->nf, t->ni, xin, ld_in, ctrl, warm, N, substeps, xout, ld_out, sens, ld_sens, t->d_stats, dshift);
+    else
+      hipLaunchKernelGGL((k_tree_v4<false, true, true>), grid, block, 0, st, t->d_f, t->d_i, t->nf, t->ni, xin, ld_in, ctrl, warm, N, substeps, xout, ld_out, sens, ld_sens, t->d_stats, dshift);
+  } else if (t->nobj) {
     if (t->self_collision)
       hipLaunchKernelGGL((k_tree_v4<true, true>), grid, block, 0, st, t->d_f, t->d_i, t->nf, t->ni, xin, ld_in, ctrl, warm, N, substeps, xout, ld_out, sens, ld_sens, t->d_stats, dshift);
     else
@@ -1483,7 +1544,7 @@ extern "C" int jh_tree_create(const void* blob, size_t nbytes, jh_tree** out) {
   const int nobj = ii[8];
   JH_REQUIRE(nobj == 0 || nobj == 1, "tree_create: the kernel carries at most one free object besides the robot (the image has %d)", nobj);
   JH_REQUIRE(ii[0] == NJ && ii[2] == (nobj ? NQO : NQ) && ii[3] == (nobj ? NVO : NVT) && ii[1] <= G - 1 - nobj,
-             "tree_create: the kernel is instantiated for a free base + 19 hinges [+ one free box] (got %d joints, nq %d, nv %d, %d geoms, %d objects)", ii[0], ii[2], ii[3], ii[1], nobj);
+             "tree_create: the kernel is instantiated for a free base + 19 hinges [+ one free box or cylinder] (got %d joints, nq %d, nv %d, %d geoms, %d objects)", ii[0], ii[2], ii[3], ii[1], nobj);
   JH_REQUIRE((size_t)(TH_F + ii[0] * TD_F + (ii[1] + nobj) * TG_F) <= (size_t)SF_MAX && (size_t)(TH_I + ii[0] * TD_I + (ii[1] + nobj) * TG_I) <= (size_t)SI_MAX,
              "tree_create: model image too large for the kernel's LDS copy");
   const size_t nf0 = (size_t)(TH_F + ii[0] * TD_F + ii[1] * TG_F + ii[4] * TS_F), ni0 = (size_t)(TH_I + ii[0] * TD_I + ii[1] * TG_I + ii[4] * TS_I + ii[6]);
@@ -1493,7 +1554,12 @@ extern "C" int jh_tree_create(const void* blob, size_t nbytes, jh_tree** out) {
   if (nobj) {  // the object section (judo_amd/tree_model.py): where the header says, one box geom, inertia at the body origin along its frame, robot-box pairs
     JH_REQUIRE((size_t)ii[9] == nf0 && (size_t)ii[10] == ni0 && ni == ni0 + TO_I + (size_t)ii[ni0 + 1], "tree_create: object section not where the header puts it");
     const float* of = f + nf0; const int* oi = ii + ni0;
-    JH_REQUIRE(oi[0] == 6, "tree_create: the free object must collide through one box geom (got geom type %d)", oi[0]);
+    JH_REQUIRE(oi[0] == 6 || oi[0] == 5, "tree_create: the free object must collide through one box or cylinder geom (got geom type %d)", oi[0]);
+    if (oi[0] == 5) {  // a cylinder's geom record: radius, half length, no third size; its bounding radius (a box's record relabelled fails here)
+      const float* g = of + OB_G;
+      JH_REQUIRE(g[0] > 0.f && g[1] > 0.f && g[2] == 0.f && fabsf(g[24] - sqrtf(g[0] * g[0] + g[1] * g[1])) <= 1e-6f * g[24],
+                 "tree_create: a cylinder object's geom record is (radius, half length, 0) with its bounding radius, not a box's (got sizes %g %g %g, bound %g)", g[0], g[1], g[2], g[24]);
+    }
     JH_REQUIRE(of[1] == 0.f && of[2] == 0.f && of[3] == 0.f && of[4] == 1.f && of[5] == 0.f && of[6] == 0.f && of[7] == 0.f && of[8] == 1.f && of[9] == 0.f && of[10] == 0.f &&
                of[11] == 0.f && of[12] == 1.f && of[0] > 0.f && of[13] > 0.f && of[14] > 0.f && of[15] > 0.f,
                "tree_create: the free object needs a positive mass and inertia, its centre of mass at its origin and its principal axes along its frame");
@@ -1513,7 +1579,7 @@ extern "C" int jh_tree_create(const void* blob, size_t nbytes, jh_tree** out) {
   jh_tree* t = new jh_tree();
   t->nf = (int)nf; t->ni = (int)ni; t->ns = ii[5];
   t->nj = ii[0]; t->ng = ii[1]; t->nq = ii[2]; t->nv = ii[3];
-  t->npair = ii[6]; t->self_collision = ii[6] > 0 ? 1 : 0; t->nobj = nobj;  // the robot collides with itself when the image lists pairs, as MuJoCo does (jh_tree_set_self_collision)
+  t->npair = ii[6]; t->self_collision = ii[6] > 0 ? 1 : 0; t->nobj = nobj; t->ocyl = nobj && ii[ni0] == 5;  // the robot collides with itself when the image lists pairs, as MuJoCo does (jh_tree_set_self_collision)
   JH_HIP(hipMalloc(&t->d_f, 4 * nf)); JH_HIP(hipMalloc(&t->d_i, 4 * ni)); JH_HIP(hipMalloc(&t->d_stats, 64 * sizeof(int)));
   JH_HIP(hipMemcpy(t->d_f, f, 4 * nf, hipMemcpyHostToDevice)); JH_HIP(hipMemcpy(t->d_i, ii, 4 * ni, hipMemcpyHostToDevice));
   JH_HIP(hipMemset(t->d_stats, 0, 64 * sizeof(int)));

@@ -80,7 +80,53 @@ def spot_box_description() -> dict:
     return d
 
 
-DERIVED_DESCRIPTIONS = {"spot_box": spot_box_description}
+def spot_tire_description() -> dict:
+    """The Spot robot with a free tire (judo/models/xml/spot_tire/robot.xml + objects/tire/tire.xml), derived from `spot.json` as `spot_box` is.
+
+    spot_tire/robot.xml restates spot_primitive's default classes and includes its body / legs / arm / actuator / contact files, so the robot is spot.json's,
+    standing at z = 0.52 (robot.xml:79).  What the tire adds (tire.xml):
+      * a body `tire` (:4, at the origin) with a free joint `tire_joint` (:5), inertia at its origin (:7: mass 15.3, diaginertia 0.57 0.96 0.57), and the sites
+        `trace_tire` and `site_object` (:93-95) at its origin;
+      * ONE collision geom, a STAND-IN: the reference collides the tire through 81 convex meshes that it does not ship.  The stand-in is the
+        reference's own primitive approximation `object_primitive_approx` (:9: a cylinder of radius 0.33 and half-length 0.17, quat 1 1 0 0 = its axis along the
+        body's y axis; TIRE_RADIUS / TIRE_HALF_WIDTH, spot_constants.py:123-124), made collidable with the meshes' class `tire_collision` (tire_defs.xml:9:
+        friction 1.15 1.0, priority 6 -- above the robot's 4 and the ground's 5, so the tire's friction and solver parameters win in every pair).
+      * the sensor list of robot.xml:95-116: 20 site sensors, 60 floats, all in the WORLD frame (spot.json's sensor_arm_link_* are relative to site_body).
+    Bodies and geoms in the MJCF compiler's order: the tire body before the fixtures that hold the plane, its geom before the plane."""
+    d = load_description("spot")
+    bodies, geoms, sites = d["bodies"], d["geoms"], d["sites"]
+    fix = next(i for i, b in enumerate(bodies) if b["name"] == "world_fixtures")
+    assert fix == len(bodies) - 1 and all(b["parent"] != fix for b in bodies)
+    tire = fix
+    for g in geoms:
+        g["body"] = g["body"] + 1 if g["body"] == fix else g["body"]
+    bodies[1] = dict(bodies[1], pos=[0.0, 0.0, 0.52])
+    bodies.insert(tire, dict(name="tire", parent=0, pos=[0.0, 0.0, 0.0], quat=[1.0, 0.0, 0.0, 0.0], mocap=False,
+                             mass=15.3, ipos=[0.0, 0.0, 0.0], iquat=[1.0, 0.0, 0.0, 0.0], inertia=[0.57, 0.96, 0.57]))
+    base = next(j for j in d["joints"] if j["type"] == "free")
+    d["joints"].append(dict(base, name="tire_joint", body=tire))
+    robot = next(g for g in geoms if g["type"] != "plane")
+    plane = next(i for i, g in enumerate(geoms) if g["type"] == "plane")
+    h = 1.0 / float(np.sqrt(2.0))                                # (quat 1 1 0 0, normalised as the MJCF compiler does)
+    geoms.insert(plane, dict(name="object_primitive_approx", body=tire, type="cylinder", condim=robot["condim"], friction=[1.15, 1.0, 0.0001],
+                             solref=list(robot["solref"]), solimp=list(robot["solimp"]), margin=0.0, gap=0.0, solmix=1.0, priority=6, pos=[0.0, 0.0, 0.0],
+                             quat=[h, h, 0.0, 0.0], size=[0.33, 0.17]))
+    obj = next(i for i, st in enumerate(sites) if st["name"] == "site_object")
+    site_object = dict(sites.pop(obj), body=tire, pos=[0.0, 0.0, 0.0])
+    sites += [dict(site_object, name="trace_tire"), site_object]
+    site = {st["name"]: i for i, st in enumerate(sites)}
+    sens = [("sensor_body", "framepos", "site_body"), ("body_x_axis", "framexaxis", "site_body"), ("object_x_axis", "framexaxis", "site_object"),
+            ("object_y_axis", "frameyaxis", "site_object"), ("object_z_axis", "framezaxis", "site_object"), ("trace_fngr_site", "framepos", "site_arm_link_fngr"),
+            ("gripper_x_axis", "framexaxis", "site_arm_link_wr1"), ("gripper_y_axis", "frameyaxis", "site_arm_link_wr1"), ("finger_x_axis", "framexaxis", "site_arm_link_fngr"),
+            ("fl_pos", "framepos", "site_front_left"), ("fr_pos", "framepos", "site_front_right"), ("hl_pos", "framepos", "site_rear_left"), ("hr_pos", "framepos", "site_rear_right")]
+    sens += [(f"sensor_arm_link_{n}", "framepos", f"site_arm_link_{n}") for n in ("sh0", "sh1", "el0", "el1", "wr0", "wr1", "fngr")]
+    d["sensors"] = [dict(name=n, type=t, adr=3 * k, objtype="site", obj=site[s], dim=3) for k, (n, t, s) in enumerate(sens)]
+    d["nsensordata"] = 3 * len(sens)
+    d["task"], d["family"], d["source"] = "spot_tire", "spot", "judo v0.0.7 judo/models/xml/spot_tire/robot.xml (derived from spot.json; cylinder stand-in for the tire's meshes)"
+    return d
+
+
+DERIVED_DESCRIPTIONS = {"spot_box": spot_box_description, "spot_tire": spot_tire_description}
 
 
 # ----------------------------------------------------------------------------------------- small rigid-body helpers

@@ -14,6 +14,11 @@ robot geom (equal priorities: mixed like a robot-robot pair; the box must carry 
 I[8] = number of objects (0 or 1), I[9] / I[10] = where the object's float / int records start; both come after everything else, so the image of a model without an
 object is the same as before the section existed.
 
+The object's geom is a box (spot_box) or a cylinder (spot_tire: radius, half length along its local z; the geom record carries its pose in the body frame -- the tire's
+cylinder lies along the body's y axis).  Contact parameters by mj_contactParam's priority rule: an object geom of the robot geoms' priority mixes like a robot geom (above);
+one of HIGHER priority (the tire: 6, above the robot's 4 and the plane's 5) brings its own friction / solref / solimp to every pair it is in -- the record's plane-mixed
+values are then its own, and the kernel's larger-friction rule for robot-object pairs picks its friction, which the packer checks is at least every robot geom's.
+
 Float image F / int image I (little-endian fp32 / int32), see the enums at the top of jh_engine_v4.hip.
 """
 
@@ -30,6 +35,7 @@ TS_F, TS_I = 16, 4            # per sensor
 TO_F, TO_I = 48, 4            # object: body record (mass, ipos 3, iR 9, inertia 3, invweight0 2, pad 2) + its box geom in the geom record's layout; type, number of robot-box pairs, pad
 SOLVER_TOL, SOLVER_MAX_ITER, SOLVER_LS_TOL = 1e-4, 20, 1e-2
 GTYPE = {"sphere": 2, "capsule": 3, "box": 6}
+OBJECT_GTYPES = {"box": 6, "cylinder": 5}   # the object shapes k_tree_v4 carries (jh_tree_create rejects every other)
 MAX_JOINTS, MAX_GEOMS, MAX_DEPTH = 25, 31, 7
 
 
@@ -102,7 +108,7 @@ def robot_pairs(desc: dict, robot_geoms: list) -> list[tuple[int, int]]:
 
 def bounding_radius(g: dict) -> float:
     size = list(g["size"]) + [0, 0, 0]
-    return {"sphere": size[0], "capsule": size[0] + size[1], "box": float(np.linalg.norm(size[:3]))}[g["type"]]
+    return {"sphere": size[0], "capsule": size[0] + size[1], "box": float(np.linalg.norm(size[:3])), "cylinder": float(np.hypot(size[0], size[1]))}[g["type"]]
 
 
 def _mix_with_plane(g: dict, plane: dict):
@@ -150,8 +156,10 @@ def pack_tree_model(desc: dict) -> tuple[np.ndarray, np.ndarray]:
             raise NotImplementedError("tree kernel: the plane must sit on a static body (zero inverse weight)")
     opairs = []
     if objects:
-        if len(obj_geoms) != 1 or obj_geoms[0]["type"] != "box":
-            raise NotImplementedError("tree kernel: a free object carries exactly one box collision geom")
+        if len(obj_geoms) != 1 or obj_geoms[0]["type"] not in OBJECT_GTYPES:
+            raise NotImplementedError("tree kernel: a free object carries exactly one box or cylinder collision geom")
+        if obj_geoms[0]["type"] == "cylinder" and len(obj_geoms[0]["size"]) != 2:
+            raise NotImplementedError("tree kernel: a cylinder's size is (radius, half length)")
         ob, og = bodies[objects[0]], obj_geoms[0]
         if np.abs(ob["ipos"]).max() > 0 or list(ob["iquat"]) != [1.0, 0.0, 0.0, 0.0]:
             raise NotImplementedError("tree kernel: a free object has its centre of mass at its origin and its principal axes along its frame")
@@ -278,12 +286,15 @@ def pack_tree_model(desc: dict) -> tuple[np.ndarray, np.ndarray]:
         cK, cB = solref_to_kb(solref, solimp, o["timestep"])
         own_k, own_b = solref_to_kb(og["solref"], og["solimp"], o["timestep"])
         ref = robot_geoms[0]
-        if og["condim"] != 3 or og["margin"] != 0 or og["gap"] != 0 or og.get("priority", 0) != ref.get("priority", 0) or og.get("solmix", 1.0) != ref.get("solmix", 1.0) or \
-                list(og["solref"]) != list(ref["solref"]) or list(og["solimp"]) != list(ref["solimp"]) or \
+        above = og.get("priority", 0) > ref.get("priority", 0)   # the object's own parameters win every robot-object pair (mj_contactParam)
+        if og["condim"] != 3 or og["margin"] != 0 or og["gap"] != 0 or og.get("priority", 0) < ref.get("priority", 0) or \
+                (not above and (og.get("solmix", 1.0) != ref.get("solmix", 1.0) or list(og["solref"]) != list(ref["solref"]) or list(og["solimp"]) != list(ref["solimp"]))) or \
+                (above and any(og["friction"][0] < robot_geoms[i]["friction"][0] for i in opairs)) or \
                 not (np.isclose(own_k, cK) and np.isclose(own_b, cB) and np.allclose(clamp_solimp(og["solimp"]), clamp_solimp(solimp))):
-            raise NotImplementedError("tree kernel: the object's box needs condim 3, no margin / gap and the robot geoms' priority / solmix / solref / solimp")
+            raise NotImplementedError("tree kernel: the object's geom needs condim 3, no margin / gap, and the robot geoms' priority / solmix / solref / solimp or a higher "
+                                      "priority with the larger friction (its plane-mixed parameters its own)")
         g = f[20: 20 + TG_F]
-        g[0:3] = og["size"][:3]
+        g[0:3] = (list(og["size"]) + [0.0, 0.0])[:3]
         g[3:6] = og["pos"]
         g[6:15] = quat_to_mat(og["quat"]).reshape(-1)
         g[15] = max(1e-5, mu)
@@ -292,7 +303,7 @@ def pack_tree_model(desc: dict) -> tuple[np.ndarray, np.ndarray]:
         g[23] = bodyw[objects[0]][0] + bodyw[plane["body"]][0]
         g[24] = bounding_radius(og)
         g[25] = max(1e-5, og["friction"][0])
-        I[ooi: ooi + TO_I] = [GTYPE[og["type"]], len(opairs), 0, 0]
+        I[ooi: ooi + TO_I] = [OBJECT_GTYPES[og["type"]], len(opairs), 0, 0]
         I[ooi + TO_I: ooi + TO_I + len(opairs)] = opairs
     return F, I
 

@@ -1,0 +1,349 @@
+"""spot_tire on the GPU: the tree kernel's cylinder instantiation (csrc/jh_engine_v4.hip, `k_tree_v4<SELF, true, true>`).
+
+  * robot against tire: the oracle engine with the `spot_tire` description, pairs = oracle.collision_pairs(desc, "all") plus the 27 robot-tire pairs (the oracle's
+    collide_cylinder_sphere / collide_convex; collision_pairs lists no cylinder pair for the Spot family);
+  * tire against plane: the oracle has no plane-cylinder routine, so one substep is pinned by a PROXY -- spheres on the tire body at the rim points the fp64 restatement
+    (tests/test_spot_tire_host.py::plane_cylinder) reports, each centred rho above its point along the normal, so that the oracle's plane-sphere rows are exactly the
+    plane-cylinder rows (depth, position, frame); the spheres carry the tire's friction, priority and solver parameters.  Exact for ONE substep: the rim points stay
+    fixed on the body only until the next collision pass;
+  * known answers over one second: an upright / a flat tire at rest, an upright tire rolling at v = omega r;
+  * the policy rollout of the spot_tire model against oracle.policy.policy_rollout (robot columns and sensors; the oracle's tire has no plane to rest on), the tasks'
+    device rewards against their numpy rewards, and short closed loops of both tasks' controllers.
+
+Floating point as in tests/test_gpu_spot_box.py (fp32 kernel stopping at 1e-4, fp64 oracle at 1e-10); tolerances are 5x the largest error observed (tests/conftest.py::bounded)."""
+
+import numpy as np
+import pytest
+
+from tests.conftest import bounded
+from tests.test_spot_tire_host import plane_cylinder
+
+pytestmark = pytest.mark.gpu
+
+NQ, NV = 33, 31
+SL = dict(pos=slice(0, 3), quat=slice(3, 7), q=slice(7, 26), opos=slice(26, 29), oquat=slice(29, 33), vlin=slice(33, 36), vang=slice(36, 39), qd=slice(39, 58),
+          ovlin=slice(58, 61), ovang=slice(61, 64))
+ROBOT = ("pos", "quat", "q", "vlin", "vang", "qd")
+# 5 x the largest error observed (per unit of `scale`).  TOL: the plane proxy and the policy rollout (observed 2.7e-8, 2.7e-8, 3.0e-7, 7.0e-8, 4.4e-8, 3.2e-7, 2.6e-6,
+# 1.7e-5, 2.5e-7, 9.6e-7).  TOL_RT: robot-tire contacts (observed 9.6e-6, 1.3e-4, 4.4e-4, 2.4e-5, 9.5e-5, 4.9e-4, 1.1e-2, 1.4e-2, 2.2e-3, 9.9e-3), largest after ONE
+# substep and not growing with more: the fp32 GJK + EPA stops within 1e-6 m of the surface, which on a curved contact (a capsule's end, the cylinder's side or rim)
+# leaves its normal within ~sqrt(2e-6 / radius of curvature), a few milliradians, of the oracle's fp64 one (csrc/jh_coop.h::collide_convex_cylinder)
+TOL = dict(pos=1.4e-7, quat=1.4e-7, q=1.5e-6, opos=3.5e-7, oquat=2.2e-7, vlin=1.6e-6, vang=1.3e-5, qd=8.5e-5, ovlin=1.2e-6, ovang=5e-6)
+TOL_RT = dict(pos=5e-5, quat=6.5e-4, q=2.2e-3, opos=1.2e-4, oquat=4.8e-4, vlin=2.5e-3, vang=5.7e-2, qd=7.1e-2, ovlin=1.1e-2, ovang=5e-2)
+
+
+def _check(what, got, ref, tol, scale=1.0, cols=tuple(SL)):
+    for name in cols:
+        sl = SL[name]
+        err = np.abs(got[..., sl] - ref[..., sl]).max()
+        assert bounded(f"spot_tire {what}: {name} error / scale", err / scale, tol[name]), f"{what} {name}: {err:.3e} > {tol[name] * scale:.1e}"
+
+
+def _tire_geom(desc):
+    return next(i for i, g in enumerate(desc["geoms"]) if g["type"] == "cylinder")
+
+
+def _pairs(O, desc):
+    """collision_pairs(desc, "all") and the robot-tire pairs MuJoCo's static filters leave (the tire hangs off the world: every robot geom)."""
+    tg = _tire_geom(desc)
+    excl = {tuple(sorted(e)) for e in desc["excludes"]}
+    tb = desc["geoms"][tg]["body"]
+    extra = [(i, tg) for i, g in enumerate(desc["geoms"]) if g["type"] != "plane" and i != tg and tuple(sorted((g["body"], tb))) not in excl]
+    return O.collision_pairs(desc, "all") + extra
+
+
+def _oracle_desc(desc, sensors):
+    """The description with a subset of its sensors, re-addressed: the oracle holds at most 48 sensor floats (spot_tire has 60)."""
+    import copy
+
+    d = copy.deepcopy(desc)
+    d["sensors"] = [dict(desc["sensors"][i], adr=3 * k) for k, i in enumerate(sensors)]
+    d["nsensordata"] = 3 * len(sensors)
+    return d
+
+
+@pytest.fixture(scope="module")
+def tire(gpu):
+    from judo_amd.models import load_description
+    from judo_amd.policy import SpotTreeEngine
+    from oracle import oracle as O
+    from oracle import policy as P
+
+    desc = load_description("spot_tire")
+    odesc = _oracle_desc(desc, range(13))   # the sensors of spot_box's list; the arm-link positions are compared in the policy-rollout test
+    pairs = _pairs(O, odesc)
+    assert len(pairs) == len(O.collision_pairs(odesc, "all")) + 27
+    om = O.Model("spot_tire", desc=odesc, pairs=pairs)
+    eng = SpotTreeEngine(desc)
+    assert (om.nq, om.nv, eng.nq, eng.nv, eng.nsensordata) == (NQ, NV, NQ, NV, 60)
+    return P, O, om, eng, odesc
+
+
+def _state(P, tire_pose, tire_vel=(0, 0, 0, 0, 0, 0)):
+    x = P.spot_reset_state()
+    return np.concatenate([x[:26], tire_pose, x[26:], tire_vel])
+
+
+def _oracle_steps(om, X, U, k, with_sensors=False):
+    res = [om.rollout(X[i], np.repeat(U[i][None], k, axis=0)[None], nthread=1) for i in range(X.shape[0])]
+    st = np.stack([r[0][0, -1] for r in res])
+    return (st, np.stack([r[1][0, -1] for r in res])) if with_sensors else st
+
+
+def _kernel(eng, X, U, k, sensors=False):
+    import torch
+
+    xs = torch.as_tensor(X, dtype=torch.float32, device="cuda")
+    us = torch.as_tensor(U, dtype=torch.float32, device="cuda")
+    warm = torch.zeros((len(X), NV), dtype=torch.float32, device="cuda")
+    sens = torch.full((len(X), 60), float("nan"), dtype=torch.float32, device="cuda") if sensors else None
+    got = eng.substeps(xs, us, warm, k, sensors=sens).cpu().numpy()
+    assert np.isfinite(got).all()
+    return (got, sens.cpu().numpy()) if sensors else got
+
+
+def _quat(axis, ang):
+    a = np.asarray(axis, float) / np.linalg.norm(axis)
+    return np.array([np.cos(ang / 2), *(np.sin(ang / 2) * a)])
+
+
+def _qmul(a, b):
+    w1, x1, y1, z1 = a
+    w2, x2, y2, z2 = b
+    return np.array([w1 * w2 - x1 * x2 - y1 * y2 - z1 * z2, w1 * x2 + x1 * w2 + y1 * z2 - z1 * y2, w1 * y2 - x1 * z2 + y1 * w2 + z1 * x2, w1 * z2 + x1 * y2 - y1 * x2 + z1 * w2])
+
+
+def _mat(q):
+    from judo_amd.models import quat_to_mat
+
+    return quat_to_mat(np.asarray(q, float) / np.linalg.norm(q))
+
+
+def _tire_contact_states(P, om, desc, n_want, seed):
+    """Robot standing, the tire (at least 3 cm above the plane, generic orientation) placed against it at random: classified by what the robot-tire contacts couple -- the
+    base alone, the base and one chain, two different chains (the dense path).  Generic orientations: no face or edge of a robot box / capsule parallel to the cylinder's
+    cap or axis, so the convex collider's witness points are unique."""
+    from judo_amd.tree_model import tree_structure
+
+    st = tree_structure(desc)
+    gs = desc["geoms"]
+    tg = _tire_geom(desc)
+
+    def chain(g):
+        b = gs[g]["body"]
+        if b not in st["body_of"]:
+            return 0
+        c0 = st["info"][st["body_of"][b]]["start"]
+        return 1 + (c0 // 3 if c0 < 12 else 4)
+
+    rng = np.random.default_rng(seed)
+    out = {"base": [], "one": [], "two": []}
+    for _ in range(6000):
+        if all(len(v) >= n_want for v in out.values()):
+            break
+        x = _state(P, [0, 0, 0, 1, 0, 0, 0])
+        x[7:19] += rng.standard_normal(12) * 0.05
+        if rng.random() < 0.5:
+            x[19:26] = [0, -0.9, 1.8, 0, -0.9, 0, 0] + rng.standard_normal(7) * 0.3
+        q = rng.standard_normal(4)
+        q /= np.linalg.norm(q)
+        R = _mat(q)
+        ax = R[:, 1]                                            # the cylinder's axis: the body's y axis
+        low = 0.33 * np.sqrt(max(0.0, 1 - ax[2] ** 2)) + 0.17 * abs(ax[2])   # centre height of a cylinder touching the plane
+        ang = rng.uniform(-np.pi, np.pi)
+        r = rng.uniform(0.3, 0.9)
+        x[26:29] = [r * np.cos(ang), r * np.sin(ang), low + rng.uniform(0.03, 0.5)]
+        x[29:33] = q
+        x[NQ + 25: NQ + 31] = rng.standard_normal(6) * 0.2
+        f = om.forward(x[:NQ], x[NQ:], x[7:26])
+        cs = f["contacts"]
+        rtc = [c for c in cs if tg in (int(c[13]), int(c[14]))]
+        rt = [int(c[13]) if int(c[14]) == tg else int(c[14]) for c in rtc]
+        if not rt or f["ncon"] > 28 or min(c[0] for c in rtc) < -0.015:
+            continue  # (deep interpenetration of a random placement: stiff, and nothing a rollout visits)
+        chains = {chain(g) for g in rt} - {0}
+        kind = "base" if not chains else ("one" if len(chains) == 1 else "two")
+        if len(out[kind]) < n_want:
+            out[kind].append(x)
+    return out
+
+
+@pytest.mark.parametrize("kind", ["base", "one", "two"])
+def test_robot_against_the_tire(tire, kind):
+    """Robot-tire contacts (sphere-cylinder for the feet and the elbow lip, the fp32 GJK + EPA for the capsules and boxes) against the oracle over 1, 2 and 5 substeps:
+    with the base alone, one chain (the tire's block eliminated by its Schur complement), and two chains at once (the dense path)."""
+    P, O, om, eng, desc = tire
+    groups = _tire_contact_states(P, om, desc, 4, seed=21)
+    X = np.stack(groups[kind])
+    assert len(X) >= 2, {k: len(v) for k, v in groups.items()}
+    U = X[:, 7:26].copy()
+    eng.stats()
+    for k in (1, 2, 5):
+        _check(f"robot-tire contact ({kind}), {k} steps", _kernel(eng, X, U, k), _oracle_steps(om, X, U, k), TOL_RT, scale=1.0 + 0.5 * (k - 1))
+    assert eng.stats()["contacts_dropped"] == 0
+    # the contacts matter: without the robot-tire pairs the tire moves differently
+    om_free = O.Model("spot_tire", desc=desc, pairs=O.collision_pairs(desc, "all"))
+    assert np.abs(_kernel(eng, X, U, 1)[:, 58:64] - _oracle_steps(om_free, X, U, 1)[:, 58:64]).max() > 1e-3
+
+
+def _proxy_model(O, desc, x):
+    """The oracle description for one state x: spheres on the tire body at the plane-cylinder rim points of x (see the module docstring)."""
+    import copy
+
+    d = copy.deepcopy(desc)
+    tg = _tire_geom(d)
+    cyl = d["geoms"][tg]
+    tb = cyl["body"]
+    plane = next(g for g in d["geoms"] if g["type"] == "plane")
+    n, pp = np.array([0.0, 0.0, 1.0]), np.array(plane["pos"], float)
+    Rb, pb = _mat(x[29:33]), x[26:29]
+    con = plane_cylinder(pp, n, pb + Rb @ np.array(cyl["pos"]), Rb @ _mat(cyl["quat"]), cyl["size"][0], cyl["size"][1])
+    rho = 0.05
+    spheres = [dict(cyl, name=f"proxy{i}", type="sphere", size=[rho], pos=list(Rb.T @ (p + rho * n - pb)), quat=[1.0, 0.0, 0.0, 0.0]) for i, (_, p, _) in enumerate(con)]
+    d["geoms"][tg + 1: tg + 1] = spheres
+    return O.Model("spot_tire", desc=d, pairs=O.collision_pairs(d, "all")), len(con)
+
+
+def test_tire_on_the_plane_one_substep_matches_the_sphere_proxy(tire):
+    """PlaneCylinder in the kernel against the oracle's plane-sphere rows at the same points: flat (3 contacts), upright (2), tilted (1), spinning and sliding upright
+    tires, each 2-3 mm into the plane, the robot standing 3 m away."""
+    P, O, om, eng, desc = tire
+    roll90 = _quat([1, 0, 0], np.pi / 2)
+    cases = {
+        "flat": (_qmul(_quat([0, 0, 1], 0.4), roll90), 0.17 - 0.003, np.zeros(6), 3),
+        "upright": (_quat([0, 0, 1], 0.7), 0.33 - 0.002, np.zeros(6), 2),
+        "tilted": (_qmul(_quat([0, 0, 1], -0.3), _quat([1, 0, 0], 0.45)), None, np.array([0.1, -0.2, 0.0, 0.3, 0.1, -0.2]), 1),
+        "spinning": (_quat([0, 0, 1], 1.1), 0.33 - 0.0025, np.array([0.0, 0.0, 0.0, 0.0, 6.0, 0.0]), 2),
+        "sliding": (_quat([0, 0, 1], -0.5), 0.33 - 0.002, np.array([0.8, -0.4, 0.0, 0.0, 0.0, 0.5]), 2),
+    }
+    X, models = [], []
+    for name, (q, z, v, ncon) in cases.items():
+        if z is None:  # the lowest rim point 2.5 mm into the plane
+            ax = _mat(q)[:, 1]
+            z = 0.33 * np.sqrt(1 - ax[2] ** 2) + 0.17 * abs(ax[2]) - 0.0025
+        x = _state(P, [3.0, 0.5, z, *q], v)
+        m, n = _proxy_model(O, desc, x)
+        assert n == ncon, (name, n)
+        X.append(x)
+        models.append(m)
+    X = np.stack(X)
+    U = X[:, 7:26].copy()
+    eng.stats()
+    got = _kernel(eng, X, U, 1)
+    ref = np.stack([_oracle_steps(m, X[i: i + 1], U[i: i + 1], 1)[0] for i, m in enumerate(models)])
+    _check("tire on the plane, one substep", got, ref, TOL)
+    assert eng.stats()["contacts_dropped"] == 0
+    # the plane contacts matter: the tire would otherwise fall freely
+    assert (got[:, 58 + 2] > -0.05).all() and np.abs(got[:, 58 + 2] - (X[:, 58 + 2] - 9.81 * 0.01)).min() > 1e-2
+
+
+def _energy(x):
+    v, w = x[..., 58:61], x[..., 61:64]
+    return 0.5 * 15.3 * (v * v).sum(-1) + 0.5 * (0.57 * w[..., 0] ** 2 + 0.96 * w[..., 1] ** 2 + 0.57 * w[..., 2] ** 2) + 15.3 * 9.81 * x[..., 28]
+
+
+def test_tire_known_answers_over_one_second(tire):
+    """One second (100 substeps) with the robot standing 3 m away: an upright tire at rest stays upright and at its radius, a flat tire at rest stays flat, an upright
+    tire started rolling at v = omega r rolls straight, covers v t and gains no energy; no contact is dropped."""
+    P, O, om, eng, desc = tire
+    v = 1.0
+    X = np.stack([
+        _state(P, [3.0, 0.5, 0.33, 1, 0, 0, 0]),                                      # upright at rest
+        _state(P, [3.0, 0.5, 0.17, *_quat([1, 0, 0], np.pi / 2)]),                     # flat at rest
+        _state(P, [3.0, 0.5, 0.33, 1, 0, 0, 0], [v, 0, 0, 0, v / 0.33, 0]),          # rolling along x, its axis along y
+    ])
+    U = X[:, 7:26].copy()
+    eng.stats()
+    got = _kernel(eng, X, U, 100)
+    assert eng.stats()["contacts_dropped"] == 0
+    y = np.stack([_mat(q)[:, 1] for q in got[:, 29:33]])
+    assert bounded("spot_tire at rest upright: |y . z| after 1 s", abs(y[0, 2]), 1.1e-9)                   # observed 2.1e-10
+    assert -0.005 < got[0, 28] - 0.33 <= 0.0 and np.linalg.norm(got[0, 26:28] - [3.0, 0.5]) < 2e-3
+    assert bounded("spot_tire at rest flat: 1 - |y . z| after 1 s", 1 - abs(y[1, 2]), 1e-6)                 # observed 0; 1e-6: fp32 resolution
+    assert -0.005 < got[1, 28] - 0.17 <= 0.0 and np.linalg.norm(got[1, 26:28] - [3.0, 0.5]) < 2e-3
+    travel = got[2, 26] - 3.0
+    assert bounded("spot_tire rolling: |travel - v t| / v t after 1 s", abs(travel - v * 1.0) / v, 8e-4)    # observed 1.6e-4
+    assert abs(got[2, 27] - 0.5) < 1e-3 and bounded("spot_tire rolling: |y . z| after 1 s", abs(y[2, 2]), 2.6e-9)   # observed 5.2e-10
+    assert _energy(got[2]) <= _energy(X[2]) * (1 + 1e-3)
+
+
+def test_policy_rollout_with_the_tire_matches_oracle(tire):
+    """jh_policy_rollout on the spot_tire image: 24 rollouts x a few command rows, the robot's state columns and its sensors against oracle.policy.policy_rollout.  The
+    tire sits 3 m away; its columns are not compared (the oracle has no plane-cylinder routine: its tire falls through the plane -- the tests above cover the tire)."""
+    from judo_amd.models import load_description
+    from judo_amd.policy import PolicyRolloutBackend
+
+    P, O, om, eng, odesc = tire
+    desc = load_description("spot_tire")
+    groups = [list(range(16)), list(range(12)) + [16, 17, 18, 19]]   # two oracle models cover the 20 sensors, 48 floats each
+    oms = [O.Model("spot_tire", desc=_oracle_desc(desc, g), pairs=_pairs(O, odesc)) for g in groups]
+    cols = [np.concatenate([np.arange(3 * i, 3 * i + 3) for i in g]) for g in groups]
+    Ws, bs = P.load_actor()
+    N, T = 24, 5
+    x0 = _state(P, [3.0, 0.0, 0.33, 1, 0, 0, 0])
+    rng = np.random.default_rng(3)
+    cmds = np.tile(P.DEFAULT_POLICY_COMMAND, (N, T, 1))
+    cmds[:, :, :3] = rng.uniform(-0.5, 0.5, (N, 1, 3))
+    cmds[:, :, 3:10] = np.array([0, -0.9, 1.8, 0, -0.9, 0, 0]) + rng.standard_normal((N, 1, 7)) * 0.3
+    be = PolicyRolloutBackend(N, desc=desc, carry_warmstart=False)
+    states, sensors, outs = be.rollout(x0, cmds, np.zeros((N, 12)))
+    assert states.shape == (N, T, 64) and sensors.shape == (N, T, 60) and outs.shape == (N, 12)
+    assert be.engine.stats()["contacts_dropped"] == 0
+    for i in range(N):
+        for m, c in zip(oms, cols):
+            ref, sref, o = P.policy_rollout(m, Ws, bs, x0, cmds[i], with_sensors=True)
+            keep = ~np.isin(c, np.arange(6, 15))   # all but the tire site's frame axes
+            _check(f"policy rollout {i}", states[i], ref, TOL, scale=4.0, cols=ROBOT)
+            assert bounded("spot_tire policy rollout: robot sensor error", np.abs(sensors[i][:, c[keep]] - sref[:, keep]).max(), 4.6e-6)   # observed 9.3e-7
+            assert bounded("spot_tire policy rollout: policy output error", np.abs(outs[i] - o).max(), 3.1e-5)                          # observed 6.2e-6
+
+
+@pytest.mark.parametrize("task_name", ["spot_tire_roll", "spot_tire_upright"])
+def test_device_reward_matches_numpy_reward(tire, task_name):
+    """The task's torch reward on the device tensors of a policy rollout equals its numpy reward on the same states and sensors (fp64 copies)."""
+    import torch
+    from judo_amd.policy import PolicyRolloutBackend
+    from judo_amd.tasks import get_registered_tasks
+
+    P, O, om, eng, _ = tire
+    task = get_registered_tasks()[task_name][0]()
+    desc = task.desc
+    N, T = 6, 4
+    x0 = task.default_state()
+    cmds = np.tile(P.DEFAULT_POLICY_COMMAND, (N, T, 1))
+    cmds[:, :, 0] = np.linspace(-0.5, 0.5, N)[:, None]
+    be = PolicyRolloutBackend(N, desc=desc, carry_warmstart=False)
+    st, se, _ = be.rollout(x0, torch.as_tensor(cmds, dtype=torch.float32, device="cuda"), torch.zeros((N, 12), dtype=torch.float32, device="cuda"))
+    ctl = torch.as_tensor(np.random.default_rng(1).uniform(-1, 1, (N, T, task.nu)), dtype=torch.float32, device="cuda")
+    r_dev = task.reward(st, se, ctl).cpu().numpy()
+    r_np = task.reward(st.double().cpu().numpy(), se.double().cpu().numpy(), ctl.double().cpu().numpy())
+    assert np.isfinite(r_dev).all()
+    assert bounded(f"{task_name} device reward vs numpy reward, relative", np.abs(r_dev - r_np).max() / np.abs(r_np).max(), 8.7e-7)   # observed 1.7e-7
+
+
+@pytest.mark.parametrize("task_name", ["spot_tire_roll", "spot_tire_upright"])
+def test_spot_tire_controller_closed_loop(tire, task_name):
+    """make_controller(task, "mppi"): plan steps on the tire model, the plan's first action applied to a one-rollout plant; the nominal knots stay finite."""
+    import torch
+    from judo_amd.controller import make_controller
+    from judo_amd.policy import PolicyRolloutBackend
+
+    np.random.seed(0)
+    ctrl = make_controller(task_name, "mppi")
+    ctrl.rollout_cutoff_time = None
+    ctrl.optimizer.seed(2)
+    task = ctrl.task
+    x = task.default_state()
+    plant = PolicyRolloutBackend(1, physics_substeps=task.physics_substeps, desc=task.desc)
+    last = np.zeros((1, 12))
+    t = 0.0
+    for _ in range(4):
+        ctrl.update_states(x[:NQ], x[NQ:], time=t)
+        ctrl.update_action()
+        assert np.isfinite(ctrl.nominal_knots).all() and np.isfinite(ctrl.rewards).all()
+        cmd = np.asarray(task.task_to_sim_ctrl(ctrl.action(t)), dtype=np.float64).reshape(1, 1, 25)
+        st, _, last = plant.rollout(x, cmd, last)
+        x = st[0, -1]
+        t += task.dt
+    assert np.isfinite(x).all() and x[2] > 0.3 and abs(x[28] - task.default_state()[28]) < 0.01
+    torch.cuda.synchronize()

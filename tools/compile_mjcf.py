@@ -71,22 +71,25 @@ def load_xml(path: str) -> ET.Element:
     """Parse an MJCF file, inlining <include file=.../> elements (relative to the including file)."""
     root = ET.parse(path).getroot()
 
-    def expand(el: ET.Element, base: str) -> None:
+    def expand(el: ET.Element, base: str, here: str) -> None:
         i = 0
         while i < len(el):
             ch = el[i]
             if ch.tag == "include":
-                inc = ET.parse(os.path.join(base, ch.get("file"))).getroot()
-                expand(inc, base)  # MuJoCo resolves nested includes relative to the top-level model file
+                fn = os.path.join(base, ch.get("file"))
+                if not os.path.exists(fn):  # (objects/tire/tire.xml names tire_defs.xml next to itself)
+                    fn = os.path.join(here, ch.get("file"))
+                inc = ET.parse(fn).getroot()
+                expand(inc, base, os.path.dirname(fn))  # MuJoCo resolves nested includes relative to the top-level model file
                 el.remove(ch)
                 for k, sub in enumerate(list(inc)):
                     el.insert(i + k, sub)
                 i += len(inc)
             else:
-                expand(ch, base)
+                expand(ch, base, here)
                 i += 1
 
-    expand(root, os.path.dirname(path))
+    expand(root, os.path.dirname(path), os.path.dirname(path))
     return root
 
 
@@ -219,8 +222,10 @@ def _check_orientation_attributes(root: ET.Element) -> None:
             raise NotImplementedError(f"<{el.tag} name={el.get('name')!r}>: `euler` is implemented for geoms only")
 
 
-def compile_model(xml_name: str, task: str) -> dict:
+def compile_model(xml_name: str, task: str, prepare=None) -> dict:
     root = load_xml(os.path.join(REF_XML, xml_name))
+    if prepare is not None:  # a transcription's documented substitutions, applied to the inlined tree
+        prepare(root)
     _check_orientation_attributes(root)
     dfl = Defaults(root)
     comp = {}
@@ -464,6 +469,31 @@ def transcribe_spot_box() -> dict:
     """judo/models/xml/spot_box/robot.xml as a description: a CROSS-CHECK only.  The product derives `spot_box` from spot.json in code
     (judo_amd/models.py::spot_box_description) and no spot_box.json is written; tests/test_spot_box_host.py compares the two."""
     m = compile_model("spot_box/robot.xml", "spot_box")
+    m["family"] = "spot"
+    return m
+
+
+def _tire_stand_in(root: ET.Element) -> None:
+    """spot_tire/robot.xml as the product models it: tire.xml's second <worldbody> merged into the first (MuJoCo merges them), the 81 collision meshes
+    (absent upstream) dropped, and the reference's primitive approximation `object_primitive_approx` made collidable with the meshes' class `tire_collision`."""
+    wbs = root.findall("worldbody")
+    for wb in wbs[1:]:
+        for ch in list(wb):
+            wbs[0].append(ch)
+        root.remove(wb)
+    for b in root.iter("body"):
+        for g in list(b.findall("geom")):
+            if g.get("class") == "tire_collision":
+                b.remove(g)
+            elif g.get("name") == "object_primitive_approx":
+                g.set("class", "tire_collision")
+                g.attrib.pop("rgba", None)
+
+
+def transcribe_spot_tire() -> dict:
+    """judo/models/xml/spot_tire/robot.xml with the cylinder stand-in for the tire's meshes (_tire_stand_in): a CROSS-CHECK of
+    judo_amd/models.py::spot_tire_description, compared by tests/test_spot_tire_host.py; no spot_tire.json is written."""
+    m = compile_model("spot_tire/robot.xml", "spot_tire", prepare=_tire_stand_in)
     m["family"] = "spot"
     return m
 
