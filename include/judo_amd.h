@@ -77,6 +77,14 @@ int jh_model_set_self_collision(jh_model* m, int on);
  * caltech_leap_cube workloads 2e-4 .. 4e-4, which is why judo_amd selects 64 for those two models.  jh_model_limits out[3] reports the setting. */
 int jh_model_set_contact_capacity(jh_model* m, int contacts);
 
+/* Which build of its kernel a model runs: out[0] = kernel generation, out[1] = contact capacity of the leap kernel's build (48 or 64; 0: another kernel), out[2] = 1 when
+ * that is the CYLINDER build (jh_engine_v5_cyl.hip), out[3] = cylinder geoms in the image.  The cylinder build is selected by the image, not by a setter: an image of the
+ * leap family that keeps caltech_leap_cube's fingertip cylinders (geom type 5, sizes (radius, half length), bounding radius sqrt(r^2 + L^2); engine_model.py,
+ * fingertips="cylinder") runs sphere-cylinder through MuJoCo's primitive and box-cylinder / cylinder-cylinder through a bounded fp32 GJK + EPA, at 64 contacts per
+ * rollout.  jh_model_create refuses a malformed cylinder record and a cylinder in any other family; kernel generations 1 and 2 and the 48-contact setting refuse such a
+ * model; the sphere builds refuse its image.  HOST pointer. */
+int jh_model_build(const jh_model* m, int* out /* HOST, 4 ints */);
+
 /* Traces without a second rollout (judo/controller/controller.py:323-363, `update_traces`: line segments of the best rollouts' `trace*` framepos sensors).  The
  * reference reads them out of the sensor array its rollout materialises for every sample; the fused path has no such array, so round 1-2 re-rolled the elites in
  * materialise mode when the traces were read (8 ms on the headline workload: one lone wave for 64 serial steps).  jh_rollout_cost_traced (jh_rollout_cost with one more argument) on

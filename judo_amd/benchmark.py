@@ -15,12 +15,13 @@ import time
 import numpy as np
 
 
-def plan_times(task: str, optimizer: str, num_samples: int, warmup: int, rollouts: int | None) -> np.ndarray:
+def plan_times(task, optimizer: str, num_samples: int, warmup: int, rollouts: int | None) -> np.ndarray:
+    """`task`: a registered task's name, or a Task instance (e.g. `CaltechLeapCube(fingertips="cylinder")`) to time with the shipped overrides of its name."""
     import torch
 
-    from judo_amd.controller import make_controller
+    from judo_amd.controller import make_controller, make_controller_for
 
-    ctrl = make_controller(task, optimizer)
+    ctrl = make_controller(task, optimizer) if isinstance(task, str) else make_controller_for(task, optimizer)
     if rollouts:
         ctrl.optimizer.config.num_rollouts = rollouts
     ctrl.reset()

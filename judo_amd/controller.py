@@ -940,13 +940,21 @@ def make_controller(init_task: str, init_optimizer: str, device: torch.device | 
         raise ValueError(f"Task {init_task} not found in task registry.")
     if init_optimizer not in opts:
         raise ValueError(f"Optimizer {init_optimizer} not found in optimizer registry.")
-    task = tasks[init_task][0]()
+    return make_controller_for(tasks[init_task][0](), init_optimizer, device=device, group=group)
+
+
+def make_controller_for(task: Task, init_optimizer: str, device: torch.device | None = None, group: Any = None) -> Controller:
+    """The same construction around a task INSTANCE (one built with constructor arguments, e.g. `CaltechLeapCube(fingertips="cylinder")`): the optimizer and
+    controller overrides registered for the task's name."""
+    opts = get_registered_optimizers()
+    if init_optimizer not in opts:
+        raise ValueError(f"Optimizer {init_optimizer} not found in optimizer registry.")
     opt_cls, opt_cfg_cls = opts[init_optimizer]
     opt_cfg = opt_cfg_cls()
-    opt_cfg.set_override(init_task)
+    opt_cfg.set_override(task.name)
     optimizer = opt_cls(opt_cfg, task.nu)
     ctrl_cfg = ControllerConfig()
-    ctrl_cfg.set_override(init_task)
+    ctrl_cfg.set_override(task.name)
     return Controller(ctrl_cfg, task, optimizer, device=device, group=group)
 
 

@@ -1,4 +1,5 @@
 // jh_api.hip -- C-ABI entry points of libjudo_amd.so (argument checks, model handles, dispatch).
+#include <cmath>
 #include <cstdlib>
 #include <cstring>
 
@@ -17,6 +18,27 @@ void jh_set_error(const char* fmt, ...) {
 extern "C" const char* jh_last_error(void) { return g_err; }
 extern "C" int jh_version(void) { return 100; }
 
+// Cylinder geoms of an articulated image (type code 5 in the kernel's geom table, header I[5] records behind the bodies, blocks and actuators): their number, or -1 with
+// the error set when a record is malformed.  Only the leap family has a kernel that collides them (jh_engine_v5_cyl.hip); jh_model_create refuses them elsewhere.
+static int image_cylinders(const jh_blob_header& h, const float* F, const int* I) {
+  constexpr int HEADER = 24, BODY_I = 6, BODY_F = 32, BLOCK_I = 4, DOF_F = 20, ACT_I = 2, ACT_F = 8, GEOM_I = 2, GEOM_F = 20, GF_RBOUND = 15;
+  if (h.nint < (uint32_t)HEADER || h.nfloat < (uint32_t)HEADER) return 0;  // (not an engine image: the launchers refuse it)
+  const long NM = I[0], NBLK = I[1], nv = I[2], nu = I[4], NG = I[5];
+  if (NM < 0 || NBLK < 0 || nv < 0 || nu < 0 || NG < 0) return 0;
+  const long oI = HEADER + NM * BODY_I + NBLK * BLOCK_I + nu * ACT_I, oF = HEADER + NM * BODY_F + nv * DOF_F + nu * ACT_F;
+  if (oI + NG * GEOM_I > (long)h.nint || oF + NG * GEOM_F > (long)h.nfloat) return 0;
+  int n = 0;
+  for (long g = 0; g < NG; g++) {
+    if (I[oI + g * GEOM_I + 1] != 5) continue;
+    const float* f = F + oF + g * GEOM_F;
+    const float r = f[0], L = f[1], rb = f[GF_RBOUND], want = sqrtf(r * r + L * L);
+    if (!(r > 0.f) || !(L > 0.f) || f[2] != 0.f) { jh_set_error("model_create: cylinder geom %ld: sizes must be (radius > 0, half length > 0, 0), got (%g, %g, %g)", g, r, L, f[2]); return -1; }
+    if (!(fabsf(rb - want) <= 1e-5f * want)) { jh_set_error("model_create: cylinder geom %ld: bounding radius %g is not sqrt(r^2 + L^2) = %g", g, rb, want); return -1; }
+    n++;
+  }
+  return n;
+}
+
 extern "C" int jh_model_create(const void* blob, size_t nbytes, int device, jh_model** out) {
   JH_REQUIRE(blob && out, "model_create: null pointer");
   if (nbytes < sizeof(jh_blob_header)) { jh_set_error("model_create: blob too small (%zu bytes)", nbytes); return JH_ERR_BLOB; }
@@ -29,10 +51,19 @@ extern "C" int jh_model_create(const void* blob, size_t nbytes, int device, jh_m
   if (h.kind == JH_TASK_CARTPOLE && h.nfloat < CP_NPARAM) { jh_set_error("model_create: cartpole blob has %u floats, need %d", h.nfloat, CP_NPARAM); return JH_ERR_BLOB; }
   if (h.kind == JH_TASK_CYLINDER_PUSH && h.nfloat < CY_NPARAM) { jh_set_error("model_create: cylinder blob has %u floats, need %d", h.nfloat, CY_NPARAM); return JH_ERR_BLOB; }
   if (h.ntaskparam > JH_MAX_TASK_PARAMS) { jh_set_error("model_create: too many task params"); return JH_ERR_BLOB; }
+  int cylinders = 0;
+  if (h.kind == JH_TASK_LEAP_CUBE || h.kind == JH_TASK_FR3_PICK) {
+    const char* q = (const char*)blob + sizeof(h);
+    std::vector<float> F((const float*)q, (const float*)q + h.nfloat);  // (copies: the blob need not be aligned)
+    std::vector<int> I((const int*)(q + 4 * (size_t)h.nfloat), (const int*)(q + 4 * (size_t)h.nfloat) + h.nint);
+    cylinders = image_cylinders(h, F.data(), I.data());
+    if (cylinders < 0) return JH_ERR_BLOB;
+    if (cylinders > 0 && h.kind != JH_TASK_LEAP_CUBE) { jh_set_error("model_create: %d cylinder geoms, and only the leap kernel has a cylinder build", cylinders); return JH_ERR_BLOB; }
+  }
   JH_HIP(hipSetDevice(device));
   jh_model* m = new jh_model();
   m->device = device; m->kind = (int)h.kind; m->nq = h.nq; m->nv = h.nv; m->nu = h.nu; m->ns = h.ns; m->ntaskparam = h.ntaskparam;
-  m->nf = h.nfloat; m->ni = h.nint; m->d_f = nullptr; m->d_i = nullptr; m->d_stats = nullptr; m->kernel_gen = (h.kind == JH_TASK_LEAP_CUBE || h.kind == JH_TASK_FR3_PICK) ? 3 : 2; m->self_collision = 1; m->contact_capacity = 48;
+  m->nf = h.nfloat; m->ni = h.nint; m->d_f = nullptr; m->d_i = nullptr; m->d_stats = nullptr; m->kernel_gen = (h.kind == JH_TASK_LEAP_CUBE || h.kind == JH_TASK_FR3_PICK) ? 3 : 2; m->self_collision = 1; m->contact_capacity = cylinders > 0 ? 64 : 48; m->cylinders = cylinders;
   { const char* e = getenv("JUDO_AMD_PLAN_STEP_LAUNCHES"); m->plan_step_launches = (e && e[0] == '2') ? 2 : 0; }  // (the environment sets the default; jh_model_set_plan_step_launches changes it per model)
   const char* p = (const char*)blob + sizeof(h);
   m->h_f.assign((const float*)p, (const float*)p + h.nfloat);
@@ -115,6 +146,10 @@ extern "C" int jh_model_set_kernel(jh_model* m, int generation) {
     jh_set_error("model_set_kernel: generations 1 and 2 are cross-check kernels of the test build (libjudo_amd_xcheck.so), not part of this library");
     return JH_ERR_UNSUPPORTED;
   }
+  if (generation != 3 && m->cylinders > 0) {
+    jh_set_error("model_set_kernel: the image holds %d cylinder geoms; only generation 3 (the cylinder build of the leap kernel) collides them", m->cylinders);
+    return JH_ERR_UNSUPPORTED;
+  }
   m->kernel_gen = generation;
   return JH_OK;
 }
@@ -137,7 +172,17 @@ extern "C" int jh_model_trace_layout(const jh_model* m, int* out) {
 extern "C" int jh_model_set_contact_capacity(jh_model* m, int contacts) {
   JH_REQUIRE(m != nullptr, "model_set_contact_capacity: null pointer");
   JH_REQUIRE(m->kind == JH_TASK_LEAP_CUBE && (contacts == 48 || contacts == 64), "model_set_contact_capacity: the leap_cube kernel is built for 48 and for 64 contacts per rollout (got %d)", contacts);
+  JH_REQUIRE(m->cylinders == 0 || contacts == 64, "model_set_contact_capacity: the cylinder build of the leap kernel holds 64 contacts per rollout (got %d)", contacts);
   m->contact_capacity = contacts;
+  return JH_OK;
+}
+
+extern "C" int jh_model_build(const jh_model* m, int* out) {
+  JH_REQUIRE(m && out, "model_build: null pointer");
+  out[0] = m->kernel_gen;
+  out[1] = m->kind == JH_TASK_LEAP_CUBE && m->kernel_gen == 3 ? m->contact_capacity : 0;
+  out[2] = m->kind == JH_TASK_LEAP_CUBE && m->kernel_gen == 3 && m->cylinders > 0 ? 1 : 0;
+  out[3] = m->cylinders;
   return JH_OK;
 }
 
@@ -286,7 +331,8 @@ extern "C" int jh_rollout_cost_traced(const jh_model* m, const float* x0, const 
   if (m->kind == JH_TASK_CARTPOLE || m->kind == JH_TASK_CYLINDER_PUSH)
     return jh_simple_rollout_cost(m, x0, nominal, noise, ldn, sigma, W, lohi, tp, N, n_offset, H, K, costs, knots_out, trace, st);
   if (m->kind == JH_TASK_LEAP_CUBE && m->kernel_gen == 3)
-    return m->contact_capacity > 48 ? jh_engine5_rollout_cost_cap64(m, x0, nominal, noise, ldn, sigma, W, lohi, tp, N, n_offset, H, K, costs, knots_out, trace, st)
+    return m->cylinders > 0         ? jh_engine5_rollout_cost_cyl(m, x0, nominal, noise, ldn, sigma, W, lohi, tp, N, n_offset, H, K, costs, knots_out, trace, st)
+           : m->contact_capacity > 48 ? jh_engine5_rollout_cost_cap64(m, x0, nominal, noise, ldn, sigma, W, lohi, tp, N, n_offset, H, K, costs, knots_out, trace, st)
                                     : jh_engine5_rollout_cost(m, x0, nominal, noise, ldn, sigma, W, lohi, tp, N, n_offset, H, K, costs, knots_out, trace, st);
   if (m->kind == JH_TASK_FR3_PICK && m->kernel_gen == 3) return jh_engine6_rollout_cost(m, x0, nominal, noise, ldn, sigma, W, lohi, tp, phase, N, n_offset, H, K, costs, knots_out, trace, st);
   JH_REQUIRE(trace == nullptr, "rollout_cost_traced: only the product kernels (generation 3, cartpole, cylinder_push) write trace sensors");
@@ -403,7 +449,7 @@ extern "C" int jh_rollout_materialize(const jh_model* m, const float* x0, int x0
   hipStream_t st = (hipStream_t)stream;
   if (m->kind == JH_TASK_CARTPOLE || m->kind == JH_TASK_CYLINDER_PUSH) return jh_simple_materialize(m, x0, x0_batched, controls, N, H, states, sensors, st);
   if (m->kind == JH_TASK_LEAP_CUBE && m->kernel_gen == 3)
-    return m->contact_capacity > 48 ? jh_engine5_materialize_cap64(m, x0, x0_batched, controls, N, H, states, sensors, st) : jh_engine5_materialize(m, x0, x0_batched, controls, N, H, states, sensors, st);
+    return m->cylinders > 0 ? jh_engine5_materialize_cyl(m, x0, x0_batched, controls, N, H, states, sensors, st) : m->contact_capacity > 48 ? jh_engine5_materialize_cap64(m, x0, x0_batched, controls, N, H, states, sensors, st) : jh_engine5_materialize(m, x0, x0_batched, controls, N, H, states, sensors, st);
   if (m->kind == JH_TASK_FR3_PICK && m->kernel_gen == 3) return jh_engine6_materialize(m, x0, x0_batched, controls, N, H, states, sensors, st);
   if (!g_xcheck.rollout_materialize) { jh_set_error("rollout_materialize: no kernel for this model / generation in this library"); return JH_ERR_UNSUPPORTED; }
   return g_xcheck.rollout_materialize(m, m->kernel_gen, x0, x0_batched, controls, N, H, states, sensors, stream);

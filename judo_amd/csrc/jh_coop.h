@@ -363,6 +363,11 @@ __device__ __forceinline__ void collide_cylinder_sphere(Sink& sk, const float* p
 constexpr int CVX_MAXV = 40, CVX_MAXF = 2 * CVX_MAXV, CVX_GJK_IT = 48;
 constexpr float CVX_TOL = 1e-6f;
 struct CvxShape { int type; float s0, s1, s2; float p[3], R[9]; };
+// REORTHO (the leap kernel's cylinder build; the tree kernel's instantiations leave it off and compile to the code they had): the part of d across a cylinder's axis is
+// made orthogonal to the axis a second time.  For d within about 1e-5 rad of the axis that part is the rounding residue of d - (d . ax) ax, which is not orthogonal to
+// the axis; scaled to the radius it puts the "support point" up to a quarter of a millimetre above the cap of a 14 mm cylinder, outside the shape, and the polytope
+// built on it misses a minimum translation that runs along the axis (a cap contact).  A rim point in whatever direction the residue has is a valid support point.
+template <bool REORTHO = false>
 __device__ __forceinline__ void cvx_support(const CvxShape& s, const float* d, float* out) {
   out[0] = s.p[0]; out[1] = s.p[1]; out[2] = s.p[2];
   if (s.type == 6) {
@@ -378,15 +383,17 @@ __device__ __forceinline__ void cvx_support(const CvxShape& s, const float* d, f
     out[0] = fmaf(ax[0], e, out[0]); out[1] = fmaf(ax[1], e, out[1]); out[2] = fmaf(ax[2], e, out[2]);
     float r[3] = {d[0], d[1], d[2]};
     if (s.type == 5) { r[0] -= da * ax[0]; r[1] -= da * ax[1]; r[2] -= da * ax[2]; }
+    if constexpr (REORTHO) { if (s.type == 5) { const float db = dot3(r, ax); r[0] -= db * ax[0]; r[1] -= db * ax[1]; r[2] -= db * ax[2]; } }
     const float l = sqrtf(dot3(r, r));
     if (l > 1e-7f * (fabsf(da) + l)) { const float k = s.s0 / l; out[0] = fmaf(r[0], k, out[0]); out[1] = fmaf(r[1], k, out[1]); out[2] = fmaf(r[2], k, out[2]); }
   }
 }
 struct CvxVert { float w[3], a[3]; };  // w = a - b on the Minkowski difference A - B; a the support point of A (b follows)
+template <bool REORTHO = false>
 __device__ __forceinline__ void cvx_vertex(const CvxShape& A, const CvxShape& B, const float* d, CvxVert& v) {
   const float nd[3] = {-d[0], -d[1], -d[2]};
   float b[3];
-  cvx_support(A, d, v.a); cvx_support(B, nd, b);
+  cvx_support<REORTHO>(A, d, v.a); cvx_support<REORTHO>(B, nd, b);
   v.w[0] = v.a[0] - b[0]; v.w[1] = v.a[1] - b[1]; v.w[2] = v.a[2] - b[2];
 }
 struct CvxFace { float n[3], dist; int v; };  // v: vertex indices 0-7 / 8-15 / 16-23, bit 31 dead
@@ -402,11 +409,12 @@ __device__ __forceinline__ bool cvx_face(const CvxVert* V, int i, int j, int k, 
   return true;
 }
 // GJK on A - B, overlap only (the oracle's ccd_gjk): true with four vertices around the origin in sx[0..3]
+template <bool REORTHO = false>
 __device__ __forceinline__ bool cvx_gjk(const CvxShape& A, const CvxShape& B, CvxVert* sx) {
   float d[3] = {B.p[0] - A.p[0], B.p[1] - A.p[1], B.p[2] - A.p[2]};
   if (dot3(d, d) < 1e-20f) { d[0] = 1.f; d[1] = 0.f; d[2] = 0.f; }
   int n = 1;
-  cvx_vertex(A, B, d, sx[0]);
+  cvx_vertex<REORTHO>(A, B, d, sx[0]);
   d[0] = -sx[0].w[0]; d[1] = -sx[0].w[1]; d[2] = -sx[0].w[2];
   for (int it = 0; it < CVX_GJK_IT; it++) {
     if (dot3(d, d) < 1e-24f) {  // the origin lies on the simplex: any direction that grows it
@@ -418,7 +426,7 @@ __device__ __forceinline__ bool cvx_gjk(const CvxShape& A, const CvxShape& B, Cv
       }
       d[0] = e[0]; d[1] = e[1]; d[2] = e[2];
     }
-    CvxVert nv; cvx_vertex(A, B, d, nv);
+    CvxVert nv; cvx_vertex<REORTHO>(A, B, d, nv);
     if (dot3(nv.w, d) < 0.f) return false;  // the new support point did not pass the origin: separated
     sx[3] = sx[2]; sx[2] = sx[1]; sx[1] = sx[0]; sx[0] = nv; n++;
     const float* a = sx[0].w; const float* b = sx[1].w;
@@ -455,13 +463,15 @@ __device__ __forceinline__ bool cvx_gjk(const CvxShape& A, const CvxShape& B, Cv
   }
   return false;
 }
-// geom A (capsule / box) against geom B (the cylinder): at most one contact, normal from A to B
-template <class Sink>
+// geom A (capsule / box) against geom B (the cylinder): at most one contact, normal from A to B.  (Either side may be a box, a capsule or a cylinder: the leap kernel's
+// cylinder build calls it with the cylinder first, MuJoCo's order of a box-cylinder pair, and with two cylinders.)  STOP_NM: the stop in nanometres, CVX_TOL = 1 000 by default.
+template <class Sink, bool REORTHO = false, int STOP_NM = 1000>
 __device__ __noinline__ void collide_convex_cylinder(Sink& sk, const CvxShape& A, const CvxShape& B) {
+  constexpr float STOP = STOP_NM == 1000 ? CVX_TOL : 1e-9f * (float)STOP_NM;
   CvxVert V[CVX_MAXV];
   CvxFace F[CVX_MAXF];
   int ed[CVX_MAXF];
-  if (!cvx_gjk(A, B, V)) return;
+  if (!cvx_gjk<REORTHO>(A, B, V)) return;
   int nv = 4, nf = 0;
   {
     const int idx[4][3] = {{0, 1, 2}, {0, 2, 3}, {0, 3, 1}, {1, 3, 2}};
@@ -480,8 +490,8 @@ __device__ __noinline__ void collide_convex_cylinder(Sink& sk, const CvxShape& A
     best = -1;
     for (int f = 0; f < nf; f++) if (F[f].v >= 0 && (best < 0 || F[f].dist < F[best].dist)) best = f;
     if (best < 0) return;
-    CvxVert nw; cvx_vertex(A, B, F[best].n, nw);
-    if (dot3(nw.w, F[best].n) - F[best].dist < CVX_TOL || nv >= CVX_MAXV) break;
+    CvxVert nw; cvx_vertex<REORTHO>(A, B, F[best].n, nw);
+    if (dot3(nw.w, F[best].n) - F[best].dist < STOP || nv >= CVX_MAXV) break;
     int ne = 0;  // the faces the new point sees go; their unshared edges form the horizon
     for (int f = 0; f < nf; f++) {
       if (F[f].v < 0 || dot3(F[f].n, nw.w) - F[f].dist <= 0.f) continue;

@@ -140,6 +140,15 @@ constexpr int NCH = 4, NLK = 4;
 #ifndef JH_V5_NS1PROB
 #define JH_V5_NS1PROB 0.5
 #endif
+#ifndef JH_V5_CYL
+#define JH_V5_CYL 0  // 1 (jh_engine_v5_cyl.hip): the build for an image that keeps caltech_leap_cube's fingertip cylinders (geom type 5: radius, half length along the geom's z).
+                     // Sphere against cylinder is MuJoCo's primitive; box and cylinder against cylinder go through the bounded fp32 GJK + EPA of jh_coop.h, a call that is
+                     // not inlined and keeps its polytope in the lane's private memory -- behind a test that only a lane with such a pair passes.  0: no line of it is compiled.
+#endif
+#ifndef JH_V5_CVX_STOP_NM
+#define JH_V5_CVX_STOP_NM 1000  // the stop of this build's GJK + EPA in nanometres (jh_coop.h: 1 000 = CVX_TOL, the tree kernel's); profiles/caltech_cylinder.md has 1 000 against 100
+#endif
+constexpr int GCYL = 5;
 constexpr int NSLOT = JH_V5_NSLOT;  // contact slots per lane of the common case: steps with at most 16 * NSLOT contacts in every rollout of the wave
 constexpr int NSBIG = JH_V5_NSBIG;  // ... of the rare case (6e-4 of the rollout-steps of the headline workload): the wave runs a second copy of the solver with this many slots
 #ifndef JH_V5_NSLDS
@@ -234,6 +243,13 @@ struct LeapSink {  // contacts of one geom pair: sides packed as A | B << 8; `fl
     push_contact(pc, pos, nn, dist, sides, mu, tran);
   }
 };
+
+#if JH_V5_CYL
+struct CvxOne {  // the one contact of collide_convex_cylinder
+  float pos[3], n[3], dist; bool hit;
+  __device__ __forceinline__ void push(const float* p, const float* nn, float d) { for (int k = 0; k < 3; k++) { pos[k] = p[k]; n[k] = nn[k]; } dist = d; hit = true; }
+};
+#endif
 
 // ------------------------------------------------------------------------------------------------ per-lane contact slot (27 registers)
 struct Slot {
@@ -813,12 +829,23 @@ __global__ __launch_bounds__(WAVE * WPB, JH_V5_WAVES_PER_EU) JH_V5_REGATTR void 
         const float dc[3] = {gp[0] - qc[0], gp[1] - qc[1], gp[2] - qc[2]}, rs = rb + crb;
         float cl[3]; mulMTV(cl, Rc, dc);
         bool hit = (gid >= 0) & (dot3(dc, dc) <= rs * rs) & (fabsf(cl[0]) <= chs[0] + rb) & (fabsf(cl[1]) <= chs[1] + rb) & (fabsf(cl[2]) <= chs[2] + rb);
+#if JH_V5_CYL
+        if (hit && gtype != GSPHERE) {  // (a cylinder's box in its own frame: (r, r, L))
+          const bool cyl = gtype == GCYL;
+          const float gh[3] = {gf[GF_SIZE], cyl ? gf[GF_SIZE] : gf[GF_SIZE + 1], cyl ? gf[GF_SIZE + 1] : gf[GF_SIZE + 2]};
+          float gR[9], gl[3];
+          if (gbody < 0) { for (int k = 0; k < 9; k++) gR[k] = gf[GF_R + k]; } else mulMM(gR, Rwr, gf + GF_R);
+          mulMTV(gl, gR, dc);
+          hit = fabsf(gl[0]) <= gh[0] + crb && fabsf(gl[1]) <= gh[1] + crb && fabsf(gl[2]) <= gh[2] + crb;
+        }
+#else
         if (hit && gtype == GBOX) {
           float gR[9], gl[3];
           if (gbody < 0) { for (int k = 0; k < 9; k++) gR[k] = gf[GF_R + k]; } else mulMM(gR, Rwr, gf + GF_R);
           mulMTV(gl, gR, dc);
           hit = fabsf(gl[0]) <= gf[GF_SIZE] + crb && fabsf(gl[1]) <= gf[GF_SIZE + 1] + crb && fabsf(gl[2]) <= gf[GF_SIZE + 2] + crb;
         }
+#endif
         unsigned m16 = (unsigned)((__ballot(hit) >> (16 * r)) & 0xFFFFull);
         int pos = nh + __popc(m16 & ((1u << l) - 1u));
         if (hit && pos < MAXHIT) S.hits[pos] = (unsigned short)gid;
@@ -912,9 +939,15 @@ __global__ __launch_bounds__(WAVE * WPB, JH_V5_WAVES_PER_EU) JH_V5_REGATTR void 
               float RA[9], RB[9];
               if (static_code(ba)) { for (int k = 0; k < 9; k++) RA[k] = fa[GF_R + k]; } else mulMM(RA, S.xR[ba], fa + GF_R);
               mulMM(RB, S.xR[bb], fb + GF_R);
+#if JH_V5_CYL
+              const int tyA = sGeomI[ga * GEOM_I + 1], tyB = sGeomI[gb * GEOM_I + 1];  // (a cylinder counts as the box (r, r, L) around it)
+              const float hA[3] = {fa[GF_SIZE], tyA == GBOX ? fa[GF_SIZE + 1] : fa[GF_SIZE], tyA == GBOX ? fa[GF_SIZE + 2] : (tyA == GCYL ? fa[GF_SIZE + 1] : fa[GF_SIZE])};
+              const float hB[3] = {fb[GF_SIZE], tyB == GBOX ? fb[GF_SIZE + 1] : fb[GF_SIZE], tyB == GBOX ? fb[GF_SIZE + 2] : (tyB == GCYL ? fb[GF_SIZE + 1] : fb[GF_SIZE])};
+#else
               const bool sphA = sGeomI[ga * GEOM_I + 1] != GBOX, sphB = sGeomI[gb * GEOM_I + 1] != GBOX;
               const float hA[3] = {fa[GF_SIZE], sphA ? fa[GF_SIZE] : fa[GF_SIZE + 1], sphA ? fa[GF_SIZE] : fa[GF_SIZE + 2]};
               const float hB[3] = {fb[GF_SIZE], sphB ? fb[GF_SIZE] : fb[GF_SIZE + 1], sphB ? fb[GF_SIZE] : fb[GF_SIZE + 2]};
+#endif
               hit = obb_face_overlap(ca, RA, hA, cb, RB, hB);
             }
           }
@@ -962,6 +995,28 @@ __global__ __launch_bounds__(WAVE * WPB, JH_V5_WAVES_PER_EU) JH_V5_REGATTR void 
           // contact parameters: friction = the larger of the two geoms' (the cube's is folded into GF_MU), R from the two bodies' inverse weights
           const float mu = (!SELF || ga < 0) ? fb[GF_MU] : fmaxf(mua, fb[GF_MUOWN]);
           LeapSink sk{pc, codea | ((bodyb < 0 ? 0 : bodyb) << 8), mu, trana + fb[GF_TRAN], false};
+#if JH_V5_CYL
+          // pairs with a cylinder.  The routines get the two geoms in MuJoCo's order (mj_collideGeoms: the geom of the lower type is geom 1; sphere 2 < cylinder 5 <
+          // box 6), as the oracle's collision() has it; the pool stores the normal from side A to side B, so `flip` where that order swaps the sides.  The convex
+          // routine gives at most one contact: a capturing sink, pushed here, keeps the pool's LDS atomics out of the non-inlined call.
+          if (ta == GCYL || tb == GCYL) {
+            const bool cylA = ta == GCYL;
+            if ((cylA ? tb : ta) == GSPHERE) {  // cylinder-sphere (jh_coop.h: the primitive's normal runs from the cylinder to the sphere)
+              if (cylA) collide_cylinder_sphere(sk, pA, RA, hA[0], hA[1], pB, fb[GF_SIZE]);
+              else { sk.flip = true; collide_cylinder_sphere(sk, pB, RB, fb[GF_SIZE], fb[GF_SIZE + 1], pA, hA[0]); }
+            } else {
+              // geom 1 of the convex routine: the cylinder of a box-cylinder pair; of two cylinders, side A
+              const bool swap = !cylA;
+              CvxShape X{swap ? tb : ta, swap ? fb[GF_SIZE] : hA[0], swap ? fb[GF_SIZE + 1] : hA[1], swap ? fb[GF_SIZE + 2] : hA[2], {}, {}};
+              CvxShape Y{swap ? ta : tb, swap ? hA[0] : fb[GF_SIZE], swap ? hA[1] : fb[GF_SIZE + 1], swap ? hA[2] : fb[GF_SIZE + 2], {}, {}};
+              for (int k = 0; k < 3; k++) { X.p[k] = swap ? pB[k] : pA[k]; Y.p[k] = swap ? pA[k] : pB[k]; }
+              for (int k = 0; k < 9; k++) { X.R[k] = swap ? RB[k] : RA[k]; Y.R[k] = swap ? RA[k] : RB[k]; }
+              CvxOne one{{0.f, 0.f, 0.f}, {0.f, 0.f, 0.f}, 0.f, false};
+              collide_convex_cylinder<CvxOne, true, JH_V5_CVX_STOP_NM>(one, X, Y);
+              if (one.hit) { sk.flip = swap; sk.push(one.pos, one.n, one.dist); }
+            }
+          } else
+#endif
           if ((!SELF || ta == GBOX) && tb == GBOX) collide_box_box(sk, pA, RA, hA, pB, RB, fb + GF_SIZE);
           else if (!SELF || ta == GBOX) collide_box_sphere(sk, pA, RA, hA, pB, fb[GF_SIZE]);
           else if (tb == GBOX) { sk.flip = true; collide_box_sphere(sk, pB, RB, fb + GF_SIZE, pA, hA[0]); }
@@ -1935,6 +1990,7 @@ bool model_is_leap(const jh_model* m) {
 int JH_V5_NAME(jh_engine5_rollout_cost)(const jh_model* m, const float* x0, const float* nominal, const float* noise, int ldn, const float* sigma, const float* W,
                             const float* lohi, const float* tp, int N, int n_offset, int H, int K, float* costs, float* knots_out, float* trace, hipStream_t st) {
   if (!model_is_leap(m)) { jh_set_error("rollout_cost: the cooperative engine kernel is instantiated for leap_cube only"); return JH_ERR_UNSUPPORTED; }
+  if ((m->cylinders > 0) != (JH_V5_CYL != 0)) { jh_set_error("rollout_cost: an image with cylinder geoms runs on the cylinder build of the leap kernel and no other image does (%d cylinders)", m->cylinders); return JH_ERR_UNSUPPORTED; }
 #if JH_V5_KNOTS_LDS
   JH_REQUIRE(K <= MAXK, "rollout_cost: the cooperative leap kernel keeps at most 8 knots per actuator (K=%d)", K);
 #endif
@@ -1954,6 +2010,7 @@ int JH_V5_NAME(jh_engine5_rollout_cost)(const jh_model* m, const float* x0, cons
 int JH_V5_NAME(jh_engine5_materialize)(const jh_model* m, const float* x0, int x0_batched, const float* controls, int N, int H, float* states, float* sensors,
                            hipStream_t st) {
   if (!model_is_leap(m)) { jh_set_error("rollout_materialize: the cooperative engine kernel is instantiated for leap_cube only"); return JH_ERR_UNSUPPORTED; }
+  if ((m->cylinders > 0) != (JH_V5_CYL != 0)) { jh_set_error("rollout_materialize: an image with cylinder geoms runs on the cylinder build of the leap kernel and no other image does (%d cylinders)", m->cylinders); return JH_ERR_UNSUPPORTED; }
   const int dshift = jh_latency_shift(N, RPW); const int per_block = (RPW >> dshift) * JH_V5_WPB;
   int grid = (N + per_block - 1) / per_block;
   float* ovf = nullptr;  // one row per rollout for the contacts above the LDS pool: stream-ordered allocation, no state on the model handle

@@ -95,6 +95,9 @@ class GpuModel:
         # contacts per rollout-step at 48, the SHIPPED workloads of the caged / primitive-hand variants 2e-4 .. 4e-4 (tools/diag/shipped_config_stats.py): those take 64
         self.closed_form = self.task in ("cartpole", "cylinder_push")  # jh_simple.hip: rollout kernels of ~50 us -- the plan step runs as one launch that reads its host block in place
         self.contact_capacity = 0
+        # caltech_leap_cube's fingertips as the kernel collides them: "sphere" (the stand-in of engine_model.kernel_stand_ins) or "cylinder" (the MJCF's geometry: an image
+        # that keeps the cylinders, and with it the cylinder build of the leap kernel, 64 contacts).  The library decides from the image; this reports what it chose.
+        self.fingertips = "cylinder" if self.build()["cylinder_build"] else "sphere"
         if self.desc.get("family", self.task) == "leap_cube":
             self.set_contact_capacity(48 if self.task == "leap_cube" else 64)
 
@@ -105,6 +108,12 @@ class GpuModel:
         self.kernel_generation = int(generation)
         # only generation 3 of the leap family models the hand's own contacts: what bench.py / tests report must follow the kernel actually selected
         self.self_collision = self._self_collision_requested and self.kernel_generation == 3 and self.desc.get("family", self.task) == "leap_cube"
+
+    def build(self) -> dict:
+        """`jh_model_build`: which build of its kernel this model runs."""
+        out = (C.c_int * 4)()
+        _lib.check(_lib.lib().jh_model_build(self.handle, out), "jh_model_build")
+        return {"kernel_generation": int(out[0]), "contact_capacity": int(out[1]), "cylinder_build": bool(out[2]), "cylinders": int(out[3])}
 
     def set_contact_capacity(self, contacts: int) -> None:
         """leap_cube family: 48 or 64 contacts per rollout (`jh_model_set_contact_capacity`)."""

@@ -30,7 +30,8 @@ from judo_amd.models import (
 )
 
 JFREE, JSLIDE, JHINGE = 0, 2, 3
-GBOX, GSPHERE, GCAPSULE = 6, 2, 3
+GBOX, GSPHERE, GCAPSULE, GCYLINDER = 6, 2, 3, 5  # (MuJoCo's geom type codes)
+GTYPE = {"box": GBOX, "sphere": GSPHERE, "capsule": GCAPSULE, "cylinder": GCYLINDER}
 MAX_MOVING, MAX_DOF, MAX_BLOCKS, MAX_BLOCK_DOF, MAX_GEOM, MAX_SITE = 20, 24, 4, 9, 80, 8
 
 # ints per record
@@ -250,8 +251,9 @@ def generic_pairs(desc: dict, fused: dict, st: dict, cube_only: bool | None = No
                 ia, ib = b, a
             ga, gb = geoms[ia], geoms[ib]
             ta, tb = ga["type"], gb["type"]
-            if not ((ta == "box" and tb in ("box", "sphere", "capsule")) or (ta == "sphere" and tb == "box") or (ta == "sphere" and tb == "sphere" and cube_only is False)):
-                continue  # (sphere-sphere: the fingertips of two fingers; only jh_engine_v5.hip collides the hand with itself)
+            round_ = ("sphere", "cylinder")  # (a cylinder is in `geoms` only when the image keeps the fingertips as the MJCF has them: pack_engine_model(fingertips="cylinder"))
+            if not ((ta == "box" and tb in ("box", "sphere", "capsule", "cylinder")) or (ta in round_ and tb == "box") or (ta in round_ and tb in round_ and cube_only is False)):
+                continue  # (sphere-sphere, and cylinder against sphere or cylinder: the fingertips of two fingers; only jh_engine_v5.hip collides the hand with itself)
             ba, bb = ga["orig_body"], gb["orig_body"]
             wa, wb = weld(ba), weld(bb)
             if tb == "capsule" and not (wa == 0 or ga["body"] == free_fused):
@@ -287,8 +289,31 @@ def kernel_stand_ins(desc: dict) -> dict:
     return out
 
 
-def pack_engine_model(desc: dict) -> bytes:
-    desc = kernel_stand_ins(desc)
+def bounding_box_half(g: dict) -> np.ndarray:
+    """Half sizes of the box around a geom in the geom's own frame (the broad phase's second level): a sphere's cube, a cylinder's (r, r, L), a box itself."""
+    if g["type"] == "sphere":
+        return np.array([g["size"][0]] * 3)
+    if g["type"] == "cylinder":
+        return np.array([g["size"][0], g["size"][0], g["size"][1]])
+    return np.array(g["size"][:3])
+
+
+def pack_engine_model(desc: dict, fingertips: str | None = None) -> bytes:
+    """`fingertips` (leap family; default: the description's own "fingertips" entry, else "sphere"): "sphere" packs `kernel_stand_ins(desc)`, the image every
+    build of the leap kernel runs; "cylinder" keeps the MJCF's cylinders -- type code 5, sizes (radius, half length), bounding radius sqrt(r^2 + L^2) -- for the
+    cylinder build (jh_engine_v5_cyl.hip), which jh_model_create selects by itself when it finds one."""
+    fingertips = desc.get("fingertips", "sphere") if fingertips is None else fingertips
+    if fingertips not in ("sphere", "cylinder"):
+        raise ValueError(f"fingertips must be 'sphere' or 'cylinder', got {fingertips!r}")
+    keep_cyl = fingertips == "cylinder" and desc.get("family", desc["task"]) == "leap_cube"
+    if fingertips == "cylinder" and not keep_cyl:
+        raise NotImplementedError("fingertips='cylinder': only the leap kernel has a cylinder build")
+    for g in desc["geoms"]:
+        if keep_cyl and g["type"] == "cylinder" and (len(g["size"]) != 2 or min(g["size"]) <= 0):
+            raise NotImplementedError(f"geom {g.get('name')}: a cylinder's size is (radius, half length), both positive")
+    kinds = ("box", "sphere", "cylinder") if keep_cyl else ("box", "sphere")  # what the leap kernel's narrow phase takes
+    if not keep_cyl:
+        desc = kernel_stand_ins(desc)
     orig = desc
     ref_frames = sensor_reference_frames(orig)
     dofw_o, bodyw_o = inverse_weights(orig)
@@ -308,7 +333,7 @@ def pack_engine_model(desc: dict) -> bytes:
         raise NotImplementedError("free body must carry exactly one box geom centred on the body origin")
     cube = cube_geoms[0]
     # contacts modelled: cube geom vs every other collision geom (hand self-collision: out of scope this round)
-    others = [g for g in desc["geoms"] if g["body"] != st["free"] and g["type"] in ("box", "sphere")]
+    others = [g for g in desc["geoms"] if g["body"] != st["free"] and g["type"] in kinds]
     # geoms sorted by owning body so that the kernel loads each body pose once
     others.sort(key=lambda g: (-1 if st["is_static"][g["body"]] else midx[g["body"]]))
     if len(others) > MAX_GEOM:
@@ -404,9 +429,9 @@ def pack_engine_model(desc: dict) -> bytes:
         else:
             pos, R, mb = np.array(g["pos"]), quat_to_mat(g["quat"]), midx[b]
         size = (list(g["size"]) + [0, 0, 0])[:3]
-        rb = size[0] if g["type"] == "sphere" else float(np.linalg.norm(size))
+        rb = size[0] if g["type"] == "sphere" else float(np.linalg.norm(size))  # (cylinder: size = (r, L, 0), so this is sqrt(r^2 + L^2))
         mu = max(MINMU, max(g["friction"][0], mu_cube))
-        I += [mb, GBOX if g["type"] == "box" else GSPHERE]
+        I += [mb, GTYPE[g["type"]]]
         F += [*size, *pos, *R.reshape(-1), rb, mu, bodyw_geom(g), max(MINMU, g["friction"][0]), 0]
     # ---- sites + sensors
     for s in sites:
@@ -453,7 +478,7 @@ def pack_engine_model(desc: dict) -> bytes:
         # hand self-collision (jh_engine_v5.hip): candidate geom pairs between hand bodies after MuJoCo's static filters (same welded body, parent-child,
         # the 18 excludes), grouped by body pair; a bounding sphere per body (static geometry: one sphere in world coordinates)
         oidx = {id(g): i for i, g in enumerate(others)}
-        og = [g for g in desc["geoms"] if g["type"] in ("box", "sphere")]
+        og = [g for g in desc["geoms"] if g["type"] in kinds]
         hh = [(a, b) for a, b in generic_pairs(orig, dict(desc, geoms=og), st, cube_only=False) if st["free"] not in (og[a]["body"], og[b]["body"])]
         # hand "bodies" of the self-collision tables: 1..16 = finger links; the static geometry is one body (0) when all of it collides with the same links
         # (leap_cube: the palm), else one body per set of static geoms with the same partners (caltech_leap_cube: floor + hand mount, palm): 0, 17, 18, 19
@@ -511,7 +536,7 @@ def pack_engine_model(desc: dict) -> bytes:
                     gp, gR = bpos + quat_to_mat(bquat) @ np.array(g["pos"]), quat_to_mat(quat_mul(bquat, g["quat"]))
                 else:
                     gp, gR = np.array(g["pos"]), quat_to_mat(g["quat"])
-                hs = np.array([g["size"][0]] * 3) if g["type"] == "sphere" else np.array(g["size"][:3])
+                hs = bounding_box_half(g)
                 for sx in (-1, 1):
                     for sy in (-1, 1):
                         for sz in (-1, 1):
@@ -522,7 +547,7 @@ def pack_engine_model(desc: dict) -> bytes:
             F += [*ctr, float(np.linalg.norm(half)), *half, 0.0]
     # ---- generic sections (reference kernel): every collision geom incl. the cube, explicit candidate pairs, joint
     # equalities, sensor frames with orientation, geom-distance sensors
-    allg = [g for g in desc["geoms"] if g["type"] in ("box", "sphere", "capsule")]
+    allg = [g for g in desc["geoms"] if g["type"] in kinds + ("capsule",)]
     gidx = {id(g): i for i, g in enumerate(allg)}
     pairs_all = generic_pairs(orig, dict(desc, geoms=allg), st)
     frames = []
@@ -548,7 +573,7 @@ def pack_engine_model(desc: dict) -> bytes:
             pos, R, mb = np.array(g["pos"]), quat_to_mat(g["quat"]), midx[b]
         size = (list(g["size"]) + [0, 0, 0])[:3]
         rb = size[0] if g["type"] == "sphere" else (size[0] + size[1] if g["type"] == "capsule" else float(np.linalg.norm(size)))
-        I += [mb, {"box": GBOX, "sphere": GSPHERE, "capsule": GCAPSULE}[g["type"]]]
+        I += [mb, GTYPE[g["type"]]]
         F += [*size, *pos, *R.reshape(-1), rb, max(MINMU, g["friction"][0]), bodyw_geom(g), 0, 0]
     for g in allg:  # per-geom solver parameters, mixed per contact (solref/solimp averaged, friction max)
         F += [*g["solref"], *clamp_solimp(g["solimp"]), 0.0]

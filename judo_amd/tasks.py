@@ -362,8 +362,16 @@ class CaltechLeapCube(LeapCube):
     name = "caltech_leap_cube"
     config_t = CaltechLeapCubeConfig
 
-    def __init__(self) -> None:
+    def __init__(self, fingertips: str = "sphere") -> None:
+        """`fingertips`: how the kernel collides the four fingertip cylinders of the MJCF (caltech_leap_components/leap_rh.xml: r = 14 mm, half length 7 mm).
+        "sphere" (default, what `make_controller` builds): spheres of the cylinders' radius, the stand-in of DESIGN.md section 8.  "cylinder": the cylinders
+        themselves, on the cylinder build of the leap kernel -- `gpu_model()`, a `GpuRolloutBackend` on it and a `Controller` on this task all run that build."""
+        if fingertips not in ("sphere", "cylinder"):
+            raise ValueError(f"fingertips must be 'sphere' or 'cylinder', got {fingertips!r}")
         Task.__init__(self)
+        self.fingertips = fingertips
+        if fingertips == "cylinder":
+            self.desc = dict(self.desc, fingertips="cylinder")  # (read by engine_model.pack_engine_model when the device image is packed)
         self.goal_pos = np.array([0.11, 0.005, 0.03])
         self.goal_quat = np.array([1.0, 0.0, 0.0, 0.0])
         self.qpos_home = CALTECH_LEAP_QPOS_HOME
