@@ -121,6 +121,12 @@ int jh_model_one_launch_max_knots(const jh_model* m, int H);
  * launch (a plan step it cannot hold -- K above the limit, or knots_out requested -- fails with JH_ERR_INVALID), 2 = always two.  The environment variable
  * JUDO_AMD_PLAN_STEP_LAUNCHES=2 makes 2 the default of every model created after it is set.  1 is refused for the articulated models, which always take two. */
 int jh_model_set_plan_step_launches(jh_model* m, int launches);
+/* How the fused leap_cube kernel of generation 3 (jh_rollout_cost, jh_plan_step ...) places its groups of four rollouts on the GPU: 0 = automatic (the default): a launch with
+ * more groups than the GPU holds waves of the kernel at once starts one workgroup per resident slot, and every wave draws group after group from a per-launch queue
+ * (persistent waves); a launch that fits at once, and every latency-mode launch, has one group per wave of its grid.  1 = always the static grid.  2 = the queue wherever
+ * the kernel has it (every fused launch outside the latency mode).  All three give the same bits: a rollout's result does not depend on the wave that runs it.  The
+ * environment variable JUDO_AMD_ROLLOUT_SCHEDULE=1 / 2 sets the default of every model created after it is set.  Accepted and without effect on the other models. */
+int jh_model_set_rollout_schedule(jh_model* m, int mode);
 
 /* Plan-step I/O in one call each (the two transfers of a plan step: < 2 KB down, the new nominal knots up): an asynchronous copy of `nbytes` from
  * pinned HOST memory to the device on `stream`; and an asynchronous copy from the device to pinned HOST memory followed by a wait for `stream`

@@ -64,6 +64,7 @@ extern "C" int jh_model_create(const void* blob, size_t nbytes, int device, jh_m
   jh_model* m = new jh_model();
   m->device = device; m->kind = (int)h.kind; m->nq = h.nq; m->nv = h.nv; m->nu = h.nu; m->ns = h.ns; m->ntaskparam = h.ntaskparam;
   m->nf = h.nfloat; m->ni = h.nint; m->d_f = nullptr; m->d_i = nullptr; m->d_stats = nullptr; m->kernel_gen = (h.kind == JH_TASK_LEAP_CUBE || h.kind == JH_TASK_FR3_PICK) ? 3 : 2; m->self_collision = 1; m->contact_capacity = cylinders > 0 ? 64 : 48; m->cylinders = cylinders;
+  { const char* e = getenv("JUDO_AMD_ROLLOUT_SCHEDULE"); m->rollout_schedule = (e && (e[0] == '1' || e[0] == '2')) ? e[0] - '0' : 0; }  // (the environment sets the default; jh_model_set_rollout_schedule changes it per model)
   { const char* e = getenv("JUDO_AMD_PLAN_STEP_LAUNCHES"); m->plan_step_launches = (e && e[0] == '2') ? 2 : 0; }  // (the environment sets the default; jh_model_set_plan_step_launches changes it per model)
   const char* p = (const char*)blob + sizeof(h);
   m->h_f.assign((const float*)p, (const float*)p + h.nfloat);
@@ -237,6 +238,12 @@ extern "C" int jh_model_set_plan_step_launches(jh_model* m, int launches) {
   JH_REQUIRE(m != nullptr && launches >= 0 && launches <= 2, "model_set_plan_step_launches: launches must be 0 (automatic), 1 or 2");
   JH_REQUIRE(launches != 1 || m->kind == JH_TASK_CARTPOLE || m->kind == JH_TASK_CYLINDER_PUSH, "model_set_plan_step_launches: only the closed-form models have a one-launch plan step");
   m->plan_step_launches = launches;
+  return JH_OK;
+}
+
+extern "C" int jh_model_set_rollout_schedule(jh_model* m, int mode) {
+  JH_REQUIRE(m != nullptr && mode >= 0 && mode <= 2, "model_set_rollout_schedule: mode must be 0 (automatic), 1 (static grid) or 2 (persistent waves wherever the kernel has them)");
+  m->rollout_schedule = mode;
   return JH_OK;
 }
 

@@ -24,6 +24,11 @@ using namespace jh_coop;
 
 namespace {
 
+#ifdef JH_V5_WAVESTAMP
+__device__ unsigned long long* g_wavestamp = nullptr;  // six words per group of four rollouts (see the kernel); set by jh_v5_wavestamp_buffer
+__device__ int g_wavestamp_cap = 0;
+#endif
+
 constexpr int G = 16, RPW = 4, WAVE = 64;
 constexpr int NCH = 4, NLK = 4;
 #ifndef JH_V5_LSMAX
@@ -520,7 +525,12 @@ __device__ __forceinline__ bool chain_elim_order(int cmask, int c, int& level, i
 }
 
 // ------------------------------------------------------------------------------------------------ the kernel
-template <bool MATERIALIZE, int WPB, bool SELF>
+// PERSIST (fused mode, launches with more groups of four rollouts than the GPU has wave slots): the launch has one workgroup per resident slot, and every wave runs a queue of
+// groups -- first the one of its own global wave index, then tickets drawn from `head` (zeroed by the launcher in front of the kernel) with one returning device-scope
+// atomicAdd by lane 0 -- until the tickets pass the group count.  A wave slot is then never held for a workgroup-mate's longer rollouts, and the launch drains over one
+// group's duration per wave instead of one workgroup's.  No wave waits for another, so nothing depends on which workgroups are resident.  The static instantiations
+// (PERSIST = false: a wave's group is its place in the grid, `head` unused) compile to the code they had without it.
+template <bool MATERIALIZE, int WPB, bool SELF, bool PERSIST = false>
 #ifdef JH_V5_NUM_VGPR  // (occupancy experiments: a register budget independent of what the LDS footprint allows)
 #define JH_V5_REGATTR __attribute__((amdgpu_num_vgpr(JH_V5_NUM_VGPR)))
 #else
@@ -531,7 +541,7 @@ __global__ __launch_bounds__(WAVE * WPB, JH_V5_WAVES_PER_EU) JH_V5_REGATTR void 
                                                    const float* __restrict__ sigma, const float* __restrict__ W, const float* __restrict__ lohi,
                                                    const float* __restrict__ tp, int N, int n_offset, int H, int K, float* __restrict__ costs,
                                                    float* __restrict__ knots_out, const float* __restrict__ controls, float* __restrict__ states,
-                                                   float* __restrict__ sensors, int* __restrict__ stats, int dshift, float* __restrict__ trace, float* __restrict__ ovf_all) {
+                                                   float* __restrict__ sensors, int* __restrict__ stats, int dshift_, float* __restrict__ trace, float* __restrict__ ovf_all, unsigned* __restrict__ head) {
 #ifdef JH_V5_X_DYNRS  // (occupancy experiments: the compiler does not see the per-rollout LDS, so the register budget follows JH_V5_WAVES_PER_EU alone)
   extern __shared__ __attribute__((aligned(16))) unsigned char dynRS[];
   RS* sRS = reinterpret_cast<RS*>(dynRS);
@@ -549,6 +559,12 @@ __global__ __launch_bounds__(WAVE * WPB, JH_V5_WAVES_PER_EU) JH_V5_REGATTR void 
   __shared__ float sBB[SELF ? NBC * 8 : 4];  // per hand body: bounding-box centre (body frame; static geometry: world), bounding radius, half sizes
 #if JH_V5_KNOTS_LDS
   __shared__ float sKnAll[MAXK * WAVE * WPB];
+#endif
+  __shared__ int sGrp[WPB];  // PERSIST: the group each wave is running (re-read in the step loop instead of held in a register; unused and dropped otherwise)
+  const int dshift = PERSIST ? 0 : dshift_;  // (the queue is for launches that fill the GPU: never the latency mode)
+#ifdef JH_V5_WAVESTAMP  // diagnostic builds (tools/diag/wave_schedule.py): per group of four rollouts, the 100 MHz wall clock at the wave's entry, after the staging barrier, at the
+                         // group's start and end, with the workgroup, the wave and the hardware id (__smid) that ran it
+  const unsigned long long ws_entry = wall_clock64(); unsigned long long ws_staged = ws_entry;
 #endif
   const int tid = threadIdx.x, wv = tid >> 6, lane = tid & 63, r = lane >> 4;
   int l = lane & 15, c = l >> 2, s = l & 3;  // (not const: see the top of the step loop)
@@ -585,7 +601,20 @@ __global__ __launch_bounds__(WAVE * WPB, JH_V5_WAVES_PER_EU) JH_V5_REGATTR void 
   // Rollout handled by this row of 16 lanes.  A launch too small to fill the GPU (`dshift` > 0, chosen by the launcher) gives a wave 4 >> dshift rollouts instead of four and
   // lets 1 << dshift rows compute the same one: the copies run the same arithmetic (a rollout's result does not depend on its wave-mates), only the first writes, and the
   // wave no longer waits for the slowest of four different Newton solves in every step -- the latency mode of small shards and of the reference's 32-rollout configurations.
-  const int n = ((blockIdx.x * WPB + wv) << (2 - dshift)) + (r >> dshift);
+  int grp = blockIdx.x * WPB + wv;  // the group of 4 >> dshift rollouts this wave runs: static launches have one per wave, its place in the grid
+  const int ngroups = (N + RPW - 1) / RPW;
+  if constexpr (PERSIST) {
+    __syncthreads();  // the only workgroup barrier: the model image is staged (once per workgroup, for all the groups its waves will run)
+#ifdef JH_V5_WAVESTAMP
+    ws_staged = wall_clock64();
+#endif
+  }
+  for (; !PERSIST || grp < ngroups;) {  // one pass for a static launch (it leaves at the bottom); the queue's groups otherwise.  (The body keeps the kernel's indentation.)
+  if constexpr (PERSIST) { if (lane == 0) sGrp[wv] = grp; }  // (published to the wave by the WSYNC in front of the step loop)
+#ifdef JH_V5_WAVESTAMP
+  const unsigned long long ws_start = wall_clock64();
+#endif
+  const int n = (grp << (2 - dshift)) + (r >> dshift);
   const bool live = n < N && (r & ((1 << dshift) - 1)) == 0;
   const int nc = n < N ? n : N - 1;
   const float h = gF[HF_DT], impratio = gF[HF_IMPRATIO], tol = gF[HF_TOL], lstol = gF[HF_LSTOL]; const int cap = (int)gF[HF_MAXITER];
@@ -635,7 +664,13 @@ __global__ __launch_bounds__(WAVE * WPB, JH_V5_WAVES_PER_EU) JH_V5_REGATTR void 
 #ifdef JH_V5_COUNT
   int cnt_dense = 0, cnt_it = 0, cnt_l2 = 0, cnt_bp = 0, cnt_hh = 0, cnt_cls[4] = {0, 0, 0, 0};
 #endif
-  __syncthreads();  // the only workgroup barrier: the model image is staged
+  if constexpr (PERSIST) WSYNC();  // (this group's S.ws / S.cmd / sGrp; the workgroup barrier was taken once, in front of the queue)
+  else {
+    __syncthreads();  // the only workgroup barrier: the model image is staged
+#ifdef JH_V5_WAVESTAMP
+    ws_staged = wall_clock64();
+#endif
+  }
 
   for (int hh = 0; hh < H; hh++) {
 #if JH_V5_OPAQUE_LANE
@@ -654,7 +689,8 @@ __global__ __launch_bounds__(WAVE * WPB, JH_V5_WAVES_PER_EU) JH_V5_REGATTR void 
 #else
       {  // (the rollout index is recomputed from an opaque copy of the lane id: held across the step loop it would cost a register the loop does not have)
         int lo_ = lane; OPAQUE(lo_);
-        const int n_ = ((blockIdx.x * WPB + wv) << (2 - dshift)) + ((lo_ >> 4) >> dshift), nc_ = n_ < N ? n_ : N - 1;
+        const int g_ = PERSIST ? sGrp[wv] : (int)(blockIdx.x * WPB + wv);
+        const int n_ = (g_ << (2 - dshift)) + ((lo_ >> 4) >> dshift), nc_ = n_ < N ? n_ : N - 1;
         for (int k = 0; k < K; k++) u = fmaf(W[hh * K + k], knot_at(k, l, nc_), u);
       }
 #endif
@@ -1966,6 +2002,19 @@ __global__ __launch_bounds__(WAVE * WPB, JH_V5_WAVES_PER_EU) JH_V5_REGATTR void 
   if (!MATERIALIZE && live && l == 0) costs[n] = acc / (float)H;
   if (stats && live && l == 0) { if (n_maxed) atomicAdd(stats + 1, n_maxed); atomicAdd(stats + 2, n_iters); atomicAdd(stats + 3, H); }
   if (stats && lane == 0 && live) { atomicAdd(stats + 20, n_wave_iters); atomicAdd(stats + 21, H); }
+#ifdef JH_V5_WAVESTAMP
+  if (lane == 0 && g_wavestamp && grp < g_wavestamp_cap) {
+    unsigned long long* w = g_wavestamp + (size_t)grp * 6;
+    w[0] = ((unsigned long long)blockIdx.x << 32) | ((unsigned long long)wv << 8) | (__smid() & 0xff); w[1] = ws_entry; w[2] = ws_staged; w[3] = ws_start; w[4] = wall_clock64(); w[5] = 1;
+  }
+#endif
+  if constexpr (!PERSIST) break;
+  else {  // the next ticket: one returning device-scope atomic per group (a vector atomic of lane 0, broadcast to the wave)
+    int t = 0;
+    if (lane == 0) t = (int)atomicAdd(head, 1u);
+    grp = (int)(gridDim.x * WPB) + __builtin_amdgcn_readfirstlane(t);
+  }
+  }
 }
 
 bool model_is_leap(const jh_model* m) {
@@ -1975,6 +2024,11 @@ bool model_is_leap(const jh_model* m) {
          && m->h_f.size() > (size_t)HF_CINERTIA + 2 && m->h_f[HF_CINERTIA] == m->h_f[HF_CINERTIA + 1] && m->h_f[HF_CINERTIA] == m->h_f[HF_CINERTIA + 2]  // isotropic cube inertia (JH_V5_WORLDROT)
 #endif
          ;
+}
+
+int device_cus(const jh_model* m) {  // (per call, of the model's device: a process may drive several)
+  int v = 0;
+  return (hipDeviceGetAttribute(&v, hipDeviceAttributeMultiprocessorCount, m->device) == hipSuccess && v > 0) ? v : 256;
 }
 
 }  // namespace
@@ -1987,6 +2041,13 @@ bool model_is_leap(const jh_model* m) {
 #ifndef JH_V5_NAME
 #define JH_V5_NAME(f) f
 #endif
+#ifdef JH_V5_WAVESTAMP
+extern "C" int JH_V5_NAME(jh_v5_wavestamp_buffer)(unsigned long long* buf, int groups) {  // diagnostic builds: where the kernel stores its stamps (nullptr: nowhere)
+  JH_HIP(hipMemcpyToSymbol(HIP_SYMBOL(g_wavestamp), &buf, sizeof(buf)));
+  JH_HIP(hipMemcpyToSymbol(HIP_SYMBOL(g_wavestamp_cap), &groups, sizeof(groups)));
+  return JH_OK;
+}
+#endif
 int JH_V5_NAME(jh_engine5_rollout_cost)(const jh_model* m, const float* x0, const float* nominal, const float* noise, int ldn, const float* sigma, const float* W,
                             const float* lohi, const float* tp, int N, int n_offset, int H, int K, float* costs, float* knots_out, float* trace, hipStream_t st) {
   if (!model_is_leap(m)) { jh_set_error("rollout_cost: the cooperative engine kernel is instantiated for leap_cube only"); return JH_ERR_UNSUPPORTED; }
@@ -1996,15 +2057,26 @@ int JH_V5_NAME(jh_engine5_rollout_cost)(const jh_model* m, const float* x0, cons
 #endif
   const int dshift = jh_latency_shift(N, RPW); const int per_block = (RPW >> dshift) * JH_V5_WPB;
   int grid = (N + per_block - 1) / per_block;
-  float* ovf = nullptr;  // one row per rollout for the contacts above the LDS pool: stream-ordered allocation, no state on the model handle
-  if (NOVF > 0) ovf = jh_launch_scratch(m, (size_t)N * NOVF * POOL_F * sizeof(float), st);  // (nullptr: the LDS capacity alone, drops and the fallback counted)
-  if (m->self_collision && m->h_i[17] > 0)
-    hipLaunchKernelGGL((k_leap_v5<false, JH_V5_WPB, true>), dim3(grid), dim3(WAVE * JH_V5_WPB), JH_V5_DYNBYTES, st, m->d_f, m->d_i, x0, 0, nominal, noise, ldn, sigma, W, lohi, tp, N, n_offset, H, K, costs,
-                       knots_out, (const float*)nullptr, (float*)nullptr, (float*)nullptr, m->d_stats, dshift, trace, ovf);
-  else
-    hipLaunchKernelGGL((k_leap_v5<false, JH_V5_WPB, false>), dim3(grid), dim3(WAVE * JH_V5_WPB), JH_V5_DYNBYTES, st, m->d_f, m->d_i, x0, 0, nominal, noise, ldn, sigma, W, lohi, tp, N, n_offset, H, K, costs,
-                       knots_out, (const float*)nullptr, (float*)nullptr, (float*)nullptr, m->d_stats, dshift, trace, ovf);
-  return jh_launch_done(ovf, st);
+  // Launch shape (jh_model_set_rollout_schedule).  A launch with more groups of four rollouts than the GPU holds waves of this kernel (two workgroups per CU) runs one workgroup
+  // per resident slot and lets the waves draw their groups from a queue; one that fits at once, and every latency-mode launch, keeps one group per wave of the grid.
+  bool persist = dshift == 0 && m->rollout_schedule != 1; int slots = 0;
+  if (persist) { slots = 2 * device_cus(m); persist = m->rollout_schedule == 2 || grid > slots; }
+  // Stream-ordered scratch of the launch, no state on the model handle (two streams may run one model): a 16-byte block for the queue's head word, zeroed in front of every
+  // launch that uses it, then one row per rollout for the contacts above the LDS pool.
+  const size_t ovf_bytes = NOVF > 0 ? (size_t)N * NOVF * POOL_F * sizeof(float) : 0;
+  float* scratch = nullptr; float* ovf = nullptr; unsigned* head = nullptr;
+  if (ovf_bytes > 0 || persist) scratch = jh_launch_scratch(m, ovf_bytes + (persist ? 16 : 0), st, ovf_bytes > 0);  // (nullptr: the LDS capacity alone, drops and the fallback counted -- and the static shape)
+  if (scratch && persist && hipMemsetAsync(scratch, 0, 16, st) != hipSuccess) { (void)hipGetLastError(); persist = false; }
+  if (!scratch) persist = false;
+  if (persist) { head = (unsigned*)scratch; if (grid > slots) grid = slots; }
+  if (scratch && ovf_bytes > 0) ovf = scratch + (head ? 4 : 0);
+#define JH_V5_LAUNCH_COST(SELF_, PERSIST_)                                                                                                                                        \
+  hipLaunchKernelGGL((k_leap_v5<false, JH_V5_WPB, SELF_, PERSIST_>), dim3(grid), dim3(WAVE * JH_V5_WPB), JH_V5_DYNBYTES, st, m->d_f, m->d_i, x0, 0, nominal, noise, ldn, sigma, W, \
+                     lohi, tp, N, n_offset, H, K, costs, knots_out, (const float*)nullptr, (float*)nullptr, (float*)nullptr, m->d_stats, dshift, trace, ovf, head)
+  if (m->self_collision && m->h_i[17] > 0) { if (persist) JH_V5_LAUNCH_COST(true, true); else JH_V5_LAUNCH_COST(true, false); }
+  else { if (persist) JH_V5_LAUNCH_COST(false, true); else JH_V5_LAUNCH_COST(false, false); }
+#undef JH_V5_LAUNCH_COST
+  return jh_launch_done(scratch, st);
 }
 
 int JH_V5_NAME(jh_engine5_materialize)(const jh_model* m, const float* x0, int x0_batched, const float* controls, int N, int H, float* states, float* sensors,
@@ -2018,10 +2090,10 @@ int JH_V5_NAME(jh_engine5_materialize)(const jh_model* m, const float* x0, int x
   if (m->self_collision && m->h_i[17] > 0)
     hipLaunchKernelGGL((k_leap_v5<true, JH_V5_WPB, true>), dim3(grid), dim3(WAVE * JH_V5_WPB), JH_V5_DYNBYTES, st, m->d_f, m->d_i, x0, x0_batched, (const float*)nullptr, (const float*)nullptr, 0,
                        (const float*)nullptr, (const float*)nullptr, (const float*)nullptr, (const float*)nullptr, N, 0, H, 0, (float*)nullptr, (float*)nullptr,
-                       controls, states, sensors, m->d_stats, dshift, (float*)nullptr, ovf);
+                       controls, states, sensors, m->d_stats, dshift, (float*)nullptr, ovf, (unsigned*)nullptr);
   else
     hipLaunchKernelGGL((k_leap_v5<true, JH_V5_WPB, false>), dim3(grid), dim3(WAVE * JH_V5_WPB), JH_V5_DYNBYTES, st, m->d_f, m->d_i, x0, x0_batched, (const float*)nullptr, (const float*)nullptr, 0,
                        (const float*)nullptr, (const float*)nullptr, (const float*)nullptr, (const float*)nullptr, N, 0, H, 0, (float*)nullptr, (float*)nullptr,
-                       controls, states, sensors, m->d_stats, dshift, (float*)nullptr, ovf);
+                       controls, states, sensors, m->d_stats, dshift, (float*)nullptr, ovf, (unsigned*)nullptr);
   return jh_launch_done(ovf, st);
 }

@@ -30,6 +30,7 @@ struct jh_model {
   int contact_capacity;  // leap_cube generation 3: 48 (all in LDS, jh_engine_v5.hip) or 64 (jh_engine_v5_cap64.hip); jh_model_set_contact_capacity
   int cylinders;  // leap_cube family: cylinder geoms in the image (caltech_leap_cube packed with fingertips="cylinder"); > 0 selects the cylinder build (jh_engine_v5_cyl.hip: generation 3, 64 contacts) and nothing else runs such an image
   int self_collision;  // leap_cube on jh_engine_v5.hip: model the hand's own contacts (finger-finger, finger-palm) as MuJoCo does; 0 = the cube's contacts only
+  int rollout_schedule;  // leap_cube generation 3, fused launches: 0 = persistent waves on a queue of rollout groups where the launch exceeds the GPU's wave slots (the default), 1 = always the static grid, 2 = the queue wherever the kernel has it (jh_model_set_rollout_schedule)
   int plan_step_launches;  // closed-form models' plan step: 0 = one launch where it fits (the default), 1 = always one launch, 2 = always two (jh_model_set_plan_step_launches)
   mutable int one_launch_steps = 0;  // plan steps that ran as one launch (jh_model_stats out[7]); __atomic builtins, as ovf_fallbacks
   mutable int ovf_fallbacks = 0;  // launches that ran without their overflow rows (jh_launch_scratch); updated with __atomic builtins: a planner thread may launch while another polls jh_model_stats
@@ -42,11 +43,13 @@ void jh_set_error(const char* fmt, ...);
 
 // Per-launch scratch of the cooperative kernels (the contacts above the LDS pool, one row per rollout): a stream-ordered allocation from the default pool of the MODEL's
 // device (not of whatever device is current in the calling thread).  nullptr when the pool refuses: the kernel then holds what its LDS pool holds, the drops are
-// counted, and the launch is counted in `ovf_fallbacks` (jh_model_stats out[6]) so that the lower capacity does not go unnoticed.
-inline float* jh_launch_scratch(const jh_model* m, size_t bytes, hipStream_t st) {
+// counted, and the launch is counted in `ovf_fallbacks` (jh_model_stats out[6]) so that the lower capacity does not go unnoticed.  `overflow_rows` = false: the block
+// holds no overflow rows (the leap kernel's queue head alone), and a refusal costs no capacity and is not counted.
+inline float* jh_launch_scratch(const jh_model* m, size_t bytes, hipStream_t st, bool overflow_rows = true) {
   hipMemPool_t pool = nullptr; void* p = nullptr;
   if (hipDeviceGetDefaultMemPool(&pool, m->device) == hipSuccess && pool && hipMallocFromPoolAsync(&p, bytes, pool, st) == hipSuccess) return (float*)p;
   (void)hipGetLastError();
+  if (!overflow_rows) return nullptr;
   if (__atomic_fetch_add(&m->ovf_fallbacks, 1, __ATOMIC_RELAXED) == 0)  // the first fallback of a model is also logged: the lower capacity must not depend on somebody polling the counter
     fprintf(stderr, "judo_amd: no stream-ordered scratch for the contacts above the LDS pool (%zu bytes): this launch runs with the LDS capacity alone; see jh_model_stats out[6]\n", bytes);
   return nullptr;

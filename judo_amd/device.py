@@ -169,6 +169,11 @@ class GpuModel:
         """0: one launch where it fits (default), 1: always one launch, 2: always two (`jh_model_set_plan_step_launches`)."""
         _lib.check(_lib.lib().jh_model_set_plan_step_launches(self.handle, int(launches)), "jh_model_set_plan_step_launches")
 
+    def set_rollout_schedule(self, mode: int) -> None:
+        """leap_cube, kernel generation 3: 0 = persistent waves on a queue of rollout groups where the launch exceeds the GPU's wave slots (default), 1 = always the static
+        grid, 2 = the queue wherever the kernel has it (`jh_model_set_rollout_schedule`).  The bits do not depend on it."""
+        _lib.check(_lib.lib().jh_model_set_rollout_schedule(self.handle, int(mode)), "jh_model_set_rollout_schedule")
+
     def stats(self, reset: bool = True) -> dict:
         """Diagnostic counters of the articulated-body kernels (synchronises)."""
         out = (C.c_int * 8)()

@@ -1,0 +1,88 @@
+"""How the leap kernel's launch fills the GPU, measured: a -DJH_V5_WAVESTAMP build (selected with JUDO_AMD_LIB) stores, per group of four rollouts, the 100 MHz wall clock at
+its wave's entry, after the staging barrier, at the group's start and at its end, with the workgroup and wave that ran it.  Plan steps of the recorded headline inputs
+(tools/diag/ab_inputs_leap.npz, as ab_fixed_inputs.py replays them) run under the static grid and under the queue (jh_model_set_rollout_schedule 1 / 2); printed per launch:
+the distribution of group durations, what a workgroup's waves wait for each other, the occupied wave slots over time, the drain at the end -- and what a greedy placement
+of the MEASURED durations (constant speed per slot) predicts for the static grid, a per-wave queue, a queue of horizon quarters and the ideal.
+build:  tools/diag/build_variant.sh wavestamp judo_amd/csrc/jh_engine_v5.hip -DJH_V5_WAVESTAMP
+usage:  JUDO_AMD_LIB=variants/libjudo_amd_wavestamp.so python tools/diag/wave_schedule.py [plan steps, default 5,35] [schedules, default 1,2]"""
+import ctypes as C, heapq, os, sys
+import numpy as np, torch
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__)))))
+from judo_amd.controller import make_controller
+from judo_amd import _lib
+
+N, H, WPB, TICK_US = 65536, 64, 4, 0.01
+d = np.load(os.path.join(os.path.dirname(os.path.abspath(__file__)), "ab_inputs_leap.npz"))
+c = make_controller("leap_cube", "mppi"); c.optimizer.config.num_rollouts = N; c.controller_cfg.horizon = H * c.task.dt
+c.reset(); c.current_state = c.task.default_state(); c.system_metadata = {"goal_quat": np.array([0.0, 1.0, 0.0, 0.0])}
+L = _lib.lib()
+L.jh_v5_wavestamp_buffer.argtypes = [C.c_void_p, C.c_int]; L.jh_v5_wavestamp_buffer.restype = C.c_int  # AttributeError: not a -DJH_V5_WAVESTAMP build
+G = (N + 3) // 4
+buf = torch.zeros((G, 6), dtype=torch.int64, device="cuda")
+assert L.jh_v5_wavestamp_buffer(buf.data_ptr(), G) == 0
+SLOTS = 2 * torch.cuda.get_device_properties(0).multi_processor_count * WPB  # waves of this kernel the GPU holds: two workgroups of four per CU
+steps = [int(a) for a in (sys.argv[1] if len(sys.argv) > 1 else "5,35").split(",")]
+modes = [int(a) for a in (sys.argv[2] if len(sys.argv) > 2 else "1,2").split(",")]
+
+
+def greedy(units, slots):
+    """Launch length when `units` (durations, in ticket order) go one after the other to whichever of `slots` slots is free first."""
+    free = [0.0] * min(slots, len(units)); heapq.heapify(free)
+    end = 0.0
+    for u in units:
+        t = heapq.heappop(free) + u; end = max(end, t); heapq.heappush(free, t)
+    return end
+
+
+def model(dur):
+    """The greedy model on measured group durations `dur` (launch order)."""
+    pad = np.concatenate([dur, np.zeros(-len(dur) % WPB)]).reshape(-1, WPB)
+    static = greedy(pad.max(axis=1), SLOTS // WPB)  # a workgroup's slots are held until its slowest wave ends
+    queue = greedy(dur, SLOTS)
+    quarters = greedy(np.tile(dur / 4, 4), SLOTS)  # slice-major tickets: all first quarters before any second (hand-off waits not modelled)
+    ideal = dur.sum() / SLOTS
+    return static, queue, quarters, ideal
+
+
+def pct(a, q): return float(np.percentile(a, q))
+
+
+for i in steps:
+    for mode in modes:
+        c.model.set_rollout_schedule(mode)
+        for rep in range(2):  # (the second launch is the one read: the first may carry one-off costs)
+            buf.zero_()
+            c.optimizer.seed(1000 + i); c.nominal_knots = d["knots"][i].copy(); c.times = d["times"][i].copy(); c.update_spline(c.times, c.nominal_knots); c.time = float(d["t"][i])
+            c.update_action(); torch.cuda.synchronize()
+        a = buf.cpu().numpy()
+        assert (a[:, 5] == 1).all(), "groups without a stamp"
+        wg, wv = a[:, 0] >> 32, (a[:, 0] >> 8) & 0xFF
+        t0 = a[:, 1].min()
+        entry, staged, start, end = ((a[:, k] - t0) * TICK_US for k in (1, 2, 3, 4))  # microseconds from the first wave's entry
+        dur = end - start
+        kernel = end.max()
+        print(f"\nplan step {i}, schedule {mode} ({'static grid' if mode == 1 else 'queue'}): {G} groups on {int(wg.max()) + 1} workgroups, {SLOTS} wave slots; launch {kernel / 1e3:.2f} ms from first entry to last end")
+        print(f"  group duration [ms]: mean {dur.mean() / 1e3:.3f}  cv {dur.std() / dur.mean():.4f}  p50 {pct(dur, 50) / 1e3:.3f}  p90 {pct(dur, 90) / 1e3:.3f}  p99 {pct(dur, 99) / 1e3:.3f}  max {dur.max() / 1e3:.3f}")
+        print(f"  staging (entry -> barrier passed) [us]: mean {(staged - entry).mean():.1f}  max {(staged - entry).max():.1f}")
+        wave = wg * WPB + wv  # the wave (slot holder) that ran each group
+        order = np.argsort(wave, kind="stable")
+        first = np.concatenate([[True], wave[order][1:] != wave[order][:-1]])
+        w_entry, w_end = np.minimum.reduceat(entry[order], np.flatnonzero(first)), np.maximum.reduceat(end[order], np.flatnonzero(first))
+        w_wg = wg[order][first]
+        per_wg = [(w_end[w_wg == g] - w_entry[w_wg == g]) for g in np.unique(w_wg)[:: max(1, len(np.unique(w_wg)) // 512)]]
+        print(f"  waves: {len(w_end)}, lifetime mean {(w_end - w_entry).mean() / 1e3:.3f} ms; over (sampled) workgroups, mean of (max - mean) of their waves' lifetimes: {np.mean([p.max() - p.mean() for p in per_wg]) / 1e3:.3f} ms"
+              f" ({100 * np.mean([(p.max() - p.mean()) / p.max() for p in per_wg]):.1f} % of the workgroup's lifetime)")
+        # occupied slots over time: a slot is occupied from its wave's entry to the end of the wave's last group (static grid: the wave's only group)
+        ts = np.concatenate([w_entry, w_end]); dv = np.concatenate([np.ones(len(w_entry)), -np.ones(len(w_end))])
+        o = np.argsort(ts, kind="stable"); ts, occ = ts[o], np.cumsum(dv[o])
+        grid_t = np.linspace(0, kernel, 21)[1:-1]
+        print("  occupied wave slots at 5 % .. 95 % of the launch: " + " ".join(str(int(occ[np.searchsorted(ts, t, side='right') - 1])) for t in grid_t))
+        share = float((occ[:-1] * np.diff(ts)).sum() / (SLOTS * kernel))
+        # the drain: once the last group has started nothing is left to hand out, and the first slot that frees after that stays empty
+        drain = kernel - end[end > start.max()].min()
+        print(f"  resident-wave share from the stamps {share:.3f}; most waves at once {int(occ.max())}; from the first slot that stays empty to the end {drain / 1e3:.3f} ms ({100 * drain / kernel:.1f} % of the launch)")
+        if mode == 1:
+            s_, q_, h_, id_ = model(dur)
+            print(f"  greedy model on these durations: static grid {s_ / 1e3:.2f} ms (measured {kernel / 1e3:.2f}); per-wave queue {q_ / 1e3:.2f} ms ({100 * (1 - q_ / s_):.1f} % shorter); "
+                  f"queue of horizon quarters {h_ / 1e3:.2f} ms ({100 * (1 - h_ / s_):.1f} %); ideal {id_ / 1e3:.2f} ms ({100 * (1 - id_ / s_):.1f} %)")
+assert L.jh_v5_wavestamp_buffer(None, 0) == 0
