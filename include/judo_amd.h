@@ -85,6 +85,14 @@ int jh_model_set_contact_capacity(jh_model* m, int contacts);
  * model; the sphere builds refuse its image.  HOST pointer. */
 int jh_model_build(const jh_model* m, int* out /* HOST, 4 ints */);
 
+/* The same report for the fr3_pick kernel: out[0] = 1 when the model runs the SELF-COLLISION build (jh_engine_v6_self.hip), out[1] = the image's candidate pairs the
+ * default build leaves out (between two arm bodies other than finger against finger, or a box on the arm against the capsule of the static base), out[2] / out[3] = 1
+ * when the default / the self-collision build accepts the image.  Selected by the image, as the cylinder build is: an image packed from a description with
+ * "self_collision" (engine_model.py; FR3Pick(self_collision=True)) holds all 190 pairs the MJCF leaves after MuJoCo's static filters, the default image 78.  The
+ * self-collision build takes capsule against capsule (MuJoCo's primitive) and a contact with both sides on the arm.  jh_model_create refuses a malformed pair of that
+ * kind; kernel generations 1 and 2 refuse such a model; the default build refuses its image.  Another model family: all zero.  HOST pointer. */
+int jh_model_fr3_build(const jh_model* m, int* out /* HOST, 4 ints */);
+
 /* Traces without a second rollout (judo/controller/controller.py:323-363, `update_traces`: line segments of the best rollouts' `trace*` framepos sensors).  The
  * reference reads them out of the sensor array its rollout materialises for every sample; the fused path has no such array, so round 1-2 re-rolled the elites in
  * materialise mode when the traces were read (8 ms on the headline workload: one lone wave for 64 serial steps).  jh_rollout_cost_traced (jh_rollout_cost with one more argument) on

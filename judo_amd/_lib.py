@@ -33,6 +33,7 @@ _SIGNATURES = {
     "jh_model_set_self_collision": (C.c_int, [C.c_void_p, C.c_int]),
     "jh_model_set_contact_capacity": (C.c_int, [C.c_void_p, C.c_int]),
     "jh_model_build": (C.c_int, [C.c_void_p, C.POINTER(C.c_int)]),
+    "jh_model_fr3_build": (C.c_int, [C.c_void_p, C.POINTER(C.c_int)]),
     "jh_model_trace_layout": (C.c_int, [C.c_void_p, C.POINTER(C.c_int)]),
     "jh_trace_gather": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p]),
     "jh_upload_async": (C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]),

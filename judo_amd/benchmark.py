@@ -16,7 +16,7 @@ import numpy as np
 
 
 def plan_times(task, optimizer: str, num_samples: int, warmup: int, rollouts: int | None) -> np.ndarray:
-    """`task`: a registered task's name, or a Task instance (e.g. `CaltechLeapCube(fingertips="cylinder")`) to time with the shipped overrides of its name."""
+    """`task`: a registered task's name, or a Task instance (e.g. `CaltechLeapCube(fingertips="cylinder")`, `FR3Pick(self_collision=True)`) to time with the shipped overrides of its name."""
     import torch
 
     from judo_amd.controller import make_controller, make_controller_for

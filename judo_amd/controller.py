@@ -944,7 +944,7 @@ def make_controller(init_task: str, init_optimizer: str, device: torch.device | 
 
 
 def make_controller_for(task: Task, init_optimizer: str, device: torch.device | None = None, group: Any = None) -> Controller:
-    """The same construction around a task INSTANCE (one built with constructor arguments, e.g. `CaltechLeapCube(fingertips="cylinder")`): the optimizer and
+    """The same construction around a task INSTANCE (one built with constructor arguments, e.g. `CaltechLeapCube(fingertips="cylinder")` or `FR3Pick(self_collision=True)`): the optimizer and
     controller overrides registered for the task's name."""
     opts = get_registered_optimizers()
     if init_optimizer not in opts:

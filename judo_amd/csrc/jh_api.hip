@@ -39,6 +39,31 @@ static int image_cylinders(const jh_blob_header& h, const float* F, const int* I
   return n;
 }
 
+// Arm pairs of an fr3_pick image (the generic section behind header I[13]: geom records, then the candidate pairs): the pairs between two moving bodies of the arm (body
+// codes >= 1) other than finger against finger (bodies 8 and 9), plus those of a box or a capsule on the arm against a capsule of the static geometry (the fr3_link0 stand-in) -- what the
+// default build of k_fr3_v6 leaves out and its self-collision build (jh_engine_v6_self.hip) collides.  -1 with the error set when a pair record is malformed.
+static int image_arm_pairs(const jh_blob_header& h, const int* I) {
+  constexpr int HEADER = 24, GEOM_I = 2, GBOX = 6, GCAPSULE = 3, LF = 8, RF = 9;
+  if (h.nint < (uint32_t)HEADER) return 0;  // (not an engine image: the launchers refuse it)
+  const long gi = I[13];
+  if (gi < HEADER || gi + 8 > (long)h.nint) return 0;
+  const long nag = I[gi], npair = I[gi + 1];
+  if (nag < 0 || npair < 0 || gi + 8 + nag * GEOM_I + npair * 2 > (long)h.nint) return 0;
+  int n = 0;
+  for (long p = 0; p < npair; p++) {
+    const long g1 = I[gi + 8 + nag * GEOM_I + 2 * p], g2 = I[gi + 8 + nag * GEOM_I + 2 * p + 1];
+    if (g1 < 0 || g1 >= nag || g2 < 0 || g2 >= nag || g1 == g2) { jh_set_error("model_create: candidate pair %ld names geoms (%ld, %ld) of %ld", p, g1, g2, nag); return -1; }
+    const int b1 = I[gi + 8 + g1 * GEOM_I], t1 = I[gi + 8 + g1 * GEOM_I + 1], b2 = I[gi + 8 + g2 * GEOM_I], t2 = I[gi + 8 + g2 * GEOM_I + 1];
+    const bool arm_arm = b1 >= 1 && b2 >= 1 && !((b1 == LF && b2 == RF) || (b1 == RF && b2 == LF));
+    const bool arm_capsule = t1 == GCAPSULE || (t1 == GBOX && t2 == GCAPSULE && b1 >= 1);  // (a capsule of the arm or of the static base against the arm)
+    if (!arm_arm && !arm_capsule) continue;
+    if (b1 == b2) { jh_set_error("model_create: candidate pair %ld collides two geoms of arm body %d with each other", p, b1); return -1; }
+    if (t1 == GCAPSULE && t2 != GCAPSULE) { jh_set_error("model_create: candidate pair %ld between arm bodies has its capsule first; the kernel takes (box, capsule)", p); return -1; }
+    n++;
+  }
+  return n;
+}
+
 extern "C" int jh_model_create(const void* blob, size_t nbytes, int device, jh_model** out) {
   JH_REQUIRE(blob && out, "model_create: null pointer");
   if (nbytes < sizeof(jh_blob_header)) { jh_set_error("model_create: blob too small (%zu bytes)", nbytes); return JH_ERR_BLOB; }
@@ -51,7 +76,7 @@ extern "C" int jh_model_create(const void* blob, size_t nbytes, int device, jh_m
   if (h.kind == JH_TASK_CARTPOLE && h.nfloat < CP_NPARAM) { jh_set_error("model_create: cartpole blob has %u floats, need %d", h.nfloat, CP_NPARAM); return JH_ERR_BLOB; }
   if (h.kind == JH_TASK_CYLINDER_PUSH && h.nfloat < CY_NPARAM) { jh_set_error("model_create: cylinder blob has %u floats, need %d", h.nfloat, CY_NPARAM); return JH_ERR_BLOB; }
   if (h.ntaskparam > JH_MAX_TASK_PARAMS) { jh_set_error("model_create: too many task params"); return JH_ERR_BLOB; }
-  int cylinders = 0;
+  int cylinders = 0, arm_pairs = 0;
   if (h.kind == JH_TASK_LEAP_CUBE || h.kind == JH_TASK_FR3_PICK) {
     const char* q = (const char*)blob + sizeof(h);
     std::vector<float> F((const float*)q, (const float*)q + h.nfloat);  // (copies: the blob need not be aligned)
@@ -59,11 +84,15 @@ extern "C" int jh_model_create(const void* blob, size_t nbytes, int device, jh_m
     cylinders = image_cylinders(h, F.data(), I.data());
     if (cylinders < 0) return JH_ERR_BLOB;
     if (cylinders > 0 && h.kind != JH_TASK_LEAP_CUBE) { jh_set_error("model_create: %d cylinder geoms, and only the leap kernel has a cylinder build", cylinders); return JH_ERR_BLOB; }
+    if (h.kind == JH_TASK_FR3_PICK) {
+      arm_pairs = image_arm_pairs(h, I.data());
+      if (arm_pairs < 0) return JH_ERR_BLOB;
+    }
   }
   JH_HIP(hipSetDevice(device));
   jh_model* m = new jh_model();
   m->device = device; m->kind = (int)h.kind; m->nq = h.nq; m->nv = h.nv; m->nu = h.nu; m->ns = h.ns; m->ntaskparam = h.ntaskparam;
-  m->nf = h.nfloat; m->ni = h.nint; m->d_f = nullptr; m->d_i = nullptr; m->d_stats = nullptr; m->kernel_gen = (h.kind == JH_TASK_LEAP_CUBE || h.kind == JH_TASK_FR3_PICK) ? 3 : 2; m->self_collision = 1; m->contact_capacity = cylinders > 0 ? 64 : 48; m->cylinders = cylinders;
+  m->nf = h.nfloat; m->ni = h.nint; m->d_f = nullptr; m->d_i = nullptr; m->d_stats = nullptr; m->kernel_gen = (h.kind == JH_TASK_LEAP_CUBE || h.kind == JH_TASK_FR3_PICK) ? 3 : 2; m->self_collision = 1; m->contact_capacity = cylinders > 0 ? 64 : 48; m->cylinders = cylinders; m->arm_pairs = arm_pairs;
   { const char* e = getenv("JUDO_AMD_ROLLOUT_SCHEDULE"); m->rollout_schedule = (e && (e[0] == '1' || e[0] == '2')) ? e[0] - '0' : 0; }  // (the environment sets the default; jh_model_set_rollout_schedule changes it per model)
   { const char* e = getenv("JUDO_AMD_PLAN_STEP_LAUNCHES"); m->plan_step_launches = (e && e[0] == '2') ? 2 : 0; }  // (the environment sets the default; jh_model_set_plan_step_launches changes it per model)
   const char* p = (const char*)blob + sizeof(h);
@@ -151,6 +180,10 @@ extern "C" int jh_model_set_kernel(jh_model* m, int generation) {
     jh_set_error("model_set_kernel: the image holds %d cylinder geoms; only generation 3 (the cylinder build of the leap kernel) collides them", m->cylinders);
     return JH_ERR_UNSUPPORTED;
   }
+  if (generation != 3 && m->arm_pairs > 0) {
+    jh_set_error("model_set_kernel: the image holds %d pairs between arm bodies; only generation 3 (the self-collision build of the fr3 kernel) collides them", m->arm_pairs);
+    return JH_ERR_UNSUPPORTED;
+  }
   m->kernel_gen = generation;
   return JH_OK;
 }
@@ -184,6 +217,16 @@ extern "C" int jh_model_build(const jh_model* m, int* out) {
   out[1] = m->kind == JH_TASK_LEAP_CUBE && m->kernel_gen == 3 ? m->contact_capacity : 0;
   out[2] = m->kind == JH_TASK_LEAP_CUBE && m->kernel_gen == 3 && m->cylinders > 0 ? 1 : 0;
   out[3] = m->cylinders;
+  return JH_OK;
+}
+
+extern "C" int jh_model_fr3_build(const jh_model* m, int* out) {
+  JH_REQUIRE(m && out, "model_fr3_build: null pointer");
+  const bool fr3 = m->kind == JH_TASK_FR3_PICK;
+  out[0] = fr3 && m->kernel_gen == 3 && m->arm_pairs > 0 ? 1 : 0;
+  out[1] = fr3 ? m->arm_pairs : 0;
+  out[2] = fr3 && jh_model_is_fr3(m) ? 1 : 0;
+  out[3] = fr3 && jh_model_is_fr3_self(m) ? 1 : 0;
   return JH_OK;
 }
 
@@ -341,7 +384,9 @@ extern "C" int jh_rollout_cost_traced(const jh_model* m, const float* x0, const 
     return m->cylinders > 0         ? jh_engine5_rollout_cost_cyl(m, x0, nominal, noise, ldn, sigma, W, lohi, tp, N, n_offset, H, K, costs, knots_out, trace, st)
            : m->contact_capacity > 48 ? jh_engine5_rollout_cost_cap64(m, x0, nominal, noise, ldn, sigma, W, lohi, tp, N, n_offset, H, K, costs, knots_out, trace, st)
                                     : jh_engine5_rollout_cost(m, x0, nominal, noise, ldn, sigma, W, lohi, tp, N, n_offset, H, K, costs, knots_out, trace, st);
-  if (m->kind == JH_TASK_FR3_PICK && m->kernel_gen == 3) return jh_engine6_rollout_cost(m, x0, nominal, noise, ldn, sigma, W, lohi, tp, phase, N, n_offset, H, K, costs, knots_out, trace, st);
+  if (m->kind == JH_TASK_FR3_PICK && m->kernel_gen == 3)
+    return m->arm_pairs > 0 ? jh_engine6_rollout_cost_self(m, x0, nominal, noise, ldn, sigma, W, lohi, tp, phase, N, n_offset, H, K, costs, knots_out, trace, st)
+                            : jh_engine6_rollout_cost(m, x0, nominal, noise, ldn, sigma, W, lohi, tp, phase, N, n_offset, H, K, costs, knots_out, trace, st);
   JH_REQUIRE(trace == nullptr, "rollout_cost_traced: only the product kernels (generation 3, cartpole, cylinder_push) write trace sensors");
   if (!g_xcheck.rollout_cost) { jh_set_error("rollout_cost: no kernel for this model / generation in this library"); return JH_ERR_UNSUPPORTED; }
   return g_xcheck.rollout_cost(m, m->kernel_gen, x0, nominal, noise, ldn, sigma, W, lohi, tp, phase, N, n_offset, H, K, costs, knots_out, stream);
@@ -457,7 +502,8 @@ extern "C" int jh_rollout_materialize(const jh_model* m, const float* x0, int x0
   if (m->kind == JH_TASK_CARTPOLE || m->kind == JH_TASK_CYLINDER_PUSH) return jh_simple_materialize(m, x0, x0_batched, controls, N, H, states, sensors, st);
   if (m->kind == JH_TASK_LEAP_CUBE && m->kernel_gen == 3)
     return m->cylinders > 0 ? jh_engine5_materialize_cyl(m, x0, x0_batched, controls, N, H, states, sensors, st) : m->contact_capacity > 48 ? jh_engine5_materialize_cap64(m, x0, x0_batched, controls, N, H, states, sensors, st) : jh_engine5_materialize(m, x0, x0_batched, controls, N, H, states, sensors, st);
-  if (m->kind == JH_TASK_FR3_PICK && m->kernel_gen == 3) return jh_engine6_materialize(m, x0, x0_batched, controls, N, H, states, sensors, st);
+  if (m->kind == JH_TASK_FR3_PICK && m->kernel_gen == 3)
+    return m->arm_pairs > 0 ? jh_engine6_materialize_self(m, x0, x0_batched, controls, N, H, states, sensors, st) : jh_engine6_materialize(m, x0, x0_batched, controls, N, H, states, sensors, st);
   if (!g_xcheck.rollout_materialize) { jh_set_error("rollout_materialize: no kernel for this model / generation in this library"); return JH_ERR_UNSUPPORTED; }
   return g_xcheck.rollout_materialize(m, m->kernel_gen, x0, x0_batched, controls, N, H, states, sensors, stream);
 }

@@ -26,6 +26,14 @@ template <int N, class F>
 __device__ __forceinline__ void static_for(F&& f) { static_for_impl<N>(f, std::make_integer_sequence<int, N>{}); }  // f(integral_constant<int, 0>) ... f(<N - 1>): compile-time indices for DPP controls
 
 
+#ifndef JH_V6_SELF
+#define JH_V6_SELF 0  // 1 (jh_engine_v6_self.hip): the build for an image with every pair the MJCF leaves (engine_model.pack_engine_model on a description with "self_collision"):
+                      // arm bodies against each other -- link capsule against link capsule, hand / finger box against link capsule -- as general contacts whose two sides
+                      // both lie on the chain (slot_sides), and a capsule-capsule narrow phase.  0: the code the default build had.
+#endif
+#ifndef JH_V6_NAME
+#define JH_V6_NAME(f) f
+#endif
 constexpr int G = 16, RPW = 4, WAVE = 64;
 constexpr int NA = 9, NCHAIN = 7, NVT = 15, NQ = 16, NU = 8, NS = 14, NX = 31, NMB = 10;
 #ifndef JH_V6_NSBIG
@@ -140,12 +148,22 @@ __device__ __forceinline__ void pyramid_dir(const float* jar, const float* jp, f
 
 // A general contact has at most one side on the free box and at most one on the arm (arm against arm is the finger-finger case, in slots of its own): `csign` = +1 / -1 / 0 for
 // the box on side B / side A / neither, `ab` = the arm-side body (0: none) and `asign` its side's sign.
-struct Sides6 { float csign, asign; int ab; };
+// The self-collision build (JH_V6_SELF) also takes both sides on the arm.  The arm is a serial chain and both sides share the contact point, so the columns of the hinges above
+// the SHALLOWER body cancel: the relative Jacobian is the deeper body's with the hinges j < `lo` zeroed (`lo` = the shallower body, 0 when that side is not on the arm; the
+// fingers are the deepest bodies, so a finger's slide column stays).  `ab` = the deeper body, `asign` its side's sign.  Finger against finger stays in its own slots.
+struct Sides6 { float csign, asign; int ab, lo; };
 __device__ __forceinline__ Sides6 slot_sides(int sa, int sb) {
   Sides6 z;
   z.csign = (sb == 0 ? 1.f : 0.f) - (sa == 0 ? 1.f : 0.f);
+#if JH_V6_SELF
+  z.ab = max(max(sa, sb), 0);
+  z.asign = sb >= sa ? 1.f : -1.f;
+  z.lo = max(min(sa, sb), 0);
+#else
   z.ab = sa >= 1 ? sa : (sb >= 1 ? sb : 0);
   z.asign = sb >= 1 ? 1.f : -1.f;
+  z.lo = 0;
+#endif
   return z;
 }
 // the world columns of the arm's eight dofs for a point carried by the arm: hinge j -> axis_j x (pos - anchor_j), entry 7 -> the slide axis of finger `fb` (8 or 9).  ALL of
@@ -175,7 +193,7 @@ __device__ __forceinline__ void slot_Jx(const Slot6& t, const RS6& S, const floa
     float c3[NCHAIN + 1][3]; arm_cols(S, t.pos, fb, c3);
 #pragma unroll
     for (int j = 0; j < NCHAIN; j++) {
-      const float xj = j < z.ab ? z.asign * xa[j] : 0.f;
+      const float xj = (j < z.ab && (!JH_V6_SELF || j >= z.lo)) ? z.asign * xa[j] : 0.f;
       w[0] = fmaf(c3[j][0], xj, w[0]); w[1] = fmaf(c3[j][1], xj, w[1]); w[2] = fmaf(c3[j][2], xj, w[2]);
     }
     const float xs7 = xa[NCHAIN], xs8 = xa[NCHAIN + 1];
@@ -201,7 +219,7 @@ __device__ __forceinline__ void slot_force(RS6& S, const Slot6& t, const float* 
 #pragma unroll
     for (int j = 0; j <= NCHAIN; j++) v[j] = -z.asign * dot3(c3[j], Fw);
 #pragma unroll
-    for (int j = 0; j < NCHAIN; j++) if (j < z.ab) atomicAdd(&S.g[6 + j], v[j]);
+    for (int j = 0; j < NCHAIN; j++) if (j < z.ab && (!JH_V6_SELF || j >= z.lo)) atomicAdd(&S.g[6 + j], v[j]);
     if (z.ab > NCHAIN) atomicAdd(&S.g[6 + z.ab - 1], v[NCHAIN]);
   }
 }
@@ -253,11 +271,14 @@ __device__ __forceinline__ void slot_assemble(RS6& S, const Slot6& t, const floa
     float cu[NCHAIN + 1][3]; arm_cols(S, t.pos, fb, cu);
 #pragma unroll
     for (int u = 0; u <= NCHAIN; u++) {  // arm columns 0..6 = hinges, 7 = the finger's slide
-      if (!(u < NCHAIN ? u < ab : ab > NCHAIN)) continue;
+      if (!(u < NCHAIN ? (u < ab && (!JH_V6_SELF || u >= z.lo)) : ab > NCHAIN)) continue;
       float y[3]; Amul(cu[u], y);
       const int du = u < NCHAIN ? 6 + u : dsl;
 #pragma unroll
-      for (int v = 0; v <= u; v++) atomicAdd(&S.H[du][v < NCHAIN ? 6 + v : dsl], dot3(cu[v], y));
+      for (int v = 0; v <= u; v++) {
+        if (JH_V6_SELF && v < NCHAIN && v < z.lo) continue;  // (self-collision build: the hinges above the shallower body are no columns of this contact)
+        atomicAdd(&S.H[du][v < NCHAIN ? 6 + v : dsl], dot3(cu[v], y));
+      }
       if (cube) {
 #pragma unroll
         for (int q = 0; q < 3; q++) atomicAdd(&S.H[du][q], -y[q]);
@@ -369,6 +390,47 @@ __device__ __forceinline__ void rodrigues(float* Rq, const float* al, float sn, 
   Rq[3] = t * x * y + sn * z; Rq[4] = t * y * y + cs; Rq[5] = t * y * z - sn * x;
   Rq[6] = t * x * z - sn * y; Rq[7] = t * y * z + sn * x; Rq[8] = t * z * z + cs;
 }
+
+#if JH_V6_SELF
+// capsule against capsule (MuJoCo's mjc_CapsuleCapsule as oracle/jo_engine.c::collide_capsule_capsule restates it; jh_engine_v4.hip has the same routine for the Spot robot
+// against itself, inside its kernel -- restated here so that the tree kernel compiles to the code it had): the closest points of the two axis segments, then sphere against
+// sphere there; parallel axes: the ends of either capsule against the other's segment, at most two contacts.  Normal from the first capsule to the second.
+template <class Sink>
+__device__ __forceinline__ void collide_capsule_capsule(Sink& sk, const float* p1, const float* R1, float r1, float L1, const float* p2, const float* R2, float r2, float L2) {
+  auto sphere_sphere = [&](const float* ca, const float* cb) __attribute__((always_inline)) {
+    const float d[3] = {cb[0] - ca[0], cb[1] - ca[1], cb[2] - ca[2]}; const float ln = sqrtf(dot3(d, d)), dist = ln - r1 - r2;
+    if (dist > 0.f) return false;
+    const bool same = ln < 1e-12f;  // coincident centres: mju_normalize3 returns (1, 0, 0)
+    const float n3[3] = {same ? 1.f : d[0] / ln, same ? 0.f : d[1] / ln, same ? 0.f : d[2] / ln}, mm = r1 + 0.5f * dist;
+    const float ps[3] = {ca[0] + mm * n3[0], ca[1] + mm * n3[1], ca[2] + mm * n3[2]};
+    sk.push(ps, n3, dist);
+    return true;
+  };
+  float a1[3], a2[3]; col3(a1, R1, 2); col3(a2, R2, 2);
+  for (int i = 0; i < 3; i++) { a1[i] *= L1; a2[i] *= L2; }
+  const float dif[3] = {p1[0] - p2[0], p1[1] - p2[1], p1[2] - p2[2]};
+  const float ma = dot3(a1, a1), mb = -dot3(a1, a2), mc = dot3(a2, a2), u = -dot3(a1, dif), v = dot3(a2, dif);
+  const float det = ma * mc - mb * mb;
+  if (fabsf(det) >= 1e-6f * ma * mc) {  // (MuJoCo: |det| >= mjMINVAL in fp64; in fp32 the determinant of two axes less than ~1e-3 rad apart is rounding noise)
+    float x1 = (mc * u - mb * v) / det, x2 = (ma * v - mb * u) / det;
+    if (x1 > 1.f) { x1 = 1.f; x2 = (v - mb) / mc; } else if (x1 < -1.f) { x1 = -1.f; x2 = (v + mb) / mc; }
+    if (x2 > 1.f) { x2 = 1.f; x1 = jh_clampf((u - mb) / ma, -1.f, 1.f); }
+    else if (x2 < -1.f) { x2 = -1.f; x1 = jh_clampf((u + mb) / ma, -1.f, 1.f); }
+    const float v1[3] = {p1[0] + a1[0] * x1, p1[1] + a1[1] * x1, p1[2] + a1[2] * x1}, v2[3] = {p2[0] + a2[0] * x2, p2[1] + a2[1] * x2, p2[2] + a2[2] * x2};
+    sphere_sphere(v1, v2);
+  } else {
+    int nfound = 0;
+#pragma unroll 1
+    for (int e = 0; e < 4; e++) {
+      float x1, x2;
+      if (e < 2) { x1 = e == 0 ? 1.f : -1.f; x2 = jh_clampf((v - x1 * mb) / mc, -1.f, 1.f); }
+      else { x2 = e == 2 ? 1.f : -1.f; x1 = jh_clampf((u - x2 * mb) / ma, -1.f, 1.f); }
+      const float v1[3] = {p1[0] + a1[0] * x1, p1[1] + a1[1] * x1, p1[2] + a1[2] * x1}, v2[3] = {p2[0] + a2[0] * x2, p2[1] + a2[1] * x2, p2[2] + a2[2] * x2};
+      if (nfound < 2 && sphere_sphere(v1, v2)) nfound++;
+    }
+  }
+}
+#endif
 
 // world pose of collision geom g (all fr3 collision geoms are boxes); body -1 = static (pose stored in world coordinates)
 __device__ __forceinline__ void geom_pose3(const RS6& S, const float* gf, int body, float* gp, float* gR, bool want_R) {
@@ -707,7 +769,13 @@ __global__ __launch_bounds__(WAVE) __attribute__((amdgpu_waves_per_eu(JH_V6_WPE,
             const int b1 = gI[m.oAGI + g1 * GEOM_I];
             if (b1 < 0) { for (int k = 0; k < 9; k++) R1[k] = f1[GF_R + k]; } else mulMM(R1, S.xR[b1], f1 + GF_R);
             mulMTV(dl, R1, dc);
+#if JH_V6_SELF
+            const bool cap1 = gI[m.oAGI + g1 * GEOM_I + 1] == GCAPSULE;  // (a capsule as geom 1, against another capsule: the box around it is (r, r, L + r))
+            const float bx = f1[GF_SIZE], by = cap1 ? f1[GF_SIZE] : f1[GF_SIZE + 1], bz = cap1 ? f1[GF_SIZE] + f1[GF_SIZE + 1] : f1[GF_SIZE + 2];
+            const float ex = fmaxf(fabsf(dl[0]) - bx, 0.f), ey = fmaxf(fabsf(dl[1]) - by, 0.f), ez = fmaxf(fabsf(dl[2]) - bz, 0.f);
+#else
             const float ex = fmaxf(fabsf(dl[0]) - f1[GF_SIZE], 0.f), ey = fmaxf(fabsf(dl[1]) - f1[GF_SIZE + 1], 0.f), ez = fmaxf(fabsf(dl[2]) - f1[GF_SIZE + 2], 0.f);
+#endif
             hit = ex * ex + ey * ey + ez * ez <= rb2 * rb2;
           }
         }
@@ -730,7 +798,16 @@ __global__ __launch_bounds__(WAVE) __attribute__((amdgpu_waves_per_eu(JH_V6_WPE,
           float p1[3], R1[9], p2[3], R2[9], h1[3] = {f1[GF_SIZE], f1[GF_SIZE + 1], f1[GF_SIZE + 2]}, h2[3] = {f2[GF_SIZE], f2[GF_SIZE + 1], f2[GF_SIZE + 2]};
           geom_pose3(S, f1, gI[m.oAGI + g1 * GEOM_I], p1, R1, true); geom_pose3(S, f2, gI[m.oAGI + g2 * GEOM_I], p2, R2, true);
           const int sbA = gI[m.oAGI + g1 * GEOM_I], sbB = gI[m.oAGI + g2 * GEOM_I];
-          Sink6 sk{&S, stats, p, sbA >= 1 && sbB >= 1, ovf_all ? ovf_all + (size_t)nc * (NOVF * RAW_F) : nullptr};  // (copies of a rollout in latency mode write the same values to the same row)
+#if JH_V6_SELF
+          const bool ffp = (sbA == LF && sbB == RF) || (sbA == RF && sbB == LF);  // (the other pairs between two arm bodies are general contacts: slot_sides)
+#else
+          const bool ffp = sbA >= 1 && sbB >= 1;
+#endif
+          Sink6 sk{&S, stats, p, ffp, ovf_all ? ovf_all + (size_t)nc * (NOVF * RAW_F) : nullptr};  // (copies of a rollout in latency mode write the same values to the same row)
+#if JH_V6_SELF
+          if (gI[m.oAGI + g1 * GEOM_I + 1] == GCAPSULE) collide_capsule_capsule(sk, p1, R1, h1[0], h1[1], p2, R2, h2[0], h2[1]);  // (link against link; a capsule first meets a capsule only)
+          else
+#endif
           if (gI[m.oAGI + g2 * GEOM_I + 1] == GCAPSULE) collide_box_capsule(sk, p1, R1, h1, p2, R2, h2[0], h2[1]);  // (a pair's capsule is its second geom: jh_model_is_fr3)
           else collide_box_box(sk, p1, R1, h1, p2, R2, h2);
         }
@@ -1201,7 +1278,7 @@ __global__ __launch_bounds__(WAVE) __attribute__((amdgpu_waves_per_eu(JH_V6_WPE,
 
 }  // namespace
 
-bool jh_model_is_fr3(const jh_model* m) {
+bool JH_V6_NAME(jh_model_is_fr3)(const jh_model* m) {
   if (!(m->kind == JH_TASK_FR3_PICK && m->nq == NQ && m->nv == NVT && m->nu == NU && m->ns == NS && m->h_i.size() > 24 && m->h_i[0] == NMB && m->h_i[9] == 0)) return false;
   const int gi = m->h_i[13];
   // 7 hinges in a chain welded to the world, two slides on the last link; boxes only; at most one joint equality on the fingers
@@ -1229,10 +1306,16 @@ bool jh_model_is_fr3(const jh_model* m) {
   for (int p = 0; p < npair; p++) {  // pairs between two articulated bodies are kept as finger-finger contacts: nothing else qualifies
     const int* pi = m->h_i.data() + gi + 8 + nag * jh_eng::GEOM_I + 2 * p;
     const int b1 = m->h_i[gi + 8 + pi[0] * jh_eng::GEOM_I], b2 = m->h_i[gi + 8 + pi[1] * jh_eng::GEOM_I];
+#if JH_V6_SELF
+    // the self-collision build: any two different bodies, of which at most one is static and at most one the free box; a capsule first meets a capsule only
+    if (pi[0] < 0 || pi[0] >= nag || pi[1] < 0 || pi[1] >= nag || b1 == b2 || b1 > RF || b2 > RF) return false;
+    if (m->h_i[gi + 8 + pi[0] * jh_eng::GEOM_I + 1] == jh_eng::GCAPSULE && m->h_i[gi + 8 + pi[1] * jh_eng::GEOM_I + 1] != jh_eng::GCAPSULE) return false;
+#else
     if (b1 >= 1 && b2 >= 1 && !((b1 == LF && b2 == RF) || (b1 == RF && b2 == LF))) return false;
     // a capsule is always the second geom of its pair and meets a box of the static geometry or of the free body only
     if (m->h_i[gi + 8 + pi[0] * jh_eng::GEOM_I + 1] != jh_eng::GBOX) return false;
     if (m->h_i[gi + 8 + pi[1] * jh_eng::GEOM_I + 1] == jh_eng::GCAPSULE && b1 >= 1) return false;
+#endif
   }
   {  // the two finger slides must be antiparallel in the frame of their common parent: the finger-finger slots rely on it (struct SlotF)
     float w[2][3];
@@ -1247,9 +1330,9 @@ bool jh_model_is_fr3(const jh_model* m) {
   return true;
 }
 
-int jh_engine6_rollout_cost(const jh_model* m, const float* x0, const float* nominal, const float* noise, int ldn, const float* sigma, const float* W,
+int JH_V6_NAME(jh_engine6_rollout_cost)(const jh_model* m, const float* x0, const float* nominal, const float* noise, int ldn, const float* sigma, const float* W,
                             const float* lohi, const float* tp, int phase, int N, int n_offset, int H, int K, float* costs, float* knots_out, float* trace, hipStream_t st) {
-  if (!jh_model_is_fr3(m)) { jh_set_error("rollout_cost: the cooperative arm kernel (matrix-free generation) is instantiated for fr3_pick only"); return JH_ERR_UNSUPPORTED; }
+  if (!JH_V6_NAME(jh_model_is_fr3)(m)) { jh_set_error(JH_V6_SELF ? "rollout_cost: the self-collision build of the cooperative arm kernel is instantiated for fr3_pick with its arm pairs only" : "rollout_cost: the cooperative arm kernel (matrix-free generation) is instantiated for fr3_pick only; an image with pairs between arm bodies runs on its self-collision build"); return JH_ERR_UNSUPPORTED; }
   JH_REQUIRE(K <= 8, "rollout_cost: the cooperative arm kernel keeps at most 8 knots per actuator in registers (K=%d)", K);
   const int dshift = jh_latency_shift(N, RPW), per_wave = RPW >> dshift;
   int grid = (N + per_wave - 1) / per_wave;
@@ -1262,9 +1345,9 @@ int jh_engine6_rollout_cost(const jh_model* m, const float* x0, const float* nom
   return jh_launch_done(ovf, st);
 }
 
-int jh_engine6_materialize(const jh_model* m, const float* x0, int x0_batched, const float* controls, int N, int H, float* states, float* sensors,
+int JH_V6_NAME(jh_engine6_materialize)(const jh_model* m, const float* x0, int x0_batched, const float* controls, int N, int H, float* states, float* sensors,
                            hipStream_t st) {
-  if (!jh_model_is_fr3(m)) { jh_set_error("rollout_materialize: the cooperative arm kernel is instantiated for fr3_pick only"); return JH_ERR_UNSUPPORTED; }
+  if (!JH_V6_NAME(jh_model_is_fr3)(m)) { jh_set_error(JH_V6_SELF ? "rollout_materialize: the self-collision build of the cooperative arm kernel is instantiated for fr3_pick with its arm pairs only" : "rollout_materialize: the cooperative arm kernel is instantiated for fr3_pick only; an image with pairs between arm bodies runs on its self-collision build"); return JH_ERR_UNSUPPORTED; }
   const int dshift = jh_latency_shift(N, RPW), per_wave = RPW >> dshift;
   int grid = (N + per_wave - 1) / per_wave;
   // one overflow row per rollout for the general contacts above the LDS pool: stream-ordered allocation (the pool hands the same block back launch after launch),

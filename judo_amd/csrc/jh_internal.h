@@ -29,6 +29,7 @@ struct jh_model {
   int kernel_gen;  // articulated engine kernel: 3 = cooperative 16-lanes-per-rollout, two waves per SIMD (leap_cube: v5; fr3_pick: v6, matrix-free contact Jacobian), 2 = cooperative, one wave per SIMD (leap_cube: v2, fr3_pick: v3), 1 = one lane per rollout
   int contact_capacity;  // leap_cube generation 3: 48 (all in LDS, jh_engine_v5.hip) or 64 (jh_engine_v5_cap64.hip); jh_model_set_contact_capacity
   int cylinders;  // leap_cube family: cylinder geoms in the image (caltech_leap_cube packed with fingertips="cylinder"); > 0 selects the cylinder build (jh_engine_v5_cyl.hip: generation 3, 64 contacts) and nothing else runs such an image
+  int arm_pairs;  // fr3_pick: candidate pairs of the image between two arm bodies other than the two fingers, or of a box on the arm against a capsule on the arm or the static base (engine_model.pack_engine_model on a description with "self_collision"); > 0 selects the self-collision build (jh_engine_v6_self.hip: generation 3) and nothing else runs such an image
   int self_collision;  // leap_cube on jh_engine_v5.hip: model the hand's own contacts (finger-finger, finger-palm) as MuJoCo does; 0 = the cube's contacts only
   int rollout_schedule;  // leap_cube generation 3, fused launches: 0 = persistent waves on a queue of rollout groups where the launch exceeds the GPU's wave slots (the default), 1 = always the static grid, 2 = the queue wherever the kernel has it (jh_model_set_rollout_schedule)
   int plan_step_launches;  // closed-form models' plan step: 0 = one launch where it fits (the default), 1 = always one launch, 2 = always two (jh_model_set_plan_step_launches)
@@ -150,6 +151,12 @@ int jh_engine6_rollout_cost(const jh_model* m, const float* x0, const float* nom
                             const float* lohi, const float* tp, int phase, int N, int n_offset, int H, int K, float* costs, float* knots_out, float* trace, hipStream_t st);
 int jh_engine6_materialize(const jh_model* m, const float* x0, int x0_batched, const float* controls, int N, int H, float* states, float* sensors,
                            hipStream_t st);
+// jh_engine_v6_self.hip: the same kernel with the arm's own pairs (an image with jh_model::arm_pairs > 0, which jh_model_is_fr3 refuses)
+bool jh_model_is_fr3_self(const jh_model* m);
+int jh_engine6_rollout_cost_self(const jh_model* m, const float* x0, const float* nominal, const float* noise, int ldn, const float* sigma, const float* W,
+                                 const float* lohi, const float* tp, int phase, int N, int n_offset, int H, int K, float* costs, float* knots_out, float* trace, hipStream_t st);
+int jh_engine6_materialize_self(const jh_model* m, const float* x0, int x0_batched, const float* controls, int N, int H, float* states, float* sensors,
+                                hipStream_t st);
 
 // ---- device helpers ------------------------------------------------------------------------------------------
 // MuJoCo's impedance curve d(x) (solimp = dmin, dmax, width, midpoint, power), x = |pos - margin| / width.

@@ -98,6 +98,9 @@ class GpuModel:
         # caltech_leap_cube's fingertips as the kernel collides them: "sphere" (the stand-in of engine_model.kernel_stand_ins) or "cylinder" (the MJCF's geometry: an image
         # that keeps the cylinders, and with it the cylinder build of the leap kernel, 64 contacts).  The library decides from the image; this reports what it chose.
         self.fingertips = "cylinder" if self.build()["cylinder_build"] else "sphere"
+        # fr3_pick: the arm's own pairs (link against link, gripper against link) are in the image or not ("self_collision" in the description); the library selects the
+        # self-collision build of the fr3 kernel from the image, and this reports what it chose
+        self.arm_self_collision = self.fr3_build()["self_collision_build"]
         if self.desc.get("family", self.task) == "leap_cube":
             self.set_contact_capacity(48 if self.task == "leap_cube" else 64)
 
@@ -114,6 +117,12 @@ class GpuModel:
         out = (C.c_int * 4)()
         _lib.check(_lib.lib().jh_model_build(self.handle, out), "jh_model_build")
         return {"kernel_generation": int(out[0]), "contact_capacity": int(out[1]), "cylinder_build": bool(out[2]), "cylinders": int(out[3])}
+
+    def fr3_build(self) -> dict:
+        """`jh_model_fr3_build`: whether this model runs the self-collision build of the fr3 kernel, and how many pairs of its image only that build collides."""
+        out = (C.c_int * 4)()
+        _lib.check(_lib.lib().jh_model_fr3_build(self.handle, out), "jh_model_fr3_build")
+        return {"self_collision_build": bool(out[0]), "arm_pairs": int(out[1]), "default_build_accepts": bool(out[2]), "self_collision_build_accepts": bool(out[3])}
 
     def set_contact_capacity(self, contacts: int) -> None:
         """leap_cube family: 48 or 64 contacts per rollout (`jh_model_set_contact_capacity`)."""

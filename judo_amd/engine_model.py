@@ -225,7 +225,11 @@ def sensor_reference_frames(desc: dict) -> list[float] | None:
 def generic_pairs(desc: dict, fused: dict, st: dict, cube_only: bool | None = None) -> list[tuple[int, int]]:
     """Candidate box-box / box-sphere pairs for the generic (reference-kernel) contact path, MuJoCo's static filters
     applied on the ORIGINAL bodies: same welded body, parent-child (unless the parent is welded to the world), excludes.
-    leap_cube: restricted to pairs that involve the cube (hand self-collision is out of scope this round)."""
+    leap_cube: restricted to pairs that involve the cube (hand self-collision is out of scope this round).
+    fr3_pick: the arm links' capsules against static geometry and the free body only (78 pairs, what the default build of k_fr3_v6 collides), unless the description
+    carries "self_collision": then every pair the MJCF leaves (190 = oracle.collision_pairs(desc)), the other 112 -- link against link, hand / finger box against link --
+    BEHIND the default list, which stays a prefix."""
+    arm_pairs = bool(desc.get("self_collision", False))
     bodies = desc["bodies"]
     njnt = [0] * len(bodies)
     for j in desc["joints"]:
@@ -243,7 +247,7 @@ def generic_pairs(desc: dict, fused: dict, st: dict, cube_only: bool | None = No
     excl = {tuple(sorted(e)) for e in desc["excludes"]}
     geoms = fused["geoms"]
     free_fused = st["free"]
-    out = []
+    out, extra = [], []
     for a in range(len(geoms)):
         for b in range(a + 1, len(geoms)):
             ia, ib = a, b
@@ -252,12 +256,14 @@ def generic_pairs(desc: dict, fused: dict, st: dict, cube_only: bool | None = No
             ga, gb = geoms[ia], geoms[ib]
             ta, tb = ga["type"], gb["type"]
             round_ = ("sphere", "cylinder")  # (a cylinder is in `geoms` only when the image keeps the fingertips as the MJCF has them: pack_engine_model(fingertips="cylinder"))
-            if not ((ta == "box" and tb in ("box", "sphere", "capsule", "cylinder")) or (ta in round_ and tb == "box") or (ta in round_ and tb in round_ and cube_only is False)):
+            if not ((ta == "box" and tb in ("box", "sphere", "capsule", "cylinder")) or (ta in round_ and tb == "box") or (ta in round_ and tb in round_ and cube_only is False)
+                    or (arm_pairs and ta == tb == "capsule")):
                 continue  # (sphere-sphere, and cylinder against sphere or cylinder: the fingertips of two fingers; only jh_engine_v5.hip collides the hand with itself)
             ba, bb = ga["orig_body"], gb["orig_body"]
             wa, wb = weld(ba), weld(bb)
-            if tb == "capsule" and not (wa == 0 or ga["body"] == free_fused):
-                continue  # the arm links' stand-ins meet static geometry and the free body only (oracle/oracle.py::collision_pairs has the reason)
+            new = ta == "capsule" or (tb == "capsule" and not (wa == 0 or ga["body"] == free_fused))
+            if new and not arm_pairs:
+                continue  # the arm links' stand-ins meet static geometry and the free body only (oracle/oracle.py::collision_pairs has the reason) in the default image
             if wa == wb or tuple(sorted((ba, bb))) in excl:
                 continue
             if (weld_parent(ba) == wb and wb != 0) or (weld_parent(bb) == wa and wa != 0):
@@ -265,7 +271,7 @@ def generic_pairs(desc: dict, fused: dict, st: dict, cube_only: bool | None = No
             leap = desc.get("family", desc["task"]) == "leap_cube"
             if (leap if cube_only is None else cube_only) and free_fused not in (ga["body"], gb["body"]):
                 continue  # (the one-lane reference kernel and jh_engine_v2.hip model the cube's contacts only; jh_engine_v5.hip adds the hand's own)
-            out.append((ia, ib))
+            (extra if new else out).append((ia, ib))
     # order by importance for the fixed-capacity contact pools: pairs with the free body first, then pairs against static
     # geometry, pairs between two articulated bodies (e.g. the two fingers' pad stacks) last -- those are the ones dropped on overflow
     def rank(pr):
@@ -274,7 +280,7 @@ def generic_pairs(desc: dict, fused: dict, st: dict, cube_only: bool | None = No
             return 0
         return 1 if (st["is_static"][ba] or st["is_static"][bb]) else 2
     out.sort(key=rank)  # stable: original order within a class
-    return out
+    return out + extra  # (the self-collision image's own pairs, in model order)
 
 
 def kernel_stand_ins(desc: dict) -> dict:
@@ -306,6 +312,10 @@ def pack_engine_model(desc: dict, fingertips: str | None = None) -> bytes:
     if fingertips not in ("sphere", "cylinder"):
         raise ValueError(f"fingertips must be 'sphere' or 'cylinder', got {fingertips!r}")
     keep_cyl = fingertips == "cylinder" and desc.get("family", desc["task"]) == "leap_cube"
+    if not isinstance(desc.get("self_collision", False), bool):
+        raise ValueError(f"self_collision must be a bool, got {desc['self_collision']!r}")
+    if desc.get("self_collision", False) and desc.get("family", desc["task"]) != "fr3_pick":
+        raise NotImplementedError("self_collision: only the fr3 kernel has a build selected by this entry (the leap kernel models the hand's own contacts by default)")
     if fingertips == "cylinder" and not keep_cyl:
         raise NotImplementedError("fingertips='cylinder': only the leap kernel has a cylinder build")
     for g in desc["geoms"]:

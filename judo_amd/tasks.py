@@ -434,8 +434,16 @@ class FR3Pick(Task[FR3PickConfig]):
     name = "fr3_pick"
     config_t = FR3PickConfig
 
-    def __init__(self) -> None:
+    def __init__(self, self_collision: bool = False) -> None:
+        """`self_collision`: which collision pairs the kernel models.  False (default, what `make_controller` builds): the 78 pairs of DESIGN.md section 8 -- the arm links
+        against table and cube only.  True: all 190 pairs the MJCF leaves (fr3_components/fr3.xml:11-99), link against link and gripper against link included, on the
+        self-collision build of the fr3 kernel -- `gpu_model()`, a `GpuRolloutBackend` on it and a `Controller` on this task all run that build."""
+        if not isinstance(self_collision, bool):
+            raise ValueError(f"self_collision must be a bool, got {self_collision!r}")
         super().__init__()
+        self.self_collision = self_collision
+        if self_collision:
+            self.desc = dict(self.desc, self_collision=True)  # (read by engine_model.generic_pairs when the device image is packed)
         self.reset_command = np.array([0, 0, 0, -1.57079, 0, 1.57079, -0.7853, 0.0])
         self._phase = Phase.LIFT
         self.reset()
