@@ -243,6 +243,32 @@ int jh_update_fused(const float* costs, const float* knots_nku, const float* nom
 int jh_plan_step(const jh_model* m, void* blk_dev, const void* blk_host, size_t blk_bytes, int o_nominal, int o_sigma, int o_tp, int o_lohi, const float* noise, int ldn,
                  const float* W, int phase, int N, int n_offset, int H, int K, float* costs, float* knots_out, float* trace, int mode, float lambda, int k, int tie_high, int E,
                  int row_floats, int colmajor, float* scratch, float* out, void* out_host_mark, void* const* timing, void* stream);
+/* B independent plan steps of ONE model in one call and one wait: B controllers (several robots, several goals, a domain-randomised sweep) whose iterations of
+ * Controller.update_action's loop (judo/controller/controller.py:250-299) the reference would run back to back, one process and one launch chain each.  jh_plan_step with a
+ * leading B and strides; the problems share the model, N, H, K, W, the optimizer kind and the scalar arguments (mode, lambda, k, tie_high, E), and each has its own
+ *   packed block   [x0 | nominal | sigma | task params | ctrl bounds], B sub-blocks blk_stride_bytes apart (a multiple of 4, >= blk_bytes), all with the same o_* offsets;
+ *   noise          (K * nu, ldn) per problem, noise_stride_floats apart (>= K * nu * ldn);
+ *   costs          B x N;     trace   B x (N x row_floats), or NULL (row_floats = H x jh_model_trace_layout out[1], as for jh_plan_step);
+ *   scratch        B x jh_update_fused_scratch_floats(N, K, nu) = jh_plan_batch_scratch_floats(B, N, K, nu) floats, ZERO before the first use (every problem's ticket and,
+ *                  in word 1 of problem 0's, the batch's; every launch leaves them at zero);
+ *   out            B x out_stride_floats (>= 2 * K * nu + E * (2 + row_floats)), each [nominal | sigma | E trace records].
+ * blk_dev == blk_host reads the blocks in place; out_host_mark != out is the polled completion word, stored ONCE, behind the last of the B problems (each problem's last
+ * workgroup bumps a batch counter behind a fence of its outputs, the one that draws B - 1 stores the word behind a system-scope fence); out_host_mark == out: the stream's
+ * event.  One GPU (n_offset = 0), no knots_out.  A problem's costs, nominal, sigma and trace records are bit for bit those of jh_plan_step on its sub-block: the kernels run
+ * the single call's code on offset pointers (cartpole, cylinder_push: one launch with blockIdx.y = problem, or two above jh_model_one_launch_max_knots; the leap family:
+ * the rollout kernel on the static grid (groups, B) -- the latency mode chosen from B * N rollouts, no persistent queue -- then the batched update tail).  B = 1 takes the same
+ * code.  JH_ERR_INVALID: B < 1, B > 65535 (the grid's second dimension), a stride smaller than a block / a noise slice / an output record, a forced one-launch plan step that
+ * does not fit.  JH_ERR_UNSUPPORTED: fr3_pick (its phase is a per-problem host decision, judo/tasks/fr3_pick.py:191-223) and the cross-check kernel generations; Spot, the
+ * sharded path, the materialise and plugin-reward paths have no batched form. */
+size_t jh_plan_batch_scratch_floats(int B, int N, int K, int nu);
+int jh_plan_step_batch(const jh_model* m, int B, void* blk_dev, const void* blk_host, size_t blk_bytes, size_t blk_stride_bytes, int o_nominal, int o_sigma, int o_tp, int o_lohi,
+                       const float* noise, int ldn, size_t noise_stride_floats, const float* W, int N, int H, int K, float* costs, float* trace, int mode, float lambda, int k,
+                       int tie_high, int E, int row_floats, int colmajor, float* scratch, float* out, size_t out_stride_floats, void* out_host_mark, void* const* timing,
+                       void* stream);
+/* The noise of those B problems in one launch (judo/optimizers/{mppi.py:52,ps.py:43,cem.py:67}, one np.random.randn per controller): problem b's (rows, ldn) slice of `out`
+ * (B x rows x ldn floats) is bit for bit what jh_noise_normal(seeds[b], draws[b], rows, 0, n_local, out + b * rows * ldn, ldn) writes; columns n_local .. ldn - 1 are left
+ * alone.  seeds / draws: HOST arrays of B entries, read before the call returns (one launch per 256 problems: the pairs travel as kernel arguments). */
+int jh_noise_normal_batch(int B, const unsigned long long* seeds /* HOST */, const unsigned int* draws /* HOST */, int rows, int n_local, float* out, int ldn, void* stream);
 /* The same iteration with the rollouts sharded over G ranks (the reference has no multi-process form: judo/controller/controller.py:246-299 runs in one
  * process): launch -> all-gather -> merge.  jh_update_shard is jh_update_fused with the last stage left to the ranks' merge: it writes this rank's record
  *   [ MPPI: beta, S, V(K*nu)  |  elites: k x (cost, global index (bits), knots(K*nu)) ]  followed by  E x (cost, global index (bits), trace row(row_floats))

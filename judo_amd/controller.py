@@ -120,6 +120,7 @@ class Controller:
         self._shift_cache: tuple = (None, None)
         self._grid_cache: tuple = (None, None)
         self._lohi_cache: tuple = (None, None)
+        self._shard_cache: tuple = (None, None)
         self._bufs: _PlanBuffers | None = None
         self._bufs_key: tuple | None = None
         self._noise_bufs: list[torch.Tensor] | None = None
@@ -413,35 +414,9 @@ class Controller:
 
     def update_action(self) -> None:
         lib = _lib.lib()
-        opt, task, dev = self.optimizer, self.task, self.device
-        if self.current_state.shape != (task.nq + task.nv,):
-            raise ValueError(f"current state must have shape ({task.nq + task.nv},), got {self.current_state.shape}")
-        if self.optimizer_cfg.num_rollouts <= 0:
-            raise ValueError("need at least one rollout")
-        self._fix_num_nodes()
-        N, K, nu, H = opt.num_rollouts, opt.num_nodes, self.nu, self.num_timesteps
-        if K * nu > _lib.MAX_KNOT_DIM:
-            raise ValueError(f"num_nodes * nu = {K * nu} exceeds the update kernels' limit of {_lib.MAX_KNOT_DIM} (include/judo_amd.h JH_MAX_KNOT_DIM)")
-        world, rank = world_info(self.group)
-        shard: Shard = shard_rollouts(N, world, rank)
-        self._prefetch_args = None
-
-        # time shift (host; needs the previous plan's spline)
-        new_times = self.time + self.spline_timesteps
-        nominal_knots = self._shifted_nominal(new_times)
-        want_threads = shard.count if task.uses_locomotion_policy else N
-        if self.rollout_backend.num_threads != want_threads:  # controller.py:225-229
-            self.rollout_backend.update(want_threads)
-            self._last_policy_output = None
-        nrm = self._current_normalizer()
-        nominal_n = nrm.normalize(nominal_knots)  # the optimiser's state lives in normalised units (controller.py:222)
-        opt.pre_optimization(self.times, new_times)
-
-        W = self._weights(K, H)
-        x0 = np.array(self.current_state, dtype=np.float64)
-        fused_opt = self.uses_fused_optimizer
-        E = self._num_trace_elites(N)
-        tp0 = task.task_params(self.system_metadata)
+        opt, task = self.optimizer, self.task
+        p = self._begin_plan()
+        N, K, nu, H, world, shard, nrm, nominal_n, W, x0, new_times, fused_opt, E, tp0 = p
         b = self._buffers(shard.count, K, nu, task.nq + task.nv, len(tp0), opt.record_floats() if fused_opt else 0, E)
         stream = self._stream = current_stream_ptr()
         state: dict[str, Any] = dict(E=E, x0=x0, new_times=new_times)
@@ -458,12 +433,50 @@ class Controller:
             else:
                 nominal_n = self._candidates_iteration(lib, b, nrm, nominal_n, W, shard, H, K, nu, N, stream, state)
             i += 1
+        self._end_plan(p, b, state, nominal_n, i, staged, stream)
 
-        if i > 0:
+    def _begin_plan(self) -> tuple:
+        """The host prelude of a plan step (controller.py:210-238): checks, the time shift of the nominal, the normaliser, `pre_optimization`, W.  Shared with
+        `ControllerFleet.update_action`, which runs it for every member in front of its one batched launch.  Returns (N, K, nu, H, world, shard, normaliser,
+        normalised nominal, W, x0, new knot times, fused optimizer?, trace elites, task params)."""
+        opt, task = self.optimizer, self.task
+        if self.current_state.shape != (task.nq + task.nv,):
+            raise ValueError(f"current state must have shape ({task.nq + task.nv},), got {self.current_state.shape}")
+        if self.optimizer_cfg.num_rollouts <= 0:
+            raise ValueError("need at least one rollout")
+        self._fix_num_nodes()
+        N, K, nu, H = opt.num_rollouts, opt.num_nodes, self.nu, self.num_timesteps
+        if K * nu > _lib.MAX_KNOT_DIM:
+            raise ValueError(f"num_nodes * nu = {K * nu} exceeds the update kernels' limit of {_lib.MAX_KNOT_DIM} (include/judo_amd.h JH_MAX_KNOT_DIM)")
+        world, rank = world_info(self.group)
+        if self._shard_cache[0] != (N, world, rank):  # (an immutable record of three integers: built when one of them changes, not in every plan step)
+            self._shard_cache = ((N, world, rank), shard_rollouts(N, world, rank))
+        shard: Shard = self._shard_cache[1]
+        self._prefetch_args = None
+
+        # time shift (host; needs the previous plan's spline)
+        new_times = self.time + self.spline_timesteps
+        nominal_knots = self._shifted_nominal(new_times)
+        want_threads = shard.count if task.uses_locomotion_policy else N
+        if self.rollout_backend.num_threads != want_threads:  # controller.py:225-229
+            self.rollout_backend.update(want_threads)
+            self._last_policy_output = None
+        nrm = self._current_normalizer()
+        nominal_n = nrm.normalize(nominal_knots)  # the optimiser's state lives in normalised units (controller.py:222)
+        opt.pre_optimization(self.times, new_times)
+
+        W = self._weights(K, H)
+        x0 = np.array(self.current_state, dtype=np.float64)
+        return (N, K, nu, H, world, shard, nrm, nominal_n, W, x0, new_times, self.uses_fused_optimizer, self._num_trace_elites(N), task.task_params(self.system_metadata))
+
+    def _end_plan(self, p: tuple, b, state: dict, nominal_n: np.ndarray, iters: int, staged: bool, stream) -> None:
+        """The host epilogue of a plan step (controller.py:293-299): the trace stage if no iteration set it, the denormalised nominal, the new spline.  `p`: what `_begin_plan` returned."""
+        N, K, nu, H, world, shard, nrm, _, W, x0, new_times, fused_opt, E, tp0 = p
+        if iters > 0:
             self.costs_device = state["costs"]
             self.candidate_knots_device = state.get("knots_out")
             if not staged:
-                self._stage_traces(lib, b, state, shard, world, E, x0, new_times, K, nu, stream)
+                self._stage_traces(_lib.lib(), b, state, shard, world, E, x0, new_times, K, nu, stream)
         self.last_shard = shard
         self.nominal_knots = nrm.denormalize(nominal_n)  # with the statistics as updated in the loop (controller.py:296)
         self.times = new_times
@@ -552,18 +565,12 @@ class Controller:
     def _fused_iteration(self, lib, b: _PlanBuffers, nrm: Normalizer, nominal_n: np.ndarray, W, shard: Shard, world: int, H: int, K: int, nu: int, N: int,
                          stream, state: dict) -> np.ndarray:
         opt = self.optimizer
-        sigma_n = np.asarray(opt.knot_sigma(), dtype=np.float64)  # normalised units; may advance CEM state
-        # every shipped normaliser is affine per actuator: raw = center + scale * normalised (judo_amd/normalization.py)
-        scale, center = nrm.noise_scale(), nrm.denormalize(np.zeros(nu))
-        nominal_raw = nrm.denormalize(nominal_n)
-        sigma_raw = sigma_n * scale[None, :]
         shape = self._iteration_shape(world, nrm)
         one_call = shape in ("plan_step", "plan_step_shard")
-        self._pack_block(b, nominal_raw, sigma_raw, self._raw_bounds(nrm), upload=not one_call)  # (the plan-step calls upload the block themselves or read it in place)
+        scale, center = self._iteration_inputs(b, nrm, nominal_n, nu, upload=not one_call)  # (the plan-step calls upload the block themselves or read it in place)
         noise = self._draw_noise(shard.count, shard.offset)  # (K, nu, shard.count), possibly a view into the full draw
         self._prefetch_args = (shard.count, shard.offset)
         ldn, noise_p = int(noise.stride(1)), noise.data_ptr()
-        self._last_sigma_raw, self._last_nominal_before = sigma_raw, nominal_raw.copy()
         knots_out = None
         if self.keep_candidates:
             # the rollout kernels write candidate (k, u) of local rollout n at [(k * nu + u) * ldn + n] with the NOISE's row stride (include/judo_amd.h):
@@ -572,12 +579,30 @@ class Controller:
                 b.knots_out = torch.empty((K, nu, ldn), dtype=torch.float32, device=self.device)
             knots_out = b.knots_out[:, :, : shard.count]
         state.update(knots_out=knots_out, noise_p=noise_p, ldn=ldn, knots_nku=None, trace_buf=None)
-        is_cem = isinstance(getattr(opt, "sigma", None), np.ndarray)
-        n_res = 2 * K * nu if is_cem else K * nu  # nominal (| sigma); the trace records behind them carry an index column of int bit patterns and are not widened
         if one_call:
             E_t = self._plan_step(lib, b, shape, noise_p, ldn, knots_out, W, shard, world, H, K, nu, stream, state)
         else:
+            n_res = 2 * K * nu if isinstance(getattr(opt, "sigma", None), np.ndarray) else K * nu  # nominal (| sigma) to copy down
             E_t = self._rollout_update(lib, b, shape, nrm, noise_p, ldn, knots_out, W, shard, world, H, K, nu, N, n_res, stream, state)
+        return self._iteration_result(b, state, noise, noise_p, ldn, shard, H, K, nu, E_t, scale, center)
+
+    def _iteration_inputs(self, b, nrm: Normalizer, nominal_n: np.ndarray, nu: int, upload: bool) -> tuple[np.ndarray, np.ndarray]:
+        """The optimizer's sigma (may advance CEM state) and the packed block x0 | nominal | sigma | task params | bounds in raw units.  Returns the normaliser's
+        (scale, center): every shipped normaliser is affine per actuator, raw = center + scale * normalised (judo_amd/normalization.py)."""
+        sigma_n = np.asarray(self.optimizer.knot_sigma(), dtype=np.float64)  # normalised units
+        scale, center = nrm.noise_scale(), nrm.denormalize(np.zeros(nu))
+        nominal_raw = nrm.denormalize(nominal_n)
+        sigma_raw = sigma_n * scale[None, :]
+        self._pack_block(b, nominal_raw, sigma_raw, self._raw_bounds(nrm), upload=upload)
+        self._last_sigma_raw, self._last_nominal_before = sigma_raw, nominal_raw.copy()
+        return scale, center
+
+    def _iteration_result(self, b, state: dict, noise, noise_p: int, ldn: int, shard: Shard, H: int, K: int, nu: int, E_t: int, scale: np.ndarray, center: np.ndarray) -> np.ndarray:
+        """What an iteration's update left in the pinned output block nominal | sigma | E_t trace records: the new nominal in normalised units, the CEM sigma refit,
+        the staged trace records."""
+        opt = self.optimizer
+        is_cem = isinstance(getattr(opt, "sigma", None), np.ndarray)
+        n_res = 2 * K * nu if is_cem else K * nu  # nominal (| sigma); the trace records behind them carry an index column of int bit patterns and are not widened
         res = b.out_np[:n_res].astype(np.float64)
         if E_t:  # the update wrote the trace elites' records behind nominal | sigma, best first
             stride = 2 + state["trace_buf"][1]

@@ -1,4 +1,5 @@
 // jh_api.hip -- C-ABI entry points of libjudo_amd.so (argument checks, model handles, dispatch).
+#include <algorithm>
 #include <cmath>
 #include <cstdlib>
 #include <cstring>
@@ -454,6 +455,68 @@ extern "C" int jh_plan_step(const jh_model* m, void* blk_dev, const void* blk_ho
   unsigned* flag = (out_host_mark && out_host_mark != (void*)out) ? (unsigned*)out_host_mark : nullptr;  // (out_host_mark == out: the stream's event)
   return plan_step("plan_step", m, blk_dev, blk_host, blk_bytes, o_nominal, o_sigma, o_tp, o_lohi, noise, ldn, W, phase, N, n_offset, H, K, costs, knots_out, trace, mode, lambda, k,
                    tie_high, E, row_floats, colmajor, scratch, out, flag, nullptr, timing, stream);
+}
+
+// B plan steps of one model as ONE call (include/judo_amd.h): the B packed blocks go up in one copy (or are read in place), the kernels take the problem from blockIdx.y and
+// reach its buffers through strides, and one completion mark stands behind all of them.  Problem 0's launch record is built by the single call's own checks
+// (jh_update_tail_args); the kernels derive problem b's from it.
+extern "C" int jh_plan_step_batch(const jh_model* m, int B, void* blk_dev, const void* blk_host, size_t blk_bytes, size_t blk_stride_bytes, int o_nominal, int o_sigma, int o_tp, int o_lohi,
+                                  const float* noise, int ldn, size_t noise_stride_floats, const float* W, int N, int H, int K, float* costs, float* trace, int mode, float lambda, int k,
+                                  int tie_high, int E, int row_floats, int colmajor, float* scratch, float* out, size_t out_stride_floats, void* out_host_mark, void* const* timing,
+                                  void* stream) {
+  JH_REQUIRE(m && blk_dev && blk_host && out && scratch && noise && W && costs, "plan_step_batch: null pointer");
+  if (m->kind == JH_TASK_FR3_PICK) { jh_set_error("plan_step_batch: fr3_pick has no batched plan step (its phase is chosen per problem on the host)"); return JH_ERR_UNSUPPORTED; }
+  if (m->kind == JH_TASK_LEAP_CUBE && m->kernel_gen != 3) { jh_set_error("plan_step_batch: only kernel generation 3 of the leap family has a batched launch (this model runs %d)", m->kernel_gen); return JH_ERR_UNSUPPORTED; }
+  JH_REQUIRE(B >= 1, "plan_step_batch: B must be at least 1 (B=%d)", B);
+  JH_REQUIRE(B <= 65535, "plan_step_batch: B = %d exceeds the 65535 problems of a launch (the grid's second dimension)", B);
+  JH_REQUIRE(N > 0 && H > 0 && K >= 1, "plan_step_batch: N, H, K must be positive (N=%d H=%d K=%d)", N, H, K);
+  JH_REQUIRE(ldn >= N, "plan_step_batch: ldn (%d) < N (%d)", ldn, N);
+  const int KU = K * m->nu;
+  JH_REQUIRE(KU <= JH_MAX_KNOT_DIM, "plan_step_batch: K*nu = %d exceeds %d", KU, JH_MAX_KNOT_DIM);
+  const int nx = m->nq + m->nv;
+  JH_REQUIRE(o_nominal >= 0 && o_sigma >= 0 && o_tp >= 0 && o_lohi >= 0, "plan_step_batch: negative block offset");
+  const size_t need = sizeof(float) * (size_t)std::max(std::max(nx, o_nominal + KU), std::max(std::max(o_sigma + KU, o_tp + m->ntaskparam), o_lohi + 2 * m->nu));
+  JH_REQUIRE(blk_bytes >= need, "plan_step_batch: a block of %zu bytes does not hold x0 | nominal | sigma | task params | bounds at the given offsets (%zu bytes)", blk_bytes, need);
+  JH_REQUIRE(blk_stride_bytes >= blk_bytes && blk_stride_bytes % sizeof(float) == 0, "plan_step_batch: blk_stride_bytes = %zu is smaller than a block (%zu bytes) or no multiple of 4", blk_stride_bytes, blk_bytes);
+  JH_REQUIRE(noise_stride_floats >= (size_t)KU * (size_t)ldn, "plan_step_batch: noise_stride_floats = %zu is smaller than a problem's noise (K*nu*ldn = %zu)", noise_stride_floats, (size_t)KU * (size_t)ldn);
+  int t_adr = 0, t_nfl = 0, t_cm = 0;
+  if (trace) { trace_layout(m, &t_adr, &t_nfl, &t_cm); JH_REQUIRE(t_nfl > 0 && row_floats == H * t_nfl, "plan_step_batch: row_floats = %d is not H x the model's %d trace floats per step (jh_model_trace_layout)", row_floats, t_nfl); }
+  const int E_t = trace ? E : 0;
+  JH_REQUIRE(E_t >= 0 && E_t <= JH_MAX_ELITES, "plan_step_batch: bad trace arguments (E=%d)", E);
+  const size_t rec = 2 * (size_t)KU + (size_t)E_t * (2 + (size_t)(E_t > 0 ? row_floats : 0));
+  JH_REQUIRE(out_stride_floats >= rec, "plan_step_batch: out_stride_floats = %zu is smaller than an output record (nominal | sigma | E trace records = %zu floats)", out_stride_floats, rec);
+  const bool closed = m->kind == JH_TASK_CARTPOLE || m->kind == JH_TASK_CYLINDER_PUSH;
+  if (!closed && m->kind != JH_TASK_LEAP_CUBE) { jh_set_error("plan_step_batch: no batched kernel for this model"); return JH_ERR_UNSUPPORTED; }
+  hipStream_t st = (hipStream_t)stream;
+  const float* b = (const float*)blk_dev;
+  if (blk_dev != blk_host) { const int rc = jh_upload_async(blk_dev, blk_host, (size_t)(B - 1) * blk_stride_bytes + blk_bytes, stream); if (rc != JH_OK) return rc; }
+  if (timing) JH_HIP(hipEventRecord((hipEvent_t)timing[0], st));
+  unsigned* flag = (out_host_mark && out_host_mark != (void*)out) ? (unsigned*)out_host_mark : nullptr;  // (out_host_mark == out: the stream's event)
+  const unsigned expect = flag ? __atomic_load_n(flag, __ATOMIC_RELAXED) + 1u : 0u;
+  bool one = false;
+  if (int rc = plan_step_launches(m, N, H, K, costs, nullptr, W, noise, ldn, &one)) return rc;
+  jh_upd::TailArgs a;
+  if (int rc = jh_update_tail_args("plan_step_batch", costs, nullptr, b + o_nominal, noise, ldn, b + o_sigma, b + o_lohi, N, 0, K, m->nu, mode, lambda, k, tie_high, E_t, trace, row_floats, colmajor,
+                                   scratch, out, out + KU, E_t > 0 ? out + 2 * KU : nullptr, nullptr, &a)) return rc;
+  jh_upd::BatchArgs s;
+  s.B = B; s.blk = (long long)(blk_stride_bytes / sizeof(float)); s.noise = (long long)noise_stride_floats; s.costs = N; s.trace = (long long)N * row_floats;
+  s.scratch = (long long)jh_update_fused_scratch_floats(N, K, m->nu); s.out = (long long)out_stride_floats;
+  s.counter = reinterpret_cast<unsigned*>(scratch) + 1; s.done_flag = flag; s.done_value = expect;
+  int rc = JH_OK;
+  if (one) rc = jh_simple_plan_step_batch(m, b, W, b + o_tp, H, K, a, s, st);
+  else {
+    if (closed) rc = jh_simple_rollout_cost_batch(m, b, b + o_tp, W, H, K, a, s, st);
+    else
+      rc = m->cylinders > 0           ? jh_engine5_rollout_cost_batch_cyl(m, B, b, b + o_nominal, b + o_sigma, b + o_lohi, b + o_tp, s.blk, noise, ldn, s.noise, W, N, H, K, costs, trace, st)
+           : m->contact_capacity > 48 ? jh_engine5_rollout_cost_batch_cap64(m, B, b, b + o_nominal, b + o_sigma, b + o_lohi, b + o_tp, s.blk, noise, ldn, s.noise, W, N, H, K, costs, trace, st)
+                                      : jh_engine5_rollout_cost_batch(m, B, b, b + o_nominal, b + o_sigma, b + o_lohi, b + o_tp, s.blk, noise, ldn, s.noise, W, N, H, K, costs, trace, st);
+    if (rc == JH_OK && timing) JH_HIP(hipEventRecord((hipEvent_t)timing[1], st));
+    if (rc == JH_OK) rc = jh_update_tail_batch_launch(a, s, st);
+  }
+  if (rc == JH_OK && one && timing) JH_HIP(hipEventRecord((hipEvent_t)timing[1], st));
+  if (rc == JH_OK && timing) JH_HIP(hipEventRecord((hipEvent_t)timing[2], st));
+  if (rc == JH_OK) rc = download_begin(out, out, 0, stream, flag, expect);
+  return rc;
 }
 
 // The same iteration when the rollouts are sharded over G ranks: launch -> all-gather -> merge.  The tail writes this rank's record; jh_plan_merge

@@ -530,7 +530,13 @@ __device__ __forceinline__ bool chain_elim_order(int cmask, int c, int& level, i
 // atomicAdd by lane 0 -- until the tickets pass the group count.  A wave slot is then never held for a workgroup-mate's longer rollouts, and the launch drains over one
 // group's duration per wave instead of one workgroup's.  No wave waits for another, so nothing depends on which workgroups are resident.  The static instantiations
 // (PERSIST = false: a wave's group is its place in the grid, `head` unused) compile to the code they had without it.
-template <bool MATERIALIZE, int WPB, bool SELF, bool PERSIST = false>
+// BATCH (fused mode, static grid only -- there is NO queue for batched launches: a batch's problems fill the GPU side by side, and a queue across problems would have to
+// re-stage a workgroup's task parameters per group): B independent problems in one launch (jh_plan_step_batch), grid (groups of a problem, B).  A workgroup stages sTp once,
+// so it belongs to one problem, blockIdx.y; everything a problem owns -- its packed block (x0, nominal, sigma, task parameters, bounds: `batch_blk` floats apart), its noise
+// (`batch_noise` floats apart), its costs, trace rows and overflow rows (N rollouts apart) -- is reached by offsetting the kernel's pointers once, at the top, with
+// arithmetic on kernel arguments and blockIdx.y alone: the bases stay in SGPRs, and a rollout's code below is the single launch's.  The other instantiations ignore the
+// two strides and compile to the code they had without them.
+template <bool MATERIALIZE, int WPB, bool SELF, bool PERSIST = false, bool BATCH = false>
 #ifdef JH_V5_NUM_VGPR  // (occupancy experiments: a register budget independent of what the LDS footprint allows)
 #define JH_V5_REGATTR __attribute__((amdgpu_num_vgpr(JH_V5_NUM_VGPR)))
 #else
@@ -541,7 +547,16 @@ __global__ __launch_bounds__(WAVE * WPB, JH_V5_WAVES_PER_EU) JH_V5_REGATTR void 
                                                    const float* __restrict__ sigma, const float* __restrict__ W, const float* __restrict__ lohi,
                                                    const float* __restrict__ tp, int N, int n_offset, int H, int K, float* __restrict__ costs,
                                                    float* __restrict__ knots_out, const float* __restrict__ controls, float* __restrict__ states,
-                                                   float* __restrict__ sensors, int* __restrict__ stats, int dshift_, float* __restrict__ trace, float* __restrict__ ovf_all, unsigned* __restrict__ head) {
+                                                   float* __restrict__ sensors, int* __restrict__ stats, int dshift_, float* __restrict__ trace, float* __restrict__ ovf_all, unsigned* __restrict__ head,
+                                                   long long batch_blk, long long batch_noise) {
+  static_assert(!BATCH || (!MATERIALIZE && !PERSIST), "batched launches are fused launches on the static grid");
+  if constexpr (BATCH) {
+    const long long pb = blockIdx.y;
+    x0 += pb * batch_blk; nominal += pb * batch_blk; sigma += pb * batch_blk; lohi += pb * batch_blk; tp += pb * batch_blk;
+    noise += pb * batch_noise; costs += pb * N;
+    if (trace) trace += pb * N * H * 15;
+    if (NOVF > 0 && ovf_all) ovf_all += pb * N * (NOVF * POOL_F);  // (the overflow rows are indexed by rollout: a problem's N rows behind the one before)
+  }
 #ifdef JH_V5_X_DYNRS  // (occupancy experiments: the compiler does not see the per-rollout LDS, so the register budget follows JH_V5_WAVES_PER_EU alone)
   extern __shared__ __attribute__((aligned(16))) unsigned char dynRS[];
   RS* sRS = reinterpret_cast<RS*>(dynRS);
@@ -2072,7 +2087,7 @@ int JH_V5_NAME(jh_engine5_rollout_cost)(const jh_model* m, const float* x0, cons
   if (scratch && ovf_bytes > 0) ovf = scratch + (head ? 4 : 0);
 #define JH_V5_LAUNCH_COST(SELF_, PERSIST_)                                                                                                                                        \
   hipLaunchKernelGGL((k_leap_v5<false, JH_V5_WPB, SELF_, PERSIST_>), dim3(grid), dim3(WAVE * JH_V5_WPB), JH_V5_DYNBYTES, st, m->d_f, m->d_i, x0, 0, nominal, noise, ldn, sigma, W, \
-                     lohi, tp, N, n_offset, H, K, costs, knots_out, (const float*)nullptr, (float*)nullptr, (float*)nullptr, m->d_stats, dshift, trace, ovf, head)
+                     lohi, tp, N, n_offset, H, K, costs, knots_out, (const float*)nullptr, (float*)nullptr, (float*)nullptr, m->d_stats, dshift, trace, ovf, head, 0ll, 0ll)
   if (m->self_collision && m->h_i[17] > 0) { if (persist) JH_V5_LAUNCH_COST(true, true); else JH_V5_LAUNCH_COST(true, false); }
   else { if (persist) JH_V5_LAUNCH_COST(false, true); else JH_V5_LAUNCH_COST(false, false); }
 #undef JH_V5_LAUNCH_COST
@@ -2090,10 +2105,33 @@ int JH_V5_NAME(jh_engine5_materialize)(const jh_model* m, const float* x0, int x
   if (m->self_collision && m->h_i[17] > 0)
     hipLaunchKernelGGL((k_leap_v5<true, JH_V5_WPB, true>), dim3(grid), dim3(WAVE * JH_V5_WPB), JH_V5_DYNBYTES, st, m->d_f, m->d_i, x0, x0_batched, (const float*)nullptr, (const float*)nullptr, 0,
                        (const float*)nullptr, (const float*)nullptr, (const float*)nullptr, (const float*)nullptr, N, 0, H, 0, (float*)nullptr, (float*)nullptr,
-                       controls, states, sensors, m->d_stats, dshift, (float*)nullptr, ovf, (unsigned*)nullptr);
+                       controls, states, sensors, m->d_stats, dshift, (float*)nullptr, ovf, (unsigned*)nullptr, 0ll, 0ll);
   else
     hipLaunchKernelGGL((k_leap_v5<true, JH_V5_WPB, false>), dim3(grid), dim3(WAVE * JH_V5_WPB), JH_V5_DYNBYTES, st, m->d_f, m->d_i, x0, x0_batched, (const float*)nullptr, (const float*)nullptr, 0,
                        (const float*)nullptr, (const float*)nullptr, (const float*)nullptr, (const float*)nullptr, N, 0, H, 0, (float*)nullptr, (float*)nullptr,
-                       controls, states, sensors, m->d_stats, dshift, (float*)nullptr, ovf, (unsigned*)nullptr);
+                       controls, states, sensors, m->d_stats, dshift, (float*)nullptr, ovf, (unsigned*)nullptr, 0ll, 0ll);
+  return jh_launch_done(ovf, st);
+}
+
+// (Defined last in the file: the batched instantiations are emitted behind every other kernel and shift none of them in the code object.)
+// B problems in one launch (jh_plan_step_batch): the static grid with the problem in its second dimension.  x0 ... tp are problem 0's; `blk_stride` / `noise_stride` floats
+// lead to the next problem's.  The latency shift is chosen from B * N, the rollouts of the launch (the bits do not depend on it), and there is no queue.
+int JH_V5_NAME(jh_engine5_rollout_cost_batch)(const jh_model* m, int B, const float* x0, const float* nominal, const float* sigma, const float* lohi, const float* tp, long long blk_stride,
+                                  const float* noise, int ldn, long long noise_stride, const float* W, int N, int H, int K, float* costs, float* trace, hipStream_t st) {
+  if (!model_is_leap(m)) { jh_set_error("plan_step_batch: the cooperative engine kernel is instantiated for leap_cube only"); return JH_ERR_UNSUPPORTED; }
+  if ((m->cylinders > 0) != (JH_V5_CYL != 0)) { jh_set_error("plan_step_batch: an image with cylinder geoms runs on the cylinder build of the leap kernel and no other image does (%d cylinders)", m->cylinders); return JH_ERR_UNSUPPORTED; }
+#if JH_V5_KNOTS_LDS
+  JH_REQUIRE(K <= MAXK, "plan_step_batch: the cooperative leap kernel keeps at most 8 knots per actuator (K=%d)", K);
+#endif
+  JH_REQUIRE((long long)B * N <= 0x7fffffffll, "plan_step_batch: B * N = %lld rollouts exceed one launch", (long long)B * N);
+  const int dshift = jh_latency_shift(B * N, RPW); const int per_block = (RPW >> dshift) * JH_V5_WPB;
+  const int grid = (N + per_block - 1) / per_block;
+  const size_t ovf_bytes = NOVF > 0 ? (size_t)B * N * NOVF * POOL_F * sizeof(float) : 0;  // one row per rollout of every problem for the contacts above the LDS pool
+  float* ovf = ovf_bytes > 0 ? jh_launch_scratch(m, ovf_bytes, st) : nullptr;  // (nullptr: the LDS capacity alone, drops and the fallback counted)
+#define JH_V5_LAUNCH_BATCH(SELF_)                                                                                                                                                  \
+  hipLaunchKernelGGL((k_leap_v5<false, JH_V5_WPB, SELF_, false, true>), dim3(grid, B), dim3(WAVE * JH_V5_WPB), JH_V5_DYNBYTES, st, m->d_f, m->d_i, x0, 0, nominal, noise, ldn, sigma, W, \
+                     lohi, tp, N, 0, H, K, costs, (float*)nullptr, (const float*)nullptr, (float*)nullptr, (float*)nullptr, m->d_stats, dshift, trace, ovf, (unsigned*)nullptr, blk_stride, noise_stride)
+  if (m->self_collision && m->h_i[17] > 0) JH_V5_LAUNCH_BATCH(true); else JH_V5_LAUNCH_BATCH(false);
+#undef JH_V5_LAUNCH_BATCH
   return jh_launch_done(ovf, st);
 }

@@ -100,6 +100,11 @@ __global__ __launch_bounds__(kUB) void k_elite_merge(const float* __restrict__ r
 }
 
 __global__ __launch_bounds__(kUB) void k_update_tail(TailArgs a) { update_tail_body(a); }
+// the same tail for B problems (jh_plan_step_batch): blockIdx.y picks the problem, whose record is derived from problem 0's and the strides
+__global__ __launch_bounds__(kUB) void k_update_tail_batch(TailArgs base, BatchArgs s) {
+  const TailArgs a = batch_problem(base, s, (int)blockIdx.y);
+  batch_done(s, update_tail_body(a));
+}
 
 int check_dims(int N, int K, int nu) {
   JH_REQUIRE(N > 0 && K > 0 && nu > 0, "N, K, nu must be positive (N=%d K=%d nu=%d)", N, K, nu);
@@ -132,7 +137,7 @@ __host__ __device__ inline void philox4x32_10(uint32_t c0, uint32_t c1, uint32_t
   out[0] = c0; out[1] = c1; out[2] = c2; out[3] = c3;
 }
 
-__global__ __launch_bounds__(kUB) void k_noise_normal(uint32_t seed_lo, uint32_t seed_hi, uint32_t draw, int rows, int n_offset, int n_local, float* __restrict__ out, int ldn) {
+__device__ __forceinline__ void noise_normal_body(uint32_t seed_lo, uint32_t seed_hi, uint32_t draw, int rows, int n_offset, int n_local, float* __restrict__ out, int ldn) {
   const int blocks_per_row = (n_offset + n_local + 3) / 4 - n_offset / 4;  // Philox blocks that touch this shard's columns
   const size_t t = (size_t)blockIdx.x * kUB + threadIdx.x;
   if (t >= (size_t)rows * blocks_per_row) return;
@@ -153,7 +158,34 @@ __global__ __launch_bounds__(kUB) void k_noise_normal(uint32_t seed_lo, uint32_t
   else
     for (int k = 0; k < 4; k++) if (n0 + k >= 0 && n0 + k < n_local) o[k] = z[k];
 }
+__global__ __launch_bounds__(kUB) void k_noise_normal(uint32_t seed_lo, uint32_t seed_hi, uint32_t draw, int rows, int n_offset, int n_local, float* __restrict__ out, int ldn) {
+  noise_normal_body(seed_lo, seed_hi, draw, rows, n_offset, n_local, out, ldn);
+}
+// B draws in one launch (jh_noise_normal_batch): blockIdx.y picks the (seed, draw) pair -- they travel in the kernel arguments, kNoiseBatch of them per launch -- and the
+// (rows, ldn) slice it fills; the same body, so the same bits as B launches of k_noise_normal
+constexpr int kNoiseBatch = 256;
+struct NoiseBatch { uint32_t seed_lo[kNoiseBatch], seed_hi[kNoiseBatch], draw[kNoiseBatch]; };
+__global__ __launch_bounds__(kUB) void k_noise_normal_batch(NoiseBatch nb, int rows, int n_local, float* __restrict__ out, int ldn) {
+  const int b = blockIdx.y;
+  noise_normal_body(nb.seed_lo[b], nb.seed_hi[b], nb.draw[b], rows, 0, n_local, out + (size_t)b * rows * ldn, ldn);
+}
 }  // namespace
+
+extern "C" int jh_noise_normal_batch(int B, const unsigned long long* seeds, const unsigned int* draws, int rows, int n_local, float* out, int ldn, void* stream) {
+  JH_REQUIRE(out != nullptr && seeds != nullptr && draws != nullptr, "noise_normal_batch: null pointer");
+  JH_REQUIRE(B >= 1, "noise_normal_batch: B must be at least 1 (B=%d)", B);
+  JH_REQUIRE(rows > 0 && n_local > 0 && ldn >= n_local, "noise_normal_batch: rows, n_local must be positive, ldn >= n_local (rows=%d n_local=%d ldn=%d)", rows, n_local, ldn);
+  const size_t total = (size_t)rows * (size_t)((n_local + 3) / 4);
+  for (int b0 = 0; b0 < B; b0 += kNoiseBatch) {  // (one launch up to kNoiseBatch problems: the pairs are kernel arguments, no device copy of the host arrays)
+    const int nb = B - b0 < kNoiseBatch ? B - b0 : kNoiseBatch;
+    NoiseBatch a;
+    for (int i = 0; i < nb; i++) { a.seed_lo[i] = (uint32_t)seeds[b0 + i]; a.seed_hi[i] = (uint32_t)(seeds[b0 + i] >> 32); a.draw[i] = (uint32_t)draws[b0 + i]; }
+    for (int i = nb; i < kNoiseBatch; i++) { a.seed_lo[i] = 0u; a.seed_hi[i] = 0u; a.draw[i] = 0u; }
+    hipLaunchKernelGGL(k_noise_normal_batch, dim3((unsigned)((total + kUB - 1) / kUB), (unsigned)nb), dim3(kUB), 0, (hipStream_t)stream, a, rows, n_local, out + (size_t)b0 * rows * ldn, ldn);
+  }
+  JH_HIP(hipGetLastError());
+  return JH_OK;
+}
 
 extern "C" int jh_noise_normal(unsigned long long seed, unsigned int draw, int rows, int n_offset, int n_local, float* out, int ldn, void* stream) {
   JH_REQUIRE(out != nullptr, "noise_normal: null pointer");
@@ -292,6 +324,14 @@ int jh_update_tail_args(const char* who, const float* costs, const float* knots_
   if (rec_out) {  // the shard form: this rank's record [update record | E trace records]
     a.nominal_out = nullptr; a.sigma_out = nullptr; a.rec_out = rec_out; a.trace_out = rec_out + (mode == 0 ? 2 + K * nu : k * (2 + K * nu));
   } else { a.nominal_out = nominal_out; a.sigma_out = sigma_out; a.trace_out = trace_out; a.rec_out = nullptr; }
+  return JH_OK;
+}
+
+extern "C" size_t jh_plan_batch_scratch_floats(int B, int N, int K, int nu) { return (size_t)(B > 0 ? B : 0) * jh_update_fused_scratch_floats(N, K, nu); }
+
+int jh_update_tail_batch_launch(const TailArgs& a, const BatchArgs& s, hipStream_t st) {
+  hipLaunchKernelGGL(k_update_tail_batch, dim3((a.N + kUB - 1) / kUB, s.B), dim3(kUB), 0, st, a, s);
+  JH_HIP(hipGetLastError());
   return JH_OK;
 }
 

@@ -250,7 +250,8 @@ __device__ long long g_tail_ticks[16];
 #else
 #define TAIL_TICK(i)
 #endif
-__device__ __forceinline__ void update_tail_body(const TailArgs& a) {
+// (returns true in every thread of the workgroup that drew the last ticket and wrote the outputs: the batched kernels count those, batch_done below)
+__device__ __forceinline__ bool update_tail_body(const TailArgs& a) {
   __shared__ float sred[4];
   __shared__ float sS;
   __shared__ float sV[4][JH_MAX_KNOT_DIM];
@@ -280,7 +281,7 @@ __device__ __forceinline__ void update_tail_body(const TailArgs& a) {
   __syncthreads();
   if (tid == 0) s_last = (atomicAdd(counter, 1u) == (unsigned)(nb - 1));
   __syncthreads();
-  if (!s_last) return;
+  if (!s_last) return false;
 #ifdef JH_TAIL_TICKS
   if (tid == 0) { g_tail_ticks[0] = t_in; g_tail_ticks[1] = t_b1; g_tail_ticks[2] = t_b2; }
 #endif
@@ -318,6 +319,41 @@ __device__ __forceinline__ void update_tail_body(const TailArgs& a) {
     if (tid == 0) __hip_atomic_store(a.done_flag, a.done_value, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_SYSTEM);
   }
   TAIL_TICK(7);
+  return true;
+}
+
+// ---------------------------------------------------------------- B independent plan steps in one launch (jh_plan_step_batch)
+// The launch has a second grid dimension: blockIdx.y is the problem, and a problem's workgroups run rollout_cost_body / update_tail_body unchanged on pointers offset by
+// the problem's strides (a workgroup belongs to one problem; the tail takes its workgroup count from gridDim.x).  Each problem keeps its own ticket in its own scratch
+// block.  The completion word is a second level: the last workgroup of a problem bumps the batch counter behind a fence of its outputs, and the one that draws B - 1
+// resets the counter and stores the word behind a system-scope fence -- once, behind the last of the B problems.  B = 1 takes the same code.
+struct BatchArgs {
+  int B;
+  long long blk, noise, costs, trace, scratch, out;  // floats from one problem's packed block / noise / costs / trace buffer / update scratch / output block to the next one's
+  unsigned* counter;                                 // the batch ticket: word 1 of problem 0's scratch (zero before the first launch, left at zero)
+  unsigned* done_flag; unsigned done_value;          // as TailArgs', for the whole batch (the per-problem records carry none)
+};
+// problem b's record from problem 0's: wave-uniform arithmetic on kernel arguments and blockIdx.y
+__device__ __forceinline__ TailArgs batch_problem(const TailArgs& base, const BatchArgs& s, int b) {
+  TailArgs a = base;
+  a.costs += b * s.costs; a.src.nominal += b * s.blk; a.src.sigma += b * s.blk; a.src.lohi += b * s.blk; a.src.noise += b * s.noise;
+  if (a.trace) a.trace += b * s.trace;
+  a.scratch += b * s.scratch; a.nominal_out += b * s.out;
+  if (a.sigma_out) a.sigma_out += b * s.out;
+  if (a.trace_out) a.trace_out += b * s.out;
+  a.done_flag = nullptr; a.done_value = 0u;
+  return a;
+}
+// `last`: update_tail_body's result (uniform over the workgroup)
+__device__ __forceinline__ void batch_done(const BatchArgs& s, bool last) {
+  if (!last) return;
+  __threadfence_system();  // every thread's stores to this problem's output block (device memory or the host's pinned block) in front of the ticket
+  __syncthreads();
+  if (threadIdx.x != 0) return;
+  if (atomicAdd(s.counter, 1u) != (unsigned)(s.B - 1)) return;
+  *s.counter = 0u;  // (the next launch on this stream finds it reset)
+  __threadfence_system();  // the other problems' outputs, published by their tickets, in front of the word
+  if (s.done_flag) __hip_atomic_store(s.done_flag, s.done_value, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_SYSTEM);
 }
 
 }  // namespace jh_upd
@@ -330,3 +366,7 @@ int jh_update_tail_args(const char* who, const float* costs, const float* knots_
 int jh_update_tail_launch(const jh_upd::TailArgs& a, hipStream_t st);  // k_update_tail on its own (the articulated models' plan step)
 bool jh_simple_plan_step_fits(const jh_model* m, int H, int K);
 int jh_simple_plan_step(const jh_model* m, const float* x0, const float* W, const float* tp, int H, int K, const jh_upd::TailArgs& a, hipStream_t st);
+// the batched forms (jh_plan_step_batch): `a` is problem 0's record, `s` the strides; grid (workgroups of a problem, B)
+int jh_update_tail_batch_launch(const jh_upd::TailArgs& a, const jh_upd::BatchArgs& s, hipStream_t st);
+int jh_simple_plan_step_batch(const jh_model* m, const float* x0, const float* W, const float* tp, int H, int K, const jh_upd::TailArgs& a, const jh_upd::BatchArgs& s, hipStream_t st);
+int jh_simple_rollout_cost_batch(const jh_model* m, const float* x0, const float* tp, const float* W, int H, int K, const jh_upd::TailArgs& a, const jh_upd::BatchArgs& s, hipStream_t st);

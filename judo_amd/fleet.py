@@ -1,0 +1,258 @@
+"""B controllers of one model planned in ONE launch (`jh_plan_step_batch`, include/judo_amd.h).
+
+The reference runs one `Controller.update_action` (judo/controller/controller.py:210-299) per process; somebody with several robots, several goals or a
+domain-randomised sweep runs B of them back to back and pays B launch chains and B host round trips for work that fits the GPU at once.  A `ControllerFleet`
+holds B ordinary `Controller` objects that share one `GpuModel`.  `fleet.update_action()` runs every member's host prelude (time shift, normaliser,
+`pre_optimization`, the packed block x0 | nominal | sigma | task params | bounds, the noise) into the member's slice of the fleet's buffers, then ONE
+`jh_plan_step_batch` and one `jh_download_end`, then every member's epilogue (denormalise, CEM sigma refit, `update_spline`, the staged trace records).
+Afterwards each member is bit for bit where its own `update_action()` would have left it: the kernels run the single plan step's code on offset pointers.
+
+What the members must share is what the launch shares: the model, N, K, H, the spline order, the trace count, the optimizer kind and its scalar arguments.
+Everything else -- state, time, goal and the other task parameters, seed or injected noise, CEM sigma -- is a member's own.
+"""
+
+from __future__ import annotations
+
+import ctypes as C
+from typing import Any, Sequence
+
+import numpy as np
+import torch
+
+from judo_amd import _lib
+from judo_amd.controller import Controller, make_controller_for
+from judo_amd.device import current_stream_ptr
+from judo_amd.distributed import world_info
+from judo_amd.optimizers import Optimizer, _NoiseStream
+from judo_amd.tasks import get_registered_tasks
+
+
+class _MemberBuffers:
+    """A member's slice of the fleet's buffers under the names `Controller`'s helpers use on a `_PlanBuffers`."""
+
+    def __init__(self, fleet: "_FleetBuffers", i: int) -> None:
+        f = fleet
+        self.sizes, self.offsets = f.sizes, f.offsets
+        nblk = f.nblk
+        self.host_np = f.host_np[i * f.blk_stride : i * f.blk_stride + nblk]
+        self.host_ptr, self.nblk_bytes = f.host_ptr + 4 * i * f.blk_stride, 4 * nblk
+        self.blk = f.blk[i * f.blk_stride : i * f.blk_stride + nblk]
+        self.x0, self.nominal, self.sigma, self.tp, self.lohi = torch.split(self.blk, self.sizes)
+        self.blk_stale = True
+        self.costs = f.costs[0][i]
+        self.dev = f.dev
+        # the trace stage of a member whose kernel writes no trace rows (the elites' knots, re-rolled when the traces are read): its own small buffers, made when first needed
+        self._fleet, self._i = f, i
+        self.trace_rows, self.trace_flip = None, 0
+        self._scratch, self._trace_recs = None, None
+
+    @property
+    def out_np(self) -> np.ndarray:  # (the fleet's output block may be re-sized between plan steps)
+        f = self._fleet
+        return f.out_np[self._i * f.out_stride : (self._i + 1) * f.out_stride]
+
+    @property
+    def scratch(self) -> torch.Tensor:
+        if self._scratch is None:
+            f = self._fleet
+            self._scratch = torch.empty(int(_lib.lib().jh_update_scratch_floats(f.N, f.K, f.nu)), dtype=torch.float32, device=self.dev)
+        return self._scratch
+
+    @property
+    def trace_recs(self) -> list[torch.Tensor]:
+        if self._trace_recs is None:
+            f = self._fleet
+            self._trace_recs = [torch.full((max(f.E, 1) * (2 + f.K * f.nu),), float("inf"), dtype=torch.float32, device=self.dev) for _ in range(2)]
+        return self._trace_recs
+
+
+class _FleetBuffers:
+    """Everything a fleet's plan step touches, for B problems of one size: B packed blocks in one pinned host buffer (and its device copy), the noise, costs,
+    trace rows, update scratch, and the pinned output block with its completion word."""
+
+    def __init__(self, dev: torch.device, B: int, N: int, K: int, nu: int, nx: int, ntp: int, E: int) -> None:
+        L = _lib.lib()
+        self.dev, self.B, self.N, self.K, self.nu, self.E = dev, B, N, K, nu, E
+        self.sizes = [nx, K * nu, K * nu, ntp, 2 * nu]
+        self.nblk = sum(self.sizes)
+        self.offsets = [int(v) for v in np.cumsum([0] + self.sizes)]
+        self.blk_stride = self.nblk  # floats from a member's block to the next one's
+        self.host = torch.zeros(B * self.blk_stride, dtype=torch.float32).pin_memory()
+        self.host_np, self.host_ptr = self.host.numpy(), self.host.data_ptr()
+        self.blk = torch.zeros(B * self.blk_stride, dtype=torch.float32, device=dev)
+        self.noise = [torch.empty((B, K, nu, N), dtype=torch.float32, device=dev) for _ in range(2)]  # alternated: the other one backs the members' lazy `candidate_knots`
+        self.noise_cur = 0
+        self.costs = [torch.empty((B, N), dtype=torch.float32, device=dev) for _ in range(2)]  # alternated likewise (`rewards` is read lazily)
+        self.scratch = torch.zeros(int(L.jh_plan_batch_scratch_floats(B, N, K, nu)), dtype=torch.float32, device=dev)  # (zero: the tickets)
+        self.done = torch.zeros(4, dtype=torch.int32).pin_memory()
+        self.trace_buf: torch.Tensor | None = None
+        self.out_stride = 0
+        self.size_out(2 * K * nu)
+        self.members = [_MemberBuffers(self, i) for i in range(B)]
+
+    def size_out(self, stride: int) -> None:
+        if self.out_stride >= stride:
+            return
+        self.out_stride = stride
+        self.out_host = torch.zeros(self.B * stride, dtype=torch.float32).pin_memory()  # (zeros: MPPI / PS never write the sigma region)
+        self.out_np, self.out_host_ptr = self.out_host.numpy(), self.out_host.data_ptr()
+
+
+class ControllerFleet:
+    """B controllers of one task and optimizer kind whose plan steps run as one launch.  `fleet[i]` is an ordinary `Controller`: `update_states`,
+    `system_metadata`, `optimizer.seed`, `optimizer.injected_noise`, `action(t)`, `traces`, `rewards` work per member as they do on a controller alone."""
+
+    def __init__(self, controllers: Sequence[Controller]) -> None:
+        self.controllers = list(controllers)
+        if not self.controllers:
+            raise ValueError("a fleet needs at least one controller")
+        first = self.controllers[0]
+        self.device = first.device
+        for i, c in enumerate(self.controllers):
+            self._check_member(i, c, first)
+        self.model = first.model
+        for c in self.controllers[1:]:  # one image of the model constants on the device for the whole fleet
+            if c.model is not self.model:
+                c.model = c.task._gpu = c.rollout_backend.model = self.model
+        self._bufs: _FleetBuffers | None = None
+        self._bufs_key: tuple | None = None
+
+    def __len__(self) -> int:
+        return len(self.controllers)
+
+    def __getitem__(self, i: int) -> Controller:
+        return self.controllers[i]
+
+    def __iter__(self):
+        return iter(self.controllers)
+
+    # ---- what a member must share with the fleet ---------------------------------------------------------------------------------------------------
+    @staticmethod
+    def _shared(c: Controller) -> dict[str, Any]:
+        opt = c.optimizer
+        return {"task class": type(c.task), "optimizer class": type(opt), "num_rollouts": opt.num_rollouts, "num_nodes": opt.num_nodes, "horizon": c.horizon,
+                "spline_order": c.spline_order, "max_num_traces": c.max_num_traces, "max_opt_iters": c.max_opt_iters,
+                "fused_update_args": opt.fused_update_args() if hasattr(opt, "fused_update_args") else None}
+
+    def _check_member(self, i: int, c: Controller, first: Controller) -> None:
+        if c.task.uses_locomotion_policy or c.model is None:
+            raise ValueError(f"fleet member {i}: the Spot policy tasks have no batched plan step")
+        if c.model.desc.get("family", c.model.task) == "fr3_pick":
+            raise ValueError(f"fleet member {i}: fr3_pick has no batched plan step (its phase is chosen per problem on the host)")
+        if c.device != first.device:
+            raise ValueError(f"fleet member {i} is on {c.device}, the fleet on {first.device}")
+        mine, want = self._shared(c), self._shared(first)
+        for key in want:
+            if mine[key] != want[key]:
+                raise ValueError(f"fleet member {i} differs from member 0 in {key}: {mine[key]!r} against {want[key]!r}")
+        if c.model is not first.model and (c.model._blob != first.model._blob or c.model.build() != first.model.build() or c.model.self_collision != first.model.self_collision):
+            raise ValueError(f"fleet member {i} has another model image or kernel build than member 0")
+        world, _ = world_info(c.group)
+        shape = c._iteration_shape(world, c._current_normalizer())
+        if shape != "plan_step" or c.keep_candidates or c.record_kernel_events:
+            why = ("a process group" if world > 1 or c.force_shard_path else "keep_candidates" if c.keep_candidates else "record_kernel_events" if c.record_kernel_events
+                   else "a running normaliser" if c._current_normalizer().needs_moments else "a plugin reward, hook or optimizer, or a knot count above the fused kernel's limit")
+            raise ValueError(f"fleet member {i} does not run its iteration as one jh_plan_step call ({why}): only such controllers can share a launch")
+
+    # ---- the plan step --------------------------------------------------------------------------------------------------------------------------------
+    def _buffers(self, key: tuple) -> _FleetBuffers:
+        if self._bufs_key != key:
+            self._bufs, self._bufs_key = _FleetBuffers(self.device, *key), key
+        return self._bufs
+
+    def _draw_noise(self, fb: _FleetBuffers, N: int, K: int, nu: int) -> torch.Tensor:
+        """The members' noise into the next (B, K, nu, N) buffer: one `jh_noise_normal_batch` when every member draws from the device generator (each member's draw
+        counter advances by one, as its own `draw_noise` would leave it), else member by member through `draw_noise`."""
+        fb.noise_cur ^= 1
+        noise = fb.noise[fb.noise_cur]
+        opts = [c.optimizer for c in self.controllers]
+        if all(o.injected_noise is None and type(o).draw_noise is Optimizer.draw_noise for o in opts):
+            B = len(opts)
+            for o in opts:
+                if o._generator is None:
+                    o._generator = _NoiseStream(o._seed)
+            seeds = (C.c_ulonglong * B)(*[o._generator.seed for o in opts])
+            draws = (C.c_uint * B)(*[o._generator.draws & 0xFFFFFFFF for o in opts])
+            _lib.check(_lib.lib().jh_noise_normal_batch(B, seeds, draws, K * nu, N, noise.data_ptr(), N, current_stream_ptr()), "jh_noise_normal_batch")
+            for i, o in enumerate(opts):
+                o._generator.draws += 1
+                o.last_noise = noise[i]
+        else:
+            for i, o in enumerate(opts):
+                got = o.draw_noise(N, 0, self.device, out=noise[i])
+                if got.data_ptr() != noise[i].data_ptr():  # (injected noise, or a plugin's own draw: a tensor of its own)
+                    noise[i].copy_(got)
+                    o.last_noise = noise[i]
+        return noise
+
+    def update_action(self) -> None:
+        lib = _lib.lib()
+        cs = self.controllers
+        first = cs[0]
+        for i, c in enumerate(cs):  # (live edits of a config between plan steps must not silently split the fleet)
+            self._check_member(i, c, first)
+        plans = [c._begin_plan() for c in cs]
+        # (a plan: N, K, nu, H, world, shard, normaliser, normalised nominal, W, x0, new knot times, fused optimizer?, trace elites, task params -- Controller._begin_plan)
+        N, K, nu, H, _, _, _, _, W, _, _, _, E, tp0 = plans[0]
+        for i, p in enumerate(plans):
+            if (p[0], p[1], p[2], p[3], p[12], len(p[13])) != (N, K, nu, H, E, len(tp0)):
+                raise ValueError(f"fleet member {i} plans another problem size than member 0")
+        B = len(cs)
+        fb = self._buffers((B, N, K, nu, first.task.nq + first.task.nv, len(tp0), E))
+        stream = current_stream_ptr()
+        shards, nrms = [p[5] for p in plans], [p[6] for p in plans]
+        states: list[dict[str, Any]] = [dict(E=E, x0=p[9], new_times=p[10]) for p in plans]
+        nominal_n = [p[7] for p in plans]
+        mode, lam, k_el, tie = first.optimizer.fused_update_args()
+        nfl = first._fused_trace_floats()
+        colmajor = int(first._trace_colmajor) if nfl else 0
+        iters, staged = 0, False
+        while iters < first.max_opt_iters and not any(c.optimizer.stop_cond() for c in cs):
+            last = iters == first.max_opt_iters - 1
+            affine = []
+            for c, mb, nrm, n_n in zip(cs, fb.members, nrms, nominal_n):
+                c._stream = stream
+                c.task.pre_rollout(c.current_state)
+                affine.append(c._iteration_inputs(mb, nrm, n_n, nu, upload=False))
+            noise = self._draw_noise(fb, N, K, nu)
+            costs = fb.costs[fb.noise_cur]
+            row = H * nfl
+            if nfl and (fb.trace_buf is None or fb.trace_buf.numel() != B * N * row):
+                fb.trace_buf = torch.empty(B * N * row, dtype=torch.float32, device=self.device)
+            E_t = min(E, _lib.MAX_ELITES) if (last and nfl) else 0
+            fb.size_out(2 * K * nu + E_t * (2 + row))
+            in_place = self.model.closed_form  # (the closed-form kernels read the host blocks in place and the host polls the completion word; the leap family uploads and keeps the stream's event)
+            off = fb.offsets
+            st = lib.jh_plan_step_batch(self.model.handle, B, fb.host_ptr if in_place else fb.blk.data_ptr(), fb.host_ptr, 4 * fb.nblk, 4 * fb.blk_stride, off[1], off[2], off[3], off[4],
+                                        noise.data_ptr(), N, K * nu * N, _lib.ptr(W), N, H, K, costs.data_ptr(), fb.trace_buf.data_ptr() if nfl else None, mode, lam, k_el, tie, E_t,
+                                        row, colmajor, fb.scratch.data_ptr(), fb.out_host_ptr, fb.out_stride, fb.done.data_ptr() if in_place else fb.out_host_ptr, None, stream)
+            _lib.check(st, "jh_plan_step_batch")
+            _lib.check(lib.jh_download_end(), "jh_download_end")
+            for i, (c, mb, shard, st_i) in enumerate(zip(cs, fb.members, shards, states)):
+                mb.blk_stale = in_place
+                mb.costs = costs[i]
+                trace_i = (fb.trace_buf[i * N * row : (i + 1) * N * row], row) if nfl else None
+                st_i.update(costs=mb.costs, knots_out=None, noise_p=noise[i].data_ptr(), ldn=N, knots_nku=None, trace_buf=trace_i, stage=(True if last else None))
+                nominal_n[i] = c._iteration_result(mb, st_i, noise[i], noise[i].data_ptr(), N, shard, H, K, nu, E_t, *affine[i])
+                if last and not E_t:  # (no trace rows from the kernel: the elites' knots, re-rolled when the traces are read)
+                    c._stage_traces(lib, mb, st_i, shard, 1, E, st_i["x0"], st_i["new_times"], K, nu, stream)
+            staged = last
+            iters += 1
+        for c, mb, p, st_i, n_n in zip(cs, fb.members, plans, states, nominal_n):
+            c._end_plan(p, mb, st_i, n_n, iters, staged, stream)
+
+
+def make_controller_fleet(task: str, optimizer: str, B: int, device: torch.device | None = None) -> ControllerFleet:
+    """B controllers of the registered task and optimizer (`make_controller`, judo/controller/controller.py:404-442, B times) around ONE `GpuModel`."""
+    tasks = get_registered_tasks()
+    if task not in tasks:
+        raise ValueError(f"Task {task} not found in task registry.")
+    if B < 1:
+        raise ValueError("a fleet needs at least one controller")
+    members: list[Controller] = []
+    for _ in range(B):
+        t = tasks[task][0]()
+        if members:
+            t._gpu = members[0].model  # (Task.gpu_model hands it out instead of packing and uploading the image again)
+        members.append(make_controller_for(t, optimizer, device=device))
+    return ControllerFleet(members)
