@@ -258,8 +258,9 @@ int jh_plan_step(const jh_model* m, void* blk_dev, const void* blk_host, size_t 
  * the single call's code on offset pointers (cartpole, cylinder_push: one launch with blockIdx.y = problem, or two above jh_model_one_launch_max_knots; the leap family:
  * the rollout kernel on the static grid (groups, B) -- the latency mode chosen from B * N rollouts, no persistent queue -- then the batched update tail).  B = 1 takes the same
  * code.  JH_ERR_INVALID: B < 1, B > 65535 (the grid's second dimension), a stride smaller than a block / a noise slice / an output record, a forced one-launch plan step that
- * does not fit.  JH_ERR_UNSUPPORTED: fr3_pick (its phase is a per-problem host decision, judo/tasks/fr3_pick.py:191-223) and the cross-check kernel generations; Spot, the
- * sharded path, the materialise and plugin-reward paths have no batched form. */
+ * does not fit.  JH_ERR_UNSUPPORTED: fr3_pick (its phase is a per-problem host decision, judo/tasks/fr3_pick.py:191-223) and the cross-check kernel generations.  The Spot
+ * policy tasks, whose iteration is the materialise path, batch through jh_spline_controls_batch / jh_policy_rollout_batch / jh_update_fused_batch below; the sharded and the
+ * plugin-reward paths have no batched form. */
 size_t jh_plan_batch_scratch_floats(int B, int N, int K, int nu);
 int jh_plan_step_batch(const jh_model* m, int B, void* blk_dev, const void* blk_host, size_t blk_bytes, size_t blk_stride_bytes, int o_nominal, int o_sigma, int o_tp, int o_lohi,
                        const float* noise, int ldn, size_t noise_stride_floats, const float* W, int N, int H, int K, float* costs, float* trace, int mode, float lambda, int k,
@@ -269,6 +270,25 @@ int jh_plan_step_batch(const jh_model* m, int B, void* blk_dev, const void* blk_
  * (B x rows x ldn floats) is bit for bit what jh_noise_normal(seeds[b], draws[b], rows, 0, n_local, out + b * rows * ldn, ldn) writes; columns n_local .. ldn - 1 are left
  * alone.  seeds / draws: HOST arrays of B entries, read before the call returns (one launch per 256 problems: the pairs travel as kernel arguments). */
 int jh_noise_normal_batch(int B, const unsigned long long* seeds /* HOST */, const unsigned int* draws /* HOST */, int rows, int n_local, float* out, int ldn, void* stream);
+/* The materialise path of those B problems where the rollout is not a jh_model's (the Spot policy tasks: judo/controller/controller.py:239-299 with
+ * judo/utils/policy_mj_rollout_backend.py:60-125 as the rollout), one launch per stage instead of B:
+ * jh_spline_controls_batch = jh_spline_controls for B problems (judo/controller/controller.py:239-249, the candidate splines at the rollout times, once per controller): the knots
+ * are recomputed as clip(nominal + sigma * noise) from problem b's nominal | sigma | ctrl bounds at the float offsets o_* of its sub-block of `blk` (B sub-blocks
+ * blk_stride_floats apart) and its (K * nu, ldn) noise (noise_stride_floats apart); every problem's rollout 0 is its nominal.  controls is (B * N, H, nu), problem-major;
+ * problem b's N rows are bit for bit those of jh_spline_controls on its sub-block (the same LDS-staged or global-memory form, chosen from H, K, nu as there).
+ * JH_ERR_INVALID: B < 1, B > 65535, a stride smaller than a block (the end of the furthest of the three parts) or than a noise slice (K * nu * ldn). */
+int jh_spline_controls_batch(const float* W, int B, const float* blk, size_t blk_stride_floats, int o_nominal, int o_sigma, int o_lohi, const float* noise, int ldn,
+                             size_t noise_stride_floats, int N, int H, int K, int nu, float* controls, void* stream);
+/* jh_update_fused for B problems whose costs are given (Optimizer.update_nominal_knots and update_traces, judo/controller/controller.py:283-299, once per controller): costs is
+ * B x N; nominal | sigma | ctrl bounds and the noise as for jh_spline_controls_batch; trace B x (N x row_floats) or NULL (then E is ignored: the Spot tasks take their traces
+ * from the materialised sensors); scratch jh_plan_batch_scratch_floats(B, N, K, nu) floats, ZERO before the first use (the B + 1 tickets, which every launch leaves at zero);
+ * out B records [nominal K*nu | sigma K*nu | E x (2 + row_floats) trace records], out_stride_floats apart, in device memory or device-visible pinned host memory, behind ONE
+ * completion mark that jh_download_end waits for: out_host_mark == out is the stream's event, anything else a 4-byte word in device-visible pinned host memory that receives
+ * its old value + 1 behind the last problem's results (both as for jh_plan_step_batch, whose update stage this is).  Problem b's record is bit for bit what jh_update_fused
+ * writes for its costs, sub-block and noise.  JH_ERR_INVALID: B < 1, B > 65535, a stride smaller than a block / a noise slice / an output record. */
+int jh_update_fused_batch(int B, const float* costs, const float* blk, size_t blk_stride_floats, int o_nominal, int o_sigma, int o_lohi, const float* noise, int ldn,
+                          size_t noise_stride_floats, int N, int K, int nu, int mode, float lambda, int k, int tie_high, int E, const float* trace, int row_floats, int colmajor,
+                          float* scratch, float* out, size_t out_stride_floats, void* out_host_mark, void* stream);
 /* The same iteration with the rollouts sharded over G ranks (the reference has no multi-process form: judo/controller/controller.py:246-299 runs in one
  * process): launch -> all-gather -> merge.  jh_update_shard is jh_update_fused with the last stage left to the ranks' merge: it writes this rank's record
  *   [ MPPI: beta, S, V(K*nu)  |  elites: k x (cost, global index (bits), knots(K*nu)) ]  followed by  E x (cost, global index (bits), trace row(row_floats))
@@ -343,6 +363,16 @@ int jh_tree_substeps(const jh_tree* t, const float* state_in, const float* ctrl,
 size_t jh_policy_rollout_scratch_floats(int N);
 int jh_policy_rollout(const jh_policy* p, jh_tree* t, const float* x0, int x0_batched, const float* commands, float* policy_out, float* warmstart, int reset_warmstart,
                       int N, int T, int substeps, double cutoff_seconds, float* states, float* sensors, float* scratch, int* steps_done, void* stream);
+/* threaded_rollout for B problems of n rollouts each in one launch chain (the reference runs one threaded_rollout per controller process,
+ * mujoco_extensions/system/system_class.cpp:277-367 under judo/utils/policy_mj_rollout_backend.py:60-125): N = B * n rollouts, problem-major; rollout r starts from problem r / n's
+ * state, the B states lying x0_stride_floats apart in DEVICE memory (the x0 parts of a fleet's packed blocks).  commands, policy_out, warmstart, states, sensors, scratch
+ * (jh_policy_rollout_scratch_floats(B * n)), reset_warmstart, cutoff_seconds and *steps_done as for jh_policy_rollout with N = B * n; the deadline is one per call.  The
+ * start states are copied out to one row per rollout in row T - 1 of `states`, which the last control step overwrites (T = 1: that step reads and writes row 0 in place, as
+ * jh_tree_substeps allows).  States, sensors, policy outputs and warm start of
+ * problem b are bit for bit those of jh_policy_rollout with N = n from its state: a rollout's result depends neither on its wave-mates nor on the latency mode nor on the
+ * policy launch shape its batch size selects.  JH_ERR_INVALID: B < 1, n < 1, x0_stride_floats smaller than a state. */
+int jh_policy_rollout_batch(const jh_policy* p, jh_tree* t, int B, const float* x0, size_t x0_stride_floats, const float* commands, float* policy_out, float* warmstart,
+                            int reset_warmstart, int n, int T, int substeps, double cutoff_seconds, float* states, float* sensors, float* scratch, int* steps_done, void* stream);
 
 #ifdef __cplusplus
 }

@@ -47,6 +47,7 @@ _SIGNATURES = {
     "jh_noise_normal": (C.c_int, [C.c_ulonglong, C.c_uint, C.c_int, C.c_int, C.c_int, f32p, C.c_int, C.c_void_p]),
     "jh_sample_knots": (C.c_int, [f32p, f32p, C.c_int, f32p, f32p, C.c_int, C.c_int, C.c_int, C.c_int, f32p, C.c_void_p]),
     "jh_spline_controls": (C.c_int, [f32p, f32p, f32p, f32p, C.c_int, f32p, f32p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, f32p, C.c_void_p]),
+    "jh_spline_controls_batch": (C.c_int, [f32p, C.c_int, f32p, C.c_size_t, C.c_int, C.c_int, C.c_int, f32p, C.c_int, C.c_size_t, C.c_int, C.c_int, C.c_int, C.c_int, f32p, C.c_void_p]),
     "jh_knot_moments": (C.c_int, [f32p, f32p, f32p, C.c_int, f32p, f32p, f32p, C.c_int, C.c_int, C.c_int, C.c_int, f32p, C.c_void_p]),
     "jh_policy_create": (C.c_int, [C.POINTER(C.c_void_p), C.POINTER(C.c_void_p), C.POINTER(C.c_void_p)]),
     "jh_policy_destroy": (None, [C.c_void_p]),
@@ -60,6 +61,8 @@ _SIGNATURES = {
     "jh_tree_substeps": (C.c_int, [C.c_void_p, f32p, f32p, f32p, C.c_int, C.c_int, f32p, f32p, C.c_void_p]),
     "jh_policy_rollout_scratch_floats": (C.c_size_t, [C.c_int]),
     "jh_policy_rollout": (C.c_int, [C.c_void_p, C.c_void_p, f32p, C.c_int, f32p, f32p, f32p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_double, f32p, f32p, f32p, C.POINTER(C.c_int), C.c_void_p]),
+    "jh_policy_rollout_batch": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, f32p, C.c_size_t, f32p, f32p, f32p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_double, f32p, f32p, f32p, C.POINTER(C.c_int),
+                                          C.c_void_p]),
     "jh_update_scratch_floats": (C.c_size_t, [C.c_int, C.c_int, C.c_int]),
     "jh_mppi_partial": (C.c_int, [f32p, f32p, f32p, f32p, C.c_int, f32p, f32p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_float, f32p, f32p, C.c_void_p]),
     "jh_mppi_merge": (C.c_int, [f32p, C.c_int, C.c_int, C.c_int, C.c_float, f32p, C.c_void_p]),
@@ -72,6 +75,8 @@ _SIGNATURES = {
     "jh_plan_batch_scratch_floats": (C.c_size_t, [C.c_int, C.c_int, C.c_int, C.c_int]),
     "jh_plan_step_batch": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_size_t, C.c_size_t, C.c_int, C.c_int, C.c_int, C.c_int, f32p, C.c_int, C.c_size_t, f32p, C.c_int, C.c_int, C.c_int,
                                      f32p, f32p, C.c_int, C.c_float, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, f32p, f32p, C.c_size_t, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "jh_update_fused_batch": (C.c_int, [C.c_int, f32p, f32p, C.c_size_t, C.c_int, C.c_int, C.c_int, f32p, C.c_int, C.c_size_t, C.c_int, C.c_int, C.c_int, C.c_int, C.c_float, C.c_int, C.c_int, C.c_int,
+                                        f32p, C.c_int, C.c_int, f32p, f32p, C.c_size_t, C.c_void_p, C.c_void_p]),
     "jh_noise_normal_batch": (C.c_int, [C.c_int, C.POINTER(C.c_ulonglong), C.POINTER(C.c_uint), C.c_int, C.c_int, f32p, C.c_int, C.c_void_p]),
     "jh_shard_record_floats": (C.c_size_t, [C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int]),
     "jh_update_shard": (C.c_int, [f32p, f32p, f32p, f32p, C.c_int, f32p, f32p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_float, C.c_int, C.c_int, C.c_int, f32p, C.c_int, C.c_int,

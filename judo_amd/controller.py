@@ -86,7 +86,9 @@ class Controller:
     """Same attribute/method surface as the reference Controller for the hot path."""
 
     def __init__(self, controller_config: ControllerConfig, task: Task, optimizer: Optimizer, device: torch.device | None = None,
-                 group: Any = None) -> None:
+                 group: Any = None, policy_share: Any = None) -> None:
+        """`policy_share` (policy tasks only): a `PolicyRolloutBackend` of the same model whose engine and policy this controller's backend uses instead of uploading its own
+        (`make_controller_fleet`)."""
         self._controller_cfg = controller_config
         self.task = task
         self.optimizer = optimizer
@@ -101,7 +103,8 @@ class Controller:
             world, rank = world_info(group)
             self.model = None
             self.rollout_backend = PolicyRolloutBackend(shard_rollouts(self.optimizer_cfg.num_rollouts, world, rank).count, physics_substeps=task.physics_substeps,
-                                                        policy_path=task.locomotion_policy_path, desc=task.desc, device=self.device)
+                                                        policy_path=task.locomotion_policy_path, desc=task.desc, device=self.device,
+                                                        share=policy_share)
             self.rollout_cutoff_time: float | None = DEFAULT_SPOT_ROLLOUT_CUTOFF_TIME  # policy_mj_rollout_backend.py:94; None = no deadline
         else:
             self.model = task.gpu_model(self.device)
@@ -777,6 +780,12 @@ class Controller:
         else:  # a RolloutBackend plugin with the reference's numpy signature only (assigned to `controller.rollout_backend`)
             s_np, y_np, _ = self.rollout_backend.rollout(np.asarray(self.current_state), task.task_to_sim_ctrl(controls).cpu().numpy().astype(np.float64), None)
             states, sensors = torch.as_tensor(s_np, dtype=torch.float32, device=self.device), torch.as_tensor(y_np, dtype=torch.float32, device=self.device)
+        return self._score_rollout(states, sensors, controls)
+
+    def _score_rollout(self, states: torch.Tensor, sensors: torch.Tensor, controls: torch.Tensor, out: torch.Tensor | None = None) -> torch.Tensor:
+        """judo/controller/controller.py:274-279 on a materialised rollout: Task.post_rollout, Task.reward, and the arrays kept as `last_rollout`.  Returns costs = -rewards
+        (fp32, device), written into `out` when given.  `ControllerFleet` calls it per member on that member's rows of the fleet's arrays."""
+        task, n = self.task, int(states.shape[0])
         if getattr(task, "reward_accepts_torch", True):
             args = (states, sensors, controls)
         else:  # numpy-only plugin reward: one host round trip of the trajectories
@@ -784,10 +793,10 @@ class Controller:
         task.post_rollout(*args, self.system_metadata)
         rewards = task.reward(*args, self.system_metadata)
         rewards = torch.as_tensor(rewards, device=self.device).to(torch.float32).reshape(-1)
-        if rewards.shape[0] != shard.count:
-            raise ValueError(f"Task.reward must return ({shard.count},) rewards, got {tuple(rewards.shape)}")
+        if rewards.shape[0] != n:
+            raise ValueError(f"Task.reward must return ({n},) rewards, got {tuple(rewards.shape)}")
         self.last_rollout = (states, sensors, controls)
-        return (-rewards).contiguous()
+        return (-rewards).contiguous() if out is None else torch.neg(rewards, out=out)
 
     @property
     def rewards_local(self) -> np.ndarray:
@@ -968,7 +977,7 @@ def make_controller(init_task: str, init_optimizer: str, device: torch.device | 
     return make_controller_for(tasks[init_task][0](), init_optimizer, device=device, group=group)
 
 
-def make_controller_for(task: Task, init_optimizer: str, device: torch.device | None = None, group: Any = None) -> Controller:
+def make_controller_for(task: Task, init_optimizer: str, device: torch.device | None = None, group: Any = None, policy_share: Any = None) -> Controller:
     """The same construction around a task INSTANCE (one built with constructor arguments, e.g. `CaltechLeapCube(fingertips="cylinder")` or `FR3Pick(self_collision=True)`): the optimizer and
     controller overrides registered for the task's name."""
     opts = get_registered_optimizers()
@@ -980,7 +989,7 @@ def make_controller_for(task: Task, init_optimizer: str, device: torch.device | 
     optimizer = opt_cls(opt_cfg, task.nu)
     ctrl_cfg = ControllerConfig()
     ctrl_cfg.set_override(task.name)
-    return Controller(ctrl_cfg, task, optimizer, device=device, group=group)
+    return Controller(ctrl_cfg, task, optimizer, device=device, group=group, policy_share=policy_share)
 
 
 assert set(SPLINE_KINDS) == {"zero", "linear", "cubic"}

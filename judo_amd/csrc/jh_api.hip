@@ -519,6 +519,38 @@ extern "C" int jh_plan_step_batch(const jh_model* m, int B, void* blk_dev, const
   return rc;
 }
 
+// The update alone for B problems whose costs are given (the materialise path of a fleet: the Spot policy rollout, judo_amd/fleet.py): jh_plan_step_batch's last stage --
+// k_update_tail_batch with the two-level ticket -- and its completion mark, without an upload or a rollout kernel in front.
+extern "C" int jh_update_fused_batch(int B, const float* costs, const float* blk, size_t blk_stride_floats, int o_nominal, int o_sigma, int o_lohi, const float* noise, int ldn,
+                                     size_t noise_stride_floats, int N, int K, int nu, int mode, float lambda, int k, int tie_high, int E, const float* trace, int row_floats,
+                                     int colmajor, float* scratch, float* out, size_t out_stride_floats, void* out_host_mark, void* stream) {
+  JH_REQUIRE(costs && blk && noise && scratch && out, "update_fused_batch: null pointer");
+  JH_REQUIRE(B >= 1, "update_fused_batch: B must be at least 1 (B=%d)", B);
+  JH_REQUIRE(B <= 65535, "update_fused_batch: B = %d exceeds the 65535 problems of a launch (the grid's second dimension)", B);
+  JH_REQUIRE(N > 0 && K > 0 && nu > 0 && K * nu <= JH_MAX_KNOT_DIM, "update_fused_batch: N, K, nu must be positive and K*nu <= %d (N=%d K=%d nu=%d)", JH_MAX_KNOT_DIM, N, K, nu);
+  JH_REQUIRE(o_nominal >= 0 && o_sigma >= 0 && o_lohi >= 0, "update_fused_batch: negative block offset");
+  const int KU = K * nu;
+  const size_t need = (size_t)std::max(std::max(o_nominal + KU, o_sigma + KU), o_lohi + 2 * nu);
+  JH_REQUIRE(blk_stride_floats >= need, "update_fused_batch: blk_stride_floats = %zu is smaller than a block (nominal | sigma | bounds at the given offsets end at %zu floats)", blk_stride_floats, need);
+  JH_REQUIRE(ldn >= N && noise_stride_floats >= (size_t)KU * (size_t)ldn, "update_fused_batch: ldn (%d) < N (%d), or noise_stride_floats = %zu is smaller than a problem's noise (K*nu*ldn = %zu)", ldn, N,
+             noise_stride_floats, (size_t)KU * (size_t)ldn);
+  const int E_t = trace ? E : 0;
+  JH_REQUIRE(E_t >= 0 && E_t <= JH_MAX_ELITES && (E_t == 0 || row_floats >= 1), "update_fused_batch: bad trace arguments (E=%d row_floats=%d)", E, row_floats);
+  const size_t rec = 2 * (size_t)KU + (size_t)E_t * (2 + (size_t)(E_t > 0 ? row_floats : 0));
+  JH_REQUIRE(out_stride_floats >= rec, "update_fused_batch: out_stride_floats = %zu is smaller than an output record (nominal | sigma | E trace records = %zu floats)", out_stride_floats, rec);
+  unsigned* flag = (out_host_mark && out_host_mark != (void*)out) ? (unsigned*)out_host_mark : nullptr;  // (out_host_mark == out: the stream's event)
+  const unsigned expect = flag ? __atomic_load_n(flag, __ATOMIC_RELAXED) + 1u : 0u;
+  jh_upd::TailArgs a;
+  if (int rc = jh_update_tail_args("update_fused_batch", costs, nullptr, blk + o_nominal, noise, ldn, blk + o_sigma, blk + o_lohi, N, 0, K, nu, mode, lambda, k, tie_high, E_t, trace, row_floats,
+                                   colmajor, scratch, out, out + KU, E_t > 0 ? out + 2 * KU : nullptr, nullptr, &a)) return rc;
+  jh_upd::BatchArgs s;
+  s.B = B; s.blk = (long long)blk_stride_floats; s.noise = (long long)noise_stride_floats; s.costs = N; s.trace = (long long)N * row_floats;
+  s.scratch = (long long)jh_update_fused_scratch_floats(N, K, nu); s.out = (long long)out_stride_floats;
+  s.counter = reinterpret_cast<unsigned*>(scratch) + 1; s.done_flag = flag; s.done_value = expect;
+  if (int rc = jh_update_tail_batch_launch(a, s, (hipStream_t)stream)) return rc;
+  return download_begin(out, out, 0, stream, flag, expect);
+}
+
 // The same iteration when the rollouts are sharded over G ranks: launch -> all-gather -> merge.  The tail writes this rank's record; jh_plan_merge
 // finishes the update on every rank (jh_shard_merge: identical nominal everywhere, no broadcast) into the same output block jh_plan_step fills and sets the same
 // completion mark.

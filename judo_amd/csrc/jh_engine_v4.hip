@@ -1650,12 +1650,9 @@ __global__ void k_fill_after_cutoff(float* rows, int W, int N, int T, int done) 
 
 extern "C" size_t jh_policy_rollout_scratch_floats(int N) { return jh_policy_scratch_floats(N) + (size_t)(N > 0 ? N : 0) * NJ; }
 
-extern "C" int jh_policy_rollout(const jh_policy* p, jh_tree* t, const float* x0, int x0_batched, const float* commands, float* policy_out, float* warmstart, int reset_warmstart,
-                                 int N, int T, int substeps, double cutoff_seconds, float* states, float* sensors, float* scratch, int* steps_done, void* stream) {
-  JH_REQUIRE(p && t && x0 && commands && policy_out && states && scratch, "policy_rollout: null pointer");
-  JH_REQUIRE(N > 0 && T > 0 && substeps > 0, "policy_rollout: need at least one rollout, one command row and one substep");
-  JH_REQUIRE(!reset_warmstart || warmstart, "policy_rollout: reset_warmstart needs a warmstart buffer");
-  hipStream_t st = (hipStream_t)stream;
+// The loop over the command rows: the first control step reads rollout n's start state at x0 + n * ld0 (ld0 = 0: one state for all), every later one the row before it in `states`.
+static int policy_rollout(const jh_policy* p, jh_tree* t, const float* x0, int ld0, const float* commands, float* policy_out, float* warmstart, int reset_warmstart, int N, int T,
+                          int substeps, double cutoff_seconds, float* states, float* sensors, float* scratch, int* steps_done, hipStream_t st) {
   float* control = scratch + jh_policy_scratch_floats(N);
   const int NX = t->nq + t->nv, NQ = t->nq, NVT = t->nv;  // the state row of the image's model (robot [+ free box]): the policy reads the robot's part at its offsets
   const bool deadline = cutoff_seconds >= 0.0;
@@ -1671,7 +1668,7 @@ extern "C" int jh_policy_rollout(const jh_policy* p, jh_tree* t, const float* x0
       if (!((double)ms * 1e-3 < cutoff_seconds)) { done = i; break; }
     }
     const float* xin = i == 0 ? x0 : states + (size_t)(i - 1) * NX;
-    const int ld = i == 0 ? (x0_batched ? NX : 0) : T * NX;
+    const int ld = i == 0 ? ld0 : T * NX;
     const int rc = jh_policy_step_strided(p, xin, ld, NQ, 0, 0, 7, 6, commands + (size_t)i * 25, T * 25, policy_out, control, scratch, N, st);
     if (rc != JH_OK) return rc;
     if (reset_warmstart) JH_HIP(hipMemsetAsync(warmstart, 0, (size_t)N * NVT * sizeof(float), st));
@@ -1690,4 +1687,44 @@ extern "C" int jh_policy_rollout(const jh_policy* p, jh_tree* t, const float* x0
   }
   if (steps_done) *steps_done = done;
   return JH_OK;
+}
+
+extern "C" int jh_policy_rollout(const jh_policy* p, jh_tree* t, const float* x0, int x0_batched, const float* commands, float* policy_out, float* warmstart, int reset_warmstart,
+                                 int N, int T, int substeps, double cutoff_seconds, float* states, float* sensors, float* scratch, int* steps_done, void* stream) {
+  JH_REQUIRE(p && t && x0 && commands && policy_out && states && scratch, "policy_rollout: null pointer");
+  JH_REQUIRE(N > 0 && T > 0 && substeps > 0, "policy_rollout: need at least one rollout, one command row and one substep");
+  JH_REQUIRE(!reset_warmstart || warmstart, "policy_rollout: reset_warmstart needs a warmstart buffer");
+  return policy_rollout(p, t, x0, x0_batched ? t->nq + t->nv : 0, commands, policy_out, warmstart, reset_warmstart, N, T, substeps, cutoff_seconds, states, sensors, scratch, steps_done,
+                        (hipStream_t)stream);
+}
+
+// B problems of n rollouts each in one launch chain (jh_policy_rollout_batch): rollout r starts from problem r / n's state.  The policy and tree kernels read a rollout's state
+// at a row stride, so the B start states are first copied out to one row per rollout -- into row T - 1 of `states`, which nothing reads before the last control step
+// overwrites it (the first step reads it there as every later step reads the row before its own) -- and the single call's loop runs on N = B * n rollouts unchanged.
+// With T = 1 that row is row 0, which the one control step reads and writes in place: the case jh_tree_substeps documents (state_in / state_out may alias -- k_tree_v4
+// holds a rollout's state in registers before it stores, and the policy step that reads the row runs in a launch of its own in front).
+namespace {
+__global__ void k_expand_start_states(const float* __restrict__ x0, size_t x0_stride, int n, int N, int NX, float* __restrict__ rows, size_t ld) {
+  const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= (size_t)N * NX) return;
+  const size_t r = i / NX, c = i % NX;
+  rows[r * ld + c] = x0[(r / n) * x0_stride + c];
+}
+}  // namespace
+
+extern "C" int jh_policy_rollout_batch(const jh_policy* p, jh_tree* t, int B, const float* x0, size_t x0_stride_floats, const float* commands, float* policy_out, float* warmstart,
+                                       int reset_warmstart, int n, int T, int substeps, double cutoff_seconds, float* states, float* sensors, float* scratch, int* steps_done,
+                                       void* stream) {
+  JH_REQUIRE(p && t && x0 && commands && policy_out && states && scratch, "policy_rollout_batch: null pointer");
+  JH_REQUIRE(B >= 1 && n > 0 && T > 0 && substeps > 0, "policy_rollout_batch: need at least one problem, one rollout, one command row and one substep (B=%d n=%d T=%d)", B, n, T);
+  JH_REQUIRE((long long)B * n <= 0x7fffffffLL, "policy_rollout_batch: B * n = %lld rollouts exceed one launch", (long long)B * n);
+  JH_REQUIRE(!reset_warmstart || warmstart, "policy_rollout_batch: reset_warmstart needs a warmstart buffer");
+  const int NX = t->nq + t->nv, N = B * n;
+  JH_REQUIRE(x0_stride_floats >= (size_t)NX, "policy_rollout_batch: x0_stride_floats = %zu is smaller than a state (%d floats)", x0_stride_floats, NX);
+  hipStream_t st = (hipStream_t)stream;
+  float* start = states + (size_t)(T - 1) * NX;
+  const size_t tot = (size_t)N * NX;
+  hipLaunchKernelGGL(k_expand_start_states, dim3((unsigned)((tot + 255) / 256)), dim3(256), 0, st, x0, x0_stride_floats, n, N, NX, start, (size_t)T * NX);
+  JH_HIP(hipGetLastError());
+  return policy_rollout(p, t, start, T * NX, commands, policy_out, warmstart, reset_warmstart, N, T, substeps, cutoff_seconds, states, sensors, scratch, steps_done, st);
 }

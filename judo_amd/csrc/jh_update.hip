@@ -9,6 +9,7 @@
 // across the four waves of a workgroup, one partial record per workgroup, finished by a single-workgroup merge with a
 // log-sum-exp rescale so that no global minimum pass is needed first.
 #include "jh_update_dev.h"
+#include <algorithm>
 
 namespace {
 
@@ -41,11 +42,37 @@ __global__ __launch_bounds__(64) void k_spline_controls(KnotSrc src, const float
     out[(size_t)(n0 + r) * row + i] = v;
   }
 }
+// B problems in one launch (jh_spline_controls_batch): blockIdx.y picks the problem, whose knot source lies `blk` / `noise` floats behind the one before's and whose N rows
+// of `out` follow the one before's.  k_spline_controls' statements on those pointers, so the same bits as B launches of it (restated, not shared: the single kernel
+// compiled through a common device function schedules two instructions differently, and the existing entries keep their code as compiled).
+struct SplineBatch { long long blk, noise; };
+__device__ __forceinline__ KnotSrc spline_problem(KnotSrc src, const SplineBatch& s, int b) {
+  src.nominal += b * s.blk; src.sigma += b * s.blk; src.lohi += b * s.blk; src.noise += b * s.noise;
+  return src;
+}
+__global__ __launch_bounds__(64) void k_spline_controls_batch(KnotSrc src0, SplineBatch s, const float* __restrict__ W, int N, int H, int K, float* __restrict__ out0) {
+  extern __shared__ float sm[];
+  const KnotSrc src = spline_problem(src0, s, (int)blockIdx.y);
+  const int KU = src.KU, nu = src.nu, SK = KU | 1, row = H * nu;
+  float* __restrict__ out = out0 + (size_t)blockIdx.y * N * row;
+  float* sW = sm;            // H*K
+  float* sK = sm + H * K;    // 64 * SK
+  const int lane = threadIdx.x, n0 = blockIdx.x * 64, nvalid = min(64, N - n0);
+  for (int i = lane; i < H * K; i += 64) sW[i] = W[i];
+  if (lane < nvalid) for (int idx = 0; idx < KU; idx++) sK[lane * SK + idx] = src.get(n0 + lane, idx);
+  __syncthreads();
+  for (int f = lane; f < nvalid * row; f += 64) {
+    const int r = f / row, i = f - r * row, h = i / nu, u = i - h * nu;
+    float v = 0.f;
+    for (int k = 0; k < K; k++) v = fmaf(sW[h * K + k], sK[r * SK + k * nu + u], v);
+    out[(size_t)(n0 + r) * row + i] = v;
+  }
+}
 
 // The same sum where W and 64 rollouts' knots do not fit the LDS (K * nu >= 256, or a long horizon): one thread per output element reads W and the knots from global
 // memory (the knots recomputed by KnotSrc where they are not given).  Same products in the same order as k_spline_controls: the same bits.  Only K * nu and H*K above the
 // LDS staging take it -- the materialise path above the fused kernels' knot limit (include/judo_amd.h: a live num_nodes edit must not raise).
-__global__ __launch_bounds__(kUB) void k_spline_controls_global(KnotSrc src, const float* __restrict__ W, int N, int H, int K, float* __restrict__ out) {
+__device__ __forceinline__ void spline_controls_global_body(const KnotSrc& src, const float* __restrict__ W, int N, int H, int K, float* __restrict__ out) {
   const int nu = src.nu, row = H * nu;
   const size_t f = (size_t)blockIdx.x * kUB + threadIdx.x;
   if (f >= (size_t)N * row) return;
@@ -53,6 +80,13 @@ __global__ __launch_bounds__(kUB) void k_spline_controls_global(KnotSrc src, con
   float v = 0.f;
   for (int k = 0; k < K; k++) v = fmaf(W[(size_t)h * K + k], src.get(r, k * nu + u), v);
   out[f] = v;
+}
+__global__ __launch_bounds__(kUB) void k_spline_controls_global(KnotSrc src, const float* __restrict__ W, int N, int H, int K, float* __restrict__ out) {
+  spline_controls_global_body(src, W, N, H, K, out);
+}
+__global__ __launch_bounds__(kUB) void k_spline_controls_global_batch(KnotSrc src, SplineBatch s, const float* __restrict__ W, int N, int H, int K, float* __restrict__ out) {
+  const int b = blockIdx.y;
+  spline_controls_global_body(spline_problem(src, s, b), W, N, H, K, out + (size_t)b * N * H * src.nu);
 }
 
 // Moments of the candidate knots per actuator for the running action normaliser (judo/utils/normalization.py:176-200 on
@@ -223,6 +257,32 @@ extern "C" int jh_spline_controls(const float* W, const float* knots_nku, const 
     const size_t total = (size_t)N * H * nu;
     JH_REQUIRE(total / kUB < 0x7fffffffu, "spline_controls: N * H * nu = %zu too large for one launch", total);
     hipLaunchKernelGGL(k_spline_controls_global, dim3((unsigned)((total + kUB - 1) / kUB)), dim3(kUB), 0, (hipStream_t)stream, src, W, N, H, K, controls);
+  }
+  JH_HIP(hipGetLastError());
+  return JH_OK;
+}
+
+extern "C" int jh_spline_controls_batch(const float* W, int B, const float* blk, size_t blk_stride_floats, int o_nominal, int o_sigma, int o_lohi, const float* noise, int ldn,
+                                        size_t noise_stride_floats, int N, int H, int K, int nu, float* controls, void* stream) {
+  if (int e = check_dims(N, K, nu)) return e;
+  JH_REQUIRE(W && blk && noise && controls, "spline_controls_batch: null pointer");
+  JH_REQUIRE(B >= 1, "spline_controls_batch: B must be at least 1 (B=%d)", B);
+  JH_REQUIRE(B <= 65535, "spline_controls_batch: B = %d exceeds the 65535 problems of a launch (the grid's second dimension)", B);
+  JH_REQUIRE(H > 0, "spline_controls_batch: H must be positive");
+  JH_REQUIRE(ldn >= N, "spline_controls_batch: ldn (%d) < N (%d)", ldn, N);
+  JH_REQUIRE(o_nominal >= 0 && o_sigma >= 0 && o_lohi >= 0, "spline_controls_batch: negative block offset");
+  const int KU = K * nu;
+  const size_t need = (size_t)std::max(std::max(o_nominal + KU, o_sigma + KU), o_lohi + 2 * nu);
+  JH_REQUIRE(blk_stride_floats >= need, "spline_controls_batch: blk_stride_floats = %zu is smaller than a block (nominal | sigma | bounds at the given offsets end at %zu floats)", blk_stride_floats, need);
+  JH_REQUIRE(noise_stride_floats >= (size_t)KU * (size_t)ldn, "spline_controls_batch: noise_stride_floats = %zu is smaller than a problem's noise (K*nu*ldn = %zu)", noise_stride_floats, (size_t)KU * (size_t)ldn);
+  const size_t lds = sizeof(float) * ((size_t)H * K + 64 * (size_t)(KU | 1));
+  const KnotSrc src{nullptr, blk + o_nominal, noise, blk + o_sigma, blk + o_lohi, ldn, 0, KU, nu};
+  const SplineBatch s{(long long)blk_stride_floats, (long long)noise_stride_floats};
+  if (lds <= 64 * 1024) hipLaunchKernelGGL(k_spline_controls_batch, dim3((N + 63) / 64, B), dim3(64), lds, (hipStream_t)stream, src, s, W, N, H, K, controls);
+  else {  // (the same switch as the single call: a problem's rows come from the same form there and here)
+    const size_t total = (size_t)N * H * nu;
+    JH_REQUIRE(total / kUB < 0x7fffffffu, "spline_controls_batch: N * H * nu = %zu too large for one launch", total);
+    hipLaunchKernelGGL(k_spline_controls_global_batch, dim3((unsigned)((total + kUB - 1) / kUB), B), dim3(kUB), 0, (hipStream_t)stream, src, s, W, N, H, K, controls);
   }
   JH_HIP(hipGetLastError());
   return JH_OK;

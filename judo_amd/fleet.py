@@ -9,18 +9,24 @@ Afterwards each member is bit for bit where its own `update_action()` would have
 
 What the members must share is what the launch shares: the model, N, K, H, the spline order, the trace count, the optimizer kind and its scalar arguments.
 Everything else -- state, time, goal and the other task parameters, seed or injected noise, CEM sigma -- is a member's own.
+
+The Spot policy tasks have no `GpuModel` and no one-call plan step: their iteration is spline -> command mapping -> policy + plant rollout -> `Task.reward` -> update.  A fleet
+of them runs that chain ONCE for the B * n rollouts of its members (`jh_spline_controls_batch`, `jh_policy_rollout_batch`, `jh_update_fused_batch`) around one
+`SpotTreeEngine`, one `SpotLocomotionPolicy` and a `PolicyRolloutBackend` of B * n threads; only the rewards stay per member, each task's own `reward` with its own
+configuration on its rows.  A rollout's bits depend neither on its wave-mates nor on the batch size (tests/test_gpu_spot.py), so the contract is the same: bit for bit.
 """
 
 from __future__ import annotations
 
 import ctypes as C
+import weakref
 from typing import Any, Sequence
 
 import numpy as np
 import torch
 
 from judo_amd import _lib
-from judo_amd.controller import Controller, make_controller_for
+from judo_amd.controller import POLICY_OUTPUT_DIM, Controller, make_controller_for
 from judo_amd.device import current_stream_ptr
 from judo_amd.distributed import world_info
 from judo_amd.optimizers import Optimizer, _NoiseStream
@@ -111,6 +117,16 @@ class ControllerFleet:
         for i, c in enumerate(self.controllers):
             self._check_member(i, c, first)
         self.model = first.model
+        self.policy_backend = None  # the Spot policy tasks: the fleet's own backend of B * n threads around the members' one engine and one policy
+        if first.task.uses_locomotion_policy:
+            for i, c in enumerate(self.controllers):  # (a member's carried state becomes a view of THIS fleet's tensors, _load_carry: a controller is in one fleet at a time)
+                other = getattr(c, "_fleet_ref", lambda: None)()
+                if other is not None and other is not self:
+                    raise ValueError(f"fleet member {i} already belongs to another ControllerFleet: a Spot controller is a member of at most one fleet at a time")
+                c._fleet_ref = weakref.ref(self)
+            for c in self.controllers[1:]:  # one model image and one copy of the actor weights on the device for the whole fleet
+                c.rollout_backend.engine, c.rollout_backend.policy = first.rollout_backend.engine, first.rollout_backend.policy
+            self._policy_out: torch.Tensor | None = None  # (B * n, 12): the members' `_last_policy_output` are views of it
         for c in self.controllers[1:]:  # one image of the model constants on the device for the whole fleet
             if c.model is not self.model:
                 c.model = c.task._gpu = c.rollout_backend.model = self.model
@@ -134,10 +150,16 @@ class ControllerFleet:
                 "spline_order": c.spline_order, "max_num_traces": c.max_num_traces, "max_opt_iters": c.max_opt_iters,
                 "fused_update_args": opt.fused_update_args() if hasattr(opt, "fused_update_args") else None}
 
+    @staticmethod
+    def _shared_policy(c: Controller) -> dict[str, Any]:
+        """What the members of a Spot fleet share beyond `_shared`: what the one rollout launch chain and the one command mapping take from member 0."""
+        t, rb = c.task, c.rollout_backend
+        return {"physics_substeps": rb.physics_substeps, "rollout_cutoff_time": c.rollout_cutoff_time, "carry_warmstart": rb.carry_warmstart, "self_collision": rb.engine.self_collision,
+                "use_arm": t.use_arm, "use_gripper": t.use_gripper, "use_legs": t.use_legs, "use_torso": t.use_torso, "command_mask": t.command_mask.tolist(),
+                "default_policy_command": np.asarray(t.default_policy_command).tolist()}
+
     def _check_member(self, i: int, c: Controller, first: Controller) -> None:
-        if c.task.uses_locomotion_policy or c.model is None:
-            raise ValueError(f"fleet member {i}: the Spot policy tasks have no batched plan step")
-        if c.model.desc.get("family", c.model.task) == "fr3_pick":
+        if c.model is not None and c.model.desc.get("family", c.model.task) == "fr3_pick":
             raise ValueError(f"fleet member {i}: fr3_pick has no batched plan step (its phase is chosen per problem on the host)")
         if c.device != first.device:
             raise ValueError(f"fleet member {i} is on {c.device}, the fleet on {first.device}")
@@ -145,14 +167,27 @@ class ControllerFleet:
         for key in want:
             if mine[key] != want[key]:
                 raise ValueError(f"fleet member {i} differs from member 0 in {key}: {mine[key]!r} against {want[key]!r}")
-        if c.model is not first.model and (c.model._blob != first.model._blob or c.model.build() != first.model.build() or c.model.self_collision != first.model.self_collision):
+        policy = c.task.uses_locomotion_policy
+        if policy:
+            mine, want = self._shared_policy(c), self._shared_policy(first)
+            for key in want:
+                if mine[key] != want[key]:
+                    raise ValueError(f"fleet member {i} differs from member 0 in {key}: {mine[key]!r} against {want[key]!r}")
+            mine_e, want_e = c.rollout_backend.engine, first.rollout_backend.engine
+            if mine_e is not want_e and bytes(mine_e._blob) != bytes(want_e._blob):
+                raise ValueError(f"fleet member {i} has another model image than member 0")
+        elif c.model is not first.model and (c.model._blob != first.model._blob or c.model.build() != first.model.build() or c.model.self_collision != first.model.self_collision):
             raise ValueError(f"fleet member {i} has another model image or kernel build than member 0")
         world, _ = world_info(c.group)
-        shape = c._iteration_shape(world, c._current_normalizer())
-        if shape != "plan_step" or c.keep_candidates or c.record_kernel_events:
+        nrm = c._current_normalizer()
+        shape = c._iteration_shape(world, nrm)
+        # a Spot member's iteration is the materialise path without moments ("update_fused"); everybody else's the one jh_plan_step call
+        ok = (shape == "update_fused" and not nrm.needs_moments) if policy else shape == "plan_step"
+        if not ok or c.keep_candidates or c.record_kernel_events:
             why = ("a process group" if world > 1 or c.force_shard_path else "keep_candidates" if c.keep_candidates else "record_kernel_events" if c.record_kernel_events
-                   else "a running normaliser" if c._current_normalizer().needs_moments else "a plugin reward, hook or optimizer, or a knot count above the fused kernel's limit")
-            raise ValueError(f"fleet member {i} does not run its iteration as one jh_plan_step call ({why}): only such controllers can share a launch")
+                   else "a running normaliser" if nrm.needs_moments else "a plugin reward, hook or optimizer, or a knot count above the fused kernel's limit")
+            how = "as spline, policy rollout, reward and jh_update_fused" if policy else "as one jh_plan_step call"
+            raise ValueError(f"fleet member {i} does not run its iteration {how} ({why}): only such controllers can share a launch")
 
     # ---- the plan step --------------------------------------------------------------------------------------------------------------------------------
     def _buffers(self, key: tuple) -> _FleetBuffers:
@@ -191,6 +226,8 @@ class ControllerFleet:
         first = cs[0]
         for i, c in enumerate(cs):  # (live edits of a config between plan steps must not silently split the fleet)
             self._check_member(i, c, first)
+        if first.task.uses_locomotion_policy:
+            return self._update_action_policy()
         plans = [c._begin_plan() for c in cs]
         # (a plan: N, K, nu, H, world, shard, normaliser, normalised nominal, W, x0, new knot times, fused optimizer?, trace elites, task params -- Controller._begin_plan)
         N, K, nu, H, _, _, _, _, W, _, _, _, E, tp0 = plans[0]
@@ -242,8 +279,102 @@ class ControllerFleet:
             c._end_plan(p, mb, st_i, n_n, iters, staged, stream)
 
 
+    # ---- the plan step of the Spot policy tasks ------------------------------------------------------------------------------------------------------
+    def _load_carry(self, B: int, n: int) -> torch.Tensor:
+        """The fleet's backend of B * n threads, its warm start and the (B * n, 12) policy outputs holding every member's carried state: a member's `_last_policy_output` and
+        its backend's warm start are views of its n rows, so what a member brings along from elsewhere -- zeros after `reset()` or `rollout_backend.update()`, its own arrays
+        after plan steps on its own -- is copied in here, and what the fleet's rollout leaves is the member's without a copy.  Whether a member's tensor already is its
+        view is told from its address and shape, which holds because a Spot controller belongs to at most one fleet at a time (checked in `__init__`)."""
+        first = self.controllers[0].rollout_backend
+        pb = self.policy_backend
+        if pb is None or pb.engine is not first.engine or pb.policy is not first.policy:
+            from judo_amd.policy import PolicyRolloutBackend
+
+            pb = self.policy_backend = PolicyRolloutBackend(B * n, physics_substeps=first.physics_substeps, device=self.device, carry_warmstart=first.carry_warmstart, share=first)
+        pb.physics_substeps, pb.carry_warmstart = first.physics_substeps, first.carry_warmstart
+        if pb.num_threads != B * n:
+            pb.update(B * n)
+        if self._policy_out is None or self._policy_out.shape[0] != B * n:
+            self._policy_out = torch.zeros((B * n, POLICY_OUTPUT_DIM), dtype=torch.float32, device=self.device)
+        for i, c in enumerate(self.controllers):
+            warm, out = pb._warm[i * n : (i + 1) * n], self._policy_out[i * n : (i + 1) * n]
+            mine = c.rollout_backend._warm
+            if mine.data_ptr() != warm.data_ptr() or mine.shape != warm.shape:
+                warm.copy_(mine)
+                c.rollout_backend._warm = warm
+            mine = c._last_policy_output
+            if mine is None:
+                out.zero_()
+            elif mine.data_ptr() != out.data_ptr() or mine.shape != out.shape:
+                out.copy_(mine)
+            c._last_policy_output = out
+        return self._policy_out
+
+    def _update_action_policy(self) -> None:
+        """`Controller.update_action` of B Spot members (the iteration shape "update_fused": Controller._rollout_update with Controller._materialised_costs) as one launch
+        chain per iteration: every stage that runs on the device once per controller there runs once per fleet here."""
+        lib = _lib.lib()
+        cs = self.controllers
+        first = cs[0]
+        plans = [c._begin_plan() for c in cs]
+        N, K, nu, H, _, _, _, _, W, _, _, _, E, tp0 = plans[0]
+        for i, p in enumerate(plans):
+            if (p[0], p[1], p[2], p[3], p[12], len(p[13])) != (N, K, nu, H, E, len(tp0)):
+                raise ValueError(f"fleet member {i} plans another problem size than member 0")
+        B = len(cs)
+        fb = self._buffers((B, N, K, nu, first.task.nq + first.task.nv, len(tp0), E))
+        stream = current_stream_ptr()
+        shards, nrms = [p[5] for p in plans], [p[6] for p in plans]
+        states: list[dict[str, Any]] = [dict(E=E, x0=p[9], new_times=p[10]) for p in plans]
+        nominal_n = [p[7] for p in plans]
+        mode, lam, k_el, tie = first.optimizer.fused_update_args()
+        off = fb.offsets
+        policy_out = self._load_carry(B, N)
+        iters, staged = 0, False
+        while iters < first.max_opt_iters and not any(c.optimizer.stop_cond() for c in cs):
+            last = iters == first.max_opt_iters - 1
+            affine = []
+            for c, mb, nrm, n_n in zip(cs, fb.members, nrms, nominal_n):
+                c._stream = stream
+                c.task.pre_rollout(c.current_state)
+                affine.append(c._iteration_inputs(mb, nrm, n_n, nu, upload=False))
+            _lib.check(lib.jh_upload_async(fb.blk.data_ptr(), fb.host_ptr, 4 * ((B - 1) * fb.blk_stride + fb.nblk), stream), "jh_upload_async")
+            noise = self._draw_noise(fb, N, K, nu)
+            costs = fb.costs[fb.noise_cur]
+            controls = torch.empty((B * N, H, nu), dtype=torch.float32, device=self.device)  # (fresh arrays per iteration, as the controller alone makes them: `last_rollout` keeps views)
+            st = lib.jh_spline_controls_batch(_lib.ptr(W), B, fb.blk.data_ptr(), fb.blk_stride, off[1], off[2], off[4], noise.data_ptr(), N, K * nu * N, N, H, K, nu, controls.data_ptr(), stream)
+            _lib.check(st, "jh_spline_controls_batch")
+            # the members' `use_*` flags agree (_check_member), so the command mapping is one elementwise pass over all rows (judo/tasks/spot/spot_base.py:325-391)
+            commands = first.task.task_to_sim_ctrl(controls).contiguous()
+            states_d, sensors_d = self.policy_backend.rollout_grouped(fb.blk, fb.blk_stride, B, commands, policy_out, cutoff_time=first.rollout_cutoff_time)
+            for i, c in enumerate(cs):
+                r = slice(i * N, (i + 1) * N)
+                c._score_rollout(states_d[r], sensors_d[r], controls[r], out=costs[i])
+            st = lib.jh_update_fused_batch(B, costs.data_ptr(), fb.blk.data_ptr(), fb.blk_stride, off[1], off[2], off[4], noise.data_ptr(), N, K * nu * N, N, K, nu, mode, lam, k_el, tie,
+                                           0, None, 0, 0, fb.scratch.data_ptr(), fb.out_host_ptr, fb.out_stride, fb.out_host_ptr, stream)
+            _lib.check(st, "jh_update_fused_batch")
+            _lib.check(lib.jh_download_end(), "jh_download_end")
+            for i, (c, mb, shard, st_i) in enumerate(zip(cs, fb.members, shards, states)):
+                mb.blk_stale = False
+                mb.costs = costs[i]
+                st_i.update(costs=mb.costs, knots_out=None, noise_p=noise[i].data_ptr(), ldn=N, knots_nku=None, trace_buf=None, stage=(True if last else None))
+                nominal_n[i] = c._iteration_result(mb, st_i, noise[i], noise[i].data_ptr(), N, shard, H, K, nu, 0, *affine[i])
+                if last:  # (the trace elites' rows of the materialised sensors, Controller._stage_traces' `last_rollout` branch)
+                    c._stage_traces(lib, mb, st_i, shard, 1, E, st_i["x0"], st_i["new_times"], K, nu, stream)
+            staged = last
+            iters += 1
+        for c, mb, p, st_i, n_n in zip(cs, fb.members, plans, states, nominal_n):
+            c._end_plan(p, mb, st_i, n_n, iters, staged, stream)
+
+    def solver_stats(self, reset: bool = True) -> dict:
+        """`Controller.solver_stats` for the fleet.  The members share one engine (one `GpuModel`, or one `SpotTreeEngine`) and the counters live on it: they are fleet-wide,
+        and a member's own `solver_stats()` reads -- and resets -- the same fleet-wide counters, not that member's share."""
+        return self.controllers[0].solver_stats(reset)
+
+
 def make_controller_fleet(task: str, optimizer: str, B: int, device: torch.device | None = None) -> ControllerFleet:
-    """B controllers of the registered task and optimizer (`make_controller`, judo/controller/controller.py:404-442, B times) around ONE `GpuModel`."""
+    """B controllers of the registered task and optimizer (`make_controller`, judo/controller/controller.py:404-442, B times) around ONE `GpuModel` -- or, for the Spot
+    policy tasks, ONE `SpotTreeEngine` and ONE `SpotLocomotionPolicy`."""
     tasks = get_registered_tasks()
     if task not in tasks:
         raise ValueError(f"Task {task} not found in task registry.")
@@ -252,7 +383,10 @@ def make_controller_fleet(task: str, optimizer: str, B: int, device: torch.devic
     members: list[Controller] = []
     for _ in range(B):
         t = tasks[task][0]()
-        if members:
+        share = None
+        if members and t.uses_locomotion_policy:
+            share = members[0].rollout_backend  # (Controller builds its PolicyRolloutBackend around that one's engine and policy)
+        elif members:
             t._gpu = members[0].model  # (Task.gpu_model hands it out instead of packing and uploading the image again)
-        members.append(make_controller_for(t, optimizer, device=device))
+        members.append(make_controller_for(t, optimizer, device=device, policy_share=share))
     return ControllerFleet(members)

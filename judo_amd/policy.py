@@ -154,10 +154,17 @@ class PolicyRolloutBackend(RolloutBackend):
     `rollout` call) to the next; False restarts every control step from a zero warm start (what the oracle's `policy_rollout` does)."""
 
     def __init__(self, num_threads: int, physics_substeps: int = 2, policy_path: str = POLICY_PATH, desc: dict | None = None, device: torch.device | None = None,
-                 carry_warmstart: bool = True) -> None:
+                 carry_warmstart: bool = True, share: "PolicyRolloutBackend | None" = None) -> None:
+        """`share`: another backend of the same model whose engine and policy handles this one uses instead of uploading the model image and the actor weights again (the
+        members of a `ControllerFleet`); its `desc`, `policy_path` and device then stand for this one's."""
         self.device = device or require_gpu()
-        self.engine = SpotTreeEngine(desc, self.device)
-        self.policy = SpotLocomotionPolicy(policy_path, self.device)
+        if share is not None:
+            if share.device != self.device:
+                raise ValueError(f"a shared policy backend lives on {share.device}, this one on {self.device}")
+            self.engine, self.policy = share.engine, share.policy
+        else:
+            self.engine = SpotTreeEngine(desc, self.device)
+            self.policy = SpotLocomotionPolicy(policy_path, self.device)
         self.layout = SpotStateLayout(nq=self.engine.nq, nv=self.engine.nv)
         self.physics_substeps = int(physics_substeps)
         self.carry_warmstart = carry_warmstart
@@ -207,3 +214,32 @@ class PolicyRolloutBackend(RolloutBackend):
         if as_numpy:
             return states.cpu().numpy().astype(np.float64), sensors.cpu().numpy().astype(np.float64), out.cpu().numpy().astype(np.float64)
         return states, sensors, out
+
+    def rollout_grouped(self, x0_blocks: torch.Tensor, x0_stride: int, B: int, commands: torch.Tensor, policy_out: torch.Tensor, cutoff_time: float | None = None):
+        """B problems of num_threads / B rollouts each in one launch chain (`jh_policy_rollout_batch`): rollout r starts from problem r // n's state, the B states lying
+        `x0_stride` floats apart in the device tensor `x0_blocks` (the x0 parts of a fleet's packed blocks).  commands (B * n, T, 25) and policy_out (B * n, 12), contiguous
+        float32 device tensors; policy_out and this backend's warm start are read and overwritten IN PLACE (a fleet's members hold views into them).  Returns (states, sensors);
+        problem b's rows are bit for bit those of `rollout` with n threads from its state."""
+        N, nx = self.num_threads, self.engine.nq + self.engine.nv
+        if B < 1 or N % B:
+            raise ValueError(f"{N} threads do not split into {B} problems")
+        if commands.ndim != 3 or commands.shape[0] != N or commands.shape[2] != SpotLocomotionPolicy.NCMD or not commands.is_contiguous() or commands.dtype != torch.float32:
+            raise ValueError(f"commands must be a contiguous float32 ({N}, T, 25) tensor, got {tuple(commands.shape)}")
+        if tuple(policy_out.shape) != (N, SpotLocomotionPolicy.ACT) or not policy_out.is_contiguous() or policy_out.dtype != torch.float32:
+            raise ValueError(f"policy_out must be a contiguous float32 ({N}, 12) tensor, got {tuple(policy_out.shape)}")
+        if x0_blocks.dtype != torch.float32 or x0_stride < nx or x0_blocks.numel() < (B - 1) * x0_stride + nx:
+            raise ValueError(f"x0_blocks must hold {B} float32 states of {nx} floats, {x0_stride} apart")
+        T = int(commands.shape[1])
+        states = torch.empty((N, T, nx), dtype=torch.float32, device=self.device)
+        sensors = torch.empty((N, T, self.engine.nsensordata), dtype=torch.float32, device=self.device)
+        L = _lib.lib()
+        need = int(L.jh_policy_rollout_scratch_floats(N))
+        if self._scratch is None or self._scratch.numel() < need:
+            self._scratch = torch.empty(need, dtype=torch.float32, device=self.device)
+        done = C.c_int(0)
+        s = L.jh_policy_rollout_batch(self.policy.handle, self.engine.handle, B, _lib.ptr(x0_blocks), int(x0_stride), _lib.ptr(commands), _lib.ptr(policy_out), _lib.ptr(self._warm),
+                                      int(not self.carry_warmstart), N // B, T, self.physics_substeps, -1.0 if cutoff_time is None else float(cutoff_time), _lib.ptr(states),
+                                      _lib.ptr(sensors) if sensors.numel() else None, _lib.ptr(self._scratch), C.byref(done), current_stream_ptr())
+        _lib.check(s, "jh_policy_rollout_batch")
+        self.steps_computed = int(done.value)
+        return states, sensors
