@@ -85,6 +85,15 @@ constexpr int NCH = 4, NLK = 4;
 #ifndef JH_V5_HCMERGE
 #define JH_V5_HCMERGE 1  // (round 6) the hand-capable copy's chain part with one exec-masked region per joint (see the contact pass)
 #endif
+// ---- The lane mapping of the hand's broad phase (profiles/leap_broad_phase.md).  Both switches keep the candidate list S.hits[] of every rollout and step entry for entry, in
+// the same order (0 = the loops as they were): the same tests on the same operands, only on other lanes and in fewer, fuller passes -- every output keeps its bits.
+#ifndef JH_V5_L1LIST
+#define JH_V5_L1LIST 1  // level 1: the body pairs whose bounding spheres overlap are written to S.bpl in ascending order, and the oriented-box test runs over that list 16 entries
+                        // per pass, compacting it in place -- instead of once per pass of 16 body PAIRS (7 or 8 passes, a few lanes each)
+#endif
+#ifndef JH_V5_L2COMBO
+#define JH_V5_L2COMBO 1  // level 2 (b): one lane per (near geom of A, near geom of B) combination, 16 per pass -- instead of one trip per near geom of A with only B's near lanes at work
+#endif
 #ifndef JH_V5_C3PAD
 #define JH_V5_C3PAD 278
 #endif
@@ -284,6 +293,20 @@ __device__ __forceinline__ bool obb_face_overlap(const float* ca, const float* R
   }
   return ok;
 }
+
+// index of the k-th set bit (k = 0: the lowest) of a 16-bit mask with more than k bits set: four halvings on the population count, no loop and no table
+__device__ __forceinline__ int nth_bit16(unsigned m, int k) {
+  int pos = 0, c = __popc(m & 0xFFu);
+  bool up = k >= c; k = up ? k - c : k; m = up ? m >> 8 : m; pos = up ? 8 : 0;
+  c = __popc(m & 0xFu); up = k >= c; k = up ? k - c : k; m = up ? m >> 4 : m; pos = up ? pos + 4 : pos;
+  c = __popc(m & 0x3u); up = k >= c; k = up ? k - c : k; m = up ? m >> 2 : m; pos = up ? pos + 2 : pos;
+  return k >= (int)(m & 1u) ? pos + 1 : pos;
+}
+#ifdef JH_V5_COUNT
+__device__ __forceinline__ int wave_rowmax(int v) {  // the maximum over the wave's four rows of a value that is uniform within a row
+  return max(max(__builtin_amdgcn_readlane(v, 0), __builtin_amdgcn_readlane(v, 16)), max(__builtin_amdgcn_readlane(v, 32), __builtin_amdgcn_readlane(v, 48)));
+}
+#endif
 
 // The three functions below visit the joints above a finger link.  JH_V5_LINKBATCH (round 4): all four joints of the chain are loaded and their columns
 // axis_j x (pos - anchor_j) computed UNCONDITIONALLY, the depth of the link only masks what is accumulated.  The per-joint form (`if (j <= dep) { load; compute; }`) put every
@@ -678,6 +701,16 @@ __global__ __launch_bounds__(WAVE * WPB, JH_V5_WAVES_PER_EU) JH_V5_REGATTR void 
 #endif
 #ifdef JH_V5_COUNT
   int cnt_dense = 0, cnt_it = 0, cnt_l2 = 0, cnt_bp = 0, cnt_hh = 0, cnt_cls[4] = {0, 0, 0, 0};
+  // the broad phase's lane use (tools/diag/count_broadphase.py; profiles/leap_broad_phase.md), stats[34..53].  Sums over rollout-steps (R) or wave-steps (W), maxima (M):
+  // 34 R sphere survivors of level 1, 35 W their maximum over the wave, 36 W the maximum of the box survivors, 37 W passes of 16 body pairs with a sphere survivor (= runs of the
+  // box region in the per-pair form), 38 W ceil(35 / 16) (= runs in the list form), 39 W trips of the per-geom loop of level 2 (b), 40 R body pairs that reach (b), 41 R their
+  // combinations T = near A x near B, 42 W passes of 16 combinations, 43 W geom slots of the cube's sweep with a lane in the box region, 44 lanes in it, 45 M sphere survivors,
+  // 46 M box survivors, 47 M T, 48 R steps without a sphere survivor, 49 / 50 R pairs in (b) with one near geom on side A / B, 51 R trips a rollout needs by itself,
+  // 52 R steps with more than MAXBPL sphere survivors, 53 M MAXBP - sphere survivors (the fewest seen)
+  enum { CB_SPH = 34, CB_SPHMAX, CB_BOXMAX, CB_L1PAIRPASS, CB_L1LISTPASS, CB_TRIPS, CB_BPAIRS, CB_T, CB_COMBOPASS, CB_CUBEBOX, CB_CUBEBOXLANES, CB_MSPH, CB_MBOX, CB_MT, CB_NOSPH, CB_ONEA, CB_ONEB,
+         CB_OWNTRIPS, CB_SPHOVER, CB_FEWSPH };
+#define V5_CADD(k, v) do { if (stats) atomicAdd(stats + (k), (int)(v)); } while (0)
+#define V5_CMAX(k, v) do { if (stats) atomicMax(stats + (k), (int)(v)); } while (0)
 #endif
   if constexpr (PERSIST) WSYNC();  // (this group's S.ws / S.cmd / sGrp; the workgroup barrier was taken once, in front of the queue)
   else {
@@ -890,6 +923,9 @@ __global__ __launch_bounds__(WAVE * WPB, JH_V5_WAVES_PER_EU) JH_V5_REGATTR void 
           hit = fabsf(gl[0]) <= gh[0] + crb && fabsf(gl[1]) <= gh[1] + crb && fabsf(gl[2]) <= gh[2] + crb;
         }
 #else
+#ifdef JH_V5_COUNT
+        if constexpr (SELF) { const unsigned long long bx = __ballot(hit && gtype == GBOX); if (lane == 0 && bx != 0) { V5_CADD(CB_CUBEBOX, 1); V5_CADD(CB_CUBEBOXLANES, __popcll(bx)); } }
+#endif
         if (hit && gtype == GBOX) {
           float gR[9], gl[3];
           if (gbody < 0) { for (int k = 0; k < 9; k++) gR[k] = gf[GF_R + k]; } else mulMM(gR, Rwr, gf + GF_R);
@@ -922,6 +958,51 @@ __global__ __launch_bounds__(WAVE * WPB, JH_V5_WAVES_PER_EU) JH_V5_REGATTR void 
           const float d[3] = {sa[0] - sb[0], sa[1] - sb[1], sa[2] - sb[2]}, rs = sa[3] + sb[3];
           sph |= ((i * G + l < nBP) & (dot3(d, d) <= rs * rs)) ? 1u << i : 0u;
         }
+#ifdef JH_V5_COUNT
+        {
+          int ns = 0, npass = 0;
+          for (int i = 0; i < NPASS; i++) { const unsigned long long b = __ballot((sph >> i) & 1u); ns += __popc((unsigned)((b >> (16 * r)) & 0xFFFFull)); npass += b != 0; }
+          const int nsm = wave_rowmax(ns);
+          if (l == 0 && live) { V5_CADD(CB_SPH, ns); V5_CMAX(CB_MSPH, ns); V5_CADD(CB_NOSPH, ns == 0); V5_CADD(CB_SPHOVER, ns > MAXBPL); V5_CMAX(CB_FEWSPH, MAXBP - ns); }
+          if (lane == 0) { V5_CADD(CB_SPHMAX, nsm); V5_CADD(CB_L1PAIRPASS, npass); V5_CADD(CB_L1LISTPASS, (nsm + G - 1) / G); }
+        }
+#endif
+#if JH_V5_L1LIST
+        // the sphere survivors in ascending pair order -> S.bpl.  The list can hold every pair of the model (up to MAXBP), S.bpl MAXBPL of them: the tail goes to the contact
+        // pool's storage, which nothing uses between the Newton solve of the last step and this step's narrow phase
+        unsigned char* const tail = reinterpret_cast<unsigned char*>(&S.pool[0][0]);
+        static_assert(sizeof(((RS*)nullptr)->pool) >= MAXBP - MAXBPL, "the tail of the sphere survivors fits the contact pool's storage");
+        int nsl = 0;
+#pragma unroll
+        for (int i = 0; i < NPASS; i++) {
+          if (i * G >= nBP) break;
+          const bool hit = (sph >> i) & 1u;
+          const unsigned m16 = (unsigned)((__ballot(hit) >> (16 * r)) & 0xFFFFull);
+          const int pos = nsl + __popc(m16 & ((1u << l) - 1u));
+          if (hit) { if (pos < MAXBPL) S.bpl[pos] = (unsigned char)(i * G + l); else tail[pos - MAXBPL] = (unsigned char)(i * G + l); }
+          nsl += __popc(m16);
+        }
+        WSYNC();
+        // the box test over the list, 16 entries per pass; the survivors go back to the front of S.bpl in the same order.  A pass reads its 16 entries before it writes
+        // (the ballot needs every lane's result), and it writes below the next pass's first entry: the list is compacted in place
+        for (int base = 0; __any(base < nsl); base += G) {
+          const int idx = base + l;
+          bool hit = idx < nsl; int pi = 0;
+          if (hit) {  // the two bodies' bounding boxes (static geometry: axis-aligned in the world)
+            pi = idx < MAXBPL ? S.bpl[idx] : tail[idx - MAXBPL];
+            const int ba = sBP[2 * pi], bb = sBP[2 * pi + 1];
+            const float* sa = S.bs[ba]; const float* sb = S.bs[bb];
+            const float I9[9] = {1, 0, 0, 0, 1, 0, 0, 0, 1};
+            float Ra[9]; for (int k = 0; k < 9; k++) Ra[k] = static_code(ba) ? I9[k] : S.xR[ba][k];  // (side A is the static one of a pair, if any)
+            hit = obb_face_overlap(sa, Ra, sBB + 8 * ba + 4, sb, S.xR[bb], sBB + 8 * bb + 4);
+          }
+          unsigned m16 = (unsigned)((__ballot(hit) >> (16 * r)) & 0xFFFFull);
+          int pos = nbl + __popc(m16 & ((1u << l) - 1u));
+          if (hit && pos < MAXBPL) S.bpl[pos] = (unsigned char)pi;
+          nbl += __popc(m16);
+          WSYNC();
+        }
+#else
 #pragma unroll
         for (int i = 0; i < NPASS; i++) {
           if (i * G >= nBP) break;
@@ -939,7 +1020,11 @@ __global__ __launch_bounds__(WAVE * WPB, JH_V5_WAVES_PER_EU) JH_V5_REGATTR void 
           if (hit && pos < MAXBPL) S.bpl[pos] = (unsigned char)pi;
           nbl += __popc(m16);
         }
+#endif
       }
+#ifdef JH_V5_COUNT
+      { const int nbm = wave_rowmax(nbl); if (lane == 0) V5_CADD(CB_BOXMAX, nbm); if (l == 0 && live) V5_CMAX(CB_MBOX, nbl); }
+#endif
       if (nbl > MAXBPL) { if (l == 0 && live && stats) atomicAdd(stats, nbl - MAXBPL); nbl = MAXBPL; }  // (counted with the dropped contacts)
 #ifdef JH_V5_COUNT
       if (l == 0 && live) cnt_bp += nbl;
@@ -973,12 +1058,37 @@ __global__ __launch_bounds__(WAVE * WPB, JH_V5_WAVES_PER_EU) JH_V5_REGATTR void 
         }
         const unsigned m16 = (unsigned)((__ballot(near) >> (16 * r)) & 0xFFFFull);
         const unsigned mB = (m16 >> na) & ((1u << nb) - 1u);
-        unsigned rem = mB != 0 ? (m16 & ((1u << na) - 1u)) : 0u;
+        const unsigned mA = mB != 0 ? (m16 & ((1u << na) - 1u)) : 0u;
+        const int nB = __popc(mB), T = __popc(mA) * nB;  // combinations (near geom of A, near geom of B) of this body pair
+#ifdef JH_V5_COUNT
+        {
+          const int tm = wave_rowmax((T + G - 1) / G);
+          if (lane == 0) V5_CADD(CB_COMBOPASS, tm);
+          if (l == 0 && live && T != 0) { V5_CADD(CB_BPAIRS, 1); V5_CADD(CB_T, T); V5_CMAX(CB_MT, T); V5_CADD(CB_ONEA, __popc(mA) == 1); V5_CADD(CB_ONEB, nB == 1); V5_CADD(CB_OWNTRIPS, __popc(mA)); }
+        }
+#endif
+#if JH_V5_L2COMBO
+        // combination t = ia' * nB + ib' (ia', ib': ranks among the near geoms of A and of B) goes to lane t mod 16 of pass t / 16: ascending t is ascending geom of A, then
+        // ascending geom of B -- the order in which the per-geom loop appended its survivors.  t / nB without a division: t < 256, nB <= 16, and (t + 0.5) / nB lies at least
+        // 1 / 32 from an integer, far above the error of the reciprocal
+        const float rnB = __builtin_amdgcn_rcpf((float)nB);
+        for (int t = l; __any(t - l < T); t += G) {
+          bool hit = false;
+          int ga = 0, gb = 0;
+          if (t < T) {
+            const int ra = (int)(((float)t + 0.5f) * rnB), rb = t - ra * nB;
+            ga = ga0 + nth_bit16(mA, ra); gb = gb0 + nth_bit16(mB, rb);
+#else
+        unsigned rem = mA;
         while (__any(rem != 0)) {
+#ifdef JH_V5_COUNT
+          if (lane == 0) V5_CADD(CB_TRIPS, 1);
+#endif
           const int ia = rem != 0 ? __ffs(rem) - 1 : 0;
           bool hit = false;
           const int ga = ga0 + ia, gb = gb0 + l;
           if (rem != 0 && l < nb && ((mB >> l) & 1u)) {
+#endif
             const float* fa = sGeomF + ga * GEOM_F; const float* fb = sGeomF + gb * GEOM_F;
             float ca[3], cb[3];
             if (static_code(ba)) { ca[0] = fa[GF_POS]; ca[1] = fa[GF_POS + 1]; ca[2] = fa[GF_POS + 2]; }
@@ -1006,7 +1116,9 @@ __global__ __launch_bounds__(WAVE * WPB, JH_V5_WAVES_PER_EU) JH_V5_REGATTR void 
           const int pos = nh + __popc(h16 & ((1u << l) - 1u));
           if (hit && pos < MAXHIT) S.hits[pos] = (unsigned short)(HITPAIR + (ga << 7 | gb));
           nh += __popc(h16);
+#if !JH_V5_L2COMBO
           rem &= rem - 1u;
+#endif
         }
       }
 #ifdef JH_V5_COUNT
