@@ -31,21 +31,6 @@ __device__ int g_wavestamp_cap = 0;
 
 constexpr int G = 16, RPW = 4, WAVE = 64;
 constexpr int NCH = 4, NLK = 4;
-#ifndef JH_V5_LSMAX
-#define JH_V5_LSMAX 16
-#endif
-#ifndef JH_V5_LSKINK
-#define JH_V5_LSKINK 0  // 1: where the plain safeguarded Newton search is in trouble the line search tries the step lengths at which the slope jumps (below).  Round 4, recorded
-                        // inputs (profiles/r04_leap_experiments.txt): it does what the CPU prototype promised -- 3.65 instead of 4.68 slope evaluations per Newton iteration of a
-                        // wave, the 9..16-evaluation searches gone (15 % -> 3 % of the wave's searches) -- and the kernel is 2.1 % SLOWER (82.45 against 80.75 ms): a slope
-                        // evaluation is ~1 % of an iteration's issue slots, the candidates' registers and the extra block cost more than a fifth of them.  Off.
-#endif
-#ifndef JH_V5_LSSHRINK
-#define JH_V5_LSSHRINK 0.9f
-#endif
-#ifndef JH_V5_LSREV
-#define JH_V5_LSREV 0.03f
-#endif
 // ---- The Newton iteration's formulation (round 4).  The alternatives below were A/B-measured on the recorded plan inputs within one GPU box each
 // (profiles/r04_leap_experiments.txt) and then taken out of the source (the git history has them as JH_V5_* switches):
 //  * gradient and Hessian of an iterate from ONE pass over the contacts (joint columns, world force and cone weights computed once, one fence less) instead of a gradient pass,
@@ -62,119 +47,67 @@ constexpr int NCH = 4, NLK = 4;
 //  * J'WJ from world-frame dof columns and A = Fr' W Fr (one symmetric 3 x 3 per contact; the cube's translation columns are unit vectors) instead of frame-space columns
 //    times W: 63.3 -> 61.7 ms;
 //  * two surviving hand body pairs per level-2 broad-phase pass when both have at most 8 geoms: never applies (the survivors involve the palm's geom groups), +0.8 %.
-#ifndef JH_V5_HCSPLIT
-#define JH_V5_HCSPLIT 1  // wave-steps without a candidate pair off the cube (two thirds of them on the headline workload) take a copy of the solver compiled without the code for the
-                         // hand's own contacts: 61.1 -> 59.4 ms.  The same contacts through the hand-capable copy cost 14 % more (48.5 against 42.5 ms with the hand's broad phase
-                         // switched off) for the registers its extra paths hold.  The two copies must give the same bits for a cube contact (a rollout's result may not depend on
-                         // its wave-mates: tests/test_gpu_leap.py permutes them): with -ffp-contract=fast they do not -- the backend fuses a product into an add only when the
-                         // product has no other use, and the hand paths are such uses -- so this file is built with -ffp-contract=on (fusion within a source expression only:
-                         // +0.7 % on its own, jh_engine_v5.flags).
-#endif
-#ifndef JH_V5_C3CACHE
-#define JH_V5_C3CACHE 1  // (round 5; recorded inputs 59.3 -> 58.3 ms, the same iterates bit for bit; profiles/r05_leap_experiments.txt)  1: the joint columns axis_j x (pos - anchor_j) of the FIRST slot's side-B link (12 floats per lane, invariant over the Newton iterations of a step) are computed
-                         // once per step and kept in the part of the contact pool's storage the Newton matrices leave free (768 of 820 bytes), three ds_read_b128 per use instead of
-                         // 24 loads + 36 multiply-adds, twice per iteration
-#endif
-#ifndef JH_V5_WORLDROT
-#define JH_V5_WORLDROT 1  // (round 6) the cube's three rotational dofs are solved for in WORLD coordinates (w = R w_body) inside the constraint solver: with the cube's isotropic
-                          // inertia (a cube: leap_cube, leap_cube_down, caltech_leap_cube; checked at model load) the quadratic term is the same in both frames, and the
-                          // rotation columns of a contact become e_q x r -- two non-zeros each -- instead of (R e_q) x r: no read of the cube's rotation matrix, no 3 x 3 product
-                          // anywhere in a Newton iteration (gradient torque, Hessian columns, J p of the line search).  The warm start and the integrated acceleration stay in
-                          // the body frame (MuJoCo's free-joint convention): two 3 x 3 products per STEP.  Same minimiser, different rounding than the body-frame form.
-#endif
-#ifndef JH_V5_HCMERGE
-#define JH_V5_HCMERGE 1  // (round 6) the hand-capable copy's chain part with one exec-masked region per joint (see the contact pass)
-#endif
-// ---- The lane mapping of the hand's broad phase (profiles/leap_broad_phase.md).  Both switches keep the candidate list S.hits[] of every rollout and step entry for entry, in
-// the same order (0 = the loops as they were): the same tests on the same operands, only on other lanes and in fewer, fuller passes -- every output keeps its bits.
-#ifndef JH_V5_L1LIST
-#define JH_V5_L1LIST 1  // level 1: the body pairs whose bounding spheres overlap are written to S.bpl in ascending order, and the oriented-box test runs over that list 16 entries
-                        // per pass, compacting it in place -- instead of once per pass of 16 body PAIRS (7 or 8 passes, a few lanes each)
-#endif
-#ifndef JH_V5_L2COMBO
-#define JH_V5_L2COMBO 1  // level 2 (b): one lane per (near geom of A, near geom of B) combination, 16 per pass -- instead of one trip per near geom of A with only B's near lanes at work
-#endif
-#ifndef JH_V5_C3PAD
-#define JH_V5_C3PAD 278
-#endif
-#ifndef JH_V5_LSRCP
-#define JH_V5_LSRCP 1  // the line search's Newton step divides with v_rcp_f32 (1 ulp) instead of the correctly rounded division sequence (10 instructions per evaluation): -0.2 %
-#endif
-#ifndef JH_V5_WAVES_PER_EU
-#define JH_V5_WAVES_PER_EU 2
-#endif
-#ifndef JH_V5_WPB
-#define JH_V5_WPB 4  // waves per workgroup: they share one LDS copy of the model image and nothing else
-#endif
+// Measured since and taken out the same way:
+//  * a line search that, where the safeguarded Newton search is in trouble, tries the step lengths at which the slope jumps (a friction-loss row's zero crossing, a contact's
+//    friction reversal): 3.65 instead of 4.68 slope evaluations per Newton iteration of a wave, the 9..16-evaluation searches gone (15 % -> 3 % of the searches), and the
+//    kernel 2.1 % SLOWER (82.45 against 80.75 ms): an evaluation is ~1 % of an iteration's issue slots, the candidates' registers and the extra block cost more than a fifth of
+//    them (profiles/r04_leap_experiments.txt; no gain on the round-6 kernel either, profiles/r06_experiments.txt);
+//  * a third copy of the constraint rows + solver with ONE slot per lane for the wave-steps in which no rollout has more than 16 contacts: 93 % of the wave-steps qualify and
+//    the kernel is 1.1 % faster (79.7 against 80.6 ms), but the copies contract differently, so a rollout's bits depend on its wave-mates (test_leap_full_size_properties
+//    fails); under -ffp-contract=on, bit-identical and +-0.2 % (profiles/r04_leap_experiments.txt, profiles/r06_experiments.txt);
+//  * the joints above a link visited one by one, each under its own `j <= depth` test, instead of link_c3's batch: 71.8 against 70.0 ms without the SLP vectorizer (with
+//    packed-fp32 code, rounds 2-3, the batch was the slower form, 83.0 against 79.4 ms: no room for 24 joint floats beside the packed operands' register pairs);
+//  * the line search's Newton step with the correctly rounded division (10 instructions per evaluation) instead of v_rcp_f32: +0.2 %;
+//  * OPAQUE on a contact slot's frame as well as its sides and lever arm, or again before the Hessian assembly and the line search: 71.6 and 71.0 against 70.0 ms (with the
+//    hand's own contacts and packed-fp32 code, rounds 2-3, the frame paid); the lane id left transparent at the top of the step loop: 73.6 against 70.0 ms; the step-level state
+//    held across the Newton loop instead of parked in LDS: 71.7 against 71.4 ms (all profiles/r04_leap_experiments.txt);
+//  * the lane's spline knots staged in LDS, at most 8 per actuator (the round-1..3 layout), and round 3's occupancy experiments on the cube-only instantiations -- the hand's
+//    arrays shrunk to stubs, the per-rollout LDS hidden from the compiler, a fixed register budget: DESIGN.md section 5.1, profiles/r03_leap_occupancy_experiment.txt;
+//  * the joint columns of the first slot's side-B link recomputed at every use instead of cached per step: 59.3 against 58.3 ms, the same iterates bit for bit
+//    (profiles/r05_leap_experiments.txt);
+//  * the kernel without its trace rows, a probe of what re-rolling the E <= 5 elites instead would save in this launch: profiles/r05_trace_ab.txt;
+//  * the cube's rotation solved in the body frame (rotation columns (R e_q) x r, a 3 x 3 product wherever they are used): 58.0-58.2 against 57.5-57.6 ms; the hand-capable
+//    copy's chain part with an exec-masked region per joint and per coupling, or with the coupling of a contact off the cube added as zeros (profiles/r06_experiments.txt);
+//  * the hand's broad phase with one box-test pass per 16 body PAIRS (7 or 8 passes, a few lanes each) and one level-2 trip per near geom of side A with only B's near lanes at
+//    work: the same candidate list entry for entry, in more and emptier passes (profiles/leap_broad_phase.md).
+
+// ---- tuning constants
+constexpr int LSMAX = 16;           // slope evaluations per line search at the most (12 and 20: no gain, profiles/r06_experiments.txt)
+constexpr int WAVES_PER_EU = 2;     // the kernel's launch bound: the register budget of two waves per SIMD
+constexpr int WAVES_PER_BLOCK = 4;  // waves per workgroup: they share one LDS copy of the model image and nothing else
+constexpr int BFS = 33;             // row stride of the LDS copy of the body records (BODY_F = 32 floats each): odd, the four chains' rows in different banks
+constexpr int PAS = 9;              // row stride of S.pa
+constexpr int RSPAD = 4;            // floats behind an RS record (see its last member)
+constexpr int C3PAD = 278;          // floats in front of the c3 cache inside the pool's storage (see RS)
+constexpr int NSLDS = 3;            // slots per lane whose contacts the LDS pool holds
+constexpr double BIGPROB = 0.999999;  // how sure the compiler may be that a wave-step stays on the NSLOT copy (block frequencies steer the placement of register spills)
+constexpr int CVX_STOP_NM = 1000;   // the stop of the cylinder build's GJK + EPA in nanometres (jh_coop.h: 1 000 = CVX_TOL, the tree kernel's); profiles/caltech_cylinder.md has 1 000 against 100
 // Waves of a workgroup never exchange data after the image is staged: inside the step loop a "barrier" only has to order one wave's own LDS traffic
 // (a wave's LDS instructions execute in issue order), so it is a compiler fence, not an s_barrier -- rollouts in different waves never wait for each other.
 // OPAQUE(x): the compiler forgets what it knows about x, so nothing derived from it is hoisted out of the enclosing loop.  Used on the contact slots at the top of
 // every Newton iteration: otherwise the slots' Jacobian columns, lever arms and LDS addresses (all invariant over the iterations) are computed once before
 // the loop, do not fit in the register file and are spilled and reloaded in every iteration.
 #define OPAQUE(x) asm volatile("" : "+v"(x))
-#ifndef JH_V5_RSPAD
-#define JH_V5_RSPAD 4
-#endif
-#ifndef JH_V5_LCN
-#define JH_V5_LCN 25
-#endif
-#ifndef JH_V5_BFS
-#define JH_V5_BFS 33   // row stride of the LDS copy of the body records (BODY_F = 32 floats each): odd, the four chains' rows in different banks
-#endif
-#ifndef JH_V5_PAS
-#define JH_V5_PAS 9    // row stride of S.pa
-#endif
-#ifndef JH_V5_PARK
-#define JH_V5_PARK 1
-#endif
-#ifndef JH_V5_OPAQUE_LANE
-#define JH_V5_OPAQUE_LANE 1
-#endif
-#ifndef JH_V5_OPAQUE
-#define JH_V5_OPAQUE -1  // -1: per instantiation (2 for both since round 4's -fno-slp-vectorize build: 71.4 against 72.9 ms with 3; rounds 2-3: 3 with the hand's own contacts); 0 = off, 1 = the sides, 2 = + lever arm, 3 = + frame,
-                         // 4 = 3 and again before the Hessian assembly and before the line search
-#endif
 #define WSYNC() do { __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront"); __builtin_amdgcn_wave_barrier(); __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront"); } while (0)
 #ifndef JH_V5_NSLOT
 #define JH_V5_NSLOT 2
 #endif
-#ifndef JH_V5_BIGPROB
-#define JH_V5_BIGPROB 0.999999  // how sure the compiler may be that a wave-step stays on the NSLOT copy (block frequencies steer the placement of register spills)
-#endif
 #ifndef JH_V5_NSBIG
 #define JH_V5_NSBIG 3  // 4: 64 contacts, the 16 above the LDS pool in a row of global memory (as jh_engine_v6.hip does): 0 instead of 1.7e-6 contacts dropped per rollout-step on the
                        // recorded headline inputs and 97 % instead of 91 % of the jammed-cube sweep inside the capacity, for +2.8 % on every plan step (81.0 against 78.8 ms): not the default
-#endif
-#ifndef JH_V5_NS1
-#define JH_V5_NS1 0  // 1: a third copy of the constraint rows + Newton solver with ONE slot per lane for the wave-steps in which no rollout of the wave has more than 16 contacts.
-                     // Measured in round 4 (recorded inputs; profiles/r04_leap_experiments.txt): 93 % of the wave-steps qualify (5.2 contacts per rollout-step on average, the
-                     // wave's maximum 8.2), and the kernel is 1.1 % faster (79.7 against 80.6 ms) -- the second slot's code is skipped by wave-uniform branches already -- while the
-                     // bits of a rollout then depend on its wave-mates (the copies contract differently; test_leap_full_size_properties fails).  Off.
-#endif
-#ifndef JH_V5_NS1PROB
-#define JH_V5_NS1PROB 0.5
 #endif
 #ifndef JH_V5_CYL
 #define JH_V5_CYL 0  // 1 (jh_engine_v5_cyl.hip): the build for an image that keeps caltech_leap_cube's fingertip cylinders (geom type 5: radius, half length along the geom's z).
                      // Sphere against cylinder is MuJoCo's primitive; box and cylinder against cylinder go through the bounded fp32 GJK + EPA of jh_coop.h, a call that is
                      // not inlined and keeps its polytope in the lane's private memory -- behind a test that only a lane with such a pair passes.  0: no line of it is compiled.
 #endif
-#ifndef JH_V5_CVX_STOP_NM
-#define JH_V5_CVX_STOP_NM 1000  // the stop of this build's GJK + EPA in nanometres (jh_coop.h: 1 000 = CVX_TOL, the tree kernel's); profiles/caltech_cylinder.md has 1 000 against 100
-#endif
 constexpr int GCYL = 5;
 constexpr int NSLOT = JH_V5_NSLOT;  // contact slots per lane of the common case: steps with at most 16 * NSLOT contacts in every rollout of the wave
 constexpr int NSBIG = JH_V5_NSBIG;  // ... of the rare case (6e-4 of the rollout-steps of the headline workload): the wave runs a second copy of the solver with this many slots
-#ifndef JH_V5_NSLDS
-#define JH_V5_NSLDS 3
-#endif
-constexpr int NCP = 16 * (NSBIG < JH_V5_NSLDS ? NSBIG : JH_V5_NSLDS);  // contact pool per rollout in LDS
-constexpr int NCAP = 16 * NSBIG;                                          // contacts a rollout can hold: those above the LDS pool live in its row of the global overflow pool
+constexpr int NCP = 16 * (NSBIG < NSLDS ? NSBIG : NSLDS);  // contact pool per rollout in LDS
+constexpr int NCAP = 16 * NSBIG;                           // contacts a rollout can hold: those above the LDS pool live in its row of the global overflow pool
 constexpr int NOVF = NCAP - NCP;
-#ifndef JH_V5_MAXHIT
-#define JH_V5_MAXHIT 64
-#endif
-constexpr int MAXHIT = JH_V5_MAXHIT;  // broad-phase survivors (candidate geom pairs) per rollout and step; 16 bits each.  More than that are counted as dropped contacts
+constexpr int MAXHIT = 64;  // broad-phase survivors (candidate geom pairs) per rollout and step; 16 bits each.  More than that are counted as dropped contacts
 constexpr int POOL_F = 10;  // pos3, normal3, dist, mu, body, tran
 constexpr int MAXG = 80, MAXLG = 8;
 constexpr int CUBE = 17;          // contact side codes: 0 = static geometry, 1..16 = finger link (1 + 4*chain + depth), 17 = the cube
@@ -186,24 +119,12 @@ constexpr int NDH = 22 * 23 / 2;  // dense Hessian (packed lower) of a rollout w
 constexpr int NV = 22, NQ = 23, NU = 16, NS = 31, NS_CALTECH = 23, NX = 45, NMB = 17;
 constexpr int NBC = 20;  // hand bodies of the self-collision tables: 0 = static geometry, 1..16 = finger links, 17..19 = further groups of static geometry (engine_model.py)
 __device__ __forceinline__ bool static_code(int b) { return b == 0 || b >= NMB; }
-#ifndef JH_V5_KNOTS_LDS
-#define JH_V5_KNOTS_LDS 0  // 1: the round-1..3 layout (the lane's knots staged in LDS; at most JH_V5_MAXK of them)
-#endif
-#ifndef JH_V5_MAXK
-#define JH_V5_MAXK 8
-#endif
-constexpr int MAXK = JH_V5_MAXK;
 
 // per-lane model constants staged in LDS (index = lane & 15)
-enum { LC_DAMP = 0, LC_KVD, LC_KP, LC_KV, LC_CLO, LC_CHI, LC_CLIM, LC_FL, LC_FB, LC_FD, LC_INVW, LC_LIMITED, LC_LO, LC_HI, LC_LK, LC_LB, LC_SI, LC_IMCK = LC_SI + 5, LC_N = JH_V5_LCN };  // (LC_IMCK: 1 / (the cube's mass or inertia of dof l), lanes 0..5; zero elsewhere)  // (row stride of the LDS table: odd, so that the 16 lanes' rows start in 16 different banks)
+enum { LC_DAMP = 0, LC_KVD, LC_KP, LC_KV, LC_CLO, LC_CHI, LC_CLIM, LC_FL, LC_FB, LC_FD, LC_INVW, LC_LIMITED, LC_LO, LC_HI, LC_LK, LC_LB, LC_SI, LC_IMCK = LC_SI + 5, LC_N = 25 };  // (LC_IMCK: 1 / (the cube's mass or inertia of dof l), lanes 0..5; zero elsewhere)  // (row stride of the LDS table: odd, so that the 16 lanes' rows start in 16 different banks)
 
-#ifdef JH_V5_X_DIET  // occupancy experiments on the cube-only instantiations: the arrays only the hand's own contacts use shrink to stubs
-constexpr int RS_NBC = 1, RS_NBPL = 4, RS_NHX = 1, RS_NDH = 4;
-#else
-constexpr int RS_NBC = NBC, RS_NBPL = MAXBPL, RS_NHX = 6, RS_NDH = NDH;
-#endif
 struct __attribute__((aligned(16))) RS {  // per-rollout shared state in LDS
-  float pa[NMB][JH_V5_PAS];   // body origin (0..2) and joint axis in the world (4..6); odd row stride: lanes reading 16 different bodies hit 16 different banks
+  float pa[NMB][PAS];   // body origin (0..2) and joint axis in the world (4..6); odd row stride: lanes reading 16 different bodies hit 16 different banks
   float xR[NMB][9];
   float qv[NV], g[NV], p[NV], ws[NV];
   float acn[6];       // constraint-consistent cube acceleration of this step (every lane integrates the replicated cube state)
@@ -212,10 +133,10 @@ struct __attribute__((aligned(16))) RS {  // per-rollout shared state in LDS
   float cmd[4];      // the cube's mass and its three principal inertias: the diagonal of its mass block, next to rhs6 so that the Schur step's reads bring it along
   union {
     struct {
-      float bs[RS_NBC][4];   // bounding sphere of the hand bodies (0, 17.. = static geometry, 1..16 = finger links): world centre, radius (the centre is the
+      float bs[NBC][4];   // bounding sphere of the hand bodies (0, 17.. = static geometry, 1..16 = finger links): world centre, radius (the centre is the
                           // bounding box's too; its half sizes and axes come from the model image and the body rotation)
       unsigned short hits[MAXHIT];
-      unsigned char bpl[RS_NBPL];
+      unsigned char bpl[MAXBPL];
     };
     // the collision arrays are dead from the constraint rows on: the step-level state the Newton loop does not touch is parked here instead of being held in
     // registers (or spilled to scratch memory by the compiler) across the loop.  The joint velocity and the cube's velocity are in qv already.
@@ -223,22 +144,16 @@ struct __attribute__((aligned(16))) RS {  // per-rollout shared state in LDS
   };
   union {  // the contact pool is dead once every lane has loaded its slots; the Newton Hessian then reuses its storage
     float pool[NCP][POOL_F];
-    struct { float Hcc[21], Hbb[NCH][10], Hcb[NCH][24], Hx[RS_NHX][16]; };  // Hcb[c][j*6+q]: chain column j, cube row q; Hx[pidx(a,b)][ib*4+ia]: block (chain b, chain a)
-                                                                         // of a contact-coupled pair of chains a < b (hand self-collision)
-    struct { float Hd[RS_NDH], dinv[NV]; };                    // dense path (contacts between two finger chains): packed lower 22 x 22, reciprocal pivots
-#if JH_V5_C3CACHE
-    struct { float c3pad_[JH_V5_C3PAD]; float c3s[G][12]; };   // behind the Newton matrices (275 floats at most): the first slot's joint columns, per lane; 16-byte aligned rows (static_assert below)
-#endif
+    struct { float Hcc[21], Hbb[NCH][10], Hcb[NCH][24], Hx[6][16]; };  // Hcb[c][j*6+q]: chain column j, cube row q; Hx[pidx(a,b)][ib*4+ia]: block (chain b, chain a)
+                                                                       // of a contact-coupled pair of chains a < b (hand self-collision)
+    struct { float Hd[NDH], dinv[NV]; };                    // dense path (contacts between two finger chains): packed lower 22 x 22, reciprocal pivots
+    struct { float c3pad_[C3PAD]; float c3s[G][12]; };   // behind the Newton matrices (275 floats at most): the first slot's joint columns, per lane; 16-byte aligned rows (static_assert below)
   };
   int ncon, nhit;
-#if JH_V5_RSPAD > 0
-  float pad_[JH_V5_RSPAD];  // record size = 16 banks modulo 64: the same field of a wave's four rollouts starts in four disjoint groups of 16 banks
-#endif
+  float pad_[RSPAD];  // record size = 16 banks modulo 64: the same field of a wave's four rollouts starts in four disjoint groups of 16 banks
 };
 
-#if JH_V5_C3CACHE
-static_assert(offsetof(RS, c3s) % 16 == 0 && JH_V5_C3PAD >= RS_NDH + NV && sizeof(((RS*)nullptr)->c3pad_) + sizeof(((RS*)nullptr)->c3s) <= sizeof(((RS*)nullptr)->pool), "c3 cache: aligned rows behind the Newton matrices, inside the pool's storage");
-#endif
+static_assert(offsetof(RS, c3s) % 16 == 0 && C3PAD >= NDH + NV && sizeof(((RS*)nullptr)->c3pad_) + sizeof(((RS*)nullptr)->c3s) <= sizeof(((RS*)nullptr)->pool), "c3 cache: aligned rows behind the Newton matrices, inside the pool's storage");
 struct PoolCtx { RS* S; int* overflow; float* ovf; };  // ovf: this rollout's row of the global overflow pool (NOVF x POOL_F floats), or null
 
 __device__ __forceinline__ void push_contact(const PoolCtx& pc, const float* pos, const float* n, float dist, int body, float mu, float tran) {
@@ -308,14 +223,10 @@ __device__ __forceinline__ int wave_rowmax(int v) {  // the maximum over the wav
 }
 #endif
 
-// The three functions below visit the joints above a finger link.  JH_V5_LINKBATCH (round 4): all four joints of the chain are loaded and their columns
-// axis_j x (pos - anchor_j) computed UNCONDITIONALLY, the depth of the link only masks what is accumulated.  The per-joint form (`if (j <= dep) { load; compute; }`) put every
-// joint's LDS loads under its own exec mask, so each of them was a round trip of its own -- 50 of the 80 `s_waitcnt lgkmcnt(0)` of a Newton iteration sat in these loops;
-// the batched form waits once per call and has no branches (the wasted columns of the shallower links are cheaper than the waits).  Same expressions: same bits.
-#ifndef JH_V5_LINKBATCH
-#define JH_V5_LINKBATCH 1  // (with packed-fp32 code this was 4.5 % SLOWER -- 83.0 against 79.4 ms: the register pairs of the packed operands left no room for 24 joint floats at once;
-                           // without the SLP vectorizer it is 1-2.5 % faster: 72.2 against 72.9, and 70.0 against 71.8 ms in the adopted combination)
-#endif
+// The three functions below visit the joints above a finger link.  All four joints of the chain are loaded and their columns axis_j x (pos - anchor_j) computed
+// UNCONDITIONALLY (link_c3), the depth of the link only masks what is accumulated.  A per-joint form (`if (j <= dep) { load; compute; }`) puts every joint's LDS loads under
+// its own exec mask, so each of them is a round trip of its own -- 50 of the 80 `s_waitcnt lgkmcnt(0)` of a Newton iteration sat in these loops; the batched form waits once
+// per call and has no branches (the wasted columns of the shallower links are cheaper than the waits).  Same expressions: same bits.
 __device__ __forceinline__ void link_c3(const RS& S, int ch, const float* pos, float (*c3)[3]) {
 #pragma unroll
   for (int j = 0; j < NLK; j++) {
@@ -324,15 +235,14 @@ __device__ __forceinline__ void link_c3(const RS& S, int ch, const float* pos, f
     cross3(c3[j], pj + 4, rb);
   }
 }
-// velocity of the point `pos` carried by finger link `code` for the joint-rate vector `vec` (22-vector in LDS), times `sign`, added to w
-// (c3c: the lane's cached columns of this link and point, JH_V5_C3CACHE, or null)
 __device__ __forceinline__ void load_c3(const float* c3c, float (*c3)[3]) {
   const float4 a = *reinterpret_cast<const float4*>(c3c), b = *reinterpret_cast<const float4*>(c3c + 4), c = *reinterpret_cast<const float4*>(c3c + 8);
   c3[0][0] = a.x; c3[0][1] = a.y; c3[0][2] = a.z; c3[1][0] = a.w; c3[1][1] = b.x; c3[1][2] = b.y; c3[2][0] = b.z; c3[2][1] = b.w; c3[2][2] = c.x; c3[3][0] = c.y; c3[3][1] = c.z; c3[3][2] = c.w;
 }
+// velocity of the point `pos` carried by finger link `code` for the joint-rate vector `vec` (22-vector in LDS), times `sign`, added to w
+// (c3c: the lane's cached columns of this link and point -- the c3 cache, S.c3s -- or null)
 __device__ __forceinline__ void link_vel(const RS& S, int code, const float* pos, const float* vec, float sign, float* w, const float* c3c = nullptr) {
   const int ch = (code - 1) >> 2, dep = (code - 1) & 3;
-#if JH_V5_LINKBATCH
   float c3[NLK][3]; if (c3c) load_c3(c3c, c3); else link_c3(S, ch, pos, c3);
 #pragma unroll
   for (int j = 0; j < NLK; j++) {
@@ -340,56 +250,26 @@ __device__ __forceinline__ void link_vel(const RS& S, int code, const float* pos
     const float xj = j <= dep ? sign * vj : 0.f;
     w[0] = fmaf(c3[j][0], xj, w[0]); w[1] = fmaf(c3[j][1], xj, w[1]); w[2] = fmaf(c3[j][2], xj, w[2]);
   }
-#else
-#pragma unroll
-  for (int j = 0; j < NLK; j++) if (j <= dep) {
-    const float* pj = S.pa[1 + 4 * ch + j];
-    const float rb[3] = {pos[0] - pj[0], pos[1] - pj[1], pos[2] - pj[2]}; float c3[3];
-    cross3(c3, pj + 4, rb);
-    const float xj = sign * vec[6 + 4 * ch + j];
-    w[0] = fmaf(c3[0], xj, w[0]); w[1] = fmaf(c3[1], xj, w[1]); w[2] = fmaf(c3[2], xj, w[2]);
-  }
-#endif
 }
 // -J'F for the joints of finger link `code` (F = world force on side B; sign = +1 for side B, -1 for side A): LDS float atomics into g
 __device__ __forceinline__ void link_force(RS& S, int code, const float* pos, const float* Fw, float sign) {
   const int ch = (code - 1) >> 2, dep = (code - 1) & 3;
-#if JH_V5_LINKBATCH
   float c3[NLK][3]; link_c3(S, ch, pos, c3);
   float v[NLK];
 #pragma unroll
   for (int j = 0; j < NLK; j++) v[j] = -sign * dot3(c3[j], Fw);
 #pragma unroll
   for (int j = 0; j < NLK; j++) if (j <= dep) atomicAdd(&S.g[6 + 4 * ch + j], v[j]);
-#else
-#pragma unroll
-  for (int j = 0; j < NLK; j++) if (j <= dep) {
-    const float* pj = S.pa[1 + 4 * ch + j];
-    const float rb[3] = {pos[0] - pj[0], pos[1] - pj[1], pos[2] - pj[2]}; float c3[3];
-    cross3(c3, pj + 4, rb);
-    atomicAdd(&S.g[6 + 4 * ch + j], -sign * dot3(c3, Fw));
-  }
-#endif
 }
 // Jacobian columns (contact frame) of the joints of finger link `code`, times `sign`, added to Jb[j] (j = depth in the chain)
 __device__ __forceinline__ void link_cols(const RS& S, int code, const float* pos, const float* fr, float sign, float (*Jb)[3]) {
   const int ch = (code - 1) >> 2, dep = (code - 1) & 3;
-#if JH_V5_LINKBATCH
   float c3[NLK][3]; link_c3(S, ch, pos, c3);
 #pragma unroll
   for (int j = 0; j < NLK; j++) {
     const float sg = j <= dep ? sign : 0.f;
     Jb[j][0] = fmaf(sg, dot3(fr, c3[j]), Jb[j][0]); Jb[j][1] = fmaf(sg, dot3(fr + 3, c3[j]), Jb[j][1]); Jb[j][2] = fmaf(sg, dot3(fr + 6, c3[j]), Jb[j][2]);
   }
-#else
-#pragma unroll
-  for (int j = 0; j < NLK; j++) if (j <= dep) {
-    const float* pj = S.pa[1 + 4 * ch + j];
-    const float rb[3] = {pos[0] - pj[0], pos[1] - pj[1], pos[2] - pj[2]}; float c3[3];
-    cross3(c3, pj + 4, rb);
-    Jb[j][0] = fmaf(sign, dot3(fr, c3), Jb[j][0]); Jb[j][1] = fmaf(sign, dot3(fr + 3, c3), Jb[j][1]); Jb[j][2] = fmaf(sign, dot3(fr + 6, c3), Jb[j][2]);
-  }
-#endif
 }
 
 // contact-frame image of the relative point velocity (side B minus side A) for the generalised velocity whose cube part is (xl = linear, world;
@@ -560,12 +440,7 @@ __device__ __forceinline__ bool chain_elim_order(int cmask, int c, int& level, i
 // arithmetic on kernel arguments and blockIdx.y alone: the bases stay in SGPRs, and a rollout's code below is the single launch's.  The other instantiations ignore the
 // two strides and compile to the code they had without them.
 template <bool MATERIALIZE, int WPB, bool SELF, bool PERSIST = false, bool BATCH = false>
-#ifdef JH_V5_NUM_VGPR  // (occupancy experiments: a register budget independent of what the LDS footprint allows)
-#define JH_V5_REGATTR __attribute__((amdgpu_num_vgpr(JH_V5_NUM_VGPR)))
-#else
-#define JH_V5_REGATTR
-#endif
-__global__ __launch_bounds__(WAVE * WPB, JH_V5_WAVES_PER_EU) JH_V5_REGATTR void k_leap_v5(const float* __restrict__ gF, const int* __restrict__ gI, const float* __restrict__ x0, int x0_batched,
+__global__ __launch_bounds__(WAVE * WPB, WAVES_PER_EU) void k_leap_v5(const float* __restrict__ gF, const int* __restrict__ gI, const float* __restrict__ x0, int x0_batched,
                                                    const float* __restrict__ nominal, const float* __restrict__ noise, int ldn,
                                                    const float* __restrict__ sigma, const float* __restrict__ W, const float* __restrict__ lohi,
                                                    const float* __restrict__ tp, int N, int n_offset, int H, int K, float* __restrict__ costs,
@@ -580,13 +455,8 @@ __global__ __launch_bounds__(WAVE * WPB, JH_V5_WAVES_PER_EU) JH_V5_REGATTR void 
     if (trace) trace += pb * N * H * 15;
     if (NOVF > 0 && ovf_all) ovf_all += pb * N * (NOVF * POOL_F);  // (the overflow rows are indexed by rollout: a problem's N rows behind the one before)
   }
-#ifdef JH_V5_X_DYNRS  // (occupancy experiments: the compiler does not see the per-rollout LDS, so the register budget follows JH_V5_WAVES_PER_EU alone)
-  extern __shared__ __attribute__((aligned(16))) unsigned char dynRS[];
-  RS* sRS = reinterpret_cast<RS*>(dynRS);
-#else
   __shared__ RS sRS[RPW * WPB];
-#endif
-  __shared__ float sBody[16 * JH_V5_BFS];
+  __shared__ float sBody[16 * BFS];
   __shared__ float sTp[16];
   __shared__ float sGeomF[MAXG * GEOM_F];
   __shared__ int sGeomI[MAXG * GEOM_I];
@@ -595,9 +465,6 @@ __global__ __launch_bounds__(WAVE * WPB, JH_V5_WAVES_PER_EU) JH_V5_REGATTR void 
   __shared__ int sBP[SELF ? 2 * MAXBP : 4];    // hand body pairs (side A, side B): every geom of A is a candidate against every geom of B
   __shared__ int sBG[SELF ? 2 * NBC : 4];    // per hand body: first collision geom, number of geoms (contiguous in the geom table)
   __shared__ float sBB[SELF ? NBC * 8 : 4];  // per hand body: bounding-box centre (body frame; static geometry: world), bounding radius, half sizes
-#if JH_V5_KNOTS_LDS
-  __shared__ float sKnAll[MAXK * WAVE * WPB];
-#endif
   __shared__ int sGrp[WPB];  // PERSIST: the group each wave is running (re-read in the step loop instead of held in a register; unused and dropped otherwise)
   const int dshift = PERSIST ? 0 : dshift_;  // (the queue is for launches that fill the GPU: never the latency mode)
 #ifdef JH_V5_WAVESTAMP  // diagnostic builds (tools/diag/wave_schedule.py): per group of four rollouts, the 100 MHz wall clock at the wave's entry, after the staging barrier, at the
@@ -607,15 +474,12 @@ __global__ __launch_bounds__(WAVE * WPB, JH_V5_WAVES_PER_EU) JH_V5_REGATTR void 
   const int tid = threadIdx.x, wv = tid >> 6, lane = tid & 63, r = lane >> 4;
   int l = lane & 15, c = l >> 2, s = l & 3;  // (not const: see the top of the step loop)
   RS& S = sRS[wv * RPW + r];
-#if JH_V5_KNOTS_LDS
-  float* sKn = sKnAll + wv * (MAXK * WAVE);
-#endif
   const int nmI = gI[0], nblkI = gI[1], nuI = gI[4], ngI = gI[5], nsiteI = gI[6], nsI = gI[7], oRef = gI[18];
   const int oBodyF = HEADER_F, oDofF = oBodyF + nmI * BODY_F, oActF = oDofF + gI[2] * DOF_F, oGeomF = oActF + nuI * ACT_F, oSiteF = oGeomF + ngI * GEOM_F;
   const int oGeomI = HEADER_I + nmI * BODY_I + nblkI * BLOCK_I + nuI * ACT_I, oSiteI = oGeomI + ngI * GEOM_I;
   const int oLane = gI[11], lgm = gI[12];
   const int oBP = gI[15], oBS = gI[16], nBP = gI[17], oBG = oBP + 2 * nBP;  // hand self-collision: body pairs, body bounding volumes, per-body geom ranges
-  for (int i = tid; i < 16 * BODY_F; i += WAVE * WPB) sBody[(i / BODY_F) * JH_V5_BFS + i % BODY_F] = gF[oBodyF + BODY_F + i];
+  for (int i = tid; i < 16 * BODY_F; i += WAVE * WPB) sBody[(i / BODY_F) * BFS + i % BODY_F] = gF[oBodyF + BODY_F + i];
   for (int i = tid; i < ngI * GEOM_F; i += WAVE * WPB) sGeomF[i] = gF[oGeomF + i];
   for (int i = tid; i < ngI * GEOM_I; i += WAVE * WPB) sGeomI[i] = gI[oGeomI + i];
   for (int i = tid; i < 16 * lgm; i += WAVE * WPB) sLaneG[i] = gI[oLane + i];
@@ -681,9 +545,6 @@ __global__ __launch_bounds__(WAVE * WPB, JH_V5_WAVES_PER_EU) JH_V5_REGATTR void 
     return jh_clampf(v, lohi[ll], lohi[NU + ll]);
   };
   if (!MATERIALIZE) {
-#if JH_V5_KNOTS_LDS
-    for (int k = 0; k < MAXK; k++) sKn[k * WAVE + lane] = k < K ? knot_at(k, l, nc) : 0.f;
-#endif
     if (knots_out && live) for (int k = 0; k < K; k++) knots_out[(size_t)(k * NU + l) * ldn + n] = knot_at(k, l, nc);
   }
   S.ws[6 + l] = 0.f; if (l < 6) S.ws[l] = 0.f;
@@ -703,7 +564,7 @@ __global__ __launch_bounds__(WAVE * WPB, JH_V5_WAVES_PER_EU) JH_V5_REGATTR void 
   int cnt_dense = 0, cnt_it = 0, cnt_l2 = 0, cnt_bp = 0, cnt_hh = 0, cnt_cls[4] = {0, 0, 0, 0};
   // the broad phase's lane use (tools/diag/count_broadphase.py; profiles/leap_broad_phase.md), stats[34..53].  Sums over rollout-steps (R) or wave-steps (W), maxima (M):
   // 34 R sphere survivors of level 1, 35 W their maximum over the wave, 36 W the maximum of the box survivors, 37 W passes of 16 body pairs with a sphere survivor (= runs of the
-  // box region in the per-pair form), 38 W ceil(35 / 16) (= runs in the list form), 39 W trips of the per-geom loop of level 2 (b), 40 R body pairs that reach (b), 41 R their
+  // box region in the per-pair form), 38 W ceil(35 / 16) (= runs in the list form), 39 W trips of a loop over the near geoms of side A in level 2 (b) (the form before the combination passes: stays zero), 40 R body pairs that reach (b), 41 R their
   // combinations T = near A x near B, 42 W passes of 16 combinations, 43 W geom slots of the cube's sweep with a lane in the box region, 44 lanes in it, 45 M sphere survivors,
   // 46 M box survivors, 47 M T, 48 R steps without a sphere survivor, 49 / 50 R pairs in (b) with one near geom on side A / B, 51 R trips a rollout needs by itself,
   // 52 R steps with more than MAXBPL sphere survivors, 53 M MAXBP - sphere survivors (the fewest seen)
@@ -721,27 +582,21 @@ __global__ __launch_bounds__(WAVE * WPB, JH_V5_WAVES_PER_EU) JH_V5_REGATTR void 
   }
 
   for (int hh = 0; hh < H; hh++) {
-#if JH_V5_OPAQUE_LANE
     // the model constants of a lane (sBody, sLane, ...) do not change over the steps: left alone the compiler loads them once before the loop, runs out of
     // registers and reloads them from scratch memory in every step instead of from LDS
     OPAQUE(l); c = l >> 2; s = l & 3;
     const float* lc = sLane + l * LC_N;
-#endif
     // ================================================================ controls
     float u;
     if (MATERIALIZE) u = controls[((size_t)nc * H + hh) * NU + l];
     else {
       u = 0.f;
-#if JH_V5_KNOTS_LDS
-      for (int k = 0; k < K && k < MAXK; k++) u = fmaf(W[hh * K + k], sKn[k * WAVE + lane], u);
-#else
       {  // (the rollout index is recomputed from an opaque copy of the lane id: held across the step loop it would cost a register the loop does not have)
         int lo_ = lane; OPAQUE(lo_);
         const int g_ = PERSIST ? sGrp[wv] : (int)(blockIdx.x * WPB + wv);
         const int n_ = (g_ << (2 - dshift)) + ((lo_ >> 4) >> dshift), nc_ = n_ < N ? n_ : N - 1;
         for (int k = 0; k < K; k++) u = fmaf(W[hh * K + k], knot_at(k, l, nc_), u);
       }
-#endif
     }
     // ================================================================ kinematics (each lane walks its chain up to its own link)
     float Mrow[NLK], fs_own, a0_own;
@@ -755,7 +610,7 @@ __global__ __launch_bounds__(WAVE * WPB, JH_V5_WAVES_PER_EU) JH_V5_REGATTR void 
         float sn_own, cs_own; sincosf(q, &sn_own, &cs_own);
 #pragma unroll
         for (int j = 0; j < NLK; j++) {
-          const float* bf = sBody + (4 * c + j) * JH_V5_BFS;
+          const float* bf = sBody + (4 * c + j) * BFS;
           float P2[3], R0[9];
           if (j == 0) { for (int k = 0; k < 3; k++) P2[k] = bf[BF_LPOS + k]; for (int k = 0; k < 9; k++) R0[k] = bf[BF_LR + k]; }
           else { mulMV(P2, R, bf + BF_LPOS); for (int k = 0; k < 3; k++) P2[k] += P[k]; mulMM(R0, R, bf + BF_LR); }
@@ -775,7 +630,6 @@ __global__ __launch_bounds__(WAVE * WPB, JH_V5_WAVES_PER_EU) JH_V5_REGATTR void 
       }
       // fused mode with a trace buffer (jh_rollout_cost_traced): the five trace sites of this forward pass -- what the materialise mode writes as sensors 16..30 --
       // for EVERY rollout: 60 B per rollout-step, 250 MB per plan step of the headline workload, and `Controller.traces` becomes a gather instead of a re-rollout
-#ifndef JH_V5_X_NOTRACE  // (A/B probe, profiles/r05_trace_ab.txt: the kernel without its trace rows -- what re-rolling the E <= 5 elites instead would save in this launch)
       if (!MATERIALIZE && trace && nsI == NS) {
         WSYNC();
         if (live && l < nsiteI && l < 5) {
@@ -784,7 +638,6 @@ __global__ __launch_bounds__(WAVE * WPB, JH_V5_WAVES_PER_EU) JH_V5_REGATTR void 
           for (int k = 0; k < 3; k++) tr[k] = p3[k] + S.pa[b][k];
         }
       }
-#endif
       // sensors of this forward pass (materialise mode): 16 joint positions, then 5 site positions
       if (MATERIALIZE && sensors) {
         float* y = sensors + ((size_t)nc * H + hh) * nsI;
@@ -807,7 +660,7 @@ __global__ __launch_bounds__(WAVE * WPB, JH_V5_WAVES_PER_EU) JH_V5_REGATTR void 
       }
       // ================================================================ chain dynamics: inertia block, bias, smooth force
       {
-        const float* bf = sBody + (4 * c + s) * JH_V5_BFS;
+        const float* bf = sBody + (4 * c + s) * BFS;
         float Rk[9], rr[3], cs3[3]; mulMM(Rk, Rown, bf + BF_IR); mulMV(rr, Rown, bf + BF_IPOS);
         for (int k = 0; k < 3; k++) cs3[k] = pown[k] + rr[k];
         const float mass = bf[BF_MASS]; const float* di = bf + BF_INERTIA;
@@ -872,12 +725,8 @@ __global__ __launch_bounds__(WAVE * WPB, JH_V5_WAVES_PER_EU) JH_V5_REGATTR void 
     float a0c_own = 0.f;
     {
       float Icw[3] = {cI[0] * vc[3], cI[1] * vc[4], cI[2] * vc[5]}, gc[3]; cross3(gc, vc + 3, Icw);
-#if JH_V5_WORLDROT
-      (void)gc;  // isotropic inertia: w x (I w) = 0 exactly -- the body-frame expression only carries its own rounding noise
+      (void)gc;  // isotropic inertia (model_is_leap): w x (I w) = 0 exactly -- the body-frame expression only carries its own rounding noise
       a0c_own = l < 3 ? (l == 0 ? grav[0] : (l == 1 ? grav[1] : grav[2])) : 0.f;
-#else
-      a0c_own = l < 3 ? (l == 0 ? grav[0] : (l == 1 ? grav[1] : grav[2])) : (l == 3 ? -gc[0] / cI[0] : (l == 4 ? -gc[1] / cI[1] : (l == 5 ? -gc[2] / cI[2] : 0.f)));
-#endif
     }
     WSYNC();
     V5_TICK(0)
@@ -941,7 +790,6 @@ __global__ __launch_bounds__(WAVE * WPB, JH_V5_WAVES_PER_EU) JH_V5_REGATTR void 
       WSYNC();
       V5_TICK(13)  // (fine split of the broad phase: 13 = the cube against the lane's geoms, 14 = hand body pairs, 1 = geom level of the surviving pairs)
       if constexpr (SELF) {
-#ifndef JH_V5_X_NOL1
       // hand self-collision, level 1: body pairs whose bounding spheres overlap (106 candidate pairs after MuJoCo's static filters, 16 per pass)
       int nbl = 0;
       {
@@ -967,7 +815,9 @@ __global__ __launch_bounds__(WAVE * WPB, JH_V5_WAVES_PER_EU) JH_V5_REGATTR void 
           if (lane == 0) { V5_CADD(CB_SPHMAX, nsm); V5_CADD(CB_L1PAIRPASS, npass); V5_CADD(CB_L1LISTPASS, (nsm + G - 1) / G); }
         }
 #endif
-#if JH_V5_L1LIST
+        // The candidate list S.hits[] of a rollout and step is the one a plain loop over the pairs would build, entry for entry and in the same order: the same tests on the
+        // same operands, only on other lanes and in fewer, fuller passes (profiles/leap_broad_phase.md).  Level 1 is list-driven: the sphere survivors are written out in
+        // ascending order, and the oriented-box test runs over that list 16 entries per pass instead of once per pass of 16 body pairs with a few lanes each.
         // the sphere survivors in ascending pair order -> S.bpl.  The list can hold every pair of the model (up to MAXBP), S.bpl MAXBPL of them: the tail goes to the contact
         // pool's storage, which nothing uses between the Newton solve of the last step and this step's narrow phase
         unsigned char* const tail = reinterpret_cast<unsigned char*>(&S.pool[0][0]);
@@ -1002,25 +852,6 @@ __global__ __launch_bounds__(WAVE * WPB, JH_V5_WAVES_PER_EU) JH_V5_REGATTR void 
           nbl += __popc(m16);
           WSYNC();
         }
-#else
-#pragma unroll
-        for (int i = 0; i < NPASS; i++) {
-          if (i * G >= nBP) break;
-          const int pi = i * G + l;
-          bool hit = (sph >> i) & 1u;
-          if (hit) {  // the two bodies' bounding boxes (static geometry: axis-aligned in the world)
-            const int ba = pab[i] & 0xFF, bb = pab[i] >> 8;
-            const float* sa = S.bs[ba]; const float* sb = S.bs[bb];
-            const float I9[9] = {1, 0, 0, 0, 1, 0, 0, 0, 1};
-            float Ra[9]; for (int k = 0; k < 9; k++) Ra[k] = static_code(ba) ? I9[k] : S.xR[ba][k];  // (side A is the static one of a pair, if any)
-            hit = obb_face_overlap(sa, Ra, sBB + 8 * ba + 4, sb, S.xR[bb], sBB + 8 * bb + 4);
-          }
-          unsigned m16 = (unsigned)((__ballot(hit) >> (16 * r)) & 0xFFFFull);
-          int pos = nbl + __popc(m16 & ((1u << l) - 1u));
-          if (hit && pos < MAXBPL) S.bpl[pos] = (unsigned char)pi;
-          nbl += __popc(m16);
-        }
-#endif
       }
 #ifdef JH_V5_COUNT
       { const int nbm = wave_rowmax(nbl); if (lane == 0) V5_CADD(CB_BOXMAX, nbm); if (l == 0 && live) V5_CMAX(CB_MBOX, nbl); }
@@ -1067,9 +898,8 @@ __global__ __launch_bounds__(WAVE * WPB, JH_V5_WAVES_PER_EU) JH_V5_REGATTR void 
           if (l == 0 && live && T != 0) { V5_CADD(CB_BPAIRS, 1); V5_CADD(CB_T, T); V5_CMAX(CB_MT, T); V5_CADD(CB_ONEA, __popc(mA) == 1); V5_CADD(CB_ONEB, nB == 1); V5_CADD(CB_OWNTRIPS, __popc(mA)); }
         }
 #endif
-#if JH_V5_L2COMBO
-        // combination t = ia' * nB + ib' (ia', ib': ranks among the near geoms of A and of B) goes to lane t mod 16 of pass t / 16: ascending t is ascending geom of A, then
-        // ascending geom of B -- the order in which the per-geom loop appended its survivors.  t / nB without a division: t < 256, nB <= 16, and (t + 0.5) / nB lies at least
+        // (b) runs one lane per (near geom of A, near geom of B) combination, 16 per pass: combination t = ia' * nB + ib' (ia', ib': ranks among the near geoms of A and of B)
+        // goes to lane t mod 16 of pass t / 16: ascending t is ascending geom of A, then ascending geom of B -- the order in which a loop over A's near geoms appends its survivors.  t / nB without a division: t < 256, nB <= 16, and (t + 0.5) / nB lies at least
         // 1 / 32 from an integer, far above the error of the reciprocal
         const float rnB = __builtin_amdgcn_rcpf((float)nB);
         for (int t = l; __any(t - l < T); t += G) {
@@ -1078,17 +908,6 @@ __global__ __launch_bounds__(WAVE * WPB, JH_V5_WAVES_PER_EU) JH_V5_REGATTR void 
           if (t < T) {
             const int ra = (int)(((float)t + 0.5f) * rnB), rb = t - ra * nB;
             ga = ga0 + nth_bit16(mA, ra); gb = gb0 + nth_bit16(mB, rb);
-#else
-        unsigned rem = mA;
-        while (__any(rem != 0)) {
-#ifdef JH_V5_COUNT
-          if (lane == 0) V5_CADD(CB_TRIPS, 1);
-#endif
-          const int ia = rem != 0 ? __ffs(rem) - 1 : 0;
-          bool hit = false;
-          const int ga = ga0 + ia, gb = gb0 + l;
-          if (rem != 0 && l < nb && ((mB >> l) & 1u)) {
-#endif
             const float* fa = sGeomF + ga * GEOM_F; const float* fb = sGeomF + gb * GEOM_F;
             float ca[3], cb[3];
             if (static_code(ba)) { ca[0] = fa[GF_POS]; ca[1] = fa[GF_POS + 1]; ca[2] = fa[GF_POS + 2]; }
@@ -1116,16 +935,12 @@ __global__ __launch_bounds__(WAVE * WPB, JH_V5_WAVES_PER_EU) JH_V5_REGATTR void 
           const int pos = nh + __popc(h16 & ((1u << l) - 1u));
           if (hit && pos < MAXHIT) S.hits[pos] = (unsigned short)(HITPAIR + (ga << 7 | gb));
           nh += __popc(h16);
-#if !JH_V5_L2COMBO
-          rem &= rem - 1u;
-#endif
         }
       }
 #ifdef JH_V5_COUNT
       if (l == 0 && live) cnt_hh += nh - nh_cube;
 #endif
       hand_hits = nh > nh_cube;
-#endif
       }
       if (nh > MAXHIT) { if (l == 0 && live && stats) atomicAdd(stats, nh - MAXHIT); nh = MAXHIT; }  // (candidate pairs lost: counted with the dropped contacts)
       WSYNC();
@@ -1175,7 +990,7 @@ __global__ __launch_bounds__(WAVE * WPB, JH_V5_WAVES_PER_EU) JH_V5_REGATTR void 
               for (int k = 0; k < 3; k++) { X.p[k] = swap ? pB[k] : pA[k]; Y.p[k] = swap ? pA[k] : pB[k]; }
               for (int k = 0; k < 9; k++) { X.R[k] = swap ? RB[k] : RA[k]; Y.R[k] = swap ? RA[k] : RB[k]; }
               CvxOne one{{0.f, 0.f, 0.f}, {0.f, 0.f, 0.f}, 0.f, false};
-              collide_convex_cylinder<CvxOne, true, JH_V5_CVX_STOP_NM>(one, X, Y);
+              collide_convex_cylinder<CvxOne, true, CVX_STOP_NM>(one, X, Y);
               if (one.hit) { sk.flip = swap; sk.push(one.pos, one.n, one.dist); }
             }
           } else
@@ -1219,7 +1034,7 @@ __global__ __launch_bounds__(WAVE * WPB, JH_V5_WAVES_PER_EU) JH_V5_REGATTR void 
       if (lane == 0) { atomicAdd(stats + 344 + min(Pw, 15), 1); atomicAdd(stats + 372 + min(cw, 11), 1); }
     }
 #endif
-    auto solve_step = [&](auto NS_, auto HC_) __attribute__((always_inline)) -> bool {
+    auto solve_step = [&](auto NS_, auto HC_) __attribute__((always_inline)) {
     constexpr bool HC = decltype(HC_)::value;  // hand contacts (a side that is not the cube) possible in this wave-step: false = the copy without their code (see the dispatch below)
     constexpr int NS = decltype(NS_)::value;
     const int ncap = (NOVF > 0 && (ovf_all == nullptr || n >= N) && 16 * NS > NCP) ? NCP : 16 * NS;  // (no overflow row: what the LDS pool holds)
@@ -1252,7 +1067,9 @@ __global__ __launch_bounds__(WAVE * WPB, JH_V5_WAVES_PER_EU) JH_V5_REGATTR void 
         }
       }
     }
-#if JH_V5_C3CACHE
+    // The c3 cache: the joint columns axis_j x (pos - anchor_j) of the FIRST slot's side-B link (12 floats per lane, invariant over the Newton iterations of a step) are computed
+    // once per step and kept in the part of the contact pool's storage the Newton matrices leave free (768 of 820 bytes): three ds_read_b128 per use instead of 24 loads +
+    // 36 multiply-adds, twice per iteration.
     // (every lane has loaded its slots: the pool's storage is free from here on -- a wave's LDS instructions execute in order)
     if (sl[0].la >= 0 && sl[0].lb > 0) {
       const float pos0[3] = {sl[0].rc[0] + qc[0], sl[0].rc[1] + qc[1], sl[0].rc[2] + qc[2]};
@@ -1261,9 +1078,6 @@ __global__ __launch_bounds__(WAVE * WPB, JH_V5_WAVES_PER_EU) JH_V5_REGATTR void 
       o[0] = make_float4(c3[0][0], c3[0][1], c3[0][2], c3[1][0]); o[1] = make_float4(c3[1][1], c3[1][2], c3[2][0], c3[2][1]); o[2] = make_float4(c3[2][2], c3[3][0], c3[3][1], c3[3][2]);
     }
 #define V5_C3C(k) ((k) == 0 ? (const float*)S.c3s[l] : (const float*)nullptr)
-#else
-#define V5_C3C(k) ((const float*)nullptr)
-#endif
     DofRows dr;
     dr.fl = lc[LC_FL]; dr.fD = lc[LC_FD]; dr.fR = dr.fD > 0.f ? 1.f / dr.fD : 0.f; dr.faref = -lc[LC_FB] * qd; dr.lims = 0.f; dr.laref = 0.f; dr.lD = 0.f; dr.jf = dr.jl = dr.pf = dr.pl = 0.f;
     if (lc[LC_LIMITED] != 0.f) {
@@ -1296,12 +1110,13 @@ __global__ __launch_bounds__(WAVE * WPB, JH_V5_WAVES_PER_EU) JH_V5_REGATTR void 
       }
 #endif
     }
-    if constexpr (HC && NS < NSLOT) { if (__any(dense_row)) return false; }  // (the one-slot copy has no dense direction: the wave takes the NSLOT copy; nothing was written yet)
-#if JH_V5_PARK
     S.pk_q[l] = q; S.pk_fs[l] = fs_own;
     if (l == 0) { S.pk_cq[0] = qc[3]; S.pk_cq[1] = qc[4]; S.pk_cq[2] = qc[5]; S.pk_cq[3] = qc[6]; S.pk_acc = acc; }
-#endif
     // ================================================================ Newton solver (rows distributed over the 16 lanes)
+    // The cube's three rotational dofs are solved for in WORLD coordinates (w = R w_body): with the cube's isotropic inertia (a cube: leap_cube, leap_cube_down,
+    // caltech_leap_cube; checked at model load) the quadratic term is the same in both frames, and the rotation columns of a contact become e_q x r -- two non-zeros each --
+    // instead of (R e_q) x r: no read of the cube's rotation matrix, no 3 x 3 product anywhere in a Newton iteration (gradient torque, Hessian columns, J p of the line
+    // search).  The warm start and the integrated acceleration stay in the body frame (MuJoCo's free-joint convention): two 3 x 3 products per STEP.
     const float Mdiag_own = sel4(Mrow, s), iMd = 1.f / Mdiag_own;
     const float fsc_own = mck * a0c_own;
     const float snorm = gsum(fs_own * fs_own * iMd + fsc_own * fsc_own * lc[LC_IMCK]);
@@ -1313,11 +1128,7 @@ __global__ __launch_bounds__(WAVE * WPB, JH_V5_WAVES_PER_EU) JH_V5_REGATTR void 
       {
         const float qws = S.ws[6 + l];
         float xl[3] = {S.ws[0], S.ws[1], S.ws[2]}, xr[3] = {S.ws[3], S.ws[4], S.ws[5]}, wa[3]; mulMV(wa, S.xR[0], xr);  // (S.ws keeps the body-frame acceleration of the last step)
-#if JH_V5_WORLDROT
         const float wsc_own = l < 3 ? S.ws[l] : (l == 3 ? wa[0] : (l == 4 ? wa[1] : (l == 5 ? wa[2] : 0.f)));
-#else
-        const float wsc_own = l < 6 ? S.ws[l] : 0.f;
-#endif
         float cs = 0.f, jx[3], jar_ws[NS][3];
 #pragma unroll
         for (int k = 0; k < NS; k++) if (sl[k].la >= 0) {
@@ -1337,11 +1148,7 @@ __global__ __launch_bounds__(WAVE * WPB, JH_V5_WAVES_PER_EU) JH_V5_REGATTR void 
         S.p[6 + l] = a0_own; if (l < 6) S.p[l] = a0c_own;
         WSYNC();
         float xl0[3] = {S.p[0], S.p[1], S.p[2]}, xr0[3] = {S.p[3], S.p[4], S.p[5]};
-#if JH_V5_WORLDROT
         wa[0] = xr0[0]; wa[1] = xr0[1]; wa[2] = xr0[2];
-#else
-        mulMV(wa, S.xR[0], xr0);
-#endif
         cs = 0.f;
 #pragma unroll
         for (int k = 0; k < NS; k++) if (sl[k].la >= 0) {
@@ -1364,16 +1171,9 @@ __global__ __launch_bounds__(WAVE * WPB, JH_V5_WAVES_PER_EU) JH_V5_REGATTR void 
       V5_TICK(3)
       // The Newton loop exists twice: waves in which some rollout needs the dense direction this step run the copy that contains it, all others a copy
       // without that code (the register needs of the rare path would otherwise make the allocator spill inside every iteration of every rollout)
-      constexpr int OPQ = JH_V5_OPAQUE >= 0 ? JH_V5_OPAQUE : 2;
-      auto forget_slots = [&]() __attribute__((always_inline)) {
-        if constexpr (OPQ > 0) {
+      auto forget_slots = [&]() __attribute__((always_inline)) {  // (the sides and the lever arm of every slot; not the frame: see the top of the file)
 #pragma unroll
-          for (int k = 0; k < NS; k++) {
-            OPAQUE(sl[k].la); OPAQUE(sl[k].lb);
-            if constexpr (OPQ > 1) { OPAQUE(sl[k].rc[0]); OPAQUE(sl[k].rc[1]); OPAQUE(sl[k].rc[2]); }
-            if constexpr (OPQ > 2) { for (int q9 = 0; q9 < 9; q9++) OPAQUE(sl[k].fr[q9]); }
-          }
-        }
+        for (int k = 0; k < NS; k++) { OPAQUE(sl[k].la); OPAQUE(sl[k].lb); OPAQUE(sl[k].rc[0]); OPAQUE(sl[k].rc[1]); OPAQUE(sl[k].rc[2]); }
       };
       auto newton_loop = [&](auto dense_tag) __attribute__((always_inline)) {
       constexpr bool DENSE = decltype(dense_tag)::value;
@@ -1451,20 +1251,12 @@ __global__ __launch_bounds__(WAVE * WPB, JH_V5_WAVES_PER_EU) JH_V5_REGATTR void 
             auto Amul = [&](const float* v, float* y) __attribute__((always_inline)) {
               y[0] = A[0] * v[0] + A[1] * v[1] + A[3] * v[2]; y[1] = A[1] * v[0] + A[2] * v[1] + A[4] * v[2]; y[2] = A[3] * v[0] + A[4] * v[1] + A[5] * v[2];
             };
-#if !JH_V5_WORLDROT
-            float cq[3][3];  // the cube's rotation columns (body axes x arm), up to the sign
-#endif
             if (cube) {
-#if JH_V5_WORLDROT
               float tb[3]; cross3(tb, t.rc, Fw);  // torque about the cube's origin, world
-#else
-              float tq[3], tb[3]; cross3(tq, t.rc, Fw); mulMTV(tb, S.xR[0], tq);
-#endif
               gcp[0] += Fw[0]; gcp[1] += Fw[1]; gcp[2] += Fw[2]; gcp[3] += tb[0]; gcp[4] += tb[1]; gcp[5] += tb[2];
               if (on) {
 #pragma unroll
                 for (int e = 0; e < 6; e++) hcp[e] += A[e];
-#if JH_V5_WORLDROT
                 // rotation columns e_q x r = (0, -rz, ry), (rz, 0, -rx), (-ry, rx, 0): z_q = A (e_q x r) is a combination of two columns of A, and a dot product with
                 // e_p x r has two terms
                 const float rx = t.rc[0], ry = t.rc[1], rz = t.rc[2];
@@ -1480,18 +1272,6 @@ __global__ __launch_bounds__(WAVE * WPB, JH_V5_WAVES_PER_EU) JH_V5_REGATTR void 
                 hcp[tri(3, 3)] += ry * zq[0][2] - rz * zq[0][1];
                 hcp[tri(4, 3)] += ry * zq[1][2] - rz * zq[1][1]; hcp[tri(4, 4)] += rz * zq[1][0] - rx * zq[1][2];
                 hcp[tri(5, 3)] += ry * zq[2][2] - rz * zq[2][1]; hcp[tri(5, 4)] += rz * zq[2][0] - rx * zq[2][2]; hcp[tri(5, 5)] += rx * zq[2][1] - ry * zq[2][0];
-#else
-#pragma unroll
-                for (int q = 0; q < 3; q++) { float ea[3]; col3(ea, S.xR[0], q); cross3(cq[q], ea, t.rc); }
-#pragma unroll
-                for (int q = 0; q < 3; q++) {
-                  float z[3]; Amul(cq[q], z);
-#pragma unroll
-                  for (int r2 = 0; r2 < 3; r2++) hcp[tri(3 + q, r2)] += z[r2];
-#pragma unroll
-                  for (int r2 = 0; r2 <= q; r2++) hcp[tri(3 + q, 3 + r2)] += dot3(cq[r2], z);
-                }
-#endif
                 hcany = true;
               }
             }
@@ -1513,18 +1293,12 @@ __global__ __launch_bounds__(WAVE * WPB, JH_V5_WAVES_PER_EU) JH_V5_REGATTR void 
                   for (int v4 = 0; v4 <= u4; v4++) atomicAdd(&S.Hbb[ch][tri(u4, v4)], dot3(cb[v4], y));
 #pragma unroll
                   for (int q = 0; q < 3; q++) atomicAdd(&S.Hcb[ch][u4 * 6 + q], -y[q]);
-#if JH_V5_WORLDROT
                   atomicAdd(&S.Hcb[ch][u4 * 6 + 3], t.rc[2] * y[1] - t.rc[1] * y[2]);  // -(e_q x r) . y
                   atomicAdd(&S.Hcb[ch][u4 * 6 + 4], t.rc[0] * y[2] - t.rc[2] * y[0]);
                   atomicAdd(&S.Hcb[ch][u4 * 6 + 5], t.rc[1] * y[0] - t.rc[0] * y[1]);
-#else
-#pragma unroll
-                  for (int q = 0; q < 3; q++) atomicAdd(&S.Hcb[ch][u4 * 6 + 3 + q], -dot3(cq[q], y));
-#endif
                 }
               } else {
-#if JH_V5_HCMERGE
-              // (round 6, the hand-capable copy as the other one: a joint's gradient entry, its row of the chain block and its coupling to the cube under ONE test per joint; the
+              // (the hand-capable copy as the other one: a joint's gradient entry, its row of the chain block and its coupling to the cube under ONE test per joint; the
               // coupling of a contact that is not the cube's is added as zeros instead of sitting in a nested exec-masked region per joint; the opposite force of a contact with both
               // sides in one chain -- rare -- behind one wave-uniform test.  The same values reach the same addresses in the same order.)
               float fjs[NLK];
@@ -1539,20 +1313,11 @@ __global__ __launch_bounds__(WAVE * WPB, JH_V5_WAVES_PER_EU) JH_V5_REGATTR void 
                     float y[3]; Amul(cb[u4], y);
 #pragma unroll
                     for (int v4 = 0; v4 <= u4; v4++) atomicAdd(&S.Hbb[ch][tri(u4, v4)], dot3(cb[v4], y));
-#if JH_V5_WORLDROT
                     const float hv[6] = {-y[0], -y[1], -y[2], t.rc[2] * y[1] - t.rc[1] * y[2], t.rc[0] * y[2] - t.rc[2] * y[0], t.rc[1] * y[0] - t.rc[0] * y[1]};  // -(e_q x r) . y
-#else
-                    const float hv[6] = {-y[0], -y[1], -y[2], -dot3(cq[0], y), -dot3(cq[1], y), -dot3(cq[2], y)};
-#endif
-#if JH_V5_HCMERGE > 1
-#pragma unroll
-                    for (int q = 0; q < 6; q++) atomicAdd(&S.Hcb[ch][u4 * 6 + q], cube ? hv[q] : 0.f);
-#else
                     if (cube) {
 #pragma unroll
                       for (int q = 0; q < 6; q++) atomicAdd(&S.Hcb[ch][u4 * 6 + q], hv[q]);
                     }
-#endif
                   }
                 }
               }
@@ -1560,36 +1325,6 @@ __global__ __launch_bounds__(WAVE * WPB, JH_V5_WAVES_PER_EU) JH_V5_REGATTR void 
 #pragma unroll
                 for (int j = 0; j < NLK; j++) if (same && j <= depa) atomicAdd(&S.g[6 + 4 * ch + j], fjs[j]);  // side A of the same chain: the opposite force
               }
-#else
-#pragma unroll
-              for (int j = 0; j < NLK; j++) {
-                const float fj = dot3(cb[j], Fw);
-                if (j <= dep) atomicAdd(&S.g[6 + 4 * ch + j], -fj);       // side B: -J'f
-                if (same && j <= depa) atomicAdd(&S.g[6 + 4 * ch + j], fj);  // side A of the same chain: the opposite force
-                const float sg = (j <= dep ? 1.f : 0.f) - ((same && j <= depa) ? 1.f : 0.f);
-                cb[j][0] *= sg; cb[j][1] *= sg; cb[j][2] *= sg;
-              }
-              if (on) {
-#pragma unroll
-                for (int u4 = 0; u4 < NLK; u4++) if (u4 <= dep) {
-                  float y[3]; Amul(cb[u4], y);
-#pragma unroll
-                  for (int v4 = 0; v4 <= u4; v4++) atomicAdd(&S.Hbb[ch][tri(u4, v4)], dot3(cb[v4], y));
-                  if (cube) {
-#pragma unroll
-                    for (int q = 0; q < 3; q++) atomicAdd(&S.Hcb[ch][u4 * 6 + q], -y[q]);
-#if JH_V5_WORLDROT
-                    atomicAdd(&S.Hcb[ch][u4 * 6 + 3], t.rc[2] * y[1] - t.rc[1] * y[2]);  // -(e_q x r) . y
-                    atomicAdd(&S.Hcb[ch][u4 * 6 + 4], t.rc[0] * y[2] - t.rc[2] * y[0]);
-                    atomicAdd(&S.Hcb[ch][u4 * 6 + 5], t.rc[1] * y[0] - t.rc[0] * y[1]);
-#else
-#pragma unroll
-                    for (int q = 0; q < 3; q++) atomicAdd(&S.Hcb[ch][u4 * 6 + 3 + q], -dot3(cq[q], y));
-#endif
-                  }
-                }
-              }
-#endif
               if (linkA && !same) {  // side A sits in another chain: its own block, and the pair's coupling block -Jb'W Ja in Hx (B's chain is always the higher one)
                 float ca[NLK][3]; link_c3(S, cha, pos, ca);
 #pragma unroll
@@ -1644,7 +1379,6 @@ __global__ __launch_bounds__(WAVE * WPB, JH_V5_WAVES_PER_EU) JH_V5_REGATTR void 
         n_wave_iters++;
         // ---- (3) Hessian: M + dof rows on the chain diagonals, cube inertia on Hcc, J'WJ of the contacts as atomics into the arrow blocks.  A rollout with a
         // contact between two finger chains has no arrow structure: its Hessian is assembled densely further down (aact = false here)
-        if constexpr (OPQ > 3) forget_slots();
         const bool aact = act && !(DENSE && dense_row);
         V5_TICK(5)
         // ---- (4) arrow factorisation: chain blocks first (each chain's 4 lanes redundantly); the coupling columns Y_q = L^-1 Hcb[:,q] are shared
@@ -1782,7 +1516,6 @@ __global__ __launch_bounds__(WAVE * WPB, JH_V5_WAVES_PER_EU) JH_V5_REGATTR void 
         WSYNC();
         // ---- (4b) dense path: rollouts with a contact between two finger chains (hand self-collision; rare).  H = M + J'WJ as a packed 22 x 22 matrix in
         // LDS, Cholesky by rows in registers and the two triangular solves with the rollout's 16 lanes (rows l and l + 16)
-#ifndef JH_V5_X_NODENSE
         if constexpr (HC && DENSE) {
 #ifdef JH_V5_COUNT
         if (lane == 0) { cnt_it++; cnt_dense += __any(act && dense_row) ? 1 : 0; }
@@ -1815,11 +1548,7 @@ __global__ __launch_bounds__(WAVE * WPB, JH_V5_WAVES_PER_EU) JH_V5_REGATTR void 
               n0 = 6;
               for (int q3 = 0; q3 < 3; q3++) {
                 X0[q3][0] = -t.fr[q3]; X0[q3][1] = -t.fr[3 + q3]; X0[q3][2] = -t.fr[6 + q3];
-#if JH_V5_WORLDROT
                 const float ea[3] = {q3 == 0 ? 1.f : 0.f, q3 == 1 ? 1.f : 0.f, q3 == 2 ? 1.f : 0.f}; float c3[3]; cross3(c3, ea, t.rc);
-#else
-                float ea[3], c3[3]; col3(ea, S.xR[0], q3); cross3(c3, ea, t.rc);
-#endif
                 X0[3 + q3][0] = -dot3(t.fr, c3); X0[3 + q3][1] = -dot3(t.fr + 3, c3); X0[3 + q3][2] = -dot3(t.fr + 6, c3);
               }
             } else if (t.la > 0) { o0 = 6 + 4 * ((t.la - 1) >> 2); n0 = 1 + ((t.la - 1) & 3); link_cols(S, t.la, pos, t.fr, -1.f, X0); }
@@ -1909,10 +1638,8 @@ __global__ __launch_bounds__(WAVE * WPB, JH_V5_WAVES_PER_EU) JH_V5_REGATTR void 
           }
         }
 }
-#endif
         V5_TICK(9)
         // ---- (5) exact line search along p
-        if constexpr (OPQ > 3) forget_slots();
         float Mp_own = 0.f;
 #pragma unroll
         for (int j = 0; j < NLK; j++) Mp_own += Mrow[j] * pc4[j];
@@ -1921,94 +1648,37 @@ __global__ __launch_bounds__(WAVE * WPB, JH_V5_WAVES_PER_EU) JH_V5_REGATTR void 
         const float gp = gsum(g_own * p_own + gcl * xcl);
         if (act && !(gp < 0.f)) act = false;
         {
-#if JH_V5_WORLDROT
           const float* wa = xc6 + 3;
-#else
-          float wa[3]; mulMV(wa, S.xR[0], xc6 + 3);
-#endif
 #pragma unroll
           for (int k = 0; k < NS; k++) {
-            if (!HC && JH_V5_C3CACHE && k == 0) { slot_Jx_first(sl[0], xc6, wa, S.p, sl[0].jp, V5_C3C(0)); continue; }
+            if (!HC && k == 0) { slot_Jx_first(sl[0], xc6, wa, S.p, sl[0].jp, V5_C3C(0)); continue; }
             if (k > 0 && !((used >> k) & 1u)) continue;  // (wave-uniform: nobody's slot k holds a contact)
             if (sl[k].la >= 0) slot_Jx<HC>(sl[k], S, qc, xc6, wa, S.p, sl[k].jp, V5_C3C(k));
           }
         }
         dr.pf = p_own; dr.pl = dr.lims * p_own;
-#if JH_V5_LSKINK
-        // Step lengths at which the slope of the 1-D cost (all but) JUMPS: the zero crossing of the own dof's friction-loss row, and for a contact the point where its
-        // tangential part passes closest to zero, if it gets there within JH_V5_LSREV of where it is at 0 or at 1 -- Coulomb friction reverses there, and with a cone as
-        // narrow as impratio = 100 makes it that is a jump.  A root of the slope AT such a jump is what the long searches of this workload were looking for (Newton from
-        // either side lands beyond the jump, inside the bracket, and the bracket shrinks by parts in a thousand per evaluation: 15 % of the wave's searches took 9 to 16
-        // evaluations, half of all its evaluations; CPU prototype: oracle/jo_engine.c::jo_set_ls_experiment, tools/proto/ls_experiment.py).  The search tries the candidate
-        // closest to the middle of the bracket whenever a Newton step leaves the bracket or an evaluation leaves more than JH_V5_LSSHRINK of it.
-        float kc[NS + 1];
-        kc[NS] = (dr.fl > 0.f && dr.pf != 0.f) ? -dr.jf * __frcp_rn(dr.pf) : -1.f;
-#pragma unroll
-        for (int k = 0; k < NS; k++) {
-          kc[k] = -1.f;
-          if (sl[k].la >= 0) {
-            const float U1 = sl[k].jar[1], U2 = sl[k].jar[2], V1 = sl[k].jp[1], V2 = sl[k].jp[2];  // (both tangential rows carry the same friction coefficient: it drops out)
-            const float vv = V1 * V1 + V2 * V2, uv = U1 * V1 + U2 * V2, uu = U1 * U1 + U2 * U2;
-            if (vv > 0.f) { const float a = -uv * __frcp_rn(vv); if (uu + a * uv <= JH_V5_LSREV * JH_V5_LSREV * fmaxf(uu, uu + 2.f * uv + vv)) kc[k] = a; }
-          }
-        }
-#endif
         V5_TICK(10)
         float lo = 0.f, hi = -1.f, alpha = 1.f; bool lsact = act;
 #ifdef JH_V5_CENSUS
         int cen_ls = 0, cen_lsw = 0; const bool cen_act = act;
         if (stats && lane == 0) atomicAdd(stats + 320 + __popcll(__ballot(act && l == 0)), 1);
 #endif
-        for (int ls = 0; ls < JH_V5_LSMAX && __any(lsact); ls++) {
+        for (int ls = 0; ls < LSMAX && __any(lsact); ls++) {
           float d1, d2;
 #ifdef JH_V5_CENSUS
           cen_ls += lsact; cen_lsw++;
 #endif
           lane_rows_dir<NS>(sl, dr, alpha, &d1, &d2, used);
           d1 = gsum(d1) + pMd + alpha * pMp; d2 = gsum(d2) + pMp;
-#if JH_V5_LSKINK
-          bool trouble = false; float nx = alpha;
-          if (lsact) {
-            if (fabsf(d1) <= lstol * fabsf(gp)) lsact = false;
-            else {
-              const float wprev = hi >= 0.f ? hi - lo : -1.f;
-              if (d1 < 0.f) lo = alpha; else hi = alpha;
-              nx = alpha - d1 * __frcp_rn(d2);
-              if (hi < 0.f) { if (nx <= lo) nx = 2.f * alpha; }
-              else {
-                const bool rejected = nx <= lo || nx >= hi;
-                trouble = rejected || (wprev > 0.f && hi - lo > JH_V5_LSSHRINK * wprev);
-                if (rejected) nx = 0.5f * (lo + hi);
-              }
-            }
-          }
-          if (__any(trouble)) {  // the candidate closest to the middle of the bracket, strictly inside it: |a - mid| with the side in the last mantissa bit, one row minimum
-            const float mid = 0.5f * (lo + hi), eps = 1e-6f * hi;
-            int key = 0x7f800000;
-#pragma unroll
-            for (int k = 0; k <= NS; k++) {
-              const float a = kc[k], dm = a - mid;
-              if (trouble && a > lo + eps && a < hi - eps) key = min(key, (__float_as_int(fabsf(dm)) & ~1) | (dm < 0.f ? 1 : 0));
-            }
-            key = gmini(trouble ? key : 0x7f800000);
-            if (trouble && key != 0x7f800000) { const float mag = __int_as_float(key & ~1); nx = (key & 1) ? mid - mag : mid + mag; }
-          }
-          if (lsact) alpha = nx;
-#else
           {  // safeguarded Newton step on the slope, as selects (round 6: the nested branches were a dozen exec-mask instructions per evaluation; the same arithmetic)
             const bool upd = lsact & !(fabsf(d1) <= lstol * fabsf(gp)), neg = d1 < 0.f;
             lo = (upd & neg) ? alpha : lo; hi = (upd & !neg) ? alpha : hi;
-#if JH_V5_LSRCP
-            float nx = alpha - d1 * __builtin_amdgcn_rcpf(d2);
-#else
-            float nx = alpha - d1 * __frcp_rn(d2);
-#endif
+            float nx = alpha - d1 * __builtin_amdgcn_rcpf(d2);  // (v_rcp_f32, 1 ulp: the correctly rounded division is 10 instructions per evaluation)
             const bool out_lo = nx <= lo, out_hi = nx >= hi;
             float dbl = 2.f * alpha, mid_ = 0.5f * (lo + hi); asm volatile("" : "+v"(dbl), "+v"(mid_));  // (both computed: selects, not branches)
             nx = hi < 0.f ? (out_lo ? dbl : nx) : ((out_lo | out_hi) ? mid_ : nx);
             alpha = upd ? nx : alpha; lsact = upd;
           }
-#endif
         }
 #ifdef JH_V5_CENSUS
         if (stats) { if (l == 0 && live && cen_act) atomicAdd(stats + 256 + min(cen_ls, 31), 1); if (lane == 0) atomicAdd(stats + 288 + min(cen_lsw, 31), 1); }
@@ -2033,39 +1703,27 @@ __global__ __launch_bounds__(WAVE * WPB, JH_V5_WAVES_PER_EU) JH_V5_REGATTR void 
       else newton_loop(std::false_type{});
       if (l == 0) { n_iters += iters_this; n_maxed += (iters_this >= cap); }
     }
-    return true;
     };
-    if (__builtin_expect_with_probability(NSBIG > NSLOT && __any(S.ncon > 16 * NSLOT), 0, JH_V5_BIGPROB)) {
+    if (__builtin_expect_with_probability(NSBIG > NSLOT && __any(S.ncon > 16 * NSLOT), 0, BIGPROB)) {
       if (NOVF > 0 && __any(S.ncon > NCP)) __threadfence();  // the overflow rows were written with plain global stores by other lanes of this wave
       solve_step(std::integral_constant<int, NSBIG>{}, std::integral_constant<bool, SELF>{});
     } else {
-      bool done = false;
-      if constexpr (JH_V5_NS1 == 1 && NSLOT > 1) {
-        if (__builtin_expect_with_probability(!__any(S.ncon > 16), 1, JH_V5_NS1PROB)) done = solve_step(std::integral_constant<int, 1>{}, std::integral_constant<bool, SELF>{});
-      }
-      if constexpr (JH_V5_NS1 == 2 && NSLOT > 1 && SELF) {  // (the one-slot copy only without the hand's code)
-        if (!__any(hand_hits) && !__any(S.ncon > 16)) done = solve_step(std::integral_constant<int, 1>{}, std::false_type{});
-      }
-#if JH_V5_HCSPLIT
-      // A wave-step in which no rollout has a candidate pair off the cube has cube contacts only: it takes the copy of the solver compiled without the code for the hand's own
-      // contacts (link on side A, chain-coupling blocks, staged elimination, dense direction) -- the same expressions for what remains, fewer live values around them.
-      if constexpr (SELF) { if (!done && !__any(hand_hits)) done = solve_step(std::integral_constant<int, NSLOT>{}, std::false_type{}); }
-#endif
-      if (!done) solve_step(std::integral_constant<int, NSLOT>{}, std::integral_constant<bool, SELF>{});
+      // A wave-step in which no rollout has a candidate pair off the cube (two thirds of them on the headline workload) has cube contacts only: it takes the copy of the solver
+      // compiled without the code for the hand's own contacts (link on side A, chain-coupling blocks, staged elimination, dense direction) -- the same expressions for what
+      // remains, fewer live values around them: 61.1 -> 59.4 ms.  The same contacts through the hand-capable copy cost 14 % more (48.5 against 42.5 ms with the hand's broad
+      // phase switched off) for the registers its extra paths hold.  The two copies must give the same bits for a cube contact (a rollout's result may not depend on its
+      // wave-mates: tests/test_gpu_leap.py permutes them): with -ffp-contract=fast they do not -- the backend fuses a product into an add only when the product has no other
+      // use, and the hand paths are such uses -- so this file is built with -ffp-contract=on (fusion within a source expression only: +0.7 % on its own, jh_engine_v5.flags).
+      if (SELF && !__any(hand_hits)) solve_step(std::integral_constant<int, NSLOT>{}, std::false_type{});
+      else solve_step(std::integral_constant<int, NSLOT>{}, std::integral_constant<bool, SELF>{});
     }
 #ifdef JH_V5_CENSUS
     if (stats) { if (l == 0 && live) atomicAdd(stats + 192 + min(iters_this, 31), 1); if (lane == 0) atomicAdd(stats + 224 + min(n_wave_iters - wave_it0, 31), 1); }
 #endif
     // ================================================================ implicitfast integration: (M + h diag(d + kv)) qacc = fs + M (a - a0)
     {
-#if JH_V5_WORLDROT
       S.ws[6 + l] = a_own; if (l < 6) { S.acn[l] = ac_own; if (l < 3) S.ws[l] = ac_own; }  // (rotational part: world here; body frame below)
-#else
-      S.ws[6 + l] = a_own; if (l < 6) { S.ws[l] = ac_own; S.acn[l] = ac_own; }
-#endif
-#if JH_V5_PARK
       q = S.pk_q[l]; qd = S.qv[6 + l]; fs_own = S.pk_fs[l];  // (own entries: no other lane wrote them)
-#endif
       const float da_own = a_own - a0_own;
       float rhs_own = fs_own, x4[NLK], L[10];
 #pragma unroll
@@ -2080,20 +1738,14 @@ __global__ __launch_bounds__(WAVE * WPB, JH_V5_WAVES_PER_EU) JH_V5_REGATTR void 
       const float qacc = sel4(x4, s);
       qd = fmaf(h, qacc, qd); q = fmaf(h, qd, q);
       WSYNC();
-#if JH_V5_PARK
       for (int k = 0; k < 6; k++) vc[k] = S.qv[k];
       for (int k = 0; k < 4; k++) qc[3 + k] = S.pk_cq[k];
       if (!MATERIALIZE) acc = S.pk_acc;
-#endif
-#if JH_V5_WORLDROT
       {  // the constrained rotational acceleration back in the body frame (MuJoCo's free-joint convention): integrated, and kept as the next step's warm start
         const float aw[3] = {S.acn[3], S.acn[4], S.acn[5]}; float ab[3]; mulMTV(ab, S.xR[0], aw);
         for (int k = 0; k < 3; k++) { vc[k] = fmaf(h, S.acn[k], vc[k]); vc[3 + k] = fmaf(h, ab[k], vc[3 + k]); }
         if (l < 3) S.ws[3 + l] = l == 0 ? ab[0] : (l == 1 ? ab[1] : ab[2]);
       }
-#else
-      for (int k = 0; k < 6; k++) vc[k] = fmaf(h, S.acn[k], vc[k]);  // the cube's inertia is diagonal: its new acceleration is the constrained one itself
-#endif
       for (int k = 0; k < 3; k++) qc[k] = fmaf(h, vc[k], qc[k]);
       float wn = sqrtf(vc[3] * vc[3] + vc[4] * vc[4] + vc[5] * vc[5]), ang = wn * h;
       if (ang > 0.f) {
@@ -2147,9 +1799,7 @@ __global__ __launch_bounds__(WAVE * WPB, JH_V5_WAVES_PER_EU) JH_V5_REGATTR void 
 bool model_is_leap(const jh_model* m) {
   return m->kind == JH_TASK_LEAP_CUBE && m->nq == 23 && m->nv == 22 && m->nu == 16 && (m->ns == NS || (m->ns == NS_CALTECH && m->h_i.size() > 18 && m->h_i[18] > 0)) && m->h_i.size() > 17 &&
          m->h_i[0] == 17 && m->h_i[1] == 4 && m->h_i[11] > 0 && m->h_i[5] <= MAXG && m->h_i[12] <= MAXLG && m->h_i[17] <= MAXBP
-#if JH_V5_WORLDROT
-         && m->h_f.size() > (size_t)HF_CINERTIA + 2 && m->h_f[HF_CINERTIA] == m->h_f[HF_CINERTIA + 1] && m->h_f[HF_CINERTIA] == m->h_f[HF_CINERTIA + 2]  // isotropic cube inertia (JH_V5_WORLDROT)
-#endif
+         && m->h_f.size() > (size_t)HF_CINERTIA + 2 && m->h_f[HF_CINERTIA] == m->h_f[HF_CINERTIA + 1] && m->h_f[HF_CINERTIA] == m->h_f[HF_CINERTIA + 2]  // isotropic cube inertia: the solver works on the rotation in the world frame
          ;
 }
 
@@ -2160,11 +1810,6 @@ int device_cus(const jh_model* m) {  // (per call, of the model's device: a proc
 
 }  // namespace
 
-#ifdef JH_V5_X_DYNRS
-#define JH_V5_DYNBYTES (sizeof(RS) * RPW * JH_V5_WPB)
-#else
-#define JH_V5_DYNBYTES 0
-#endif
 #ifndef JH_V5_NAME
 #define JH_V5_NAME(f) f
 #endif
@@ -2179,10 +1824,7 @@ int JH_V5_NAME(jh_engine5_rollout_cost)(const jh_model* m, const float* x0, cons
                             const float* lohi, const float* tp, int N, int n_offset, int H, int K, float* costs, float* knots_out, float* trace, hipStream_t st) {
   if (!model_is_leap(m)) { jh_set_error("rollout_cost: the cooperative engine kernel is instantiated for leap_cube only"); return JH_ERR_UNSUPPORTED; }
   if ((m->cylinders > 0) != (JH_V5_CYL != 0)) { jh_set_error("rollout_cost: an image with cylinder geoms runs on the cylinder build of the leap kernel and no other image does (%d cylinders)", m->cylinders); return JH_ERR_UNSUPPORTED; }
-#if JH_V5_KNOTS_LDS
-  JH_REQUIRE(K <= MAXK, "rollout_cost: the cooperative leap kernel keeps at most 8 knots per actuator (K=%d)", K);
-#endif
-  const int dshift = jh_latency_shift(N, RPW); const int per_block = (RPW >> dshift) * JH_V5_WPB;
+  const int dshift = jh_latency_shift(N, RPW); const int per_block = (RPW >> dshift) * WAVES_PER_BLOCK;
   int grid = (N + per_block - 1) / per_block;
   // Launch shape (jh_model_set_rollout_schedule).  A launch with more groups of four rollouts than the GPU holds waves of this kernel (two workgroups per CU) runs one workgroup
   // per resident slot and lets the waves draw their groups from a queue; one that fits at once, and every latency-mode launch, keeps one group per wave of the grid.
@@ -2198,7 +1840,7 @@ int JH_V5_NAME(jh_engine5_rollout_cost)(const jh_model* m, const float* x0, cons
   if (persist) { head = (unsigned*)scratch; if (grid > slots) grid = slots; }
   if (scratch && ovf_bytes > 0) ovf = scratch + (head ? 4 : 0);
 #define JH_V5_LAUNCH_COST(SELF_, PERSIST_)                                                                                                                                        \
-  hipLaunchKernelGGL((k_leap_v5<false, JH_V5_WPB, SELF_, PERSIST_>), dim3(grid), dim3(WAVE * JH_V5_WPB), JH_V5_DYNBYTES, st, m->d_f, m->d_i, x0, 0, nominal, noise, ldn, sigma, W, \
+  hipLaunchKernelGGL((k_leap_v5<false, WAVES_PER_BLOCK, SELF_, PERSIST_>), dim3(grid), dim3(WAVE * WAVES_PER_BLOCK), 0, st, m->d_f, m->d_i, x0, 0, nominal, noise, ldn, sigma, W, \
                      lohi, tp, N, n_offset, H, K, costs, knots_out, (const float*)nullptr, (float*)nullptr, (float*)nullptr, m->d_stats, dshift, trace, ovf, head, 0ll, 0ll)
   if (m->self_collision && m->h_i[17] > 0) { if (persist) JH_V5_LAUNCH_COST(true, true); else JH_V5_LAUNCH_COST(true, false); }
   else { if (persist) JH_V5_LAUNCH_COST(false, true); else JH_V5_LAUNCH_COST(false, false); }
@@ -2210,16 +1852,16 @@ int JH_V5_NAME(jh_engine5_materialize)(const jh_model* m, const float* x0, int x
                            hipStream_t st) {
   if (!model_is_leap(m)) { jh_set_error("rollout_materialize: the cooperative engine kernel is instantiated for leap_cube only"); return JH_ERR_UNSUPPORTED; }
   if ((m->cylinders > 0) != (JH_V5_CYL != 0)) { jh_set_error("rollout_materialize: an image with cylinder geoms runs on the cylinder build of the leap kernel and no other image does (%d cylinders)", m->cylinders); return JH_ERR_UNSUPPORTED; }
-  const int dshift = jh_latency_shift(N, RPW); const int per_block = (RPW >> dshift) * JH_V5_WPB;
+  const int dshift = jh_latency_shift(N, RPW); const int per_block = (RPW >> dshift) * WAVES_PER_BLOCK;
   int grid = (N + per_block - 1) / per_block;
   float* ovf = nullptr;  // one row per rollout for the contacts above the LDS pool: stream-ordered allocation, no state on the model handle
   if (NOVF > 0) ovf = jh_launch_scratch(m, (size_t)N * NOVF * POOL_F * sizeof(float), st);  // (nullptr: the LDS capacity alone, drops and the fallback counted)
   if (m->self_collision && m->h_i[17] > 0)
-    hipLaunchKernelGGL((k_leap_v5<true, JH_V5_WPB, true>), dim3(grid), dim3(WAVE * JH_V5_WPB), JH_V5_DYNBYTES, st, m->d_f, m->d_i, x0, x0_batched, (const float*)nullptr, (const float*)nullptr, 0,
+    hipLaunchKernelGGL((k_leap_v5<true, WAVES_PER_BLOCK, true>), dim3(grid), dim3(WAVE * WAVES_PER_BLOCK), 0, st, m->d_f, m->d_i, x0, x0_batched, (const float*)nullptr, (const float*)nullptr, 0,
                        (const float*)nullptr, (const float*)nullptr, (const float*)nullptr, (const float*)nullptr, N, 0, H, 0, (float*)nullptr, (float*)nullptr,
                        controls, states, sensors, m->d_stats, dshift, (float*)nullptr, ovf, (unsigned*)nullptr, 0ll, 0ll);
   else
-    hipLaunchKernelGGL((k_leap_v5<true, JH_V5_WPB, false>), dim3(grid), dim3(WAVE * JH_V5_WPB), JH_V5_DYNBYTES, st, m->d_f, m->d_i, x0, x0_batched, (const float*)nullptr, (const float*)nullptr, 0,
+    hipLaunchKernelGGL((k_leap_v5<true, WAVES_PER_BLOCK, false>), dim3(grid), dim3(WAVE * WAVES_PER_BLOCK), 0, st, m->d_f, m->d_i, x0, x0_batched, (const float*)nullptr, (const float*)nullptr, 0,
                        (const float*)nullptr, (const float*)nullptr, (const float*)nullptr, (const float*)nullptr, N, 0, H, 0, (float*)nullptr, (float*)nullptr,
                        controls, states, sensors, m->d_stats, dshift, (float*)nullptr, ovf, (unsigned*)nullptr, 0ll, 0ll);
   return jh_launch_done(ovf, st);
@@ -2232,16 +1874,13 @@ int JH_V5_NAME(jh_engine5_rollout_cost_batch)(const jh_model* m, int B, const fl
                                   const float* noise, int ldn, long long noise_stride, const float* W, int N, int H, int K, float* costs, float* trace, hipStream_t st) {
   if (!model_is_leap(m)) { jh_set_error("plan_step_batch: the cooperative engine kernel is instantiated for leap_cube only"); return JH_ERR_UNSUPPORTED; }
   if ((m->cylinders > 0) != (JH_V5_CYL != 0)) { jh_set_error("plan_step_batch: an image with cylinder geoms runs on the cylinder build of the leap kernel and no other image does (%d cylinders)", m->cylinders); return JH_ERR_UNSUPPORTED; }
-#if JH_V5_KNOTS_LDS
-  JH_REQUIRE(K <= MAXK, "plan_step_batch: the cooperative leap kernel keeps at most 8 knots per actuator (K=%d)", K);
-#endif
   JH_REQUIRE((long long)B * N <= 0x7fffffffll, "plan_step_batch: B * N = %lld rollouts exceed one launch", (long long)B * N);
-  const int dshift = jh_latency_shift(B * N, RPW); const int per_block = (RPW >> dshift) * JH_V5_WPB;
+  const int dshift = jh_latency_shift(B * N, RPW); const int per_block = (RPW >> dshift) * WAVES_PER_BLOCK;
   const int grid = (N + per_block - 1) / per_block;
   const size_t ovf_bytes = NOVF > 0 ? (size_t)B * N * NOVF * POOL_F * sizeof(float) : 0;  // one row per rollout of every problem for the contacts above the LDS pool
   float* ovf = ovf_bytes > 0 ? jh_launch_scratch(m, ovf_bytes, st) : nullptr;  // (nullptr: the LDS capacity alone, drops and the fallback counted)
 #define JH_V5_LAUNCH_BATCH(SELF_)                                                                                                                                                  \
-  hipLaunchKernelGGL((k_leap_v5<false, JH_V5_WPB, SELF_, false, true>), dim3(grid, B), dim3(WAVE * JH_V5_WPB), JH_V5_DYNBYTES, st, m->d_f, m->d_i, x0, 0, nominal, noise, ldn, sigma, W, \
+  hipLaunchKernelGGL((k_leap_v5<false, WAVES_PER_BLOCK, SELF_, false, true>), dim3(grid, B), dim3(WAVE * WAVES_PER_BLOCK), 0, st, m->d_f, m->d_i, x0, 0, nominal, noise, ldn, sigma, W, \
                      lohi, tp, N, 0, H, K, costs, (float*)nullptr, (const float*)nullptr, (float*)nullptr, (float*)nullptr, m->d_stats, dshift, trace, ovf, (unsigned*)nullptr, blk_stride, noise_stride)
   if (m->self_collision && m->h_i[17] > 0) JH_V5_LAUNCH_BATCH(true); else JH_V5_LAUNCH_BATCH(false);
 #undef JH_V5_LAUNCH_BATCH

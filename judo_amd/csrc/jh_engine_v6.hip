@@ -39,25 +39,15 @@ constexpr int NA = 9, NCHAIN = 7, NVT = 15, NQ = 16, NU = 8, NS = 14, NX = 31, N
 #ifndef JH_V6_NSBIG
 #define JH_V6_NSBIG 6  // 96 general contacts per rollout (32 in LDS, 64 in the global row); 4 and 6 cost the common path the same (nothing: 11.14 / 11.17 ms on recorded inputs)
 #endif
-#ifndef JH_V6_BIGPROB
-#define JH_V6_BIGPROB 0.999999  // how sure the compiler may be that a wave-step stays on the two-slot copy of the solver (block frequencies steer the placement of register spills)
-#endif
+constexpr double BIGPROB = 0.999999;  // how sure the compiler may be that a wave-step stays on the two-slot copy of the solver (block frequencies steer the placement of register spills)
 // General contacts: NCP in the LDS pool (two slots per lane, the common case); a rollout with more -- a gripper pressed flat onto the table stacks 4-point manifolds of ten pad
 // boxes: 40-60 contacts, the reference's SHIPPED 1 s horizon visits such states all the time -- writes the rest to a row of global memory, and its wave runs a second copy
 // of the constraint rows + Newton solver with NSBIG slots per lane (the leap kernel's recipe, jh_engine_v5.hip `solve_step`).
 constexpr int NCP = 32, NSL = NCP / G, NSBIG = JH_V6_NSBIG, NOVF = (NSBIG - NSL) * G, MAXHIT = 64, RAW_F = 8, JW = NVT * 3;  // MAXHIT: broad-phase survivors (candidate pairs) per rollout and step, 16 bits each
 constexpr int MAXDT = 32;  // box pairs behind the distance sensors
-#ifndef JH_V6_NFS
-#define JH_V6_NFS 6
-#endif
 constexpr int FF_F = 5;
-constexpr int NFS = JH_V6_NFS, NFF = NFS * G;  // finger-finger contacts: kept in registers of their owner lanes (6 per lane = 96 per rollout), never in the LDS Jacobian
-#ifndef JH_V6_NOISE
-#define JH_V6_NOISE 1.2e-7f  // one fp32 ulp (2^-23), relative: the resolution of the iterate
-#endif
-#ifndef JH_V6_OPAQUE
-#define JH_V6_OPAQUE 1
-#endif
+constexpr int NFS = 6, NFF = NFS * G;  // finger-finger contacts: kept in registers of their owner lanes (6 per lane = 96 per rollout), never in the LDS Jacobian
+constexpr float NOISE = 1.2e-7f;  // one fp32 ulp (2^-23), relative: the resolution of the iterate
 #define OPAQUE6(x) asm volatile("" : "+v"(x))
 // Measured and taken out of the source in round 4 (profiles/r04_leap_experiments.txt; the git history has it as JH_V6_RIGHTLOOK): a right-looking row Cholesky (one LDS write per
 // lane and step, independent updates) with a column-oriented backward solve: 9.54 against 9.60 ms, within the noise -- the factorisation (19 % of the kernel,
@@ -67,19 +57,8 @@ constexpr int NFS = JH_V6_NFS, NFF = NFS * G;  // finger-finger contacts: kept i
 // Round 5 (the git history has the LDS row form as JH_V6_DPPCHOL=0): that conclusion was wrong about the cause.  The factorisation in registers with DPP row broadcasts (step (4) of
 // the Newton iteration: no LDS, no barrier, the same subtraction order and so the same bits) took the kernel from 8.26 to 7.68 ms on the recorded inputs: what the LDS
 // variants had in common was the publish / wait / read-back round trip per pivot, whichever way the updates were arranged around it.
-#ifndef JH_V6_NS1
-#define JH_V6_NS1 1  // among the wave-steps without a finger-finger contact, those with at most 16 general contacts per rollout take a one-slot copy: 8.98 -> 8.79 ms
-#endif
-#ifndef JH_V6_FFSPLIT
-#define JH_V6_FFSPLIT 1  // wave-steps without a finger-finger contact take a copy of rows + solver without the six finger-finger slots per lane (48 registers): 9.59 -> 9.37 ms, and 8.99 ms
-                         // with -ffp-contract=on (jh_engine_v6.flags), under which the two copies also round alike (the leap kernel's note on JH_V5_HCSPLIT)
-#endif
-#ifndef JH_V6_LSCAP
-#define JH_V6_LSCAP 12  // line-search evaluations per Newton iteration
-#endif
-#ifndef JH_V6_WPE
-#define JH_V6_WPE 2   // waves per SIMD the register allocation aims at (19.9 KB of LDS per one-wave workgroup: eight workgroups per CU)
-#endif
+constexpr int LSCAP = 12;  // line-search evaluations per Newton iteration
+constexpr int WPE = 2;     // waves per SIMD the register allocation aims at (19.9 KB of LDS per one-wave workgroup: eight workgroups per CU)
 constexpr int LF = 8, RF = 9;       // moving-body indices of the two fingers (arm dofs 7 / 8 = lanes 13 / 14)
 
 struct __attribute__((aligned(16))) RS6 {  // per-rollout shared state
@@ -443,7 +422,7 @@ __device__ __forceinline__ void geom_pose3(const RS6& S, const float* gf, int bo
 }
 
 template <bool MATERIALIZE>
-__global__ __launch_bounds__(WAVE) __attribute__((amdgpu_waves_per_eu(JH_V6_WPE, JH_V6_WPE))) void k_fr3_v6(const float* __restrict__ gF, const int* __restrict__ gI, const float* __restrict__ x0, int x0_batched,
+__global__ __launch_bounds__(WAVE) __attribute__((amdgpu_waves_per_eu(WPE, WPE))) void k_fr3_v6(const float* __restrict__ gF, const int* __restrict__ gI, const float* __restrict__ x0, int x0_batched,
                                                     const float* __restrict__ nominal, const float* __restrict__ noise, int ldn,
                                                     const float* __restrict__ sigma, const float* __restrict__ W, const float* __restrict__ lohi,
                                                     const float* __restrict__ tp, int phase, int N, int n_offset, int H, int K,
@@ -953,7 +932,6 @@ __global__ __launch_bounds__(WAVE) __attribute__((amdgpu_waves_per_eu(JH_V6_WPE,
         // Everything a contact slot needs in an iteration is invariant over the iterations, so the compiler would compute it once before the loop (lever arms,
         // Jacobian columns, pyramid constants of every slot), run out of registers and reload all of it from scratch memory in every iteration; with the
         // slots made opaque it recomputes from the 25 / 8 numbers of a slot instead (jh_engine_v5.hip found the same)
-#if JH_V6_OPAQUE
 #pragma unroll
         for (int k = 0; k < NS; k++) {
           OPAQUE6(sl[k].sa); OPAQUE6(sl[k].sb);
@@ -963,7 +941,6 @@ __global__ __launch_bounds__(WAVE) __attribute__((amdgpu_waves_per_eu(JH_V6_WPE,
         }
 #pragma unroll
         for (int k = 0; k < NF; k++) { OPAQUE6(sf[k].D); OPAQUE6(sf[k].mu); for (int w = 0; w < 3; w++) { OPAQUE6(sf[k].Jf[w]); OPAQUE6(sf[k].aref[w]); } }
-#endif
         // ---- (1) gradient row: M (a - a0) + dof rows + equality - J' f
         const float da_own = a_own - a0_own;
         if (hasdof) S.vec[0][l] = da_own;
@@ -1018,7 +995,7 @@ __global__ __launch_bounds__(WAVE) __attribute__((amdgpu_waves_per_eu(JH_V6_WPE,
         // the iterate then sits on the fp32 number nearest to the minimiser, the gradient test never passes and the solve would run to the iteration cap
         // hopping in the soft directions on the rounding noise of the stiff ones.  H_ll is the diagonal of the last assembled Hessian (0 before the first).
         // Row by row: only what a row's gradient exceeds its own floor by counts, so the soft rows still have to meet the tolerance themselves.
-        const float gfl = JH_V6_NOISE * hdiag * a_own;
+        const float gfl = NOISE * hdiag * a_own;
         const float gn = gsum(hasdof ? fmaxf(g_own * g_own - gfl * gfl, 0.f) * iMd : 0.f);
         const float gtol = tol * tol * fmaxf(snorm, 1e-12f);
 #ifdef JH_V6_EXITSTATS
@@ -1133,7 +1110,7 @@ __global__ __launch_bounds__(WAVE) __attribute__((amdgpu_waves_per_eu(JH_V6_WPE,
         dr.pf = p_own; dr.pl = dr.lims * p_own;
         ejp = has_eq ? p[13] - e_a1 * p[14] : 0.f;
         float lo = 0.f, hi = -1.f, alpha = 1.f; bool lsact = act;
-        for (int ls = 0; ls < JH_V6_LSCAP && __any(lsact); ls++) {
+        for (int ls = 0; ls < LSCAP && __any(lsact); ls++) {
           float d1, d2;
           lane_rows_dir<NS, NF>(sl, sf, sff, spf, dr, eq_lane, eD, ejar, ejp, alpha, &d1, &d2);
           d1 = gsum(d1) + pMd + alpha * pMp; d2 = gsum(d2) + pMp;
@@ -1174,16 +1151,15 @@ __global__ __launch_bounds__(WAVE) __attribute__((amdgpu_waves_per_eu(JH_V6_WPE,
 #endif
     }
     };
-    if (__builtin_expect_with_probability(ovf_all != nullptr && __any(S.ncon > NCP), 0, JH_V6_BIGPROB)) {
+    // Wave-steps without a finger-finger contact take a copy of rows + solver without the six finger-finger slots per lane (48 registers): 9.59 -> 9.37 ms, and 8.99 ms with
+    // -ffp-contract=on (jh_engine_v6.flags), under which the two copies also round alike (the leap kernel's note at its own solve_step dispatch).  Among them, those with at
+    // most 16 general contacts per rollout take a one-slot copy: 8.98 -> 8.79 ms.
+    if (__builtin_expect_with_probability(ovf_all != nullptr && __any(S.ncon > NCP), 0, BIGPROB)) {
       __threadfence();  // the overflow rows were written with plain global stores by other lanes of this wave
       solve_step(std::integral_constant<int, NSBIG>{}, std::integral_constant<int, NFS>{});
     }
-#if JH_V6_FFSPLIT
-#if JH_V6_NS1
-    else if (!__any(S.nff > 0) && !__any(S.ncon > G)) solve_step(std::integral_constant<int, 1>{}, std::integral_constant<int, 0>{});  // (and at most 16 general contacts per rollout)
-#endif
+    else if (!__any(S.nff > 0) && !__any(S.ncon > G)) solve_step(std::integral_constant<int, 1>{}, std::integral_constant<int, 0>{});
     else if (!__any(S.nff > 0)) solve_step(std::integral_constant<int, NSL>{}, std::integral_constant<int, 0>{});
-#endif
     else solve_step(std::integral_constant<int, NSL>{}, std::integral_constant<int, NFS>{});
     PH6(5)
     // ================================================================ implicitfast integration: (M + h diag(d + kv)) qacc = fs + M (a - a0)

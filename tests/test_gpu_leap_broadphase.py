@@ -1,4 +1,4 @@
-"""The lane mapping of the hand's broad phase (jh_engine_v5.hip: JH_V5_L1LIST, JH_V5_L2COMBO) changes where a test runs and nothing else: the candidate list of every
+"""The lane mapping of the hand's broad phase (jh_engine_v5.hip: the list-driven level 1 and the combination-per-lane level 2) changes where a test runs and nothing else: the candidate list of every
 rollout and step keeps its entries and their order, so every output keeps its bits.  Compared word for word with tests/golden/leap_broadphase_bits.npz, the kernel's own
 output from before the mapping was changed (tools/record_leap_broadphase_bits.py, which is also this test's runner; the fixture's metadata names the commit and compiler):
 tangled hand configurations chosen so that the recorded rollout-steps have more than 16 box survivors at level 1, a body pair with more than 16 geom combinations and pairs with

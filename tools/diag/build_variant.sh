@@ -10,7 +10,7 @@ base=$(basename "$src" .hip)
 mkdir -p variants build/var
 /opt/rocm/bin/hipcc --offload-arch=gfx950 -O3 -std=c++17 -fPIC -ffp-contract=fast -Iinclude -Ijudo_amd/csrc ${VARIANT_FLAGS-$(cat "${src%.hip}.flags" 2>/dev/null)} -c "$src" -o "build/var/${base}_${name}.o" "$@"
 objs=""
-for o in jh_api jh_simple jh_update jh_reward jh_engine_v5 jh_engine_v5_cap64 jh_engine_v5_cyl jh_engine_v6 jh_engine_v4 jh_policy; do
+for o in $(python3 -c "import __graft_entry__ as g; print(' '.join(s[:-len('.hip')] for s in g.HIP_SOURCES))"); do  # the product library's translation units
   if [ "$o" == "$base" ]; then objs="$objs build/var/${base}_${name}.o"; else objs="$objs build/$o.o"; fi
 done
 /opt/rocm/bin/hipcc --offload-arch=gfx950 -shared -fPIC -o "variants/libjudo_amd_${name}.so" $objs

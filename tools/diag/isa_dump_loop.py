@@ -3,7 +3,7 @@ usage: python tools/diag/isa_dump_loop.py build/isa/v5.s [hand|lean] > loop.txt"
 import re, sys
 asm = sys.argv[1]; which = sys.argv[2] if len(sys.argv) > 2 else "hand"
 src = open("judo_amd/csrc/jh_engine_v5.hip").read().split("\n")
-pat = "done = solve_step(std::integral_constant<int, NSLOT>{}, std::false_type{})" if which == "lean" else "if (!done) solve_step(std::integral_constant<int, NSLOT>{}, std::integral_constant<bool, SELF>{})"
+pat = "if (SELF && !__any(hand_hits)) solve_step(std::integral_constant<int, NSLOT>{}, std::false_type{})" if which == "lean" else "else solve_step(std::integral_constant<int, NSLOT>{}, std::integral_constant<bool, SELF>{})"
 l_solve = next(i + 1 for i, l in enumerate(src) if pat in l)
 if which == "lean": l_loop = next(i + 1 for i, l in enumerate(src) if l.strip().startswith("else newton_loop(std::false_type{});"))
 else: l_loop = next(i + 1 for i, l in enumerate(src) if "NS == NSLOT" in l and "newton_loop(std::false_type{})" in l)

@@ -5,9 +5,9 @@ import collections, re, sys
 asm = sys.argv[1]
 src = open("judo_amd/csrc/jh_engine_v5.hip").read().split("\n")
 # call sites: newton_loop(std::false_type{}) inside `else if constexpr (SELF && NS == NSLOT)` and solve_step(NSLOT)
-# which copy of the solver: "hand" (default) = the hand-capable copy, "lean" = the copy without the hand-contact code (JH_V5_HCSPLIT dispatch)
+# which copy of the solver: "hand" (default) = the hand-capable copy, "lean" = the copy without the hand-contact code (the dispatch behind solve_step)
 which = sys.argv[2] if len(sys.argv) > 2 else "hand"
-pat = "done = solve_step(std::integral_constant<int, NSLOT>{}, std::false_type{})" if which == "lean" else "if (!done) solve_step(std::integral_constant<int, NSLOT>{}, std::integral_constant<bool, SELF>{})"
+pat = "if (SELF && !__any(hand_hits)) solve_step(std::integral_constant<int, NSLOT>{}, std::false_type{})" if which == "lean" else "else solve_step(std::integral_constant<int, NSLOT>{}, std::integral_constant<bool, SELF>{})"
 l_solve = next(i + 1 for i, l in enumerate(src) if pat in l)
 if which == "lean":  # HC = false: the loop is instantiated by the last branch, `else newton_loop(std::false_type{});`
     l_loop = next(i + 1 for i, l in enumerate(src) if l.strip().startswith("else newton_loop(std::false_type{});"))

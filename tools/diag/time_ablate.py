@@ -1,5 +1,5 @@
 """Scratch diagnostic (GPU box): share of each phase of the cooperative leap_cube kernel, measured by repeating one phase
-R times in a -DJH_V2_ABLATE build (tools/build_variant.sh ablate -DJH_V2_ABLATE) and differencing the plan-step times."""
+R times in a -DJH_V2_ABLATE build of jh_engine_v2.hip (round 2, when that kernel was in the product library) and differencing the plan-step times."""
 import os, sys, time
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__)))))
 import numpy as np, torch

@@ -1,6 +1,6 @@
 #!/bin/bash
 # GPU box: Newton tolerance x contact-pool sweep on the recorded 40 plan steps of the headline workload (hand self-collision on).
-# Reference = tol 1e-6 with the 48-contact pool (build/libjudo_amd_ns3.so = tools/build_variant.sh ns3 -DJH_V5_NSLOT=3).
+# Reference = tol 1e-6 with the 48-contact pool (build/libjudo_amd_ns3.so = a copy of variants/libjudo_amd_ns3.so from tools/diag/build_variant.sh ns3 judo_amd/csrc/jh_engine_v5.hip -DJH_V5_NSLOT=3).
 cd $GRAFT_REPO_ROOT
 R="python tools/diag/ab_fixed_inputs.py replay tools/diag/ab_inputs_leap.npz"
 mkdir -p gpurun_out/sweep
