@@ -266,6 +266,36 @@ int jh_plan_step_batch(const jh_model* m, int B, void* blk_dev, const void* blk_
                        const float* noise, int ldn, size_t noise_stride_floats, const float* W, int N, int H, int K, float* costs, float* trace, int mode, float lambda, int k,
                        int tie_high, int E, int row_floats, int colmajor, float* scratch, float* out, size_t out_stride_floats, void* out_host_mark, void* const* timing,
                        void* stream);
+/* jh_plan_step_batch with a model image PER PROBLEM (randomised physics: B planners of one task with B cube masses or friction coefficients, a bank of mass hypotheses,
+ * one controller over perturbed plants).  The reference has no counterpart.  A model set is B model handles whose FLOAT sections sit in one device buffer, a fixed stride
+ * apart; everything else -- the int section (topology, pair lists, lane lists), the dimensions, the kernel build and its settings -- is member 0's and must be the same in
+ * every member.  That is what a description perturbed in its masses, inertias, friction coefficients or actuator gains packs to (judo_amd.models.scaled_description).
+ *   jh_model_set_create   checks the members (below), then copies their float sections device to device into one allocation on member 0's device; the stride is the float
+ *                         count rounded up to a multiple of 64 floats, so every image keeps the alignment a model's own has.  The set keeps models[0] -- which must outlive
+ *                         it -- for everything else; the other handles may be destroyed.  Settings (jh_model_set_self_collision, jh_model_set_plan_step_launches ...) are
+ *                         read from member 0 at every launch.
+ *   jh_model_set_update   replaces member b's image, after the same checks (re-randomising between episodes).  Synchronous; not meant for the plan loop.  b = 0: `model`
+ *                         becomes the handle the set keeps.
+ *   jh_model_set_info     out[0] = B, out[1] = floats per image, out[2] = the stride in floats, out[3] = members whose image differs from member 0's.
+ *   jh_plan_step_batch_models   jh_plan_step_batch without `m` and `B`: the same blocks, noise, costs, trace, scratch and out with the same strides, the same completion mark.
+ *                         Problem b runs on image b: its costs, nominal, sigma and trace records are bit for bit those of jh_plan_step on member b's own handle and
+ *                         sub-block (the kernels offset the base of the float section by blockIdx.y * stride, scalar arithmetic on kernel arguments, and run the single
+ *                         call's code).  jh_plan_step_batch itself is this code path with stride 0.
+ * The diagnostic counters of a set launch (jh_model_stats) land in MEMBER 0's handle, whichever problem a rollout belongs to.
+ * jh_model_set_create / _update refuse, with jh_last_error naming the member and the field: B < 1 or B > 65535 (JH_ERR_INVALID); a member on another device, or with another
+ * kind, nq, nv, nu, ns, ntaskparam, nf or ni; an int section (h_i) that is not byte for byte member 0's; another kernel_gen, contact_capacity, cylinders, self_collision,
+ * rollout_schedule or plan_step_launches (all JH_ERR_INVALID); fr3_pick and leap models off kernel generation 3, as jh_plan_step_batch does (JH_ERR_UNSUPPORTED); and a
+ * member whose image the kernel's own launcher would refuse -- each image is held to the single call's acceptance test on its own floats, e.g. the leap kernel's isotropic
+ * cube inertia (JH_ERR_UNSUPPORTED). */
+typedef struct jh_model_set jh_model_set;
+int jh_model_set_create(const jh_model* const* models /* HOST array of B handles */, int B, jh_model_set** out);
+int jh_model_set_update(jh_model_set* set, int b, const jh_model* model);
+int jh_model_set_info(const jh_model_set* set, int* out /* HOST, 4 ints */);
+void jh_model_set_destroy(jh_model_set* set);
+int jh_plan_step_batch_models(const jh_model_set* set, void* blk_dev, const void* blk_host, size_t blk_bytes, size_t blk_stride_bytes, int o_nominal, int o_sigma, int o_tp, int o_lohi,
+                              const float* noise, int ldn, size_t noise_stride_floats, const float* W, int N, int H, int K, float* costs, float* trace, int mode, float lambda, int k,
+                              int tie_high, int E, int row_floats, int colmajor, float* scratch, float* out, size_t out_stride_floats, void* out_host_mark, void* const* timing,
+                              void* stream);
 /* The noise of those B problems in one launch (judo/optimizers/{mppi.py:52,ps.py:43,cem.py:67}, one np.random.randn per controller): problem b's (rows, ldn) slice of `out`
  * (B x rows x ldn floats) is bit for bit what jh_noise_normal(seeds[b], draws[b], rows, 0, n_local, out + b * rows * ldn, ldn) writes; columns n_local .. ldn - 1 are left
  * alone.  seeds / draws: HOST arrays of B entries, read before the call returns (one launch per 256 problems: the pairs travel as kernel arguments). */

@@ -459,34 +459,35 @@ extern "C" int jh_plan_step(const jh_model* m, void* blk_dev, const void* blk_ho
 
 // B plan steps of one model as ONE call (include/judo_amd.h): the B packed blocks go up in one copy (or are read in place), the kernels take the problem from blockIdx.y and
 // reach its buffers through strides, and one completion mark stands behind all of them.  Problem 0's launch record is built by the single call's own checks
-// (jh_update_tail_args); the kernels derive problem b's from it.
-extern "C" int jh_plan_step_batch(const jh_model* m, int B, void* blk_dev, const void* blk_host, size_t blk_bytes, size_t blk_stride_bytes, int o_nominal, int o_sigma, int o_tp, int o_lohi,
-                                  const float* noise, int ldn, size_t noise_stride_floats, const float* W, int N, int H, int K, float* costs, float* trace, int mode, float lambda, int k,
-                                  int tie_high, int E, int row_floats, int colmajor, float* scratch, float* out, size_t out_stride_floats, void* out_host_mark, void* const* timing,
-                                  void* stream) {
-  JH_REQUIRE(m && blk_dev && blk_host && out && scratch && noise && W && costs, "plan_step_batch: null pointer");
-  if (m->kind == JH_TASK_FR3_PICK) { jh_set_error("plan_step_batch: fr3_pick has no batched plan step (its phase is chosen per problem on the host)"); return JH_ERR_UNSUPPORTED; }
-  if (m->kind == JH_TASK_LEAP_CUBE && m->kernel_gen != 3) { jh_set_error("plan_step_batch: only kernel generation 3 of the leap family has a batched launch (this model runs %d)", m->kernel_gen); return JH_ERR_UNSUPPORTED; }
-  JH_REQUIRE(B >= 1, "plan_step_batch: B must be at least 1 (B=%d)", B);
-  JH_REQUIRE(B <= 65535, "plan_step_batch: B = %d exceeds the 65535 problems of a launch (the grid's second dimension)", B);
-  JH_REQUIRE(N > 0 && H > 0 && K >= 1, "plan_step_batch: N, H, K must be positive (N=%d H=%d K=%d)", N, H, K);
-  JH_REQUIRE(ldn >= N, "plan_step_batch: ldn (%d) < N (%d)", ldn, N);
+// (jh_update_tail_args); the kernels derive problem b's from it.  `images` / `image_stride`: the float section the rollout kernels read for problem 0 and the floats to
+// problem b + 1's from problem b's -- m->d_f and 0 for jh_plan_step_batch, a model set's buffer and stride for jh_plan_step_batch_models: one code path.
+static int plan_step_batch(const char* who, const jh_model* m, const float* images, long long image_stride, int B, void* blk_dev, const void* blk_host, size_t blk_bytes, size_t blk_stride_bytes,
+                           int o_nominal, int o_sigma, int o_tp, int o_lohi, const float* noise, int ldn, size_t noise_stride_floats, const float* W, int N, int H, int K, float* costs,
+                           float* trace, int mode, float lambda, int k, int tie_high, int E, int row_floats, int colmajor, float* scratch, float* out, size_t out_stride_floats,
+                           void* out_host_mark, void* const* timing, void* stream) {
+  JH_REQUIRE(m && blk_dev && blk_host && out && scratch && noise && W && costs, "%s: null pointer", who);
+  if (m->kind == JH_TASK_FR3_PICK) { jh_set_error("%s: fr3_pick has no batched plan step (its phase is chosen per problem on the host)", who); return JH_ERR_UNSUPPORTED; }
+  if (m->kind == JH_TASK_LEAP_CUBE && m->kernel_gen != 3) { jh_set_error("%s: only kernel generation 3 of the leap family has a batched launch (this model runs %d)", who, m->kernel_gen); return JH_ERR_UNSUPPORTED; }
+  JH_REQUIRE(B >= 1, "%s: B must be at least 1 (B=%d)", who, B);
+  JH_REQUIRE(B <= 65535, "%s: B = %d exceeds the 65535 problems of a launch (the grid's second dimension)", who, B);
+  JH_REQUIRE(N > 0 && H > 0 && K >= 1, "%s: N, H, K must be positive (N=%d H=%d K=%d)", who, N, H, K);
+  JH_REQUIRE(ldn >= N, "%s: ldn (%d) < N (%d)", who, ldn, N);
   const int KU = K * m->nu;
-  JH_REQUIRE(KU <= JH_MAX_KNOT_DIM, "plan_step_batch: K*nu = %d exceeds %d", KU, JH_MAX_KNOT_DIM);
+  JH_REQUIRE(KU <= JH_MAX_KNOT_DIM, "%s: K*nu = %d exceeds %d", who, KU, JH_MAX_KNOT_DIM);
   const int nx = m->nq + m->nv;
-  JH_REQUIRE(o_nominal >= 0 && o_sigma >= 0 && o_tp >= 0 && o_lohi >= 0, "plan_step_batch: negative block offset");
+  JH_REQUIRE(o_nominal >= 0 && o_sigma >= 0 && o_tp >= 0 && o_lohi >= 0, "%s: negative block offset", who);
   const size_t need = sizeof(float) * (size_t)std::max(std::max(nx, o_nominal + KU), std::max(std::max(o_sigma + KU, o_tp + m->ntaskparam), o_lohi + 2 * m->nu));
-  JH_REQUIRE(blk_bytes >= need, "plan_step_batch: a block of %zu bytes does not hold x0 | nominal | sigma | task params | bounds at the given offsets (%zu bytes)", blk_bytes, need);
-  JH_REQUIRE(blk_stride_bytes >= blk_bytes && blk_stride_bytes % sizeof(float) == 0, "plan_step_batch: blk_stride_bytes = %zu is smaller than a block (%zu bytes) or no multiple of 4", blk_stride_bytes, blk_bytes);
-  JH_REQUIRE(noise_stride_floats >= (size_t)KU * (size_t)ldn, "plan_step_batch: noise_stride_floats = %zu is smaller than a problem's noise (K*nu*ldn = %zu)", noise_stride_floats, (size_t)KU * (size_t)ldn);
+  JH_REQUIRE(blk_bytes >= need, "%s: a block of %zu bytes does not hold x0 | nominal | sigma | task params | bounds at the given offsets (%zu bytes)", who, blk_bytes, need);
+  JH_REQUIRE(blk_stride_bytes >= blk_bytes && blk_stride_bytes % sizeof(float) == 0, "%s: blk_stride_bytes = %zu is smaller than a block (%zu bytes) or no multiple of 4", who, blk_stride_bytes, blk_bytes);
+  JH_REQUIRE(noise_stride_floats >= (size_t)KU * (size_t)ldn, "%s: noise_stride_floats = %zu is smaller than a problem's noise (K*nu*ldn = %zu)", who, noise_stride_floats, (size_t)KU * (size_t)ldn);
   int t_adr = 0, t_nfl = 0, t_cm = 0;
-  if (trace) { trace_layout(m, &t_adr, &t_nfl, &t_cm); JH_REQUIRE(t_nfl > 0 && row_floats == H * t_nfl, "plan_step_batch: row_floats = %d is not H x the model's %d trace floats per step (jh_model_trace_layout)", row_floats, t_nfl); }
+  if (trace) { trace_layout(m, &t_adr, &t_nfl, &t_cm); JH_REQUIRE(t_nfl > 0 && row_floats == H * t_nfl, "%s: row_floats = %d is not H x the model's %d trace floats per step (jh_model_trace_layout)", who, row_floats, t_nfl); }
   const int E_t = trace ? E : 0;
-  JH_REQUIRE(E_t >= 0 && E_t <= JH_MAX_ELITES, "plan_step_batch: bad trace arguments (E=%d)", E);
+  JH_REQUIRE(E_t >= 0 && E_t <= JH_MAX_ELITES, "%s: bad trace arguments (E=%d)", who, E);
   const size_t rec = 2 * (size_t)KU + (size_t)E_t * (2 + (size_t)(E_t > 0 ? row_floats : 0));
-  JH_REQUIRE(out_stride_floats >= rec, "plan_step_batch: out_stride_floats = %zu is smaller than an output record (nominal | sigma | E trace records = %zu floats)", out_stride_floats, rec);
+  JH_REQUIRE(out_stride_floats >= rec, "%s: out_stride_floats = %zu is smaller than an output record (nominal | sigma | E trace records = %zu floats)", who, out_stride_floats, rec);
   const bool closed = m->kind == JH_TASK_CARTPOLE || m->kind == JH_TASK_CYLINDER_PUSH;
-  if (!closed && m->kind != JH_TASK_LEAP_CUBE) { jh_set_error("plan_step_batch: no batched kernel for this model"); return JH_ERR_UNSUPPORTED; }
+  if (!closed && m->kind != JH_TASK_LEAP_CUBE) { jh_set_error("%s: no batched kernel for this model", who); return JH_ERR_UNSUPPORTED; }
   hipStream_t st = (hipStream_t)stream;
   const float* b = (const float*)blk_dev;
   if (blk_dev != blk_host) { const int rc = jh_upload_async(blk_dev, blk_host, (size_t)(B - 1) * blk_stride_bytes + blk_bytes, stream); if (rc != JH_OK) return rc; }
@@ -496,20 +497,20 @@ extern "C" int jh_plan_step_batch(const jh_model* m, int B, void* blk_dev, const
   bool one = false;
   if (int rc = plan_step_launches(m, N, H, K, costs, nullptr, W, noise, ldn, &one)) return rc;
   jh_upd::TailArgs a;
-  if (int rc = jh_update_tail_args("plan_step_batch", costs, nullptr, b + o_nominal, noise, ldn, b + o_sigma, b + o_lohi, N, 0, K, m->nu, mode, lambda, k, tie_high, E_t, trace, row_floats, colmajor,
+  if (int rc = jh_update_tail_args(who, costs, nullptr, b + o_nominal, noise, ldn, b + o_sigma, b + o_lohi, N, 0, K, m->nu, mode, lambda, k, tie_high, E_t, trace, row_floats, colmajor,
                                    scratch, out, out + KU, E_t > 0 ? out + 2 * KU : nullptr, nullptr, &a)) return rc;
   jh_upd::BatchArgs s;
   s.B = B; s.blk = (long long)(blk_stride_bytes / sizeof(float)); s.noise = (long long)noise_stride_floats; s.costs = N; s.trace = (long long)N * row_floats;
   s.scratch = (long long)jh_update_fused_scratch_floats(N, K, m->nu); s.out = (long long)out_stride_floats;
-  s.counter = reinterpret_cast<unsigned*>(scratch) + 1; s.done_flag = flag; s.done_value = expect;
+  s.counter = reinterpret_cast<unsigned*>(scratch) + 1; s.done_flag = flag; s.done_value = expect; s.image = image_stride;
   int rc = JH_OK;
-  if (one) rc = jh_simple_plan_step_batch(m, b, W, b + o_tp, H, K, a, s, st);
+  if (one) rc = jh_simple_plan_step_batch(m, images, b, W, b + o_tp, H, K, a, s, st);
   else {
-    if (closed) rc = jh_simple_rollout_cost_batch(m, b, b + o_tp, W, H, K, a, s, st);
+    if (closed) rc = jh_simple_rollout_cost_batch(m, images, b, b + o_tp, W, H, K, a, s, st);
     else
-      rc = m->cylinders > 0           ? jh_engine5_rollout_cost_batch_cyl(m, B, b, b + o_nominal, b + o_sigma, b + o_lohi, b + o_tp, s.blk, noise, ldn, s.noise, W, N, H, K, costs, trace, st)
-           : m->contact_capacity > 48 ? jh_engine5_rollout_cost_batch_cap64(m, B, b, b + o_nominal, b + o_sigma, b + o_lohi, b + o_tp, s.blk, noise, ldn, s.noise, W, N, H, K, costs, trace, st)
-                                      : jh_engine5_rollout_cost_batch(m, B, b, b + o_nominal, b + o_sigma, b + o_lohi, b + o_tp, s.blk, noise, ldn, s.noise, W, N, H, K, costs, trace, st);
+      rc = m->cylinders > 0           ? jh_engine5_rollout_cost_batch_cyl(m, images, image_stride, B, b, b + o_nominal, b + o_sigma, b + o_lohi, b + o_tp, s.blk, noise, ldn, s.noise, W, N, H, K, costs, trace, st)
+           : m->contact_capacity > 48 ? jh_engine5_rollout_cost_batch_cap64(m, images, image_stride, B, b, b + o_nominal, b + o_sigma, b + o_lohi, b + o_tp, s.blk, noise, ldn, s.noise, W, N, H, K, costs, trace, st)
+                                      : jh_engine5_rollout_cost_batch(m, images, image_stride, B, b, b + o_nominal, b + o_sigma, b + o_lohi, b + o_tp, s.blk, noise, ldn, s.noise, W, N, H, K, costs, trace, st);
     if (rc == JH_OK && timing) JH_HIP(hipEventRecord((hipEvent_t)timing[1], st));
     if (rc == JH_OK) rc = jh_update_tail_batch_launch(a, s, st);
   }
@@ -517,6 +518,117 @@ extern "C" int jh_plan_step_batch(const jh_model* m, int B, void* blk_dev, const
   if (rc == JH_OK && timing) JH_HIP(hipEventRecord((hipEvent_t)timing[2], st));
   if (rc == JH_OK) rc = download_begin(out, out, 0, stream, flag, expect);
   return rc;
+}
+
+extern "C" int jh_plan_step_batch(const jh_model* m, int B, void* blk_dev, const void* blk_host, size_t blk_bytes, size_t blk_stride_bytes, int o_nominal, int o_sigma, int o_tp, int o_lohi,
+                                  const float* noise, int ldn, size_t noise_stride_floats, const float* W, int N, int H, int K, float* costs, float* trace, int mode, float lambda, int k,
+                                  int tie_high, int E, int row_floats, int colmajor, float* scratch, float* out, size_t out_stride_floats, void* out_host_mark, void* const* timing,
+                                  void* stream) {
+  JH_REQUIRE(m != nullptr, "plan_step_batch: null pointer");
+  return plan_step_batch("plan_step_batch", m, m->d_f, 0, B, blk_dev, blk_host, blk_bytes, blk_stride_bytes, o_nominal, o_sigma, o_tp, o_lohi, noise, ldn, noise_stride_floats, W, N, H, K, costs, trace,
+                         mode, lambda, k, tie_high, E, row_floats, colmajor, scratch, out, out_stride_floats, out_host_mark, timing, stream);
+}
+
+// ---- model sets: B images of one model's float section in one device buffer, a fixed stride apart (include/judo_amd.h) ----
+// Everything but the float section is member 0's: the launchers read its int section, its settings and its counters, so a member must agree with it on all of them.
+struct jh_model_set {
+  int B;
+  size_t nf, stride;                   // floats per image; floats from one image to the next (nf rounded up to a multiple of 64)
+  float* d_images;                     // B x stride floats on member 0's device
+  const jh_model* m0;                  // member 0: the int section, the dimensions, the kernel build and settings, d_stats
+  std::vector<std::vector<float>> hf;  // host copies of the members' float sections (jh_model_set_info: how many differ from member 0's)
+};
+
+// May `m` be member `b` of a set whose member 0 is `m0` (b == 0: may `m` lead a set)?  JH_OK, or the status with the error set: it names the member and the field.
+static int model_set_member(const char* who, const jh_model* m0, const jh_model* m, int b) {
+  JH_REQUIRE(m != nullptr, "%s: member %d is a null pointer", who, b);
+  if (m->kind == JH_TASK_FR3_PICK) { jh_set_error("%s: member %d is an fr3_pick model, which has no batched plan step (its phase is chosen per problem on the host)", who, b); return JH_ERR_UNSUPPORTED; }
+  if (m->kind == JH_TASK_LEAP_CUBE && m->kernel_gen != 3) { jh_set_error("%s: member %d runs kernel_gen %d: only kernel generation 3 of the leap family has a batched launch", who, b, m->kernel_gen); return JH_ERR_UNSUPPORTED; }
+  if (m->kind != JH_TASK_CARTPOLE && m->kind != JH_TASK_CYLINDER_PUSH && m->kind != JH_TASK_LEAP_CUBE) { jh_set_error("%s: member %d: no batched kernel for this model (kind %d)", who, b, m->kind); return JH_ERR_UNSUPPORTED; }
+  if (m != m0) {
+#define JH_SET_SAME(field, fmt)                                                                                                                                    \
+  JH_REQUIRE(m->field == m0->field, "%s: member %d differs from the set's member 0 in " #field " (" fmt " against " fmt ")", who, b, m->field, m0->field)
+    JH_SET_SAME(device, "%d"); JH_SET_SAME(kind, "%d"); JH_SET_SAME(nq, "%d"); JH_SET_SAME(nv, "%d"); JH_SET_SAME(nu, "%d"); JH_SET_SAME(ns, "%d"); JH_SET_SAME(ntaskparam, "%d");
+    JH_SET_SAME(nf, "%zu"); JH_SET_SAME(ni, "%zu");
+    if (m->h_i != m0->h_i) {
+      size_t w = 0;
+      while (w < m->h_i.size() && m->h_i[w] == m0->h_i[w]) w++;
+      jh_set_error("%s: member %d differs from the set's member 0 in the int section h_i (word %zu: %d against %d): topology, pair lists and lane lists are one for the launch", who, b, w, m->h_i[w], m0->h_i[w]);
+      return JH_ERR_INVALID;
+    }
+    JH_SET_SAME(kernel_gen, "%d"); JH_SET_SAME(contact_capacity, "%d"); JH_SET_SAME(cylinders, "%d"); JH_SET_SAME(self_collision, "%d"); JH_SET_SAME(rollout_schedule, "%d");
+    JH_SET_SAME(plan_step_launches, "%d");
+#undef JH_SET_SAME
+  }
+  JH_REQUIRE(m->h_f.size() == m->nf && m->d_f, "%s: member %d has no float section of nf = %zu floats", who, b, m->nf);
+  if (m->kind == JH_TASK_LEAP_CUBE) {  // the single-call launcher's own acceptance test, on this member's floats (model_is_leap reads h_f: an isotropic cube inertia)
+    const bool ok = m->cylinders > 0 ? jh_engine5_accepts_cyl(m) : m->contact_capacity > 48 ? jh_engine5_accepts_cap64(m) : jh_engine5_accepts(m);
+    if (!ok) {
+      jh_set_error("%s: member %d: the leap kernel does not accept this image (dimensions, table sizes, or h_f: the cube's inertia must be isotropic)", who, b);
+      return JH_ERR_UNSUPPORTED;
+    }
+  }
+  return JH_OK;
+}
+
+static int model_set_upload(jh_model_set* s, int b, const jh_model* m) {
+  if (s->nf) JH_HIP(hipMemcpy(s->d_images + (size_t)b * s->stride, m->d_f, 4 * s->nf, hipMemcpyDeviceToDevice));  // (synchronous: not for the plan loop)
+  s->hf[b] = m->h_f;
+  return JH_OK;
+}
+
+extern "C" int jh_model_set_create(const jh_model* const* models, int B, jh_model_set** out) {
+  JH_REQUIRE(models && out, "model_set_create: null pointer");
+  JH_REQUIRE(B >= 1, "model_set_create: B must be at least 1 (B=%d)", B);
+  JH_REQUIRE(B <= 65535, "model_set_create: B = %d exceeds the 65535 problems of a launch (the grid's second dimension)", B);
+  for (int b = 0; b < B; b++) if (int rc = model_set_member("model_set_create", models[0], models[b], b)) return rc;
+  const jh_model* m0 = models[0];
+  JH_HIP(hipSetDevice(m0->device));
+  jh_model_set* s = new jh_model_set();
+  s->B = B; s->nf = m0->nf; s->stride = (m0->nf + 63) / 64 * 64; s->d_images = nullptr; s->m0 = m0; s->hf.resize(B);
+  if (s->stride == 0) s->stride = 64;
+  hipError_t e = hipMalloc(&s->d_images, 4 * s->stride * (size_t)B);
+  if (e == hipSuccess) e = hipMemset(s->d_images, 0, 4 * s->stride * (size_t)B);  // (the padding between the images is never read; zero all the same)
+  int rc = JH_OK;
+  if (e != hipSuccess) { jh_set_error("model_set_create: device allocation failed: %s", hipGetErrorString(e)); rc = JH_ERR_HIP; }
+  for (int b = 0; b < B && rc == JH_OK; b++) rc = model_set_upload(s, b, models[b]);
+  if (rc != JH_OK) { if (s->d_images) (void)hipFree(s->d_images); delete s; return rc; }
+  *out = s;
+  return JH_OK;
+}
+
+extern "C" int jh_model_set_update(jh_model_set* s, int b, const jh_model* model) {
+  JH_REQUIRE(s && model, "model_set_update: null pointer");
+  JH_REQUIRE(b >= 0 && b < s->B, "model_set_update: member %d of a set of %d", b, s->B);
+  // (a new member 0 is held to the old one, which the others were held to; it then leads the set)
+  if (int rc = model_set_member("model_set_update", s->m0, model, b)) return rc;
+  JH_HIP(hipSetDevice(s->m0->device));
+  if (int rc = model_set_upload(s, b, model)) return rc;
+  if (b == 0) s->m0 = model;
+  return JH_OK;
+}
+
+extern "C" int jh_model_set_info(const jh_model_set* s, int* out) {
+  JH_REQUIRE(s && out, "model_set_info: null pointer");
+  int differ = 0;
+  for (int b = 1; b < s->B; b++) differ += s->hf[b].size() != s->hf[0].size() || memcmp(s->hf[b].data(), s->hf[0].data(), 4 * s->hf[0].size()) != 0;
+  out[0] = s->B; out[1] = (int)s->nf; out[2] = (int)s->stride; out[3] = differ;
+  return JH_OK;
+}
+
+extern "C" void jh_model_set_destroy(jh_model_set* s) {
+  if (!s) return;
+  if (s->d_images) (void)hipFree(s->d_images);
+  delete s;
+}
+
+extern "C" int jh_plan_step_batch_models(const jh_model_set* set, void* blk_dev, const void* blk_host, size_t blk_bytes, size_t blk_stride_bytes, int o_nominal, int o_sigma, int o_tp, int o_lohi,
+                                         const float* noise, int ldn, size_t noise_stride_floats, const float* W, int N, int H, int K, float* costs, float* trace, int mode, float lambda,
+                                         int k, int tie_high, int E, int row_floats, int colmajor, float* scratch, float* out, size_t out_stride_floats, void* out_host_mark,
+                                         void* const* timing, void* stream) {
+  JH_REQUIRE(set != nullptr, "plan_step_batch_models: null pointer");
+  return plan_step_batch("plan_step_batch_models", set->m0, set->d_images, (long long)set->stride, set->B, blk_dev, blk_host, blk_bytes, blk_stride_bytes, o_nominal, o_sigma, o_tp, o_lohi, noise, ldn,
+                         noise_stride_floats, W, N, H, K, costs, trace, mode, lambda, k, tie_high, E, row_floats, colmajor, scratch, out, out_stride_floats, out_host_mark, timing, stream);
 }
 
 // The update alone for B problems whose costs are given (the materialise path of a fleet: the Spot policy rollout, judo_amd/fleet.py): jh_plan_step_batch's last stage --

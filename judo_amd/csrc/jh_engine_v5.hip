@@ -437,8 +437,9 @@ __device__ __forceinline__ bool chain_elim_order(int cmask, int c, int& level, i
 // re-stage a workgroup's task parameters per group): B independent problems in one launch (jh_plan_step_batch), grid (groups of a problem, B).  A workgroup stages sTp once,
 // so it belongs to one problem, blockIdx.y; everything a problem owns -- its packed block (x0, nominal, sigma, task parameters, bounds: `batch_blk` floats apart), its noise
 // (`batch_noise` floats apart), its costs, trace rows and overflow rows (N rollouts apart) -- is reached by offsetting the kernel's pointers once, at the top, with
-// arithmetic on kernel arguments and blockIdx.y alone: the bases stay in SGPRs, and a rollout's code below is the single launch's.  The other instantiations ignore the
-// two strides and compile to the code they had without them.
+// arithmetic on kernel arguments and blockIdx.y alone: the bases stay in SGPRs, and a rollout's code below is the single launch's.  A model set
+// (jh_plan_step_batch_models) gives every problem its own image of the float section as well, `batch_image` floats apart (0: one image for all); the int section --
+// topology, pair lists, lane lists -- is one for the launch.  The other instantiations ignore the three strides and compile to the code they had without them.
 template <bool MATERIALIZE, int WPB, bool SELF, bool PERSIST = false, bool BATCH = false>
 __global__ __launch_bounds__(WAVE * WPB, WAVES_PER_EU) void k_leap_v5(const float* __restrict__ gF, const int* __restrict__ gI, const float* __restrict__ x0, int x0_batched,
                                                    const float* __restrict__ nominal, const float* __restrict__ noise, int ldn,
@@ -446,12 +447,12 @@ __global__ __launch_bounds__(WAVE * WPB, WAVES_PER_EU) void k_leap_v5(const floa
                                                    const float* __restrict__ tp, int N, int n_offset, int H, int K, float* __restrict__ costs,
                                                    float* __restrict__ knots_out, const float* __restrict__ controls, float* __restrict__ states,
                                                    float* __restrict__ sensors, int* __restrict__ stats, int dshift_, float* __restrict__ trace, float* __restrict__ ovf_all, unsigned* __restrict__ head,
-                                                   long long batch_blk, long long batch_noise) {
+                                                   long long batch_blk, long long batch_noise, long long batch_image) {
   static_assert(!BATCH || (!MATERIALIZE && !PERSIST), "batched launches are fused launches on the static grid");
   if constexpr (BATCH) {
     const long long pb = blockIdx.y;
     x0 += pb * batch_blk; nominal += pb * batch_blk; sigma += pb * batch_blk; lohi += pb * batch_blk; tp += pb * batch_blk;
-    noise += pb * batch_noise; costs += pb * N;
+    noise += pb * batch_noise; costs += pb * N; gF += pb * batch_image;
     if (trace) trace += pb * N * H * 15;
     if (NOVF > 0 && ovf_all) ovf_all += pb * N * (NOVF * POOL_F);  // (the overflow rows are indexed by rollout: a problem's N rows behind the one before)
   }
@@ -1841,7 +1842,7 @@ int JH_V5_NAME(jh_engine5_rollout_cost)(const jh_model* m, const float* x0, cons
   if (scratch && ovf_bytes > 0) ovf = scratch + (head ? 4 : 0);
 #define JH_V5_LAUNCH_COST(SELF_, PERSIST_)                                                                                                                                        \
   hipLaunchKernelGGL((k_leap_v5<false, WAVES_PER_BLOCK, SELF_, PERSIST_>), dim3(grid), dim3(WAVE * WAVES_PER_BLOCK), 0, st, m->d_f, m->d_i, x0, 0, nominal, noise, ldn, sigma, W, \
-                     lohi, tp, N, n_offset, H, K, costs, knots_out, (const float*)nullptr, (float*)nullptr, (float*)nullptr, m->d_stats, dshift, trace, ovf, head, 0ll, 0ll)
+                     lohi, tp, N, n_offset, H, K, costs, knots_out, (const float*)nullptr, (float*)nullptr, (float*)nullptr, m->d_stats, dshift, trace, ovf, head, 0ll, 0ll, 0ll)
   if (m->self_collision && m->h_i[17] > 0) { if (persist) JH_V5_LAUNCH_COST(true, true); else JH_V5_LAUNCH_COST(true, false); }
   else { if (persist) JH_V5_LAUNCH_COST(false, true); else JH_V5_LAUNCH_COST(false, false); }
 #undef JH_V5_LAUNCH_COST
@@ -1859,18 +1860,20 @@ int JH_V5_NAME(jh_engine5_materialize)(const jh_model* m, const float* x0, int x
   if (m->self_collision && m->h_i[17] > 0)
     hipLaunchKernelGGL((k_leap_v5<true, WAVES_PER_BLOCK, true>), dim3(grid), dim3(WAVE * WAVES_PER_BLOCK), 0, st, m->d_f, m->d_i, x0, x0_batched, (const float*)nullptr, (const float*)nullptr, 0,
                        (const float*)nullptr, (const float*)nullptr, (const float*)nullptr, (const float*)nullptr, N, 0, H, 0, (float*)nullptr, (float*)nullptr,
-                       controls, states, sensors, m->d_stats, dshift, (float*)nullptr, ovf, (unsigned*)nullptr, 0ll, 0ll);
+                       controls, states, sensors, m->d_stats, dshift, (float*)nullptr, ovf, (unsigned*)nullptr, 0ll, 0ll, 0ll);
   else
     hipLaunchKernelGGL((k_leap_v5<true, WAVES_PER_BLOCK, false>), dim3(grid), dim3(WAVE * WAVES_PER_BLOCK), 0, st, m->d_f, m->d_i, x0, x0_batched, (const float*)nullptr, (const float*)nullptr, 0,
                        (const float*)nullptr, (const float*)nullptr, (const float*)nullptr, (const float*)nullptr, N, 0, H, 0, (float*)nullptr, (float*)nullptr,
-                       controls, states, sensors, m->d_stats, dshift, (float*)nullptr, ovf, (unsigned*)nullptr, 0ll, 0ll);
+                       controls, states, sensors, m->d_stats, dshift, (float*)nullptr, ovf, (unsigned*)nullptr, 0ll, 0ll, 0ll);
   return jh_launch_done(ovf, st);
 }
 
 // (Defined last in the file: the batched instantiations are emitted behind every other kernel and shift none of them in the code object.)
 // B problems in one launch (jh_plan_step_batch): the static grid with the problem in its second dimension.  x0 ... tp are problem 0's; `blk_stride` / `noise_stride` floats
-// lead to the next problem's.  The latency shift is chosen from B * N, the rollouts of the launch (the bits do not depend on it), and there is no queue.
-int JH_V5_NAME(jh_engine5_rollout_cost_batch)(const jh_model* m, int B, const float* x0, const float* nominal, const float* sigma, const float* lohi, const float* tp, long long blk_stride,
+// lead to the next problem's, and `image_stride` floats from `images`, problem 0's float section, to the next problem's (m->d_f and 0 where the problems share the model;
+// a model set's members passed jh_engine5_accepts one by one when the set was made).  The latency shift is chosen from B * N, the rollouts of the launch (the bits do
+// not depend on it), and there is no queue.
+int JH_V5_NAME(jh_engine5_rollout_cost_batch)(const jh_model* m, const float* images, long long image_stride, int B, const float* x0, const float* nominal, const float* sigma, const float* lohi, const float* tp, long long blk_stride,
                                   const float* noise, int ldn, long long noise_stride, const float* W, int N, int H, int K, float* costs, float* trace, hipStream_t st) {
   if (!model_is_leap(m)) { jh_set_error("plan_step_batch: the cooperative engine kernel is instantiated for leap_cube only"); return JH_ERR_UNSUPPORTED; }
   if ((m->cylinders > 0) != (JH_V5_CYL != 0)) { jh_set_error("plan_step_batch: an image with cylinder geoms runs on the cylinder build of the leap kernel and no other image does (%d cylinders)", m->cylinders); return JH_ERR_UNSUPPORTED; }
@@ -1880,9 +1883,12 @@ int JH_V5_NAME(jh_engine5_rollout_cost_batch)(const jh_model* m, int B, const fl
   const size_t ovf_bytes = NOVF > 0 ? (size_t)B * N * NOVF * POOL_F * sizeof(float) : 0;  // one row per rollout of every problem for the contacts above the LDS pool
   float* ovf = ovf_bytes > 0 ? jh_launch_scratch(m, ovf_bytes, st) : nullptr;  // (nullptr: the LDS capacity alone, drops and the fallback counted)
 #define JH_V5_LAUNCH_BATCH(SELF_)                                                                                                                                                  \
-  hipLaunchKernelGGL((k_leap_v5<false, WAVES_PER_BLOCK, SELF_, false, true>), dim3(grid, B), dim3(WAVE * WAVES_PER_BLOCK), 0, st, m->d_f, m->d_i, x0, 0, nominal, noise, ldn, sigma, W, \
-                     lohi, tp, N, 0, H, K, costs, (float*)nullptr, (const float*)nullptr, (float*)nullptr, (float*)nullptr, m->d_stats, dshift, trace, ovf, (unsigned*)nullptr, blk_stride, noise_stride)
+  hipLaunchKernelGGL((k_leap_v5<false, WAVES_PER_BLOCK, SELF_, false, true>), dim3(grid, B), dim3(WAVE * WAVES_PER_BLOCK), 0, st, images, m->d_i, x0, 0, nominal, noise, ldn, sigma, W, \
+                     lohi, tp, N, 0, H, K, costs, (float*)nullptr, (const float*)nullptr, (float*)nullptr, (float*)nullptr, m->d_stats, dshift, trace, ovf, (unsigned*)nullptr, blk_stride, noise_stride, image_stride)
   if (m->self_collision && m->h_i[17] > 0) JH_V5_LAUNCH_BATCH(true); else JH_V5_LAUNCH_BATCH(false);
 #undef JH_V5_LAUNCH_BATCH
   return jh_launch_done(ovf, st);
 }
+
+// What the launchers above ask of a model before they run it, for a caller that must know in advance (jh_model_set_create: every member of a set, on its own floats).
+bool JH_V5_NAME(jh_engine5_accepts)(const jh_model* m) { return model_is_leap(m) && (m->cylinders > 0) == (JH_V5_CYL != 0); }

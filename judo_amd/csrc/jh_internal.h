@@ -139,13 +139,19 @@ int jh_engine5_rollout_cost_cyl(const jh_model* m, const float* x0, const float*
 int jh_engine5_materialize_cyl(const jh_model* m, const float* x0, int x0_batched, const float* controls, int N, int H, float* states, float* sensors,
                                hipStream_t st);
 
-// the leap kernel for B problems in one launch (jh_plan_step_batch): x0 ... tp of problem 0, `blk_stride` / `noise_stride` floats to the next problem's
-int jh_engine5_rollout_cost_batch(const jh_model* m, int B, const float* x0, const float* nominal, const float* sigma, const float* lohi, const float* tp, long long blk_stride,
+// the leap kernel for B problems in one launch (jh_plan_step_batch): x0 ... tp of problem 0, `blk_stride` / `noise_stride` floats to the next problem's; `images`: problem
+// 0's float section, `image_stride` floats to the next problem's (m->d_f and 0: one image for all)
+int jh_engine5_rollout_cost_batch(const jh_model* m, const float* images, long long image_stride, int B, const float* x0, const float* nominal, const float* sigma, const float* lohi, const float* tp, long long blk_stride,
                                   const float* noise, int ldn, long long noise_stride, const float* W, int N, int H, int K, float* costs, float* trace, hipStream_t st);
-int jh_engine5_rollout_cost_batch_cap64(const jh_model* m, int B, const float* x0, const float* nominal, const float* sigma, const float* lohi, const float* tp, long long blk_stride,
+int jh_engine5_rollout_cost_batch_cap64(const jh_model* m, const float* images, long long image_stride, int B, const float* x0, const float* nominal, const float* sigma, const float* lohi, const float* tp, long long blk_stride,
                                         const float* noise, int ldn, long long noise_stride, const float* W, int N, int H, int K, float* costs, float* trace, hipStream_t st);
-int jh_engine5_rollout_cost_batch_cyl(const jh_model* m, int B, const float* x0, const float* nominal, const float* sigma, const float* lohi, const float* tp, long long blk_stride,
+int jh_engine5_rollout_cost_batch_cyl(const jh_model* m, const float* images, long long image_stride, int B, const float* x0, const float* nominal, const float* sigma, const float* lohi, const float* tp, long long blk_stride,
                                       const float* noise, int ldn, long long noise_stride, const float* W, int N, int H, int K, float* costs, float* trace, hipStream_t st);
+
+// does the build's launcher accept this model (its own acceptance test, on the model's own image)?
+bool jh_engine5_accepts(const jh_model* m);
+bool jh_engine5_accepts_cap64(const jh_model* m);
+bool jh_engine5_accepts_cyl(const jh_model* m);
 
 // jh_engine_v3.hip: cooperative kernel for fr3_pick (serial arm with a two-finger fork + free box, pyramidal cones)
 bool jh_model_is_fr3(const jh_model* m);

@@ -235,13 +235,14 @@ __global__ __launch_bounds__(jh_upd::kUB) void k_plan_step(const float* __restri
   jh_upd::update_tail_body(a);
 }
 // B plan steps in one launch (jh_plan_step_batch): blockIdx.y picks the problem; its packed block (x0, nominal, sigma, task params, bounds), noise, costs, trace buffer,
-// update scratch and output block lie the batch's strides behind problem 0's.  The bodies are the ones above, so a problem's bits are those of its own k_plan_step launch.
+// update scratch and output block lie the batch's strides behind problem 0's, and so does its image of the model constants (s.image floats; 0: one image for all).  The
+// bodies are the ones above, so a problem's bits are those of its own k_plan_step launch.
 template <class T>
 __global__ __launch_bounds__(jh_upd::kUB) void k_plan_step_batch(const float* __restrict__ P, const float* __restrict__ x0, const float* __restrict__ W, const float* __restrict__ tp, int H, int K,
                                                                  jh_upd::TailArgs base, jh_upd::BatchArgs s) {
   const int b = blockIdx.y;
   const jh_upd::TailArgs a = jh_upd::batch_problem(base, s, b);
-  rollout_cost_body<T, jh_upd::kUB>(P, x0 + b * s.blk, a.src.nominal, a.src.noise, a.src.ldn, a.src.sigma, W, a.src.lohi, tp + b * s.blk, a.N, a.n_offset, H, K, const_cast<float*>(a.costs), nullptr,
+  rollout_cost_body<T, jh_upd::kUB>(P + b * s.image, x0 + b * s.blk, a.src.nominal, a.src.noise, a.src.ldn, a.src.sigma, W, a.src.lohi, tp + b * s.blk, a.N, a.n_offset, H, K, const_cast<float*>(a.costs), nullptr,
                                     const_cast<float*>(a.trace));
   __syncthreads();
   jh_upd::batch_done(s, jh_upd::update_tail_body(a));
@@ -252,7 +253,7 @@ __global__ __launch_bounds__(kBlock) void k_rollout_cost_batch(const float* __re
                                                                jh_upd::TailArgs base, jh_upd::BatchArgs s) {
   const int b = blockIdx.y;
   const jh_upd::TailArgs a = jh_upd::batch_problem(base, s, b);
-  rollout_cost_body<T, kBlock>(P, x0 + b * s.blk, a.src.nominal, a.src.noise, a.src.ldn, a.src.sigma, W, a.src.lohi, tp + b * s.blk, a.N, a.n_offset, H, K, const_cast<float*>(a.costs), nullptr,
+  rollout_cost_body<T, kBlock>(P + b * s.image, x0 + b * s.blk, a.src.nominal, a.src.noise, a.src.ldn, a.src.sigma, W, a.src.lohi, tp + b * s.blk, a.N, a.n_offset, H, K, const_cast<float*>(a.costs), nullptr,
                                const_cast<float*>(a.trace));
 }
 #ifdef JH_TAIL_TICKS
@@ -387,33 +388,33 @@ int launch_plan_step(const jh_model* m, const float* x0, const float* W, const f
 }
 
 template <class T>
-int launch_plan_step_batch(const jh_model* m, const float* x0, const float* W, const float* tp, int H, int K, const jh_upd::TailArgs& a, const jh_upd::BatchArgs& s, hipStream_t st) {
+int launch_plan_step_batch(const float* P, const float* x0, const float* W, const float* tp, int H, int K, const jh_upd::TailArgs& a, const jh_upd::BatchArgs& s, hipStream_t st) {
   constexpr int BS = jh_upd::kUB;
   size_t lds = sizeof(float) * ((size_t)H * K + (size_t)K * T::NU * BS + T::NP + T::NTP + T::NX);
   JH_REQUIRE(lds <= 48 * 1024, "plan_step_batch: H*K too large for the LDS staging of the one-launch plan step (%zu bytes)", lds);
-  hipLaunchKernelGGL(k_plan_step_batch<T>, dim3((a.N + BS - 1) / BS, s.B), dim3(BS), lds, st, m->d_f, x0, W, tp, H, K, a, s);
+  hipLaunchKernelGGL(k_plan_step_batch<T>, dim3((a.N + BS - 1) / BS, s.B), dim3(BS), lds, st, P, x0, W, tp, H, K, a, s);
   JH_HIP(hipGetLastError());
   return JH_OK;
 }
 
 template <class T>
-int launch_cost_batch(const jh_model* m, const float* x0, const float* W, const float* tp, int H, int K, const jh_upd::TailArgs& a, const jh_upd::BatchArgs& s, hipStream_t st) {
+int launch_cost_batch(const float* P, const float* x0, const float* W, const float* tp, int H, int K, const jh_upd::TailArgs& a, const jh_upd::BatchArgs& s, hipStream_t st) {
   size_t lds = sizeof(float) * ((size_t)H * K + (size_t)K * T::NU * kBlock + T::NP + T::NTP + T::NX);
   JH_REQUIRE(lds <= 64 * 1024, "plan_step_batch: H*K too large for the LDS staging (%zu bytes)", lds);
-  hipLaunchKernelGGL(k_rollout_cost_batch<T>, dim3((a.N + kBlock - 1) / kBlock, s.B), dim3(kBlock), lds, st, m->d_f, x0, W, tp, H, K, a, s);
+  hipLaunchKernelGGL(k_rollout_cost_batch<T>, dim3((a.N + kBlock - 1) / kBlock, s.B), dim3(kBlock), lds, st, P, x0, W, tp, H, K, a, s);
   JH_HIP(hipGetLastError());
   return JH_OK;
 }
 
 }  // namespace
 
-int jh_simple_plan_step_batch(const jh_model* m, const float* x0, const float* W, const float* tp, int H, int K, const jh_upd::TailArgs& a, const jh_upd::BatchArgs& s, hipStream_t st) {
-  if (m->kind == JH_TASK_CARTPOLE) return launch_plan_step_batch<Cartpole>(m, x0, W, tp, H, K, a, s, st);
-  return launch_plan_step_batch<CylinderPush>(m, x0, W, tp, H, K, a, s, st);
+int jh_simple_plan_step_batch(const jh_model* m, const float* P, const float* x0, const float* W, const float* tp, int H, int K, const jh_upd::TailArgs& a, const jh_upd::BatchArgs& s, hipStream_t st) {
+  if (m->kind == JH_TASK_CARTPOLE) return launch_plan_step_batch<Cartpole>(P, x0, W, tp, H, K, a, s, st);
+  return launch_plan_step_batch<CylinderPush>(P, x0, W, tp, H, K, a, s, st);
 }
-int jh_simple_rollout_cost_batch(const jh_model* m, const float* x0, const float* tp, const float* W, int H, int K, const jh_upd::TailArgs& a, const jh_upd::BatchArgs& s, hipStream_t st) {
-  if (m->kind == JH_TASK_CARTPOLE) return launch_cost_batch<Cartpole>(m, x0, W, tp, H, K, a, s, st);
-  return launch_cost_batch<CylinderPush>(m, x0, W, tp, H, K, a, s, st);
+int jh_simple_rollout_cost_batch(const jh_model* m, const float* P, const float* x0, const float* tp, const float* W, int H, int K, const jh_upd::TailArgs& a, const jh_upd::BatchArgs& s, hipStream_t st) {
+  if (m->kind == JH_TASK_CARTPOLE) return launch_cost_batch<Cartpole>(P, x0, W, tp, H, K, a, s, st);
+  return launch_cost_batch<CylinderPush>(P, x0, W, tp, H, K, a, s, st);
 }
 
 // can the plan step of this model run as one launch?  (closed-form models; the knots of a workgroup of 256 rollouts must fit the LDS staging next to the update's own 9 KB)

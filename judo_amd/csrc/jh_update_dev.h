@@ -327,11 +327,14 @@ __device__ __forceinline__ bool update_tail_body(const TailArgs& a) {
 // the problem's strides (a workgroup belongs to one problem; the tail takes its workgroup count from gridDim.x).  Each problem keeps its own ticket in its own scratch
 // block.  The completion word is a second level: the last workgroup of a problem bumps the batch counter behind a fence of its outputs, and the one that draws B - 1
 // resets the counter and stores the word behind a system-scope fence -- once, behind the last of the B problems.  B = 1 takes the same code.
+// A model set (jh_plan_step_batch_models) also gives every problem its own image of the model's float section: the kernels that read the model offset its base by
+// blockIdx.y * image once, next to the problem's record (k_update_tail_batch reads no model and ignores the field).
 struct BatchArgs {
   int B;
   long long blk, noise, costs, trace, scratch, out;  // floats from one problem's packed block / noise / costs / trace buffer / update scratch / output block to the next one's
   unsigned* counter;                                 // the batch ticket: word 1 of problem 0's scratch (zero before the first launch, left at zero)
   unsigned* done_flag; unsigned done_value;          // as TailArgs', for the whole batch (the per-problem records carry none)
+  long long image = 0;                               // floats from one problem's image of the model's float section to the next one's; 0: the problems share one image
 };
 // problem b's record from problem 0's: wave-uniform arithmetic on kernel arguments and blockIdx.y
 __device__ __forceinline__ TailArgs batch_problem(const TailArgs& base, const BatchArgs& s, int b) {
@@ -368,5 +371,6 @@ bool jh_simple_plan_step_fits(const jh_model* m, int H, int K);
 int jh_simple_plan_step(const jh_model* m, const float* x0, const float* W, const float* tp, int H, int K, const jh_upd::TailArgs& a, hipStream_t st);
 // the batched forms (jh_plan_step_batch): `a` is problem 0's record, `s` the strides; grid (workgroups of a problem, B)
 int jh_update_tail_batch_launch(const jh_upd::TailArgs& a, const jh_upd::BatchArgs& s, hipStream_t st);
-int jh_simple_plan_step_batch(const jh_model* m, const float* x0, const float* W, const float* tp, int H, int K, const jh_upd::TailArgs& a, const jh_upd::BatchArgs& s, hipStream_t st);
-int jh_simple_rollout_cost_batch(const jh_model* m, const float* x0, const float* tp, const float* W, int H, int K, const jh_upd::TailArgs& a, const jh_upd::BatchArgs& s, hipStream_t st);
+// (`P`: the float section of problem 0's model image, s.image floats to the next problem's -- m->d_f with s.image = 0 where the problems share the model)
+int jh_simple_plan_step_batch(const jh_model* m, const float* P, const float* x0, const float* W, const float* tp, int H, int K, const jh_upd::TailArgs& a, const jh_upd::BatchArgs& s, hipStream_t st);
+int jh_simple_rollout_cost_batch(const jh_model* m, const float* P, const float* x0, const float* tp, const float* W, int H, int K, const jh_upd::TailArgs& a, const jh_upd::BatchArgs& s, hipStream_t st);

@@ -1,6 +1,7 @@
 """Device plumbing: PyTorch-ROCm is used only as the container for device memory, streams and RCCL.
 
-`GpuModel` owns one `jh_model` handle (model constants resident in HBM) per (task, device).
+`GpuModel` owns one `jh_model` handle (model constants resident in HBM) per (task, device); `GpuModelSet` one `jh_model_set`: the float sections of B models of one
+structure side by side, for a batched plan step with a model image per problem.
 """
 
 from __future__ import annotations
@@ -195,5 +196,46 @@ class GpuModel:
             if getattr(self, "handle", None):
                 _lib.lib().jh_model_destroy(self.handle)
                 self.handle = None
+        except Exception:
+            pass
+
+
+class GpuModelSet:
+    """B `GpuModel`s whose images differ in the float section alone, as ONE device buffer for `jh_plan_step_batch_models` (include/judo_amd.h): problem b of the batched
+    plan step runs on `models[b]`'s constants.  The library checks the members (same dimensions, int section, kernel build and settings; each image acceptable to its
+    kernel) and raises ValueError / JudoAmdError naming the member and the field.  The set keeps its members alive: member 0's handle stays in use for everything but the
+    float sections, and its `stats()` collect the counters of the whole launch."""
+
+    def __init__(self, models) -> None:
+        self.models = list(models)
+        if not self.models:
+            raise ValueError("a model set needs at least one model")
+        handles = (C.c_void_p * len(self.models))(*[m.handle.value for m in self.models])
+        handle = C.c_void_p()
+        _lib.check(_lib.lib().jh_model_set_create(handles, len(self.models), C.byref(handle)), "jh_model_set_create")
+        self.handle = handle
+
+    def __len__(self) -> int:
+        return len(self.models)
+
+    def info(self) -> dict:
+        """`jh_model_set_info`: members, floats per image, floats from one image to the next, members whose image differs from member 0's."""
+        out = (C.c_int * 4)()
+        _lib.check(_lib.lib().jh_model_set_info(self.handle, out), "jh_model_set_info")
+        return {"B": int(out[0]), "image_floats": int(out[1]), "stride_floats": int(out[2]), "distinct_from_first": int(out[3])}
+
+    def update(self, b: int, model: GpuModel) -> None:
+        """Replace member b's image (`jh_model_set_update`: the same checks; synchronous -- between episodes, not in the plan loop)."""
+        _lib.check(_lib.lib().jh_model_set_update(self.handle, int(b), model.handle), "jh_model_set_update")
+        self.models[int(b)] = model
+
+    def close(self) -> None:
+        if getattr(self, "handle", None):
+            _lib.lib().jh_model_set_destroy(self.handle)
+            self.handle = None
+
+    def __del__(self) -> None:
+        try:
+            self.close()
         except Exception:
             pass

@@ -1,4 +1,4 @@
-"""B controllers of one model planned in ONE launch (`jh_plan_step_batch`, include/judo_amd.h).
+"""B controllers of one model planned in ONE launch (`jh_plan_step_batch` / `jh_plan_step_batch_models`, include/judo_amd.h).
 
 The reference runs one `Controller.update_action` (judo/controller/controller.py:210-299) per process; somebody with several robots, several goals or a
 domain-randomised sweep runs B of them back to back and pays B launch chains and B host round trips for work that fits the GPU at once.  A `ControllerFleet`
@@ -7,8 +7,11 @@ holds B ordinary `Controller` objects that share one `GpuModel`.  `fleet.update_
 `jh_plan_step_batch` and one `jh_download_end`, then every member's epilogue (denormalise, CEM sigma refit, `update_spline`, the staged trace records).
 Afterwards each member is bit for bit where its own `update_action()` would have left it: the kernels run the single plan step's code on offset pointers.
 
-What the members must share is what the launch shares: the model, N, K, H, the spline order, the trace count, the optimizer kind and its scalar arguments.
-Everything else -- state, time, goal and the other task parameters, seed or injected noise, CEM sigma -- is a member's own.
+What the members must share is what the launch shares: the model's structure, N, K, H, the spline order, the trace count, the optimizer kind and its scalar arguments.
+Everything else -- state, time, goal and the other task parameters, seed or injected noise, CEM sigma -- is a member's own.  So are the model's PHYSICS: members whose
+packed images differ in the float section alone (masses, inertias, friction, gains: `models.scaled_description`, `make_controller_fleet(..., descriptions=...)`) keep
+their own `GpuModel`, and the fleet plans them through one `GpuModelSet` and `jh_plan_step_batch_models`, a model image per problem.  The header and the int section
+of the image (dimensions, topology, pair lists), the kernel build and the self-collision setting stay shared.
 
 The Spot policy tasks have no `GpuModel` and no one-call plan step: their iteration is spline -> command mapping -> policy + plant rollout -> `Task.reward` -> update.  A fleet
 of them runs that chain ONCE for the B * n rollouts of its members (`jh_spline_controls_batch`, `jh_policy_rollout_batch`, `jh_update_fused_batch`) around one
@@ -27,8 +30,9 @@ import torch
 
 from judo_amd import _lib
 from judo_amd.controller import POLICY_OUTPUT_DIM, Controller, make_controller_for
-from judo_amd.device import current_stream_ptr
+from judo_amd.device import GpuModelSet, current_stream_ptr
 from judo_amd.distributed import world_info
+from judo_amd.models import image_sections, layout
 from judo_amd.optimizers import Optimizer, _NoiseStream
 from judo_amd.tasks import get_registered_tasks
 
@@ -127,9 +131,10 @@ class ControllerFleet:
             for c in self.controllers[1:]:  # one model image and one copy of the actor weights on the device for the whole fleet
                 c.rollout_backend.engine, c.rollout_backend.policy = first.rollout_backend.engine, first.rollout_backend.policy
             self._policy_out: torch.Tensor | None = None  # (B * n, 12): the members' `_last_policy_output` are views of it
-        for c in self.controllers[1:]:  # one image of the model constants on the device for the whole fleet
-            if c.model is not self.model:
+        for c in self.controllers[1:]:  # one image of the model constants on the device for every member whose image is member 0's, byte for byte
+            if c.model is not self.model and c.model._blob == self.model._blob:
                 c.model = c.task._gpu = c.rollout_backend.model = self.model
+        self._model_set: GpuModelSet | None = None  # members with images of their own (randomised physics): their float sections side by side, made at the first plan step
         self._bufs: _FleetBuffers | None = None
         self._bufs_key: tuple | None = None
 
@@ -176,8 +181,14 @@ class ControllerFleet:
             mine_e, want_e = c.rollout_backend.engine, first.rollout_backend.engine
             if mine_e is not want_e and bytes(mine_e._blob) != bytes(want_e._blob):
                 raise ValueError(f"fleet member {i} has another model image than member 0")
-        elif c.model is not first.model and (c.model._blob != first.model._blob or c.model.build() != first.model.build() or c.model.self_collision != first.model.self_collision):
-            raise ValueError(f"fleet member {i} has another model image or kernel build than member 0")
+        elif c.model is not first.model:
+            if c.model._blob != first.model._blob:  # images may differ in the float section alone: physics per problem, one structure for the launch
+                mine_s, want_s = image_sections(c.model._blob), image_sections(first.model._blob)
+                for name, x, y in zip(("header", "float section", "int section"), mine_s, want_s):
+                    if (x != y and name != "float section") or len(x) != len(y):
+                        raise ValueError(f"fleet member {i} has another model image or kernel build than member 0: the {name} of its image differs")
+            if c.model.build() != first.model.build() or c.model.self_collision != first.model.self_collision:
+                raise ValueError(f"fleet member {i} has another model image or kernel build than member 0: the kernel build or the self-collision setting differs")
         world, _ = world_info(c.group)
         nrm = c._current_normalizer()
         shape = c._iteration_shape(world, nrm)
@@ -190,6 +201,16 @@ class ControllerFleet:
             raise ValueError(f"fleet member {i} does not run its iteration {how} ({why}): only such controllers can share a launch")
 
     # ---- the plan step --------------------------------------------------------------------------------------------------------------------------------
+    def _models(self) -> GpuModelSet | None:
+        """None where every member plans on the fleet's one `GpuModel` (`jh_plan_step_batch`); else the set of the members' models, rebuilt when a member's model was
+        exchanged between plan steps."""
+        models = [c.model for c in self.controllers]
+        if all(m is self.model for m in models):
+            self._model_set = None
+        elif self._model_set is None or len(self._model_set.models) != len(models) or any(a is not b for a, b in zip(self._model_set.models, models)):
+            self._model_set = GpuModelSet(models)
+        return self._model_set
+
     def _buffers(self, key: tuple) -> _FleetBuffers:
         if self._bufs_key != key:
             self._bufs, self._bufs_key = _FleetBuffers(self.device, *key), key
@@ -228,6 +249,7 @@ class ControllerFleet:
             self._check_member(i, c, first)
         if first.task.uses_locomotion_policy:
             return self._update_action_policy()
+        model_set = self._models()
         plans = [c._begin_plan() for c in cs]
         # (a plan: N, K, nu, H, world, shard, normaliser, normalised nominal, W, x0, new knot times, fused optimizer?, trace elites, task params -- Controller._begin_plan)
         N, K, nu, H, _, _, _, _, W, _, _, _, E, tp0 = plans[0]
@@ -260,10 +282,16 @@ class ControllerFleet:
             fb.size_out(2 * K * nu + E_t * (2 + row))
             in_place = self.model.closed_form  # (the closed-form kernels read the host blocks in place and the host polls the completion word; the leap family uploads and keeps the stream's event)
             off = fb.offsets
-            st = lib.jh_plan_step_batch(self.model.handle, B, fb.host_ptr if in_place else fb.blk.data_ptr(), fb.host_ptr, 4 * fb.nblk, 4 * fb.blk_stride, off[1], off[2], off[3], off[4],
-                                        noise.data_ptr(), N, K * nu * N, _lib.ptr(W), N, H, K, costs.data_ptr(), fb.trace_buf.data_ptr() if nfl else None, mode, lam, k_el, tie, E_t,
-                                        row, colmajor, fb.scratch.data_ptr(), fb.out_host_ptr, fb.out_stride, fb.done.data_ptr() if in_place else fb.out_host_ptr, None, stream)
-            _lib.check(st, "jh_plan_step_batch")
+            if model_set is not None:  # a model image per problem: the same call without the model and B, which the set holds
+                st = lib.jh_plan_step_batch_models(model_set.handle, fb.host_ptr if in_place else fb.blk.data_ptr(), fb.host_ptr, 4 * fb.nblk, 4 * fb.blk_stride, off[1], off[2], off[3], off[4],
+                                                   noise.data_ptr(), N, K * nu * N, _lib.ptr(W), N, H, K, costs.data_ptr(), fb.trace_buf.data_ptr() if nfl else None, mode, lam, k_el, tie,
+                                                   E_t, row, colmajor, fb.scratch.data_ptr(), fb.out_host_ptr, fb.out_stride, fb.done.data_ptr() if in_place else fb.out_host_ptr, None, stream)
+                _lib.check(st, "jh_plan_step_batch_models")
+            else:
+                st = lib.jh_plan_step_batch(self.model.handle, B, fb.host_ptr if in_place else fb.blk.data_ptr(), fb.host_ptr, 4 * fb.nblk, 4 * fb.blk_stride, off[1], off[2], off[3], off[4],
+                                            noise.data_ptr(), N, K * nu * N, _lib.ptr(W), N, H, K, costs.data_ptr(), fb.trace_buf.data_ptr() if nfl else None, mode, lam, k_el, tie, E_t,
+                                            row, colmajor, fb.scratch.data_ptr(), fb.out_host_ptr, fb.out_stride, fb.done.data_ptr() if in_place else fb.out_host_ptr, None, stream)
+                _lib.check(st, "jh_plan_step_batch")
             _lib.check(lib.jh_download_end(), "jh_download_end")
             for i, (c, mb, shard, st_i) in enumerate(zip(cs, fb.members, shards, states)):
                 mb.blk_stale = in_place
@@ -368,23 +396,37 @@ class ControllerFleet:
 
     def solver_stats(self, reset: bool = True) -> dict:
         """`Controller.solver_stats` for the fleet.  The members share one engine (one `GpuModel`, or one `SpotTreeEngine`) and the counters live on it: they are fleet-wide,
-        and a member's own `solver_stats()` reads -- and resets -- the same fleet-wide counters, not that member's share."""
+        and a member's own `solver_stats()` reads -- and resets -- the same fleet-wide counters, not that member's share.  A fleet with a model image per member counts its
+        launches on member 0's model too."""
         return self.controllers[0].solver_stats(reset)
 
 
-def make_controller_fleet(task: str, optimizer: str, B: int, device: torch.device | None = None) -> ControllerFleet:
+def make_controller_fleet(task: str, optimizer: str, B: int, device: torch.device | None = None, descriptions: Sequence[dict] | None = None) -> ControllerFleet:
     """B controllers of the registered task and optimizer (`make_controller`, judo/controller/controller.py:404-442, B times) around ONE `GpuModel` -- or, for the Spot
-    policy tasks, ONE `SpotTreeEngine` and ONE `SpotLocomotionPolicy`."""
+    policy tasks, ONE `SpotTreeEngine` and ONE `SpotLocomotionPolicy`.
+
+    `descriptions`: B model descriptions, one per member (randomised physics: `models.scaled_description(task.desc, body_mass=..., geom_friction=..., actuator_kp=...)`).
+    Member i's task takes `descriptions[i]` before its first device use and keeps a `GpuModel` of its own; the fleet still plans in one launch, a model image per problem.
+    The descriptions must pack to images that differ in the float section alone; the Spot policy tasks and fr3_pick take none."""
     tasks = get_registered_tasks()
     if task not in tasks:
         raise ValueError(f"Task {task} not found in task registry.")
     if B < 1:
         raise ValueError("a fleet needs at least one controller")
+    if descriptions is not None and len(descriptions) != B:
+        raise ValueError(f"{len(descriptions)} descriptions for a fleet of {B}")
     members: list[Controller] = []
-    for _ in range(B):
+    for i in range(B):
         t = tasks[task][0]()
         share = None
-        if members and t.uses_locomotion_policy:
+        if descriptions is not None:
+            if t.uses_locomotion_policy:
+                raise ValueError("a Spot fleet is one policy rollout over all members' rows and shares one model image: it takes no per-member descriptions")
+            t.desc = descriptions[i]
+            t._layout, t._ctrlrange, t._jadr = layout(t.desc), None, None
+            if members and t.desc is members[0].task.desc:
+                t._gpu = members[0].model
+        elif members and t.uses_locomotion_policy:
             share = members[0].rollout_backend  # (Controller builds its PolicyRolloutBackend around that one's engine and policy)
         elif members:
             t._gpu = members[0].model  # (Task.gpu_model hands it out instead of packing and uploading the image again)

@@ -11,6 +11,7 @@ This is the product's own host code: numpy only, no oracle, no MuJoCo.
 
 from __future__ import annotations
 
+import copy
 import json
 import os
 import struct
@@ -379,3 +380,56 @@ def pack_model(desc: dict) -> bytes:
     from judo_amd.engine_model import pack_engine_model  # articulated-body engine (leap_cube, fr3_pick)
 
     return pack_engine_model(desc)
+
+
+# ----------------------------------------------------------------------------------------- randomised physics
+def _scale_named(items: list[dict], factors: dict | None, what: str, apply) -> None:
+    if not factors:
+        return
+    names = {it["name"] for it in items}
+    for name, factor in factors.items():
+        if name is not None and name not in names:
+            raise ValueError(f"scaled_description: no {what} named {name!r} (known: {sorted(names)})")
+        for it in items:
+            if name is None or it["name"] == name:
+                apply(it, float(factor))
+
+
+def scaled_description(desc: dict, *, body_mass: dict | None = None, geom_friction: dict | None = None, actuator_kp: dict | None = None) -> dict:
+    """A deep copy of `desc` with perturbed physics: the named bodies' mass and inertia scaled together (the same body, denser), the named geoms' sliding friction
+    scaled, the named actuators' `kp` scaled.  Each argument maps a name to a factor; the key `None` means every body / geom / actuator (named keys apply on top of it,
+    in the dict's order).  Unknown names raise ValueError; `desc` itself is not touched.
+
+    Nothing else in the description moves, so what changes in the packed image (`pack_model`) is words of its float section alone -- masses, inertias and the inverse
+    weights derived from them, friction coefficients, gains -- while the header and the int section (topology, pair lists, lane lists) stay byte for byte: such images
+    can share one batched launch (`device.GpuModelSet`, `ControllerFleet`, `make_controller_fleet(..., descriptions=...)`)."""
+    out = copy.deepcopy(desc)
+
+    def mass(b: dict, f: float) -> None:
+        b["mass"] = b["mass"] * f
+        b["inertia"] = [v * f for v in b["inertia"]]
+
+    def friction(g: dict, f: float) -> None:
+        g["friction"] = [g["friction"][0] * f] + list(g["friction"][1:])
+
+    def kp(a: dict, f: float) -> None:
+        a["kp"] = a["kp"] * f
+
+    _scale_named(out["bodies"], body_mass, "body", mass)
+    _scale_named(out["geoms"], geom_friction, "geom", friction)
+    _scale_named(out["actuators"], actuator_kp, "actuator", kp)
+    return out
+
+
+def image_sections(blob: bytes) -> tuple[bytes, bytes, bytes]:
+    """(header, float section, int section) of a packed image (`pack_model`; the layout of `_pack`): 64 header bytes, then `nfloat` fp32, then `nint` int32."""
+    blob = bytes(blob)
+    if len(blob) < 64:
+        raise ValueError(f"image_sections: {len(blob)} bytes are no model image (the header alone has 64)")
+    head = struct.unpack("<16I", blob[:64])
+    if head[0] != BLOB_MAGIC:
+        raise ValueError(f"image_sections: bad magic {head[0]:08x}")
+    nf, ni = head[8], head[9]
+    if len(blob) != 64 + 4 * (nf + ni):
+        raise ValueError(f"image_sections: {len(blob)} bytes, the header announces {64 + 4 * (nf + ni)}")
+    return blob[:64], blob[64 : 64 + 4 * nf], blob[64 + 4 * nf :]
