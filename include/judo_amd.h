@@ -292,6 +292,18 @@ int jh_model_set_create(const jh_model* const* models /* HOST array of B handles
 int jh_model_set_update(jh_model_set* set, int b, const jh_model* model);
 int jh_model_set_info(const jh_model_set* set, int* out /* HOST, 4 ints */);
 void jh_model_set_destroy(jh_model_set* set);
+
+/* The hand's pair tables (leap family; judo_amd/engine_model.py::hand_pair_tables): bit grids over two joint angles in the image's int section that tell the kernel which
+ * hand body pairs cannot touch at a step's pose.  jh_model_create refuses a malformed block (JH_ERR_BLOB).  A model set reads ONE int section, member 0's, so it keeps the
+ * tables only while every member agrees with member 0 on the tables and on everything they were computed from -- the hand bodies' frames, joint axes and ranges, the hand
+ * geoms' sizes and poses, the bodies' bounding volumes; members that differ only in the cube, masses, gains or friction keep them.  Otherwise the set's launches read a
+ * copy of the int section without tables (the same results, every pair tested).
+ * The two entry points below are DIAGNOSTIC: they report what the library decided and change nothing; tests and tools/diag use them.  (So is the description key
+ * "pair_tables": false, which packs an image without tables.)
+ *   jh_model_set_pair_tables   1: the set's launches use the tables, 0: they do not (or the images have none).
+ *   jh_pair_tables_shared      the same rule on two packed blobs, without a device: 1 if a set of the two keeps blob0's tables, 0 if not; negative: not a model blob. */
+int jh_model_set_pair_tables(const jh_model_set* set);
+int jh_pair_tables_shared(const void* blob0, size_t nbytes0, const void* blob, size_t nbytes);
 int jh_plan_step_batch_models(const jh_model_set* set, void* blk_dev, const void* blk_host, size_t blk_bytes, size_t blk_stride_bytes, int o_nominal, int o_sigma, int o_tp, int o_lohi,
                               const float* noise, int ldn, size_t noise_stride_floats, const float* W, int N, int H, int K, float* costs, float* trace, int mode, float lambda, int k,
                               int tie_high, int E, int row_floats, int colmajor, float* scratch, float* out, size_t out_stride_floats, void* out_host_mark, void* const* timing,

@@ -79,6 +79,8 @@ _SIGNATURES = {
     "jh_model_set_update": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p]),
     "jh_model_set_info": (C.c_int, [C.c_void_p, C.POINTER(C.c_int)]),
     "jh_model_set_destroy": (None, [C.c_void_p]),
+    "jh_model_set_pair_tables": (C.c_int, [C.c_void_p]),
+    "jh_pair_tables_shared": (C.c_int, [C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t]),
     "jh_plan_step_batch_models": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_size_t, C.c_int, C.c_int, C.c_int, C.c_int, f32p, C.c_int, C.c_size_t, f32p, C.c_int, C.c_int, C.c_int,
                                             f32p, f32p, C.c_int, C.c_float, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, f32p, f32p, C.c_size_t, C.c_void_p, C.c_void_p, C.c_void_p]),
     "jh_update_fused_batch": (C.c_int, [C.c_int, f32p, f32p, C.c_size_t, C.c_int, C.c_int, C.c_int, f32p, C.c_int, C.c_size_t, C.c_int, C.c_int, C.c_int, C.c_int, C.c_float, C.c_int, C.c_int, C.c_int,

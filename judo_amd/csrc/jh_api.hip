@@ -65,6 +65,67 @@ static int image_arm_pairs(const jh_blob_header& h, const int* I) {
   return n;
 }
 
+// The pair tables of a leap image (the hand's broad phase, jh_engine_v5.hip): header I[19] is the offset of [count, PT_MAX records of PT_I ints] behind everything else
+// in the int section, 0 in an image without them.  Ints of the block (0: none), or -1 with the error set when it is malformed: the kernel indexes lanes and
+// pair bits with what the records hold.
+static int image_pair_tables(const jh_blob_header& h, const int* I) {
+  constexpr int HEADER = 24, PT_SLOT = JH_PT_SLOT, PT_MAX = JH_PT_MAX, PT_I = JH_PT_I, LANES = 16;
+  if (h.nint < (uint32_t)HEADER || I[PT_SLOT] == 0) return 0;
+  const long o = I[PT_SLOT], len = JH_PT_LEN, nbp = I[17];
+  if (o < HEADER || o + len > (long)h.nint) { jh_set_error("model_create: the pair tables at int %ld (%ld ints) lie outside the int section of %u", o, len, h.nint); return -1; }
+  const int n = I[o];
+  if (n < 0 || n > PT_MAX) { jh_set_error("model_create: %d pair tables, at most %d", n, PT_MAX); return -1; }
+  for (int t = 0; t < PT_MAX; t++) {
+    const int* T = I + o + 1 + t * PT_I;
+    if (t >= n) { for (int k = 0; k < PT_I; k++) if (T[k] != 0) { jh_set_error("model_create: pair table %d is beyond the count of %d and not zero", t, n); return -1; } continue; }
+    float f[4]; memcpy(f, T + 3, sizeof(f));
+    if (T[0] < 0 || T[0] >= nbp || (t > 0 && T[0] <= T[-PT_I])) { jh_set_error("model_create: pair table %d names body pair %d of %ld (ascending, each once)", t, T[0], nbp); return -1; }
+    if (T[1] < 0 || T[1] >= LANES || T[2] < 0 || T[2] >= LANES) { jh_set_error("model_create: pair table %d names joints (%d, %d) of %d", t, T[1], T[2], LANES); return -1; }
+    if (!std::isfinite(f[0]) || !std::isfinite(f[2]) || !std::isfinite(f[1]) || !std::isfinite(f[3]) || !(f[1] > 0.f) || !(f[3] >= 0.f)) {
+      jh_set_error("model_create: pair table %d: grid origins (%g, %g) and inverse cell widths (%g, %g) must be finite, the first width positive", t, f[0], f[2], f[1], f[3]);
+      return -1;
+    }
+  }
+  return (int)len;
+}
+
+// May two images of one model set share the pair tables in the set's int section?  Only if the tables are the same words and everything they were computed from is:
+// the hand bodies' frames and joint axes, the joint ranges, every hand geom's size and pose, the bodies' bounding volumes.  (The cube, masses, gains and friction
+// are free to differ.)  Images without tables share "none".
+static bool pair_tables_shared(const std::vector<float>& F0, const std::vector<int>& I0, const std::vector<float>& F, const std::vector<int>& I) {
+  constexpr int HEADER = 24, PT_SLOT = JH_PT_SLOT, BODY_F = 32, DOF_F = 20, ACT_F = 8, GEOM_F = 20, NBC = 20;
+  if (I0.size() <= (size_t)PT_SLOT || I.size() != I0.size() || F.size() != F0.size() || I[PT_SLOT] != I0[PT_SLOT]) return false;
+  const long o = I0[PT_SLOT], len = JH_PT_LEN;
+  if (o == 0) return true;
+  if (o < HEADER || o + len > (long)I0.size() || memcmp(&I[o], &I0[o], 4 * len) != 0) return false;
+  const long NM = I0[0], nv = I0[2], nu = I0[4], NG = I0[5], oBS = I0[16];
+  const long oDof = HEADER + NM * BODY_F, oGeom = oDof + nv * DOF_F + nu * ACT_F;
+  if (NM < 1 || nv < 6 || nu < 0 || NG < 0 || oGeom + NG * GEOM_F > (long)F0.size() || oBS < 0 || oBS + NBC * 8 > (long)F0.size()) return false;
+  auto same = [&](long at, long n) { return memcmp(&F[at], &F0[at], 4 * n) == 0; };
+  for (long b = 1; b < NM; b++) if (!same(HEADER + b * BODY_F, 12) || !same(HEADER + b * BODY_F + 28, 3)) return false;  // frame in the parent (position, rotation), joint axis
+  for (long d = 6; d < nv; d++) if (!same(oDof + d * DOF_F + 6, 3)) return false;                                      // limited, range
+  for (long g = 0; g < NG; g++) if (!same(oGeom + g * GEOM_F, 16)) return false;                                       // size, position, rotation, bounding radius
+  return same(oBS, NBC * 8);                                                                                            // bounding sphere and box per hand body
+}
+
+static bool blob_sections(const void* blob, size_t nbytes, std::vector<float>& F, std::vector<int>& I) {
+  jh_blob_header h;
+  if (!blob || nbytes < sizeof(h)) return false;
+  memcpy(&h, blob, sizeof(h));
+  if (h.magic != JH_BLOB_MAGIC || nbytes != sizeof(h) + 4 * ((size_t)h.nfloat + h.nint)) return false;
+  const char* q = (const char*)blob + sizeof(h);
+  F.assign((const float*)q, (const float*)q + h.nfloat);
+  I.assign((const int*)(q + 4 * (size_t)h.nfloat), (const int*)(q + 4 * (size_t)h.nfloat) + h.nint);
+  return true;
+}
+
+// The model-set rule on two packed images, without a device: 1 if a set of the two keeps the pair tables of `blob0`, 0 if it runs without them.
+extern "C" int jh_pair_tables_shared(const void* blob0, size_t nbytes0, const void* blob, size_t nbytes) {
+  std::vector<float> F0, F; std::vector<int> I0, I;
+  JH_REQUIRE(blob_sections(blob0, nbytes0, F0, I0) && blob_sections(blob, nbytes, F, I), "pair_tables_shared: not a model blob");
+  return pair_tables_shared(F0, I0, F, I) ? 1 : 0;
+}
+
 extern "C" int jh_model_create(const void* blob, size_t nbytes, int device, jh_model** out) {
   JH_REQUIRE(blob && out, "model_create: null pointer");
   if (nbytes < sizeof(jh_blob_header)) { jh_set_error("model_create: blob too small (%zu bytes)", nbytes); return JH_ERR_BLOB; }
@@ -84,6 +145,7 @@ extern "C" int jh_model_create(const void* blob, size_t nbytes, int device, jh_m
     std::vector<int> I((const int*)(q + 4 * (size_t)h.nfloat), (const int*)(q + 4 * (size_t)h.nfloat) + h.nint);
     cylinders = image_cylinders(h, F.data(), I.data());
     if (cylinders < 0) return JH_ERR_BLOB;
+    if (h.kind == JH_TASK_LEAP_CUBE && image_pair_tables(h, I.data()) < 0) return JH_ERR_BLOB;
     if (cylinders > 0 && h.kind != JH_TASK_LEAP_CUBE) { jh_set_error("model_create: %d cylinder geoms, and only the leap kernel has a cylinder build", cylinders); return JH_ERR_BLOB; }
     if (h.kind == JH_TASK_FR3_PICK) {
       arm_pairs = image_arm_pairs(h, I.data());
@@ -460,8 +522,9 @@ extern "C" int jh_plan_step(const jh_model* m, void* blk_dev, const void* blk_ho
 // B plan steps of one model as ONE call (include/judo_amd.h): the B packed blocks go up in one copy (or are read in place), the kernels take the problem from blockIdx.y and
 // reach its buffers through strides, and one completion mark stands behind all of them.  Problem 0's launch record is built by the single call's own checks
 // (jh_update_tail_args); the kernels derive problem b's from it.  `images` / `image_stride`: the float section the rollout kernels read for problem 0 and the floats to
-// problem b + 1's from problem b's -- m->d_f and 0 for jh_plan_step_batch, a model set's buffer and stride for jh_plan_step_batch_models: one code path.
-static int plan_step_batch(const char* who, const jh_model* m, const float* images, long long image_stride, int B, void* blk_dev, const void* blk_host, size_t blk_bytes, size_t blk_stride_bytes,
+// problem b + 1's from problem b's -- m->d_f and 0 for jh_plan_step_batch, a model set's buffer and stride for jh_plan_step_batch_models: one code path.  `ints`: the int
+// section the leap kernel reads -- m->d_i, or a model set's copy without pair tables.
+static int plan_step_batch(const char* who, const jh_model* m, const float* images, long long image_stride, const int* ints, int B, void* blk_dev, const void* blk_host, size_t blk_bytes, size_t blk_stride_bytes,
                            int o_nominal, int o_sigma, int o_tp, int o_lohi, const float* noise, int ldn, size_t noise_stride_floats, const float* W, int N, int H, int K, float* costs,
                            float* trace, int mode, float lambda, int k, int tie_high, int E, int row_floats, int colmajor, float* scratch, float* out, size_t out_stride_floats,
                            void* out_host_mark, void* const* timing, void* stream) {
@@ -508,9 +571,9 @@ static int plan_step_batch(const char* who, const jh_model* m, const float* imag
   else {
     if (closed) rc = jh_simple_rollout_cost_batch(m, images, b, b + o_tp, W, H, K, a, s, st);
     else
-      rc = m->cylinders > 0           ? jh_engine5_rollout_cost_batch_cyl(m, images, image_stride, B, b, b + o_nominal, b + o_sigma, b + o_lohi, b + o_tp, s.blk, noise, ldn, s.noise, W, N, H, K, costs, trace, st)
-           : m->contact_capacity > 48 ? jh_engine5_rollout_cost_batch_cap64(m, images, image_stride, B, b, b + o_nominal, b + o_sigma, b + o_lohi, b + o_tp, s.blk, noise, ldn, s.noise, W, N, H, K, costs, trace, st)
-                                      : jh_engine5_rollout_cost_batch(m, images, image_stride, B, b, b + o_nominal, b + o_sigma, b + o_lohi, b + o_tp, s.blk, noise, ldn, s.noise, W, N, H, K, costs, trace, st);
+      rc = m->cylinders > 0           ? jh_engine5_rollout_cost_batch_cyl(m, images, image_stride, ints, B, b, b + o_nominal, b + o_sigma, b + o_lohi, b + o_tp, s.blk, noise, ldn, s.noise, W, N, H, K, costs, trace, st)
+           : m->contact_capacity > 48 ? jh_engine5_rollout_cost_batch_cap64(m, images, image_stride, ints, B, b, b + o_nominal, b + o_sigma, b + o_lohi, b + o_tp, s.blk, noise, ldn, s.noise, W, N, H, K, costs, trace, st)
+                                      : jh_engine5_rollout_cost_batch(m, images, image_stride, ints, B, b, b + o_nominal, b + o_sigma, b + o_lohi, b + o_tp, s.blk, noise, ldn, s.noise, W, N, H, K, costs, trace, st);
     if (rc == JH_OK && timing) JH_HIP(hipEventRecord((hipEvent_t)timing[1], st));
     if (rc == JH_OK) rc = jh_update_tail_batch_launch(a, s, st);
   }
@@ -525,7 +588,7 @@ extern "C" int jh_plan_step_batch(const jh_model* m, int B, void* blk_dev, const
                                   int tie_high, int E, int row_floats, int colmajor, float* scratch, float* out, size_t out_stride_floats, void* out_host_mark, void* const* timing,
                                   void* stream) {
   JH_REQUIRE(m != nullptr, "plan_step_batch: null pointer");
-  return plan_step_batch("plan_step_batch", m, m->d_f, 0, B, blk_dev, blk_host, blk_bytes, blk_stride_bytes, o_nominal, o_sigma, o_tp, o_lohi, noise, ldn, noise_stride_floats, W, N, H, K, costs, trace,
+  return plan_step_batch("plan_step_batch", m, m->d_f, 0, m->d_i, B, blk_dev, blk_host, blk_bytes, blk_stride_bytes, o_nominal, o_sigma, o_tp, o_lohi, noise, ldn, noise_stride_floats, W, N, H, K, costs, trace,
                          mode, lambda, k, tie_high, E, row_floats, colmajor, scratch, out, out_stride_floats, out_host_mark, timing, stream);
 }
 
@@ -537,7 +600,30 @@ struct jh_model_set {
   float* d_images;                     // B x stride floats on member 0's device
   const jh_model* m0;                  // member 0: the int section, the dimensions, the kernel build and settings, d_stats
   std::vector<std::vector<float>> hf;  // host copies of the members' float sections (jh_model_set_info: how many differ from member 0's)
+  std::vector<std::vector<int>> hi;    // ... and of their int sections (they differ in the pair tables at most)
+  int* d_i_plain;                      // member 0's int section with the pair tables' header slot zeroed: what the launch reads when the members cannot share the tables
+  bool tables;                         // every member may share member 0's pair tables (pair_tables_shared)
 };
+
+// The int sections of two members of a set agree but for the pair tables' block, which `pair_tables_shared` weighs: the word where they differ, or -1.
+static long int_sections_differ(const std::vector<int>& a, const std::vector<int>& b) {
+  constexpr long PT_SLOT = JH_PT_SLOT, PT_LEN = JH_PT_LEN;
+  if (a.size() != b.size()) return 0;
+  const long o = a.size() > (size_t)PT_SLOT && a[PT_SLOT] == b[PT_SLOT] && a[PT_SLOT] > 0 ? a[PT_SLOT] : -1;
+  for (long w = 0; w < (long)a.size(); w++) if (a[w] != b[w] && !(o >= 0 && w >= o && w < o + PT_LEN)) return w;
+  return -1;
+}
+
+// (Re)derive what follows from the members: whether they share the pair tables, and the int section without them.
+static int model_set_tables(jh_model_set* s, bool member0_changed) {
+  s->tables = true;
+  for (int b = 1; b < s->B && s->tables; b++) s->tables = pair_tables_shared(s->hf[0], s->hi[0], s->hf[b], s->hi[b]);
+  if (!member0_changed) return JH_OK;  // (the int section without tables is member 0's: uploaded when the set is made and when member 0 is replaced)
+  std::vector<int> plain = s->hi[0];
+  if (plain.size() > (size_t)JH_PT_SLOT) plain[JH_PT_SLOT] = 0;
+  if (!plain.empty()) JH_HIP(hipMemcpy(s->d_i_plain, plain.data(), 4 * plain.size(), hipMemcpyHostToDevice));
+  return JH_OK;
+}
 
 // May `m` be member `b` of a set whose member 0 is `m0` (b == 0: may `m` lead a set)?  JH_OK, or the status with the error set: it names the member and the field.
 static int model_set_member(const char* who, const jh_model* m0, const jh_model* m, int b) {
@@ -550,10 +636,8 @@ static int model_set_member(const char* who, const jh_model* m0, const jh_model*
   JH_REQUIRE(m->field == m0->field, "%s: member %d differs from the set's member 0 in " #field " (" fmt " against " fmt ")", who, b, m->field, m0->field)
     JH_SET_SAME(device, "%d"); JH_SET_SAME(kind, "%d"); JH_SET_SAME(nq, "%d"); JH_SET_SAME(nv, "%d"); JH_SET_SAME(nu, "%d"); JH_SET_SAME(ns, "%d"); JH_SET_SAME(ntaskparam, "%d");
     JH_SET_SAME(nf, "%zu"); JH_SET_SAME(ni, "%zu");
-    if (m->h_i != m0->h_i) {
-      size_t w = 0;
-      while (w < m->h_i.size() && m->h_i[w] == m0->h_i[w]) w++;
-      jh_set_error("%s: member %d differs from the set's member 0 in the int section h_i (word %zu: %d against %d): topology, pair lists and lane lists are one for the launch", who, b, w, m->h_i[w], m0->h_i[w]);
+    if (const long w = int_sections_differ(m->h_i, m0->h_i); w >= 0) {
+      jh_set_error("%s: member %d differs from the set's member 0 in the int section h_i (word %ld: %d against %d): topology, pair lists and lane lists are one for the launch", who, b, w, m->h_i[w], m0->h_i[w]);
       return JH_ERR_INVALID;
     }
     JH_SET_SAME(kernel_gen, "%d"); JH_SET_SAME(contact_capacity, "%d"); JH_SET_SAME(cylinders, "%d"); JH_SET_SAME(self_collision, "%d"); JH_SET_SAME(rollout_schedule, "%d");
@@ -573,7 +657,7 @@ static int model_set_member(const char* who, const jh_model* m0, const jh_model*
 
 static int model_set_upload(jh_model_set* s, int b, const jh_model* m) {
   if (s->nf) JH_HIP(hipMemcpy(s->d_images + (size_t)b * s->stride, m->d_f, 4 * s->nf, hipMemcpyDeviceToDevice));  // (synchronous: not for the plan loop)
-  s->hf[b] = m->h_f;
+  s->hf[b] = m->h_f; s->hi[b] = m->h_i;
   return JH_OK;
 }
 
@@ -585,14 +669,16 @@ extern "C" int jh_model_set_create(const jh_model* const* models, int B, jh_mode
   const jh_model* m0 = models[0];
   JH_HIP(hipSetDevice(m0->device));
   jh_model_set* s = new jh_model_set();
-  s->B = B; s->nf = m0->nf; s->stride = (m0->nf + 63) / 64 * 64; s->d_images = nullptr; s->m0 = m0; s->hf.resize(B);
+  s->B = B; s->nf = m0->nf; s->stride = (m0->nf + 63) / 64 * 64; s->d_images = nullptr; s->m0 = m0; s->hf.resize(B); s->hi.resize(B); s->d_i_plain = nullptr; s->tables = false;
   if (s->stride == 0) s->stride = 64;
   hipError_t e = hipMalloc(&s->d_images, 4 * s->stride * (size_t)B);
   if (e == hipSuccess) e = hipMemset(s->d_images, 0, 4 * s->stride * (size_t)B);  // (the padding between the images is never read; zero all the same)
   int rc = JH_OK;
   if (e != hipSuccess) { jh_set_error("model_set_create: device allocation failed: %s", hipGetErrorString(e)); rc = JH_ERR_HIP; }
+  if (rc == JH_OK && hipMalloc(&s->d_i_plain, 4 * (m0->ni ? m0->ni : 1)) != hipSuccess) { jh_set_error("model_set_create: device allocation failed"); rc = JH_ERR_HIP; }
   for (int b = 0; b < B && rc == JH_OK; b++) rc = model_set_upload(s, b, models[b]);
-  if (rc != JH_OK) { if (s->d_images) (void)hipFree(s->d_images); delete s; return rc; }
+  if (rc == JH_OK) rc = model_set_tables(s, true);
+  if (rc != JH_OK) { if (s->d_images) (void)hipFree(s->d_images); if (s->d_i_plain) (void)hipFree(s->d_i_plain); delete s; return rc; }
   *out = s;
   return JH_OK;
 }
@@ -605,7 +691,7 @@ extern "C" int jh_model_set_update(jh_model_set* s, int b, const jh_model* model
   JH_HIP(hipSetDevice(s->m0->device));
   if (int rc = model_set_upload(s, b, model)) return rc;
   if (b == 0) s->m0 = model;
-  return JH_OK;
+  return model_set_tables(s, b == 0);
 }
 
 extern "C" int jh_model_set_info(const jh_model_set* s, int* out) {
@@ -619,7 +705,13 @@ extern "C" int jh_model_set_info(const jh_model_set* s, int* out) {
 extern "C" void jh_model_set_destroy(jh_model_set* s) {
   if (!s) return;
   if (s->d_images) (void)hipFree(s->d_images);
+  if (s->d_i_plain) (void)hipFree(s->d_i_plain);
   delete s;
+}
+
+extern "C" int jh_model_set_pair_tables(const jh_model_set* s) {
+  JH_REQUIRE(s != nullptr, "model_set_pair_tables: null pointer");
+  return s->tables && s->hi[0].size() > (size_t)JH_PT_SLOT && s->hi[0][JH_PT_SLOT] > 0 ? 1 : 0;
 }
 
 extern "C" int jh_plan_step_batch_models(const jh_model_set* set, void* blk_dev, const void* blk_host, size_t blk_bytes, size_t blk_stride_bytes, int o_nominal, int o_sigma, int o_tp, int o_lohi,
@@ -627,7 +719,7 @@ extern "C" int jh_plan_step_batch_models(const jh_model_set* set, void* blk_dev,
                                          int k, int tie_high, int E, int row_floats, int colmajor, float* scratch, float* out, size_t out_stride_floats, void* out_host_mark,
                                          void* const* timing, void* stream) {
   JH_REQUIRE(set != nullptr, "plan_step_batch_models: null pointer");
-  return plan_step_batch("plan_step_batch_models", set->m0, set->d_images, (long long)set->stride, set->B, blk_dev, blk_host, blk_bytes, blk_stride_bytes, o_nominal, o_sigma, o_tp, o_lohi, noise, ldn,
+  return plan_step_batch("plan_step_batch_models", set->m0, set->d_images, (long long)set->stride, set->tables ? set->m0->d_i : set->d_i_plain, set->B, blk_dev, blk_host, blk_bytes, blk_stride_bytes, o_nominal, o_sigma, o_tp, o_lohi, noise, ldn,
                          noise_stride_floats, W, N, H, K, costs, trace, mode, lambda, k, tie_high, E, row_floats, colmajor, scratch, out, out_stride_floats, out_host_mark, timing, stream);
 }
 

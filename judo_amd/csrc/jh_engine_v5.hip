@@ -114,6 +114,7 @@ constexpr int CUBE = 17;          // contact side codes: 0 = static geometry, 1.
 constexpr int HITPAIR = 1 << 15;  // broad-phase survivors >= HITPAIR are hand-hand geom pairs (ga << 7 | gb, geom ids < 128), smaller ones are cube-vs-geom
 static_assert(MAXG <= 128, "hand geom pairs are packed into 14 bits");
 constexpr int MAXBP = 128;         // hand body pairs in the model image (leap_cube 106, caltech_leap_cube 122)
+constexpr int PT_SLOT = JH_PT_SLOT, PT_MAX = JH_PT_MAX, PT_I = JH_PT_I;  // pair tables of the hand's broad phase: at most four, nine ints each (pair, the two joints' lanes, grid origins and inverse cell widths as float bits, the 64-bit word)
 constexpr int MAXBPL = 96;        // hand body pairs whose bounding volumes overlap, per rollout and step (one byte each: pair indices < MAXBP <= 256)
 constexpr int NDH = 22 * 23 / 2;  // dense Hessian (packed lower) of a rollout whose contacts couple two finger chains
 constexpr int NV = 22, NQ = 23, NU = 16, NS = 31, NS_CALTECH = 23, NX = 45, NMB = 17;
@@ -563,14 +564,14 @@ __global__ __launch_bounds__(WAVE * WPB, WAVES_PER_EU) void k_leap_v5(const floa
 #endif
 #ifdef JH_V5_COUNT
   int cnt_dense = 0, cnt_it = 0, cnt_l2 = 0, cnt_bp = 0, cnt_hh = 0, cnt_cls[4] = {0, 0, 0, 0};
-  // the broad phase's lane use (tools/diag/count_broadphase.py; profiles/leap_broad_phase.md), stats[34..53].  Sums over rollout-steps (R) or wave-steps (W), maxima (M):
+  // the broad phase's lane use (tools/diag/count_broadphase.py; profiles/leap_broad_phase.md), stats[34..55].  Sums over rollout-steps (R) or wave-steps (W), maxima (M):
   // 34 R sphere survivors of level 1, 35 W their maximum over the wave, 36 W the maximum of the box survivors, 37 W passes of 16 body pairs with a sphere survivor (= runs of the
   // box region in the per-pair form), 38 W ceil(35 / 16) (= runs in the list form), 39 W trips of a loop over the near geoms of side A in level 2 (b) (the form before the combination passes: stays zero), 40 R body pairs that reach (b), 41 R their
   // combinations T = near A x near B, 42 W passes of 16 combinations, 43 W geom slots of the cube's sweep with a lane in the box region, 44 lanes in it, 45 M sphere survivors,
   // 46 M box survivors, 47 M T, 48 R steps without a sphere survivor, 49 / 50 R pairs in (b) with one near geom on side A / B, 51 R trips a rollout needs by itself,
   // 52 R steps with more than MAXBPL sphere survivors, 53 M MAXBP - sphere survivors (the fewest seen)
   enum { CB_SPH = 34, CB_SPHMAX, CB_BOXMAX, CB_L1PAIRPASS, CB_L1LISTPASS, CB_TRIPS, CB_BPAIRS, CB_T, CB_COMBOPASS, CB_CUBEBOX, CB_CUBEBOXLANES, CB_MSPH, CB_MBOX, CB_MT, CB_NOSPH, CB_ONEA, CB_ONEB,
-         CB_OWNTRIPS, CB_SPHOVER, CB_FEWSPH };
+         CB_OWNTRIPS, CB_SPHOVER, CB_FEWSPH, CB_TSAFE, CB_TDROP };  // 54 R pairs whose table reads safe, 55 R those of them with overlapping bounding spheres (dropped from the list)
 #define V5_CADD(k, v) do { if (stats) atomicAdd(stats + (k), (int)(v)); } while (0)
 #define V5_CMAX(k, v) do { if (stats) atomicMax(stats + (k), (int)(v)); } while (0)
 #endif
@@ -816,6 +817,34 @@ __global__ __launch_bounds__(WAVE * WPB, WAVES_PER_EU) void k_leap_v5(const floa
           if (lane == 0) { V5_CADD(CB_SPHMAX, nsm); V5_CADD(CB_L1PAIRPASS, npass); V5_CADD(CB_L1LISTPASS, (nsm + G - 1) / G); }
         }
 #endif
+        // pair tables (engine_model.py::hand_pair_tables): a body pair whose relative pose is a function of two joint angles carries an 8 x 8 bit grid over them, a set
+        // bit = no pose in the cell gives the pair a level-2 candidate.  Such a pair is taken out here, behind the sphere test and in front of its box test: it would have gone through level 2 and
+        // appended nothing, so S.hits[] keeps its entries and their order.  The angles are this step's `q` of the two joints' lanes -- what the kinematics above ran on --
+        // taken per row of 16 lanes (a wave's rollouts differ); an angle off the grid, or a NaN, reads as unsafe.  The records are wave-uniform: scalar loads.
+        // The header slot is read here, in every step, through an index the compiler cannot see through: held across the step loop it costs a register the loop does not have.
+        // Records beyond the image's count are zero and rule nothing out (a zero word), so the loop runs over all PT_MAX without reading the count.
+        int pt_slot = PT_SLOT; asm volatile("" : "+s"(pt_slot));
+        const int oPT = gI[pt_slot];  // (0: an image without tables)
+#pragma unroll 1
+        for (int t = 0; oPT > 0 && t < PT_MAX; t++) {
+          const int* T = gI + oPT + 1 + t * PT_I;
+          // (the two angles of each of the wave's four rows through scalar registers, then the own row's by select: eight v_readlane and no vector temporaries --
+          // two ds_bpermute cost the Newton loop three more scratch loads per iteration in the queue instantiation, profiles/leap_pair_tables.md section 3)
+          const int qi = __float_as_int(q), ja = T[1], jb = T[2];
+          const int a0 = __builtin_amdgcn_readlane(qi, ja), a1 = __builtin_amdgcn_readlane(qi, 16 + ja), a2 = __builtin_amdgcn_readlane(qi, 32 + ja), a3 = __builtin_amdgcn_readlane(qi, 48 + ja);
+          const int b0 = __builtin_amdgcn_readlane(qi, jb), b1 = __builtin_amdgcn_readlane(qi, 16 + jb), b2 = __builtin_amdgcn_readlane(qi, 32 + jb), b3 = __builtin_amdgcn_readlane(qi, 48 + jb);
+          const float qa = __int_as_float(r == 0 ? a0 : (r == 1 ? a1 : (r == 2 ? a2 : a3))), qb = __int_as_float(r == 0 ? b0 : (r == 1 ? b1 : (r == 2 ? b2 : b3)));
+          const float fa = (qa - __int_as_float(T[3])) * __int_as_float(T[4]), fb = (qb - __int_as_float(T[5])) * __int_as_float(T[6]);
+          const bool in = fa >= 0.f && fa < 8.f && fb >= 0.f && fb < 8.f;
+          const unsigned long long w = (unsigned long long)(unsigned)T[7] | (unsigned long long)(unsigned)T[8] << 32;
+          const bool safe = in && ((w >> (((int)fa + 8 * (int)fb) & 63)) & 1ull);
+          const unsigned drop = (safe && l == (T[0] & (G - 1))) ? 1u << (T[0] / G) : 0u;  // (pair i * G + l is bit i of lane l)
+#ifdef JH_V5_COUNT
+          if (live && l == 0 && safe) V5_CADD(CB_TSAFE, 1);
+          if (live && (sph & drop) != 0) V5_CADD(CB_TDROP, 1);  // (the one lane that holds the pair)
+#endif
+          sph &= ~drop;
+        }
         // The candidate list S.hits[] of a rollout and step is the one a plain loop over the pairs would build, entry for entry and in the same order: the same tests on the
         // same operands, only on other lanes and in fewer, fuller passes (profiles/leap_broad_phase.md).  Level 1 is list-driven: the sphere survivors are written out in
         // ascending order, and the oriented-box test runs over that list 16 entries per pass instead of once per pass of 16 body pairs with a few lanes each.
@@ -1873,7 +1902,7 @@ int JH_V5_NAME(jh_engine5_materialize)(const jh_model* m, const float* x0, int x
 // lead to the next problem's, and `image_stride` floats from `images`, problem 0's float section, to the next problem's (m->d_f and 0 where the problems share the model;
 // a model set's members passed jh_engine5_accepts one by one when the set was made).  The latency shift is chosen from B * N, the rollouts of the launch (the bits do
 // not depend on it), and there is no queue.
-int JH_V5_NAME(jh_engine5_rollout_cost_batch)(const jh_model* m, const float* images, long long image_stride, int B, const float* x0, const float* nominal, const float* sigma, const float* lohi, const float* tp, long long blk_stride,
+int JH_V5_NAME(jh_engine5_rollout_cost_batch)(const jh_model* m, const float* images, long long image_stride, const int* ints, int B, const float* x0, const float* nominal, const float* sigma, const float* lohi, const float* tp, long long blk_stride,
                                   const float* noise, int ldn, long long noise_stride, const float* W, int N, int H, int K, float* costs, float* trace, hipStream_t st) {
   if (!model_is_leap(m)) { jh_set_error("plan_step_batch: the cooperative engine kernel is instantiated for leap_cube only"); return JH_ERR_UNSUPPORTED; }
   if ((m->cylinders > 0) != (JH_V5_CYL != 0)) { jh_set_error("plan_step_batch: an image with cylinder geoms runs on the cylinder build of the leap kernel and no other image does (%d cylinders)", m->cylinders); return JH_ERR_UNSUPPORTED; }
@@ -1883,7 +1912,7 @@ int JH_V5_NAME(jh_engine5_rollout_cost_batch)(const jh_model* m, const float* im
   const size_t ovf_bytes = NOVF > 0 ? (size_t)B * N * NOVF * POOL_F * sizeof(float) : 0;  // one row per rollout of every problem for the contacts above the LDS pool
   float* ovf = ovf_bytes > 0 ? jh_launch_scratch(m, ovf_bytes, st) : nullptr;  // (nullptr: the LDS capacity alone, drops and the fallback counted)
 #define JH_V5_LAUNCH_BATCH(SELF_)                                                                                                                                                  \
-  hipLaunchKernelGGL((k_leap_v5<false, WAVES_PER_BLOCK, SELF_, false, true>), dim3(grid, B), dim3(WAVE * WAVES_PER_BLOCK), 0, st, images, m->d_i, x0, 0, nominal, noise, ldn, sigma, W, \
+  hipLaunchKernelGGL((k_leap_v5<false, WAVES_PER_BLOCK, SELF_, false, true>), dim3(grid, B), dim3(WAVE * WAVES_PER_BLOCK), 0, st, images, ints, x0, 0, nominal, noise, ldn, sigma, W, \
                      lohi, tp, N, 0, H, K, costs, (float*)nullptr, (const float*)nullptr, (float*)nullptr, (float*)nullptr, m->d_stats, dshift, trace, ovf, (unsigned*)nullptr, blk_stride, noise_stride, image_stride)
   if (m->self_collision && m->h_i[17] > 0) JH_V5_LAUNCH_BATCH(true); else JH_V5_LAUNCH_BATCH(false);
 #undef JH_V5_LAUNCH_BATCH

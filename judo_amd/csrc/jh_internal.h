@@ -14,6 +14,9 @@
 #define JH_BLOB_MAGIC 0x314D484Au /* "JHM1" */
 #define JH_BLOB_VERSION 1u
 #define JH_NSTATS 512
+// The hand's pair tables in a leap image's int section (judo_amd/engine_model.py::hand_pair_tables, PT_*): header slot JH_PT_SLOT holds the offset of the block
+// [count, JH_PT_MAX records of JH_PT_I ints] (0: none).  One definition for jh_model_create's check, the model-set rule and the kernel.
+constexpr int JH_PT_SLOT = 19, JH_PT_MAX = 4, JH_PT_I = 9, JH_PT_LEN = 1 + JH_PT_MAX * JH_PT_I;
 
 // Host-side blob header produced by judo_amd/models.py::pack_model (little-endian, 64 bytes):
 struct jh_blob_header {
@@ -140,12 +143,13 @@ int jh_engine5_materialize_cyl(const jh_model* m, const float* x0, int x0_batche
                                hipStream_t st);
 
 // the leap kernel for B problems in one launch (jh_plan_step_batch): x0 ... tp of problem 0, `blk_stride` / `noise_stride` floats to the next problem's; `images`: problem
-// 0's float section, `image_stride` floats to the next problem's (m->d_f and 0: one image for all)
-int jh_engine5_rollout_cost_batch(const jh_model* m, const float* images, long long image_stride, int B, const float* x0, const float* nominal, const float* sigma, const float* lohi, const float* tp, long long blk_stride,
+// 0's float section, `image_stride` floats to the next problem's (m->d_f and 0: one image for all); `ints`: the int section on the device (m->d_i, or a model set's
+// copy without the hand's pair tables)
+int jh_engine5_rollout_cost_batch(const jh_model* m, const float* images, long long image_stride, const int* ints, int B, const float* x0, const float* nominal, const float* sigma, const float* lohi, const float* tp, long long blk_stride,
                                   const float* noise, int ldn, long long noise_stride, const float* W, int N, int H, int K, float* costs, float* trace, hipStream_t st);
-int jh_engine5_rollout_cost_batch_cap64(const jh_model* m, const float* images, long long image_stride, int B, const float* x0, const float* nominal, const float* sigma, const float* lohi, const float* tp, long long blk_stride,
+int jh_engine5_rollout_cost_batch_cap64(const jh_model* m, const float* images, long long image_stride, const int* ints, int B, const float* x0, const float* nominal, const float* sigma, const float* lohi, const float* tp, long long blk_stride,
                                         const float* noise, int ldn, long long noise_stride, const float* W, int N, int H, int K, float* costs, float* trace, hipStream_t st);
-int jh_engine5_rollout_cost_batch_cyl(const jh_model* m, const float* images, long long image_stride, int B, const float* x0, const float* nominal, const float* sigma, const float* lohi, const float* tp, long long blk_stride,
+int jh_engine5_rollout_cost_batch_cyl(const jh_model* m, const float* images, long long image_stride, const int* ints, int B, const float* x0, const float* nominal, const float* sigma, const float* lohi, const float* tp, long long blk_stride,
                                       const float* noise, int ldn, long long noise_stride, const float* W, int N, int H, int K, float* costs, float* trace, hipStream_t st);
 
 // does the build's launcher accept this model (its own acceptance test, on the model's own image)?

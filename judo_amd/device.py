@@ -224,6 +224,10 @@ class GpuModelSet:
         _lib.check(_lib.lib().jh_model_set_info(self.handle, out), "jh_model_set_info")
         return {"B": int(out[0]), "image_floats": int(out[1]), "stride_floats": int(out[2]), "distinct_from_first": int(out[3])}
 
+    def pair_tables(self) -> bool:
+        """`jh_model_set_pair_tables`: do the set's launches use the hand's pair tables (every member agrees with member 0 on what they were computed from)?"""
+        return bool(_lib.lib().jh_model_set_pair_tables(self.handle))
+
     def update(self, b: int, model: GpuModel) -> None:
         """Replace member b's image (`jh_model_set_update`: the same checks; synchronous -- between episodes, not in the plan loop)."""
         _lib.check(_lib.lib().jh_model_set_update(self.handle, int(b), model.handle), "jh_model_set_update")

@@ -14,6 +14,8 @@ Layout of the float (F) and int (I) sections is mirrored by `struct EngineModel`
 
 from __future__ import annotations
 
+import collections
+
 import numpy as np
 
 from judo_amd.models import (
@@ -304,8 +306,243 @@ def bounding_box_half(g: dict) -> np.ndarray:
     return np.array(g["size"][:3])
 
 
-def pack_engine_model(desc: dict, fingertips: str | None = None) -> bytes:
-    """`fingertips` (leap family; default: the description's own "fingertips" entry, else "sphere"): "sphere" packs `kernel_stand_ins(desc)`, the image every
+# ---- pair tables of the hand's broad phase (jh_engine_v5.hip, level 1) ---------------------------------------------------------------------------------------
+# A hand body pair whose relative pose depends on one or two hinge joints gets a bit grid over those joints' angles: a set bit says that NO pose in the cell can
+# give the pair a level-2 candidate, and the kernel drops the pair before its box test.  Layout of the section (header slot PT_SLOT holds its offset; 0: none):
+# [count, then PT_MAX records of PT_I ints: pair index, lane of joint 1, lane of joint 2, origin 1, 1 / cell width 1, origin 2, 1 / cell width 2 (float bits),
+# the 64-bit word (low, high)]; bit ix + 8 * iy.  A single-joint table is a row: joint 2 = joint 1 with 1 / cell width 0 (iy = 0).  Unused records are zero.
+PT_SLOT, PT_MAX, PT_I, PT_CELLS = 19, 4, 9, 8
+PT_SUB = 16        # sub-samples per cell and joint (cell midpoints of a PT_SUB x PT_SUB subdivision)
+PT_MARGIN = 0.2    # rad by which the grid reaches beyond each joint's range on both sides (the limits are soft: a joint runs past them under load)
+# What the table's bounds are widened by on top of the displacement bound D below: the kernel evaluates the same tests in fp32 in world coordinates -- operands
+# below 1 m, chains of a few dozen operations at 6e-8 relative error each, rotation matrices accumulated over four links (1e-6, times a lever below 0.2 m) -- which
+# stays below 1e-6 m; and it finds the cell as (int)((q - origin) * inv) in fp32, which can put an angle up to a few 1e-7 rad beyond a cell's edge into that cell:
+# times a lever below 0.2 m, below 1e-7 m.  1e-5 m covers both ten times over.
+PT_SLACK = 1e-5
+PT_SUB_COARSE = (2, 4, 8)  # the coarser samplings a cell goes through first (see hand_pair_tables)
+PT_CACHE = 8       # hand geometries whose tables are kept
+_pt_cache: collections.OrderedDict[bytes, list] = collections.OrderedDict()
+
+
+def _rot_axis(al: np.ndarray, q: np.ndarray) -> np.ndarray:
+    """Rotation by q (N,) about the unit axis `al`, the kernel's expression."""
+    sn, cs = np.sin(q), np.cos(q)
+    t, (x, y, z) = 1.0 - cs, al
+    return np.stack([t * x * x + cs, t * x * y - sn * z, t * x * z + sn * y, t * x * y + sn * z, t * y * y + cs, t * y * z - sn * x,
+                     t * x * z - sn * y, t * y * z + sn * x, t * z * z + cs], -1).reshape(-1, 3, 3)
+
+
+def _obb_faces(ca, Ra, ha, cb, Rb, hb, infl):
+    """obb_face_overlap of the kernel over N poses, every one of the six bounds widened by `infl`."""
+    d = cb - ca
+    C = np.abs(np.einsum("nki,nkj->nij", Ra, Rb))
+    da, db = np.abs(np.einsum("nki,nk->ni", Ra, d)), np.abs(np.einsum("nki,nk->ni", Rb, d))
+    return (da <= ha + C @ hb + infl).all(-1) & (db <= hb + np.einsum("nki,k->ni", C, ha) + infl).all(-1)
+
+
+def hand_pair_tables(F: list, I: list) -> list[dict]:
+    """The pair tables of a leap-family image under construction (F, I as `pack_engine_model` has them behind the body-pair tables): at most PT_MAX dicts
+    (pair, j1, j2, o1, inv1, o2, inv2, word, score), ascending in the pair index.
+
+    Eligible: a pair (A, B) of the image's list whose relative pose is a function of one or two hinge joints -- the links on the tree path between them, A's side
+    and B's side of their last common ancestor (static geometry: the world, no links).  The grid spans each joint's range widened by PT_MARGIN in PT_CELLS cells.
+
+    Conservative by construction.  A cell is sampled at the midpoints of a PT_SUB x PT_SUB subdivision, so every pose of the closed cell lies within half a sample
+    spacing, s_j / 2, of a sample in each joint.  Turning joint j by an angle a is, up to a rigid motion of the whole pair (which none of the tests sees), a rotation
+    of B's side about the joint's anchor with A's side held, or of A's side with B's held: a point of either body at distance r from the anchor moves by at most
+    a * r against the other body.  With L_j the largest distance, over all samples, from joint j's anchor to a point of either body's test volumes (each geom's
+    centre plus the half diagonal of its box, each body's bounding-box centre plus its half diagonal), and D the largest displacement between a pose and its
+    nearest sample, the distances on the way are at most L_j + 2 D (anchor and point each move by at most D), so D <= sum_j s_j / 2 * (L_j + 2 D), that is
+    D <= sum_j s_j / 2 * L_j / (1 - sum_j s_j).  Every test of levels 1 and 2 is a comparison |projection of a centre difference| <= bound or |distance| <= bound,
+    in which a box enters through the interval its points project to: the rotation of the boxes themselves is the displacement of their corners, which L_j
+    covers.  So a test that passes at a pose passes at its nearest sample with the bound widened by D, and the tests are evaluated at the samples with every
+    bound widened by D + PT_SLACK.  A cell is safe when no sample in it then passes level 1 and yields a level-2 candidate.  The argument holds for any sampling
+    with its own D, so a cell is first sampled at the coarser spacings of PT_SUB_COARSE (each with its larger D): what one of them proves safe is safe, and only the rest
+    is sampled PT_SUB x PT_SUB.  A pair whose bounding volumes overlap nowhere on the grid is not evaluated further.
+
+    The tables chosen are those with the most cells that are safe AND pass the unwidened level 1 at some sample -- the cells where the table saves the kernel work --
+    ties to the lower pair index; pairs with no such cell get none."""
+    Ff = np.asarray(F, np.float32).astype(np.float64)  # (the values the kernel reads)
+    NM, NBLK, nv, nu, NG = I[0], I[1], I[2], I[4], I[5]
+    oDofF = HEADER_F + NM * BODY_F
+    oGeomF = oDofF + nv * DOF_F + nu * ACT_F
+    oGeomI = HEADER_I + NM * BODY_I + NBLK * BLOCK_I + nu * ACT_I
+    oBP, oBS, nBP = I[15], I[16], I[17]
+    oBG, NBC = oBP + 2 * nBP, 20
+    # The tables are a function of the pair list, the bodies' tree, frames, joint axes and ranges, the geoms' types, sizes and poses, and the bodies' bounding
+    # volumes -- not of the cube, masses, gains or friction: images that differ in those alone (randomised physics) share one cache entry.  The cache is small and
+    # bounded: an entry per hand geometry in use.
+    bodies = Ff[HEADER_F: HEADER_F + NM * BODY_F].reshape(NM, BODY_F)[1:]
+    geoms = Ff[oGeomF: oGeomF + NG * GEOM_F].reshape(NG, GEOM_F)
+    key = b"".join(np.ascontiguousarray(x).tobytes() for x in (
+        np.asarray(I[HEADER_I: HEADER_I + NM * BODY_I] + I[oGeomI: oGeomI + NG * GEOM_I] + I[oBP: oBG + 2 * NBC] + [NM, NBLK, nv, nu, NG], np.int64),
+        bodies[:, 0:12], bodies[:, 28:31], Ff[oDofF + 6 * DOF_F: oDofF + nv * DOF_F].reshape(-1, DOF_F)[:, 6:9], geoms[:, 0:16], Ff[oBS: oBS + 8 * NBC]))
+    if key in _pt_cache:
+        _pt_cache.move_to_end(key)
+        return _pt_cache[key]
+    # (the half sizes below take a geom that is neither a sphere nor a cylinder for a box, as the kernel's builds do for the kinds the packer lets through)
+    assert all(I[oGeomI + g * GEOM_I + 1] in (GBOX, GSPHERE, GCYLINDER) for g in range(NG)), "pair tables: a geom kind the broad phase's restatement does not know"
+    static = lambda c: c == 0 or c >= NM  # noqa: E731
+    par = lambda c: I[HEADER_I + c * BODY_I]  # noqa: E731
+
+    def chain(c):  # the links from the static root down to link c
+        out = []
+        while not static(c) and c > 0:
+            out.append(c)
+            c = par(c)
+        return out[::-1]
+
+    def body_volumes(c):
+        g0, n = I[oBG + 2 * c], I[oBG + 2 * c + 1]
+        G = Ff[oGeomF + g0 * GEOM_F: oGeomF + (g0 + n) * GEOM_F].reshape(n, GEOM_F)
+        ty = [I[oGeomI + (g0 + k) * GEOM_I + 1] for k in range(n)]
+        half = np.array([[g[0]] * 3 if t == GSPHERE else ([g[0], g[0], g[1]] if t == GCYLINDER else list(g[0:3])) for g, t in zip(G, ty)])
+        bb = Ff[oBS + 8 * c: oBS + 8 * c + 8]
+        return dict(pos=G[:, 3:6], R=G[:, 6:15].reshape(n, 3, 3), half=half, rb=G[:, 15], ctr=bb[0:3], rad=bb[3], bhalf=bb[4:7])
+
+    cand = []
+    for pi in range(nBP):
+        ca, cb = I[oBP + 2 * pi], I[oBP + 2 * pi + 1]
+        la, lb = chain(ca), chain(cb)
+        while la and lb and la[0] == lb[0]:
+            la, lb = la[1:], lb[1:]
+        links = la + lb
+        if not 1 <= len(links) <= 2 or any(I[HEADER_I + k * BODY_I + 1] != JHINGE or Ff[oDofF + (5 + k) * DOF_F + 6] == 0 for k in links):
+            continue
+        # the grid
+        lo = [Ff[oDofF + (5 + k) * DOF_F + 7] - PT_MARGIN for k in links]
+        w = [(Ff[oDofF + (5 + k) * DOF_F + 8] + PT_MARGIN - l0) / PT_CELLS for k, l0 in zip(links, lo)]
+        two = len(links) == 2
+        ncell = PT_CELLS * (PT_CELLS if two else 1)
+        A, B = body_volumes(ca), body_volumes(cb)
+
+        def evaluate(cells, sub):
+            """Per cell of `cells`, sampled sub x sub: some sample passes the widened level 1 and yields a widened level-2 candidate; some sample does with nothing
+            widened; some sample passes the unwidened level 1; and the displacement bound D of this sampling."""
+            k1, k2 = np.meshgrid(np.arange(sub), np.arange(sub if two else 1), indexing="ij")
+            qs = {links[0]: (lo[0] + ((cells % PT_CELLS)[:, None] + (k1.ravel() + 0.5) / sub) * w[0]).ravel()}
+            if two:
+                qs[links[1]] = (lo[1] + ((cells // PT_CELLS)[:, None] + (k2.ravel() + 0.5) / sub) * w[1]).ravel()
+            cell = np.repeat(np.arange(len(cells)), k1.size)
+            N = cell.size
+
+            def side(ls):  # pose of the side's body in the frame of the last common ancestor (the world if there is none), and its links' anchors
+                R, P, anchors = np.broadcast_to(np.eye(3), (N, 3, 3)), np.zeros((N, 3)), []
+                for k in ls:
+                    bf = Ff[HEADER_F + k * BODY_F: HEADER_F + (k + 1) * BODY_F]
+                    P = P + R @ bf[0:3]
+                    anchors.append(P)
+                    R = R @ bf[3:12].reshape(3, 3) @ _rot_axis(bf[28:31], qs[k])
+                return R, P, anchors
+
+            (RA, pA, anA), (RB, pB, anB) = side(la), side(lb)
+            cAw, cBw = pA + RA @ A["ctr"], pB + RB @ B["ctr"]
+            gA, gB = pA[:, None] + np.einsum("nij,gj->ngi", RA, A["pos"]), pB[:, None] + np.einsum("nij,gj->ngi", RB, B["pos"])
+            # the displacement bound D
+            L = []
+            for an in anA + anB:
+                r = max(np.linalg.norm(cAw - an, axis=-1).max() + A["rad"], np.linalg.norm(cBw - an, axis=-1).max() + B["rad"])
+                for g, V in ((gA, A), (gB, B)):
+                    r = max(r, (np.linalg.norm(g - an[:, None], axis=-1) + np.linalg.norm(V["half"], axis=-1)).max())
+                L.append(r)
+            sp = [x / sub for x in w]
+            D = sum(0.5 * s_ * r for s_, r in zip(sp, L)) / (1.0 - sum(sp))
+
+            def level1(idx, infl):
+                d = cAw[idx] - cBw[idx]
+                idx = idx[(d * d).sum(-1) <= (A["rad"] + B["rad"] + infl) ** 2]
+                return idx[_obb_faces(cAw[idx], RA[idx], A["bhalf"], cBw[idx], RB[idx], B["bhalf"], infl)]
+
+            def candidate(idx, infl):  # the samples of `idx` that pass level 1 and yield a level-2 candidate, every bound widened by `infl`
+                s1, out = level1(idx, infl), np.zeros(N, bool)
+                if not s1.size:
+                    return out
+
+                def near(g, V, co, Ro, ho):  # a geom of one body against the other body's bounding box
+                    e = np.maximum(np.abs(np.einsum("nki,ngk->ngi", Ro, g - co[:, None])) - ho, 0.0)
+                    return (e * e).sum(-1) <= (V["rb"] + infl) ** 2
+                nA, nB = near(gA[s1], A, cBw[s1], RB[s1], B["bhalf"]), near(gB[s1], B, cAw[s1], RA[s1], A["bhalf"])
+                for a in range(nA.shape[1]):
+                    for b in range(nB.shape[1]):
+                        i = s1[nA[:, a] & nB[:, b] & ~out[s1]]
+                        if not i.size:
+                            continue
+                        e = gA[i, a] - gB[i, b]
+                        i = i[(e * e).sum(-1) <= (A["rb"][a] + B["rb"][b] + infl) ** 2]
+                        if i.size:
+                            out[i] = _obb_faces(gA[i, a], RA[i] @ A["R"][a], A["half"][a], gB[i, b], RB[i] @ B["R"][b], B["half"][b], infl)
+                return out
+
+            everything = np.arange(N)
+            l1_plain = np.zeros(N, bool)
+            l1_plain[level1(everything, 0.0)] = True
+            unsafe = candidate(everything, D + PT_SLACK)
+            certain = candidate(np.flatnonzero(unsafe), 0.0)  # (a candidate with nothing widened: no finer sampling will call the cell safe)
+            n = len(cells)
+            return np.bincount(cell, weights=unsafe, minlength=n) > 0, np.bincount(cell, weights=certain, minlength=n) > 0, np.bincount(cell, weights=l1_plain, minlength=n) > 0, D
+
+        # coarse to fine: a cell that a coarser sampling (with its own, larger D) already proves safe is safe; only the others go on to the next, down to PT_SUB x PT_SUB
+        cells = np.arange(ncell)
+        unsafe, certain, useful, D = evaluate(cells, PT_SUB_COARSE[0])
+        if not useful.any():
+            continue  # (the bounding volumes never overlap on the grid: level 1 drops the pair by itself, a table would save nothing)
+        for sub in PT_SUB_COARSE[1:] + (PT_SUB,):
+            again = np.flatnonzero(unsafe & ~certain)  # (a cell with a candidate at a sample, nothing widened, stays unsafe: not sampled again)
+            if again.size:
+                u2, c2, f2, D = evaluate(again, sub)
+                unsafe[again], certain[again], useful[again] = u2, c2, useful[again] | f2
+        safe = ~unsafe
+        word = sum(1 << int(c) for c in np.flatnonzero(safe))
+        cand.append(dict(pair=pi, j1=links[0] - 1, j2=links[-1] - 1, o1=float(lo[0]), inv1=float(1.0 / w[0]), o2=float(lo[1]) if two else 0.0,
+                         inv2=float(1.0 / w[1]) if two else 0.0, word=word, score=int((safe & useful).sum()), D=float(D)))
+    best = sorted((t for t in cand if t["score"] > 0), key=lambda t: (-t["score"], t["pair"]))[:PT_MAX]
+    out = sorted(best, key=lambda t: t["pair"])
+    _pt_cache[key] = out
+    while len(_pt_cache) > PT_CACHE:
+        _pt_cache.popitem(last=False)
+    return out
+
+
+def pair_table_section(tables: list[dict]) -> list[int]:
+    """The int section's table block (see PT_SLOT)."""
+    bits = lambda x: int(np.float32(x).view(np.int32))  # noqa: E731
+    s32 = lambda u: u - (1 << 32) if u >= 1 << 31 else u  # noqa: E731
+    out = [len(tables)]
+    for t in tables:
+        out += [t["pair"], t["j1"], t["j2"], bits(t["o1"]), bits(t["inv1"]), bits(t["o2"]), bits(t["inv2"]), s32(t["word"] & 0xFFFFFFFF), s32(t["word"] >> 32)]
+    return out + [0] * (PT_I * (PT_MAX - len(tables)))
+
+
+def read_pair_tables(blob: bytes) -> list[dict]:
+    """The pair tables of a packed image: dicts as `hand_pair_tables` returns them (without score), [] where the image has none."""
+    nf = int(np.frombuffer(blob[:64], np.uint32)[8])
+    Iv = np.frombuffer(blob[64 + 4 * nf:], np.int32)
+    o = int(Iv[PT_SLOT]) if Iv.size > PT_SLOT else 0
+    out = []
+    for t in range(int(Iv[o]) if o > 0 else 0):
+        r = Iv[o + 1 + t * PT_I: o + 1 + (t + 1) * PT_I]
+        f = r[3:7].view(np.float32)
+        out.append(dict(pair=int(r[0]), j1=int(r[1]), j2=int(r[2]), o1=float(f[0]), inv1=float(f[1]), o2=float(f[2]), inv2=float(f[3]),
+                        word=(int(r[7]) & 0xFFFFFFFF) | (int(r[8]) & 0xFFFFFFFF) << 32))
+    return out
+
+
+def pair_table_safe(t: dict, qa, qb) -> np.ndarray:
+    """The kernel's lookup, in its fp32 arithmetic: does table `t` rule the pair out at joint angles (qa, qb)?  An angle off the grid, or a NaN, reads as unsafe."""
+    f32 = np.float32
+    with np.errstate(invalid="ignore"):
+        fa = (np.asarray(qa, f32) - f32(t["o1"])) * f32(t["inv1"])
+        fb = (np.asarray(qb, f32) - f32(t["o2"])) * f32(t["inv2"])
+        inside = (fa >= 0) & (fa < PT_CELLS) & (fb >= 0) & (fb < PT_CELLS)
+    bit = np.where(inside, fa, 0).astype(np.int64) + PT_CELLS * np.where(inside, fb, 0).astype(np.int64)
+    word = np.array([(t["word"] >> k) & 1 for k in range(64)], bool)
+    return inside & word[bit]
+
+
+def pack_engine_model(desc: dict, fingertips: str | None = None, pair_tables: bool = True) -> bytes:
+    """`pair_tables` (leap family): False packs the image without the hand's pair tables (`hand_pair_tables`); the kernel then tests every body pair.
+
+    `fingertips` (leap family; default: the description's own "fingertips" entry, else "sphere"): "sphere" packs `kernel_stand_ins(desc)`, the image every
     build of the leap kernel runs; "cylinder" keeps the MJCF's cylinders -- type code 5, sizes (radius, half length), bounding radius sqrt(r^2 + L^2) -- for the
     cylinder build (jh_engine_v5_cyl.hip), which jh_model_create selects by itself when it finds one."""
     fingertips = desc.get("fingertips", "sphere") if fingertips is None else fingertips
@@ -555,6 +792,9 @@ def pack_engine_model(desc: dict, fingertips: str | None = None) -> bytes:
             lo, hi = corners.min(0), corners.max(0)
             ctr, half = 0.5 * (lo + hi), 0.5 * (hi - lo)
             F += [*ctr, float(np.linalg.norm(half)), *half, 0.0]
+        hand_tables = hand_pair_tables(F, I) if pair_tables else []
+    else:
+        hand_tables = []
     # ---- generic sections (reference kernel): every collision geom incl. the cube, explicit candidate pairs, joint
     # equalities, sensor frames with orientation, geom-distance sensors
     allg = [g for g in desc["geoms"] if g["type"] in kinds + ("capsule",)]
@@ -634,6 +874,9 @@ def pack_engine_model(desc: dict, fingertips: str | None = None) -> bytes:
     if ref_frames is not None:  # reference frames of the sensors (jh_engine_v5.hip, caltech_leap_cube layout)
         I[18] = len(F)
         F += ref_frames
+    if hand_tables:  # behind everything else in the int section, found through header slot 19 (zero in an image without tables): no other offset moves
+        I[PT_SLOT] = len(I)
+        I += pair_table_section(hand_tables)
     ntp = 9 if desc.get("family", desc["task"]) == "leap_cube" else 22
     return _pack(TASK_KIND[desc.get("family", desc["task"])], lay, ntp, F, I)
 

@@ -379,7 +379,7 @@ def pack_model(desc: dict) -> bytes:
         return _pack_cylinder(desc)
     from judo_amd.engine_model import pack_engine_model  # articulated-body engine (leap_cube, fr3_pick)
 
-    return pack_engine_model(desc)
+    return pack_engine_model(desc, pair_tables=bool(desc.get("pair_tables", True)))  # ("pair_tables": false in a description: the leap image without them, every hand pair tested)
 
 
 # ----------------------------------------------------------------------------------------- randomised physics
