@@ -135,6 +135,19 @@ int jh_model_set_plan_step_launches(jh_model* m, int launches);
  * the kernel has it (every fused launch outside the latency mode).  All three give the same bits: a rollout's result does not depend on the wave that runs it.  The
  * environment variable JUDO_AMD_ROLLOUT_SCHEDULE=1 / 2 sets the default of every model created after it is set.  Accepted and without effect on the other models. */
 int jh_model_set_rollout_schedule(jh_model* m, int mode);
+/* The units of that queue.  `slices`: 0 = automatic (the default): a launch that runs the queue AND has at least two groups per resident wave splits every group's horizon
+ * into slices, and a queue unit is (group, slice) -- all first slices, then all second ones -- so that the launch drains over a slice's duration instead of a group's; every
+ * other launch keeps whole groups.  1 .. 64 forces that many slices (clipped to the horizon) wherever the queue runs; 1 = whole groups.  A slice hands the rollouts' state
+ * to the next one through the launch's scratch and a flag that is read once, never waited for: a wave that finds it unset recomputes the group's steps up to its slice.
+ * `max_workgroups`: 0 = one workgroup per resident slot; > 0 caps the queue's grid (a test hook: a small launch then draws tickets and hands states over).  `flags` bit 0:
+ * every hand-off counts as missed (a test hook for the recomputation).  None of this changes a bit of any output.  Other values: JH_ERR_INVALID.  Accepted and without
+ * effect on the other models.  The environment variable JUDO_AMD_ROLLOUT_SLICES=1 .. 64 sets the default `slices` of every model created after it is set. */
+int jh_model_set_rollout_slices(jh_model* m, int slices, int max_workgroups, int flags);
+/* What the model's last fused leap_cube launch of generation 3 ran: 0 = the static grid, 1 = the queue of whole groups, S > 1 = the queue of S slices per group. */
+int jh_model_last_rollout_slices(const jh_model* m);
+/* Queue units that found their hand-off unset and recomputed their group up to their slice, summed over the model's launches since the counters were last reset
+ * (jh_model_stats with reset != 0); synchronises.  A negative jh_status on failure. */
+int jh_model_recomputed_units(jh_model* m);
 
 /* Plan-step I/O in one call each (the two transfers of a plan step: < 2 KB down, the new nominal knots up): an asynchronous copy of `nbytes` from
  * pinned HOST memory to the device on `stream`; and an asynchronous copy from the device to pinned HOST memory followed by a wait for `stream`

@@ -157,6 +157,7 @@ extern "C" int jh_model_create(const void* blob, size_t nbytes, int device, jh_m
   m->device = device; m->kind = (int)h.kind; m->nq = h.nq; m->nv = h.nv; m->nu = h.nu; m->ns = h.ns; m->ntaskparam = h.ntaskparam;
   m->nf = h.nfloat; m->ni = h.nint; m->d_f = nullptr; m->d_i = nullptr; m->d_stats = nullptr; m->kernel_gen = (h.kind == JH_TASK_LEAP_CUBE || h.kind == JH_TASK_FR3_PICK) ? 3 : 2; m->self_collision = 1; m->contact_capacity = cylinders > 0 ? 64 : 48; m->cylinders = cylinders; m->arm_pairs = arm_pairs;
   { const char* e = getenv("JUDO_AMD_ROLLOUT_SCHEDULE"); m->rollout_schedule = (e && (e[0] == '1' || e[0] == '2')) ? e[0] - '0' : 0; }  // (the environment sets the default; jh_model_set_rollout_schedule changes it per model)
+  { const char* e = getenv("JUDO_AMD_ROLLOUT_SLICES"); const int v = e ? atoi(e) : 0; m->rollout_slices = (v >= 1 && v <= 64) ? v : 0; }  // (likewise; jh_model_set_rollout_slices)
   { const char* e = getenv("JUDO_AMD_PLAN_STEP_LAUNCHES"); m->plan_step_launches = (e && e[0] == '2') ? 2 : 0; }  // (the environment sets the default; jh_model_set_plan_step_launches changes it per model)
   const char* p = (const char*)blob + sizeof(h);
   m->h_f.assign((const float*)p, (const float*)p + h.nfloat);
@@ -351,6 +352,26 @@ extern "C" int jh_model_set_rollout_schedule(jh_model* m, int mode) {
   JH_REQUIRE(m != nullptr && mode >= 0 && mode <= 2, "model_set_rollout_schedule: mode must be 0 (automatic), 1 (static grid) or 2 (persistent waves wherever the kernel has them)");
   m->rollout_schedule = mode;
   return JH_OK;
+}
+
+extern "C" int jh_model_set_rollout_slices(jh_model* m, int slices, int max_workgroups, int flags) {
+  JH_REQUIRE(m != nullptr && slices >= 0 && slices <= 64, "model_set_rollout_slices: slices must be 0 (automatic) or 1 .. 64");
+  JH_REQUIRE(max_workgroups >= 0, "model_set_rollout_slices: max_workgroups must be 0 (the resident slots) or a positive cap on the queue's grid");
+  JH_REQUIRE((flags & ~1) == 0, "model_set_rollout_slices: flags has bit 0 (every hand-off counts as missed) and no other");
+  m->rollout_slices = slices; m->rollout_max_workgroups = max_workgroups; m->rollout_slice_flags = flags;
+  return JH_OK;
+}
+
+extern "C" int jh_model_last_rollout_slices(const jh_model* m) {
+  JH_REQUIRE(m != nullptr, "model_last_rollout_slices: null model");
+  return __atomic_load_n(&m->last_rollout_slices, __ATOMIC_RELAXED);
+}
+
+extern "C" int jh_model_recomputed_units(jh_model* m) {
+  JH_REQUIRE(m != nullptr, "model_recomputed_units: null model");
+  int v = 0;
+  JH_HIP(hipMemcpy(&v, m->d_stats + 56, sizeof(int), hipMemcpyDeviceToHost));  // (STAT_RECOMPUTED of jh_engine_v5.hip)
+  return v;
 }
 
 extern "C" int jh_upload_async(void* dst, const void* src, size_t nbytes, void* stream) {
@@ -641,6 +662,7 @@ static int model_set_member(const char* who, const jh_model* m0, const jh_model*
       return JH_ERR_INVALID;
     }
     JH_SET_SAME(kernel_gen, "%d"); JH_SET_SAME(contact_capacity, "%d"); JH_SET_SAME(cylinders, "%d"); JH_SET_SAME(self_collision, "%d"); JH_SET_SAME(rollout_schedule, "%d");
+    JH_SET_SAME(rollout_slices, "%d"); JH_SET_SAME(rollout_max_workgroups, "%d"); JH_SET_SAME(rollout_slice_flags, "%d");
     JH_SET_SAME(plan_step_launches, "%d");
 #undef JH_SET_SAME
   }

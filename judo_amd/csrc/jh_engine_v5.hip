@@ -88,6 +88,14 @@ constexpr int CVX_STOP_NM = 1000;   // the stop of the cylinder build's GJK + EP
 // every Newton iteration: otherwise the slots' Jacobian columns, lever arms and LDS addresses (all invariant over the iterations) are computed once before
 // the loop, do not fit in the register file and are spilled and reloaded in every iteration.
 #define OPAQUE(x) asm volatile("" : "+v"(x))
+// The parked state of a horizon slice (see the kernel): PARK_F floats per queue unit, every word stored and loaded at device scope
+constexpr int PARK_F = 5 * 64;
+constexpr int STAT_RECOMPUTED = 56;  // stats word (every build): queue units whose hand-off was missed and which recomputed their group up to their slice (jh_model_recomputed_units)
+#ifndef JH_V5_AUTO_SLICES
+#define JH_V5_AUTO_SLICES 4  // the slices of the automatic schedule (profiles/leap_horizon_slices.md)
+#endif
+#define PARK_LD(p) __hip_atomic_load((p), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT)
+#define PARK_ST(p, v) __hip_atomic_store((p), (v), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT)
 #define WSYNC() do { __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront"); __builtin_amdgcn_wave_barrier(); __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront"); } while (0)
 #ifndef JH_V5_NSLOT
 #define JH_V5_NSLOT 2
@@ -434,6 +442,15 @@ __device__ __forceinline__ bool chain_elim_order(int cmask, int c, int& level, i
 // atomicAdd by lane 0 -- until the tickets pass the group count.  A wave slot is then never held for a workgroup-mate's longer rollouts, and the launch drains over one
 // group's duration per wave instead of one workgroup's.  No wave waits for another, so nothing depends on which workgroups are resident.  The static instantiations
 // (PERSIST = false: a wave's group is its place in the grid, `head` unused) compile to the code they had without it.
+// Horizon slices (`slices_` & 0xff = S > 1): a queue unit is (group, slice) -- ticket t in [0, S * groups) is slice t / groups of group t % groups, all first slices in front
+// of all second ones, and slice s runs steps [s H / S, (s + 1) H / S) -- so that the launch drains over a slice's duration instead of a group's.  A slice that is not the
+// last parks what the step loop carries (PARK_F floats per unit, rows of 64 lanes: q, qd, the joints' warm start, then per rollout the cube's state, the running cost and
+// the cube's warm start) behind the flag words in `pflags`, fences at device scope and sets the unit's flag; the next slice's wave reads that flag ONCE.  Set: it fences
+// and resumes from the parked rows (fp32 out, fp32 in).  Not set (the producer is still running; or bit 8 of `slices_`, a test hook): it runs the group from x0 up to its
+// slice's first step -- the same instructions on the same inputs, the same bits; trace rows written twice carry the same words -- zeroes the counters and goes on into its own
+// slice.  While it recomputes it adds to no counter (`stats` is null for that pass: the dropped contacts and lost candidate pairs of those steps are the producer's to count) and
+// its contacts above the LDS pool go to a row of its wave slot's own behind the rollouts' rows (the producer may still be running the same rollouts on theirs); the
+// launch counts such units in stats[STAT_RECOMPUTED].  Nothing polls and no wave waits for another.  Every flag and every parked row is written by one unit and read by at most one, once per launch.
 // BATCH (fused mode, static grid only -- there is NO queue for batched launches: a batch's problems fill the GPU side by side, and a queue across problems would have to
 // re-stage a workgroup's task parameters per group): B independent problems in one launch (jh_plan_step_batch), grid (groups of a problem, B).  A workgroup stages sTp once,
 // so it belongs to one problem, blockIdx.y; everything a problem owns -- its packed block (x0, nominal, sigma, task parameters, bounds: `batch_blk` floats apart), its noise
@@ -447,15 +464,15 @@ __global__ __launch_bounds__(WAVE * WPB, WAVES_PER_EU) void k_leap_v5(const floa
                                                    const float* __restrict__ sigma, const float* __restrict__ W, const float* __restrict__ lohi,
                                                    const float* __restrict__ tp, int N, int n_offset, int H, int K, float* __restrict__ costs,
                                                    float* __restrict__ knots_out, const float* __restrict__ controls, float* __restrict__ states,
-                                                   float* __restrict__ sensors, int* __restrict__ stats, int dshift_, float* __restrict__ trace, float* __restrict__ ovf_all, unsigned* __restrict__ head,
-                                                   long long batch_blk, long long batch_noise, long long batch_image) {
+                                                   float* __restrict__ sensors, int* __restrict__ stats_, int dshift_, float* __restrict__ trace, float* __restrict__ ovf_all_, unsigned* __restrict__ head,
+                                                   long long batch_blk, long long batch_noise, long long batch_image, unsigned* pflags, int slices_) {
   static_assert(!BATCH || (!MATERIALIZE && !PERSIST), "batched launches are fused launches on the static grid");
   if constexpr (BATCH) {
     const long long pb = blockIdx.y;
     x0 += pb * batch_blk; nominal += pb * batch_blk; sigma += pb * batch_blk; lohi += pb * batch_blk; tp += pb * batch_blk;
     noise += pb * batch_noise; costs += pb * N; gF += pb * batch_image;
     if (trace) trace += pb * N * H * 15;
-    if (NOVF > 0 && ovf_all) ovf_all += pb * N * (NOVF * POOL_F);  // (the overflow rows are indexed by rollout: a problem's N rows behind the one before)
+    if (NOVF > 0 && ovf_all_) ovf_all_ += pb * N * (NOVF * POOL_F);  // (the overflow rows are indexed by rollout: a problem's N rows behind the one before)
   }
   __shared__ RS sRS[RPW * WPB];
   __shared__ float sBody[16 * BFS];
@@ -468,6 +485,7 @@ __global__ __launch_bounds__(WAVE * WPB, WAVES_PER_EU) void k_leap_v5(const floa
   __shared__ int sBG[SELF ? 2 * NBC : 4];    // per hand body: first collision geom, number of geoms (contiguous in the geom table)
   __shared__ float sBB[SELF ? NBC * 8 : 4];  // per hand body: bounding-box centre (body frame; static geometry: world), bounding radius, half sizes
   __shared__ int sGrp[WPB];  // PERSIST: the group each wave is running (re-read in the step loop instead of held in a register; unused and dropped otherwise)
+  __shared__ int sUnit[4 * WPB];  // PERSIST, per wave: the step at which the running pass of the step loop ends, the unit's first step, the step behind its last, its ticket (in LDS for the reason sGrp is)
   const int dshift = PERSIST ? 0 : dshift_;  // (the queue is for launches that fill the GPU: never the latency mode)
 #ifdef JH_V5_WAVESTAMP  // diagnostic builds (tools/diag/wave_schedule.py): per group of four rollouts, the 100 MHz wall clock at the wave's entry, after the staging barrier, at the
                          // group's start and end, with the workgroup, the wave and the hardware id (__smid) that ran it
@@ -513,14 +531,47 @@ __global__ __launch_bounds__(WAVE * WPB, WAVES_PER_EU) void k_leap_v5(const floa
     ws_staged = wall_clock64();
 #endif
   }
-  for (; !PERSIST || grp < ngroups;) {  // one pass for a static launch (it leaves at the bottom); the queue's groups otherwise.  (The body keeps the kernel's indentation.)
-  if constexpr (PERSIST) { if (lane == 0) sGrp[wv] = grp; }  // (published to the wave by the WSYNC in front of the step loop)
+  int unit = grp;  // PERSIST: the ticket of the unit this wave runs
+  const int nsl = PERSIST ? max(1, min(slices_ & 0xff, H)) : 1, nunits = nsl * ngroups;
+  float* park = (float*)(pflags + ((nunits + 3) & ~3));  // (PERSIST, nsl > 1; never read through a const or __restrict__ pointer: other waves write it during the launch)
+  bool again = false;  // PERSIST: the unit's hand-off was missed and the steps in front of its slice have been recomputed: the next pass of the loop below runs the slice itself
+  float q, qd, qc[7], vc[6], acc;  // the state the step loop carries: own joint, the replicated cube, the running cost (declared here: kept from the one pass to the other)
 #ifdef JH_V5_WAVESTAMP
-  const unsigned long long ws_start = wall_clock64();
+  unsigned long long ws_start = 0;
+#endif
+  for (; !PERSIST || unit < nunits;) {  // one pass for a static launch (it leaves at the bottom); the queue's units otherwise.  (The body keeps the kernel's indentation.)
+  bool resumed = false, prefix = false; int hh0 = 0;  // PERSIST: the previous slice's state was parked in time / was not, and this pass recomputes the steps in front of the slice; the step this pass starts at (0: the group's start, also for a slice whose hand-off was missed)
+  if constexpr (PERSIST) if (again) {  // (the state is in registers and in S.ws; the counters below start from zero: the recomputed steps are another unit's to count)
+    unit = __builtin_amdgcn_readfirstlane(sUnit[4 * wv + 3]); grp = unit % ngroups; hh0 = __builtin_amdgcn_readfirstlane(sUnit[4 * wv + 1]);
+    const int h1 = __builtin_amdgcn_readfirstlane(sUnit[4 * wv + 2]);
+    WSYNC();
+    if (lane == 0) sUnit[4 * wv] = h1;
+  }
+  if constexpr (PERSIST) if (!again) {
+    grp = unit % ngroups;
+    const int sl = unit / ngroups, h0 = sl * H / nsl, h1 = (sl + 1) * H / nsl;
+    if (sl > 0) {  // the flag of (group, slice - 1), read once: an acquire load of lane 0, broadcast, and the wave's acquire fence in front of the parked rows
+      unsigned f = 0;
+      if (lane == 0 && !(slices_ & 0x100)) f = __hip_atomic_load(pflags + (unit - ngroups), __ATOMIC_ACQUIRE, __HIP_MEMORY_SCOPE_AGENT);
+      resumed = __builtin_amdgcn_readfirstlane(f) != 0;
+      if (resumed) { __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent"); hh0 = h0; }
+      prefix = !resumed;
+    }
+    if (lane == 0) { sGrp[wv] = grp; sUnit[4 * wv] = (sl == 0 || resumed) ? h1 : h0; sUnit[4 * wv + 1] = h0; sUnit[4 * wv + 2] = h1; sUnit[4 * wv + 3] = unit; }  // (published to the wave by the WSYNC in front of the step loop)
+  }
+#ifdef JH_V5_WAVESTAMP
+  if (!PERSIST || !again) ws_start = wall_clock64();
 #endif
   const int n = (grp << (2 - dshift)) + (r >> dshift);
   const bool live = n < N && (r & ((1 << dshift) - 1)) == 0;
   const int nc = n < N ? n : N - 1;
+  // What the pass counts into and where its contacts above the LDS pool go: the launch's counters and the rollout's overflow row -- except while a missed hand-off is
+  // recomputed (PERSIST): nothing is counted, and the row is one of this wave slot's own, behind the N rollouts' (the code below indexes by the rollout: hence the offset).
+  int* stats = stats_; float* ovf_all = ovf_all_;
+  if constexpr (PERSIST) if (prefix) {
+    stats = nullptr;
+    if (NOVF > 0 && ovf_all_) ovf_all = ovf_all_ + ((long long)N + (long long)(blockIdx.x * WPB + wv) * RPW + r - nc) * (NOVF * POOL_F);
+  }
   const float h = gF[HF_DT], impratio = gF[HF_IMPRATIO], tol = gF[HF_TOL], lstol = gF[HF_LSTOL]; const int cap = (int)gF[HF_MAXITER];
   const float grav[3] = {gF[HF_GRAV], gF[HF_GRAV + 1], gF[HF_GRAV + 2]};
   const float cmass = gF[HF_CMASS], cI[3] = {gF[HF_CINERTIA], gF[HF_CINERTIA + 1], gF[HF_CINERTIA + 2]};
@@ -530,8 +581,7 @@ __global__ __launch_bounds__(WAVE * WPB, WAVES_PER_EU) void k_leap_v5(const floa
   // own cube dof (lanes 0..5): inertia and its inverse; zero elsewhere
   const float mck = (l < 3 ? cmass : (l == 3 ? cI[0] : (l == 4 ? cI[1] : (l == 5 ? cI[2] : 0.f))));
   // ---- state: own joint + replicated cube
-  float q, qd, qc[7], vc[6];
-  {
+  if (!PERSIST || !again) {
     const float* xi = x0 + ((MATERIALIZE && x0_batched) ? (size_t)nc * NX : 0);
     for (int k = 0; k < 7; k++) qc[k] = xi[k];
     for (int k = 0; k < 6; k++) vc[k] = xi[NQ + k];
@@ -547,12 +597,20 @@ __global__ __launch_bounds__(WAVE * WPB, WAVES_PER_EU) void k_leap_v5(const floa
     return jh_clampf(v, lohi[ll], lohi[NU + ll]);
   };
   if (!MATERIALIZE) {
-    if (knots_out && live) for (int k = 0; k < K; k++) knots_out[(size_t)(k * NU + l) * ldn + n] = knot_at(k, l, nc);
+    if (knots_out && live && (!PERSIST || unit < ngroups)) for (int k = 0; k < K; k++) knots_out[(size_t)(k * NU + l) * ldn + n] = knot_at(k, l, nc);
   }
-  S.ws[6 + l] = 0.f; if (l < 6) S.ws[l] = 0.f;
+  if (!PERSIST || !again) { S.ws[6 + l] = 0.f; if (l < 6) S.ws[l] = 0.f; }
   if (l < 4) S.cmd[l] = l == 0 ? cmass : (l == 1 ? cI[0] : (l == 2 ? cI[1] : cI[2]));
   int n_iters = 0, n_maxed = 0, n_wave_iters = 0;  // (the last: iterations this wave ran -- per step the maximum over its four rollouts)
-  float acc = 0.f;
+  if (!PERSIST || !again) acc = 0.f;
+  if constexpr (PERSIST) if (resumed) {  // the parked rows of (group, slice - 1): device-scope loads, one per lane and value
+    float* pk = park + (size_t)(unit - ngroups) * PARK_F; const int r16 = lane & 48;
+    q = PARK_LD(pk + lane); qd = PARK_LD(pk + 64 + lane); S.ws[6 + l] = PARK_LD(pk + 128 + lane);
+    for (int k = 0; k < 7; k++) qc[k] = PARK_LD(pk + 192 + r16 + k);
+    for (int k = 0; k < 6; k++) vc[k] = PARK_LD(pk + 199 + r16 + k);
+    acc = PARK_LD(pk + 205 + r16);
+    if (l < 6) S.ws[l] = PARK_LD(pk + 256 + lane);
+  }
 #ifdef JH_V5_TICKS  // shader-clock totals per phase (diagnostic builds; tools/diag/profile_v5.py): 0 kinematics+dynamics, 1 broad phase, 2 narrow phase, 3 rows+warm start,
                      // 4 gradient, 5 Newton matrix, 6 factorisation+direction, 7 line search+step and integration
   long long cyc[16] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0}, t0 = clock64();
@@ -583,7 +641,8 @@ __global__ __launch_bounds__(WAVE * WPB, WAVES_PER_EU) void k_leap_v5(const floa
 #endif
   }
 
-  for (int hh = 0; hh < H; hh++) {
+  const int hend = PERSIST ? __builtin_amdgcn_readfirstlane(sUnit[4 * wv]) : H;  // (a scalar register across the loop: re-read from LDS at every step it cost the loop 30 spilled VGPRs)
+  for (int hh = hh0; hh < hend; hh++) {
     // the model constants of a lane (sBody, sLane, ...) do not change over the steps: left alone the compiler loads them once before the loop, runs out of
     // registers and reloads them from scratch memory in every step instead of from LDS
     OPAQUE(l); c = l >> 2; s = l & 3;
@@ -1801,19 +1860,34 @@ __global__ __launch_bounds__(WAVE * WPB, WAVES_PER_EU) void k_leap_v5(const floa
     } else acc += leap_step_cost(sTp, qc);
     WSYNC();
   }
+  if constexpr (PERSIST) {  // a missed hand-off: that was the group up to the slice's first step -- once more round the loop for the slice, nothing flushed
+    again = __builtin_amdgcn_readfirstlane(sUnit[4 * wv]) < __builtin_amdgcn_readfirstlane(sUnit[4 * wv + 2]);
+    if (again) { if (lane == 0 && stats_) atomicAdd(stats_ + STAT_RECOMPUTED, 1); continue; }
+  }
+  int usteps = H; bool last = true;  // the steps this unit ran (and counts); whether it ends the rollouts
+  if constexpr (PERSIST) { const int h0 = __builtin_amdgcn_readfirstlane(sUnit[4 * wv + 1]), h1 = __builtin_amdgcn_readfirstlane(sUnit[4 * wv + 2]); usteps = h1 - h0; last = h1 >= H; unit = __builtin_amdgcn_readfirstlane(sUnit[4 * wv + 3]); }
 #ifdef JH_V5_COUNT
-  if (stats) { if (lane == 0) { atomicAdd(stats + 24, cnt_dense); atomicAdd(stats + 25, cnt_it); atomicAdd(stats + 26, cnt_l2); atomicAdd(stats + 28, H); } if (l == 0 && live) { atomicAdd(stats + 27, cnt_bp); atomicAdd(stats + 29, cnt_hh); for (int k = 0; k < 4; k++) atomicAdd(stats + 30 + k, cnt_cls[k]); } }
+  if (stats) { if (lane == 0) { atomicAdd(stats + 24, cnt_dense); atomicAdd(stats + 25, cnt_it); atomicAdd(stats + 26, cnt_l2); atomicAdd(stats + 28, usteps); } if (l == 0 && live) { atomicAdd(stats + 27, cnt_bp); atomicAdd(stats + 29, cnt_hh); for (int k = 0; k < 4; k++) atomicAdd(stats + 30 + k, cnt_cls[k]); } }
 #endif
 #ifdef JH_V5_TICKS
   if (lane == 0 && stats) { for (int k = 0; k < 8; k++) atomicAdd((unsigned long long*)(stats + 4) + k, (unsigned long long)cyc[k]);
                             for (int k = 0; k < 16; k++) atomicAdd((unsigned long long*)(stats + 384) + k, (unsigned long long)cyc[k]); }
 #endif
-  if (!MATERIALIZE && live && l == 0) costs[n] = acc / (float)H;
-  if (stats && live && l == 0) { if (n_maxed) atomicAdd(stats + 1, n_maxed); atomicAdd(stats + 2, n_iters); atomicAdd(stats + 3, H); }
-  if (stats && lane == 0 && live) { atomicAdd(stats + 20, n_wave_iters); atomicAdd(stats + 21, H); }
+  if (!MATERIALIZE && live && l == 0 && last) costs[n] = acc / (float)H;
+  if (stats && live && l == 0) { if (n_maxed) atomicAdd(stats + 1, n_maxed); atomicAdd(stats + 2, n_iters); atomicAdd(stats + 3, usteps); }
+  if (stats && lane == 0 && live) { atomicAdd(stats + 20, n_wave_iters); atomicAdd(stats + 21, usteps); }
+  if constexpr (PERSIST) if (!last) {  // park the state for the next slice: the rows, a device-scope release by the whole wave, then the unit's flag
+    float* pk = park + (size_t)unit * PARK_F;
+    float pv = l == 13 ? acc : 0.f;
+    for (int k = 0; k < 7; k++) if (l == k) pv = qc[k];
+    for (int k = 0; k < 6; k++) if (l == 7 + k) pv = vc[k];
+    PARK_ST(pk + lane, q); PARK_ST(pk + 64 + lane, qd); PARK_ST(pk + 128 + lane, S.ws[6 + l]); PARK_ST(pk + 192 + lane, pv); PARK_ST(pk + 256 + lane, l < 6 ? S.ws[l] : 0.f);
+    __threadfence();
+    if (lane == 0) __hip_atomic_store(pflags + unit, 1u, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_AGENT);
+  }
 #ifdef JH_V5_WAVESTAMP
-  if (lane == 0 && g_wavestamp && grp < g_wavestamp_cap) {
-    unsigned long long* w = g_wavestamp + (size_t)grp * 6;
+  if (lane == 0 && g_wavestamp && (PERSIST ? unit : grp) < g_wavestamp_cap) {  // (a row per queue unit: ticket t is slice t / groups of group t % groups)
+    unsigned long long* w = g_wavestamp + (size_t)(PERSIST ? unit : grp) * 6;
     w[0] = ((unsigned long long)blockIdx.x << 32) | ((unsigned long long)wv << 8) | (__smid() & 0xff); w[1] = ws_entry; w[2] = ws_staged; w[3] = ws_start; w[4] = wall_clock64(); w[5] = 1;
   }
 #endif
@@ -1821,7 +1895,7 @@ __global__ __launch_bounds__(WAVE * WPB, WAVES_PER_EU) void k_leap_v5(const floa
   else {  // the next ticket: one returning device-scope atomic per group (a vector atomic of lane 0, broadcast to the wave)
     int t = 0;
     if (lane == 0) t = (int)atomicAdd(head, 1u);
-    grp = (int)(gridDim.x * WPB) + __builtin_amdgcn_readfirstlane(t);
+    unit = (int)(gridDim.x * WPB) + __builtin_amdgcn_readfirstlane(t);
   }
   }
 }
@@ -1860,18 +1934,41 @@ int JH_V5_NAME(jh_engine5_rollout_cost)(const jh_model* m, const float* x0, cons
   // per resident slot and lets the waves draw their groups from a queue; one that fits at once, and every latency-mode launch, keeps one group per wave of the grid.
   bool persist = dshift == 0 && m->rollout_schedule != 1; int slots = 0;
   if (persist) { slots = 2 * device_cus(m); persist = m->rollout_schedule == 2 || grid > slots; }
-  // Stream-ordered scratch of the launch, no state on the model handle (two streams may run one model): a 16-byte block for the queue's head word, zeroed in front of every
-  // launch that uses it, then one row per rollout for the contacts above the LDS pool.
-  const size_t ovf_bytes = NOVF > 0 ? (size_t)N * NOVF * POOL_F * sizeof(float) : 0;
+  // Horizon slices (jh_model_set_rollout_slices): the queue's units are (group, slice) where the queue runs and the launch has at least two groups per wave slot -- dependent
+  // units are then so many tickets apart that a slice's predecessor has as good as always parked its state in time -- or wherever the queue runs if a number is forced.
+  const int ngroups = (N + RPW - 1) / RPW;
+  int slices = 1;
+  if (persist) {
+    slices = m->rollout_slices > 0 ? m->rollout_slices : (ngroups >= 2 * slots * WAVES_PER_BLOCK ? JH_V5_AUTO_SLICES : 1);
+    if (slices > H) slices = H;
+    if (slices < 1 || (long long)slices * ngroups > 0x7fffffffll) slices = 1;
+  }
+  // Stream-ordered scratch of the launch, no state on the model handle (two streams may run one model): the queue's head word in a 16-byte block, the flag words of the
+  // slices (one per unit, padded to 16 bytes) -- both zeroed in front of every launch that uses them --, the parked rows of the slices, then one row per rollout for the
+  // contacts above the LDS pool and, under slices, one more per rollout row of every wave slot for a pass that recomputes a missed hand-off.  A sliced request the pool
+  // refuses is asked again for whole groups (the parked rows are the bulk of it) before the launch gives the queue up.
+  int qgrid = grid;  // the queue's grid
+  if (persist) { if (qgrid > slots) qgrid = slots; if (m->rollout_max_workgroups > 0 && qgrid > m->rollout_max_workgroups) qgrid = m->rollout_max_workgroups; }  // (the cap: a test hook, few waves and many tickets)
+  size_t flag_words = 0, queue_bytes = 0, ovf_bytes = 0;
   float* scratch = nullptr; float* ovf = nullptr; unsigned* head = nullptr;
-  if (ovf_bytes > 0 || persist) scratch = jh_launch_scratch(m, ovf_bytes + (persist ? 16 : 0), st, ovf_bytes > 0);  // (nullptr: the LDS capacity alone, drops and the fallback counted -- and the static shape)
-  if (scratch && persist && hipMemsetAsync(scratch, 0, 16, st) != hipSuccess) { (void)hipGetLastError(); persist = false; }
+  for (;;) {
+    flag_words = slices > 1 ? (((size_t)slices * ngroups + 3) & ~(size_t)3) : 0;
+    const size_t park_floats = slices > 1 ? (size_t)(slices - 1) * ngroups * PARK_F : 0, own_rows = slices > 1 ? (size_t)qgrid * WAVES_PER_BLOCK * RPW : 0;
+    queue_bytes = persist ? 16 + (flag_words + park_floats) * sizeof(float) : 0;
+    ovf_bytes = NOVF > 0 ? ((size_t)N + own_rows) * NOVF * POOL_F * sizeof(float) : 0;
+    if (ovf_bytes > 0 || persist) scratch = jh_launch_scratch(m, ovf_bytes + queue_bytes, st, ovf_bytes > 0 && slices == 1);  // (nullptr: the LDS capacity alone, drops and the fallback counted -- and the static shape)
+    if (scratch || slices == 1) break;
+    slices = 1;
+  }
+  if (scratch && persist && hipMemsetAsync(scratch, 0, 16 + flag_words * sizeof(unsigned), st) != hipSuccess) { (void)hipGetLastError(); persist = false; }
   if (!scratch) persist = false;
-  if (persist) { head = (unsigned*)scratch; if (grid > slots) grid = slots; }
-  if (scratch && ovf_bytes > 0) ovf = scratch + (head ? 4 : 0);
+  if (persist) { head = (unsigned*)scratch; grid = qgrid; } else slices = 1;
+  if (scratch && ovf_bytes > 0) ovf = scratch + (head ? queue_bytes / sizeof(float) : 0);
+  __atomic_store_n(&m->last_rollout_slices, persist ? slices : 0, __ATOMIC_RELAXED);
+  const int slices_arg = slices | ((m->rollout_slice_flags & 1) << 8);
 #define JH_V5_LAUNCH_COST(SELF_, PERSIST_)                                                                                                                                        \
   hipLaunchKernelGGL((k_leap_v5<false, WAVES_PER_BLOCK, SELF_, PERSIST_>), dim3(grid), dim3(WAVE * WAVES_PER_BLOCK), 0, st, m->d_f, m->d_i, x0, 0, nominal, noise, ldn, sigma, W, \
-                     lohi, tp, N, n_offset, H, K, costs, knots_out, (const float*)nullptr, (float*)nullptr, (float*)nullptr, m->d_stats, dshift, trace, ovf, head, 0ll, 0ll, 0ll)
+                     lohi, tp, N, n_offset, H, K, costs, knots_out, (const float*)nullptr, (float*)nullptr, (float*)nullptr, m->d_stats, dshift, trace, ovf, head, 0ll, 0ll, 0ll, head ? head + 4 : (unsigned*)nullptr, slices_arg)
   if (m->self_collision && m->h_i[17] > 0) { if (persist) JH_V5_LAUNCH_COST(true, true); else JH_V5_LAUNCH_COST(true, false); }
   else { if (persist) JH_V5_LAUNCH_COST(false, true); else JH_V5_LAUNCH_COST(false, false); }
 #undef JH_V5_LAUNCH_COST
@@ -1889,11 +1986,11 @@ int JH_V5_NAME(jh_engine5_materialize)(const jh_model* m, const float* x0, int x
   if (m->self_collision && m->h_i[17] > 0)
     hipLaunchKernelGGL((k_leap_v5<true, WAVES_PER_BLOCK, true>), dim3(grid), dim3(WAVE * WAVES_PER_BLOCK), 0, st, m->d_f, m->d_i, x0, x0_batched, (const float*)nullptr, (const float*)nullptr, 0,
                        (const float*)nullptr, (const float*)nullptr, (const float*)nullptr, (const float*)nullptr, N, 0, H, 0, (float*)nullptr, (float*)nullptr,
-                       controls, states, sensors, m->d_stats, dshift, (float*)nullptr, ovf, (unsigned*)nullptr, 0ll, 0ll, 0ll);
+                       controls, states, sensors, m->d_stats, dshift, (float*)nullptr, ovf, (unsigned*)nullptr, 0ll, 0ll, 0ll, (unsigned*)nullptr, 0);
   else
     hipLaunchKernelGGL((k_leap_v5<true, WAVES_PER_BLOCK, false>), dim3(grid), dim3(WAVE * WAVES_PER_BLOCK), 0, st, m->d_f, m->d_i, x0, x0_batched, (const float*)nullptr, (const float*)nullptr, 0,
                        (const float*)nullptr, (const float*)nullptr, (const float*)nullptr, (const float*)nullptr, N, 0, H, 0, (float*)nullptr, (float*)nullptr,
-                       controls, states, sensors, m->d_stats, dshift, (float*)nullptr, ovf, (unsigned*)nullptr, 0ll, 0ll, 0ll);
+                       controls, states, sensors, m->d_stats, dshift, (float*)nullptr, ovf, (unsigned*)nullptr, 0ll, 0ll, 0ll, (unsigned*)nullptr, 0);
   return jh_launch_done(ovf, st);
 }
 
@@ -1913,7 +2010,7 @@ int JH_V5_NAME(jh_engine5_rollout_cost_batch)(const jh_model* m, const float* im
   float* ovf = ovf_bytes > 0 ? jh_launch_scratch(m, ovf_bytes, st) : nullptr;  // (nullptr: the LDS capacity alone, drops and the fallback counted)
 #define JH_V5_LAUNCH_BATCH(SELF_)                                                                                                                                                  \
   hipLaunchKernelGGL((k_leap_v5<false, WAVES_PER_BLOCK, SELF_, false, true>), dim3(grid, B), dim3(WAVE * WAVES_PER_BLOCK), 0, st, images, ints, x0, 0, nominal, noise, ldn, sigma, W, \
-                     lohi, tp, N, 0, H, K, costs, (float*)nullptr, (const float*)nullptr, (float*)nullptr, (float*)nullptr, m->d_stats, dshift, trace, ovf, (unsigned*)nullptr, blk_stride, noise_stride, image_stride)
+                     lohi, tp, N, 0, H, K, costs, (float*)nullptr, (const float*)nullptr, (float*)nullptr, (float*)nullptr, m->d_stats, dshift, trace, ovf, (unsigned*)nullptr, blk_stride, noise_stride, image_stride, (unsigned*)nullptr, 0)
   if (m->self_collision && m->h_i[17] > 0) JH_V5_LAUNCH_BATCH(true); else JH_V5_LAUNCH_BATCH(false);
 #undef JH_V5_LAUNCH_BATCH
   return jh_launch_done(ovf, st);

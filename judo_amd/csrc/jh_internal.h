@@ -35,6 +35,8 @@ struct jh_model {
   int arm_pairs;  // fr3_pick: candidate pairs of the image between two arm bodies other than the two fingers, or of a box on the arm against a capsule on the arm or the static base (engine_model.pack_engine_model on a description with "self_collision"); > 0 selects the self-collision build (jh_engine_v6_self.hip: generation 3) and nothing else runs such an image
   int self_collision;  // leap_cube on jh_engine_v5.hip: model the hand's own contacts (finger-finger, finger-palm) as MuJoCo does; 0 = the cube's contacts only
   int rollout_schedule;  // leap_cube generation 3, fused launches: 0 = persistent waves on a queue of rollout groups where the launch exceeds the GPU's wave slots (the default), 1 = always the static grid, 2 = the queue wherever the kernel has it (jh_model_set_rollout_schedule)
+  int rollout_slices = 0, rollout_max_workgroups = 0, rollout_slice_flags = 0;  // the queue's horizon slices (jh_model_set_rollout_slices): 0 = automatic or 1..64 forced; a cap on the queue's grid (0: the resident slots); bit 0: every hand-off counts as missed
+  mutable int last_rollout_slices = 0;  // what the model's last fused leap launch ran: 0 = the static grid, 1 = the queue of groups, S > 1 = the queue of S slices per group (jh_model_last_rollout_slices); __atomic builtins, as ovf_fallbacks
   int plan_step_launches;  // closed-form models' plan step: 0 = one launch where it fits (the default), 1 = always one launch, 2 = always two (jh_model_set_plan_step_launches)
   mutable int one_launch_steps = 0;  // plan steps that ran as one launch (jh_model_stats out[7]); __atomic builtins, as ovf_fallbacks
   mutable int ovf_fallbacks = 0;  // launches that ran without their overflow rows (jh_launch_scratch); updated with __atomic builtins: a planner thread may launch while another polls jh_model_stats

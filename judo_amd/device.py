@@ -184,6 +184,23 @@ class GpuModel:
         grid, 2 = the queue wherever the kernel has it (`jh_model_set_rollout_schedule`).  The bits do not depend on it."""
         _lib.check(_lib.lib().jh_model_set_rollout_schedule(self.handle, int(mode)), "jh_model_set_rollout_schedule")
 
+    def set_rollout_slices(self, slices: int = 0, max_workgroups: int = 0, flags: int = 0) -> None:
+        """leap_cube, kernel generation 3, the queue's units: `slices` 0 = (group, horizon slice) where the queue runs and the launch has at least two groups per resident
+        wave (default), 1..64 = that many slices wherever the queue runs (1: whole groups).  `max_workgroups` > 0 caps the queue's grid and `flags` bit 0 makes every
+        hand-off count as missed: test hooks (`jh_model_set_rollout_slices`).  The bits do not depend on any of it."""
+        _lib.check(_lib.lib().jh_model_set_rollout_slices(self.handle, int(slices), int(max_workgroups), int(flags)), "jh_model_set_rollout_slices")
+
+    def last_rollout_slices(self) -> int:
+        """What the last fused launch ran: 0 = the static grid, 1 = the queue of whole groups, S > 1 = the queue of S slices per group."""
+        return int(_lib.lib().jh_model_last_rollout_slices(self.handle))
+
+    def recomputed_units(self) -> int:
+        """Queue units that missed their hand-off and recomputed their group up to their slice, since the counters were last reset by `stats()` (synchronises)."""
+        v = int(_lib.lib().jh_model_recomputed_units(self.handle))
+        if v < 0:
+            _lib.check(v, "jh_model_recomputed_units")
+        return v
+
     def stats(self, reset: bool = True) -> dict:
         """Diagnostic counters of the articulated-body kernels (synchronises)."""
         out = (C.c_int * 8)()

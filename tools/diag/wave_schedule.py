@@ -2,9 +2,13 @@
 its wave's entry, after the staging barrier, at the group's start and at its end, with the workgroup and wave that ran it.  Plan steps of the recorded headline inputs
 (tools/diag/ab_inputs_leap.npz, as ab_fixed_inputs.py replays them) run under the static grid and under the queue (jh_model_set_rollout_schedule 1 / 2); printed per launch:
 the distribution of group durations, what a workgroup's waves wait for each other, the occupied wave slots over time, the drain at the end -- and what a greedy placement
-of the MEASURED durations (constant speed per slot) predicts for the static grid, a per-wave queue, a queue of horizon quarters and the ideal.
+of the MEASURED durations (constant speed per slot) predicts for the static grid, a per-wave queue, a queue of horizon slices and the ideal.
+--slices S[,S..] (default 1,2,4): the replay's queue of (group, slice) units -- a group's S equal parts, each the group's measured duration / S, taken breadth-first
+(all first slices, then all second ones; hand-offs not modelled).  S = 1 is the per-wave queue.
+--kernel-slices S (default 0: the launcher's rule): what jh_model_set_rollout_slices is given for the launches themselves; the kernel stamps per UNIT, so the
+durations printed for a sliced launch are a slice's, and the replay is printed for unsliced launches only.  --max-workgroups W caps the queue's grid (0: the resident slots).
 build:  tools/diag/build_variant.sh wavestamp judo_amd/csrc/jh_engine_v5.hip -DJH_V5_WAVESTAMP
-usage:  JUDO_AMD_LIB=variants/libjudo_amd_wavestamp.so python tools/diag/wave_schedule.py [plan steps, default 5,35] [schedules, default 1,2]"""
+usage:  JUDO_AMD_LIB=variants/libjudo_amd_wavestamp.so python tools/diag/wave_schedule.py [plan steps, default 5,35] [schedules, default 1,2] [--slices 1,2,4] [--kernel-slices S]"""
 import ctypes as C, heapq, os, sys
 import numpy as np, torch
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__)))))
@@ -12,14 +16,29 @@ from judo_amd.controller import make_controller
 from judo_amd import _lib
 
 N, H, WPB, TICK_US = 65536, 64, 4, 0.01
+
+
+def _opt(name, default):
+    """Takes `name VALUE` out of sys.argv."""
+    if name in sys.argv:
+        k = sys.argv.index(name); v = sys.argv[k + 1]; del sys.argv[k:k + 2]
+        return v
+    return default
+
+
+SLICES = [int(a) for a in _opt("--slices", "1,2,4").split(",")]
+KSLICES, MAXWG = int(_opt("--kernel-slices", "0")), int(_opt("--max-workgroups", "0"))
 d = np.load(os.path.join(os.path.dirname(os.path.abspath(__file__)), "ab_inputs_leap.npz"))
 c = make_controller("leap_cube", "mppi"); c.optimizer.config.num_rollouts = N; c.controller_cfg.horizon = H * c.task.dt
 c.reset(); c.current_state = c.task.default_state(); c.system_metadata = {"goal_quat": np.array([0.0, 1.0, 0.0, 0.0])}
 L = _lib.lib()
 L.jh_v5_wavestamp_buffer.argtypes = [C.c_void_p, C.c_int]; L.jh_v5_wavestamp_buffer.restype = C.c_int  # AttributeError: not a -DJH_V5_WAVESTAMP build
 G = (N + 3) // 4
-buf = torch.zeros((G, 6), dtype=torch.int64, device="cuda")
-assert L.jh_v5_wavestamp_buffer(buf.data_ptr(), G) == 0
+ROWS = G * (min(KSLICES, H) if KSLICES else 8)  # one stamp row per queue unit: unit t is slice t // G of group t % G (unsliced launches: the group); room for an automatic schedule of up to 8 slices
+buf = torch.zeros((ROWS, 6), dtype=torch.int64, device="cuda")
+assert L.jh_v5_wavestamp_buffer(buf.data_ptr(), ROWS) == 0
+if KSLICES or MAXWG:
+    c.model.set_rollout_slices(KSLICES, MAXWG, 0)  # (AttributeError: a library from before the slices)
 SLOTS = 2 * torch.cuda.get_device_properties(0).multi_processor_count * WPB  # waves of this kernel the GPU holds: two workgroups of four per CU
 steps = [int(a) for a in (sys.argv[1] if len(sys.argv) > 1 else "5,35").split(",")]
 modes = [int(a) for a in (sys.argv[2] if len(sys.argv) > 2 else "1,2").split(",")]
@@ -38,10 +57,9 @@ def model(dur):
     """The greedy model on measured group durations `dur` (launch order)."""
     pad = np.concatenate([dur, np.zeros(-len(dur) % WPB)]).reshape(-1, WPB)
     static = greedy(pad.max(axis=1), SLOTS // WPB)  # a workgroup's slots are held until its slowest wave ends
-    queue = greedy(dur, SLOTS)
-    quarters = greedy(np.tile(dur / 4, 4), SLOTS)  # slice-major tickets: all first quarters before any second (hand-off waits not modelled)
+    sliced = [greedy(np.tile(dur / s, s), SLOTS) for s in SLICES]  # breadth-first tickets: all first slices before any second (hand-offs not modelled); S = 1: the per-wave queue
     ideal = dur.sum() / SLOTS
-    return static, queue, quarters, ideal
+    return static, sliced, ideal
 
 
 def pct(a, q): return float(np.percentile(a, q))
@@ -55,14 +73,16 @@ for i in steps:
             c.optimizer.seed(1000 + i); c.nominal_knots = d["knots"][i].copy(); c.times = d["times"][i].copy(); c.update_spline(c.times, c.nominal_knots); c.time = float(d["t"][i])
             c.update_action(); torch.cuda.synchronize()
         a = buf.cpu().numpy()
-        assert (a[:, 5] == 1).all(), "groups without a stamp"
+        a = a[a[:, 5] == 1]  # (a sliced launch stamps its units; a launch the rule leaves unsliced, and the static grid, the first G rows)
+        assert len(a) == G * max(1, c.model.last_rollout_slices()), "units without a stamp"
+        sliced_launch = len(a) > G
         wg, wv = a[:, 0] >> 32, (a[:, 0] >> 8) & 0xFF
         t0 = a[:, 1].min()
         entry, staged, start, end = ((a[:, k] - t0) * TICK_US for k in (1, 2, 3, 4))  # microseconds from the first wave's entry
         dur = end - start
         kernel = end.max()
-        print(f"\nplan step {i}, schedule {mode} ({'static grid' if mode == 1 else 'queue'}): {G} groups on {int(wg.max()) + 1} workgroups, {SLOTS} wave slots; launch {kernel / 1e3:.2f} ms from first entry to last end")
-        print(f"  group duration [ms]: mean {dur.mean() / 1e3:.3f}  cv {dur.std() / dur.mean():.4f}  p50 {pct(dur, 50) / 1e3:.3f}  p90 {pct(dur, 90) / 1e3:.3f}  p99 {pct(dur, 99) / 1e3:.3f}  max {dur.max() / 1e3:.3f}")
+        print(f"\nplan step {i}, schedule {mode} ({'static grid' if mode == 1 else 'queue'}): {len(a)} {'units (group, slice)' if sliced_launch else 'groups'} on {int(wg.max()) + 1} workgroups, {SLOTS} wave slots; launch {kernel / 1e3:.2f} ms from first entry to last end")
+        print(f"  {'unit' if sliced_launch else 'group'} duration [ms]: mean {dur.mean() / 1e3:.3f}  cv {dur.std() / dur.mean():.4f}  p50 {pct(dur, 50) / 1e3:.3f}  p90 {pct(dur, 90) / 1e3:.3f}  p99 {pct(dur, 99) / 1e3:.3f}  max {dur.max() / 1e3:.3f}")
         print(f"  staging (entry -> barrier passed) [us]: mean {(staged - entry).mean():.1f}  max {(staged - entry).max():.1f}")
         wave = wg * WPB + wv  # the wave (slot holder) that ran each group
         order = np.argsort(wave, kind="stable")
@@ -81,8 +101,9 @@ for i in steps:
         # the drain: once the last group has started nothing is left to hand out, and the first slot that frees after that stays empty
         drain = kernel - end[end > start.max()].min()
         print(f"  resident-wave share from the stamps {share:.3f}; most waves at once {int(occ.max())}; from the first slot that stays empty to the end {drain / 1e3:.3f} ms ({100 * drain / kernel:.1f} % of the launch)")
-        if mode == 1:
-            s_, q_, h_, id_ = model(dur)
-            print(f"  greedy model on these durations: static grid {s_ / 1e3:.2f} ms (measured {kernel / 1e3:.2f}); per-wave queue {q_ / 1e3:.2f} ms ({100 * (1 - q_ / s_):.1f} % shorter); "
-                  f"queue of horizon quarters {h_ / 1e3:.2f} ms ({100 * (1 - h_ / s_):.1f} %); ideal {id_ / 1e3:.2f} ms ({100 * (1 - id_ / s_):.1f} %)")
+        if not sliced_launch:  # (the replay wants whole groups' durations, in ticket order: under the queue the first SLOTS groups are the waves' own, the rest in the order drawn)
+            s_, sl_, id_ = model(dur)
+            ref_ = kernel if mode == 2 else s_
+            print(f"  greedy model on these durations: static grid {s_ / 1e3:.2f} ms; " + "; ".join(f"queue, S = {s} {v / 1e3:.2f} ms ({100 * (1 - v / ref_):.1f} %)" for s, v in zip(SLICES, sl_))
+                  + f"; ideal {id_ / 1e3:.2f} ms ({100 * (1 - id_ / ref_):.1f} %)  [per cent shorter than {'this measured launch' if mode == 2 else 'the replayed static grid'}, {ref_ / 1e3:.2f} ms]")
 assert L.jh_v5_wavestamp_buffer(None, 0) == 0
