@@ -204,8 +204,8 @@ extern "C" int jh_model_dims(const jh_model* m, int* dims) {
 
 extern "C" int jh_model_stats(jh_model* m, int* out, int reset) {
   JH_REQUIRE(m && out, "model_stats: null pointer");
-  JH_HIP(hipMemcpy(out, m->d_stats, 4 * sizeof(int), hipMemcpyDeviceToHost));
-  JH_HIP(hipMemcpy(out + 4, m->d_stats + 20, 2 * sizeof(int), hipMemcpyDeviceToHost));
+  JH_HIP(hipMemcpy(out, m->d_stats + JH_STAT_DROPS, 4 * sizeof(int), hipMemcpyDeviceToHost));  // (... JH_STAT_STEPS)
+  JH_HIP(hipMemcpy(out + 4, m->d_stats + JH_STAT_WAVE_ITERS, 2 * sizeof(int), hipMemcpyDeviceToHost));  // (and JH_STAT_WAVE_STEPS)
   out[6] = reset ? __atomic_exchange_n(&m->ovf_fallbacks, 0, __ATOMIC_RELAXED) : __atomic_load_n(&m->ovf_fallbacks, __ATOMIC_RELAXED);
   out[7] = reset ? __atomic_exchange_n(&m->one_launch_steps, 0, __ATOMIC_RELAXED) : __atomic_load_n(&m->one_launch_steps, __ATOMIC_RELAXED);
   if (reset) JH_HIP(hipMemset(m->d_stats, 0, JH_NSTATS * sizeof(int)));
@@ -233,6 +233,16 @@ extern "C" int jh_register_xcheck(const jh_xcheck_launchers* launchers) {
 }
 
 static bool articulated(const jh_model* m) { return m->kind == JH_TASK_LEAP_CUBE || m->kind == JH_TASK_FR3_PICK; }
+
+// The build that runs a model: the one place that chooses among the rows of jh_internal.h.  The leap family: the cylinder build for an image with cylinders, else the
+// 64-contact build where jh_model_set_contact_capacity asked for it, else the 48-contact one; fr3: the self-collision build for an image with arm pairs, else the default.
+// Null: a closed-form model, or a cross-check generation (g_xcheck).
+static const jh_engine_build* engine_build(const jh_model* m) {
+  if (m->kernel_gen != 3) return nullptr;
+  if (m->kind == JH_TASK_LEAP_CUBE) return m->cylinders > 0 ? &jh_engine5_build_cyl : m->contact_capacity > 48 ? &jh_engine5_build_cap64 : &jh_engine5_build;
+  if (m->kind == JH_TASK_FR3_PICK) return m->arm_pairs > 0 ? &jh_engine6_build_self : &jh_engine6_build;
+  return nullptr;
+}
 
 extern "C" int jh_model_set_kernel(jh_model* m, int generation) {
   JH_REQUIRE(m && generation >= 1 && generation <= 3, "model_set_kernel: generation must be 1, 2 or 3");
@@ -278,8 +288,9 @@ extern "C" int jh_model_set_contact_capacity(jh_model* m, int contacts) {
 extern "C" int jh_model_build(const jh_model* m, int* out) {
   JH_REQUIRE(m && out, "model_build: null pointer");
   out[0] = m->kernel_gen;
-  out[1] = m->kind == JH_TASK_LEAP_CUBE && m->kernel_gen == 3 ? m->contact_capacity : 0;
-  out[2] = m->kind == JH_TASK_LEAP_CUBE && m->kernel_gen == 3 && m->cylinders > 0 ? 1 : 0;
+  const jh_engine_build* eb = engine_build(m);
+  out[1] = eb && m->kind == JH_TASK_LEAP_CUBE ? eb->contact_capacity : 0;
+  out[2] = eb == &jh_engine5_build_cyl ? 1 : 0;
   out[3] = m->cylinders;
   return JH_OK;
 }
@@ -287,10 +298,10 @@ extern "C" int jh_model_build(const jh_model* m, int* out) {
 extern "C" int jh_model_fr3_build(const jh_model* m, int* out) {
   JH_REQUIRE(m && out, "model_fr3_build: null pointer");
   const bool fr3 = m->kind == JH_TASK_FR3_PICK;
-  out[0] = fr3 && m->kernel_gen == 3 && m->arm_pairs > 0 ? 1 : 0;
+  out[0] = engine_build(m) == &jh_engine6_build_self ? 1 : 0;
   out[1] = fr3 ? m->arm_pairs : 0;
-  out[2] = fr3 && jh_model_is_fr3(m) ? 1 : 0;
-  out[3] = fr3 && jh_model_is_fr3_self(m) ? 1 : 0;
+  out[2] = fr3 && jh_engine6_build.accepts(m) ? 1 : 0;
+  out[3] = fr3 && jh_engine6_build_self.accepts(m) ? 1 : 0;
   return JH_OK;
 }
 
@@ -326,7 +337,8 @@ extern "C" int jh_model_limits(const jh_model* m, int* out) {
   out[0] = max_fused_knots(m, 1);  // upper bound over all horizons; jh_model_max_fused_knots(m, H) is the figure for a given H
   out[1] = JH_MAX_KNOT_DIM;
   out[2] = JH_MAX_ELITES;
-  out[3] = m->kind == JH_TASK_LEAP_CUBE ? (m->kernel_gen >= 3 ? m->contact_capacity : 32) : (m->kind == JH_TASK_FR3_PICK ? (m->kernel_gen >= 3 ? 96 : 32) : 0);  // (generation 3: leap 48, all in LDS, or 64 with 16 in a row of global memory: jh_model_set_contact_capacity; fr3 32 in LDS + 64 in such a row, next to its 96 pad-against-pad slots)
+  const jh_engine_build* eb = engine_build(m);
+  out[3] = eb ? eb->contact_capacity : (articulated(m) ? 32 : 0);  // (generation 3: leap 48, all in LDS, or 64 with 16 in a row of global memory: jh_model_set_contact_capacity; fr3 32 in LDS + 64 in such a row, next to its 96 pad-against-pad slots; the cross-check generations: 32)
   return JH_OK;
 }
 
@@ -370,7 +382,7 @@ extern "C" int jh_model_last_rollout_slices(const jh_model* m) {
 extern "C" int jh_model_recomputed_units(jh_model* m) {
   JH_REQUIRE(m != nullptr, "model_recomputed_units: null model");
   int v = 0;
-  JH_HIP(hipMemcpy(&v, m->d_stats + 56, sizeof(int), hipMemcpyDeviceToHost));  // (STAT_RECOMPUTED of jh_engine_v5.hip)
+  JH_HIP(hipMemcpy(&v, m->d_stats + JH_STAT_RECOMPUTED, sizeof(int), hipMemcpyDeviceToHost));
   return v;
 }
 
@@ -446,34 +458,33 @@ extern "C" int jh_model_profile(jh_model* m, long long* out /* 10 phase cycle to
   return JH_OK;
 }
 
-extern "C" int jh_rollout_cost(const jh_model* m, const float* x0, const float* nominal, const float* noise, int ldn, const float* sigma,
-                               const float* W, const float* lohi, const float* tp, int phase, int N, int n_offset, int H, int K, float* costs,
-                               float* knots_out, void* stream) {
-  return jh_rollout_cost_traced(m, x0, nominal, noise, ldn, sigma, W, lohi, tp, phase, N, n_offset, H, K, costs, knots_out, nullptr, stream);
+// One fused launch on the record: the argument checks, then the model's build (or the closed-form kernels, or the cross-check library).
+static int rollout_cost(const jh_model* m, const jh_rollout_args& a, void* stream) {
+  JH_REQUIRE(m && a.x0 && a.nominal && a.noise && a.sigma && a.W && a.lohi && a.tp && a.costs, "rollout_cost: null pointer");
+  if (a.trace) { int adr, nfl, cm; trace_layout(m, &adr, &nfl, &cm); JH_REQUIRE(nfl > 0, "rollout_cost_traced: this model's fused kernel writes no trace sensors (jh_model_trace_layout)"); }
+  JH_REQUIRE(a.N > 0 && a.H > 0 && a.K >= 1, "rollout_cost: N, H, K must be positive (N=%d H=%d K=%d)", a.N, a.H, a.K);
+  JH_REQUIRE(a.ldn >= a.N, "rollout_cost: ldn (%d) < N (%d)", a.ldn, a.N);
+  JH_REQUIRE(a.K * m->nu <= JH_MAX_KNOT_DIM, "rollout_cost: K*nu = %d exceeds %d", a.K * m->nu, JH_MAX_KNOT_DIM);
+  JH_REQUIRE(a.n_offset >= 0, "rollout_cost: negative n_offset");
+  hipStream_t st = (hipStream_t)stream;
+  if (m->kind == JH_TASK_CARTPOLE || m->kind == JH_TASK_CYLINDER_PUSH) return jh_simple_rollout_cost(m, a, st);
+  if (const jh_engine_build* eb = engine_build(m)) return eb->rollout_cost(m, a, st);
+  JH_REQUIRE(a.trace == nullptr, "rollout_cost_traced: only the product kernels (generation 3, cartpole, cylinder_push) write trace sensors");
+  if (!g_xcheck.rollout_cost) { jh_set_error("rollout_cost: no kernel for this model / generation in this library"); return JH_ERR_UNSUPPORTED; }
+  return g_xcheck.rollout_cost(m, m->kernel_gen, a.x0, a.nominal, a.noise, a.ldn, a.sigma, a.W, a.lohi, a.tp, a.phase, a.N, a.n_offset, a.H, a.K, a.costs, a.knots_out, stream);
 }
 
 extern "C" int jh_rollout_cost_traced(const jh_model* m, const float* x0, const float* nominal, const float* noise, int ldn, const float* sigma,
                                       const float* W, const float* lohi, const float* tp, int phase, int N, int n_offset, int H, int K, float* costs,
                                       float* knots_out, float* trace, void* stream) {
-  JH_REQUIRE(m && x0 && nominal && noise && sigma && W && lohi && tp && costs, "rollout_cost: null pointer");
-  if (trace) { int adr, nfl, cm; trace_layout(m, &adr, &nfl, &cm); JH_REQUIRE(nfl > 0, "rollout_cost_traced: this model's fused kernel writes no trace sensors (jh_model_trace_layout)"); }
-  JH_REQUIRE(N > 0 && H > 0 && K >= 1, "rollout_cost: N, H, K must be positive (N=%d H=%d K=%d)", N, H, K);
-  JH_REQUIRE(ldn >= N, "rollout_cost: ldn (%d) < N (%d)", ldn, N);
-  JH_REQUIRE(K * m->nu <= JH_MAX_KNOT_DIM, "rollout_cost: K*nu = %d exceeds %d", K * m->nu, JH_MAX_KNOT_DIM);
-  JH_REQUIRE(n_offset >= 0, "rollout_cost: negative n_offset");
-  hipStream_t st = (hipStream_t)stream;
-  if (m->kind == JH_TASK_CARTPOLE || m->kind == JH_TASK_CYLINDER_PUSH)
-    return jh_simple_rollout_cost(m, x0, nominal, noise, ldn, sigma, W, lohi, tp, N, n_offset, H, K, costs, knots_out, trace, st);
-  if (m->kind == JH_TASK_LEAP_CUBE && m->kernel_gen == 3)
-    return m->cylinders > 0         ? jh_engine5_rollout_cost_cyl(m, x0, nominal, noise, ldn, sigma, W, lohi, tp, N, n_offset, H, K, costs, knots_out, trace, st)
-           : m->contact_capacity > 48 ? jh_engine5_rollout_cost_cap64(m, x0, nominal, noise, ldn, sigma, W, lohi, tp, N, n_offset, H, K, costs, knots_out, trace, st)
-                                    : jh_engine5_rollout_cost(m, x0, nominal, noise, ldn, sigma, W, lohi, tp, N, n_offset, H, K, costs, knots_out, trace, st);
-  if (m->kind == JH_TASK_FR3_PICK && m->kernel_gen == 3)
-    return m->arm_pairs > 0 ? jh_engine6_rollout_cost_self(m, x0, nominal, noise, ldn, sigma, W, lohi, tp, phase, N, n_offset, H, K, costs, knots_out, trace, st)
-                            : jh_engine6_rollout_cost(m, x0, nominal, noise, ldn, sigma, W, lohi, tp, phase, N, n_offset, H, K, costs, knots_out, trace, st);
-  JH_REQUIRE(trace == nullptr, "rollout_cost_traced: only the product kernels (generation 3, cartpole, cylinder_push) write trace sensors");
-  if (!g_xcheck.rollout_cost) { jh_set_error("rollout_cost: no kernel for this model / generation in this library"); return JH_ERR_UNSUPPORTED; }
-  return g_xcheck.rollout_cost(m, m->kernel_gen, x0, nominal, noise, ldn, sigma, W, lohi, tp, phase, N, n_offset, H, K, costs, knots_out, stream);
+  const jh_rollout_args a = {x0, nominal, noise, ldn, sigma, W, lohi, tp, phase, N, n_offset, H, K, costs, knots_out, trace};
+  return rollout_cost(m, a, stream);
+}
+
+extern "C" int jh_rollout_cost(const jh_model* m, const float* x0, const float* nominal, const float* noise, int ldn, const float* sigma,
+                               const float* W, const float* lohi, const float* tp, int phase, int N, int n_offset, int H, int K, float* costs,
+                               float* knots_out, void* stream) {
+  return jh_rollout_cost_traced(m, x0, nominal, noise, ldn, sigma, W, lohi, tp, phase, N, n_offset, H, K, costs, knots_out, nullptr, stream);
 }
 
 // Closed-form models (cartpole, cylinder_push): the rollout kernels are ~50 us, so a second launch and the gap in front of it are a fifth of the plan step -- the two run as
@@ -517,7 +528,8 @@ static int plan_step(const char* who, const jh_model* m, void* blk_dev, const vo
   if (rc == JH_OK) rc = plan_step_launches(m, N, H, K, costs, knots_out, W, noise, ldn, &one);
   // two launches: the rollout kernel, then k_update_tail; one (closed-form models): rollout + cost + the update's tail in jh_simple.hip's k_plan_step, where the
   // rollout / update split of the timing events collapses
-  if (rc == JH_OK && !one) rc = jh_rollout_cost_traced(m, b, b + o_nominal, noise, ldn, b + o_sigma, W, b + o_lohi, b + o_tp, phase, N, n_offset, H, K, costs, knots_out, trace, stream);
+  const jh_rollout_args ra = {b, b + o_nominal, noise, ldn, b + o_sigma, W, b + o_lohi, b + o_tp, phase, N, n_offset, H, K, costs, knots_out, trace};
+  if (rc == JH_OK && !one) rc = rollout_cost(m, ra, stream);
   if (rc == JH_OK && !one && timing) JH_HIP(hipEventRecord((hipEvent_t)timing[1], st));
   jh_upd::TailArgs a;
   if (rc == JH_OK)
@@ -571,7 +583,8 @@ static int plan_step_batch(const char* who, const jh_model* m, const float* imag
   const size_t rec = 2 * (size_t)KU + (size_t)E_t * (2 + (size_t)(E_t > 0 ? row_floats : 0));
   JH_REQUIRE(out_stride_floats >= rec, "%s: out_stride_floats = %zu is smaller than an output record (nominal | sigma | E trace records = %zu floats)", who, out_stride_floats, rec);
   const bool closed = m->kind == JH_TASK_CARTPOLE || m->kind == JH_TASK_CYLINDER_PUSH;
-  if (!closed && m->kind != JH_TASK_LEAP_CUBE) { jh_set_error("%s: no batched kernel for this model", who); return JH_ERR_UNSUPPORTED; }
+  const jh_engine_build* eb = engine_build(m);
+  if (!closed && !(eb && eb->rollout_cost_batch)) { jh_set_error("%s: no batched kernel for this model", who); return JH_ERR_UNSUPPORTED; }
   hipStream_t st = (hipStream_t)stream;
   const float* b = (const float*)blk_dev;
   if (blk_dev != blk_host) { const int rc = jh_upload_async(blk_dev, blk_host, (size_t)(B - 1) * blk_stride_bytes + blk_bytes, stream); if (rc != JH_OK) return rc; }
@@ -591,10 +604,11 @@ static int plan_step_batch(const char* who, const jh_model* m, const float* imag
   if (one) rc = jh_simple_plan_step_batch(m, images, b, W, b + o_tp, H, K, a, s, st);
   else {
     if (closed) rc = jh_simple_rollout_cost_batch(m, images, b, b + o_tp, W, H, K, a, s, st);
-    else
-      rc = m->cylinders > 0           ? jh_engine5_rollout_cost_batch_cyl(m, images, image_stride, ints, B, b, b + o_nominal, b + o_sigma, b + o_lohi, b + o_tp, s.blk, noise, ldn, s.noise, W, N, H, K, costs, trace, st)
-           : m->contact_capacity > 48 ? jh_engine5_rollout_cost_batch_cap64(m, images, image_stride, ints, B, b, b + o_nominal, b + o_sigma, b + o_lohi, b + o_tp, s.blk, noise, ldn, s.noise, W, N, H, K, costs, trace, st)
-                                      : jh_engine5_rollout_cost_batch(m, images, image_stride, ints, B, b, b + o_nominal, b + o_sigma, b + o_lohi, b + o_tp, s.blk, noise, ldn, s.noise, W, N, H, K, costs, trace, st);
+    else {
+      const jh_rollout_args ra = {b, b + o_nominal, noise, ldn, b + o_sigma, W, b + o_lohi, b + o_tp, 0, N, 0, H, K, costs, nullptr, trace};
+      const jh_rollout_batch rb = {images, image_stride, ints, B, s.blk, s.noise};
+      rc = eb->rollout_cost_batch(m, ra, rb, st);
+    }
     if (rc == JH_OK && timing) JH_HIP(hipEventRecord((hipEvent_t)timing[1], st));
     if (rc == JH_OK) rc = jh_update_tail_batch_launch(a, s, st);
   }
@@ -668,8 +682,7 @@ static int model_set_member(const char* who, const jh_model* m0, const jh_model*
   }
   JH_REQUIRE(m->h_f.size() == m->nf && m->d_f, "%s: member %d has no float section of nf = %zu floats", who, b, m->nf);
   if (m->kind == JH_TASK_LEAP_CUBE) {  // the single-call launcher's own acceptance test, on this member's floats (model_is_leap reads h_f: an isotropic cube inertia)
-    const bool ok = m->cylinders > 0 ? jh_engine5_accepts_cyl(m) : m->contact_capacity > 48 ? jh_engine5_accepts_cap64(m) : jh_engine5_accepts(m);
-    if (!ok) {
+    if (!engine_build(m)->accepts(m)) {  // (generation 3: checked above)
       jh_set_error("%s: member %d: the leap kernel does not accept this image (dimensions, table sizes, or h_f: the cube's inertia must be isotropic)", who, b);
       return JH_ERR_UNSUPPORTED;
     }
@@ -821,10 +834,7 @@ extern "C" int jh_rollout_materialize(const jh_model* m, const float* x0, int x0
   JH_REQUIRE(N > 0 && H > 0, "rollout_materialize: N and H must be positive (N=%d H=%d)", N, H);
   hipStream_t st = (hipStream_t)stream;
   if (m->kind == JH_TASK_CARTPOLE || m->kind == JH_TASK_CYLINDER_PUSH) return jh_simple_materialize(m, x0, x0_batched, controls, N, H, states, sensors, st);
-  if (m->kind == JH_TASK_LEAP_CUBE && m->kernel_gen == 3)
-    return m->cylinders > 0 ? jh_engine5_materialize_cyl(m, x0, x0_batched, controls, N, H, states, sensors, st) : m->contact_capacity > 48 ? jh_engine5_materialize_cap64(m, x0, x0_batched, controls, N, H, states, sensors, st) : jh_engine5_materialize(m, x0, x0_batched, controls, N, H, states, sensors, st);
-  if (m->kind == JH_TASK_FR3_PICK && m->kernel_gen == 3)
-    return m->arm_pairs > 0 ? jh_engine6_materialize_self(m, x0, x0_batched, controls, N, H, states, sensors, st) : jh_engine6_materialize(m, x0, x0_batched, controls, N, H, states, sensors, st);
+  if (const jh_engine_build* eb = engine_build(m)) return eb->materialize(m, x0, x0_batched, controls, N, H, states, sensors, st);
   if (!g_xcheck.rollout_materialize) { jh_set_error("rollout_materialize: no kernel for this model / generation in this library"); return JH_ERR_UNSUPPORTED; }
   return g_xcheck.rollout_materialize(m, m->kernel_gen, x0, x0_batched, controls, N, H, states, sensors, stream);
 }

@@ -90,7 +90,6 @@ constexpr int CVX_STOP_NM = 1000;   // the stop of the cylinder build's GJK + EP
 #define OPAQUE(x) asm volatile("" : "+v"(x))
 // The parked state of a horizon slice (see the kernel): PARK_F floats per queue unit, every word stored and loaded at device scope
 constexpr int PARK_F = 5 * 64;
-constexpr int STAT_RECOMPUTED = 56;  // stats word (every build): queue units whose hand-off was missed and which recomputed their group up to their slice (jh_model_recomputed_units)
 #ifndef JH_V5_AUTO_SLICES
 #define JH_V5_AUTO_SLICES 4  // the slices of the automatic schedule (profiles/leap_horizon_slices.md)
 #endif
@@ -450,7 +449,7 @@ __device__ __forceinline__ bool chain_elim_order(int cmask, int c, int& level, i
 // slice's first step -- the same instructions on the same inputs, the same bits; trace rows written twice carry the same words -- zeroes the counters and goes on into its own
 // slice.  While it recomputes it adds to no counter (`stats` is null for that pass: the dropped contacts and lost candidate pairs of those steps are the producer's to count) and
 // its contacts above the LDS pool go to a row of its wave slot's own behind the rollouts' rows (the producer may still be running the same rollouts on theirs); the
-// launch counts such units in stats[STAT_RECOMPUTED].  Nothing polls and no wave waits for another.  Every flag and every parked row is written by one unit and read by at most one, once per launch.
+// launch counts such units in stats[JH_STAT_RECOMPUTED].  Nothing polls and no wave waits for another.  Every flag and every parked row is written by one unit and read by at most one, once per launch.
 // BATCH (fused mode, static grid only -- there is NO queue for batched launches: a batch's problems fill the GPU side by side, and a queue across problems would have to
 // re-stage a workgroup's task parameters per group): B independent problems in one launch (jh_plan_step_batch), grid (groups of a problem, B).  A workgroup stages sTp once,
 // so it belongs to one problem, blockIdx.y; everything a problem owns -- its packed block (x0, nominal, sigma, task parameters, bounds: `batch_blk` floats apart), its noise
@@ -945,7 +944,7 @@ __global__ __launch_bounds__(WAVE * WPB, WAVES_PER_EU) void k_leap_v5(const floa
 #ifdef JH_V5_COUNT
       { const int nbm = wave_rowmax(nbl); if (lane == 0) V5_CADD(CB_BOXMAX, nbm); if (l == 0 && live) V5_CMAX(CB_MBOX, nbl); }
 #endif
-      if (nbl > MAXBPL) { if (l == 0 && live && stats) atomicAdd(stats, nbl - MAXBPL); nbl = MAXBPL; }  // (counted with the dropped contacts)
+      if (nbl > MAXBPL) { if (l == 0 && live && stats) atomicAdd(stats + JH_STAT_DROPS, nbl - MAXBPL); nbl = MAXBPL; }  // (counted with the dropped contacts)
 #ifdef JH_V5_COUNT
       if (l == 0 && live) cnt_bp += nbl;
 #endif
@@ -1031,7 +1030,7 @@ __global__ __launch_bounds__(WAVE * WPB, WAVES_PER_EU) void k_leap_v5(const floa
 #endif
       hand_hits = nh > nh_cube;
       }
-      if (nh > MAXHIT) { if (l == 0 && live && stats) atomicAdd(stats, nh - MAXHIT); nh = MAXHIT; }  // (candidate pairs lost: counted with the dropped contacts)
+      if (nh > MAXHIT) { if (l == 0 && live && stats) atomicAdd(stats + JH_STAT_DROPS, nh - MAXHIT); nh = MAXHIT; }  // (candidate pairs lost: counted with the dropped contacts)
       WSYNC();
       V5_TICK(1)
       // narrow phase: survivor i goes to lane i; side A is the cube or the first geom of a hand pair, side B a hand geom
@@ -1862,7 +1861,7 @@ __global__ __launch_bounds__(WAVE * WPB, WAVES_PER_EU) void k_leap_v5(const floa
   }
   if constexpr (PERSIST) {  // a missed hand-off: that was the group up to the slice's first step -- once more round the loop for the slice, nothing flushed
     again = __builtin_amdgcn_readfirstlane(sUnit[4 * wv]) < __builtin_amdgcn_readfirstlane(sUnit[4 * wv + 2]);
-    if (again) { if (lane == 0 && stats_) atomicAdd(stats_ + STAT_RECOMPUTED, 1); continue; }
+    if (again) { if (lane == 0 && stats_) atomicAdd(stats_ + JH_STAT_RECOMPUTED, 1); continue; }
   }
   int usteps = H; bool last = true;  // the steps this unit ran (and counts); whether it ends the rollouts
   if constexpr (PERSIST) { const int h0 = __builtin_amdgcn_readfirstlane(sUnit[4 * wv + 1]), h1 = __builtin_amdgcn_readfirstlane(sUnit[4 * wv + 2]); usteps = h1 - h0; last = h1 >= H; unit = __builtin_amdgcn_readfirstlane(sUnit[4 * wv + 3]); }
@@ -1874,8 +1873,8 @@ __global__ __launch_bounds__(WAVE * WPB, WAVES_PER_EU) void k_leap_v5(const floa
                             for (int k = 0; k < 16; k++) atomicAdd((unsigned long long*)(stats + 384) + k, (unsigned long long)cyc[k]); }
 #endif
   if (!MATERIALIZE && live && l == 0 && last) costs[n] = acc / (float)H;
-  if (stats && live && l == 0) { if (n_maxed) atomicAdd(stats + 1, n_maxed); atomicAdd(stats + 2, n_iters); atomicAdd(stats + 3, usteps); }
-  if (stats && lane == 0 && live) { atomicAdd(stats + 20, n_wave_iters); atomicAdd(stats + 21, usteps); }
+  if (stats && live && l == 0) { if (n_maxed) atomicAdd(stats + JH_STAT_ITER_CAP, n_maxed); atomicAdd(stats + JH_STAT_ITERS, n_iters); atomicAdd(stats + JH_STAT_STEPS, usteps); }
+  if (stats && lane == 0 && live) { atomicAdd(stats + JH_STAT_WAVE_ITERS, n_wave_iters); atomicAdd(stats + JH_STAT_WAVE_STEPS, usteps); }
   if constexpr (PERSIST) if (!last) {  // park the state for the next slice: the rows, a device-scope release by the whole wave, then the unit's flag
     float* pk = park + (size_t)unit * PARK_F;
     float pv = l == 13 ? acc : 0.f;
@@ -1912,6 +1911,41 @@ int device_cus(const jh_model* m) {  // (per call, of the model's device: a proc
   return (hipDeviceGetAttribute(&v, hipDeviceAttributeMultiprocessorCount, m->device) == hipSuccess && v > 0) ? v : 256;
 }
 
+// The build's acceptance test: JH_OK, or the status with the error set under the caller's name (`who` null: no message).
+int leap_refusal(const jh_model* m, const char* who) {
+  if (!model_is_leap(m)) { if (who) jh_set_error("%s: the cooperative engine kernel is instantiated for leap_cube only", who); return JH_ERR_UNSUPPORTED; }
+  if ((m->cylinders > 0) != (JH_V5_CYL != 0)) { if (who) jh_set_error("%s: an image with cylinder geoms runs on the cylinder build of the leap kernel and no other image does (%d cylinders)", who, m->cylinders); return JH_ERR_UNSUPPORTED; }
+  return JH_OK;
+}
+bool accepts(const jh_model* m) { return leap_refusal(m, nullptr) == JH_OK; }
+
+// k_leap_v5's arguments: the fused launch's record `a` (materialise mode: x0, N, H, the rest null / 0) and what stands beside it.  What a launch shape does not use stays null / 0.
+struct LeapArgs {
+  const jh_rollout_args& a; const float* gF; const int* gI; int* stats; int dshift, grid;  // grid: not an argument -- the workgroups of a problem on the static grid
+  int x0_batched = 0; const float* controls = nullptr; float *states = nullptr, *sensors = nullptr;  // materialise mode
+  float* ovf = nullptr; unsigned *head = nullptr, *pflags = nullptr; int slices = 0;
+  long long batch_blk = 0, batch_noise = 0, batch_image = 0;
+};
+
+// What every launcher starts with: the latency shift chosen from the `rollouts` of the whole launch and the static grid for a problem's N.
+LeapArgs leap_args(const jh_model* m, const jh_rollout_args& a, const float* gF, const int* gI, int rollouts) {
+  const int dshift = jh_latency_shift(rollouts, RPW), per_block = (RPW >> dshift) * WAVES_PER_BLOCK;
+  return {a, gF, gI, m->d_stats, dshift, (a.N + per_block - 1) / per_block};
+}
+
+// one row per rollout for the contacts above the LDS pool
+size_t ovf_bytes(size_t rows) { return NOVF > 0 ? rows * NOVF * POOL_F * sizeof(float) : 0; }
+
+template <bool MATERIALIZE, bool SELF, bool PERSIST = false, bool BATCH = false>
+void launch(const LeapArgs& k, dim3 grid, hipStream_t st) {
+  const jh_rollout_args& a = k.a;
+  hipLaunchKernelGGL((k_leap_v5<MATERIALIZE, WAVES_PER_BLOCK, SELF, PERSIST, BATCH>), grid, dim3(WAVE * WAVES_PER_BLOCK), 0, st, k.gF, k.gI, a.x0, k.x0_batched, a.nominal, a.noise, a.ldn,
+                     a.sigma, a.W, a.lohi, a.tp, a.N, a.n_offset, a.H, a.K, a.costs, a.knots_out, k.controls, k.states, k.sensors, k.stats, k.dshift, a.trace, k.ovf, k.head,
+                     k.batch_blk, k.batch_noise, k.batch_image, k.pflags, k.slices);
+}
+
+bool hand_contacts(const jh_model* m) { return m->self_collision && m->h_i[17] > 0; }  // the SELF instantiations: the hand's own contacts are on and the image has body pairs
+
 }  // namespace
 
 #ifndef JH_V5_NAME
@@ -1924,16 +1958,14 @@ extern "C" int JH_V5_NAME(jh_v5_wavestamp_buffer)(unsigned long long* buf, int g
   return JH_OK;
 }
 #endif
-int JH_V5_NAME(jh_engine5_rollout_cost)(const jh_model* m, const float* x0, const float* nominal, const float* noise, int ldn, const float* sigma, const float* W,
-                            const float* lohi, const float* tp, int N, int n_offset, int H, int K, float* costs, float* knots_out, float* trace, hipStream_t st) {
-  if (!model_is_leap(m)) { jh_set_error("rollout_cost: the cooperative engine kernel is instantiated for leap_cube only"); return JH_ERR_UNSUPPORTED; }
-  if ((m->cylinders > 0) != (JH_V5_CYL != 0)) { jh_set_error("rollout_cost: an image with cylinder geoms runs on the cylinder build of the leap kernel and no other image does (%d cylinders)", m->cylinders); return JH_ERR_UNSUPPORTED; }
-  const int dshift = jh_latency_shift(N, RPW); const int per_block = (RPW >> dshift) * WAVES_PER_BLOCK;
-  int grid = (N + per_block - 1) / per_block;
+static int rollout_cost(const jh_model* m, const jh_rollout_args& a, hipStream_t st) {
+  if (int rc = leap_refusal(m, "rollout_cost")) return rc;
+  const int N = a.N, H = a.H;
+  LeapArgs k = leap_args(m, a, m->d_f, m->d_i, N);
   // Launch shape (jh_model_set_rollout_schedule).  A launch with more groups of four rollouts than the GPU holds waves of this kernel (two workgroups per CU) runs one workgroup
   // per resident slot and lets the waves draw their groups from a queue; one that fits at once, and every latency-mode launch, keeps one group per wave of the grid.
-  bool persist = dshift == 0 && m->rollout_schedule != 1; int slots = 0;
-  if (persist) { slots = 2 * device_cus(m); persist = m->rollout_schedule == 2 || grid > slots; }
+  bool persist = k.dshift == 0 && m->rollout_schedule != 1; int slots = 0;
+  if (persist) { slots = 2 * device_cus(m); persist = m->rollout_schedule == 2 || k.grid > slots; }
   // Horizon slices (jh_model_set_rollout_slices): the queue's units are (group, slice) where the queue runs and the launch has at least two groups per wave slot -- dependent
   // units are then so many tickets apart that a slice's predecessor has as good as always parked its state in time -- or wherever the queue runs if a number is forced.
   const int ngroups = (N + RPW - 1) / RPW;
@@ -1947,74 +1979,60 @@ int JH_V5_NAME(jh_engine5_rollout_cost)(const jh_model* m, const float* x0, cons
   // slices (one per unit, padded to 16 bytes) -- both zeroed in front of every launch that uses them --, the parked rows of the slices, then one row per rollout for the
   // contacts above the LDS pool and, under slices, one more per rollout row of every wave slot for a pass that recomputes a missed hand-off.  A sliced request the pool
   // refuses is asked again for whole groups (the parked rows are the bulk of it) before the launch gives the queue up.
-  int qgrid = grid;  // the queue's grid
+  int qgrid = k.grid;  // the queue's grid
   if (persist) { if (qgrid > slots) qgrid = slots; if (m->rollout_max_workgroups > 0 && qgrid > m->rollout_max_workgroups) qgrid = m->rollout_max_workgroups; }  // (the cap: a test hook, few waves and many tickets)
-  size_t flag_words = 0, queue_bytes = 0, ovf_bytes = 0;
-  float* scratch = nullptr; float* ovf = nullptr; unsigned* head = nullptr;
+  size_t flag_words = 0, queue_bytes = 0, ovf_b = 0;
+  float* scratch = nullptr; unsigned* head = nullptr;
   for (;;) {
     flag_words = slices > 1 ? (((size_t)slices * ngroups + 3) & ~(size_t)3) : 0;
     const size_t park_floats = slices > 1 ? (size_t)(slices - 1) * ngroups * PARK_F : 0, own_rows = slices > 1 ? (size_t)qgrid * WAVES_PER_BLOCK * RPW : 0;
     queue_bytes = persist ? 16 + (flag_words + park_floats) * sizeof(float) : 0;
-    ovf_bytes = NOVF > 0 ? ((size_t)N + own_rows) * NOVF * POOL_F * sizeof(float) : 0;
-    if (ovf_bytes > 0 || persist) scratch = jh_launch_scratch(m, ovf_bytes + queue_bytes, st, ovf_bytes > 0 && slices == 1);  // (nullptr: the LDS capacity alone, drops and the fallback counted -- and the static shape)
+    ovf_b = ovf_bytes((size_t)N + own_rows);
+    if (ovf_b > 0 || persist) scratch = jh_launch_scratch(m, ovf_b + queue_bytes, st, ovf_b > 0 && slices == 1);  // (nullptr: the LDS capacity alone, drops and the fallback counted -- and the static shape)
     if (scratch || slices == 1) break;
     slices = 1;
   }
   if (scratch && persist && hipMemsetAsync(scratch, 0, 16 + flag_words * sizeof(unsigned), st) != hipSuccess) { (void)hipGetLastError(); persist = false; }
   if (!scratch) persist = false;
-  if (persist) { head = (unsigned*)scratch; grid = qgrid; } else slices = 1;
-  if (scratch && ovf_bytes > 0) ovf = scratch + (head ? queue_bytes / sizeof(float) : 0);
+  if (persist) { head = (unsigned*)scratch; k.grid = qgrid; } else slices = 1;
+  if (scratch && ovf_b > 0) k.ovf = scratch + (head ? queue_bytes / sizeof(float) : 0);
   __atomic_store_n(&m->last_rollout_slices, persist ? slices : 0, __ATOMIC_RELAXED);
-  const int slices_arg = slices | ((m->rollout_slice_flags & 1) << 8);
-#define JH_V5_LAUNCH_COST(SELF_, PERSIST_)                                                                                                                                        \
-  hipLaunchKernelGGL((k_leap_v5<false, WAVES_PER_BLOCK, SELF_, PERSIST_>), dim3(grid), dim3(WAVE * WAVES_PER_BLOCK), 0, st, m->d_f, m->d_i, x0, 0, nominal, noise, ldn, sigma, W, \
-                     lohi, tp, N, n_offset, H, K, costs, knots_out, (const float*)nullptr, (float*)nullptr, (float*)nullptr, m->d_stats, dshift, trace, ovf, head, 0ll, 0ll, 0ll, head ? head + 4 : (unsigned*)nullptr, slices_arg)
-  if (m->self_collision && m->h_i[17] > 0) { if (persist) JH_V5_LAUNCH_COST(true, true); else JH_V5_LAUNCH_COST(true, false); }
-  else { if (persist) JH_V5_LAUNCH_COST(false, true); else JH_V5_LAUNCH_COST(false, false); }
-#undef JH_V5_LAUNCH_COST
+  k.head = head; k.pflags = head ? head + 4 : nullptr; k.slices = slices | ((m->rollout_slice_flags & 1) << 8);
+  if (hand_contacts(m)) { if (persist) launch<false, true, true>(k, dim3(k.grid), st); else launch<false, true, false>(k, dim3(k.grid), st); }
+  else { if (persist) launch<false, false, true>(k, dim3(k.grid), st); else launch<false, false, false>(k, dim3(k.grid), st); }
   return jh_launch_done(scratch, st);
 }
 
-int JH_V5_NAME(jh_engine5_materialize)(const jh_model* m, const float* x0, int x0_batched, const float* controls, int N, int H, float* states, float* sensors,
-                           hipStream_t st) {
-  if (!model_is_leap(m)) { jh_set_error("rollout_materialize: the cooperative engine kernel is instantiated for leap_cube only"); return JH_ERR_UNSUPPORTED; }
-  if ((m->cylinders > 0) != (JH_V5_CYL != 0)) { jh_set_error("rollout_materialize: an image with cylinder geoms runs on the cylinder build of the leap kernel and no other image does (%d cylinders)", m->cylinders); return JH_ERR_UNSUPPORTED; }
-  const int dshift = jh_latency_shift(N, RPW); const int per_block = (RPW >> dshift) * WAVES_PER_BLOCK;
-  int grid = (N + per_block - 1) / per_block;
-  float* ovf = nullptr;  // one row per rollout for the contacts above the LDS pool: stream-ordered allocation, no state on the model handle
-  if (NOVF > 0) ovf = jh_launch_scratch(m, (size_t)N * NOVF * POOL_F * sizeof(float), st);  // (nullptr: the LDS capacity alone, drops and the fallback counted)
-  if (m->self_collision && m->h_i[17] > 0)
-    hipLaunchKernelGGL((k_leap_v5<true, WAVES_PER_BLOCK, true>), dim3(grid), dim3(WAVE * WAVES_PER_BLOCK), 0, st, m->d_f, m->d_i, x0, x0_batched, (const float*)nullptr, (const float*)nullptr, 0,
-                       (const float*)nullptr, (const float*)nullptr, (const float*)nullptr, (const float*)nullptr, N, 0, H, 0, (float*)nullptr, (float*)nullptr,
-                       controls, states, sensors, m->d_stats, dshift, (float*)nullptr, ovf, (unsigned*)nullptr, 0ll, 0ll, 0ll, (unsigned*)nullptr, 0);
-  else
-    hipLaunchKernelGGL((k_leap_v5<true, WAVES_PER_BLOCK, false>), dim3(grid), dim3(WAVE * WAVES_PER_BLOCK), 0, st, m->d_f, m->d_i, x0, x0_batched, (const float*)nullptr, (const float*)nullptr, 0,
-                       (const float*)nullptr, (const float*)nullptr, (const float*)nullptr, (const float*)nullptr, N, 0, H, 0, (float*)nullptr, (float*)nullptr,
-                       controls, states, sensors, m->d_stats, dshift, (float*)nullptr, ovf, (unsigned*)nullptr, 0ll, 0ll, 0ll, (unsigned*)nullptr, 0);
-  return jh_launch_done(ovf, st);
+static int materialize(const jh_model* m, const float* x0, int x0_batched, const float* controls, int N, int H, float* states, float* sensors, hipStream_t st) {
+  if (int rc = leap_refusal(m, "rollout_materialize")) return rc;
+  jh_rollout_args a = {};
+  a.x0 = x0; a.N = N; a.H = H;
+  LeapArgs k = leap_args(m, a, m->d_f, m->d_i, N);
+  k.x0_batched = x0_batched; k.controls = controls; k.states = states; k.sensors = sensors;
+  if (const size_t b = ovf_bytes(N)) k.ovf = jh_launch_scratch(m, b, st);  // stream-ordered allocation, no state on the model handle (nullptr: the LDS capacity alone, drops and the fallback counted)
+  if (hand_contacts(m)) launch<true, true>(k, dim3(k.grid), st);
+  else launch<true, false>(k, dim3(k.grid), st);
+  return jh_launch_done(k.ovf, st);
 }
 
 // (Defined last in the file: the batched instantiations are emitted behind every other kernel and shift none of them in the code object.)
-// B problems in one launch (jh_plan_step_batch): the static grid with the problem in its second dimension.  x0 ... tp are problem 0's; `blk_stride` / `noise_stride` floats
+// B problems in one launch (jh_plan_step_batch): the static grid with the problem in its second dimension.  The record is problem 0's; `blk_stride` / `noise_stride` floats
 // lead to the next problem's, and `image_stride` floats from `images`, problem 0's float section, to the next problem's (m->d_f and 0 where the problems share the model;
-// a model set's members passed jh_engine5_accepts one by one when the set was made).  The latency shift is chosen from B * N, the rollouts of the launch (the bits do
+// a model set's members passed the row's `accepts` one by one when the set was made).  The latency shift is chosen from B * N, the rollouts of the launch (the bits do
 // not depend on it), and there is no queue.
-int JH_V5_NAME(jh_engine5_rollout_cost_batch)(const jh_model* m, const float* images, long long image_stride, const int* ints, int B, const float* x0, const float* nominal, const float* sigma, const float* lohi, const float* tp, long long blk_stride,
-                                  const float* noise, int ldn, long long noise_stride, const float* W, int N, int H, int K, float* costs, float* trace, hipStream_t st) {
-  if (!model_is_leap(m)) { jh_set_error("plan_step_batch: the cooperative engine kernel is instantiated for leap_cube only"); return JH_ERR_UNSUPPORTED; }
-  if ((m->cylinders > 0) != (JH_V5_CYL != 0)) { jh_set_error("plan_step_batch: an image with cylinder geoms runs on the cylinder build of the leap kernel and no other image does (%d cylinders)", m->cylinders); return JH_ERR_UNSUPPORTED; }
-  JH_REQUIRE((long long)B * N <= 0x7fffffffll, "plan_step_batch: B * N = %lld rollouts exceed one launch", (long long)B * N);
-  const int dshift = jh_latency_shift(B * N, RPW); const int per_block = (RPW >> dshift) * WAVES_PER_BLOCK;
-  const int grid = (N + per_block - 1) / per_block;
-  const size_t ovf_bytes = NOVF > 0 ? (size_t)B * N * NOVF * POOL_F * sizeof(float) : 0;  // one row per rollout of every problem for the contacts above the LDS pool
-  float* ovf = ovf_bytes > 0 ? jh_launch_scratch(m, ovf_bytes, st) : nullptr;  // (nullptr: the LDS capacity alone, drops and the fallback counted)
-#define JH_V5_LAUNCH_BATCH(SELF_)                                                                                                                                                  \
-  hipLaunchKernelGGL((k_leap_v5<false, WAVES_PER_BLOCK, SELF_, false, true>), dim3(grid, B), dim3(WAVE * WAVES_PER_BLOCK), 0, st, images, ints, x0, 0, nominal, noise, ldn, sigma, W, \
-                     lohi, tp, N, 0, H, K, costs, (float*)nullptr, (const float*)nullptr, (float*)nullptr, (float*)nullptr, m->d_stats, dshift, trace, ovf, (unsigned*)nullptr, blk_stride, noise_stride, image_stride, (unsigned*)nullptr, 0)
-  if (m->self_collision && m->h_i[17] > 0) JH_V5_LAUNCH_BATCH(true); else JH_V5_LAUNCH_BATCH(false);
-#undef JH_V5_LAUNCH_BATCH
-  return jh_launch_done(ovf, st);
+static int rollout_cost_batch(const jh_model* m, const jh_rollout_args& a, const jh_rollout_batch& s, hipStream_t st) {
+  if (int rc = leap_refusal(m, "plan_step_batch")) return rc;
+  JH_REQUIRE((long long)s.B * a.N <= 0x7fffffffll, "plan_step_batch: B * N = %lld rollouts exceed one launch", (long long)s.B * a.N);
+  LeapArgs k = leap_args(m, a, s.images, s.ints, s.B * a.N);
+  k.batch_blk = s.blk_stride; k.batch_noise = s.noise_stride; k.batch_image = s.image_stride;
+  if (const size_t b = ovf_bytes((size_t)s.B * a.N)) k.ovf = jh_launch_scratch(m, b, st);  // (every problem's rows; nullptr: the LDS capacity alone, drops and the fallback counted)
+  if (hand_contacts(m)) launch<false, true, false, true>(k, dim3(k.grid, s.B), st);
+  else launch<false, false, false, true>(k, dim3(k.grid, s.B), st);
+  return jh_launch_done(k.ovf, st);
 }
 
-// What the launchers above ask of a model before they run it, for a caller that must know in advance (jh_model_set_create: every member of a set, on its own floats).
-bool JH_V5_NAME(jh_engine5_accepts)(const jh_model* m) { return model_is_leap(m) && (m->cylinders > 0) == (JH_V5_CYL != 0); }
+// This build's row of the table (jh_internal.h); `accepts` is what the launchers above ask of a model, for a caller that must know in advance (jh_model_set_create: every
+// member of a set, on its own floats).  Host pass only: a const object with a constant initialiser would be emitted into the code object as well.
+#ifndef __HIP_DEVICE_COMPILE__
+const jh_engine_build JH_V5_NAME(jh_engine5_build) = {JH_V5_CYL ? "leap, cylinders" : NCAP > 48 ? "leap, 64 contacts" : "leap, 48 contacts", accepts, rollout_cost, rollout_cost_batch, materialize, NCAP};
+#endif

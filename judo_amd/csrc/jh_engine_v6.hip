@@ -763,7 +763,7 @@ __global__ __launch_bounds__(WAVE) __attribute__((amdgpu_waves_per_eu(WPE, WPE))
         if (hit && pos < MAXHIT) S.hits[pos] = (unsigned short)p;
         nh += __popc(m16);
       }
-      if (nh > MAXHIT) { if (l == 0 && live && stats) atomicAdd(stats, nh - MAXHIT); nh = MAXHIT; }  // candidate pairs beyond the list: counted with the dropped contacts
+      if (nh > MAXHIT) { if (l == 0 && live && stats) atomicAdd(stats + JH_STAT_DROPS, nh - MAXHIT); nh = MAXHIT; }  // candidate pairs beyond the list: counted with the dropped contacts
       __syncthreads();
 #ifdef JH_V6_PHASE_BROAD
       PH6(6)  // (diagnostic: the broad phase lands in the 'tail' slot)
@@ -1249,7 +1249,7 @@ __global__ __launch_bounds__(WAVE) __attribute__((amdgpu_waves_per_eu(WPE, WPE))
   if (stats && lane == 0) for (int k = 0; k < 10; k++) atomicAdd((unsigned long long*)(stats + 4) + k, (unsigned long long)ph_acc[k]);
 #endif
 #endif
-  if (stats && live && l == 0) { if (n_maxed) atomicAdd(stats + 1, n_maxed); atomicAdd(stats + 2, n_iters); atomicAdd(stats + 3, H); }
+  if (stats && live && l == 0) { if (n_maxed) atomicAdd(stats + JH_STAT_ITER_CAP, n_maxed); atomicAdd(stats + JH_STAT_ITERS, n_iters); atomicAdd(stats + JH_STAT_STEPS, H); }
 }
 
 }  // namespace
@@ -1306,32 +1306,36 @@ bool JH_V6_NAME(jh_model_is_fr3)(const jh_model* m) {
   return true;
 }
 
-int JH_V6_NAME(jh_engine6_rollout_cost)(const jh_model* m, const float* x0, const float* nominal, const float* noise, int ldn, const float* sigma, const float* W,
-                            const float* lohi, const float* tp, int phase, int N, int n_offset, int H, int K, float* costs, float* knots_out, float* trace, hipStream_t st) {
-  if (!JH_V6_NAME(jh_model_is_fr3)(m)) { jh_set_error(JH_V6_SELF ? "rollout_cost: the self-collision build of the cooperative arm kernel is instantiated for fr3_pick with its arm pairs only" : "rollout_cost: the cooperative arm kernel (matrix-free generation) is instantiated for fr3_pick only; an image with pairs between arm bodies runs on its self-collision build"); return JH_ERR_UNSUPPORTED; }
-  JH_REQUIRE(K <= 8, "rollout_cost: the cooperative arm kernel keeps at most 8 knots per actuator in registers (K=%d)", K);
-  const int dshift = jh_latency_shift(N, RPW), per_wave = RPW >> dshift;
-  int grid = (N + per_wave - 1) / per_wave;
+// Both entries: the build's acceptance test under the caller's name (`note`: what the fused mode's message adds), the launch shape, the overflow rows, the launch.  `a`: the fused
+// launch's record (materialise mode: x0, N, H, the rest null / 0).
+template <bool MATERIALIZE>
+static int launch(const jh_model* m, const char* who, const char* note, const jh_rollout_args& a, int x0_batched, const float* controls, float* states, float* sensors, hipStream_t st) {
+  if (!JH_V6_NAME(jh_model_is_fr3)(m)) {
+    if (JH_V6_SELF) jh_set_error("%s: the self-collision build of the cooperative arm kernel is instantiated for fr3_pick with its arm pairs only", who);
+    else jh_set_error("%s: the cooperative arm kernel%s is instantiated for fr3_pick only; an image with pairs between arm bodies runs on its self-collision build", who, note);
+    return JH_ERR_UNSUPPORTED;
+  }
+  JH_REQUIRE(a.K <= 8, "rollout_cost: the cooperative arm kernel keeps at most 8 knots per actuator in registers (K=%d)", a.K);  // (materialise mode has none)
+  const int dshift = jh_latency_shift(a.N, RPW), per_wave = RPW >> dshift, grid = (a.N + per_wave - 1) / per_wave;
   // one overflow row per rollout for the general contacts above the LDS pool: stream-ordered allocation (the pool hands the same block back launch after launch),
   // no state on the model handle
-  float* ovf = nullptr;
-  ovf = jh_launch_scratch(m, (size_t)N * NOVF * RAW_F * sizeof(float), st);  // (nullptr: the LDS capacity alone, drops and the fallback counted)
-  hipLaunchKernelGGL(k_fr3_v6<false>, dim3(grid), dim3(WAVE), 0, st, m->d_f, m->d_i, x0, 0, nominal, noise, ldn, sigma, W, lohi, tp, phase, N, n_offset, H, K,
-                     costs, knots_out, (const float*)nullptr, (float*)nullptr, (float*)nullptr, m->d_stats, dshift, trace, ovf);
+  float* ovf = jh_launch_scratch(m, (size_t)a.N * NOVF * RAW_F * sizeof(float), st);  // (nullptr: the LDS capacity alone, drops and the fallback counted)
+  hipLaunchKernelGGL(k_fr3_v6<MATERIALIZE>, dim3(grid), dim3(WAVE), 0, st, m->d_f, m->d_i, a.x0, x0_batched, a.nominal, a.noise, a.ldn, a.sigma, a.W, a.lohi, a.tp, a.phase, a.N, a.n_offset,
+                     a.H, a.K, a.costs, a.knots_out, controls, states, sensors, m->d_stats, dshift, a.trace, ovf);
   return jh_launch_done(ovf, st);
 }
 
+static int rollout_cost(const jh_model* m, const jh_rollout_args& a, hipStream_t st) { return launch<false>(m, "rollout_cost", " (matrix-free generation)", a, 0, nullptr, nullptr, nullptr, st); }
+
 int JH_V6_NAME(jh_engine6_materialize)(const jh_model* m, const float* x0, int x0_batched, const float* controls, int N, int H, float* states, float* sensors,
                            hipStream_t st) {
-  if (!JH_V6_NAME(jh_model_is_fr3)(m)) { jh_set_error(JH_V6_SELF ? "rollout_materialize: the self-collision build of the cooperative arm kernel is instantiated for fr3_pick with its arm pairs only" : "rollout_materialize: the cooperative arm kernel is instantiated for fr3_pick only; an image with pairs between arm bodies runs on its self-collision build"); return JH_ERR_UNSUPPORTED; }
-  const int dshift = jh_latency_shift(N, RPW), per_wave = RPW >> dshift;
-  int grid = (N + per_wave - 1) / per_wave;
-  // one overflow row per rollout for the general contacts above the LDS pool: stream-ordered allocation (the pool hands the same block back launch after launch),
-  // no state on the model handle
-  float* ovf = nullptr;
-  ovf = jh_launch_scratch(m, (size_t)N * NOVF * RAW_F * sizeof(float), st);  // (nullptr: the LDS capacity alone, drops and the fallback counted)
-  hipLaunchKernelGGL(k_fr3_v6<true>, dim3(grid), dim3(WAVE), 0, st, m->d_f, m->d_i, x0, x0_batched, (const float*)nullptr, (const float*)nullptr, 0,
-                     (const float*)nullptr, (const float*)nullptr, (const float*)nullptr, (const float*)nullptr, 0, N, 0, H, 0, (float*)nullptr,
-                     (float*)nullptr, controls, states, sensors, m->d_stats, dshift, (float*)nullptr, ovf);
-  return jh_launch_done(ovf, st);
+  jh_rollout_args a = {};
+  a.x0 = x0; a.N = N; a.H = H;
+  return launch<true>(m, "rollout_materialize", "", a, x0_batched, controls, states, sensors, st);
 }
+
+// This build's row of the table (jh_internal.h); the contact capacity is the LDS pool plus the overflow row.  Host pass only: a const object with a constant initialiser
+// would be emitted into the code object as well.
+#ifndef __HIP_DEVICE_COMPILE__
+const jh_engine_build JH_V6_NAME(jh_engine6_build) = {JH_V6_SELF ? "fr3, self-collision" : "fr3", JH_V6_NAME(jh_model_is_fr3), rollout_cost, nullptr, JH_V6_NAME(jh_engine6_materialize), NCP + NOVF};
+#endif

@@ -40,7 +40,7 @@ struct jh_model {
   int plan_step_launches;  // closed-form models' plan step: 0 = one launch where it fits (the default), 1 = always one launch, 2 = always two (jh_model_set_plan_step_launches)
   mutable int one_launch_steps = 0;  // plan steps that ran as one launch (jh_model_stats out[7]); __atomic builtins, as ovf_fallbacks
   mutable int ovf_fallbacks = 0;  // launches that ran without their overflow rows (jh_launch_scratch); updated with __atomic builtins: a planner thread may launch while another polls jh_model_stats
-  int* d_stats;  // JH_NSTATS diagnostic counters: [0..3] contact-cap overflows, Newton iteration-cap hits, Newton iterations, steps; [20..21] wave-level iterations, steps; the rest: diagnostic builds
+  int* d_stats;  // JH_NSTATS diagnostic counters: the JH_STAT_* words below; the rest: diagnostic builds
   std::vector<float> h_f;
   std::vector<int> h_i;
 };
@@ -102,9 +102,41 @@ enum {
 };
 
 // ---- launchers implemented per translation unit ------------------------------------------------------------
-int jh_simple_rollout_cost(const jh_model* m, const float* x0, const float* nominal, const float* noise, int ldn, const float* sigma,
-                           const float* W, const float* lohi, const float* tp, int N, int n_offset, int H, int K, float* costs,
-                           float* knots_out, float* trace, hipStream_t st);
+// One fused launch (rollouts + cost): what jh_rollout_cost_traced receives after the model.  Filled once by the entry point (or by the plan step, from its packed block's
+// offsets) and passed by reference to the launcher.
+struct jh_rollout_args {
+  const float *x0, *nominal, *noise; int ldn;
+  const float *sigma, *W, *lohi, *tp; int phase, N, n_offset, H, K;
+  float *costs, *knots_out, *trace;
+};
+// What the leap kernel's launch for B problems (jh_plan_step_batch) takes on top: the record is problem 0's, `blk_stride` / `noise_stride` floats lead to the next problem's;
+// `images`: problem 0's float section, `image_stride` floats to the next problem's (m->d_f and 0: one image for all); `ints`: the int section on the device (m->d_i, or a
+// model set's copy without the hand's pair tables)
+struct jh_rollout_batch {
+  const float* images; long long image_stride; const int* ints;
+  int B; long long blk_stride, noise_stride;
+};
+
+// One build of an articulated product kernel: each translation unit that instantiates k_leap_v5 or k_fr3_v6 defines its row, and jh_api.hip's engine_build() maps a model
+// to the row that runs it.  A new build is a new row and a line of that function.
+struct jh_engine_build {
+  const char* name;                       // for messages
+  bool (*accepts)(const jh_model* m);     // the launchers' own acceptance test, on the model's own image
+  int (*rollout_cost)(const jh_model* m, const jh_rollout_args& a, hipStream_t st);
+  int (*rollout_cost_batch)(const jh_model* m, const jh_rollout_args& a, const jh_rollout_batch& s, hipStream_t st);  // null: the build has no batched launch (fr3)
+  int (*materialize)(const jh_model* m, const float* x0, int x0_batched, const float* controls, int N, int H, float* states, float* sensors, hipStream_t st);
+  int contact_capacity;                   // contacts a rollout can hold (jh_model_limits out[3]), from the build's own constants
+};
+// (hidden: the rows are the library's own, not part of its boundary)
+extern __attribute__((visibility("hidden"))) const jh_engine_build jh_engine5_build, jh_engine5_build_cap64, jh_engine5_build_cyl;  // jh_engine_v5.hip: the leap kernel for 48 and 64 contacts, and with cylinders
+extern __attribute__((visibility("hidden"))) const jh_engine_build jh_engine6_build, jh_engine6_build_self;  // jh_engine_v6.hip: the fr3 kernel, and with the arm's own pairs (jh_model::arm_pairs > 0)
+
+// The words of jh_model::d_stats that every product build writes and the host reads (jh_model_stats, jh_model_recomputed_units): contact-cap overflows, Newton iteration-cap
+// hits, Newton iterations, steps; wave-level iterations, steps; leap queue units whose hand-off was missed and which recomputed their group up to their slice.  The rest
+// belongs to diagnostic builds.
+enum { JH_STAT_DROPS = 0, JH_STAT_ITER_CAP, JH_STAT_ITERS, JH_STAT_STEPS, JH_STAT_WAVE_ITERS = 20, JH_STAT_WAVE_STEPS, JH_STAT_RECOMPUTED = 56 };
+
+int jh_simple_rollout_cost(const jh_model* m, const jh_rollout_args& a, hipStream_t st);
 // Latency mode of the cooperative kernels (rows of `lanes` lanes, `rpw` rows per wave): a launch too small to give every SIMD a wave lets 1 << shift rows of a wave
 // compute the same rollout -- the copies run the same arithmetic, only the first writes -- so that a wave no longer waits for the slowest of `rpw` different Newton
 // solves in every step.  Returns the largest shift (<= log2 rpw) that still leaves every wave of the launch a SIMD of its own; JUDO_AMD_LATENCY_SHIFT=0..2 overrides.
@@ -130,53 +162,12 @@ int jh_engine2_rollout_cost(const jh_model* m, const float* x0, const float* nom
 int jh_engine2_materialize(const jh_model* m, const float* x0, int x0_batched, const float* controls, int N, int H, float* states, float* sensors,
                            hipStream_t st);
 
-// jh_engine_v5.hip: the leap_cube cooperative kernel on a register diet (several waves per SIMD)
-int jh_engine5_rollout_cost(const jh_model* m, const float* x0, const float* nominal, const float* noise, int ldn, const float* sigma, const float* W,
-                            const float* lohi, const float* tp, int N, int n_offset, int H, int K, float* costs, float* knots_out, float* trace, hipStream_t st);
-int jh_engine5_materialize(const jh_model* m, const float* x0, int x0_batched, const float* controls, int N, int H, float* states, float* sensors,
-                           hipStream_t st);
-int jh_engine5_rollout_cost_cap64(const jh_model* m, const float* x0, const float* nominal, const float* noise, int ldn, const float* sigma, const float* W,
-                                  const float* lohi, const float* tp, int N, int n_offset, int H, int K, float* costs, float* knots_out, float* trace, hipStream_t st);
-int jh_engine5_materialize_cap64(const jh_model* m, const float* x0, int x0_batched, const float* controls, int N, int H, float* states, float* sensors,
-                                 hipStream_t st);
-int jh_engine5_rollout_cost_cyl(const jh_model* m, const float* x0, const float* nominal, const float* noise, int ldn, const float* sigma, const float* W,
-                                const float* lohi, const float* tp, int N, int n_offset, int H, int K, float* costs, float* knots_out, float* trace, hipStream_t st);
-int jh_engine5_materialize_cyl(const jh_model* m, const float* x0, int x0_batched, const float* controls, int N, int H, float* states, float* sensors,
-                               hipStream_t st);
-
-// the leap kernel for B problems in one launch (jh_plan_step_batch): x0 ... tp of problem 0, `blk_stride` / `noise_stride` floats to the next problem's; `images`: problem
-// 0's float section, `image_stride` floats to the next problem's (m->d_f and 0: one image for all); `ints`: the int section on the device (m->d_i, or a model set's
-// copy without the hand's pair tables)
-int jh_engine5_rollout_cost_batch(const jh_model* m, const float* images, long long image_stride, const int* ints, int B, const float* x0, const float* nominal, const float* sigma, const float* lohi, const float* tp, long long blk_stride,
-                                  const float* noise, int ldn, long long noise_stride, const float* W, int N, int H, int K, float* costs, float* trace, hipStream_t st);
-int jh_engine5_rollout_cost_batch_cap64(const jh_model* m, const float* images, long long image_stride, const int* ints, int B, const float* x0, const float* nominal, const float* sigma, const float* lohi, const float* tp, long long blk_stride,
-                                        const float* noise, int ldn, long long noise_stride, const float* W, int N, int H, int K, float* costs, float* trace, hipStream_t st);
-int jh_engine5_rollout_cost_batch_cyl(const jh_model* m, const float* images, long long image_stride, const int* ints, int B, const float* x0, const float* nominal, const float* sigma, const float* lohi, const float* tp, long long blk_stride,
-                                      const float* noise, int ldn, long long noise_stride, const float* W, int N, int H, int K, float* costs, float* trace, hipStream_t st);
-
-// does the build's launcher accept this model (its own acceptance test, on the model's own image)?
-bool jh_engine5_accepts(const jh_model* m);
-bool jh_engine5_accepts_cap64(const jh_model* m);
-bool jh_engine5_accepts_cyl(const jh_model* m);
-
 // jh_engine_v3.hip: cooperative kernel for fr3_pick (serial arm with a two-finger fork + free box, pyramidal cones)
-bool jh_model_is_fr3(const jh_model* m);
+bool jh_model_is_fr3(const jh_model* m);  // (defined by jh_engine_v6.hip: the default build's acceptance test, which the cross-check kernel shares)
 int jh_engine3_rollout_cost(const jh_model* m, const float* x0, const float* nominal, const float* noise, int ldn, const float* sigma, const float* W,
                             const float* lohi, const float* tp, int phase, int N, int n_offset, int H, int K, float* costs, float* knots_out, hipStream_t st);
 int jh_engine3_materialize(const jh_model* m, const float* x0, int x0_batched, const float* controls, int N, int H, float* states, float* sensors,
                            hipStream_t st);
-
-// jh_engine_v6.hip: fr3_pick, matrix-free contact Jacobian (kernel generation 3 of the fr3 model)
-int jh_engine6_rollout_cost(const jh_model* m, const float* x0, const float* nominal, const float* noise, int ldn, const float* sigma, const float* W,
-                            const float* lohi, const float* tp, int phase, int N, int n_offset, int H, int K, float* costs, float* knots_out, float* trace, hipStream_t st);
-int jh_engine6_materialize(const jh_model* m, const float* x0, int x0_batched, const float* controls, int N, int H, float* states, float* sensors,
-                           hipStream_t st);
-// jh_engine_v6_self.hip: the same kernel with the arm's own pairs (an image with jh_model::arm_pairs > 0, which jh_model_is_fr3 refuses)
-bool jh_model_is_fr3_self(const jh_model* m);
-int jh_engine6_rollout_cost_self(const jh_model* m, const float* x0, const float* nominal, const float* noise, int ldn, const float* sigma, const float* W,
-                                 const float* lohi, const float* tp, int phase, int N, int n_offset, int H, int K, float* costs, float* knots_out, float* trace, hipStream_t st);
-int jh_engine6_materialize_self(const jh_model* m, const float* x0, int x0_batched, const float* controls, int N, int H, float* states, float* sensors,
-                                hipStream_t st);
 
 // ---- device helpers ------------------------------------------------------------------------------------------
 // MuJoCo's impedance curve d(x) (solimp = dmin, dmax, width, midpoint, power), x = |pos - margin| / width.

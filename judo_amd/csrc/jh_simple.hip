@@ -365,13 +365,12 @@ __global__ __launch_bounds__(kBlock) void k_reward(const float* __restrict__ sta
 }
 
 template <class T>
-int launch_cost(const jh_model* m, const float* x0, const float* nominal, const float* noise, int ldn, const float* sigma, const float* W,
-                const float* lohi, const float* tp, int N, int n_offset, int H, int K, float* costs, float* knots_out, float* trace, hipStream_t st) {
-  size_t lds = sizeof(float) * ((size_t)H * K + (size_t)K * T::NU * kBlock + T::NP + T::NTP + T::NX);
+int launch_cost(const jh_model* m, const jh_rollout_args& a, hipStream_t st) {
+  size_t lds = sizeof(float) * ((size_t)a.H * a.K + (size_t)a.K * T::NU * kBlock + T::NP + T::NTP + T::NX);
   JH_REQUIRE(lds <= 64 * 1024, "rollout_cost: H*K too large for the LDS staging (%zu bytes)", lds);
-  int grid = (N + kBlock - 1) / kBlock;
-  hipLaunchKernelGGL(k_rollout_cost<T>, dim3(grid), dim3(kBlock), lds, st, m->d_f, x0, nominal, noise, ldn, sigma, W, lohi, tp, N, n_offset, H, K,
-                     costs, knots_out, trace);
+  int grid = (a.N + kBlock - 1) / kBlock;
+  hipLaunchKernelGGL(k_rollout_cost<T>, dim3(grid), dim3(kBlock), lds, st, m->d_f, a.x0, a.nominal, a.noise, a.ldn, a.sigma, a.W, a.lohi, a.tp, a.N, a.n_offset, a.H, a.K,
+                     a.costs, a.knots_out, a.trace);
   JH_HIP(hipGetLastError());
   return JH_OK;
 }
@@ -439,11 +438,9 @@ template <class T>
 static int max_knots(int H) { return (int)((16 * 1024 - T::NP - T::NTP - T::NX) / ((size_t)H + (size_t)T::NU * kBlock)); }
 int jh_simple_max_knots(const jh_model* m, int H) { return m->kind == JH_TASK_CARTPOLE ? max_knots<Cartpole>(H) : max_knots<CylinderPush>(H); }
 
-int jh_simple_rollout_cost(const jh_model* m, const float* x0, const float* nominal, const float* noise, int ldn, const float* sigma,
-                           const float* W, const float* lohi, const float* tp, int N, int n_offset, int H, int K, float* costs,
-                           float* knots_out, float* trace, hipStream_t st) {
-  if (m->kind == JH_TASK_CARTPOLE) return launch_cost<Cartpole>(m, x0, nominal, noise, ldn, sigma, W, lohi, tp, N, n_offset, H, K, costs, knots_out, trace, st);
-  return launch_cost<CylinderPush>(m, x0, nominal, noise, ldn, sigma, W, lohi, tp, N, n_offset, H, K, costs, knots_out, trace, st);
+int jh_simple_rollout_cost(const jh_model* m, const jh_rollout_args& a, hipStream_t st) {
+  if (m->kind == JH_TASK_CARTPOLE) return launch_cost<Cartpole>(m, a, st);
+  return launch_cost<CylinderPush>(m, a, st);
 }
 
 int jh_simple_materialize(const jh_model* m, const float* x0, int x0_batched, const float* controls, int N, int H, float* states,

@@ -22,7 +22,7 @@ N, H = 32, 64
 
 
 def leap_waves(B: int, n: int, cus: int) -> tuple[int, int, int]:
-    """(latency shift, waves of the batched leap launch, waves the GPU holds at once) -- the launcher's rule (jh_latency_shift, jh_engine5_rollout_cost_batch)."""
+    """(latency shift, waves of the batched leap launch, waves the GPU holds at once) -- the launcher's rule (jh_latency_shift, rollout_cost_batch of jh_engine_v5.hip)."""
     shift = next((s for s in (2, 1) if ((B * n) << s) <= cus * 4 * 4), 0)
     per_block = (4 >> shift) * 4
     return shift, B * ((n + per_block - 1) // per_block) * 4, 8 * cus
