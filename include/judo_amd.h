@@ -46,6 +46,7 @@ enum jh_spline_kind { JH_SPLINE_ZERO = 0, JH_SPLINE_LINEAR = 1, JH_SPLINE_CUBIC 
 #define JH_MAX_TASK_PARAMS 32
 #define JH_MAX_KNOT_DIM 512 /* K * nu */
 #define JH_MAX_ELITES 32
+#define JH_MAX_ENSEMBLE 32 /* members of a model set that jh_plan_step_ensemble plans against */
 
 const char* jh_last_error(void);
 int jh_version(void);
@@ -321,6 +322,29 @@ int jh_plan_step_batch_models(const jh_model_set* set, void* blk_dev, const void
                               const float* noise, int ldn, size_t noise_stride_floats, const float* W, int N, int H, int K, float* costs, float* trace, int mode, float lambda, int k,
                               int tie_high, int E, int row_floats, int colmajor, float* scratch, float* out, size_t out_stride_floats, void* out_host_mark, void* const* timing,
                               void* stream);
+/* ONE plan step against an ensemble of plants (sim-to-real: one controller with one nominal spline over M perturbed models; the reference has no counterpart).  The N
+ * candidates of one packed block and one noise slice are rolled out on every member of a model set, M <= JH_MAX_ENSEMBLE, and a candidate's cost is a risk measure over
+ * its M member costs c[0..M-1], fixed here so that it can be tested bit for bit: with `worst` = j, 1 <= j <= M,
+ *   take the j largest values as a multiset (equal values are interchangeable), add them in fp32 in DESCENDING order starting from the largest (acc = v0; acc += v1; ...),
+ *   then cost = acc / (float)j, a correctly rounded fp32 division.
+ * j = 1 is the exact maximum (the worst case), j = M the mean, in between the mean of the worst j, a tail mean that stands in for CVaR.  +inf and the 3.0e38 sentinel behave
+ * as IEEE arithmetic makes them (3.0e38 + 3.0e38 = +inf); NaN member costs are outside the contract.  judo_amd/ensemble.py::aggregate_costs_host restates it in numpy.
+ *   jh_ensemble_costs       the aggregation alone: member m's cost of rollout r at member_costs[m * ld + r] (ld >= N; what lies between N and ld is not read), costs[0..N-1]
+ *                           written.  JH_ERR_INVALID, with jh_last_error naming the argument: a null pointer, M outside 1..JH_MAX_ENSEMBLE, N < 1, ld < N, worst outside 1..M.
+ *   jh_plan_step_ensemble   jh_plan_step on the set: one upload of the block (blk_dev == blk_host: read in place), the batched rollout kernel on the grid (workgroups, M) with the
+ *                           members sharing the block and the noise -- member b's costs land in member_costs[b * N ..] and are bit for bit those of jh_plan_step on member b's
+ *                           own handle --, then ONE launch that writes the aggregated costs into `costs` and runs the update's tail on them: out = [nominal K*nu | sigma K*nu]
+ *                           is bit for bit what jh_update_fused writes for those costs.  Two launches for every model; no trace buffer and no knots_out (the caller re-rolls its
+ *                           trace elites on the member it calls nominal).  One completion mark, as for jh_plan_step: out_host_mark == out is the stream's event, anything else the
+ *                           polled 4-byte word.  scratch: jh_update_fused_scratch_floats(N, K, nu) floats, ZERO before the first use; every launch leaves the ticket at zero.
+ *                           M = 1 takes the same code.  The diagnostic counters land in member 0's handle.  JH_ERR_INVALID, naming the argument: a null pointer, a set of more than
+ *                           JH_MAX_ENSEMBLE members, worst outside 1..M, N, H or K < 1, ldn < N, K * nu > JH_MAX_KNOT_DIM, a negative offset or a block too small for them, a bad
+ *                           mode / lambda / k, and a member 0 whose plan step is forced to one launch.  JH_ERR_UNSUPPORTED: as jh_plan_step_batch (a set holds neither fr3_pick
+ *                           nor a cross-check generation when it is made; a later change of member 0's kernel generation is caught here). */
+int jh_ensemble_costs(const float* member_costs /* DEVICE, M x ld */, int M, int N, int ld, int worst, float* costs /* DEVICE, N */, void* stream);
+int jh_plan_step_ensemble(const jh_model_set* set, void* blk_dev, const void* blk_host, size_t blk_bytes, int o_nominal, int o_sigma, int o_tp, int o_lohi, const float* noise, int ldn,
+                          const float* W, int N, int H, int K, float* member_costs /* DEVICE, M x N */, float* costs /* DEVICE, N */, int worst, int mode, float lambda, int k,
+                          int tie_high, float* scratch, float* out /* nominal | sigma */, void* out_host_mark, void* const* timing, void* stream);
 /* The noise of those B problems in one launch (judo/optimizers/{mppi.py:52,ps.py:43,cem.py:67}, one np.random.randn per controller): problem b's (rows, ldn) slice of `out`
  * (B x rows x ldn floats) is bit for bit what jh_noise_normal(seeds[b], draws[b], rows, 0, n_local, out + b * rows * ldn, ldn) writes; columns n_local .. ldn - 1 are left
  * alone.  seeds / draws: HOST arrays of B entries, read before the call returns (one launch per 256 problems: the pairs travel as kernel arguments). */

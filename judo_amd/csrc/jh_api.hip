@@ -758,6 +758,66 @@ extern "C" int jh_plan_step_batch_models(const jh_model_set* set, void* blk_dev,
                          noise_stride_floats, W, N, H, K, costs, trace, mode, lambda, k, tie_high, E, row_floats, colmajor, scratch, out, out_stride_floats, out_host_mark, timing, stream);
 }
 
+// ONE plan step against the M members of a model set (include/judo_amd.h): the batched rollout kernels on grid (workgroups, M) with the block and noise strides 0 -- every
+// member rolls out the same N candidates from the same block, on its own image, into its own row of member_costs -- then k_update_tail_ensemble, which aggregates the M
+// rows into `costs` and runs the single call's tail on them.  The records are built here: the batched entry points refuse strides below a block, rightly for what they do.
+// Always two launches (the closed-form models' one-launch form would roll a candidate out on one member per workgroup); no trace buffer, no knots_out.
+extern "C" int jh_plan_step_ensemble(const jh_model_set* set, void* blk_dev, const void* blk_host, size_t blk_bytes, int o_nominal, int o_sigma, int o_tp, int o_lohi, const float* noise, int ldn,
+                                     const float* W, int N, int H, int K, float* member_costs, float* costs, int worst, int mode, float lambda, int k, int tie_high, float* scratch, float* out,
+                                     void* out_host_mark, void* const* timing, void* stream) {
+  const char* who = "plan_step_ensemble";
+#define JH_ENS_PTR(p) JH_REQUIRE((p) != nullptr, "%s: " #p " is a null pointer", who)
+  JH_ENS_PTR(set); JH_ENS_PTR(blk_dev); JH_ENS_PTR(blk_host); JH_ENS_PTR(noise); JH_ENS_PTR(W); JH_ENS_PTR(member_costs); JH_ENS_PTR(costs); JH_ENS_PTR(scratch); JH_ENS_PTR(out);
+#undef JH_ENS_PTR
+  const jh_model* m = set->m0;
+  const int M = set->B;
+  JH_REQUIRE(M <= JH_MAX_ENSEMBLE, "%s: a set of %d members exceeds JH_MAX_ENSEMBLE = %d", who, M, JH_MAX_ENSEMBLE);
+  JH_REQUIRE(worst >= 1 && worst <= M, "%s: worst = %d outside [1, M = %d]", who, worst, M);
+  if (m->kind == JH_TASK_FR3_PICK) { jh_set_error("%s: fr3_pick has no batched plan step (its phase is chosen per problem on the host)", who); return JH_ERR_UNSUPPORTED; }
+  if (m->kind == JH_TASK_LEAP_CUBE && m->kernel_gen != 3) { jh_set_error("%s: only kernel generation 3 of the leap family has a batched launch (this model runs %d)", who, m->kernel_gen); return JH_ERR_UNSUPPORTED; }
+  JH_REQUIRE(N > 0 && H > 0 && K >= 1, "%s: N, H, K must be positive (N=%d H=%d K=%d)", who, N, H, K);
+  JH_REQUIRE(ldn >= N, "%s: ldn (%d) < N (%d)", who, ldn, N);
+  const int KU = K * m->nu;
+  JH_REQUIRE(KU <= JH_MAX_KNOT_DIM, "%s: K*nu = %d exceeds %d", who, KU, JH_MAX_KNOT_DIM);
+  const int nx = m->nq + m->nv;
+  JH_REQUIRE(o_nominal >= 0 && o_sigma >= 0 && o_tp >= 0 && o_lohi >= 0, "%s: negative block offset", who);
+  const size_t need = sizeof(float) * (size_t)std::max(std::max(nx, o_nominal + KU), std::max(std::max(o_sigma + KU, o_tp + m->ntaskparam), o_lohi + 2 * m->nu));
+  JH_REQUIRE(blk_bytes >= need, "%s: a block of %zu bytes does not hold x0 | nominal | sigma | task params | bounds at the given offsets (%zu bytes)", who, blk_bytes, need);
+  JH_REQUIRE(m->plan_step_launches != 1, "%s: one launch is forced (jh_model_set_plan_step_launches) but the ensemble's plan step is two launches", who);
+  const bool closed = m->kind == JH_TASK_CARTPOLE || m->kind == JH_TASK_CYLINDER_PUSH;
+  const jh_engine_build* eb = engine_build(m);
+  if (!closed && !(eb && eb->rollout_cost_batch)) { jh_set_error("%s: no batched kernel for this model", who); return JH_ERR_UNSUPPORTED; }
+  unsigned* flag = (out_host_mark && out_host_mark != (void*)out) ? (unsigned*)out_host_mark : nullptr;  // (out_host_mark == out: the stream's event)
+  const float* b = (const float*)blk_dev;
+  jh_upd::TailArgs a;  // (the tail's own checks before anything is enqueued: mode, lambda, k)
+  if (int rc = jh_update_tail_args(who, costs, nullptr, b + o_nominal, noise, ldn, b + o_sigma, b + o_lohi, N, 0, K, m->nu, mode, lambda, k, tie_high, 0, nullptr, 0, 0, scratch, out, out + KU,
+                                   nullptr, nullptr, &a)) return rc;
+  hipStream_t st = (hipStream_t)stream;
+  if (blk_dev != blk_host) { if (int rc = jh_upload_async(blk_dev, blk_host, blk_bytes, stream)) return rc; }  // (blk_dev == blk_host: read in place, as jh_plan_step)
+  if (timing) JH_HIP(hipEventRecord((hipEvent_t)timing[0], st));
+  const unsigned expect = flag ? __atomic_load_n(flag, __ATOMIC_RELAXED) + 1u : 0u;
+  a.done_flag = flag; a.done_value = expect;
+  const int* ints = set->tables ? m->d_i : set->d_i_plain;
+  int rc = JH_OK;
+  if (closed) {
+    jh_upd::TailArgs ra = a;  // the rollout kernel's view of the record: member b's costs lie b * N behind member 0's, everything else is shared
+    ra.costs = member_costs; ra.done_flag = nullptr; ra.done_value = 0u;
+    jh_upd::BatchArgs s;
+    s.B = M; s.blk = 0; s.noise = 0; s.costs = N; s.trace = 0; s.scratch = 0; s.out = 0; s.counter = nullptr; s.done_flag = nullptr; s.done_value = 0u; s.image = (long long)set->stride;
+    rc = jh_simple_rollout_cost_batch(m, set->d_images, b, b + o_tp, W, H, K, ra, s, st);
+  } else {
+    const jh_rollout_args ra = {b, b + o_nominal, noise, ldn, b + o_sigma, W, b + o_lohi, b + o_tp, 0, N, 0, H, K, member_costs, nullptr, nullptr};
+    const jh_rollout_batch rb = {set->d_images, (long long)set->stride, ints, M, 0, 0};
+    rc = eb->rollout_cost_batch(m, ra, rb, st);
+  }
+  if (rc == JH_OK && timing) JH_HIP(hipEventRecord((hipEvent_t)timing[1], st));
+  const jh_upd::EnsembleArgs e{member_costs, costs, M, worst, (long long)N};
+  if (rc == JH_OK) rc = jh_update_tail_ensemble_launch(a, e, st);
+  if (rc == JH_OK && timing) JH_HIP(hipEventRecord((hipEvent_t)timing[2], st));
+  if (rc == JH_OK) rc = download_begin(out, out, 0, stream, flag, expect);
+  return rc;
+}
+
 // The update alone for B problems whose costs are given (the materialise path of a fleet: the Spot policy rollout, judo_amd/fleet.py): jh_plan_step_batch's last stage --
 // k_update_tail_batch with the two-level ticket -- and its completion mark, without an upload or a rollout kernel in front.
 extern "C" int jh_update_fused_batch(int B, const float* costs, const float* blk, size_t blk_stride_floats, int o_nominal, int o_sigma, int o_lohi, const float* noise, int ldn,

@@ -487,3 +487,40 @@ extern "C" int jh_elite_merge(const float* recs, int G, int k, int K, int nu, in
   JH_HIP(hipGetLastError());
   return JH_OK;
 }
+
+// ------------------------------------------------------------------------------------------------ one controller against an ensemble of M plants
+// (Defined last in the file: the two kernels are emitted behind every other one and shift none of them in the code object.)
+// jh_ensemble_costs is the aggregation alone (jh_update_dev.h: ensemble_cost), one thread per rollout.  k_update_tail_ensemble is what jh_plan_step_ensemble launches
+// behind the batched rollout kernel: thread t of workgroup x holds rollout x * kUB + t in the tail's block stage, so a workgroup first writes the aggregated costs of
+// its own rollouts, then runs the tail unchanged -- one problem, one ticket, the single call's completion word.
+namespace {
+__global__ __launch_bounds__(kUB) void k_ensemble_costs(EnsembleArgs e, int N) {
+  const int r = blockIdx.x * kUB + threadIdx.x;
+  if (r < N) e.costs[r] = ensemble_cost(e.member_costs, e.M, e.stride, r, e.worst);
+}
+__global__ __launch_bounds__(kUB) void k_update_tail_ensemble(TailArgs a, EnsembleArgs e) {
+  const int r = blockIdx.x * kUB + threadIdx.x;
+  if (r < a.N) e.costs[r] = ensemble_cost(e.member_costs, e.M, e.stride, r, e.worst);
+  __syncthreads();  // (a thread reads back the cost it wrote: as behind the rollout body of the one-launch plan step)
+  update_tail_body(a);
+}
+}  // namespace
+
+extern "C" int jh_ensemble_costs(const float* member_costs, int M, int N, int ld, int worst, float* costs, void* stream) {
+  JH_REQUIRE(member_costs != nullptr, "ensemble_costs: member_costs is a null pointer");
+  JH_REQUIRE(costs != nullptr, "ensemble_costs: costs is a null pointer");
+  JH_REQUIRE(M >= 1 && M <= JH_MAX_ENSEMBLE, "ensemble_costs: M = %d outside [1, JH_MAX_ENSEMBLE = %d]", M, JH_MAX_ENSEMBLE);
+  JH_REQUIRE(N > 0, "ensemble_costs: N must be positive (N=%d)", N);
+  JH_REQUIRE(ld >= N, "ensemble_costs: ld (%d) < N (%d)", ld, N);
+  JH_REQUIRE(worst >= 1 && worst <= M, "ensemble_costs: worst = %d outside [1, M = %d]", worst, M);
+  const EnsembleArgs e{member_costs, costs, M, worst, (long long)ld};
+  hipLaunchKernelGGL(k_ensemble_costs, dim3((N + kUB - 1) / kUB), dim3(kUB), 0, (hipStream_t)stream, e, N);
+  JH_HIP(hipGetLastError());
+  return JH_OK;
+}
+
+int jh_update_tail_ensemble_launch(const TailArgs& a, const EnsembleArgs& e, hipStream_t st) {
+  hipLaunchKernelGGL(k_update_tail_ensemble, dim3((a.N + kUB - 1) / kUB), dim3(kUB), 0, st, a, e);
+  JH_HIP(hipGetLastError());
+  return JH_OK;
+}

@@ -359,6 +359,42 @@ __device__ __forceinline__ void batch_done(const BatchArgs& s, bool last) {
   if (s.done_flag) __hip_atomic_store(s.done_flag, s.done_value, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_SYSTEM);
 }
 
+// ---------------------------------------------------------------- one controller against an ensemble of M plants (jh_plan_step_ensemble)
+// The batched rollout kernels ran the N candidates of ONE problem on M model images (grid (workgroups, M), block and noise strides 0): member m's cost of rollout r is
+// member_costs[m * stride + r].  A rollout's aggregated cost is the mean of its `worst` largest member costs: the values are added in fp32 in descending order, starting
+// from the largest, and the sum is divided by (float)worst, correctly rounded (include/judo_amd.h; judo_amd/ensemble.py::aggregate_costs_host restates it in numpy).
+// One thread per rollout: lane-consecutive reads of every member's row.  The M values live in registers -- the member loops are unrolled to JH_MAX_ENSEMBLE with the
+// wave-uniform guard m < M, so every index is a constant and nothing goes to scratch -- and the selection is by passes: a pass finds the largest value below the one
+// taken last and how often it occurs, and adds it that often (or as often as `worst` still allows).  Equal values are interchangeable, so ties need no rule; at most
+// `worst` passes.  A pass that finds nothing (NaN members, outside the contract) ends the loop.
+struct EnsembleArgs {
+  const float* member_costs; float* costs;  // M x stride in, N out (`costs` is the tail's TailArgs::costs)
+  int M, worst; long long stride;
+};
+__device__ __forceinline__ float ensemble_cost(const float* __restrict__ member_costs, int M, long long stride, int r, int worst) {
+  float v[JH_MAX_ENSEMBLE];
+#pragma unroll
+  for (int m = 0; m < JH_MAX_ENSEMBLE; m++) v[m] = m < M ? member_costs[m * stride + r] : 0.f;
+  float acc = 0.f, hi = 0.f;
+  int taken = 0;
+  while (taken < worst) {
+    float cur = 0.f; int cnt = 0;
+#pragma unroll
+    for (int m = 0; m < JH_MAX_ENSEMBLE; m++) {
+      const float x = v[m];
+      const bool open = m < M && (taken == 0 || x < hi);  // not yet taken: every value at or above `hi` went in an earlier pass
+      const bool up = open && (cnt == 0 || x > cur);
+      cnt = up ? 1 : cnt + ((open && x == cur) ? 1 : 0);
+      cur = up ? x : cur;
+    }
+    if (cnt == 0) break;
+    const int take = min(cnt, worst - taken);
+    for (int t = 0; t < take; t++) acc = (taken + t == 0) ? cur : acc + cur;
+    taken += take; hi = cur;
+  }
+  return __fdiv_rn(acc, (float)worst);
+}
+
 }  // namespace jh_upd
 
 // jh_update.hip: the argument checks of jh_update_fused / jh_update_shard and the launch record of the tail (rec_out non-null: the shard form)
@@ -371,6 +407,8 @@ bool jh_simple_plan_step_fits(const jh_model* m, int H, int K);
 int jh_simple_plan_step(const jh_model* m, const float* x0, const float* W, const float* tp, int H, int K, const jh_upd::TailArgs& a, hipStream_t st);
 // the batched forms (jh_plan_step_batch): `a` is problem 0's record, `s` the strides; grid (workgroups of a problem, B)
 int jh_update_tail_batch_launch(const jh_upd::TailArgs& a, const jh_upd::BatchArgs& s, hipStream_t st);
+// the ensemble form (jh_plan_step_ensemble): the aggregation of e.member_costs into e.costs == a.costs, then the tail, in one launch
+int jh_update_tail_ensemble_launch(const jh_upd::TailArgs& a, const jh_upd::EnsembleArgs& e, hipStream_t st);
 // (`P`: the float section of problem 0's model image, s.image floats to the next problem's -- m->d_f with s.image = 0 where the problems share the model)
 int jh_simple_plan_step_batch(const jh_model* m, const float* P, const float* x0, const float* W, const float* tp, int H, int K, const jh_upd::TailArgs& a, const jh_upd::BatchArgs& s, hipStream_t st);
 int jh_simple_rollout_cost_batch(const jh_model* m, const float* P, const float* x0, const float* tp, const float* W, int H, int K, const jh_upd::TailArgs& a, const jh_upd::BatchArgs& s, hipStream_t st);

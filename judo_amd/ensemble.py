@@ -1,0 +1,216 @@
+"""One controller planned against an ensemble of M plants (`jh_plan_step_ensemble`, include/judo_amd.h).
+
+A `ControllerFleet` over M descriptions is M controllers with M nominals, each of which believes its own plant.  An `EnsembleController` is ONE controller with ONE
+nominal spline: each of its N candidates is rolled out on all M members of a `GpuModelSet` -- one block, one noise slice, a model image per member -- and scored by a
+risk measure over the M costs: the mean of the `worst` largest (`worst` = 1: the worst case, `worst` = M: the mean, in between a tail mean that stands in for CVaR).
+MPPI / CEM / PS then run once on the aggregated costs, in the same launch that aggregates them.  The reference has no counterpart.
+
+Member 0 is the nominal plant: the controller's `model`, on which the traces are re-rolled.  `aggregate_costs_host` restates the aggregation in numpy fp32, operation
+for operation; the device result equals it bit for bit (tests/test_gpu_ensemble_costs.py)."""
+
+from __future__ import annotations
+
+import ctypes as C
+from typing import Sequence
+
+import numpy as np
+import torch
+
+from judo_amd import _lib
+from judo_amd.config import ControllerConfig
+from judo_amd.controller import Controller, _PlanBuffers
+from judo_amd.device import GpuModel, GpuModelSet
+from judo_amd.distributed import Shard
+from judo_amd.models import image_sections, layout, pack_model
+from judo_amd.optimizers import get_registered_optimizers
+from judo_amd.tasks import Task, get_registered_tasks
+
+MAX_ENSEMBLE = _lib.MAX_ENSEMBLE
+
+
+def aggregate_costs_host(member_costs, worst: int) -> np.ndarray:
+    """The aggregated cost of every rollout, (N,) fp32, from `member_costs` (M, N): the `worst` largest of a rollout's M member costs are added in fp32 in descending
+    order, starting from the largest, and the sum is divided by `worst` in fp32 (correctly rounded).  `worst` = 1 is the exact maximum, `worst` = M the mean.  +inf and
+    the 3.0e38 sentinel behave as IEEE arithmetic makes them; NaN is outside the contract.  What `ensemble_cost` (judo_amd/csrc/jh_update_dev.h) computes, bit for bit."""
+    c = np.asarray(member_costs, dtype=np.float32)
+    if c.ndim != 2:
+        raise ValueError(f"member_costs must be (M, N), got {c.shape}")
+    M = c.shape[0]
+    j = int(worst)
+    if not 1 <= j <= M:
+        raise ValueError(f"worst = {worst} outside [1, M = {M}]")
+    top = -np.sort(-c, axis=0)[:j]  # the j largest per rollout, largest first (equal values are interchangeable)
+    with np.errstate(over="ignore"):  # (3.0e38 + 3.0e38 = +inf, as on the device)
+        acc = top[0].copy()
+        for i in range(1, j):
+            acc = (acc + top[i]).astype(np.float32)  # sequential fp32 adds
+        return (acc / np.float32(j)).astype(np.float32)
+
+
+def check_descriptions(descriptions: Sequence[dict]) -> list[bytes]:
+    """The admission rule of an ensemble, without a device (the rule `ControllerFleet` applies to members with images of their own): the descriptions pack to images
+    whose header and int section are member 0's byte for byte -- the float section alone may differ (masses, inertias, friction, gains: `models.scaled_description`).
+    Returns the packed images; raises ValueError naming the member and the section."""
+    if len(descriptions) < 1:
+        raise ValueError("an ensemble needs at least one description")
+    if len(descriptions) > MAX_ENSEMBLE:
+        raise ValueError(f"an ensemble of {len(descriptions)} members exceeds the {MAX_ENSEMBLE} of a launch (include/judo_amd.h JH_MAX_ENSEMBLE)")
+    blobs = [bytes(pack_model(d)) for d in descriptions]
+    want = image_sections(blobs[0])
+    for i, blob in enumerate(blobs[1:], start=1):
+        if blob == blobs[0]:
+            continue
+        for name, x, y in zip(("header", "float section", "int section"), image_sections(blob), want):
+            if (x != y and name != "float section") or len(x) != len(y):
+                raise ValueError(f"ensemble member {i} has another model image than member 0: the {name} of its image differs")
+    return blobs
+
+
+class EnsembleController(Controller):
+    """A `Controller` whose plan step rolls every candidate out on M plants and updates on the aggregated costs.  Everything else -- `update_states`, `action(t)`,
+    `traces`, `max_opt_iters`, the three optimizers, the `none` / `min_max` normalisers, a live change of `num_rollouts` -- is the controller's own.
+
+    `rewards` are the negated aggregated costs; `member_costs` / `member_rewards` the (M, N) costs behind them; `worst` may be set between plan steps, and
+    `set_member(b, description)` replaces one plant."""
+
+    def __init__(self, controller_config: ControllerConfig, task: Task, optimizer, descriptions: Sequence[dict], worst: int | None = None,
+                 device: torch.device | None = None) -> None:
+        if task.uses_locomotion_policy:
+            raise ValueError("the Spot policy tasks have no ensemble plan step: their iteration is the materialise path (spline, policy rollout, reward, update), not one library call")
+        if task.desc.get("family", task.desc["task"]) == "fr3_pick":
+            raise ValueError("fr3_pick has no ensemble plan step: its phase is chosen per problem on the host and its kernel has no batched launch")
+        check_descriptions(descriptions)
+        self._descriptions = list(descriptions)
+        task.desc = self._descriptions[0]
+        task._layout, task._ctrlrange, task._jadr, task._gpu = layout(task.desc), None, None, None
+        super().__init__(controller_config, task, optimizer, device=device)
+        self._members = [self.model] + [GpuModel(d, self.device) for d in self._descriptions[1:]]
+        self.model_set = GpuModelSet(self._members)
+        self._worst = len(self._members)
+        self.worst = len(self._members) if worst is None else worst
+        self._member_costs: torch.Tensor | None = None
+
+    # ---- the ensemble ------------------------------------------------------------------------------------------------------------------------------
+    @property
+    def descriptions(self) -> list[dict]:
+        return list(self._descriptions)
+
+    @property
+    def num_members(self) -> int:
+        return len(self._members)
+
+    @property
+    def worst(self) -> int:
+        """How many of a rollout's largest member costs are averaged: 1 = the worst case, M = the mean."""
+        return self._worst
+
+    @worst.setter
+    def worst(self, j: int) -> None:
+        if not 1 <= int(j) <= len(self._members):
+            raise ValueError(f"worst = {j} outside [1, M = {len(self._members)}]")
+        self._worst = int(j)
+
+    def set_member(self, b: int, description: dict) -> None:
+        """Replace member b's plant (`GpuModelSet.update`: the library's checks; synchronous -- between plan steps).  b = 0 replaces the nominal plant too."""
+        b = int(b)
+        if not 0 <= b < len(self._members):
+            raise ValueError(f"member {b} of an ensemble of {len(self._members)}")
+        trial = list(self._descriptions)
+        trial[b] = description
+        check_descriptions(trial)
+        model = GpuModel(description, self.device)
+        self.model_set.update(b, model)
+        self._members[b], self._descriptions[b] = model, description
+        if b == 0:
+            self.task.desc, self.task._gpu = description, model
+            self.task._layout, self.task._ctrlrange, self.task._jadr = layout(description), None, None
+            self.model = self.rollout_backend.model = model
+
+    @property
+    def member_costs(self) -> np.ndarray:
+        """(M, N) fp32: member b's cost of every candidate of the last iteration."""
+        if self._member_costs is None:
+            raise RuntimeError("member_costs needs a completed update_action()")
+        return self._member_costs.cpu().numpy()
+
+    @property
+    def member_rewards(self) -> np.ndarray:
+        return -self.member_costs.astype(np.float64)
+
+    # ---- the plan step -----------------------------------------------------------------------------------------------------------------------------
+    def _ensemble_refusal(self, world: int, nrm) -> str | None:
+        """Why this controller's iteration is not the one-call shape, or None."""
+        if world > 1 or self.force_shard_path:
+            return "a process group or force_shard_path: the sharded path has no ensemble form"
+        if nrm.needs_moments:
+            return "the running normaliser: its moments need the materialise path"
+        if self.keep_candidates:
+            return "keep_candidates: the ensemble launch writes no candidate knots"
+        if self.model is not None and self.optimizer.num_nodes > self.model.max_fused_knots_at(self.num_timesteps):
+            return f"num_nodes = {self.optimizer.num_nodes} above the fused kernel's limit of {self.model.max_fused_knots_at(self.num_timesteps)} knots at this horizon (max_fused_knots_at)"
+        if not self.uses_fused_cost or not (self.fused_update and hasattr(self.optimizer, "fused_update_args")):
+            return "a plugin reward, hook or optimizer (uses_fused_cost is false): the members' costs come from the fused kernels alone"
+        return None
+
+    def _iteration_shape(self, world: int, nrm) -> str:
+        why = self._ensemble_refusal(world, nrm)
+        if why is not None:
+            raise ValueError(f"an ensemble controller runs its iteration as one jh_plan_step_ensemble call, which this configuration rules out ({why})")
+        return "plan_step"
+
+    def update_action(self) -> None:
+        if not self.uses_fused_optimizer:
+            raise ValueError("an ensemble controller runs its iteration as one jh_plan_step_ensemble call, which this configuration rules out "
+                             "(a plugin reward, hook or optimizer (uses_fused_cost is false): the members' costs come from the fused kernels alone)")
+        super().update_action()
+
+    def _plan_step(self, lib, b: _PlanBuffers, shape: str, noise_p: int, ldn: int, knots_out, W, shard: Shard, world: int, H: int, K: int, nu: int, stream,
+                   state: dict) -> int:
+        """Shape "plan_step" on the ensemble: one upload (or the host block read in place), the batched rollout kernel on (workgroups, M), the update's tail with the
+        aggregation in front, one completion mark.  No trace buffer: the trace elites' knots are staged and re-rolled on member 0 when the traces are read."""
+        opt = self.optimizer
+        M, N = len(self._members), shard.count
+        state["trace_buf"] = None
+        b.size_out(2 * K * nu)
+        if self._member_costs is None or tuple(self._member_costs.shape) != (M, N):
+            self._member_costs = torch.empty((M, N), dtype=torch.float32, device=self.device)
+        mode, lam, k_el, tie = opt.fused_update_args()
+        evs = [self._timing_event() for _ in range(3)] if self.record_kernel_events else None
+        timing = (C.c_void_p * 3)(*[e.handle for e in evs]) if evs else None
+        off = b.offsets
+        in_place = b.blk_stale = self.model.closed_form
+        mark = b.done_ptr if self.model.closed_form else b.out_host_ptr
+        st = lib.jh_plan_step_ensemble(self.model_set.handle, b.host_ptr if in_place else b.blk.data_ptr(), b.host_ptr, b.nblk_bytes, int(off[1]), int(off[2]), int(off[3]), int(off[4]),
+                                       noise_p, ldn, _lib.ptr(W), N, H, K, self._member_costs.data_ptr(), _lib.ptr(b.costs), self._worst, mode, lam, k_el, tie, _lib.ptr(b.fused_scratch),
+                                       b.out_host_ptr, mark, timing, stream)
+        _lib.check(st, "jh_plan_step_ensemble")
+        state["costs"] = b.costs
+        if evs:
+            self.kernel_events.append((evs[0], evs[1]))
+            self.exchange_events.append((evs[1], evs[2]))
+        self._fetch(b, begun=True)
+        if state.get("stage") is not None:
+            state["stage"]()
+        return 0
+
+
+def make_ensemble_controller(task: str | Task, optimizer: str, descriptions: Sequence[dict], worst: int | None = None, device: torch.device | None = None) -> EnsembleController:
+    """`make_controller` for one controller over M plants: the registered task and optimizer (with the task's overrides) around `descriptions`, M model descriptions of
+    that task (`models.scaled_description(task.desc, body_mass=..., geom_friction=..., actuator_kp=...)`).  Member 0 is the nominal plant.  `worst`: how many of a
+    candidate's largest member costs are averaged; None: all M, the mean."""
+    tasks, opts = get_registered_tasks(), get_registered_optimizers()
+    if isinstance(task, str):
+        if task not in tasks:
+            raise ValueError(f"Task {task} not found in task registry.")
+        task = tasks[task][0]()
+    if optimizer not in opts:
+        raise ValueError(f"Optimizer {optimizer} not found in optimizer registry.")
+    opt_cls, opt_cfg_cls = opts[optimizer]
+    opt_cfg = opt_cfg_cls()
+    opt_cfg.set_override(task.name)
+    ctrl_cfg = ControllerConfig()
+    ctrl_cfg.set_override(task.name)
+    return EnsembleController(ctrl_cfg, task, opt_cls(opt_cfg, task.nu), descriptions, worst=worst, device=device)
+
+
+__all__ = ["EnsembleController", "MAX_ENSEMBLE", "aggregate_costs_host", "check_descriptions", "make_ensemble_controller"]
