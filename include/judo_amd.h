@@ -144,8 +144,23 @@ int jh_model_set_rollout_schedule(jh_model* m, int mode);
  * every hand-off counts as missed (a test hook for the recomputation).  None of this changes a bit of any output.  Other values: JH_ERR_INVALID.  Accepted and without
  * effect on the other models.  The environment variable JUDO_AMD_ROLLOUT_SLICES=1 .. 64 sets the default `slices` of every model created after it is set. */
 int jh_model_set_rollout_slices(jh_model* m, int slices, int max_workgroups, int flags);
+/* An explicit schedule of that queue's slices, which need not be equal: `first_steps[0 .. n)` are the first steps of slices 1 .. n (slice 0 starts at step 0), positive and
+ * strictly increasing, n <= 15 (at most 16 slices); n = 0 clears it.  At a launch, entries at or behind the horizon are dropped, so one schedule serves any horizon; what is
+ * left runs wherever the queue runs.  Of this setter and jh_model_set_rollout_slices THE LATER CALL DECIDES the slices: setting a schedule (n > 0) puts `slices` back to 0 and
+ * leaves `max_workgroups` and `flags` as they are, and every call of jh_model_set_rollout_slices clears the schedule.  With neither, the automatic rule below.  None of this
+ * changes a bit of any output.  Other values: JH_ERR_INVALID.  The environment variable JUDO_AMD_ROLLOUT_SLICE_BOUNDS=a,b,... sets the default of every model created after
+ * it is set (and goes in front of JUDO_AMD_ROLLOUT_SLICES). */
+int jh_model_set_rollout_slice_bounds(jh_model* m, const int* first_steps, int n);
 /* What the model's last fused leap_cube launch of generation 3 ran: 0 = the static grid, 1 = the queue of whole groups, S > 1 = the queue of S slices per group. */
 int jh_model_last_rollout_slices(const jh_model* m);
+/* The first steps of slices 1 .. S - 1 of that launch (equal slices: s H / S): at most `cap` of them go to `out`, the return value is their number (0 for whole groups and for
+ * the static grid), or a negative jh_status. */
+int jh_model_last_rollout_slice_bounds(const jh_model* m, int* out, int cap);
+/* The automatic schedule as a pure function (no model, no device): a fused launch of `groups` groups of four rollouts over `H` steps on a GPU that holds `wave_slots` waves of
+ * the kernel (8 per CU).  Fewer than two groups per slot: whole groups (returns 0).  From two: four equal slices (H = 8: 2, 4, 6).  From four groups per slot and H >= 32:
+ * five slices of 3/8, 1/4, 3/16, 1/8 and 1/16 of the horizon (H = 64: 24, 40, 52, 60), so that the units drawn last, over which the launch drains, are short.  At most `cap`
+ * first steps go to `first_steps`; the return value is their number, or a negative jh_status.  Every first step is inside (0, H). */
+int jh_rollout_slice_schedule(int H, int groups, int wave_slots, int* first_steps, int cap);
 /* Queue units that found their hand-off unset and recomputed their group up to their slice, summed over the model's launches since the counters were last reset
  * (jh_model_stats with reset != 0); synchronises.  A negative jh_status on failure. */
 int jh_model_recomputed_units(jh_model* m);

@@ -32,6 +32,9 @@ _SIGNATURES = {
     "jh_model_set_rollout_schedule": (C.c_int, [C.c_void_p, C.c_int]),
     "jh_model_set_rollout_slices": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int]),
     "jh_model_last_rollout_slices": (C.c_int, [C.c_void_p]),
+    "jh_model_set_rollout_slice_bounds": (C.c_int, [C.c_void_p, C.POINTER(C.c_int), C.c_int]),
+    "jh_model_last_rollout_slice_bounds": (C.c_int, [C.c_void_p, C.POINTER(C.c_int), C.c_int]),
+    "jh_rollout_slice_schedule": (C.c_int, [C.c_int, C.c_int, C.c_int, C.POINTER(C.c_int), C.c_int]),
     "jh_model_recomputed_units": (C.c_int, [C.c_void_p]),
     "jh_model_set_self_collision": (C.c_int, [C.c_void_p, C.c_int]),
     "jh_model_set_contact_capacity": (C.c_int, [C.c_void_p, C.c_int]),

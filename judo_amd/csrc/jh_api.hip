@@ -158,6 +158,11 @@ extern "C" int jh_model_create(const void* blob, size_t nbytes, int device, jh_m
   m->nf = h.nfloat; m->ni = h.nint; m->d_f = nullptr; m->d_i = nullptr; m->d_stats = nullptr; m->kernel_gen = (h.kind == JH_TASK_LEAP_CUBE || h.kind == JH_TASK_FR3_PICK) ? 3 : 2; m->self_collision = 1; m->contact_capacity = cylinders > 0 ? 64 : 48; m->cylinders = cylinders; m->arm_pairs = arm_pairs;
   { const char* e = getenv("JUDO_AMD_ROLLOUT_SCHEDULE"); m->rollout_schedule = (e && (e[0] == '1' || e[0] == '2')) ? e[0] - '0' : 0; }  // (the environment sets the default; jh_model_set_rollout_schedule changes it per model)
   { const char* e = getenv("JUDO_AMD_ROLLOUT_SLICES"); const int v = e ? atoi(e) : 0; m->rollout_slices = (v >= 1 && v <= 64) ? v : 0; }  // (likewise; jh_model_set_rollout_slices)
+  if (const char* e = getenv("JUDO_AMD_ROLLOUT_SLICE_BOUNDS")) {  // (likewise, and in front of the number above where both are set; "24,40,52,60"; jh_model_set_rollout_slice_bounds; a list it would refuse is ignored)
+    int b[JH_MAX_SLICE_BOUNDS + 1], n = 0; bool ok = true;
+    for (const char* p = e; *p && ok;) { char* q; const long v = strtol(p, &q, 10); ok = q != p && n <= JH_MAX_SLICE_BOUNDS - 1 && v > (n ? b[n - 1] : 0) && v < (1l << 30) && (*q == ',' || *q == 0); if (ok) { b[n++] = (int)v; p = *q ? q + 1 : q; } }
+    if (ok && n > 0) { for (int i = 0; i < n; i++) m->rollout_bounds[i] = b[i]; m->rollout_nbounds = n; m->rollout_slices = 0; }
+  }
   { const char* e = getenv("JUDO_AMD_PLAN_STEP_LAUNCHES"); m->plan_step_launches = (e && e[0] == '2') ? 2 : 0; }  // (the environment sets the default; jh_model_set_plan_step_launches changes it per model)
   const char* p = (const char*)blob + sizeof(h);
   m->h_f.assign((const float*)p, (const float*)p + h.nfloat);
@@ -371,7 +376,56 @@ extern "C" int jh_model_set_rollout_slices(jh_model* m, int slices, int max_work
   JH_REQUIRE(max_workgroups >= 0, "model_set_rollout_slices: max_workgroups must be 0 (the resident slots) or a positive cap on the queue's grid");
   JH_REQUIRE((flags & ~1) == 0, "model_set_rollout_slices: flags has bit 0 (every hand-off counts as missed) and no other");
   m->rollout_slices = slices; m->rollout_max_workgroups = max_workgroups; m->rollout_slice_flags = flags;
+  m->rollout_nbounds = 0;  // (the later call decides: an explicit schedule set before is gone)
   return JH_OK;
+}
+
+extern "C" int jh_model_set_rollout_slice_bounds(jh_model* m, const int* first_steps, int n) {
+  JH_REQUIRE(m != nullptr && n >= 0 && n <= JH_MAX_SLICE_BOUNDS && (n == 0 || first_steps != nullptr), "model_set_rollout_slice_bounds: 0 (none) to %d first steps", JH_MAX_SLICE_BOUNDS);
+  for (int i = 0; i < n; i++)
+    JH_REQUIRE(first_steps[i] > (i ? first_steps[i - 1] : 0), "model_set_rollout_slice_bounds: first steps must be positive and strictly increasing (entry %d is %d)", i, first_steps[i]);
+  for (int i = 0; i < n; i++) m->rollout_bounds[i] = first_steps[i];
+  m->rollout_nbounds = n;
+  if (n > 0) m->rollout_slices = 0;  // (the later call decides: a forced number of equal slices is gone; the grid's cap and the flags stay)
+  return JH_OK;
+}
+
+extern "C" int jh_model_last_rollout_slice_bounds(const jh_model* m, int* out, int cap) {
+  JH_REQUIRE(m != nullptr && cap >= 0 && (cap == 0 || out != nullptr), "model_last_rollout_slice_bounds: null model or output");
+  const int n = __atomic_load_n(&m->last_rollout_nbounds, __ATOMIC_RELAXED);
+  for (int i = 0; i < n && i < cap; i++) out[i] = __atomic_load_n(&m->last_rollout_bounds[i], __ATOMIC_RELAXED);
+  return n;
+}
+
+void jh_model_note_slice_bounds(const jh_model* m, int slices, int H, const int* bounds) {
+  const int n = slices > 1 ? (slices - 1 < 63 ? slices - 1 : 63) : 0;
+  for (int i = 0; i < n; i++) __atomic_store_n(&m->last_rollout_bounds[i], bounds ? bounds[i] : (i + 1) * H / slices, __ATOMIC_RELAXED);
+  __atomic_store_n(&m->last_rollout_nbounds, n, __ATOMIC_RELAXED);
+}
+
+// The automatic schedule of the leap queue's horizon slices, a pure function of the launch's shape (profiles/leap_tapered_slices.md).  Below two groups per wave slot: whole
+// groups (a slice's producer must as good as always have parked its state by the time the slice is drawn).  From two: four equal slices.  From JH_TAPER_DEPTH groups per slot
+// and JH_TAPER_MIN_H steps: slices that shorten towards the end of the horizon -- 3/8, 1/4, 3/16, 1/8 and 1/16 of it, 24 / 16 / 12 / 8 / 4 steps of 64 -- so that the tickets
+// drawn last, over which the launch drains, are the short ones; one hand-off more than the equal slices.  The depth condition: a missed hand-off of the last slice recomputes
+// fifteen sixteenths of the horizon, which would undo the gain in the launch's tail.
+#ifndef JH_AUTO_TAPER
+#define JH_AUTO_TAPER 1
+#endif
+constexpr int JH_TAPER_DEPTH = 4, JH_TAPER_MIN_H = 32;
+extern "C" int jh_rollout_slice_schedule(int H, int groups, int wave_slots, int* first_steps, int cap) {
+  JH_REQUIRE(H >= 0 && groups >= 0 && wave_slots >= 0 && cap >= 0 && (cap == 0 || first_steps != nullptr), "rollout_slice_schedule: negative argument or null output");
+  int b[4], n = 0;
+  if (wave_slots > 0 && (long long)groups >= 2ll * wave_slots) {
+    if (JH_AUTO_TAPER && H >= JH_TAPER_MIN_H && (long long)groups >= (long long)JH_TAPER_DEPTH * wave_slots) {
+      const long long num[4] = {6, 10, 13, 15};
+      for (n = 0; n < 4; n++) b[n] = (int)(num[n] * H / 16);
+    } else {
+      const int S = H < 4 ? H : 4;
+      for (int i = 1; i < S; i++) b[n++] = i * H / S;
+    }
+  }
+  for (int i = 0; i < n && i < cap; i++) first_steps[i] = b[i];
+  return n;
 }
 
 extern "C" int jh_model_last_rollout_slices(const jh_model* m) {
@@ -676,7 +730,9 @@ static int model_set_member(const char* who, const jh_model* m0, const jh_model*
       return JH_ERR_INVALID;
     }
     JH_SET_SAME(kernel_gen, "%d"); JH_SET_SAME(contact_capacity, "%d"); JH_SET_SAME(cylinders, "%d"); JH_SET_SAME(self_collision, "%d"); JH_SET_SAME(rollout_schedule, "%d");
-    JH_SET_SAME(rollout_slices, "%d"); JH_SET_SAME(rollout_max_workgroups, "%d"); JH_SET_SAME(rollout_slice_flags, "%d");
+    JH_SET_SAME(rollout_slices, "%d"); JH_SET_SAME(rollout_nbounds, "%d");
+    for (int i = 0; i < m0->rollout_nbounds; i++) JH_SET_SAME(rollout_bounds[i], "%d");
+ JH_SET_SAME(rollout_max_workgroups, "%d"); JH_SET_SAME(rollout_slice_flags, "%d");
     JH_SET_SAME(plan_step_launches, "%d");
 #undef JH_SET_SAME
   }

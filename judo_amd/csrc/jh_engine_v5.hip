@@ -90,9 +90,10 @@ constexpr int CVX_STOP_NM = 1000;   // the stop of the cylinder build's GJK + EP
 #define OPAQUE(x) asm volatile("" : "+v"(x))
 // The parked state of a horizon slice (see the kernel): PARK_F floats per queue unit, every word stored and loaded at device scope
 constexpr int PARK_F = 5 * 64;
-#ifndef JH_V5_AUTO_SLICES
-#define JH_V5_AUTO_SLICES 4  // the slices of the automatic schedule (profiles/leap_horizon_slices.md)
-#endif
+// An explicit schedule of horizon slices (jh_model_set_rollout_slice_bounds, and the automatic taper): sixteen 16-bit step indices, two to a word, passed to the kernel by
+// value -- entry s is the step behind slice s's last, entries from the last slice on hold H -- and read from the kernel arguments with a uniform load, once per unit.
+struct SliceBounds { unsigned w[8]; };
+constexpr int MAX_BOUND_SLICES = 16;
 #define PARK_LD(p) __hip_atomic_load((p), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT)
 #define PARK_ST(p, v) __hip_atomic_store((p), (v), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT)
 #define WSYNC() do { __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront"); __builtin_amdgcn_wave_barrier(); __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront"); } while (0)
@@ -446,7 +447,8 @@ __device__ __forceinline__ bool chain_elim_order(int cmask, int c, int& level, i
 // last parks what the step loop carries (PARK_F floats per unit, rows of 64 lanes: q, qd, the joints' warm start, then per rollout the cube's state, the running cost and
 // the cube's warm start) behind the flag words in `pflags`, fences at device scope and sets the unit's flag; the next slice's wave reads that flag ONCE.  Set: it fences
 // and resumes from the parked rows (fp32 out, fp32 in).  Not set (the producer is still running; or bit 8 of `slices_`, a test hook): it runs the group from x0 up to its
-// slice's first step -- the same instructions on the same inputs, the same bits; trace rows written twice carry the same words -- zeroes the counters and goes on into its own
+// slice's first step (bit 9 of `slices_`: slice s runs steps [sb_[s - 1], sb_[s]) of the bounds table instead, S <= 16: slices that shorten towards the end of the horizon, so
+// that the tickets drawn last are the short ones) -- the same instructions on the same inputs, the same bits; trace rows written twice carry the same words -- zeroes the counters and goes on into its own
 // slice.  While it recomputes it adds to no counter (`stats` is null for that pass: the dropped contacts and lost candidate pairs of those steps are the producer's to count) and
 // its contacts above the LDS pool go to a row of its wave slot's own behind the rollouts' rows (the producer may still be running the same rollouts on theirs); the
 // launch counts such units in stats[JH_STAT_RECOMPUTED].  Nothing polls and no wave waits for another.  Every flag and every parked row is written by one unit and read by at most one, once per launch.
@@ -464,7 +466,7 @@ __global__ __launch_bounds__(WAVE * WPB, WAVES_PER_EU) void k_leap_v5(const floa
                                                    const float* __restrict__ tp, int N, int n_offset, int H, int K, float* __restrict__ costs,
                                                    float* __restrict__ knots_out, const float* __restrict__ controls, float* __restrict__ states,
                                                    float* __restrict__ sensors, int* __restrict__ stats_, int dshift_, float* __restrict__ trace, float* __restrict__ ovf_all_, unsigned* __restrict__ head,
-                                                   long long batch_blk, long long batch_noise, long long batch_image, unsigned* pflags, int slices_) {
+                                                   long long batch_blk, long long batch_noise, long long batch_image, unsigned* pflags, int slices_, SliceBounds sb_) {
   static_assert(!BATCH || (!MATERIALIZE && !PERSIST), "batched launches are fused launches on the static grid");
   if constexpr (BATCH) {
     const long long pb = blockIdx.y;
@@ -548,7 +550,11 @@ __global__ __launch_bounds__(WAVE * WPB, WAVES_PER_EU) void k_leap_v5(const floa
   }
   if constexpr (PERSIST) if (!again) {
     grp = unit % ngroups;
-    const int sl = unit / ngroups, h0 = sl * H / nsl, h1 = (sl + 1) * H / nsl;
+    const int sl = unit / ngroups; int h0 = sl * H / nsl, h1 = (sl + 1) * H / nsl;
+    if (slices_ & 0x200) {  // slices of unequal length: the table of bounds (at most 16 slices), read here and nowhere else -- h0 and h1 go into the unit's words below as ever
+      const auto bound = [&](int i) -> int { return (int)((sb_.w[i >> 1] >> ((i & 1) << 4)) & 0xffffu); };
+      h1 = bound(sl); h0 = sl > 0 ? bound(sl - 1) : 0;
+    }
     if (sl > 0) {  // the flag of (group, slice - 1), read once: an acquire load of lane 0, broadcast, and the wave's acquire fence in front of the parked rows
       unsigned f = 0;
       if (lane == 0 && !(slices_ & 0x100)) f = __hip_atomic_load(pflags + (unit - ngroups), __ATOMIC_ACQUIRE, __HIP_MEMORY_SCOPE_AGENT);
@@ -1923,7 +1929,7 @@ bool accepts(const jh_model* m) { return leap_refusal(m, nullptr) == JH_OK; }
 struct LeapArgs {
   const jh_rollout_args& a; const float* gF; const int* gI; int* stats; int dshift, grid;  // grid: not an argument -- the workgroups of a problem on the static grid
   int x0_batched = 0; const float* controls = nullptr; float *states = nullptr, *sensors = nullptr;  // materialise mode
-  float* ovf = nullptr; unsigned *head = nullptr, *pflags = nullptr; int slices = 0;
+  float* ovf = nullptr; unsigned *head = nullptr, *pflags = nullptr; int slices = 0; SliceBounds sb = {};
   long long batch_blk = 0, batch_noise = 0, batch_image = 0;
 };
 
@@ -1941,7 +1947,7 @@ void launch(const LeapArgs& k, dim3 grid, hipStream_t st) {
   const jh_rollout_args& a = k.a;
   hipLaunchKernelGGL((k_leap_v5<MATERIALIZE, WAVES_PER_BLOCK, SELF, PERSIST, BATCH>), grid, dim3(WAVE * WAVES_PER_BLOCK), 0, st, k.gF, k.gI, a.x0, k.x0_batched, a.nominal, a.noise, a.ldn,
                      a.sigma, a.W, a.lohi, a.tp, a.N, a.n_offset, a.H, a.K, a.costs, a.knots_out, k.controls, k.states, k.sensors, k.stats, k.dshift, a.trace, k.ovf, k.head,
-                     k.batch_blk, k.batch_noise, k.batch_image, k.pflags, k.slices);
+                     k.batch_blk, k.batch_noise, k.batch_image, k.pflags, k.slices, k.sb);
 }
 
 bool hand_contacts(const jh_model* m) { return m->self_collision && m->h_i[17] > 0; }  // the SELF instantiations: the hand's own contacts are on and the image has body pairs
@@ -1969,11 +1975,18 @@ static int rollout_cost(const jh_model* m, const jh_rollout_args& a, hipStream_t
   // Horizon slices (jh_model_set_rollout_slices): the queue's units are (group, slice) where the queue runs and the launch has at least two groups per wave slot -- dependent
   // units are then so many tickets apart that a slice's predecessor has as good as always parked its state in time -- or wherever the queue runs if a number is forced.
   const int ngroups = (N + RPW - 1) / RPW;
-  int slices = 1;
+  // The slices' first steps come from the model's explicit schedule (jh_model_set_rollout_slice_bounds; bounds at or behind H are dropped, so a schedule holds for any horizon),
+  // from a forced number of equal slices, or from the automatic rule (jh_rollout_slice_schedule: a taper where the queue is deep, equal slices from two groups per wave slot).
+  // Equal slices run on the kernel's own division, as they did before there was a table; any other schedule goes to the kernel as its table of bounds.
+  int slices = 1, bounds[JH_MAX_SLICE_BOUNDS], nb = 0; bool table = false;
   if (persist) {
-    slices = m->rollout_slices > 0 ? m->rollout_slices : (ngroups >= 2 * slots * WAVES_PER_BLOCK ? JH_V5_AUTO_SLICES : 1);
+    if (m->rollout_nbounds > 0) { for (int i = 0; i < m->rollout_nbounds; i++) if (m->rollout_bounds[i] < H) bounds[nb++] = m->rollout_bounds[i]; slices = nb + 1; }
+    else if (m->rollout_slices > 0) slices = m->rollout_slices;
+    else { nb = jh_rollout_slice_schedule(H, ngroups, slots * WAVES_PER_BLOCK, bounds, JH_MAX_SLICE_BOUNDS); slices = nb + 1; }
     if (slices > H) slices = H;
     if (slices < 1 || (long long)slices * ngroups > 0x7fffffffll) slices = 1;
+    for (int i = 0; i < nb && slices == nb + 1; i++) table = table || bounds[i] != (i + 1) * H / slices;
+    if (table && (slices > MAX_BOUND_SLICES || H > 0xffff)) { slices = 1; table = false; }  // (what the table cannot hold: never reached through the setters and the rule)
   }
   // Stream-ordered scratch of the launch, no state on the model handle (two streams may run one model): the queue's head word in a 16-byte block, the flag words of the
   // slices (one per unit, padded to 16 bytes) -- both zeroed in front of every launch that uses them --, the parked rows of the slices, then one row per rollout for the
@@ -1990,14 +2003,16 @@ static int rollout_cost(const jh_model* m, const jh_rollout_args& a, hipStream_t
     ovf_b = ovf_bytes((size_t)N + own_rows);
     if (ovf_b > 0 || persist) scratch = jh_launch_scratch(m, ovf_b + queue_bytes, st, ovf_b > 0 && slices == 1);  // (nullptr: the LDS capacity alone, drops and the fallback counted -- and the static shape)
     if (scratch || slices == 1) break;
-    slices = 1;
+    slices = 1; table = false;
   }
   if (scratch && persist && hipMemsetAsync(scratch, 0, 16 + flag_words * sizeof(unsigned), st) != hipSuccess) { (void)hipGetLastError(); persist = false; }
   if (!scratch) persist = false;
-  if (persist) { head = (unsigned*)scratch; k.grid = qgrid; } else slices = 1;
+  if (persist) { head = (unsigned*)scratch; k.grid = qgrid; } else { slices = 1; table = false; }
+  if (table) for (int i = 0; i < MAX_BOUND_SLICES; i++) k.sb.w[i >> 1] |= (unsigned)(i < nb ? bounds[i] : H) << ((i & 1) << 4);
+  jh_model_note_slice_bounds(m, slices, H, table ? bounds : nullptr);
   if (scratch && ovf_b > 0) k.ovf = scratch + (head ? queue_bytes / sizeof(float) : 0);
   __atomic_store_n(&m->last_rollout_slices, persist ? slices : 0, __ATOMIC_RELAXED);
-  k.head = head; k.pflags = head ? head + 4 : nullptr; k.slices = slices | ((m->rollout_slice_flags & 1) << 8);
+  k.head = head; k.pflags = head ? head + 4 : nullptr; k.slices = slices | ((m->rollout_slice_flags & 1) << 8) | (table ? 0x200 : 0);
   if (hand_contacts(m)) { if (persist) launch<false, true, true>(k, dim3(k.grid), st); else launch<false, true, false>(k, dim3(k.grid), st); }
   else { if (persist) launch<false, false, true>(k, dim3(k.grid), st); else launch<false, false, false>(k, dim3(k.grid), st); }
   return jh_launch_done(scratch, st);

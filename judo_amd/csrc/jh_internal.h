@@ -24,6 +24,8 @@ struct jh_blob_header {
   uint32_t reserved[6];
 };
 
+constexpr int JH_MAX_SLICE_BOUNDS = 15;  // an explicit schedule has at most 16 slices: the kernel's table of bounds (jh_engine_v5.hip)
+
 struct jh_model {
   int device, kind, nq, nv, nu, ns, ntaskparam;
   size_t nf, ni;
@@ -36,6 +38,8 @@ struct jh_model {
   int self_collision;  // leap_cube on jh_engine_v5.hip: model the hand's own contacts (finger-finger, finger-palm) as MuJoCo does; 0 = the cube's contacts only
   int rollout_schedule;  // leap_cube generation 3, fused launches: 0 = persistent waves on a queue of rollout groups where the launch exceeds the GPU's wave slots (the default), 1 = always the static grid, 2 = the queue wherever the kernel has it (jh_model_set_rollout_schedule)
   int rollout_slices = 0, rollout_max_workgroups = 0, rollout_slice_flags = 0;  // the queue's horizon slices (jh_model_set_rollout_slices): 0 = automatic or 1..64 forced; a cap on the queue's grid (0: the resident slots); bit 0: every hand-off counts as missed
+  int rollout_bounds[JH_MAX_SLICE_BOUNDS] = {}, rollout_nbounds = 0;  // an explicit schedule of slices (jh_model_set_rollout_slice_bounds): the first steps of slices 1 .. n, strictly increasing; n = 0: none.  The later call of the two setters decides
+  mutable int last_rollout_bounds[63] = {}, last_rollout_nbounds = 0;  // the first steps of slices 1 .. S - 1 of that launch (jh_model_last_rollout_slice_bounds); __atomic builtins
   mutable int last_rollout_slices = 0;  // what the model's last fused leap launch ran: 0 = the static grid, 1 = the queue of groups, S > 1 = the queue of S slices per group (jh_model_last_rollout_slices); __atomic builtins, as ovf_fallbacks
   int plan_step_launches;  // closed-form models' plan step: 0 = one launch where it fits (the default), 1 = always one launch, 2 = always two (jh_model_set_plan_step_launches)
   mutable int one_launch_steps = 0;  // plan steps that ran as one launch (jh_model_stats out[7]); __atomic builtins, as ovf_fallbacks
@@ -46,6 +50,8 @@ struct jh_model {
 };
 
 void jh_set_error(const char* fmt, ...);
+// The leap launcher's record of the slices it ran (jh_api.hip): `bounds` null = `slices` equal ones of a horizon H.
+void jh_model_note_slice_bounds(const jh_model* m, int slices, int H, const int* bounds);
 
 // Per-launch scratch of the cooperative kernels (the contacts above the LDS pool, one row per rollout): a stream-ordered allocation from the default pool of the MODEL's
 // device (not of whatever device is current in the calling thread).  nullptr when the pool refuses: the kernel then holds what its LDS pool holds, the drops are

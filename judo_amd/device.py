@@ -194,6 +194,22 @@ class GpuModel:
         """What the last fused launch ran: 0 = the static grid, 1 = the queue of whole groups, S > 1 = the queue of S slices per group."""
         return int(_lib.lib().jh_model_last_rollout_slices(self.handle))
 
+    def set_rollout_slice_bounds(self, first_steps=()) -> None:
+        """leap_cube, kernel generation 3: an explicit schedule of the queue's slices -- the first steps of slices 1 .. n, positive and strictly increasing, at most 15; empty
+        clears it.  Entries at or behind a launch's horizon are dropped at that launch.  Of this and `set_rollout_slices` the later call decides the slices
+        (`jh_model_set_rollout_slice_bounds`).  The bits do not depend on it."""
+        steps = [int(s) for s in first_steps]
+        arr = (C.c_int * max(1, len(steps)))(*steps)
+        _lib.check(_lib.lib().jh_model_set_rollout_slice_bounds(self.handle, arr, len(steps)), "jh_model_set_rollout_slice_bounds")
+
+    def last_rollout_slice_bounds(self) -> tuple:
+        """The first steps of slices 1 .. S - 1 of the last fused launch (empty: whole groups, or the static grid)."""
+        out = (C.c_int * 63)()
+        n = int(_lib.lib().jh_model_last_rollout_slice_bounds(self.handle, out, 63))
+        if n < 0:
+            _lib.check(n, "jh_model_last_rollout_slice_bounds")
+        return tuple(out[:n])
+
     def recomputed_units(self) -> int:
         """Queue units that missed their hand-off and recomputed their group up to their slice, since the counters were last reset by `stats()` (synchronises)."""
         v = int(_lib.lib().jh_model_recomputed_units(self.handle))
@@ -260,3 +276,13 @@ class GpuModelSet:
             self.close()
         except Exception:
             pass
+
+
+def rollout_slice_schedule(horizon: int, groups: int, wave_slots: int) -> tuple:
+    """The leap queue's automatic schedule of horizon slices as a pure function of the launch's shape (`jh_rollout_slice_schedule`; no device needed): the first steps of
+    slices 1 .. n for `groups` groups of four rollouts over `horizon` steps on a GPU that holds `wave_slots` waves of the kernel.  Empty: whole groups."""
+    out = (C.c_int * 15)()
+    n = int(_lib.lib().jh_rollout_slice_schedule(int(horizon), int(groups), int(wave_slots), out, 15))
+    if n < 0:
+        _lib.check(n, "jh_rollout_slice_schedule")
+    return tuple(out[:n])
