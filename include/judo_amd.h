@@ -47,6 +47,7 @@ enum jh_spline_kind { JH_SPLINE_ZERO = 0, JH_SPLINE_LINEAR = 1, JH_SPLINE_CUBIC 
 #define JH_MAX_KNOT_DIM 512 /* K * nu */
 #define JH_MAX_ELITES 32
 #define JH_MAX_ENSEMBLE 32 /* members of a model set that jh_plan_step_ensemble plans against */
+#define JH_MAX_ENSEMBLE_FLEET 256 /* controllers of one jh_plan_step_ensemble_batch call (their `worst` travel in the kernel arguments, a byte each) */
 
 const char* jh_last_error(void);
 int jh_version(void);
@@ -360,6 +361,27 @@ int jh_ensemble_costs(const float* member_costs /* DEVICE, M x ld */, int M, int
 int jh_plan_step_ensemble(const jh_model_set* set, void* blk_dev, const void* blk_host, size_t blk_bytes, int o_nominal, int o_sigma, int o_tp, int o_lohi, const float* noise, int ldn,
                           const float* W, int N, int H, int K, float* member_costs /* DEVICE, M x N */, float* costs /* DEVICE, N */, int worst, int mode, float lambda, int k,
                           int tie_high, float* scratch, float* out /* nominal | sigma */, void* out_host_mark, void* const* timing, void* stream);
+/* B ensemble plan steps as ONE call with ONE completion mark (several robots, or one robot swept over risk levels, goals or seeds: B controllers that each plan against
+ * M plants; the reference has no counterpart).  Controller b rolls its own N candidates out on its M plants, aggregates them with its own worst[b] and updates its own
+ * nominal; its results are bit for bit those of jh_plan_step_ensemble on its block, its noise and its plants with worst[b].
+ *   per controller   the packed block x0 | nominal | sigma | task params | bounds, blk_stride_bytes apart; the noise, noise_stride_floats apart; the update scratch,
+ *                    jh_update_fused_scratch_floats(N, K, nu) floats apart (jh_plan_batch_scratch_floats(B, N, K, nu) in all, ZERO before the first use: the B + 1 ticket
+ *                    words, which every launch leaves at zero); the output record nominal K*nu | sigma K*nu, out_stride_floats apart; the row b of `costs` (B x N); the slab
+ *                    b of `member_costs` (B x M x N, controller-major: plant m's cost of controller b's rollout r at (b * M + m) * N + r); worst[b]
+ *   shared           N, H, K, W, mode, lambda, k, tie_high; no trace buffer and no knots_out, as for the ensemble call
+ *   the plants       a set of M members, which every controller plans against, or a set of B * M members, controller-major: member b * M + m is controller b's plant m.
+ *                    M <= JH_MAX_ENSEMBLE, B <= JH_MAX_ENSEMBLE_FLEET.  A set of any other size: JH_ERR_INVALID with the three numbers
+ *   worst            a HOST array of B ints, each in 1..M (the error names the controller), read before the call returns: the values travel in the kernel arguments
+ * Two launches for every model: the batched rollout kernel on the grid (workgroups, M, B) -- the leap kernel's latency mode is chosen from the B * M * N rollouts of the
+ * launch, and the bits do not depend on it; no queue --, then the aggregation and the update's tail on (tail workgroups, B) with the two-level ticket of
+ * jh_plan_step_batch.  The completion mark is that call's: out_host_mark == out is the stream's event, anything else the polled 4-byte word, which receives its old value
+ * + 1 behind the last controller's results.  B = 1 and M = 1 take the same code.  Everything is checked before anything is enqueued.  JH_ERR_INVALID, naming the
+ * argument: what jh_plan_step_ensemble refuses (each null pointer by name, `worst` included), B or M outside their limits, a stride smaller than a block / a noise slice
+ * / an output record, a member 0 whose plan step is forced to one launch.  JH_ERR_UNSUPPORTED: as jh_plan_step_ensemble. */
+int jh_plan_step_ensemble_batch(const jh_model_set* set, int B, int M, void* blk_dev, const void* blk_host, size_t blk_bytes, size_t blk_stride_bytes, int o_nominal, int o_sigma, int o_tp,
+                                int o_lohi, const float* noise, int ldn, size_t noise_stride_floats, const float* W, int N, int H, int K, float* member_costs /* DEVICE, B x M x N */,
+                                float* costs /* DEVICE, B x N */, const int* worst /* HOST, B */, int mode, float lambda, int k, int tie_high, float* scratch, float* out, size_t out_stride_floats,
+                                void* out_host_mark, void* const* timing, void* stream);
 /* The noise of those B problems in one launch (judo/optimizers/{mppi.py:52,ps.py:43,cem.py:67}, one np.random.randn per controller): problem b's (rows, ldn) slice of `out`
  * (B x rows x ldn floats) is bit for bit what jh_noise_normal(seeds[b], draws[b], rows, 0, n_local, out + b * rows * ldn, ldn) writes; columns n_local .. ldn - 1 are left
  * alone.  seeds / draws: HOST arrays of B entries, read before the call returns (one launch per 256 problems: the pairs travel as kernel arguments). */

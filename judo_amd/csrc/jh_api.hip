@@ -874,6 +874,80 @@ extern "C" int jh_plan_step_ensemble(const jh_model_set* set, void* blk_dev, con
   return rc;
 }
 
+// B of those plan steps as ONE call (include/judo_amd.h): B controllers, each with its own block, noise, `worst`, costs and output record, each against M plants.  The
+// rollout kernels run once on the grid (workgroups, M, B): blockIdx.y is the member as above (block and noise strides 0, the set's image stride), blockIdx.z the
+// controller with the strides of jh_plan_step_batch; a set of M members is shared by all controllers (image stride 0 on that axis), a set of B * M holds controller b's
+// plants at b * M ...  Then k_update_tail_ensemble_batch on (tail workgroups, B): aggregation, tail, the two-level ticket, one completion word.  The checks are the
+// ensemble call's and the batched call's, all in front of the first enqueue.
+extern "C" int jh_plan_step_ensemble_batch(const jh_model_set* set, int B, int M, void* blk_dev, const void* blk_host, size_t blk_bytes, size_t blk_stride_bytes, int o_nominal, int o_sigma, int o_tp,
+                                           int o_lohi, const float* noise, int ldn, size_t noise_stride_floats, const float* W, int N, int H, int K, float* member_costs, float* costs,
+                                           const int* worst, int mode, float lambda, int k, int tie_high, float* scratch, float* out, size_t out_stride_floats, void* out_host_mark,
+                                           void* const* timing, void* stream) {
+  const char* who = "plan_step_ensemble_batch";
+#define JH_ENS_PTR(p) JH_REQUIRE((p) != nullptr, "%s: " #p " is a null pointer", who)
+  JH_ENS_PTR(set); JH_ENS_PTR(blk_dev); JH_ENS_PTR(blk_host); JH_ENS_PTR(noise); JH_ENS_PTR(W); JH_ENS_PTR(member_costs); JH_ENS_PTR(costs); JH_ENS_PTR(worst); JH_ENS_PTR(scratch); JH_ENS_PTR(out);
+#undef JH_ENS_PTR
+  const jh_model* m = set->m0;
+  JH_REQUIRE(B >= 1 && B <= JH_MAX_ENSEMBLE_FLEET, "%s: B = %d outside [1, JH_MAX_ENSEMBLE_FLEET = %d]", who, B, JH_MAX_ENSEMBLE_FLEET);
+  JH_REQUIRE(M >= 1 && M <= JH_MAX_ENSEMBLE, "%s: M = %d outside [1, JH_MAX_ENSEMBLE = %d]", who, M, JH_MAX_ENSEMBLE);
+  JH_REQUIRE(set->B == M || set->B == B * M, "%s: a set of %d members is neither the M = %d plants every controller shares nor the B * M = %d plants of B = %d controllers", who, set->B, M, B * M, B);
+  for (int b = 0; b < B; b++) JH_REQUIRE(worst[b] >= 1 && worst[b] <= M, "%s: controller %d: worst = %d outside [1, M = %d]", who, b, worst[b], M);
+  if (m->kind == JH_TASK_FR3_PICK) { jh_set_error("%s: fr3_pick has no batched plan step (its phase is chosen per problem on the host)", who); return JH_ERR_UNSUPPORTED; }
+  if (m->kind == JH_TASK_LEAP_CUBE && m->kernel_gen != 3) { jh_set_error("%s: only kernel generation 3 of the leap family has a batched launch (this model runs %d)", who, m->kernel_gen); return JH_ERR_UNSUPPORTED; }
+  JH_REQUIRE(N > 0 && H > 0 && K >= 1, "%s: N, H, K must be positive (N=%d H=%d K=%d)", who, N, H, K);
+  JH_REQUIRE(ldn >= N, "%s: ldn (%d) < N (%d)", who, ldn, N);
+  const int KU = K * m->nu;
+  JH_REQUIRE(KU <= JH_MAX_KNOT_DIM, "%s: K*nu = %d exceeds %d", who, KU, JH_MAX_KNOT_DIM);
+  const int nx = m->nq + m->nv;
+  JH_REQUIRE(o_nominal >= 0 && o_sigma >= 0 && o_tp >= 0 && o_lohi >= 0, "%s: negative block offset", who);
+  const size_t need = sizeof(float) * (size_t)std::max(std::max(nx, o_nominal + KU), std::max(std::max(o_sigma + KU, o_tp + m->ntaskparam), o_lohi + 2 * m->nu));
+  JH_REQUIRE(blk_bytes >= need, "%s: a block of %zu bytes does not hold x0 | nominal | sigma | task params | bounds at the given offsets (%zu bytes)", who, blk_bytes, need);
+  JH_REQUIRE(blk_stride_bytes >= blk_bytes && blk_stride_bytes % sizeof(float) == 0, "%s: blk_stride_bytes = %zu is smaller than a block (%zu bytes) or no multiple of 4", who, blk_stride_bytes, blk_bytes);
+  JH_REQUIRE(noise_stride_floats >= (size_t)KU * (size_t)ldn, "%s: noise_stride_floats = %zu is smaller than a problem's noise (K*nu*ldn = %zu)", who, noise_stride_floats, (size_t)KU * (size_t)ldn);
+  JH_REQUIRE(out_stride_floats >= 2 * (size_t)KU, "%s: out_stride_floats = %zu is smaller than an output record (nominal | sigma = %zu floats)", who, out_stride_floats, 2 * (size_t)KU);
+  JH_REQUIRE(m->plan_step_launches != 1, "%s: one launch is forced (jh_model_set_plan_step_launches) but the ensemble's plan step is two launches", who);
+  const bool closed = m->kind == JH_TASK_CARTPOLE || m->kind == JH_TASK_CYLINDER_PUSH;
+  const jh_engine_build* eb = engine_build(m);
+  if (!closed && !(eb && eb->rollout_cost_batch)) { jh_set_error("%s: no batched kernel for this model", who); return JH_ERR_UNSUPPORTED; }
+  JH_REQUIRE((long long)B * M * N <= 0x7fffffffll, "%s: B * M * N = %lld rollouts exceed one launch", who, (long long)B * M * N);
+  unsigned* flag = (out_host_mark && out_host_mark != (void*)out) ? (unsigned*)out_host_mark : nullptr;  // (out_host_mark == out: the stream's event)
+  const float* b = (const float*)blk_dev;
+  jh_upd::TailArgs a;  // (controller 0's record; the tail's own checks before anything is enqueued: mode, lambda, k)
+  if (int rc = jh_update_tail_args(who, costs, nullptr, b + o_nominal, noise, ldn, b + o_sigma, b + o_lohi, N, 0, K, m->nu, mode, lambda, k, tie_high, 0, nullptr, 0, 0, scratch, out, out + KU,
+                                   nullptr, nullptr, &a)) return rc;
+  hipStream_t st = (hipStream_t)stream;
+  if (blk_dev != blk_host) { if (int rc = jh_upload_async(blk_dev, blk_host, (size_t)(B - 1) * blk_stride_bytes + blk_bytes, stream)) return rc; }
+  if (timing) JH_HIP(hipEventRecord((hipEvent_t)timing[0], st));
+  const unsigned expect = flag ? __atomic_load_n(flag, __ATOMIC_RELAXED) + 1u : 0u;
+  const long long blk_c = (long long)(blk_stride_bytes / sizeof(float)), image_c = set->B == M ? 0ll : (long long)M * (long long)set->stride;
+  const int* ints = set->tables ? m->d_i : set->d_i_plain;
+  int rc = JH_OK;
+  if (closed) {
+    jh_upd::TailArgs ra = a;  // the rollout kernel's view: pair (c, b)'s costs lie (c * M + b) * N behind member_costs, the block and the noise are the controller's
+    ra.costs = member_costs; ra.done_flag = nullptr; ra.done_value = 0u;
+    jh_upd::BatchArgs s;
+    s.B = M; s.blk = 0; s.noise = 0; s.costs = N; s.trace = 0; s.scratch = 0; s.out = 0; s.counter = nullptr; s.done_flag = nullptr; s.done_value = 0u; s.image = (long long)set->stride;
+    jh_upd::ControllerAxis z;
+    z.C = B; z.blk = blk_c; z.noise = (long long)noise_stride_floats; z.image = image_c;
+    rc = jh_simple_rollout_cost_batch(m, set->d_images, b, b + o_tp, W, H, K, ra, s, st, z);
+  } else {
+    const jh_rollout_args ra = {b, b + o_nominal, noise, ldn, b + o_sigma, W, b + o_lohi, b + o_tp, 0, N, 0, H, K, member_costs, nullptr, nullptr};
+    const jh_rollout_batch rb = {set->d_images, (long long)set->stride, ints, M, 0, 0, B, blk_c, (long long)noise_stride_floats, image_c};
+    rc = eb->rollout_cost_batch(m, ra, rb, st);
+  }
+  if (rc == JH_OK && timing) JH_HIP(hipEventRecord((hipEvent_t)timing[1], st));
+  jh_upd::BatchArgs s;  // the tail's axis: the controllers
+  s.B = B; s.blk = blk_c; s.noise = (long long)noise_stride_floats; s.costs = N; s.trace = 0; s.scratch = (long long)jh_update_fused_scratch_floats(N, K, m->nu); s.out = (long long)out_stride_floats;
+  s.counter = reinterpret_cast<unsigned*>(scratch) + 1; s.done_flag = flag; s.done_value = expect;
+  jh_upd::EnsembleBatchArgs e;
+  e.member_costs = member_costs; e.costs = costs; e.M = M; e.stride = (long long)N;
+  for (int i = 0; i < JH_MAX_ENSEMBLE_FLEET; i++) e.worst[i] = (unsigned char)(i < B ? worst[i] : 1);
+  if (rc == JH_OK) rc = jh_update_tail_ensemble_batch_launch(a, s, e, st);
+  if (rc == JH_OK && timing) JH_HIP(hipEventRecord((hipEvent_t)timing[2], st));
+  if (rc == JH_OK) rc = download_begin(out, out, 0, stream, flag, expect);
+  return rc;
+}
+
 // The update alone for B problems whose costs are given (the materialise path of a fleet: the Spot policy rollout, judo_amd/fleet.py): jh_plan_step_batch's last stage --
 // k_update_tail_batch with the two-level ticket -- and its completion mark, without an upload or a rollout kernel in front.
 extern "C" int jh_update_fused_batch(int B, const float* costs, const float* blk, size_t blk_stride_floats, int o_nominal, int o_sigma, int o_lohi, const float* noise, int ldn,

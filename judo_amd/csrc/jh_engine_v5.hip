@@ -92,7 +92,12 @@ constexpr int CVX_STOP_NM = 1000;   // the stop of the cylinder build's GJK + EP
 constexpr int PARK_F = 5 * 64;
 // An explicit schedule of horizon slices (jh_model_set_rollout_slice_bounds, and the automatic taper): sixteen 16-bit step indices, two to a word, passed to the kernel by
 // value -- entry s is the step behind slice s's last, entries from the last slice on hold H -- and read from the kernel arguments with a uniform load, once per unit.
+// A batched launch has no queue and no slices: when it has a controller axis (jh_plan_step_ensemble_batch) the same eight words carry that axis's three strides --
+// block, noise, image, in floats, each as a low and a high word -- so the kernel's argument list, and with it the argument offsets of every other instantiation, stays
+// what it was.
 struct SliceBounds { unsigned w[8]; };
+__host__ __device__ inline long long axis_stride(const SliceBounds& sb, int i) { return (long long)(((unsigned long long)sb.w[2 * i + 1] << 32) | sb.w[2 * i]); }
+inline void set_axis_stride(SliceBounds& sb, int i, long long v) { sb.w[2 * i] = (unsigned)((unsigned long long)v & 0xffffffffull); sb.w[2 * i + 1] = (unsigned)((unsigned long long)v >> 32); }
 constexpr int MAX_BOUND_SLICES = 16;
 #define PARK_LD(p) __hip_atomic_load((p), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT)
 #define PARK_ST(p, v) __hip_atomic_store((p), (v), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT)
@@ -469,11 +474,14 @@ __global__ __launch_bounds__(WAVE * WPB, WAVES_PER_EU) void k_leap_v5(const floa
                                                    long long batch_blk, long long batch_noise, long long batch_image, unsigned* pflags, int slices_, SliceBounds sb_) {
   static_assert(!BATCH || (!MATERIALIZE && !PERSIST), "batched launches are fused launches on the static grid");
   if constexpr (BATCH) {
-    const long long pb = blockIdx.y;
-    x0 += pb * batch_blk; nominal += pb * batch_blk; sigma += pb * batch_blk; lohi += pb * batch_blk; tp += pb * batch_blk;
-    noise += pb * batch_noise; costs += pb * N; gF += pb * batch_image;
-    if (trace) trace += pb * N * H * 15;
-    if (NOVF > 0 && ovf_all_) ovf_all_ += pb * N * (NOVF * POOL_F);  // (the overflow rows are indexed by rollout: a problem's N rows behind the one before)
+    // blockIdx.z: the controller of jh_plan_step_ensemble_batch, whose M plants are the problems of blockIdx.y -- strides of its own in sb_ (all 0 and gridDim.z == 1 for
+    // every other batched launch); `pr`: the (controller, problem) pair, which owns the costs, trace and overflow rows
+    const long long pb = blockIdx.y, pc = blockIdx.z, pr = pc * gridDim.y + pb;
+    const long long ob = pb * batch_blk + pc * axis_stride(sb_, 0);
+    x0 += ob; nominal += ob; sigma += ob; lohi += ob; tp += ob;
+    noise += pb * batch_noise + pc * axis_stride(sb_, 1); costs += pr * N; gF += pb * batch_image + pc * axis_stride(sb_, 2);
+    if (trace) trace += pr * N * H * 15;
+    if (NOVF > 0 && ovf_all_) ovf_all_ += pr * N * (NOVF * POOL_F);  // (the overflow rows are indexed by rollout: a problem's N rows behind the one before)
   }
   __shared__ RS sRS[RPW * WPB];
   __shared__ float sBody[16 * BFS];
@@ -2037,12 +2045,14 @@ static int materialize(const jh_model* m, const float* x0, int x0_batched, const
 // not depend on it), and there is no queue.
 static int rollout_cost_batch(const jh_model* m, const jh_rollout_args& a, const jh_rollout_batch& s, hipStream_t st) {
   if (int rc = leap_refusal(m, "plan_step_batch")) return rc;
-  JH_REQUIRE((long long)s.B * a.N <= 0x7fffffffll, "plan_step_batch: B * N = %lld rollouts exceed one launch", (long long)s.B * a.N);
-  LeapArgs k = leap_args(m, a, s.images, s.ints, s.B * a.N);
+  const long long rollouts = (long long)s.C * s.B * a.N;  // (s.C: the controller axis of jh_plan_step_ensemble_batch, 1 everywhere else)
+  JH_REQUIRE(s.C >= 1 && s.C <= 65535 && rollouts <= 0x7fffffffll, "plan_step_batch: B * N = %lld rollouts exceed one launch", rollouts);
+  LeapArgs k = leap_args(m, a, s.images, s.ints, (int)rollouts);
   k.batch_blk = s.blk_stride; k.batch_noise = s.noise_stride; k.batch_image = s.image_stride;
-  if (const size_t b = ovf_bytes((size_t)s.B * a.N)) k.ovf = jh_launch_scratch(m, b, st);  // (every problem's rows; nullptr: the LDS capacity alone, drops and the fallback counted)
-  if (hand_contacts(m)) launch<false, true, false, true>(k, dim3(k.grid, s.B), st);
-  else launch<false, false, false, true>(k, dim3(k.grid, s.B), st);
+  set_axis_stride(k.sb, 0, s.blk_stride_c); set_axis_stride(k.sb, 1, s.noise_stride_c); set_axis_stride(k.sb, 2, s.image_stride_c);
+  if (const size_t b = ovf_bytes((size_t)rollouts)) k.ovf = jh_launch_scratch(m, b, st);  // (every problem's rows; nullptr: the LDS capacity alone, drops and the fallback counted)
+  if (hand_contacts(m)) launch<false, true, false, true>(k, dim3(k.grid, s.B, s.C), st);
+  else launch<false, false, false, true>(k, dim3(k.grid, s.B, s.C), st);
   return jh_launch_done(k.ovf, st);
 }
 

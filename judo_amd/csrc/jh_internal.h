@@ -117,10 +117,13 @@ struct jh_rollout_args {
 };
 // What the leap kernel's launch for B problems (jh_plan_step_batch) takes on top: the record is problem 0's, `blk_stride` / `noise_stride` floats lead to the next problem's;
 // `images`: problem 0's float section, `image_stride` floats to the next problem's (m->d_f and 0: one image for all); `ints`: the int section on the device (m->d_i, or a
-// model set's copy without the hand's pair tables)
+// model set's copy without the hand's pair tables).  `C` > 1 (jh_plan_step_ensemble_batch): the launch has a controller axis in front of the problems -- the grid is
+// (groups, B, C), controller c's blocks, noise and images lie c times the `*_stride_c` floats behind controller 0's, and the (controller, problem) pair c * B + b owns the
+// costs, trace and overflow rows.  The default is the launch without that axis.
 struct jh_rollout_batch {
   const float* images; long long image_stride; const int* ints;
   int B; long long blk_stride, noise_stride;
+  int C = 1; long long blk_stride_c = 0, noise_stride_c = 0, image_stride_c = 0;
 };
 
 // One build of an articulated product kernel: each translation unit that instantiates k_leap_v5 or k_fr3_v6 defines its row, and jh_api.hip's engine_build() maps a model

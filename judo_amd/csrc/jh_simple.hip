@@ -250,11 +250,12 @@ __global__ __launch_bounds__(jh_upd::kUB) void k_plan_step_batch(const float* __
 // ... and the rollout + cost kernel alone for B problems: the first of the two launches where the one-launch form does not fit or is switched off (k_update_tail_batch follows)
 template <class T>
 __global__ __launch_bounds__(kBlock) void k_rollout_cost_batch(const float* __restrict__ P, const float* __restrict__ x0, const float* __restrict__ W, const float* __restrict__ tp, int H, int K,
-                                                               jh_upd::TailArgs base, jh_upd::BatchArgs s) {
-  const int b = blockIdx.y;
-  const jh_upd::TailArgs a = jh_upd::batch_problem(base, s, b);
-  rollout_cost_body<T, kBlock>(P + b * s.image, x0 + b * s.blk, a.src.nominal, a.src.noise, a.src.ldn, a.src.sigma, W, a.src.lohi, tp + b * s.blk, a.N, a.n_offset, H, K, const_cast<float*>(a.costs), nullptr,
-                               const_cast<float*>(a.trace));
+                                                               jh_upd::TailArgs base, jh_upd::BatchArgs s, jh_upd::ControllerAxis z) {
+  // (blockIdx.z: the controller of jh_plan_step_ensemble_batch, whose members are the problems of blockIdx.y; every other launch has gridDim.z == 1 and z's offsets are 0)
+  const int b = blockIdx.y, c = blockIdx.z;
+  const jh_upd::TailArgs a = jh_upd::batch_controller(jh_upd::batch_problem(base, s, b), s, z, c, (int)gridDim.y);
+  rollout_cost_body<T, kBlock>(P + b * s.image + c * z.image, x0 + b * s.blk + c * z.blk, a.src.nominal, a.src.noise, a.src.ldn, a.src.sigma, W, a.src.lohi, tp + b * s.blk + c * z.blk, a.N, a.n_offset, H, K,
+                               const_cast<float*>(a.costs), nullptr, const_cast<float*>(a.trace));
 }
 #ifdef JH_TAIL_TICKS
 __global__ void k_tail_ticks_start() { if (threadIdx.x == 0) jh_upd::g_tail_ticks[8] = wall_clock64(); }
@@ -397,10 +398,10 @@ int launch_plan_step_batch(const float* P, const float* x0, const float* W, cons
 }
 
 template <class T>
-int launch_cost_batch(const float* P, const float* x0, const float* W, const float* tp, int H, int K, const jh_upd::TailArgs& a, const jh_upd::BatchArgs& s, hipStream_t st) {
+int launch_cost_batch(const float* P, const float* x0, const float* W, const float* tp, int H, int K, const jh_upd::TailArgs& a, const jh_upd::BatchArgs& s, const jh_upd::ControllerAxis& z, hipStream_t st) {
   size_t lds = sizeof(float) * ((size_t)H * K + (size_t)K * T::NU * kBlock + T::NP + T::NTP + T::NX);
   JH_REQUIRE(lds <= 64 * 1024, "plan_step_batch: H*K too large for the LDS staging (%zu bytes)", lds);
-  hipLaunchKernelGGL(k_rollout_cost_batch<T>, dim3((a.N + kBlock - 1) / kBlock, s.B), dim3(kBlock), lds, st, P, x0, W, tp, H, K, a, s);
+  hipLaunchKernelGGL(k_rollout_cost_batch<T>, dim3((a.N + kBlock - 1) / kBlock, s.B, z.C), dim3(kBlock), lds, st, P, x0, W, tp, H, K, a, s, z);
   JH_HIP(hipGetLastError());
   return JH_OK;
 }
@@ -411,9 +412,10 @@ int jh_simple_plan_step_batch(const jh_model* m, const float* P, const float* x0
   if (m->kind == JH_TASK_CARTPOLE) return launch_plan_step_batch<Cartpole>(P, x0, W, tp, H, K, a, s, st);
   return launch_plan_step_batch<CylinderPush>(P, x0, W, tp, H, K, a, s, st);
 }
-int jh_simple_rollout_cost_batch(const jh_model* m, const float* P, const float* x0, const float* tp, const float* W, int H, int K, const jh_upd::TailArgs& a, const jh_upd::BatchArgs& s, hipStream_t st) {
-  if (m->kind == JH_TASK_CARTPOLE) return launch_cost_batch<Cartpole>(P, x0, W, tp, H, K, a, s, st);
-  return launch_cost_batch<CylinderPush>(P, x0, W, tp, H, K, a, s, st);
+int jh_simple_rollout_cost_batch(const jh_model* m, const float* P, const float* x0, const float* tp, const float* W, int H, int K, const jh_upd::TailArgs& a, const jh_upd::BatchArgs& s, hipStream_t st,
+                                 const jh_upd::ControllerAxis& z) {
+  if (m->kind == JH_TASK_CARTPOLE) return launch_cost_batch<Cartpole>(P, x0, W, tp, H, K, a, s, z, st);
+  return launch_cost_batch<CylinderPush>(P, x0, W, tp, H, K, a, s, z, st);
 }
 
 // can the plan step of this model run as one launch?  (closed-form models; the knots of a workgroup of 256 rollouts must fit the LDS staging next to the update's own 9 KB)

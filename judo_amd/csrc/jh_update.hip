@@ -524,3 +524,24 @@ int jh_update_tail_ensemble_launch(const TailArgs& a, const EnsembleArgs& e, hip
   JH_HIP(hipGetLastError());
   return JH_OK;
 }
+
+// ------------------------------------------------------------------------------------------------ B ensemble controllers in one launch
+// (Defined behind everything else, for the reason above.)  What jh_plan_step_ensemble_batch launches behind the rollout kernel on the grid (workgroups, M, B):
+// blockIdx.y picks the controller.  A workgroup derives the controller's record, writes the aggregated costs of its own rollouts from the controller's slab of member
+// costs with the controller's `worst`, and runs the tail unchanged; batch_done is the two-level ticket and the one completion word of the batched plan step.
+namespace {
+__global__ __launch_bounds__(kUB) void k_update_tail_ensemble_batch(TailArgs base, BatchArgs s, EnsembleBatchArgs e) {
+  const int b = blockIdx.y;
+  const TailArgs a = batch_problem(base, s, b);
+  const int r = blockIdx.x * kUB + threadIdx.x;
+  if (r < a.N) e.costs[b * s.costs + r] = ensemble_cost(e.member_costs + (long long)b * e.M * e.stride, e.M, e.stride, r, (int)e.worst[b]);
+  __syncthreads();  // (a thread reads back the cost it wrote, as in k_update_tail_ensemble)
+  batch_done(s, update_tail_body(a));
+}
+}  // namespace
+
+int jh_update_tail_ensemble_batch_launch(const TailArgs& a, const BatchArgs& s, const EnsembleBatchArgs& e, hipStream_t st) {
+  hipLaunchKernelGGL(k_update_tail_ensemble_batch, dim3((a.N + kUB - 1) / kUB, s.B), dim3(kUB), 0, st, a, s, e);
+  JH_HIP(hipGetLastError());
+  return JH_OK;
+}

@@ -395,6 +395,30 @@ __device__ __forceinline__ float ensemble_cost(const float* __restrict__ member_
   return __fdiv_rn(acc, (float)worst);
 }
 
+// ---------------------------------------------------------------- B ensemble controllers in one launch (jh_plan_step_ensemble_batch)
+// The rollout launch has a third grid dimension: blockIdx.y stays the member (the problem axis above, block and noise strides 0, the set's image stride) and blockIdx.z
+// is the controller, with strides of its own -- `blk` / `noise` floats from a controller's packed block / noise to the next one's, `image` floats from its plant 0 to the
+// next controller's (0: every controller plans against the same M plants).  What a (controller, member) pair owns alone -- its row of costs, the leap kernel's overflow
+// and trace rows -- is indexed by blockIdx.z * gridDim.y + blockIdx.y.  A record of its own, not more fields of BatchArgs: BatchArgs is a kernel argument of
+// k_plan_step_batch and k_update_tail_batch, whose argument layout -- and with it the place of the hidden arguments they read gridDim from -- stays what it was.
+// The default is a launch without a controller axis (gridDim.z == 1, every offset 0).
+struct ControllerAxis {
+  int C = 1;
+  long long blk = 0, noise = 0, image = 0;
+};
+// the (controller, member) pair's record from the member's (batch_problem with blockIdx.y): wave-uniform arithmetic on kernel arguments and block indices
+__device__ __forceinline__ TailArgs batch_controller(TailArgs a, const BatchArgs& s, const ControllerAxis& z, int c, int members) {
+  a.costs += (long long)c * members * s.costs; a.src.nominal += c * z.blk; a.src.sigma += c * z.blk; a.src.lohi += c * z.blk; a.src.noise += c * z.noise;
+  return a;
+}
+// The tail of that call, grid (tail workgroups, B): controller b's record is batch_problem's -- `s` carries the controllers' strides --, its M x N slab of member costs
+// lies b * M * stride behind controller 0's, and its `worst` travels in the kernel arguments, a byte per controller (M <= JH_MAX_ENSEMBLE fits one).
+struct EnsembleBatchArgs {
+  const float* member_costs; float* costs;  // B x M x stride in, B x s.costs out (`costs` is the base record's TailArgs::costs)
+  int M; long long stride;
+  unsigned char worst[JH_MAX_ENSEMBLE_FLEET];
+};
+
 }  // namespace jh_upd
 
 // jh_update.hip: the argument checks of jh_update_fused / jh_update_shard and the launch record of the tail (rec_out non-null: the shard form)
@@ -411,4 +435,8 @@ int jh_update_tail_batch_launch(const jh_upd::TailArgs& a, const jh_upd::BatchAr
 int jh_update_tail_ensemble_launch(const jh_upd::TailArgs& a, const jh_upd::EnsembleArgs& e, hipStream_t st);
 // (`P`: the float section of problem 0's model image, s.image floats to the next problem's -- m->d_f with s.image = 0 where the problems share the model)
 int jh_simple_plan_step_batch(const jh_model* m, const float* P, const float* x0, const float* W, const float* tp, int H, int K, const jh_upd::TailArgs& a, const jh_upd::BatchArgs& s, hipStream_t st);
-int jh_simple_rollout_cost_batch(const jh_model* m, const float* P, const float* x0, const float* tp, const float* W, int H, int K, const jh_upd::TailArgs& a, const jh_upd::BatchArgs& s, hipStream_t st);
+// (`z`: the controller axis of jh_plan_step_ensemble_batch, grid (workgroups, s.B, z.C); the default is the launch without one)
+int jh_simple_rollout_cost_batch(const jh_model* m, const float* P, const float* x0, const float* tp, const float* W, int H, int K, const jh_upd::TailArgs& a, const jh_upd::BatchArgs& s, hipStream_t st,
+                                 const jh_upd::ControllerAxis& z = {});
+// the ensemble fleet's tail (jh_plan_step_ensemble_batch): `a` is controller 0's record, `s` the controllers' strides and the two-level ticket; grid (tail workgroups, s.B)
+int jh_update_tail_ensemble_batch_launch(const jh_upd::TailArgs& a, const jh_upd::BatchArgs& s, const jh_upd::EnsembleBatchArgs& e, hipStream_t st);

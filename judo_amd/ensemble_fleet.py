@@ -1,0 +1,173 @@
+"""B ensemble controllers planned in ONE launch (`jh_plan_step_ensemble_batch`, include/judo_amd.h).
+
+An `EnsembleController` plans one nominal against M plants and plans alone: somebody with several robots -- or one robot swept over risk levels (`worst` = 1 ... M),
+goals or seeds -- makes B `jh_plan_step_ensemble` calls back to back, B launch chains and B waits for plan steps that each leave most of the GPU idle.  An
+`EnsembleFleet` holds B ordinary `EnsembleController` objects and runs their iteration as one call: the rollout kernel on the grid (workgroups, M, B), one aggregating
+tail on (tail workgroups, B), one completion mark.  It is `ControllerFleet`'s loop -- every member's host prelude into its slice of the fleet's pinned block, the batched
+noise draw, one library call, one `jh_download_end`, every member's epilogue -- around another call, and afterwards each member is bit for bit where its own
+`update_action()` would have left it.
+
+What the members share is what the launch shares: `ControllerFleet`'s fields (N, K, H, the spline order, the trace count, the optimizer kind and its scalar arguments),
+M, the kernel build, and a model image that differs from fleet member 0's plant 0 in the float section alone.  State, goal, seed, nominal, CEM sigma, `worst` and the
+plants themselves are a member's own.  Where all members' plants are byte-identical list for list the launch reads one set of M images; otherwise one of B * M."""
+
+from __future__ import annotations
+
+import ctypes as C
+from typing import Sequence
+
+import torch
+
+from judo_amd import _lib
+from judo_amd.device import GpuModelSet
+from judo_amd.distributed import world_info
+from judo_amd.ensemble import MAX_ENSEMBLE, EnsembleController, check_descriptions, make_ensemble_controller
+from judo_amd.fleet import ControllerFleet, _FleetBuffers
+from judo_amd.models import image_sections
+
+MAX_ENSEMBLE_FLEET = _lib.MAX_ENSEMBLE_FLEET
+
+
+def fleet_descriptions(B: int, descriptions: Sequence) -> list[list[dict]]:
+    """`descriptions` as B lists of M: either M descriptions, which every member plans against (the shared form: B times the same list), or B lists of M (the
+    per-member form).  Raises ValueError on anything else."""
+    if B < 1:
+        raise ValueError("a fleet needs at least one controller")
+    if B > MAX_ENSEMBLE_FLEET:
+        raise ValueError(f"a fleet of {B} ensemble controllers exceeds the {MAX_ENSEMBLE_FLEET} of a launch (include/judo_amd.h JH_MAX_ENSEMBLE_FLEET)")
+    descriptions = list(descriptions)
+    if not descriptions:
+        raise ValueError("an ensemble needs at least one description")
+    if all(isinstance(d, dict) for d in descriptions):
+        return [list(descriptions) for _ in range(B)]
+    if any(isinstance(d, dict) for d in descriptions):
+        raise ValueError("descriptions are either M model descriptions, shared by every member, or B lists of M: not a mixture of the two")
+    if len(descriptions) != B:
+        raise ValueError(f"{len(descriptions)} lists of descriptions for a fleet of {B}")
+    return [list(d) for d in descriptions]
+
+
+def fleet_worst(B: int, M: int, worst) -> list[int]:
+    """`worst` as B ints in [1, M]: None is the mean (M for every member), an int holds for every member, a sequence gives one per member."""
+    if worst is None:
+        out = [M] * B
+    elif isinstance(worst, (int,)) and not isinstance(worst, bool):
+        out = [int(worst)] * B
+    else:
+        out = [int(w) for w in worst]
+        if len(out) != B:
+            raise ValueError(f"{len(out)} values of worst for a fleet of {B}")
+    for i, w in enumerate(out):
+        if not 1 <= w <= M:
+            raise ValueError(f"fleet member {i}: worst = {w} outside [1, M = {M}]")
+    return out
+
+
+def check_fleet_descriptions(lists: Sequence[Sequence[dict]]) -> list[list[bytes]]:
+    """The admission rule of an ensemble fleet on descriptions alone, without a device: every member's list is an ensemble (`ensemble.check_descriptions`), all lists
+    hold the same number of plants, and every plant's image differs from fleet member 0's plant 0 in the float section alone.  Returns the packed images, list for
+    list; raises ValueError naming the member and the field."""
+    if len(lists) < 1:
+        raise ValueError("a fleet needs at least one controller")
+    blobs = []
+    for i, descs in enumerate(lists):
+        try:
+            blobs.append(check_descriptions(descs))
+        except ValueError as e:
+            raise ValueError(f"fleet member {i}: {e}") from None
+    M = len(blobs[0])
+    want = image_sections(blobs[0][0])
+    for i, mine in enumerate(blobs):
+        if len(mine) != M:
+            raise ValueError(f"fleet member {i} differs from member 0 in the number of plants M: {len(mine)} against {M}")
+        if i == 0 or mine[0] == blobs[0][0]:
+            continue  # (the member's other plants were held to its own plant 0 by check_descriptions)
+        for name, x, y in zip(("header", "float section", "int section"), image_sections(mine[0]), want):
+            if (x != y and name != "float section") or len(x) != len(y):
+                raise ValueError(f"fleet member {i} has another model image than member 0: the {name} of its plants' image differs")
+    return blobs
+
+
+class EnsembleFleet(ControllerFleet):
+    """B `EnsembleController`s of one task and optimizer kind whose plan steps run as one launch.  `fleet[i]` is an ordinary `EnsembleController`: `update_states`,
+    `optimizer.seed`, `action(t)`, `traces`, `rewards`, `member_costs`, the `worst` setter and `set_member` work per member as they do on a controller alone, and take
+    effect at the fleet's next plan step."""
+
+    _ensemble_members = True
+
+    def __init__(self, controllers: Sequence[EnsembleController]) -> None:
+        self._set_key: tuple = ()
+        self._member_costs: torch.Tensor | None = None  # (B, M, N): the members' `_member_costs` are views of it
+        if len(controllers) > MAX_ENSEMBLE_FLEET:
+            raise ValueError(f"a fleet of {len(controllers)} ensemble controllers exceeds the {MAX_ENSEMBLE_FLEET} of a launch (include/judo_amd.h JH_MAX_ENSEMBLE_FLEET)")
+        super().__init__(controllers)
+
+    def _check_member(self, i: int, c, first) -> None:
+        if not isinstance(c, EnsembleController):
+            raise ValueError(f"fleet member {i} is a {type(c).__name__}, not an EnsembleController: controllers that believe one plant share a launch in a ControllerFleet")
+        world, _ = world_info(c.group)
+        why = c._ensemble_refusal(world, c._current_normalizer())
+        if why is None and not c.uses_fused_optimizer:
+            why = "a plugin reward, hook or optimizer (uses_fused_cost is false): the members' costs come from the fused kernels alone"
+        if why is not None:
+            raise ValueError(f"fleet member {i} does not run its iteration as one ensemble plan step ({why}): only such controllers can share a launch")
+        if c.num_members != first.num_members:
+            raise ValueError(f"fleet member {i} differs from member 0 in the number of plants M: {c.num_members} against {first.num_members}")
+        want = None
+        for j, m in enumerate(c._members):  # every plant against fleet member 0's plant 0: one structure and one kernel build for the launch
+            if m is first.model or m._blob == first.model._blob:
+                continue
+            want = want or image_sections(first.model._blob)
+            for name, x, y in zip(("header", "float section", "int section"), image_sections(m._blob), want):
+                if (x != y and name != "float section") or len(x) != len(y):
+                    raise ValueError(f"fleet member {i}: plant {j} has another model image than member 0's plant 0: the {name} of its image differs")
+            if m.build() != first.model.build() or m.self_collision != first.model.self_collision:
+                raise ValueError(f"fleet member {i}: plant {j} has another kernel build than member 0's plant 0: the kernel build or the self-collision setting differs")
+        super()._check_member(i, c, first)
+
+    def _models(self) -> GpuModelSet:
+        """The plants of the launch: member 0's M where every member's plants are byte-identical to them, list for list; else all B * M, controller-major.  Rebuilt when
+        a member's plant was exchanged between plan steps (told by identity, as `ControllerFleet._models` tells it)."""
+        lists = [c._members for c in self.controllers]
+        key = tuple(m for plants in lists for m in plants)
+        if self._model_set is not None and len(key) == len(self._set_key) and all(a is b for a, b in zip(key, self._set_key)):
+            return self._model_set
+        shared = all(all(a is b or a._blob == b._blob for a, b in zip(plants, lists[0])) for plants in lists[1:])
+        self._model_set = GpuModelSet(list(lists[0]) if shared else list(key))
+        self._set_key = key
+        return self._model_set
+
+    def _trace_floats(self) -> int:
+        return 0  # (no trace buffer, as for the ensemble call: a member stages its trace elites' knots and re-rolls them on its plant 0)
+
+    def _launch(self, lib, model_set: GpuModelSet, fb: _FleetBuffers, in_place: bool, noise: torch.Tensor, W, N: int, H: int, K: int, nu: int, costs: torch.Tensor, nfl: int,
+                update_args: tuple, E_t: int, row: int, colmajor: int, stream) -> None:
+        cs = self.controllers
+        B, M = len(cs), cs[0].num_members
+        if self._member_costs is None or tuple(self._member_costs.shape) != (B, M, N):
+            self._member_costs = torch.empty((B, M, N), dtype=torch.float32, device=self.device)
+        for i, c in enumerate(cs):
+            c._member_costs = self._member_costs[i]
+        worst = (C.c_int * B)(*[c.worst for c in cs])
+        off = fb.offsets
+        mode, lam, k_el, tie = update_args
+        st = lib.jh_plan_step_ensemble_batch(model_set.handle, B, M, fb.host_ptr if in_place else fb.blk.data_ptr(), fb.host_ptr, 4 * fb.nblk, 4 * fb.blk_stride, off[1], off[2], off[3], off[4],
+                                             noise.data_ptr(), N, K * nu * N, _lib.ptr(W), N, H, K, self._member_costs.data_ptr(), costs.data_ptr(), worst, mode, lam, k_el, tie,
+                                             fb.scratch.data_ptr(), fb.out_host_ptr, fb.out_stride, fb.done.data_ptr() if in_place else fb.out_host_ptr, None, stream)
+        _lib.check(st, "jh_plan_step_ensemble_batch")
+
+
+def make_ensemble_fleet(task: str, optimizer: str, B: int, descriptions: Sequence, worst=None, device: torch.device | None = None) -> EnsembleFleet:
+    """B `make_ensemble_controller`s in one fleet.  `descriptions`: M model descriptions of the task, which every member plans against, or B lists of M, a member's own
+    plants (`models.scaled_description(task.desc, body_mass=..., geom_friction=..., actuator_kp=...)`); plant 0 of a list is that member's nominal plant.  `worst`: an
+    int for every member, a list of B, or None for the mean."""
+    lists = fleet_descriptions(B, descriptions)
+    check_fleet_descriptions(lists)
+    M = len(lists[0])
+    if M > MAX_ENSEMBLE:
+        raise ValueError(f"an ensemble of {M} members exceeds the {MAX_ENSEMBLE} of a launch (include/judo_amd.h JH_MAX_ENSEMBLE)")
+    js = fleet_worst(B, M, worst)
+    return EnsembleFleet([make_ensemble_controller(task, optimizer, lists[i], worst=js[i], device=device) for i in range(B)])
+
+
+__all__ = ["EnsembleFleet", "MAX_ENSEMBLE_FLEET", "check_fleet_descriptions", "fleet_descriptions", "fleet_worst", "make_ensemble_fleet"]

@@ -32,6 +32,7 @@ from judo_amd import _lib
 from judo_amd.controller import POLICY_OUTPUT_DIM, Controller, make_controller_for
 from judo_amd.device import GpuModelSet, current_stream_ptr
 from judo_amd.distributed import world_info
+from judo_amd.ensemble import EnsembleController
 from judo_amd.models import image_sections, layout
 from judo_amd.optimizers import Optimizer, _NoiseStream
 from judo_amd.tasks import get_registered_tasks
@@ -110,7 +111,12 @@ class _FleetBuffers:
 
 class ControllerFleet:
     """B controllers of one task and optimizer kind whose plan steps run as one launch.  `fleet[i]` is an ordinary `Controller`: `update_states`,
-    `system_metadata`, `optimizer.seed`, `optimizer.injected_noise`, `action(t)`, `traces`, `rewards` work per member as they do on a controller alone."""
+    `system_metadata`, `optimizer.seed`, `optimizer.injected_noise`, `action(t)`, `traces`, `rewards` work per member as they do on a controller alone.
+
+    `update_action` is the one loop of every fleet whose iteration is a library call; a subclass with another call (`judo_amd.ensemble_fleet.EnsembleFleet`) replaces
+    `_check_member`, `_models`, `_trace_floats` and `_launch` and keeps the loop."""
+
+    _ensemble_members = False  # members are `EnsembleController`s, each planning against M plants (EnsembleFleet)
 
     def __init__(self, controllers: Sequence[Controller]) -> None:
         self.controllers = list(controllers)
@@ -132,7 +138,7 @@ class ControllerFleet:
                 c.rollout_backend.engine, c.rollout_backend.policy = first.rollout_backend.engine, first.rollout_backend.policy
             self._policy_out: torch.Tensor | None = None  # (B * n, 12): the members' `_last_policy_output` are views of it
         for c in self.controllers[1:]:  # one image of the model constants on the device for every member whose image is member 0's, byte for byte
-            if c.model is not self.model and c.model._blob == self.model._blob:
+            if not self._ensemble_members and c.model is not self.model and c.model._blob == self.model._blob:
                 c.model = c.task._gpu = c.rollout_backend.model = self.model
         self._model_set: GpuModelSet | None = None  # members with images of their own (randomised physics): their float sections side by side, made at the first plan step
         self._bufs: _FleetBuffers | None = None
@@ -164,6 +170,10 @@ class ControllerFleet:
                 "default_policy_command": np.asarray(t.default_policy_command).tolist()}
 
     def _check_member(self, i: int, c: Controller, first: Controller) -> None:
+        if isinstance(c, EnsembleController) and not self._ensemble_members:
+            # (its iteration shape reads "plan_step", but the batched plan step would run on `c.model`, plant 0 alone, and drop the ensemble without a word)
+            raise ValueError(f"fleet member {i} is an EnsembleController: a ControllerFleet plans every member on one plant; ensemble controllers share a launch in an "
+                             "EnsembleFleet (judo_amd.ensemble_fleet.make_ensemble_fleet)")
         if c.model is not None and c.model.desc.get("family", c.model.task) == "fr3_pick":
             raise ValueError(f"fleet member {i}: fr3_pick has no batched plan step (its phase is chosen per problem on the host)")
         if c.device != first.device:
@@ -263,7 +273,7 @@ class ControllerFleet:
         states: list[dict[str, Any]] = [dict(E=E, x0=p[9], new_times=p[10]) for p in plans]
         nominal_n = [p[7] for p in plans]
         mode, lam, k_el, tie = first.optimizer.fused_update_args()
-        nfl = first._fused_trace_floats()
+        nfl = self._trace_floats()
         colmajor = int(first._trace_colmajor) if nfl else 0
         iters, staged = 0, False
         while iters < first.max_opt_iters and not any(c.optimizer.stop_cond() for c in cs):
@@ -281,17 +291,7 @@ class ControllerFleet:
             E_t = min(E, _lib.MAX_ELITES) if (last and nfl) else 0
             fb.size_out(2 * K * nu + E_t * (2 + row))
             in_place = self.model.closed_form  # (the closed-form kernels read the host blocks in place and the host polls the completion word; the leap family uploads and keeps the stream's event)
-            off = fb.offsets
-            if model_set is not None:  # a model image per problem: the same call without the model and B, which the set holds
-                st = lib.jh_plan_step_batch_models(model_set.handle, fb.host_ptr if in_place else fb.blk.data_ptr(), fb.host_ptr, 4 * fb.nblk, 4 * fb.blk_stride, off[1], off[2], off[3], off[4],
-                                                   noise.data_ptr(), N, K * nu * N, _lib.ptr(W), N, H, K, costs.data_ptr(), fb.trace_buf.data_ptr() if nfl else None, mode, lam, k_el, tie,
-                                                   E_t, row, colmajor, fb.scratch.data_ptr(), fb.out_host_ptr, fb.out_stride, fb.done.data_ptr() if in_place else fb.out_host_ptr, None, stream)
-                _lib.check(st, "jh_plan_step_batch_models")
-            else:
-                st = lib.jh_plan_step_batch(self.model.handle, B, fb.host_ptr if in_place else fb.blk.data_ptr(), fb.host_ptr, 4 * fb.nblk, 4 * fb.blk_stride, off[1], off[2], off[3], off[4],
-                                            noise.data_ptr(), N, K * nu * N, _lib.ptr(W), N, H, K, costs.data_ptr(), fb.trace_buf.data_ptr() if nfl else None, mode, lam, k_el, tie, E_t,
-                                            row, colmajor, fb.scratch.data_ptr(), fb.out_host_ptr, fb.out_stride, fb.done.data_ptr() if in_place else fb.out_host_ptr, None, stream)
-                _lib.check(st, "jh_plan_step_batch")
+            self._launch(lib, model_set, fb, in_place, noise, W, N, H, K, nu, costs, nfl, (mode, lam, k_el, tie), E_t, row, colmajor, stream)
             _lib.check(lib.jh_download_end(), "jh_download_end")
             for i, (c, mb, shard, st_i) in enumerate(zip(cs, fb.members, shards, states)):
                 mb.blk_stale = in_place
@@ -306,6 +306,26 @@ class ControllerFleet:
         for c, mb, p, st_i, n_n in zip(cs, fb.members, plans, states, nominal_n):
             c._end_plan(p, mb, st_i, n_n, iters, staged, stream)
 
+    def _trace_floats(self) -> int:
+        """Trace floats per step that the fleet's rollout kernel writes for every rollout; 0: none, and the members re-roll their trace elites when the traces are read."""
+        return self.controllers[0]._fused_trace_floats()
+
+    def _launch(self, lib, model_set: GpuModelSet | None, fb: _FleetBuffers, in_place: bool, noise: torch.Tensor, W, N: int, H: int, K: int, nu: int, costs: torch.Tensor, nfl: int,
+                update_args: tuple, E_t: int, row: int, colmajor: int, stream) -> None:
+        """The one library call of an iteration: B plan steps on the fleet's buffers, with the completion mark that `jh_download_end` then waits for."""
+        B = len(self.controllers)
+        off = fb.offsets
+        mode, lam, k_el, tie = update_args
+        if model_set is not None:  # a model image per problem: the same call without the model and B, which the set holds
+            st = lib.jh_plan_step_batch_models(model_set.handle, fb.host_ptr if in_place else fb.blk.data_ptr(), fb.host_ptr, 4 * fb.nblk, 4 * fb.blk_stride, off[1], off[2], off[3], off[4],
+                                               noise.data_ptr(), N, K * nu * N, _lib.ptr(W), N, H, K, costs.data_ptr(), fb.trace_buf.data_ptr() if nfl else None, mode, lam, k_el, tie,
+                                               E_t, row, colmajor, fb.scratch.data_ptr(), fb.out_host_ptr, fb.out_stride, fb.done.data_ptr() if in_place else fb.out_host_ptr, None, stream)
+            _lib.check(st, "jh_plan_step_batch_models")
+        else:
+            st = lib.jh_plan_step_batch(self.model.handle, B, fb.host_ptr if in_place else fb.blk.data_ptr(), fb.host_ptr, 4 * fb.nblk, 4 * fb.blk_stride, off[1], off[2], off[3], off[4],
+                                        noise.data_ptr(), N, K * nu * N, _lib.ptr(W), N, H, K, costs.data_ptr(), fb.trace_buf.data_ptr() if nfl else None, mode, lam, k_el, tie, E_t,
+                                        row, colmajor, fb.scratch.data_ptr(), fb.out_host_ptr, fb.out_stride, fb.done.data_ptr() if in_place else fb.out_host_ptr, None, stream)
+            _lib.check(st, "jh_plan_step_batch")
 
     # ---- the plan step of the Spot policy tasks ------------------------------------------------------------------------------------------------------
     def _load_carry(self, B: int, n: int) -> torch.Tensor:
