@@ -48,6 +48,7 @@ enum jh_spline_kind { JH_SPLINE_ZERO = 0, JH_SPLINE_LINEAR = 1, JH_SPLINE_CUBIC 
 #define JH_MAX_ELITES 32
 #define JH_MAX_ENSEMBLE 32 /* members of a model set that jh_plan_step_ensemble plans against */
 #define JH_MAX_ENSEMBLE_FLEET 256 /* controllers of one jh_plan_step_ensemble_batch call (their `worst` travel in the kernel arguments, a byte each) */
+#define JH_MAX_PLANT_BLOCKS 64 /* rollout blocks of one jh_plan_step_randomized call (their plants travel in the kernel arguments, a byte each) */
 
 const char* jh_last_error(void);
 int jh_version(void);
@@ -382,6 +383,27 @@ int jh_plan_step_ensemble_batch(const jh_model_set* set, int B, int M, void* blk
                                 int o_lohi, const float* noise, int ldn, size_t noise_stride_floats, const float* W, int N, int H, int K, float* member_costs /* DEVICE, B x M x N */,
                                 float* costs /* DEVICE, B x N */, const int* worst /* HOST, B */, int mode, float lambda, int k, int tie_high, float* scratch, float* out, size_t out_stride_floats,
                                 void* out_host_mark, void* const* timing, void* stream);
+/* ONE domain-randomised plan step (MPPI / CEM / PS with a plant drawn per rollout; the reference has no counterpart): one controller, one nominal spline, N candidates,
+ * each rolled out on ONE member of a model set, M <= JH_MAX_ENSEMBLE, and the update on the N costs as they are -- the rollouts of a plain plan step, never fitted to one
+ * plant.  The rule, fixed here so that it can be tested bit for bit: the N candidates form G contiguous blocks of Nb = N / G rollouts (N % G == 0), block g is rollouts
+ * [g * Nb, (g + 1) * Nb) and runs on plant plant_of_block[g], 0 <= plant < M.  1 <= G <= JH_MAX_PLANT_BLOCKS; G may exceed M, and a plant named by several blocks carries
+ * that share of the candidates (this is how weights are expressed); G = 1 is a plain plan step on that plant.
+ *   costs            the cost of rollout r is bit for bit costs[r] of jh_plan_step on the handle of plant plant_of_block[r / Nb] with the same block, noise (pitch ldn,
+ *                    column r), W, N, H and K
+ *   noise            global rollout 0 is the noise-free nominal, as everywhere else; the first rollout of every later block carries its noise
+ *   update           out = [nominal K*nu | sigma K*nu] is bit for bit what jh_update_fused writes for those N costs
+ *   plant_of_block   a HOST array of G bytes, read before the call returns: the values travel in the kernel arguments, so another assignment for the next plan step costs
+ *                    no copy and no launch
+ * Two launches for every model, as for jh_plan_step_ensemble: the batched rollout kernel on the grid (workgroups of Nb rollouts, G) -- the block stride 0, the noise, cost
+ * and rollout-index strides Nb, the image from the table; the leap kernel's latency mode is chosen from the N rollouts of the launch, as the single call chooses it; no queue
+ * and no horizon slices --, then the one-problem update tail on `costs`.  The completion mark, the scratch (jh_update_fused_scratch_floats(N, K, nu) floats, ZERO before the
+ * first use; every launch leaves the ticket at zero), the int section and the counters (member 0's handle) are jh_plan_step_ensemble's; no trace buffer and no knots_out.
+ * Everything is checked before anything is enqueued.  JH_ERR_INVALID, with jh_last_error naming the argument: what jh_plan_step_ensemble refuses (each null pointer by
+ * name, plant_of_block included), G outside 1..JH_MAX_PLANT_BLOCKS, N % G != 0, an entry of the table >= M (named with its block).  JH_ERR_UNSUPPORTED: as
+ * jh_plan_step_ensemble. */
+int jh_plan_step_randomized(const jh_model_set* set, void* blk_dev, const void* blk_host, size_t blk_bytes, int o_nominal, int o_sigma, int o_tp, int o_lohi, const float* noise, int ldn,
+                            const float* W, int N, int H, int K, const unsigned char* plant_of_block /* HOST, G */, int G, float* costs /* DEVICE, N */, int mode, float lambda, int k,
+                            int tie_high, float* scratch, float* out /* nominal | sigma */, void* out_host_mark, void* const* timing, void* stream);
 /* The noise of those B problems in one launch (judo/optimizers/{mppi.py:52,ps.py:43,cem.py:67}, one np.random.randn per controller): problem b's (rows, ldn) slice of `out`
  * (B x rows x ldn floats) is bit for bit what jh_noise_normal(seeds[b], draws[b], rows, 0, n_local, out + b * rows * ldn, ldn) writes; columns n_local .. ldn - 1 are left
  * alone.  seeds / draws: HOST arrays of B entries, read before the call returns (one launch per 256 problems: the pairs travel as kernel arguments). */

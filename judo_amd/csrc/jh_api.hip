@@ -874,7 +874,73 @@ extern "C" int jh_plan_step_ensemble(const jh_model_set* set, void* blk_dev, con
   return rc;
 }
 
-// B of those plan steps as ONE call (include/judo_amd.h): B controllers, each with its own block, noise, `worst`, costs and output record, each against M plants.  The
+// ONE domain-randomised plan step (include/judo_amd.h): the N candidates of one problem in G blocks of Nb = N / G, block g on plant plant_of_block[g] of the set.  The
+// batched rollout kernels on grid (workgroups of Nb rollouts, G): the block stride 0 -- every block reads the one packed block --, the noise and cost strides Nb -- block
+// g's columns of the one noise matrix (pitch ldn) and its slice of `costs` --, the plant axis (jh_internal.h) with the rollout-index stride Nb -- only global rollout 0
+// drops its noise -- and the table, which travels in the kernel arguments.  Then the single call's own tail on the N costs.  The checks are the ensemble call's.
+extern "C" int jh_plan_step_randomized(const jh_model_set* set, void* blk_dev, const void* blk_host, size_t blk_bytes, int o_nominal, int o_sigma, int o_tp, int o_lohi, const float* noise, int ldn,
+                                       const float* W, int N, int H, int K, const unsigned char* plant_of_block, int G, float* costs, int mode, float lambda, int k, int tie_high, float* scratch,
+                                       float* out, void* out_host_mark, void* const* timing, void* stream) {
+  const char* who = "plan_step_randomized";
+#define JH_RND_PTR(p) JH_REQUIRE((p) != nullptr, "%s: " #p " is a null pointer", who)
+  JH_RND_PTR(set); JH_RND_PTR(blk_dev); JH_RND_PTR(blk_host); JH_RND_PTR(noise); JH_RND_PTR(W); JH_RND_PTR(plant_of_block); JH_RND_PTR(costs); JH_RND_PTR(scratch); JH_RND_PTR(out);
+#undef JH_RND_PTR
+  const jh_model* m = set->m0;
+  const int M = set->B;
+  JH_REQUIRE(M <= JH_MAX_ENSEMBLE, "%s: a set of %d members exceeds JH_MAX_ENSEMBLE = %d", who, M, JH_MAX_ENSEMBLE);
+  JH_REQUIRE(G >= 1 && G <= JH_MAX_PLANT_BLOCKS, "%s: G = %d outside [1, JH_MAX_PLANT_BLOCKS = %d]", who, G, JH_MAX_PLANT_BLOCKS);
+  if (m->kind == JH_TASK_FR3_PICK) { jh_set_error("%s: fr3_pick has no batched plan step (its phase is chosen per problem on the host)", who); return JH_ERR_UNSUPPORTED; }
+  if (m->kind == JH_TASK_LEAP_CUBE && m->kernel_gen != 3) { jh_set_error("%s: only kernel generation 3 of the leap family has a batched launch (this model runs %d)", who, m->kernel_gen); return JH_ERR_UNSUPPORTED; }
+  JH_REQUIRE(N > 0 && H > 0 && K >= 1, "%s: N, H, K must be positive (N=%d H=%d K=%d)", who, N, H, K);
+  JH_REQUIRE(N % G == 0, "%s: N = %d is no multiple of G = %d (the blocks are N / G rollouts each)", who, N, G);
+  for (int g = 0; g < G; g++) JH_REQUIRE((int)plant_of_block[g] < M, "%s: plant_of_block[%d] = %d outside [0, M = %d): block %d names no member of the set", who, g, (int)plant_of_block[g], M, g);
+  JH_REQUIRE(ldn >= N, "%s: ldn (%d) < N (%d)", who, ldn, N);
+  const int KU = K * m->nu;
+  JH_REQUIRE(KU <= JH_MAX_KNOT_DIM, "%s: K*nu = %d exceeds %d", who, KU, JH_MAX_KNOT_DIM);
+  const int nx = m->nq + m->nv;
+  JH_REQUIRE(o_nominal >= 0 && o_sigma >= 0 && o_tp >= 0 && o_lohi >= 0, "%s: negative block offset", who);
+  const size_t need = sizeof(float) * (size_t)std::max(std::max(nx, o_nominal + KU), std::max(std::max(o_sigma + KU, o_tp + m->ntaskparam), o_lohi + 2 * m->nu));
+  JH_REQUIRE(blk_bytes >= need, "%s: a block of %zu bytes does not hold x0 | nominal | sigma | task params | bounds at the given offsets (%zu bytes)", who, blk_bytes, need);
+  JH_REQUIRE(m->plan_step_launches != 1, "%s: one launch is forced (jh_model_set_plan_step_launches) but the randomised plan step is two launches", who);
+  const bool closed = m->kind == JH_TASK_CARTPOLE || m->kind == JH_TASK_CYLINDER_PUSH;
+  const jh_engine_build* eb = engine_build(m);
+  if (!closed && !(eb && eb->rollout_cost_batch)) { jh_set_error("%s: no batched kernel for this model", who); return JH_ERR_UNSUPPORTED; }
+  unsigned* flag = (out_host_mark && out_host_mark != (void*)out) ? (unsigned*)out_host_mark : nullptr;  // (out_host_mark == out: the stream's event)
+  const float* b = (const float*)blk_dev;
+  jh_upd::TailArgs a;  // (the tail's own checks before anything is enqueued: mode, lambda, k)
+  if (int rc = jh_update_tail_args(who, costs, nullptr, b + o_nominal, noise, ldn, b + o_sigma, b + o_lohi, N, 0, K, m->nu, mode, lambda, k, tie_high, 0, nullptr, 0, 0, scratch, out, out + KU,
+                                   nullptr, nullptr, &a)) return rc;
+  const int Nb = N / G;
+  jh_plant_axis plants;
+  plants.n_stride = Nb;
+  for (int g = 0; g < G; g++) jh_plant_set(plants, g, plant_of_block[g]);
+  hipStream_t st = (hipStream_t)stream;
+  if (blk_dev != blk_host) { if (int rc = jh_upload_async(blk_dev, blk_host, blk_bytes, stream)) return rc; }  // (blk_dev == blk_host: read in place, as jh_plan_step)
+  if (timing) JH_HIP(hipEventRecord((hipEvent_t)timing[0], st));
+  const unsigned expect = flag ? __atomic_load_n(flag, __ATOMIC_RELAXED) + 1u : 0u;
+  a.done_flag = flag; a.done_value = expect;
+  const int* ints = set->tables ? m->d_i : set->d_i_plain;
+  int rc = JH_OK;
+  if (closed) {
+    jh_upd::TailArgs ra = a;  // the rollout kernel's view of the record: a block of Nb rollouts, block g's costs and noise columns g * Nb behind block 0's
+    ra.N = Nb; ra.done_flag = nullptr; ra.done_value = 0u;
+    jh_upd::BatchArgs s;
+    s.B = G; s.blk = 0; s.noise = Nb; s.costs = Nb; s.trace = 0; s.scratch = 0; s.out = 0; s.counter = nullptr; s.done_flag = nullptr; s.done_value = 0u; s.image = (long long)set->stride;
+    rc = jh_simple_rollout_cost_batch(m, set->d_images, b, b + o_tp, W, H, K, ra, s, st, {}, plants);
+  } else {
+    const jh_rollout_args ra = {b, b + o_nominal, noise, ldn, b + o_sigma, W, b + o_lohi, b + o_tp, 0, Nb, 0, H, K, costs, nullptr, nullptr};
+    jh_rollout_batch rb = {set->d_images, (long long)set->stride, ints, G, 0, (long long)Nb};
+    rb.plants = plants;
+    rc = eb->rollout_cost_batch(m, ra, rb, st);
+  }
+  if (rc == JH_OK && timing) JH_HIP(hipEventRecord((hipEvent_t)timing[1], st));
+  if (rc == JH_OK) rc = jh_update_tail_launch(a, st);
+  if (rc == JH_OK && timing) JH_HIP(hipEventRecord((hipEvent_t)timing[2], st));
+  if (rc == JH_OK) rc = download_begin(out, out, 0, stream, flag, expect);
+  return rc;
+}
+
+// B ensemble plan steps (jh_plan_step_ensemble) as ONE call (include/judo_amd.h): B controllers, each with its own block, noise, `worst`, costs and output record, each against M plants.  The
 // rollout kernels run once on the grid (workgroups, M, B): blockIdx.y is the member as above (block and noise strides 0, the set's image stride), blockIdx.z the
 // controller with the strides of jh_plan_step_batch; a set of M members is shared by all controllers (image stride 0 on that axis), a set of B * M holds controller b's
 // plants at b * M ...  Then k_update_tail_ensemble_batch on (tail workgroups, B): aggregation, tail, the two-level ticket, one completion word.  The checks are the

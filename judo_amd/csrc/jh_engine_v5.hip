@@ -98,6 +98,9 @@ constexpr int PARK_F = 5 * 64;
 struct SliceBounds { unsigned w[8]; };
 __host__ __device__ inline long long axis_stride(const SliceBounds& sb, int i) { return (long long)(((unsigned long long)sb.w[2 * i + 1] << 32) | sb.w[2 * i]); }
 inline void set_axis_stride(SliceBounds& sb, int i, long long v) { sb.w[2 * i] = (unsigned)((unsigned long long)v & 0xffffffffull); sb.w[2 * i + 1] = (unsigned)((unsigned long long)v >> 32); }
+// The batched instantiations' last argument: those eight words and, behind them, the plant axis (jh_internal.h: the rollout-index stride and the table that maps a
+// problem to its image).  A type of its own for BATCH alone, so that every other instantiation keeps the argument block it had, byte for byte.
+struct BatchBounds : SliceBounds { jh_plant_axis plants; };
 constexpr int MAX_BOUND_SLICES = 16;
 #define PARK_LD(p) __hip_atomic_load((p), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT)
 #define PARK_ST(p, v) __hip_atomic_store((p), (v), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT)
@@ -463,7 +466,9 @@ __device__ __forceinline__ bool chain_elim_order(int cmask, int c, int& level, i
 // (`batch_noise` floats apart), its costs, trace rows and overflow rows (N rollouts apart) -- is reached by offsetting the kernel's pointers once, at the top, with
 // arithmetic on kernel arguments and blockIdx.y alone: the bases stay in SGPRs, and a rollout's code below is the single launch's.  A model set
 // (jh_plan_step_batch_models) gives every problem its own image of the float section as well, `batch_image` floats apart (0: one image for all); the int section --
-// topology, pair lists, lane lists -- is one for the launch.  The other instantiations ignore the three strides and compile to the code they had without them.
+// topology, pair lists, lane lists -- is one for the launch.  The plant axis (jh_plan_step_randomized; jh_internal.h) makes the problems blocks of ONE problem's rollouts:
+// a stride on the global rollout index, so that only global rollout 0 is the noise-free nominal, and a by-value table from the problem to its image in place of the
+// problem's own index -- 0 and the identity for every other batched launch.  The other instantiations ignore the three strides and compile to the code they had without them.
 template <bool MATERIALIZE, int WPB, bool SELF, bool PERSIST = false, bool BATCH = false>
 __global__ __launch_bounds__(WAVE * WPB, WAVES_PER_EU) void k_leap_v5(const float* __restrict__ gF, const int* __restrict__ gI, const float* __restrict__ x0, int x0_batched,
                                                    const float* __restrict__ nominal, const float* __restrict__ noise, int ldn,
@@ -471,7 +476,8 @@ __global__ __launch_bounds__(WAVE * WPB, WAVES_PER_EU) void k_leap_v5(const floa
                                                    const float* __restrict__ tp, int N, int n_offset, int H, int K, float* __restrict__ costs,
                                                    float* __restrict__ knots_out, const float* __restrict__ controls, float* __restrict__ states,
                                                    float* __restrict__ sensors, int* __restrict__ stats_, int dshift_, float* __restrict__ trace, float* __restrict__ ovf_all_, unsigned* __restrict__ head,
-                                                   long long batch_blk, long long batch_noise, long long batch_image, unsigned* pflags, int slices_, SliceBounds sb_) {
+                                                   long long batch_blk, long long batch_noise, long long batch_image, unsigned* pflags, int slices_,
+                                                   std::conditional_t<BATCH, BatchBounds, SliceBounds> sb_) {
   static_assert(!BATCH || (!MATERIALIZE && !PERSIST), "batched launches are fused launches on the static grid");
   if constexpr (BATCH) {
     // blockIdx.z: the controller of jh_plan_step_ensemble_batch, whose M plants are the problems of blockIdx.y -- strides of its own in sb_ (all 0 and gridDim.z == 1 for
@@ -479,7 +485,9 @@ __global__ __launch_bounds__(WAVE * WPB, WAVES_PER_EU) void k_leap_v5(const floa
     const long long pb = blockIdx.y, pc = blockIdx.z, pr = pc * gridDim.y + pb;
     const long long ob = pb * batch_blk + pc * axis_stride(sb_, 0);
     x0 += ob; nominal += ob; sigma += ob; lohi += ob; tp += ob;
-    noise += pb * batch_noise + pc * axis_stride(sb_, 1); costs += pr * N; gF += pb * batch_image + pc * axis_stride(sb_, 2);
+    // the plant axis (jh_plan_step_randomized): the problem's first global rollout index and the image its table names -- 0 and image pb for every other launch
+    n_offset += (int)pb * sb_.plants.n_stride;
+    noise += pb * batch_noise + pc * axis_stride(sb_, 1); costs += pr * N; gF += jh_plant_of(sb_.plants, (int)pb) * batch_image + pc * axis_stride(sb_, 2);
     if (trace) trace += pr * N * H * 15;
     if (NOVF > 0 && ovf_all_) ovf_all_ += pr * N * (NOVF * POOL_F);  // (the overflow rows are indexed by rollout: a problem's N rows behind the one before)
   }
@@ -1937,7 +1945,7 @@ bool accepts(const jh_model* m) { return leap_refusal(m, nullptr) == JH_OK; }
 struct LeapArgs {
   const jh_rollout_args& a; const float* gF; const int* gI; int* stats; int dshift, grid;  // grid: not an argument -- the workgroups of a problem on the static grid
   int x0_batched = 0; const float* controls = nullptr; float *states = nullptr, *sensors = nullptr;  // materialise mode
-  float* ovf = nullptr; unsigned *head = nullptr, *pflags = nullptr; int slices = 0; SliceBounds sb = {};
+  float* ovf = nullptr; unsigned *head = nullptr, *pflags = nullptr; int slices = 0; BatchBounds sb = {};  // (the plant axis behind the eight words goes to the batched instantiations alone)
   long long batch_blk = 0, batch_noise = 0, batch_image = 0;
 };
 
@@ -1955,7 +1963,7 @@ void launch(const LeapArgs& k, dim3 grid, hipStream_t st) {
   const jh_rollout_args& a = k.a;
   hipLaunchKernelGGL((k_leap_v5<MATERIALIZE, WAVES_PER_BLOCK, SELF, PERSIST, BATCH>), grid, dim3(WAVE * WAVES_PER_BLOCK), 0, st, k.gF, k.gI, a.x0, k.x0_batched, a.nominal, a.noise, a.ldn,
                      a.sigma, a.W, a.lohi, a.tp, a.N, a.n_offset, a.H, a.K, a.costs, a.knots_out, k.controls, k.states, k.sensors, k.stats, k.dshift, a.trace, k.ovf, k.head,
-                     k.batch_blk, k.batch_noise, k.batch_image, k.pflags, k.slices, k.sb);
+                     k.batch_blk, k.batch_noise, k.batch_image, k.pflags, k.slices, static_cast<const std::conditional_t<BATCH, BatchBounds, SliceBounds>&>(k.sb));
 }
 
 bool hand_contacts(const jh_model* m) { return m->self_collision && m->h_i[17] > 0; }  // the SELF instantiations: the hand's own contacts are on and the image has body pairs
@@ -2050,6 +2058,7 @@ static int rollout_cost_batch(const jh_model* m, const jh_rollout_args& a, const
   LeapArgs k = leap_args(m, a, s.images, s.ints, (int)rollouts);
   k.batch_blk = s.blk_stride; k.batch_noise = s.noise_stride; k.batch_image = s.image_stride;
   set_axis_stride(k.sb, 0, s.blk_stride_c); set_axis_stride(k.sb, 1, s.noise_stride_c); set_axis_stride(k.sb, 2, s.image_stride_c);
+  k.sb.plants = s.plants;
   if (const size_t b = ovf_bytes((size_t)rollouts)) k.ovf = jh_launch_scratch(m, b, st);  // (every problem's rows; nullptr: the LDS capacity alone, drops and the fallback counted)
   if (hand_contacts(m)) launch<false, true, false, true>(k, dim3(k.grid, s.B, s.C), st);
   else launch<false, false, false, true>(k, dim3(k.grid, s.B, s.C), st);

@@ -239,23 +239,25 @@ __global__ __launch_bounds__(jh_upd::kUB) void k_plan_step(const float* __restri
 // bodies are the ones above, so a problem's bits are those of its own k_plan_step launch.
 template <class T>
 __global__ __launch_bounds__(jh_upd::kUB) void k_plan_step_batch(const float* __restrict__ P, const float* __restrict__ x0, const float* __restrict__ W, const float* __restrict__ tp, int H, int K,
-                                                                 jh_upd::TailArgs base, jh_upd::BatchArgs s) {
+                                                                 jh_upd::TailArgs base, jh_upd::BatchArgs s, jh_plant_axis p) {
+  // (p, the plant axis of jh_internal.h: the problem's first global rollout index and the image its table names; 0 and image b for the independent problems of every caller so far)
   const int b = blockIdx.y;
   const jh_upd::TailArgs a = jh_upd::batch_problem(base, s, b);
-  rollout_cost_body<T, jh_upd::kUB>(P + b * s.image, x0 + b * s.blk, a.src.nominal, a.src.noise, a.src.ldn, a.src.sigma, W, a.src.lohi, tp + b * s.blk, a.N, a.n_offset, H, K, const_cast<float*>(a.costs), nullptr,
-                                    const_cast<float*>(a.trace));
+  rollout_cost_body<T, jh_upd::kUB>(P + jh_plant_of(p, b) * s.image, x0 + b * s.blk, a.src.nominal, a.src.noise, a.src.ldn, a.src.sigma, W, a.src.lohi, tp + b * s.blk, a.N, a.n_offset + b * p.n_stride, H, K,
+                                    const_cast<float*>(a.costs), nullptr, const_cast<float*>(a.trace));
   __syncthreads();
   jh_upd::batch_done(s, jh_upd::update_tail_body(a));
 }
 // ... and the rollout + cost kernel alone for B problems: the first of the two launches where the one-launch form does not fit or is switched off (k_update_tail_batch follows)
 template <class T>
 __global__ __launch_bounds__(kBlock) void k_rollout_cost_batch(const float* __restrict__ P, const float* __restrict__ x0, const float* __restrict__ W, const float* __restrict__ tp, int H, int K,
-                                                               jh_upd::TailArgs base, jh_upd::BatchArgs s, jh_upd::ControllerAxis z) {
+                                                               jh_upd::TailArgs base, jh_upd::BatchArgs s, jh_upd::ControllerAxis z, jh_plant_axis p) {
   // (blockIdx.z: the controller of jh_plan_step_ensemble_batch, whose members are the problems of blockIdx.y; every other launch has gridDim.z == 1 and z's offsets are 0)
+  // (p, the plant axis of jh_plan_step_randomized: the problems are blocks of one problem's rollouts -- block b starts at global rollout b * p.n_stride and runs on the image its table names)
   const int b = blockIdx.y, c = blockIdx.z;
   const jh_upd::TailArgs a = jh_upd::batch_controller(jh_upd::batch_problem(base, s, b), s, z, c, (int)gridDim.y);
-  rollout_cost_body<T, kBlock>(P + b * s.image + c * z.image, x0 + b * s.blk + c * z.blk, a.src.nominal, a.src.noise, a.src.ldn, a.src.sigma, W, a.src.lohi, tp + b * s.blk + c * z.blk, a.N, a.n_offset, H, K,
-                               const_cast<float*>(a.costs), nullptr, const_cast<float*>(a.trace));
+  rollout_cost_body<T, kBlock>(P + jh_plant_of(p, b) * s.image + c * z.image, x0 + b * s.blk + c * z.blk, a.src.nominal, a.src.noise, a.src.ldn, a.src.sigma, W, a.src.lohi, tp + b * s.blk + c * z.blk, a.N,
+                               a.n_offset + b * p.n_stride, H, K, const_cast<float*>(a.costs), nullptr, const_cast<float*>(a.trace));
 }
 #ifdef JH_TAIL_TICKS
 __global__ void k_tail_ticks_start() { if (threadIdx.x == 0) jh_upd::g_tail_ticks[8] = wall_clock64(); }
@@ -388,34 +390,35 @@ int launch_plan_step(const jh_model* m, const float* x0, const float* W, const f
 }
 
 template <class T>
-int launch_plan_step_batch(const float* P, const float* x0, const float* W, const float* tp, int H, int K, const jh_upd::TailArgs& a, const jh_upd::BatchArgs& s, hipStream_t st) {
+int launch_plan_step_batch(const float* P, const float* x0, const float* W, const float* tp, int H, int K, const jh_upd::TailArgs& a, const jh_upd::BatchArgs& s, const jh_plant_axis& p, hipStream_t st) {
   constexpr int BS = jh_upd::kUB;
   size_t lds = sizeof(float) * ((size_t)H * K + (size_t)K * T::NU * BS + T::NP + T::NTP + T::NX);
   JH_REQUIRE(lds <= 48 * 1024, "plan_step_batch: H*K too large for the LDS staging of the one-launch plan step (%zu bytes)", lds);
-  hipLaunchKernelGGL(k_plan_step_batch<T>, dim3((a.N + BS - 1) / BS, s.B), dim3(BS), lds, st, P, x0, W, tp, H, K, a, s);
+  hipLaunchKernelGGL(k_plan_step_batch<T>, dim3((a.N + BS - 1) / BS, s.B), dim3(BS), lds, st, P, x0, W, tp, H, K, a, s, p);
   JH_HIP(hipGetLastError());
   return JH_OK;
 }
 
 template <class T>
-int launch_cost_batch(const float* P, const float* x0, const float* W, const float* tp, int H, int K, const jh_upd::TailArgs& a, const jh_upd::BatchArgs& s, const jh_upd::ControllerAxis& z, hipStream_t st) {
+int launch_cost_batch(const float* P, const float* x0, const float* W, const float* tp, int H, int K, const jh_upd::TailArgs& a, const jh_upd::BatchArgs& s, const jh_upd::ControllerAxis& z, const jh_plant_axis& p, hipStream_t st) {
   size_t lds = sizeof(float) * ((size_t)H * K + (size_t)K * T::NU * kBlock + T::NP + T::NTP + T::NX);
   JH_REQUIRE(lds <= 64 * 1024, "plan_step_batch: H*K too large for the LDS staging (%zu bytes)", lds);
-  hipLaunchKernelGGL(k_rollout_cost_batch<T>, dim3((a.N + kBlock - 1) / kBlock, s.B, z.C), dim3(kBlock), lds, st, P, x0, W, tp, H, K, a, s, z);
+  hipLaunchKernelGGL(k_rollout_cost_batch<T>, dim3((a.N + kBlock - 1) / kBlock, s.B, z.C), dim3(kBlock), lds, st, P, x0, W, tp, H, K, a, s, z, p);
   JH_HIP(hipGetLastError());
   return JH_OK;
 }
 
 }  // namespace
 
-int jh_simple_plan_step_batch(const jh_model* m, const float* P, const float* x0, const float* W, const float* tp, int H, int K, const jh_upd::TailArgs& a, const jh_upd::BatchArgs& s, hipStream_t st) {
-  if (m->kind == JH_TASK_CARTPOLE) return launch_plan_step_batch<Cartpole>(P, x0, W, tp, H, K, a, s, st);
-  return launch_plan_step_batch<CylinderPush>(P, x0, W, tp, H, K, a, s, st);
+int jh_simple_plan_step_batch(const jh_model* m, const float* P, const float* x0, const float* W, const float* tp, int H, int K, const jh_upd::TailArgs& a, const jh_upd::BatchArgs& s, hipStream_t st,
+                              const jh_plant_axis& p) {
+  if (m->kind == JH_TASK_CARTPOLE) return launch_plan_step_batch<Cartpole>(P, x0, W, tp, H, K, a, s, p, st);
+  return launch_plan_step_batch<CylinderPush>(P, x0, W, tp, H, K, a, s, p, st);
 }
 int jh_simple_rollout_cost_batch(const jh_model* m, const float* P, const float* x0, const float* tp, const float* W, int H, int K, const jh_upd::TailArgs& a, const jh_upd::BatchArgs& s, hipStream_t st,
-                                 const jh_upd::ControllerAxis& z) {
-  if (m->kind == JH_TASK_CARTPOLE) return launch_cost_batch<Cartpole>(P, x0, W, tp, H, K, a, s, z, st);
-  return launch_cost_batch<CylinderPush>(P, x0, W, tp, H, K, a, s, z, st);
+                                 const jh_upd::ControllerAxis& z, const jh_plant_axis& p) {
+  if (m->kind == JH_TASK_CARTPOLE) return launch_cost_batch<Cartpole>(P, x0, W, tp, H, K, a, s, z, p, st);
+  return launch_cost_batch<CylinderPush>(P, x0, W, tp, H, K, a, s, z, p, st);
 }
 
 // can the plan step of this model run as one launch?  (closed-form models; the knots of a workgroup of 256 rollouts must fit the LDS staging next to the update's own 9 KB)

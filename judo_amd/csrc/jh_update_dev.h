@@ -328,7 +328,9 @@ __device__ __forceinline__ bool update_tail_body(const TailArgs& a) {
 // block.  The completion word is a second level: the last workgroup of a problem bumps the batch counter behind a fence of its outputs, and the one that draws B - 1
 // resets the counter and stores the word behind a system-scope fence -- once, behind the last of the B problems.  B = 1 takes the same code.
 // A model set (jh_plan_step_batch_models) also gives every problem its own image of the model's float section: the kernels that read the model offset its base by
-// blockIdx.y * image once, next to the problem's record (k_update_tail_batch reads no model and ignores the field).
+// blockIdx.y * image once, next to the problem's record (k_update_tail_batch reads no model and ignores the field).  Which image a problem reads, and where its
+// rollouts stand in the global numbering (jh_plan_step_randomized), is a record of its own that only the rollout kernels take -- jh_plant_axis, jh_internal.h -- for the
+// reason ControllerAxis below is one: BatchArgs is a kernel argument of the tails as well, whose argument layout stays what it was.
 struct BatchArgs {
   int B;
   long long blk, noise, costs, trace, scratch, out;  // floats from one problem's packed block / noise / costs / trace buffer / update scratch / output block to the next one's
@@ -434,9 +436,11 @@ int jh_update_tail_batch_launch(const jh_upd::TailArgs& a, const jh_upd::BatchAr
 // the ensemble form (jh_plan_step_ensemble): the aggregation of e.member_costs into e.costs == a.costs, then the tail, in one launch
 int jh_update_tail_ensemble_launch(const jh_upd::TailArgs& a, const jh_upd::EnsembleArgs& e, hipStream_t st);
 // (`P`: the float section of problem 0's model image, s.image floats to the next problem's -- m->d_f with s.image = 0 where the problems share the model)
-int jh_simple_plan_step_batch(const jh_model* m, const float* P, const float* x0, const float* W, const float* tp, int H, int K, const jh_upd::TailArgs& a, const jh_upd::BatchArgs& s, hipStream_t st);
+// (`p`: the plant axis of jh_internal.h, the rollout-index stride and the table from a problem to its image; the default, 0 and the identity, is B independent problems)
+int jh_simple_plan_step_batch(const jh_model* m, const float* P, const float* x0, const float* W, const float* tp, int H, int K, const jh_upd::TailArgs& a, const jh_upd::BatchArgs& s, hipStream_t st,
+                              const jh_plant_axis& p = {});
 // (`z`: the controller axis of jh_plan_step_ensemble_batch, grid (workgroups, s.B, z.C); the default is the launch without one)
 int jh_simple_rollout_cost_batch(const jh_model* m, const float* P, const float* x0, const float* tp, const float* W, int H, int K, const jh_upd::TailArgs& a, const jh_upd::BatchArgs& s, hipStream_t st,
-                                 const jh_upd::ControllerAxis& z = {});
+                                 const jh_upd::ControllerAxis& z = {}, const jh_plant_axis& p = {});
 // the ensemble fleet's tail (jh_plan_step_ensemble_batch): `a` is controller 0's record, `s` the controllers' strides and the two-level ticket; grid (tail workgroups, s.B)
 int jh_update_tail_ensemble_batch_launch(const jh_upd::TailArgs& a, const jh_upd::BatchArgs& s, const jh_upd::EnsembleBatchArgs& e, hipStream_t st);

@@ -24,6 +24,7 @@ from judo_amd.distributed import world_info
 from judo_amd.ensemble import MAX_ENSEMBLE, EnsembleController, check_descriptions, make_ensemble_controller
 from judo_amd.fleet import ControllerFleet, _FleetBuffers
 from judo_amd.models import image_sections
+from judo_amd.randomized import RandomizedController
 
 MAX_ENSEMBLE_FLEET = _lib.MAX_ENSEMBLE_FLEET
 
@@ -103,6 +104,9 @@ class EnsembleFleet(ControllerFleet):
         super().__init__(controllers)
 
     def _check_member(self, i: int, c, first) -> None:
+        if isinstance(c, RandomizedController):
+            raise ValueError(f"fleet member {i} is a RandomizedController: it rolls each candidate out on one plant of its set, not on all of them, and its plan step "
+                             "(jh_plan_step_randomized) has no batched launch yet; it plans alone")
         if not isinstance(c, EnsembleController):
             raise ValueError(f"fleet member {i} is a {type(c).__name__}, not an EnsembleController: controllers that believe one plant share a launch in a ControllerFleet")
         world, _ = world_info(c.group)

@@ -33,6 +33,7 @@ from judo_amd.controller import POLICY_OUTPUT_DIM, Controller, make_controller_f
 from judo_amd.device import GpuModelSet, current_stream_ptr
 from judo_amd.distributed import world_info
 from judo_amd.ensemble import EnsembleController
+from judo_amd.randomized import RandomizedController
 from judo_amd.models import image_sections, layout
 from judo_amd.optimizers import Optimizer, _NoiseStream
 from judo_amd.tasks import get_registered_tasks
@@ -170,6 +171,10 @@ class ControllerFleet:
                 "default_policy_command": np.asarray(t.default_policy_command).tolist()}
 
     def _check_member(self, i: int, c: Controller, first: Controller) -> None:
+        if isinstance(c, RandomizedController):
+            # (its iteration shape reads "plan_step" too, and the batched plan step would run every block on `c.model`, plant 0, and drop the assignment without a word)
+            raise ValueError(f"fleet member {i} is a RandomizedController: its plan step spreads the rollout blocks over the plants of its own set "
+                             "(jh_plan_step_randomized), which no batched launch does yet; it plans alone")
         if isinstance(c, EnsembleController) and not self._ensemble_members:
             # (its iteration shape reads "plan_step", but the batched plan step would run on `c.model`, plant 0 alone, and drop the ensemble without a word)
             raise ValueError(f"fleet member {i} is an EnsembleController: a ControllerFleet plans every member on one plant; ensemble controllers share a launch in an "
