@@ -49,6 +49,7 @@ enum jh_spline_kind { JH_SPLINE_ZERO = 0, JH_SPLINE_LINEAR = 1, JH_SPLINE_CUBIC 
 #define JH_MAX_ENSEMBLE 32 /* members of a model set that jh_plan_step_ensemble plans against */
 #define JH_MAX_ENSEMBLE_FLEET 256 /* controllers of one jh_plan_step_ensemble_batch call (their `worst` travel in the kernel arguments, a byte each) */
 #define JH_MAX_PLANT_BLOCKS 64 /* rollout blocks of one jh_plan_step_randomized call (their plants travel in the kernel arguments, a byte each) */
+#define JH_MAX_FLEET_PLANT_BLOCKS 256 /* B * G, the (controller, block) pairs of one jh_plan_step_randomized_batch call: the bytes of its table in the kernel arguments */
 
 const char* jh_last_error(void);
 int jh_version(void);
@@ -404,6 +405,32 @@ int jh_plan_step_ensemble_batch(const jh_model_set* set, int B, int M, void* blk
 int jh_plan_step_randomized(const jh_model_set* set, void* blk_dev, const void* blk_host, size_t blk_bytes, int o_nominal, int o_sigma, int o_tp, int o_lohi, const float* noise, int ldn,
                             const float* W, int N, int H, int K, const unsigned char* plant_of_block /* HOST, G */, int G, float* costs /* DEVICE, N */, int mode, float lambda, int k,
                             int tie_high, float* scratch, float* out /* nominal | sigma */, void* out_host_mark, void* const* timing, void* stream);
+/* B domain-randomised plan steps as ONE call with ONE completion mark (several robots, or one robot swept over seeds, goals or plant weights: B controllers that each
+ * spread their N candidates over the plants of a set; the reference has no counterpart).  Controller b's results -- its row of `costs` and its record nominal | sigma --
+ * are bit for bit what jh_plan_step_randomized writes on b's block, b's noise slice and b's plants with the table plant_of_block[b * G .. b * G + G).
+ *   per controller   the packed block x0 | nominal | sigma | task params | bounds, blk_stride_bytes apart; the noise, noise_stride_floats apart; the update scratch,
+ *                    jh_update_fused_scratch_floats(N, K, nu) floats apart (jh_plan_batch_scratch_floats(B, N, K, nu) in all, ZERO before the first use: the B + 1 ticket
+ *                    words, which every launch leaves at zero); the output record nominal K*nu | sigma K*nu, out_stride_floats apart; the row b of `costs` (B x N); its G
+ *                    bytes of the table
+ *   shared           N, H, K, G, W, mode, lambda, k, tie_high; no trace buffer and no knots_out, as for the randomised call
+ *   the plants       a set of M members, which every controller shares, or a set of B * M members, controller-major: member b * M + m is controller b's plant m.
+ *                    M <= JH_MAX_ENSEMBLE.  A set of any other size: JH_ERR_INVALID with the three numbers
+ *   plant_of_block   a HOST array of B x G bytes, controller-major, each < M, read before the call returns: the values travel in the kernel arguments, so a re-drawn
+ *                    assignment costs no copy and no launch.  G is a grid dimension and therefore one for the launch
+ *   limits           1 <= B <= JH_MAX_ENSEMBLE_FLEET, 1 <= G <= JH_MAX_PLANT_BLOCKS, B * G <= JH_MAX_FLEET_PLANT_BLOCKS (the bytes of the table in the kernel arguments)
+ * Two launches for every model: the batched rollout kernel on the grid (workgroups of Nb = N / G rollouts, G, B) -- block stride 0 on y and the controller's on z; noise,
+ * cost and rollout-index strides Nb on y; the image from the table entry (controller, block), plus the controller's image stride where the set has B * M members; every
+ * controller's global rollout 0 is its noise-free nominal and the first rollout of its later blocks keeps its noise; the leap kernel's latency mode is chosen from the
+ * B * N rollouts of the launch, and the bits do not depend on it; no queue and no horizon slices --, then the update's tail on (tail workgroups, B) with the two-level
+ * ticket of jh_plan_step_batch.  The completion mark is that call's: out_host_mark == out is the stream's event, anything else the polled 4-byte word, which receives
+ * its old value + 1 behind the last controller's results.  B = 1 and G = 1 take the same code.  Everything is checked before anything is enqueued.  JH_ERR_INVALID,
+ * naming the argument: each null pointer by name (plant_of_block included); B, G, M or B * G outside their limits; N % G != 0; an entry of the table >= M (named with
+ * its controller and block); a stride smaller than a block / a noise slice / an output record; a member 0 whose plan step is forced to one launch; what
+ * jh_plan_step_randomized refuses otherwise.  JH_ERR_UNSUPPORTED: as jh_plan_step_randomized. */
+int jh_plan_step_randomized_batch(const jh_model_set* set, int B, int M, void* blk_dev, const void* blk_host, size_t blk_bytes, size_t blk_stride_bytes, int o_nominal, int o_sigma, int o_tp,
+                                  int o_lohi, const float* noise, int ldn, size_t noise_stride_floats, const float* W, int N, int H, int K,
+                                  const unsigned char* plant_of_block /* HOST, B x G */, int G, float* costs /* DEVICE, B x N */, int mode, float lambda, int k, int tie_high, float* scratch,
+                                  float* out, size_t out_stride_floats, void* out_host_mark, void* const* timing, void* stream);
 /* The noise of those B problems in one launch (judo/optimizers/{mppi.py:52,ps.py:43,cem.py:67}, one np.random.randn per controller): problem b's (rows, ldn) slice of `out`
  * (B x rows x ldn floats) is bit for bit what jh_noise_normal(seeds[b], draws[b], rows, 0, n_local, out + b * rows * ldn, ldn) writes; columns n_local .. ldn - 1 are left
  * alone.  seeds / draws: HOST arrays of B entries, read before the call returns (one launch per 256 problems: the pairs travel as kernel arguments). */

@@ -96,6 +96,8 @@ _SIGNATURES = {
                                               C.c_int, C.c_int, f32p, f32p, C.POINTER(C.c_int), C.c_int, C.c_float, C.c_int, C.c_int, f32p, f32p, C.c_size_t, C.c_void_p, C.c_void_p, C.c_void_p]),
     "jh_plan_step_randomized": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_int, C.c_int, C.c_int, C.c_int, f32p, C.c_int, f32p, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_ubyte), C.c_int,
                                           f32p, C.c_int, C.c_float, C.c_int, C.c_int, f32p, f32p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "jh_plan_step_randomized_batch": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_size_t, C.c_size_t, C.c_int, C.c_int, C.c_int, C.c_int, f32p, C.c_int, C.c_size_t, f32p, C.c_int,
+                                                C.c_int, C.c_int, C.POINTER(C.c_ubyte), C.c_int, f32p, C.c_int, C.c_float, C.c_int, C.c_int, f32p, f32p, C.c_size_t, C.c_void_p, C.c_void_p, C.c_void_p]),
     "jh_update_fused_batch": (C.c_int, [C.c_int, f32p, f32p, C.c_size_t, C.c_int, C.c_int, C.c_int, f32p, C.c_int, C.c_size_t, C.c_int, C.c_int, C.c_int, C.c_int, C.c_float, C.c_int, C.c_int, C.c_int,
                                         f32p, C.c_int, C.c_int, f32p, f32p, C.c_size_t, C.c_void_p, C.c_void_p]),
     "jh_noise_normal_batch": (C.c_int, [C.c_int, C.POINTER(C.c_ulonglong), C.POINTER(C.c_uint), C.c_int, C.c_int, f32p, C.c_int, C.c_void_p]),
@@ -123,6 +125,7 @@ MAX_TASK_PARAMS = 32  # JH_MAX_TASK_PARAMS
 MAX_ENSEMBLE = 32  # JH_MAX_ENSEMBLE: members of a model set that jh_plan_step_ensemble plans against
 MAX_ENSEMBLE_FLEET = 256  # JH_MAX_ENSEMBLE_FLEET: controllers of one jh_plan_step_ensemble_batch call
 MAX_PLANT_BLOCKS = 64  # JH_MAX_PLANT_BLOCKS: rollout blocks of one jh_plan_step_randomized call
+MAX_FLEET_PLANT_BLOCKS = 256  # JH_MAX_FLEET_PLANT_BLOCKS: B * G, the (controller, block) pairs of one jh_plan_step_randomized_batch call
 
 
 class JudoAmdError(RuntimeError):

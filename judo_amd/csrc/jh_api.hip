@@ -1014,6 +1014,90 @@ extern "C" int jh_plan_step_ensemble_batch(const jh_model_set* set, int B, int M
   return rc;
 }
 
+// B randomised plan steps (jh_plan_step_randomized) as ONE call (include/judo_amd.h): B controllers, each with its own block, noise, costs, output record and its own table
+// from rollout block to plant.  The rollout kernels run once on the grid (workgroups of Nb rollouts, G, B): blockIdx.y is the block as above (block stride 0; noise, cost and
+// rollout-index strides Nb), blockIdx.z the controller with the strides of jh_plan_step_ensemble_batch, and the plant axis carries the B x G table, whose entry is the
+// pair's (jh_internal.h).  A set of M members is shared by all controllers (image stride 0 on that axis), a set of B * M holds controller b's plants at b * M ...  Then
+// k_update_tail_batch on (tail workgroups, B): the tail, the two-level ticket, one completion word.  The checks are the randomised call's and the batched call's, all in
+// front of the first enqueue.
+extern "C" int jh_plan_step_randomized_batch(const jh_model_set* set, int B, int M, void* blk_dev, const void* blk_host, size_t blk_bytes, size_t blk_stride_bytes, int o_nominal, int o_sigma,
+                                             int o_tp, int o_lohi, const float* noise, int ldn, size_t noise_stride_floats, const float* W, int N, int H, int K,
+                                             const unsigned char* plant_of_block, int G, float* costs, int mode, float lambda, int k, int tie_high, float* scratch, float* out,
+                                             size_t out_stride_floats, void* out_host_mark, void* const* timing, void* stream) {
+  const char* who = "plan_step_randomized_batch";
+#define JH_RND_PTR(p) JH_REQUIRE((p) != nullptr, "%s: " #p " is a null pointer", who)
+  JH_RND_PTR(set); JH_RND_PTR(blk_dev); JH_RND_PTR(blk_host); JH_RND_PTR(noise); JH_RND_PTR(W); JH_RND_PTR(plant_of_block); JH_RND_PTR(costs); JH_RND_PTR(scratch); JH_RND_PTR(out);
+#undef JH_RND_PTR
+  const jh_model* m = set->m0;
+  JH_REQUIRE(B >= 1 && B <= JH_MAX_ENSEMBLE_FLEET, "%s: B = %d outside [1, JH_MAX_ENSEMBLE_FLEET = %d]", who, B, JH_MAX_ENSEMBLE_FLEET);
+  JH_REQUIRE(M >= 1 && M <= JH_MAX_ENSEMBLE, "%s: M = %d outside [1, JH_MAX_ENSEMBLE = %d]", who, M, JH_MAX_ENSEMBLE);
+  JH_REQUIRE(G >= 1 && G <= JH_MAX_PLANT_BLOCKS, "%s: G = %d outside [1, JH_MAX_PLANT_BLOCKS = %d]", who, G, JH_MAX_PLANT_BLOCKS);
+  JH_REQUIRE(B * G <= JH_MAX_FLEET_PLANT_BLOCKS, "%s: B * G = %d * %d = %d exceeds JH_MAX_FLEET_PLANT_BLOCKS = %d (the bytes of the table in the kernel arguments)", who, B, G, B * G,
+             JH_MAX_FLEET_PLANT_BLOCKS);
+  JH_REQUIRE(set->B == M || set->B == B * M, "%s: a set of %d members is neither the M = %d plants every controller shares nor the B * M = %d plants of B = %d controllers", who, set->B, M, B * M, B);
+  if (m->kind == JH_TASK_FR3_PICK) { jh_set_error("%s: fr3_pick has no batched plan step (its phase is chosen per problem on the host)", who); return JH_ERR_UNSUPPORTED; }
+  if (m->kind == JH_TASK_LEAP_CUBE && m->kernel_gen != 3) { jh_set_error("%s: only kernel generation 3 of the leap family has a batched launch (this model runs %d)", who, m->kernel_gen); return JH_ERR_UNSUPPORTED; }
+  JH_REQUIRE(N > 0 && H > 0 && K >= 1, "%s: N, H, K must be positive (N=%d H=%d K=%d)", who, N, H, K);
+  JH_REQUIRE(N % G == 0, "%s: N = %d is no multiple of G = %d (the blocks are N / G rollouts each)", who, N, G);
+  for (int c = 0; c < B; c++)
+    for (int g = 0; g < G; g++)
+      JH_REQUIRE((int)plant_of_block[c * G + g] < M, "%s: plant_of_block[%d] = %d outside [0, M = %d): controller %d, block %d names no member of the set", who, c * G + g,
+                 (int)plant_of_block[c * G + g], M, c, g);
+  JH_REQUIRE(ldn >= N, "%s: ldn (%d) < N (%d)", who, ldn, N);
+  const int KU = K * m->nu;
+  JH_REQUIRE(KU <= JH_MAX_KNOT_DIM, "%s: K*nu = %d exceeds %d", who, KU, JH_MAX_KNOT_DIM);
+  const int nx = m->nq + m->nv;
+  JH_REQUIRE(o_nominal >= 0 && o_sigma >= 0 && o_tp >= 0 && o_lohi >= 0, "%s: negative block offset", who);
+  const size_t need = sizeof(float) * (size_t)std::max(std::max(nx, o_nominal + KU), std::max(std::max(o_sigma + KU, o_tp + m->ntaskparam), o_lohi + 2 * m->nu));
+  JH_REQUIRE(blk_bytes >= need, "%s: a block of %zu bytes does not hold x0 | nominal | sigma | task params | bounds at the given offsets (%zu bytes)", who, blk_bytes, need);
+  JH_REQUIRE(blk_stride_bytes >= blk_bytes && blk_stride_bytes % sizeof(float) == 0, "%s: blk_stride_bytes = %zu is smaller than a block (%zu bytes) or no multiple of 4", who, blk_stride_bytes, blk_bytes);
+  JH_REQUIRE(noise_stride_floats >= (size_t)KU * (size_t)ldn, "%s: noise_stride_floats = %zu is smaller than a problem's noise (K*nu*ldn = %zu)", who, noise_stride_floats, (size_t)KU * (size_t)ldn);
+  JH_REQUIRE(out_stride_floats >= 2 * (size_t)KU, "%s: out_stride_floats = %zu is smaller than an output record (nominal | sigma = %zu floats)", who, out_stride_floats, 2 * (size_t)KU);
+  JH_REQUIRE(m->plan_step_launches != 1, "%s: one launch is forced (jh_model_set_plan_step_launches) but the randomised plan step is two launches", who);
+  const bool closed = m->kind == JH_TASK_CARTPOLE || m->kind == JH_TASK_CYLINDER_PUSH;
+  const jh_engine_build* eb = engine_build(m);
+  if (!closed && !(eb && eb->rollout_cost_batch)) { jh_set_error("%s: no batched kernel for this model", who); return JH_ERR_UNSUPPORTED; }
+  JH_REQUIRE((long long)B * N <= 0x7fffffffll, "%s: B * N = %lld rollouts exceed one launch", who, (long long)B * N);
+  unsigned* flag = (out_host_mark && out_host_mark != (void*)out) ? (unsigned*)out_host_mark : nullptr;  // (out_host_mark == out: the stream's event)
+  const float* b = (const float*)blk_dev;
+  jh_upd::TailArgs a;  // (controller 0's record; the tail's own checks before anything is enqueued: mode, lambda, k)
+  if (int rc = jh_update_tail_args(who, costs, nullptr, b + o_nominal, noise, ldn, b + o_sigma, b + o_lohi, N, 0, K, m->nu, mode, lambda, k, tie_high, 0, nullptr, 0, 0, scratch, out, out + KU,
+                                   nullptr, nullptr, &a)) return rc;
+  const int Nb = N / G;
+  jh_plant_axis plants;
+  plants.n_stride = Nb;
+  for (int e = 0; e < B * G; e++) jh_plant_set(plants, e, plant_of_block[e]);
+  hipStream_t st = (hipStream_t)stream;
+  if (blk_dev != blk_host) { if (int rc = jh_upload_async(blk_dev, blk_host, (size_t)(B - 1) * blk_stride_bytes + blk_bytes, stream)) return rc; }
+  if (timing) JH_HIP(hipEventRecord((hipEvent_t)timing[0], st));
+  const unsigned expect = flag ? __atomic_load_n(flag, __ATOMIC_RELAXED) + 1u : 0u;
+  const long long blk_c = (long long)(blk_stride_bytes / sizeof(float)), image_c = set->B == M ? 0ll : (long long)M * (long long)set->stride;
+  const int* ints = set->tables ? m->d_i : set->d_i_plain;
+  int rc = JH_OK;
+  if (closed) {
+    jh_upd::TailArgs ra = a;  // the rollout kernel's view: a block of Nb rollouts; pair (c, g)'s costs lie (c * G + g) * Nb behind `costs`, its noise columns g * Nb behind the controller's
+    ra.N = Nb; ra.done_flag = nullptr; ra.done_value = 0u;
+    jh_upd::BatchArgs s;
+    s.B = G; s.blk = 0; s.noise = Nb; s.costs = Nb; s.trace = 0; s.scratch = 0; s.out = 0; s.counter = nullptr; s.done_flag = nullptr; s.done_value = 0u; s.image = (long long)set->stride;
+    jh_upd::ControllerAxis z;
+    z.C = B; z.blk = blk_c; z.noise = (long long)noise_stride_floats; z.image = image_c;
+    rc = jh_simple_rollout_cost_batch(m, set->d_images, b, b + o_tp, W, H, K, ra, s, st, z, plants);
+  } else {
+    const jh_rollout_args ra = {b, b + o_nominal, noise, ldn, b + o_sigma, W, b + o_lohi, b + o_tp, 0, Nb, 0, H, K, costs, nullptr, nullptr};
+    jh_rollout_batch rb = {set->d_images, (long long)set->stride, ints, G, 0, (long long)Nb, B, blk_c, (long long)noise_stride_floats, image_c};
+    rb.plants = plants;
+    rc = eb->rollout_cost_batch(m, ra, rb, st);
+  }
+  if (rc == JH_OK && timing) JH_HIP(hipEventRecord((hipEvent_t)timing[1], st));
+  jh_upd::BatchArgs s;  // the tail's axis: the controllers
+  s.B = B; s.blk = blk_c; s.noise = (long long)noise_stride_floats; s.costs = N; s.trace = 0; s.scratch = (long long)jh_update_fused_scratch_floats(N, K, m->nu); s.out = (long long)out_stride_floats;
+  s.counter = reinterpret_cast<unsigned*>(scratch) + 1; s.done_flag = flag; s.done_value = expect;
+  if (rc == JH_OK) rc = jh_update_tail_batch_launch(a, s, st);
+  if (rc == JH_OK && timing) JH_HIP(hipEventRecord((hipEvent_t)timing[2], st));
+  if (rc == JH_OK) rc = download_begin(out, out, 0, stream, flag, expect);
+  return rc;
+}
+
 // The update alone for B problems whose costs are given (the materialise path of a fleet: the Spot policy rollout, judo_amd/fleet.py): jh_plan_step_batch's last stage --
 // k_update_tail_batch with the two-level ticket -- and its completion mark, without an upload or a rollout kernel in front.
 extern "C" int jh_update_fused_batch(int B, const float* costs, const float* blk, size_t blk_stride_floats, int o_nominal, int o_sigma, int o_lohi, const float* noise, int ldn,

@@ -485,9 +485,10 @@ __global__ __launch_bounds__(WAVE * WPB, WAVES_PER_EU) void k_leap_v5(const floa
     const long long pb = blockIdx.y, pc = blockIdx.z, pr = pc * gridDim.y + pb;
     const long long ob = pb * batch_blk + pc * axis_stride(sb_, 0);
     x0 += ob; nominal += ob; sigma += ob; lohi += ob; tp += ob;
-    // the plant axis (jh_plan_step_randomized): the problem's first global rollout index and the image its table names -- 0 and image pb for every other launch
+    // the plant axis (jh_plan_step_randomized): the problem's first global rollout index and the image its table names -- 0 and image pb for every other launch; the
+    // table's entry is the pair's, `pr` (jh_plan_step_randomized_batch: an assignment per controller), which is pb wherever gridDim.z == 1
     n_offset += (int)pb * sb_.plants.n_stride;
-    noise += pb * batch_noise + pc * axis_stride(sb_, 1); costs += pr * N; gF += jh_plant_of(sb_.plants, (int)pb) * batch_image + pc * axis_stride(sb_, 2);
+    noise += pb * batch_noise + pc * axis_stride(sb_, 1); costs += pr * N; gF += jh_plant_of(sb_.plants, (int)pr, (int)pb) * batch_image + pc * axis_stride(sb_, 2);
     if (trace) trace += pr * N * H * 15;
     if (NOVF > 0 && ovf_all_) ovf_all_ += pr * N * (NOVF * POOL_F);  // (the overflow rows are indexed by rollout: a problem's N rows behind the one before)
   }

@@ -121,14 +121,17 @@ struct jh_rollout_args {
 //    first rollout of every later problem keeps its noise.  0: every problem's local rollout 0 is its nominal, the independent problems of jh_plan_step_batch.
 //  - the table: problem b reads image plant[b] of the set, a byte per problem packed four to a word, if `mapped`; image b otherwise (the identity needs no table, and a
 //    batch has up to 65535 problems).  It travels by value and is read with one uniform load of the word that holds the byte.
-// Both are wave-uniform arithmetic on kernel arguments and blockIdx.y, done once at the top of the kernel.
+//  - the table has two dimensions where the launch has a controller axis in blockIdx.z (jh_plan_step_randomized_batch: every controller draws its own assignment):
+//    the entry of (controller c, problem b) is c * gridDim.y + b, controller-major, JH_MAX_FLEET_PLANT_BLOCKS entries in all.  With gridDim.z == 1 that is b.
+// Both are wave-uniform arithmetic on kernel arguments and the block indices, done once at the top of the kernel.
 struct jh_plant_axis {
   int n_stride = 0;
   unsigned mapped = 0;
-  unsigned plant[JH_MAX_PLANT_BLOCKS / 4] = {};
+  unsigned plant[JH_MAX_FLEET_PLANT_BLOCKS / 4] = {};
 };
-__host__ __device__ inline int jh_plant_of(const jh_plant_axis& p, int b) { return p.mapped ? (int)((p.plant[b >> 2] >> ((b & 3) << 3)) & 0xffu) : b; }
-inline void jh_plant_set(jh_plant_axis& p, int b, int plant) { p.mapped = 1u; p.plant[b >> 2] |= (unsigned)(plant & 0xff) << ((b & 3) << 3); }
+// the image of problem b, whose entry of the table is e (e == b in a launch without a controller axis)
+__host__ __device__ inline int jh_plant_of(const jh_plant_axis& p, int e, int b) { return p.mapped ? (int)((p.plant[e >> 2] >> ((e & 3) << 3)) & 0xffu) : b; }
+inline void jh_plant_set(jh_plant_axis& p, int e, int plant) { p.mapped = 1u; p.plant[e >> 2] |= (unsigned)(plant & 0xff) << ((e & 3) << 3); }
 
 // What the leap kernel's launch for B problems (jh_plan_step_batch) takes on top: the record is problem 0's, `blk_stride` / `noise_stride` floats lead to the next problem's;
 // `images`: problem 0's float section, `image_stride` floats to the next problem's (m->d_f and 0: one image for all); `ints`: the int section on the device (m->d_i, or a
@@ -136,7 +139,8 @@ inline void jh_plant_set(jh_plant_axis& p, int b, int plant) { p.mapped = 1u; p.
 // (groups, B, C), controller c's blocks, noise and images lie c times the `*_stride_c` floats behind controller 0's, and the (controller, problem) pair c * B + b owns the
 // costs, trace and overflow rows.  The default is the launch without that axis.
 // `plants` (jh_plan_step_randomized): the problems are slices of ONE problem's rollouts, each on a plant of the set -- problem b's global rollout index starts
-// plants.n_stride behind problem b - 1's, and its image is plants' table entry b instead of b.  The default, 0 and the identity, is every other launch.
+// plants.n_stride behind problem b - 1's, and its image is plants' table entry b instead of b (entry c * B + b with a controller axis, jh_plan_step_randomized_batch).  The default, 0 and the identity, is every
+// other launch.
 struct jh_rollout_batch {
   const float* images; long long image_stride; const int* ints;
   int B; long long blk_stride, noise_stride;

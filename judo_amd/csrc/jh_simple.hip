@@ -243,7 +243,7 @@ __global__ __launch_bounds__(jh_upd::kUB) void k_plan_step_batch(const float* __
   // (p, the plant axis of jh_internal.h: the problem's first global rollout index and the image its table names; 0 and image b for the independent problems of every caller so far)
   const int b = blockIdx.y;
   const jh_upd::TailArgs a = jh_upd::batch_problem(base, s, b);
-  rollout_cost_body<T, jh_upd::kUB>(P + jh_plant_of(p, b) * s.image, x0 + b * s.blk, a.src.nominal, a.src.noise, a.src.ldn, a.src.sigma, W, a.src.lohi, tp + b * s.blk, a.N, a.n_offset + b * p.n_stride, H, K,
+  rollout_cost_body<T, jh_upd::kUB>(P + jh_plant_of(p, b, b) * s.image, x0 + b * s.blk, a.src.nominal, a.src.noise, a.src.ldn, a.src.sigma, W, a.src.lohi, tp + b * s.blk, a.N, a.n_offset + b * p.n_stride, H, K,
                                     const_cast<float*>(a.costs), nullptr, const_cast<float*>(a.trace));
   __syncthreads();
   jh_upd::batch_done(s, jh_upd::update_tail_body(a));
@@ -254,9 +254,10 @@ __global__ __launch_bounds__(kBlock) void k_rollout_cost_batch(const float* __re
                                                                jh_upd::TailArgs base, jh_upd::BatchArgs s, jh_upd::ControllerAxis z, jh_plant_axis p) {
   // (blockIdx.z: the controller of jh_plan_step_ensemble_batch, whose members are the problems of blockIdx.y; every other launch has gridDim.z == 1 and z's offsets are 0)
   // (p, the plant axis of jh_plan_step_randomized: the problems are blocks of one problem's rollouts -- block b starts at global rollout b * p.n_stride and runs on the image its table names)
+  // (... and of jh_plan_step_randomized_batch, which has both axes: the table's entry is the (controller, block) pair's, c * gridDim.y + b)
   const int b = blockIdx.y, c = blockIdx.z;
   const jh_upd::TailArgs a = jh_upd::batch_controller(jh_upd::batch_problem(base, s, b), s, z, c, (int)gridDim.y);
-  rollout_cost_body<T, kBlock>(P + jh_plant_of(p, b) * s.image + c * z.image, x0 + b * s.blk + c * z.blk, a.src.nominal, a.src.noise, a.src.ldn, a.src.sigma, W, a.src.lohi, tp + b * s.blk + c * z.blk, a.N,
+  rollout_cost_body<T, kBlock>(P + jh_plant_of(p, c * (int)gridDim.y + b, b) * s.image + c * z.image, x0 + b * s.blk + c * z.blk, a.src.nominal, a.src.noise, a.src.ldn, a.src.sigma, W, a.src.lohi, tp + b * s.blk + c * z.blk, a.N,
                                a.n_offset + b * p.n_stride, H, K, const_cast<float*>(a.costs), nullptr, const_cast<float*>(a.trace));
 }
 #ifdef JH_TAIL_TICKS

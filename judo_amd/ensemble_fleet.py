@@ -106,7 +106,8 @@ class EnsembleFleet(ControllerFleet):
     def _check_member(self, i: int, c, first) -> None:
         if isinstance(c, RandomizedController):
             raise ValueError(f"fleet member {i} is a RandomizedController: it rolls each candidate out on one plant of its set, not on all of them, and its plan step "
-                             "(jh_plan_step_randomized) has no batched launch yet; it plans alone")
+                             "(jh_plan_step_randomized) is another launch; randomised controllers share one in a RandomizedFleet "
+                             "(judo_amd.randomized_fleet.make_randomized_fleet)")
         if not isinstance(c, EnsembleController):
             raise ValueError(f"fleet member {i} is a {type(c).__name__}, not an EnsembleController: controllers that believe one plant share a launch in a ControllerFleet")
         world, _ = world_info(c.group)

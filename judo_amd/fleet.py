@@ -118,6 +118,7 @@ class ControllerFleet:
     `_check_member`, `_models`, `_trace_floats` and `_launch` and keeps the loop."""
 
     _ensemble_members = False  # members are `EnsembleController`s, each planning against M plants (EnsembleFleet)
+    _randomized_members = False  # members are `RandomizedController`s, each spreading its rollout blocks over the M plants of its set (RandomizedFleet)
 
     def __init__(self, controllers: Sequence[Controller]) -> None:
         self.controllers = list(controllers)
@@ -139,7 +140,7 @@ class ControllerFleet:
                 c.rollout_backend.engine, c.rollout_backend.policy = first.rollout_backend.engine, first.rollout_backend.policy
             self._policy_out: torch.Tensor | None = None  # (B * n, 12): the members' `_last_policy_output` are views of it
         for c in self.controllers[1:]:  # one image of the model constants on the device for every member whose image is member 0's, byte for byte
-            if not self._ensemble_members and c.model is not self.model and c.model._blob == self.model._blob:
+            if not (self._ensemble_members or self._randomized_members) and c.model is not self.model and c.model._blob == self.model._blob:
                 c.model = c.task._gpu = c.rollout_backend.model = self.model
         self._model_set: GpuModelSet | None = None  # members with images of their own (randomised physics): their float sections side by side, made at the first plan step
         self._bufs: _FleetBuffers | None = None
@@ -171,10 +172,11 @@ class ControllerFleet:
                 "default_policy_command": np.asarray(t.default_policy_command).tolist()}
 
     def _check_member(self, i: int, c: Controller, first: Controller) -> None:
-        if isinstance(c, RandomizedController):
+        if isinstance(c, RandomizedController) and not self._randomized_members:
             # (its iteration shape reads "plan_step" too, and the batched plan step would run every block on `c.model`, plant 0, and drop the assignment without a word)
             raise ValueError(f"fleet member {i} is a RandomizedController: its plan step spreads the rollout blocks over the plants of its own set "
-                             "(jh_plan_step_randomized), which no batched launch does yet; it plans alone")
+                             "(jh_plan_step_randomized), which a ControllerFleet's launch does not do; randomised controllers share a launch in a RandomizedFleet "
+                             "(judo_amd.randomized_fleet.make_randomized_fleet)")
         if isinstance(c, EnsembleController) and not self._ensemble_members:
             # (its iteration shape reads "plan_step", but the batched plan step would run on `c.model`, plant 0 alone, and drop the ensemble without a word)
             raise ValueError(f"fleet member {i} is an EnsembleController: a ControllerFleet plans every member on one plant; ensemble controllers share a launch in an "

@@ -67,6 +67,14 @@ def plant_of_rollout(assignment: Sequence[int], num_rollouts: int) -> np.ndarray
     return np.repeat(np.asarray(assignment, dtype=np.int64), N // G)
 
 
+def check_task(task: Task) -> None:
+    """The tasks without a randomised plan step, refused before any model is made; raises ValueError."""
+    if task.uses_locomotion_policy:
+        raise ValueError("the Spot policy tasks have no randomised plan step: their iteration is the materialise path (spline, policy rollout, reward, update), not one library call")
+    if task.desc.get("family", task.desc["task"]) == "fr3_pick":
+        raise ValueError("fr3_pick has no randomised plan step: its phase is chosen per problem on the host and its kernel has no batched launch")
+
+
 class RandomizedController(Controller):
     """A `Controller` whose plan step rolls block g of its candidates out on plant `assignment[g]` and updates on the N costs.  Everything else -- `update_states`,
     `action(t)`, `traces`, `max_opt_iters`, the three optimizers, the `none` / `min_max` normalisers -- is the controller's own.
@@ -76,10 +84,7 @@ class RandomizedController(Controller):
 
     def __init__(self, controller_config: ControllerConfig, task: Task, optimizer, descriptions: Sequence[dict], blocks: int | None = None,
                  weights: Sequence[float] | None = None, device: torch.device | None = None) -> None:
-        if task.uses_locomotion_policy:
-            raise ValueError("the Spot policy tasks have no randomised plan step: their iteration is the materialise path (spline, policy rollout, reward, update), not one library call")
-        if task.desc.get("family", task.desc["task"]) == "fr3_pick":
-            raise ValueError("fr3_pick has no randomised plan step: its phase is chosen per problem on the host and its kernel has no batched launch")
+        check_task(task)
         check_descriptions(descriptions)
         self._descriptions = list(descriptions)
         M = len(self._descriptions)
@@ -232,4 +237,4 @@ def make_randomized_controller(task: str | Task, optimizer: str, descriptions: S
     return RandomizedController(ctrl_cfg, task, opt_cls(opt_cfg, task.nu), descriptions, blocks=blocks, weights=weights, device=device)
 
 
-__all__ = ["MAX_PLANT_BLOCKS", "RandomizedController", "blocks_from_weights", "check_assignment", "make_randomized_controller", "plant_of_rollout"]
+__all__ = ["MAX_PLANT_BLOCKS", "RandomizedController", "blocks_from_weights", "check_assignment", "check_task", "make_randomized_controller", "plant_of_rollout"]
