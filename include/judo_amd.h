@@ -290,7 +290,7 @@ int jh_plan_step(const jh_model* m, void* blk_dev, const void* blk_host, size_t 
  * the single call's code on offset pointers (cartpole, cylinder_push: one launch with blockIdx.y = problem, or two above jh_model_one_launch_max_knots; the leap family:
  * the rollout kernel on the static grid (groups, B) -- the latency mode chosen from B * N rollouts, no persistent queue -- then the batched update tail).  B = 1 takes the same
  * code.  JH_ERR_INVALID: B < 1, B > 65535 (the grid's second dimension), a stride smaller than a block / a noise slice / an output record, a forced one-launch plan step that
- * does not fit.  JH_ERR_UNSUPPORTED: fr3_pick (its phase is a per-problem host decision, judo/tasks/fr3_pick.py:191-223) and the cross-check kernel generations.  The Spot
+ * does not fit.  JH_ERR_UNSUPPORTED: fr3_pick (its phase is a per-problem host decision, judo/tasks/fr3_pick.py:191-223: jh_plan_step_batch_phases below takes one per problem) and the cross-check kernel generations.  The Spot
  * policy tasks, whose iteration is the materialise path, batch through jh_spline_controls_batch / jh_policy_rollout_batch / jh_update_fused_batch below; the sharded and the
  * plugin-reward paths have no batched form. */
 size_t jh_plan_batch_scratch_floats(int B, int N, int K, int nu);
@@ -298,6 +298,22 @@ int jh_plan_step_batch(const jh_model* m, int B, void* blk_dev, const void* blk_
                        const float* noise, int ldn, size_t noise_stride_floats, const float* W, int N, int H, int K, float* costs, float* trace, int mode, float lambda, int k,
                        int tie_high, int E, int row_floats, int colmajor, float* scratch, float* out, size_t out_stride_floats, void* out_host_mark, void* const* timing,
                        void* stream);
+/* jh_plan_step_batch for fr3_pick: B arms, each in its own phase, in one call and one wait instead of B jh_plan_step calls back to back (the reference's shipped
+ * configuration, 64 rollouts x 250 steps, is 16-64 one-wave workgroups per call).  jh_plan_step takes the phase (LIFT / MOVE / PLACE / HOMING, judo/tasks/fr3_pick.py:191-223:
+ * a host decision from the controller's own state) as an argument; here it is one more word of every problem's packed block,
+ *   packed block   [x0 | nominal | sigma | task params | ctrl bounds | ... phase ...], the phase word at float offset o_phase (4 * (o_phase + 1) <= blk_bytes),
+ * a FLOAT holding exactly 0.0, 1.0, 2.0 or 3.0 -- the block is a block of floats everywhere else.  The rollout kernel runs on the grid (groups, B), reads its problem's
+ * word once per workgroup with a uniform load and converts it once; the latency mode is chosen from B * N rollouts.  Everything else -- blocks, strides, noise, costs,
+ * trace (6 floats per step), scratch, out, the completion mark, timing -- is jh_plan_step_batch's.  Problem b's costs, nominal, sigma and trace records are bit for bit
+ * those of jh_plan_step(..., phase_b, ...) on its sub-block; both builds of the fr3 kernel (jh_model_fr3_build) are served.  The counters of jh_model_stats are the model's,
+ * whichever problem a rollout belongs to.
+ * JH_ERR_UNSUPPORTED: any model that is not fr3_pick (jh_plan_step_batch plans those).  JH_ERR_INVALID: o_phase < 0 or outside the block; a phase word that is not
+ * exactly 0, 1, 2 or 3 (read from blk_host before anything is launched; the message names the problem); K > 8; everything jh_plan_step_batch refuses.  jh_plan_step_batch and
+ * the model-set, ensemble and randomised entries keep refusing fr3_pick: a model image per problem is not available for it. */
+int jh_plan_step_batch_phases(const jh_model* m, int B, void* blk_dev, const void* blk_host, size_t blk_bytes, size_t blk_stride_bytes, int o_nominal, int o_sigma, int o_tp, int o_lohi,
+                              int o_phase, const float* noise, int ldn, size_t noise_stride_floats, const float* W, int N, int H, int K, float* costs, float* trace, int mode,
+                              float lambda, int k, int tie_high, int E, int row_floats, int colmajor, float* scratch, float* out, size_t out_stride_floats, void* out_host_mark,
+                              void* const* timing, void* stream);
 /* jh_plan_step_batch with a model image PER PROBLEM (randomised physics: B planners of one task with B cube masses or friction coefficients, a bank of mass hypotheses,
  * one controller over perturbed plants).  The reference has no counterpart.  A model set is B model handles whose FLOAT sections sit in one device buffer, a fixed stride
  * apart; everything else -- the int section (topology, pair lists, lane lists), the dimensions, the kernel build and its settings -- is member 0's and must be the same in

@@ -612,15 +612,18 @@ extern "C" int jh_plan_step(const jh_model* m, void* blk_dev, const void* blk_ho
 // problem b + 1's from problem b's -- m->d_f and 0 for jh_plan_step_batch, a model set's buffer and stride for jh_plan_step_batch_models: one code path.  `ints`: the int
 // section the leap kernel reads -- m->d_i, or a model set's copy without pair tables.
 static int plan_step_batch(const char* who, const jh_model* m, const float* images, long long image_stride, const int* ints, int B, void* blk_dev, const void* blk_host, size_t blk_bytes, size_t blk_stride_bytes,
-                           int o_nominal, int o_sigma, int o_tp, int o_lohi, const float* noise, int ldn, size_t noise_stride_floats, const float* W, int N, int H, int K, float* costs,
+                           int o_nominal, int o_sigma, int o_tp, int o_lohi, int o_phase, const float* noise, int ldn, size_t noise_stride_floats, const float* W, int N, int H, int K, float* costs,
                            float* trace, int mode, float lambda, int k, int tie_high, int E, int row_floats, int colmajor, float* scratch, float* out, size_t out_stride_floats,
                            void* out_host_mark, void* const* timing, void* stream) {
   JH_REQUIRE(m && blk_dev && blk_host && out && scratch && noise && W && costs, "%s: null pointer", who);
-  if (m->kind == JH_TASK_FR3_PICK) { jh_set_error("%s: fr3_pick has no batched plan step (its phase is chosen per problem on the host)", who); return JH_ERR_UNSUPPORTED; }
+  // o_phase: the float offset of every block's phase word (jh_plan_step_batch_phases, fr3_pick alone), or -1: an entry without one, which keeps refusing fr3_pick
+  if (m->kind == JH_TASK_FR3_PICK && o_phase < 0) { jh_set_error("%s: fr3_pick has no batched plan step (its phase is chosen per problem on the host) behind this entry: jh_plan_step_batch_phases takes a phase word per problem", who); return JH_ERR_UNSUPPORTED; }
+  if (m->kind != JH_TASK_FR3_PICK && o_phase >= 0) { jh_set_error("%s: a phase word per problem is fr3_pick's alone; jh_plan_step_batch plans this model", who); return JH_ERR_UNSUPPORTED; }
   if (m->kind == JH_TASK_LEAP_CUBE && m->kernel_gen != 3) { jh_set_error("%s: only kernel generation 3 of the leap family has a batched launch (this model runs %d)", who, m->kernel_gen); return JH_ERR_UNSUPPORTED; }
   JH_REQUIRE(B >= 1, "%s: B must be at least 1 (B=%d)", who, B);
   JH_REQUIRE(B <= 65535, "%s: B = %d exceeds the 65535 problems of a launch (the grid's second dimension)", who, B);
   JH_REQUIRE(N > 0 && H > 0 && K >= 1, "%s: N, H, K must be positive (N=%d H=%d K=%d)", who, N, H, K);
+  JH_REQUIRE(o_phase < 0 || K <= 8, "%s: the cooperative arm kernel keeps at most 8 knots per actuator in registers (K=%d)", who, K);
   JH_REQUIRE(ldn >= N, "%s: ldn (%d) < N (%d)", who, ldn, N);
   const int KU = K * m->nu;
   JH_REQUIRE(KU <= JH_MAX_KNOT_DIM, "%s: K*nu = %d exceeds %d", who, KU, JH_MAX_KNOT_DIM);
@@ -639,6 +642,13 @@ static int plan_step_batch(const char* who, const jh_model* m, const float* imag
   const bool closed = m->kind == JH_TASK_CARTPOLE || m->kind == JH_TASK_CYLINDER_PUSH;
   const jh_engine_build* eb = engine_build(m);
   if (!closed && !(eb && eb->rollout_cost_batch)) { jh_set_error("%s: no batched kernel for this model", who); return JH_ERR_UNSUPPORTED; }
+  if (o_phase >= 0) {  // the B phase words, on the host, before anything is enqueued: the kernel converts the word and branches on it
+    JH_REQUIRE(sizeof(float) * ((size_t)o_phase + 1) <= blk_bytes, "%s: o_phase = %d lies outside a block of %zu bytes", who, o_phase, blk_bytes);
+    for (int p = 0; p < B; p++) {
+      const float w = reinterpret_cast<const float*>(static_cast<const char*>(blk_host) + (size_t)p * blk_stride_bytes)[o_phase];
+      JH_REQUIRE(w == 0.f || w == 1.f || w == 2.f || w == 3.f, "%s: the phase word of problem %d is %g, not exactly 0, 1, 2 or 3 (LIFT, MOVE, PLACE, HOMING)", who, p, (double)w);
+    }
+  }
   hipStream_t st = (hipStream_t)stream;
   const float* b = (const float*)blk_dev;
   if (blk_dev != blk_host) { const int rc = jh_upload_async(blk_dev, blk_host, (size_t)(B - 1) * blk_stride_bytes + blk_bytes, stream); if (rc != JH_OK) return rc; }
@@ -660,7 +670,8 @@ static int plan_step_batch(const char* who, const jh_model* m, const float* imag
     if (closed) rc = jh_simple_rollout_cost_batch(m, images, b, b + o_tp, W, H, K, a, s, st);
     else {
       const jh_rollout_args ra = {b, b + o_nominal, noise, ldn, b + o_sigma, W, b + o_lohi, b + o_tp, 0, N, 0, H, K, costs, nullptr, trace};
-      const jh_rollout_batch rb = {images, image_stride, ints, B, s.blk, s.noise};
+      jh_rollout_batch rb = {images, image_stride, ints, B, s.blk, s.noise};
+      rb.o_phase = o_phase;
       rc = eb->rollout_cost_batch(m, ra, rb, st);
     }
     if (rc == JH_OK && timing) JH_HIP(hipEventRecord((hipEvent_t)timing[1], st));
@@ -677,8 +688,19 @@ extern "C" int jh_plan_step_batch(const jh_model* m, int B, void* blk_dev, const
                                   int tie_high, int E, int row_floats, int colmajor, float* scratch, float* out, size_t out_stride_floats, void* out_host_mark, void* const* timing,
                                   void* stream) {
   JH_REQUIRE(m != nullptr, "plan_step_batch: null pointer");
-  return plan_step_batch("plan_step_batch", m, m->d_f, 0, m->d_i, B, blk_dev, blk_host, blk_bytes, blk_stride_bytes, o_nominal, o_sigma, o_tp, o_lohi, noise, ldn, noise_stride_floats, W, N, H, K, costs, trace,
+  return plan_step_batch("plan_step_batch", m, m->d_f, 0, m->d_i, B, blk_dev, blk_host, blk_bytes, blk_stride_bytes, o_nominal, o_sigma, o_tp, o_lohi, -1, noise, ldn, noise_stride_floats, W, N, H, K, costs, trace,
                          mode, lambda, k, tie_high, E, row_floats, colmajor, scratch, out, out_stride_floats, out_host_mark, timing, stream);
+}
+
+// jh_plan_step_batch for fr3_pick (include/judo_amd.h): the same code path with a phase word in every problem's block.
+extern "C" int jh_plan_step_batch_phases(const jh_model* m, int B, void* blk_dev, const void* blk_host, size_t blk_bytes, size_t blk_stride_bytes, int o_nominal, int o_sigma, int o_tp, int o_lohi,
+                                         int o_phase, const float* noise, int ldn, size_t noise_stride_floats, const float* W, int N, int H, int K, float* costs, float* trace, int mode,
+                                         float lambda, int k, int tie_high, int E, int row_floats, int colmajor, float* scratch, float* out, size_t out_stride_floats, void* out_host_mark,
+                                         void* const* timing, void* stream) {
+  JH_REQUIRE(m != nullptr, "plan_step_batch_phases: null pointer");
+  JH_REQUIRE(o_phase >= 0, "plan_step_batch_phases: negative block offset (o_phase=%d)", o_phase);
+  return plan_step_batch("plan_step_batch_phases", m, m->d_f, 0, m->d_i, B, blk_dev, blk_host, blk_bytes, blk_stride_bytes, o_nominal, o_sigma, o_tp, o_lohi, o_phase, noise, ldn, noise_stride_floats, W, N,
+                         H, K, costs, trace, mode, lambda, k, tie_high, E, row_floats, colmajor, scratch, out, out_stride_floats, out_host_mark, timing, stream);
 }
 
 // ---- model sets: B images of one model's float section in one device buffer, a fixed stride apart (include/judo_amd.h) ----
@@ -810,7 +832,7 @@ extern "C" int jh_plan_step_batch_models(const jh_model_set* set, void* blk_dev,
                                          int k, int tie_high, int E, int row_floats, int colmajor, float* scratch, float* out, size_t out_stride_floats, void* out_host_mark,
                                          void* const* timing, void* stream) {
   JH_REQUIRE(set != nullptr, "plan_step_batch_models: null pointer");
-  return plan_step_batch("plan_step_batch_models", set->m0, set->d_images, (long long)set->stride, set->tables ? set->m0->d_i : set->d_i_plain, set->B, blk_dev, blk_host, blk_bytes, blk_stride_bytes, o_nominal, o_sigma, o_tp, o_lohi, noise, ldn,
+  return plan_step_batch("plan_step_batch_models", set->m0, set->d_images, (long long)set->stride, set->tables ? set->m0->d_i : set->d_i_plain, set->B, blk_dev, blk_host, blk_bytes, blk_stride_bytes, o_nominal, o_sigma, o_tp, o_lohi, -1, noise, ldn,
                          noise_stride_floats, W, N, H, K, costs, trace, mode, lambda, k, tie_high, E, row_floats, colmajor, scratch, out, out_stride_floats, out_host_mark, timing, stream);
 }
 

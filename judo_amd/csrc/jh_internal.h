@@ -141,11 +141,15 @@ inline void jh_plant_set(jh_plant_axis& p, int e, int plant) { p.mapped = 1u; p.
 // `plants` (jh_plan_step_randomized): the problems are slices of ONE problem's rollouts, each on a plant of the set -- problem b's global rollout index starts
 // plants.n_stride behind problem b - 1's, and its image is plants' table entry b instead of b (entry c * B + b with a controller axis, jh_plan_step_randomized_batch).  The default, 0 and the identity, is every
 // other launch.
+// `o_phase` (jh_plan_step_batch_phases, the fr3 kernel alone): the float offset of the problem's phase word in its packed block, whose first word is the record's x0 --
+// the one argument of the single launch that is a problem's own.  -1: the launch has no phase (the leap kernel ignores the field).  The fr3 launcher implements the
+// record's first two lines only and refuses C > 1, a plant axis and image_stride != 0.
 struct jh_rollout_batch {
   const float* images; long long image_stride; const int* ints;
   int B; long long blk_stride, noise_stride;
   int C = 1; long long blk_stride_c = 0, noise_stride_c = 0, image_stride_c = 0;
   jh_plant_axis plants = {};
+  int o_phase = -1;
 };
 
 // One build of an articulated product kernel: each translation unit that instantiates k_leap_v5 or k_fr3_v6 defines its row, and jh_api.hip's engine_build() maps a model
@@ -154,7 +158,7 @@ struct jh_engine_build {
   const char* name;                       // for messages
   bool (*accepts)(const jh_model* m);     // the launchers' own acceptance test, on the model's own image
   int (*rollout_cost)(const jh_model* m, const jh_rollout_args& a, hipStream_t st);
-  int (*rollout_cost_batch)(const jh_model* m, const jh_rollout_args& a, const jh_rollout_batch& s, hipStream_t st);  // null: the build has no batched launch (fr3)
+  int (*rollout_cost_batch)(const jh_model* m, const jh_rollout_args& a, const jh_rollout_batch& s, hipStream_t st);  // null: the build has no batched launch (none of the shipped rows; fr3: a phase per problem, jh_rollout_batch::o_phase)
   int (*materialize)(const jh_model* m, const float* x0, int x0_batched, const float* controls, int N, int H, float* states, float* sensors, hipStream_t st);
   int contact_capacity;                   // contacts a rollout can hold (jh_model_limits out[3]), from the build's own constants
 };

@@ -78,7 +78,7 @@ class EnsembleController(Controller):
         if task.uses_locomotion_policy:
             raise ValueError("the Spot policy tasks have no ensemble plan step: their iteration is the materialise path (spline, policy rollout, reward, update), not one library call")
         if task.desc.get("family", task.desc["task"]) == "fr3_pick":
-            raise ValueError("fr3_pick has no ensemble plan step: its phase is chosen per problem on the host and its kernel has no batched launch")
+            raise ValueError("fr3_pick has no ensemble plan step: its phase is chosen per problem on the host and its batched launch (judo_amd.fr3_fleet) reads one model image, not a model set")
         check_descriptions(descriptions)
         self._descriptions = list(descriptions)
         task.desc = self._descriptions[0]

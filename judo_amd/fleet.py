@@ -45,7 +45,7 @@ class _MemberBuffers:
     def __init__(self, fleet: "_FleetBuffers", i: int) -> None:
         f = fleet
         self.sizes, self.offsets = f.sizes, f.offsets
-        nblk = f.nblk
+        nblk = f.nblk  # (the five sections: a fleet's extra words lie behind them, inside the stride, and are the fleet's to write)
         self.host_np = f.host_np[i * f.blk_stride : i * f.blk_stride + nblk]
         self.host_ptr, self.nblk_bytes = f.host_ptr + 4 * i * f.blk_stride, 4 * nblk
         self.blk = f.blk[i * f.blk_stride : i * f.blk_stride + nblk]
@@ -80,15 +80,17 @@ class _MemberBuffers:
 
 class _FleetBuffers:
     """Everything a fleet's plan step touches, for B problems of one size: B packed blocks in one pinned host buffer (and its device copy), the noise, costs,
-    trace rows, update scratch, and the pinned output block with its completion word."""
+    trace rows, update scratch, and the pinned output block with its completion word.  `extra`: words of every block behind `bounds` that belong to the fleet, not to
+    the member's five sections (FR3Fleet: the phase word); a member's views end in front of them."""
 
-    def __init__(self, dev: torch.device, B: int, N: int, K: int, nu: int, nx: int, ntp: int, E: int) -> None:
+    def __init__(self, dev: torch.device, B: int, N: int, K: int, nu: int, nx: int, ntp: int, E: int, extra: int = 0) -> None:
         L = _lib.lib()
         self.dev, self.B, self.N, self.K, self.nu, self.E = dev, B, N, K, nu, E
         self.sizes = [nx, K * nu, K * nu, ntp, 2 * nu]
         self.nblk = sum(self.sizes)
         self.offsets = [int(v) for v in np.cumsum([0] + self.sizes)]
-        self.blk_stride = self.nblk  # floats from a member's block to the next one's
+        self.extra = extra
+        self.blk_stride = self.nblk + extra  # floats from a member's block to the next one's
         self.host = torch.zeros(B * self.blk_stride, dtype=torch.float32).pin_memory()
         self.host_np, self.host_ptr = self.host.numpy(), self.host.data_ptr()
         self.blk = torch.zeros(B * self.blk_stride, dtype=torch.float32, device=dev)
@@ -119,6 +121,8 @@ class ControllerFleet:
 
     _ensemble_members = False  # members are `EnsembleController`s, each planning against M plants (EnsembleFleet)
     _randomized_members = False  # members are `RandomizedController`s, each spreading its rollout blocks over the M plants of its set (RandomizedFleet)
+    _fr3_members = False  # members are fr3_pick controllers, whose phase travels in the packed block (judo_amd.fr3_fleet.FR3Fleet)
+    _block_extra_words = 0  # words of every packed block behind the bounds that the fleet writes itself (FR3Fleet: 1, the phase word)
 
     def __init__(self, controllers: Sequence[Controller]) -> None:
         self.controllers = list(controllers)
@@ -181,8 +185,9 @@ class ControllerFleet:
             # (its iteration shape reads "plan_step", but the batched plan step would run on `c.model`, plant 0 alone, and drop the ensemble without a word)
             raise ValueError(f"fleet member {i} is an EnsembleController: a ControllerFleet plans every member on one plant; ensemble controllers share a launch in an "
                              "EnsembleFleet (judo_amd.ensemble_fleet.make_ensemble_fleet)")
-        if c.model is not None and c.model.desc.get("family", c.model.task) == "fr3_pick":
-            raise ValueError(f"fleet member {i}: fr3_pick has no batched plan step (its phase is chosen per problem on the host)")
+        if c.model is not None and c.model.desc.get("family", c.model.task) == "fr3_pick" and not self._fr3_members:
+            raise ValueError(f"fleet member {i}: fr3_pick has no batched plan step (its phase is chosen per problem on the host) in a ControllerFleet: fr3_pick controllers "
+                             "share a launch in an FR3Fleet (judo_amd.fr3_fleet.make_fr3_fleet)")
         if c.device != first.device:
             raise ValueError(f"fleet member {i} is on {c.device}, the fleet on {first.device}")
         mine, want = self._shared(c), self._shared(first)
@@ -230,7 +235,7 @@ class ControllerFleet:
 
     def _buffers(self, key: tuple) -> _FleetBuffers:
         if self._bufs_key != key:
-            self._bufs, self._bufs_key = _FleetBuffers(self.device, *key), key
+            self._bufs, self._bufs_key = _FleetBuffers(self.device, *key, extra=self._block_extra_words), key
         return self._bufs
 
     def _draw_noise(self, fb: _FleetBuffers, N: int, K: int, nu: int) -> torch.Tensor:

@@ -1,0 +1,74 @@
+"""B fr3_pick controllers planned in ONE launch (`jh_plan_step_batch_phases`, include/judo_amd.h).
+
+fr3_pick is the one model family whose plan step takes a host decision per problem: `FR3Pick.pre_rollout` picks the phase (LIFT / MOVE / PLACE / HOMING,
+judo/tasks/fr3_pick.py:191-223) from the controller's own state, and the kernel's step cost and its choice of distance sensors depend on it.  B arms are in B phases,
+so `ControllerFleet` and `jh_plan_step_batch`, whose problems share every scalar argument, refuse the family.  An `FR3Fleet` is `ControllerFleet`'s loop around another
+call: every member's block carries one more word behind its bounds, the member's phase as a float, and the rollout kernel on the grid (groups, B) reads its problem's word.
+The reference's shipped configuration is 64 rollouts x 250 steps, a handful of one-wave workgroups per controller: eight arms fit the GPU side by side
+(profiles/fr3_fleet.md has the measured sweep).
+
+What the members share is what `ControllerFleet`'s members share, and ONE model image: a model set per problem is not available for fr3_pick, so members with perturbed
+physics are refused, as is a mixture of the default and the self-collision build.  State, time, goal, seed, nominal, CEM sigma and the phase are a member's own.
+Afterwards each member is bit for bit where its own `update_action()` would have left it."""
+
+from __future__ import annotations
+
+import torch
+
+from judo_amd import _lib
+from judo_amd.controller import Controller, make_controller_for
+from judo_amd.device import GpuModelSet
+from judo_amd.fleet import ControllerFleet, _FleetBuffers
+from judo_amd.tasks import FR3Pick
+
+
+class FR3Fleet(ControllerFleet):
+    """B fr3_pick `Controller`s of one optimizer kind whose plan steps run as one launch.  `fleet[i]` is an ordinary `Controller`: `update_states`, `optimizer.seed`,
+    `action(t)`, `traces`, `rewards` and `task.phase` work per member as they do on a controller alone."""
+
+    _fr3_members = True
+    _block_extra_words = 1  # the phase word, behind the bounds
+
+    def _check_member(self, i: int, c: Controller, first: Controller) -> None:
+        if c.model is None or c.model.desc.get("family", c.model.task) != "fr3_pick" or not isinstance(c.task, FR3Pick):
+            raise ValueError(f"fleet member {i} is no fr3_pick controller ({type(c.task).__name__}): an FR3Fleet plans fr3_pick alone; every other model family shares a "
+                             "launch in a ControllerFleet (judo_amd.fleet.make_controller_fleet)")
+        if c.task.self_collision != first.task.self_collision or c.model.self_collision != first.model.self_collision:
+            raise ValueError(f"fleet member {i} differs from member 0 in self_collision: the launch runs one build of the fr3 kernel")
+        if c.model is not first.model and c.model._blob != first.model._blob:
+            raise ValueError(f"fleet member {i} has another model image than member 0: an FR3Fleet plans every member on ONE image; a model set per problem "
+                             "(randomised physics) is not available for fr3_pick")
+        super()._check_member(i, c, first)
+
+    def _models(self) -> GpuModelSet | None:
+        return None  # (one image: byte-identical members were pointed at member 0's model when the fleet was made)
+
+    def _launch(self, lib, model_set, fb: _FleetBuffers, in_place: bool, noise: torch.Tensor, W, N: int, H: int, K: int, nu: int, costs: torch.Tensor, nfl: int,
+                update_args: tuple, E_t: int, row: int, colmajor: int, stream) -> None:
+        """The members' phases (decided by their `pre_rollout` in this iteration) into the phase words, then the B plan steps as one call."""
+        cs = self.controllers
+        off = fb.offsets
+        for i, c in enumerate(cs):
+            fb.host_np[i * fb.blk_stride + fb.nblk] = float(int(c.task.phase))
+        mode, lam, k_el, tie = update_args
+        st = lib.jh_plan_step_batch_phases(self.model.handle, len(cs), fb.host_ptr if in_place else fb.blk.data_ptr(), fb.host_ptr, 4 * (fb.nblk + fb.extra), 4 * fb.blk_stride, off[1], off[2],
+                                           off[3], off[4], fb.nblk, noise.data_ptr(), N, K * nu * N, _lib.ptr(W), N, H, K, costs.data_ptr(), fb.trace_buf.data_ptr() if nfl else None, mode, lam,
+                                           k_el, tie, E_t, row, colmajor, fb.scratch.data_ptr(), fb.out_host_ptr, fb.out_stride, fb.done.data_ptr() if in_place else fb.out_host_ptr, None, stream)
+        _lib.check(st, "jh_plan_step_batch_phases")
+
+
+def make_fr3_fleet(optimizer: str, B: int, device: torch.device | None = None, self_collision: bool = False) -> FR3Fleet:
+    """B fr3_pick controllers with the registered optimizer (`make_controller_for(FR3Pick(self_collision), optimizer)`, B times) around ONE `GpuModel`.
+    `self_collision`: every member on the self-collision build of the kernel (all 190 pairs of the MJCF) instead of the default one."""
+    if B < 1:
+        raise ValueError("a fleet needs at least one controller")
+    members: list[Controller] = []
+    for _ in range(B):
+        t = FR3Pick(self_collision=self_collision)
+        if members:
+            t._gpu = members[0].model  # (Task.gpu_model hands it out instead of packing and uploading the image again)
+        members.append(make_controller_for(t, optimizer, device=device))
+    return FR3Fleet(members)
+
+
+__all__ = ["FR3Fleet", "make_fr3_fleet"]
