@@ -309,7 +309,8 @@ int jh_plan_step_batch(const jh_model* m, int B, void* blk_dev, const void* blk_
  * whichever problem a rollout belongs to.
  * JH_ERR_UNSUPPORTED: any model that is not fr3_pick (jh_plan_step_batch plans those).  JH_ERR_INVALID: o_phase < 0 or outside the block; a phase word that is not
  * exactly 0, 1, 2 or 3 (read from blk_host before anything is launched; the message names the problem); K > 8; everything jh_plan_step_batch refuses.  jh_plan_step_batch and
- * the model-set, ensemble and randomised entries keep refusing fr3_pick: a model image per problem is not available for it. */
+ * the model-set, ensemble and randomised entries keep refusing fr3_pick; a model image per problem comes with jh_fr3_model_set_create and
+ * jh_plan_step_batch_phases_models below. */
 int jh_plan_step_batch_phases(const jh_model* m, int B, void* blk_dev, const void* blk_host, size_t blk_bytes, size_t blk_stride_bytes, int o_nominal, int o_sigma, int o_tp, int o_lohi,
                               int o_phase, const float* noise, int ldn, size_t noise_stride_floats, const float* W, int N, int H, int K, float* costs, float* trace, int mode,
                               float lambda, int k, int tie_high, int E, int row_floats, int colmajor, float* scratch, float* out, size_t out_stride_floats, void* out_host_mark,
@@ -340,6 +341,34 @@ int jh_model_set_create(const jh_model* const* models /* HOST array of B handles
 int jh_model_set_update(jh_model_set* set, int b, const jh_model* model);
 int jh_model_set_info(const jh_model_set* set, int* out /* HOST, 4 ints */);
 void jh_model_set_destroy(jh_model_set* set);
+/* A model set of fr3_pick models (pick-and-place under an unknown cube mass, pad friction or gripper gain).  jh_model_set_create keeps refusing the family, because the
+ * five entries above and below that take its sets carry no phase; this constructor makes the same record for fr3_pick members alone, and the two entries that carry a
+ * phase plan it:
+ *   jh_fr3_model_set_create            the checks of jh_model_set_create member by member -- the same fields, arm_pairs among them, so the default and the self-collision
+ *                                      build do not mix; each image must pass its own build's acceptance test on its own floats (the finger slides antiparallel).
+ *                                      JH_ERR_UNSUPPORTED for a member that is no fr3_pick model.  jh_model_set_update, _info and _destroy work on the set; _update refuses an
+ *                                      fr3_pick member for any other set and any other member for this one (JH_ERR_UNSUPPORTED).  fr3_pick images hold no pair tables
+ *                                      (jh_model_set_pair_tables: 0), and the launches read member 0's int section as it is.
+ *   jh_plan_step_batch_phases_models   jh_plan_step_batch_phases with the set in place of the model: B must be the set's size (JH_ERR_INVALID otherwise), problem b runs on
+ *                                      image b with the phase word of its block, and its costs, nominal, sigma and trace records are bit for bit those of
+ *                                      jh_plan_step(member b's own handle, ..., phase_b, ...) on its sub-block.  The kernel offsets the base of the float section by
+ *                                      blockIdx.y * stride, scalar arithmetic on kernel arguments; jh_plan_step_batch_phases is this code path with stride 0.
+ *                                      JH_ERR_UNSUPPORTED: a set of any other family (jh_plan_step_batch_models plans those).
+ *   jh_plan_step_randomized_phase      jh_plan_step_randomized (below) with `phase`, 0..3, behind W: one arm in one phase, its N candidates in G blocks of N / G, block g
+ *                                      on plant plant_of_block[g].  costs[r] is bit for bit costs[r] of jh_plan_step(handle of plant plant_of_block[r / Nb], ..., phase, ...)
+ *                                      with the same block and noise; only global rollout 0 is noise-free; out = nominal | sigma is what jh_update_fused writes for the
+ *                                      N costs.  No trace buffer.  Every check of jh_plan_step_randomized, plus JH_ERR_INVALID for a phase outside 0..3 and K > 8 and
+ *                                      JH_ERR_UNSUPPORTED for a set that is not fr3_pick, all before anything is enqueued.
+ * The fr3 launch has no controller axis: an fr3 ensemble and a fleet of randomised fr3 controllers do not exist, and jh_plan_step_ensemble, _ensemble_batch,
+ * _randomized, _randomized_batch and jh_plan_step_batch_models refuse an fr3 set (JH_ERR_UNSUPPORTED), naming the entry above that serves it. */
+int jh_fr3_model_set_create(const jh_model* const* models /* HOST array of B handles */, int B, jh_model_set** out);
+int jh_plan_step_batch_phases_models(const jh_model_set* set, int B, void* blk_dev, const void* blk_host, size_t blk_bytes, size_t blk_stride_bytes, int o_nominal, int o_sigma, int o_tp,
+                                     int o_lohi, int o_phase, const float* noise, int ldn, size_t noise_stride_floats, const float* W, int N, int H, int K, float* costs, float* trace,
+                                     int mode, float lambda, int k, int tie_high, int E, int row_floats, int colmajor, float* scratch, float* out, size_t out_stride_floats,
+                                     void* out_host_mark, void* const* timing, void* stream);
+int jh_plan_step_randomized_phase(const jh_model_set* set, void* blk_dev, const void* blk_host, size_t blk_bytes, int o_nominal, int o_sigma, int o_tp, int o_lohi, const float* noise, int ldn,
+                                  const float* W, int phase, int N, int H, int K, const unsigned char* plant_of_block /* HOST, G */, int G, float* costs /* DEVICE, N */, int mode,
+                                  float lambda, int k, int tie_high, float* scratch, float* out /* nominal | sigma */, void* out_host_mark, void* const* timing, void* stream);
 
 /* The hand's pair tables (leap family; judo_amd/engine_model.py::hand_pair_tables): bit grids over two joint angles in the image's int section that tell the kernel which
  * hand body pairs cannot touch at a step's pose.  jh_model_create refuses a malformed block (JH_ERR_BLOB).  A model set reads ONE int section, member 0's, so it keeps the

@@ -617,7 +617,7 @@ static int plan_step_batch(const char* who, const jh_model* m, const float* imag
                            void* out_host_mark, void* const* timing, void* stream) {
   JH_REQUIRE(m && blk_dev && blk_host && out && scratch && noise && W && costs, "%s: null pointer", who);
   // o_phase: the float offset of every block's phase word (jh_plan_step_batch_phases, fr3_pick alone), or -1: an entry without one, which keeps refusing fr3_pick
-  if (m->kind == JH_TASK_FR3_PICK && o_phase < 0) { jh_set_error("%s: fr3_pick has no batched plan step (its phase is chosen per problem on the host) behind this entry: jh_plan_step_batch_phases takes a phase word per problem", who); return JH_ERR_UNSUPPORTED; }
+  if (m->kind == JH_TASK_FR3_PICK && o_phase < 0) { jh_set_error("%s: fr3_pick has no batched plan step (its phase is chosen per problem on the host) behind this entry: jh_plan_step_batch_phases takes a phase word per problem, jh_plan_step_batch_phases_models a set of fr3_pick models as well", who); return JH_ERR_UNSUPPORTED; }
   if (m->kind != JH_TASK_FR3_PICK && o_phase >= 0) { jh_set_error("%s: a phase word per problem is fr3_pick's alone; jh_plan_step_batch plans this model", who); return JH_ERR_UNSUPPORTED; }
   if (m->kind == JH_TASK_LEAP_CUBE && m->kernel_gen != 3) { jh_set_error("%s: only kernel generation 3 of the leap family has a batched launch (this model runs %d)", who, m->kernel_gen); return JH_ERR_UNSUPPORTED; }
   JH_REQUIRE(B >= 1, "%s: B must be at least 1 (B=%d)", who, B);
@@ -728,6 +728,7 @@ static long int_sections_differ(const std::vector<int>& a, const std::vector<int
 // (Re)derive what follows from the members: whether they share the pair tables, and the int section without them.
 static int model_set_tables(jh_model_set* s, bool member0_changed) {
   s->tables = true;
+  if (s->m0->kind == JH_TASK_FR3_PICK) return JH_OK;  // (no pair tables: the members' int sections are member 0's word for word, and the launch reads m0->d_i)
   for (int b = 1; b < s->B && s->tables; b++) s->tables = pair_tables_shared(s->hf[0], s->hi[0], s->hf[b], s->hi[b]);
   if (!member0_changed) return JH_OK;  // (the int section without tables is member 0's: uploaded when the set is made and when member 0 is replaced)
   std::vector<int> plain = s->hi[0];
@@ -737,11 +738,18 @@ static int model_set_tables(jh_model_set* s, bool member0_changed) {
 }
 
 // May `m` be member `b` of a set whose member 0 is `m0` (b == 0: may `m` lead a set)?  JH_OK, or the status with the error set: it names the member and the field.
-static int model_set_member(const char* who, const jh_model* m0, const jh_model* m, int b) {
+// `fr3`: the set is one of fr3_pick models (jh_fr3_model_set_create), which the phase-taking entries plan; every other set keeps refusing the family.
+static int model_set_member(const char* who, const jh_model* m0, const jh_model* m, int b, bool fr3) {
   JH_REQUIRE(m != nullptr, "%s: member %d is a null pointer", who, b);
-  if (m->kind == JH_TASK_FR3_PICK) { jh_set_error("%s: member %d is an fr3_pick model, which has no batched plan step (its phase is chosen per problem on the host)", who, b); return JH_ERR_UNSUPPORTED; }
+  if (m->kind == JH_TASK_FR3_PICK && !fr3) {
+    jh_set_error("%s: member %d is an fr3_pick model, which has no batched plan step (its phase is chosen per problem on the host) behind the entries that take this set.  "
+                 "jh_fr3_model_set_create makes a set of fr3_pick models for jh_plan_step_batch_phases_models and jh_plan_step_randomized_phase", who, b);
+    return JH_ERR_UNSUPPORTED;
+  }
+  if (m->kind != JH_TASK_FR3_PICK && fr3) { jh_set_error("%s: member %d is no fr3_pick model (kind %d): this set holds fr3_pick models alone; jh_model_set_create makes a set of every other family", who, b, m->kind); return JH_ERR_UNSUPPORTED; }
   if (m->kind == JH_TASK_LEAP_CUBE && m->kernel_gen != 3) { jh_set_error("%s: member %d runs kernel_gen %d: only kernel generation 3 of the leap family has a batched launch", who, b, m->kernel_gen); return JH_ERR_UNSUPPORTED; }
-  if (m->kind != JH_TASK_CARTPOLE && m->kind != JH_TASK_CYLINDER_PUSH && m->kind != JH_TASK_LEAP_CUBE) { jh_set_error("%s: member %d: no batched kernel for this model (kind %d)", who, b, m->kind); return JH_ERR_UNSUPPORTED; }
+  if (m->kind == JH_TASK_FR3_PICK && m->kernel_gen != 3) { jh_set_error("%s: member %d runs kernel_gen %d: only kernel generation 3 of fr3_pick has a batched launch", who, b, m->kernel_gen); return JH_ERR_UNSUPPORTED; }
+  if (m->kind != JH_TASK_CARTPOLE && m->kind != JH_TASK_CYLINDER_PUSH && m->kind != JH_TASK_LEAP_CUBE && m->kind != JH_TASK_FR3_PICK) { jh_set_error("%s: member %d: no batched kernel for this model (kind %d)", who, b, m->kind); return JH_ERR_UNSUPPORTED; }
   if (m != m0) {
 #define JH_SET_SAME(field, fmt)                                                                                                                                    \
   JH_REQUIRE(m->field == m0->field, "%s: member %d differs from the set's member 0 in " #field " (" fmt " against " fmt ")", who, b, m->field, m0->field)
@@ -751,7 +759,7 @@ static int model_set_member(const char* who, const jh_model* m0, const jh_model*
       jh_set_error("%s: member %d differs from the set's member 0 in the int section h_i (word %ld: %d against %d): topology, pair lists and lane lists are one for the launch", who, b, w, m->h_i[w], m0->h_i[w]);
       return JH_ERR_INVALID;
     }
-    JH_SET_SAME(kernel_gen, "%d"); JH_SET_SAME(contact_capacity, "%d"); JH_SET_SAME(cylinders, "%d"); JH_SET_SAME(self_collision, "%d"); JH_SET_SAME(rollout_schedule, "%d");
+    JH_SET_SAME(kernel_gen, "%d"); JH_SET_SAME(contact_capacity, "%d"); JH_SET_SAME(cylinders, "%d"); JH_SET_SAME(arm_pairs, "%d"); JH_SET_SAME(self_collision, "%d"); JH_SET_SAME(rollout_schedule, "%d");
     JH_SET_SAME(rollout_slices, "%d"); JH_SET_SAME(rollout_nbounds, "%d");
     for (int i = 0; i < m0->rollout_nbounds; i++) JH_SET_SAME(rollout_bounds[i], "%d");
  JH_SET_SAME(rollout_max_workgroups, "%d"); JH_SET_SAME(rollout_slice_flags, "%d");
@@ -765,6 +773,12 @@ static int model_set_member(const char* who, const jh_model* m0, const jh_model*
       return JH_ERR_UNSUPPORTED;
     }
   }
+  if (m->kind == JH_TASK_FR3_PICK) {  // likewise: the build this image selects (arm_pairs) must accept it; jh_model_is_fr3 reads h_f for the finger slides
+    if (!engine_build(m)->accepts(m)) {
+      jh_set_error("%s: member %d: the %s build of the cooperative arm kernel does not accept this image (dimensions, pair lists, or h_f: the finger slides must be antiparallel)", who, b, engine_build(m)->name);
+      return JH_ERR_UNSUPPORTED;
+    }
+  }
   return JH_OK;
 }
 
@@ -774,11 +788,11 @@ static int model_set_upload(jh_model_set* s, int b, const jh_model* m) {
   return JH_OK;
 }
 
-extern "C" int jh_model_set_create(const jh_model* const* models, int B, jh_model_set** out) {
-  JH_REQUIRE(models && out, "model_set_create: null pointer");
-  JH_REQUIRE(B >= 1, "model_set_create: B must be at least 1 (B=%d)", B);
-  JH_REQUIRE(B <= 65535, "model_set_create: B = %d exceeds the 65535 problems of a launch (the grid's second dimension)", B);
-  for (int b = 0; b < B; b++) if (int rc = model_set_member("model_set_create", models[0], models[b], b)) return rc;
+static int model_set_create(const char* who, const jh_model* const* models, int B, jh_model_set** out, bool fr3) {
+  JH_REQUIRE(models && out, "%s: null pointer", who);
+  JH_REQUIRE(B >= 1, "%s: B must be at least 1 (B=%d)", who, B);
+  JH_REQUIRE(B <= 65535, "%s: B = %d exceeds the 65535 problems of a launch (the grid's second dimension)", who, B);
+  for (int b = 0; b < B; b++) if (int rc = model_set_member(who, models[0], models[b], b, fr3)) return rc;
   const jh_model* m0 = models[0];
   JH_HIP(hipSetDevice(m0->device));
   jh_model_set* s = new jh_model_set();
@@ -787,8 +801,8 @@ extern "C" int jh_model_set_create(const jh_model* const* models, int B, jh_mode
   hipError_t e = hipMalloc(&s->d_images, 4 * s->stride * (size_t)B);
   if (e == hipSuccess) e = hipMemset(s->d_images, 0, 4 * s->stride * (size_t)B);  // (the padding between the images is never read; zero all the same)
   int rc = JH_OK;
-  if (e != hipSuccess) { jh_set_error("model_set_create: device allocation failed: %s", hipGetErrorString(e)); rc = JH_ERR_HIP; }
-  if (rc == JH_OK && hipMalloc(&s->d_i_plain, 4 * (m0->ni ? m0->ni : 1)) != hipSuccess) { jh_set_error("model_set_create: device allocation failed"); rc = JH_ERR_HIP; }
+  if (e != hipSuccess) { jh_set_error("%s: device allocation failed: %s", who, hipGetErrorString(e)); rc = JH_ERR_HIP; }
+  if (rc == JH_OK && hipMalloc(&s->d_i_plain, 4 * (m0->ni ? m0->ni : 1)) != hipSuccess) { jh_set_error("%s: device allocation failed", who); rc = JH_ERR_HIP; }
   for (int b = 0; b < B && rc == JH_OK; b++) rc = model_set_upload(s, b, models[b]);
   if (rc == JH_OK) rc = model_set_tables(s, true);
   if (rc != JH_OK) { if (s->d_images) (void)hipFree(s->d_images); if (s->d_i_plain) (void)hipFree(s->d_i_plain); delete s; return rc; }
@@ -796,11 +810,17 @@ extern "C" int jh_model_set_create(const jh_model* const* models, int B, jh_mode
   return JH_OK;
 }
 
+extern "C" int jh_model_set_create(const jh_model* const* models, int B, jh_model_set** out) { return model_set_create("model_set_create", models, B, out, false); }
+
+// A set of fr3_pick models (include/judo_amd.h): the same record and the same checks, member by member, for the family the generic constructor refuses; the entries that
+// carry a phase plan it.
+extern "C" int jh_fr3_model_set_create(const jh_model* const* models, int B, jh_model_set** out) { return model_set_create("fr3_model_set_create", models, B, out, true); }
+
 extern "C" int jh_model_set_update(jh_model_set* s, int b, const jh_model* model) {
   JH_REQUIRE(s && model, "model_set_update: null pointer");
   JH_REQUIRE(b >= 0 && b < s->B, "model_set_update: member %d of a set of %d", b, s->B);
-  // (a new member 0 is held to the old one, which the others were held to; it then leads the set)
-  if (int rc = model_set_member("model_set_update", s->m0, model, b)) return rc;
+  // (a new member 0 is held to the old one, which the others were held to; it then leads the set.  An fr3 set takes fr3_pick members alone and no other set takes one.)
+  if (int rc = model_set_member("model_set_update", s->m0, model, b, s->m0->kind == JH_TASK_FR3_PICK)) return rc;
   JH_HIP(hipSetDevice(s->m0->device));
   if (int rc = model_set_upload(s, b, model)) return rc;
   if (b == 0) s->m0 = model;
@@ -836,6 +856,20 @@ extern "C" int jh_plan_step_batch_models(const jh_model_set* set, void* blk_dev,
                          noise_stride_floats, W, N, H, K, costs, trace, mode, lambda, k, tie_high, E, row_floats, colmajor, scratch, out, out_stride_floats, out_host_mark, timing, stream);
 }
 
+// jh_plan_step_batch_phases on a set of fr3_pick models (include/judo_amd.h): the same code path with the set's images and stride; the int section is member 0's own.
+extern "C" int jh_plan_step_batch_phases_models(const jh_model_set* set, int B, void* blk_dev, const void* blk_host, size_t blk_bytes, size_t blk_stride_bytes, int o_nominal, int o_sigma, int o_tp,
+                                                int o_lohi, int o_phase, const float* noise, int ldn, size_t noise_stride_floats, const float* W, int N, int H, int K, float* costs, float* trace,
+                                                int mode, float lambda, int k, int tie_high, int E, int row_floats, int colmajor, float* scratch, float* out, size_t out_stride_floats,
+                                                void* out_host_mark, void* const* timing, void* stream) {
+  const char* who = "plan_step_batch_phases_models";
+  JH_REQUIRE(set != nullptr, "%s: null pointer", who);
+  if (set->m0->kind != JH_TASK_FR3_PICK) { jh_set_error("%s: a phase word per problem is fr3_pick's alone; jh_plan_step_batch_models plans this set", who); return JH_ERR_UNSUPPORTED; }
+  JH_REQUIRE(B == set->B, "%s: B = %d problems for a set of %d members: problem b runs on member b", who, B, set->B);
+  JH_REQUIRE(o_phase >= 0, "%s: negative block offset (o_phase=%d)", who, o_phase);
+  return plan_step_batch(who, set->m0, set->d_images, (long long)set->stride, set->m0->d_i, B, blk_dev, blk_host, blk_bytes, blk_stride_bytes, o_nominal, o_sigma, o_tp, o_lohi, o_phase, noise, ldn,
+                         noise_stride_floats, W, N, H, K, costs, trace, mode, lambda, k, tie_high, E, row_floats, colmajor, scratch, out, out_stride_floats, out_host_mark, timing, stream);
+}
+
 // ONE plan step against the M members of a model set (include/judo_amd.h): the batched rollout kernels on grid (workgroups, M) with the block and noise strides 0 -- every
 // member rolls out the same N candidates from the same block, on its own image, into its own row of member_costs -- then k_update_tail_ensemble, which aggregates the M
 // rows into `costs` and runs the single call's tail on them.  The records are built here: the batched entry points refuse strides below a block, rightly for what they do.
@@ -851,7 +885,7 @@ extern "C" int jh_plan_step_ensemble(const jh_model_set* set, void* blk_dev, con
   const int M = set->B;
   JH_REQUIRE(M <= JH_MAX_ENSEMBLE, "%s: a set of %d members exceeds JH_MAX_ENSEMBLE = %d", who, M, JH_MAX_ENSEMBLE);
   JH_REQUIRE(worst >= 1 && worst <= M, "%s: worst = %d outside [1, M = %d]", who, worst, M);
-  if (m->kind == JH_TASK_FR3_PICK) { jh_set_error("%s: fr3_pick has no batched plan step (its phase is chosen per problem on the host)", who); return JH_ERR_UNSUPPORTED; }
+  if (m->kind == JH_TASK_FR3_PICK) { jh_set_error("%s: fr3_pick has no batched plan step (its phase is chosen per problem on the host) behind this entry: an fr3_pick set has no ensemble form; jh_plan_step_randomized_phase spreads one arm's candidates over the set's plants", who); return JH_ERR_UNSUPPORTED; }
   if (m->kind == JH_TASK_LEAP_CUBE && m->kernel_gen != 3) { jh_set_error("%s: only kernel generation 3 of the leap family has a batched launch (this model runs %d)", who, m->kernel_gen); return JH_ERR_UNSUPPORTED; }
   JH_REQUIRE(N > 0 && H > 0 && K >= 1, "%s: N, H, K must be positive (N=%d H=%d K=%d)", who, N, H, K);
   JH_REQUIRE(ldn >= N, "%s: ldn (%d) < N (%d)", who, ldn, N);
@@ -900,10 +934,11 @@ extern "C" int jh_plan_step_ensemble(const jh_model_set* set, void* blk_dev, con
 // batched rollout kernels on grid (workgroups of Nb rollouts, G): the block stride 0 -- every block reads the one packed block --, the noise and cost strides Nb -- block
 // g's columns of the one noise matrix (pitch ldn) and its slice of `costs` --, the plant axis (jh_internal.h) with the rollout-index stride Nb -- only global rollout 0
 // drops its noise -- and the table, which travels in the kernel arguments.  Then the single call's own tail on the N costs.  The checks are the ensemble call's.
-extern "C" int jh_plan_step_randomized(const jh_model_set* set, void* blk_dev, const void* blk_host, size_t blk_bytes, int o_nominal, int o_sigma, int o_tp, int o_lohi, const float* noise, int ldn,
-                                       const float* W, int N, int H, int K, const unsigned char* plant_of_block, int G, float* costs, int mode, float lambda, int k, int tie_high, float* scratch,
-                                       float* out, void* out_host_mark, void* const* timing, void* stream) {
-  const char* who = "plan_step_randomized";
+// `phase`: -1 for jh_plan_step_randomized, which has none and refuses fr3_pick; 0..3 for jh_plan_step_randomized_phase, which plans fr3_pick alone (checked by the entry):
+// the one controller's phase travels in the launch record, and every block's workgroups take it as the single launch takes its argument.
+static int plan_step_randomized(const char* who, const jh_model_set* set, void* blk_dev, const void* blk_host, size_t blk_bytes, int o_nominal, int o_sigma, int o_tp, int o_lohi, const float* noise,
+                                int ldn, const float* W, int phase, int N, int H, int K, const unsigned char* plant_of_block, int G, float* costs, int mode, float lambda, int k, int tie_high,
+                                float* scratch, float* out, void* out_host_mark, void* const* timing, void* stream) {
 #define JH_RND_PTR(p) JH_REQUIRE((p) != nullptr, "%s: " #p " is a null pointer", who)
   JH_RND_PTR(set); JH_RND_PTR(blk_dev); JH_RND_PTR(blk_host); JH_RND_PTR(noise); JH_RND_PTR(W); JH_RND_PTR(plant_of_block); JH_RND_PTR(costs); JH_RND_PTR(scratch); JH_RND_PTR(out);
 #undef JH_RND_PTR
@@ -911,7 +946,9 @@ extern "C" int jh_plan_step_randomized(const jh_model_set* set, void* blk_dev, c
   const int M = set->B;
   JH_REQUIRE(M <= JH_MAX_ENSEMBLE, "%s: a set of %d members exceeds JH_MAX_ENSEMBLE = %d", who, M, JH_MAX_ENSEMBLE);
   JH_REQUIRE(G >= 1 && G <= JH_MAX_PLANT_BLOCKS, "%s: G = %d outside [1, JH_MAX_PLANT_BLOCKS = %d]", who, G, JH_MAX_PLANT_BLOCKS);
-  if (m->kind == JH_TASK_FR3_PICK) { jh_set_error("%s: fr3_pick has no batched plan step (its phase is chosen per problem on the host)", who); return JH_ERR_UNSUPPORTED; }
+  if (m->kind == JH_TASK_FR3_PICK && phase < 0) { jh_set_error("%s: fr3_pick has no batched plan step (its phase is chosen per problem on the host) behind this entry: jh_plan_step_randomized_phase takes the arm's phase", who); return JH_ERR_UNSUPPORTED; }
+  if (m->kind != JH_TASK_FR3_PICK && phase >= 0) { jh_set_error("%s: a phase is fr3_pick's alone; jh_plan_step_randomized plans this set", who); return JH_ERR_UNSUPPORTED; }
+  JH_REQUIRE(phase < 0 || K <= 8, "%s: the cooperative arm kernel keeps at most 8 knots per actuator in registers (K=%d)", who, K);
   if (m->kind == JH_TASK_LEAP_CUBE && m->kernel_gen != 3) { jh_set_error("%s: only kernel generation 3 of the leap family has a batched launch (this model runs %d)", who, m->kernel_gen); return JH_ERR_UNSUPPORTED; }
   JH_REQUIRE(N > 0 && H > 0 && K >= 1, "%s: N, H, K must be positive (N=%d H=%d K=%d)", who, N, H, K);
   JH_REQUIRE(N % G == 0, "%s: N = %d is no multiple of G = %d (the blocks are N / G rollouts each)", who, N, G);
@@ -953,6 +990,7 @@ extern "C" int jh_plan_step_randomized(const jh_model_set* set, void* blk_dev, c
     const jh_rollout_args ra = {b, b + o_nominal, noise, ldn, b + o_sigma, W, b + o_lohi, b + o_tp, 0, Nb, 0, H, K, costs, nullptr, nullptr};
     jh_rollout_batch rb = {set->d_images, (long long)set->stride, ints, G, 0, (long long)Nb};
     rb.plants = plants;
+    rb.phase = phase;
     rc = eb->rollout_cost_batch(m, ra, rb, st);
   }
   if (rc == JH_OK && timing) JH_HIP(hipEventRecord((hipEvent_t)timing[1], st));
@@ -960,6 +998,25 @@ extern "C" int jh_plan_step_randomized(const jh_model_set* set, void* blk_dev, c
   if (rc == JH_OK && timing) JH_HIP(hipEventRecord((hipEvent_t)timing[2], st));
   if (rc == JH_OK) rc = download_begin(out, out, 0, stream, flag, expect);
   return rc;
+}
+
+extern "C" int jh_plan_step_randomized(const jh_model_set* set, void* blk_dev, const void* blk_host, size_t blk_bytes, int o_nominal, int o_sigma, int o_tp, int o_lohi, const float* noise, int ldn,
+                                       const float* W, int N, int H, int K, const unsigned char* plant_of_block, int G, float* costs, int mode, float lambda, int k, int tie_high, float* scratch,
+                                       float* out, void* out_host_mark, void* const* timing, void* stream) {
+  return plan_step_randomized("plan_step_randomized", set, blk_dev, blk_host, blk_bytes, o_nominal, o_sigma, o_tp, o_lohi, noise, ldn, W, -1, N, H, K, plant_of_block, G, costs, mode, lambda, k, tie_high,
+                              scratch, out, out_host_mark, timing, stream);
+}
+
+// jh_plan_step_randomized for fr3_pick (include/judo_amd.h): the same code path with the arm's phase, which the fr3 kernel's blocks take from the launch record.
+extern "C" int jh_plan_step_randomized_phase(const jh_model_set* set, void* blk_dev, const void* blk_host, size_t blk_bytes, int o_nominal, int o_sigma, int o_tp, int o_lohi, const float* noise,
+                                             int ldn, const float* W, int phase, int N, int H, int K, const unsigned char* plant_of_block, int G, float* costs, int mode, float lambda, int k,
+                                             int tie_high, float* scratch, float* out, void* out_host_mark, void* const* timing, void* stream) {
+  const char* who = "plan_step_randomized_phase";
+  JH_REQUIRE(set != nullptr, "%s: set is a null pointer", who);
+  if (set->m0->kind != JH_TASK_FR3_PICK) { jh_set_error("%s: a phase is fr3_pick's alone; jh_plan_step_randomized plans this set", who); return JH_ERR_UNSUPPORTED; }
+  JH_REQUIRE(phase >= 0 && phase <= 3, "%s: phase = %d is not 0, 1, 2 or 3 (LIFT, MOVE, PLACE, HOMING)", who, phase);
+  return plan_step_randomized(who, set, blk_dev, blk_host, blk_bytes, o_nominal, o_sigma, o_tp, o_lohi, noise, ldn, W, phase, N, H, K, plant_of_block, G, costs, mode, lambda, k, tie_high, scratch, out,
+                              out_host_mark, timing, stream);
 }
 
 // B ensemble plan steps (jh_plan_step_ensemble) as ONE call (include/judo_amd.h): B controllers, each with its own block, noise, `worst`, costs and output record, each against M plants.  The
@@ -980,7 +1037,7 @@ extern "C" int jh_plan_step_ensemble_batch(const jh_model_set* set, int B, int M
   JH_REQUIRE(M >= 1 && M <= JH_MAX_ENSEMBLE, "%s: M = %d outside [1, JH_MAX_ENSEMBLE = %d]", who, M, JH_MAX_ENSEMBLE);
   JH_REQUIRE(set->B == M || set->B == B * M, "%s: a set of %d members is neither the M = %d plants every controller shares nor the B * M = %d plants of B = %d controllers", who, set->B, M, B * M, B);
   for (int b = 0; b < B; b++) JH_REQUIRE(worst[b] >= 1 && worst[b] <= M, "%s: controller %d: worst = %d outside [1, M = %d]", who, b, worst[b], M);
-  if (m->kind == JH_TASK_FR3_PICK) { jh_set_error("%s: fr3_pick has no batched plan step (its phase is chosen per problem on the host)", who); return JH_ERR_UNSUPPORTED; }
+  if (m->kind == JH_TASK_FR3_PICK) { jh_set_error("%s: fr3_pick has no batched plan step (its phase is chosen per problem on the host) behind this entry: an fr3_pick set has no ensemble form; jh_plan_step_batch_phases_models plans B arms on B plants", who); return JH_ERR_UNSUPPORTED; }
   if (m->kind == JH_TASK_LEAP_CUBE && m->kernel_gen != 3) { jh_set_error("%s: only kernel generation 3 of the leap family has a batched launch (this model runs %d)", who, m->kernel_gen); return JH_ERR_UNSUPPORTED; }
   JH_REQUIRE(N > 0 && H > 0 && K >= 1, "%s: N, H, K must be positive (N=%d H=%d K=%d)", who, N, H, K);
   JH_REQUIRE(ldn >= N, "%s: ldn (%d) < N (%d)", who, ldn, N);
@@ -1057,7 +1114,7 @@ extern "C" int jh_plan_step_randomized_batch(const jh_model_set* set, int B, int
   JH_REQUIRE(B * G <= JH_MAX_FLEET_PLANT_BLOCKS, "%s: B * G = %d * %d = %d exceeds JH_MAX_FLEET_PLANT_BLOCKS = %d (the bytes of the table in the kernel arguments)", who, B, G, B * G,
              JH_MAX_FLEET_PLANT_BLOCKS);
   JH_REQUIRE(set->B == M || set->B == B * M, "%s: a set of %d members is neither the M = %d plants every controller shares nor the B * M = %d plants of B = %d controllers", who, set->B, M, B * M, B);
-  if (m->kind == JH_TASK_FR3_PICK) { jh_set_error("%s: fr3_pick has no batched plan step (its phase is chosen per problem on the host)", who); return JH_ERR_UNSUPPORTED; }
+  if (m->kind == JH_TASK_FR3_PICK) { jh_set_error("%s: fr3_pick has no batched plan step (its phase is chosen per problem on the host) behind this entry: jh_plan_step_randomized_phase plans one arm over the set's plants and jh_plan_step_batch_phases_models B arms on B plants", who); return JH_ERR_UNSUPPORTED; }
   if (m->kind == JH_TASK_LEAP_CUBE && m->kernel_gen != 3) { jh_set_error("%s: only kernel generation 3 of the leap family has a batched launch (this model runs %d)", who, m->kernel_gen); return JH_ERR_UNSUPPORTED; }
   JH_REQUIRE(N > 0 && H > 0 && K >= 1, "%s: N, H, K must be positive (N=%d H=%d K=%d)", who, N, H, K);
   JH_REQUIRE(N % G == 0, "%s: N = %d is no multiple of G = %d (the blocks are N / G rollouts each)", who, N, G);

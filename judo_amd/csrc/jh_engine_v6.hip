@@ -426,8 +426,13 @@ __device__ __forceinline__ void geom_pose3(const RS6& S, const float* gf, int bo
 // `batch_blk` floats apart; x0 is the block's first word), its noise (`batch_noise` floats apart), its costs, trace rows and overflow rows (N rollouts apart) -- is reached
 // by offsetting the kernel's pointers once, at the top, with arithmetic on kernel arguments and blockIdx.y alone: the bases stay in SGPRs and a rollout's code below is the
 // single launch's.  The phase, which the single launch takes as an argument, is a word of the problem's block at float offset `o_phase`: a float holding 0, 1, 2 or 3 (the
-// entry point checks it), read once per workgroup with a uniform load and converted once, in front of both of its uses.  The model image and the counters are the
-// launch's.  The other instantiations ignore the three trailing arguments and compile to the code they had without them.
+// entry point checks it), read once per workgroup with a uniform load and converted once, in front of both of its uses; `o_phase` < 0: the launch's `phase` argument,
+// one controller's one phase (jh_plan_step_randomized_phase).  A model set (jh_plan_step_batch_phases_models) gives every problem its own image of the float section,
+// `batch_image` floats apart (0: one image for all); the int section is one for the launch.  The plant axis (jh_internal.h) makes the problems blocks of ONE problem's
+// rollouts: a stride on the global rollout index, so that only global rollout 0 is the noise-free nominal, and a by-value table from the problem to its image in place
+// of the problem's own index -- 0 and the identity for jh_plan_step_batch_phases.  The counters are the launch's.  The other instantiations take an empty record in the
+// table's place, ignore the trailing arguments and compile to the code they had without them.
+struct NoPlantAxis {};
 template <bool MATERIALIZE, bool BATCH = false>
 __global__ __launch_bounds__(WAVE) __attribute__((amdgpu_waves_per_eu(WPE, WPE))) void k_fr3_v6(const float* __restrict__ gF, const int* __restrict__ gI, const float* __restrict__ x0, int x0_batched,
                                                     const float* __restrict__ nominal, const float* __restrict__ noise, int ldn,
@@ -435,15 +440,18 @@ __global__ __launch_bounds__(WAVE) __attribute__((amdgpu_waves_per_eu(WPE, WPE))
                                                     const float* __restrict__ tp, int phase, int N, int n_offset, int H, int K,
                                                     float* __restrict__ costs, float* __restrict__ knots_out, const float* __restrict__ controls,
                                                     float* __restrict__ states, float* __restrict__ sensors, int* __restrict__ stats, int dshift, float* __restrict__ trace, float* __restrict__ ovf_all,
-                                                    long long batch_blk, long long batch_noise, int o_phase) {
+                                                    long long batch_blk, long long batch_noise, int o_phase, long long batch_image,
+                                                    std::conditional_t<BATCH, jh_plant_axis, NoPlantAxis> plants) {
   static_assert(!BATCH || !MATERIALIZE, "batched launches are fused launches");
   if constexpr (BATCH) {
     const long long pb = blockIdx.y, ob = pb * batch_blk;
     x0 += ob; nominal += ob; sigma += ob; lohi += ob; tp += ob;
-    noise += pb * batch_noise; costs += pb * N;
+    // the plant axis: the problem's first global rollout index and the image its table names -- 0 and image pb for a launch without one
+    n_offset += (int)pb * plants.n_stride;
+    noise += pb * batch_noise; costs += pb * N; gF += jh_plant_of(plants, (int)pb, (int)pb) * batch_image;
     if (trace) trace += pb * N * H * 6;
     if (ovf_all) ovf_all += pb * N * (NOVF * RAW_F);  // (the overflow rows are indexed by rollout: a problem's N rows behind the one before)
-    phase = (int)x0[o_phase];
+    if (o_phase >= 0) phase = (int)x0[o_phase];
   }
   __shared__ RS6 sRS[RPW];
   __shared__ int sDT[MAXDT][3];  // distance-sensor tasks: sensordata address, geom a, geom b
@@ -1338,7 +1346,7 @@ static int launch(const jh_model* m, const char* who, const char* note, const jh
   // no state on the model handle
   float* ovf = jh_launch_scratch(m, (size_t)a.N * NOVF * RAW_F * sizeof(float), st);  // (nullptr: the LDS capacity alone, drops and the fallback counted)
   hipLaunchKernelGGL(k_fr3_v6<MATERIALIZE>, dim3(grid), dim3(WAVE), 0, st, m->d_f, m->d_i, a.x0, x0_batched, a.nominal, a.noise, a.ldn, a.sigma, a.W, a.lohi, a.tp, a.phase, a.N, a.n_offset,
-                     a.H, a.K, a.costs, a.knots_out, controls, states, sensors, m->d_stats, dshift, a.trace, ovf, 0ll, 0ll, 0);
+                     a.H, a.K, a.costs, a.knots_out, controls, states, sensors, m->d_stats, dshift, a.trace, ovf, 0ll, 0ll, 0, 0ll, NoPlantAxis{});
   return jh_launch_done(ovf, st);
 }
 
@@ -1352,9 +1360,12 @@ int JH_V6_NAME(jh_engine6_materialize)(const jh_model* m, const float* x0, int x
 }
 
 // (Defined behind every other launcher: the batched instantiation is emitted behind the other kernels.)
-// B problems in one launch (jh_plan_step_batch_phases): the grid with the problem in its second dimension.  The record is problem 0's, whose x0 is the first word of its
-// packed block; `blk_stride` / `noise_stride` floats lead to the next problem's, and `o_phase` is the float offset of the problem's phase word in its block.  The latency
-// shift is chosen from B * N, the rollouts of the launch (the bits do not depend on it).  What the record can say and this kernel does not implement is refused.
+// B problems in one launch (jh_plan_step_batch_phases, jh_plan_step_batch_phases_models): the grid with the problem in its second dimension.  The record is problem 0's,
+// whose x0 is the first word of its packed block; `blk_stride` / `noise_stride` floats lead to the next problem's, and `o_phase` is the float offset of the problem's phase
+// word in its block -- or negative, and `s.phase` is every problem's (jh_plan_step_randomized_phase: the problems are blocks of one controller's rollouts).  `s.images` /
+// `s.image_stride`: problem 0's float section and the floats to the next problem's; `s.plants`: the plant axis, by value.  The int section is the model's own: fr3_pick has
+// no pair tables, so a set's members share it as it is.  The latency shift is chosen from B * N, the rollouts of the launch (the bits do not depend on it).  What the
+// record can say and this kernel does not implement is refused.
 static int rollout_cost_batch(const jh_model* m, const jh_rollout_args& a, const jh_rollout_batch& s, hipStream_t st) {
   if (!JH_V6_NAME(jh_model_is_fr3)(m)) {
     if (JH_V6_SELF) jh_set_error("plan_step_batch_phases: the self-collision build of the cooperative arm kernel is instantiated for fr3_pick with its arm pairs only");
@@ -1362,16 +1373,16 @@ static int rollout_cost_batch(const jh_model* m, const jh_rollout_args& a, const
     return JH_ERR_UNSUPPORTED;
   }
   JH_REQUIRE(a.K <= 8, "plan_step_batch_phases: the cooperative arm kernel keeps at most 8 knots per actuator in registers (K=%d)", a.K);
-  JH_REQUIRE(s.C == 1, "plan_step_batch_phases: the fr3 kernel's batched launch has no controller axis (C=%d)", s.C);
-  JH_REQUIRE(s.plants.n_stride == 0 && s.plants.mapped == 0, "plan_step_batch_phases: the fr3 kernel's batched launch has no plant axis (a stride on the rollout index or a plant table)");
-  JH_REQUIRE(s.image_stride == 0, "plan_step_batch_phases: the fr3 kernel's batched launch reads one model image (image_stride=%lld): a model image per problem is not available for fr3_pick", s.image_stride);
-  JH_REQUIRE(s.o_phase >= 0 && a.knots_out == nullptr && a.n_offset == 0, "plan_step_batch_phases: the fr3 kernel's batched launch needs a phase word and takes neither knots_out nor a rollout offset");
+  JH_REQUIRE(s.C == 1, "plan_step_batch_phases: the fr3 launch has no controller axis (C=%d)", s.C);
+  JH_REQUIRE(s.images != nullptr && s.image_stride >= 0, "plan_step_batch_phases: the fr3 kernel's batched launch needs the problems' images (image_stride=%lld)", s.image_stride);
+  JH_REQUIRE(a.knots_out == nullptr && a.n_offset == 0, "plan_step_batch_phases: the fr3 kernel's batched launch takes neither knots_out nor a rollout offset");
+  JH_REQUIRE(s.o_phase >= 0 || (s.phase >= 0 && s.phase <= 3), "plan_step_batch_phases: the fr3 kernel's batched launch needs a phase word per problem or a phase 0..3 in its record (phase=%d)", s.phase);
   const long long rollouts = (long long)s.B * a.N;
   JH_REQUIRE(s.B >= 1 && s.B <= 65535 && rollouts <= 0x7fffffffll, "plan_step_batch_phases: B * N = %lld rollouts exceed one launch", rollouts);
   const int dshift = jh_latency_shift((int)rollouts, RPW), per_wave = RPW >> dshift, grid = (a.N + per_wave - 1) / per_wave;
   float* ovf = jh_launch_scratch(m, (size_t)rollouts * NOVF * RAW_F * sizeof(float), st);  // (every problem's rows; nullptr: the LDS capacity alone, drops and the fallback counted)
-  hipLaunchKernelGGL((k_fr3_v6<false, true>), dim3(grid, s.B), dim3(WAVE), 0, st, m->d_f, m->d_i, a.x0, 0, a.nominal, a.noise, a.ldn, a.sigma, a.W, a.lohi, a.tp, 0, a.N, 0,
-                     a.H, a.K, a.costs, nullptr, nullptr, nullptr, nullptr, m->d_stats, dshift, a.trace, ovf, s.blk_stride, s.noise_stride, s.o_phase);
+  hipLaunchKernelGGL((k_fr3_v6<false, true>), dim3(grid, s.B), dim3(WAVE), 0, st, s.images, m->d_i, a.x0, 0, a.nominal, a.noise, a.ldn, a.sigma, a.W, a.lohi, a.tp, s.o_phase < 0 ? s.phase : 0, a.N, 0,
+                     a.H, a.K, a.costs, nullptr, nullptr, nullptr, nullptr, m->d_stats, dshift, a.trace, ovf, s.blk_stride, s.noise_stride, s.o_phase, s.image_stride, s.plants);
   return jh_launch_done(ovf, st);
 }
 

@@ -142,14 +142,17 @@ inline void jh_plant_set(jh_plant_axis& p, int e, int plant) { p.mapped = 1u; p.
 // plants.n_stride behind problem b - 1's, and its image is plants' table entry b instead of b (entry c * B + b with a controller axis, jh_plan_step_randomized_batch).  The default, 0 and the identity, is every
 // other launch.
 // `o_phase` (jh_plan_step_batch_phases, the fr3 kernel alone): the float offset of the problem's phase word in its packed block, whose first word is the record's x0 --
-// the one argument of the single launch that is a problem's own.  -1: the launch has no phase (the leap kernel ignores the field).  The fr3 launcher implements the
-// record's first two lines only and refuses C > 1, a plant axis and image_stride != 0.
+// the one argument of the single launch that is a problem's own.  -1: the launch has no phase word (the leap kernel ignores the field), and the fr3 kernel takes
+// `phase`, 0..3, for every problem: the problems are blocks of one controller's rollouts (jh_plan_step_randomized_phase), and one controller has one phase.  `phase` is
+// read only when o_phase < 0.  The fr3 launcher implements the images and the plant axis as the leap launcher does, reads the model's own int section (fr3_pick has no
+// pair tables; `ints` is not used) and refuses C > 1: the fr3 launch has no controller axis.
 struct jh_rollout_batch {
   const float* images; long long image_stride; const int* ints;
   int B; long long blk_stride, noise_stride;
   int C = 1; long long blk_stride_c = 0, noise_stride_c = 0, image_stride_c = 0;
   jh_plant_axis plants = {};
   int o_phase = -1;
+  int phase = -1;
 };
 
 // One build of an articulated product kernel: each translation unit that instantiates k_leap_v5 or k_fr3_v6 defines its row, and jh_api.hip's engine_build() maps a model

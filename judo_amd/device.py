@@ -237,7 +237,8 @@ class GpuModelSet:
     """B `GpuModel`s whose images differ in the float section alone, as ONE device buffer for `jh_plan_step_batch_models` (include/judo_amd.h): problem b of the batched
     plan step runs on `models[b]`'s constants.  The library checks the members (same dimensions, int section, kernel build and settings; each image acceptable to its
     kernel) and raises ValueError / JudoAmdError naming the member and the field.  The set keeps its members alive: member 0's handle stays in use for everything but the
-    float sections, and its `stats()` collect the counters of the whole launch."""
+    float sections, and its `stats()` collect the counters of the whole launch.  fr3_pick members make an fr3 set (`jh_fr3_model_set_create`, `fr3` is True), which the
+    entries that carry a phase plan: `jh_plan_step_batch_phases_models` and `jh_plan_step_randomized_phase`."""
 
     def __init__(self, models) -> None:
         self.models = list(models)
@@ -245,7 +246,11 @@ class GpuModelSet:
             raise ValueError("a model set needs at least one model")
         handles = (C.c_void_p * len(self.models))(*[m.handle.value for m in self.models])
         handle = C.c_void_p()
-        _lib.check(_lib.lib().jh_model_set_create(handles, len(self.models), C.byref(handle)), "jh_model_set_create")
+        # the members' family picks the constructor: fr3_pick members alone make an fr3 set, which the phase-taking entries plan (`jh_plan_step_batch_phases_models`,
+        # `jh_plan_step_randomized_phase`); anything else, a mixture included, goes to the generic constructor and meets its checks
+        self.fr3 = all(m.desc.get("family", m.task) == "fr3_pick" for m in self.models)
+        create = "jh_fr3_model_set_create" if self.fr3 else "jh_model_set_create"
+        _lib.check(getattr(_lib.lib(), create)(handles, len(self.models), C.byref(handle)), create)
         self.handle = handle
 
     def __len__(self) -> int:

@@ -78,7 +78,8 @@ class EnsembleController(Controller):
         if task.uses_locomotion_policy:
             raise ValueError("the Spot policy tasks have no ensemble plan step: their iteration is the materialise path (spline, policy rollout, reward, update), not one library call")
         if task.desc.get("family", task.desc["task"]) == "fr3_pick":
-            raise ValueError("fr3_pick has no ensemble plan step: its phase is chosen per problem on the host and its batched launch (judo_amd.fr3_fleet) reads one model image, not a model set")
+            raise ValueError("fr3_pick has no ensemble plan step: its phase is chosen per problem on the host and the ensemble entries carry none.  One arm against perturbed "
+                             "plants at the cost of a plain plan step is judo_amd.fr3_randomized.make_fr3_randomized_controller")
         check_descriptions(descriptions)
         self._descriptions = list(descriptions)
         task.desc = self._descriptions[0]

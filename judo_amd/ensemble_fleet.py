@@ -22,7 +22,7 @@ from judo_amd import _lib
 from judo_amd.device import GpuModelSet
 from judo_amd.distributed import world_info
 from judo_amd.ensemble import MAX_ENSEMBLE, EnsembleController, check_descriptions, make_ensemble_controller
-from judo_amd.fleet import ControllerFleet, _FleetBuffers
+from judo_amd.fleet import ControllerFleet, _FleetBuffers, refuse_fr3_randomized
 from judo_amd.models import image_sections
 from judo_amd.randomized import RandomizedController
 
@@ -104,6 +104,7 @@ class EnsembleFleet(ControllerFleet):
         super().__init__(controllers)
 
     def _check_member(self, i: int, c, first) -> None:
+        refuse_fr3_randomized(i, c)
         if isinstance(c, RandomizedController):
             raise ValueError(f"fleet member {i} is a RandomizedController: it rolls each candidate out on one plant of its set, not on all of them, and its plan step "
                              "(jh_plan_step_randomized) is another launch; randomised controllers share one in a RandomizedFleet "

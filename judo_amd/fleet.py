@@ -39,6 +39,14 @@ from judo_amd.optimizers import Optimizer, _NoiseStream
 from judo_amd.tasks import get_registered_tasks
 
 
+def refuse_fr3_randomized(i: int, c: Controller) -> None:
+    """No fleet takes an `FR3RandomizedController` (judo_amd.fr3_randomized): raises ValueError naming why.  Every fleet's `_check_member` begins with it."""
+    if getattr(c, "_fr3_randomized", False):
+        raise ValueError(f"fleet member {i} is an FR3RandomizedController: its plan step (jh_plan_step_randomized_phase) puts the rollout blocks of ONE arm on the launch's "
+                         "problem axis, and the fr3 launch has no controller axis behind it, so it shares a launch with no other controller.  Fleets of fr3_pick controllers "
+                         "that believe one plant each are an FR3Fleet or an FR3PlantFleet (judo_amd.fr3_fleet.make_fr3_fleet)")
+
+
 class _MemberBuffers:
     """A member's slice of the fleet's buffers under the names `Controller`'s helpers use on a `_PlanBuffers`."""
 
@@ -176,6 +184,7 @@ class ControllerFleet:
                 "default_policy_command": np.asarray(t.default_policy_command).tolist()}
 
     def _check_member(self, i: int, c: Controller, first: Controller) -> None:
+        refuse_fr3_randomized(i, c)
         if isinstance(c, RandomizedController) and not self._randomized_members:
             # (its iteration shape reads "plan_step" too, and the batched plan step would run every block on `c.model`, plant 0, and drop the assignment without a word)
             raise ValueError(f"fleet member {i} is a RandomizedController: its plan step spreads the rollout blocks over the plants of its own set "

@@ -9,16 +9,25 @@ The reference's shipped configuration is 64 rollouts x 250 steps, a handful of o
 
 What the members share is what `ControllerFleet`'s members share, and ONE model image: a model set per problem is not available for fr3_pick, so members with perturbed
 physics are refused, as is a mixture of the default and the self-collision build.  State, time, goal, seed, nominal, CEM sigma and the phase are a member's own.
-Afterwards each member is bit for bit where its own `update_action()` would have left it."""
+Afterwards each member is bit for bit where its own `update_action()` would have left it.
+
+An `FR3PlantFleet` lifts the one-image rule: B arms on B plants (an unknown cube mass, pad friction or gripper gain per arm) in one launch.  Its members keep a `GpuModel`
+each, their images differ in the float section alone (`models.scaled_description`), and the fleet plans them through one `GpuModelSet` of fr3_pick models and
+`jh_plan_step_batch_phases_models`, where problem b reads image b.  The contract is the same: member b ends bit for bit where its own `update_action()` on its own plant
+would have left it, `task.phase` included.  `make_fr3_fleet(..., descriptions=[...])` makes one."""
 
 from __future__ import annotations
+
+from typing import Sequence
 
 import torch
 
 from judo_amd import _lib
 from judo_amd.controller import Controller, make_controller_for
 from judo_amd.device import GpuModelSet
-from judo_amd.fleet import ControllerFleet, _FleetBuffers
+from judo_amd.ensemble import MAX_ENSEMBLE, check_descriptions
+from judo_amd.fleet import ControllerFleet, _FleetBuffers, refuse_fr3_randomized
+from judo_amd.models import layout
 from judo_amd.tasks import FR3Pick
 
 
@@ -28,17 +37,20 @@ class FR3Fleet(ControllerFleet):
 
     _fr3_members = True
     _block_extra_words = 1  # the phase word, behind the bounds
+    _one_image = True  # every member plans on member 0's image (FR3PlantFleet: an image per member)
 
     def _check_member(self, i: int, c: Controller, first: Controller) -> None:
+        refuse_fr3_randomized(i, c)
         if c.model is None or c.model.desc.get("family", c.model.task) != "fr3_pick" or not isinstance(c.task, FR3Pick):
             raise ValueError(f"fleet member {i} is no fr3_pick controller ({type(c.task).__name__}): an FR3Fleet plans fr3_pick alone; every other model family shares a "
                              "launch in a ControllerFleet (judo_amd.fleet.make_controller_fleet)")
         if c.task.self_collision != first.task.self_collision or c.model.self_collision != first.model.self_collision:
             raise ValueError(f"fleet member {i} differs from member 0 in self_collision: the launch runs one build of the fr3 kernel")
-        if c.model is not first.model and c.model._blob != first.model._blob:
+        if self._one_image and c.model is not first.model and c.model._blob != first.model._blob:
             raise ValueError(f"fleet member {i} has another model image than member 0: an FR3Fleet plans every member on ONE image; a model set per problem "
-                             "(randomised physics) is not available for fr3_pick")
-        super()._check_member(i, c, first)
+                             "(randomised physics) is not available for fr3_pick in this class.  An FR3PlantFleet (make_fr3_fleet(..., descriptions=...)) plans "
+                             "members whose images differ in the float section alone")
+        super()._check_member(i, c, first)  # (an image of a member's own: the header and the int section must be member 0's, `image_sections`, and the kernel build)
 
     def _models(self) -> GpuModelSet | None:
         return None  # (one image: byte-identical members were pointed at member 0's model when the fleet was made)
@@ -57,18 +69,65 @@ class FR3Fleet(ControllerFleet):
         _lib.check(st, "jh_plan_step_batch_phases")
 
 
-def make_fr3_fleet(optimizer: str, B: int, device: torch.device | None = None, self_collision: bool = False) -> FR3Fleet:
+class FR3PlantFleet(FR3Fleet):
+    """An `FR3Fleet` whose members plan on plants of their own: `fleet[i].model` is member i's `GpuModel`, and the images differ in the float section alone (masses,
+    inertias, friction, gains).  One launch, a model image and a phase per problem.  Members that share member 0's image byte for byte share its `GpuModel`; a fleet of
+    such members alone plans as an `FR3Fleet` does."""
+
+    _one_image = False
+
+    def _models(self) -> GpuModelSet | None:
+        return ControllerFleet._models(self)  # (None while every member plans on the fleet's one model; else the set, which `GpuModelSet` makes with the fr3 constructor)
+
+    def _launch(self, lib, model_set, fb: _FleetBuffers, in_place: bool, noise: torch.Tensor, W, N: int, H: int, K: int, nu: int, costs: torch.Tensor, nfl: int,
+                update_args: tuple, E_t: int, row: int, colmajor: int, stream) -> None:
+        """The phase words, then the B plan steps as one call on the set: problem b on image b."""
+        if model_set is None:
+            return super()._launch(lib, model_set, fb, in_place, noise, W, N, H, K, nu, costs, nfl, update_args, E_t, row, colmajor, stream)
+        cs = self.controllers
+        off = fb.offsets
+        for i, c in enumerate(cs):
+            fb.host_np[i * fb.blk_stride + fb.nblk] = float(int(c.task.phase))
+        mode, lam, k_el, tie = update_args
+        st = lib.jh_plan_step_batch_phases_models(model_set.handle, len(cs), fb.host_ptr if in_place else fb.blk.data_ptr(), fb.host_ptr, 4 * (fb.nblk + fb.extra), 4 * fb.blk_stride, off[1],
+                                                  off[2], off[3], off[4], fb.nblk, noise.data_ptr(), N, K * nu * N, _lib.ptr(W), N, H, K, costs.data_ptr(),
+                                                  fb.trace_buf.data_ptr() if nfl else None, mode, lam, k_el, tie, E_t, row, colmajor, fb.scratch.data_ptr(), fb.out_host_ptr, fb.out_stride,
+                                                  fb.done.data_ptr() if in_place else fb.out_host_ptr, None, stream)
+        _lib.check(st, "jh_plan_step_batch_phases_models")
+
+
+def make_fr3_fleet(optimizer: str, B: int, device: torch.device | None = None, self_collision: bool = False, descriptions: Sequence[dict] | None = None) -> FR3Fleet:
     """B fr3_pick controllers with the registered optimizer (`make_controller_for(FR3Pick(self_collision), optimizer)`, B times) around ONE `GpuModel`.
-    `self_collision`: every member on the self-collision build of the kernel (all 190 pairs of the MJCF) instead of the default one."""
+    `self_collision`: every member on the self-collision build of the kernel (all 190 pairs of the MJCF) instead of the default one.
+
+    `descriptions`: B model descriptions, one per member (`models.scaled_description(FR3Pick(self_collision).desc, body_mass=..., geom_friction=..., actuator_kp=...)`): an
+    `FR3PlantFleet`, where member i's task takes `descriptions[i]` and keeps a `GpuModel` of its own.  The descriptions must pack to images that differ in the float
+    section alone (`ensemble.check_descriptions`) and carry the `self_collision` key of the build asked for."""
     if B < 1:
         raise ValueError("a fleet needs at least one controller")
+    if descriptions is not None:
+        descriptions = list(descriptions)
+        if len(descriptions) != B:
+            raise ValueError(f"{len(descriptions)} descriptions for a fleet of {B}")
+        for i, d in enumerate(descriptions):
+            if d.get("family", d.get("task")) != "fr3_pick":
+                raise ValueError(f"description {i} is no fr3_pick description (task {d.get('task')!r})")
+            if bool(d.get("self_collision")) != bool(self_collision):
+                raise ValueError(f"description {i} differs from the fleet in self_collision: derive the descriptions from FR3Pick(self_collision={bool(self_collision)}).desc")
+        for lo in range(0, B, MAX_ENSEMBLE - 1):  # (the rule has an ensemble's size limit: every chunk is held to member 0)
+            check_descriptions(descriptions[:1] + descriptions[max(lo, 1) : lo + MAX_ENSEMBLE - 1])
     members: list[Controller] = []
-    for _ in range(B):
+    for i in range(B):
         t = FR3Pick(self_collision=self_collision)
-        if members:
+        if descriptions is not None:
+            t.desc = descriptions[i]
+            t._layout, t._ctrlrange, t._jadr = layout(t.desc), None, None
+            if members and t.desc is members[0].task.desc:
+                t._gpu = members[0].model
+        elif members:
             t._gpu = members[0].model  # (Task.gpu_model hands it out instead of packing and uploading the image again)
         members.append(make_controller_for(t, optimizer, device=device))
-    return FR3Fleet(members)
+    return FR3PlantFleet(members) if descriptions is not None else FR3Fleet(members)
 
 
-__all__ = ["FR3Fleet", "make_fr3_fleet"]
+__all__ = ["FR3Fleet", "FR3PlantFleet", "make_fr3_fleet"]

@@ -67,12 +67,14 @@ def plant_of_rollout(assignment: Sequence[int], num_rollouts: int) -> np.ndarray
     return np.repeat(np.asarray(assignment, dtype=np.int64), N // G)
 
 
-def check_task(task: Task) -> None:
-    """The tasks without a randomised plan step, refused before any model is made; raises ValueError."""
+def check_task(task: Task, fr3: bool = False) -> None:
+    """The tasks without a randomised plan step, refused before any model is made; raises ValueError.  `fr3`: the caller's plan step carries the arm's phase
+    (judo_amd.fr3_randomized), so fr3_pick passes."""
     if task.uses_locomotion_policy:
         raise ValueError("the Spot policy tasks have no randomised plan step: their iteration is the materialise path (spline, policy rollout, reward, update), not one library call")
-    if task.desc.get("family", task.desc["task"]) == "fr3_pick":
-        raise ValueError("fr3_pick has no randomised plan step: its phase is chosen per problem on the host and its batched launch (judo_amd.fr3_fleet) reads one model image, not a model set")
+    if task.desc.get("family", task.desc["task"]) == "fr3_pick" and not fr3:
+        raise ValueError("fr3_pick has no randomised plan step behind this class: its phase is chosen per problem on the host, and jh_plan_step_randomized carries none.  "
+                         "judo_amd.fr3_randomized.make_fr3_randomized_controller makes the controller whose plan step carries the phase")
 
 
 class RandomizedController(Controller):
@@ -82,9 +84,19 @@ class RandomizedController(Controller):
     `assignment` (G plant indices, default g % M) may be set between plan steps; `plant_of_rollout` and `plant_rewards()` say which plant a reward belongs to, and
     `set_member(b, description)` replaces one plant."""
 
+    _fr3_randomized = False  # (FR3RandomizedController: the plan step carries the arm's phase; no fleet takes such a member)
+    _entry = "jh_plan_step_randomized"  # the library call of the plan step
+
+    def _check_task(self, task: Task) -> None:
+        check_task(task)
+
+    def _entry_args(self, W, N: int, H: int, K: int) -> tuple:
+        """The entry's arguments between the noise pitch and the table: W, N, H, K."""
+        return (_lib.ptr(W), N, H, K)
+
     def __init__(self, controller_config: ControllerConfig, task: Task, optimizer, descriptions: Sequence[dict], blocks: int | None = None,
                  weights: Sequence[float] | None = None, device: torch.device | None = None) -> None:
-        check_task(task)
+        self._check_task(task)
         check_descriptions(descriptions)
         self._descriptions = list(descriptions)
         M = len(self._descriptions)
@@ -201,10 +213,10 @@ class RandomizedController(Controller):
         in_place = b.blk_stale = self.model.closed_form
         mark = b.done_ptr if self.model.closed_form else b.out_host_ptr
         table = (C.c_ubyte * len(a))(*a)
-        st = lib.jh_plan_step_randomized(self.model_set.handle, b.host_ptr if in_place else b.blk.data_ptr(), b.host_ptr, b.nblk_bytes, int(off[1]), int(off[2]), int(off[3]), int(off[4]),
-                                         noise_p, ldn, _lib.ptr(W), N, H, K, table, len(a), _lib.ptr(b.costs), mode, lam, k_el, tie, _lib.ptr(b.fused_scratch), b.out_host_ptr, mark,
-                                         timing, stream)
-        _lib.check(st, "jh_plan_step_randomized")
+        st = getattr(lib, self._entry)(self.model_set.handle, b.host_ptr if in_place else b.blk.data_ptr(), b.host_ptr, b.nblk_bytes, int(off[1]), int(off[2]), int(off[3]), int(off[4]),
+                                       noise_p, ldn, *self._entry_args(W, N, H, K), table, len(a), _lib.ptr(b.costs), mode, lam, k_el, tie, _lib.ptr(b.fused_scratch), b.out_host_ptr, mark,
+                                       timing, stream)
+        _lib.check(st, self._entry)
         self._assignment_used = list(a)
         state["costs"] = b.costs
         if evs:

@@ -23,7 +23,7 @@ from judo_amd.device import GpuModelSet
 from judo_amd.distributed import world_info
 from judo_amd.ensemble import MAX_ENSEMBLE
 from judo_amd.ensemble_fleet import MAX_ENSEMBLE_FLEET, check_fleet_descriptions, fleet_descriptions
-from judo_amd.fleet import ControllerFleet, _FleetBuffers
+from judo_amd.fleet import ControllerFleet, _FleetBuffers, refuse_fr3_randomized
 from judo_amd.models import image_sections
 from judo_amd.randomized import MAX_PLANT_BLOCKS, RandomizedController, blocks_from_weights, check_task, make_randomized_controller
 from judo_amd.tasks import get_registered_tasks
@@ -93,6 +93,7 @@ class RandomizedFleet(ControllerFleet):
         super().__init__(controllers)
 
     def _check_member(self, i: int, c, first) -> None:
+        refuse_fr3_randomized(i, c)
         if not isinstance(c, RandomizedController):
             raise ValueError(f"fleet member {i} is a {type(c).__name__}, not a RandomizedController: controllers that believe one plant share a launch in a ControllerFleet, "
                              "ensemble controllers in an EnsembleFleet")
