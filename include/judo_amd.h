@@ -342,8 +342,8 @@ int jh_model_set_update(jh_model_set* set, int b, const jh_model* model);
 int jh_model_set_info(const jh_model_set* set, int* out /* HOST, 4 ints */);
 void jh_model_set_destroy(jh_model_set* set);
 /* A model set of fr3_pick models (pick-and-place under an unknown cube mass, pad friction or gripper gain).  jh_model_set_create keeps refusing the family, because the
- * five entries above and below that take its sets carry no phase; this constructor makes the same record for fr3_pick members alone, and the two entries that carry a
- * phase plan it:
+ * five entries above and below that take its sets carry no phase; this constructor makes the same record for fr3_pick members alone, and the entries that carry a
+ * phase plan it -- the two here and the three `_phase` / `_phases` forms of the ensemble and randomised entries below:
  *   jh_fr3_model_set_create            the checks of jh_model_set_create member by member -- the same fields, arm_pairs among them, so the default and the self-collision
  *                                      build do not mix; each image must pass its own build's acceptance test on its own floats (the finger slides antiparallel).
  *                                      JH_ERR_UNSUPPORTED for a member that is no fr3_pick model.  jh_model_set_update, _info and _destroy work on the set; _update refuses an
@@ -359,8 +359,9 @@ void jh_model_set_destroy(jh_model_set* set);
  *                                      with the same block and noise; only global rollout 0 is noise-free; out = nominal | sigma is what jh_update_fused writes for the
  *                                      N costs.  No trace buffer.  Every check of jh_plan_step_randomized, plus JH_ERR_INVALID for a phase outside 0..3 and K > 8 and
  *                                      JH_ERR_UNSUPPORTED for a set that is not fr3_pick, all before anything is enqueued.
- * The fr3 launch has no controller axis: an fr3 ensemble and a fleet of randomised fr3 controllers do not exist, and jh_plan_step_ensemble, _ensemble_batch,
- * _randomized, _randomized_batch and jh_plan_step_batch_models refuse an fr3 set (JH_ERR_UNSUPPORTED), naming the entry above that serves it. */
+ * The fr3 launch has a controller axis in blockIdx.z, as the leap kernel's has, and three more entries use it for an fr3 set (documented with the entries they extend,
+ * below): jh_plan_step_ensemble_phase, jh_plan_step_ensemble_batch_phases and jh_plan_step_randomized_batch_phases.  jh_plan_step_ensemble, _ensemble_batch,
+ * _randomized, _randomized_batch and jh_plan_step_batch_models carry no phase and keep refusing an fr3 set (JH_ERR_UNSUPPORTED), naming the entries that serve it. */
 int jh_fr3_model_set_create(const jh_model* const* models /* HOST array of B handles */, int B, jh_model_set** out);
 int jh_plan_step_batch_phases_models(const jh_model_set* set, int B, void* blk_dev, const void* blk_host, size_t blk_bytes, size_t blk_stride_bytes, int o_nominal, int o_sigma, int o_tp,
                                      int o_lohi, int o_phase, const float* noise, int ldn, size_t noise_stride_floats, const float* W, int N, int H, int K, float* costs, float* trace,
@@ -408,6 +409,14 @@ int jh_ensemble_costs(const float* member_costs /* DEVICE, M x ld */, int M, int
 int jh_plan_step_ensemble(const jh_model_set* set, void* blk_dev, const void* blk_host, size_t blk_bytes, int o_nominal, int o_sigma, int o_tp, int o_lohi, const float* noise, int ldn,
                           const float* W, int N, int H, int K, float* member_costs /* DEVICE, M x N */, float* costs /* DEVICE, N */, int worst, int mode, float lambda, int k,
                           int tie_high, float* scratch, float* out /* nominal | sigma */, void* out_host_mark, void* const* timing, void* stream);
+/* jh_plan_step_ensemble for fr3_pick, with `phase`, 0..3, behind W: one arm in one phase against the M plants of an fr3 set (jh_fr3_model_set_create).  The fr3 kernel's
+ * batched launch on the grid (workgroups, M): every member takes the phase from the launch record as the single launch takes its argument, so row m of member_costs is
+ * bit for bit the costs of jh_plan_step(member m's own handle, ..., phase, ...) with the same block and noise; `costs` and out = nominal | sigma are the ensemble call's.
+ * The latency mode is chosen from the M * N rollouts of the launch (the bits do not depend on it).  Every check of jh_plan_step_ensemble, plus JH_ERR_INVALID for a phase
+ * outside 0..3 and K > 8 and JH_ERR_UNSUPPORTED for a set that is not fr3_pick (jh_plan_step_ensemble plans those), all before anything is enqueued. */
+int jh_plan_step_ensemble_phase(const jh_model_set* set, void* blk_dev, const void* blk_host, size_t blk_bytes, int o_nominal, int o_sigma, int o_tp, int o_lohi, const float* noise, int ldn,
+                                const float* W, int phase, int N, int H, int K, float* member_costs /* DEVICE, M x N */, float* costs /* DEVICE, N */, int worst, int mode, float lambda, int k,
+                                int tie_high, float* scratch, float* out /* nominal | sigma */, void* out_host_mark, void* const* timing, void* stream);
 /* B ensemble plan steps as ONE call with ONE completion mark (several robots, or one robot swept over risk levels, goals or seeds: B controllers that each plan against
  * M plants; the reference has no counterpart).  Controller b rolls its own N candidates out on its M plants, aggregates them with its own worst[b] and updates its own
  * nominal; its results are bit for bit those of jh_plan_step_ensemble on its block, its noise and its plants with worst[b].
@@ -429,6 +438,16 @@ int jh_plan_step_ensemble_batch(const jh_model_set* set, int B, int M, void* blk
                                 int o_lohi, const float* noise, int ldn, size_t noise_stride_floats, const float* W, int N, int H, int K, float* member_costs /* DEVICE, B x M x N */,
                                 float* costs /* DEVICE, B x N */, const int* worst /* HOST, B */, int mode, float lambda, int k, int tie_high, float* scratch, float* out, size_t out_stride_floats,
                                 void* out_host_mark, void* const* timing, void* stream);
+/* jh_plan_step_ensemble_batch for fr3_pick, with `o_phase` behind o_lohi as in jh_plan_step_batch_phases: controller c's phase is the float word at offset o_phase of its
+ * own packed block (0.0, 1.0, 2.0 or 3.0), which its M members all read -- the members' block stride is 0, the controller's is blk_stride_bytes.  The fr3 kernel's batched
+ * launch on the grid (workgroups, M, B); controller c's results are bit for bit those of jh_plan_step_ensemble_phase on its block, noise and plants with worst[c] and its
+ * phase.  The set is shared (M plants) or per controller (B * M), as above.  Every check of jh_plan_step_ensemble_batch, plus JH_ERR_INVALID for an o_phase that is negative
+ * or outside the block, for a phase word that is not exactly 0, 1, 2 or 3 (read from the HOST block; the error names the controller) and for K > 8, and
+ * JH_ERR_UNSUPPORTED for a set that is not fr3_pick (jh_plan_step_ensemble_batch plans those), all before anything is enqueued. */
+int jh_plan_step_ensemble_batch_phases(const jh_model_set* set, int B, int M, void* blk_dev, const void* blk_host, size_t blk_bytes, size_t blk_stride_bytes, int o_nominal, int o_sigma, int o_tp,
+                                       int o_lohi, int o_phase, const float* noise, int ldn, size_t noise_stride_floats, const float* W, int N, int H, int K,
+                                       float* member_costs /* DEVICE, B x M x N */, float* costs /* DEVICE, B x N */, const int* worst /* HOST, B */, int mode, float lambda, int k, int tie_high,
+                                       float* scratch, float* out, size_t out_stride_floats, void* out_host_mark, void* const* timing, void* stream);
 /* ONE domain-randomised plan step (MPPI / CEM / PS with a plant drawn per rollout; the reference has no counterpart): one controller, one nominal spline, N candidates,
  * each rolled out on ONE member of a model set, M <= JH_MAX_ENSEMBLE, and the update on the N costs as they are -- the rollouts of a plain plan step, never fitted to one
  * plant.  The rule, fixed here so that it can be tested bit for bit: the N candidates form G contiguous blocks of Nb = N / G rollouts (N % G == 0), block g is rollouts
@@ -476,6 +495,15 @@ int jh_plan_step_randomized_batch(const jh_model_set* set, int B, int M, void* b
                                   int o_lohi, const float* noise, int ldn, size_t noise_stride_floats, const float* W, int N, int H, int K,
                                   const unsigned char* plant_of_block /* HOST, B x G */, int G, float* costs /* DEVICE, B x N */, int mode, float lambda, int k, int tie_high, float* scratch,
                                   float* out, size_t out_stride_floats, void* out_host_mark, void* const* timing, void* stream);
+/* jh_plan_step_randomized_batch for fr3_pick, with `o_phase` behind o_lohi: controller c's phase is the float word at offset o_phase of its own packed block, under the
+ * rules of jh_plan_step_ensemble_batch_phases.  The fr3 kernel's batched launch on the grid (workgroups of Nb rollouts, G, B); controller c's row of `costs` and its
+ * record are bit for bit what jh_plan_step_randomized_phase writes on c's block, noise slice and plants with its table and its phase, and only each controller's global
+ * rollout 0 is noise-free.  Every check of jh_plan_step_randomized_batch, plus the phase-word checks and K > 8 (JH_ERR_INVALID) and JH_ERR_UNSUPPORTED for a set that
+ * is not fr3_pick (jh_plan_step_randomized_batch plans those), all before anything is enqueued. */
+int jh_plan_step_randomized_batch_phases(const jh_model_set* set, int B, int M, void* blk_dev, const void* blk_host, size_t blk_bytes, size_t blk_stride_bytes, int o_nominal, int o_sigma,
+                                         int o_tp, int o_lohi, int o_phase, const float* noise, int ldn, size_t noise_stride_floats, const float* W, int N, int H, int K,
+                                         const unsigned char* plant_of_block /* HOST, B x G */, int G, float* costs /* DEVICE, B x N */, int mode, float lambda, int k, int tie_high,
+                                         float* scratch, float* out, size_t out_stride_floats, void* out_host_mark, void* const* timing, void* stream);
 /* The noise of those B problems in one launch (judo/optimizers/{mppi.py:52,ps.py:43,cem.py:67}, one np.random.randn per controller): problem b's (rows, ldn) slice of `out`
  * (B x rows x ldn floats) is bit for bit what jh_noise_normal(seeds[b], draws[b], rows, 0, n_local, out + b * rows * ldn, ldn) writes; columns n_local .. ldn - 1 are left
  * alone.  seeds / draws: HOST arrays of B entries, read before the call returns (one launch per 256 problems: the pairs travel as kernel arguments). */

@@ -99,12 +99,20 @@ _SIGNATURES = {
     "jh_ensemble_costs": (C.c_int, [f32p, C.c_int, C.c_int, C.c_int, C.c_int, f32p, C.c_void_p]),
     "jh_plan_step_ensemble": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_int, C.c_int, C.c_int, C.c_int, f32p, C.c_int, f32p, C.c_int, C.c_int, C.c_int, f32p, f32p, C.c_int, C.c_int,
                                         C.c_float, C.c_int, C.c_int, f32p, f32p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "jh_plan_step_ensemble_phase": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_int, C.c_int, C.c_int, C.c_int, f32p, C.c_int, f32p, C.c_int, C.c_int, C.c_int, C.c_int, f32p, f32p, C.c_int,
+                                              C.c_int, C.c_float, C.c_int, C.c_int, f32p, f32p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "jh_plan_step_ensemble_batch": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_size_t, C.c_size_t, C.c_int, C.c_int, C.c_int, C.c_int, f32p, C.c_int, C.c_size_t, f32p, C.c_int,
                                               C.c_int, C.c_int, f32p, f32p, C.POINTER(C.c_int), C.c_int, C.c_float, C.c_int, C.c_int, f32p, f32p, C.c_size_t, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "jh_plan_step_ensemble_batch_phases": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_size_t, C.c_size_t, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, f32p, C.c_int, C.c_size_t, f32p,
+                                                     C.c_int, C.c_int, C.c_int, f32p, f32p, C.POINTER(C.c_int), C.c_int, C.c_float, C.c_int, C.c_int, f32p, f32p, C.c_size_t, C.c_void_p, C.c_void_p,
+                                                     C.c_void_p]),
     "jh_plan_step_randomized": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_int, C.c_int, C.c_int, C.c_int, f32p, C.c_int, f32p, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_ubyte), C.c_int,
                                           f32p, C.c_int, C.c_float, C.c_int, C.c_int, f32p, f32p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "jh_plan_step_randomized_batch": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_size_t, C.c_size_t, C.c_int, C.c_int, C.c_int, C.c_int, f32p, C.c_int, C.c_size_t, f32p, C.c_int,
                                                 C.c_int, C.c_int, C.POINTER(C.c_ubyte), C.c_int, f32p, C.c_int, C.c_float, C.c_int, C.c_int, f32p, f32p, C.c_size_t, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "jh_plan_step_randomized_batch_phases": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_size_t, C.c_size_t, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, f32p, C.c_int, C.c_size_t, f32p,
+                                                       C.c_int, C.c_int, C.c_int, C.POINTER(C.c_ubyte), C.c_int, f32p, C.c_int, C.c_float, C.c_int, C.c_int, f32p, f32p, C.c_size_t, C.c_void_p, C.c_void_p,
+                                                       C.c_void_p]),
     "jh_update_fused_batch": (C.c_int, [C.c_int, f32p, f32p, C.c_size_t, C.c_int, C.c_int, C.c_int, f32p, C.c_int, C.c_size_t, C.c_int, C.c_int, C.c_int, C.c_int, C.c_float, C.c_int, C.c_int, C.c_int,
                                         f32p, C.c_int, C.c_int, f32p, f32p, C.c_size_t, C.c_void_p, C.c_void_p]),
     "jh_noise_normal_batch": (C.c_int, [C.c_int, C.POINTER(C.c_ulonglong), C.POINTER(C.c_uint), C.c_int, C.c_int, f32p, C.c_int, C.c_void_p]),

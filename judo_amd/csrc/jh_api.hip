@@ -606,6 +606,16 @@ extern "C" int jh_plan_step(const jh_model* m, void* blk_dev, const void* blk_ho
                    tie_high, E, row_floats, colmajor, scratch, out, flag, nullptr, timing, stream);
 }
 
+// The B phase words of a batched fr3_pick call (`what`: whose, for the message), on the host, before anything is enqueued: the kernel converts the word and branches on it.
+static int phase_words(const char* who, const char* what, int B, const void* blk_host, size_t blk_bytes, size_t blk_stride_bytes, int o_phase) {
+  JH_REQUIRE(sizeof(float) * ((size_t)o_phase + 1) <= blk_bytes, "%s: o_phase = %d lies outside a block of %zu bytes", who, o_phase, blk_bytes);
+  for (int p = 0; p < B; p++) {
+    const float w = reinterpret_cast<const float*>(static_cast<const char*>(blk_host) + (size_t)p * blk_stride_bytes)[o_phase];
+    JH_REQUIRE(w == 0.f || w == 1.f || w == 2.f || w == 3.f, "%s: the phase word of %s %d is %g, not exactly 0, 1, 2 or 3 (LIFT, MOVE, PLACE, HOMING)", who, what, p, (double)w);
+  }
+  return JH_OK;
+}
+
 // B plan steps of one model as ONE call (include/judo_amd.h): the B packed blocks go up in one copy (or are read in place), the kernels take the problem from blockIdx.y and
 // reach its buffers through strides, and one completion mark stands behind all of them.  Problem 0's launch record is built by the single call's own checks
 // (jh_update_tail_args); the kernels derive problem b's from it.  `images` / `image_stride`: the float section the rollout kernels read for problem 0 and the floats to
@@ -642,13 +652,7 @@ static int plan_step_batch(const char* who, const jh_model* m, const float* imag
   const bool closed = m->kind == JH_TASK_CARTPOLE || m->kind == JH_TASK_CYLINDER_PUSH;
   const jh_engine_build* eb = engine_build(m);
   if (!closed && !(eb && eb->rollout_cost_batch)) { jh_set_error("%s: no batched kernel for this model", who); return JH_ERR_UNSUPPORTED; }
-  if (o_phase >= 0) {  // the B phase words, on the host, before anything is enqueued: the kernel converts the word and branches on it
-    JH_REQUIRE(sizeof(float) * ((size_t)o_phase + 1) <= blk_bytes, "%s: o_phase = %d lies outside a block of %zu bytes", who, o_phase, blk_bytes);
-    for (int p = 0; p < B; p++) {
-      const float w = reinterpret_cast<const float*>(static_cast<const char*>(blk_host) + (size_t)p * blk_stride_bytes)[o_phase];
-      JH_REQUIRE(w == 0.f || w == 1.f || w == 2.f || w == 3.f, "%s: the phase word of problem %d is %g, not exactly 0, 1, 2 or 3 (LIFT, MOVE, PLACE, HOMING)", who, p, (double)w);
-    }
-  }
+  if (o_phase >= 0) { if (int rc = phase_words(who, "problem", B, blk_host, blk_bytes, blk_stride_bytes, o_phase)) return rc; }
   hipStream_t st = (hipStream_t)stream;
   const float* b = (const float*)blk_dev;
   if (blk_dev != blk_host) { const int rc = jh_upload_async(blk_dev, blk_host, (size_t)(B - 1) * blk_stride_bytes + blk_bytes, stream); if (rc != JH_OK) return rc; }
@@ -874,10 +878,11 @@ extern "C" int jh_plan_step_batch_phases_models(const jh_model_set* set, int B, 
 // member rolls out the same N candidates from the same block, on its own image, into its own row of member_costs -- then k_update_tail_ensemble, which aggregates the M
 // rows into `costs` and runs the single call's tail on them.  The records are built here: the batched entry points refuse strides below a block, rightly for what they do.
 // Always two launches (the closed-form models' one-launch form would roll a candidate out on one member per workgroup); no trace buffer, no knots_out.
-extern "C" int jh_plan_step_ensemble(const jh_model_set* set, void* blk_dev, const void* blk_host, size_t blk_bytes, int o_nominal, int o_sigma, int o_tp, int o_lohi, const float* noise, int ldn,
-                                     const float* W, int N, int H, int K, float* member_costs, float* costs, int worst, int mode, float lambda, int k, int tie_high, float* scratch, float* out,
-                                     void* out_host_mark, void* const* timing, void* stream) {
-  const char* who = "plan_step_ensemble";
+// `phase`: -1 for jh_plan_step_ensemble, which has none and refuses fr3_pick; 0..3 for jh_plan_step_ensemble_phase, which plans fr3_pick alone (checked by the entry):
+// the one controller's phase travels in the launch record, and every member's workgroups take it as the single launch takes its argument.
+static int plan_step_ensemble(const char* who, const jh_model_set* set, void* blk_dev, const void* blk_host, size_t blk_bytes, int o_nominal, int o_sigma, int o_tp, int o_lohi, const float* noise, int ldn,
+                              const float* W, int phase, int N, int H, int K, float* member_costs, float* costs, int worst, int mode, float lambda, int k, int tie_high, float* scratch, float* out,
+                              void* out_host_mark, void* const* timing, void* stream) {
 #define JH_ENS_PTR(p) JH_REQUIRE((p) != nullptr, "%s: " #p " is a null pointer", who)
   JH_ENS_PTR(set); JH_ENS_PTR(blk_dev); JH_ENS_PTR(blk_host); JH_ENS_PTR(noise); JH_ENS_PTR(W); JH_ENS_PTR(member_costs); JH_ENS_PTR(costs); JH_ENS_PTR(scratch); JH_ENS_PTR(out);
 #undef JH_ENS_PTR
@@ -885,7 +890,9 @@ extern "C" int jh_plan_step_ensemble(const jh_model_set* set, void* blk_dev, con
   const int M = set->B;
   JH_REQUIRE(M <= JH_MAX_ENSEMBLE, "%s: a set of %d members exceeds JH_MAX_ENSEMBLE = %d", who, M, JH_MAX_ENSEMBLE);
   JH_REQUIRE(worst >= 1 && worst <= M, "%s: worst = %d outside [1, M = %d]", who, worst, M);
-  if (m->kind == JH_TASK_FR3_PICK) { jh_set_error("%s: fr3_pick has no batched plan step (its phase is chosen per problem on the host) behind this entry: an fr3_pick set has no ensemble form; jh_plan_step_randomized_phase spreads one arm's candidates over the set's plants", who); return JH_ERR_UNSUPPORTED; }
+  if (m->kind == JH_TASK_FR3_PICK && phase < 0) { jh_set_error("%s: fr3_pick has no batched plan step (its phase is chosen per problem on the host) behind this entry: jh_plan_step_ensemble_phase takes the arm's phase and plans it against the set's plants; jh_plan_step_randomized_phase spreads one arm's candidates over them", who); return JH_ERR_UNSUPPORTED; }
+  if (m->kind != JH_TASK_FR3_PICK && phase >= 0) { jh_set_error("%s: a phase is fr3_pick's alone; jh_plan_step_ensemble plans this set", who); return JH_ERR_UNSUPPORTED; }
+  JH_REQUIRE(phase < 0 || K <= 8, "%s: the cooperative arm kernel keeps at most 8 knots per actuator in registers (K=%d)", who, K);
   if (m->kind == JH_TASK_LEAP_CUBE && m->kernel_gen != 3) { jh_set_error("%s: only kernel generation 3 of the leap family has a batched launch (this model runs %d)", who, m->kernel_gen); return JH_ERR_UNSUPPORTED; }
   JH_REQUIRE(N > 0 && H > 0 && K >= 1, "%s: N, H, K must be positive (N=%d H=%d K=%d)", who, N, H, K);
   JH_REQUIRE(ldn >= N, "%s: ldn (%d) < N (%d)", who, ldn, N);
@@ -896,6 +903,7 @@ extern "C" int jh_plan_step_ensemble(const jh_model_set* set, void* blk_dev, con
   const size_t need = sizeof(float) * (size_t)std::max(std::max(nx, o_nominal + KU), std::max(std::max(o_sigma + KU, o_tp + m->ntaskparam), o_lohi + 2 * m->nu));
   JH_REQUIRE(blk_bytes >= need, "%s: a block of %zu bytes does not hold x0 | nominal | sigma | task params | bounds at the given offsets (%zu bytes)", who, blk_bytes, need);
   JH_REQUIRE(m->plan_step_launches != 1, "%s: one launch is forced (jh_model_set_plan_step_launches) but the ensemble's plan step is two launches", who);
+  JH_REQUIRE((long long)M * N <= 0x7fffffffll, "%s: M * N = %lld rollouts exceed one launch", who, (long long)M * N);
   const bool closed = m->kind == JH_TASK_CARTPOLE || m->kind == JH_TASK_CYLINDER_PUSH;
   const jh_engine_build* eb = engine_build(m);
   if (!closed && !(eb && eb->rollout_cost_batch)) { jh_set_error("%s: no batched kernel for this model", who); return JH_ERR_UNSUPPORTED; }
@@ -919,7 +927,8 @@ extern "C" int jh_plan_step_ensemble(const jh_model_set* set, void* blk_dev, con
     rc = jh_simple_rollout_cost_batch(m, set->d_images, b, b + o_tp, W, H, K, ra, s, st);
   } else {
     const jh_rollout_args ra = {b, b + o_nominal, noise, ldn, b + o_sigma, W, b + o_lohi, b + o_tp, 0, N, 0, H, K, member_costs, nullptr, nullptr};
-    const jh_rollout_batch rb = {set->d_images, (long long)set->stride, ints, M, 0, 0};
+    jh_rollout_batch rb = {set->d_images, (long long)set->stride, ints, M, 0, 0};
+    rb.phase = phase;
     rc = eb->rollout_cost_batch(m, ra, rb, st);
   }
   if (rc == JH_OK && timing) JH_HIP(hipEventRecord((hipEvent_t)timing[1], st));
@@ -928,6 +937,25 @@ extern "C" int jh_plan_step_ensemble(const jh_model_set* set, void* blk_dev, con
   if (rc == JH_OK && timing) JH_HIP(hipEventRecord((hipEvent_t)timing[2], st));
   if (rc == JH_OK) rc = download_begin(out, out, 0, stream, flag, expect);
   return rc;
+}
+
+extern "C" int jh_plan_step_ensemble(const jh_model_set* set, void* blk_dev, const void* blk_host, size_t blk_bytes, int o_nominal, int o_sigma, int o_tp, int o_lohi, const float* noise, int ldn,
+                                     const float* W, int N, int H, int K, float* member_costs, float* costs, int worst, int mode, float lambda, int k, int tie_high, float* scratch, float* out,
+                                     void* out_host_mark, void* const* timing, void* stream) {
+  return plan_step_ensemble("plan_step_ensemble", set, blk_dev, blk_host, blk_bytes, o_nominal, o_sigma, o_tp, o_lohi, noise, ldn, W, -1, N, H, K, member_costs, costs, worst, mode, lambda, k, tie_high,
+                            scratch, out, out_host_mark, timing, stream);
+}
+
+// jh_plan_step_ensemble for fr3_pick (include/judo_amd.h): the same code path with the arm's phase, which the fr3 kernel's members take from the launch record.
+extern "C" int jh_plan_step_ensemble_phase(const jh_model_set* set, void* blk_dev, const void* blk_host, size_t blk_bytes, int o_nominal, int o_sigma, int o_tp, int o_lohi, const float* noise,
+                                           int ldn, const float* W, int phase, int N, int H, int K, float* member_costs, float* costs, int worst, int mode, float lambda, int k, int tie_high,
+                                           float* scratch, float* out, void* out_host_mark, void* const* timing, void* stream) {
+  const char* who = "plan_step_ensemble_phase";
+  JH_REQUIRE(set != nullptr, "%s: set is a null pointer", who);
+  if (set->m0->kind != JH_TASK_FR3_PICK) { jh_set_error("%s: a phase is fr3_pick's alone; jh_plan_step_ensemble plans this set", who); return JH_ERR_UNSUPPORTED; }
+  JH_REQUIRE(phase >= 0 && phase <= 3, "%s: phase = %d is not 0, 1, 2 or 3 (LIFT, MOVE, PLACE, HOMING)", who, phase);
+  return plan_step_ensemble(who, set, blk_dev, blk_host, blk_bytes, o_nominal, o_sigma, o_tp, o_lohi, noise, ldn, W, phase, N, H, K, member_costs, costs, worst, mode, lambda, k, tie_high, scratch, out,
+                            out_host_mark, timing, stream);
 }
 
 // ONE domain-randomised plan step (include/judo_amd.h): the N candidates of one problem in G blocks of Nb = N / G, block g on plant plant_of_block[g] of the set.  The
@@ -1024,11 +1052,14 @@ extern "C" int jh_plan_step_randomized_phase(const jh_model_set* set, void* blk_
 // controller with the strides of jh_plan_step_batch; a set of M members is shared by all controllers (image stride 0 on that axis), a set of B * M holds controller b's
 // plants at b * M ...  Then k_update_tail_ensemble_batch on (tail workgroups, B): aggregation, tail, the two-level ticket, one completion word.  The checks are the
 // ensemble call's and the batched call's, all in front of the first enqueue.
-extern "C" int jh_plan_step_ensemble_batch(const jh_model_set* set, int B, int M, void* blk_dev, const void* blk_host, size_t blk_bytes, size_t blk_stride_bytes, int o_nominal, int o_sigma, int o_tp,
-                                           int o_lohi, const float* noise, int ldn, size_t noise_stride_floats, const float* W, int N, int H, int K, float* member_costs, float* costs,
-                                           const int* worst, int mode, float lambda, int k, int tie_high, float* scratch, float* out, size_t out_stride_floats, void* out_host_mark,
-                                           void* const* timing, void* stream) {
-  const char* who = "plan_step_ensemble_batch";
+// `o_phase`: -1 for jh_plan_step_ensemble_batch, which has none and refuses fr3_pick; the float offset of every controller's phase word in its block for
+// jh_plan_step_ensemble_batch_phases, which plans fr3_pick alone (checked by the entry).  The members' block stride is 0, so the kernel reads the controller's own word;
+// the B words are checked on the host (phase_words).
+
+static int plan_step_ensemble_batch(const char* who, const jh_model_set* set, int B, int M, void* blk_dev, const void* blk_host, size_t blk_bytes, size_t blk_stride_bytes, int o_nominal, int o_sigma, int o_tp,
+                                    int o_lohi, int o_phase, const float* noise, int ldn, size_t noise_stride_floats, const float* W, int N, int H, int K, float* member_costs, float* costs,
+                                    const int* worst, int mode, float lambda, int k, int tie_high, float* scratch, float* out, size_t out_stride_floats, void* out_host_mark,
+                                    void* const* timing, void* stream) {
 #define JH_ENS_PTR(p) JH_REQUIRE((p) != nullptr, "%s: " #p " is a null pointer", who)
   JH_ENS_PTR(set); JH_ENS_PTR(blk_dev); JH_ENS_PTR(blk_host); JH_ENS_PTR(noise); JH_ENS_PTR(W); JH_ENS_PTR(member_costs); JH_ENS_PTR(costs); JH_ENS_PTR(worst); JH_ENS_PTR(scratch); JH_ENS_PTR(out);
 #undef JH_ENS_PTR
@@ -1037,7 +1068,9 @@ extern "C" int jh_plan_step_ensemble_batch(const jh_model_set* set, int B, int M
   JH_REQUIRE(M >= 1 && M <= JH_MAX_ENSEMBLE, "%s: M = %d outside [1, JH_MAX_ENSEMBLE = %d]", who, M, JH_MAX_ENSEMBLE);
   JH_REQUIRE(set->B == M || set->B == B * M, "%s: a set of %d members is neither the M = %d plants every controller shares nor the B * M = %d plants of B = %d controllers", who, set->B, M, B * M, B);
   for (int b = 0; b < B; b++) JH_REQUIRE(worst[b] >= 1 && worst[b] <= M, "%s: controller %d: worst = %d outside [1, M = %d]", who, b, worst[b], M);
-  if (m->kind == JH_TASK_FR3_PICK) { jh_set_error("%s: fr3_pick has no batched plan step (its phase is chosen per problem on the host) behind this entry: an fr3_pick set has no ensemble form; jh_plan_step_batch_phases_models plans B arms on B plants", who); return JH_ERR_UNSUPPORTED; }
+  if (m->kind == JH_TASK_FR3_PICK && o_phase < 0) { jh_set_error("%s: fr3_pick has no batched plan step (its phase is chosen per problem on the host) behind this entry: jh_plan_step_ensemble_batch_phases takes a phase word per controller; jh_plan_step_batch_phases_models plans B arms on B plants", who); return JH_ERR_UNSUPPORTED; }
+  if (m->kind != JH_TASK_FR3_PICK && o_phase >= 0) { jh_set_error("%s: a phase word per controller is fr3_pick's alone; jh_plan_step_ensemble_batch plans this set", who); return JH_ERR_UNSUPPORTED; }
+  JH_REQUIRE(o_phase < 0 || K <= 8, "%s: the cooperative arm kernel keeps at most 8 knots per actuator in registers (K=%d)", who, K);
   if (m->kind == JH_TASK_LEAP_CUBE && m->kernel_gen != 3) { jh_set_error("%s: only kernel generation 3 of the leap family has a batched launch (this model runs %d)", who, m->kernel_gen); return JH_ERR_UNSUPPORTED; }
   JH_REQUIRE(N > 0 && H > 0 && K >= 1, "%s: N, H, K must be positive (N=%d H=%d K=%d)", who, N, H, K);
   JH_REQUIRE(ldn >= N, "%s: ldn (%d) < N (%d)", who, ldn, N);
@@ -1055,6 +1088,7 @@ extern "C" int jh_plan_step_ensemble_batch(const jh_model_set* set, int B, int M
   const jh_engine_build* eb = engine_build(m);
   if (!closed && !(eb && eb->rollout_cost_batch)) { jh_set_error("%s: no batched kernel for this model", who); return JH_ERR_UNSUPPORTED; }
   JH_REQUIRE((long long)B * M * N <= 0x7fffffffll, "%s: B * M * N = %lld rollouts exceed one launch", who, (long long)B * M * N);
+  if (o_phase >= 0) { if (int rc = phase_words(who, "controller", B, blk_host, blk_bytes, blk_stride_bytes, o_phase)) return rc; }
   unsigned* flag = (out_host_mark && out_host_mark != (void*)out) ? (unsigned*)out_host_mark : nullptr;  // (out_host_mark == out: the stream's event)
   const float* b = (const float*)blk_dev;
   jh_upd::TailArgs a;  // (controller 0's record; the tail's own checks before anything is enqueued: mode, lambda, k)
@@ -1077,7 +1111,8 @@ extern "C" int jh_plan_step_ensemble_batch(const jh_model_set* set, int B, int M
     rc = jh_simple_rollout_cost_batch(m, set->d_images, b, b + o_tp, W, H, K, ra, s, st, z);
   } else {
     const jh_rollout_args ra = {b, b + o_nominal, noise, ldn, b + o_sigma, W, b + o_lohi, b + o_tp, 0, N, 0, H, K, member_costs, nullptr, nullptr};
-    const jh_rollout_batch rb = {set->d_images, (long long)set->stride, ints, M, 0, 0, B, blk_c, (long long)noise_stride_floats, image_c};
+    jh_rollout_batch rb = {set->d_images, (long long)set->stride, ints, M, 0, 0, B, blk_c, (long long)noise_stride_floats, image_c};
+    rb.o_phase = o_phase;
     rc = eb->rollout_cost_batch(m, ra, rb, st);
   }
   if (rc == JH_OK && timing) JH_HIP(hipEventRecord((hipEvent_t)timing[1], st));
@@ -1093,17 +1128,39 @@ extern "C" int jh_plan_step_ensemble_batch(const jh_model_set* set, int B, int M
   return rc;
 }
 
+extern "C" int jh_plan_step_ensemble_batch(const jh_model_set* set, int B, int M, void* blk_dev, const void* blk_host, size_t blk_bytes, size_t blk_stride_bytes, int o_nominal, int o_sigma, int o_tp,
+                                           int o_lohi, const float* noise, int ldn, size_t noise_stride_floats, const float* W, int N, int H, int K, float* member_costs, float* costs,
+                                           const int* worst, int mode, float lambda, int k, int tie_high, float* scratch, float* out, size_t out_stride_floats, void* out_host_mark,
+                                           void* const* timing, void* stream) {
+  return plan_step_ensemble_batch("plan_step_ensemble_batch", set, B, M, blk_dev, blk_host, blk_bytes, blk_stride_bytes, o_nominal, o_sigma, o_tp, o_lohi, -1, noise, ldn, noise_stride_floats, W, N, H, K,
+                                  member_costs, costs, worst, mode, lambda, k, tie_high, scratch, out, out_stride_floats, out_host_mark, timing, stream);
+}
+
+// jh_plan_step_ensemble_batch for fr3_pick (include/judo_amd.h): the same code path with a phase word in every controller's block.
+extern "C" int jh_plan_step_ensemble_batch_phases(const jh_model_set* set, int B, int M, void* blk_dev, const void* blk_host, size_t blk_bytes, size_t blk_stride_bytes, int o_nominal, int o_sigma,
+                                                  int o_tp, int o_lohi, int o_phase, const float* noise, int ldn, size_t noise_stride_floats, const float* W, int N, int H, int K, float* member_costs,
+                                                  float* costs, const int* worst, int mode, float lambda, int k, int tie_high, float* scratch, float* out, size_t out_stride_floats,
+                                                  void* out_host_mark, void* const* timing, void* stream) {
+  const char* who = "plan_step_ensemble_batch_phases";
+  JH_REQUIRE(set != nullptr, "%s: set is a null pointer", who);
+  if (set->m0->kind != JH_TASK_FR3_PICK) { jh_set_error("%s: a phase word per controller is fr3_pick's alone; jh_plan_step_ensemble_batch plans this set", who); return JH_ERR_UNSUPPORTED; }
+  JH_REQUIRE(o_phase >= 0, "%s: negative block offset (o_phase=%d)", who, o_phase);
+  return plan_step_ensemble_batch(who, set, B, M, blk_dev, blk_host, blk_bytes, blk_stride_bytes, o_nominal, o_sigma, o_tp, o_lohi, o_phase, noise, ldn, noise_stride_floats, W, N, H, K, member_costs, costs,
+                                  worst, mode, lambda, k, tie_high, scratch, out, out_stride_floats, out_host_mark, timing, stream);
+}
+
 // B randomised plan steps (jh_plan_step_randomized) as ONE call (include/judo_amd.h): B controllers, each with its own block, noise, costs, output record and its own table
 // from rollout block to plant.  The rollout kernels run once on the grid (workgroups of Nb rollouts, G, B): blockIdx.y is the block as above (block stride 0; noise, cost and
 // rollout-index strides Nb), blockIdx.z the controller with the strides of jh_plan_step_ensemble_batch, and the plant axis carries the B x G table, whose entry is the
 // pair's (jh_internal.h).  A set of M members is shared by all controllers (image stride 0 on that axis), a set of B * M holds controller b's plants at b * M ...  Then
 // k_update_tail_batch on (tail workgroups, B): the tail, the two-level ticket, one completion word.  The checks are the randomised call's and the batched call's, all in
 // front of the first enqueue.
-extern "C" int jh_plan_step_randomized_batch(const jh_model_set* set, int B, int M, void* blk_dev, const void* blk_host, size_t blk_bytes, size_t blk_stride_bytes, int o_nominal, int o_sigma,
-                                             int o_tp, int o_lohi, const float* noise, int ldn, size_t noise_stride_floats, const float* W, int N, int H, int K,
-                                             const unsigned char* plant_of_block, int G, float* costs, int mode, float lambda, int k, int tie_high, float* scratch, float* out,
-                                             size_t out_stride_floats, void* out_host_mark, void* const* timing, void* stream) {
-  const char* who = "plan_step_randomized_batch";
+// `o_phase`: -1 for jh_plan_step_randomized_batch, which has none and refuses fr3_pick; the float offset of every controller's phase word in its block for
+// jh_plan_step_randomized_batch_phases, which plans fr3_pick alone (checked by the entry), as in plan_step_ensemble_batch.
+static int plan_step_randomized_batch(const char* who, const jh_model_set* set, int B, int M, void* blk_dev, const void* blk_host, size_t blk_bytes, size_t blk_stride_bytes, int o_nominal, int o_sigma,
+                                      int o_tp, int o_lohi, int o_phase, const float* noise, int ldn, size_t noise_stride_floats, const float* W, int N, int H, int K,
+                                      const unsigned char* plant_of_block, int G, float* costs, int mode, float lambda, int k, int tie_high, float* scratch, float* out,
+                                      size_t out_stride_floats, void* out_host_mark, void* const* timing, void* stream) {
 #define JH_RND_PTR(p) JH_REQUIRE((p) != nullptr, "%s: " #p " is a null pointer", who)
   JH_RND_PTR(set); JH_RND_PTR(blk_dev); JH_RND_PTR(blk_host); JH_RND_PTR(noise); JH_RND_PTR(W); JH_RND_PTR(plant_of_block); JH_RND_PTR(costs); JH_RND_PTR(scratch); JH_RND_PTR(out);
 #undef JH_RND_PTR
@@ -1114,7 +1171,9 @@ extern "C" int jh_plan_step_randomized_batch(const jh_model_set* set, int B, int
   JH_REQUIRE(B * G <= JH_MAX_FLEET_PLANT_BLOCKS, "%s: B * G = %d * %d = %d exceeds JH_MAX_FLEET_PLANT_BLOCKS = %d (the bytes of the table in the kernel arguments)", who, B, G, B * G,
              JH_MAX_FLEET_PLANT_BLOCKS);
   JH_REQUIRE(set->B == M || set->B == B * M, "%s: a set of %d members is neither the M = %d plants every controller shares nor the B * M = %d plants of B = %d controllers", who, set->B, M, B * M, B);
-  if (m->kind == JH_TASK_FR3_PICK) { jh_set_error("%s: fr3_pick has no batched plan step (its phase is chosen per problem on the host) behind this entry: jh_plan_step_randomized_phase plans one arm over the set's plants and jh_plan_step_batch_phases_models B arms on B plants", who); return JH_ERR_UNSUPPORTED; }
+  if (m->kind == JH_TASK_FR3_PICK && o_phase < 0) { jh_set_error("%s: fr3_pick has no batched plan step (its phase is chosen per problem on the host) behind this entry: jh_plan_step_randomized_batch_phases takes a phase word per controller; jh_plan_step_randomized_phase plans one arm over the set's plants and jh_plan_step_batch_phases_models B arms on B plants", who); return JH_ERR_UNSUPPORTED; }
+  if (m->kind != JH_TASK_FR3_PICK && o_phase >= 0) { jh_set_error("%s: a phase word per controller is fr3_pick's alone; jh_plan_step_randomized_batch plans this set", who); return JH_ERR_UNSUPPORTED; }
+  JH_REQUIRE(o_phase < 0 || K <= 8, "%s: the cooperative arm kernel keeps at most 8 knots per actuator in registers (K=%d)", who, K);
   if (m->kind == JH_TASK_LEAP_CUBE && m->kernel_gen != 3) { jh_set_error("%s: only kernel generation 3 of the leap family has a batched launch (this model runs %d)", who, m->kernel_gen); return JH_ERR_UNSUPPORTED; }
   JH_REQUIRE(N > 0 && H > 0 && K >= 1, "%s: N, H, K must be positive (N=%d H=%d K=%d)", who, N, H, K);
   JH_REQUIRE(N % G == 0, "%s: N = %d is no multiple of G = %d (the blocks are N / G rollouts each)", who, N, G);
@@ -1137,6 +1196,7 @@ extern "C" int jh_plan_step_randomized_batch(const jh_model_set* set, int B, int
   const jh_engine_build* eb = engine_build(m);
   if (!closed && !(eb && eb->rollout_cost_batch)) { jh_set_error("%s: no batched kernel for this model", who); return JH_ERR_UNSUPPORTED; }
   JH_REQUIRE((long long)B * N <= 0x7fffffffll, "%s: B * N = %lld rollouts exceed one launch", who, (long long)B * N);
+  if (o_phase >= 0) { if (int rc = phase_words(who, "controller", B, blk_host, blk_bytes, blk_stride_bytes, o_phase)) return rc; }
   unsigned* flag = (out_host_mark && out_host_mark != (void*)out) ? (unsigned*)out_host_mark : nullptr;  // (out_host_mark == out: the stream's event)
   const float* b = (const float*)blk_dev;
   jh_upd::TailArgs a;  // (controller 0's record; the tail's own checks before anything is enqueued: mode, lambda, k)
@@ -1165,6 +1225,7 @@ extern "C" int jh_plan_step_randomized_batch(const jh_model_set* set, int B, int
     const jh_rollout_args ra = {b, b + o_nominal, noise, ldn, b + o_sigma, W, b + o_lohi, b + o_tp, 0, Nb, 0, H, K, costs, nullptr, nullptr};
     jh_rollout_batch rb = {set->d_images, (long long)set->stride, ints, G, 0, (long long)Nb, B, blk_c, (long long)noise_stride_floats, image_c};
     rb.plants = plants;
+    rb.o_phase = o_phase;
     rc = eb->rollout_cost_batch(m, ra, rb, st);
   }
   if (rc == JH_OK && timing) JH_HIP(hipEventRecord((hipEvent_t)timing[1], st));
@@ -1175,6 +1236,27 @@ extern "C" int jh_plan_step_randomized_batch(const jh_model_set* set, int B, int
   if (rc == JH_OK && timing) JH_HIP(hipEventRecord((hipEvent_t)timing[2], st));
   if (rc == JH_OK) rc = download_begin(out, out, 0, stream, flag, expect);
   return rc;
+}
+
+extern "C" int jh_plan_step_randomized_batch(const jh_model_set* set, int B, int M, void* blk_dev, const void* blk_host, size_t blk_bytes, size_t blk_stride_bytes, int o_nominal, int o_sigma,
+                                             int o_tp, int o_lohi, const float* noise, int ldn, size_t noise_stride_floats, const float* W, int N, int H, int K,
+                                             const unsigned char* plant_of_block, int G, float* costs, int mode, float lambda, int k, int tie_high, float* scratch, float* out,
+                                             size_t out_stride_floats, void* out_host_mark, void* const* timing, void* stream) {
+  return plan_step_randomized_batch("plan_step_randomized_batch", set, B, M, blk_dev, blk_host, blk_bytes, blk_stride_bytes, o_nominal, o_sigma, o_tp, o_lohi, -1, noise, ldn, noise_stride_floats, W, N, H, K,
+                                    plant_of_block, G, costs, mode, lambda, k, tie_high, scratch, out, out_stride_floats, out_host_mark, timing, stream);
+}
+
+// jh_plan_step_randomized_batch for fr3_pick (include/judo_amd.h): the same code path with a phase word in every controller's block.
+extern "C" int jh_plan_step_randomized_batch_phases(const jh_model_set* set, int B, int M, void* blk_dev, const void* blk_host, size_t blk_bytes, size_t blk_stride_bytes, int o_nominal, int o_sigma,
+                                                    int o_tp, int o_lohi, int o_phase, const float* noise, int ldn, size_t noise_stride_floats, const float* W, int N, int H, int K,
+                                                    const unsigned char* plant_of_block, int G, float* costs, int mode, float lambda, int k, int tie_high, float* scratch, float* out,
+                                                    size_t out_stride_floats, void* out_host_mark, void* const* timing, void* stream) {
+  const char* who = "plan_step_randomized_batch_phases";
+  JH_REQUIRE(set != nullptr, "%s: set is a null pointer", who);
+  if (set->m0->kind != JH_TASK_FR3_PICK) { jh_set_error("%s: a phase word per controller is fr3_pick's alone; jh_plan_step_randomized_batch plans this set", who); return JH_ERR_UNSUPPORTED; }
+  JH_REQUIRE(o_phase >= 0, "%s: negative block offset (o_phase=%d)", who, o_phase);
+  return plan_step_randomized_batch(who, set, B, M, blk_dev, blk_host, blk_bytes, blk_stride_bytes, o_nominal, o_sigma, o_tp, o_lohi, o_phase, noise, ldn, noise_stride_floats, W, N, H, K, plant_of_block, G,
+                                    costs, mode, lambda, k, tie_high, scratch, out, out_stride_floats, out_host_mark, timing, stream);
 }
 
 // The update alone for B problems whose costs are given (the materialise path of a fleet: the Spot policy rollout, judo_amd/fleet.py): jh_plan_step_batch's last stage --

@@ -432,7 +432,13 @@ __device__ __forceinline__ void geom_pose3(const RS6& S, const float* gf, int bo
 // rollouts: a stride on the global rollout index, so that only global rollout 0 is the noise-free nominal, and a by-value table from the problem to its image in place
 // of the problem's own index -- 0 and the identity for jh_plan_step_batch_phases.  The counters are the launch's.  The other instantiations take an empty record in the
 // table's place, ignore the trailing arguments and compile to the code they had without them.
+// The controller axis (jh_plan_step_ensemble_phase ... jh_plan_step_randomized_batch_phases), as k_leap_v5 has it: blockIdx.z is the controller, whose problems are those of
+// blockIdx.y.  Controller c's blocks, noise and images lie c times the record's three strides behind controller 0's; the (controller, problem) pair c * gridDim.y + b owns the
+// costs, trace and overflow rows and names the plant table's entry.  The phase word is read behind both offsets, so with `batch_blk` 0 it is the controller's own.  All
+// strides 0 and gridDim.z == 1: every launch without that axis.
 struct NoPlantAxis {};
+// The batched instantiation's last argument, by value: the controller axis' strides (floats) and the plant axis (jh_internal.h).
+struct BatchAxes { long long blk_c = 0, noise_c = 0, image_c = 0; jh_plant_axis plants; };
 template <bool MATERIALIZE, bool BATCH = false>
 __global__ __launch_bounds__(WAVE) __attribute__((amdgpu_waves_per_eu(WPE, WPE))) void k_fr3_v6(const float* __restrict__ gF, const int* __restrict__ gI, const float* __restrict__ x0, int x0_batched,
                                                     const float* __restrict__ nominal, const float* __restrict__ noise, int ldn,
@@ -441,16 +447,18 @@ __global__ __launch_bounds__(WAVE) __attribute__((amdgpu_waves_per_eu(WPE, WPE))
                                                     float* __restrict__ costs, float* __restrict__ knots_out, const float* __restrict__ controls,
                                                     float* __restrict__ states, float* __restrict__ sensors, int* __restrict__ stats, int dshift, float* __restrict__ trace, float* __restrict__ ovf_all,
                                                     long long batch_blk, long long batch_noise, int o_phase, long long batch_image,
-                                                    std::conditional_t<BATCH, jh_plant_axis, NoPlantAxis> plants) {
+                                                    std::conditional_t<BATCH, BatchAxes, NoPlantAxis> axes) {
   static_assert(!BATCH || !MATERIALIZE, "batched launches are fused launches");
   if constexpr (BATCH) {
-    const long long pb = blockIdx.y, ob = pb * batch_blk;
+    // `pr`: the (controller, problem) pair, which owns the costs, trace and overflow rows; pb wherever gridDim.z == 1
+    const long long pb = blockIdx.y, pc = blockIdx.z, pr = pc * gridDim.y + pb;
+    const long long ob = pb * batch_blk + pc * axes.blk_c;
     x0 += ob; nominal += ob; sigma += ob; lohi += ob; tp += ob;
-    // the plant axis: the problem's first global rollout index and the image its table names -- 0 and image pb for a launch without one
-    n_offset += (int)pb * plants.n_stride;
-    noise += pb * batch_noise; costs += pb * N; gF += jh_plant_of(plants, (int)pb, (int)pb) * batch_image;
-    if (trace) trace += pb * N * H * 6;
-    if (ovf_all) ovf_all += pb * N * (NOVF * RAW_F);  // (the overflow rows are indexed by rollout: a problem's N rows behind the one before)
+    // the plant axis: the problem's first global rollout index and the image the pair's table entry names -- 0 and image pb for a launch without one
+    n_offset += (int)pb * axes.plants.n_stride;
+    noise += pb * batch_noise + pc * axes.noise_c; costs += pr * N; gF += jh_plant_of(axes.plants, (int)pr, (int)pb) * batch_image + pc * axes.image_c;
+    if (trace) trace += pr * N * H * 6;
+    if (ovf_all) ovf_all += pr * N * (NOVF * RAW_F);  // (the overflow rows are indexed by rollout: a pair's N rows behind the one before)
     if (o_phase >= 0) phase = (int)x0[o_phase];
   }
   __shared__ RS6 sRS[RPW];
@@ -1364,8 +1372,8 @@ int JH_V6_NAME(jh_engine6_materialize)(const jh_model* m, const float* x0, int x
 // whose x0 is the first word of its packed block; `blk_stride` / `noise_stride` floats lead to the next problem's, and `o_phase` is the float offset of the problem's phase
 // word in its block -- or negative, and `s.phase` is every problem's (jh_plan_step_randomized_phase: the problems are blocks of one controller's rollouts).  `s.images` /
 // `s.image_stride`: problem 0's float section and the floats to the next problem's; `s.plants`: the plant axis, by value.  The int section is the model's own: fr3_pick has
-// no pair tables, so a set's members share it as it is.  The latency shift is chosen from B * N, the rollouts of the launch (the bits do not depend on it).  What the
-// record can say and this kernel does not implement is refused.
+// no pair tables, so a set's members share it as it is.  `s.C` > 1: the controller axis, grid (groups, B, C) with the record's three `*_stride_c`.  The latency shift is
+// chosen from C * B * N, the rollouts of the launch (the bits do not depend on it).  What the record can say and this kernel does not implement is refused.
 static int rollout_cost_batch(const jh_model* m, const jh_rollout_args& a, const jh_rollout_batch& s, hipStream_t st) {
   if (!JH_V6_NAME(jh_model_is_fr3)(m)) {
     if (JH_V6_SELF) jh_set_error("plan_step_batch_phases: the self-collision build of the cooperative arm kernel is instantiated for fr3_pick with its arm pairs only");
@@ -1373,16 +1381,18 @@ static int rollout_cost_batch(const jh_model* m, const jh_rollout_args& a, const
     return JH_ERR_UNSUPPORTED;
   }
   JH_REQUIRE(a.K <= 8, "plan_step_batch_phases: the cooperative arm kernel keeps at most 8 knots per actuator in registers (K=%d)", a.K);
-  JH_REQUIRE(s.C == 1, "plan_step_batch_phases: the fr3 launch has no controller axis (C=%d)", s.C);
   JH_REQUIRE(s.images != nullptr && s.image_stride >= 0, "plan_step_batch_phases: the fr3 kernel's batched launch needs the problems' images (image_stride=%lld)", s.image_stride);
   JH_REQUIRE(a.knots_out == nullptr && a.n_offset == 0, "plan_step_batch_phases: the fr3 kernel's batched launch takes neither knots_out nor a rollout offset");
   JH_REQUIRE(s.o_phase >= 0 || (s.phase >= 0 && s.phase <= 3), "plan_step_batch_phases: the fr3 kernel's batched launch needs a phase word per problem or a phase 0..3 in its record (phase=%d)", s.phase);
-  const long long rollouts = (long long)s.B * a.N;
-  JH_REQUIRE(s.B >= 1 && s.B <= 65535 && rollouts <= 0x7fffffffll, "plan_step_batch_phases: B * N = %lld rollouts exceed one launch", rollouts);
+  const long long rollouts = (long long)s.C * s.B * a.N;
+  JH_REQUIRE(s.B >= 1 && s.B <= 65535 && s.C >= 1 && s.C <= 65535 && rollouts <= 0x7fffffffll, "plan_step_batch_phases: C * B * N = %lld rollouts exceed one launch (B=%d, C=%d)", rollouts, s.B, s.C);
+  JH_REQUIRE(!s.plants.mapped || (long long)s.C * s.B <= JH_MAX_FLEET_PLANT_BLOCKS, "plan_step_batch_phases: C * B = %d * %d pairs exceed the %d entries of the plant table", s.C, s.B, JH_MAX_FLEET_PLANT_BLOCKS);
   const int dshift = jh_latency_shift((int)rollouts, RPW), per_wave = RPW >> dshift, grid = (a.N + per_wave - 1) / per_wave;
-  float* ovf = jh_launch_scratch(m, (size_t)rollouts * NOVF * RAW_F * sizeof(float), st);  // (every problem's rows; nullptr: the LDS capacity alone, drops and the fallback counted)
-  hipLaunchKernelGGL((k_fr3_v6<false, true>), dim3(grid, s.B), dim3(WAVE), 0, st, s.images, m->d_i, a.x0, 0, a.nominal, a.noise, a.ldn, a.sigma, a.W, a.lohi, a.tp, s.o_phase < 0 ? s.phase : 0, a.N, 0,
-                     a.H, a.K, a.costs, nullptr, nullptr, nullptr, nullptr, m->d_stats, dshift, a.trace, ovf, s.blk_stride, s.noise_stride, s.o_phase, s.image_stride, s.plants);
+  float* ovf = jh_launch_scratch(m, (size_t)rollouts * NOVF * RAW_F * sizeof(float), st);  // (every pair's rows; nullptr: the LDS capacity alone, drops and the fallback counted)
+  BatchAxes axes;
+  axes.blk_c = s.blk_stride_c; axes.noise_c = s.noise_stride_c; axes.image_c = s.image_stride_c; axes.plants = s.plants;
+  hipLaunchKernelGGL((k_fr3_v6<false, true>), dim3(grid, s.B, s.C), dim3(WAVE), 0, st, s.images, m->d_i, a.x0, 0, a.nominal, a.noise, a.ldn, a.sigma, a.W, a.lohi, a.tp, s.o_phase < 0 ? s.phase : 0, a.N, 0,
+                     a.H, a.K, a.costs, nullptr, nullptr, nullptr, nullptr, m->d_stats, dshift, a.trace, ovf, s.blk_stride, s.noise_stride, s.o_phase, s.image_stride, axes);
   return jh_launch_done(ovf, st);
 }
 

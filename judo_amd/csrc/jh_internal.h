@@ -145,7 +145,7 @@ inline void jh_plant_set(jh_plant_axis& p, int e, int plant) { p.mapped = 1u; p.
 // the one argument of the single launch that is a problem's own.  -1: the launch has no phase word (the leap kernel ignores the field), and the fr3 kernel takes
 // `phase`, 0..3, for every problem: the problems are blocks of one controller's rollouts (jh_plan_step_randomized_phase), and one controller has one phase.  `phase` is
 // read only when o_phase < 0.  The fr3 launcher implements the images and the plant axis as the leap launcher does, reads the model's own int section (fr3_pick has no
-// pair tables; `ints` is not used) and refuses C > 1: the fr3 launch has no controller axis.
+// pair tables; `ints` is not used), and the controller axis as well: C up to 65535, C * B * N rollouts in one launch.
 struct jh_rollout_batch {
   const float* images; long long image_stride; const int* ints;
   int B; long long blk_stride, noise_stride;

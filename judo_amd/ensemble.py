@@ -66,6 +66,17 @@ def check_descriptions(descriptions: Sequence[dict]) -> list[bytes]:
     return blobs
 
 
+def check_task(task: Task, fr3: bool = False) -> None:
+    """The tasks without an ensemble plan step, refused before any model is made; raises ValueError.  `fr3`: the caller's plan step carries the arm's phase
+    (judo_amd.fr3_ensemble), so fr3_pick passes."""
+    if task.uses_locomotion_policy:
+        raise ValueError("the Spot policy tasks have no ensemble plan step: their iteration is the materialise path (spline, policy rollout, reward, update), not one library call")
+    if task.desc.get("family", task.desc["task"]) == "fr3_pick" and not fr3:
+        raise ValueError("fr3_pick has no ensemble plan step: its phase is chosen per problem on the host and the ensemble entries carry none.  "
+                         "judo_amd.fr3_ensemble.make_fr3_ensemble_controller makes the controller whose plan step carries the phase; one arm against perturbed "
+                         "plants at the cost of a plain plan step is judo_amd.fr3_randomized.make_fr3_randomized_controller")
+
+
 class EnsembleController(Controller):
     """A `Controller` whose plan step rolls every candidate out on M plants and updates on the aggregated costs.  Everything else -- `update_states`, `action(t)`,
     `traces`, `max_opt_iters`, the three optimizers, the `none` / `min_max` normalisers, a live change of `num_rollouts` -- is the controller's own.
@@ -73,13 +84,19 @@ class EnsembleController(Controller):
     `rewards` are the negated aggregated costs; `member_costs` / `member_rewards` the (M, N) costs behind them; `worst` may be set between plan steps, and
     `set_member(b, description)` replaces one plant."""
 
+    _fr3_ensemble = False  # (FR3EnsembleController: the plan step carries the arm's phase; only an FR3EnsembleFleet takes such a member)
+    _entry = "jh_plan_step_ensemble"  # the library call of the plan step
+
+    def _check_task(self, task: Task) -> None:
+        check_task(task)
+
+    def _entry_args(self, W, N: int, H: int, K: int) -> tuple:
+        """The entry's arguments between the noise pitch and the member costs: W, N, H, K."""
+        return (_lib.ptr(W), N, H, K)
+
     def __init__(self, controller_config: ControllerConfig, task: Task, optimizer, descriptions: Sequence[dict], worst: int | None = None,
                  device: torch.device | None = None) -> None:
-        if task.uses_locomotion_policy:
-            raise ValueError("the Spot policy tasks have no ensemble plan step: their iteration is the materialise path (spline, policy rollout, reward, update), not one library call")
-        if task.desc.get("family", task.desc["task"]) == "fr3_pick":
-            raise ValueError("fr3_pick has no ensemble plan step: its phase is chosen per problem on the host and the ensemble entries carry none.  One arm against perturbed "
-                             "plants at the cost of a plain plan step is judo_amd.fr3_randomized.make_fr3_randomized_controller")
+        self._check_task(task)
         check_descriptions(descriptions)
         self._descriptions = list(descriptions)
         task.desc = self._descriptions[0]
@@ -181,10 +198,10 @@ class EnsembleController(Controller):
         off = b.offsets
         in_place = b.blk_stale = self.model.closed_form
         mark = b.done_ptr if self.model.closed_form else b.out_host_ptr
-        st = lib.jh_plan_step_ensemble(self.model_set.handle, b.host_ptr if in_place else b.blk.data_ptr(), b.host_ptr, b.nblk_bytes, int(off[1]), int(off[2]), int(off[3]), int(off[4]),
-                                       noise_p, ldn, _lib.ptr(W), N, H, K, self._member_costs.data_ptr(), _lib.ptr(b.costs), self._worst, mode, lam, k_el, tie, _lib.ptr(b.fused_scratch),
-                                       b.out_host_ptr, mark, timing, stream)
-        _lib.check(st, "jh_plan_step_ensemble")
+        st = getattr(lib, self._entry)(self.model_set.handle, b.host_ptr if in_place else b.blk.data_ptr(), b.host_ptr, b.nblk_bytes, int(off[1]), int(off[2]), int(off[3]), int(off[4]),
+                                       noise_p, ldn, *self._entry_args(W, N, H, K), self._member_costs.data_ptr(), _lib.ptr(b.costs), self._worst, mode, lam, k_el, tie,
+                                       _lib.ptr(b.fused_scratch), b.out_host_ptr, mark, timing, stream)
+        _lib.check(st, self._entry)
         state["costs"] = b.costs
         if evs:
             self.kernel_events.append((evs[0], evs[1]))
@@ -214,4 +231,4 @@ def make_ensemble_controller(task: str | Task, optimizer: str, descriptions: Seq
     return EnsembleController(ctrl_cfg, task, opt_cls(opt_cfg, task.nu), descriptions, worst=worst, device=device)
 
 
-__all__ = ["EnsembleController", "MAX_ENSEMBLE", "aggregate_costs_host", "check_descriptions", "make_ensemble_controller"]
+__all__ = ["EnsembleController", "MAX_ENSEMBLE", "aggregate_costs_host", "check_descriptions", "check_task", "make_ensemble_controller"]

@@ -104,7 +104,7 @@ class EnsembleFleet(ControllerFleet):
         super().__init__(controllers)
 
     def _check_member(self, i: int, c, first) -> None:
-        refuse_fr3_randomized(i, c)
+        refuse_fr3_randomized(i, c, self)
         if isinstance(c, RandomizedController):
             raise ValueError(f"fleet member {i} is a RandomizedController: it rolls each candidate out on one plant of its set, not on all of them, and its plan step "
                              "(jh_plan_step_randomized) is another launch; randomised controllers share one in a RandomizedFleet "

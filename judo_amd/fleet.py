@@ -39,12 +39,18 @@ from judo_amd.optimizers import Optimizer, _NoiseStream
 from judo_amd.tasks import get_registered_tasks
 
 
-def refuse_fr3_randomized(i: int, c: Controller) -> None:
-    """No fleet takes an `FR3RandomizedController` (judo_amd.fr3_randomized): raises ValueError naming why.  Every fleet's `_check_member` begins with it."""
-    if getattr(c, "_fr3_randomized", False):
+def refuse_fr3_randomized(i: int, c: Controller, fleet: "ControllerFleet | None" = None) -> None:
+    """Only an `FR3RandomizedFleet` takes an `FR3RandomizedController` (judo_amd.fr3_randomized) and only an `FR3EnsembleFleet` an `FR3EnsembleController`
+    (judo_amd.fr3_ensemble): raises ValueError naming why and the fleet that serves the member.  Every fleet's `_check_member` begins with it."""
+    if getattr(c, "_fr3_randomized", False) and not getattr(fleet, "_fr3_randomized_members", False):
         raise ValueError(f"fleet member {i} is an FR3RandomizedController: its plan step (jh_plan_step_randomized_phase) puts the rollout blocks of ONE arm on the launch's "
-                         "problem axis, and the fr3 launch has no controller axis behind it, so it shares a launch with no other controller.  Fleets of fr3_pick controllers "
-                         "that believe one plant each are an FR3Fleet or an FR3PlantFleet (judo_amd.fr3_fleet.make_fr3_fleet)")
+                         "problem axis, and this fleet's entry has no controller axis behind an arm's rollout blocks.  Randomised fr3_pick controllers share a launch in an "
+                         "FR3RandomizedFleet (judo_amd.fr3_randomized_fleet.make_fr3_randomized_fleet); fleets of fr3_pick controllers that believe one plant each are an "
+                         "FR3Fleet or an FR3PlantFleet (judo_amd.fr3_fleet.make_fr3_fleet)")
+    if getattr(c, "_fr3_ensemble", False) and not getattr(fleet, "_fr3_ensemble_members", False):
+        raise ValueError(f"fleet member {i} is an FR3EnsembleController: its plan step (jh_plan_step_ensemble_phase) puts the M plants of ONE arm on the launch's problem "
+                         "axis, and this fleet's entry has no controller axis behind an arm's plants.  fr3_pick ensemble controllers share a launch in an FR3EnsembleFleet "
+                         "(judo_amd.fr3_ensemble.make_fr3_ensemble_fleet)")
 
 
 class _MemberBuffers:
@@ -184,7 +190,7 @@ class ControllerFleet:
                 "default_policy_command": np.asarray(t.default_policy_command).tolist()}
 
     def _check_member(self, i: int, c: Controller, first: Controller) -> None:
-        refuse_fr3_randomized(i, c)
+        refuse_fr3_randomized(i, c, self)
         if isinstance(c, RandomizedController) and not self._randomized_members:
             # (its iteration shape reads "plan_step" too, and the batched plan step would run every block on `c.model`, plant 0, and drop the assignment without a word)
             raise ValueError(f"fleet member {i} is a RandomizedController: its plan step spreads the rollout blocks over the plants of its own set "

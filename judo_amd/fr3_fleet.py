@@ -40,7 +40,7 @@ class FR3Fleet(ControllerFleet):
     _one_image = True  # every member plans on member 0's image (FR3PlantFleet: an image per member)
 
     def _check_member(self, i: int, c: Controller, first: Controller) -> None:
-        refuse_fr3_randomized(i, c)
+        refuse_fr3_randomized(i, c, self)
         if c.model is None or c.model.desc.get("family", c.model.task) != "fr3_pick" or not isinstance(c.task, FR3Pick):
             raise ValueError(f"fleet member {i} is no fr3_pick controller ({type(c.task).__name__}): an FR3Fleet plans fr3_pick alone; every other model family shares a "
                              "launch in a ControllerFleet (judo_amd.fleet.make_controller_fleet)")

@@ -7,7 +7,7 @@ models, every block in the controller's phase, and the update on the N costs as 
 an unknown cube mass, pad friction or gripper gain decides whether a lift succeeds.
 
 Everything but the call is `RandomizedController`'s: `assignment`, `set_weights`, `plant_of_rollout`, `plant_rewards()`, `set_member`; member 0 is the nominal plant,
-on which the traces are re-rolled.  The fr3 launch has no controller axis, so no fleet takes such a controller as a member."""
+on which the traces are re-rolled.  B such controllers share a launch in an `FR3RandomizedFleet` (judo_amd.fr3_randomized_fleet), and in no other fleet."""
 
 from __future__ import annotations
 

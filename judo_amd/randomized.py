@@ -74,7 +74,8 @@ def check_task(task: Task, fr3: bool = False) -> None:
         raise ValueError("the Spot policy tasks have no randomised plan step: their iteration is the materialise path (spline, policy rollout, reward, update), not one library call")
     if task.desc.get("family", task.desc["task"]) == "fr3_pick" and not fr3:
         raise ValueError("fr3_pick has no randomised plan step behind this class: its phase is chosen per problem on the host, and jh_plan_step_randomized carries none.  "
-                         "judo_amd.fr3_randomized.make_fr3_randomized_controller makes the controller whose plan step carries the phase")
+                         "judo_amd.fr3_randomized.make_fr3_randomized_controller makes the controller whose plan step carries the phase, "
+                         "judo_amd.fr3_randomized_fleet.make_fr3_randomized_fleet a fleet of them")
 
 
 class RandomizedController(Controller):
@@ -84,7 +85,7 @@ class RandomizedController(Controller):
     `assignment` (G plant indices, default g % M) may be set between plan steps; `plant_of_rollout` and `plant_rewards()` say which plant a reward belongs to, and
     `set_member(b, description)` replaces one plant."""
 
-    _fr3_randomized = False  # (FR3RandomizedController: the plan step carries the arm's phase; no fleet takes such a member)
+    _fr3_randomized = False  # (FR3RandomizedController: the plan step carries the arm's phase; only an FR3RandomizedFleet takes such a member)
     _entry = "jh_plan_step_randomized"  # the library call of the plan step
 
     def _check_task(self, task: Task) -> None:

@@ -93,7 +93,7 @@ class RandomizedFleet(ControllerFleet):
         super().__init__(controllers)
 
     def _check_member(self, i: int, c, first) -> None:
-        refuse_fr3_randomized(i, c)
+        refuse_fr3_randomized(i, c, self)
         if not isinstance(c, RandomizedController):
             raise ValueError(f"fleet member {i} is a {type(c).__name__}, not a RandomizedController: controllers that believe one plant share a launch in a ControllerFleet, "
                              "ensemble controllers in an EnsembleFleet")
