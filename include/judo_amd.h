@@ -612,6 +612,37 @@ int jh_policy_rollout(const jh_policy* p, jh_tree* t, const float* x0, int x0_ba
 int jh_policy_rollout_batch(const jh_policy* p, jh_tree* t, int B, const float* x0, size_t x0_stride_floats, const float* commands, float* policy_out, float* warmstart,
                             int reset_warmstart, int n, int T, int substeps, double cutoff_seconds, float* states, float* sensors, float* scratch, int* steps_done, void* stream);
 
+/* ---- a set of P plants for the tree kernel: perturbed copies of one Spot model (masses, inertias, friction, gains: judo_amd/models.py scaled_description), each rollout
+ * block of a launch on a plant of the set.  jh_tree_set_create copies the float sections of P jh_trees, 1 <= P <= JH_MAX_ENSEMBLE, into one device allocation, a stride
+ * apart that is the float count rounded up to a multiple of 4, and keeps ONE copy of the int section and counters of its own; the trees stay the caller's and may be
+ * destroyed.  The members must have member 0's float and int counts, its object kind (none, box, cylinder), an int section identical to member 0's (compared on the
+ * host) and its self-collision switch, which becomes the set's; every refusal is JH_ERR_INVALID with jh_last_error naming the member and the section.
+ * jh_tree_set_update replaces plant p under the same checks (synchronous: between launches).  jh_tree_set_info: [P, float stride, nq, nv].  jh_tree_set_stats: the
+ * four counters of jh_tree_stats, summed over the set's launches. */
+typedef struct jh_tree_set jh_tree_set;
+int jh_tree_set_create(const jh_tree* const* trees, int P, jh_tree_set** out);
+int jh_tree_set_update(jh_tree_set* set, int p, const jh_tree* tree);
+int jh_tree_set_info(const jh_tree_set* set, int* out4 /* P, float stride, nq, nv */);
+int jh_tree_set_stats(jh_tree_set* set, int* out4, int reset);
+void jh_tree_set_destroy(jh_tree_set* set);
+/* jh_tree_substeps on G * n block-major rows, block g (rows g * n .. g * n + n - 1) on plant plant_of_block[g] of the set; plant_of_block is a HOST array of G entries in
+ * [0, P) that travels in the kernel arguments, G <= JH_MAX_FLEET_PLANT_BLOCKS.  Blocks never share a wave: an odd n leaves one idle row in the last wave of its block.
+ * Block g's rows are bit for bit those of jh_tree_substeps with N = n on that plant's own jh_tree.  JH_ERR_INVALID before anything is enqueued, jh_last_error naming the
+ * argument: a null pointer, G, n or substeps < 1, G above the limit, a table entry outside [0, P). */
+int jh_tree_substeps_plants(const jh_tree_set* set, const int* plant_of_block, int G, int n, const float* state_in, const float* ctrl, float* warmstart, int substeps,
+                            float* state_out, float* sensors_out, void* stream);
+/* jh_policy_rollout_batch on N = B * G * n rollouts, problem-major then block-major: rollout r starts from problem r / (G * n)'s state and runs on plant
+ * plant_of_block[r / n] of the set -- a HOST table of B * G entries in [0, P), problem-major, in the kernel arguments.  The policy step does not depend on the plant and
+ * runs on all N rows at once.  commands, policy_out, warmstart, states, sensors, scratch (jh_policy_rollout_scratch_floats(N)), reset_warmstart, cutoff_seconds and
+ * *steps_done as documented for jh_policy_rollout_batch with that N; the deadline is one per call.
+ * Contract: block (b, g)'s states, sensors, policy outputs and warm start are bit for bit those of jh_policy_rollout with N = n on plant plant_of_block[b * G + g]'s own
+ * jh_tree, from problem b's state -- whatever the latency mode and whichever blocks stand beside it.
+ * JH_ERR_INVALID before anything is enqueued, jh_last_error naming the argument: a null pointer; B, G, n, T or substeps < 1; B * G > JH_MAX_FLEET_PLANT_BLOCKS; a table
+ * entry outside [0, P); x0_stride_floats smaller than a state. */
+int jh_policy_rollout_plants(const jh_policy* p, jh_tree_set* set, int B, int G, const int* plant_of_block, const float* x0, size_t x0_stride_floats, const float* commands,
+                             float* policy_out, float* warmstart, int reset_warmstart, int n, int T, int substeps, double cutoff_seconds, float* states, float* sensors,
+                             float* scratch, int* steps_done, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -69,6 +69,14 @@ _SIGNATURES = {
     "jh_policy_rollout": (C.c_int, [C.c_void_p, C.c_void_p, f32p, C.c_int, f32p, f32p, f32p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_double, f32p, f32p, f32p, C.POINTER(C.c_int), C.c_void_p]),
     "jh_policy_rollout_batch": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, f32p, C.c_size_t, f32p, f32p, f32p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_double, f32p, f32p, f32p, C.POINTER(C.c_int),
                                           C.c_void_p]),
+    "jh_tree_set_create": (C.c_int, [C.POINTER(C.c_void_p), C.c_int, C.POINTER(C.c_void_p)]),
+    "jh_tree_set_update": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p]),
+    "jh_tree_set_info": (C.c_int, [C.c_void_p, C.POINTER(C.c_int)]),
+    "jh_tree_set_stats": (C.c_int, [C.c_void_p, C.POINTER(C.c_int), C.c_int]),
+    "jh_tree_set_destroy": (None, [C.c_void_p]),
+    "jh_tree_substeps_plants": (C.c_int, [C.c_void_p, C.POINTER(C.c_int), C.c_int, C.c_int, f32p, f32p, f32p, C.c_int, f32p, f32p, C.c_void_p]),
+    "jh_policy_rollout_plants": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.POINTER(C.c_int), f32p, C.c_size_t, f32p, f32p, f32p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_double,
+                                           f32p, f32p, f32p, C.POINTER(C.c_int), C.c_void_p]),
     "jh_update_scratch_floats": (C.c_size_t, [C.c_int, C.c_int, C.c_int]),
     "jh_mppi_partial": (C.c_int, [f32p, f32p, f32p, f32p, C.c_int, f32p, f32p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_float, f32p, f32p, C.c_void_p]),
     "jh_mppi_merge": (C.c_int, [f32p, C.c_int, C.c_int, C.c_int, C.c_float, f32p, C.c_void_p]),

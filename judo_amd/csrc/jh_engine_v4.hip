@@ -37,6 +37,8 @@
 #include <cstddef>
 #include "jh_coop.h"
 
+#include <cstring>
+#include <type_traits>
 #include <vector>
 
 using namespace jh_eng;
@@ -478,10 +480,23 @@ __device__ __forceinline__ float dot_row(const float* Mrow, const float* v) {
 }
 
 
-template <bool SELF, bool OBJ = false, bool CYL = false>
+// The plant axis of a launch on a jh_tree_set (PLANTS): the grid is (waves per block, blocks), block blockIdx.y holds N rollouts -- global rows blockIdx.y * N + local --
+// and runs on image `plants` entry blockIdx.y of the set, `image_stride` floats apart behind gF.  It takes the place of the latency shift in the argument block, so that
+// every other instantiation keeps the arguments it had, byte for byte.
+struct TreePlants { int dshift; int image_stride; jh_plant_axis plants; };
+
+template <bool SELF, bool OBJ = false, bool CYL = false, bool PLANTS = false>
 __global__ __launch_bounds__(WAVE, 1) void k_tree_v4(const float* __restrict__ gF, const int* __restrict__ gI, int nF, int nI, const float* state_in, int ld_in,
                                                     const float* __restrict__ ctrl, float* __restrict__ warm, int N, int substeps, float* state_out, int ld_out,
-                                                    float* __restrict__ sensors_out, int ld_sens, int* __restrict__ stats, int dshift) {
+                                                    float* __restrict__ sensors_out, int ld_sens, int* __restrict__ stats, std::conditional_t<PLANTS, TreePlants, int> la) {
+  int dshift, row0 = 0;  // (row0: the block's first global row)
+  if constexpr (PLANTS) {
+    // the block's image: wave-uniform arithmetic on the kernel arguments and blockIdx.y, once -- the LDS copy, the object section and the sensor records all read through gF
+    dshift = la.dshift; row0 = (int)blockIdx.y * N;
+    gF += (size_t)jh_plant_of(la.plants, (int)blockIdx.y, (int)blockIdx.y) * (size_t)la.image_stride;
+  } else {
+    dshift = la;
+  }
   using RS = RS4T<SELF, OBJ>;
   constexpr bool CI = SELF || OBJ;                          // per-contact side bookkeeping (cinfo) in shared memory
   constexpr int NQ_ = OBJ ? NQO : NQ, NV_ = OBJ ? NVO : NVT;  // state row: qpos (robot [, box]), qvel (robot [, box])
@@ -500,9 +515,12 @@ __global__ __launch_bounds__(WAVE, 1) void k_tree_v4(const float* __restrict__ g
     __syncthreads();
   }
   // (latency mode, jh_internal.h: with dshift = 1 both rows of the wave compute the same rollout and the first writes -- the shipped 24-rollout plans)
-  const int n = (blockIdx.x << (1 - dshift)) + (r >> dshift);
-  const bool live = n < N && (r & ((1 << dshift) - 1)) == 0;
-  const int nc = n < N ? n : N - 1;
+  // (PLANTS: N is the block's, so an odd N leaves a dead row in the block's last wave -- it recomputes the block's last rollout, on the block's plant -- and never takes
+  // the next block's first)
+  const int nl = (blockIdx.x << (1 - dshift)) + (r >> dshift);
+  const int n = row0 + nl;
+  const bool live = nl < N && (r & ((1 << dshift) - 1)) == 0;
+  const int nc = row0 + (nl < N ? nl : N - 1);
   const int nj = NJ, ng = sI[1];
   const int npair = SELF ? sI[6] : 0, oPair = sI[7];  // robot-robot geom pairs (g1 | g2 << 8, g1 < g2), read from the global image
   const bool isbase = l < 6, isjoint = l >= 6 && l < 6 + nj, hasdof = isbase || isjoint, isbody = l == 0 || isjoint;
@@ -1510,27 +1528,47 @@ __global__ __launch_bounds__(WAVE, 1) void k_tree_v4(const float* __restrict__ g
 
 }  // namespace
 
-struct jh_tree { float* d_f; int* d_i; int* d_stats; int nj, ng, nq, nv, nf, ni, ns, npair, self_collision, nobj, ocyl; std::vector<hipEvent_t> events; };
+struct jh_tree { float* d_f; int* d_i; int* d_stats; int nj, ng, nq, nv, nf, ni, ns, npair, self_collision, nobj, ocyl; std::vector<hipEvent_t> events; std::vector<int> h_i; };
+// P images that share one int section (jh_tree_set_create): `core` is a jh_tree whose d_f holds the P float sections `stride` floats apart, with the set's own copy of the
+// int section, its own counters and its own events -- what the launchers take from a jh_tree they take from it.
+struct jh_tree_set { jh_tree core; int P, stride; };
 
 namespace {
-// the instantiation for the image (a free box, a free cylinder or neither) and the self-collision switch; states rows of nq + nv floats
-void launch_tree(const jh_tree* t, hipStream_t st, const float* xin, int ld_in, const float* ctrl, float* warm, int N, int substeps, float* xout, int ld_out, float* sens, int ld_sens) {
-  const int dshift = jh_latency_shift(N, RPW), per_wave = RPW >> dshift;
-  const dim3 grid((N + per_wave - 1) / per_wave), block(WAVE);
+// the instantiation for the image (a free box, a free cylinder or neither) and the self-collision switch; states rows of nq + nv floats.  PLANTS: `la` carries the plant
+// axis, N is a block's rollouts and the grid has the blocks in y.
+template <bool PLANTS>
+void launch_tree_as(const jh_tree* t, dim3 grid, hipStream_t st, const float* xin, int ld_in, const float* ctrl, float* warm, int N, int substeps, float* xout, int ld_out, float* sens,
+                    int ld_sens, const std::conditional_t<PLANTS, TreePlants, int>& la) {
+  const dim3 block(WAVE);
   if (t->nobj && t->ocyl) {
     if (t->self_collision)
-      hipLaunchKernelGGL((k_tree_v4<true, true, true>), grid, block, 0, st, t->d_f, t->d_i, t->nf, t->ni, xin, ld_in, ctrl, warm, N, substeps, xout, ld_out, sens, ld_sens, t->d_stats, dshift);
+      hipLaunchKernelGGL((k_tree_v4<true, true, true, PLANTS>), grid, block, 0, st, t->d_f, t->d_i, t->nf, t->ni, xin, ld_in, ctrl, warm, N, substeps, xout, ld_out, sens, ld_sens, t->d_stats, la);
     else
-      hipLaunchKernelGGL((k_tree_v4<false, true, true>), grid, block, 0, st, t->d_f, t->d_i, t->nf, t->ni, xin, ld_in, ctrl, warm, N, substeps, xout, ld_out, sens, ld_sens, t->d_stats, dshift);
+      hipLaunchKernelGGL((k_tree_v4<false, true, true, PLANTS>), grid, block, 0, st, t->d_f, t->d_i, t->nf, t->ni, xin, ld_in, ctrl, warm, N, substeps, xout, ld_out, sens, ld_sens, t->d_stats, la);
   } else if (t->nobj) {
     if (t->self_collision)
-      hipLaunchKernelGGL((k_tree_v4<true, true>), grid, block, 0, st, t->d_f, t->d_i, t->nf, t->ni, xin, ld_in, ctrl, warm, N, substeps, xout, ld_out, sens, ld_sens, t->d_stats, dshift);
+      hipLaunchKernelGGL((k_tree_v4<true, true, false, PLANTS>), grid, block, 0, st, t->d_f, t->d_i, t->nf, t->ni, xin, ld_in, ctrl, warm, N, substeps, xout, ld_out, sens, ld_sens, t->d_stats, la);
     else
-      hipLaunchKernelGGL((k_tree_v4<false, true>), grid, block, 0, st, t->d_f, t->d_i, t->nf, t->ni, xin, ld_in, ctrl, warm, N, substeps, xout, ld_out, sens, ld_sens, t->d_stats, dshift);
+      hipLaunchKernelGGL((k_tree_v4<false, true, false, PLANTS>), grid, block, 0, st, t->d_f, t->d_i, t->nf, t->ni, xin, ld_in, ctrl, warm, N, substeps, xout, ld_out, sens, ld_sens, t->d_stats, la);
   } else if (t->self_collision)
-    hipLaunchKernelGGL(k_tree_v4<true>, grid, block, 0, st, t->d_f, t->d_i, t->nf, t->ni, xin, ld_in, ctrl, warm, N, substeps, xout, ld_out, sens, ld_sens, t->d_stats, dshift);
+    hipLaunchKernelGGL((k_tree_v4<true, false, false, PLANTS>), grid, block, 0, st, t->d_f, t->d_i, t->nf, t->ni, xin, ld_in, ctrl, warm, N, substeps, xout, ld_out, sens, ld_sens, t->d_stats, la);
   else
-    hipLaunchKernelGGL(k_tree_v4<false>, grid, block, 0, st, t->d_f, t->d_i, t->nf, t->ni, xin, ld_in, ctrl, warm, N, substeps, xout, ld_out, sens, ld_sens, t->d_stats, dshift);
+    hipLaunchKernelGGL((k_tree_v4<false, false, false, PLANTS>), grid, block, 0, st, t->d_f, t->d_i, t->nf, t->ni, xin, ld_in, ctrl, warm, N, substeps, xout, ld_out, sens, ld_sens, t->d_stats, la);
+}
+
+// The plant axis of a launch on a set's `core`: `blocks` blocks of N rollouts each, block g on image plants' entry g (blocks = 0: the launch of a single jh_tree)
+struct PlantLaunch { int blocks = 0; int image_stride = 0; jh_plant_axis plants; };
+
+void launch_tree(const jh_tree* t, hipStream_t st, const float* xin, int ld_in, const float* ctrl, float* warm, int N, int substeps, float* xout, int ld_out, float* sens, int ld_sens,
+                 const PlantLaunch* pl = nullptr) {
+  if (pl && pl->blocks > 0) {  // N: a block's rollouts.  The latency shift is the whole launch's: blocks never share a wave, so a block has ceil(N / rows per wave) waves
+    const int dshift = jh_latency_shift(pl->blocks * N, RPW), per_wave = RPW >> dshift;
+    TreePlants la; la.dshift = dshift; la.image_stride = pl->image_stride; la.plants = pl->plants;
+    launch_tree_as<true>(t, dim3((N + per_wave - 1) / per_wave, pl->blocks), st, xin, ld_in, ctrl, warm, N, substeps, xout, ld_out, sens, ld_sens, la);
+    return;
+  }
+  const int dshift = jh_latency_shift(N, RPW), per_wave = RPW >> dshift;
+  launch_tree_as<false>(t, dim3((N + per_wave - 1) / per_wave), st, xin, ld_in, ctrl, warm, N, substeps, xout, ld_out, sens, ld_sens, dshift);
 }
 }  // namespace
 
@@ -1578,6 +1616,7 @@ extern "C" int jh_tree_create(const void* blob, size_t nbytes, jh_tree** out) {
     }
   jh_tree* t = new jh_tree();
   t->nf = (int)nf; t->ni = (int)ni; t->ns = ii[5];
+  t->h_i.assign(ii, ii + ni);  // (the host copy jh_tree_set_create compares: a set's members share one int section)
   t->nj = ii[0]; t->ng = ii[1]; t->nq = ii[2]; t->nv = ii[3];
   t->npair = ii[6]; t->self_collision = ii[6] > 0 ? 1 : 0; t->nobj = nobj; t->ocyl = nobj && ii[ni0] == 5;  // the robot collides with itself when the image lists pairs, as MuJoCo does (jh_tree_set_self_collision)
   JH_HIP(hipMalloc(&t->d_f, 4 * nf)); JH_HIP(hipMalloc(&t->d_i, 4 * ni)); JH_HIP(hipMalloc(&t->d_stats, 64 * sizeof(int)));
@@ -1652,7 +1691,7 @@ extern "C" size_t jh_policy_rollout_scratch_floats(int N) { return jh_policy_scr
 
 // The loop over the command rows: the first control step reads rollout n's start state at x0 + n * ld0 (ld0 = 0: one state for all), every later one the row before it in `states`.
 static int policy_rollout(const jh_policy* p, jh_tree* t, const float* x0, int ld0, const float* commands, float* policy_out, float* warmstart, int reset_warmstart, int N, int T,
-                          int substeps, double cutoff_seconds, float* states, float* sensors, float* scratch, int* steps_done, hipStream_t st) {
+                          int substeps, double cutoff_seconds, float* states, float* sensors, float* scratch, int* steps_done, hipStream_t st, const PlantLaunch* pl = nullptr) {
   float* control = scratch + jh_policy_scratch_floats(N);
   const int NX = t->nq + t->nv, NQ = t->nq, NVT = t->nv;  // the state row of the image's model (robot [+ free box]): the policy reads the robot's part at its offsets
   const bool deadline = cutoff_seconds >= 0.0;
@@ -1672,7 +1711,7 @@ static int policy_rollout(const jh_policy* p, jh_tree* t, const float* x0, int l
     const int rc = jh_policy_step_strided(p, xin, ld, NQ, 0, 0, 7, 6, commands + (size_t)i * 25, T * 25, policy_out, control, scratch, N, st);
     if (rc != JH_OK) return rc;
     if (reset_warmstart) JH_HIP(hipMemsetAsync(warmstart, 0, (size_t)N * NVT * sizeof(float), st));
-    launch_tree(t, st, xin, ld, control, warmstart, N, substeps, states + (size_t)i * NX, T * NX, sensors ? sensors + (size_t)i * t->ns : nullptr, T * t->ns);
+    launch_tree(t, st, xin, ld, control, warmstart, pl ? N / pl->blocks : N, substeps, states + (size_t)i * NX, T * NX, sensors ? sensors + (size_t)i * t->ns : nullptr, T * t->ns, pl);
     if (deadline) JH_HIP(hipEventRecord(t->events[i + 1], st));
   }
   JH_HIP(hipGetLastError());
@@ -1727,4 +1766,126 @@ extern "C" int jh_policy_rollout_batch(const jh_policy* p, jh_tree* t, int B, co
   hipLaunchKernelGGL(k_expand_start_states, dim3((unsigned)((tot + 255) / 256)), dim3(256), 0, st, x0, x0_stride_floats, n, N, NX, start, (size_t)T * NX);
   JH_HIP(hipGetLastError());
   return policy_rollout(p, t, start, T * NX, commands, policy_out, warmstart, reset_warmstart, N, T, substeps, cutoff_seconds, states, sensors, scratch, steps_done, st);
+}
+
+// ---- sets of plants (jh_tree_set_*, include/judo_amd.h) ------------------------------------------------------------------------------------------------------------------
+namespace {
+// what a member must share with member 0 (`core`, once member 0 is in): the counts, the object kind, the int section and the self-collision switch
+int tree_set_admit(const jh_tree& core, const jh_tree* t, int p, const char* who) {
+  JH_REQUIRE(t, "%s: member %d is a null pointer", who, p);
+  JH_REQUIRE(t->nf == core.nf, "%s: member %d has another float section than member 0 (%d floats, member 0 has %d)", who, p, t->nf, core.nf);
+  JH_REQUIRE(t->ni == core.ni, "%s: member %d has another int section than member 0 (%d ints, member 0 has %d)", who, p, t->ni, core.ni);
+  JH_REQUIRE(t->nobj == core.nobj && t->ocyl == core.ocyl, "%s: member %d has another object section than member 0 (its free object is %s, member 0's %s)", who, p,
+             t->nobj ? (t->ocyl ? "a cylinder" : "a box") : "absent", core.nobj ? (core.ocyl ? "a cylinder" : "a box") : "absent");
+  JH_REQUIRE(t->h_i.size() == core.h_i.size() && memcmp(t->h_i.data(), core.h_i.data(), 4 * core.h_i.size()) == 0,
+             "%s: member %d has another int section than member 0 (a set's plants share one: only the float section may differ)", who, p);
+  JH_REQUIRE(t->self_collision == core.self_collision, "%s: member %d has its self-collision switch %s, member 0 has it %s (jh_tree_set_self_collision before the set is made)", who, p,
+             t->self_collision ? "on" : "off", core.self_collision ? "on" : "off");
+  return JH_OK;
+}
+
+// the plant axis of a launch from a HOST table of `blocks` entries; every entry is checked before anything is enqueued
+int tree_set_plants(const jh_tree_set* s, const int* table, int blocks, const char* who, PlantLaunch* out) {
+  out->blocks = blocks; out->image_stride = s->stride;
+  for (int e = 0; e < blocks; e++) {
+    JH_REQUIRE(table[e] >= 0 && table[e] < s->P, "%s: plant_of_block[%d] = %d outside [0, P = %d)", who, e, table[e], s->P);
+    jh_plant_set(out->plants, e, table[e]);
+  }
+  return JH_OK;
+}
+}  // namespace
+
+extern "C" int jh_tree_set_create(const jh_tree* const* trees, int P, jh_tree_set** out) {
+  JH_REQUIRE(trees && out, "tree_set_create: null pointer");
+  JH_REQUIRE(P >= 1 && P <= JH_MAX_ENSEMBLE, "tree_set_create: P = %d outside [1, JH_MAX_ENSEMBLE = %d]", P, JH_MAX_ENSEMBLE);
+  JH_REQUIRE(trees[0], "tree_set_create: member 0 is a null pointer");
+  jh_tree core = {};
+  const jh_tree* t0 = trees[0];
+  core.nj = t0->nj; core.ng = t0->ng; core.nq = t0->nq; core.nv = t0->nv; core.nf = t0->nf; core.ni = t0->ni; core.ns = t0->ns; core.npair = t0->npair;
+  core.self_collision = t0->self_collision; core.nobj = t0->nobj; core.ocyl = t0->ocyl; core.h_i = t0->h_i;
+  for (int p = 1; p < P; p++) { const int rc = tree_set_admit(core, trees[p], p, "tree_set_create"); if (rc != JH_OK) return rc; }
+  const int stride = (core.nf + 3) & ~3;
+  jh_tree_set* s = new jh_tree_set();
+  s->core = core; s->P = P; s->stride = stride;
+  hipError_t e = hipMalloc(&s->core.d_f, sizeof(float) * (size_t)stride * P);
+  if (e == hipSuccess) e = hipMalloc(&s->core.d_i, sizeof(int) * (size_t)core.ni);
+  if (e == hipSuccess) e = hipMalloc(&s->core.d_stats, 64 * sizeof(int));
+  if (e == hipSuccess) e = hipMemset(s->core.d_f, 0, sizeof(float) * (size_t)stride * P);
+  for (int p = 0; p < P && e == hipSuccess; p++) e = hipMemcpy(s->core.d_f + (size_t)p * stride, trees[p]->d_f, sizeof(float) * (size_t)core.nf, hipMemcpyDeviceToDevice);
+  if (e == hipSuccess) e = hipMemcpy(s->core.d_i, core.h_i.data(), sizeof(int) * (size_t)core.ni, hipMemcpyHostToDevice);
+  if (e == hipSuccess) e = hipMemset(s->core.d_stats, 0, 64 * sizeof(int));
+  if (e != hipSuccess) {
+    jh_set_error("tree_set_create: %s", hipGetErrorString(e));
+    jh_tree_set_destroy(s);
+    return JH_ERR_HIP;
+  }
+  *out = s;
+  return JH_OK;
+}
+
+extern "C" int jh_tree_set_update(jh_tree_set* s, int p, const jh_tree* tree) {
+  JH_REQUIRE(s && tree, "tree_set_update: null pointer");
+  JH_REQUIRE(p >= 0 && p < s->P, "tree_set_update: p = %d outside [0, P = %d)", p, s->P);
+  const int rc = tree_set_admit(s->core, tree, p, "tree_set_update");
+  if (rc != JH_OK) return rc;
+  JH_HIP(hipDeviceSynchronize());  // (a launch may still read the plant)
+  JH_HIP(hipMemcpy(s->core.d_f + (size_t)p * s->stride, tree->d_f, sizeof(float) * (size_t)s->core.nf, hipMemcpyDeviceToDevice));
+  return JH_OK;
+}
+
+extern "C" int jh_tree_set_info(const jh_tree_set* s, int* out4) {
+  JH_REQUIRE(s && out4, "tree_set_info: null pointer");
+  out4[0] = s->P; out4[1] = s->stride; out4[2] = s->core.nq; out4[3] = s->core.nv;
+  return JH_OK;
+}
+
+extern "C" int jh_tree_set_stats(jh_tree_set* s, int* out4, int reset) {
+  JH_REQUIRE(s && out4, "tree_set_stats: null pointer");
+  return jh_tree_stats(&s->core, out4, reset);
+}
+
+extern "C" void jh_tree_set_destroy(jh_tree_set* s) {
+  if (!s) return;
+  (void)hipFree(s->core.d_f); (void)hipFree(s->core.d_i); (void)hipFree(s->core.d_stats);
+  for (hipEvent_t e : s->core.events) (void)hipEventDestroy(e);
+  delete s;
+}
+
+extern "C" int jh_tree_substeps_plants(const jh_tree_set* s, const int* plant_of_block, int G, int n, const float* state_in, const float* ctrl, float* warmstart, int substeps,
+                                       float* state_out, float* sensors_out, void* stream) {
+  JH_REQUIRE(s && plant_of_block && state_in && ctrl && state_out, "tree_substeps_plants: null pointer (set, plant_of_block, state_in, ctrl or state_out)");
+  JH_REQUIRE(G >= 1 && n >= 1 && substeps >= 1, "tree_substeps_plants: G = %d, n = %d, substeps = %d: need at least one block, one rollout and one step", G, n, substeps);
+  JH_REQUIRE(G <= JH_MAX_FLEET_PLANT_BLOCKS, "tree_substeps_plants: G = %d exceeds JH_MAX_FLEET_PLANT_BLOCKS = %d (the bytes of the table in the kernel arguments)", G, JH_MAX_FLEET_PLANT_BLOCKS);
+  JH_REQUIRE((long long)G * n <= 0x7fffffffLL, "tree_substeps_plants: G * n = %lld rollouts exceed one launch", (long long)G * n);
+  PlantLaunch pl;
+  const int rc = tree_set_plants(s, plant_of_block, G, "tree_substeps_plants", &pl);
+  if (rc != JH_OK) return rc;
+  const int nx = s->core.nq + s->core.nv;
+  launch_tree(&s->core, (hipStream_t)stream, state_in, nx, ctrl, warmstart, n, substeps, state_out, nx, sensors_out, s->core.ns, &pl);
+  JH_HIP(hipGetLastError());
+  return JH_OK;
+}
+
+extern "C" int jh_policy_rollout_plants(const jh_policy* p, jh_tree_set* s, int B, int G, const int* plant_of_block, const float* x0, size_t x0_stride_floats, const float* commands,
+                                        float* policy_out, float* warmstart, int reset_warmstart, int n, int T, int substeps, double cutoff_seconds, float* states, float* sensors,
+                                        float* scratch, int* steps_done, void* stream) {
+  JH_REQUIRE(p && s && plant_of_block && x0 && commands && policy_out && states && scratch,
+             "policy_rollout_plants: null pointer (policy, set, plant_of_block, x0, commands, policy_out, states or scratch)");
+  JH_REQUIRE(B >= 1 && G >= 1 && n >= 1 && T >= 1 && substeps >= 1,
+             "policy_rollout_plants: B = %d, G = %d, n = %d, T = %d, substeps = %d: need at least one problem, one block, one rollout, one command row and one substep", B, G, n, T, substeps);
+  JH_REQUIRE((long long)B * G <= JH_MAX_FLEET_PLANT_BLOCKS, "policy_rollout_plants: B * G = %d * %d = %lld exceeds JH_MAX_FLEET_PLANT_BLOCKS = %d (the bytes of the table in the kernel arguments)",
+             B, G, (long long)B * G, JH_MAX_FLEET_PLANT_BLOCKS);
+  JH_REQUIRE((long long)B * G * n <= 0x7fffffffLL, "policy_rollout_plants: B * G * n = %lld rollouts exceed one launch", (long long)B * G * n);
+  JH_REQUIRE(!reset_warmstart || warmstart, "policy_rollout_plants: reset_warmstart needs a warmstart buffer");
+  const int NX = s->core.nq + s->core.nv, N = B * G * n;
+  JH_REQUIRE(x0_stride_floats >= (size_t)NX, "policy_rollout_plants: x0_stride_floats = %zu is smaller than a state (%d floats)", x0_stride_floats, NX);
+  PlantLaunch pl;
+  const int rc = tree_set_plants(s, plant_of_block, B * G, "policy_rollout_plants", &pl);
+  if (rc != JH_OK) return rc;
+  hipStream_t st = (hipStream_t)stream;
+  float* start = states + (size_t)(T - 1) * NX;  // (the start states, one row per rollout, where jh_policy_rollout_batch puts them)
+  const size_t tot = (size_t)N * NX;
+  hipLaunchKernelGGL(k_expand_start_states, dim3((unsigned)((tot + 255) / 256)), dim3(256), 0, st, x0, x0_stride_floats, G * n, N, NX, start, (size_t)T * NX);
+  JH_HIP(hipGetLastError());
+  return policy_rollout(p, &s->core, start, T * NX, commands, policy_out, warmstart, reset_warmstart, N, T, substeps, cutoff_seconds, states, sensors, scratch, steps_done, st, &pl);
 }

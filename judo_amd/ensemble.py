@@ -70,7 +70,8 @@ def check_task(task: Task, fr3: bool = False) -> None:
     """The tasks without an ensemble plan step, refused before any model is made; raises ValueError.  `fr3`: the caller's plan step carries the arm's phase
     (judo_amd.fr3_ensemble), so fr3_pick passes."""
     if task.uses_locomotion_policy:
-        raise ValueError("the Spot policy tasks have no ensemble plan step: their iteration is the materialise path (spline, policy rollout, reward, update), not one library call")
+        raise ValueError("the Spot policy tasks have no ensemble plan step: their iteration is the materialise path (spline, policy rollout, reward, update), not one library call.  "
+                         "judo_amd.spot_plants.make_spot_ensemble_controller makes the controller that keeps that path and rolls every candidate out on all the plants")
     if task.desc.get("family", task.desc["task"]) == "fr3_pick" and not fr3:
         raise ValueError("fr3_pick has no ensemble plan step: its phase is chosen per problem on the host and the ensemble entries carry none.  "
                          "judo_amd.fr3_ensemble.make_fr3_ensemble_controller makes the controller whose plan step carries the phase; one arm against perturbed "

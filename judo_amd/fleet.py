@@ -51,6 +51,10 @@ def refuse_fr3_randomized(i: int, c: Controller, fleet: "ControllerFleet | None"
         raise ValueError(f"fleet member {i} is an FR3EnsembleController: its plan step (jh_plan_step_ensemble_phase) puts the M plants of ONE arm on the launch's problem "
                          "axis, and this fleet's entry has no controller axis behind an arm's plants.  fr3_pick ensemble controllers share a launch in an FR3EnsembleFleet "
                          "(judo_amd.fr3_ensemble.make_fr3_ensemble_fleet)")
+    if getattr(c, "_spot_plants", False):
+        raise ValueError(f"fleet member {i} is a {type(c).__name__} (judo_amd.spot_plants): its rollouts run on the plants of its own SpotPlantSet "
+                         "(jh_policy_rollout_plants), and a fleet's one policy rollout runs every member's rows on ONE model image -- it would plan this member on plant 0 "
+                         "alone.  No fleet takes such a member yet: run its update_action() on its own")
 
 
 class _MemberBuffers:

@@ -28,7 +28,7 @@ from judo_amd import _lib
 from judo_amd.device import current_stream_ptr, f32, require_gpu
 from judo_amd.models import load_description
 from judo_amd.rollout_backend import RolloutBackend
-from judo_amd.tree_model import pack_tree_blob
+from judo_amd.tree_model import check_tree_descriptions, pack_tree_blob
 
 POLICY_PATH = os.path.join(os.path.dirname(os.path.abspath(__file__)), "models", "spot_locomotion_policy.npz")
 
@@ -146,6 +146,58 @@ class SpotTreeEngine:
             pass
 
 
+class SpotPlantSet:
+    """P perturbed copies of one Spot model as a device set for the tree kernel (`jh_tree_set_create`): `descriptions` that pack to images differing in the float section
+    alone (`tree_model.check_tree_descriptions`; `models.scaled_description` of `spot`, `spot_box` or `spot_tire`).  `engines[p]` is plant p's own `SpotTreeEngine` --
+    one per distinct description -- whose float section the set copied; a launch on the set puts each rollout block on a plant (`PolicyRolloutBackend.rollout_plants`)."""
+
+    def __init__(self, descriptions, device: torch.device | None = None, self_collision: bool = True) -> None:
+        self.device = device or require_gpu()
+        check_tree_descriptions(descriptions)
+        self.self_collision = bool(self_collision)
+        self.descriptions = list(descriptions)
+        self.engines: list[SpotTreeEngine] = []
+        for i, d in enumerate(self.descriptions):
+            same = next((j for j in range(i) if self.descriptions[j] is d or self.descriptions[j] == d), None)
+            self.engines.append(self.engines[same] if same is not None else SpotTreeEngine(d, self.device, self.self_collision))
+        P = len(self.engines)
+        trees = (C.c_void_p * P)(*[e.handle for e in self.engines])
+        handle = C.c_void_p()
+        with torch.cuda.device(self.device):
+            _lib.check(_lib.lib().jh_tree_set_create(trees, P, C.byref(handle)), "jh_tree_set_create")
+        self.handle = handle
+        info = (C.c_int * 4)()
+        _lib.check(_lib.lib().jh_tree_set_info(self.handle, info), "jh_tree_set_info")
+        self.num_plants, self.image_stride, self.nq, self.nv = (int(v) for v in info)
+        self.nsensordata, self.timestep = self.engines[0].nsensordata, self.engines[0].timestep
+
+    def set_member(self, p: int, desc: dict) -> None:
+        """Replace plant p (`jh_tree_set_update`: the library's checks; synchronous -- between launches)."""
+        p = int(p)
+        if not 0 <= p < len(self.engines):
+            raise ValueError(f"plant {p} of a set of {len(self.engines)}")
+        trial = list(self.descriptions)
+        trial[p] = desc
+        check_tree_descriptions(trial)
+        engine = SpotTreeEngine(desc, self.device, self.self_collision)
+        _lib.check(_lib.lib().jh_tree_set_update(self.handle, p, engine.handle), "jh_tree_set_update")
+        self.engines[p], self.descriptions[p] = engine, desc
+
+    def stats(self, reset: bool = True) -> dict:
+        """`SpotTreeEngine.stats` of the launches on the set (the members' own engines count their own launches)."""
+        buf = (C.c_int * 4)()
+        _lib.check(_lib.lib().jh_tree_set_stats(self.handle, buf, int(reset)), "jh_tree_set_stats")
+        return dict(contacts_dropped=buf[0], steps_at_cap=buf[1], newton_iterations=buf[2], steps=buf[3])
+
+    def __del__(self) -> None:
+        try:
+            if getattr(self, "handle", None):
+                _lib.lib().jh_tree_set_destroy(self.handle)
+                self.handle = None
+        except Exception:
+            pass
+
+
 class PolicyRolloutBackend(RolloutBackend):
     """Drop-in for `PolicyMJRolloutBackend` (judo/utils/policy_mj_rollout_backend.py:20-125): N rollouts of the Spot plant under the locomotion
     policy, one policy step per command row followed by `physics_substeps` engine steps; the state is recorded after the substeps.
@@ -241,5 +293,41 @@ class PolicyRolloutBackend(RolloutBackend):
                                       int(not self.carry_warmstart), N // B, T, self.physics_substeps, -1.0 if cutoff_time is None else float(cutoff_time), _lib.ptr(states),
                                       _lib.ptr(sensors) if sensors.numel() else None, _lib.ptr(self._scratch), C.byref(done), current_stream_ptr())
         _lib.check(s, "jh_policy_rollout_batch")
+        self.steps_computed = int(done.value)
+        return states, sensors
+
+    def rollout_plants(self, plants: SpotPlantSet, x0_blocks: torch.Tensor, x0_stride: int, B: int, G: int, plant_of_block, commands: torch.Tensor, policy_out: torch.Tensor,
+                       cutoff_time: float | None = None):
+        """B problems of G rollout blocks of num_threads / (B * G) rollouts each in one launch chain (`jh_policy_rollout_plants`), block (b, g) on plant
+        `plant_of_block[b * G + g]` of `plants`: rollout r starts from problem r // (G * n)'s state, the B states lying `x0_stride` floats apart in the device tensor
+        `x0_blocks`.  commands (B * G * n, T, 25) and policy_out (B * G * n, 12), contiguous float32 device tensors; policy_out and this backend's warm start are read and
+        overwritten IN PLACE.  Returns (states, sensors); block (b, g)'s rows are bit for bit those of `rollout` with n threads on that plant's own engine from problem b's
+        state.  The table travels in the kernel arguments: another one for the next call costs nothing."""
+        N, nx = self.num_threads, plants.nq + plants.nv
+        if (plants.nq, plants.nv) != (self.engine.nq, self.engine.nv):
+            raise ValueError(f"the set's plants have nq / nv = {plants.nq} / {plants.nv}, this backend's model {self.engine.nq} / {self.engine.nv}")
+        if B < 1 or G < 1 or N % (B * G):
+            raise ValueError(f"{N} threads do not split into {B} problems of {G} equal blocks")
+        table = [int(v) for v in plant_of_block]
+        if len(table) != B * G:
+            raise ValueError(f"plant_of_block has {len(table)} entries for B * G = {B} * {G} blocks")
+        if commands.ndim != 3 or commands.shape[0] != N or commands.shape[2] != SpotLocomotionPolicy.NCMD or not commands.is_contiguous() or commands.dtype != torch.float32:
+            raise ValueError(f"commands must be a contiguous float32 ({N}, T, 25) tensor, got {tuple(commands.shape)}")
+        if tuple(policy_out.shape) != (N, SpotLocomotionPolicy.ACT) or not policy_out.is_contiguous() or policy_out.dtype != torch.float32:
+            raise ValueError(f"policy_out must be a contiguous float32 ({N}, 12) tensor, got {tuple(policy_out.shape)}")
+        if x0_blocks.dtype != torch.float32 or x0_stride < nx or x0_blocks.numel() < (B - 1) * x0_stride + nx:
+            raise ValueError(f"x0_blocks must hold {B} float32 states of {nx} floats, {x0_stride} apart")
+        T = int(commands.shape[1])
+        states = torch.empty((N, T, nx), dtype=torch.float32, device=self.device)
+        sensors = torch.empty((N, T, plants.nsensordata), dtype=torch.float32, device=self.device)
+        L = _lib.lib()
+        need = int(L.jh_policy_rollout_scratch_floats(N))
+        if self._scratch is None or self._scratch.numel() < need:
+            self._scratch = torch.empty(need, dtype=torch.float32, device=self.device)
+        done = C.c_int(0)
+        s = L.jh_policy_rollout_plants(self.policy.handle, plants.handle, B, G, (C.c_int * len(table))(*table), _lib.ptr(x0_blocks), int(x0_stride), _lib.ptr(commands), _lib.ptr(policy_out),
+                                       _lib.ptr(self._warm), int(not self.carry_warmstart), N // (B * G), T, self.physics_substeps, -1.0 if cutoff_time is None else float(cutoff_time),
+                                       _lib.ptr(states), _lib.ptr(sensors) if sensors.numel() else None, _lib.ptr(self._scratch), C.byref(done), current_stream_ptr())
+        _lib.check(s, "jh_policy_rollout_plants")
         self.steps_computed = int(done.value)
         return states, sensors

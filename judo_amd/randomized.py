@@ -71,7 +71,8 @@ def check_task(task: Task, fr3: bool = False) -> None:
     """The tasks without a randomised plan step, refused before any model is made; raises ValueError.  `fr3`: the caller's plan step carries the arm's phase
     (judo_amd.fr3_randomized), so fr3_pick passes."""
     if task.uses_locomotion_policy:
-        raise ValueError("the Spot policy tasks have no randomised plan step: their iteration is the materialise path (spline, policy rollout, reward, update), not one library call")
+        raise ValueError("the Spot policy tasks have no randomised plan step: their iteration is the materialise path (spline, policy rollout, reward, update), not one library call.  "
+                         "judo_amd.spot_plants.make_spot_randomized_controller makes the controller that keeps that path and spreads the candidates over the plants")
     if task.desc.get("family", task.desc["task"]) == "fr3_pick" and not fr3:
         raise ValueError("fr3_pick has no randomised plan step behind this class: its phase is chosen per problem on the host, and jh_plan_step_randomized carries none.  "
                          "judo_amd.fr3_randomized.make_fr3_randomized_controller makes the controller whose plan step carries the phase, "

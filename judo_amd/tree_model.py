@@ -312,3 +312,31 @@ def pack_tree_blob(desc: dict) -> bytes:
     """Header (magic, counts) + float image + int image, the form jh_tree_create takes."""
     F, I = pack_tree_model(desc)
     return np.array([0x34564A54, F.size, I.size, 0], dtype=np.uint32).tobytes() + F.tobytes() + I.tobytes()
+
+
+MAX_TREE_PLANTS = 32  # JH_MAX_ENSEMBLE (include/judo_amd.h): the plants of a jh_tree_set
+
+
+def tree_image_sections(blob: bytes) -> tuple[bytes, bytes, bytes]:
+    """(header, float section, int section) of a `pack_tree_blob` image: 16 bytes, then `nf` floats, then `ni` ints."""
+    _, nf, ni, _ = np.frombuffer(blob[:16], dtype=np.uint32)
+    return blob[:16], blob[16 : 16 + 4 * int(nf)], blob[16 + 4 * int(nf) : 16 + 4 * int(nf) + 4 * int(ni)]
+
+
+def check_tree_descriptions(descriptions) -> list[bytes]:
+    """The admission rule of a set of Spot plants (`jh_tree_set_create`), without a device: the descriptions pack to tree images whose header and int section are
+    member 0's byte for byte -- the float section alone may differ (masses, inertias, friction, gains: `models.scaled_description`).  Returns the packed images; raises
+    ValueError naming the member and the section."""
+    if len(descriptions) < 1:
+        raise ValueError("a set of Spot plants needs at least one description")
+    if len(descriptions) > MAX_TREE_PLANTS:
+        raise ValueError(f"a set of {len(descriptions)} Spot plants exceeds the {MAX_TREE_PLANTS} of a launch (include/judo_amd.h JH_MAX_ENSEMBLE)")
+    blobs = [pack_tree_blob(d) for d in descriptions]
+    want = tree_image_sections(blobs[0])
+    for i, blob in enumerate(blobs[1:], start=1):
+        if blob == blobs[0]:
+            continue
+        for name, x, y in zip(("header", "float section", "int section"), tree_image_sections(blob), want):
+            if (x != y and name != "float section") or len(x) != len(y):
+                raise ValueError(f"Spot plant {i} has another model image than plant 0: the {name} of its image differs")
+    return blobs
