@@ -643,6 +643,23 @@ int jh_policy_rollout_plants(const jh_policy* p, jh_tree_set* set, int B, int G,
                              float* policy_out, float* warmstart, int reset_warmstart, int n, int T, int substeps, double cutoff_seconds, float* states, float* sensors,
                              float* scratch, int* steps_done, void* stream);
 
+/* ---- jh_rollout_materialize on the plants of a model set: the domain-randomised RolloutBackend.rollout.  G blocks of n rollouts in ONE launch, block g (rows
+ * g * n .. g * n + n - 1 of states and sensors) on plant plant_of_block[g] of the set; plant_of_block is a HOST array of G entries in [0, M) that travels in the kernel
+ * arguments, G <= JH_MAX_FLEET_PLANT_BLOCKS, M <= JH_MAX_ENSEMBLE.  x0 is one state (nq+nv) or, when x0_batched, one per row (G * n, nq+nv).  controls are (G * n, H, nu),
+ * block g's own n rows, or, when controls_shared, (n, H, nu): rows [0, n) for every block -- an ensemble rolls the same candidates out on every plant without copying
+ * them M times.  states (G * n, H, nq+nv) and sensors (G * n, H, nsensordata) as for jh_rollout_materialize; one of the two may be NULL.  Blocks never share a wave or a
+ * workgroup: a ragged last workgroup, or an idle row of a block's last wave, ends at its own block's last rollout.  The int section (topology, pair lists) is the set's
+ * one copy, as for the plan steps on a set.  Families: cartpole, cylinder_push and the leap family (kernel generation 3: 48 contacts, 64 contacts, cylinders; the hand's
+ * own contacts on or off).
+ * Contract: rows [g * n, (g + 1) * n) of states and sensors are bit for bit what jh_rollout_materialize writes on plant plant_of_block[g]'s own jh_model for those n rows
+ * (its x0 and controls), whatever the latency mode the launch's G * n rollouts select and whichever blocks stand beside it.
+ * JH_ERR_INVALID before anything is enqueued, jh_last_error naming the argument: a null pointer (set, plant_of_block, x0, controls); states and sensors both NULL; G
+ * outside 1..JH_MAX_FLEET_PLANT_BLOCKS; n or H < 1; a table entry outside [0, M) (named with its block); G * n beyond the 2^31 - 1 rollouts of one launch.
+ * JH_ERR_UNSUPPORTED: a set of fr3_pick models (jh_fr3_model_set_create) -- the arm kernel has no materialise launch on plants yet --, or a member 0 switched to
+ * another kernel generation. */
+int jh_rollout_materialize_plants(const jh_model_set* set, const int* plant_of_block, int G, int n, const float* x0, int x0_batched, const float* controls, int controls_shared,
+                                  int H, float* states, float* sensors, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -1340,6 +1340,41 @@ extern "C" int jh_rollout_materialize(const jh_model* m, const float* x0, int x0
   return g_xcheck.rollout_materialize(m, m->kernel_gen, x0, x0_batched, controls, N, H, states, sensors, stream);
 }
 
+// jh_rollout_materialize on the plants of a model set (include/judo_amd.h): G blocks of n rollouts in ONE launch on grid (workgroups of a block, G), block g on image
+// plant_of_block[g].  The table travels in the kernel arguments (jh_plant_axis); the int section is the set's one copy, by the rule the plan steps on a set use.  Every
+// check stands in front of the first enqueue.
+extern "C" int jh_rollout_materialize_plants(const jh_model_set* set, const int* plant_of_block, int G, int n, const float* x0, int x0_batched, const float* controls, int controls_shared,
+                                             int H, float* states, float* sensors, void* stream) {
+  const char* who = "rollout_materialize_plants";
+#define JH_MP_PTR(p) JH_REQUIRE((p) != nullptr, "%s: " #p " is a null pointer", who)
+  JH_MP_PTR(set); JH_MP_PTR(plant_of_block); JH_MP_PTR(x0); JH_MP_PTR(controls);
+#undef JH_MP_PTR
+  JH_REQUIRE(states || sensors, "%s: states and sensors are both null: nothing to compute", who);
+  const jh_model* m = set->m0;
+  const int M = set->B;
+  if (m->kind == JH_TASK_FR3_PICK) {
+    jh_set_error("%s: an fr3_pick set: the cooperative arm kernel has no materialise launch on plants yet (its batched instantiations are fused launches); "
+                 "jh_rollout_materialize on a member's own handle rolls one plant out", who);
+    return JH_ERR_UNSUPPORTED;
+  }
+  JH_REQUIRE(M <= JH_MAX_ENSEMBLE, "%s: a set of %d members exceeds JH_MAX_ENSEMBLE = %d", who, M, JH_MAX_ENSEMBLE);
+  JH_REQUIRE(G >= 1 && G <= JH_MAX_FLEET_PLANT_BLOCKS, "%s: G = %d outside [1, JH_MAX_FLEET_PLANT_BLOCKS = %d] (the bytes of the table in the kernel arguments)", who, G, JH_MAX_FLEET_PLANT_BLOCKS);
+  JH_REQUIRE(n >= 1, "%s: n = %d must be at least 1", who, n);
+  JH_REQUIRE(H >= 1, "%s: H = %d must be at least 1", who, H);
+  for (int g = 0; g < G; g++) JH_REQUIRE(plant_of_block[g] >= 0 && plant_of_block[g] < M, "%s: plant_of_block[%d] = %d outside [0, M = %d): block %d names no member of the set", who, g, plant_of_block[g], M, g);
+  JH_REQUIRE((long long)G * n <= 0x7fffffffll, "%s: G * n = %d * %d rollouts exceed one launch", who, G, n);
+  const bool closed = m->kind == JH_TASK_CARTPOLE || m->kind == JH_TASK_CYLINDER_PUSH;
+  const jh_engine_build* eb = engine_build(m);
+  if (!closed && !(eb && eb->materialize_plants)) { jh_set_error("%s: no materialise kernel on plants for this model / kernel generation", who); return JH_ERR_UNSUPPORTED; }
+  jh_plant_axis plants;
+  for (int g = 0; g < G; g++) jh_plant_set(plants, g, plant_of_block[g]);
+  hipStream_t st = (hipStream_t)stream;
+  if (closed) return jh_simple_materialize_plants(m, set->d_images, (long long)set->stride, plants, G, x0, x0_batched, controls, controls_shared, n, H, states, sensors, st);
+  jh_rollout_batch rb = {set->d_images, (long long)set->stride, set->tables ? m->d_i : set->d_i_plain, G, 0, 0};
+  rb.plants = plants;
+  return eb->materialize_plants(m, rb, x0, x0_batched, controls, controls_shared, n, H, states, sensors, st);
+}
+
 extern "C" int jh_task_reward(const jh_model* m, const float* states, const float* sensors, const float* controls, const float* tp, int phase, int N,
                               int H, float* rewards, void* stream) {
   JH_REQUIRE(m && states && tp && rewards, "task_reward: null pointer");

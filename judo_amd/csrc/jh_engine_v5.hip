@@ -469,6 +469,8 @@ __device__ __forceinline__ bool chain_elim_order(int cmask, int c, int& level, i
 // topology, pair lists, lane lists -- is one for the launch.  The plant axis (jh_plan_step_randomized; jh_internal.h) makes the problems blocks of ONE problem's rollouts:
 // a stride on the global rollout index, so that only global rollout 0 is the noise-free nominal, and a by-value table from the problem to its image in place of the
 // problem's own index -- 0 and the identity for every other batched launch.  The other instantiations ignore the three strides and compile to the code they had without them.
+// BATCH with MATERIALIZE (jh_rollout_materialize_plants): the blocks of a materialise launch, each on a plant of a model set -- the same grid and the same by-value table,
+// the strides put to the block's controls, x0 and image (below, at the top of the kernel).
 template <bool MATERIALIZE, int WPB, bool SELF, bool PERSIST = false, bool BATCH = false>
 __global__ __launch_bounds__(WAVE * WPB, WAVES_PER_EU) void k_leap_v5(const float* __restrict__ gF, const int* __restrict__ gI, const float* __restrict__ x0, int x0_batched,
                                                    const float* __restrict__ nominal, const float* __restrict__ noise, int ldn,
@@ -478,8 +480,20 @@ __global__ __launch_bounds__(WAVE * WPB, WAVES_PER_EU) void k_leap_v5(const floa
                                                    float* __restrict__ sensors, int* __restrict__ stats_, int dshift_, float* __restrict__ trace, float* __restrict__ ovf_all_, unsigned* __restrict__ head,
                                                    long long batch_blk, long long batch_noise, long long batch_image, unsigned* pflags, int slices_,
                                                    std::conditional_t<BATCH, BatchBounds, SliceBounds> sb_) {
-  static_assert(!BATCH || (!MATERIALIZE && !PERSIST), "batched launches are fused launches on the static grid");
-  if constexpr (BATCH) {
+  static_assert(!BATCH || !PERSIST, "batched launches run on the static grid");
+  if constexpr (BATCH && MATERIALIZE) {
+    // Materialise mode on a plant axis (jh_rollout_materialize_plants), grid (groups of a block, G): block blockIdx.y is N rollouts of its own on the image its table
+    // entry names.  The three strides are the block's here -- `batch_blk` floats to the next block's controls (0: every block reads rows [0, N)), `batch_noise` to its
+    // rows of x0 (0: one state for the launch), `batch_image` to the next image -- and its rows of states, sensors and overflow lie N rollouts behind the
+    // block before.  Pointer offsets from kernel arguments and blockIdx.y alone; below, N is the block's and a rollout's code is the single launch's.
+    const long long pb = blockIdx.y;
+    gF += jh_plant_of(sb_.plants, (int)pb, (int)pb) * batch_image;
+    x0 += pb * batch_noise; controls += pb * batch_blk;
+    if (states) states += pb * N * H * NX;
+    if (sensors) sensors += pb * N * H * gI[7];
+    if (NOVF > 0 && ovf_all_) ovf_all_ += pb * N * (NOVF * POOL_F);
+  }
+  if constexpr (BATCH && !MATERIALIZE) {
     // blockIdx.z: the controller of jh_plan_step_ensemble_batch, whose M plants are the problems of blockIdx.y -- strides of its own in sb_ (all 0 and gridDim.z == 1 for
     // every other batched launch); `pr`: the (controller, problem) pair, which owns the costs, trace and overflow rows
     const long long pb = blockIdx.y, pc = blockIdx.z, pr = pc * gridDim.y + pb;
@@ -2066,8 +2080,29 @@ static int rollout_cost_batch(const jh_model* m, const jh_rollout_args& a, const
   return jh_launch_done(k.ovf, st);
 }
 
+// (Behind the fused batched launch for the same reason.)  Materialise mode on a plant axis (jh_rollout_materialize_plants): s.B blocks of n rollouts on the grid (groups of
+// a block, s.B), block g on image s.plants[g] of s.images and on the one int section s.ints.  x0 is one state, or one per row of the s.B * n; the controls are a block's own
+// n rows, or rows [0, n) for every block.  The latency shift is chosen from s.B * n, the rollouts of the launch (the bits do not depend on it); a block's rows never share
+// a wave with another block's, and a dead row of a block's last wave recomputes that block's last rollout.
+static int materialize_plants(const jh_model* m, const jh_rollout_batch& s, const float* x0, int x0_batched, const float* controls, int controls_shared, int n, int H, float* states,
+                              float* sensors, hipStream_t st) {
+  if (int rc = leap_refusal(m, "rollout_materialize_plants")) return rc;
+  const long long rollouts = (long long)s.B * n;
+  JH_REQUIRE(rollouts <= 0x7fffffffll, "rollout_materialize_plants: G * n = %lld rollouts exceed one launch", rollouts);
+  jh_rollout_args a = {};
+  a.x0 = x0; a.N = n; a.H = H;
+  LeapArgs k = leap_args(m, a, s.images, s.ints, (int)rollouts);
+  k.x0_batched = x0_batched; k.controls = controls; k.states = states; k.sensors = sensors;
+  k.batch_blk = controls_shared ? 0 : (long long)n * H * NU; k.batch_noise = x0_batched ? (long long)n * NX : 0; k.batch_image = s.image_stride;
+  k.sb.plants = s.plants;
+  if (const size_t b = ovf_bytes((size_t)rollouts)) k.ovf = jh_launch_scratch(m, b, st);  // (every block's rows; nullptr: the LDS capacity alone, drops and the fallback counted)
+  if (hand_contacts(m)) launch<true, true, false, true>(k, dim3(k.grid, s.B), st);
+  else launch<true, false, false, true>(k, dim3(k.grid, s.B), st);
+  return jh_launch_done(k.ovf, st);
+}
+
 // This build's row of the table (jh_internal.h); `accepts` is what the launchers above ask of a model, for a caller that must know in advance (jh_model_set_create: every
 // member of a set, on its own floats).  Host pass only: a const object with a constant initialiser would be emitted into the code object as well.
 #ifndef __HIP_DEVICE_COMPILE__
-const jh_engine_build JH_V5_NAME(jh_engine5_build) = {JH_V5_CYL ? "leap, cylinders" : NCAP > 48 ? "leap, 64 contacts" : "leap, 48 contacts", accepts, rollout_cost, rollout_cost_batch, materialize, NCAP};
+const jh_engine_build JH_V5_NAME(jh_engine5_build) = {JH_V5_CYL ? "leap, cylinders" : NCAP > 48 ? "leap, 64 contacts" : "leap, 48 contacts", accepts, rollout_cost, rollout_cost_batch, materialize, NCAP, materialize_plants};
 #endif

@@ -164,6 +164,10 @@ struct jh_engine_build {
   int (*rollout_cost_batch)(const jh_model* m, const jh_rollout_args& a, const jh_rollout_batch& s, hipStream_t st);  // null: the build has no batched launch (none of the shipped rows; fr3: a phase per problem, jh_rollout_batch::o_phase)
   int (*materialize)(const jh_model* m, const float* x0, int x0_batched, const float* controls, int N, int H, float* states, float* sensors, hipStream_t st);
   int contact_capacity;                   // contacts a rollout can hold (jh_model_limits out[3]), from the build's own constants
+  // materialise mode on a plant axis (jh_rollout_materialize_plants): s.B blocks of n rollouts, block g on image s.plants[g] of s.images; of `s` the launch reads images,
+  // image_stride, ints, B and plants.  null: the build has no such launch (the fr3 rows)
+  int (*materialize_plants)(const jh_model* m, const jh_rollout_batch& s, const float* x0, int x0_batched, const float* controls, int controls_shared, int n, int H, float* states,
+                            float* sensors, hipStream_t st) = nullptr;
 };
 // (hidden: the rows are the library's own, not part of its boundary)
 extern __attribute__((visibility("hidden"))) const jh_engine_build jh_engine5_build, jh_engine5_build_cap64, jh_engine5_build_cyl;  // jh_engine_v5.hip: the leap kernel for 48 and 64 contacts, and with cylinders
@@ -184,6 +188,9 @@ int jh_simple_one_launch_max_knots(const jh_model* m, int H);  // largest K of t
 int jh_engine_max_knots(const jh_model* m, int H);
 int jh_simple_materialize(const jh_model* m, const float* x0, int x0_batched, const float* controls, int N, int H, float* states,
                           float* sensors, hipStream_t st);
+// jh_simple_materialize on a plant axis (jh_rollout_materialize_plants): G blocks of n rollouts, block g on image p's table entry g of `images`, `image_stride` floats apart
+int jh_simple_materialize_plants(const jh_model* m, const float* images, long long image_stride, const jh_plant_axis& p, int G, const float* x0, int x0_batched, const float* controls,
+                                 int controls_shared, int n, int H, float* states, float* sensors, hipStream_t st);
 int jh_simple_reward(const jh_model* m, const float* states, const float* controls, const float* tp, int N, int H, float* rewards, hipStream_t st);
 
 int jh_engine_rollout_cost(const jh_model* m, const float* x0, const float* nominal, const float* noise, int ldn, const float* sigma,

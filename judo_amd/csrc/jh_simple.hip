@@ -15,6 +15,7 @@
 // (derivation in DESIGN.md section 4): semi-implicit update  v += h*a ; q += h*v  with
 // a = (M + h*diag(damping))^-1 (qfrc_smooth + qfrc_constraint); soft constraints by solref/solimp.
 #include <cstdint>
+#include <type_traits>
 #include "jh_internal.h"
 #include "jh_update_dev.h"
 
@@ -290,10 +291,25 @@ __device__ __forceinline__ void tile_move_full(float* __restrict__ g, size_t pit
   }
 }
 
-template <class T, int TS>
+// PLANTS (jh_rollout_materialize_plants), grid (workgroups of a block, G): block blockIdx.y is N rollouts of its own on the image its table entry names.  The last
+// argument, the single launch's `vec_ok`, is then a record: the same flag, the floats from one image to the next, from one block's x0 and controls to the next block's
+// (0: one state for the launch; rows [0, N) of the controls for every block), and the table.  The block's pointers are set once at the top, from kernel arguments and
+// blockIdx.y alone; below them the code is the single launch's, so a workgroup belongs to one block and a ragged last workgroup ends at its block's last rollout.  The
+// other instantiation keeps the argument list and the code it had.
+struct MatPlants { int vec_ok; long long image, x0_stride, ctrl_stride; jh_plant_axis plants; };
+template <class T, int TS, bool PLANTS = false>
 __global__ __launch_bounds__(kBlock) void k_materialize(const float* __restrict__ P, const float* __restrict__ x0, int x0_batched,
                                                         const float* __restrict__ controls, int N, int H, float* __restrict__ states,
-                                                        float* __restrict__ sensors, int vec_ok) {
+                                                        float* __restrict__ sensors, std::conditional_t<PLANTS, MatPlants, int> vec_ok_) {
+  int vec_ok;
+  if constexpr (PLANTS) {
+    const long long g = blockIdx.y, rows = g * N * H;
+    vec_ok = vec_ok_.vec_ok;
+    P += jh_plant_of(vec_ok_.plants, (int)g, (int)g) * vec_ok_.image;
+    x0 += g * vec_ok_.x0_stride; controls += g * vec_ok_.ctrl_stride;
+    if (states) states += rows * T::NX;
+    if (sensors) sensors += rows * T::NS;
+  } else vec_ok = vec_ok_;
   constexpr int SU = (TS * T::NU) | 1, SX = (TS * T::NX) | 1, SY = (TS * T::NS) | 1;
   constexpr bool kVec = (TS * T::NU) % 4 == 0 && (TS * T::NX) % 4 == 0 && (TS * T::NS) % 4 == 0;
   __shared__ float sP[T::NP];
@@ -468,4 +484,26 @@ int jh_simple_reward(const jh_model* m, const float* states, const float* contro
   else hipLaunchKernelGGL(k_reward<CylinderPush>, dim3(grid), dim3(kBlock), 0, st, states, controls, tp, N, H, rewards);
   JH_HIP(hipGetLastError());
   return JH_OK;
+}
+
+// (Last in the file: the PLANTS instantiations of k_materialize are emitted behind every other kernel.)  G blocks of n rollouts, block g on image p's table entry g of
+// `images`; x0 one state or one per row of the G * n; the controls a block's own n rows, or rows [0, n) for every block.
+template <class T>
+static int launch_materialize_plants(const float* images, long long image_stride, const jh_plant_axis& p, int G, const float* x0, int x0_batched, const float* controls, int controls_shared, int n,
+                                     int H, float* states, float* sensors, hipStream_t st) {
+  // float4 tile moves need 16-byte aligned rows in EVERY block: aligned base pointers, H a multiple of the tile length, and block offsets of whole float4s (n * H * width
+  // floats: implied by the tile length of 8 steps, checked all the same) -- or every block falls back to the scalar path
+  const long long rows = (long long)n * H;
+  const bool offsets_ok = G == 1 || ((controls_shared || rows * T::NU % 4 == 0) && (!states || rows * T::NX % 4 == 0) && (!sensors || rows * T::NS % 4 == 0));
+  MatPlants q;
+  q.vec_ok = (H % JH_MAT_TS == 0) && offsets_ok && ((reinterpret_cast<uintptr_t>(controls) | reinterpret_cast<uintptr_t>(states) | reinterpret_cast<uintptr_t>(sensors)) & 15) == 0;
+  q.image = image_stride; q.x0_stride = x0_batched ? (long long)n * T::NX : 0; q.ctrl_stride = controls_shared ? 0 : rows * T::NU; q.plants = p;
+  hipLaunchKernelGGL((k_materialize<T, JH_MAT_TS, true>), dim3((n + kBlock - 1) / kBlock, G), dim3(kBlock), 0, st, images, x0, x0_batched, controls, n, H, states, sensors, q);
+  JH_HIP(hipGetLastError());
+  return JH_OK;
+}
+int jh_simple_materialize_plants(const jh_model* m, const float* images, long long image_stride, const jh_plant_axis& p, int G, const float* x0, int x0_batched, const float* controls,
+                                 int controls_shared, int n, int H, float* states, float* sensors, hipStream_t st) {
+  if (m->kind == JH_TASK_CARTPOLE) return launch_materialize_plants<Cartpole>(images, image_stride, p, G, x0, x0_batched, controls, controls_shared, n, H, states, sensors, st);
+  return launch_materialize_plants<CylinderPush>(images, image_stride, p, G, x0, x0_batched, controls, controls_shared, n, H, states, sensors, st);
 }

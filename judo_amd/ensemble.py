@@ -78,6 +78,14 @@ def check_task(task: Task, fr3: bool = False) -> None:
                          "plants at the cost of a plain plan step is judo_amd.fr3_randomized.make_fr3_randomized_controller")
 
 
+def _materialized_hint(why: str, fr3: bool = False) -> str:
+    """What serves a configuration this class refuses, behind the refusal: the controller of judo_amd.materialized keeps the materialise path (a plugin reward, hook or
+    optimizer, the running normaliser, more knots than the fused kernel holds) and rolls it out on the plants.  It has no sharded form and writes no candidate knots either."""
+    if fr3 or "sharded path" in why or "keep_candidates" in why:  # (fr3_pick has no materialise launch on plants)
+        return ""
+    return ".  judo_amd.materialized.make_materialized_ensemble_controller makes the controller that materialises the rollouts on the plants and scores them with Task.reward"
+
+
 class EnsembleController(Controller):
     """A `Controller` whose plan step rolls every candidate out on M plants and updates on the aggregated costs.  Everything else -- `update_states`, `action(t)`,
     `traces`, `max_opt_iters`, the three optimizers, the `none` / `min_max` normalisers, a live change of `num_rollouts` -- is the controller's own.
@@ -174,13 +182,13 @@ class EnsembleController(Controller):
     def _iteration_shape(self, world: int, nrm) -> str:
         why = self._ensemble_refusal(world, nrm)
         if why is not None:
-            raise ValueError(f"an ensemble controller runs its iteration as one jh_plan_step_ensemble call, which this configuration rules out ({why})")
+            raise ValueError(f"an ensemble controller runs its iteration as one jh_plan_step_ensemble call, which this configuration rules out ({why})" + _materialized_hint(why, self._fr3_ensemble))
         return "plan_step"
 
     def update_action(self) -> None:
         if not self.uses_fused_optimizer:
             raise ValueError("an ensemble controller runs its iteration as one jh_plan_step_ensemble call, which this configuration rules out "
-                             "(a plugin reward, hook or optimizer (uses_fused_cost is false): the members' costs come from the fused kernels alone)")
+                             "(a plugin reward, hook or optimizer (uses_fused_cost is false): the members' costs come from the fused kernels alone)" + _materialized_hint("", self._fr3_ensemble))
         super().update_action()
 
     def _plan_step(self, lib, b: _PlanBuffers, shape: str, noise_p: int, ldn: int, knots_out, W, shard: Shard, world: int, H: int, K: int, nu: int, stream,

@@ -55,6 +55,10 @@ def refuse_fr3_randomized(i: int, c: Controller, fleet: "ControllerFleet | None"
         raise ValueError(f"fleet member {i} is a {type(c).__name__} (judo_amd.spot_plants): its rollouts run on the plants of its own SpotPlantSet "
                          "(jh_policy_rollout_plants), and a fleet's one policy rollout runs every member's rows on ONE model image -- it would plan this member on plant 0 "
                          "alone.  No fleet takes such a member yet: run its update_action() on its own")
+    if getattr(c, "_materialized_plants", False):
+        raise ValueError(f"fleet member {i} is a {type(c).__name__} (judo_amd.materialized): its rollouts are materialised on the plants of its own GpuModelSet "
+                         "(jh_rollout_materialize_plants) and scored by Task.reward, and a fleet's one launch runs the fused cost of every member on ONE plant each -- it "
+                         "would plan this member on plant 0 alone.  No fleet takes such a member yet: run its update_action() on its own")
 
 
 class _MemberBuffers:

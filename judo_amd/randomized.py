@@ -79,6 +79,14 @@ def check_task(task: Task, fr3: bool = False) -> None:
                          "judo_amd.fr3_randomized_fleet.make_fr3_randomized_fleet a fleet of them")
 
 
+def _materialized_hint(why: str, fr3: bool = False) -> str:
+    """What serves a configuration this class refuses, behind the refusal: the controller of judo_amd.materialized keeps the materialise path (a plugin reward, hook or
+    optimizer, the running normaliser, more knots than the fused kernel holds) and rolls it out on the plants.  It has no sharded form and writes no candidate knots either."""
+    if fr3 or "sharded path" in why or "keep_candidates" in why:  # (fr3_pick has no materialise launch on plants)
+        return ""
+    return ".  judo_amd.materialized.make_materialized_randomized_controller makes the controller that materialises the rollouts on the plants and scores them with Task.reward"
+
+
 class RandomizedController(Controller):
     """A `Controller` whose plan step rolls block g of its candidates out on plant `assignment[g]` and updates on the N costs.  Everything else -- `update_states`,
     `action(t)`, `traces`, `max_opt_iters`, the three optimizers, the `none` / `min_max` normalisers -- is the controller's own.
@@ -189,13 +197,13 @@ class RandomizedController(Controller):
     def _iteration_shape(self, world: int, nrm) -> str:
         why = self._randomized_refusal(world, nrm)
         if why is not None:
-            raise ValueError(f"a randomised controller runs its iteration as one jh_plan_step_randomized call, which this configuration rules out ({why})")
+            raise ValueError(f"a randomised controller runs its iteration as one jh_plan_step_randomized call, which this configuration rules out ({why})" + _materialized_hint(why, self._fr3_randomized))
         return "plan_step"
 
     def update_action(self) -> None:
         if not self.uses_fused_optimizer:
             raise ValueError("a randomised controller runs its iteration as one jh_plan_step_randomized call, which this configuration rules out "
-                             "(a plugin reward, hook or optimizer (uses_fused_cost is false): the plants' costs come from the fused kernels alone)")
+                             "(a plugin reward, hook or optimizer (uses_fused_cost is false): the plants' costs come from the fused kernels alone)" + _materialized_hint("", self._fr3_randomized))
         if self.optimizer_cfg.num_rollouts > 0 and self.optimizer_cfg.num_rollouts % len(self._assignment) != 0:  # (a live change of num_rollouts)
             raise ValueError(f"num_rollouts % blocks != 0: {self.optimizer_cfg.num_rollouts} rollouts do not split into {len(self._assignment)} equal blocks")
         super().update_action()
