@@ -655,10 +655,22 @@ int jh_policy_rollout_plants(const jh_policy* p, jh_tree_set* set, int B, int G,
  * (its x0 and controls), whatever the latency mode the launch's G * n rollouts select and whichever blocks stand beside it.
  * JH_ERR_INVALID before anything is enqueued, jh_last_error naming the argument: a null pointer (set, plant_of_block, x0, controls); states and sensors both NULL; G
  * outside 1..JH_MAX_FLEET_PLANT_BLOCKS; n or H < 1; a table entry outside [0, M) (named with its block); G * n beyond the 2^31 - 1 rollouts of one launch.
- * JH_ERR_UNSUPPORTED: a set of fr3_pick models (jh_fr3_model_set_create) -- the arm kernel has no materialise launch on plants yet --, or a member 0 switched to
- * another kernel generation. */
+ * JH_ERR_UNSUPPORTED: a set of fr3_pick models (jh_fr3_model_set_create) -- behind this entry the arm kernel has no materialise launch on plants;
+ * jh_fr3_rollout_materialize_plants below is that launch --, or a member 0 switched to another kernel generation. */
 int jh_rollout_materialize_plants(const jh_model_set* set, const int* plant_of_block, int G, int n, const float* x0, int x0_batched, const float* controls, int controls_shared,
                                   int H, float* states, float* sensors, void* stream);
+
+/* ---- jh_rollout_materialize_plants for a set of fr3_pick models (jh_fr3_model_set_create): the cooperative arm kernel's materialise launch on plants, behind an entry of
+ * its own as every fr3 form is.  The arguments, their shapes and their limits are those of jh_rollout_materialize_plants; both builds of the arm kernel (the shipped
+ * pairs, the arm's own pairs) serve it, chosen by the set's member 0 as for jh_rollout_materialize.  Grid (waves of a block, G): blocks never share a wave, and an idle
+ * row of a block's last wave ends at its own block's last rollout.  The int section is member 0's own, which an fr3 set's members share word for word.  The launch has
+ * no phase: materialise mode evaluates every distance sensor and computes no cost (jh_task_reward takes the phase).  The counters are member 0's (jh_model_stats).
+ * Contract: rows [g * n, (g + 1) * n) of states and sensors are bit for bit what jh_rollout_materialize writes on plant plant_of_block[g]'s own jh_model for those n rows
+ * (its x0 and controls), whatever the latency mode the launch's G * n rollouts select and whichever blocks stand beside it.
+ * JH_ERR_INVALID before anything is enqueued, jh_last_error naming the argument: as for jh_rollout_materialize_plants.
+ * JH_ERR_UNSUPPORTED: a set that is not of fr3_pick models (jh_rollout_materialize_plants rolls it out). */
+int jh_fr3_rollout_materialize_plants(const jh_model_set* set, const int* plant_of_block, int G, int n, const float* x0, int x0_batched, const float* controls, int controls_shared,
+                                      int H, float* states, float* sensors, void* stream);
 
 #ifdef __cplusplus
 }

@@ -1342,19 +1342,24 @@ extern "C" int jh_rollout_materialize(const jh_model* m, const float* x0, int x0
 
 // jh_rollout_materialize on the plants of a model set (include/judo_amd.h): G blocks of n rollouts in ONE launch on grid (workgroups of a block, G), block g on image
 // plant_of_block[g].  The table travels in the kernel arguments (jh_plant_axis); the int section is the set's one copy, by the rule the plan steps on a set use.  Every
-// check stands in front of the first enqueue.
-extern "C" int jh_rollout_materialize_plants(const jh_model_set* set, const int* plant_of_block, int G, int n, const float* x0, int x0_batched, const float* controls, int controls_shared,
-                                             int H, float* states, float* sensors, void* stream) {
-  const char* who = "rollout_materialize_plants";
+// check stands in front of the first enqueue.  Both entries' body: `fr3_entry` is jh_fr3_rollout_materialize_plants, which takes an fr3_pick set and no other; the
+// general entry takes every other family's.
+static int materialize_plants_entry(const char* who, bool fr3_entry, const jh_model_set* set, const int* plant_of_block, int G, int n, const float* x0, int x0_batched, const float* controls,
+                                    int controls_shared, int H, float* states, float* sensors, void* stream) {
 #define JH_MP_PTR(p) JH_REQUIRE((p) != nullptr, "%s: " #p " is a null pointer", who)
   JH_MP_PTR(set); JH_MP_PTR(plant_of_block); JH_MP_PTR(x0); JH_MP_PTR(controls);
 #undef JH_MP_PTR
   JH_REQUIRE(states || sensors, "%s: states and sensors are both null: nothing to compute", who);
   const jh_model* m = set->m0;
   const int M = set->B;
-  if (m->kind == JH_TASK_FR3_PICK) {
-    jh_set_error("%s: an fr3_pick set: the cooperative arm kernel has no materialise launch on plants yet (its batched instantiations are fused launches); "
-                 "jh_rollout_materialize on a member's own handle rolls one plant out", who);
+  if (!fr3_entry && m->kind == JH_TASK_FR3_PICK) {
+    // (the wording is pinned by the tests of this entry; what serves the set stands behind it)
+    jh_set_error("%s: an fr3_pick set: behind this entry the cooperative arm kernel has no materialise launch on plants yet; "
+                 "jh_fr3_rollout_materialize_plants rolls an fr3_pick set out, and jh_rollout_materialize on a member's own handle rolls one plant out", who);
+    return JH_ERR_UNSUPPORTED;
+  }
+  if (fr3_entry && m->kind != JH_TASK_FR3_PICK) {
+    jh_set_error("%s: not an fr3_pick set: this entry is the cooperative arm kernel's; jh_rollout_materialize_plants rolls every other family's set out", who);
     return JH_ERR_UNSUPPORTED;
   }
   JH_REQUIRE(M <= JH_MAX_ENSEMBLE, "%s: a set of %d members exceeds JH_MAX_ENSEMBLE = %d", who, M, JH_MAX_ENSEMBLE);
@@ -1373,6 +1378,18 @@ extern "C" int jh_rollout_materialize_plants(const jh_model_set* set, const int*
   jh_rollout_batch rb = {set->d_images, (long long)set->stride, set->tables ? m->d_i : set->d_i_plain, G, 0, 0};
   rb.plants = plants;
   return eb->materialize_plants(m, rb, x0, x0_batched, controls, controls_shared, n, H, states, sensors, st);
+}
+
+extern "C" int jh_rollout_materialize_plants(const jh_model_set* set, const int* plant_of_block, int G, int n, const float* x0, int x0_batched, const float* controls, int controls_shared,
+                                             int H, float* states, float* sensors, void* stream) {
+  return materialize_plants_entry("rollout_materialize_plants", false, set, plant_of_block, G, n, x0, x0_batched, controls, controls_shared, H, states, sensors, stream);
+}
+
+// The same call for an fr3_pick set (include/judo_amd.h): the cooperative arm kernel's materialise launch on plants, behind an entry of its own as every fr3 form is.  The
+// argument checks are the one function above; the int section is the model's own (fr3 sets share it word for word).
+extern "C" int jh_fr3_rollout_materialize_plants(const jh_model_set* set, const int* plant_of_block, int G, int n, const float* x0, int x0_batched, const float* controls, int controls_shared,
+                                                 int H, float* states, float* sensors, void* stream) {
+  return materialize_plants_entry("fr3_rollout_materialize_plants", true, set, plant_of_block, G, n, x0, x0_batched, controls, controls_shared, H, states, sensors, stream);
 }
 
 extern "C" int jh_task_reward(const jh_model* m, const float* states, const float* sensors, const float* controls, const float* tp, int phase, int N,

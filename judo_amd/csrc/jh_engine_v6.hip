@@ -436,9 +436,13 @@ __device__ __forceinline__ void geom_pose3(const RS6& S, const float* gf, int bo
 // blockIdx.y.  Controller c's blocks, noise and images lie c times the record's three strides behind controller 0's; the (controller, problem) pair c * gridDim.y + b owns the
 // costs, trace and overflow rows and names the plant table's entry.  The phase word is read behind both offsets, so with `batch_blk` 0 it is the controller's own.  All
 // strides 0 and gridDim.z == 1: every launch without that axis.
+// BATCH with MATERIALIZE (jh_fr3_rollout_materialize_plants): the blocks of a materialise launch, each on a plant of a model set -- the same grid in two dimensions and the
+// same by-value table; a block owns its controls, x0 rows, output rows and overflow rows (the arm at the top of the kernel).
 struct NoPlantAxis {};
 // The batched instantiation's last argument, by value: the controller axis' strides (floats) and the plant axis (jh_internal.h).
 struct BatchAxes { long long blk_c = 0, noise_c = 0, image_c = 0; jh_plant_axis plants; };
+// The batched materialise instantiation's (jh_fr3_rollout_materialize_plants): the plant axis and no controller axis.
+struct PlantAxisOnly { jh_plant_axis plants; };
 template <bool MATERIALIZE, bool BATCH = false>
 __global__ __launch_bounds__(WAVE) __attribute__((amdgpu_waves_per_eu(WPE, WPE))) void k_fr3_v6(const float* __restrict__ gF, const int* __restrict__ gI, const float* __restrict__ x0, int x0_batched,
                                                     const float* __restrict__ nominal, const float* __restrict__ noise, int ldn,
@@ -447,9 +451,20 @@ __global__ __launch_bounds__(WAVE) __attribute__((amdgpu_waves_per_eu(WPE, WPE))
                                                     float* __restrict__ costs, float* __restrict__ knots_out, const float* __restrict__ controls,
                                                     float* __restrict__ states, float* __restrict__ sensors, int* __restrict__ stats, int dshift, float* __restrict__ trace, float* __restrict__ ovf_all,
                                                     long long batch_blk, long long batch_noise, int o_phase, long long batch_image,
-                                                    std::conditional_t<BATCH, BatchAxes, NoPlantAxis> axes) {
-  static_assert(!BATCH || !MATERIALIZE, "batched launches are fused launches");
-  if constexpr (BATCH) {
+                                                    std::conditional_t<BATCH, std::conditional_t<MATERIALIZE, PlantAxisOnly, BatchAxes>, NoPlantAxis> axes) {
+  static_assert(!(BATCH && MATERIALIZE) || std::is_same_v<decltype(axes), PlantAxisOnly>, "the materialise launch on plants has no controller axis: its record is the plant table alone");
+  if constexpr (BATCH && MATERIALIZE) {
+    // Materialise mode on a plant axis (jh_fr3_rollout_materialize_plants), grid (waves of a block, G): block blockIdx.y is N rollouts of its own on the image its table
+    // entry names.  The strides are the block's, as in k_leap_v5 -- `batch_blk` floats to the next block's controls (0: every block reads rows [0, N)), `batch_noise` to
+    // its x0 rows (0: one state for the launch) -- and the outputs and overflow rows are N rollouts apart.  No controller axis (gridDim.z == 1: the record is the table
+    // alone) and no phase word (materialise mode computes no cost): below, N is the block's n and the code is the single launch's.
+    const long long pb = blockIdx.y;
+    gF += jh_plant_of(axes.plants, (int)pb, (int)pb) * batch_image;
+    controls += pb * batch_blk; x0 += pb * batch_noise;
+    if (states) states += pb * N * H * NX;
+    if (sensors) sensors += pb * N * H * NS;
+    if (ovf_all) ovf_all += pb * N * (NOVF * RAW_F);
+  } else if constexpr (BATCH) {
     // `pr`: the (controller, problem) pair, which owns the costs, trace and overflow rows; pb wherever gridDim.z == 1
     const long long pb = blockIdx.y, pc = blockIdx.z, pr = pc * gridDim.y + pb;
     const long long ob = pb * batch_blk + pc * axes.blk_c;
@@ -1396,8 +1411,35 @@ static int rollout_cost_batch(const jh_model* m, const jh_rollout_args& a, const
   return jh_launch_done(ovf, st);
 }
 
+// (Behind the fused batched launch for the same reason.)  Materialise mode on a plant axis (jh_fr3_rollout_materialize_plants): s.B blocks of n rollouts on the grid (waves
+// of a block, s.B), block g on image s.plants[g] of s.images and on the model's own int section, which an fr3 set's members share word for word.  x0 is one state, or one
+// per row of the s.B * n; the controls are a block's own n rows, or rows [0, n) for every block.  The latency shift is chosen from s.B * n, the rollouts of the launch (the
+// bits do not depend on it); a block's rows never share a wave with another block's, and a dead row of a block's last wave recomputes that block's last rollout.  Of `s`
+// the launch reads images, image_stride, B, C and plants; a controller axis is refused.
+static int materialize_plants(const jh_model* m, const jh_rollout_batch& s, const float* x0, int x0_batched, const float* controls, int controls_shared, int n, int H, float* states,
+                              float* sensors, hipStream_t st) {
+  const char* who = "fr3_rollout_materialize_plants";
+  if (!JH_V6_NAME(jh_model_is_fr3)(m)) {
+    if (JH_V6_SELF) jh_set_error("%s: the self-collision build of the cooperative arm kernel is instantiated for fr3_pick with its arm pairs only", who);
+    else jh_set_error("%s: the cooperative arm kernel is instantiated for fr3_pick only; an image with pairs between arm bodies runs on its self-collision build", who);
+    return JH_ERR_UNSUPPORTED;
+  }
+  JH_REQUIRE(s.images != nullptr && s.image_stride >= 0, "%s: the fr3 kernel's launch on plants needs the set's images (image_stride=%lld)", who, s.image_stride);
+  JH_REQUIRE(s.C == 1, "%s: the fr3 kernel's materialise launch on plants has no controller axis (C=%d)", who, s.C);
+  const long long rollouts = (long long)s.B * n;
+  JH_REQUIRE(s.B >= 1 && s.B <= JH_MAX_FLEET_PLANT_BLOCKS && n >= 1 && rollouts <= 0x7fffffffll, "%s: G * n = %lld rollouts exceed one launch (G=%d)", who, rollouts, s.B);
+  const int dshift = jh_latency_shift((int)rollouts, RPW), per_wave = RPW >> dshift, grid = (n + per_wave - 1) / per_wave;
+  float* ovf = jh_launch_scratch(m, (size_t)rollouts * NOVF * RAW_F * sizeof(float), st);  // (every block's rows; nullptr: the LDS capacity alone, drops and the fallback counted)
+  PlantAxisOnly axes;
+  axes.plants = s.plants;
+  hipLaunchKernelGGL((k_fr3_v6<true, true>), dim3(grid, s.B), dim3(WAVE), 0, st, s.images, m->d_i, x0, x0_batched, nullptr, nullptr, 0, nullptr, nullptr, nullptr, nullptr, 0, n, 0,
+                     H, 0, nullptr, nullptr, controls, states, sensors, m->d_stats, dshift, nullptr, ovf, controls_shared ? 0ll : (long long)n * H * NU, x0_batched ? (long long)n * NX : 0ll,
+                     -1, s.image_stride, axes);
+  return jh_launch_done(ovf, st);
+}
+
 // This build's row of the table (jh_internal.h); the contact capacity is the LDS pool plus the overflow row.  Host pass only: a const object with a constant initialiser
 // would be emitted into the code object as well.
 #ifndef __HIP_DEVICE_COMPILE__
-const jh_engine_build JH_V6_NAME(jh_engine6_build) = {JH_V6_SELF ? "fr3, self-collision" : "fr3", JH_V6_NAME(jh_model_is_fr3), rollout_cost, rollout_cost_batch, JH_V6_NAME(jh_engine6_materialize), NCP + NOVF};
+const jh_engine_build JH_V6_NAME(jh_engine6_build) = {JH_V6_SELF ? "fr3, self-collision" : "fr3", JH_V6_NAME(jh_model_is_fr3), rollout_cost, rollout_cost_batch, JH_V6_NAME(jh_engine6_materialize), NCP + NOVF, materialize_plants};
 #endif

@@ -164,8 +164,9 @@ struct jh_engine_build {
   int (*rollout_cost_batch)(const jh_model* m, const jh_rollout_args& a, const jh_rollout_batch& s, hipStream_t st);  // null: the build has no batched launch (none of the shipped rows; fr3: a phase per problem, jh_rollout_batch::o_phase)
   int (*materialize)(const jh_model* m, const float* x0, int x0_batched, const float* controls, int N, int H, float* states, float* sensors, hipStream_t st);
   int contact_capacity;                   // contacts a rollout can hold (jh_model_limits out[3]), from the build's own constants
-  // materialise mode on a plant axis (jh_rollout_materialize_plants): s.B blocks of n rollouts, block g on image s.plants[g] of s.images; of `s` the launch reads images,
-  // image_stride, ints, B and plants.  null: the build has no such launch (the fr3 rows)
+  // materialise mode on a plant axis (jh_rollout_materialize_plants; the fr3 rows: jh_fr3_rollout_materialize_plants): s.B blocks of n rollouts, block g on image
+  // s.plants[g] of s.images; of `s` the launch reads images, image_stride, ints, B and plants -- the fr3 rows the model's own int section in place of `ints`, and C, which
+  // they refuse unless it is 1.  null: the build has no such launch (none of the shipped rows)
   int (*materialize_plants)(const jh_model* m, const jh_rollout_batch& s, const float* x0, int x0_batched, const float* controls, int controls_shared, int n, int H, float* states,
                             float* sensors, hipStream_t st) = nullptr;
 };

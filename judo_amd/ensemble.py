@@ -165,6 +165,10 @@ class EnsembleController(Controller):
         return -self.member_costs.astype(np.float64)
 
     # ---- the plan step -----------------------------------------------------------------------------------------------------------------------------
+    def _hint(self, why: str) -> str:
+        """What a refusal of the one-call shape adds: the maker that serves the configuration (`FR3EnsembleController` names the arm's)."""
+        return _materialized_hint(why, self._fr3_ensemble)
+
     def _ensemble_refusal(self, world: int, nrm) -> str | None:
         """Why this controller's iteration is not the one-call shape, or None."""
         if world > 1 or self.force_shard_path:
@@ -182,13 +186,13 @@ class EnsembleController(Controller):
     def _iteration_shape(self, world: int, nrm) -> str:
         why = self._ensemble_refusal(world, nrm)
         if why is not None:
-            raise ValueError(f"an ensemble controller runs its iteration as one jh_plan_step_ensemble call, which this configuration rules out ({why})" + _materialized_hint(why, self._fr3_ensemble))
+            raise ValueError(f"an ensemble controller runs its iteration as one jh_plan_step_ensemble call, which this configuration rules out ({why})" + self._hint(why))
         return "plan_step"
 
     def update_action(self) -> None:
         if not self.uses_fused_optimizer:
             raise ValueError("an ensemble controller runs its iteration as one jh_plan_step_ensemble call, which this configuration rules out "
-                             "(a plugin reward, hook or optimizer (uses_fused_cost is false): the members' costs come from the fused kernels alone)" + _materialized_hint("", self._fr3_ensemble))
+                             "(a plugin reward, hook or optimizer (uses_fused_cost is false): the members' costs come from the fused kernels alone)" + self._hint(""))
         super().update_action()
 
     def _plan_step(self, lib, b: _PlanBuffers, shape: str, noise_p: int, ldn: int, knots_out, W, shard: Shard, world: int, H: int, K: int, nu: int, stream,

@@ -38,6 +38,16 @@ def check_self_collision(descriptions: Sequence[dict], self_collision: bool) -> 
             raise ValueError(f"description {i} differs from the task in self_collision: derive the descriptions from FR3Pick(self_collision={bool(self_collision)}).desc")
 
 
+def materialized_hint(why: str, kind: str) -> str:
+    """What serves a configuration the fused fr3 classes refuse, behind the refusal: the controller of judo_amd.fr3_materialized keeps the materialise path (a plugin
+    reward, hook or optimizer, the running normaliser, more knots than the fused kernel holds) and rolls it out on the plants.  It has no sharded form and writes no
+    candidate knots either.  `kind`: "ensemble" or "randomized"."""
+    if "sharded path" in why or "keep_candidates" in why:
+        return ""
+    return (f".  judo_amd.fr3_materialized.make_fr3_materialized_{kind}_controller makes the controller that materialises the arm's rollouts on the plants "
+            "(jh_fr3_rollout_materialize_plants) and scores them with Task.reward")
+
+
 class FR3EnsembleController(EnsembleController):
     """An `EnsembleController` of an `FR3Pick` task.  `descriptions` derive from the task's own (`models.scaled_description(task.desc, ...)`), so they carry the
     `self_collision` key of its build."""
@@ -56,6 +66,9 @@ class FR3EnsembleController(EnsembleController):
         self._check_task(task)
         check_self_collision(descriptions, task.self_collision)
         super().__init__(controller_config, task, optimizer, descriptions, worst=worst, device=device)
+
+    def _hint(self, why: str) -> str:
+        return materialized_hint(why, "ensemble")
 
     def _entry_args(self, W, N: int, H: int, K: int) -> tuple:
         return (_lib.ptr(W), int(self.task.phase), N, H, K)  # (the phase `pre_rollout` chose in this iteration, as `Controller._plan_step` passes it to jh_plan_step)

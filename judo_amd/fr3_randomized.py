@@ -17,6 +17,7 @@ import torch
 
 from judo_amd import _lib
 from judo_amd.config import ControllerConfig
+from judo_amd.fr3_ensemble import materialized_hint
 from judo_amd.optimizers import get_registered_optimizers
 from judo_amd.randomized import RandomizedController, check_task
 from judo_amd.tasks import FR3Pick, Task
@@ -42,6 +43,9 @@ class FR3RandomizedController(RandomizedController):
             if bool(d.get("self_collision")) != bool(task.self_collision):
                 raise ValueError(f"description {i} differs from the task in self_collision: derive the descriptions from FR3Pick(self_collision={bool(task.self_collision)}).desc")
         super().__init__(controller_config, task, optimizer, descriptions, blocks=blocks, weights=weights, device=device)
+
+    def _hint(self, why: str) -> str:
+        return materialized_hint(why, "randomized")
 
     def _entry_args(self, W, N: int, H: int, K: int) -> tuple:
         return (_lib.ptr(W), int(self.task.phase), N, H, K)  # (the phase `pre_rollout` chose in this iteration, as `Controller._plan_step` passes it to jh_plan_step)

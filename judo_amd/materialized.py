@@ -13,7 +13,8 @@ candidates iteration of a plugin optimizer, numpy-only rewards) works unchanged.
   `MaterializedRandomizedController`  N candidates in G blocks of N / G, block g on plant `assignment[g]`, one reward call on the N rows: the rollouts of a plain plan step.
 
 The fused classes stay the fast path for the shipped costs.  Member 0 is the nominal plant: the controller's `model`, `last_rollout` and the traces.  Families:
-cartpole, cylinder_push and the leap family.  The reference has no counterpart."""
+cartpole, cylinder_push and the leap family; fr3_pick has the two subclasses of judo_amd/fr3_materialized.py, whose set goes through the arm's own entry.  The reference
+has no counterpart."""
 
 from __future__ import annotations
 
@@ -42,7 +43,9 @@ def check_task(task: Task, kind: str = "ensemble") -> None:
     if task.desc.get("family", task.desc["task"]) == "fr3_pick":
         raise ValueError(f"fr3_pick has no materialise launch on plants: the cooperative arm kernel's batched instantiations are fused launches, and "
                          f"jh_rollout_materialize_plants refuses an fr3_pick set.  The shipped cost plans against perturbed plants in "
-                         f"judo_amd.fr3_{kind}.make_fr3_{kind}_controller")
+                         f"judo_amd.fr3_{kind}.make_fr3_{kind}_controller; a plugin fr3_pick task (its own reward or hooks, a plugin optimizer, the running normaliser) "
+                         f"plans against them in judo_amd.fr3_materialized.make_fr3_materialized_{kind}_controller, whose rollouts go through the arm's own entry "
+                         f"(jh_fr3_rollout_materialize_plants)")
 
 
 class _MaterializedPlantController(Controller):

@@ -180,6 +180,10 @@ class RandomizedController(Controller):
             self.model = self.rollout_backend.model = model
 
     # ---- the plan step -----------------------------------------------------------------------------------------------------------------------------
+    def _hint(self, why: str) -> str:
+        """What a refusal of the one-call shape adds: the maker that serves the configuration (`FR3RandomizedController` names the arm's)."""
+        return _materialized_hint(why, self._fr3_randomized)
+
     def _randomized_refusal(self, world: int, nrm) -> str | None:
         """Why this controller's iteration is not the one-call shape, or None."""
         if world > 1 or self.force_shard_path:
@@ -197,13 +201,13 @@ class RandomizedController(Controller):
     def _iteration_shape(self, world: int, nrm) -> str:
         why = self._randomized_refusal(world, nrm)
         if why is not None:
-            raise ValueError(f"a randomised controller runs its iteration as one jh_plan_step_randomized call, which this configuration rules out ({why})" + _materialized_hint(why, self._fr3_randomized))
+            raise ValueError(f"a randomised controller runs its iteration as one jh_plan_step_randomized call, which this configuration rules out ({why})" + self._hint(why))
         return "plan_step"
 
     def update_action(self) -> None:
         if not self.uses_fused_optimizer:
             raise ValueError("a randomised controller runs its iteration as one jh_plan_step_randomized call, which this configuration rules out "
-                             "(a plugin reward, hook or optimizer (uses_fused_cost is false): the plants' costs come from the fused kernels alone)" + _materialized_hint("", self._fr3_randomized))
+                             "(a plugin reward, hook or optimizer (uses_fused_cost is false): the plants' costs come from the fused kernels alone)" + self._hint(""))
         if self.optimizer_cfg.num_rollouts > 0 and self.optimizer_cfg.num_rollouts % len(self._assignment) != 0:  # (a live change of num_rollouts)
             raise ValueError(f"num_rollouts % blocks != 0: {self.optimizer_cfg.num_rollouts} rollouts do not split into {len(self._assignment)} equal blocks")
         super().update_action()

@@ -72,7 +72,7 @@ class GpuRolloutBackend(RolloutBackend):
 
     def rollout_plants_device(self, model_set: GpuModelSet, plant_of_block, x0: torch.Tensor, controls: torch.Tensor, shared_controls: bool = False,
                               want_states: bool = True, want_sensors: bool = True):
-        """`rollout_device` on the plants of a `GpuModelSet` (`jh_rollout_materialize_plants`, one launch): G = len(plant_of_block) blocks of n rollouts, block g -- rows
+        """`rollout_device` on the plants of a `GpuModelSet` (`jh_rollout_materialize_plants`, or `jh_fr3_rollout_materialize_plants` for an fr3_pick set; one launch): G = len(plant_of_block) blocks of n rollouts, block g -- rows
         [g * n, (g + 1) * n) of the outputs -- on plant `plant_of_block[g]`.  controls are (G * n, T, nu), or with `shared_controls` (n, T, nu), which every block rolls
         out; x0 is (nq+nv,) or (G * n, nq+nv).  A block's rows are bit for bit `rollout_device` on that plant's own model."""
         table = check_plant_table(plant_of_block, len(model_set))
@@ -96,9 +96,11 @@ class GpuRolloutBackend(RolloutBackend):
         controls = controls.to(torch.float32).contiguous()
         states = torch.empty((G * n, H, gm.nx), dtype=torch.float32, device=gm.device) if want_states else None
         sensors = torch.empty((G * n, H, gm.ns), dtype=torch.float32, device=gm.device) if want_sensors else None
-        st = _lib.lib().jh_rollout_materialize_plants(model_set.handle, (C.c_int * G)(*table), G, n, _lib.ptr(x0), batched, _lib.ptr(controls), int(bool(shared_controls)), H,
-                                                      _lib.ptr(states), _lib.ptr(sensors), current_stream_ptr())
-        _lib.check(st, "jh_rollout_materialize_plants")
+        # (an fr3_pick set has an entry of its own, as every fr3 form has: the cooperative arm kernel's launch on plants)
+        entry = "jh_fr3_rollout_materialize_plants" if getattr(model_set, "fr3", False) else "jh_rollout_materialize_plants"
+        st = getattr(_lib.lib(), entry)(model_set.handle, (C.c_int * G)(*table), G, n, _lib.ptr(x0), batched, _lib.ptr(controls), int(bool(shared_controls)), H,
+                                        _lib.ptr(states), _lib.ptr(sensors), current_stream_ptr())
+        _lib.check(st, entry)
         return states, sensors
 
     def rollout_plants(self, model_set: GpuModelSet, plant_of_block, x0: np.ndarray, controls: np.ndarray, last_policy_output: np.ndarray | None = None,

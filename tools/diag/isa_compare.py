@@ -23,7 +23,7 @@ def kernels(co):
         m = re.match(r"^[0-9a-f]* ?<(.*)>:$", line)
         if m:
             cur = m.group(1); ks[cur] = []
-        elif cur is not None and line.strip():
+        elif cur is not None and line.strip() and line.strip() != "...":  # ("...": the zero padding up to the next kernel's alignment, behind s_endpgm -- the last kernel of a code object has none)
             ks[cur].append(re.sub(r"\s+", " ", line.split("//")[0].strip()))  # (the comment holds the address and the encoding)
     return ks, len(d.splitlines())
 
