@@ -980,16 +980,9 @@ def make_controller(init_task: str, init_optimizer: str, device: torch.device | 
 def make_controller_for(task: Task, init_optimizer: str, device: torch.device | None = None, group: Any = None, policy_share: Any = None) -> Controller:
     """The same construction around a task INSTANCE (one built with constructor arguments, e.g. `CaltechLeapCube(fingertips="cylinder")` or `FR3Pick(self_collision=True)`): the optimizer and
     controller overrides registered for the task's name."""
-    opts = get_registered_optimizers()
-    if init_optimizer not in opts:
-        raise ValueError(f"Optimizer {init_optimizer} not found in optimizer registry.")
-    opt_cls, opt_cfg_cls = opts[init_optimizer]
-    opt_cfg = opt_cfg_cls()
-    opt_cfg.set_override(task.name)
-    optimizer = opt_cls(opt_cfg, task.nu)
-    ctrl_cfg = ControllerConfig()
-    ctrl_cfg.set_override(task.name)
-    return Controller(ctrl_cfg, task, optimizer, device=device, group=group, policy_share=policy_share)
+    from judo_amd.plants import make_for  # (here: plants.py builds on this module)
+
+    return make_for(Controller, task, init_optimizer, device=device, group=group, policy_share=policy_share)
 
 
 assert set(SPLINE_KINDS) == {"zero", "linear", "cubic"}

@@ -616,6 +616,27 @@ static int phase_words(const char* who, const char* what, int B, const void* blk
   return JH_OK;
 }
 
+// What a packed block holds and, where every problem (or controller) has a block and a noise matrix of its own (`batched`), what lies between two of them: the checks of
+// every plan step with a problem axis, in one place.  (The output stride stays with the caller: the size of its record depends on the trace arguments.)
+struct jh_block_shape {
+  size_t bytes; int o_nominal, o_sigma, o_tp, o_lohi;  // a block's size; the float offsets of nominal | sigma | task params | bounds in it (x0 stands at 0)
+  int ldn, N, H, K;
+  bool batched = false; size_t stride_bytes = 0, noise_stride_floats = 0;
+};
+static int check_block_shape(const char* who, const jh_model* m, const jh_block_shape& s) {
+  JH_REQUIRE(s.N > 0 && s.H > 0 && s.K >= 1, "%s: N, H, K must be positive (N=%d H=%d K=%d)", who, s.N, s.H, s.K);
+  JH_REQUIRE(s.ldn >= s.N, "%s: ldn (%d) < N (%d)", who, s.ldn, s.N);
+  const int KU = s.K * m->nu, nx = m->nq + m->nv;
+  JH_REQUIRE(KU <= JH_MAX_KNOT_DIM, "%s: K*nu = %d exceeds %d", who, KU, JH_MAX_KNOT_DIM);
+  JH_REQUIRE(s.o_nominal >= 0 && s.o_sigma >= 0 && s.o_tp >= 0 && s.o_lohi >= 0, "%s: negative block offset", who);
+  const size_t need = sizeof(float) * (size_t)std::max(std::max(nx, s.o_nominal + KU), std::max(std::max(s.o_sigma + KU, s.o_tp + m->ntaskparam), s.o_lohi + 2 * m->nu));
+  JH_REQUIRE(s.bytes >= need, "%s: a block of %zu bytes does not hold x0 | nominal | sigma | task params | bounds at the given offsets (%zu bytes)", who, s.bytes, need);
+  if (!s.batched) return JH_OK;
+  JH_REQUIRE(s.stride_bytes >= s.bytes && s.stride_bytes % sizeof(float) == 0, "%s: blk_stride_bytes = %zu is smaller than a block (%zu bytes) or no multiple of 4", who, s.stride_bytes, s.bytes);
+  JH_REQUIRE(s.noise_stride_floats >= (size_t)KU * (size_t)s.ldn, "%s: noise_stride_floats = %zu is smaller than a problem's noise (K*nu*ldn = %zu)", who, s.noise_stride_floats, (size_t)KU * (size_t)s.ldn);
+  return JH_OK;
+}
+
 // B plan steps of one model as ONE call (include/judo_amd.h): the B packed blocks go up in one copy (or are read in place), the kernels take the problem from blockIdx.y and
 // reach its buffers through strides, and one completion mark stands behind all of them.  Problem 0's launch record is built by the single call's own checks
 // (jh_update_tail_args); the kernels derive problem b's from it.  `images` / `image_stride`: the float section the rollout kernels read for problem 0 and the floats to
@@ -632,17 +653,9 @@ static int plan_step_batch(const char* who, const jh_model* m, const float* imag
   if (m->kind == JH_TASK_LEAP_CUBE && m->kernel_gen != 3) { jh_set_error("%s: only kernel generation 3 of the leap family has a batched launch (this model runs %d)", who, m->kernel_gen); return JH_ERR_UNSUPPORTED; }
   JH_REQUIRE(B >= 1, "%s: B must be at least 1 (B=%d)", who, B);
   JH_REQUIRE(B <= 65535, "%s: B = %d exceeds the 65535 problems of a launch (the grid's second dimension)", who, B);
-  JH_REQUIRE(N > 0 && H > 0 && K >= 1, "%s: N, H, K must be positive (N=%d H=%d K=%d)", who, N, H, K);
   JH_REQUIRE(o_phase < 0 || K <= 8, "%s: the cooperative arm kernel keeps at most 8 knots per actuator in registers (K=%d)", who, K);
-  JH_REQUIRE(ldn >= N, "%s: ldn (%d) < N (%d)", who, ldn, N);
+  if (int rc = check_block_shape(who, m, {blk_bytes, o_nominal, o_sigma, o_tp, o_lohi, ldn, N, H, K, true, blk_stride_bytes, noise_stride_floats})) return rc;
   const int KU = K * m->nu;
-  JH_REQUIRE(KU <= JH_MAX_KNOT_DIM, "%s: K*nu = %d exceeds %d", who, KU, JH_MAX_KNOT_DIM);
-  const int nx = m->nq + m->nv;
-  JH_REQUIRE(o_nominal >= 0 && o_sigma >= 0 && o_tp >= 0 && o_lohi >= 0, "%s: negative block offset", who);
-  const size_t need = sizeof(float) * (size_t)std::max(std::max(nx, o_nominal + KU), std::max(std::max(o_sigma + KU, o_tp + m->ntaskparam), o_lohi + 2 * m->nu));
-  JH_REQUIRE(blk_bytes >= need, "%s: a block of %zu bytes does not hold x0 | nominal | sigma | task params | bounds at the given offsets (%zu bytes)", who, blk_bytes, need);
-  JH_REQUIRE(blk_stride_bytes >= blk_bytes && blk_stride_bytes % sizeof(float) == 0, "%s: blk_stride_bytes = %zu is smaller than a block (%zu bytes) or no multiple of 4", who, blk_stride_bytes, blk_bytes);
-  JH_REQUIRE(noise_stride_floats >= (size_t)KU * (size_t)ldn, "%s: noise_stride_floats = %zu is smaller than a problem's noise (K*nu*ldn = %zu)", who, noise_stride_floats, (size_t)KU * (size_t)ldn);
   int t_adr = 0, t_nfl = 0, t_cm = 0;
   if (trace) { trace_layout(m, &t_adr, &t_nfl, &t_cm); JH_REQUIRE(t_nfl > 0 && row_floats == H * t_nfl, "%s: row_floats = %d is not H x the model's %d trace floats per step (jh_model_trace_layout)", who, row_floats, t_nfl); }
   const int E_t = trace ? E : 0;
@@ -874,79 +887,140 @@ extern "C" int jh_plan_step_batch_phases_models(const jh_model_set* set, int B, 
                          noise_stride_floats, W, N, H, K, costs, trace, mode, lambda, k, tie_high, E, row_floats, colmajor, scratch, out, out_stride_floats, out_host_mark, timing, stream);
 }
 
-// ONE plan step against the M members of a model set (include/judo_amd.h): the batched rollout kernels on grid (workgroups, M) with the block and noise strides 0 -- every
-// member rolls out the same N candidates from the same block, on its own image, into its own row of member_costs -- then k_update_tail_ensemble, which aggregates the M
-// rows into `costs` and runs the single call's tail on them.  The records are built here: the batched entry points refuse strides below a block, rightly for what they do.
-// Always two launches (the closed-form models' one-launch form would roll a candidate out on one member per workgroup); no trace buffer, no knots_out.
-// `phase`: -1 for jh_plan_step_ensemble, which has none and refuses fr3_pick; 0..3 for jh_plan_step_ensemble_phase, which plans fr3_pick alone (checked by the entry):
-// the one controller's phase travels in the launch record, and every member's workgroups take it as the single launch takes its argument.
-static int plan_step_ensemble(const char* who, const jh_model_set* set, void* blk_dev, const void* blk_host, size_t blk_bytes, int o_nominal, int o_sigma, int o_tp, int o_lohi, const float* noise, int ldn,
-                              const float* W, int phase, int N, int H, int K, float* member_costs, float* costs, int worst, int mode, float lambda, int k, int tie_high, float* scratch, float* out,
-                              void* out_host_mark, void* const* timing, void* stream) {
-#define JH_ENS_PTR(p) JH_REQUIRE((p) != nullptr, "%s: " #p " is a null pointer", who)
-  JH_ENS_PTR(set); JH_ENS_PTR(blk_dev); JH_ENS_PTR(blk_host); JH_ENS_PTR(noise); JH_ENS_PTR(W); JH_ENS_PTR(member_costs); JH_ENS_PTR(costs); JH_ENS_PTR(scratch); JH_ENS_PTR(out);
-#undef JH_ENS_PTR
+// ---- plan steps on the plants of a model set (include/judo_amd.h): ONE launcher behind the eight entries, with three degrees of freedom ----
+//  - the kind, what the rollout launch's y axis means.  Ensemble: the M members -- every member rolls out the same N candidates from the same block (block and noise
+//    strides 0) on its own image into its own row of member_costs, and the tail aggregates the M rows into `costs` (the mean of the `worst` largest) before it updates.
+//    Randomised: G blocks of Nb = N / G rollouts, block g on plant plant_of_block[g] -- block stride 0, noise and cost strides Nb (block g's columns of the one noise
+//    matrix, its slice of `costs`), and the plant axis (jh_internal.h) with the rollout-index stride Nb, so that only global rollout 0 drops its noise, and the table, which
+//    travels in the kernel arguments; the tail is the plain one on the N costs.
+//  - the controller axis (`fleet`), blockIdx.z of the rollout launch: B controllers, each with its own block, noise, costs, output record and `worst` or table row
+//    (entry c * G + g), the strides of jh_plan_step_batch between them; a set of M members is shared by all controllers (image stride 0 on that axis), a set of B * M holds
+//    controller b's plants at b * M ...  The tail is then the batched one on (tail workgroups, B) with the two-level ticket and one completion word.  Without the axis the
+//    tails are the single call's (k_update_tail, k_update_tail_ensemble): not B = 1 of the batched ones.
+//  - the phase, fr3_pick's alone (the entries that take one refuse every other family): none, and fr3_pick is refused; `phase` 0..3, one controller's, which travels in the
+//    launch record to every member's or block's workgroups; or `o_phase`, the float offset of every controller's phase word in its block (the B words are checked on the host).
+// Always two launches (the closed-form models' one-launch form would roll a candidate out on one member per workgroup); no trace buffer, no knots_out.  Every check stands
+// in front of the first enqueue.
+struct jh_set_step {
+  const char* who; const jh_model_set* set;
+  void* blk_dev; const void* blk_host; jh_block_shape shape; const float *noise, *W;  // the block (blk_dev == blk_host: read in place, as jh_plan_step), its shape, noise and spline weights
+  float* costs; int mode; float lambda; int k, tie_high;                              // the update
+  float *scratch, *out; void* out_host_mark; void* const* timing; void* stream;
+  const char* fr3_hint = "";                                                          // what a non-phase entry names behind its refusal of fr3_pick
+  bool randomized = false;
+  float* member_costs = nullptr; const int* worst = nullptr;                          // ensemble: (B x) M x N costs; one `worst`, or B with a controller axis
+  const unsigned char* plant_of_block = nullptr; int G = 0;                           // randomised: the (B x) G table
+  bool fleet = false; int B = 1, M = 0; size_t out_stride_floats = 0;                 // the controller axis (its block and noise strides are the shape's)
+  int phase = -1, o_phase = -1;
+};
+
+static int plan_step_set(const jh_set_step& r) {
+  const char* who = r.who;
+  const jh_block_shape& d = r.shape;
+#define JH_SET_PTR(p) JH_REQUIRE(r.p != nullptr, "%s: " #p " is a null pointer", who)
+  JH_SET_PTR(set); JH_SET_PTR(blk_dev); JH_SET_PTR(blk_host); JH_SET_PTR(noise); JH_SET_PTR(W);
+  if (r.randomized) JH_SET_PTR(plant_of_block); else { JH_SET_PTR(member_costs); JH_SET_PTR(worst); }
+  JH_SET_PTR(costs); JH_SET_PTR(scratch); JH_SET_PTR(out);
+#undef JH_SET_PTR
+  const jh_model_set* set = r.set;
   const jh_model* m = set->m0;
-  const int M = set->B;
-  JH_REQUIRE(M <= JH_MAX_ENSEMBLE, "%s: a set of %d members exceeds JH_MAX_ENSEMBLE = %d", who, M, JH_MAX_ENSEMBLE);
-  JH_REQUIRE(worst >= 1 && worst <= M, "%s: worst = %d outside [1, M = %d]", who, worst, M);
-  if (m->kind == JH_TASK_FR3_PICK && phase < 0) { jh_set_error("%s: fr3_pick has no batched plan step (its phase is chosen per problem on the host) behind this entry: jh_plan_step_ensemble_phase takes the arm's phase and plans it against the set's plants; jh_plan_step_randomized_phase spreads one arm's candidates over them", who); return JH_ERR_UNSUPPORTED; }
-  if (m->kind != JH_TASK_FR3_PICK && phase >= 0) { jh_set_error("%s: a phase is fr3_pick's alone; jh_plan_step_ensemble plans this set", who); return JH_ERR_UNSUPPORTED; }
-  JH_REQUIRE(phase < 0 || K <= 8, "%s: the cooperative arm kernel keeps at most 8 knots per actuator in registers (K=%d)", who, K);
+  const int N = d.N, H = d.H, K = d.K, G = r.G, B = r.B, M = r.fleet ? r.M : set->B;
+  if (r.fleet) {
+    JH_REQUIRE(B >= 1 && B <= JH_MAX_ENSEMBLE_FLEET, "%s: B = %d outside [1, JH_MAX_ENSEMBLE_FLEET = %d]", who, B, JH_MAX_ENSEMBLE_FLEET);
+    JH_REQUIRE(M >= 1 && M <= JH_MAX_ENSEMBLE, "%s: M = %d outside [1, JH_MAX_ENSEMBLE = %d]", who, M, JH_MAX_ENSEMBLE);
+  } else JH_REQUIRE(M <= JH_MAX_ENSEMBLE, "%s: a set of %d members exceeds JH_MAX_ENSEMBLE = %d", who, M, JH_MAX_ENSEMBLE);
+  if (r.randomized) JH_REQUIRE(G >= 1 && G <= JH_MAX_PLANT_BLOCKS, "%s: G = %d outside [1, JH_MAX_PLANT_BLOCKS = %d]", who, G, JH_MAX_PLANT_BLOCKS);
+  if (r.randomized && r.fleet)
+    JH_REQUIRE(B * G <= JH_MAX_FLEET_PLANT_BLOCKS, "%s: B * G = %d * %d = %d exceeds JH_MAX_FLEET_PLANT_BLOCKS = %d (the bytes of the table in the kernel arguments)", who, B, G, B * G,
+               JH_MAX_FLEET_PLANT_BLOCKS);
+  if (r.fleet) JH_REQUIRE(set->B == M || set->B == B * M, "%s: a set of %d members is neither the M = %d plants every controller shares nor the B * M = %d plants of B = %d controllers", who, set->B, M, B * M, B);
+  if (!r.randomized && !r.fleet) JH_REQUIRE(r.worst[0] >= 1 && r.worst[0] <= M, "%s: worst = %d outside [1, M = %d]", who, r.worst[0], M);
+  if (!r.randomized && r.fleet) for (int b = 0; b < B; b++) JH_REQUIRE(r.worst[b] >= 1 && r.worst[b] <= M, "%s: controller %d: worst = %d outside [1, M = %d]", who, b, r.worst[b], M);
+  const bool phased = r.phase >= 0 || r.o_phase >= 0;
+  if (m->kind == JH_TASK_FR3_PICK && !phased) { jh_set_error("%s: fr3_pick has no batched plan step (its phase is chosen per problem on the host) behind this entry: %s", who, r.fr3_hint); return JH_ERR_UNSUPPORTED; }
+  JH_REQUIRE(!phased || K <= 8, "%s: the cooperative arm kernel keeps at most 8 knots per actuator in registers (K=%d)", who, K);
   if (m->kind == JH_TASK_LEAP_CUBE && m->kernel_gen != 3) { jh_set_error("%s: only kernel generation 3 of the leap family has a batched launch (this model runs %d)", who, m->kernel_gen); return JH_ERR_UNSUPPORTED; }
-  JH_REQUIRE(N > 0 && H > 0 && K >= 1, "%s: N, H, K must be positive (N=%d H=%d K=%d)", who, N, H, K);
-  JH_REQUIRE(ldn >= N, "%s: ldn (%d) < N (%d)", who, ldn, N);
+  if (int rc = check_block_shape(who, m, d)) return rc;
+  if (r.randomized) {
+    JH_REQUIRE(N % G == 0, "%s: N = %d is no multiple of G = %d (the blocks are N / G rollouts each)", who, N, G);
+    for (int e = 0; e < B * G; e++) {
+      if (r.fleet) JH_REQUIRE((int)r.plant_of_block[e] < M, "%s: plant_of_block[%d] = %d outside [0, M = %d): controller %d, block %d names no member of the set", who, e, (int)r.plant_of_block[e], M, e / G, e % G);
+      else JH_REQUIRE((int)r.plant_of_block[e] < M, "%s: plant_of_block[%d] = %d outside [0, M = %d): block %d names no member of the set", who, e, (int)r.plant_of_block[e], M, e);
+    }
+  }
   const int KU = K * m->nu;
-  JH_REQUIRE(KU <= JH_MAX_KNOT_DIM, "%s: K*nu = %d exceeds %d", who, KU, JH_MAX_KNOT_DIM);
-  const int nx = m->nq + m->nv;
-  JH_REQUIRE(o_nominal >= 0 && o_sigma >= 0 && o_tp >= 0 && o_lohi >= 0, "%s: negative block offset", who);
-  const size_t need = sizeof(float) * (size_t)std::max(std::max(nx, o_nominal + KU), std::max(std::max(o_sigma + KU, o_tp + m->ntaskparam), o_lohi + 2 * m->nu));
-  JH_REQUIRE(blk_bytes >= need, "%s: a block of %zu bytes does not hold x0 | nominal | sigma | task params | bounds at the given offsets (%zu bytes)", who, blk_bytes, need);
-  JH_REQUIRE(m->plan_step_launches != 1, "%s: one launch is forced (jh_model_set_plan_step_launches) but the ensemble's plan step is two launches", who);
-  JH_REQUIRE((long long)M * N <= 0x7fffffffll, "%s: M * N = %lld rollouts exceed one launch", who, (long long)M * N);
+  if (r.fleet) JH_REQUIRE(r.out_stride_floats >= 2 * (size_t)KU, "%s: out_stride_floats = %zu is smaller than an output record (nominal | sigma = %zu floats)", who, r.out_stride_floats, 2 * (size_t)KU);
+  JH_REQUIRE(m->plan_step_launches != 1, "%s: one launch is forced (jh_model_set_plan_step_launches) but %s plan step is two launches", who, r.randomized ? "the randomised" : "the ensemble's");
+  const long long rollouts = (long long)B * (r.randomized ? 1 : M) * N;
+  JH_REQUIRE(rollouts <= 0x7fffffffll, "%s: %s = %lld rollouts exceed one launch", who, !r.fleet ? "M * N" : r.randomized ? "B * N" : "B * M * N", rollouts);
   const bool closed = m->kind == JH_TASK_CARTPOLE || m->kind == JH_TASK_CYLINDER_PUSH;
   const jh_engine_build* eb = engine_build(m);
   if (!closed && !(eb && eb->rollout_cost_batch)) { jh_set_error("%s: no batched kernel for this model", who); return JH_ERR_UNSUPPORTED; }
-  unsigned* flag = (out_host_mark && out_host_mark != (void*)out) ? (unsigned*)out_host_mark : nullptr;  // (out_host_mark == out: the stream's event)
-  const float* b = (const float*)blk_dev;
-  jh_upd::TailArgs a;  // (the tail's own checks before anything is enqueued: mode, lambda, k)
-  if (int rc = jh_update_tail_args(who, costs, nullptr, b + o_nominal, noise, ldn, b + o_sigma, b + o_lohi, N, 0, K, m->nu, mode, lambda, k, tie_high, 0, nullptr, 0, 0, scratch, out, out + KU,
-                                   nullptr, nullptr, &a)) return rc;
-  hipStream_t st = (hipStream_t)stream;
-  if (blk_dev != blk_host) { if (int rc = jh_upload_async(blk_dev, blk_host, blk_bytes, stream)) return rc; }  // (blk_dev == blk_host: read in place, as jh_plan_step)
-  if (timing) JH_HIP(hipEventRecord((hipEvent_t)timing[0], st));
+  if (r.o_phase >= 0) { if (int rc = phase_words(who, "controller", B, r.blk_host, d.bytes, d.stride_bytes, r.o_phase)) return rc; }
+  unsigned* flag = (r.out_host_mark && r.out_host_mark != (void*)r.out) ? (unsigned*)r.out_host_mark : nullptr;  // (out_host_mark == out: the stream's event)
+  const float* b = (const float*)r.blk_dev;
+  jh_upd::TailArgs a;  // (controller 0's record; the tail's own checks before anything is enqueued: mode, lambda, k)
+  if (int rc = jh_update_tail_args(who, r.costs, nullptr, b + d.o_nominal, r.noise, d.ldn, b + d.o_sigma, b + d.o_lohi, N, 0, K, m->nu, r.mode, r.lambda, r.k, r.tie_high, 0, nullptr, 0, 0, r.scratch,
+                                   r.out, r.out + KU, nullptr, nullptr, &a)) return rc;
+  // the y axis of the rollout launch: Y problems of Nb rollouts, whose costs lie Nb and whose noise columns noise_y apart; the plant axis maps a problem to its image
+  const int Y = r.randomized ? G : M, Nb = r.randomized ? N / G : N;
+  const long long noise_y = r.randomized ? Nb : 0;
+  float* rollout_costs = r.randomized ? r.costs : r.member_costs;
+  jh_plant_axis plants;
+  if (r.randomized) { plants.n_stride = Nb; for (int e = 0; e < B * G; e++) jh_plant_set(plants, e, r.plant_of_block[e]); }
+  // ... and the z axis, the controllers (B = 1 and every stride 0 without it)
+  const long long blk_c = (long long)(d.stride_bytes / sizeof(float)), noise_c = (long long)d.noise_stride_floats, image_c = (!r.fleet || set->B == M) ? 0ll : (long long)M * (long long)set->stride;
+  hipStream_t st = (hipStream_t)r.stream;
+  if (r.blk_dev != r.blk_host) { if (int rc = jh_upload_async(r.blk_dev, r.blk_host, (size_t)(B - 1) * d.stride_bytes + d.bytes, r.stream)) return rc; }
+  if (r.timing) JH_HIP(hipEventRecord((hipEvent_t)r.timing[0], st));
   const unsigned expect = flag ? __atomic_load_n(flag, __ATOMIC_RELAXED) + 1u : 0u;
-  a.done_flag = flag; a.done_value = expect;
-  const int* ints = set->tables ? m->d_i : set->d_i_plain;
+  if (!r.fleet) { a.done_flag = flag; a.done_value = expect; }  // (with a controller axis the word is the batch ticket's)
   int rc = JH_OK;
   if (closed) {
-    jh_upd::TailArgs ra = a;  // the rollout kernel's view of the record: member b's costs lie b * N behind member 0's, everything else is shared
-    ra.costs = member_costs; ra.done_flag = nullptr; ra.done_value = 0u;
+    jh_upd::TailArgs ra = a;  // the rollout kernel's view of the record: problem (c, y)'s costs lie (c * Y + y) * Nb behind rollout_costs, the block and the noise are the controller's
+    ra.costs = rollout_costs; ra.N = Nb; ra.done_flag = nullptr; ra.done_value = 0u;
     jh_upd::BatchArgs s;
-    s.B = M; s.blk = 0; s.noise = 0; s.costs = N; s.trace = 0; s.scratch = 0; s.out = 0; s.counter = nullptr; s.done_flag = nullptr; s.done_value = 0u; s.image = (long long)set->stride;
-    rc = jh_simple_rollout_cost_batch(m, set->d_images, b, b + o_tp, W, H, K, ra, s, st);
+    s.B = Y; s.blk = 0; s.noise = noise_y; s.costs = Nb; s.trace = 0; s.scratch = 0; s.out = 0; s.counter = nullptr; s.done_flag = nullptr; s.done_value = 0u; s.image = (long long)set->stride;
+    jh_upd::ControllerAxis z;
+    z.C = B; z.blk = blk_c; z.noise = noise_c; z.image = image_c;
+    rc = jh_simple_rollout_cost_batch(m, set->d_images, b, b + d.o_tp, r.W, H, K, ra, s, st, z, plants);
   } else {
-    const jh_rollout_args ra = {b, b + o_nominal, noise, ldn, b + o_sigma, W, b + o_lohi, b + o_tp, 0, N, 0, H, K, member_costs, nullptr, nullptr};
-    jh_rollout_batch rb = {set->d_images, (long long)set->stride, ints, M, 0, 0};
-    rb.phase = phase;
+    const jh_rollout_args ra = {b, b + d.o_nominal, r.noise, d.ldn, b + d.o_sigma, r.W, b + d.o_lohi, b + d.o_tp, 0, Nb, 0, H, K, rollout_costs, nullptr, nullptr};
+    jh_rollout_batch rb = {set->d_images, (long long)set->stride, set->tables ? m->d_i : set->d_i_plain, Y, 0, noise_y, B, blk_c, noise_c, image_c};
+    rb.plants = plants; rb.o_phase = r.o_phase; rb.phase = r.phase;
     rc = eb->rollout_cost_batch(m, ra, rb, st);
   }
-  if (rc == JH_OK && timing) JH_HIP(hipEventRecord((hipEvent_t)timing[1], st));
-  const jh_upd::EnsembleArgs e{member_costs, costs, M, worst, (long long)N};
-  if (rc == JH_OK) rc = jh_update_tail_ensemble_launch(a, e, st);
-  if (rc == JH_OK && timing) JH_HIP(hipEventRecord((hipEvent_t)timing[2], st));
-  if (rc == JH_OK) rc = download_begin(out, out, 0, stream, flag, expect);
+  if (rc == JH_OK && r.timing) JH_HIP(hipEventRecord((hipEvent_t)r.timing[1], st));
+  if (rc == JH_OK && !r.fleet) rc = r.randomized ? jh_update_tail_launch(a, st) : jh_update_tail_ensemble_launch(a, jh_upd::EnsembleArgs{r.member_costs, r.costs, M, r.worst[0], (long long)N}, st);
+  if (rc == JH_OK && r.fleet) {
+    jh_upd::BatchArgs s;  // the tail's axis: the controllers
+    s.B = B; s.blk = blk_c; s.noise = noise_c; s.costs = N; s.trace = 0; s.scratch = (long long)jh_update_fused_scratch_floats(N, K, m->nu); s.out = (long long)r.out_stride_floats;
+    s.counter = reinterpret_cast<unsigned*>(r.scratch) + 1; s.done_flag = flag; s.done_value = expect;
+    jh_upd::EnsembleBatchArgs e;
+    e.member_costs = r.member_costs; e.costs = r.costs; e.M = M; e.stride = (long long)N;
+    for (int i = 0; i < JH_MAX_ENSEMBLE_FLEET; i++) e.worst[i] = (unsigned char)(!r.randomized && i < B ? r.worst[i] : 1);
+    rc = r.randomized ? jh_update_tail_batch_launch(a, s, st) : jh_update_tail_ensemble_batch_launch(a, s, e, st);
+  }
+  if (rc == JH_OK && r.timing) JH_HIP(hipEventRecord((hipEvent_t)r.timing[2], st));
+  if (rc == JH_OK) rc = download_begin(r.out, r.out, 0, r.stream, flag, expect);
   return rc;
 }
+
+// The entries: their own pre-checks, then the record.  (`JH_SET_STEP`: the fields every entry has, in the record's order.)
+#define JH_SET_STEP(who, batched, blk_stride, noise_stride)                                                                                                       \
+  {who, set, blk_dev, blk_host, {blk_bytes, o_nominal, o_sigma, o_tp, o_lohi, ldn, N, H, K, batched, blk_stride, noise_stride}, noise, W, costs, mode, lambda, k, \
+   tie_high, scratch, out, out_host_mark, timing, stream}
 
 extern "C" int jh_plan_step_ensemble(const jh_model_set* set, void* blk_dev, const void* blk_host, size_t blk_bytes, int o_nominal, int o_sigma, int o_tp, int o_lohi, const float* noise, int ldn,
                                      const float* W, int N, int H, int K, float* member_costs, float* costs, int worst, int mode, float lambda, int k, int tie_high, float* scratch, float* out,
                                      void* out_host_mark, void* const* timing, void* stream) {
-  return plan_step_ensemble("plan_step_ensemble", set, blk_dev, blk_host, blk_bytes, o_nominal, o_sigma, o_tp, o_lohi, noise, ldn, W, -1, N, H, K, member_costs, costs, worst, mode, lambda, k, tie_high,
-                            scratch, out, out_host_mark, timing, stream);
+  jh_set_step r = JH_SET_STEP("plan_step_ensemble", false, 0, 0);
+  r.fr3_hint = "jh_plan_step_ensemble_phase takes the arm's phase and plans it against the set's plants; jh_plan_step_randomized_phase spreads one arm's candidates over them";
+  r.member_costs = member_costs; r.worst = &worst;
+  return plan_step_set(r);
 }
 
-// jh_plan_step_ensemble for fr3_pick (include/judo_amd.h): the same code path with the arm's phase, which the fr3 kernel's members take from the launch record.
+// jh_plan_step_ensemble for fr3_pick: the same record with the arm's phase, which the fr3 kernel's members take from the launch record.
 extern "C" int jh_plan_step_ensemble_phase(const jh_model_set* set, void* blk_dev, const void* blk_host, size_t blk_bytes, int o_nominal, int o_sigma, int o_tp, int o_lohi, const float* noise,
                                            int ldn, const float* W, int phase, int N, int H, int K, float* member_costs, float* costs, int worst, int mode, float lambda, int k, int tie_high,
                                            float* scratch, float* out, void* out_host_mark, void* const* timing, void* stream) {
@@ -954,88 +1028,21 @@ extern "C" int jh_plan_step_ensemble_phase(const jh_model_set* set, void* blk_de
   JH_REQUIRE(set != nullptr, "%s: set is a null pointer", who);
   if (set->m0->kind != JH_TASK_FR3_PICK) { jh_set_error("%s: a phase is fr3_pick's alone; jh_plan_step_ensemble plans this set", who); return JH_ERR_UNSUPPORTED; }
   JH_REQUIRE(phase >= 0 && phase <= 3, "%s: phase = %d is not 0, 1, 2 or 3 (LIFT, MOVE, PLACE, HOMING)", who, phase);
-  return plan_step_ensemble(who, set, blk_dev, blk_host, blk_bytes, o_nominal, o_sigma, o_tp, o_lohi, noise, ldn, W, phase, N, H, K, member_costs, costs, worst, mode, lambda, k, tie_high, scratch, out,
-                            out_host_mark, timing, stream);
-}
-
-// ONE domain-randomised plan step (include/judo_amd.h): the N candidates of one problem in G blocks of Nb = N / G, block g on plant plant_of_block[g] of the set.  The
-// batched rollout kernels on grid (workgroups of Nb rollouts, G): the block stride 0 -- every block reads the one packed block --, the noise and cost strides Nb -- block
-// g's columns of the one noise matrix (pitch ldn) and its slice of `costs` --, the plant axis (jh_internal.h) with the rollout-index stride Nb -- only global rollout 0
-// drops its noise -- and the table, which travels in the kernel arguments.  Then the single call's own tail on the N costs.  The checks are the ensemble call's.
-// `phase`: -1 for jh_plan_step_randomized, which has none and refuses fr3_pick; 0..3 for jh_plan_step_randomized_phase, which plans fr3_pick alone (checked by the entry):
-// the one controller's phase travels in the launch record, and every block's workgroups take it as the single launch takes its argument.
-static int plan_step_randomized(const char* who, const jh_model_set* set, void* blk_dev, const void* blk_host, size_t blk_bytes, int o_nominal, int o_sigma, int o_tp, int o_lohi, const float* noise,
-                                int ldn, const float* W, int phase, int N, int H, int K, const unsigned char* plant_of_block, int G, float* costs, int mode, float lambda, int k, int tie_high,
-                                float* scratch, float* out, void* out_host_mark, void* const* timing, void* stream) {
-#define JH_RND_PTR(p) JH_REQUIRE((p) != nullptr, "%s: " #p " is a null pointer", who)
-  JH_RND_PTR(set); JH_RND_PTR(blk_dev); JH_RND_PTR(blk_host); JH_RND_PTR(noise); JH_RND_PTR(W); JH_RND_PTR(plant_of_block); JH_RND_PTR(costs); JH_RND_PTR(scratch); JH_RND_PTR(out);
-#undef JH_RND_PTR
-  const jh_model* m = set->m0;
-  const int M = set->B;
-  JH_REQUIRE(M <= JH_MAX_ENSEMBLE, "%s: a set of %d members exceeds JH_MAX_ENSEMBLE = %d", who, M, JH_MAX_ENSEMBLE);
-  JH_REQUIRE(G >= 1 && G <= JH_MAX_PLANT_BLOCKS, "%s: G = %d outside [1, JH_MAX_PLANT_BLOCKS = %d]", who, G, JH_MAX_PLANT_BLOCKS);
-  if (m->kind == JH_TASK_FR3_PICK && phase < 0) { jh_set_error("%s: fr3_pick has no batched plan step (its phase is chosen per problem on the host) behind this entry: jh_plan_step_randomized_phase takes the arm's phase", who); return JH_ERR_UNSUPPORTED; }
-  if (m->kind != JH_TASK_FR3_PICK && phase >= 0) { jh_set_error("%s: a phase is fr3_pick's alone; jh_plan_step_randomized plans this set", who); return JH_ERR_UNSUPPORTED; }
-  JH_REQUIRE(phase < 0 || K <= 8, "%s: the cooperative arm kernel keeps at most 8 knots per actuator in registers (K=%d)", who, K);
-  if (m->kind == JH_TASK_LEAP_CUBE && m->kernel_gen != 3) { jh_set_error("%s: only kernel generation 3 of the leap family has a batched launch (this model runs %d)", who, m->kernel_gen); return JH_ERR_UNSUPPORTED; }
-  JH_REQUIRE(N > 0 && H > 0 && K >= 1, "%s: N, H, K must be positive (N=%d H=%d K=%d)", who, N, H, K);
-  JH_REQUIRE(N % G == 0, "%s: N = %d is no multiple of G = %d (the blocks are N / G rollouts each)", who, N, G);
-  for (int g = 0; g < G; g++) JH_REQUIRE((int)plant_of_block[g] < M, "%s: plant_of_block[%d] = %d outside [0, M = %d): block %d names no member of the set", who, g, (int)plant_of_block[g], M, g);
-  JH_REQUIRE(ldn >= N, "%s: ldn (%d) < N (%d)", who, ldn, N);
-  const int KU = K * m->nu;
-  JH_REQUIRE(KU <= JH_MAX_KNOT_DIM, "%s: K*nu = %d exceeds %d", who, KU, JH_MAX_KNOT_DIM);
-  const int nx = m->nq + m->nv;
-  JH_REQUIRE(o_nominal >= 0 && o_sigma >= 0 && o_tp >= 0 && o_lohi >= 0, "%s: negative block offset", who);
-  const size_t need = sizeof(float) * (size_t)std::max(std::max(nx, o_nominal + KU), std::max(std::max(o_sigma + KU, o_tp + m->ntaskparam), o_lohi + 2 * m->nu));
-  JH_REQUIRE(blk_bytes >= need, "%s: a block of %zu bytes does not hold x0 | nominal | sigma | task params | bounds at the given offsets (%zu bytes)", who, blk_bytes, need);
-  JH_REQUIRE(m->plan_step_launches != 1, "%s: one launch is forced (jh_model_set_plan_step_launches) but the randomised plan step is two launches", who);
-  const bool closed = m->kind == JH_TASK_CARTPOLE || m->kind == JH_TASK_CYLINDER_PUSH;
-  const jh_engine_build* eb = engine_build(m);
-  if (!closed && !(eb && eb->rollout_cost_batch)) { jh_set_error("%s: no batched kernel for this model", who); return JH_ERR_UNSUPPORTED; }
-  unsigned* flag = (out_host_mark && out_host_mark != (void*)out) ? (unsigned*)out_host_mark : nullptr;  // (out_host_mark == out: the stream's event)
-  const float* b = (const float*)blk_dev;
-  jh_upd::TailArgs a;  // (the tail's own checks before anything is enqueued: mode, lambda, k)
-  if (int rc = jh_update_tail_args(who, costs, nullptr, b + o_nominal, noise, ldn, b + o_sigma, b + o_lohi, N, 0, K, m->nu, mode, lambda, k, tie_high, 0, nullptr, 0, 0, scratch, out, out + KU,
-                                   nullptr, nullptr, &a)) return rc;
-  const int Nb = N / G;
-  jh_plant_axis plants;
-  plants.n_stride = Nb;
-  for (int g = 0; g < G; g++) jh_plant_set(plants, g, plant_of_block[g]);
-  hipStream_t st = (hipStream_t)stream;
-  if (blk_dev != blk_host) { if (int rc = jh_upload_async(blk_dev, blk_host, blk_bytes, stream)) return rc; }  // (blk_dev == blk_host: read in place, as jh_plan_step)
-  if (timing) JH_HIP(hipEventRecord((hipEvent_t)timing[0], st));
-  const unsigned expect = flag ? __atomic_load_n(flag, __ATOMIC_RELAXED) + 1u : 0u;
-  a.done_flag = flag; a.done_value = expect;
-  const int* ints = set->tables ? m->d_i : set->d_i_plain;
-  int rc = JH_OK;
-  if (closed) {
-    jh_upd::TailArgs ra = a;  // the rollout kernel's view of the record: a block of Nb rollouts, block g's costs and noise columns g * Nb behind block 0's
-    ra.N = Nb; ra.done_flag = nullptr; ra.done_value = 0u;
-    jh_upd::BatchArgs s;
-    s.B = G; s.blk = 0; s.noise = Nb; s.costs = Nb; s.trace = 0; s.scratch = 0; s.out = 0; s.counter = nullptr; s.done_flag = nullptr; s.done_value = 0u; s.image = (long long)set->stride;
-    rc = jh_simple_rollout_cost_batch(m, set->d_images, b, b + o_tp, W, H, K, ra, s, st, {}, plants);
-  } else {
-    const jh_rollout_args ra = {b, b + o_nominal, noise, ldn, b + o_sigma, W, b + o_lohi, b + o_tp, 0, Nb, 0, H, K, costs, nullptr, nullptr};
-    jh_rollout_batch rb = {set->d_images, (long long)set->stride, ints, G, 0, (long long)Nb};
-    rb.plants = plants;
-    rb.phase = phase;
-    rc = eb->rollout_cost_batch(m, ra, rb, st);
-  }
-  if (rc == JH_OK && timing) JH_HIP(hipEventRecord((hipEvent_t)timing[1], st));
-  if (rc == JH_OK) rc = jh_update_tail_launch(a, st);
-  if (rc == JH_OK && timing) JH_HIP(hipEventRecord((hipEvent_t)timing[2], st));
-  if (rc == JH_OK) rc = download_begin(out, out, 0, stream, flag, expect);
-  return rc;
+  jh_set_step r = JH_SET_STEP(who, false, 0, 0);
+  r.member_costs = member_costs; r.worst = &worst; r.phase = phase;
+  return plan_step_set(r);
 }
 
 extern "C" int jh_plan_step_randomized(const jh_model_set* set, void* blk_dev, const void* blk_host, size_t blk_bytes, int o_nominal, int o_sigma, int o_tp, int o_lohi, const float* noise, int ldn,
                                        const float* W, int N, int H, int K, const unsigned char* plant_of_block, int G, float* costs, int mode, float lambda, int k, int tie_high, float* scratch,
                                        float* out, void* out_host_mark, void* const* timing, void* stream) {
-  return plan_step_randomized("plan_step_randomized", set, blk_dev, blk_host, blk_bytes, o_nominal, o_sigma, o_tp, o_lohi, noise, ldn, W, -1, N, H, K, plant_of_block, G, costs, mode, lambda, k, tie_high,
-                              scratch, out, out_host_mark, timing, stream);
+  jh_set_step r = JH_SET_STEP("plan_step_randomized", false, 0, 0);
+  r.fr3_hint = "jh_plan_step_randomized_phase takes the arm's phase";
+  r.randomized = true; r.plant_of_block = plant_of_block; r.G = G;
+  return plan_step_set(r);
 }
 
-// jh_plan_step_randomized for fr3_pick (include/judo_amd.h): the same code path with the arm's phase, which the fr3 kernel's blocks take from the launch record.
+// jh_plan_step_randomized for fr3_pick: the same record with the arm's phase, which the fr3 kernel's blocks take from the launch record.
 extern "C" int jh_plan_step_randomized_phase(const jh_model_set* set, void* blk_dev, const void* blk_host, size_t blk_bytes, int o_nominal, int o_sigma, int o_tp, int o_lohi, const float* noise,
                                              int ldn, const float* W, int phase, int N, int H, int K, const unsigned char* plant_of_block, int G, float* costs, int mode, float lambda, int k,
                                              int tie_high, float* scratch, float* out, void* out_host_mark, void* const* timing, void* stream) {
@@ -1043,100 +1050,23 @@ extern "C" int jh_plan_step_randomized_phase(const jh_model_set* set, void* blk_
   JH_REQUIRE(set != nullptr, "%s: set is a null pointer", who);
   if (set->m0->kind != JH_TASK_FR3_PICK) { jh_set_error("%s: a phase is fr3_pick's alone; jh_plan_step_randomized plans this set", who); return JH_ERR_UNSUPPORTED; }
   JH_REQUIRE(phase >= 0 && phase <= 3, "%s: phase = %d is not 0, 1, 2 or 3 (LIFT, MOVE, PLACE, HOMING)", who, phase);
-  return plan_step_randomized(who, set, blk_dev, blk_host, blk_bytes, o_nominal, o_sigma, o_tp, o_lohi, noise, ldn, W, phase, N, H, K, plant_of_block, G, costs, mode, lambda, k, tie_high, scratch, out,
-                              out_host_mark, timing, stream);
-}
-
-// B ensemble plan steps (jh_plan_step_ensemble) as ONE call (include/judo_amd.h): B controllers, each with its own block, noise, `worst`, costs and output record, each against M plants.  The
-// rollout kernels run once on the grid (workgroups, M, B): blockIdx.y is the member as above (block and noise strides 0, the set's image stride), blockIdx.z the
-// controller with the strides of jh_plan_step_batch; a set of M members is shared by all controllers (image stride 0 on that axis), a set of B * M holds controller b's
-// plants at b * M ...  Then k_update_tail_ensemble_batch on (tail workgroups, B): aggregation, tail, the two-level ticket, one completion word.  The checks are the
-// ensemble call's and the batched call's, all in front of the first enqueue.
-// `o_phase`: -1 for jh_plan_step_ensemble_batch, which has none and refuses fr3_pick; the float offset of every controller's phase word in its block for
-// jh_plan_step_ensemble_batch_phases, which plans fr3_pick alone (checked by the entry).  The members' block stride is 0, so the kernel reads the controller's own word;
-// the B words are checked on the host (phase_words).
-
-static int plan_step_ensemble_batch(const char* who, const jh_model_set* set, int B, int M, void* blk_dev, const void* blk_host, size_t blk_bytes, size_t blk_stride_bytes, int o_nominal, int o_sigma, int o_tp,
-                                    int o_lohi, int o_phase, const float* noise, int ldn, size_t noise_stride_floats, const float* W, int N, int H, int K, float* member_costs, float* costs,
-                                    const int* worst, int mode, float lambda, int k, int tie_high, float* scratch, float* out, size_t out_stride_floats, void* out_host_mark,
-                                    void* const* timing, void* stream) {
-#define JH_ENS_PTR(p) JH_REQUIRE((p) != nullptr, "%s: " #p " is a null pointer", who)
-  JH_ENS_PTR(set); JH_ENS_PTR(blk_dev); JH_ENS_PTR(blk_host); JH_ENS_PTR(noise); JH_ENS_PTR(W); JH_ENS_PTR(member_costs); JH_ENS_PTR(costs); JH_ENS_PTR(worst); JH_ENS_PTR(scratch); JH_ENS_PTR(out);
-#undef JH_ENS_PTR
-  const jh_model* m = set->m0;
-  JH_REQUIRE(B >= 1 && B <= JH_MAX_ENSEMBLE_FLEET, "%s: B = %d outside [1, JH_MAX_ENSEMBLE_FLEET = %d]", who, B, JH_MAX_ENSEMBLE_FLEET);
-  JH_REQUIRE(M >= 1 && M <= JH_MAX_ENSEMBLE, "%s: M = %d outside [1, JH_MAX_ENSEMBLE = %d]", who, M, JH_MAX_ENSEMBLE);
-  JH_REQUIRE(set->B == M || set->B == B * M, "%s: a set of %d members is neither the M = %d plants every controller shares nor the B * M = %d plants of B = %d controllers", who, set->B, M, B * M, B);
-  for (int b = 0; b < B; b++) JH_REQUIRE(worst[b] >= 1 && worst[b] <= M, "%s: controller %d: worst = %d outside [1, M = %d]", who, b, worst[b], M);
-  if (m->kind == JH_TASK_FR3_PICK && o_phase < 0) { jh_set_error("%s: fr3_pick has no batched plan step (its phase is chosen per problem on the host) behind this entry: jh_plan_step_ensemble_batch_phases takes a phase word per controller; jh_plan_step_batch_phases_models plans B arms on B plants", who); return JH_ERR_UNSUPPORTED; }
-  if (m->kind != JH_TASK_FR3_PICK && o_phase >= 0) { jh_set_error("%s: a phase word per controller is fr3_pick's alone; jh_plan_step_ensemble_batch plans this set", who); return JH_ERR_UNSUPPORTED; }
-  JH_REQUIRE(o_phase < 0 || K <= 8, "%s: the cooperative arm kernel keeps at most 8 knots per actuator in registers (K=%d)", who, K);
-  if (m->kind == JH_TASK_LEAP_CUBE && m->kernel_gen != 3) { jh_set_error("%s: only kernel generation 3 of the leap family has a batched launch (this model runs %d)", who, m->kernel_gen); return JH_ERR_UNSUPPORTED; }
-  JH_REQUIRE(N > 0 && H > 0 && K >= 1, "%s: N, H, K must be positive (N=%d H=%d K=%d)", who, N, H, K);
-  JH_REQUIRE(ldn >= N, "%s: ldn (%d) < N (%d)", who, ldn, N);
-  const int KU = K * m->nu;
-  JH_REQUIRE(KU <= JH_MAX_KNOT_DIM, "%s: K*nu = %d exceeds %d", who, KU, JH_MAX_KNOT_DIM);
-  const int nx = m->nq + m->nv;
-  JH_REQUIRE(o_nominal >= 0 && o_sigma >= 0 && o_tp >= 0 && o_lohi >= 0, "%s: negative block offset", who);
-  const size_t need = sizeof(float) * (size_t)std::max(std::max(nx, o_nominal + KU), std::max(std::max(o_sigma + KU, o_tp + m->ntaskparam), o_lohi + 2 * m->nu));
-  JH_REQUIRE(blk_bytes >= need, "%s: a block of %zu bytes does not hold x0 | nominal | sigma | task params | bounds at the given offsets (%zu bytes)", who, blk_bytes, need);
-  JH_REQUIRE(blk_stride_bytes >= blk_bytes && blk_stride_bytes % sizeof(float) == 0, "%s: blk_stride_bytes = %zu is smaller than a block (%zu bytes) or no multiple of 4", who, blk_stride_bytes, blk_bytes);
-  JH_REQUIRE(noise_stride_floats >= (size_t)KU * (size_t)ldn, "%s: noise_stride_floats = %zu is smaller than a problem's noise (K*nu*ldn = %zu)", who, noise_stride_floats, (size_t)KU * (size_t)ldn);
-  JH_REQUIRE(out_stride_floats >= 2 * (size_t)KU, "%s: out_stride_floats = %zu is smaller than an output record (nominal | sigma = %zu floats)", who, out_stride_floats, 2 * (size_t)KU);
-  JH_REQUIRE(m->plan_step_launches != 1, "%s: one launch is forced (jh_model_set_plan_step_launches) but the ensemble's plan step is two launches", who);
-  const bool closed = m->kind == JH_TASK_CARTPOLE || m->kind == JH_TASK_CYLINDER_PUSH;
-  const jh_engine_build* eb = engine_build(m);
-  if (!closed && !(eb && eb->rollout_cost_batch)) { jh_set_error("%s: no batched kernel for this model", who); return JH_ERR_UNSUPPORTED; }
-  JH_REQUIRE((long long)B * M * N <= 0x7fffffffll, "%s: B * M * N = %lld rollouts exceed one launch", who, (long long)B * M * N);
-  if (o_phase >= 0) { if (int rc = phase_words(who, "controller", B, blk_host, blk_bytes, blk_stride_bytes, o_phase)) return rc; }
-  unsigned* flag = (out_host_mark && out_host_mark != (void*)out) ? (unsigned*)out_host_mark : nullptr;  // (out_host_mark == out: the stream's event)
-  const float* b = (const float*)blk_dev;
-  jh_upd::TailArgs a;  // (controller 0's record; the tail's own checks before anything is enqueued: mode, lambda, k)
-  if (int rc = jh_update_tail_args(who, costs, nullptr, b + o_nominal, noise, ldn, b + o_sigma, b + o_lohi, N, 0, K, m->nu, mode, lambda, k, tie_high, 0, nullptr, 0, 0, scratch, out, out + KU,
-                                   nullptr, nullptr, &a)) return rc;
-  hipStream_t st = (hipStream_t)stream;
-  if (blk_dev != blk_host) { if (int rc = jh_upload_async(blk_dev, blk_host, (size_t)(B - 1) * blk_stride_bytes + blk_bytes, stream)) return rc; }
-  if (timing) JH_HIP(hipEventRecord((hipEvent_t)timing[0], st));
-  const unsigned expect = flag ? __atomic_load_n(flag, __ATOMIC_RELAXED) + 1u : 0u;
-  const long long blk_c = (long long)(blk_stride_bytes / sizeof(float)), image_c = set->B == M ? 0ll : (long long)M * (long long)set->stride;
-  const int* ints = set->tables ? m->d_i : set->d_i_plain;
-  int rc = JH_OK;
-  if (closed) {
-    jh_upd::TailArgs ra = a;  // the rollout kernel's view: pair (c, b)'s costs lie (c * M + b) * N behind member_costs, the block and the noise are the controller's
-    ra.costs = member_costs; ra.done_flag = nullptr; ra.done_value = 0u;
-    jh_upd::BatchArgs s;
-    s.B = M; s.blk = 0; s.noise = 0; s.costs = N; s.trace = 0; s.scratch = 0; s.out = 0; s.counter = nullptr; s.done_flag = nullptr; s.done_value = 0u; s.image = (long long)set->stride;
-    jh_upd::ControllerAxis z;
-    z.C = B; z.blk = blk_c; z.noise = (long long)noise_stride_floats; z.image = image_c;
-    rc = jh_simple_rollout_cost_batch(m, set->d_images, b, b + o_tp, W, H, K, ra, s, st, z);
-  } else {
-    const jh_rollout_args ra = {b, b + o_nominal, noise, ldn, b + o_sigma, W, b + o_lohi, b + o_tp, 0, N, 0, H, K, member_costs, nullptr, nullptr};
-    jh_rollout_batch rb = {set->d_images, (long long)set->stride, ints, M, 0, 0, B, blk_c, (long long)noise_stride_floats, image_c};
-    rb.o_phase = o_phase;
-    rc = eb->rollout_cost_batch(m, ra, rb, st);
-  }
-  if (rc == JH_OK && timing) JH_HIP(hipEventRecord((hipEvent_t)timing[1], st));
-  jh_upd::BatchArgs s;  // the tail's axis: the controllers
-  s.B = B; s.blk = blk_c; s.noise = (long long)noise_stride_floats; s.costs = N; s.trace = 0; s.scratch = (long long)jh_update_fused_scratch_floats(N, K, m->nu); s.out = (long long)out_stride_floats;
-  s.counter = reinterpret_cast<unsigned*>(scratch) + 1; s.done_flag = flag; s.done_value = expect;
-  jh_upd::EnsembleBatchArgs e;
-  e.member_costs = member_costs; e.costs = costs; e.M = M; e.stride = (long long)N;
-  for (int i = 0; i < JH_MAX_ENSEMBLE_FLEET; i++) e.worst[i] = (unsigned char)(i < B ? worst[i] : 1);
-  if (rc == JH_OK) rc = jh_update_tail_ensemble_batch_launch(a, s, e, st);
-  if (rc == JH_OK && timing) JH_HIP(hipEventRecord((hipEvent_t)timing[2], st));
-  if (rc == JH_OK) rc = download_begin(out, out, 0, stream, flag, expect);
-  return rc;
+  jh_set_step r = JH_SET_STEP(who, false, 0, 0);
+  r.randomized = true; r.plant_of_block = plant_of_block; r.G = G; r.phase = phase;
+  return plan_step_set(r);
 }
 
 extern "C" int jh_plan_step_ensemble_batch(const jh_model_set* set, int B, int M, void* blk_dev, const void* blk_host, size_t blk_bytes, size_t blk_stride_bytes, int o_nominal, int o_sigma, int o_tp,
                                            int o_lohi, const float* noise, int ldn, size_t noise_stride_floats, const float* W, int N, int H, int K, float* member_costs, float* costs,
                                            const int* worst, int mode, float lambda, int k, int tie_high, float* scratch, float* out, size_t out_stride_floats, void* out_host_mark,
                                            void* const* timing, void* stream) {
-  return plan_step_ensemble_batch("plan_step_ensemble_batch", set, B, M, blk_dev, blk_host, blk_bytes, blk_stride_bytes, o_nominal, o_sigma, o_tp, o_lohi, -1, noise, ldn, noise_stride_floats, W, N, H, K,
-                                  member_costs, costs, worst, mode, lambda, k, tie_high, scratch, out, out_stride_floats, out_host_mark, timing, stream);
+  jh_set_step r = JH_SET_STEP("plan_step_ensemble_batch", true, blk_stride_bytes, noise_stride_floats);
+  r.fr3_hint = "jh_plan_step_ensemble_batch_phases takes a phase word per controller; jh_plan_step_batch_phases_models plans B arms on B plants";
+  r.member_costs = member_costs; r.worst = worst;
+  r.fleet = true; r.B = B; r.M = M; r.out_stride_floats = out_stride_floats;
+  return plan_step_set(r);
 }
 
-// jh_plan_step_ensemble_batch for fr3_pick (include/judo_amd.h): the same code path with a phase word in every controller's block.
+// jh_plan_step_ensemble_batch for fr3_pick: the same record with a phase word in every controller's block.
 extern "C" int jh_plan_step_ensemble_batch_phases(const jh_model_set* set, int B, int M, void* blk_dev, const void* blk_host, size_t blk_bytes, size_t blk_stride_bytes, int o_nominal, int o_sigma,
                                                   int o_tp, int o_lohi, int o_phase, const float* noise, int ldn, size_t noise_stride_floats, const float* W, int N, int H, int K, float* member_costs,
                                                   float* costs, const int* worst, int mode, float lambda, int k, int tie_high, float* scratch, float* out, size_t out_stride_floats,
@@ -1145,108 +1075,24 @@ extern "C" int jh_plan_step_ensemble_batch_phases(const jh_model_set* set, int B
   JH_REQUIRE(set != nullptr, "%s: set is a null pointer", who);
   if (set->m0->kind != JH_TASK_FR3_PICK) { jh_set_error("%s: a phase word per controller is fr3_pick's alone; jh_plan_step_ensemble_batch plans this set", who); return JH_ERR_UNSUPPORTED; }
   JH_REQUIRE(o_phase >= 0, "%s: negative block offset (o_phase=%d)", who, o_phase);
-  return plan_step_ensemble_batch(who, set, B, M, blk_dev, blk_host, blk_bytes, blk_stride_bytes, o_nominal, o_sigma, o_tp, o_lohi, o_phase, noise, ldn, noise_stride_floats, W, N, H, K, member_costs, costs,
-                                  worst, mode, lambda, k, tie_high, scratch, out, out_stride_floats, out_host_mark, timing, stream);
-}
-
-// B randomised plan steps (jh_plan_step_randomized) as ONE call (include/judo_amd.h): B controllers, each with its own block, noise, costs, output record and its own table
-// from rollout block to plant.  The rollout kernels run once on the grid (workgroups of Nb rollouts, G, B): blockIdx.y is the block as above (block stride 0; noise, cost and
-// rollout-index strides Nb), blockIdx.z the controller with the strides of jh_plan_step_ensemble_batch, and the plant axis carries the B x G table, whose entry is the
-// pair's (jh_internal.h).  A set of M members is shared by all controllers (image stride 0 on that axis), a set of B * M holds controller b's plants at b * M ...  Then
-// k_update_tail_batch on (tail workgroups, B): the tail, the two-level ticket, one completion word.  The checks are the randomised call's and the batched call's, all in
-// front of the first enqueue.
-// `o_phase`: -1 for jh_plan_step_randomized_batch, which has none and refuses fr3_pick; the float offset of every controller's phase word in its block for
-// jh_plan_step_randomized_batch_phases, which plans fr3_pick alone (checked by the entry), as in plan_step_ensemble_batch.
-static int plan_step_randomized_batch(const char* who, const jh_model_set* set, int B, int M, void* blk_dev, const void* blk_host, size_t blk_bytes, size_t blk_stride_bytes, int o_nominal, int o_sigma,
-                                      int o_tp, int o_lohi, int o_phase, const float* noise, int ldn, size_t noise_stride_floats, const float* W, int N, int H, int K,
-                                      const unsigned char* plant_of_block, int G, float* costs, int mode, float lambda, int k, int tie_high, float* scratch, float* out,
-                                      size_t out_stride_floats, void* out_host_mark, void* const* timing, void* stream) {
-#define JH_RND_PTR(p) JH_REQUIRE((p) != nullptr, "%s: " #p " is a null pointer", who)
-  JH_RND_PTR(set); JH_RND_PTR(blk_dev); JH_RND_PTR(blk_host); JH_RND_PTR(noise); JH_RND_PTR(W); JH_RND_PTR(plant_of_block); JH_RND_PTR(costs); JH_RND_PTR(scratch); JH_RND_PTR(out);
-#undef JH_RND_PTR
-  const jh_model* m = set->m0;
-  JH_REQUIRE(B >= 1 && B <= JH_MAX_ENSEMBLE_FLEET, "%s: B = %d outside [1, JH_MAX_ENSEMBLE_FLEET = %d]", who, B, JH_MAX_ENSEMBLE_FLEET);
-  JH_REQUIRE(M >= 1 && M <= JH_MAX_ENSEMBLE, "%s: M = %d outside [1, JH_MAX_ENSEMBLE = %d]", who, M, JH_MAX_ENSEMBLE);
-  JH_REQUIRE(G >= 1 && G <= JH_MAX_PLANT_BLOCKS, "%s: G = %d outside [1, JH_MAX_PLANT_BLOCKS = %d]", who, G, JH_MAX_PLANT_BLOCKS);
-  JH_REQUIRE(B * G <= JH_MAX_FLEET_PLANT_BLOCKS, "%s: B * G = %d * %d = %d exceeds JH_MAX_FLEET_PLANT_BLOCKS = %d (the bytes of the table in the kernel arguments)", who, B, G, B * G,
-             JH_MAX_FLEET_PLANT_BLOCKS);
-  JH_REQUIRE(set->B == M || set->B == B * M, "%s: a set of %d members is neither the M = %d plants every controller shares nor the B * M = %d plants of B = %d controllers", who, set->B, M, B * M, B);
-  if (m->kind == JH_TASK_FR3_PICK && o_phase < 0) { jh_set_error("%s: fr3_pick has no batched plan step (its phase is chosen per problem on the host) behind this entry: jh_plan_step_randomized_batch_phases takes a phase word per controller; jh_plan_step_randomized_phase plans one arm over the set's plants and jh_plan_step_batch_phases_models B arms on B plants", who); return JH_ERR_UNSUPPORTED; }
-  if (m->kind != JH_TASK_FR3_PICK && o_phase >= 0) { jh_set_error("%s: a phase word per controller is fr3_pick's alone; jh_plan_step_randomized_batch plans this set", who); return JH_ERR_UNSUPPORTED; }
-  JH_REQUIRE(o_phase < 0 || K <= 8, "%s: the cooperative arm kernel keeps at most 8 knots per actuator in registers (K=%d)", who, K);
-  if (m->kind == JH_TASK_LEAP_CUBE && m->kernel_gen != 3) { jh_set_error("%s: only kernel generation 3 of the leap family has a batched launch (this model runs %d)", who, m->kernel_gen); return JH_ERR_UNSUPPORTED; }
-  JH_REQUIRE(N > 0 && H > 0 && K >= 1, "%s: N, H, K must be positive (N=%d H=%d K=%d)", who, N, H, K);
-  JH_REQUIRE(N % G == 0, "%s: N = %d is no multiple of G = %d (the blocks are N / G rollouts each)", who, N, G);
-  for (int c = 0; c < B; c++)
-    for (int g = 0; g < G; g++)
-      JH_REQUIRE((int)plant_of_block[c * G + g] < M, "%s: plant_of_block[%d] = %d outside [0, M = %d): controller %d, block %d names no member of the set", who, c * G + g,
-                 (int)plant_of_block[c * G + g], M, c, g);
-  JH_REQUIRE(ldn >= N, "%s: ldn (%d) < N (%d)", who, ldn, N);
-  const int KU = K * m->nu;
-  JH_REQUIRE(KU <= JH_MAX_KNOT_DIM, "%s: K*nu = %d exceeds %d", who, KU, JH_MAX_KNOT_DIM);
-  const int nx = m->nq + m->nv;
-  JH_REQUIRE(o_nominal >= 0 && o_sigma >= 0 && o_tp >= 0 && o_lohi >= 0, "%s: negative block offset", who);
-  const size_t need = sizeof(float) * (size_t)std::max(std::max(nx, o_nominal + KU), std::max(std::max(o_sigma + KU, o_tp + m->ntaskparam), o_lohi + 2 * m->nu));
-  JH_REQUIRE(blk_bytes >= need, "%s: a block of %zu bytes does not hold x0 | nominal | sigma | task params | bounds at the given offsets (%zu bytes)", who, blk_bytes, need);
-  JH_REQUIRE(blk_stride_bytes >= blk_bytes && blk_stride_bytes % sizeof(float) == 0, "%s: blk_stride_bytes = %zu is smaller than a block (%zu bytes) or no multiple of 4", who, blk_stride_bytes, blk_bytes);
-  JH_REQUIRE(noise_stride_floats >= (size_t)KU * (size_t)ldn, "%s: noise_stride_floats = %zu is smaller than a problem's noise (K*nu*ldn = %zu)", who, noise_stride_floats, (size_t)KU * (size_t)ldn);
-  JH_REQUIRE(out_stride_floats >= 2 * (size_t)KU, "%s: out_stride_floats = %zu is smaller than an output record (nominal | sigma = %zu floats)", who, out_stride_floats, 2 * (size_t)KU);
-  JH_REQUIRE(m->plan_step_launches != 1, "%s: one launch is forced (jh_model_set_plan_step_launches) but the randomised plan step is two launches", who);
-  const bool closed = m->kind == JH_TASK_CARTPOLE || m->kind == JH_TASK_CYLINDER_PUSH;
-  const jh_engine_build* eb = engine_build(m);
-  if (!closed && !(eb && eb->rollout_cost_batch)) { jh_set_error("%s: no batched kernel for this model", who); return JH_ERR_UNSUPPORTED; }
-  JH_REQUIRE((long long)B * N <= 0x7fffffffll, "%s: B * N = %lld rollouts exceed one launch", who, (long long)B * N);
-  if (o_phase >= 0) { if (int rc = phase_words(who, "controller", B, blk_host, blk_bytes, blk_stride_bytes, o_phase)) return rc; }
-  unsigned* flag = (out_host_mark && out_host_mark != (void*)out) ? (unsigned*)out_host_mark : nullptr;  // (out_host_mark == out: the stream's event)
-  const float* b = (const float*)blk_dev;
-  jh_upd::TailArgs a;  // (controller 0's record; the tail's own checks before anything is enqueued: mode, lambda, k)
-  if (int rc = jh_update_tail_args(who, costs, nullptr, b + o_nominal, noise, ldn, b + o_sigma, b + o_lohi, N, 0, K, m->nu, mode, lambda, k, tie_high, 0, nullptr, 0, 0, scratch, out, out + KU,
-                                   nullptr, nullptr, &a)) return rc;
-  const int Nb = N / G;
-  jh_plant_axis plants;
-  plants.n_stride = Nb;
-  for (int e = 0; e < B * G; e++) jh_plant_set(plants, e, plant_of_block[e]);
-  hipStream_t st = (hipStream_t)stream;
-  if (blk_dev != blk_host) { if (int rc = jh_upload_async(blk_dev, blk_host, (size_t)(B - 1) * blk_stride_bytes + blk_bytes, stream)) return rc; }
-  if (timing) JH_HIP(hipEventRecord((hipEvent_t)timing[0], st));
-  const unsigned expect = flag ? __atomic_load_n(flag, __ATOMIC_RELAXED) + 1u : 0u;
-  const long long blk_c = (long long)(blk_stride_bytes / sizeof(float)), image_c = set->B == M ? 0ll : (long long)M * (long long)set->stride;
-  const int* ints = set->tables ? m->d_i : set->d_i_plain;
-  int rc = JH_OK;
-  if (closed) {
-    jh_upd::TailArgs ra = a;  // the rollout kernel's view: a block of Nb rollouts; pair (c, g)'s costs lie (c * G + g) * Nb behind `costs`, its noise columns g * Nb behind the controller's
-    ra.N = Nb; ra.done_flag = nullptr; ra.done_value = 0u;
-    jh_upd::BatchArgs s;
-    s.B = G; s.blk = 0; s.noise = Nb; s.costs = Nb; s.trace = 0; s.scratch = 0; s.out = 0; s.counter = nullptr; s.done_flag = nullptr; s.done_value = 0u; s.image = (long long)set->stride;
-    jh_upd::ControllerAxis z;
-    z.C = B; z.blk = blk_c; z.noise = (long long)noise_stride_floats; z.image = image_c;
-    rc = jh_simple_rollout_cost_batch(m, set->d_images, b, b + o_tp, W, H, K, ra, s, st, z, plants);
-  } else {
-    const jh_rollout_args ra = {b, b + o_nominal, noise, ldn, b + o_sigma, W, b + o_lohi, b + o_tp, 0, Nb, 0, H, K, costs, nullptr, nullptr};
-    jh_rollout_batch rb = {set->d_images, (long long)set->stride, ints, G, 0, (long long)Nb, B, blk_c, (long long)noise_stride_floats, image_c};
-    rb.plants = plants;
-    rb.o_phase = o_phase;
-    rc = eb->rollout_cost_batch(m, ra, rb, st);
-  }
-  if (rc == JH_OK && timing) JH_HIP(hipEventRecord((hipEvent_t)timing[1], st));
-  jh_upd::BatchArgs s;  // the tail's axis: the controllers
-  s.B = B; s.blk = blk_c; s.noise = (long long)noise_stride_floats; s.costs = N; s.trace = 0; s.scratch = (long long)jh_update_fused_scratch_floats(N, K, m->nu); s.out = (long long)out_stride_floats;
-  s.counter = reinterpret_cast<unsigned*>(scratch) + 1; s.done_flag = flag; s.done_value = expect;
-  if (rc == JH_OK) rc = jh_update_tail_batch_launch(a, s, st);
-  if (rc == JH_OK && timing) JH_HIP(hipEventRecord((hipEvent_t)timing[2], st));
-  if (rc == JH_OK) rc = download_begin(out, out, 0, stream, flag, expect);
-  return rc;
+  jh_set_step r = JH_SET_STEP(who, true, blk_stride_bytes, noise_stride_floats);
+  r.member_costs = member_costs; r.worst = worst; r.o_phase = o_phase;
+  r.fleet = true; r.B = B; r.M = M; r.out_stride_floats = out_stride_floats;
+  return plan_step_set(r);
 }
 
 extern "C" int jh_plan_step_randomized_batch(const jh_model_set* set, int B, int M, void* blk_dev, const void* blk_host, size_t blk_bytes, size_t blk_stride_bytes, int o_nominal, int o_sigma,
                                              int o_tp, int o_lohi, const float* noise, int ldn, size_t noise_stride_floats, const float* W, int N, int H, int K,
                                              const unsigned char* plant_of_block, int G, float* costs, int mode, float lambda, int k, int tie_high, float* scratch, float* out,
                                              size_t out_stride_floats, void* out_host_mark, void* const* timing, void* stream) {
-  return plan_step_randomized_batch("plan_step_randomized_batch", set, B, M, blk_dev, blk_host, blk_bytes, blk_stride_bytes, o_nominal, o_sigma, o_tp, o_lohi, -1, noise, ldn, noise_stride_floats, W, N, H, K,
-                                    plant_of_block, G, costs, mode, lambda, k, tie_high, scratch, out, out_stride_floats, out_host_mark, timing, stream);
+  jh_set_step r = JH_SET_STEP("plan_step_randomized_batch", true, blk_stride_bytes, noise_stride_floats);
+  r.fr3_hint = "jh_plan_step_randomized_batch_phases takes a phase word per controller; jh_plan_step_randomized_phase plans one arm over the set's plants and jh_plan_step_batch_phases_models B arms on B plants";
+  r.randomized = true; r.plant_of_block = plant_of_block; r.G = G;
+  r.fleet = true; r.B = B; r.M = M; r.out_stride_floats = out_stride_floats;
+  return plan_step_set(r);
 }
 
-// jh_plan_step_randomized_batch for fr3_pick (include/judo_amd.h): the same code path with a phase word in every controller's block.
+// jh_plan_step_randomized_batch for fr3_pick: the same record with a phase word in every controller's block.
 extern "C" int jh_plan_step_randomized_batch_phases(const jh_model_set* set, int B, int M, void* blk_dev, const void* blk_host, size_t blk_bytes, size_t blk_stride_bytes, int o_nominal, int o_sigma,
                                                     int o_tp, int o_lohi, int o_phase, const float* noise, int ldn, size_t noise_stride_floats, const float* W, int N, int H, int K,
                                                     const unsigned char* plant_of_block, int G, float* costs, int mode, float lambda, int k, int tie_high, float* scratch, float* out,
@@ -1255,9 +1101,12 @@ extern "C" int jh_plan_step_randomized_batch_phases(const jh_model_set* set, int
   JH_REQUIRE(set != nullptr, "%s: set is a null pointer", who);
   if (set->m0->kind != JH_TASK_FR3_PICK) { jh_set_error("%s: a phase word per controller is fr3_pick's alone; jh_plan_step_randomized_batch plans this set", who); return JH_ERR_UNSUPPORTED; }
   JH_REQUIRE(o_phase >= 0, "%s: negative block offset (o_phase=%d)", who, o_phase);
-  return plan_step_randomized_batch(who, set, B, M, blk_dev, blk_host, blk_bytes, blk_stride_bytes, o_nominal, o_sigma, o_tp, o_lohi, o_phase, noise, ldn, noise_stride_floats, W, N, H, K, plant_of_block, G,
-                                    costs, mode, lambda, k, tie_high, scratch, out, out_stride_floats, out_host_mark, timing, stream);
+  jh_set_step r = JH_SET_STEP(who, true, blk_stride_bytes, noise_stride_floats);
+  r.randomized = true; r.plant_of_block = plant_of_block; r.G = G; r.o_phase = o_phase;
+  r.fleet = true; r.B = B; r.M = M; r.out_stride_floats = out_stride_floats;
+  return plan_step_set(r);
 }
+#undef JH_SET_STEP
 
 // The update alone for B problems whose costs are given (the materialise path of a fleet: the Spot policy rollout, judo_amd/fleet.py): jh_plan_step_batch's last stage --
 // k_update_tail_batch with the two-level ticket -- and its completion mark, without an upload or a rollout kernel in front.

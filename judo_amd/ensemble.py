@@ -10,7 +10,6 @@ for operation; the device result equals it bit for bit (tests/test_gpu_ensemble_
 
 from __future__ import annotations
 
-import ctypes as C
 from typing import Sequence
 
 import numpy as np
@@ -18,14 +17,9 @@ import torch
 
 from judo_amd import _lib
 from judo_amd.config import ControllerConfig
-from judo_amd.controller import Controller, _PlanBuffers
-from judo_amd.device import GpuModel, GpuModelSet
-from judo_amd.distributed import Shard
-from judo_amd.models import image_sections, layout, pack_model
-from judo_amd.optimizers import get_registered_optimizers
-from judo_amd.tasks import Task, get_registered_tasks
-
-MAX_ENSEMBLE = _lib.MAX_ENSEMBLE
+from judo_amd.controller import Controller
+from judo_amd.plants import MAX_ENSEMBLE, FusedPlantController, WorstCase, check_descriptions, make_for, materialized_hint
+from judo_amd.tasks import Task
 
 
 def aggregate_costs_host(member_costs, worst: int) -> np.ndarray:
@@ -47,25 +41,6 @@ def aggregate_costs_host(member_costs, worst: int) -> np.ndarray:
         return (acc / np.float32(j)).astype(np.float32)
 
 
-def check_descriptions(descriptions: Sequence[dict]) -> list[bytes]:
-    """The admission rule of an ensemble, without a device (the rule `ControllerFleet` applies to members with images of their own): the descriptions pack to images
-    whose header and int section are member 0's byte for byte -- the float section alone may differ (masses, inertias, friction, gains: `models.scaled_description`).
-    Returns the packed images; raises ValueError naming the member and the section."""
-    if len(descriptions) < 1:
-        raise ValueError("an ensemble needs at least one description")
-    if len(descriptions) > MAX_ENSEMBLE:
-        raise ValueError(f"an ensemble of {len(descriptions)} members exceeds the {MAX_ENSEMBLE} of a launch (include/judo_amd.h JH_MAX_ENSEMBLE)")
-    blobs = [bytes(pack_model(d)) for d in descriptions]
-    want = image_sections(blobs[0])
-    for i, blob in enumerate(blobs[1:], start=1):
-        if blob == blobs[0]:
-            continue
-        for name, x, y in zip(("header", "float section", "int section"), image_sections(blob), want):
-            if (x != y and name != "float section") or len(x) != len(y):
-                raise ValueError(f"ensemble member {i} has another model image than member 0: the {name} of its image differs")
-    return blobs
-
-
 def check_task(task: Task, fr3: bool = False) -> None:
     """The tasks without an ensemble plan step, refused before any model is made; raises ValueError.  `fr3`: the caller's plan step carries the arm's phase
     (judo_amd.fr3_ensemble), so fr3_pick passes."""
@@ -79,14 +54,11 @@ def check_task(task: Task, fr3: bool = False) -> None:
 
 
 def _materialized_hint(why: str, fr3: bool = False) -> str:
-    """What serves a configuration this class refuses, behind the refusal: the controller of judo_amd.materialized keeps the materialise path (a plugin reward, hook or
-    optimizer, the running normaliser, more knots than the fused kernel holds) and rolls it out on the plants.  It has no sharded form and writes no candidate knots either."""
-    if fr3 or "sharded path" in why or "keep_candidates" in why:  # (fr3_pick has no materialise launch on plants)
-        return ""
-    return ".  judo_amd.materialized.make_materialized_ensemble_controller makes the controller that materialises the rollouts on the plants and scores them with Task.reward"
+    """`plants.materialized_hint` with this module's maker."""
+    return materialized_hint(why, "ensemble", fr3)
 
 
-class EnsembleController(Controller):
+class EnsembleController(FusedPlantController, WorstCase, Controller):
     """A `Controller` whose plan step rolls every candidate out on M plants and updates on the aggregated costs.  Everything else -- `update_states`, `action(t)`,
     `traces`, `max_opt_iters`, the three optimizers, the `none` / `min_max` normalisers, a live change of `num_rollouts` -- is the controller's own.
 
@@ -94,154 +66,30 @@ class EnsembleController(Controller):
     `set_member(b, description)` replaces one plant."""
 
     _fr3_ensemble = False  # (FR3EnsembleController: the plan step carries the arm's phase; only an FR3EnsembleFleet takes such a member)
-    _entry = "jh_plan_step_ensemble"  # the library call of the plan step
+    _entry = "jh_plan_step_ensemble"  # the library call of the plan step: the rollout kernel on (workgroups, M), the aggregation in front of the update's tail
+    _a, _form, _whose, _call, _maker = "an ensemble", "ensemble", "members'", "jh_plan_step_ensemble", "ensemble"
+    _member_of = "an ensemble of {}"
+    _ensemble_refusal = FusedPlantController._refusal  # (the name the fleets call)
 
     def _check_task(self, task: Task) -> None:
         check_task(task)
 
-    def _entry_args(self, W, N: int, H: int, K: int) -> tuple:
-        """The entry's arguments between the noise pitch and the member costs: W, N, H, K."""
-        return (_lib.ptr(W), N, H, K)
-
     def __init__(self, controller_config: ControllerConfig, task: Task, optimizer, descriptions: Sequence[dict], worst: int | None = None,
                  device: torch.device | None = None) -> None:
-        self._check_task(task)
-        check_descriptions(descriptions)
-        self._descriptions = list(descriptions)
-        task.desc = self._descriptions[0]
-        task._layout, task._ctrlrange, task._jadr, task._gpu = layout(task.desc), None, None, None
+        self._admit(task, descriptions)
         super().__init__(controller_config, task, optimizer, device=device)
-        self._members = [self.model] + [GpuModel(d, self.device) for d in self._descriptions[1:]]
-        self.model_set = GpuModelSet(self._members)
-        self._worst = len(self._members)
-        self.worst = len(self._members) if worst is None else worst
-        self._member_costs: torch.Tensor | None = None
+        self._init_worst(worst, len(self._members))
 
-    # ---- the ensemble ------------------------------------------------------------------------------------------------------------------------------
-    @property
-    def descriptions(self) -> list[dict]:
-        return list(self._descriptions)
-
-    @property
-    def num_members(self) -> int:
-        return len(self._members)
-
-    @property
-    def worst(self) -> int:
-        """How many of a rollout's largest member costs are averaged: 1 = the worst case, M = the mean."""
-        return self._worst
-
-    @worst.setter
-    def worst(self, j: int) -> None:
-        if not 1 <= int(j) <= len(self._members):
-            raise ValueError(f"worst = {j} outside [1, M = {len(self._members)}]")
-        self._worst = int(j)
-
-    def set_member(self, b: int, description: dict) -> None:
-        """Replace member b's plant (`GpuModelSet.update`: the library's checks; synchronous -- between plan steps).  b = 0 replaces the nominal plant too."""
-        b = int(b)
-        if not 0 <= b < len(self._members):
-            raise ValueError(f"member {b} of an ensemble of {len(self._members)}")
-        trial = list(self._descriptions)
-        trial[b] = description
-        check_descriptions(trial)
-        model = GpuModel(description, self.device)
-        self.model_set.update(b, model)
-        self._members[b], self._descriptions[b] = model, description
-        if b == 0:
-            self.task.desc, self.task._gpu = description, model
-            self.task._layout, self.task._ctrlrange, self.task._jadr = layout(description), None, None
-            self.model = self.rollout_backend.model = model
-
-    @property
-    def member_costs(self) -> np.ndarray:
-        """(M, N) fp32: member b's cost of every candidate of the last iteration."""
-        if self._member_costs is None:
-            raise RuntimeError("member_costs needs a completed update_action()")
-        return self._member_costs.cpu().numpy()
-
-    @property
-    def member_rewards(self) -> np.ndarray:
-        return -self.member_costs.astype(np.float64)
-
-    # ---- the plan step -----------------------------------------------------------------------------------------------------------------------------
-    def _hint(self, why: str) -> str:
-        """What a refusal of the one-call shape adds: the maker that serves the configuration (`FR3EnsembleController` names the arm's)."""
-        return _materialized_hint(why, self._fr3_ensemble)
-
-    def _ensemble_refusal(self, world: int, nrm) -> str | None:
-        """Why this controller's iteration is not the one-call shape, or None."""
-        if world > 1 or self.force_shard_path:
-            return "a process group or force_shard_path: the sharded path has no ensemble form"
-        if nrm.needs_moments:
-            return "the running normaliser: its moments need the materialise path"
-        if self.keep_candidates:
-            return "keep_candidates: the ensemble launch writes no candidate knots"
-        if self.model is not None and self.optimizer.num_nodes > self.model.max_fused_knots_at(self.num_timesteps):
-            return f"num_nodes = {self.optimizer.num_nodes} above the fused kernel's limit of {self.model.max_fused_knots_at(self.num_timesteps)} knots at this horizon (max_fused_knots_at)"
-        if not self.uses_fused_cost or not (self.fused_update and hasattr(self.optimizer, "fused_update_args")):
-            return "a plugin reward, hook or optimizer (uses_fused_cost is false): the members' costs come from the fused kernels alone"
-        return None
-
-    def _iteration_shape(self, world: int, nrm) -> str:
-        why = self._ensemble_refusal(world, nrm)
-        if why is not None:
-            raise ValueError(f"an ensemble controller runs its iteration as one jh_plan_step_ensemble call, which this configuration rules out ({why})" + self._hint(why))
-        return "plan_step"
-
-    def update_action(self) -> None:
-        if not self.uses_fused_optimizer:
-            raise ValueError("an ensemble controller runs its iteration as one jh_plan_step_ensemble call, which this configuration rules out "
-                             "(a plugin reward, hook or optimizer (uses_fused_cost is false): the members' costs come from the fused kernels alone)" + self._hint(""))
-        super().update_action()
-
-    def _plan_step(self, lib, b: _PlanBuffers, shape: str, noise_p: int, ldn: int, knots_out, W, shard: Shard, world: int, H: int, K: int, nu: int, stream,
-                   state: dict) -> int:
-        """Shape "plan_step" on the ensemble: one upload (or the host block read in place), the batched rollout kernel on (workgroups, M), the update's tail with the
-        aggregation in front, one completion mark.  No trace buffer: the trace elites' knots are staged and re-rolled on member 0 when the traces are read."""
-        opt = self.optimizer
-        M, N = len(self._members), shard.count
-        state["trace_buf"] = None
-        b.size_out(2 * K * nu)
-        if self._member_costs is None or tuple(self._member_costs.shape) != (M, N):
-            self._member_costs = torch.empty((M, N), dtype=torch.float32, device=self.device)
-        mode, lam, k_el, tie = opt.fused_update_args()
-        evs = [self._timing_event() for _ in range(3)] if self.record_kernel_events else None
-        timing = (C.c_void_p * 3)(*[e.handle for e in evs]) if evs else None
-        off = b.offsets
-        in_place = b.blk_stale = self.model.closed_form
-        mark = b.done_ptr if self.model.closed_form else b.out_host_ptr
-        st = getattr(lib, self._entry)(self.model_set.handle, b.host_ptr if in_place else b.blk.data_ptr(), b.host_ptr, b.nblk_bytes, int(off[1]), int(off[2]), int(off[3]), int(off[4]),
-                                       noise_p, ldn, *self._entry_args(W, N, H, K), self._member_costs.data_ptr(), _lib.ptr(b.costs), self._worst, mode, lam, k_el, tie,
-                                       _lib.ptr(b.fused_scratch), b.out_host_ptr, mark, timing, stream)
-        _lib.check(st, self._entry)
-        state["costs"] = b.costs
-        if evs:
-            self.kernel_events.append((evs[0], evs[1]))
-            self.exchange_events.append((evs[1], evs[2]))
-        self._fetch(b, begun=True)
-        if state.get("stage") is not None:
-            state["stage"]()
-        return 0
+    def _kind_args(self, b, N: int) -> tuple:
+        """The entry's arguments between K and `mode`: member_costs, costs, worst."""
+        return (self._member_cost_rows(N).data_ptr(), _lib.ptr(b.costs), self._worst)
 
 
 def make_ensemble_controller(task: str | Task, optimizer: str, descriptions: Sequence[dict], worst: int | None = None, device: torch.device | None = None) -> EnsembleController:
     """`make_controller` for one controller over M plants: the registered task and optimizer (with the task's overrides) around `descriptions`, M model descriptions of
     that task (`models.scaled_description(task.desc, body_mass=..., geom_friction=..., actuator_kp=...)`).  Member 0 is the nominal plant.  `worst`: how many of a
     candidate's largest member costs are averaged; None: all M, the mean."""
-    tasks, opts = get_registered_tasks(), get_registered_optimizers()
-    if isinstance(task, str):
-        if task not in tasks:
-            raise ValueError(f"Task {task} not found in task registry.")
-        task = tasks[task][0]()
-    if optimizer not in opts:
-        raise ValueError(f"Optimizer {optimizer} not found in optimizer registry.")
-    opt_cls, opt_cfg_cls = opts[optimizer]
-    opt_cfg = opt_cfg_cls()
-    opt_cfg.set_override(task.name)
-    ctrl_cfg = ControllerConfig()
-    ctrl_cfg.set_override(task.name)
-    return EnsembleController(ctrl_cfg, task, opt_cls(opt_cfg, task.nu), descriptions, worst=worst, device=device)
+    return make_for(EnsembleController, task, optimizer, descriptions, worst=worst, device=device)
 
 
 __all__ = ["EnsembleController", "MAX_ENSEMBLE", "aggregate_costs_host", "check_descriptions", "check_task", "make_ensemble_controller"]

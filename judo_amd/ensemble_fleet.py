@@ -24,6 +24,7 @@ from judo_amd.distributed import world_info
 from judo_amd.ensemble import MAX_ENSEMBLE, EnsembleController, check_descriptions, make_ensemble_controller
 from judo_amd.fleet import ControllerFleet, _FleetBuffers, refuse_fr3_randomized
 from judo_amd.models import image_sections
+from judo_amd.plants import PlantFleet
 from judo_amd.randomized import RandomizedController
 
 MAX_ENSEMBLE_FLEET = _lib.MAX_ENSEMBLE_FLEET
@@ -89,7 +90,7 @@ def check_fleet_descriptions(lists: Sequence[Sequence[dict]]) -> list[list[bytes
     return blobs
 
 
-class EnsembleFleet(ControllerFleet):
+class EnsembleFleet(PlantFleet, ControllerFleet):
     """B `EnsembleController`s of one task and optimizer kind whose plan steps run as one launch.  `fleet[i]` is an ordinary `EnsembleController`: `update_states`,
     `optimizer.seed`, `action(t)`, `traces`, `rewards`, `member_costs`, the `worst` setter and `set_member` work per member as they do on a controller alone, and take
     effect at the fleet's next plan step."""
@@ -97,7 +98,6 @@ class EnsembleFleet(ControllerFleet):
     _ensemble_members = True
 
     def __init__(self, controllers: Sequence[EnsembleController]) -> None:
-        self._set_key: tuple = ()
         self._member_costs: torch.Tensor | None = None  # (B, M, N): the members' `_member_costs` are views of it
         if len(controllers) > MAX_ENSEMBLE_FLEET:
             raise ValueError(f"a fleet of {len(controllers)} ensemble controllers exceeds the {MAX_ENSEMBLE_FLEET} of a launch (include/judo_amd.h JH_MAX_ENSEMBLE_FLEET)")
@@ -119,29 +119,8 @@ class EnsembleFleet(ControllerFleet):
             raise ValueError(f"fleet member {i} does not run its iteration as one ensemble plan step ({why}): only such controllers can share a launch")
         if c.num_members != first.num_members:
             raise ValueError(f"fleet member {i} differs from member 0 in the number of plants M: {c.num_members} against {first.num_members}")
-        want = None
-        for j, m in enumerate(c._members):  # every plant against fleet member 0's plant 0: one structure and one kernel build for the launch
-            if m is first.model or m._blob == first.model._blob:
-                continue
-            want = want or image_sections(first.model._blob)
-            for name, x, y in zip(("header", "float section", "int section"), image_sections(m._blob), want):
-                if (x != y and name != "float section") or len(x) != len(y):
-                    raise ValueError(f"fleet member {i}: plant {j} has another model image than member 0's plant 0: the {name} of its image differs")
-            if m.build() != first.model.build() or m.self_collision != first.model.self_collision:
-                raise ValueError(f"fleet member {i}: plant {j} has another kernel build than member 0's plant 0: the kernel build or the self-collision setting differs")
+        self._check_plants(i, c, first)
         super()._check_member(i, c, first)
-
-    def _models(self) -> GpuModelSet:
-        """The plants of the launch: member 0's M where every member's plants are byte-identical to them, list for list; else all B * M, controller-major.  Rebuilt when
-        a member's plant was exchanged between plan steps (told by identity, as `ControllerFleet._models` tells it)."""
-        lists = [c._members for c in self.controllers]
-        key = tuple(m for plants in lists for m in plants)
-        if self._model_set is not None and len(key) == len(self._set_key) and all(a is b for a, b in zip(key, self._set_key)):
-            return self._model_set
-        shared = all(all(a is b or a._blob == b._blob for a, b in zip(plants, lists[0])) for plants in lists[1:])
-        self._model_set = GpuModelSet(list(lists[0]) if shared else list(key))
-        self._set_key = key
-        return self._model_set
 
     def _trace_floats(self) -> int:
         return 0  # (no trace buffer, as for the ensemble call: a member stages its trace elites' knots and re-rolls them on its plant 0)

@@ -28,6 +28,7 @@ from judo_amd.ensemble import MAX_ENSEMBLE, EnsembleController, check_task
 from judo_amd.ensemble_fleet import EnsembleFleet, check_fleet_descriptions, fleet_descriptions, fleet_worst
 from judo_amd.fleet import _FleetBuffers
 from judo_amd.optimizers import get_registered_optimizers
+from judo_amd.plants import make_for
 from judo_amd.tasks import FR3Pick, Task
 
 
@@ -112,25 +113,15 @@ class FR3EnsembleFleet(EnsembleFleet):
 
 
 def _fr3_parts(optimizer: str, self_collision: bool):
-    """`FR3Pick(self_collision)`, the registered optimizer and the controller configuration, with the task's overrides."""
-    opts = get_registered_optimizers()
-    if optimizer not in opts:
-        raise ValueError(f"Optimizer {optimizer} not found in optimizer registry.")
-    task = FR3Pick(self_collision=self_collision)
-    opt_cls, opt_cfg_cls = opts[optimizer]
-    opt_cfg = opt_cfg_cls()
-    opt_cfg.set_override(task.name)
-    ctrl_cfg = ControllerConfig()
-    ctrl_cfg.set_override(task.name)
-    return ctrl_cfg, task, opt_cls(opt_cfg, task.nu)
+    """The controller configuration, `FR3Pick(self_collision)` and the registered optimizer, with the task's overrides: `make_for`'s three parts, unassembled."""
+    return make_for(lambda *parts, device: parts, FR3Pick(self_collision=self_collision), optimizer)
 
 
 def make_fr3_ensemble_controller(optimizer: str, descriptions: Sequence[dict], worst: int | None = None, self_collision: bool = False,
                                  device: torch.device | None = None) -> FR3EnsembleController:
     """`make_ensemble_controller` for fr3_pick: `FR3Pick(self_collision)` and the registered optimizer (with the task's overrides) around `descriptions`, M model
     descriptions of that task.  Member 0 is the nominal plant.  `worst`: how many of a candidate's largest member costs are averaged; None: all M, the mean."""
-    ctrl_cfg, task, opt = _fr3_parts(optimizer, self_collision)
-    return FR3EnsembleController(ctrl_cfg, task, opt, descriptions, worst=worst, device=device)
+    return make_for(FR3EnsembleController, FR3Pick(self_collision=self_collision), optimizer, descriptions, worst=worst, device=device)
 
 
 def make_fr3_ensemble_fleet(optimizer: str, B: int, descriptions: Sequence, worst=None, self_collision: bool = False, device: torch.device | None = None) -> FR3EnsembleFleet:

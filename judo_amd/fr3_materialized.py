@@ -22,7 +22,8 @@ import torch
 
 from judo_amd.ensemble import check_descriptions
 from judo_amd.fr3_ensemble import check_self_collision
-from judo_amd.materialized import MaterializedEnsembleController, MaterializedRandomizedController, _make, check_task
+from judo_amd.materialized import MaterializedEnsembleController, MaterializedRandomizedController, check_task
+from judo_amd.plants import make_for
 from judo_amd.tasks import Task
 
 
@@ -72,7 +73,7 @@ def make_fr3_materialized_ensemble_controller(task: str | Task, optimizer: str, 
     subclass of `FR3Pick` with a reward or hooks of its own -- and the registered optimizer (fused or plugin, with the task's overrides) around `descriptions`, M model
     descriptions derived from the task's own (`models.scaled_description(task.desc, ...)`).  Member 0 is the nominal plant.  `worst`: how many of a candidate's largest
     member costs are averaged; None: all M, the mean."""
-    return _make(FR3MaterializedEnsembleController, task, optimizer, descriptions, device, worst=worst)
+    return make_for(FR3MaterializedEnsembleController, task, optimizer, descriptions, worst=worst, device=device)
 
 
 def make_fr3_materialized_randomized_controller(task: str | Task, optimizer: str, descriptions: Sequence[dict], blocks: int | None = None,
@@ -80,7 +81,7 @@ def make_fr3_materialized_randomized_controller(task: str | Task, optimizer: str
     """`materialized.make_materialized_randomized_controller` for fr3_pick, the task as for `make_fr3_materialized_ensemble_controller`.  `blocks`: the number G of rollout
     blocks, None: M; `weights`: M non-negative numbers that `randomized.blocks_from_weights` turns into the assignment, None: block g on plant g % M.  G must divide
     `num_rollouts` at the plan step."""
-    return _make(FR3MaterializedRandomizedController, task, optimizer, descriptions, device, blocks=blocks, weights=weights)
+    return make_for(FR3MaterializedRandomizedController, task, optimizer, descriptions, blocks=blocks, weights=weights, device=device)
 
 
 __all__ = ["FR3MaterializedEnsembleController", "FR3MaterializedRandomizedController", "check_fr3_task", "make_fr3_materialized_ensemble_controller",

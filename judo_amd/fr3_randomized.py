@@ -17,8 +17,8 @@ import torch
 
 from judo_amd import _lib
 from judo_amd.config import ControllerConfig
-from judo_amd.fr3_ensemble import materialized_hint
-from judo_amd.optimizers import get_registered_optimizers
+from judo_amd.fr3_ensemble import check_self_collision, materialized_hint
+from judo_amd.plants import make_for
 from judo_amd.randomized import RandomizedController, check_task
 from judo_amd.tasks import FR3Pick, Task
 
@@ -39,9 +39,7 @@ class FR3RandomizedController(RandomizedController):
     def __init__(self, controller_config: ControllerConfig, task: Task, optimizer, descriptions: Sequence[dict], blocks: int | None = None,
                  weights: Sequence[float] | None = None, device: torch.device | None = None) -> None:
         self._check_task(task)
-        for i, d in enumerate(descriptions):
-            if bool(d.get("self_collision")) != bool(task.self_collision):
-                raise ValueError(f"description {i} differs from the task in self_collision: derive the descriptions from FR3Pick(self_collision={bool(task.self_collision)}).desc")
+        check_self_collision(descriptions, task.self_collision)
         super().__init__(controller_config, task, optimizer, descriptions, blocks=blocks, weights=weights, device=device)
 
     def _hint(self, why: str) -> str:
@@ -56,16 +54,7 @@ def make_fr3_randomized_controller(optimizer: str, descriptions: Sequence[dict],
     """`make_randomized_controller` for fr3_pick: `FR3Pick(self_collision)` and the registered optimizer (with the task's overrides) around `descriptions`, M model
     descriptions of that task.  Member 0 is the nominal plant.  `blocks`: the number G of rollout blocks, None: M; `weights`: M non-negative numbers that
     `blocks_from_weights` turns into the assignment, None: block g on plant g % M."""
-    opts = get_registered_optimizers()
-    if optimizer not in opts:
-        raise ValueError(f"Optimizer {optimizer} not found in optimizer registry.")
-    task = FR3Pick(self_collision=self_collision)
-    opt_cls, opt_cfg_cls = opts[optimizer]
-    opt_cfg = opt_cfg_cls()
-    opt_cfg.set_override(task.name)
-    ctrl_cfg = ControllerConfig()
-    ctrl_cfg.set_override(task.name)
-    return FR3RandomizedController(ctrl_cfg, task, opt_cls(opt_cfg, task.nu), descriptions, blocks=blocks, weights=weights, device=device)
+    return make_for(FR3RandomizedController, FR3Pick(self_collision=self_collision), optimizer, descriptions, blocks=blocks, weights=weights, device=device)
 
 
 __all__ = ["FR3RandomizedController", "make_fr3_randomized_controller"]

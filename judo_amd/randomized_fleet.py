@@ -24,7 +24,7 @@ from judo_amd.distributed import world_info
 from judo_amd.ensemble import MAX_ENSEMBLE
 from judo_amd.ensemble_fleet import MAX_ENSEMBLE_FLEET, check_fleet_descriptions, fleet_descriptions
 from judo_amd.fleet import ControllerFleet, _FleetBuffers, refuse_fr3_randomized
-from judo_amd.models import image_sections
+from judo_amd.plants import PlantFleet
 from judo_amd.randomized import MAX_PLANT_BLOCKS, RandomizedController, blocks_from_weights, check_task, make_randomized_controller
 from judo_amd.tasks import get_registered_tasks
 
@@ -79,7 +79,7 @@ def fleet_assignments(B: int, M: int, G: int, weights) -> list[list[int]]:
     return out
 
 
-class RandomizedFleet(ControllerFleet):
+class RandomizedFleet(PlantFleet, ControllerFleet):
     """B `RandomizedController`s of one task and optimizer kind whose plan steps run as one launch.  `fleet[i]` is an ordinary `RandomizedController`: `update_states`,
     `optimizer.seed`, `action(t)`, `traces`, `rewards`, `plant_of_rollout`, `plant_rewards()`, the `assignment` setter, `set_weights` and `set_member` work per member as
     they do on a controller alone, and take effect at the fleet's next plan step."""
@@ -87,7 +87,6 @@ class RandomizedFleet(ControllerFleet):
     _randomized_members = True
 
     def __init__(self, controllers: Sequence[RandomizedController]) -> None:
-        self._set_key: tuple = ()
         if len(controllers) > MAX_ENSEMBLE_FLEET:
             raise ValueError(f"a fleet of {len(controllers)} randomised controllers exceeds the {MAX_ENSEMBLE_FLEET} of a launch (include/judo_amd.h JH_MAX_ENSEMBLE_FLEET)")
         super().__init__(controllers)
@@ -109,16 +108,7 @@ class RandomizedFleet(ControllerFleet):
             raise ValueError(f"fleet member {i} differs from member 0 in the number of blocks G: {c.blocks} against {first.blocks} (G is a grid dimension of the launch)")
         if i == 0:
             check_fleet_blocks(len(self.controllers), c.blocks)
-        want = None
-        for j, m in enumerate(c._members):  # every plant against fleet member 0's plant 0: one structure and one kernel build for the launch
-            if m is first.model or m._blob == first.model._blob:
-                continue
-            want = want or image_sections(first.model._blob)
-            for name, x, y in zip(("header", "float section", "int section"), image_sections(m._blob), want):
-                if (x != y and name != "float section") or len(x) != len(y):
-                    raise ValueError(f"fleet member {i}: plant {j} has another model image than member 0's plant 0: the {name} of its image differs")
-            if m.build() != first.model.build() or m.self_collision != first.model.self_collision:
-                raise ValueError(f"fleet member {i}: plant {j} has another kernel build than member 0's plant 0: the kernel build or the self-collision setting differs")
+        self._check_plants(i, c, first)
         super()._check_member(i, c, first)
 
     def update_action(self) -> None:
@@ -127,18 +117,6 @@ class RandomizedFleet(ControllerFleet):
         if N > 0 and N % G != 0:  # (a live change of num_rollouts; the members agree in both, _check_member)
             raise ValueError(f"num_rollouts % blocks != 0: {N} rollouts do not split into {G} equal blocks")
         super().update_action()
-
-    def _models(self) -> GpuModelSet:
-        """The plants of the launch: member 0's M where every member's plants are byte-identical to them, list for list; else all B * M, controller-major.  Rebuilt when
-        a member's plant was exchanged between plan steps (told by identity, as `ControllerFleet._models` tells it)."""
-        lists = [c._members for c in self.controllers]
-        key = tuple(m for plants in lists for m in plants)
-        if self._model_set is not None and len(key) == len(self._set_key) and all(a is b for a, b in zip(key, self._set_key)):
-            return self._model_set
-        shared = all(all(a is b or a._blob == b._blob for a, b in zip(plants, lists[0])) for plants in lists[1:])
-        self._model_set = GpuModelSet(list(lists[0]) if shared else list(key))
-        self._set_key = key
-        return self._model_set
 
     def _trace_floats(self) -> int:
         return 0  # (no trace buffer, as for the randomised call: a member stages its trace elites' knots and re-rolls them on its plant 0)

@@ -16,24 +16,22 @@ from __future__ import annotations
 import warnings
 from typing import Sequence
 
-import numpy as np
 import torch
 
 from judo_amd import _lib
 from judo_amd.config import ControllerConfig
 from judo_amd.controller import Controller
 from judo_amd.distributed import Shard
-from judo_amd.models import layout
-from judo_amd.optimizers import get_registered_optimizers
-from judo_amd.randomized import blocks_from_weights, check_assignment, plant_of_rollout
-from judo_amd.tasks import Task, get_registered_tasks
+from judo_amd.plants import Assignment, PlantSet, WorstCase, make_for, spline_controls
+from judo_amd.tasks import Task
 from judo_amd.tree_model import MAX_TREE_PLANTS, check_tree_descriptions
 
 POLICY_OUTPUT_DIM = 12
 
 
-class _SpotPlantController(Controller):
-    """What the two controllers share: the admission of task and descriptions, the `SpotPlantSet`, `set_member`, the counters, the refusal of the sharded path."""
+class _SpotPlantController(PlantSet, Controller):
+    """What the two controllers share: the admission of task and descriptions, the `SpotPlantSet` behind `plants.PlantSet`'s `set_member`, the counters, the refusal of
+    the sharded path."""
 
     _spot_plants = True  # (the fleets refuse such a member: fleet.refuse_fr3_randomized)
     _kind = "plant"  # for messages
@@ -45,31 +43,17 @@ class _SpotPlantController(Controller):
                              f"locomotion policy and has a one-call plan step: judo_amd.{self._other_maker} makes its controller")
         check_tree_descriptions(descriptions)
         self._descriptions = list(descriptions)
-        task.desc = self._descriptions[0]
-        task._layout, task._ctrlrange, task._jadr, task._gpu = layout(task.desc), None, None, None
         super().__init__(controller_config, task, optimizer, device=device)
+
+    def _make_set(self) -> None:
         from judo_amd.policy import SpotPlantSet
 
         self.plants = SpotPlantSet(self._descriptions, self.device, self_collision=self.rollout_backend.engine.self_collision)
 
-    @property
-    def descriptions(self) -> list[dict]:
-        return list(self._descriptions)
-
-    @property
-    def num_members(self) -> int:
-        return len(self._descriptions)
-
-    def set_member(self, b: int, description: dict) -> None:
-        """Replace member b's plant (`SpotPlantSet.set_member`: the library's checks; synchronous -- between plan steps).  b = 0 replaces the nominal plant too."""
-        b = int(b)
-        if not 0 <= b < len(self._descriptions):
-            raise ValueError(f"member {b} of a set of {len(self._descriptions)} plants")
+    def _replace_plant(self, b: int, description: dict) -> None:
+        """`SpotPlantSet.set_member`: the library's checks."""
         self.plants.set_member(b, description)
-        self._descriptions[b] = description
         if b == 0:
-            self.task.desc = description
-            self.task._layout, self.task._ctrlrange, self.task._jadr = layout(description), None, None
             self.rollout_backend.engine = self.plants.engines[0]
 
     def _iteration_shape(self, world: int, nrm) -> str:
@@ -94,16 +78,12 @@ class _SpotPlantController(Controller):
         return st
 
     def _spline_commands(self, nom_d, noise_p, ldn: int, sig_d, lohi_d, knots_nku, W, shard: Shard, H: int, K: int, stream) -> tuple[torch.Tensor, torch.Tensor]:
-        """The candidates' controls at the rollout times (`jh_spline_controls`, once) and the policy commands they map to."""
-        lib, nu = _lib.lib(), self.nu
-        controls = torch.empty((shard.count, H, nu), dtype=torch.float32, device=self.device)
-        st = lib.jh_spline_controls(_lib.ptr(W), _lib.ptr(knots_nku), _lib.ptr(nom_d), noise_p, ldn, _lib.ptr(sig_d), _lib.ptr(lohi_d) if knots_nku is None else None,
-                                    shard.count, shard.offset, H, K, nu, _lib.ptr(controls), stream)
-        _lib.check(st, "jh_spline_controls")
+        """The candidates' controls at the rollout times (`plants.spline_controls`, once) and the policy commands they map to."""
+        controls = spline_controls(self, nom_d, noise_p, ldn, sig_d, lohi_d, knots_nku, W, shard, H, K, stream)
         return controls, self.task.task_to_sim_ctrl(controls).to(torch.float32).contiguous()
 
 
-class SpotEnsembleController(_SpotPlantController):
+class SpotEnsembleController(WorstCase, _SpotPlantController):
     """A Spot `Controller` whose iteration rolls every candidate out on M plants and updates on the aggregated costs.  `rewards` are the negated aggregated costs;
     `member_costs` / `member_rewards` the (M, N) costs behind them; `worst` may be set between plan steps, and `set_member(b, description)` replaces one plant.
     The carried state is the (M * N, 12) policy outputs and the (M * N, nv) warm start of the plant rollout, reset wherever the controller resets its own."""
@@ -115,34 +95,8 @@ class SpotEnsembleController(_SpotPlantController):
                  device: torch.device | None = None) -> None:
         self._plant_backend = None
         self._plant_policy_out: torch.Tensor | None = None
-        self._member_costs: torch.Tensor | None = None
-        M = len(descriptions)
-        if worst is not None and not 1 <= int(worst) <= M:
-            raise ValueError(f"worst = {worst} outside [1, M = {M}]")
-        self._worst = M if worst is None else int(worst)
+        self._init_worst(worst, len(descriptions))
         super().__init__(controller_config, task, optimizer, descriptions, device=device)
-
-    @property
-    def worst(self) -> int:
-        """How many of a rollout's largest member costs are averaged: 1 = the worst case, M = the mean."""
-        return self._worst
-
-    @worst.setter
-    def worst(self, j: int) -> None:
-        if not 1 <= int(j) <= len(self._descriptions):
-            raise ValueError(f"worst = {j} outside [1, M = {len(self._descriptions)}]")
-        self._worst = int(j)
-
-    @property
-    def member_costs(self) -> np.ndarray:
-        """(M, N) fp32: member m's cost of every candidate of the last iteration."""
-        if self._member_costs is None:
-            raise RuntimeError("member_costs needs a completed update_action()")
-        return self._member_costs.cpu().numpy()
-
-    @property
-    def member_rewards(self) -> np.ndarray:
-        return -self.member_costs.astype(np.float64)
 
     def reset(self) -> None:
         super().reset()
@@ -176,17 +130,16 @@ class SpotEnsembleController(_SpotPlantController):
         pb, policy_out = self._carried(M * N)
         nx = self.plants.nq + self.plants.nv
         states, sensors = pb.rollout_plants(self.plants, x0_d, nx, 1, M, list(range(M)), commands.repeat(M, 1, 1), policy_out, cutoff_time=self.rollout_cutoff_time)
-        if self._member_costs is None or tuple(self._member_costs.shape) != (M, N):
-            self._member_costs = torch.empty((M, N), dtype=torch.float32, device=self.device)
+        rows = self._member_cost_rows(N)
         for m in range(M):  # the reward per member, in the shapes a plain controller gives it
-            self._score_rollout(states[m * N : (m + 1) * N], sensors[m * N : (m + 1) * N], controls, out=self._member_costs[m])
+            self._score_rollout(states[m * N : (m + 1) * N], sensors[m * N : (m + 1) * N], controls, out=rows[m])
         self.last_rollout = (states[:N], sensors[:N], controls)  # member 0, the nominal plant
         costs = torch.empty(N, dtype=torch.float32, device=self.device)
-        _lib.check(lib.jh_ensemble_costs(_lib.ptr(self._member_costs), M, N, N, self._worst, _lib.ptr(costs), stream), "jh_ensemble_costs")
+        _lib.check(lib.jh_ensemble_costs(_lib.ptr(rows), M, N, N, self._worst, _lib.ptr(costs), stream), "jh_ensemble_costs")
         return costs
 
 
-class SpotRandomizedController(_SpotPlantController):
+class SpotRandomizedController(Assignment, _SpotPlantController):
     """A Spot `Controller` whose iteration rolls block g of its candidates out on plant `assignment[g]` and updates on the N costs as they are.  `assignment` (G plant
     indices, default g % M) may be set between plan steps -- it travels in the kernel arguments; `plant_of_rollout` and `plant_rewards()` say which plant a reward
     belongs to, and `set_member(b, description)` replaces one plant.  The carried policy outputs and warm start are the controller's own N rows."""
@@ -196,50 +149,8 @@ class SpotRandomizedController(_SpotPlantController):
 
     def __init__(self, controller_config: ControllerConfig, task: Task, optimizer, descriptions: Sequence[dict], blocks: int | None = None,
                  weights: Sequence[float] | None = None, device: torch.device | None = None) -> None:
-        M = len(descriptions)
-        G = M if blocks is None else int(blocks)
-        if weights is not None and len(weights) != M:
-            raise ValueError(f"{len(weights)} weights for M = {M} plants")
-        self._assignment = check_assignment(blocks_from_weights(weights, G) if weights is not None else [g % max(M, 1) for g in range(max(G, 0))], M)
-        self._assignment_used: list[int] | None = None  # the assignment of the last plan step: what `rewards` were rolled out on
+        self._init_assignment(blocks, weights, len(descriptions))
         super().__init__(controller_config, task, optimizer, descriptions, device=device)
-
-    @property
-    def blocks(self) -> int:
-        return len(self._assignment)
-
-    @property
-    def assignment(self) -> list[int]:
-        """The plant of every rollout block, G indices in [0, M), validated when set.  Setting it takes effect at the next plan step and costs nothing on the device;
-        `update_action` raises ValueError if the G blocks do not divide `num_rollouts` then."""
-        return list(self._assignment)
-
-    @assignment.setter
-    def assignment(self, a: Sequence[int]) -> None:
-        self._assignment = check_assignment(a, len(self._descriptions))
-
-    def set_weights(self, weights: Sequence[float], blocks: int | None = None) -> None:
-        """`assignment = blocks_from_weights(weights, blocks)`; `blocks` None keeps the number of blocks."""
-        if len(weights) != len(self._descriptions):
-            raise ValueError(f"{len(weights)} weights for M = {len(self._descriptions)} plants")
-        self.assignment = blocks_from_weights(weights, len(self._assignment) if blocks is None else blocks)
-
-    @property
-    def plant_of_rollout(self) -> np.ndarray:
-        """(N,) ints: the plant every rollout of the last plan step ran on (of the next one, before the first)."""
-        if self._assignment_used is None:
-            return plant_of_rollout(self._assignment, self.optimizer.num_rollouts)
-        return plant_of_rollout(self._assignment_used, int(self.costs_device.numel()))
-
-    def plant_rewards(self) -> np.ndarray:
-        """(M,) fp64: the mean of `rewards` over the rollouts of every plant, NaN for a plant with no block."""
-        r, plant = np.asarray(self.rewards, dtype=np.float64), self.plant_of_rollout
-        return np.array([r[plant == m].mean() if (plant == m).any() else np.nan for m in range(len(self._descriptions))])
-
-    def update_action(self) -> None:
-        if self.optimizer_cfg.num_rollouts > 0 and self.optimizer_cfg.num_rollouts % len(self._assignment) != 0:  # (a live change of num_rollouts)
-            raise ValueError(f"num_rollouts % blocks != 0: {self.optimizer_cfg.num_rollouts} rollouts do not split into {len(self._assignment)} equal blocks")
-        super().update_action()
 
     def _materialised_costs(self, x0_d, nom_d, noise_p, ldn: int, sig_d, lohi_d, knots_nku, W, shard: Shard, H: int, K: int, stream) -> torch.Tensor:
         N, a = shard.count, list(self._assignment)
@@ -252,35 +163,19 @@ class SpotRandomizedController(_SpotPlantController):
         return self._score_rollout(states, sensors, controls)
 
 
-def _make(cls, task: str | Task, optimizer: str, descriptions: Sequence[dict], device, **kw):
-    tasks, opts = get_registered_tasks(), get_registered_optimizers()
-    if isinstance(task, str):
-        if task not in tasks:
-            raise ValueError(f"Task {task} not found in task registry.")
-        task = tasks[task][0]()
-    if optimizer not in opts:
-        raise ValueError(f"Optimizer {optimizer} not found in optimizer registry.")
-    opt_cls, opt_cfg_cls = opts[optimizer]
-    opt_cfg = opt_cfg_cls()
-    opt_cfg.set_override(task.name)
-    ctrl_cfg = ControllerConfig()
-    ctrl_cfg.set_override(task.name)
-    return cls(ctrl_cfg, task, opt_cls(opt_cfg, task.nu), descriptions, device=device, **kw)
-
-
 def make_spot_ensemble_controller(task: str | Task, optimizer: str, descriptions: Sequence[dict], worst: int | None = None,
                                   device: torch.device | None = None) -> SpotEnsembleController:
     """`make_controller` for one Spot controller over M plants: the registered task and optimizer (with the task's overrides) around `descriptions`, M descriptions of the
     task's model (`models.scaled_description(task.desc, body_mass=..., geom_friction=..., actuator_kp=...)`).  Member 0 is the nominal plant.  `worst`: how many of a
     candidate's largest member costs are averaged; None: all M, the mean."""
-    return _make(SpotEnsembleController, task, optimizer, descriptions, device, worst=worst)
+    return make_for(SpotEnsembleController, task, optimizer, descriptions, worst=worst, device=device)
 
 
 def make_spot_randomized_controller(task: str | Task, optimizer: str, descriptions: Sequence[dict], blocks: int | None = None, weights: Sequence[float] | None = None,
                                     device: torch.device | None = None) -> SpotRandomizedController:
     """`make_controller` for one Spot controller whose candidates are spread over M plants.  `blocks`: the number G of rollout blocks, None: M; `weights`: M non-negative
     numbers that `randomized.blocks_from_weights` turns into the assignment, None: block g on plant g % M.  G must divide `num_rollouts` at the plan step."""
-    return _make(SpotRandomizedController, task, optimizer, descriptions, device, blocks=blocks, weights=weights)
+    return make_for(SpotRandomizedController, task, optimizer, descriptions, blocks=blocks, weights=weights, device=device)
 
 
 __all__ = ["MAX_TREE_PLANTS", "SpotEnsembleController", "SpotRandomizedController", "check_tree_descriptions", "make_spot_ensemble_controller",
