@@ -50,6 +50,8 @@ enum jh_spline_kind { JH_SPLINE_ZERO = 0, JH_SPLINE_LINEAR = 1, JH_SPLINE_CUBIC 
 #define JH_MAX_ENSEMBLE_FLEET 256 /* controllers of one jh_plan_step_ensemble_batch call (their `worst` travel in the kernel arguments, a byte each) */
 #define JH_MAX_PLANT_BLOCKS 64 /* rollout blocks of one jh_plan_step_randomized call (their plants travel in the kernel arguments, a byte each) */
 #define JH_MAX_FLEET_PLANT_BLOCKS 256 /* B * G, the (controller, block) pairs of one jh_plan_step_randomized_batch call: the bytes of its table in the kernel arguments */
+#define JH_MAX_ID_HORIZON 64 /* steps of a recorded window that jh_plant_residuals scores: the wave width, a lane per step */
+#define JH_MAX_ID_QUATS 4 /* quaternions of a state row that jh_plant_residuals aligns (their offsets travel in the kernel arguments) */
 
 const char* jh_last_error(void);
 int jh_version(void);
@@ -671,6 +673,27 @@ int jh_rollout_materialize_plants(const jh_model_set* set, const int* plant_of_b
  * JH_ERR_UNSUPPORTED: a set that is not of fr3_pick models (jh_rollout_materialize_plants rolls it out). */
 int jh_fr3_rollout_materialize_plants(const jh_model_set* set, const int* plant_of_block, int G, int n, const float* x0, int x0_batched, const float* controls, int controls_shared,
                                       int H, float* states, float* sensors, void* stream);
+
+/* ---- jh_plant_residuals: the scoring half of plant identification.  W recorded windows of H steps were rolled out on all M plants of a set (one materialise launch on
+ * plants: M blocks of W rows, the windows' x0 tiled M times, their controls shared), and err[m * ld + w] is the weighted squared prediction error of plant m on window w.
+ * pred is what that launch wrote, (M * W, H, nx) with block m = rows [m * W, (m + 1) * W); obs (W, H, nx) the observed states; weight (nx) per-coordinate weights,
+ * 1 / sigma^2.  quat_adr is a HOST array of nquat offsets into a state row, each naming four consecutive coordinates of a unit quaternion inside [0, nq); it travels in
+ * the kernel arguments, nquat <= JH_MAX_ID_QUATS.  H <= JH_MAX_ID_HORIZON, the wave width.  What lies between W and ld in a row of err is not written.
+ * The arithmetic is fixed, all of it in fp32 with every product and sum rounded on its own (no fused multiply-add), so that a host restatement matches bit for bit
+ * (judo_amd/identify.py plant_residuals_host):
+ *   per step and quaternion   dot = ((p0 * o0 + p1 * o1) + p2 * o2) + p3 * o3; if dot < 0 the prediction is compared against -o: a pose and its antipodal quaternion
+ *                             have error exactly 0;
+ *   per coordinate d          e = p - o', t_d = (weight[d] * e) * e;
+ *   per step h                s_h = ((t_0 + t_1) + t_2) + ..., d ascending;
+ *   per window                v[0..63] = s_0 .. s_{H-1}, then +0.0; six halvings v[i] = v[i] + v[i + k], k = 32, 16, 8, 4, 2, 1; err = v[0] -- the order of a wave-wide
+ *                             butterfly with one wave per (m, w) pair and lane h holding step h.  The padding is exact: every term is non-negative.
+ * Non-finite inputs are outside the contract: NaN in gives NaN out (judo_amd.identify.PlantEstimator counts such an error as +inf).
+ * JH_ERR_INVALID before anything is enqueued, jh_last_error naming the argument: a null pred, obs, weight or err; M outside 1..JH_MAX_ENSEMBLE; W < 1; H outside
+ * 1..JH_MAX_ID_HORIZON; nx < 1; nq outside 0..nx; ld < W; nquat outside 0..JH_MAX_ID_QUATS; nquat > 0 with a null quat_adr; an offset that is negative, reaches past nq
+ * with its four coordinates, or overlaps another offset; M * W beyond the workgroups of one launch. */
+int jh_plant_residuals(const float* pred /* DEVICE, (M * W, H, nx) */, const float* obs /* DEVICE, (W, H, nx) */, const float* weight /* DEVICE, nx */,
+                       const int* quat_adr /* HOST, nquat offsets, or NULL with nquat = 0 */, int nquat, int M, int W, int H, int nx, int nq, float* err /* DEVICE, M x ld */,
+                       int ld, void* stream);
 
 #ifdef __cplusplus
 }

@@ -51,6 +51,7 @@ _SIGNATURES = {
     "jh_rollout_materialize": (C.c_int, [C.c_void_p, f32p, C.c_int, f32p, C.c_int, C.c_int, f32p, f32p, C.c_void_p]),
     "jh_rollout_materialize_plants": (C.c_int, [C.c_void_p, C.POINTER(C.c_int), C.c_int, C.c_int, f32p, C.c_int, f32p, C.c_int, C.c_int, f32p, f32p, C.c_void_p]),
     "jh_fr3_rollout_materialize_plants": (C.c_int, [C.c_void_p, C.POINTER(C.c_int), C.c_int, C.c_int, f32p, C.c_int, f32p, C.c_int, C.c_int, f32p, f32p, C.c_void_p]),
+    "jh_plant_residuals": (C.c_int, [f32p, f32p, f32p, C.POINTER(C.c_int), C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, f32p, C.c_int, C.c_void_p]),
     "jh_task_reward": (C.c_int, [C.c_void_p, f32p, f32p, f32p, f32p, C.c_int, C.c_int, C.c_int, f32p, C.c_void_p]),
     "jh_noise_normal": (C.c_int, [C.c_ulonglong, C.c_uint, C.c_int, C.c_int, C.c_int, f32p, C.c_int, C.c_void_p]),
     "jh_sample_knots": (C.c_int, [f32p, f32p, C.c_int, f32p, f32p, C.c_int, C.c_int, C.c_int, C.c_int, f32p, C.c_void_p]),
@@ -151,6 +152,8 @@ MAX_ENSEMBLE = 32  # JH_MAX_ENSEMBLE: members of a model set that jh_plan_step_e
 MAX_ENSEMBLE_FLEET = 256  # JH_MAX_ENSEMBLE_FLEET: controllers of one jh_plan_step_ensemble_batch call
 MAX_PLANT_BLOCKS = 64  # JH_MAX_PLANT_BLOCKS: rollout blocks of one jh_plan_step_randomized call
 MAX_FLEET_PLANT_BLOCKS = 256  # JH_MAX_FLEET_PLANT_BLOCKS: B * G, the (controller, block) pairs of one jh_plan_step_randomized_batch call
+MAX_ID_HORIZON = 64  # JH_MAX_ID_HORIZON: steps of a recorded window that jh_plant_residuals scores
+MAX_ID_QUATS = 4  # JH_MAX_ID_QUATS: quaternions of a state row that jh_plant_residuals aligns
 
 
 class JudoAmdError(RuntimeError):
