@@ -23,7 +23,8 @@ from __future__ import annotations
 
 import ctypes as C
 import warnings
-from typing import Any
+from dataclasses import dataclass
+from typing import Any, NamedTuple
 
 import numpy as np
 import torch
@@ -71,7 +72,6 @@ class _PlanBuffers:
         self.knots_nku: torch.Tensor | None = None
         self.mom: torch.Tensor | None = None
 
-
     def size_out(self, n: int) -> None:
         """The output block (nominal | sigma | trace elites' records) and its pinned host image hold at least n floats."""
         if getattr(self, "out", None) is not None and self.out.numel() >= n:
@@ -80,6 +80,54 @@ class _PlanBuffers:
         self.out_host = torch.zeros(n, dtype=torch.float32).pin_memory()  # (zeros: MPPI / PS never write the sigma region, and a cast of uninitialised bits may meet a signalling NaN)
         self.out_np = self.out_host.numpy()
         self.out_host_ptr = self.out_host.data_ptr()
+
+
+class _Plan(NamedTuple):
+    """What is constant over one plan step (`Controller._begin_plan`), read by name everywhere.  (A NamedTuple, not a frozen dataclass: it is made once per plan step,
+    and its construction costs 0.5 us against 2 us -- a small plan step is 0.1 ms.)"""
+
+    N: int  # rollouts over all ranks
+    K: int  # knots
+    nu: int
+    H: int  # rollout steps
+    world: int
+    shard: Shard  # this rank's rollouts
+    nrm: Normalizer
+    W: torch.Tensor  # (H, K) spline matrix, device
+    x0: np.ndarray  # the state the plan starts from, fp64
+    new_times: np.ndarray  # the knot times of the new plan
+    fused_opt: bool  # a `FusedOptimizer`: the fused or the materialise iteration, else the candidates iteration
+    E: int  # trace elites
+    tp: np.ndarray  # the task parameters (their count sizes the buffers)
+
+
+@dataclass(slots=True)
+class _IterState:
+    """What the iterations of one plan step hand from one to the next and to `_end_plan`: every field an iteration can set, with its value before the first one."""
+
+    nominal_n: np.ndarray  # the nominal in normalised units: `_begin_plan` sets it, every iteration's update replaces it
+    stream: Any = None  # the launch stream of the plan step
+    scale: np.ndarray | None = None  # the normaliser's raw = center + scale * normalised of this iteration (`_iteration_inputs`)
+    center: np.ndarray | None = None
+    noise: torch.Tensor | None = None  # (K, nu, shard.count) of a fused iteration, with its address and row stride
+    noise_p: int | None = None
+    ldn: int = 0
+    knots_out: torch.Tensor | None = None  # where the rollout kernel writes the candidates (`keep_candidates`)
+    knots_nku: torch.Tensor | None = None  # explicit (shard.count, K, nu) candidates of a candidates iteration; None: they are sampled from the noise
+    trace_buf: tuple[torch.Tensor, int] | None = None  # (buffer, floats per rollout) when the rollout kernel wrote every rollout's trace sensors
+    stages: bool = False  # this iteration stages the trace records (`_stage_traces`, or the update's own records) behind its launch: the plan step's last one
+    costs: torch.Tensor | None = None  # the iteration's costs, device
+
+
+def spline_controls(ctrl: "Controller", plan: _Plan, b, st: _IterState) -> torch.Tensor:
+    """The candidates' controls at the rollout times, (shard.count, H, nu) on the controller's device (`jh_spline_controls`, once per iteration of a materialise path):
+    of the explicit candidates `st.knots_nku`, or sampled from the block's nominal and sigma and the iteration's noise, clipped to the bounds."""
+    shard, sampled = plan.shard, st.knots_nku is None
+    controls = torch.empty((shard.count, plan.H, ctrl.nu), dtype=torch.float32, device=ctrl.device)
+    rc = _lib.lib().jh_spline_controls(_lib.ptr(plan.W), _lib.ptr(st.knots_nku), _lib.ptr(b.nominal) if sampled else None, st.noise_p, st.ldn, _lib.ptr(b.sigma) if sampled else None,
+                                       _lib.ptr(b.lohi) if sampled else None, shard.count, shard.offset, plan.H, plan.K, ctrl.nu, _lib.ptr(controls), st.stream)
+    _lib.check(rc, "jh_spline_controls")
+    return controls
 
 
 class Controller:
@@ -416,32 +464,28 @@ class Controller:
         return self.optimizer.num_nodes <= self.model.max_fused_knots_at(self.num_timesteps)
 
     def update_action(self) -> None:
-        lib = _lib.lib()
         opt, task = self.optimizer, self.task
-        p = self._begin_plan()
-        N, K, nu, H, world, shard, nrm, nominal_n, W, x0, new_times, fused_opt, E, tp0 = p
-        b = self._buffers(shard.count, K, nu, task.nq + task.nv, len(tp0), opt.record_floats() if fused_opt else 0, E)
-        stream = self._stream = current_stream_ptr()
-        state: dict[str, Any] = dict(E=E, x0=x0, new_times=new_times)
+        plan, st = self._begin_plan()
+        b = self._buffers(plan.shard.count, plan.K, plan.nu, task.nq + task.nv, len(plan.tp), opt.record_floats() if plan.fused_opt else 0, plan.E)
+        st.stream = self._stream = current_stream_ptr()
         staged = False
 
         i = 0
         while i < self.max_opt_iters and not opt.stop_cond():
             task.pre_rollout(self.current_state)
-            if fused_opt:
+            if plan.fused_opt:
                 # the trace records of the (presumably) last iteration are enqueued before its result is waited for: their host cost hides behind the kernels
-                state["stage"] = (lambda: self._stage_traces(lib, b, state, shard, world, E, x0, new_times, K, nu, stream)) if i == self.max_opt_iters - 1 else None
-                nominal_n = self._fused_iteration(lib, b, nrm, nominal_n, W, shard, world, H, K, nu, N, stream, state)
-                staged = state["stage"] is not None
+                staged = st.stages = i == self.max_opt_iters - 1
+                self._fused_iteration(plan, b, st)
             else:
-                nominal_n = self._candidates_iteration(lib, b, nrm, nominal_n, W, shard, H, K, nu, N, stream, state)
+                self._candidates_iteration(plan, b, st)
             i += 1
-        self._end_plan(p, b, state, nominal_n, i, staged, stream)
+        self._end_plan(plan, b, st, i, staged)
 
-    def _begin_plan(self) -> tuple:
+    def _begin_plan(self) -> tuple[_Plan, _IterState]:
         """The host prelude of a plan step (controller.py:210-238): checks, the time shift of the nominal, the normaliser, `pre_optimization`, W.  Shared with
-        `ControllerFleet.update_action`, which runs it for every member in front of its one batched launch.  Returns (N, K, nu, H, world, shard, normaliser,
-        normalised nominal, W, x0, new knot times, fused optimizer?, trace elites, task params)."""
+        `ControllerFleet.update_action`, which runs it for every member in front of its one batched launch.  Returns the plan record and the iteration state the
+        plan step starts from: the shifted nominal in normalised units."""
         opt, task = self.optimizer, self.task
         if self.current_state.shape != (task.nq + task.nv,):
             raise ValueError(f"current state must have shape ({task.nq + task.nv},), got {self.current_state.shape}")
@@ -470,19 +514,19 @@ class Controller:
 
         W = self._weights(K, H)
         x0 = np.array(self.current_state, dtype=np.float64)
-        return (N, K, nu, H, world, shard, nrm, nominal_n, W, x0, new_times, self.uses_fused_optimizer, self._num_trace_elites(N), task.task_params(self.system_metadata))
+        plan = _Plan(N, K, nu, H, world, shard, nrm, W, x0, new_times, self.uses_fused_optimizer, self._num_trace_elites(N), task.task_params(self.system_metadata))
+        return plan, _IterState(nominal_n)
 
-    def _end_plan(self, p: tuple, b, state: dict, nominal_n: np.ndarray, iters: int, staged: bool, stream) -> None:
-        """The host epilogue of a plan step (controller.py:293-299): the trace stage if no iteration set it, the denormalised nominal, the new spline.  `p`: what `_begin_plan` returned."""
-        N, K, nu, H, world, shard, nrm, _, W, x0, new_times, fused_opt, E, tp0 = p
+    def _end_plan(self, plan: _Plan, b, st: _IterState, iters: int, staged: bool) -> None:
+        """The host epilogue of a plan step (controller.py:293-299): the trace stage if no iteration set it, the denormalised nominal, the new spline."""
         if iters > 0:
-            self.costs_device = state["costs"]
-            self.candidate_knots_device = state.get("knots_out")
+            self.costs_device = st.costs
+            self.candidate_knots_device = st.knots_out
             if not staged:
-                self._stage_traces(_lib.lib(), b, state, shard, world, E, x0, new_times, K, nu, stream)
-        self.last_shard = shard
-        self.nominal_knots = nrm.denormalize(nominal_n)  # with the statistics as updated in the loop (controller.py:296)
-        self.times = new_times
+                self._stage_traces(plan, b, st)
+        self.last_shard = plan.shard
+        self.nominal_knots = plan.nrm.denormalize(st.nominal_n)  # with the statistics as updated in the loop (controller.py:296)
+        self.times = plan.new_times
         self.update_spline(self.times, self.nominal_knots)
 
     def _pack_block(self, b: _PlanBuffers, nominal_raw: np.ndarray, sigma_raw: np.ndarray | None, lohi: np.ndarray, upload: bool = True) -> None:
@@ -565,84 +609,78 @@ class Controller:
             return "plan_step" if world == 1 and not self.force_shard_path else "plan_step_shard"
         return "update_fused" if fused_update and world == 1 else "separate"
 
-    def _fused_iteration(self, lib, b: _PlanBuffers, nrm: Normalizer, nominal_n: np.ndarray, W, shard: Shard, world: int, H: int, K: int, nu: int, N: int,
-                         stream, state: dict) -> np.ndarray:
-        opt = self.optimizer
-        shape = self._iteration_shape(world, nrm)
+    def _fused_iteration(self, plan: _Plan, b: _PlanBuffers, st: _IterState) -> None:
+        shard = plan.shard
+        shape = self._iteration_shape(plan.world, plan.nrm)
         one_call = shape in ("plan_step", "plan_step_shard")
-        scale, center = self._iteration_inputs(b, nrm, nominal_n, nu, upload=not one_call)  # (the plan-step calls upload the block themselves or read it in place)
-        noise = self._draw_noise(shard.count, shard.offset)  # (K, nu, shard.count), possibly a view into the full draw
+        self._iteration_inputs(plan, b, st, upload=not one_call)  # (the plan-step calls upload the block themselves or read it in place)
+        noise = st.noise = self._draw_noise(shard.count, shard.offset)  # (K, nu, shard.count), possibly a view into the full draw
         self._prefetch_args = (shard.count, shard.offset)
-        ldn, noise_p = int(noise.stride(1)), noise.data_ptr()
-        knots_out = None
+        ldn = st.ldn = int(noise.stride(1))
+        st.noise_p = noise.data_ptr()
+        st.knots_out = st.knots_nku = st.trace_buf = None
         if self.keep_candidates:
             # the rollout kernels write candidate (k, u) of local rollout n at [(k * nu + u) * ldn + n] with the NOISE's row stride (include/judo_amd.h):
             # a sharded draw is a column view of the full (K, nu, total) draw, so the buffer gets rows of that length and the shard's columns are handed out
             if b.knots_out is None or b.knots_out.shape[2] != ldn:
-                b.knots_out = torch.empty((K, nu, ldn), dtype=torch.float32, device=self.device)
-            knots_out = b.knots_out[:, :, : shard.count]
-        state.update(knots_out=knots_out, noise_p=noise_p, ldn=ldn, knots_nku=None, trace_buf=None)
-        if one_call:
-            E_t = self._plan_step(lib, b, shape, noise_p, ldn, knots_out, W, shard, world, H, K, nu, stream, state)
-        else:
-            n_res = 2 * K * nu if isinstance(getattr(opt, "sigma", None), np.ndarray) else K * nu  # nominal (| sigma) to copy down
-            E_t = self._rollout_update(lib, b, shape, nrm, noise_p, ldn, knots_out, W, shard, world, H, K, nu, N, n_res, stream, state)
-        return self._iteration_result(b, state, noise, noise_p, ldn, shard, H, K, nu, E_t, scale, center)
+                b.knots_out = torch.empty((plan.K, plan.nu, ldn), dtype=torch.float32, device=self.device)
+            st.knots_out = b.knots_out[:, :, : shard.count]
+        E_t = self._plan_step(plan, b, st, shape) if one_call else self._rollout_update(plan, b, st, shape)
+        self._iteration_result(plan, b, st, E_t)
 
-    def _iteration_inputs(self, b, nrm: Normalizer, nominal_n: np.ndarray, nu: int, upload: bool) -> tuple[np.ndarray, np.ndarray]:
-        """The optimizer's sigma (may advance CEM state) and the packed block x0 | nominal | sigma | task params | bounds in raw units.  Returns the normaliser's
-        (scale, center): every shipped normaliser is affine per actuator, raw = center + scale * normalised (judo_amd/normalization.py)."""
+    def _iteration_inputs(self, plan: _Plan, b, st: _IterState, upload: bool) -> None:
+        """The optimizer's sigma (may advance CEM state) and the packed block x0 | nominal | sigma | task params | bounds in raw units.  Leaves the normaliser's
+        (scale, center) in `st`: every shipped normaliser is affine per actuator, raw = center + scale * normalised (judo_amd/normalization.py)."""
+        nrm = plan.nrm
         sigma_n = np.asarray(self.optimizer.knot_sigma(), dtype=np.float64)  # normalised units
-        scale, center = nrm.noise_scale(), nrm.denormalize(np.zeros(nu))
-        nominal_raw = nrm.denormalize(nominal_n)
+        scale = st.scale = nrm.noise_scale()
+        st.center = nrm.denormalize(np.zeros(plan.nu))
+        nominal_raw = nrm.denormalize(st.nominal_n)
         sigma_raw = sigma_n * scale[None, :]
         self._pack_block(b, nominal_raw, sigma_raw, self._raw_bounds(nrm), upload=upload)
         self._last_sigma_raw, self._last_nominal_before = sigma_raw, nominal_raw.copy()
-        return scale, center
 
-    def _iteration_result(self, b, state: dict, noise, noise_p: int, ldn: int, shard: Shard, H: int, K: int, nu: int, E_t: int, scale: np.ndarray, center: np.ndarray) -> np.ndarray:
-        """What an iteration's update left in the pinned output block nominal | sigma | E_t trace records: the new nominal in normalised units, the CEM sigma refit,
-        the staged trace records."""
-        opt = self.optimizer
+    def _iteration_result(self, plan: _Plan, b, st: _IterState, E_t: int) -> None:
+        """What an iteration's update left in the pinned output block nominal | sigma | E_t trace records: the new nominal in normalised units (into `st`), the CEM
+        sigma refit, the staged trace records."""
+        opt, K, nu, scale = self.optimizer, plan.K, plan.nu, st.scale
         is_cem = isinstance(getattr(opt, "sigma", None), np.ndarray)
         n_res = 2 * K * nu if is_cem else K * nu  # nominal (| sigma); the trace records behind them carry an index column of int bit patterns and are not widened
         res = b.out_np[:n_res].astype(np.float64)
         if E_t:  # the update wrote the trace elites' records behind nominal | sigma, best first
-            stride = 2 + state["trace_buf"][1]
+            stride = 2 + st.trace_buf[1]
             self._traces = None
-            self._trace_stage = dict(kind="sensors", recs=b.out_np[2 * K * nu : 2 * K * nu + E_t * stride].copy(), stride=stride, E=int(state["E"]), x0=state["x0"],
-                                     times=np.array(state["new_times"]), order=self.spline_order, H=H, K=K, nu=nu, index_is_bits=True, sorted=True)
-        nominal_n = (res[: K * nu].reshape(K, nu) - center[None, :]) / scale[None, :]  # the update acted on the normalised candidates
+            self._trace_stage = dict(kind="sensors", recs=b.out_np[2 * K * nu : 2 * K * nu + E_t * stride].copy(), stride=stride, E=int(plan.E), x0=plan.x0,
+                                     times=np.array(plan.new_times), order=self.spline_order, H=plan.H, K=K, nu=nu, index_is_bits=True, sorted=True)
+        st.nominal_n = (res[: K * nu].reshape(K, nu) - st.center[None, :]) / scale[None, :]  # the update acted on the normalised candidates
         if is_cem:  # CEM: refit in normalised units
             opt.sigma = np.clip(res[K * nu : 2 * K * nu].reshape(K, nu) / scale[None, :], opt.sigma_min, opt.sigma_max)
         self._rewards, self._candidate_knots = None, None
-        self._last_fused = dict(b=b, noise=noise, noise_p=noise_p, ldn=ldn, shard=shard, K=K, nu=nu)
-        return nominal_n
+        self._last_fused = dict(b=b, noise=st.noise, noise_p=st.noise_p, ldn=st.ldn, shard=plan.shard, K=K, nu=nu)
 
-    def _trace_records(self, b: _PlanBuffers, state: dict, K: int, nu: int) -> tuple[int, int]:
+    def _trace_records(self, plan: _Plan, b: _PlanBuffers, st: _IterState) -> tuple[int, int]:
         """(count, row floats) of the trace elites' records the update writes behind nominal | sigma -- in the iteration that stages the traces, when the rollout
         kernel wrote the trace buffer -- with the output block sized for them."""
-        tb = state["trace_buf"]
-        E_t = min(int(state.get("E", 0)), _lib.MAX_ELITES) if (state.get("stage") is not None and tb is not None) else 0
+        tb = st.trace_buf
+        E_t = min(int(plan.E), _lib.MAX_ELITES) if (st.stages and tb is not None) else 0
         row = tb[1] if E_t else 0
-        b.size_out(2 * K * nu + E_t * (2 + row))
+        b.size_out(2 * plan.K * plan.nu + E_t * (2 + row))
         return E_t, row
 
-    def _plan_step(self, lib, b: _PlanBuffers, shape: str, noise_p: int, ldn: int, knots_out, W, shard: Shard, world: int, H: int, K: int, nu: int, stream,
-                   state: dict) -> int:
+    def _plan_step(self, plan: _Plan, b: _PlanBuffers, st: _IterState, shape: str) -> int:
         """Shapes "plan_step" / "plan_step_shard": upload, rollout + cost kernel and the update with the trace elites' records in one library call, the results
         written straight into the pinned output block -- on several ranks through this rank's record, one all-gather and the merge.  Returns the trace records written."""
-        opt = self.optimizer
-        tb = state["trace_buf"] = self._trace_buffer(b, shard.count, H)
-        E_t, row = self._trace_records(b, state, K, nu)
+        lib, opt, shard, H, K, nu, knots_out, stream = _lib.lib(), self.optimizer, plan.shard, plan.H, plan.K, plan.nu, st.knots_out, st.stream
+        tb = st.trace_buf = self._trace_buffer(b, shard.count, H)
+        E_t, row = self._trace_records(plan, b, st)
         mode, lam, k_el, tie = opt.fused_update_args()
         evs = [self._timing_event() for _ in range(3)] if self.record_kernel_events else None  # recorded inside the call: before the rollout, before the update, behind it
         timing = (C.c_void_p * 3)(*[e.handle for e in evs]) if evs else None
         off = b.offsets
-        args = (b.host_ptr, b.nblk_bytes, int(off[1]), int(off[2]), int(off[3]), int(off[4]), noise_p, ldn, _lib.ptr(W), int(self.task.phase), shard.count, shard.offset, H, K,
-                _lib.ptr(b.costs), _lib.ptr(knots_out), _lib.ptr(tb[0]) if tb else None, mode, lam, k_el, tie, E_t, row, int(self._trace_colmajor) if tb else 0,
+        args = (b.host_ptr, b.nblk_bytes, int(off[1]), int(off[2]), int(off[3]), int(off[4]), st.noise_p, st.ldn, _lib.ptr(plan.W), int(self.task.phase), shard.count, shard.offset,
+                H, K, _lib.ptr(b.costs), _lib.ptr(knots_out), _lib.ptr(tb[0]) if tb else None, mode, lam, k_el, tie, E_t, row, int(self._trace_colmajor) if tb else 0,
                 _lib.ptr(b.fused_scratch))
-        state["costs"] = b.costs
+        st.costs = b.costs
         exchange_end = evs[2] if evs else None
         if shape == "plan_step":
             # closed-form models (plan steps of ~0.1 ms): the kernel reads the host block in place, and the host polls the completion word the update's last workgroup
@@ -661,52 +699,52 @@ class Controller:
                 self._prefetch_args = None
             b.shard_all = all_gather_records(b.shard_rec, self.group, force=self.force_shard_path)  # (world * L,), rank-major; kept alive until the merge has run
             exchange_end = self._timing_event() if evs else None  # exchange = this rank's record + the all-gather + the merge
-            st = lib.jh_plan_merge(_lib.ptr(b.shard_all), world, K, nu, mode, lam, k_el, tie, E_t, row, b.out_host_ptr, b.out_host_ptr,
+            rc = lib.jh_plan_merge(_lib.ptr(b.shard_all), plan.world, K, nu, mode, lam, k_el, tie, E_t, row, b.out_host_ptr, b.out_host_ptr,
                                    exchange_end.handle if exchange_end else None, stream)
-            _lib.check(st, "jh_plan_merge")
+            _lib.check(rc, "jh_plan_merge")
         if evs:
             self.kernel_events.append((evs[0], evs[1]))
             self.exchange_events.append((evs[1], exchange_end))
         self._fetch(b, begun=True)
-        if not E_t and state.get("stage") is not None:
-            state["stage"]()  # (no trace buffer: the elites' knots, re-rolled when the traces are read)
+        if not E_t and st.stages:
+            self._stage_traces(plan, b, st)  # (no trace buffer: the elites' knots, re-rolled when the traces are read)
         return E_t
 
-    def _rollout_update(self, lib, b: _PlanBuffers, shape: str, nrm: Normalizer, noise_p: int, ldn: int, knots_out, W, shard: Shard, world: int, H: int, K: int,
-                        nu: int, N: int, n_res: int, stream, state: dict) -> int:
+    def _rollout_update(self, plan: _Plan, b: _PlanBuffers, st: _IterState, shape: str) -> int:
         """Shapes "update_fused" / "separate": the rollout (the fused rollout + cost kernel, or the materialise path), then the update, then -- for the running
         normaliser -- the moments of this iteration's candidates.  Returns the trace records written behind nominal | sigma."""
-        opt, task = self.optimizer, self.task
+        lib, opt, task, nrm, shard, world, H, K, nu = _lib.lib(), self.optimizer, self.task, plan.nrm, plan.shard, plan.world, plan.H, plan.K, plan.nu
+        noise_p, ldn, knots_out, stream = st.noise_p, st.ldn, st.knots_out, st.stream
         ev0 = self._event()
         if self.uses_fused_cost:
-            tb = state["trace_buf"] = self._trace_buffer(b, shard.count, H)
-            st = lib.jh_rollout_cost_traced(self.model.handle, _lib.ptr(b.x0), _lib.ptr(b.nominal), noise_p, ldn, _lib.ptr(b.sigma), _lib.ptr(W),
+            tb = st.trace_buf = self._trace_buffer(b, shard.count, H)
+            rc = lib.jh_rollout_cost_traced(self.model.handle, _lib.ptr(b.x0), _lib.ptr(b.nominal), noise_p, ldn, _lib.ptr(b.sigma), _lib.ptr(plan.W),
                                             _lib.ptr(b.lohi), _lib.ptr(b.tp), int(task.phase), shard.count, shard.offset, H, K, _lib.ptr(b.costs),
                                             _lib.ptr(knots_out), _lib.ptr(tb[0]) if tb else None, stream)
-            _lib.check(st, "jh_rollout_cost")
+            _lib.check(rc, "jh_rollout_cost")
             costs = b.costs
         else:
-            costs = self._materialised_costs(b.x0, b.nominal, noise_p, ldn, b.sigma, b.lohi, None, W, shard, H, K, stream)
+            costs = self._materialised_costs(plan, b, st)
             if knots_out is not None:  # the materialise path never wrote the candidates: sample them into the (K, nu, N) layout the fused kernel uses
                 tmp = torch.empty((shard.count, K, nu), dtype=torch.float32, device=self.device)
-                st = lib.jh_sample_knots(_lib.ptr(b.nominal), noise_p, ldn, _lib.ptr(b.sigma), _lib.ptr(b.lohi), shard.count, shard.offset, K, nu, _lib.ptr(tmp), stream)
-                _lib.check(st, "jh_sample_knots")
+                rc = lib.jh_sample_knots(_lib.ptr(b.nominal), noise_p, ldn, _lib.ptr(b.sigma), _lib.ptr(b.lohi), shard.count, shard.offset, K, nu, _lib.ptr(tmp), stream)
+                _lib.check(rc, "jh_sample_knots")
                 knots_out.copy_(tmp.permute(1, 2, 0))
         if ev0 is not None:
             self.kernel_events.append((ev0, self._event()))
-        state["costs"] = costs
+        st.costs = costs
         if shape == "update_fused":
             # one GPU: block partials, merge and -- in the last iteration, when the rollout kernel wrote the trace buffer -- the trace elites' records in ONE launch,
             # nominal | sigma | records written straight into the pinned host block (device-visible: hipHostMalloc) by the last workgroup (controller.py:288-299
             # without the seven-launch chain)
-            E_t, row = self._trace_records(b, state, K, nu)
+            E_t, row = self._trace_records(plan, b, st)
             mode, lam, k_el, tie = opt.fused_update_args()
             ex0 = self._event()
             o = b.out_host_ptr
-            st = lib.jh_update_fused(_lib.ptr(costs), None, _lib.ptr(b.nominal), noise_p, ldn, _lib.ptr(b.sigma), _lib.ptr(b.lohi), shard.count, shard.offset, K, nu, mode, lam,
-                                     k_el, tie, E_t, _lib.ptr(state["trace_buf"][0]) if E_t else None, row, int(self._trace_colmajor) if E_t else 0, _lib.ptr(b.fused_scratch),
+            rc = lib.jh_update_fused(_lib.ptr(costs), None, _lib.ptr(b.nominal), noise_p, ldn, _lib.ptr(b.sigma), _lib.ptr(b.lohi), shard.count, shard.offset, K, nu, mode, lam,
+                                     k_el, tie, E_t, _lib.ptr(st.trace_buf[0]) if E_t else None, row, int(self._trace_colmajor) if E_t else 0, _lib.ptr(b.fused_scratch),
                                      o, o + 4 * K * nu, (o + 8 * K * nu) if E_t else None, stream)
-            _lib.check(st, "jh_update_fused")
+            _lib.check(rc, "jh_update_fused")
             n_copy = 0
         else:
             E_t = 0
@@ -714,32 +752,32 @@ class Controller:
             ex0 = self._event()  # the exchange of the per-rank records and the merge (bench.py attributes the plan step: kernel / exchange / host)
             recs = all_gather_records(b.rec, self.group)
             opt.device_merge(recs, world, b.out.data_ptr(), b.out.data_ptr() + 4 * K * nu, clip_sigma=False, stream=stream)
-            n_copy = n_res
+            n_copy = 2 * K * nu if isinstance(getattr(opt, "sigma", None), np.ndarray) else K * nu  # nominal (| sigma) to copy down
         if ex0 is not None:
             self.exchange_events.append((ex0, self._event()))
-        self._fetch(b, n_copy, behind=None if E_t else state.get("stage"))
+        # (the trace records of the elites' knots or sensor rows, where the update wrote none: enqueued behind the download, not waited for)
+        self._fetch(b, n_copy, behind=(lambda: self._stage_traces(plan, b, st)) if st.stages and not E_t else None)
         if nrm.needs_moments:  # running statistics over this iteration's raw candidates, all ranks (controller.py:290-291)
             if b.mom is None:
                 b.mom = torch.empty(2 * nu, dtype=torch.float32, device=self.device)
             ctr = torch.from_numpy(np.asarray(nrm.mean, dtype=np.float32)).to(self.device)
-            st = lib.jh_knot_moments(None, _lib.ptr(b.nominal), noise_p, ldn, _lib.ptr(b.sigma), _lib.ptr(b.lohi), _lib.ptr(ctr),
+            rc = lib.jh_knot_moments(None, _lib.ptr(b.nominal), noise_p, ldn, _lib.ptr(b.sigma), _lib.ptr(b.lohi), _lib.ptr(ctr),
                                      shard.count, shard.offset, K, nu, _lib.ptr(b.mom), stream)
-            _lib.check(st, "jh_knot_moments")
+            _lib.check(rc, "jh_knot_moments")
             m = all_gather_records(b.mom, self.group).cpu().numpy().astype(np.float64).reshape(world, 2, nu).sum(0)
             # the kernel centred on the fp32 image of the mean: shift the moments to the fp64 mean
             dm = np.asarray(nrm.mean, dtype=np.float32).astype(np.float64) - nrm.mean
-            cnt = N * K
+            cnt = plan.N * K
             s1 = m[0] + cnt * dm
             s2 = m[1] + 2 * dm * m[0] + cnt * dm * dm
             nrm.update_from_moments(cnt, s1, s2)
         return E_t
 
-    def _candidates_iteration(self, lib, b: _PlanBuffers, nrm: Normalizer, nominal_n: np.ndarray, W, shard: Shard, H: int, K: int, nu: int, N: int,
-                              stream, state: dict) -> np.ndarray:
+    def _candidates_iteration(self, plan: _Plan, b: _PlanBuffers, st: _IterState) -> None:
         """judo/controller/controller.py:246-291 for an optimizer that only has the reference's numpy methods: its candidates are clipped on the
         host as the reference does, the shard's rows go to the device, rollout and reward run there, the rewards come back for its update.
         With several ranks every rank must sample the same candidates (seed numpy alike) -- the reference has no multi-process form of this."""
-        opt, task = self.optimizer, self.task
+        opt, task, nrm, shard, N, K, nu, nominal_n = self.optimizer, self.task, plan.nrm, plan.shard, plan.N, plan.K, plan.nu, st.nominal_n
         cand_n = np.asarray(opt.sample_control_knots(nominal_n), dtype=np.float64)
         if cand_n.shape != (N, K, nu):
             raise ValueError(f"sample_control_knots must return ({N}, {K}, {nu}), got {cand_n.shape}")
@@ -750,29 +788,25 @@ class Controller:
         if b.knots_nku is None:
             b.knots_nku = torch.empty((shard.count, K, nu), dtype=torch.float32, device=self.device)
         b.knots_nku.copy_(torch.from_numpy(np.ascontiguousarray(self._candidate_knots[shard.offset : shard.offset + shard.count], dtype=np.float32)))
-        costs = self._materialised_costs(b.x0, None, None, 0, None, b.lohi, b.knots_nku, W, shard, H, K, stream)
+        st.knots_out, st.noise, st.noise_p, st.ldn, st.knots_nku = None, None, None, 0, b.knots_nku  # explicit candidates: nothing is sampled from noise
+        costs = st.costs = self._materialised_costs(plan, b, st)
         rewards = -costs.cpu().numpy().astype(np.float64)
         if shard.world > 1:
             from judo_amd.distributed import all_gather_costs
 
             rewards = -all_gather_costs(costs, shard, self.group).cpu().numpy().astype(np.float64)
         self._rewards = rewards
-        nominal_n = np.asarray(opt.update_nominal_knots(cand_n, rewards), dtype=np.float64)
+        st.nominal_n = np.asarray(opt.update_nominal_knots(cand_n, rewards), dtype=np.float64)
         nrm.update(self._candidate_knots)
-        state.update(costs=costs, knots_out=None, noise_p=None, ldn=0, knots_nku=b.knots_nku)
-        return nominal_n
 
-    def _materialised_costs(self, x0_d, nom_d, noise_p, ldn: int, sig_d, lohi_d, knots_nku, W, shard: Shard, H: int, K: int, stream) -> torch.Tensor:
-        """judo/controller/controller.py:239-262 on the device: candidate splines at the rollout times, RolloutBackend.rollout,
-        Task.reward, Task.post_rollout.  Returns costs = -rewards (fp32, device)."""
-        lib, task, nu = _lib.lib(), self.task, self.nu
-        controls = torch.empty((shard.count, H, nu), dtype=torch.float32, device=self.device)
-        st = lib.jh_spline_controls(_lib.ptr(W), _lib.ptr(knots_nku), _lib.ptr(nom_d), noise_p, ldn, _lib.ptr(sig_d), _lib.ptr(lohi_d) if knots_nku is None else None,
-                                    shard.count, shard.offset, H, K, nu, _lib.ptr(controls), stream)
-        _lib.check(st, "jh_spline_controls")
+    def _materialised_costs(self, plan: _Plan, b: _PlanBuffers, st: _IterState) -> torch.Tensor:
+        """judo/controller/controller.py:239-262 on the device: candidate splines at the rollout times (of `st.knots_nku`, or sampled from the iteration's noise),
+        RolloutBackend.rollout, Task.reward, Task.post_rollout.  Returns costs = -rewards (fp32, device)."""
+        task, x0_d = self.task, b.x0
+        controls = spline_controls(self, plan, b, st)
         if task.uses_locomotion_policy:  # controller.py:265-273: commands -> policy + plant; the policy outputs carry over to the next plan step
             if self._last_policy_output is None:
-                self._last_policy_output = torch.zeros((shard.count, POLICY_OUTPUT_DIM), dtype=torch.float32, device=self.device)
+                self._last_policy_output = torch.zeros((plan.shard.count, POLICY_OUTPUT_DIM), dtype=torch.float32, device=self.device)
             states, sensors, self._last_policy_output = self.rollout_backend.rollout(x0_d, task.task_to_sim_ctrl(controls), self._last_policy_output,
                                                                                     cutoff_time=self.rollout_cutoff_time)
         elif hasattr(self.rollout_backend, "rollout_device"):
@@ -867,15 +901,16 @@ class Controller:
             E = _lib.MAX_ELITES
         return max(E, 0) if self.trace_sensors else 0
 
-    def _stage_traces(self, lib, b: _PlanBuffers, state: dict, shard: Shard, world: int, E: int, x0: np.ndarray, new_times: np.ndarray, K: int, nu: int, stream) -> None:
+    def _stage_traces(self, plan: _Plan, b: _PlanBuffers, st: _IterState) -> None:
         """What `update_traces` (controller.py:323-363) needs from this plan step, kept on the device: the E best rollouts of this shard as
         records [cost, global index, payload], all-gathered over the ranks.  payload = their clipped candidate knots (re-rolled in materialise
         mode when the traces are read) or, when the iteration materialised the sensors anyway, their trace-sensor rows.  No synchronisation here."""
+        lib, shard, E, x0, new_times, K, nu, stream = _lib.lib(), plan.shard, plan.E, plan.x0, plan.new_times, plan.K, plan.nu, st.stream
         self._traces, self._trace_stage = None, None
         if E <= 0:
             self._traces = np.zeros((0, 2, 3))
             return
-        costs = state["costs"]
+        costs = st.costs
         kl = min(E, shard.count)
         H = self.num_timesteps
         if self.last_rollout is not None and (not self.uses_fused_optimizer or not self.uses_fused_cost):
@@ -897,10 +932,10 @@ class Controller:
             if kl < E:
                 trace_rec.fill_(float("inf"))
             self._ensure_block(b)
-            st = lib.jh_topk_partial(_lib.ptr(costs), _lib.ptr(state["knots_nku"]), _lib.ptr(b.nominal), state["noise_p"], state["ldn"], _lib.ptr(b.sigma), _lib.ptr(b.lohi),
+            rc = lib.jh_topk_partial(_lib.ptr(costs), _lib.ptr(st.knots_nku), _lib.ptr(b.nominal), st.noise_p, st.ldn, _lib.ptr(b.sigma), _lib.ptr(b.lohi),
                                      shard.count, shard.offset, K, nu, kl, 1, _lib.ptr(b.scratch), _lib.ptr(trace_rec), stream)
-            _lib.check(st, "jh_topk_partial")
-            tb = state.get("trace_buf")
+            _lib.check(rc, "jh_topk_partial")
+            tb = st.trace_buf
             if tb is not None:  # the elites' rows of the trace buffer travel instead of their knots: nothing is re-rolled when the traces are read
                 row = tb[1]
                 if b.trace_rows is None or b.trace_rows.numel() != 2 * E * (2 + row):
@@ -908,8 +943,8 @@ class Controller:
                 out = b.trace_rows[b.trace_flip * E * (2 + row) : (b.trace_flip + 1) * E * (2 + row)]
                 if kl < E:
                     out.fill_(float("inf"))  # (records beyond this shard's rollouts: an infinite cost marks them empty)
-                st = lib.jh_trace_gather(_lib.ptr(trace_rec), kl, stride, shard.offset, shard.count, _lib.ptr(tb[0]), row, int(self._trace_colmajor), _lib.ptr(out), stream)
-                _lib.check(st, "jh_trace_gather")
+                rc = lib.jh_trace_gather(_lib.ptr(trace_rec), kl, stride, shard.offset, shard.count, _lib.ptr(tb[0]), row, int(self._trace_colmajor), _lib.ptr(out), stream)
+                _lib.check(rc, "jh_trace_gather")
                 kind, stride = "sensors", 2 + row
                 recs = all_gather_records(out, self.group)
                 self._trace_stage = dict(kind=kind, recs=recs, stride=stride, E=E, x0=x0, times=np.array(new_times), order=self.spline_order, H=H, K=K, nu=nu, index_is_bits=True)

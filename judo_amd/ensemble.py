@@ -80,9 +80,9 @@ class EnsembleController(FusedPlantController, WorstCase, Controller):
         super().__init__(controller_config, task, optimizer, device=device)
         self._init_worst(worst, len(self._members))
 
-    def _kind_args(self, b, N: int) -> tuple:
+    def _kind_args(self, plan, b) -> tuple:
         """The entry's arguments between K and `mode`: member_costs, costs, worst."""
-        return (self._member_cost_rows(N).data_ptr(), _lib.ptr(b.costs), self._worst)
+        return (self._member_cost_rows(plan.shard.count).data_ptr(), _lib.ptr(b.costs), self._worst)
 
 
 def make_ensemble_controller(task: str | Task, optimizer: str, descriptions: Sequence[dict], worst: int | None = None, device: torch.device | None = None) -> EnsembleController:

@@ -19,10 +19,9 @@ from typing import Sequence
 import torch
 
 from judo_amd import _lib
-from judo_amd.device import GpuModelSet
 from judo_amd.distributed import world_info
 from judo_amd.ensemble import MAX_ENSEMBLE, EnsembleController, check_descriptions, make_ensemble_controller
-from judo_amd.fleet import ControllerFleet, _FleetBuffers, refuse_fr3_randomized
+from judo_amd.fleet import ControllerFleet, _LaunchStep, refuse_fr3_randomized
 from judo_amd.models import image_sections
 from judo_amd.plants import PlantFleet
 from judo_amd.randomized import RandomizedController
@@ -122,24 +121,20 @@ class EnsembleFleet(PlantFleet, ControllerFleet):
         self._check_plants(i, c, first)
         super()._check_member(i, c, first)
 
-    def _trace_floats(self) -> int:
-        return 0  # (no trace buffer, as for the ensemble call: a member stages its trace elites' knots and re-rolls them on its plant 0)
+    def _launch(self, step: _LaunchStep) -> None:
+        self._launch_ensemble(_lib.lib().jh_plan_step_ensemble_batch, step)
 
-    def _launch(self, lib, model_set: GpuModelSet, fb: _FleetBuffers, in_place: bool, noise: torch.Tensor, W, N: int, H: int, K: int, nu: int, costs: torch.Tensor, nfl: int,
-                update_args: tuple, E_t: int, row: int, colmajor: int, stream) -> None:
-        cs = self.controllers
-        B, M = len(cs), cs[0].num_members
+    def _launch_ensemble(self, entry, step: _LaunchStep) -> None:
+        """The B ensemble plan steps as one call of `entry`: the set, B, M, the runs, the (B, M, N) member costs the members' `_member_costs` are views of, the costs, `worst`."""
+        cs, s = self.controllers, step
+        B, M, N = len(cs), cs[0].num_members, s.fb.N
         if self._member_costs is None or tuple(self._member_costs.shape) != (B, M, N):
             self._member_costs = torch.empty((B, M, N), dtype=torch.float32, device=self.device)
         for i, c in enumerate(cs):
             c._member_costs = self._member_costs[i]
         worst = (C.c_int * B)(*[c.worst for c in cs])
-        off = fb.offsets
-        mode, lam, k_el, tie = update_args
-        st = lib.jh_plan_step_ensemble_batch(model_set.handle, B, M, fb.host_ptr if in_place else fb.blk.data_ptr(), fb.host_ptr, 4 * fb.nblk, 4 * fb.blk_stride, off[1], off[2], off[3], off[4],
-                                             noise.data_ptr(), N, K * nu * N, _lib.ptr(W), N, H, K, self._member_costs.data_ptr(), costs.data_ptr(), worst, mode, lam, k_el, tie,
-                                             fb.scratch.data_ptr(), fb.out_host_ptr, fb.out_stride, fb.done.data_ptr() if in_place else fb.out_host_ptr, None, stream)
-        _lib.check(st, "jh_plan_step_ensemble_batch")
+        rc = entry(s.model_set.handle, B, M, *s.block, *s.noise_args, *s.sizes, self._member_costs.data_ptr(), s.costs.data_ptr(), worst, *s.update_args, *s.tail)
+        _lib.check(rc, entry.__name__)
 
 
 def make_ensemble_fleet(task: str, optimizer: str, B: int, descriptions: Sequence, worst=None, device: torch.device | None = None) -> EnsembleFleet:

@@ -122,9 +122,14 @@ class _FleetBuffers:
         self.scratch = torch.zeros(int(L.jh_plan_batch_scratch_floats(B, N, K, nu)), dtype=torch.float32, device=dev)  # (zero: the tickets)
         self.done = torch.zeros(4, dtype=torch.int32).pin_memory()
         self.trace_buf: torch.Tensor | None = None
+        # member i's view of either noise and cost buffer, and of the trace buffer once it exists: made once, not in every iteration (a tensor view costs a microsecond)
+        self.noise_rows, self.cost_rows, self.trace_rows = [list(n) for n in self.noise], [list(c) for c in self.costs], []
         self.out_stride = 0
         self.size_out(2 * K * nu)
         self.members = [_MemberBuffers(self, i) for i in range(B)]
+        # the launch's argument record, kept from plan step to plan step.  It holds the addresses of `host`, `blk`, `scratch` and `done`: none of them may be reassigned
+        # once it exists (`out_host` may: `size_out` replaces it, and the record reads it afresh in every iteration)
+        self.step = _LaunchStep(self)
 
     def size_out(self, stride: int) -> None:
         if self.out_stride >= stride:
@@ -132,6 +137,33 @@ class _FleetBuffers:
         self.out_stride = stride
         self.out_host = torch.zeros(self.B * stride, dtype=torch.float32).pin_memory()  # (zeros: MPPI / PS never write the sigma region)
         self.out_np, self.out_host_ptr = self.out_host.numpy(), self.out_host.data_ptr()
+
+
+class _LaunchStep:
+    """One iteration's library call on a fleet's buffers, as `ControllerFleet._launch` takes it.  It lives with the buffers (`_FleetBuffers.step`), so that the runs of
+    arguments every batched plan-step entry shares (include/judo_amd.h) are tuples kept from launch to launch.  The loop assigns by name what a plan step decides --
+    `model_set`; `in_place` (the kernel reads the host blocks in place and the host polls the completion word, else the blocks are uploaded and the stream's event kept)
+    with `block = blocks[in_place]`; `sizes` (W, N, H, K); `update_args` (mode, lam, k_el, tie); `nfl` (trace floats per step the rollout kernel writes into
+    `fb.trace_buf`, 0: none); `colmajor`; `stream` -- and calls `iteration` for the rest.  An entry's call reads: its handle and B / M, `*block`, `*noise_args`, `*sizes`,
+    its own middle arguments, `*update_args`, `*tail`."""
+
+    __slots__ = ("fb", "blocks", "model_set", "in_place", "block", "sizes", "update_args", "nfl", "colmajor", "stream", "noise", "costs", "E_t", "row", "noise_args", "tail", "_fixed")
+
+    def __init__(self, fb: "_FleetBuffers") -> None:
+        self.fb = fb
+        # the blocks: device (or host, read in place), host, bytes of one, bytes from one to the next, the offsets of nominal, sigma, task params and bounds -- and of the
+        # fleet's extra word behind the bounds where the blocks have one (the fr3 entries' phase word)
+        run = (fb.host_ptr, 4 * (fb.nblk + fb.extra), 4 * fb.blk_stride, *fb.offsets[1:5]) + ((fb.nblk,) if fb.extra else ())
+        self.blocks = {False: (fb.blk.data_ptr(), *run), True: (fb.host_ptr, *run)}
+        self._fixed = (fb.N, fb.K * fb.nu * fb.N, fb.scratch.data_ptr(), fb.done.data_ptr())
+
+    def iteration(self, noise: torch.Tensor, costs: torch.Tensor, E_t: int, row: int) -> None:
+        """This iteration's (B, K, nu, N) noise and (B, N) costs, and the `E_t` trace elites' records of `row` floats behind every problem's nominal | sigma -- with the
+        output block as the loop has sized it: the tail is update scratch, output block, its stride, the completion mark, no timing events, the stream."""
+        fb, (n, pitch, scratch_p, done_p) = self.fb, self._fixed
+        self.noise, self.costs, self.E_t, self.row = noise, costs, E_t, row
+        self.noise_args = (noise.data_ptr(), n, pitch)
+        self.tail = (scratch_p, fb.out_host_ptr, fb.out_stride, done_p if self.in_place else fb.out_host_ptr, None, self.stream)
 
 
 class ControllerFleet:
@@ -295,72 +327,105 @@ class ControllerFleet:
         if first.task.uses_locomotion_policy:
             return self._update_action_policy()
         model_set = self._models()
-        plans = [c._begin_plan() for c in cs]
-        # (a plan: N, K, nu, H, world, shard, normaliser, normalised nominal, W, x0, new knot times, fused optimizer?, trace elites, task params -- Controller._begin_plan)
-        N, K, nu, H, _, _, _, _, W, _, _, _, E, tp0 = plans[0]
-        for i, p in enumerate(plans):
-            if (p[0], p[1], p[2], p[3], p[12], len(p[13])) != (N, K, nu, H, E, len(tp0)):
-                raise ValueError(f"fleet member {i} plans another problem size than member 0")
-        B = len(cs)
-        fb = self._buffers((B, N, K, nu, first.task.nq + first.task.nv, len(tp0), E))
-        stream = current_stream_ptr()
-        shards, nrms = [p[5] for p in plans], [p[6] for p in plans]
-        states: list[dict[str, Any]] = [dict(E=E, x0=p[9], new_times=p[10]) for p in plans]
-        nominal_n = [p[7] for p in plans]
-        mode, lam, k_el, tie = first.optimizer.fused_update_args()
+        plans, fb, states = self._begin_plans()
+        p0, stream = plans[0], states[0].stream
+        N, K, nu, H, E, B = p0.N, p0.K, p0.nu, p0.H, p0.E, len(cs)
         nfl = self._trace_floats()
-        colmajor = int(first._trace_colmajor) if nfl else 0
+        in_place = self.model.closed_form  # (the closed-form kernels read the host blocks in place and the host polls the completion word; the leap family uploads and keeps the stream's event)
+        step = fb.step
+        step.model_set, step.in_place, step.block, step.sizes = model_set, in_place, step.blocks[in_place], (p0.W.data_ptr(), N, H, K)
+        step.update_args, step.nfl, step.colmajor, step.stream = first.optimizer.fused_update_args(), nfl, int(first._trace_colmajor) if nfl else 0, stream
         iters, staged = 0, False
         while iters < first.max_opt_iters and not any(c.optimizer.stop_cond() for c in cs):
             last = iters == first.max_opt_iters - 1
-            affine = []
-            for c, mb, nrm, n_n in zip(cs, fb.members, nrms, nominal_n):
-                c._stream = stream
-                c.task.pre_rollout(c.current_state)
-                affine.append(c._iteration_inputs(mb, nrm, n_n, nu, upload=False))
+            self._member_inputs(plans, fb, states)
             noise = self._draw_noise(fb, N, K, nu)
             costs = fb.costs[fb.noise_cur]
             row = H * nfl
             if nfl and (fb.trace_buf is None or fb.trace_buf.numel() != B * N * row):
                 fb.trace_buf = torch.empty(B * N * row, dtype=torch.float32, device=self.device)
+                fb.trace_rows = list(fb.trace_buf.view(B, N * row))
             E_t = min(E, _lib.MAX_ELITES) if (last and nfl) else 0
             fb.size_out(2 * K * nu + E_t * (2 + row))
-            in_place = self.model.closed_form  # (the closed-form kernels read the host blocks in place and the host polls the completion word; the leap family uploads and keeps the stream's event)
-            self._launch(lib, model_set, fb, in_place, noise, W, N, H, K, nu, costs, nfl, (mode, lam, k_el, tie), E_t, row, colmajor, stream)
+            step.iteration(noise, costs, E_t, row)
+            self._launch(step)
             _lib.check(lib.jh_download_end(), "jh_download_end")
-            for i, (c, mb, shard, st_i) in enumerate(zip(cs, fb.members, shards, states)):
-                mb.blk_stale = in_place
-                mb.costs = costs[i]
-                trace_i = (fb.trace_buf[i * N * row : (i + 1) * N * row], row) if nfl else None
-                st_i.update(costs=mb.costs, knots_out=None, noise_p=noise[i].data_ptr(), ldn=N, knots_nku=None, trace_buf=trace_i, stage=(True if last else None))
-                nominal_n[i] = c._iteration_result(mb, st_i, noise[i], noise[i].data_ptr(), N, shard, H, K, nu, E_t, *affine[i])
-                if last and not E_t:  # (no trace rows from the kernel: the elites' knots, re-rolled when the traces are read)
-                    c._stage_traces(lib, mb, st_i, shard, 1, E, st_i["x0"], st_i["new_times"], K, nu, stream)
+            self._member_results(plans, fb, states, in_place, row, E_t, last)
             staged = last
             iters += 1
-        for c, mb, p, st_i, n_n in zip(cs, fb.members, plans, states, nominal_n):
-            c._end_plan(p, mb, st_i, n_n, iters, staged, stream)
+        self._end_plans(plans, fb, states, iters, staged)
+
+    # ---- what both loops share: the members' host work in front of, inside and behind the iterations ------------------------------------------------------------
+    def _begin_plans(self) -> tuple[tuple, _FleetBuffers, tuple]:
+        """Every member's `_begin_plan`, the agreement of the problem sizes, the fleet's buffers for them and the launch stream in every member's iteration state."""
+        cs = self.controllers
+        plans, states = zip(*[c._begin_plan() for c in cs])
+        size = None
+        for i, p in enumerate(plans):
+            mine = (p.N, p.K, p.nu, p.H, p.E, len(p.tp))
+            if size is None:
+                size = mine
+            if mine != size:
+                raise ValueError(f"fleet member {i} plans another problem size than member 0")
+            assert p.world == 1 and p.shard.count == p.N  # (`_check_member` refused a member with a process group: the members' trace stage calls all_gather_records with no group)
+        N, K, nu, _, E, ntp = size
+        fb = self._buffers((len(cs), N, K, nu, cs[0].task.nq + cs[0].task.nv, ntp, E))
+        stream = current_stream_ptr()
+        for st in states:
+            st.stream = stream
+        return plans, fb, states
+
+    def _member_inputs(self, plans: tuple, fb: _FleetBuffers, states: tuple) -> None:
+        """An iteration's host prelude: every member's `pre_rollout` and its packed block, in its slice of the fleet's pinned host block (not uploaded here)."""
+        for c, p, mb, st in zip(self.controllers, plans, fb.members, states):
+            c._stream = st.stream
+            c.task.pre_rollout(c.current_state)
+            c._iteration_inputs(p, mb, st, upload=False)
+
+    def _member_results(self, plans: tuple, fb: _FleetBuffers, states: tuple, stale: bool, row: int, E_t: int, last: bool) -> None:
+        """Behind an iteration's wait: every member's iteration state as its own iteration would have left it, the update's result read from its slice of the output
+        block, and -- in the last iteration, where the update wrote no trace records -- its trace stage (the elites' knots, re-rolled when the traces are read, or
+        their rows of the materialised sensors).  The iteration's noise and costs are the buffers `_draw_noise` flipped to.  `stale`: the device copy of the blocks was
+        not written; `row`: trace floats per rollout in `fb.trace_buf`, 0: none."""
+        N, noise, costs, traces = fb.N, fb.noise_rows[fb.noise_cur], fb.cost_rows[fb.noise_cur], fb.trace_rows
+        for i, (c, p, mb, st) in enumerate(zip(self.controllers, plans, fb.members, states)):
+            mb.blk_stale = stale
+            st.costs = mb.costs = costs[i]
+            n_i = st.noise = noise[i]
+            st.noise_p, st.ldn = n_i.data_ptr(), N
+            st.knots_out = st.knots_nku = None
+            st.trace_buf = (traces[i], row) if row else None
+            st.stages = last
+            c._iteration_result(p, mb, st, E_t)
+            if last and not E_t:
+                c._stage_traces(p, mb, st)
+
+    def _end_plans(self, plans: tuple, fb: _FleetBuffers, states: tuple, iters: int, staged: bool) -> None:
+        for c, p, mb, st in zip(self.controllers, plans, fb.members, states):
+            c._end_plan(p, mb, st, iters, staged)
 
     def _trace_floats(self) -> int:
         """Trace floats per step that the fleet's rollout kernel writes for every rollout; 0: none, and the members re-roll their trace elites when the traces are read."""
         return self.controllers[0]._fused_trace_floats()
 
-    def _launch(self, lib, model_set: GpuModelSet | None, fb: _FleetBuffers, in_place: bool, noise: torch.Tensor, W, N: int, H: int, K: int, nu: int, costs: torch.Tensor, nfl: int,
-                update_args: tuple, E_t: int, row: int, colmajor: int, stream) -> None:
+    def _launch(self, step: _LaunchStep) -> None:
         """The one library call of an iteration: B plan steps on the fleet's buffers, with the completion mark that `jh_download_end` then waits for."""
-        B = len(self.controllers)
-        off = fb.offsets
-        mode, lam, k_el, tie = update_args
-        if model_set is not None:  # a model image per problem: the same call without the model and B, which the set holds
-            st = lib.jh_plan_step_batch_models(model_set.handle, fb.host_ptr if in_place else fb.blk.data_ptr(), fb.host_ptr, 4 * fb.nblk, 4 * fb.blk_stride, off[1], off[2], off[3], off[4],
-                                               noise.data_ptr(), N, K * nu * N, _lib.ptr(W), N, H, K, costs.data_ptr(), fb.trace_buf.data_ptr() if nfl else None, mode, lam, k_el, tie,
-                                               E_t, row, colmajor, fb.scratch.data_ptr(), fb.out_host_ptr, fb.out_stride, fb.done.data_ptr() if in_place else fb.out_host_ptr, None, stream)
-            _lib.check(st, "jh_plan_step_batch_models")
+        if step.model_set is not None:  # a model image per problem: the same call without B, which the set holds
+            self._launch_traced(_lib.lib().jh_plan_step_batch_models, (step.model_set.handle,), step)
         else:
-            st = lib.jh_plan_step_batch(self.model.handle, B, fb.host_ptr if in_place else fb.blk.data_ptr(), fb.host_ptr, 4 * fb.nblk, 4 * fb.blk_stride, off[1], off[2], off[3], off[4],
-                                        noise.data_ptr(), N, K * nu * N, _lib.ptr(W), N, H, K, costs.data_ptr(), fb.trace_buf.data_ptr() if nfl else None, mode, lam, k_el, tie, E_t,
-                                        row, colmajor, fb.scratch.data_ptr(), fb.out_host_ptr, fb.out_stride, fb.done.data_ptr() if in_place else fb.out_host_ptr, None, stream)
-            _lib.check(st, "jh_plan_step_batch")
+            self._launch_traced(_lib.lib().jh_plan_step_batch, (self.model.handle, len(self.controllers)), step)
+
+    @staticmethod
+    def _launch_traced(entry, head: tuple, step: _LaunchStep) -> None:
+        """The entries of the controllers that believe one plant each, whose rollout kernel writes the trace rows: `head` (the model or the set, B), then the runs."""
+        s = step
+        rc = entry(*head, *s.block, *s.noise_args, *s.sizes, s.costs.data_ptr(), s.fb.trace_buf.data_ptr() if s.nfl else None, *s.update_args, s.E_t, s.row, s.colmajor, *s.tail)
+        _lib.check(rc, entry.__name__)
+
+    def _write_phases(self, fb: _FleetBuffers) -> None:
+        """The fr3 fleets: the members' phases (decided by their `pre_rollout` in this iteration) into the phase words behind their blocks' bounds."""
+        for i, c in enumerate(self.controllers):
+            fb.host_np[i * fb.blk_stride + fb.nblk] = float(int(c.task.phase))
 
     # ---- the plan step of the Spot policy tasks ------------------------------------------------------------------------------------------------------
     def _load_carry(self, B: int, n: int) -> torch.Tensor:
@@ -399,28 +464,16 @@ class ControllerFleet:
         lib = _lib.lib()
         cs = self.controllers
         first = cs[0]
-        plans = [c._begin_plan() for c in cs]
-        N, K, nu, H, _, _, _, _, W, _, _, _, E, tp0 = plans[0]
-        for i, p in enumerate(plans):
-            if (p[0], p[1], p[2], p[3], p[12], len(p[13])) != (N, K, nu, H, E, len(tp0)):
-                raise ValueError(f"fleet member {i} plans another problem size than member 0")
-        B = len(cs)
-        fb = self._buffers((B, N, K, nu, first.task.nq + first.task.nv, len(tp0), E))
-        stream = current_stream_ptr()
-        shards, nrms = [p[5] for p in plans], [p[6] for p in plans]
-        states: list[dict[str, Any]] = [dict(E=E, x0=p[9], new_times=p[10]) for p in plans]
-        nominal_n = [p[7] for p in plans]
+        plans, fb, states = self._begin_plans()
+        p0, stream = plans[0], states[0].stream
+        N, K, nu, H, W, B = p0.N, p0.K, p0.nu, p0.H, p0.W, len(cs)
         mode, lam, k_el, tie = first.optimizer.fused_update_args()
         off = fb.offsets
         policy_out = self._load_carry(B, N)
         iters, staged = 0, False
         while iters < first.max_opt_iters and not any(c.optimizer.stop_cond() for c in cs):
             last = iters == first.max_opt_iters - 1
-            affine = []
-            for c, mb, nrm, n_n in zip(cs, fb.members, nrms, nominal_n):
-                c._stream = stream
-                c.task.pre_rollout(c.current_state)
-                affine.append(c._iteration_inputs(mb, nrm, n_n, nu, upload=False))
+            self._member_inputs(plans, fb, states)
             _lib.check(lib.jh_upload_async(fb.blk.data_ptr(), fb.host_ptr, 4 * ((B - 1) * fb.blk_stride + fb.nblk), stream), "jh_upload_async")
             noise = self._draw_noise(fb, N, K, nu)
             costs = fb.costs[fb.noise_cur]
@@ -437,17 +490,10 @@ class ControllerFleet:
                                            0, None, 0, 0, fb.scratch.data_ptr(), fb.out_host_ptr, fb.out_stride, fb.out_host_ptr, stream)
             _lib.check(st, "jh_update_fused_batch")
             _lib.check(lib.jh_download_end(), "jh_download_end")
-            for i, (c, mb, shard, st_i) in enumerate(zip(cs, fb.members, shards, states)):
-                mb.blk_stale = False
-                mb.costs = costs[i]
-                st_i.update(costs=mb.costs, knots_out=None, noise_p=noise[i].data_ptr(), ldn=N, knots_nku=None, trace_buf=None, stage=(True if last else None))
-                nominal_n[i] = c._iteration_result(mb, st_i, noise[i], noise[i].data_ptr(), N, shard, H, K, nu, 0, *affine[i])
-                if last:  # (the trace elites' rows of the materialised sensors, Controller._stage_traces' `last_rollout` branch)
-                    c._stage_traces(lib, mb, st_i, shard, 1, E, st_i["x0"], st_i["new_times"], K, nu, stream)
+            self._member_results(plans, fb, states, False, 0, 0, last)  # (no trace rows from a kernel: the elites' rows of the materialised sensors, Controller._stage_traces' `last_rollout` branch)
             staged = last
             iters += 1
-        for c, mb, p, st_i, n_n in zip(cs, fb.members, plans, states, nominal_n):
-            c._end_plan(p, mb, st_i, n_n, iters, staged, stream)
+        self._end_plans(plans, fb, states, iters, staged)
 
     def solver_stats(self, reset: bool = True) -> dict:
         """`Controller.solver_stats` for the fleet.  The members share one engine (one `GpuModel`, or one `SpotTreeEngine`) and the counters live on it: they are fleet-wide,

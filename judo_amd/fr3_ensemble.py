@@ -16,17 +16,14 @@ own `update_action()` would have left it, `task.phase` included."""
 
 from __future__ import annotations
 
-import ctypes as C
 from typing import Sequence
 
 import torch
 
 from judo_amd import _lib
 from judo_amd.config import ControllerConfig
-from judo_amd.device import GpuModelSet
 from judo_amd.ensemble import MAX_ENSEMBLE, EnsembleController, check_task
 from judo_amd.ensemble_fleet import EnsembleFleet, check_fleet_descriptions, fleet_descriptions, fleet_worst
-from judo_amd.fleet import _FleetBuffers
 from judo_amd.optimizers import get_registered_optimizers
 from judo_amd.plants import make_for
 from judo_amd.tasks import FR3Pick, Task
@@ -71,8 +68,8 @@ class FR3EnsembleController(EnsembleController):
     def _hint(self, why: str) -> str:
         return materialized_hint(why, "ensemble")
 
-    def _entry_args(self, W, N: int, H: int, K: int) -> tuple:
-        return (_lib.ptr(W), int(self.task.phase), N, H, K)  # (the phase `pre_rollout` chose in this iteration, as `Controller._plan_step` passes it to jh_plan_step)
+    def _entry_args(self, plan, b) -> tuple:
+        return (_lib.ptr(plan.W), int(self.task.phase), plan.shard.count, plan.H, plan.K)  # (the phase `pre_rollout` chose in this iteration, as `Controller._plan_step` passes it to jh_plan_step)
 
 
 class FR3EnsembleFleet(EnsembleFleet):
@@ -92,24 +89,10 @@ class FR3EnsembleFleet(EnsembleFleet):
             raise ValueError(f"fleet member {i} differs from member 0 in self_collision: the launch runs one build of the fr3 kernel")
         super()._check_member(i, c, first)
 
-    def _launch(self, lib, model_set: GpuModelSet, fb: _FleetBuffers, in_place: bool, noise: torch.Tensor, W, N: int, H: int, K: int, nu: int, costs: torch.Tensor, nfl: int,
-                update_args: tuple, E_t: int, row: int, colmajor: int, stream) -> None:
+    def _launch(self, step) -> None:
         """The members' phases (decided by their `pre_rollout` in this iteration) into the phase words, then the B ensemble plan steps as one call."""
-        cs = self.controllers
-        B, M = len(cs), cs[0].num_members
-        if self._member_costs is None or tuple(self._member_costs.shape) != (B, M, N):
-            self._member_costs = torch.empty((B, M, N), dtype=torch.float32, device=self.device)
-        for i, c in enumerate(cs):
-            c._member_costs = self._member_costs[i]
-            fb.host_np[i * fb.blk_stride + fb.nblk] = float(int(c.task.phase))
-        worst = (C.c_int * B)(*[c.worst for c in cs])
-        off = fb.offsets
-        mode, lam, k_el, tie = update_args
-        st = lib.jh_plan_step_ensemble_batch_phases(model_set.handle, B, M, fb.host_ptr if in_place else fb.blk.data_ptr(), fb.host_ptr, 4 * (fb.nblk + fb.extra), 4 * fb.blk_stride, off[1],
-                                                    off[2], off[3], off[4], fb.nblk, noise.data_ptr(), N, K * nu * N, _lib.ptr(W), N, H, K, self._member_costs.data_ptr(), costs.data_ptr(),
-                                                    worst, mode, lam, k_el, tie, fb.scratch.data_ptr(), fb.out_host_ptr, fb.out_stride,
-                                                    fb.done.data_ptr() if in_place else fb.out_host_ptr, None, stream)
-        _lib.check(st, "jh_plan_step_ensemble_batch_phases")
+        self._write_phases(step.fb)
+        self._launch_ensemble(_lib.lib().jh_plan_step_ensemble_batch_phases, step)
 
 
 def _fr3_parts(optimizer: str, self_collision: bool):

@@ -26,7 +26,7 @@ from judo_amd import _lib
 from judo_amd.controller import Controller, make_controller_for
 from judo_amd.device import GpuModelSet
 from judo_amd.ensemble import MAX_ENSEMBLE, check_descriptions
-from judo_amd.fleet import ControllerFleet, _FleetBuffers, refuse_fr3_randomized
+from judo_amd.fleet import ControllerFleet, _LaunchStep, refuse_fr3_randomized
 from judo_amd.models import layout
 from judo_amd.tasks import FR3Pick
 
@@ -55,18 +55,10 @@ class FR3Fleet(ControllerFleet):
     def _models(self) -> GpuModelSet | None:
         return None  # (one image: byte-identical members were pointed at member 0's model when the fleet was made)
 
-    def _launch(self, lib, model_set, fb: _FleetBuffers, in_place: bool, noise: torch.Tensor, W, N: int, H: int, K: int, nu: int, costs: torch.Tensor, nfl: int,
-                update_args: tuple, E_t: int, row: int, colmajor: int, stream) -> None:
+    def _launch(self, step: _LaunchStep) -> None:
         """The members' phases (decided by their `pre_rollout` in this iteration) into the phase words, then the B plan steps as one call."""
-        cs = self.controllers
-        off = fb.offsets
-        for i, c in enumerate(cs):
-            fb.host_np[i * fb.blk_stride + fb.nblk] = float(int(c.task.phase))
-        mode, lam, k_el, tie = update_args
-        st = lib.jh_plan_step_batch_phases(self.model.handle, len(cs), fb.host_ptr if in_place else fb.blk.data_ptr(), fb.host_ptr, 4 * (fb.nblk + fb.extra), 4 * fb.blk_stride, off[1], off[2],
-                                           off[3], off[4], fb.nblk, noise.data_ptr(), N, K * nu * N, _lib.ptr(W), N, H, K, costs.data_ptr(), fb.trace_buf.data_ptr() if nfl else None, mode, lam,
-                                           k_el, tie, E_t, row, colmajor, fb.scratch.data_ptr(), fb.out_host_ptr, fb.out_stride, fb.done.data_ptr() if in_place else fb.out_host_ptr, None, stream)
-        _lib.check(st, "jh_plan_step_batch_phases")
+        self._write_phases(step.fb)
+        self._launch_traced(_lib.lib().jh_plan_step_batch_phases, (self.model.handle, len(self.controllers)), step)
 
 
 class FR3PlantFleet(FR3Fleet):
@@ -79,21 +71,12 @@ class FR3PlantFleet(FR3Fleet):
     def _models(self) -> GpuModelSet | None:
         return ControllerFleet._models(self)  # (None while every member plans on the fleet's one model; else the set, which `GpuModelSet` makes with the fr3 constructor)
 
-    def _launch(self, lib, model_set, fb: _FleetBuffers, in_place: bool, noise: torch.Tensor, W, N: int, H: int, K: int, nu: int, costs: torch.Tensor, nfl: int,
-                update_args: tuple, E_t: int, row: int, colmajor: int, stream) -> None:
+    def _launch(self, step: _LaunchStep) -> None:
         """The phase words, then the B plan steps as one call on the set: problem b on image b."""
-        if model_set is None:
-            return super()._launch(lib, model_set, fb, in_place, noise, W, N, H, K, nu, costs, nfl, update_args, E_t, row, colmajor, stream)
-        cs = self.controllers
-        off = fb.offsets
-        for i, c in enumerate(cs):
-            fb.host_np[i * fb.blk_stride + fb.nblk] = float(int(c.task.phase))
-        mode, lam, k_el, tie = update_args
-        st = lib.jh_plan_step_batch_phases_models(model_set.handle, len(cs), fb.host_ptr if in_place else fb.blk.data_ptr(), fb.host_ptr, 4 * (fb.nblk + fb.extra), 4 * fb.blk_stride, off[1],
-                                                  off[2], off[3], off[4], fb.nblk, noise.data_ptr(), N, K * nu * N, _lib.ptr(W), N, H, K, costs.data_ptr(),
-                                                  fb.trace_buf.data_ptr() if nfl else None, mode, lam, k_el, tie, E_t, row, colmajor, fb.scratch.data_ptr(), fb.out_host_ptr, fb.out_stride,
-                                                  fb.done.data_ptr() if in_place else fb.out_host_ptr, None, stream)
-        _lib.check(st, "jh_plan_step_batch_phases_models")
+        if step.model_set is None:
+            return super()._launch(step)
+        self._write_phases(step.fb)
+        self._launch_traced(_lib.lib().jh_plan_step_batch_phases_models, (step.model_set.handle, len(self.controllers)), step)
 
 
 def make_fr3_fleet(optimizer: str, B: int, device: torch.device | None = None, self_collision: bool = False, descriptions: Sequence[dict] | None = None) -> FR3Fleet:

@@ -45,8 +45,8 @@ class FR3RandomizedController(RandomizedController):
     def _hint(self, why: str) -> str:
         return materialized_hint(why, "randomized")
 
-    def _entry_args(self, W, N: int, H: int, K: int) -> tuple:
-        return (_lib.ptr(W), int(self.task.phase), N, H, K)  # (the phase `pre_rollout` chose in this iteration, as `Controller._plan_step` passes it to jh_plan_step)
+    def _entry_args(self, plan, b) -> tuple:
+        return (_lib.ptr(plan.W), int(self.task.phase), plan.shard.count, plan.H, plan.K)  # (the phase `pre_rollout` chose in this iteration, as `Controller._plan_step` passes it to jh_plan_step)
 
 
 def make_fr3_randomized_controller(optimizer: str, descriptions: Sequence[dict], blocks: int | None = None, weights: Sequence[float] | None = None,

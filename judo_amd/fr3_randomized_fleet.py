@@ -8,16 +8,13 @@ own.  Afterwards each member is bit for bit where its own `update_action()` woul
 
 from __future__ import annotations
 
-import ctypes as C
 from typing import Sequence
 
 import torch
 
 from judo_amd import _lib
-from judo_amd.device import GpuModelSet
 from judo_amd.ensemble import MAX_ENSEMBLE
 from judo_amd.ensemble_fleet import check_fleet_descriptions, fleet_descriptions
-from judo_amd.fleet import _FleetBuffers
 from judo_amd.fr3_ensemble import check_self_collision
 from judo_amd.fr3_randomized import FR3RandomizedController, make_fr3_randomized_controller
 from judo_amd.optimizers import get_registered_optimizers
@@ -41,23 +38,10 @@ class FR3RandomizedFleet(RandomizedFleet):
             raise ValueError(f"fleet member {i} differs from member 0 in self_collision: the launch runs one build of the fr3 kernel")
         super()._check_member(i, c, first)
 
-    def _launch(self, lib, model_set: GpuModelSet, fb: _FleetBuffers, in_place: bool, noise: torch.Tensor, W, N: int, H: int, K: int, nu: int, costs: torch.Tensor, nfl: int,
-                update_args: tuple, E_t: int, row: int, colmajor: int, stream) -> None:
+    def _launch(self, step) -> None:
         """The members' phases (decided by their `pre_rollout` in this iteration) into the phase words, then the B randomised plan steps as one call."""
-        cs = self.controllers
-        B, M, G = len(cs), cs[0].num_members, cs[0].blocks
-        used = [list(c._assignment) for c in cs]  # the B assignments in force, controller-major
-        table = (C.c_ubyte * (B * G))(*[p for a in used for p in a])
-        for i, c in enumerate(cs):
-            fb.host_np[i * fb.blk_stride + fb.nblk] = float(int(c.task.phase))
-        off = fb.offsets
-        mode, lam, k_el, tie = update_args
-        st = lib.jh_plan_step_randomized_batch_phases(model_set.handle, B, M, fb.host_ptr if in_place else fb.blk.data_ptr(), fb.host_ptr, 4 * (fb.nblk + fb.extra), 4 * fb.blk_stride, off[1],
-                                                      off[2], off[3], off[4], fb.nblk, noise.data_ptr(), N, K * nu * N, _lib.ptr(W), N, H, K, table, G, costs.data_ptr(), mode, lam, k_el, tie,
-                                                      fb.scratch.data_ptr(), fb.out_host_ptr, fb.out_stride, fb.done.data_ptr() if in_place else fb.out_host_ptr, None, stream)
-        _lib.check(st, "jh_plan_step_randomized_batch_phases")
-        for c, a in zip(cs, used):
-            c._assignment_used = a
+        self._write_phases(step.fb)
+        self._launch_randomized(_lib.lib().jh_plan_step_randomized_batch_phases, step)
 
 
 def make_fr3_randomized_fleet(optimizer: str, B: int, descriptions: Sequence, blocks: int | None = None, weights=None, self_collision: bool = False,

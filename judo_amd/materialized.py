@@ -25,7 +25,6 @@ import torch
 from judo_amd import _lib
 from judo_amd.config import ControllerConfig
 from judo_amd.controller import Controller
-from judo_amd.distributed import Shard
 from judo_amd.plants import Assignment, GpuPlantSet, WorstCase, make_for, spline_controls
 from judo_amd.tasks import Task
 
@@ -73,9 +72,9 @@ class _MaterializedPlantController(GpuPlantSet, Controller):
         self._refuse_shards(world)
         return super()._iteration_shape(world, nrm)
 
-    def _candidates_iteration(self, lib, b, nrm, nominal_n, W, shard: Shard, H, K, nu, N, stream, state):
-        self._refuse_shards(shard.world)
-        return super()._candidates_iteration(lib, b, nrm, nominal_n, W, shard, H, K, nu, N, stream, state)
+    def _candidates_iteration(self, plan, b, st) -> None:
+        self._refuse_shards(plan.shard.world)
+        super()._candidates_iteration(plan, b, st)
 
     def _rollout_plants(self, table: list[int], x0_d, sim_controls: torch.Tensor, shared: bool) -> tuple[torch.Tensor, torch.Tensor]:
         rb = self.rollout_backend
@@ -98,16 +97,16 @@ class MaterializedEnsembleController(WorstCase, _MaterializedPlantController):
         self._init_worst(worst, self._admit(task, descriptions))
         super().__init__(controller_config, task, optimizer, device=device)
 
-    def _materialised_costs(self, x0_d, nom_d, noise_p, ldn: int, sig_d, lohi_d, knots_nku, W, shard: Shard, H: int, K: int, stream) -> torch.Tensor:
-        M, N = len(self._members), shard.count
-        controls = spline_controls(self, nom_d, noise_p, ldn, sig_d, lohi_d, knots_nku, W, shard, H, K, stream)
-        states, sensors = self._rollout_plants(list(range(M)), x0_d, self._sim_controls(controls), shared=True)  # M blocks of N rows, the one (N, H, nu) controls for all of them
+    def _materialised_costs(self, plan, b, st) -> torch.Tensor:
+        M, N = len(self._members), plan.shard.count
+        controls = spline_controls(self, plan, b, st)
+        states, sensors = self._rollout_plants(list(range(M)), b.x0, self._sim_controls(controls), shared=True)  # M blocks of N rows, the one (N, H, nu) controls for all of them
         rows = self._member_cost_rows(N)
         for m in range(M):  # the reward per member, in the shapes a plain controller gives it
             self._score_rollout(states[m * N : (m + 1) * N], sensors[m * N : (m + 1) * N], controls, out=rows[m])
         self.last_rollout = (states[:N], sensors[:N], controls)  # member 0, the nominal plant
         costs = torch.empty(N, dtype=torch.float32, device=self.device)
-        _lib.check(_lib.lib().jh_ensemble_costs(_lib.ptr(rows), M, N, N, self._worst, _lib.ptr(costs), stream), "jh_ensemble_costs")
+        _lib.check(_lib.lib().jh_ensemble_costs(_lib.ptr(rows), M, N, N, self._worst, _lib.ptr(costs), st.stream), "jh_ensemble_costs")
         return costs
 
 
@@ -124,10 +123,10 @@ class MaterializedRandomizedController(Assignment, _MaterializedPlantController)
         self._init_assignment(blocks, weights, self._admit(task, descriptions))
         super().__init__(controller_config, task, optimizer, device=device)
 
-    def _materialised_costs(self, x0_d, nom_d, noise_p, ldn: int, sig_d, lohi_d, knots_nku, W, shard: Shard, H: int, K: int, stream) -> torch.Tensor:
+    def _materialised_costs(self, plan, b, st) -> torch.Tensor:
         a = list(self._assignment)
-        controls = spline_controls(self, nom_d, noise_p, ldn, sig_d, lohi_d, knots_nku, W, shard, H, K, stream)
-        states, sensors = self._rollout_plants(a, x0_d, self._sim_controls(controls), shared=False)  # G blocks of N / G rows, each on its own rows of the controls
+        controls = spline_controls(self, plan, b, st)
+        states, sensors = self._rollout_plants(a, b.x0, self._sim_controls(controls), shared=False)  # G blocks of N / G rows, each on its own rows of the controls
         self._assignment_used = a
         return self._score_rollout(states, sensors, controls)
 

@@ -10,8 +10,8 @@ The classes of judo_amd/ensemble.py, randomized.py, materialized.py and spot_pla
                          forms: one launcher in the library, judo_amd/csrc/jh_api.hip plan_step_set), with its refusals.
   `PlantFleet`           what `EnsembleFleet` and `RandomizedFleet` add to `ControllerFleet`: every plant held to fleet member 0's plant 0, and the set of the launch.
 
-`make_for` is the registry lookup behind every `make_*_controller`; `spline_controls` the `jh_spline_controls` call of the materialise paths.  The host functions of the
-admission (`check_descriptions`, `check_assignment`, `blocks_from_weights`, `plant_of_rollout`) live here and stay importable from ensemble.py and randomized.py."""
+`make_for` is the registry lookup behind every `make_*_controller`; `spline_controls` the `jh_spline_controls` call of the materialise paths (controller.py's).  The host
+functions of the admission (`check_descriptions`, `check_assignment`, `blocks_from_weights`, `plant_of_rollout`) live here and stay importable from ensemble.py and randomized.py."""
 
 from __future__ import annotations
 
@@ -23,9 +23,8 @@ import torch
 
 from judo_amd import _lib
 from judo_amd.config import ControllerConfig
-from judo_amd.controller import _PlanBuffers
+from judo_amd.controller import _IterState, _Plan, _PlanBuffers, spline_controls
 from judo_amd.device import GpuModel, GpuModelSet
-from judo_amd.distributed import Shard
 from judo_amd.models import image_sections, layout, pack_model
 from judo_amd.optimizers import get_registered_optimizers
 from judo_amd.tasks import Task, get_registered_tasks
@@ -117,15 +116,6 @@ def materialized_hint(why: str, kind: str, fr3: bool = False) -> str:
     if fr3 or "sharded path" in why or "keep_candidates" in why:  # (fr3_pick has no materialise launch on plants)
         return ""
     return f".  judo_amd.materialized.make_materialized_{kind}_controller makes the controller that materialises the rollouts on the plants and scores them with Task.reward"
-
-
-def spline_controls(ctrl, nom_d, noise_p, ldn: int, sig_d, lohi_d, knots_nku, W, shard: Shard, H: int, K: int, stream) -> torch.Tensor:
-    """The candidates' controls at the rollout times, (shard.count, H, nu) on the controller's device (`jh_spline_controls`, once per iteration of a materialise path)."""
-    controls = torch.empty((shard.count, H, ctrl.nu), dtype=torch.float32, device=ctrl.device)
-    st = _lib.lib().jh_spline_controls(_lib.ptr(W), _lib.ptr(knots_nku), _lib.ptr(nom_d), noise_p, ldn, _lib.ptr(sig_d), _lib.ptr(lohi_d) if knots_nku is None else None,
-                                       shard.count, shard.offset, H, K, ctrl.nu, _lib.ptr(controls), stream)
-    _lib.check(st, "jh_spline_controls")
-    return controls
 
 
 # ---- the set ---------------------------------------------------------------------------------------------------------------------------------------------------
@@ -293,9 +283,9 @@ class FusedPlantController(GpuPlantSet):
 
     _a, _form, _whose, _call, _maker = "a plant", "plant", "plants'", "jh_plan_step", "kind"  # in messages: the controller, its form, whose costs, the call; `materialized_hint`'s kind
 
-    def _entry_args(self, W, N: int, H: int, K: int) -> tuple:
+    def _entry_args(self, plan: _Plan, b: _PlanBuffers) -> tuple:
         """The entry's arguments between the noise pitch and `_kind_args`: W, N, H, K."""
-        return (_lib.ptr(W), N, H, K)
+        return (_lib.ptr(plan.W), plan.shard.count, plan.H, plan.K)
 
     def _hint(self, why: str) -> str:
         """What a refusal of the one-call shape adds: the maker that serves the configuration (the fr3 subclasses name the arm's)."""
@@ -332,31 +322,30 @@ class FusedPlantController(GpuPlantSet):
     def _after_call(self, kind_args: tuple) -> None:
         pass
 
-    def _plan_step(self, lib, b: _PlanBuffers, shape: str, noise_p: int, ldn: int, knots_out, W, shard: Shard, world: int, H: int, K: int, nu: int, stream,
-                   state: dict) -> int:
+    def _plan_step(self, plan: _Plan, b: _PlanBuffers, st: _IterState, shape: str) -> int:
         """Shape "plan_step" on the set: one upload (or the host block read in place), the batched rollout kernel with the plants on its second grid dimension, the
         update's tail, one completion mark.  No trace buffer: the trace elites' knots are staged and re-rolled on member 0 when the traces are read."""
-        N = shard.count
-        state["trace_buf"] = None
-        b.size_out(2 * K * nu)
-        kind_args = self._kind_args(b, N)
+        st.trace_buf = None
+        b.size_out(2 * plan.K * plan.nu)
+        kind_args = self._kind_args(plan, b)
         mode, lam, k_el, tie = self.optimizer.fused_update_args()
         evs = [self._timing_event() for _ in range(3)] if self.record_kernel_events else None
         timing = (C.c_void_p * 3)(*[e.handle for e in evs]) if evs else None
         off = b.offsets
         in_place = b.blk_stale = self.model.closed_form
         mark = b.done_ptr if self.model.closed_form else b.out_host_ptr
-        st = getattr(lib, self._entry)(self.model_set.handle, b.host_ptr if in_place else b.blk.data_ptr(), b.host_ptr, b.nblk_bytes, int(off[1]), int(off[2]), int(off[3]), int(off[4]),
-                                       noise_p, ldn, *self._entry_args(W, N, H, K), *kind_args, mode, lam, k_el, tie, _lib.ptr(b.fused_scratch), b.out_host_ptr, mark, timing, stream)
-        _lib.check(st, self._entry)
+        rc = getattr(_lib.lib(), self._entry)(self.model_set.handle, b.host_ptr if in_place else b.blk.data_ptr(), b.host_ptr, b.nblk_bytes, int(off[1]), int(off[2]), int(off[3]),
+                                              int(off[4]), st.noise_p, st.ldn, *self._entry_args(plan, b), *kind_args, mode, lam, k_el, tie, _lib.ptr(b.fused_scratch), b.out_host_ptr,
+                                              mark, timing, st.stream)
+        _lib.check(rc, self._entry)
         self._after_call(kind_args)
-        state["costs"] = b.costs
+        st.costs = b.costs
         if evs:
             self.kernel_events.append((evs[0], evs[1]))
             self.exchange_events.append((evs[1], evs[2]))
         self._fetch(b, begun=True)
-        if state.get("stage") is not None:
-            state["stage"]()
+        if st.stages:
+            self._stage_traces(plan, b, st)
         return 0
 
 
@@ -379,6 +368,9 @@ class PlantFleet:
                     raise ValueError(f"fleet member {i}: plant {j} has another model image than member 0's plant 0: the {name} of its image differs")
             if m.build() != first.model.build() or m.self_collision != first.model.self_collision:
                 raise ValueError(f"fleet member {i}: plant {j} has another kernel build than member 0's plant 0: the kernel build or the self-collision setting differs")
+
+    def _trace_floats(self) -> int:
+        return 0  # (no trace buffer, as for the members' own call: a member stages its trace elites' knots and re-rolls them on its plant 0)
 
     def _models(self) -> GpuModelSet:
         """The plants of the launch: member 0's M where every member's plants are byte-identical to them, list for list; else all B * M, controller-major.  Rebuilt when

@@ -59,7 +59,7 @@ class RandomizedController(FusedPlantController, Assignment, Controller):
         self._init_assignment(blocks, weights, self._admit(task, descriptions))
         super().__init__(controller_config, task, optimizer, device=device)
 
-    def _kind_args(self, b, N: int) -> tuple:
+    def _kind_args(self, plan, b) -> tuple:
         """The entry's arguments between K and `mode`: the table, G, costs."""
         a = self._assignment
         return ((C.c_ubyte * len(a))(*a), len(a), _lib.ptr(b.costs))

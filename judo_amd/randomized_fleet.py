@@ -19,11 +19,10 @@ from typing import Sequence
 import torch
 
 from judo_amd import _lib
-from judo_amd.device import GpuModelSet
 from judo_amd.distributed import world_info
 from judo_amd.ensemble import MAX_ENSEMBLE
 from judo_amd.ensemble_fleet import MAX_ENSEMBLE_FLEET, check_fleet_descriptions, fleet_descriptions
-from judo_amd.fleet import ControllerFleet, _FleetBuffers, refuse_fr3_randomized
+from judo_amd.fleet import ControllerFleet, _LaunchStep, refuse_fr3_randomized
 from judo_amd.plants import PlantFleet
 from judo_amd.randomized import MAX_PLANT_BLOCKS, RandomizedController, blocks_from_weights, check_task, make_randomized_controller
 from judo_amd.tasks import get_registered_tasks
@@ -118,21 +117,17 @@ class RandomizedFleet(PlantFleet, ControllerFleet):
             raise ValueError(f"num_rollouts % blocks != 0: {N} rollouts do not split into {G} equal blocks")
         super().update_action()
 
-    def _trace_floats(self) -> int:
-        return 0  # (no trace buffer, as for the randomised call: a member stages its trace elites' knots and re-rolls them on its plant 0)
+    def _launch(self, step: _LaunchStep) -> None:
+        self._launch_randomized(_lib.lib().jh_plan_step_randomized_batch, step)
 
-    def _launch(self, lib, model_set: GpuModelSet, fb: _FleetBuffers, in_place: bool, noise: torch.Tensor, W, N: int, H: int, K: int, nu: int, costs: torch.Tensor, nfl: int,
-                update_args: tuple, E_t: int, row: int, colmajor: int, stream) -> None:
-        cs = self.controllers
+    def _launch_randomized(self, entry, step: _LaunchStep) -> None:
+        """The B randomised plan steps as one call of `entry`: the set, B, M, the runs, the B assignments in force (which become the members' `_assignment_used`), G, the costs."""
+        cs, s = self.controllers, step
         B, M, G = len(cs), cs[0].num_members, cs[0].blocks
         used = [list(c._assignment) for c in cs]  # the B assignments in force, controller-major
         table = (C.c_ubyte * (B * G))(*[p for a in used for p in a])
-        off = fb.offsets
-        mode, lam, k_el, tie = update_args
-        st = lib.jh_plan_step_randomized_batch(model_set.handle, B, M, fb.host_ptr if in_place else fb.blk.data_ptr(), fb.host_ptr, 4 * fb.nblk, 4 * fb.blk_stride, off[1], off[2], off[3], off[4],
-                                               noise.data_ptr(), N, K * nu * N, _lib.ptr(W), N, H, K, table, G, costs.data_ptr(), mode, lam, k_el, tie, fb.scratch.data_ptr(),
-                                               fb.out_host_ptr, fb.out_stride, fb.done.data_ptr() if in_place else fb.out_host_ptr, None, stream)
-        _lib.check(st, "jh_plan_step_randomized_batch")
+        rc = entry(s.model_set.handle, B, M, *s.block, *s.noise_args, *s.sizes, table, G, s.costs.data_ptr(), *s.update_args, *s.tail)
+        _lib.check(rc, entry.__name__)
         for c, a in zip(cs, used):
             c._assignment_used = a
 

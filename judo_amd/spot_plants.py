@@ -21,7 +21,6 @@ import torch
 from judo_amd import _lib
 from judo_amd.config import ControllerConfig
 from judo_amd.controller import Controller
-from judo_amd.distributed import Shard
 from judo_amd.plants import Assignment, PlantSet, WorstCase, make_for, spline_controls
 from judo_amd.tasks import Task
 from judo_amd.tree_model import MAX_TREE_PLANTS, check_tree_descriptions
@@ -62,11 +61,11 @@ class _SpotPlantController(PlantSet, Controller):
                              f"(a process group or force_shard_path: the sharded path has no {self._kind} form)")
         return super()._iteration_shape(world, nrm)
 
-    def _candidates_iteration(self, lib, b, nrm, nominal_n, W, shard: Shard, H, K, nu, N, stream, state):
-        if shard.world > 1:
+    def _candidates_iteration(self, plan, b, st) -> None:
+        if plan.shard.world > 1:
             raise ValueError(f"a Spot {self._kind} controller runs its rollouts as one jh_policy_rollout_plants call, which this configuration rules out "
                              f"(a process group or force_shard_path: the sharded path has no {self._kind} form)")
-        return super()._candidates_iteration(lib, b, nrm, nominal_n, W, shard, H, K, nu, N, stream, state)
+        super()._candidates_iteration(plan, b, st)
 
     def solver_stats(self, reset: bool = True) -> dict:
         """`Controller.solver_stats` from the set's counters: the plan steps' launches run on the set, not on a member's engine."""
@@ -77,9 +76,9 @@ class _SpotPlantController(PlantSet, Controller):
                           f"constraint solves stopped at the iteration cap in {st['steps']} physics steps -- those rollouts are approximate", stacklevel=2)
         return st
 
-    def _spline_commands(self, nom_d, noise_p, ldn: int, sig_d, lohi_d, knots_nku, W, shard: Shard, H: int, K: int, stream) -> tuple[torch.Tensor, torch.Tensor]:
+    def _spline_commands(self, plan, b, st) -> tuple[torch.Tensor, torch.Tensor]:
         """The candidates' controls at the rollout times (`plants.spline_controls`, once) and the policy commands they map to."""
-        controls = spline_controls(self, nom_d, noise_p, ldn, sig_d, lohi_d, knots_nku, W, shard, H, K, stream)
+        controls = spline_controls(self, plan, b, st)
         return controls, self.task.task_to_sim_ctrl(controls).to(torch.float32).contiguous()
 
 
@@ -123,19 +122,18 @@ class SpotEnsembleController(WorstCase, _SpotPlantController):
             self._last_policy_output = self._plant_policy_out[: rows // len(self._descriptions)]
         return pb, self._plant_policy_out
 
-    def _materialised_costs(self, x0_d, nom_d, noise_p, ldn: int, sig_d, lohi_d, knots_nku, W, shard: Shard, H: int, K: int, stream) -> torch.Tensor:
-        lib = _lib.lib()
-        M, N = len(self._descriptions), shard.count
-        controls, commands = self._spline_commands(nom_d, noise_p, ldn, sig_d, lohi_d, knots_nku, W, shard, H, K, stream)
+    def _materialised_costs(self, plan, b, st) -> torch.Tensor:
+        M, N = len(self._descriptions), plan.shard.count
+        controls, commands = self._spline_commands(plan, b, st)
         pb, policy_out = self._carried(M * N)
         nx = self.plants.nq + self.plants.nv
-        states, sensors = pb.rollout_plants(self.plants, x0_d, nx, 1, M, list(range(M)), commands.repeat(M, 1, 1), policy_out, cutoff_time=self.rollout_cutoff_time)
+        states, sensors = pb.rollout_plants(self.plants, b.x0, nx, 1, M, list(range(M)), commands.repeat(M, 1, 1), policy_out, cutoff_time=self.rollout_cutoff_time)
         rows = self._member_cost_rows(N)
         for m in range(M):  # the reward per member, in the shapes a plain controller gives it
             self._score_rollout(states[m * N : (m + 1) * N], sensors[m * N : (m + 1) * N], controls, out=rows[m])
         self.last_rollout = (states[:N], sensors[:N], controls)  # member 0, the nominal plant
         costs = torch.empty(N, dtype=torch.float32, device=self.device)
-        _lib.check(lib.jh_ensemble_costs(_lib.ptr(rows), M, N, N, self._worst, _lib.ptr(costs), stream), "jh_ensemble_costs")
+        _lib.check(_lib.lib().jh_ensemble_costs(_lib.ptr(rows), M, N, N, self._worst, _lib.ptr(costs), st.stream), "jh_ensemble_costs")
         return costs
 
 
@@ -152,13 +150,13 @@ class SpotRandomizedController(Assignment, _SpotPlantController):
         self._init_assignment(blocks, weights, len(descriptions))
         super().__init__(controller_config, task, optimizer, descriptions, device=device)
 
-    def _materialised_costs(self, x0_d, nom_d, noise_p, ldn: int, sig_d, lohi_d, knots_nku, W, shard: Shard, H: int, K: int, stream) -> torch.Tensor:
-        N, a = shard.count, list(self._assignment)
-        controls, commands = self._spline_commands(nom_d, noise_p, ldn, sig_d, lohi_d, knots_nku, W, shard, H, K, stream)
+    def _materialised_costs(self, plan, b, st) -> torch.Tensor:
+        N, a = plan.shard.count, list(self._assignment)
+        controls, commands = self._spline_commands(plan, b, st)
         if self._last_policy_output is None:
             self._last_policy_output = torch.zeros((N, POLICY_OUTPUT_DIM), dtype=torch.float32, device=self.device)
         nx = self.plants.nq + self.plants.nv
-        states, sensors = self.rollout_backend.rollout_plants(self.plants, x0_d, nx, 1, len(a), a, commands, self._last_policy_output, cutoff_time=self.rollout_cutoff_time)
+        states, sensors = self.rollout_backend.rollout_plants(self.plants, b.x0, nx, 1, len(a), a, commands, self._last_policy_output, cutoff_time=self.rollout_cutoff_time)
         self._assignment_used = a
         return self._score_rollout(states, sensors, controls)
 
