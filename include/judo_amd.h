@@ -419,6 +419,36 @@ int jh_plan_step_ensemble(const jh_model_set* set, void* blk_dev, const void* bl
 int jh_plan_step_ensemble_phase(const jh_model_set* set, void* blk_dev, const void* blk_host, size_t blk_bytes, int o_nominal, int o_sigma, int o_tp, int o_lohi, const float* noise, int ldn,
                                 const float* W, int phase, int N, int H, int K, float* member_costs /* DEVICE, M x N */, float* costs /* DEVICE, N */, int worst, int mode, float lambda, int k,
                                 int tie_high, float* scratch, float* out /* nominal | sigma */, void* out_host_mark, void* const* timing, void* stream);
+/* The plant-weighted risk measure: the tail mean (CVaR) of a candidate's member costs c[0..M-1] under fp32 weights p[0..M-1] (each finite and >= 0, at least one > 0; a
+ * posterior over the plants, judo_amd/identify.py) with the tail mass `tail`, fp32 in (0, 1].  Fixed here so that it can be tested bit for bit:
+ *   got = 0.  Visit the DISTINCT values of c in strictly descending order.  For a value v: ws is the sum of the weights of the members with c[m] == v, taken in ascending
+ *   m and starting from the first (ws = p[m0]; ws = ws + p[m1]; ...); take = min(ws, tail - got).  If take > 0: t = take * v; acc = t for the first such term, else
+ *   acc = acc + t; got = got + take.  A group with take == 0 contributes nothing (a +inf member of weight zero makes no NaN).  Stop when got >= tail or the values are
+ *   exhausted.  cost = acc / got.
+ * Every product, sum, difference and quotient is rounded to fp32 on its own; no fused multiply-add.  The divisor is the mass actually taken, so weights that add up to
+ * less than `tail` give the weighted mean of everything, and the weights need not add up to 1.  +inf and the 3.0e38 sentinel behave as IEEE arithmetic makes them; NaN
+ * member costs are outside the contract.  One-hot weights with tail = 1 return that member's costs exactly; uniform weights 1 / M with tail = j / M, M a power of two, are
+ * bit for bit `worst` = j on a rollout whose M costs are pairwise distinct (with ties 3 * v is rounded once and v + v + v twice).
+ * judo_amd/ensemble.py::aggregate_costs_weighted_host restates it in numpy.
+ *   jh_ensemble_costs_weighted            jh_ensemble_costs with `weights` (HOST, M floats, read before the call returns: they travel in the kernel arguments) and `tail`
+ *                                         where `worst` stands.  JH_ERR_INVALID, naming the argument: what jh_ensemble_costs refuses, null `weights`, a weight that is
+ *                                         negative or not finite (the index is named), all weights zero, `tail` outside (0, 1] or NaN.
+ *   jh_plan_step_ensemble_weighted        jh_plan_step_ensemble with `weights` and `tail` where `worst` stands: the same rollout launch, so member_costs are bit for bit the
+ *                                         unweighted entry's; the tail launch aggregates with the weighted measure and updates.  Following a belief between plan steps
+ *                                         costs no copy and no launch.  Every check of jh_plan_step_ensemble but `worst`'s, and those of the weights and the tail above,
+ *                                         all before anything is enqueued.
+ *   jh_plan_step_ensemble_weighted_phase  the same for fr3_pick, `phase` behind W: the rules of jh_plan_step_ensemble_phase.
+ * The batched entries have no weighted form: B x M weights do not fit in the kernel arguments. */
+int jh_ensemble_costs_weighted(const float* member_costs /* DEVICE, M x ld */, int M, int N, int ld, const float* weights /* HOST, M */, float tail, float* costs /* DEVICE, N */,
+                               void* stream);
+int jh_plan_step_ensemble_weighted(const jh_model_set* set, void* blk_dev, const void* blk_host, size_t blk_bytes, int o_nominal, int o_sigma, int o_tp, int o_lohi, const float* noise,
+                                   int ldn, const float* W, int N, int H, int K, float* member_costs /* DEVICE, M x N */, float* costs /* DEVICE, N */,
+                                   const float* weights /* HOST, M */, float tail, int mode, float lambda, int k, int tie_high, float* scratch, float* out /* nominal | sigma */,
+                                   void* out_host_mark, void* const* timing, void* stream);
+int jh_plan_step_ensemble_weighted_phase(const jh_model_set* set, void* blk_dev, const void* blk_host, size_t blk_bytes, int o_nominal, int o_sigma, int o_tp, int o_lohi,
+                                         const float* noise, int ldn, const float* W, int phase, int N, int H, int K, float* member_costs /* DEVICE, M x N */,
+                                         float* costs /* DEVICE, N */, const float* weights /* HOST, M */, float tail, int mode, float lambda, int k, int tie_high, float* scratch,
+                                         float* out /* nominal | sigma */, void* out_host_mark, void* const* timing, void* stream);
 /* B ensemble plan steps as ONE call with ONE completion mark (several robots, or one robot swept over risk levels, goals or seeds: B controllers that each plan against
  * M plants; the reference has no counterpart).  Controller b rolls its own N candidates out on its M plants, aggregates them with its own worst[b] and updates its own
  * nominal; its results are bit for bit those of jh_plan_step_ensemble on its block, its noise and its plants with worst[b].

@@ -887,9 +887,10 @@ extern "C" int jh_plan_step_batch_phases_models(const jh_model_set* set, int B, 
                          noise_stride_floats, W, N, H, K, costs, trace, mode, lambda, k, tie_high, E, row_floats, colmajor, scratch, out, out_stride_floats, out_host_mark, timing, stream);
 }
 
-// ---- plan steps on the plants of a model set (include/judo_amd.h): ONE launcher behind the eight entries, with three degrees of freedom ----
+// ---- plan steps on the plants of a model set (include/judo_amd.h): ONE launcher behind the ten entries, with three degrees of freedom ----
 //  - the kind, what the rollout launch's y axis means.  Ensemble: the M members -- every member rolls out the same N candidates from the same block (block and noise
 //    strides 0) on its own image into its own row of member_costs, and the tail aggregates the M rows into `costs` (the mean of the `worst` largest) before it updates.
+//    With `weights` set the tail is the plant-weighted one (the tail mean under the weights, which travel in the kernel arguments); the rollout launch is the same call.
 //    Randomised: G blocks of Nb = N / G rollouts, block g on plant plant_of_block[g] -- block stride 0, noise and cost strides Nb (block g's columns of the one noise
 //    matrix, its slice of `costs`), and the plant axis (jh_internal.h) with the rollout-index stride Nb, so that only global rollout 0 drops its noise, and the table, which
 //    travels in the kernel arguments; the tail is the plain one on the N costs.
@@ -909,6 +910,7 @@ struct jh_set_step {
   const char* fr3_hint = "";                                                          // what a non-phase entry names behind its refusal of fr3_pick
   bool randomized = false;
   float* member_costs = nullptr; const int* worst = nullptr;                          // ensemble: (B x) M x N costs; one `worst`, or B with a controller axis
+  const float* weights = nullptr; float tail = 0.f;                                   // ensemble, set: the plant-weighted risk measure (HOST, M) stands where `worst` does
   const unsigned char* plant_of_block = nullptr; int G = 0;                           // randomised: the (B x) G table
   bool fleet = false; int B = 1, M = 0; size_t out_stride_floats = 0;                 // the controller axis (its block and noise strides are the shape's)
   int phase = -1, o_phase = -1;
@@ -919,7 +921,7 @@ static int plan_step_set(const jh_set_step& r) {
   const jh_block_shape& d = r.shape;
 #define JH_SET_PTR(p) JH_REQUIRE(r.p != nullptr, "%s: " #p " is a null pointer", who)
   JH_SET_PTR(set); JH_SET_PTR(blk_dev); JH_SET_PTR(blk_host); JH_SET_PTR(noise); JH_SET_PTR(W);
-  if (r.randomized) JH_SET_PTR(plant_of_block); else { JH_SET_PTR(member_costs); JH_SET_PTR(worst); }
+  if (r.randomized) JH_SET_PTR(plant_of_block); else { JH_SET_PTR(member_costs); if (!r.weights) JH_SET_PTR(worst); }
   JH_SET_PTR(costs); JH_SET_PTR(scratch); JH_SET_PTR(out);
 #undef JH_SET_PTR
   const jh_model_set* set = r.set;
@@ -934,7 +936,9 @@ static int plan_step_set(const jh_set_step& r) {
     JH_REQUIRE(B * G <= JH_MAX_FLEET_PLANT_BLOCKS, "%s: B * G = %d * %d = %d exceeds JH_MAX_FLEET_PLANT_BLOCKS = %d (the bytes of the table in the kernel arguments)", who, B, G, B * G,
                JH_MAX_FLEET_PLANT_BLOCKS);
   if (r.fleet) JH_REQUIRE(set->B == M || set->B == B * M, "%s: a set of %d members is neither the M = %d plants every controller shares nor the B * M = %d plants of B = %d controllers", who, set->B, M, B * M, B);
-  if (!r.randomized && !r.fleet) JH_REQUIRE(r.worst[0] >= 1 && r.worst[0] <= M, "%s: worst = %d outside [1, M = %d]", who, r.worst[0], M);
+  jh_upd::EnsembleWeights weights;  // (read here: the caller's array is free when the call returns)
+  if (r.weights) { if (int rc = jh_ensemble_weights_check(who, r.weights, M, r.tail, &weights)) return rc; }
+  if (!r.randomized && !r.fleet && !r.weights) JH_REQUIRE(r.worst[0] >= 1 && r.worst[0] <= M, "%s: worst = %d outside [1, M = %d]", who, r.worst[0], M);
   if (!r.randomized && r.fleet) for (int b = 0; b < B; b++) JH_REQUIRE(r.worst[b] >= 1 && r.worst[b] <= M, "%s: controller %d: worst = %d outside [1, M = %d]", who, b, r.worst[b], M);
   const bool phased = r.phase >= 0 || r.o_phase >= 0;
   if (m->kind == JH_TASK_FR3_PICK && !phased) { jh_set_error("%s: fr3_pick has no batched plan step (its phase is chosen per problem on the host) behind this entry: %s", who, r.fr3_hint); return JH_ERR_UNSUPPORTED; }
@@ -991,7 +995,8 @@ static int plan_step_set(const jh_set_step& r) {
     rc = eb->rollout_cost_batch(m, ra, rb, st);
   }
   if (rc == JH_OK && r.timing) JH_HIP(hipEventRecord((hipEvent_t)r.timing[1], st));
-  if (rc == JH_OK && !r.fleet) rc = r.randomized ? jh_update_tail_launch(a, st) : jh_update_tail_ensemble_launch(a, jh_upd::EnsembleArgs{r.member_costs, r.costs, M, r.worst[0], (long long)N}, st);
+  if (rc == JH_OK && r.weights) rc = jh_update_tail_ensemble_weighted_launch(a, jh_upd::EnsembleWeightedArgs{r.member_costs, r.costs, M, r.tail, (long long)N, weights}, st);
+  else if (rc == JH_OK && !r.fleet) rc = r.randomized ? jh_update_tail_launch(a, st) : jh_update_tail_ensemble_launch(a, jh_upd::EnsembleArgs{r.member_costs, r.costs, M, r.worst[0], (long long)N}, st);
   if (rc == JH_OK && r.fleet) {
     jh_upd::BatchArgs s;  // the tail's axis: the controllers
     s.B = B; s.blk = blk_c; s.noise = noise_c; s.costs = N; s.trace = 0; s.scratch = (long long)jh_update_fused_scratch_floats(N, K, m->nu); s.out = (long long)r.out_stride_floats;
@@ -1020,6 +1025,19 @@ extern "C" int jh_plan_step_ensemble(const jh_model_set* set, void* blk_dev, con
   return plan_step_set(r);
 }
 
+// jh_plan_step_ensemble with the plant-weighted risk measure: the same record with the weights and the tail mass, so the rollout launch is the same call and the tail
+// launch the weighted one.
+extern "C" int jh_plan_step_ensemble_weighted(const jh_model_set* set, void* blk_dev, const void* blk_host, size_t blk_bytes, int o_nominal, int o_sigma, int o_tp, int o_lohi, const float* noise,
+                                              int ldn, const float* W, int N, int H, int K, float* member_costs, float* costs, const float* weights, float tail, int mode, float lambda, int k,
+                                              int tie_high, float* scratch, float* out, void* out_host_mark, void* const* timing, void* stream) {
+  const char* who = "plan_step_ensemble_weighted";
+  JH_REQUIRE(weights != nullptr, "%s: weights is a null pointer", who);
+  jh_set_step r = JH_SET_STEP(who, false, 0, 0);
+  r.fr3_hint = "jh_plan_step_ensemble_weighted_phase takes the arm's phase and plans it against the set's plants";
+  r.member_costs = member_costs; r.weights = weights; r.tail = tail;
+  return plan_step_set(r);
+}
+
 // jh_plan_step_ensemble for fr3_pick: the same record with the arm's phase, which the fr3 kernel's members take from the launch record.
 extern "C" int jh_plan_step_ensemble_phase(const jh_model_set* set, void* blk_dev, const void* blk_host, size_t blk_bytes, int o_nominal, int o_sigma, int o_tp, int o_lohi, const float* noise,
                                            int ldn, const float* W, int phase, int N, int H, int K, float* member_costs, float* costs, int worst, int mode, float lambda, int k, int tie_high,
@@ -1030,6 +1048,21 @@ extern "C" int jh_plan_step_ensemble_phase(const jh_model_set* set, void* blk_de
   JH_REQUIRE(phase >= 0 && phase <= 3, "%s: phase = %d is not 0, 1, 2 or 3 (LIFT, MOVE, PLACE, HOMING)", who, phase);
   jh_set_step r = JH_SET_STEP(who, false, 0, 0);
   r.member_costs = member_costs; r.worst = &worst; r.phase = phase;
+  return plan_step_set(r);
+}
+
+// jh_plan_step_ensemble_phase with the plant-weighted risk measure.
+extern "C" int jh_plan_step_ensemble_weighted_phase(const jh_model_set* set, void* blk_dev, const void* blk_host, size_t blk_bytes, int o_nominal, int o_sigma, int o_tp, int o_lohi,
+                                                    const float* noise, int ldn, const float* W, int phase, int N, int H, int K, float* member_costs, float* costs, const float* weights,
+                                                    float tail, int mode, float lambda, int k, int tie_high, float* scratch, float* out, void* out_host_mark, void* const* timing,
+                                                    void* stream) {
+  const char* who = "plan_step_ensemble_weighted_phase";
+  JH_REQUIRE(set != nullptr, "%s: set is a null pointer", who);
+  if (set->m0->kind != JH_TASK_FR3_PICK) { jh_set_error("%s: a phase is fr3_pick's alone; jh_plan_step_ensemble_weighted plans this set", who); return JH_ERR_UNSUPPORTED; }
+  JH_REQUIRE(phase >= 0 && phase <= 3, "%s: phase = %d is not 0, 1, 2 or 3 (LIFT, MOVE, PLACE, HOMING)", who, phase);
+  JH_REQUIRE(weights != nullptr, "%s: weights is a null pointer", who);
+  jh_set_step r = JH_SET_STEP(who, false, 0, 0);
+  r.member_costs = member_costs; r.weights = weights; r.tail = tail; r.phase = phase;
   return plan_step_set(r);
 }
 

@@ -10,6 +10,7 @@
 // log-sum-exp rescale so that no global minimum pass is needed first.
 #include "jh_update_dev.h"
 #include <algorithm>
+#include <cmath>
 
 namespace {
 
@@ -542,6 +543,58 @@ __global__ __launch_bounds__(kUB) void k_update_tail_ensemble_batch(TailArgs bas
 
 int jh_update_tail_ensemble_batch_launch(const TailArgs& a, const BatchArgs& s, const EnsembleBatchArgs& e, hipStream_t st) {
   hipLaunchKernelGGL(k_update_tail_ensemble_batch, dim3((a.N + kUB - 1) / kUB, s.B), dim3(kUB), 0, st, a, s, e);
+  JH_HIP(hipGetLastError());
+  return JH_OK;
+}
+
+// ------------------------------------------------------------------------------------------------ the plant-weighted risk measure of an ensemble
+// (Defined behind everything else, for the reason above.)  k_ensemble_costs_weighted is the weighted aggregation alone (jh_update_dev.h: ensemble_cost_weighted),
+// k_update_tail_ensemble_weighted what jh_plan_step_ensemble_weighted launches behind the batched rollout kernel: k_update_tail_ensemble with the weights and the
+// tail mass in the kernel arguments where `worst` stands.
+namespace {
+__global__ __launch_bounds__(kUB) void k_ensemble_costs_weighted(EnsembleWeightedArgs e, int N) {
+  const int r = blockIdx.x * kUB + threadIdx.x;
+  if (r < N) e.costs[r] = ensemble_cost_weighted(e.member_costs, e.M, e.stride, r, e.weights, e.tail);
+}
+__global__ __launch_bounds__(kUB) void k_update_tail_ensemble_weighted(TailArgs a, EnsembleWeightedArgs e) {
+  const int r = blockIdx.x * kUB + threadIdx.x;
+  if (r < a.N) e.costs[r] = ensemble_cost_weighted(e.member_costs, e.M, e.stride, r, e.weights, e.tail);
+  __syncthreads();  // (a thread reads back the cost it wrote, as in k_update_tail_ensemble)
+  update_tail_body(a);
+}
+}  // namespace
+
+int jh_ensemble_weights_check(const char* who, const float* weights, int M, float tail, EnsembleWeights* out) {
+  JH_REQUIRE(weights != nullptr, "%s: weights is a null pointer", who);
+  JH_REQUIRE(M >= 1 && M <= JH_MAX_ENSEMBLE, "%s: M = %d outside [1, JH_MAX_ENSEMBLE = %d]", who, M, JH_MAX_ENSEMBLE);
+  bool positive = false;
+  for (int m = 0; m < JH_MAX_ENSEMBLE; m++) {
+    const float p = m < M ? weights[m] : 0.f;
+    JH_REQUIRE(std::isfinite(p) && p >= 0.f, "%s: weights[%d] = %g is negative or not finite", who, m, (double)p);
+    positive = positive || p > 0.f;
+    out->p[m] = p;
+  }
+  JH_REQUIRE(positive, "%s: weights are all zero (M = %d): at least one plant needs a positive weight", who, M);
+  JH_REQUIRE(tail > 0.f && tail <= 1.f, "%s: tail = %g outside (0, 1]", who, (double)tail);  // (false for NaN)
+  return JH_OK;
+}
+
+extern "C" int jh_ensemble_costs_weighted(const float* member_costs, int M, int N, int ld, const float* weights, float tail, float* costs, void* stream) {
+  const char* who = "ensemble_costs_weighted";
+  JH_REQUIRE(member_costs != nullptr, "%s: member_costs is a null pointer", who);
+  JH_REQUIRE(costs != nullptr, "%s: costs is a null pointer", who);
+  JH_REQUIRE(M >= 1 && M <= JH_MAX_ENSEMBLE, "%s: M = %d outside [1, JH_MAX_ENSEMBLE = %d]", who, M, JH_MAX_ENSEMBLE);
+  JH_REQUIRE(N > 0, "%s: N must be positive (N=%d)", who, N);
+  JH_REQUIRE(ld >= N, "%s: ld (%d) < N (%d)", who, ld, N);
+  EnsembleWeightedArgs e{member_costs, costs, M, tail, (long long)ld, {}};
+  if (int rc = jh_ensemble_weights_check(who, weights, M, tail, &e.weights)) return rc;
+  hipLaunchKernelGGL(k_ensemble_costs_weighted, dim3((N + kUB - 1) / kUB), dim3(kUB), 0, (hipStream_t)stream, e, N);
+  JH_HIP(hipGetLastError());
+  return JH_OK;
+}
+
+int jh_update_tail_ensemble_weighted_launch(const TailArgs& a, const EnsembleWeightedArgs& e, hipStream_t st) {
+  hipLaunchKernelGGL(k_update_tail_ensemble_weighted, dim3((a.N + kUB - 1) / kUB), dim3(kUB), 0, st, a, e);
   JH_HIP(hipGetLastError());
   return JH_OK;
 }

@@ -397,6 +397,54 @@ __device__ __forceinline__ float ensemble_cost(const float* __restrict__ member_
   return __fdiv_rn(acc, (float)worst);
 }
 
+// The plant-weighted form (jh_plan_step_ensemble_weighted, jh_ensemble_costs_weighted): the tail mean (CVaR) of the member costs under the weights p[0..M-1] with the
+// tail mass `tail`, as include/judo_amd.h fixes it and judo_amd/ensemble.py::aggregate_costs_weighted_host restates it.  The distinct values are visited in strictly
+// descending order; a value's group weight ws is the sum of its members' weights in ascending m; take = min(ws, tail - got); a group with take > 0 adds take * value
+// and its take to the mass `got`; the result is acc / got.  Every operation is rounded to fp32 on its own (no fused multiply-add).  The same shape as ensemble_cost:
+// one thread per rollout, the M values in registers through loops unrolled to JH_MAX_ENSEMBLE under the wave-uniform guard m < M, selection by passes -- a pass finds
+// the largest value below the one visited last and its group weight; at most M passes.  The weights are a by-value record in the kernel arguments: after unrolling
+// every index into it is a constant and the weights are scalar operands.  A pass that finds nothing ends the loop, so NaN members (outside the contract) end it too.
+struct EnsembleWeights {
+  float p[JH_MAX_ENSEMBLE];
+};
+struct EnsembleWeightedArgs {
+  const float* member_costs; float* costs;  // M x stride in, N out (`costs` is the tail's TailArgs::costs)
+  int M; float tail; long long stride;
+  EnsembleWeights weights;
+};
+__device__ __forceinline__ float ensemble_cost_weighted(const float* __restrict__ member_costs, int M, long long stride, int r, const EnsembleWeights& weights, float tail) {
+  float v[JH_MAX_ENSEMBLE];
+#pragma unroll
+  for (int m = 0; m < JH_MAX_ENSEMBLE; m++) v[m] = m < M ? member_costs[m * stride + r] : 0.f;
+  float acc = 0.f, got = 0.f, hi = 0.f;
+  bool started = false;
+  for (int pass = 0; pass < M; pass++) {
+    float cur = 0.f, ws = 0.f; bool have = false;
+#pragma unroll
+    for (int m = 0; m < JH_MAX_ENSEMBLE; m++) {
+      const float x = v[m];
+      const bool open = m < M && (pass == 0 || x < hi);  // not yet visited: every value at or above `hi` went in an earlier pass
+      const bool up = open && (!have || x > cur);
+      ws = up ? weights.p[m] : ((open && x == cur) ? __fadd_rn(ws, weights.p[m]) : ws);
+      cur = up ? x : cur;
+      have = have || open;
+    }
+    if (!have) break;
+    const float rem = __fsub_rn(tail, got);
+    const float take = ws < rem ? ws : rem;
+    if (take > 0.f) {  // (a group of weight zero contributes nothing: a +inf member of weight zero makes no NaN)
+      float t = __fmul_rn(take, cur);
+      asm volatile("" : "+v"(t));  // the product is a rounded value of its own: HIP's __fmul_rn is a plain `*`, which -ffp-contract=fast would fuse into the sum below
+      acc = started ? __fadd_rn(acc, t) : t;
+      got = __fadd_rn(got, take);
+      started = true;
+    }
+    hi = cur;
+    if (got >= tail) break;
+  }
+  return __fdiv_rn(acc, got);
+}
+
 // ---------------------------------------------------------------- B ensemble controllers in one launch (jh_plan_step_ensemble_batch)
 // The rollout launch has a third grid dimension: blockIdx.y stays the member (the problem axis above, block and noise strides 0, the set's image stride) and blockIdx.z
 // is the controller, with strides of its own -- `blk` / `noise` floats from a controller's packed block / noise to the next one's, `image` floats from its plant 0 to the
@@ -444,3 +492,7 @@ int jh_simple_rollout_cost_batch(const jh_model* m, const float* P, const float*
                                  const jh_upd::ControllerAxis& z = {}, const jh_plant_axis& p = {});
 // the ensemble fleet's tail (jh_plan_step_ensemble_batch): `a` is controller 0's record, `s` the controllers' strides and the two-level ticket; grid (tail workgroups, s.B)
 int jh_update_tail_ensemble_batch_launch(const jh_upd::TailArgs& a, const jh_upd::BatchArgs& s, const jh_upd::EnsembleBatchArgs& e, hipStream_t st);
+// the plant-weighted ensemble form (jh_plan_step_ensemble_weighted): jh_update_tail_ensemble_launch with the weighted aggregation in front of the tail.
+// jh_ensemble_weights_check is the host check of both weighted entries -- `weights` HOST, M finite values >= 0 with one above 0, `tail` in (0, 1] -- and fills the record.
+int jh_ensemble_weights_check(const char* who, const float* weights, int M, float tail, jh_upd::EnsembleWeights* out);
+int jh_update_tail_ensemble_weighted_launch(const jh_upd::TailArgs& a, const jh_upd::EnsembleWeightedArgs& e, hipStream_t st);

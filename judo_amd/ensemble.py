@@ -41,6 +41,58 @@ def aggregate_costs_host(member_costs, worst: int) -> np.ndarray:
         return (acc / np.float32(j)).astype(np.float32)
 
 
+def aggregate_costs_weighted_host(member_costs, weights, tail) -> np.ndarray:
+    """The plant-weighted aggregated cost of every rollout, (N,) fp32, from `member_costs` (M, N): the tail mean (CVaR) of a rollout's M member costs under `weights`
+    (M fp32 values, each finite and >= 0, at least one > 0) with the tail mass `tail`, fp32 in (0, 1], as include/judo_amd.h fixes it.  The distinct values are visited
+    in strictly descending order; a value's weight ws is the sum of its members' weights in ascending m; take = min(ws, tail - got); a group with take > 0 adds
+    take * value to the sum and take to the mass `got`; the result is the sum over `got`.  Every operation is rounded to fp32 on its own.  +inf and the 3.0e38 sentinel
+    behave as IEEE arithmetic makes them; NaN costs are outside the contract.  What `ensemble_cost_weighted` (judo_amd/csrc/jh_update_dev.h) computes, bit for bit.
+    Raises ValueError for what `jh_ensemble_costs_weighted` refuses."""
+    c = np.asarray(member_costs, dtype=np.float32)
+    if c.ndim != 2:
+        raise ValueError(f"member_costs must be (M, N), got {c.shape}")
+    M, N = c.shape
+    if not 1 <= M <= MAX_ENSEMBLE:
+        raise ValueError(f"M = {M} outside [1, JH_MAX_ENSEMBLE = {MAX_ENSEMBLE}]")
+    if weights is None:
+        raise ValueError("weights is None")
+    with np.errstate(over="ignore"):
+        p = np.asarray(weights, dtype=np.float32).reshape(-1)
+    if p.size != M:
+        raise ValueError(f"{p.size} weights for M = {M} plants")
+    for m in range(M):
+        if not (np.isfinite(p[m]) and p[m] >= 0):
+            raise ValueError(f"weights[{m}] = {p[m]} is negative or not finite")
+    if not (p > 0).any():
+        raise ValueError(f"weights are all zero (M = {M}): at least one plant needs a positive weight")
+    tail = np.float32(tail)
+    if not (tail > 0 and tail <= 1):  # (false for NaN)
+        raise ValueError(f"tail = {tail} outside (0, 1]")
+    f32 = np.float32
+    acc, got, hi = np.zeros(N, f32), np.zeros(N, f32), np.zeros(N, f32)
+    started, live = np.zeros(N, bool), np.ones(N, bool)
+    with np.errstate(over="ignore", invalid="ignore"):
+        for step in range(M):  # one pass per distinct value, at most M
+            cur, ws, have = np.zeros(N, f32), np.zeros(N, f32), np.zeros(N, bool)
+            for m in range(M):
+                x = c[m]
+                is_open = live & (x < hi) if step else live.copy()  # not yet visited
+                up = is_open & (~have | (x > cur))
+                ws = np.where(up, p[m], np.where(is_open & (x == cur), (ws + p[m]).astype(f32), ws)).astype(f32)
+                cur = np.where(up, x, cur)
+                have |= is_open
+            rem = (tail - got).astype(f32)
+            take = np.where(ws < rem, ws, rem).astype(f32)
+            add = have & (take > 0)
+            t = (take * cur).astype(f32)
+            acc = np.where(add, np.where(started, (acc + t).astype(f32), t), acc).astype(f32)
+            got = np.where(add, (got + take).astype(f32), got).astype(f32)
+            started |= add
+            hi = np.where(have, cur, hi)
+            live &= have & ~(got >= tail)
+        return (acc / got).astype(f32)
+
+
 def check_task(task: Task, fr3: bool = False) -> None:
     """The tasks without an ensemble plan step, refused before any model is made; raises ValueError.  `fr3`: the caller's plan step carries the arm's phase
     (judo_amd.fr3_ensemble), so fr3_pick passes."""
@@ -67,6 +119,7 @@ class EnsembleController(FusedPlantController, WorstCase, Controller):
 
     _fr3_ensemble = False  # (FR3EnsembleController: the plan step carries the arm's phase; only an FR3EnsembleFleet takes such a member)
     _entry = "jh_plan_step_ensemble"  # the library call of the plan step: the rollout kernel on (workgroups, M), the aggregation in front of the update's tail
+    _weighted_entry = "jh_plan_step_ensemble_weighted"  # ... while plant weights are set: the same rollout launch, the plant-weighted aggregation in the tail
     _a, _form, _whose, _call, _maker = "an ensemble", "ensemble", "members'", "jh_plan_step_ensemble", "ensemble"
     _member_of = "an ensemble of {}"
     _ensemble_refusal = FusedPlantController._refusal  # (the name the fleets call)
@@ -80,9 +133,14 @@ class EnsembleController(FusedPlantController, WorstCase, Controller):
         super().__init__(controller_config, task, optimizer, device=device)
         self._init_worst(worst, len(self._members))
 
+    def _entry_name(self) -> str:
+        """The weighted form of the call while weights are set (`set_weights`)."""
+        return self._weighted_entry if self._risk_weights is not None else self._entry
+
     def _kind_args(self, plan, b) -> tuple:
-        """The entry's arguments between K and `mode`: member_costs, costs, worst."""
-        return (self._member_cost_rows(plan.shard.count).data_ptr(), _lib.ptr(b.costs), self._worst)
+        """The entry's arguments between K and `mode`: member_costs, costs, and `worst` or the host weights and the tail mass."""
+        risk = (self._risk_weights, self.tail) if self._risk_weights is not None else (self._worst,)
+        return (self._member_cost_rows(plan.shard.count).data_ptr(), _lib.ptr(b.costs), *risk)
 
 
 def make_ensemble_controller(task: str | Task, optimizer: str, descriptions: Sequence[dict], worst: int | None = None, device: torch.device | None = None) -> EnsembleController:
@@ -92,4 +150,4 @@ def make_ensemble_controller(task: str | Task, optimizer: str, descriptions: Seq
     return make_for(EnsembleController, task, optimizer, descriptions, worst=worst, device=device)
 
 
-__all__ = ["EnsembleController", "MAX_ENSEMBLE", "aggregate_costs_host", "check_descriptions", "check_task", "make_ensemble_controller"]
+__all__ = ["EnsembleController", "MAX_ENSEMBLE", "aggregate_costs_host", "aggregate_costs_weighted_host", "check_descriptions", "check_task", "make_ensemble_controller"]

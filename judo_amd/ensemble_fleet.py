@@ -116,10 +116,18 @@ class EnsembleFleet(PlantFleet, ControllerFleet):
             why = "a plugin reward, hook or optimizer (uses_fused_cost is false): the members' costs come from the fused kernels alone"
         if why is not None:
             raise ValueError(f"fleet member {i} does not run its iteration as one ensemble plan step ({why}): only such controllers can share a launch")
+        self._refuse_weights(i, c)
         if c.num_members != first.num_members:
             raise ValueError(f"fleet member {i} differs from member 0 in the number of plants M: {c.num_members} against {first.num_members}")
         self._check_plants(i, c, first)
         super()._check_member(i, c, first)
+
+    @staticmethod
+    def _refuse_weights(i: int, c) -> None:
+        """A member under the plant-weighted risk measure (`set_weights`) has no place in the launch (`_check_member`: at admission and again in front of every plan step)."""
+        if c.weights is not None:
+            raise ValueError(f"fleet member {i} has plant weights set (set_weights): the fleet launch carries one `worst` per controller, and B x M weights do not fit in "
+                             "its kernel arguments.  set_weights(None) returns the member to the `worst` measure; a weighted controller plans on its own")
 
     def _launch(self, step: _LaunchStep) -> None:
         self._launch_ensemble(_lib.lib().jh_plan_step_ensemble_batch, step)

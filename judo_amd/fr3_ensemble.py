@@ -52,6 +52,7 @@ class FR3EnsembleController(EnsembleController):
 
     _fr3_ensemble = True
     _entry = "jh_plan_step_ensemble_phase"
+    _weighted_entry = "jh_plan_step_ensemble_weighted_phase"
 
     def _check_task(self, task: Task) -> None:
         check_task(task, fr3=True)  # (every line but fr3_pick's)

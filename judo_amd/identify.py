@@ -324,8 +324,8 @@ class PlantEstimator:
     def apply(self, ctrl, floor: float = 0.25) -> np.ndarray:
         """A randomised controller's next assignment from the posterior: `ctrl.set_weights((1 - floor) * posterior + floor / M)`, returned.  With `floor` > 0 every plant
         keeps a remainder in the apportionment (`plants.blocks_from_weights`), so evidence against the current belief can still arrive.  `ctrl` is a controller with an
-        `Assignment`: `RandomizedController`, `MaterializedRandomizedController` and their fr3 forms.  An ensemble controller is refused: a plant-weighted risk measure
-        does not exist; follow the belief there with `ctrl.set_member` on the MAP plant's neighbours, or by pruning the set."""
+        `Assignment`: `RandomizedController`, `MaterializedRandomizedController` and their fr3 forms.  An ensemble controller is refused here: it has no assignment; `apply_risk`
+        hands it the posterior as the weights of its plant-weighted risk measure."""
         if not 0 <= floor <= 1:
             raise ValueError(f"floor = {floor} outside [0, 1]")
         if isinstance(ctrl, WorstCase):
@@ -336,6 +336,22 @@ class PlantEstimator:
                              f"MaterializedRandomizedController or one of their fr3 forms")
         w = (1.0 - float(floor)) * self.posterior + float(floor) / self.num_plants
         ctrl.set_weights(w)
+        return w
+
+    def apply_risk(self, ctrl, floor: float = 0.0, tail: float | None = None) -> np.ndarray:
+        """An ensemble controller's plant-weighted risk measure from the posterior: `ctrl.set_weights((1 - floor) * posterior + floor / M, tail)`, the weights returned.
+        From the next plan step on a candidate's cost is the tail mean of its member costs under these weights (`plants.WorstCase.set_weights`), so a plant the
+        observed steps have ruled out no longer drives the plan.  `floor` > 0 keeps every plant at a positive weight; `tail` None keeps the controller's tail mass.
+        `ctrl` is a controller with a `WorstCase`: `EnsembleController`, `MaterializedEnsembleController`, their fr3 forms and `SpotEnsembleController`; a randomised
+        controller follows the belief with `apply`."""
+        if not 0 <= floor <= 1:
+            raise ValueError(f"floor = {floor} outside [0, 1]")
+        if not isinstance(ctrl, WorstCase):
+            raise ValueError(f"ctrl is a {type(ctrl).__name__}, which has no risk measure over its plants: apply_risk needs an EnsembleController, a "
+                             f"MaterializedEnsembleController, one of their fr3 forms or a SpotEnsembleController"
+                             + ("; a randomised controller follows the belief with apply" if isinstance(ctrl, Assignment) else ""))
+        w = (1.0 - float(floor)) * self.posterior + float(floor) / self.num_plants
+        ctrl.set_weights(w, tail)
         return w
 
 

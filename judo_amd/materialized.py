@@ -22,7 +22,6 @@ from typing import Sequence
 
 import torch
 
-from judo_amd import _lib
 from judo_amd.config import ControllerConfig
 from judo_amd.controller import Controller
 from judo_amd.plants import Assignment, GpuPlantSet, WorstCase, make_for, spline_controls
@@ -106,7 +105,7 @@ class MaterializedEnsembleController(WorstCase, _MaterializedPlantController):
             self._score_rollout(states[m * N : (m + 1) * N], sensors[m * N : (m + 1) * N], controls, out=rows[m])
         self.last_rollout = (states[:N], sensors[:N], controls)  # member 0, the nominal plant
         costs = torch.empty(N, dtype=torch.float32, device=self.device)
-        _lib.check(_lib.lib().jh_ensemble_costs(_lib.ptr(rows), M, N, N, self._worst, _lib.ptr(costs), st.stream), "jh_ensemble_costs")
+        self._aggregate(rows, M, N, costs, st.stream)  # (`jh_ensemble_costs`, or its weighted form while plant weights are set)
         return costs
 
 

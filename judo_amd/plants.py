@@ -4,7 +4,7 @@ The classes of judo_amd/ensemble.py, randomized.py, materialized.py and spot_pla
 
   `PlantSet`             the M descriptions, member 0 as the nominal plant, `set_member`; `GpuPlantSet` is the one over a `GpuModelSet` (`jh_model_set_create`),
                          `spot_plants._SpotPlantController` supplies the one over a `SpotPlantSet`.
-  `WorstCase`            the risk measure of the ensemble controllers: `worst`, `member_costs`, `member_rewards`, the (M, N) buffer.
+  `WorstCase`            the risk measure of the ensemble controllers: `worst`, `member_costs`, `member_rewards`, the (M, N) buffer; `set_weights`, `weights`, `tail`: the plant-weighted one.
   `Assignment`           the table from rollout block to plant of the randomised controllers: `blocks`, `assignment`, `set_weights`, `plant_of_rollout`, `plant_rewards`.
   `FusedPlantController` the one-call plan step of `EnsembleController` and `RandomizedController` (`jh_plan_step_ensemble`, `jh_plan_step_randomized` and their `_phase`
                          forms: one launcher in the library, judo_amd/csrc/jh_api.hip plan_step_set), with its refusals.
@@ -185,12 +185,70 @@ class GpuPlantSet(PlantSet):
 # ---- the two kinds -----------------------------------------------------------------------------------------------------------------------------------------------
 class WorstCase:
     """The risk measure of a controller that rolls every candidate out on all M plants: a candidate's cost is the mean of the `worst` largest of its M member costs
-    (`jh_plan_step_ensemble`'s tail or `jh_ensemble_costs`; `ensemble.aggregate_costs_host` restates it)."""
+    (`jh_plan_step_ensemble`'s tail or `jh_ensemble_costs`; `ensemble.aggregate_costs_host` restates it).  With `set_weights` it becomes the plant-weighted one, the
+    tail mean of the M member costs under a probability vector (`jh_plan_step_ensemble_weighted`'s tail or `jh_ensemble_costs_weighted`;
+    `ensemble.aggregate_costs_weighted_host` restates it): the weights and the tail mass travel in the kernel arguments, so new ones for the next plan step cost no
+    copy and no launch."""
+
+    _risk_weights = None  # the (JH_MAX_ENSEMBLE,) ctypes floats of the weighted measure (the first M are the weights), or None: the `worst` measure
+    _risk_tail: float | None = None  # the tail mass, once set; before that `worst / M`
 
     def _init_worst(self, worst: int | None, M: int) -> None:
         self._worst, self._member_costs = M, None
+        self._risk_weights, self._risk_tail = None, None
         if worst is not None:
             self._worst = self._checked_worst(worst, M)
+
+    def set_weights(self, weights: Sequence[float] | None, tail: float | None = None, **assignment) -> None:
+        """The plant-weighted risk measure from the next plan step on: a candidate's cost is the tail mean of its M member costs under `weights` with the tail mass
+        `tail`.  `weights`: M non-negative, finite numbers with a positive sum; they are normalised in fp64 and rounded to fp32.  `tail`: in (0, 1]; None keeps the
+        current one, which is `worst / M` before any was set -- uniform weights then mean what `worst` meant.  `set_weights(None)` returns to the `worst` measure (the
+        tail is kept).  Validated here; raises ValueError and changes nothing.  (No controller is both a `WorstCase` and an `Assignment`; a class assembled from both
+        pieces keeps `set_weights` for its assignment, with that method's keywords.)"""
+        if isinstance(self, Assignment):
+            return Assignment.set_weights(self, weights, **({} if tail is None else {"tail": tail}), **assignment)
+        if assignment:
+            raise TypeError(f"set_weights() got an unexpected keyword argument {next(iter(assignment))!r}")
+        M = len(self._descriptions)
+        if tail is not None:
+            t = float(np.float32(tail))
+            if not 0 < t <= 1:  # (false for NaN)
+                raise ValueError(f"tail = {tail} outside (0, 1]")
+        if weights is None:
+            self._risk_weights = None
+        else:
+            w = np.asarray(weights, dtype=np.float64).reshape(-1)
+            if w.size != M:
+                raise ValueError(f"{w.size} weights for M = {M} plants")
+            if not np.isfinite(w).all() or (w < 0).any() or not w.sum() > 0 or not np.isfinite(w.sum()):
+                raise ValueError(f"weights must be non-negative, finite numbers with a positive sum, got {list(w)}")
+            p = (w / w.sum()).astype(np.float32)
+            if not (p > 0).any():
+                raise ValueError(f"weights must be non-negative, finite numbers with a positive sum, got {list(w)}")
+            self._risk_weights = (C.c_float * MAX_ENSEMBLE)(*p.tolist())
+        if tail is not None:
+            self._risk_tail = t
+
+    @property
+    def weights(self) -> np.ndarray | None:
+        """None under the `worst` measure; else a copy of the M fp32 weights of the plant-weighted one."""
+        if self._risk_weights is None:
+            return None
+        return np.array(self._risk_weights[: len(self._descriptions)], dtype=np.float32)
+
+    @property
+    def tail(self) -> float:
+        """The tail mass of the plant-weighted measure: what `set_weights` set last, `worst / M` before that."""
+        if self._risk_tail is not None:
+            return self._risk_tail
+        return float(np.float32(self._worst) / np.float32(len(self._descriptions)))
+
+    def _aggregate(self, rows: torch.Tensor, M: int, N: int, costs: torch.Tensor, stream) -> None:
+        """The aggregation alone on the (M, N) member costs of a materialise path: `jh_ensemble_costs_weighted` while weights are set, else `jh_ensemble_costs`."""
+        if self._risk_weights is not None:
+            _lib.check(_lib.lib().jh_ensemble_costs_weighted(_lib.ptr(rows), M, N, N, self._risk_weights, self.tail, _lib.ptr(costs), stream), "jh_ensemble_costs_weighted")
+        else:
+            _lib.check(_lib.lib().jh_ensemble_costs(_lib.ptr(rows), M, N, N, self._worst, _lib.ptr(costs), stream), "jh_ensemble_costs")
 
     @staticmethod
     def _checked_worst(j: int, M: int) -> int:
@@ -322,6 +380,10 @@ class FusedPlantController(GpuPlantSet):
     def _after_call(self, kind_args: tuple) -> None:
         pass
 
+    def _entry_name(self) -> str:
+        """The library call of this plan step: `_entry`, unless a subclass's state picks another form of it."""
+        return self._entry
+
     def _plan_step(self, plan: _Plan, b: _PlanBuffers, st: _IterState, shape: str) -> int:
         """Shape "plan_step" on the set: one upload (or the host block read in place), the batched rollout kernel with the plants on its second grid dimension, the
         update's tail, one completion mark.  No trace buffer: the trace elites' knots are staged and re-rolled on member 0 when the traces are read."""
@@ -334,10 +396,11 @@ class FusedPlantController(GpuPlantSet):
         off = b.offsets
         in_place = b.blk_stale = self.model.closed_form
         mark = b.done_ptr if self.model.closed_form else b.out_host_ptr
-        rc = getattr(_lib.lib(), self._entry)(self.model_set.handle, b.host_ptr if in_place else b.blk.data_ptr(), b.host_ptr, b.nblk_bytes, int(off[1]), int(off[2]), int(off[3]),
+        entry = self._entry_name()
+        rc = getattr(_lib.lib(), entry)(self.model_set.handle, b.host_ptr if in_place else b.blk.data_ptr(), b.host_ptr, b.nblk_bytes, int(off[1]), int(off[2]), int(off[3]),
                                               int(off[4]), st.noise_p, st.ldn, *self._entry_args(plan, b), *kind_args, mode, lam, k_el, tie, _lib.ptr(b.fused_scratch), b.out_host_ptr,
                                               mark, timing, st.stream)
-        _lib.check(rc, self._entry)
+        _lib.check(rc, entry)
         self._after_call(kind_args)
         st.costs = b.costs
         if evs:
