@@ -19,94 +19,7 @@ void jh_set_error(const char* fmt, ...) {
 extern "C" const char* jh_last_error(void) { return g_err; }
 extern "C" int jh_version(void) { return 100; }
 
-// Cylinder geoms of an articulated image (type code 5 in the kernel's geom table, header I[5] records behind the bodies, blocks and actuators): their number, or -1 with
-// the error set when a record is malformed.  Only the leap family has a kernel that collides them (jh_engine_v5_cyl.hip); jh_model_create refuses them elsewhere.
-static int image_cylinders(const jh_blob_header& h, const float* F, const int* I) {
-  constexpr int HEADER = 24, BODY_I = 6, BODY_F = 32, BLOCK_I = 4, DOF_F = 20, ACT_I = 2, ACT_F = 8, GEOM_I = 2, GEOM_F = 20, GF_RBOUND = 15;
-  if (h.nint < (uint32_t)HEADER || h.nfloat < (uint32_t)HEADER) return 0;  // (not an engine image: the launchers refuse it)
-  const long NM = I[0], NBLK = I[1], nv = I[2], nu = I[4], NG = I[5];
-  if (NM < 0 || NBLK < 0 || nv < 0 || nu < 0 || NG < 0) return 0;
-  const long oI = HEADER + NM * BODY_I + NBLK * BLOCK_I + nu * ACT_I, oF = HEADER + NM * BODY_F + nv * DOF_F + nu * ACT_F;
-  if (oI + NG * GEOM_I > (long)h.nint || oF + NG * GEOM_F > (long)h.nfloat) return 0;
-  int n = 0;
-  for (long g = 0; g < NG; g++) {
-    if (I[oI + g * GEOM_I + 1] != 5) continue;
-    const float* f = F + oF + g * GEOM_F;
-    const float r = f[0], L = f[1], rb = f[GF_RBOUND], want = sqrtf(r * r + L * L);
-    if (!(r > 0.f) || !(L > 0.f) || f[2] != 0.f) { jh_set_error("model_create: cylinder geom %ld: sizes must be (radius > 0, half length > 0, 0), got (%g, %g, %g)", g, r, L, f[2]); return -1; }
-    if (!(fabsf(rb - want) <= 1e-5f * want)) { jh_set_error("model_create: cylinder geom %ld: bounding radius %g is not sqrt(r^2 + L^2) = %g", g, rb, want); return -1; }
-    n++;
-  }
-  return n;
-}
-
-// Arm pairs of an fr3_pick image (the generic section behind header I[13]: geom records, then the candidate pairs): the pairs between two moving bodies of the arm (body
-// codes >= 1) other than finger against finger (bodies 8 and 9), plus those of a box or a capsule on the arm against a capsule of the static geometry (the fr3_link0 stand-in) -- what the
-// default build of k_fr3_v6 leaves out and its self-collision build (jh_engine_v6_self.hip) collides.  -1 with the error set when a pair record is malformed.
-static int image_arm_pairs(const jh_blob_header& h, const int* I) {
-  constexpr int HEADER = 24, GEOM_I = 2, GBOX = 6, GCAPSULE = 3, LF = 8, RF = 9;
-  if (h.nint < (uint32_t)HEADER) return 0;  // (not an engine image: the launchers refuse it)
-  const long gi = I[13];
-  if (gi < HEADER || gi + 8 > (long)h.nint) return 0;
-  const long nag = I[gi], npair = I[gi + 1];
-  if (nag < 0 || npair < 0 || gi + 8 + nag * GEOM_I + npair * 2 > (long)h.nint) return 0;
-  int n = 0;
-  for (long p = 0; p < npair; p++) {
-    const long g1 = I[gi + 8 + nag * GEOM_I + 2 * p], g2 = I[gi + 8 + nag * GEOM_I + 2 * p + 1];
-    if (g1 < 0 || g1 >= nag || g2 < 0 || g2 >= nag || g1 == g2) { jh_set_error("model_create: candidate pair %ld names geoms (%ld, %ld) of %ld", p, g1, g2, nag); return -1; }
-    const int b1 = I[gi + 8 + g1 * GEOM_I], t1 = I[gi + 8 + g1 * GEOM_I + 1], b2 = I[gi + 8 + g2 * GEOM_I], t2 = I[gi + 8 + g2 * GEOM_I + 1];
-    const bool arm_arm = b1 >= 1 && b2 >= 1 && !((b1 == LF && b2 == RF) || (b1 == RF && b2 == LF));
-    const bool arm_capsule = t1 == GCAPSULE || (t1 == GBOX && t2 == GCAPSULE && b1 >= 1);  // (a capsule of the arm or of the static base against the arm)
-    if (!arm_arm && !arm_capsule) continue;
-    if (b1 == b2) { jh_set_error("model_create: candidate pair %ld collides two geoms of arm body %d with each other", p, b1); return -1; }
-    if (t1 == GCAPSULE && t2 != GCAPSULE) { jh_set_error("model_create: candidate pair %ld between arm bodies has its capsule first; the kernel takes (box, capsule)", p); return -1; }
-    n++;
-  }
-  return n;
-}
-
-// The pair tables of a leap image (the hand's broad phase, jh_engine_v5.hip): header I[19] is the offset of [count, PT_MAX records of PT_I ints] behind everything else
-// in the int section, 0 in an image without them.  Ints of the block (0: none), or -1 with the error set when it is malformed: the kernel indexes lanes and
-// pair bits with what the records hold.
-static int image_pair_tables(const jh_blob_header& h, const int* I) {
-  constexpr int HEADER = 24, PT_SLOT = JH_PT_SLOT, PT_MAX = JH_PT_MAX, PT_I = JH_PT_I, LANES = 16;
-  if (h.nint < (uint32_t)HEADER || I[PT_SLOT] == 0) return 0;
-  const long o = I[PT_SLOT], len = JH_PT_LEN, nbp = I[17];
-  if (o < HEADER || o + len > (long)h.nint) { jh_set_error("model_create: the pair tables at int %ld (%ld ints) lie outside the int section of %u", o, len, h.nint); return -1; }
-  const int n = I[o];
-  if (n < 0 || n > PT_MAX) { jh_set_error("model_create: %d pair tables, at most %d", n, PT_MAX); return -1; }
-  for (int t = 0; t < PT_MAX; t++) {
-    const int* T = I + o + 1 + t * PT_I;
-    if (t >= n) { for (int k = 0; k < PT_I; k++) if (T[k] != 0) { jh_set_error("model_create: pair table %d is beyond the count of %d and not zero", t, n); return -1; } continue; }
-    float f[4]; memcpy(f, T + 3, sizeof(f));
-    if (T[0] < 0 || T[0] >= nbp || (t > 0 && T[0] <= T[-PT_I])) { jh_set_error("model_create: pair table %d names body pair %d of %ld (ascending, each once)", t, T[0], nbp); return -1; }
-    if (T[1] < 0 || T[1] >= LANES || T[2] < 0 || T[2] >= LANES) { jh_set_error("model_create: pair table %d names joints (%d, %d) of %d", t, T[1], T[2], LANES); return -1; }
-    if (!std::isfinite(f[0]) || !std::isfinite(f[2]) || !std::isfinite(f[1]) || !std::isfinite(f[3]) || !(f[1] > 0.f) || !(f[3] >= 0.f)) {
-      jh_set_error("model_create: pair table %d: grid origins (%g, %g) and inverse cell widths (%g, %g) must be finite, the first width positive", t, f[0], f[2], f[1], f[3]);
-      return -1;
-    }
-  }
-  return (int)len;
-}
-
-// May two images of one model set share the pair tables in the set's int section?  Only if the tables are the same words and everything they were computed from is:
-// the hand bodies' frames and joint axes, the joint ranges, every hand geom's size and pose, the bodies' bounding volumes.  (The cube, masses, gains and friction
-// are free to differ.)  Images without tables share "none".
-static bool pair_tables_shared(const std::vector<float>& F0, const std::vector<int>& I0, const std::vector<float>& F, const std::vector<int>& I) {
-  constexpr int HEADER = 24, PT_SLOT = JH_PT_SLOT, BODY_F = 32, DOF_F = 20, ACT_F = 8, GEOM_F = 20, NBC = 20;
-  if (I0.size() <= (size_t)PT_SLOT || I.size() != I0.size() || F.size() != F0.size() || I[PT_SLOT] != I0[PT_SLOT]) return false;
-  const long o = I0[PT_SLOT], len = JH_PT_LEN;
-  if (o == 0) return true;
-  if (o < HEADER || o + len > (long)I0.size() || memcmp(&I[o], &I0[o], 4 * len) != 0) return false;
-  const long NM = I0[0], nv = I0[2], nu = I0[4], NG = I0[5], oBS = I0[16];
-  const long oDof = HEADER + NM * BODY_F, oGeom = oDof + nv * DOF_F + nu * ACT_F;
-  if (NM < 1 || nv < 6 || nu < 0 || NG < 0 || oGeom + NG * GEOM_F > (long)F0.size() || oBS < 0 || oBS + NBC * 8 > (long)F0.size()) return false;
-  auto same = [&](long at, long n) { return memcmp(&F[at], &F0[at], 4 * n) == 0; };
-  for (long b = 1; b < NM; b++) if (!same(HEADER + b * BODY_F, 12) || !same(HEADER + b * BODY_F + 28, 3)) return false;  // frame in the parent (position, rotation), joint axis
-  for (long d = 6; d < nv; d++) if (!same(oDof + d * DOF_F + 6, 3)) return false;                                      // limited, range
-  for (long g = 0; g < NG; g++) if (!same(oGeom + g * GEOM_F, 16)) return false;                                       // size, position, rotation, bounding radius
-  return same(oBS, NBC * 8);                                                                                            // bounding sphere and box per hand body
-}
+using jh_eng::HI_PT;
 
 static bool blob_sections(const void* blob, size_t nbytes, std::vector<float>& F, std::vector<int>& I) {
   jh_blob_header h;
@@ -123,7 +36,9 @@ static bool blob_sections(const void* blob, size_t nbytes, std::vector<float>& F
 extern "C" int jh_pair_tables_shared(const void* blob0, size_t nbytes0, const void* blob, size_t nbytes) {
   std::vector<float> F0, F; std::vector<int> I0, I;
   JH_REQUIRE(blob_sections(blob0, nbytes0, F0, I0) && blob_sections(blob, nbytes, F, I), "pair_tables_shared: not a model blob");
-  return pair_tables_shared(F0, I0, F, I) ? 1 : 0;
+  jh_eng::HostImage a, b;
+  a.bind(F0.data(), I0.data(), F0.size(), I0.size()); b.bind(F.data(), I.data(), F.size(), I.size());
+  return jh_eng::pair_tables_shared(a, b) ? 1 : 0;
 }
 
 extern "C" int jh_model_create(const void* blob, size_t nbytes, int device, jh_model** out) {
@@ -138,17 +53,23 @@ extern "C" int jh_model_create(const void* blob, size_t nbytes, int device, jh_m
   if (h.kind == JH_TASK_CARTPOLE && h.nfloat < CP_NPARAM) { jh_set_error("model_create: cartpole blob has %u floats, need %d", h.nfloat, CP_NPARAM); return JH_ERR_BLOB; }
   if (h.kind == JH_TASK_CYLINDER_PUSH && h.nfloat < CY_NPARAM) { jh_set_error("model_create: cylinder blob has %u floats, need %d", h.nfloat, CY_NPARAM); return JH_ERR_BLOB; }
   if (h.ntaskparam > JH_MAX_TASK_PARAMS) { jh_set_error("model_create: too many task params"); return JH_ERR_BLOB; }
+  const char* p = (const char*)blob + sizeof(h);
+  std::vector<float> F((const float*)p, (const float*)p + h.nfloat);  // (copies: the blob need not be aligned; the model keeps them)
+  std::vector<int> I((const int*)(p + 4 * (size_t)h.nfloat), (const int*)(p + 4 * (size_t)h.nfloat) + h.nint);
+  // The articulated kinds: the view of the image and whether it fits, once, for the readers here and for every launch's acceptance test.  An image that does not fit is
+  // still a model (not an engine image: the launchers refuse it).
+  jh_eng::HostImage image;
   int cylinders = 0, arm_pairs = 0;
   if (h.kind == JH_TASK_LEAP_CUBE || h.kind == JH_TASK_FR3_PICK) {
-    const char* q = (const char*)blob + sizeof(h);
-    std::vector<float> F((const float*)q, (const float*)q + h.nfloat);  // (copies: the blob need not be aligned)
-    std::vector<int> I((const int*)(q + 4 * (size_t)h.nfloat), (const int*)(q + 4 * (size_t)h.nfloat) + h.nint);
-    cylinders = image_cylinders(h, F.data(), I.data());
+    image.bind(F.data(), I.data(), F.size(), I.size());
+    const jh_eng::EngineModel& v = image.v;
+    image.fits = image.fits && v.NQ == (int)h.nq && v.NV == (int)h.nv && v.NU == (int)h.nu && v.NS == (int)h.ns;  // (the kernels size their loops by the image's counts, the launchers their buffers by the blob header's)
+    cylinders = jh_eng::image_cylinders(image);
     if (cylinders < 0) return JH_ERR_BLOB;
-    if (h.kind == JH_TASK_LEAP_CUBE && image_pair_tables(h, I.data()) < 0) return JH_ERR_BLOB;
+    if (h.kind == JH_TASK_LEAP_CUBE && jh_eng::image_pair_tables(image) < 0) return JH_ERR_BLOB;
     if (cylinders > 0 && h.kind != JH_TASK_LEAP_CUBE) { jh_set_error("model_create: %d cylinder geoms, and only the leap kernel has a cylinder build", cylinders); return JH_ERR_BLOB; }
     if (h.kind == JH_TASK_FR3_PICK) {
-      arm_pairs = image_arm_pairs(h, I.data());
+      arm_pairs = jh_eng::image_arm_pairs(image);
       if (arm_pairs < 0) return JH_ERR_BLOB;
     }
   }
@@ -164,9 +85,7 @@ extern "C" int jh_model_create(const void* blob, size_t nbytes, int device, jh_m
     if (ok && n > 0) { for (int i = 0; i < n; i++) m->rollout_bounds[i] = b[i]; m->rollout_nbounds = n; m->rollout_slices = 0; }
   }
   { const char* e = getenv("JUDO_AMD_PLAN_STEP_LAUNCHES"); m->plan_step_launches = (e && e[0] == '2') ? 2 : 0; }  // (the environment sets the default; jh_model_set_plan_step_launches changes it per model)
-  const char* p = (const char*)blob + sizeof(h);
-  m->h_f.assign((const float*)p, (const float*)p + h.nfloat);
-  m->h_i.assign((const int*)(p + 4 * (size_t)h.nfloat), (const int*)(p + 4 * (size_t)h.nfloat) + h.nint);
+  m->h_f = std::move(F); m->h_i = std::move(I); m->image = image;  // (a moved vector keeps its storage: the view's pointers hold)
   {  // the cooperative kernels take a per-launch scratch block from the device's stream-ordered pool (contacts above the LDS pool): let the pool keep what it is
      // handed back instead of returning it to the driver at every synchronisation (the default release threshold is 0: 0.2 ms per launch)
     hipMemPool_t pool = nullptr; int dev = 0;
@@ -735,10 +654,9 @@ struct jh_model_set {
 
 // The int sections of two members of a set agree but for the pair tables' block, which `pair_tables_shared` weighs: the word where they differ, or -1.
 static long int_sections_differ(const std::vector<int>& a, const std::vector<int>& b) {
-  constexpr long PT_SLOT = JH_PT_SLOT, PT_LEN = JH_PT_LEN;
   if (a.size() != b.size()) return 0;
-  const long o = a.size() > (size_t)PT_SLOT && a[PT_SLOT] == b[PT_SLOT] && a[PT_SLOT] > 0 ? a[PT_SLOT] : -1;
-  for (long w = 0; w < (long)a.size(); w++) if (a[w] != b[w] && !(o >= 0 && w >= o && w < o + PT_LEN)) return w;
+  const long o = a.size() > (size_t)HI_PT && a[HI_PT] == b[HI_PT] && a[HI_PT] > 0 ? a[HI_PT] : -1;
+  for (long w = 0; w < (long)a.size(); w++) if (a[w] != b[w] && !(o >= 0 && w >= o && w < o + JH_PT_LEN)) return w;
   return -1;
 }
 
@@ -746,10 +664,16 @@ static long int_sections_differ(const std::vector<int>& a, const std::vector<int
 static int model_set_tables(jh_model_set* s, bool member0_changed) {
   s->tables = true;
   if (s->m0->kind == JH_TASK_FR3_PICK) return JH_OK;  // (no pair tables: the members' int sections are member 0's word for word, and the launch reads m0->d_i)
-  for (int b = 1; b < s->B && s->tables; b++) s->tables = pair_tables_shared(s->hf[0], s->hi[0], s->hf[b], s->hi[b]);
+  jh_eng::HostImage lead;
+  lead.bind(s->hf[0].data(), s->hi[0].data(), s->hf[0].size(), s->hi[0].size());
+  for (int b = 1; b < s->B && s->tables; b++) {
+    jh_eng::HostImage member;
+    member.bind(s->hf[b].data(), s->hi[b].data(), s->hf[b].size(), s->hi[b].size());
+    s->tables = jh_eng::pair_tables_shared(lead, member);
+  }
   if (!member0_changed) return JH_OK;  // (the int section without tables is member 0's: uploaded when the set is made and when member 0 is replaced)
   std::vector<int> plain = s->hi[0];
-  if (plain.size() > (size_t)JH_PT_SLOT) plain[JH_PT_SLOT] = 0;
+  if (plain.size() > (size_t)HI_PT) plain[HI_PT] = 0;
   if (!plain.empty()) JH_HIP(hipMemcpy(s->d_i_plain, plain.data(), 4 * plain.size(), hipMemcpyHostToDevice));
   return JH_OK;
 }
@@ -861,7 +785,7 @@ extern "C" void jh_model_set_destroy(jh_model_set* s) {
 
 extern "C" int jh_model_set_pair_tables(const jh_model_set* s) {
   JH_REQUIRE(s != nullptr, "model_set_pair_tables: null pointer");
-  return s->tables && s->hi[0].size() > (size_t)JH_PT_SLOT && s->hi[0][JH_PT_SLOT] > 0 ? 1 : 0;
+  return s->tables && s->hi[0].size() > (size_t)HI_PT && s->hi[0][HI_PT] > 0 ? 1 : 0;
 }
 
 extern "C" int jh_plan_step_batch_models(const jh_model_set* set, void* blk_dev, const void* blk_host, size_t blk_bytes, size_t blk_stride_bytes, int o_nominal, int o_sigma, int o_tp, int o_lohi,

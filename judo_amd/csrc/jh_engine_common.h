@@ -1,52 +1,10 @@
-// jh_engine_common.h -- device helpers shared by the articulated-body kernels (gfx950): model-image layout (mirrors
-// judo_amd/engine_model.py), small vector algebra, MuJoCo's impedance curve and contact-frame convention, the
+// jh_engine_common.h -- device helpers shared by the articulated-body kernels (gfx950): the model image's layout and view (jh_image.h), small vector algebra, MuJoCo's impedance curve and contact-frame convention, the
 // elliptic-cone cost/force/Hessian of one contact, and the leap_cube running cost.
 #pragma once
+#include "jh_image.h"
 #include "jh_internal.h"
 
 namespace jh_eng {
-
-constexpr int JFREE = 0, JSLIDE = 2, JHINGE = 3;
-constexpr int GBOX = 6, GSPHERE = 2, GCAPSULE = 3;
-constexpr int HEADER_I = 24, HEADER_F = 24;
-constexpr int BODY_I = 6, GEOM_I = 2, ACT_I = 2, BLOCK_I = 4, SENS_I = 3;
-constexpr int BODY_F = 32, DOF_F = 20, ACT_F = 8, GEOM_F = 20, SITE_F = 3;
-constexpr int EQ_I = 5, EQ_F = 12, FRAME_F = 12, GP_F = 8;  // GP: solref[2], solimp[5], pad
-enum { EF_A0 = 0, EF_A1, EF_K, EF_B, EF_SOLIMP, EF_INVW = 9 };
-// header floats
-enum { HF_DT = 0, HF_IMPRATIO = 1, HF_TOL = 2, HF_MAXITER = 22, HF_LSTOL = 23, HF_GRAV = 3, HF_CK = 6, HF_CB = 7, HF_SOLIMP = 8, HF_CMASS = 13, HF_CINERTIA = 14, HF_CSIZE = 17, HF_CRBOUND = 20, HF_CTRAN = 21 };
-// body floats
-enum { BF_LPOS = 0, BF_LR = 3, BF_MASS = 12, BF_IPOS = 13, BF_IR = 16, BF_INERTIA = 25, BF_AXIS = 28, BF_TRAN = 31 };
-// dof floats
-enum { DF_DAMP = 0, DF_ARM, DF_FL, DF_FB, DF_FD, DF_INVW, DF_LIMITED, DF_LO, DF_HI, DF_LK, DF_LB, DF_SOLIMP, DF_FRCLIM = 16, DF_FRCLO, DF_FRCHI, DF_KV };
-// actuator floats
-enum { AF_KP = 0, AF_KV, AF_CLIM, AF_CLO, AF_CHI };
-// geom floats
-enum { GF_SIZE = 0, GF_POS = 3, GF_R = 6, GF_RBOUND = 15, GF_MU = 16 /* max(own, cube's) */, GF_TRAN = 17, GF_MUOWN = 18 };
-
-struct EngineModel {  // views into the LDS copy of the blob
-  const float* F;
-  const int* I;
-  int NM, NBLK, NV, NQ, NU, NG, NSITE, NS, NSENS;
-  int oBodyI, oBlockI, oActI, oGeomI, oSiteI, oSensI;
-  int oBodyF, oDofF, oActF, oGeomF, oSiteF;
-  // generic sections (reference kernel): all geoms incl. the cube, explicit pairs, equalities, frames, distance sensors
-  int NAG, NPAIR, NEQ, NFRAME, NDIST, NGS, cone;
-  int oAGI, oPairI, oEqI, oFrameI, oDistI, oSensG, oGlist, oAGF, oGPF, oEqF, oFrameF, oDistF;
-  __device__ void init(const float* f, const int* i) {
-    F = f; I = i;
-    NM = i[0]; NBLK = i[1]; NV = i[2]; NQ = i[3]; NU = i[4]; NG = i[5]; NSITE = i[6]; NS = i[7]; NSENS = i[10];
-    oBodyI = HEADER_I; oBlockI = oBodyI + NM * BODY_I; oActI = oBlockI + NBLK * BLOCK_I; oGeomI = oActI + NU * ACT_I;
-    oSiteI = oGeomI + NG * GEOM_I; oSensI = oSiteI + NSITE;
-    oBodyF = HEADER_F; oDofF = oBodyF + NM * BODY_F; oActF = oDofF + NV * DOF_F; oGeomF = oActF + NU * ACT_F; oSiteF = oGeomF + NG * GEOM_F;
-    cone = i[9];
-    const int gi = i[13], gf = i[14];
-    NAG = i[gi]; NPAIR = i[gi + 1]; NEQ = i[gi + 2]; NFRAME = i[gi + 3]; NDIST = i[gi + 4]; NGS = i[gi + 5];
-    oAGI = gi + 8; oPairI = oAGI + NAG * GEOM_I; oEqI = oPairI + NPAIR * 2; oFrameI = oEqI + NEQ * EQ_I; oDistI = oFrameI + NFRAME;
-    oSensG = oDistI + NDIST * 4; oGlist = oSensG + NGS * 4;
-    oAGF = gf; oGPF = oAGF + NAG * GEOM_F; oEqF = oGPF + NAG * GP_F; oFrameF = oEqF + NEQ * EQ_F; oDistF = oFrameF + NFRAME * FRAME_F;
-  }
-};
 
 template <int NM_, int NV_, int NQ_, int NU_, int NBLK_, int BD_, int NCON_, int NS_>
 struct Cfg {

@@ -130,11 +130,11 @@ constexpr int CUBE = 17;          // contact side codes: 0 = static geometry, 1.
 constexpr int HITPAIR = 1 << 15;  // broad-phase survivors >= HITPAIR are hand-hand geom pairs (ga << 7 | gb, geom ids < 128), smaller ones are cube-vs-geom
 static_assert(MAXG <= 128, "hand geom pairs are packed into 14 bits");
 constexpr int MAXBP = 128;         // hand body pairs in the model image (leap_cube 106, caltech_leap_cube 122)
-constexpr int PT_SLOT = JH_PT_SLOT, PT_MAX = JH_PT_MAX, PT_I = JH_PT_I;  // pair tables of the hand's broad phase: at most four, nine ints each (pair, the two joints' lanes, grid origins and inverse cell widths as float bits, the 64-bit word)
+constexpr int PT_MAX = JH_PT_MAX, PT_I = JH_PT_I;  // pair tables of the hand's broad phase: at most four, nine ints each (pair, the two joints' lanes, grid origins and inverse cell widths as float bits, the 64-bit word)
 constexpr int MAXBPL = 96;        // hand body pairs whose bounding volumes overlap, per rollout and step (one byte each: pair indices < MAXBP <= 256)
 constexpr int NDH = 22 * 23 / 2;  // dense Hessian (packed lower) of a rollout whose contacts couple two finger chains
 constexpr int NV = 22, NQ = 23, NU = 16, NS = 31, NS_CALTECH = 23, NX = 45, NMB = 17;
-constexpr int NBC = 20;  // hand bodies of the self-collision tables: 0 = static geometry, 1..16 = finger links, 17..19 = further groups of static geometry (engine_model.py)
+constexpr int NBC = BODY_CODES;  // hand bodies of the self-collision tables: 0 = static geometry, 1..16 = finger links, 17..19 = further groups of static geometry (engine_model.py)
 __device__ __forceinline__ bool static_code(int b) { return b == 0 || b >= NMB; }
 
 // per-lane model constants staged in LDS (index = lane & 15)
@@ -490,7 +490,7 @@ __global__ __launch_bounds__(WAVE * WPB, WAVES_PER_EU) void k_leap_v5(const floa
     gF += jh_plant_of(sb_.plants, (int)pb, (int)pb) * batch_image;
     x0 += pb * batch_noise; controls += pb * batch_blk;
     if (states) states += pb * N * H * NX;
-    if (sensors) sensors += pb * N * H * gI[7];
+    if (sensors) sensors += pb * N * H * gI[HI_NS];
     if (NOVF > 0 && ovf_all_) ovf_all_ += pb * N * (NOVF * POOL_F);
   }
   if constexpr (BATCH && !MATERIALIZE) {
@@ -526,11 +526,11 @@ __global__ __launch_bounds__(WAVE * WPB, WAVES_PER_EU) void k_leap_v5(const floa
   const int tid = threadIdx.x, wv = tid >> 6, lane = tid & 63, r = lane >> 4;
   int l = lane & 15, c = l >> 2, s = l & 3;  // (not const: see the top of the step loop)
   RS& S = sRS[wv * RPW + r];
-  const int nmI = gI[0], nblkI = gI[1], nuI = gI[4], ngI = gI[5], nsiteI = gI[6], nsI = gI[7], oRef = gI[18];
-  const int oBodyF = HEADER_F, oDofF = oBodyF + nmI * BODY_F, oActF = oDofF + gI[2] * DOF_F, oGeomF = oActF + nuI * ACT_F, oSiteF = oGeomF + ngI * GEOM_F;
+  const int nmI = gI[HI_NM], nblkI = gI[HI_NBLK], nuI = gI[HI_NU], ngI = gI[HI_NG], nsiteI = gI[HI_NSITE], nsI = gI[HI_NS], oRef = gI[HI_REF];
+  const int oBodyF = HEADER_F, oDofF = oBodyF + nmI * BODY_F, oActF = oDofF + gI[HI_NV] * DOF_F, oGeomF = oActF + nuI * ACT_F, oSiteF = oGeomF + ngI * GEOM_F;
   const int oGeomI = HEADER_I + nmI * BODY_I + nblkI * BLOCK_I + nuI * ACT_I, oSiteI = oGeomI + ngI * GEOM_I;
-  const int oLane = gI[11], lgm = gI[12];
-  const int oBP = gI[15], oBS = gI[16], nBP = gI[17], oBG = oBP + 2 * nBP;  // hand self-collision: body pairs, body bounding volumes, per-body geom ranges
+  const int oLane = gI[HI_LANES], lgm = gI[HI_LGM];
+  const int oBP = gI[HI_BP], oBS = gI[HI_BS], nBP = gI[HI_NBP], oBG = oBP + 2 * nBP;  // hand self-collision: body pairs, body bounding volumes, per-body geom ranges
   for (int i = tid; i < 16 * BODY_F; i += WAVE * WPB) sBody[(i / BODY_F) * BFS + i % BODY_F] = gF[oBodyF + BODY_F + i];
   for (int i = tid; i < ngI * GEOM_F; i += WAVE * WPB) sGeomF[i] = gF[oGeomF + i];
   for (int i = tid; i < ngI * GEOM_I; i += WAVE * WPB) sGeomI[i] = gI[oGeomI + i];
@@ -918,7 +918,7 @@ __global__ __launch_bounds__(WAVE * WPB, WAVES_PER_EU) void k_leap_v5(const floa
         // taken per row of 16 lanes (a wave's rollouts differ); an angle off the grid, or a NaN, reads as unsafe.  The records are wave-uniform: scalar loads.
         // The header slot is read here, in every step, through an index the compiler cannot see through: held across the step loop it costs a register the loop does not have.
         // Records beyond the image's count are zero and rule nothing out (a zero word), so the loop runs over all PT_MAX without reading the count.
-        int pt_slot = PT_SLOT; asm volatile("" : "+s"(pt_slot));
+        int pt_slot = HI_PT; asm volatile("" : "+s"(pt_slot));
         const int oPT = gI[pt_slot];  // (0: an image without tables)
 #pragma unroll 1
         for (int t = 0; oPT > 0 && t < PT_MAX; t++) {
@@ -1937,9 +1937,10 @@ __global__ __launch_bounds__(WAVE * WPB, WAVES_PER_EU) void k_leap_v5(const floa
 }
 
 bool model_is_leap(const jh_model* m) {
-  return m->kind == JH_TASK_LEAP_CUBE && m->nq == 23 && m->nv == 22 && m->nu == 16 && (m->ns == NS || (m->ns == NS_CALTECH && m->h_i.size() > 18 && m->h_i[18] > 0)) && m->h_i.size() > 17 &&
-         m->h_i[0] == 17 && m->h_i[1] == 4 && m->h_i[11] > 0 && m->h_i[5] <= MAXG && m->h_i[12] <= MAXLG && m->h_i[17] <= MAXBP
-         && m->h_f.size() > (size_t)HF_CINERTIA + 2 && m->h_f[HF_CINERTIA] == m->h_f[HF_CINERTIA + 1] && m->h_f[HF_CINERTIA] == m->h_f[HF_CINERTIA + 2]  // isotropic cube inertia: the solver works on the rotation in the world frame
+  const HostImage& im = m->image;
+  return im.fits && m->kind == JH_TASK_LEAP_CUBE && m->nq == 23 && m->nv == 22 && m->nu == 16 && (m->ns == NS || (m->ns == NS_CALTECH && im.oRef > 0)) &&
+         im.v.NM == 17 && im.v.NBLK == 4 && im.oLane > 0 && im.v.NG <= MAXG && im.LGM <= MAXLG && im.NBP <= MAXBP
+         && m->h_f[HF_CINERTIA] == m->h_f[HF_CINERTIA + 1] && m->h_f[HF_CINERTIA] == m->h_f[HF_CINERTIA + 2]  // isotropic cube inertia: the solver works on the rotation in the world frame
          ;
 }
 
@@ -1981,7 +1982,7 @@ void launch(const LeapArgs& k, dim3 grid, hipStream_t st) {
                      k.batch_blk, k.batch_noise, k.batch_image, k.pflags, k.slices, static_cast<const std::conditional_t<BATCH, BatchBounds, SliceBounds>&>(k.sb));
 }
 
-bool hand_contacts(const jh_model* m) { return m->self_collision && m->h_i[17] > 0; }  // the SELF instantiations: the hand's own contacts are on and the image has body pairs
+bool hand_contacts(const jh_model* m) { return m->self_collision && m->image.fits && m->image.NBP > 0; }  // the SELF instantiations: the hand's own contacts are on and the image has body pairs
 
 }  // namespace
 

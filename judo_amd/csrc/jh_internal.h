@@ -8,16 +8,13 @@
 #include <cstdio>
 #include <vector>
 
+#include "jh_image.h"  // (the articulated models' image: layout, view, host readers)
 #include "judo_amd.h"
 #include "judo_amd_xcheck.h"  // (the test-build hooks: the cross-check kernel generations register through them)
 
 #define JH_BLOB_MAGIC 0x314D484Au /* "JHM1" */
 #define JH_BLOB_VERSION 1u
 #define JH_NSTATS 512
-// The hand's pair tables in a leap image's int section (judo_amd/engine_model.py::hand_pair_tables, PT_*): header slot JH_PT_SLOT holds the offset of the block
-// [count, JH_PT_MAX records of JH_PT_I ints] (0: none).  One definition for jh_model_create's check, the model-set rule and the kernel.
-constexpr int JH_PT_SLOT = 19, JH_PT_MAX = 4, JH_PT_I = 9, JH_PT_LEN = 1 + JH_PT_MAX * JH_PT_I;
-
 // Host-side blob header produced by judo_amd/models.py::pack_model (little-endian, 64 bytes):
 struct jh_blob_header {
   uint32_t magic, version, kind, nq, nv, nu, ns, ntaskparam, nfloat, nint;
@@ -47,6 +44,7 @@ struct jh_model {
   int* d_stats;  // JH_NSTATS diagnostic counters: the JH_STAT_* words below; the rest: diagnostic builds
   std::vector<float> h_f;
   std::vector<int> h_i;
+  jh_eng::HostImage image;  // the articulated kinds: the view of h_f / h_i and whether it fits them and the blob header's dimensions (jh_model_create, once); the launchers' acceptance tests ask it first
 };
 
 void jh_set_error(const char* fmt, ...);

@@ -1,4 +1,4 @@
-"""Device model image for the articulated-body rollout engine (`judo_amd/csrc/jh_engine.hip`).
+"""Device model image for the articulated-body rollout engines (the leap and fr3 kernels, `judo_amd/csrc/jh_engine_v5.hip` and `jh_engine_v6.hip`).
 
 Structure the engine exploits (it holds for leap_cube and fr3_pick): ONE free body (the manipulated cube) plus
 articulated "blocks" (serial chains / small trees of hinge or slide joints) hanging off bodies that are welded to
@@ -9,12 +9,14 @@ the world.  Consequences used by the kernels:
   * every contact modelled this round is cube <-> hand geom, so a contact row touches the 6 cube DoF and at most
     one block: the Newton Hessian is an arrow matrix (cube block + per-chain blocks + cube-chain couplings).
 
-Layout of the float (F) and int (I) sections is mirrored by `struct EngineModel` in jh_engine.hip.
+The layout of the float (F) and int (I) sections is written down once, in `judo_amd/csrc/jh_image.h`: the table at its top, the constants and slot names that the ones
+below repeat (tests/test_image_layout.py holds the two sides to each other), and `struct EngineModel`, whose `init` is `image_offsets` here.
 """
 
 from __future__ import annotations
 
 import collections
+import types
 
 import numpy as np
 
@@ -37,10 +39,20 @@ GTYPE = {"box": GBOX, "sphere": GSPHERE, "capsule": GCAPSULE, "cylinder": GCYLIN
 MAX_MOVING, MAX_DOF, MAX_BLOCKS, MAX_BLOCK_DOF, MAX_GEOM, MAX_SITE = 20, 24, 4, 9, 80, 8
 
 # ints per record
-BODY_I, GEOM_I, ACT_I, BLOCK_I = 6, 2, 2, 4
+BODY_I, GEOM_I, ACT_I, BLOCK_I, SENS_I, EQ_I = 6, 2, 2, 4, 3, 5
 # floats per record
-BODY_F, DOF_F, ACT_F, GEOM_F, SITE_F = 32, 20, 8, 20, 3
+BODY_F, DOF_F, ACT_F, GEOM_F, SITE_F, EQ_F, FRAME_F, GP_F = 32, 20, 8, 20, 3, 12, 12, 8
 HEADER_I, HEADER_F = 24, 24
+LANES, BODY_CODES, BV_F, REF_F, GEN_I = 16, 20, 8, 16, 8  # lane lists; the hand's body codes and floats per bounding volume; reference frames; the generic block's counts
+# header ints (jh_image.h has the table): counts, integrator, cone; lane lists (offset, length of a list); generic block (ints, floats); body pairs, bounding
+# volumes, number of pairs; reference frames; pair tables; the two words of diagnostic builds
+(HI_NM, HI_NBLK, HI_NV, HI_NQ, HI_NU, HI_NG, HI_NSITE, HI_NS, HI_INTEG, HI_CONE, HI_NSENS, HI_LANES, HI_LGM, HI_GI, HI_GF, HI_BP, HI_BS, HI_NBP, HI_REF, HI_PT,
+ HI_ABLATE, HI_ABLATE_N) = range(22)
+GI_NAG, GI_NPAIR, GI_NEQ, GI_NFRAME, GI_NDIST, GI_NGS = range(6)  # the generic block's own counts
+BF_LPOS, BF_LR, BF_AXIS = 0, 3, 28  # body floats: frame in the parent (position, rotation), joint axis
+DF_LIMITED, DF_LO, DF_HI = 6, 7, 8  # dof floats: the joint's range
+GF_SIZE, GF_POS, GF_R, GF_RBOUND = 0, 3, 6, 15  # geom floats
+
 # Newton termination on the GPU: |grad|_Minv <= tol * |qfrc_smooth|_Minv (or the expected decrease of a step falls below
 # tol^2 of the same scale), at most SOLVER_MAX_ITER iterations (MuJoCo: tolerance 1e-8 in fp64, 100 iterations); the exact line search
 # stops at |slope| <= SOLVER_LS_TOL * |slope at 0| (MuJoCo's ls_tolerance default is 0.01 too; 1e-3 costs 2.4 % more on fixed plan inputs
@@ -53,6 +65,37 @@ HEADER_I, HEADER_F = 24, 24
 SOLVER_TOL, SOLVER_MAX_ITER, SOLVER_LS_TOL = 1e-5, 50, 1e-2
 # diagnostics: (phase, repeats) read only by -DJH_V2_ABLATE builds of the cooperative kernel (tools/diag/time_ablate.py)
 ABLATE = (0, 1)
+
+
+def image_offsets(I) -> types.SimpleNamespace:
+    """Where the sections of an image start, from its int section (a list under construction, or an array): `EngineModel::init` of jh_image.h restated, name for name
+    -- every run of records starts where the one before it ends -- with the leap family's sections as its `HostImage` names them (zero where the image has none).
+    The generic block's entries are there once the block is."""
+    slots = (("NM", HI_NM), ("NBLK", HI_NBLK), ("NV", HI_NV), ("NQ", HI_NQ), ("NU", HI_NU), ("NG", HI_NG), ("NSITE", HI_NSITE), ("NS", HI_NS), ("NSENS", HI_NSENS), ("cone", HI_CONE),
+             ("oLane", HI_LANES), ("LGM", HI_LGM), ("oBP", HI_BP), ("NBP", HI_NBP), ("oBS", HI_BS), ("oRef", HI_REF), ("oPT", HI_PT))
+    o = types.SimpleNamespace(**{name: int(I[slot]) for name, slot in slots})
+
+    def run(start, records):  # (name, ints or floats the records take)
+        for name, size in records:
+            setattr(o, name, start)
+            start += size
+
+    run(HEADER_I, (("oBodyI", o.NM * BODY_I), ("oBlockI", o.NBLK * BLOCK_I), ("oActI", o.NU * ACT_I), ("oGeomI", o.NG * GEOM_I), ("oSiteI", o.NSITE), ("oSensI", 0)))
+    run(HEADER_F, (("oBodyF", o.NM * BODY_F), ("oDofF", o.NV * DOF_F), ("oActF", o.NU * ACT_F), ("oGeomF", o.NG * GEOM_F), ("oSiteF", 0)))
+    o.oBG = o.oBP + 2 * o.NBP
+    gi, gf = int(I[HI_GI]), int(I[HI_GF])
+    if gi > 0:
+        for name, k in (("NAG", GI_NAG), ("NPAIR", GI_NPAIR), ("NEQ", GI_NEQ), ("NFRAME", GI_NFRAME), ("NDIST", GI_NDIST), ("NGS", GI_NGS)):
+            setattr(o, name, int(I[gi + k]))
+        run(gi + GEN_I, (("oAGI", o.NAG * GEOM_I), ("oPairI", o.NPAIR * 2), ("oEqI", o.NEQ * EQ_I), ("oFrameI", o.NFRAME), ("oDistI", o.NDIST * 4), ("oSensG", o.NGS * 4), ("oGlist", 0)))
+        run(gf, (("oAGF", o.NAG * GEOM_F), ("oGPF", o.NAG * GP_F), ("oEqF", o.NEQ * EQ_F), ("oFrameF", o.NFRAME * FRAME_F), ("oDistF", 0)))
+    return o
+
+
+def blob_sections(blob: bytes) -> tuple[np.ndarray, np.ndarray]:
+    """The float and the int section of a packed image."""
+    nf = int(np.frombuffer(blob[:64], np.uint32)[8])
+    return np.frombuffer(blob[64: 64 + 4 * nf], np.float32), np.frombuffer(blob[64 + 4 * nf:], np.int32)
 
 
 def _static_world_pose(desc: dict, b: int) -> tuple[np.ndarray, np.ndarray]:
@@ -308,10 +351,10 @@ def bounding_box_half(g: dict) -> np.ndarray:
 
 # ---- pair tables of the hand's broad phase (jh_engine_v5.hip, level 1) ---------------------------------------------------------------------------------------
 # A hand body pair whose relative pose depends on one or two hinge joints gets a bit grid over those joints' angles: a set bit says that NO pose in the cell can
-# give the pair a level-2 candidate, and the kernel drops the pair before its box test.  Layout of the section (header slot PT_SLOT holds its offset; 0: none):
+# give the pair a level-2 candidate, and the kernel drops the pair before its box test.  Layout of the section (header slot HI_PT holds its offset; 0: none):
 # [count, then PT_MAX records of PT_I ints: pair index, lane of joint 1, lane of joint 2, origin 1, 1 / cell width 1, origin 2, 1 / cell width 2 (float bits),
 # the 64-bit word (low, high)]; bit ix + 8 * iy.  A single-joint table is a row: joint 2 = joint 1 with 1 / cell width 0 (iy = 0).  Unused records are zero.
-PT_SLOT, PT_MAX, PT_I, PT_CELLS = 19, 4, 9, 8
+PT_MAX, PT_I, PT_CELLS = 4, 9, 8
 PT_SUB = 16        # sub-samples per cell and joint (cell midpoints of a PT_SUB x PT_SUB subdivision)
 PT_MARGIN = 0.2    # rad by which the grid reaches beyond each joint's range on both sides (the limits are soft: a joint runs past them under load)
 # What the table's bounds are widened by on top of the displacement bound D below: the kernel evaluates the same tests in fp32 in world coordinates -- operands
@@ -363,12 +406,9 @@ def hand_pair_tables(F: list, I: list) -> list[dict]:
     The tables chosen are those with the most cells that are safe AND pass the unwidened level 1 at some sample -- the cells where the table saves the kernel work --
     ties to the lower pair index; pairs with no such cell get none."""
     Ff = np.asarray(F, np.float32).astype(np.float64)  # (the values the kernel reads)
-    NM, NBLK, nv, nu, NG = I[0], I[1], I[2], I[4], I[5]
-    oDofF = HEADER_F + NM * BODY_F
-    oGeomF = oDofF + nv * DOF_F + nu * ACT_F
-    oGeomI = HEADER_I + NM * BODY_I + NBLK * BLOCK_I + nu * ACT_I
-    oBP, oBS, nBP = I[15], I[16], I[17]
-    oBG, NBC = oBP + 2 * nBP, 20
+    o = image_offsets(I)
+    NM, NBLK, nv, nu, NG, oDofF, oGeomF, oGeomI = o.NM, o.NBLK, o.NV, o.NU, o.NG, o.oDofF, o.oGeomF, o.oGeomI
+    oBP, oBS, nBP, oBG, NBC = o.oBP, o.oBS, o.NBP, o.oBG, BODY_CODES
     # The tables are a function of the pair list, the bodies' tree, frames, joint axes and ranges, the geoms' types, sizes and poses, and the bodies' bounding
     # volumes -- not of the cube, masses, gains or friction: images that differ in those alone (randomised physics) share one cache entry.  The cache is small and
     # bounded: an entry per hand geometry in use.
@@ -376,7 +416,8 @@ def hand_pair_tables(F: list, I: list) -> list[dict]:
     geoms = Ff[oGeomF: oGeomF + NG * GEOM_F].reshape(NG, GEOM_F)
     key = b"".join(np.ascontiguousarray(x).tobytes() for x in (
         np.asarray(I[HEADER_I: HEADER_I + NM * BODY_I] + I[oGeomI: oGeomI + NG * GEOM_I] + I[oBP: oBG + 2 * NBC] + [NM, NBLK, nv, nu, NG], np.int64),
-        bodies[:, 0:12], bodies[:, 28:31], Ff[oDofF + 6 * DOF_F: oDofF + nv * DOF_F].reshape(-1, DOF_F)[:, 6:9], geoms[:, 0:16], Ff[oBS: oBS + 8 * NBC]))
+        bodies[:, BF_LPOS:BF_LPOS + 12], bodies[:, BF_AXIS:BF_AXIS + 3], Ff[oDofF + 6 * DOF_F: oDofF + nv * DOF_F].reshape(-1, DOF_F)[:, DF_LIMITED:DF_HI + 1],
+        geoms[:, 0:GF_RBOUND + 1], Ff[oBS: oBS + BV_F * NBC]))
     if key in _pt_cache:
         _pt_cache.move_to_end(key)
         return _pt_cache[key]
@@ -397,7 +438,7 @@ def hand_pair_tables(F: list, I: list) -> list[dict]:
         G = Ff[oGeomF + g0 * GEOM_F: oGeomF + (g0 + n) * GEOM_F].reshape(n, GEOM_F)
         ty = [I[oGeomI + (g0 + k) * GEOM_I + 1] for k in range(n)]
         half = np.array([[g[0]] * 3 if t == GSPHERE else ([g[0], g[0], g[1]] if t == GCYLINDER else list(g[0:3])) for g, t in zip(G, ty)])
-        bb = Ff[oBS + 8 * c: oBS + 8 * c + 8]
+        bb = Ff[oBS + BV_F * c: oBS + BV_F * (c + 1)]
         return dict(pos=G[:, 3:6], R=G[:, 6:15].reshape(n, 3, 3), half=half, rb=G[:, 15], ctr=bb[0:3], rad=bb[3], bhalf=bb[4:7])
 
     cand = []
@@ -407,11 +448,11 @@ def hand_pair_tables(F: list, I: list) -> list[dict]:
         while la and lb and la[0] == lb[0]:
             la, lb = la[1:], lb[1:]
         links = la + lb
-        if not 1 <= len(links) <= 2 or any(I[HEADER_I + k * BODY_I + 1] != JHINGE or Ff[oDofF + (5 + k) * DOF_F + 6] == 0 for k in links):
+        if not 1 <= len(links) <= 2 or any(I[HEADER_I + k * BODY_I + 1] != JHINGE or Ff[oDofF + (5 + k) * DOF_F + DF_LIMITED] == 0 for k in links):
             continue
         # the grid
-        lo = [Ff[oDofF + (5 + k) * DOF_F + 7] - PT_MARGIN for k in links]
-        w = [(Ff[oDofF + (5 + k) * DOF_F + 8] + PT_MARGIN - l0) / PT_CELLS for k, l0 in zip(links, lo)]
+        lo = [Ff[oDofF + (5 + k) * DOF_F + DF_LO] - PT_MARGIN for k in links]
+        w = [(Ff[oDofF + (5 + k) * DOF_F + DF_HI] + PT_MARGIN - l0) / PT_CELLS for k, l0 in zip(links, lo)]
         two = len(links) == 2
         ncell = PT_CELLS * (PT_CELLS if two else 1)
         A, B = body_volumes(ca), body_volumes(cb)
@@ -432,7 +473,7 @@ def hand_pair_tables(F: list, I: list) -> list[dict]:
                     bf = Ff[HEADER_F + k * BODY_F: HEADER_F + (k + 1) * BODY_F]
                     P = P + R @ bf[0:3]
                     anchors.append(P)
-                    R = R @ bf[3:12].reshape(3, 3) @ _rot_axis(bf[28:31], qs[k])
+                    R = R @ bf[3:12].reshape(3, 3) @ _rot_axis(bf[BF_AXIS:BF_AXIS + 3], qs[k])
                 return R, P, anchors
 
             (RA, pA, anA), (RB, pB, anB) = side(la), side(lb)
@@ -504,7 +545,7 @@ def hand_pair_tables(F: list, I: list) -> list[dict]:
 
 
 def pair_table_section(tables: list[dict]) -> list[int]:
-    """The int section's table block (see PT_SLOT)."""
+    """The int section's table block (see HI_PT)."""
     bits = lambda x: int(np.float32(x).view(np.int32))  # noqa: E731
     s32 = lambda u: u - (1 << 32) if u >= 1 << 31 else u  # noqa: E731
     out = [len(tables)]
@@ -515,9 +556,8 @@ def pair_table_section(tables: list[dict]) -> list[int]:
 
 def read_pair_tables(blob: bytes) -> list[dict]:
     """The pair tables of a packed image: dicts as `hand_pair_tables` returns them (without score), [] where the image has none."""
-    nf = int(np.frombuffer(blob[:64], np.uint32)[8])
-    Iv = np.frombuffer(blob[64 + 4 * nf:], np.int32)
-    o = int(Iv[PT_SLOT]) if Iv.size > PT_SLOT else 0
+    Iv = blob_sections(blob)[1]
+    o = int(Iv[HI_PT]) if Iv.size > HI_PT else 0
     out = []
     for t in range(int(Iv[o]) if o > 0 else 0):
         r = Iv[o + 1 + t * PT_I: o + 1 + (t + 1) * PT_I]
@@ -594,7 +634,9 @@ def pack_engine_model(desc: dict, fingertips: str | None = None, pair_tables: bo
         raise NotImplementedError("engine kernels implement the implicitfast integrator (leap_cube / fr3_pick)")
     sites = desc["sites"]
     sens = desc["sensors"]
-    I[0:12] = [NM, NBLK, lay.nv, lay.nq, lay.nu, len(others), len(sites), lay.ns, integ, cone, len(sens), 0]
+    for slot, val in ((HI_NM, NM), (HI_NBLK, NBLK), (HI_NV, lay.nv), (HI_NQ, lay.nq), (HI_NU, lay.nu), (HI_NG, len(others)), (HI_NSITE, len(sites)), (HI_NS, lay.ns), (HI_INTEG, integ),
+                      (HI_CONE, cone), (HI_NSENS, len(sens))):
+        I[slot] = val
     # contact solver parameters are shared by all geoms in these models (checked)
     uniform = all(g["solref"] == cube["solref"] and g["solimp"] == cube["solimp"] for g in others)
     for g in others:
@@ -692,7 +734,7 @@ def pack_engine_model(desc: dict, fingertips: str | None = None, pair_tables: bo
         F += list(s["pos"])
     for s in sens:
         if s["type"] == "framepos" and s.get("reftype") is not None and s["objtype"] == "body":
-            I += [6, midx[s["obj"]], s["adr"]]  # body position in the static reference frame (tail block I[18])
+            I += [6, midx[s["obj"]], s["adr"]]  # body position in the static reference frame (tail block I[HI_REF])
         elif s["type"] == "framequat":
             I += [7, midx[s["obj"]], s["adr"]]  # body orientation relative to the static reference quaternion
         elif s["type"] == "framepos" and s["objtype"] == "site":
@@ -719,7 +761,7 @@ def pack_engine_model(desc: dict, fingertips: str | None = None, pair_tables: bo
             if st["is_static"][g["body"]]:
                 min(lists, key=len).append(gi)
         lgm = max(len(x) for x in lists)
-        I[11], I[12] = len(I), lgm
+        I[HI_LANES], I[HI_LGM] = len(I), lgm
         for x in lists:
             I += x + [-1] * (lgm - len(x))
         # hand self-collision (jh_engine_v5.hip): candidate geom pairs between hand bodies after MuJoCo's static filters (same welded body, parent-child,
@@ -744,7 +786,7 @@ def pack_engine_model(desc: dict, fingertips: str | None = None, pair_tables: bo
         if len(sgroups) > 4:
             raise NotImplementedError("more than four groups of static collision geometry")
         SCODES = [0, 17, 18, 19]
-        NBC = 20  # body codes in the image (jh_engine_v5.hip NBC)
+        NBC = BODY_CODES  # body codes in the image (jh_engine_v5.hip NBC)
         code = lambda g: SCODES[sgroups.index(frozenset(partners.get(g["body"], ())))] if st["is_static"][g["body"]] else link_code(g)  # noqa: E731
         is_static_code = lambda c: c == 0 or c > 16  # noqa: E731
         groups: dict[tuple[int, int], list[tuple[int, int]]] = {}
@@ -765,12 +807,12 @@ def pack_engine_model(desc: dict, fingertips: str | None = None, pair_tables: bo
             rng[c] = (idxs[0], len(idxs)) if idxs else (0, 0)
         for (ca, cb), lst in groups.items():
             assert len(lst) == rng[ca][1] * rng[cb][1] and rng[ca][1] + rng[cb][1] <= 16, (ca, cb, len(lst))
-        I[15], I[17] = len(I), len(groups)
+        I[HI_BP], I[HI_NBP] = len(I), len(groups)
         for (ca, cb) in groups:
             I += [ca, cb]
         for c in range(NBC):
             I += list(rng[c])
-        I[16] = len(F)
+        I[HI_BS] = len(F)
         for c in range(NBC):  # per hand body (static geometry: in world coordinates): bounding sphere and bounding box of its collision geoms, body frame
             gs = [g for g in others if code(g) == c]
             if not gs:
@@ -809,8 +851,8 @@ def pack_engine_model(desc: dict, fingertips: str | None = None, pair_tables: bo
             frames.append(dict(body=midx[sx["body"]], pos=sx["pos"], quat=sx.get("quat", [1, 0, 0, 0])))
     dists = [sx for sx in sens if sx["type"] == "distance"]
     eqs = desc["equalities"]
-    I[13], I[14] = len(I), len(F)
-    I[20], I[21] = ABLATE
+    I[HI_GI], I[HI_GF] = len(I), len(F)
+    I[HI_ABLATE], I[HI_ABLATE_N] = ABLATE
     I += [len(allg), len(pairs_all), len(eqs), len(frames), len(dists), len(sens), 0, 0]
     for g in allg:
         b = g["body"]
@@ -872,10 +914,10 @@ def pack_engine_model(desc: dict, fingertips: str | None = None, pair_tables: bo
             idist += 1
     I += glists
     if ref_frames is not None:  # reference frames of the sensors (jh_engine_v5.hip, caltech_leap_cube layout)
-        I[18] = len(F)
+        I[HI_REF] = len(F)
         F += ref_frames
-    if hand_tables:  # behind everything else in the int section, found through header slot 19 (zero in an image without tables): no other offset moves
-        I[PT_SLOT] = len(I)
+    if hand_tables:  # behind everything else in the int section, found through header slot HI_PT (zero in an image without tables): no other offset moves
+        I[HI_PT] = len(I)
         I += pair_table_section(hand_tables)
     ntp = 9 if desc.get("family", desc["task"]) == "leap_cube" else 22
     return _pack(TASK_KIND[desc.get("family", desc["task"])], lay, ntp, F, I)

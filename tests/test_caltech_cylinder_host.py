@@ -24,9 +24,8 @@ def _geom_table(blob: bytes):
     from judo_amd import engine_model as E
 
     F, I = _sections(blob)
-    NM, NBLK, nv, nu, NG = int(I[0]), int(I[1]), int(I[2]), int(I[4]), int(I[5])
-    oI = E.HEADER_I + NM * E.BODY_I + NBLK * E.BLOCK_I + nu * E.ACT_I
-    oF = E.HEADER_F + NM * E.BODY_F + nv * E.DOF_F + nu * E.ACT_F
+    o = E.image_offsets(I)
+    NG, oI, oF = o.NG, o.oGeomI, o.oGeomF
     return I[oI:oI + NG * E.GEOM_I].reshape(NG, E.GEOM_I), F[oF:oF + NG * E.GEOM_F].reshape(NG, E.GEOM_F)
 
 

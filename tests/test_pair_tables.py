@@ -37,13 +37,9 @@ class Hand:
     def __init__(self, blob, dtype):
         F, I = sections(blob)
         self.F, self.I, self.dt = F.astype(dtype), I, dtype
-        NM, NBLK, nv, nu, NG = (int(I[k]) for k in (0, 1, 2, 4, 5))
-        self.oDof = em.HEADER_F + NM * em.BODY_F
-        self.oGeomF = self.oDof + nv * em.DOF_F + nu * em.ACT_F
-        self.oGeomI = em.HEADER_I + NM * em.BODY_I + NBLK * em.BLOCK_I + nu * em.ACT_I
-        self.oBP, self.oBS, self.nBP = int(I[15]), int(I[16]), int(I[17])
-        self.oBG = self.oBP + 2 * self.nBP
-        self.ranges = np.array([[F[self.oDof + (6 + l) * em.DOF_F + 7], F[self.oDof + (6 + l) * em.DOF_F + 8]] for l in range(16)], np.float64)
+        o = em.image_offsets(I)
+        self.oDof, self.oGeomF, self.oGeomI, self.oBP, self.oBS, self.nBP, self.oBG = o.oDofF, o.oGeomF, o.oGeomI, o.oBP, o.oBS, o.NBP, o.oBG
+        self.ranges = np.array([[F[self.oDof + (6 + l) * em.DOF_F + em.DF_LO], F[self.oDof + (6 + l) * em.DOF_F + em.DF_HI]] for l in range(16)], np.float64)
 
     def kinematics(self, q):
         """World pose of the 16 links (body codes 1..16) at joint angles q (N, 16): the kernel's chain walk."""
@@ -137,7 +133,7 @@ def finger_tables(image):
     _, I = sections(image["blob"])
     out = {}
     for t in image["tables"]:
-        a, b = (image["code_name"].get(int(I[int(I[15]) + 2 * t["pair"] + k])) for k in (0, 1))
+        a, b = (image["code_name"].get(int(I[em.image_offsets(I).oBP + 2 * t["pair"] + k])) for k in (0, 1))
         for f in FINGERS:
             if (a, b) == (f + "_bs", f + "_md"):
                 out[f] = t
@@ -153,9 +149,9 @@ def test_the_three_base_to_middle_pairs_have_tables(image):
         assert names == [f + "_px", f + "_md"], names
     assert em.read_pair_tables(em.pack_engine_model(image["desc"], pair_tables=False)) == []
     a, b = sections(image["blob"]), sections(em.pack_engine_model(image["desc"], pair_tables=False))
-    o = int(a[1][em.PT_SLOT])
-    assert o == len(b[1]) and (a[0] == b[0]).all() and b[1][em.PT_SLOT] == 0  # behind everything else; nothing moved
-    keep = np.arange(o) != em.PT_SLOT
+    o = int(a[1][em.HI_PT])
+    assert o == len(b[1]) and (a[0] == b[0]).all() and b[1][em.HI_PT] == 0  # behind everything else; nothing moved
+    keep = np.arange(o) != em.HI_PT
     assert (a[1][:o][keep] == b[1][keep]).all()
 
 
@@ -217,11 +213,11 @@ def test_a_malformed_table_section_is_refused():
     """jh_model_create checks the block before it touches the device: the kernel indexes lanes and pair bits with what the records hold."""
     blob = em.pack_engine_model(models.load_description("leap_cube"))
     F, I = sections(blob)
-    o, nbp = int(I[em.PT_SLOT]), int(I[17])
+    o, nbp = int(I[em.HI_PT]), em.image_offsets(I).NBP
     nan = int(np.float32(np.nan).view(np.int32))
     bad = {"count": (o, em.PT_MAX + 1), "negative count": (o, -1), "pair": (o + 1, nbp), "negative pair": (o + 1, -1), "order": (o + 1 + em.PT_I, int(I[o + 1])),
-           "lane": (o + 2, 16), "lane 2": (o + 3, -1), "origin": (o + 4, nan), "cell width": (o + 5, 0), "cell width 2": (o + 7, nan), "offset": (em.PT_SLOT, len(I) - 3),
-           "offset in the header": (em.PT_SLOT, 5)}
+           "lane": (o + 2, 16), "lane 2": (o + 3, -1), "origin": (o + 4, nan), "cell width": (o + 5, 0), "cell width 2": (o + 7, nan), "offset": (em.HI_PT, len(I) - 3),
+           "offset in the header": (em.HI_PT, 5)}
     for what, (at, value) in bad.items():
         J = I.copy()
         J[at] = value
