@@ -438,7 +438,8 @@ int jh_plan_step_ensemble_phase(const jh_model_set* set, void* blk_dev, const vo
  *                                         costs no copy and no launch.  Every check of jh_plan_step_ensemble but `worst`'s, and those of the weights and the tail above,
  *                                         all before anything is enqueued.
  *   jh_plan_step_ensemble_weighted_phase  the same for fr3_pick, `phase` behind W: the rules of jh_plan_step_ensemble_phase.
- * The batched entries have no weighted form: B x M weights do not fit in the kernel arguments. */
+ * The batched entries take the measure per controller from a risk record in the controller's packed block (jh_plan_step_ensemble_batch_risk, below): B x M weights do
+ * not fit in the kernel arguments. */
 int jh_ensemble_costs_weighted(const float* member_costs /* DEVICE, M x ld */, int M, int N, int ld, const float* weights /* HOST, M */, float tail, float* costs /* DEVICE, N */,
                                void* stream);
 int jh_plan_step_ensemble_weighted(const jh_model_set* set, void* blk_dev, const void* blk_host, size_t blk_bytes, int o_nominal, int o_sigma, int o_tp, int o_lohi, const float* noise,
@@ -480,6 +481,43 @@ int jh_plan_step_ensemble_batch_phases(const jh_model_set* set, int B, int M, vo
                                        int o_lohi, int o_phase, const float* noise, int ldn, size_t noise_stride_floats, const float* W, int N, int H, int K,
                                        float* member_costs /* DEVICE, B x M x N */, float* costs /* DEVICE, B x N */, const int* worst /* HOST, B */, int mode, float lambda, int k, int tie_high,
                                        float* scratch, float* out, size_t out_stride_floats, void* out_host_mark, void* const* timing, void* stream);
+/* B ensemble plan steps in one call, each controller under a risk measure of its own: counted (`worst`) or plant-weighted, chosen per controller and per plan step.  With
+ * B <= JH_MAX_ENSEMBLE_FLEET and M <= JH_MAX_ENSEMBLE the weights are up to 32 KB and cannot travel by value, so they travel where fr3_pick's phase word does: in words of the
+ * controller's own packed block, behind its five sections, which go up with the block upload that happens anyway or are read in place with the block.
+ *   the risk record  1 + M fp32 words at the float offset `o_risk` of every controller's block (the same offset for all):
+ *                      the tail word   exactly 0.0: the counted measure with worst[b], as in jh_plan_step_ensemble_batch (the weights are not read); any other value is
+ *                                      the tail mass of the weighted measure and lies in (0, 1].  NaN, negative values and values above 1 are refused.
+ *                      the M weights   each finite and >= 0, at least one > 0; read only where the tail word is not zero.
+ *   the cost         a weighted controller's aggregated cost is, word for word, the definition above jh_ensemble_costs_weighted with its record's weights and tail; an
+ *                    unweighted controller's is jh_ensemble_costs' with worst[b].  Nothing new is defined, only where the parameters come from.
+ *   jh_ensemble_costs_risk_batch          the aggregation alone for B controllers: plant m's cost of controller b's rollout r at member_costs[(b * M + m) * ld + r] (ld >= N;
+ *                                         what lies between N and ld is not read), controller b's record at risk[b * risk_stride_floats ..] (risk_stride_floats >= 1 + M;
+ *                                         the words behind 1 + M are not read), costs[b * ldc + r] written (ldc >= N; what lies between N and ldc is not written).  The
+ *                                         records are DEVICE memory here, so the entry checks what it can before the enqueue -- each pointer, B in 1..JH_MAX_ENSEMBLE_FLEET,
+ *                                         M in 1..JH_MAX_ENSEMBLE, N >= 1, ld >= N, ldc >= N, the stride, every worst[b] in 1..M (HOST, B ints), JH_ERR_INVALID naming
+ *                                         the argument -- and NOT the records' contents: a record outside the rules above is outside the contract.
+ *   jh_plan_step_ensemble_batch_risk      jh_plan_step_ensemble_batch with `o_risk` behind o_lohi.  The rollout launch is the same call, so member_costs are bit for bit the
+ *                                         unweighted batched entry's; the tail on (tail workgroups, B) reads its controller's record as wave-uniform loads and aggregates
+ *                                         with the measure it names.  Controller b's costs and output record are bit for bit jh_plan_step_ensemble_weighted's with its
+ *                                         weights and tail, or jh_plan_step_ensemble's with worst[b] where its tail word is 0.0; with every tail word 0.0 the call equals
+ *                                         jh_plan_step_ensemble_batch in every output.  New records for the next plan step cost no copy and no launch of their own.
+ *                                         Every check before the first enqueue, JH_ERR_INVALID naming the argument: everything jh_plan_step_ensemble_batch refuses; worst[b]
+ *                                         outside 1..M for every b, weighted or not; o_risk negative; o_risk + 1 + M beyond blk_bytes / 4 (blk_bytes must cover the record:
+ *                                         the upload copies (B - 1) * blk_stride_bytes + blk_bytes); a record that overlaps x0, nominal, sigma, the task params, the bounds
+ *                                         or the phase word; and, read from the HOST block, a tail word that is NaN, negative or above 1 (the controller is named), a weight
+ *                                         that is negative or not finite (controller and index named), all weights zero (controller named).  JH_ERR_UNSUPPORTED as
+ *                                         jh_plan_step_ensemble_batch: an fr3_pick set is refused, and the error names the phase entry.
+ *   jh_plan_step_ensemble_batch_phases_risk  jh_plan_step_ensemble_batch_phases with `o_risk` behind o_phase: the same rules; any set but fr3_pick's is JH_ERR_UNSUPPORTED. */
+int jh_ensemble_costs_risk_batch(const float* member_costs /* DEVICE, B x M x ld */, int B, int M, int N, int ld, const float* risk /* DEVICE, B records */, size_t risk_stride_floats,
+                                 const int* worst /* HOST, B */, float* costs /* DEVICE, B x ldc */, int ldc, void* stream);
+int jh_plan_step_ensemble_batch_risk(const jh_model_set* set, int B, int M, void* blk_dev, const void* blk_host, size_t blk_bytes, size_t blk_stride_bytes, int o_nominal, int o_sigma, int o_tp,
+                                     int o_lohi, int o_risk, const float* noise, int ldn, size_t noise_stride_floats, const float* W, int N, int H, int K,
+                                     float* member_costs /* DEVICE, B x M x N */, float* costs /* DEVICE, B x N */, const int* worst /* HOST, B */, int mode, float lambda, int k, int tie_high,
+                                     float* scratch, float* out, size_t out_stride_floats, void* out_host_mark, void* const* timing, void* stream);
+int jh_plan_step_ensemble_batch_phases_risk(const jh_model_set* set, int B, int M, void* blk_dev, const void* blk_host, size_t blk_bytes, size_t blk_stride_bytes, int o_nominal, int o_sigma,
+                                            int o_tp, int o_lohi, int o_phase, int o_risk, const float* noise, int ldn, size_t noise_stride_floats, const float* W, int N, int H, int K,
+                                            float* member_costs /* DEVICE, B x M x N */, float* costs /* DEVICE, B x N */, const int* worst /* HOST, B */, int mode, float lambda, int k,
+                                            int tie_high, float* scratch, float* out, size_t out_stride_floats, void* out_host_mark, void* const* timing, void* stream);
 /* ONE domain-randomised plan step (MPPI / CEM / PS with a plant drawn per rollout; the reference has no counterpart): one controller, one nominal spline, N candidates,
  * each rolled out on ONE member of a model set, M <= JH_MAX_ENSEMBLE, and the update on the N costs as they are -- the rollouts of a plain plan step, never fitted to one
  * plant.  The rule, fixed here so that it can be tested bit for bit: the N candidates form G contiguous blocks of Nb = N / G rollouts (N % G == 0), block g is rollouts

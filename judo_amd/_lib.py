@@ -122,6 +122,13 @@ _SIGNATURES = {
     "jh_plan_step_ensemble_batch_phases": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_size_t, C.c_size_t, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, f32p, C.c_int, C.c_size_t, f32p,
                                                      C.c_int, C.c_int, C.c_int, f32p, f32p, C.POINTER(C.c_int), C.c_int, C.c_float, C.c_int, C.c_int, f32p, f32p, C.c_size_t, C.c_void_p, C.c_void_p,
                                                      C.c_void_p]),
+    "jh_ensemble_costs_risk_batch": (C.c_int, [f32p, C.c_int, C.c_int, C.c_int, C.c_int, f32p, C.c_size_t, C.POINTER(C.c_int), f32p, C.c_int, C.c_void_p]),
+    "jh_plan_step_ensemble_batch_risk": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_size_t, C.c_size_t, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, f32p, C.c_int, C.c_size_t,
+                                                   f32p, C.c_int, C.c_int, C.c_int, f32p, f32p, C.POINTER(C.c_int), C.c_int, C.c_float, C.c_int, C.c_int, f32p, f32p, C.c_size_t, C.c_void_p,
+                                                   C.c_void_p, C.c_void_p]),
+    "jh_plan_step_ensemble_batch_phases_risk": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_size_t, C.c_size_t, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, f32p, C.c_int,
+                                                          C.c_size_t, f32p, C.c_int, C.c_int, C.c_int, f32p, f32p, C.POINTER(C.c_int), C.c_int, C.c_float, C.c_int, C.c_int, f32p, f32p, C.c_size_t,
+                                                          C.c_void_p, C.c_void_p, C.c_void_p]),
     "jh_plan_step_randomized": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_int, C.c_int, C.c_int, C.c_int, f32p, C.c_int, f32p, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_ubyte), C.c_int,
                                           f32p, C.c_int, C.c_float, C.c_int, C.c_int, f32p, f32p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "jh_plan_step_randomized_batch": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_size_t, C.c_size_t, C.c_int, C.c_int, C.c_int, C.c_int, f32p, C.c_int, C.c_size_t, f32p, C.c_int,

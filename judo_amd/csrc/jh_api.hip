@@ -811,7 +811,7 @@ extern "C" int jh_plan_step_batch_phases_models(const jh_model_set* set, int B, 
                          noise_stride_floats, W, N, H, K, costs, trace, mode, lambda, k, tie_high, E, row_floats, colmajor, scratch, out, out_stride_floats, out_host_mark, timing, stream);
 }
 
-// ---- plan steps on the plants of a model set (include/judo_amd.h): ONE launcher behind the ten entries, with three degrees of freedom ----
+// ---- plan steps on the plants of a model set (include/judo_amd.h): ONE launcher behind the twelve entries, with three degrees of freedom ----
 //  - the kind, what the rollout launch's y axis means.  Ensemble: the M members -- every member rolls out the same N candidates from the same block (block and noise
 //    strides 0) on its own image into its own row of member_costs, and the tail aggregates the M rows into `costs` (the mean of the `worst` largest) before it updates.
 //    With `weights` set the tail is the plant-weighted one (the tail mean under the weights, which travel in the kernel arguments); the rollout launch is the same call.
@@ -822,6 +822,8 @@ extern "C" int jh_plan_step_batch_phases_models(const jh_model_set* set, int B, 
 //    (entry c * G + g), the strides of jh_plan_step_batch between them; a set of M members is shared by all controllers (image stride 0 on that axis), a set of B * M holds
 //    controller b's plants at b * M ...  The tail is then the batched one on (tail workgroups, B) with the two-level ticket and one completion word.  Without the axis the
 //    tails are the single call's (k_update_tail, k_update_tail_ensemble): not B = 1 of the batched ones.
+//    With `o_risk` set, an ensemble's controllers each carry a risk record in their block (the tail word, 0.0 for `worst`, then M weights; the B records are checked on
+//    the host) and the batched tail is the one that reads them: the measure per controller and per plan step, where B x M weights would not fit in the kernel arguments.
 //  - the phase, fr3_pick's alone (the entries that take one refuse every other family): none, and fr3_pick is refused; `phase` 0..3, one controller's, which travels in the
 //    launch record to every member's or block's workgroups; or `o_phase`, the float offset of every controller's phase word in its block (the B words are checked on the host).
 // Always two launches (the closed-form models' one-launch form would roll a candidate out on one member per workgroup); no trace buffer, no knots_out.  Every check stands
@@ -838,7 +840,33 @@ struct jh_set_step {
   const unsigned char* plant_of_block = nullptr; int G = 0;                           // randomised: the (B x) G table
   bool fleet = false; int B = 1, M = 0; size_t out_stride_floats = 0;                 // the controller axis (its block and noise strides are the shape's)
   int phase = -1, o_phase = -1;
+  int o_risk = -1;                                                                    // ensemble with a controller axis: the float offset of every controller's risk record in its block
 };
+
+// The B risk records of jh_plan_step_ensemble_batch_risk, on the host, before anything is enqueued (as phase_words reads the phases): the record's place in the block --
+// inside blk_bytes, which the upload copies, and clear of the five sections and the phase word --, then every controller's tail word and, where that is not zero, weights.
+static int risk_records(const char* who, const jh_model* m, int B, int M, const void* blk_host, const jh_block_shape& d, int o_phase, int o_risk) {
+  const long long lo = o_risk, hi = (long long)o_risk + 1 + M;
+  JH_REQUIRE(sizeof(float) * (size_t)hi <= d.bytes, "%s: o_risk = %d: a risk record of 1 + M = %d floats ends outside a block of %zu bytes", who, o_risk, 1 + M, d.bytes);
+  const int KU = d.K * m->nu;
+  const struct { const char* name; long long at, n; } parts[] = {{"x0", 0, m->nq + m->nv}, {"nominal", d.o_nominal, KU}, {"sigma", d.o_sigma, KU}, {"task params", d.o_tp, m->ntaskparam},
+                                                                 {"bounds", d.o_lohi, 2 * m->nu}, {"phase word", o_phase, o_phase >= 0 ? 1 : 0}};
+  for (const auto& p : parts)
+    JH_REQUIRE(p.n <= 0 || hi <= p.at || p.at + p.n <= lo, "%s: o_risk = %d: the risk record [%lld, %lld) overlaps the block's %s [%lld, %lld)", who, o_risk, lo, hi, p.name, p.at, p.at + p.n);
+  for (int b = 0; b < B; b++) {
+    const float* rec = reinterpret_cast<const float*>(static_cast<const char*>(blk_host) + (size_t)b * d.stride_bytes) + o_risk;
+    const float tail = rec[0];
+    JH_REQUIRE(tail >= 0.f && tail <= 1.f, "%s: controller %d: the tail word of its risk record is %g, neither 0 (the `worst` measure) nor in (0, 1]", who, b, (double)tail);  // (false for NaN)
+    if (tail == 0.f) continue;
+    bool positive = false;
+    for (int i = 0; i < M; i++) {
+      JH_REQUIRE(std::isfinite(rec[1 + i]) && rec[1 + i] >= 0.f, "%s: controller %d: weights[%d] = %g is negative or not finite", who, b, i, (double)rec[1 + i]);
+      positive = positive || rec[1 + i] > 0.f;
+    }
+    JH_REQUIRE(positive, "%s: controller %d: weights are all zero (M = %d): at least one plant needs a positive weight", who, b, M);
+  }
+  return JH_OK;
+}
 
 static int plan_step_set(const jh_set_step& r) {
   const char* who = r.who;
@@ -885,6 +913,8 @@ static int plan_step_set(const jh_set_step& r) {
   const jh_engine_build* eb = engine_build(m);
   if (!closed && !(eb && eb->rollout_cost_batch)) { jh_set_error("%s: no batched kernel for this model", who); return JH_ERR_UNSUPPORTED; }
   if (r.o_phase >= 0) { if (int rc = phase_words(who, "controller", B, r.blk_host, d.bytes, d.stride_bytes, r.o_phase)) return rc; }
+  const bool risk = r.fleet && !r.randomized && r.o_risk >= 0;
+  if (risk) { if (int rc = risk_records(who, m, B, M, r.blk_host, d, r.o_phase, r.o_risk)) return rc; }
   unsigned* flag = (r.out_host_mark && r.out_host_mark != (void*)r.out) ? (unsigned*)r.out_host_mark : nullptr;  // (out_host_mark == out: the stream's event)
   const float* b = (const float*)r.blk_dev;
   jh_upd::TailArgs a;  // (controller 0's record; the tail's own checks before anything is enqueued: mode, lambda, k)
@@ -928,7 +958,13 @@ static int plan_step_set(const jh_set_step& r) {
     jh_upd::EnsembleBatchArgs e;
     e.member_costs = r.member_costs; e.costs = r.costs; e.M = M; e.stride = (long long)N;
     for (int i = 0; i < JH_MAX_ENSEMBLE_FLEET; i++) e.worst[i] = (unsigned char)(!r.randomized && i < B ? r.worst[i] : 1);
-    rc = r.randomized ? jh_update_tail_batch_launch(a, s, st) : jh_update_tail_ensemble_batch_launch(a, s, e, st);
+    if (risk) {
+      jh_upd::EnsembleRiskBatchArgs q;
+      q.member_costs = r.member_costs; q.costs = r.costs; q.M = M; q.stride = (long long)N; q.slab = (long long)M * N; q.ldc = s.costs;
+      q.risk = b + r.o_risk; q.risk_stride = blk_c;
+      for (int i = 0; i < JH_MAX_ENSEMBLE_FLEET; i++) q.worst[i] = e.worst[i];
+      rc = jh_update_tail_ensemble_risk_batch_launch(a, s, q, st);
+    } else rc = r.randomized ? jh_update_tail_batch_launch(a, s, st) : jh_update_tail_ensemble_batch_launch(a, s, e, st);
   }
   if (rc == JH_OK && r.timing) JH_HIP(hipEventRecord((hipEvent_t)r.timing[2], st));
   if (rc == JH_OK) rc = download_begin(r.out, r.out, 0, r.stream, flag, expect);
@@ -1034,6 +1070,37 @@ extern "C" int jh_plan_step_ensemble_batch_phases(const jh_model_set* set, int B
   JH_REQUIRE(o_phase >= 0, "%s: negative block offset (o_phase=%d)", who, o_phase);
   jh_set_step r = JH_SET_STEP(who, true, blk_stride_bytes, noise_stride_floats);
   r.member_costs = member_costs; r.worst = worst; r.o_phase = o_phase;
+  r.fleet = true; r.B = B; r.M = M; r.out_stride_floats = out_stride_floats;
+  return plan_step_set(r);
+}
+
+// jh_plan_step_ensemble_batch with a risk record in every controller's block (include/judo_amd.h): the same record with `o_risk`, so the rollout launch is the same call
+// and the tail launch the one that reads the records.
+extern "C" int jh_plan_step_ensemble_batch_risk(const jh_model_set* set, int B, int M, void* blk_dev, const void* blk_host, size_t blk_bytes, size_t blk_stride_bytes, int o_nominal, int o_sigma,
+                                                int o_tp, int o_lohi, int o_risk, const float* noise, int ldn, size_t noise_stride_floats, const float* W, int N, int H, int K, float* member_costs,
+                                                float* costs, const int* worst, int mode, float lambda, int k, int tie_high, float* scratch, float* out, size_t out_stride_floats,
+                                                void* out_host_mark, void* const* timing, void* stream) {
+  const char* who = "plan_step_ensemble_batch_risk";
+  JH_REQUIRE(o_risk >= 0, "%s: negative block offset (o_risk=%d)", who, o_risk);
+  jh_set_step r = JH_SET_STEP(who, true, blk_stride_bytes, noise_stride_floats);
+  r.fr3_hint = "jh_plan_step_ensemble_batch_phases_risk takes a phase word per controller as well";
+  r.member_costs = member_costs; r.worst = worst; r.o_risk = o_risk;
+  r.fleet = true; r.B = B; r.M = M; r.out_stride_floats = out_stride_floats;
+  return plan_step_set(r);
+}
+
+// jh_plan_step_ensemble_batch_phases with a risk record in every controller's block.
+extern "C" int jh_plan_step_ensemble_batch_phases_risk(const jh_model_set* set, int B, int M, void* blk_dev, const void* blk_host, size_t blk_bytes, size_t blk_stride_bytes, int o_nominal,
+                                                       int o_sigma, int o_tp, int o_lohi, int o_phase, int o_risk, const float* noise, int ldn, size_t noise_stride_floats, const float* W, int N,
+                                                       int H, int K, float* member_costs, float* costs, const int* worst, int mode, float lambda, int k, int tie_high, float* scratch, float* out,
+                                                       size_t out_stride_floats, void* out_host_mark, void* const* timing, void* stream) {
+  const char* who = "plan_step_ensemble_batch_phases_risk";
+  JH_REQUIRE(set != nullptr, "%s: set is a null pointer", who);
+  if (set->m0->kind != JH_TASK_FR3_PICK) { jh_set_error("%s: a phase word per controller is fr3_pick's alone; jh_plan_step_ensemble_batch_risk plans this set", who); return JH_ERR_UNSUPPORTED; }
+  JH_REQUIRE(o_phase >= 0, "%s: negative block offset (o_phase=%d)", who, o_phase);
+  JH_REQUIRE(o_risk >= 0, "%s: negative block offset (o_risk=%d)", who, o_risk);
+  jh_set_step r = JH_SET_STEP(who, true, blk_stride_bytes, noise_stride_floats);
+  r.member_costs = member_costs; r.worst = worst; r.o_phase = o_phase; r.o_risk = o_risk;
   r.fleet = true; r.B = B; r.M = M; r.out_stride_floats = out_stride_floats;
   return plan_step_set(r);
 }

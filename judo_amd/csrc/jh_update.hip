@@ -598,3 +598,52 @@ int jh_update_tail_ensemble_weighted_launch(const TailArgs& a, const EnsembleWei
   JH_HIP(hipGetLastError());
   return JH_OK;
 }
+
+// ------------------------------------------------------------------------------------------------ B ensemble controllers, a risk record each
+// (Defined behind everything else, for the reason above.)  k_ensemble_costs_risk_batch is the aggregation alone on (workgroups, B): controller blockIdx.y's slab of
+// member costs under its own risk record (jh_update_dev.h: ensemble_cost_risk).  k_update_tail_ensemble_risk_batch is what jh_plan_step_ensemble_batch_risk launches
+// behind the rollout kernel: k_update_tail_ensemble_batch with the record read from the controller's packed block where `worst` alone stood.
+namespace {
+__global__ __launch_bounds__(kUB) void k_ensemble_costs_risk_batch(EnsembleRiskBatchArgs e, int N) {
+  const int b = blockIdx.y;
+  const int r = blockIdx.x * kUB + threadIdx.x;
+  if (r < N) e.costs[b * e.ldc + r] = ensemble_cost_risk(e.member_costs + b * e.slab, e.M, e.stride, r, e.risk + b * e.risk_stride, (int)e.worst[b]);
+}
+__global__ __launch_bounds__(kUB) void k_update_tail_ensemble_risk_batch(TailArgs base, BatchArgs s, EnsembleRiskBatchArgs e) {
+  const int b = blockIdx.y;
+  const TailArgs a = batch_problem(base, s, b);
+  const int r = blockIdx.x * kUB + threadIdx.x;
+  if (r < a.N) e.costs[b * e.ldc + r] = ensemble_cost_risk(e.member_costs + b * e.slab, e.M, e.stride, r, e.risk + b * e.risk_stride, (int)e.worst[b]);
+  __syncthreads();  // (a thread reads back the cost it wrote, as in k_update_tail_ensemble)
+  batch_done(s, update_tail_body(a));
+}
+}  // namespace
+
+extern "C" int jh_ensemble_costs_risk_batch(const float* member_costs, int B, int M, int N, int ld, const float* risk, size_t risk_stride_floats, const int* worst, float* costs, int ldc,
+                                            void* stream) {
+  const char* who = "ensemble_costs_risk_batch";
+  JH_REQUIRE(member_costs != nullptr, "%s: member_costs is a null pointer", who);
+  JH_REQUIRE(risk != nullptr, "%s: risk is a null pointer", who);
+  JH_REQUIRE(worst != nullptr, "%s: worst is a null pointer", who);
+  JH_REQUIRE(costs != nullptr, "%s: costs is a null pointer", who);
+  JH_REQUIRE(B >= 1 && B <= JH_MAX_ENSEMBLE_FLEET, "%s: B = %d outside [1, JH_MAX_ENSEMBLE_FLEET = %d]", who, B, JH_MAX_ENSEMBLE_FLEET);
+  JH_REQUIRE(M >= 1 && M <= JH_MAX_ENSEMBLE, "%s: M = %d outside [1, JH_MAX_ENSEMBLE = %d]", who, M, JH_MAX_ENSEMBLE);
+  JH_REQUIRE(N > 0, "%s: N must be positive (N=%d)", who, N);
+  JH_REQUIRE(ld >= N, "%s: ld (%d) < N (%d)", who, ld, N);
+  JH_REQUIRE(ldc >= N, "%s: ldc (%d) < N (%d)", who, ldc, N);
+  JH_REQUIRE(risk_stride_floats >= (size_t)(1 + M), "%s: risk_stride_floats = %zu is smaller than a risk record (1 + M = %d floats)", who, risk_stride_floats, 1 + M);
+  for (int b = 0; b < B; b++) JH_REQUIRE(worst[b] >= 1 && worst[b] <= M, "%s: controller %d: worst = %d outside [1, M = %d]", who, b, worst[b], M);
+  EnsembleRiskBatchArgs e;
+  e.member_costs = member_costs; e.costs = costs; e.M = M; e.stride = (long long)ld; e.slab = (long long)M * ld; e.ldc = (long long)ldc;
+  e.risk = risk; e.risk_stride = (long long)risk_stride_floats;
+  for (int i = 0; i < JH_MAX_ENSEMBLE_FLEET; i++) e.worst[i] = (unsigned char)(i < B ? worst[i] : 1);
+  hipLaunchKernelGGL(k_ensemble_costs_risk_batch, dim3((N + kUB - 1) / kUB, B), dim3(kUB), 0, (hipStream_t)stream, e, N);
+  JH_HIP(hipGetLastError());
+  return JH_OK;
+}
+
+int jh_update_tail_ensemble_risk_batch_launch(const TailArgs& a, const BatchArgs& s, const EnsembleRiskBatchArgs& e, hipStream_t st) {
+  hipLaunchKernelGGL(k_update_tail_ensemble_risk_batch, dim3((a.N + kUB - 1) / kUB, s.B), dim3(kUB), 0, st, a, s, e);
+  JH_HIP(hipGetLastError());
+  return JH_OK;
+}

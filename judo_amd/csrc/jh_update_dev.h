@@ -469,6 +469,29 @@ struct EnsembleBatchArgs {
   unsigned char worst[JH_MAX_ENSEMBLE_FLEET];
 };
 
+// ---------------------------------------------------------------- ... each with a risk measure of its own (jh_plan_step_ensemble_batch_risk)
+// B x M weights do not fit in the kernel arguments, so a controller's risk measure travels where its phase word does (fr3): in words of its own packed block, behind
+// the five sections.  The risk record is 1 + M floats at the same offset of every block: the tail word, then the M weights.  A tail word of exactly 0.0 is the counted
+// measure with worst[b] (ensemble_cost); any other is the tail mass of the plant-weighted one (ensemble_cost_weighted) under the M weights behind it.  The record's
+// address -- `risk` + blockIdx.y * the record stride -- is wave-uniform: the words are scalar loads, the branch is uniform over the workgroup, and the weights fill an
+// EnsembleWeights through a loop unrolled to JH_MAX_ENSEMBLE under the uniform guard m < M, so the weighted aggregation finds them where the by-value record had them.
+// The host has checked the B records (jh_api.hip: risk_records) before anything was enqueued.
+struct EnsembleRiskBatchArgs {
+  const float* member_costs; float* costs;  // B x slab in, B x ldc out (the tail: slab = M * stride, ldc = s.costs, and `costs` is the base record's TailArgs::costs)
+  int M; long long stride, slab, ldc;
+  const float* risk; long long risk_stride;  // controller 0's record; floats from a controller's record to the next one's (the tail: s.blk)
+  unsigned char worst[JH_MAX_ENSEMBLE_FLEET];
+};
+// rollout r's aggregated cost under the record at `risk` (wave-uniform)
+__device__ __forceinline__ float ensemble_cost_risk(const float* __restrict__ member_costs, int M, long long stride, int r, const float* __restrict__ risk, int worst) {
+  const float tail = risk[0];
+  if (tail == 0.f) return ensemble_cost(member_costs, M, stride, r, worst);
+  EnsembleWeights w;
+#pragma unroll
+  for (int m = 0; m < JH_MAX_ENSEMBLE; m++) w.p[m] = m < M ? risk[1 + m] : 0.f;
+  return ensemble_cost_weighted(member_costs, M, stride, r, w, tail);
+}
+
 }  // namespace jh_upd
 
 // jh_update.hip: the argument checks of jh_update_fused / jh_update_shard and the launch record of the tail (rec_out non-null: the shard form)
@@ -496,3 +519,6 @@ int jh_update_tail_ensemble_batch_launch(const jh_upd::TailArgs& a, const jh_upd
 // jh_ensemble_weights_check is the host check of both weighted entries -- `weights` HOST, M finite values >= 0 with one above 0, `tail` in (0, 1] -- and fills the record.
 int jh_ensemble_weights_check(const char* who, const float* weights, int M, float tail, jh_upd::EnsembleWeights* out);
 int jh_update_tail_ensemble_weighted_launch(const jh_upd::TailArgs& a, const jh_upd::EnsembleWeightedArgs& e, hipStream_t st);
+// the ensemble fleet's tail with a risk record per controller (jh_plan_step_ensemble_batch_risk): jh_update_tail_ensemble_batch_launch with the records where `worst`
+// alone stood; e.slab, e.ldc and e.risk_stride are the tail's (M * e.stride, s.costs, s.blk)
+int jh_update_tail_ensemble_risk_batch_launch(const jh_upd::TailArgs& a, const jh_upd::BatchArgs& s, const jh_upd::EnsembleRiskBatchArgs& e, hipStream_t st);

@@ -93,6 +93,33 @@ def aggregate_costs_weighted_host(member_costs, weights, tail) -> np.ndarray:
         return (acc / got).astype(f32)
 
 
+def aggregate_costs_risk_batch_host(member_costs, worst, risk) -> np.ndarray:
+    """The aggregated costs of B controllers, (B, N) fp32, from `member_costs` (B, M, N), `worst` (B,) and the controllers' risk records `risk` (B, 1 + M) as
+    include/judo_amd.h fixes them for `jh_ensemble_costs_risk_batch`: a tail word of exactly 0 is the counted measure with `worst[b]` (`aggregate_costs_host`; the
+    weights are not read), any other the tail mass of the plant-weighted one under the M weights behind it (`aggregate_costs_weighted_host`).  Nothing is computed
+    here: controller by controller it is one of the two restatements.  Raises ValueError for what they refuse, naming the controller."""
+    c = np.asarray(member_costs, dtype=np.float32)
+    if c.ndim != 3:
+        raise ValueError(f"member_costs must be (B, M, N), got {c.shape}")
+    B, M, N = c.shape
+    j = np.asarray(worst).reshape(-1)
+    if j.size != B:
+        raise ValueError(f"{j.size} values of worst for B = {B} controllers")
+    with np.errstate(over="ignore"):
+        rec = np.asarray(risk, dtype=np.float32)
+    if rec.shape != (B, 1 + M):
+        raise ValueError(f"risk must be (B, 1 + M) = ({B}, {1 + M}), got {rec.shape}")
+    out = np.empty((B, N), dtype=np.float32)
+    for b in range(B):
+        try:
+            if not 1 <= int(j[b]) <= M:  # (every controller's, weighted or not, as the library checks it)
+                raise ValueError(f"worst = {j[b]} outside [1, M = {M}]")
+            out[b] = aggregate_costs_host(c[b], int(j[b])) if rec[b, 0] == 0 else aggregate_costs_weighted_host(c[b], rec[b, 1:], rec[b, 0])
+        except ValueError as e:
+            raise ValueError(f"controller {b}: {e}") from None
+    return out
+
+
 def check_task(task: Task, fr3: bool = False) -> None:
     """The tasks without an ensemble plan step, refused before any model is made; raises ValueError.  `fr3`: the caller's plan step carries the arm's phase
     (judo_amd.fr3_ensemble), so fr3_pick passes."""
@@ -150,4 +177,4 @@ def make_ensemble_controller(task: str | Task, optimizer: str, descriptions: Seq
     return make_for(EnsembleController, task, optimizer, descriptions, worst=worst, device=device)
 
 
-__all__ = ["EnsembleController", "MAX_ENSEMBLE", "aggregate_costs_host", "aggregate_costs_weighted_host", "check_descriptions", "check_task", "make_ensemble_controller"]
+__all__ = ["EnsembleController", "MAX_ENSEMBLE", "aggregate_costs_host", "aggregate_costs_risk_batch_host", "aggregate_costs_weighted_host", "check_descriptions", "check_task", "make_ensemble_controller"]

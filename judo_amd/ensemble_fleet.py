@@ -127,7 +127,8 @@ class EnsembleFleet(PlantFleet, ControllerFleet):
         """A member under the plant-weighted risk measure (`set_weights`) has no place in the launch (`_check_member`: at admission and again in front of every plan step)."""
         if c.weights is not None:
             raise ValueError(f"fleet member {i} has plant weights set (set_weights): the fleet launch carries one `worst` per controller, and B x M weights do not fit in "
-                             "its kernel arguments.  set_weights(None) returns the member to the `worst` measure; a weighted controller plans on its own")
+                             "its kernel arguments.  set_weights(None) returns the member to the `worst` measure; a weighted controller plans on its own, or shares a launch in a "
+                             "WeightedEnsembleFleet (judo_amd.weighted_fleet.make_weighted_ensemble_fleet), whose launch reads a risk record from every member's packed block")
 
     def _launch(self, step: _LaunchStep) -> None:
         self._launch_ensemble(_lib.lib().jh_plan_step_ensemble_batch, step)

@@ -103,15 +103,17 @@ class _MemberBuffers:
 class _FleetBuffers:
     """Everything a fleet's plan step touches, for B problems of one size: B packed blocks in one pinned host buffer (and its device copy), the noise, costs,
     trace rows, update scratch, and the pinned output block with its completion word.  `extra`: words of every block behind `bounds` that belong to the fleet, not to
-    the member's five sections (FR3Fleet: the phase word); a member's views end in front of them."""
+    the member's five sections (FR3Fleet: the phase word); a member's views end in front of them.  `extra_at`: where in those words the records begin whose offsets the
+    fleet's entry takes behind the bounds' (the phase word at 0; a weighted fleet's risk record behind it)."""
 
-    def __init__(self, dev: torch.device, B: int, N: int, K: int, nu: int, nx: int, ntp: int, E: int, extra: int = 0) -> None:
+    def __init__(self, dev: torch.device, B: int, N: int, K: int, nu: int, nx: int, ntp: int, E: int, extra: int = 0, extra_at: Sequence[int] = (0,)) -> None:
         L = _lib.lib()
         self.dev, self.B, self.N, self.K, self.nu, self.E = dev, B, N, K, nu, E
         self.sizes = [nx, K * nu, K * nu, ntp, 2 * nu]
         self.nblk = sum(self.sizes)
         self.offsets = [int(v) for v in np.cumsum([0] + self.sizes)]
         self.extra = extra
+        self.extra_offsets = tuple(self.nblk + int(at) for at in extra_at) if extra else ()  # float offsets in a block, as the entry takes them
         self.blk_stride = self.nblk + extra  # floats from a member's block to the next one's
         self.host = torch.zeros(B * self.blk_stride, dtype=torch.float32).pin_memory()
         self.host_np, self.host_ptr = self.host.numpy(), self.host.data_ptr()
@@ -152,8 +154,8 @@ class _LaunchStep:
     def __init__(self, fb: "_FleetBuffers") -> None:
         self.fb = fb
         # the blocks: device (or host, read in place), host, bytes of one, bytes from one to the next, the offsets of nominal, sigma, task params and bounds -- and of the
-        # fleet's extra word behind the bounds where the blocks have one (the fr3 entries' phase word)
-        run = (fb.host_ptr, 4 * (fb.nblk + fb.extra), 4 * fb.blk_stride, *fb.offsets[1:5]) + ((fb.nblk,) if fb.extra else ())
+        # fleet's extra words behind the bounds where the blocks have some (the fr3 entries' phase word, the weighted fleets' risk record)
+        run = (fb.host_ptr, 4 * (fb.nblk + fb.extra), 4 * fb.blk_stride, *fb.offsets[1:5], *fb.extra_offsets)
         self.blocks = {False: (fb.blk.data_ptr(), *run), True: (fb.host_ptr, *run)}
         self._fixed = (fb.N, fb.K * fb.nu * fb.N, fb.scratch.data_ptr(), fb.done.data_ptr())
 
@@ -177,6 +179,7 @@ class ControllerFleet:
     _randomized_members = False  # members are `RandomizedController`s, each spreading its rollout blocks over the M plants of its set (RandomizedFleet)
     _fr3_members = False  # members are fr3_pick controllers, whose phase travels in the packed block (judo_amd.fr3_fleet.FR3Fleet)
     _block_extra_words = 0  # words of every packed block behind the bounds that the fleet writes itself (FR3Fleet: 1, the phase word)
+    _block_extra_at: tuple = (0,)  # where in those words the records begin whose offsets the entry takes (judo_amd.weighted_fleet: the risk record, behind the phase word if any)
 
     def __init__(self, controllers: Sequence[Controller]) -> None:
         self.controllers = list(controllers)
@@ -290,7 +293,7 @@ class ControllerFleet:
 
     def _buffers(self, key: tuple) -> _FleetBuffers:
         if self._bufs_key != key:
-            self._bufs, self._bufs_key = _FleetBuffers(self.device, *key, extra=self._block_extra_words), key
+            self._bufs, self._bufs_key = _FleetBuffers(self.device, *key, extra=self._block_extra_words, extra_at=self._block_extra_at), key
         return self._bufs
 
     def _draw_noise(self, fb: _FleetBuffers, N: int, K: int, nu: int) -> torch.Tensor:
