@@ -313,6 +313,45 @@ __device__ __forceinline__ void collide_box_capsule(Sink& sk, const float* pb, c
   }
 }
 
+// capsule against capsule (MuJoCo's mjc_CapsuleCapsule as oracle/jo_engine.c::collide_capsule_capsule restates it; the shared routine: the fr3 kernel's self-collision build
+// calls it, and jh_engine_v4.hip keeps a copy of its own inside its kernel for the Spot robot against itself, which compiles to the code it had): the closest points of the two axis segments, then sphere against
+// sphere there; parallel axes: the ends of either capsule against the other's segment, at most two contacts.  Normal from the first capsule to the second.
+template <class Sink>
+__device__ __forceinline__ void collide_capsule_capsule(Sink& sk, const float* p1, const float* R1, float r1, float L1, const float* p2, const float* R2, float r2, float L2) {
+  auto sphere_sphere = [&](const float* ca, const float* cb) __attribute__((always_inline)) {
+    const float d[3] = {cb[0] - ca[0], cb[1] - ca[1], cb[2] - ca[2]}; const float ln = sqrtf(dot3(d, d)), dist = ln - r1 - r2;
+    if (dist > 0.f) return false;
+    const bool same = ln < 1e-12f;  // coincident centres: mju_normalize3 returns (1, 0, 0)
+    const float n3[3] = {same ? 1.f : d[0] / ln, same ? 0.f : d[1] / ln, same ? 0.f : d[2] / ln}, mm = r1 + 0.5f * dist;
+    const float ps[3] = {ca[0] + mm * n3[0], ca[1] + mm * n3[1], ca[2] + mm * n3[2]};
+    sk.push(ps, n3, dist);
+    return true;
+  };
+  float a1[3], a2[3]; col3(a1, R1, 2); col3(a2, R2, 2);
+  for (int i = 0; i < 3; i++) { a1[i] *= L1; a2[i] *= L2; }
+  const float dif[3] = {p1[0] - p2[0], p1[1] - p2[1], p1[2] - p2[2]};
+  const float ma = dot3(a1, a1), mb = -dot3(a1, a2), mc = dot3(a2, a2), u = -dot3(a1, dif), v = dot3(a2, dif);
+  const float det = ma * mc - mb * mb;
+  if (fabsf(det) >= 1e-6f * ma * mc) {  // (MuJoCo: |det| >= mjMINVAL in fp64; in fp32 the determinant of two axes less than ~1e-3 rad apart is rounding noise)
+    float x1 = (mc * u - mb * v) / det, x2 = (ma * v - mb * u) / det;
+    if (x1 > 1.f) { x1 = 1.f; x2 = (v - mb) / mc; } else if (x1 < -1.f) { x1 = -1.f; x2 = (v + mb) / mc; }
+    if (x2 > 1.f) { x2 = 1.f; x1 = jh_clampf((u - mb) / ma, -1.f, 1.f); }
+    else if (x2 < -1.f) { x2 = -1.f; x1 = jh_clampf((u + mb) / ma, -1.f, 1.f); }
+    const float v1[3] = {p1[0] + a1[0] * x1, p1[1] + a1[1] * x1, p1[2] + a1[2] * x1}, v2[3] = {p2[0] + a2[0] * x2, p2[1] + a2[1] * x2, p2[2] + a2[2] * x2};
+    sphere_sphere(v1, v2);
+  } else {
+    int nfound = 0;
+#pragma unroll 1
+    for (int e = 0; e < 4; e++) {
+      float x1, x2;
+      if (e < 2) { x1 = e == 0 ? 1.f : -1.f; x2 = jh_clampf((v - x1 * mb) / mc, -1.f, 1.f); }
+      else { x2 = e == 2 ? 1.f : -1.f; x1 = jh_clampf((u - x2 * mb) / ma, -1.f, 1.f); }
+      const float v1[3] = {p1[0] + a1[0] * x1, p1[1] + a1[1] * x1, p1[2] + a1[2] * x1}, v2[3] = {p2[0] + a2[0] * x2, p2[1] + a2[1] * x2, p2[2] + a2[2] * x2};
+      if (nfound < 2 && sphere_sphere(v1, v2)) nfound++;
+    }
+  }
+}
+
 // ---- a cylinder (radius r, half length L along the local z of Rc) against the robot's geoms: the spot_tire object (csrc/jh_engine_v4.hip, k_tree_v4<SELF, true, true>)
 
 // sphere against cylinder (MuJoCo's primitive mjc_SphereCylinder, as the oracle restates it in collide_cylinder_sphere): the closest point of the solid cylinder to the
@@ -359,15 +398,18 @@ __device__ __forceinline__ void collide_cylinder_sphere(Sink& sk, const float* p
 // triangulation of V vertices has 2V - 4), each expansion O(faces).  The polytope lives in the lane's private memory (about 2.6 KB, scratch), not in LDS.  It stops when
 // the closest face is a supporting plane within CVX_TOL = 1e-6 (m); a curved contact that needs more than 36 expansions keeps the closest face found so far, whose
 // depth is then below the true one by less than the last expansion's growth.  Where the closest feature is not unique (parallel faces or edges) the witness points --
-// and so the position -- may differ from the oracle's within that feature; depth and normal do not.
+// and so the position -- may differ from the oracle's within that feature; the depth does not (measured within 1.3e-6 m of the oracle's).  The normal of a CURVED contact
+// does: a supporting plane within the stop of a face of radius r may be tilted by sqrt(2 CVX_TOL / r), about 1e-2 at r = 20 mm (measured: up to 9.1e-3,
+// profiles/narrow_phase_pairs.md); along the reported normal the shapes overlap by the reported depth to within the stop, which is what the solver needs.
 constexpr int CVX_MAXV = 40, CVX_MAXF = 2 * CVX_MAXV, CVX_GJK_IT = 48;
 constexpr float CVX_TOL = 1e-6f;
+constexpr int CVX_STOP_NM = 1000;  // the stop of the leap cylinder build's GJK + EPA in nanometres (1 000 = CVX_TOL, the tree kernel's); profiles/caltech_cylinder.md has 1 000 against 100
 struct CvxShape { int type; float s0, s1, s2; float p[3], R[9]; };
-// REORTHO (the leap kernel's cylinder build; the tree kernel's instantiations leave it off and compile to the code they had): the part of d across a cylinder's axis is
-// made orthogonal to the axis a second time.  For d within about 1e-5 rad of the axis that part is the rounding residue of d - (d . ax) ax, which is not orthogonal to
+// The part of d across a cylinder's axis is made orthogonal to the axis a SECOND time.  For d within about 1e-5 rad of the axis that part is the rounding residue of d - (d . ax) ax, which is not orthogonal to
 // the axis; scaled to the radius it puts the "support point" up to a quarter of a millimetre above the cap of a 14 mm cylinder, outside the shape, and the polytope
 // built on it misses a minimum translation that runs along the axis (a cap contact).  A rim point in whatever direction the residue has is a valid support point.
-template <bool REORTHO = false>
+// (This was a template switch that only the leap kernel's cylinder build turned on; the tree kernel ran without it until the routine was tested alone: against the 0.33 m tire it reported contacts up to 8 mm deeper than the shapes overlap,
+// profiles/narrow_phase_pairs.md; EPA's face normals converge onto the cap's, so directions that close to the axis are the rule there.)
 __device__ __forceinline__ void cvx_support(const CvxShape& s, const float* d, float* out) {
   out[0] = s.p[0]; out[1] = s.p[1]; out[2] = s.p[2];
   if (s.type == 6) {
@@ -383,17 +425,16 @@ __device__ __forceinline__ void cvx_support(const CvxShape& s, const float* d, f
     out[0] = fmaf(ax[0], e, out[0]); out[1] = fmaf(ax[1], e, out[1]); out[2] = fmaf(ax[2], e, out[2]);
     float r[3] = {d[0], d[1], d[2]};
     if (s.type == 5) { r[0] -= da * ax[0]; r[1] -= da * ax[1]; r[2] -= da * ax[2]; }
-    if constexpr (REORTHO) { if (s.type == 5) { const float db = dot3(r, ax); r[0] -= db * ax[0]; r[1] -= db * ax[1]; r[2] -= db * ax[2]; } }
+    if (s.type == 5) { const float db = dot3(r, ax); r[0] -= db * ax[0]; r[1] -= db * ax[1]; r[2] -= db * ax[2]; }
     const float l = sqrtf(dot3(r, r));
     if (l > 1e-7f * (fabsf(da) + l)) { const float k = s.s0 / l; out[0] = fmaf(r[0], k, out[0]); out[1] = fmaf(r[1], k, out[1]); out[2] = fmaf(r[2], k, out[2]); }
   }
 }
 struct CvxVert { float w[3], a[3]; };  // w = a - b on the Minkowski difference A - B; a the support point of A (b follows)
-template <bool REORTHO = false>
 __device__ __forceinline__ void cvx_vertex(const CvxShape& A, const CvxShape& B, const float* d, CvxVert& v) {
   const float nd[3] = {-d[0], -d[1], -d[2]};
   float b[3];
-  cvx_support<REORTHO>(A, d, v.a); cvx_support<REORTHO>(B, nd, b);
+  cvx_support(A, d, v.a); cvx_support(B, nd, b);
   v.w[0] = v.a[0] - b[0]; v.w[1] = v.a[1] - b[1]; v.w[2] = v.a[2] - b[2];
 }
 struct CvxFace { float n[3], dist; int v; };  // v: vertex indices 0-7 / 8-15 / 16-23, bit 31 dead
@@ -409,12 +450,11 @@ __device__ __forceinline__ bool cvx_face(const CvxVert* V, int i, int j, int k, 
   return true;
 }
 // GJK on A - B, overlap only (the oracle's ccd_gjk): true with four vertices around the origin in sx[0..3]
-template <bool REORTHO = false>
 __device__ __forceinline__ bool cvx_gjk(const CvxShape& A, const CvxShape& B, CvxVert* sx) {
   float d[3] = {B.p[0] - A.p[0], B.p[1] - A.p[1], B.p[2] - A.p[2]};
   if (dot3(d, d) < 1e-20f) { d[0] = 1.f; d[1] = 0.f; d[2] = 0.f; }
   int n = 1;
-  cvx_vertex<REORTHO>(A, B, d, sx[0]);
+  cvx_vertex(A, B, d, sx[0]);
   d[0] = -sx[0].w[0]; d[1] = -sx[0].w[1]; d[2] = -sx[0].w[2];
   for (int it = 0; it < CVX_GJK_IT; it++) {
     if (dot3(d, d) < 1e-24f) {  // the origin lies on the simplex: any direction that grows it
@@ -426,7 +466,7 @@ __device__ __forceinline__ bool cvx_gjk(const CvxShape& A, const CvxShape& B, Cv
       }
       d[0] = e[0]; d[1] = e[1]; d[2] = e[2];
     }
-    CvxVert nv; cvx_vertex<REORTHO>(A, B, d, nv);
+    CvxVert nv; cvx_vertex(A, B, d, nv);
     if (dot3(nv.w, d) < 0.f) return false;  // the new support point did not pass the origin: separated
     sx[3] = sx[2]; sx[2] = sx[1]; sx[1] = sx[0]; sx[0] = nv; n++;
     const float* a = sx[0].w; const float* b = sx[1].w;
@@ -465,13 +505,13 @@ __device__ __forceinline__ bool cvx_gjk(const CvxShape& A, const CvxShape& B, Cv
 }
 // geom A (capsule / box) against geom B (the cylinder): at most one contact, normal from A to B.  (Either side may be a box, a capsule or a cylinder: the leap kernel's
 // cylinder build calls it with the cylinder first, MuJoCo's order of a box-cylinder pair, and with two cylinders.)  STOP_NM: the stop in nanometres, CVX_TOL = 1 000 by default.
-template <class Sink, bool REORTHO = false, int STOP_NM = 1000>
+template <class Sink, int STOP_NM = 1000>
 __device__ __noinline__ void collide_convex_cylinder(Sink& sk, const CvxShape& A, const CvxShape& B) {
   constexpr float STOP = STOP_NM == 1000 ? CVX_TOL : 1e-9f * (float)STOP_NM;
   CvxVert V[CVX_MAXV];
   CvxFace F[CVX_MAXF];
   int ed[CVX_MAXF];
-  if (!cvx_gjk<REORTHO>(A, B, V)) return;
+  if (!cvx_gjk(A, B, V)) return;
   int nv = 4, nf = 0;
   {
     const int idx[4][3] = {{0, 1, 2}, {0, 2, 3}, {0, 3, 1}, {1, 3, 2}};
@@ -490,7 +530,7 @@ __device__ __noinline__ void collide_convex_cylinder(Sink& sk, const CvxShape& A
     best = -1;
     for (int f = 0; f < nf; f++) if (F[f].v >= 0 && (best < 0 || F[f].dist < F[best].dist)) best = f;
     if (best < 0) return;
-    CvxVert nw; cvx_vertex<REORTHO>(A, B, F[best].n, nw);
+    CvxVert nw; cvx_vertex(A, B, F[best].n, nw);
     if (dot3(nw.w, F[best].n) - F[best].dist < STOP || nv >= CVX_MAXV) break;
     int ne = 0;  // the faces the new point sees go; their unshared edges form the horizon
     for (int f = 0; f < nf; f++) {

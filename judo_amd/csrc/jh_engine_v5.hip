@@ -81,7 +81,6 @@ constexpr int RSPAD = 4;            // floats behind an RS record (see its last 
 constexpr int C3PAD = 278;          // floats in front of the c3 cache inside the pool's storage (see RS)
 constexpr int NSLDS = 3;            // slots per lane whose contacts the LDS pool holds
 constexpr double BIGPROB = 0.999999;  // how sure the compiler may be that a wave-step stays on the NSLOT copy (block frequencies steer the placement of register spills)
-constexpr int CVX_STOP_NM = 1000;   // the stop of the cylinder build's GJK + EPA in nanometres (jh_coop.h: 1 000 = CVX_TOL, the tree kernel's); profiles/caltech_cylinder.md has 1 000 against 100
 // Waves of a workgroup never exchange data after the image is staged: inside the step loop a "barrier" only has to order one wave's own LDS traffic
 // (a wave's LDS instructions execute in issue order), so it is a compiler fence, not an s_barrier -- rollouts in different waves never wait for each other.
 // OPAQUE(x): the compiler forgets what it knows about x, so nothing derived from it is hoisted out of the enclosing loop.  Used on the contact slots at the top of
@@ -1115,7 +1114,7 @@ __global__ __launch_bounds__(WAVE * WPB, WAVES_PER_EU) void k_leap_v5(const floa
               for (int k = 0; k < 3; k++) { X.p[k] = swap ? pB[k] : pA[k]; Y.p[k] = swap ? pA[k] : pB[k]; }
               for (int k = 0; k < 9; k++) { X.R[k] = swap ? RB[k] : RA[k]; Y.R[k] = swap ? RA[k] : RB[k]; }
               CvxOne one{{0.f, 0.f, 0.f}, {0.f, 0.f, 0.f}, 0.f, false};
-              collide_convex_cylinder<CvxOne, true, CVX_STOP_NM>(one, X, Y);
+              collide_convex_cylinder<CvxOne, CVX_STOP_NM>(one, X, Y);
               if (one.hit) { sk.flip = swap; sk.push(one.pos, one.n, one.dist); }
             }
           } else

@@ -370,46 +370,7 @@ __device__ __forceinline__ void rodrigues(float* Rq, const float* al, float sn, 
   Rq[6] = t * x * z - sn * y; Rq[7] = t * y * z + sn * x; Rq[8] = t * z * z + cs;
 }
 
-#if JH_V6_SELF
-// capsule against capsule (MuJoCo's mjc_CapsuleCapsule as oracle/jo_engine.c::collide_capsule_capsule restates it; jh_engine_v4.hip has the same routine for the Spot robot
-// against itself, inside its kernel -- restated here so that the tree kernel compiles to the code it had): the closest points of the two axis segments, then sphere against
-// sphere there; parallel axes: the ends of either capsule against the other's segment, at most two contacts.  Normal from the first capsule to the second.
-template <class Sink>
-__device__ __forceinline__ void collide_capsule_capsule(Sink& sk, const float* p1, const float* R1, float r1, float L1, const float* p2, const float* R2, float r2, float L2) {
-  auto sphere_sphere = [&](const float* ca, const float* cb) __attribute__((always_inline)) {
-    const float d[3] = {cb[0] - ca[0], cb[1] - ca[1], cb[2] - ca[2]}; const float ln = sqrtf(dot3(d, d)), dist = ln - r1 - r2;
-    if (dist > 0.f) return false;
-    const bool same = ln < 1e-12f;  // coincident centres: mju_normalize3 returns (1, 0, 0)
-    const float n3[3] = {same ? 1.f : d[0] / ln, same ? 0.f : d[1] / ln, same ? 0.f : d[2] / ln}, mm = r1 + 0.5f * dist;
-    const float ps[3] = {ca[0] + mm * n3[0], ca[1] + mm * n3[1], ca[2] + mm * n3[2]};
-    sk.push(ps, n3, dist);
-    return true;
-  };
-  float a1[3], a2[3]; col3(a1, R1, 2); col3(a2, R2, 2);
-  for (int i = 0; i < 3; i++) { a1[i] *= L1; a2[i] *= L2; }
-  const float dif[3] = {p1[0] - p2[0], p1[1] - p2[1], p1[2] - p2[2]};
-  const float ma = dot3(a1, a1), mb = -dot3(a1, a2), mc = dot3(a2, a2), u = -dot3(a1, dif), v = dot3(a2, dif);
-  const float det = ma * mc - mb * mb;
-  if (fabsf(det) >= 1e-6f * ma * mc) {  // (MuJoCo: |det| >= mjMINVAL in fp64; in fp32 the determinant of two axes less than ~1e-3 rad apart is rounding noise)
-    float x1 = (mc * u - mb * v) / det, x2 = (ma * v - mb * u) / det;
-    if (x1 > 1.f) { x1 = 1.f; x2 = (v - mb) / mc; } else if (x1 < -1.f) { x1 = -1.f; x2 = (v + mb) / mc; }
-    if (x2 > 1.f) { x2 = 1.f; x1 = jh_clampf((u - mb) / ma, -1.f, 1.f); }
-    else if (x2 < -1.f) { x2 = -1.f; x1 = jh_clampf((u + mb) / ma, -1.f, 1.f); }
-    const float v1[3] = {p1[0] + a1[0] * x1, p1[1] + a1[1] * x1, p1[2] + a1[2] * x1}, v2[3] = {p2[0] + a2[0] * x2, p2[1] + a2[1] * x2, p2[2] + a2[2] * x2};
-    sphere_sphere(v1, v2);
-  } else {
-    int nfound = 0;
-#pragma unroll 1
-    for (int e = 0; e < 4; e++) {
-      float x1, x2;
-      if (e < 2) { x1 = e == 0 ? 1.f : -1.f; x2 = jh_clampf((v - x1 * mb) / mc, -1.f, 1.f); }
-      else { x2 = e == 2 ? 1.f : -1.f; x1 = jh_clampf((u - x2 * mb) / ma, -1.f, 1.f); }
-      const float v1[3] = {p1[0] + a1[0] * x1, p1[1] + a1[1] * x1, p1[2] + a1[2] * x1}, v2[3] = {p2[0] + a2[0] * x2, p2[1] + a2[1] * x2, p2[2] + a2[2] * x2};
-      if (nfound < 2 && sphere_sphere(v1, v2)) nfound++;
-    }
-  }
-}
-#endif
+// (capsule against capsule, the self-collision build's link-against-link routine: jh_coop.h collide_capsule_capsule)
 
 // world pose of collision geom g (all fr3 collision geoms are boxes); body -1 = static (pose stored in world coordinates)
 __device__ __forceinline__ void geom_pose3(const RS6& S, const float* gf, int body, float* gp, float* gR, bool want_R) {
