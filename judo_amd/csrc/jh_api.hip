@@ -156,21 +156,23 @@ extern "C" int jh_register_xcheck(const jh_xcheck_launchers* launchers) {
   return JH_OK;
 }
 
-static bool articulated(const jh_model* m) { return m->kind == JH_TASK_LEAP_CUBE || m->kind == JH_TASK_FR3_PICK; }
-
-// The build that runs a model: the one place that chooses among the rows of jh_internal.h.  The leap family: the cylinder build for an image with cylinders, else the
-// 64-contact build where jh_model_set_contact_capacity asked for it, else the 48-contact one; fr3: the self-collision build for an image with arm pairs, else the default.
-// Null: a closed-form model, or a cross-check generation (g_xcheck).
+// The build that runs a model: the one place that chooses among the rows of jh_internal.h.  The closed-form models: their one row, whatever generation is set on them.
+// The leap family: the cylinder build for an image with cylinders, else the 64-contact build where jh_model_set_contact_capacity asked for it, else the 48-contact one;
+// fr3: the self-collision build for an image with arm pairs, else the default.  Null: a cross-check generation of an articulated model (g_xcheck), and nothing else.
 static const jh_engine_build* engine_build(const jh_model* m) {
+  if (m->kind == JH_TASK_CARTPOLE || m->kind == JH_TASK_CYLINDER_PUSH) return &jh_simple_build;
   if (m->kernel_gen != 3) return nullptr;
   if (m->kind == JH_TASK_LEAP_CUBE) return m->cylinders > 0 ? &jh_engine5_build_cyl : m->contact_capacity > 48 ? &jh_engine5_build_cap64 : &jh_engine5_build;
   if (m->kind == JH_TASK_FR3_PICK) return m->arm_pairs > 0 ? &jh_engine6_build_self : &jh_engine6_build;
   return nullptr;
 }
 
+// A model whose row serves it under every kernel generation: setting one has no effect on it and needs no cross-check library.
+static bool every_generation(const jh_model* m) { return engine_build(m) == &jh_simple_build; }
+
 extern "C" int jh_model_set_kernel(jh_model* m, int generation) {
   JH_REQUIRE(m && generation >= 1 && generation <= 3, "model_set_kernel: generation must be 1, 2 or 3");
-  if (generation != 3 && articulated(m) && !g_xcheck.rollout_cost) {
+  if (generation != 3 && !every_generation(m) && !g_xcheck.rollout_cost) {
     jh_set_error("model_set_kernel: generations 1 and 2 are cross-check kernels of the test build (libjudo_amd_xcheck.so), not part of this library");
     return JH_ERR_UNSUPPORTED;
   }
@@ -186,18 +188,16 @@ extern "C" int jh_model_set_kernel(jh_model* m, int generation) {
   return JH_OK;
 }
 
-// trace sensors the fused kernel can write per rollout and step: first sensor address, number of floats (0: none -- the elites are re-rolled in materialise mode instead)
-static void trace_layout(const jh_model* m, int* adr, int* nfl, int* colmajor) {
-  *adr = 0; *nfl = 0; *colmajor = 0;
-  if (m->kind == JH_TASK_CARTPOLE || m->kind == JH_TASK_CYLINDER_PUSH) { *nfl = 6; *colmajor = 1; return; }  // both models' six sensors are their two trace sites; one lane per rollout: column-major
-  if (m->kernel_gen != 3) return;
-  if (m->kind == JH_TASK_LEAP_CUBE && m->ns == 31) { *adr = 16; *nfl = 15; }   // trace_cube, trace_{if,mf,rf,th}_tip (leap_cube.xml: the five framepos sensors)
-  else if (m->kind == JH_TASK_FR3_PICK) { *adr = 8; *nfl = 6; }               // trace_object, trace_grasp_site
+// trace sensors the model's fused kernel can write per rollout and step: its row's answer, and none for a cross-check generation
+static jh_trace_layout trace_layout(const jh_model* m) {
+  const jh_engine_build* eb = engine_build(m);
+  return eb && eb->trace_layout ? eb->trace_layout(m) : jh_trace_layout{};
 }
 
 extern "C" int jh_model_trace_layout(const jh_model* m, int* out) {
   JH_REQUIRE(m && out, "model_trace_layout: null pointer");
-  trace_layout(m, out, out + 1, out + 2);
+  const jh_trace_layout t = trace_layout(m);
+  out[0] = t.adr; out[1] = t.floats; out[2] = t.colmajor;
   return JH_OK;
 }
 
@@ -247,13 +247,14 @@ int jh_latency_shift(int N, int rpw) {
 }
 
 static int max_fused_knots(const jh_model* m, int H) {
-  const bool coop = m->kernel_gen >= 2 && (m->kind == JH_TASK_LEAP_CUBE || m->kind == JH_TASK_FR3_PICK);
-  int k = JH_MAX_KNOT_DIM / (m->nu > 0 ? m->nu : 1);
-  if (coop && m->kind == JH_TASK_LEAP_CUBE && m->kernel_gen >= 3) return k;  // generation 3 reads its knots from memory every step: no on-chip staging, no limit of its own
-  if (coop) return k < 8 ? k : 8;
-  // the one-lane kernels stage W (H x K) and 64 lanes' knots in LDS: the launcher's 64 KiB budget bounds K as well
-  const int lds_k = (m->kind == JH_TASK_CARTPOLE || m->kind == JH_TASK_CYLINDER_PUSH) ? jh_simple_max_knots(m, H) : (g_xcheck.max_knots ? g_xcheck.max_knots(m, H) : 0);
-  return k < lds_k ? k : lds_k;
+  const int k = JH_MAX_KNOT_DIM / (m->nu > 0 ? m->nu : 1);
+  const jh_engine_build* eb = engine_build(m);
+  int own = k;  // the build's own bound, where it has one
+  if (eb && eb->max_fused_knots) own = eb->max_fused_knots(m, H);
+  // the cross-check generations: the cooperative one keeps 8 knots per actuator in registers; the one-lane kernel stages W (H x K) and 64 lanes' knots in LDS, and the
+  // launcher's 64 KiB budget bounds K as well
+  if (!eb) own = m->kernel_gen >= 2 ? 8 : (g_xcheck.max_knots ? g_xcheck.max_knots(m, H) : 0);
+  return k < own ? k : own;
 }
 
 extern "C" int jh_model_limits(const jh_model* m, int* out) {
@@ -262,7 +263,7 @@ extern "C" int jh_model_limits(const jh_model* m, int* out) {
   out[1] = JH_MAX_KNOT_DIM;
   out[2] = JH_MAX_ELITES;
   const jh_engine_build* eb = engine_build(m);
-  out[3] = eb ? eb->contact_capacity : (articulated(m) ? 32 : 0);  // (generation 3: leap 48, all in LDS, or 64 with 16 in a row of global memory: jh_model_set_contact_capacity; fr3 32 in LDS + 64 in such a row, next to its 96 pad-against-pad slots; the cross-check generations: 32)
+  out[3] = eb ? eb->contact_capacity : 32;  // (generation 3: leap 48, all in LDS, or 64 with 16 in a row of global memory: jh_model_set_contact_capacity; fr3 32 in LDS + 64 in such a row, next to its 96 pad-against-pad slots; the closed-form models: 0; the cross-check generations: 32)
   return JH_OK;
 }
 
@@ -273,13 +274,15 @@ extern "C" int jh_model_max_fused_knots(const jh_model* m, int H) {
 
 extern "C" int jh_model_one_launch_max_knots(const jh_model* m, int H) {
   JH_REQUIRE(m != nullptr && H >= 1, "model_one_launch_max_knots: null model or H < 1");
-  const int k = JH_MAX_KNOT_DIM / (m->nu > 0 ? m->nu : 1), lds_k = jh_simple_one_launch_max_knots(m, H);
+  const jh_engine_build* eb = engine_build(m);
+  const int k = JH_MAX_KNOT_DIM / (m->nu > 0 ? m->nu : 1), lds_k = eb && eb->plan_step ? eb->one_launch_max_knots(m, H) : 0;
   return k < lds_k ? k : lds_k;
 }
 
 extern "C" int jh_model_set_plan_step_launches(jh_model* m, int launches) {
   JH_REQUIRE(m != nullptr && launches >= 0 && launches <= 2, "model_set_plan_step_launches: launches must be 0 (automatic), 1 or 2");
-  JH_REQUIRE(launches != 1 || m->kind == JH_TASK_CARTPOLE || m->kind == JH_TASK_CYLINDER_PUSH, "model_set_plan_step_launches: only the closed-form models have a one-launch plan step");
+  const jh_engine_build* eb = engine_build(m);
+  JH_REQUIRE(launches != 1 || (eb && eb->plan_step), "model_set_plan_step_launches: only the closed-form models have a one-launch plan step");
   m->plan_step_launches = launches;
   return JH_OK;
 }
@@ -431,16 +434,15 @@ extern "C" int jh_model_profile(jh_model* m, long long* out /* 10 phase cycle to
   return JH_OK;
 }
 
-// One fused launch on the record: the argument checks, then the model's build (or the closed-form kernels, or the cross-check library).
+// One fused launch on the record: the argument checks, then the model's build, else the cross-check library.
 static int rollout_cost(const jh_model* m, const jh_rollout_args& a, void* stream) {
   JH_REQUIRE(m && a.x0 && a.nominal && a.noise && a.sigma && a.W && a.lohi && a.tp && a.costs, "rollout_cost: null pointer");
-  if (a.trace) { int adr, nfl, cm; trace_layout(m, &adr, &nfl, &cm); JH_REQUIRE(nfl > 0, "rollout_cost_traced: this model's fused kernel writes no trace sensors (jh_model_trace_layout)"); }
+  if (a.trace) JH_REQUIRE(trace_layout(m).floats > 0, "rollout_cost_traced: this model's fused kernel writes no trace sensors (jh_model_trace_layout)");
   JH_REQUIRE(a.N > 0 && a.H > 0 && a.K >= 1, "rollout_cost: N, H, K must be positive (N=%d H=%d K=%d)", a.N, a.H, a.K);
   JH_REQUIRE(a.ldn >= a.N, "rollout_cost: ldn (%d) < N (%d)", a.ldn, a.N);
   JH_REQUIRE(a.K * m->nu <= JH_MAX_KNOT_DIM, "rollout_cost: K*nu = %d exceeds %d", a.K * m->nu, JH_MAX_KNOT_DIM);
   JH_REQUIRE(a.n_offset >= 0, "rollout_cost: negative n_offset");
   hipStream_t st = (hipStream_t)stream;
-  if (m->kind == JH_TASK_CARTPOLE || m->kind == JH_TASK_CYLINDER_PUSH) return jh_simple_rollout_cost(m, a, st);
   if (const jh_engine_build* eb = engine_build(m)) return eb->rollout_cost(m, a, st);
   JH_REQUIRE(a.trace == nullptr, "rollout_cost_traced: only the product kernels (generation 3, cartpole, cylinder_push) write trace sensors");
   if (!g_xcheck.rollout_cost) { jh_set_error("rollout_cost: no kernel for this model / generation in this library"); return JH_ERR_UNSUPPORTED; }
@@ -466,8 +468,9 @@ extern "C" int jh_rollout_cost(const jh_model* m, const float* x0, const float* 
 // Forced one launch where it cannot run (knots_out requested, or K above the limit) is an error, not a quiet switch.
 static int plan_step_launches(const jh_model* m, int N, int H, int K, const float* costs, const float* knots_out, const float* W, const float* noise, int ldn, bool* one) {
   *one = false;
-  if (m->plan_step_launches == 2 || !(m->kind == JH_TASK_CARTPOLE || m->kind == JH_TASK_CYLINDER_PUSH)) return JH_OK;
-  const bool fits = costs && W && noise && N > 0 && H > 0 && K >= 1 && ldn >= N && K * m->nu <= JH_MAX_KNOT_DIM && jh_simple_plan_step_fits(m, H, K);
+  const jh_engine_build* eb = engine_build(m);
+  if (m->plan_step_launches == 2 || !(eb && eb->plan_step)) return JH_OK;
+  const bool fits = costs && W && noise && N > 0 && H > 0 && K >= 1 && ldn >= N && K * m->nu <= JH_MAX_KNOT_DIM && K <= eb->one_launch_max_knots(m, H);
   if (m->plan_step_launches == 1) {
     JH_REQUIRE(!knots_out, "plan_step: the one-launch plan step writes no candidate knots (knots_out), and one launch is forced (jh_model_set_plan_step_launches)");
     JH_REQUIRE(fits, "plan_step: one launch is forced but K = %d exceeds its LDS staging at H = %d (jh_model_one_launch_max_knots)", K, H);
@@ -477,26 +480,45 @@ static int plan_step_launches(const jh_model* m, int N, int H, int K, const floa
   return JH_OK;
 }
 
+// What every plan step does around its launches, written once.
+// The completion mark: `out_host_mark` other than `out` (and not null) is a 4-byte word in device-visible pinned host memory -- the update's last workgroup stores its old
+// value + 1 there behind the results, and jh_download_end polls it; out_host_mark == out (or null): the stream's event alone.
+struct jh_step_mark { unsigned* flag; unsigned expect; };
+static jh_step_mark step_mark(void* out_host_mark, const float* out) {
+  unsigned* flag = (out_host_mark && out_host_mark != (const void*)out) ? (unsigned*)out_host_mark : nullptr;
+  return {flag, flag ? __atomic_load_n(flag, __ATOMIC_RELAXED) + 1u : 0u};
+}
+// The front: the packed block(s) go up -- unless blk_dev == blk_host, a device-visible pinned host block the kernels read in place (the closed-form models: a few hundred
+// bytes read once per workgroup cost less than the copy in front of the launch) --, then timing[0].
+static int step_begin(void* blk_dev, const void* blk_host, size_t bytes, void* const* timing, void* stream) {
+  if (blk_dev != blk_host) { if (int rc = jh_upload_async(blk_dev, blk_host, bytes, stream)) return rc; }
+  if (timing) JH_HIP(hipEventRecord((hipEvent_t)timing[0], (hipStream_t)stream));
+  return JH_OK;
+}
+// The end, if the launches went out (`rc`): timing[2], then the mark behind `out` (null: the shard form, which has none).
+static int step_end(int rc, float* out, const jh_step_mark& mk, void* const* timing, void* stream) {
+  if (rc == JH_OK && timing) JH_HIP(hipEventRecord((hipEvent_t)timing[2], (hipStream_t)stream));
+  if (rc == JH_OK && out) rc = download_begin(out, out, 0, stream, mk.flag, mk.expect);
+  return rc;
+}
+
 // One plan-step iteration as ONE call (Controller.update_action's loop body, judo/controller/controller.py:250-299): the packed host block x0 | nominal | sigma |
 // task params | bounds goes up, the fused rollout + cost kernel runs, and the update's tail reduces the costs.  Everything is enqueued on `stream`; nothing is waited for
 // here.  Five ctypes calls less per plan step than the separate entry points: a tenth of a small one.  The tail writes one of two destinations:
 //  - `out` (jh_plan_step): nominal | sigma | trace records, normally the pinned host block itself, then the completion mark of jh_download_begin, which
-//    jh_download_end waits for.  `flag` non-null: a 4-byte word in device-visible pinned host memory -- the update's last workgroup stores its old value + 1 there
-//    behind the results and jh_download_end polls it instead of waiting for the stream's event;
+//    jh_download_end waits for (`out_host_mark`: step_mark above);
 //  - `rec_out` (jh_plan_step_shard): this rank's RECORD (jh_update_shard's) instead of the nominal, and no mark: the caller all-gathers the G records and
 //    jh_plan_merge finishes the update.
 static int plan_step(const char* who, const jh_model* m, void* blk_dev, const void* blk_host, size_t blk_bytes, int o_nominal, int o_sigma, int o_tp, int o_lohi,
                      const float* noise, int ldn, const float* W, int phase, int N, int n_offset, int H, int K, float* costs, float* knots_out, float* trace, int mode,
-                     float lambda, int k, int tie_high, int E, int row_floats, int colmajor, float* scratch, float* out, unsigned* flag, float* rec_out,
+                     float lambda, int k, int tie_high, int E, int row_floats, int colmajor, float* scratch, float* out, void* out_host_mark, float* rec_out,
                      void* const* timing, void* stream) {
   JH_REQUIRE(m && blk_dev && blk_host && (out || rec_out) && scratch, "%s: null pointer", who);
   const float* b = (const float*)blk_dev;
   hipStream_t st = (hipStream_t)stream;
-  // blk_dev == blk_host: a device-visible pinned host block the kernels read in place (the closed-form models: a few hundred bytes read once per workgroup cost less than the copy in front of the launch)
-  int rc = blk_dev == blk_host ? JH_OK : jh_upload_async(blk_dev, blk_host, blk_bytes, stream);
-  if (rc == JH_OK && timing) JH_HIP(hipEventRecord((hipEvent_t)timing[0], st));
+  int rc = step_begin(blk_dev, blk_host, blk_bytes, timing, stream);
   const int KU = K * m->nu;
-  const unsigned expect = flag ? __atomic_load_n(flag, __ATOMIC_RELAXED) + 1u : 0u;
+  const jh_step_mark mk = step_mark(out_host_mark, out);
   bool one = false;
   if (rc == JH_OK) rc = plan_step_launches(m, N, H, K, costs, knots_out, W, noise, ldn, &one);
   // two launches: the rollout kernel, then k_update_tail; one (closed-form models): rollout + cost + the update's tail in jh_simple.hip's k_plan_step, where the
@@ -508,21 +530,18 @@ static int plan_step(const char* who, const jh_model* m, void* blk_dev, const vo
   if (rc == JH_OK)
     rc = jh_update_tail_args(who, costs, nullptr, b + o_nominal, noise, ldn, b + o_sigma, b + o_lohi, N, n_offset, K, m->nu, mode, lambda, k, tie_high, trace ? E : 0, trace, row_floats,
                              colmajor, scratch, out, out ? out + KU : nullptr, (out && trace && E > 0) ? out + 2 * KU : nullptr, rec_out, &a);
-  a.done_flag = flag; a.done_value = expect;
-  if (rc == JH_OK) rc = one ? jh_simple_plan_step(m, b, W, b + o_tp, H, K, a, st) : jh_update_tail_launch(a, st);
+  a.done_flag = mk.flag; a.done_value = mk.expect;
+  if (rc == JH_OK) rc = one ? engine_build(m)->plan_step(m, b, W, b + o_tp, H, K, a, st) : jh_update_tail_launch(a, st);
   if (rc == JH_OK && one && timing) JH_HIP(hipEventRecord((hipEvent_t)timing[1], st));
-  if (rc == JH_OK && timing) JH_HIP(hipEventRecord((hipEvent_t)timing[2], st));
-  if (rc == JH_OK && out) rc = download_begin(out, out, 0, stream, flag, expect);
-  return rc;
+  return step_end(rc, out, mk, timing, stream);
 }
 
 extern "C" int jh_plan_step(const jh_model* m, void* blk_dev, const void* blk_host, size_t blk_bytes, int o_nominal, int o_sigma, int o_tp, int o_lohi, const float* noise, int ldn,
                             const float* W, int phase, int N, int n_offset, int H, int K, float* costs, float* knots_out, float* trace, int mode, float lambda, int k, int tie_high, int E,
                             int row_floats, int colmajor, float* scratch, float* out, void* out_host_mark, void* const* timing /* 3 events of jh_event_create, or NULL */, void* stream) {
   JH_REQUIRE(out, "plan_step: null pointer");
-  unsigned* flag = (out_host_mark && out_host_mark != (void*)out) ? (unsigned*)out_host_mark : nullptr;  // (out_host_mark == out: the stream's event)
   return plan_step("plan_step", m, blk_dev, blk_host, blk_bytes, o_nominal, o_sigma, o_tp, o_lohi, noise, ldn, W, phase, N, n_offset, H, K, costs, knots_out, trace, mode, lambda, k,
-                   tie_high, E, row_floats, colmajor, scratch, out, flag, nullptr, timing, stream);
+                   tie_high, E, row_floats, colmajor, scratch, out, out_host_mark, nullptr, timing, stream);
 }
 
 // The B phase words of a batched fr3_pick call (`what`: whose, for the message), on the host, before anything is enqueued: the kernel converts the word and branches on it.
@@ -560,72 +579,75 @@ static int check_block_shape(const char* who, const jh_model* m, const jh_block_
 // reach its buffers through strides, and one completion mark stands behind all of them.  Problem 0's launch record is built by the single call's own checks
 // (jh_update_tail_args); the kernels derive problem b's from it.  `images` / `image_stride`: the float section the rollout kernels read for problem 0 and the floats to
 // problem b + 1's from problem b's -- m->d_f and 0 for jh_plan_step_batch, a model set's buffer and stride for jh_plan_step_batch_models: one code path.  `ints`: the int
-// section the leap kernel reads -- m->d_i, or a model set's copy without pair tables.
-static int plan_step_batch(const char* who, const jh_model* m, const float* images, long long image_stride, const int* ints, int B, void* blk_dev, const void* blk_host, size_t blk_bytes, size_t blk_stride_bytes,
-                           int o_nominal, int o_sigma, int o_tp, int o_lohi, int o_phase, const float* noise, int ldn, size_t noise_stride_floats, const float* W, int N, int H, int K, float* costs,
-                           float* trace, int mode, float lambda, int k, int tie_high, int E, int row_floats, int colmajor, float* scratch, float* out, size_t out_stride_floats,
-                           void* out_host_mark, void* const* timing, void* stream) {
-  JH_REQUIRE(m && blk_dev && blk_host && out && scratch && noise && W && costs, "%s: null pointer", who);
-  // o_phase: the float offset of every block's phase word (jh_plan_step_batch_phases, fr3_pick alone), or -1: an entry without one, which keeps refusing fr3_pick
-  if (m->kind == JH_TASK_FR3_PICK && o_phase < 0) { jh_set_error("%s: fr3_pick has no batched plan step (its phase is chosen per problem on the host) behind this entry: jh_plan_step_batch_phases takes a phase word per problem, jh_plan_step_batch_phases_models a set of fr3_pick models as well", who); return JH_ERR_UNSUPPORTED; }
-  if (m->kind != JH_TASK_FR3_PICK && o_phase >= 0) { jh_set_error("%s: a phase word per problem is fr3_pick's alone; jh_plan_step_batch plans this model", who); return JH_ERR_UNSUPPORTED; }
+// section the leap kernel reads -- m->d_i, or a model set's copy without pair tables.  The record is jh_set_step's sibling (below): what the four entries share.
+struct jh_batch_step {
+  const char* who; const jh_model* m; const float* images; long long image_stride; const int* ints; int B;
+  void* blk_dev; const void* blk_host; jh_block_shape shape; const float *noise, *W;  // the B blocks (blk_dev == blk_host: read in place, as jh_plan_step), their shape and strides, noise and spline weights
+  float *costs, *trace; int mode; float lambda; int k, tie_high, E, row_floats, colmajor;  // the update and its trace records
+  float *scratch, *out; size_t out_stride_floats; void* out_host_mark; void* const* timing; void* stream;
+  int o_phase = -1;  // the float offset of every block's phase word (jh_plan_step_batch_phases, fr3_pick alone), or -1: an entry without one, which keeps refusing fr3_pick
+};
+
+static int plan_step_batch(const jh_batch_step& r) {
+  const char* who = r.who;
+  const jh_model* m = r.m;
+  const jh_block_shape& d = r.shape;
+  const int B = r.B, N = d.N, H = d.H, K = d.K;
+  JH_REQUIRE(m && r.blk_dev && r.blk_host && r.out && r.scratch && r.noise && r.W && r.costs, "%s: null pointer", who);
+  if (m->kind == JH_TASK_FR3_PICK && r.o_phase < 0) { jh_set_error("%s: fr3_pick has no batched plan step (its phase is chosen per problem on the host) behind this entry: jh_plan_step_batch_phases takes a phase word per problem, jh_plan_step_batch_phases_models a set of fr3_pick models as well", who); return JH_ERR_UNSUPPORTED; }
+  if (m->kind != JH_TASK_FR3_PICK && r.o_phase >= 0) { jh_set_error("%s: a phase word per problem is fr3_pick's alone; jh_plan_step_batch plans this model", who); return JH_ERR_UNSUPPORTED; }
   if (m->kind == JH_TASK_LEAP_CUBE && m->kernel_gen != 3) { jh_set_error("%s: only kernel generation 3 of the leap family has a batched launch (this model runs %d)", who, m->kernel_gen); return JH_ERR_UNSUPPORTED; }
   JH_REQUIRE(B >= 1, "%s: B must be at least 1 (B=%d)", who, B);
   JH_REQUIRE(B <= 65535, "%s: B = %d exceeds the 65535 problems of a launch (the grid's second dimension)", who, B);
-  JH_REQUIRE(o_phase < 0 || K <= 8, "%s: the cooperative arm kernel keeps at most 8 knots per actuator in registers (K=%d)", who, K);
-  if (int rc = check_block_shape(who, m, {blk_bytes, o_nominal, o_sigma, o_tp, o_lohi, ldn, N, H, K, true, blk_stride_bytes, noise_stride_floats})) return rc;
+  JH_REQUIRE(r.o_phase < 0 || K <= 8, "%s: the cooperative arm kernel keeps at most 8 knots per actuator in registers (K=%d)", who, K);
+  if (int rc = check_block_shape(who, m, d)) return rc;
   const int KU = K * m->nu;
-  int t_adr = 0, t_nfl = 0, t_cm = 0;
-  if (trace) { trace_layout(m, &t_adr, &t_nfl, &t_cm); JH_REQUIRE(t_nfl > 0 && row_floats == H * t_nfl, "%s: row_floats = %d is not H x the model's %d trace floats per step (jh_model_trace_layout)", who, row_floats, t_nfl); }
-  const int E_t = trace ? E : 0;
-  JH_REQUIRE(E_t >= 0 && E_t <= JH_MAX_ELITES, "%s: bad trace arguments (E=%d)", who, E);
-  const size_t rec = 2 * (size_t)KU + (size_t)E_t * (2 + (size_t)(E_t > 0 ? row_floats : 0));
-  JH_REQUIRE(out_stride_floats >= rec, "%s: out_stride_floats = %zu is smaller than an output record (nominal | sigma | E trace records = %zu floats)", who, out_stride_floats, rec);
-  const bool closed = m->kind == JH_TASK_CARTPOLE || m->kind == JH_TASK_CYLINDER_PUSH;
+  if (r.trace) { const int t_nfl = trace_layout(m).floats; JH_REQUIRE(t_nfl > 0 && r.row_floats == H * t_nfl, "%s: row_floats = %d is not H x the model's %d trace floats per step (jh_model_trace_layout)", who, r.row_floats, t_nfl); }
+  const int E_t = r.trace ? r.E : 0;
+  JH_REQUIRE(E_t >= 0 && E_t <= JH_MAX_ELITES, "%s: bad trace arguments (E=%d)", who, r.E);
+  const size_t rec = 2 * (size_t)KU + (size_t)E_t * (2 + (size_t)(E_t > 0 ? r.row_floats : 0));
+  JH_REQUIRE(r.out_stride_floats >= rec, "%s: out_stride_floats = %zu is smaller than an output record (nominal | sigma | E trace records = %zu floats)", who, r.out_stride_floats, rec);
   const jh_engine_build* eb = engine_build(m);
-  if (!closed && !(eb && eb->rollout_cost_batch)) { jh_set_error("%s: no batched kernel for this model", who); return JH_ERR_UNSUPPORTED; }
-  if (o_phase >= 0) { if (int rc = phase_words(who, "problem", B, blk_host, blk_bytes, blk_stride_bytes, o_phase)) return rc; }
-  hipStream_t st = (hipStream_t)stream;
-  const float* b = (const float*)blk_dev;
-  if (blk_dev != blk_host) { const int rc = jh_upload_async(blk_dev, blk_host, (size_t)(B - 1) * blk_stride_bytes + blk_bytes, stream); if (rc != JH_OK) return rc; }
-  if (timing) JH_HIP(hipEventRecord((hipEvent_t)timing[0], st));
-  unsigned* flag = (out_host_mark && out_host_mark != (void*)out) ? (unsigned*)out_host_mark : nullptr;  // (out_host_mark == out: the stream's event)
-  const unsigned expect = flag ? __atomic_load_n(flag, __ATOMIC_RELAXED) + 1u : 0u;
+  if (!(eb && eb->rollout_cost_batch)) { jh_set_error("%s: no batched kernel for this model", who); return JH_ERR_UNSUPPORTED; }
+  if (r.o_phase >= 0) { if (int rc = phase_words(who, "problem", B, r.blk_host, d.bytes, d.stride_bytes, r.o_phase)) return rc; }
+  hipStream_t st = (hipStream_t)r.stream;
+  const float* b = (const float*)r.blk_dev;
+  if (int rc = step_begin(r.blk_dev, r.blk_host, (size_t)(B - 1) * d.stride_bytes + d.bytes, r.timing, r.stream)) return rc;
+  const jh_step_mark mk = step_mark(r.out_host_mark, r.out);
   bool one = false;
-  if (int rc = plan_step_launches(m, N, H, K, costs, nullptr, W, noise, ldn, &one)) return rc;
+  if (int rc = plan_step_launches(m, N, H, K, r.costs, nullptr, r.W, r.noise, d.ldn, &one)) return rc;
   jh_upd::TailArgs a;
-  if (int rc = jh_update_tail_args(who, costs, nullptr, b + o_nominal, noise, ldn, b + o_sigma, b + o_lohi, N, 0, K, m->nu, mode, lambda, k, tie_high, E_t, trace, row_floats, colmajor,
-                                   scratch, out, out + KU, E_t > 0 ? out + 2 * KU : nullptr, nullptr, &a)) return rc;
+  if (int rc = jh_update_tail_args(who, r.costs, nullptr, b + d.o_nominal, r.noise, d.ldn, b + d.o_sigma, b + d.o_lohi, N, 0, K, m->nu, r.mode, r.lambda, r.k, r.tie_high, E_t, r.trace, r.row_floats,
+                                   r.colmajor, r.scratch, r.out, r.out + KU, E_t > 0 ? r.out + 2 * KU : nullptr, nullptr, &a)) return rc;
   jh_upd::BatchArgs s;
-  s.B = B; s.blk = (long long)(blk_stride_bytes / sizeof(float)); s.noise = (long long)noise_stride_floats; s.costs = N; s.trace = (long long)N * row_floats;
-  s.scratch = (long long)jh_update_fused_scratch_floats(N, K, m->nu); s.out = (long long)out_stride_floats;
-  s.counter = reinterpret_cast<unsigned*>(scratch) + 1; s.done_flag = flag; s.done_value = expect; s.image = image_stride;
+  s.B = B; s.blk = (long long)(d.stride_bytes / sizeof(float)); s.noise = (long long)d.noise_stride_floats; s.costs = N; s.trace = (long long)N * r.row_floats;
+  s.scratch = (long long)jh_update_fused_scratch_floats(N, K, m->nu); s.out = (long long)r.out_stride_floats;
+  s.counter = reinterpret_cast<unsigned*>(r.scratch) + 1; s.done_flag = mk.flag; s.done_value = mk.expect; s.image = r.image_stride;
   int rc = JH_OK;
-  if (one) rc = jh_simple_plan_step_batch(m, images, b, W, b + o_tp, H, K, a, s, st);
+  if (one) rc = eb->plan_step_batch(m, r.images, b, r.W, b + d.o_tp, H, K, a, s, st);
   else {
-    if (closed) rc = jh_simple_rollout_cost_batch(m, images, b, b + o_tp, W, H, K, a, s, st);
-    else {
-      const jh_rollout_args ra = {b, b + o_nominal, noise, ldn, b + o_sigma, W, b + o_lohi, b + o_tp, 0, N, 0, H, K, costs, nullptr, trace};
-      jh_rollout_batch rb = {images, image_stride, ints, B, s.blk, s.noise};
-      rb.o_phase = o_phase;
-      rc = eb->rollout_cost_batch(m, ra, rb, st);
-    }
-    if (rc == JH_OK && timing) JH_HIP(hipEventRecord((hipEvent_t)timing[1], st));
+    const jh_rollout_args ra = {b, b + d.o_nominal, r.noise, d.ldn, b + d.o_sigma, r.W, b + d.o_lohi, b + d.o_tp, 0, N, 0, H, K, r.costs, nullptr, r.trace};
+    jh_rollout_batch rb = {r.images, r.image_stride, r.ints, B, s.blk, s.noise};
+    rb.o_phase = r.o_phase;
+    rc = eb->rollout_cost_batch(m, ra, rb, st);
+    if (rc == JH_OK && r.timing) JH_HIP(hipEventRecord((hipEvent_t)r.timing[1], st));
     if (rc == JH_OK) rc = jh_update_tail_batch_launch(a, s, st);
   }
-  if (rc == JH_OK && one && timing) JH_HIP(hipEventRecord((hipEvent_t)timing[1], st));
-  if (rc == JH_OK && timing) JH_HIP(hipEventRecord((hipEvent_t)timing[2], st));
-  if (rc == JH_OK) rc = download_begin(out, out, 0, stream, flag, expect);
-  return rc;
+  if (rc == JH_OK && one && r.timing) JH_HIP(hipEventRecord((hipEvent_t)r.timing[1], st));
+  return step_end(rc, r.out, mk, r.timing, r.stream);
 }
+
+// The entries: their own pre-checks, then the record.  (`JH_BATCH_STEP`: the fields every entry has, in the record's order.)
+#define JH_BATCH_STEP(who, m, images, image_stride, ints, B)                                                                                                               \
+  {who, m, images, image_stride, ints, B, blk_dev, blk_host, {blk_bytes, o_nominal, o_sigma, o_tp, o_lohi, ldn, N, H, K, true, blk_stride_bytes, noise_stride_floats}, noise, W, \
+   costs, trace, mode, lambda, k, tie_high, E, row_floats, colmajor, scratch, out, out_stride_floats, out_host_mark, timing, stream}
 
 extern "C" int jh_plan_step_batch(const jh_model* m, int B, void* blk_dev, const void* blk_host, size_t blk_bytes, size_t blk_stride_bytes, int o_nominal, int o_sigma, int o_tp, int o_lohi,
                                   const float* noise, int ldn, size_t noise_stride_floats, const float* W, int N, int H, int K, float* costs, float* trace, int mode, float lambda, int k,
                                   int tie_high, int E, int row_floats, int colmajor, float* scratch, float* out, size_t out_stride_floats, void* out_host_mark, void* const* timing,
                                   void* stream) {
   JH_REQUIRE(m != nullptr, "plan_step_batch: null pointer");
-  return plan_step_batch("plan_step_batch", m, m->d_f, 0, m->d_i, B, blk_dev, blk_host, blk_bytes, blk_stride_bytes, o_nominal, o_sigma, o_tp, o_lohi, -1, noise, ldn, noise_stride_floats, W, N, H, K, costs, trace,
-                         mode, lambda, k, tie_high, E, row_floats, colmajor, scratch, out, out_stride_floats, out_host_mark, timing, stream);
+  return plan_step_batch(JH_BATCH_STEP("plan_step_batch", m, m->d_f, 0, m->d_i, B));
 }
 
 // jh_plan_step_batch for fr3_pick (include/judo_amd.h): the same code path with a phase word in every problem's block.
@@ -635,8 +657,9 @@ extern "C" int jh_plan_step_batch_phases(const jh_model* m, int B, void* blk_dev
                                          void* const* timing, void* stream) {
   JH_REQUIRE(m != nullptr, "plan_step_batch_phases: null pointer");
   JH_REQUIRE(o_phase >= 0, "plan_step_batch_phases: negative block offset (o_phase=%d)", o_phase);
-  return plan_step_batch("plan_step_batch_phases", m, m->d_f, 0, m->d_i, B, blk_dev, blk_host, blk_bytes, blk_stride_bytes, o_nominal, o_sigma, o_tp, o_lohi, o_phase, noise, ldn, noise_stride_floats, W, N,
-                         H, K, costs, trace, mode, lambda, k, tie_high, E, row_floats, colmajor, scratch, out, out_stride_floats, out_host_mark, timing, stream);
+  jh_batch_step r = JH_BATCH_STEP("plan_step_batch_phases", m, m->d_f, 0, m->d_i, B);
+  r.o_phase = o_phase;
+  return plan_step_batch(r);
 }
 
 // ---- model sets: B images of one model's float section in one device buffer, a fixed stride apart (include/judo_amd.h) ----
@@ -690,7 +713,7 @@ static int model_set_member(const char* who, const jh_model* m0, const jh_model*
   if (m->kind != JH_TASK_FR3_PICK && fr3) { jh_set_error("%s: member %d is no fr3_pick model (kind %d): this set holds fr3_pick models alone; jh_model_set_create makes a set of every other family", who, b, m->kind); return JH_ERR_UNSUPPORTED; }
   if (m->kind == JH_TASK_LEAP_CUBE && m->kernel_gen != 3) { jh_set_error("%s: member %d runs kernel_gen %d: only kernel generation 3 of the leap family has a batched launch", who, b, m->kernel_gen); return JH_ERR_UNSUPPORTED; }
   if (m->kind == JH_TASK_FR3_PICK && m->kernel_gen != 3) { jh_set_error("%s: member %d runs kernel_gen %d: only kernel generation 3 of fr3_pick has a batched launch", who, b, m->kernel_gen); return JH_ERR_UNSUPPORTED; }
-  if (m->kind != JH_TASK_CARTPOLE && m->kind != JH_TASK_CYLINDER_PUSH && m->kind != JH_TASK_LEAP_CUBE && m->kind != JH_TASK_FR3_PICK) { jh_set_error("%s: member %d: no batched kernel for this model (kind %d)", who, b, m->kind); return JH_ERR_UNSUPPORTED; }
+  if (const jh_engine_build* eb = engine_build(m); !(eb && eb->rollout_cost_batch)) { jh_set_error("%s: member %d: no batched kernel for this model (kind %d)", who, b, m->kind); return JH_ERR_UNSUPPORTED; }
   if (m != m0) {
 #define JH_SET_SAME(field, fmt)                                                                                                                                    \
   JH_REQUIRE(m->field == m0->field, "%s: member %d differs from the set's member 0 in " #field " (" fmt " against " fmt ")", who, b, m->field, m0->field)
@@ -793,8 +816,7 @@ extern "C" int jh_plan_step_batch_models(const jh_model_set* set, void* blk_dev,
                                          int k, int tie_high, int E, int row_floats, int colmajor, float* scratch, float* out, size_t out_stride_floats, void* out_host_mark,
                                          void* const* timing, void* stream) {
   JH_REQUIRE(set != nullptr, "plan_step_batch_models: null pointer");
-  return plan_step_batch("plan_step_batch_models", set->m0, set->d_images, (long long)set->stride, set->tables ? set->m0->d_i : set->d_i_plain, set->B, blk_dev, blk_host, blk_bytes, blk_stride_bytes, o_nominal, o_sigma, o_tp, o_lohi, -1, noise, ldn,
-                         noise_stride_floats, W, N, H, K, costs, trace, mode, lambda, k, tie_high, E, row_floats, colmajor, scratch, out, out_stride_floats, out_host_mark, timing, stream);
+  return plan_step_batch(JH_BATCH_STEP("plan_step_batch_models", set->m0, set->d_images, (long long)set->stride, set->tables ? set->m0->d_i : set->d_i_plain, set->B));
 }
 
 // jh_plan_step_batch_phases on a set of fr3_pick models (include/judo_amd.h): the same code path with the set's images and stride; the int section is member 0's own.
@@ -807,9 +829,11 @@ extern "C" int jh_plan_step_batch_phases_models(const jh_model_set* set, int B, 
   if (set->m0->kind != JH_TASK_FR3_PICK) { jh_set_error("%s: a phase word per problem is fr3_pick's alone; jh_plan_step_batch_models plans this set", who); return JH_ERR_UNSUPPORTED; }
   JH_REQUIRE(B == set->B, "%s: B = %d problems for a set of %d members: problem b runs on member b", who, B, set->B);
   JH_REQUIRE(o_phase >= 0, "%s: negative block offset (o_phase=%d)", who, o_phase);
-  return plan_step_batch(who, set->m0, set->d_images, (long long)set->stride, set->m0->d_i, B, blk_dev, blk_host, blk_bytes, blk_stride_bytes, o_nominal, o_sigma, o_tp, o_lohi, o_phase, noise, ldn,
-                         noise_stride_floats, W, N, H, K, costs, trace, mode, lambda, k, tie_high, E, row_floats, colmajor, scratch, out, out_stride_floats, out_host_mark, timing, stream);
+  jh_batch_step r = JH_BATCH_STEP(who, set->m0, set->d_images, (long long)set->stride, set->m0->d_i, B);
+  r.o_phase = o_phase;
+  return plan_step_batch(r);
 }
+#undef JH_BATCH_STEP
 
 // ---- plan steps on the plants of a model set (include/judo_amd.h): ONE launcher behind the twelve entries, with three degrees of freedom ----
 //  - the kind, what the rollout launch's y axis means.  Ensemble: the M members -- every member rolls out the same N candidates from the same block (block and noise
@@ -909,13 +933,11 @@ static int plan_step_set(const jh_set_step& r) {
   JH_REQUIRE(m->plan_step_launches != 1, "%s: one launch is forced (jh_model_set_plan_step_launches) but %s plan step is two launches", who, r.randomized ? "the randomised" : "the ensemble's");
   const long long rollouts = (long long)B * (r.randomized ? 1 : M) * N;
   JH_REQUIRE(rollouts <= 0x7fffffffll, "%s: %s = %lld rollouts exceed one launch", who, !r.fleet ? "M * N" : r.randomized ? "B * N" : "B * M * N", rollouts);
-  const bool closed = m->kind == JH_TASK_CARTPOLE || m->kind == JH_TASK_CYLINDER_PUSH;
   const jh_engine_build* eb = engine_build(m);
-  if (!closed && !(eb && eb->rollout_cost_batch)) { jh_set_error("%s: no batched kernel for this model", who); return JH_ERR_UNSUPPORTED; }
+  if (!(eb && eb->rollout_cost_batch)) { jh_set_error("%s: no batched kernel for this model", who); return JH_ERR_UNSUPPORTED; }
   if (r.o_phase >= 0) { if (int rc = phase_words(who, "controller", B, r.blk_host, d.bytes, d.stride_bytes, r.o_phase)) return rc; }
   const bool risk = r.fleet && !r.randomized && r.o_risk >= 0;
   if (risk) { if (int rc = risk_records(who, m, B, M, r.blk_host, d, r.o_phase, r.o_risk)) return rc; }
-  unsigned* flag = (r.out_host_mark && r.out_host_mark != (void*)r.out) ? (unsigned*)r.out_host_mark : nullptr;  // (out_host_mark == out: the stream's event)
   const float* b = (const float*)r.blk_dev;
   jh_upd::TailArgs a;  // (controller 0's record; the tail's own checks before anything is enqueued: mode, lambda, k)
   if (int rc = jh_update_tail_args(who, r.costs, nullptr, b + d.o_nominal, r.noise, d.ldn, b + d.o_sigma, b + d.o_lohi, N, 0, K, m->nu, r.mode, r.lambda, r.k, r.tie_high, 0, nullptr, 0, 0, r.scratch,
@@ -929,32 +951,21 @@ static int plan_step_set(const jh_set_step& r) {
   // ... and the z axis, the controllers (B = 1 and every stride 0 without it)
   const long long blk_c = (long long)(d.stride_bytes / sizeof(float)), noise_c = (long long)d.noise_stride_floats, image_c = (!r.fleet || set->B == M) ? 0ll : (long long)M * (long long)set->stride;
   hipStream_t st = (hipStream_t)r.stream;
-  if (r.blk_dev != r.blk_host) { if (int rc = jh_upload_async(r.blk_dev, r.blk_host, (size_t)(B - 1) * d.stride_bytes + d.bytes, r.stream)) return rc; }
-  if (r.timing) JH_HIP(hipEventRecord((hipEvent_t)r.timing[0], st));
-  const unsigned expect = flag ? __atomic_load_n(flag, __ATOMIC_RELAXED) + 1u : 0u;
-  if (!r.fleet) { a.done_flag = flag; a.done_value = expect; }  // (with a controller axis the word is the batch ticket's)
-  int rc = JH_OK;
-  if (closed) {
-    jh_upd::TailArgs ra = a;  // the rollout kernel's view of the record: problem (c, y)'s costs lie (c * Y + y) * Nb behind rollout_costs, the block and the noise are the controller's
-    ra.costs = rollout_costs; ra.N = Nb; ra.done_flag = nullptr; ra.done_value = 0u;
-    jh_upd::BatchArgs s;
-    s.B = Y; s.blk = 0; s.noise = noise_y; s.costs = Nb; s.trace = 0; s.scratch = 0; s.out = 0; s.counter = nullptr; s.done_flag = nullptr; s.done_value = 0u; s.image = (long long)set->stride;
-    jh_upd::ControllerAxis z;
-    z.C = B; z.blk = blk_c; z.noise = noise_c; z.image = image_c;
-    rc = jh_simple_rollout_cost_batch(m, set->d_images, b, b + d.o_tp, r.W, H, K, ra, s, st, z, plants);
-  } else {
-    const jh_rollout_args ra = {b, b + d.o_nominal, r.noise, d.ldn, b + d.o_sigma, r.W, b + d.o_lohi, b + d.o_tp, 0, Nb, 0, H, K, rollout_costs, nullptr, nullptr};
-    jh_rollout_batch rb = {set->d_images, (long long)set->stride, set->tables ? m->d_i : set->d_i_plain, Y, 0, noise_y, B, blk_c, noise_c, image_c};
-    rb.plants = plants; rb.o_phase = r.o_phase; rb.phase = r.phase;
-    rc = eb->rollout_cost_batch(m, ra, rb, st);
-  }
+  if (int rc = step_begin(r.blk_dev, r.blk_host, (size_t)(B - 1) * d.stride_bytes + d.bytes, r.timing, r.stream)) return rc;
+  const jh_step_mark mk = step_mark(r.out_host_mark, r.out);
+  if (!r.fleet) { a.done_flag = mk.flag; a.done_value = mk.expect; }  // (with a controller axis the word is the batch ticket's)
+  // the rollout launch's record: problem (c, y)'s costs lie (c * Y + y) * Nb behind rollout_costs, the block and the noise are the controller's
+  const jh_rollout_args ra = {b, b + d.o_nominal, r.noise, d.ldn, b + d.o_sigma, r.W, b + d.o_lohi, b + d.o_tp, 0, Nb, 0, H, K, rollout_costs, nullptr, nullptr};
+  jh_rollout_batch rb = {set->d_images, (long long)set->stride, set->tables ? m->d_i : set->d_i_plain, Y, 0, noise_y, B, blk_c, noise_c, image_c};
+  rb.plants = plants; rb.o_phase = r.o_phase; rb.phase = r.phase;
+  int rc = eb->rollout_cost_batch(m, ra, rb, st);
   if (rc == JH_OK && r.timing) JH_HIP(hipEventRecord((hipEvent_t)r.timing[1], st));
   if (rc == JH_OK && r.weights) rc = jh_update_tail_ensemble_weighted_launch(a, jh_upd::EnsembleWeightedArgs{r.member_costs, r.costs, M, r.tail, (long long)N, weights}, st);
   else if (rc == JH_OK && !r.fleet) rc = r.randomized ? jh_update_tail_launch(a, st) : jh_update_tail_ensemble_launch(a, jh_upd::EnsembleArgs{r.member_costs, r.costs, M, r.worst[0], (long long)N}, st);
   if (rc == JH_OK && r.fleet) {
     jh_upd::BatchArgs s;  // the tail's axis: the controllers
     s.B = B; s.blk = blk_c; s.noise = noise_c; s.costs = N; s.trace = 0; s.scratch = (long long)jh_update_fused_scratch_floats(N, K, m->nu); s.out = (long long)r.out_stride_floats;
-    s.counter = reinterpret_cast<unsigned*>(r.scratch) + 1; s.done_flag = flag; s.done_value = expect;
+    s.counter = reinterpret_cast<unsigned*>(r.scratch) + 1; s.done_flag = mk.flag; s.done_value = mk.expect;
     jh_upd::EnsembleBatchArgs e;
     e.member_costs = r.member_costs; e.costs = r.costs; e.M = M; e.stride = (long long)N;
     for (int i = 0; i < JH_MAX_ENSEMBLE_FLEET; i++) e.worst[i] = (unsigned char)(!r.randomized && i < B ? r.worst[i] : 1);
@@ -966,9 +977,7 @@ static int plan_step_set(const jh_set_step& r) {
       rc = jh_update_tail_ensemble_risk_batch_launch(a, s, q, st);
     } else rc = r.randomized ? jh_update_tail_batch_launch(a, s, st) : jh_update_tail_ensemble_batch_launch(a, s, e, st);
   }
-  if (rc == JH_OK && r.timing) JH_HIP(hipEventRecord((hipEvent_t)r.timing[2], st));
-  if (rc == JH_OK) rc = download_begin(r.out, r.out, 0, r.stream, flag, expect);
-  return rc;
+  return step_end(rc, r.out, mk, r.timing, r.stream);
 }
 
 // The entries: their own pre-checks, then the record.  (`JH_SET_STEP`: the fields every entry has, in the record's order.)
@@ -1151,17 +1160,15 @@ extern "C" int jh_update_fused_batch(int B, const float* costs, const float* blk
   JH_REQUIRE(E_t >= 0 && E_t <= JH_MAX_ELITES && (E_t == 0 || row_floats >= 1), "update_fused_batch: bad trace arguments (E=%d row_floats=%d)", E, row_floats);
   const size_t rec = 2 * (size_t)KU + (size_t)E_t * (2 + (size_t)(E_t > 0 ? row_floats : 0));
   JH_REQUIRE(out_stride_floats >= rec, "update_fused_batch: out_stride_floats = %zu is smaller than an output record (nominal | sigma | E trace records = %zu floats)", out_stride_floats, rec);
-  unsigned* flag = (out_host_mark && out_host_mark != (void*)out) ? (unsigned*)out_host_mark : nullptr;  // (out_host_mark == out: the stream's event)
-  const unsigned expect = flag ? __atomic_load_n(flag, __ATOMIC_RELAXED) + 1u : 0u;
+  const jh_step_mark mk = step_mark(out_host_mark, out);
   jh_upd::TailArgs a;
   if (int rc = jh_update_tail_args("update_fused_batch", costs, nullptr, blk + o_nominal, noise, ldn, blk + o_sigma, blk + o_lohi, N, 0, K, nu, mode, lambda, k, tie_high, E_t, trace, row_floats,
                                    colmajor, scratch, out, out + KU, E_t > 0 ? out + 2 * KU : nullptr, nullptr, &a)) return rc;
   jh_upd::BatchArgs s;
   s.B = B; s.blk = (long long)blk_stride_floats; s.noise = (long long)noise_stride_floats; s.costs = N; s.trace = (long long)N * row_floats;
   s.scratch = (long long)jh_update_fused_scratch_floats(N, K, nu); s.out = (long long)out_stride_floats;
-  s.counter = reinterpret_cast<unsigned*>(scratch) + 1; s.done_flag = flag; s.done_value = expect;
-  if (int rc = jh_update_tail_batch_launch(a, s, (hipStream_t)stream)) return rc;
-  return download_begin(out, out, 0, stream, flag, expect);
+  s.counter = reinterpret_cast<unsigned*>(scratch) + 1; s.done_flag = mk.flag; s.done_value = mk.expect;
+  return step_end(jh_update_tail_batch_launch(a, s, (hipStream_t)stream), out, mk, nullptr, stream);
 }
 
 // The same iteration when the rollouts are sharded over G ranks: launch -> all-gather -> merge.  The tail writes this rank's record; jh_plan_merge
@@ -1207,7 +1214,6 @@ extern "C" int jh_rollout_materialize(const jh_model* m, const float* x0, int x0
   JH_REQUIRE(states || sensors, "rollout_materialize: both outputs are null");
   JH_REQUIRE(N > 0 && H > 0, "rollout_materialize: N and H must be positive (N=%d H=%d)", N, H);
   hipStream_t st = (hipStream_t)stream;
-  if (m->kind == JH_TASK_CARTPOLE || m->kind == JH_TASK_CYLINDER_PUSH) return jh_simple_materialize(m, x0, x0_batched, controls, N, H, states, sensors, st);
   if (const jh_engine_build* eb = engine_build(m)) return eb->materialize(m, x0, x0_batched, controls, N, H, states, sensors, st);
   if (!g_xcheck.rollout_materialize) { jh_set_error("rollout_materialize: no kernel for this model / generation in this library"); return JH_ERR_UNSUPPORTED; }
   return g_xcheck.rollout_materialize(m, m->kernel_gen, x0, x0_batched, controls, N, H, states, sensors, stream);
@@ -1241,16 +1247,11 @@ static int materialize_plants_entry(const char* who, bool fr3_entry, const jh_mo
   JH_REQUIRE(H >= 1, "%s: H = %d must be at least 1", who, H);
   for (int g = 0; g < G; g++) JH_REQUIRE(plant_of_block[g] >= 0 && plant_of_block[g] < M, "%s: plant_of_block[%d] = %d outside [0, M = %d): block %d names no member of the set", who, g, plant_of_block[g], M, g);
   JH_REQUIRE((long long)G * n <= 0x7fffffffll, "%s: G * n = %d * %d rollouts exceed one launch", who, G, n);
-  const bool closed = m->kind == JH_TASK_CARTPOLE || m->kind == JH_TASK_CYLINDER_PUSH;
   const jh_engine_build* eb = engine_build(m);
-  if (!closed && !(eb && eb->materialize_plants)) { jh_set_error("%s: no materialise kernel on plants for this model / kernel generation", who); return JH_ERR_UNSUPPORTED; }
-  jh_plant_axis plants;
-  for (int g = 0; g < G; g++) jh_plant_set(plants, g, plant_of_block[g]);
-  hipStream_t st = (hipStream_t)stream;
-  if (closed) return jh_simple_materialize_plants(m, set->d_images, (long long)set->stride, plants, G, x0, x0_batched, controls, controls_shared, n, H, states, sensors, st);
+  if (!(eb && eb->materialize_plants)) { jh_set_error("%s: no materialise kernel on plants for this model / kernel generation", who); return JH_ERR_UNSUPPORTED; }
   jh_rollout_batch rb = {set->d_images, (long long)set->stride, set->tables ? m->d_i : set->d_i_plain, G, 0, 0};
-  rb.plants = plants;
-  return eb->materialize_plants(m, rb, x0, x0_batched, controls, controls_shared, n, H, states, sensors, st);
+  for (int g = 0; g < G; g++) jh_plant_set(rb.plants, g, plant_of_block[g]);
+  return eb->materialize_plants(m, rb, x0, x0_batched, controls, controls_shared, n, H, states, sensors, (hipStream_t)stream);
 }
 
 extern "C" int jh_rollout_materialize_plants(const jh_model_set* set, const int* plant_of_block, int G, int n, const float* x0, int x0_batched, const float* controls, int controls_shared,

@@ -2103,6 +2103,9 @@ static int materialize_plants(const jh_model* m, const jh_rollout_batch& s, cons
 
 // This build's row of the table (jh_internal.h); `accepts` is what the launchers above ask of a model, for a caller that must know in advance (jh_model_set_create: every
 // member of a set, on its own floats).  Host pass only: a const object with a constant initialiser would be emitted into the code object as well.
+// No bound of its own on K: the kernel reads its knots from memory every step, no on-chip staging.  The trace: trace_cube, trace_{if,mf,rf,th}_tip, the five framepos
+// sensors behind the 16 joint positions of leap_cube.xml's NS sensors (the kernel writes them for that sensor list alone).
 #ifndef __HIP_DEVICE_COMPILE__
-const jh_engine_build JH_V5_NAME(jh_engine5_build) = {JH_V5_CYL ? "leap, cylinders" : NCAP > 48 ? "leap, 64 contacts" : "leap, 48 contacts", accepts, rollout_cost, rollout_cost_batch, materialize, NCAP, materialize_plants};
+const jh_engine_build JH_V5_NAME(jh_engine5_build) = {JH_V5_CYL ? "leap, cylinders" : NCAP > 48 ? "leap, 64 contacts" : "leap, 48 contacts", accepts, rollout_cost, rollout_cost_batch, materialize, NCAP, materialize_plants,
+                                                      nullptr, [](const jh_model* m) { return m->ns == NS ? jh_trace_layout{16, 15, 0} : jh_trace_layout{}; }};
 #endif

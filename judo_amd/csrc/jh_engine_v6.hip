@@ -1401,7 +1401,8 @@ static int materialize_plants(const jh_model* m, const jh_rollout_batch& s, cons
 }
 
 // This build's row of the table (jh_internal.h); the contact capacity is the LDS pool plus the overflow row.  Host pass only: a const object with a constant initialiser
-// would be emitted into the code object as well.
+// would be emitted into the code object as well.  K: the 8 knots per actuator the kernel keeps in registers, at every horizon.  The trace: trace_object, trace_grasp_site.
 #ifndef __HIP_DEVICE_COMPILE__
-const jh_engine_build JH_V6_NAME(jh_engine6_build) = {JH_V6_SELF ? "fr3, self-collision" : "fr3", JH_V6_NAME(jh_model_is_fr3), rollout_cost, rollout_cost_batch, JH_V6_NAME(jh_engine6_materialize), NCP + NOVF, materialize_plants};
+const jh_engine_build JH_V6_NAME(jh_engine6_build) = {JH_V6_SELF ? "fr3, self-collision" : "fr3", JH_V6_NAME(jh_model_is_fr3), rollout_cost, rollout_cost_batch, JH_V6_NAME(jh_engine6_materialize), NCP + NOVF, materialize_plants,
+                                                      [](const jh_model*, int) { return 8; }, [](const jh_model*) { return jh_trace_layout{8, 6, 0}; }};
 #endif

@@ -153,8 +153,13 @@ struct jh_rollout_batch {
   int phase = -1;
 };
 
-// One build of an articulated product kernel: each translation unit that instantiates k_leap_v5 or k_fr3_v6 defines its row, and jh_api.hip's engine_build() maps a model
-// to the row that runs it.  A new build is a new row and a line of that function.
+// The trace sensors a fused kernel writes per rollout and step: the first sensor address, the number of floats (0: none -- the elites are re-rolled in materialise mode
+// instead) and whether the buffer is column-major (one lane per rollout) or a row per rollout.
+struct jh_trace_layout { int adr = 0, floats = 0, colmajor = 0; };
+namespace jh_upd { struct TailArgs; struct BatchArgs; }  // (jh_update_dev.h: the update tail's kernel arguments, which the one-launch plan step takes as they are)
+
+// One build of a product kernel: each translation unit that instantiates k_leap_v5 or k_fr3_v6 defines its row, jh_simple.hip one for the two closed-form models, and
+// jh_api.hip's engine_build() maps a model to the row that runs it.  A new build is a new row and a line of that function.
 struct jh_engine_build {
   const char* name;                       // for messages
   bool (*accepts)(const jh_model* m);     // the launchers' own acceptance test, on the model's own image
@@ -167,8 +172,18 @@ struct jh_engine_build {
   // they refuse unless it is 1.  null: the build has no such launch (none of the shipped rows)
   int (*materialize_plants)(const jh_model* m, const jh_rollout_batch& s, const float* x0, int x0_batched, const float* controls, int controls_shared, int n, int H, float* states,
                             float* sensors, hipStream_t st) = nullptr;
+  int (*max_fused_knots)(const jh_model* m, int H) = nullptr;    // the build's own bound on a fused launch's K at horizon H, under JH_MAX_KNOT_DIM / nu (jh_model_max_fused_knots); null: none of its own
+  jh_trace_layout (*trace_layout)(const jh_model* m) = nullptr;  // what a fused launch with a trace buffer writes (jh_model_trace_layout); null: this build writes no trace
+  // The plan step as ONE launch, rollout + cost + the update's tail (jh_model_set_plan_step_launches): the largest K whose staging fits at horizon H, the launch on the
+  // tail's own record, and the batched launch on problem 0's record, `images` as in jh_rollout_batch and s.image floats apart.  All null: a build whose plan step is two
+  // launches (every articulated row).
+  int (*one_launch_max_knots)(const jh_model* m, int H) = nullptr;
+  int (*plan_step)(const jh_model* m, const float* x0, const float* W, const float* tp, int H, int K, const jh_upd::TailArgs& a, hipStream_t st) = nullptr;
+  int (*plan_step_batch)(const jh_model* m, const float* images, const float* x0, const float* W, const float* tp, int H, int K, const jh_upd::TailArgs& a, const jh_upd::BatchArgs& s,
+                         hipStream_t st) = nullptr;
 };
 // (hidden: the rows are the library's own, not part of its boundary)
+extern __attribute__((visibility("hidden"))) const jh_engine_build jh_simple_build;  // jh_simple.hip: cartpole and cylinder_push, one row for both (contact capacity 0: neither model holds contacts in a pool)
 extern __attribute__((visibility("hidden"))) const jh_engine_build jh_engine5_build, jh_engine5_build_cap64, jh_engine5_build_cyl;  // jh_engine_v5.hip: the leap kernel for 48 and 64 contacts, and with cylinders
 extern __attribute__((visibility("hidden"))) const jh_engine_build jh_engine6_build, jh_engine6_build_self;  // jh_engine_v6.hip: the fr3 kernel, and with the arm's own pairs (jh_model::arm_pairs > 0)
 
@@ -177,20 +192,12 @@ extern __attribute__((visibility("hidden"))) const jh_engine_build jh_engine6_bu
 // belongs to diagnostic builds.
 enum { JH_STAT_DROPS = 0, JH_STAT_ITER_CAP, JH_STAT_ITERS, JH_STAT_STEPS, JH_STAT_WAVE_ITERS = 20, JH_STAT_WAVE_STEPS, JH_STAT_RECOMPUTED = 56 };
 
-int jh_simple_rollout_cost(const jh_model* m, const jh_rollout_args& a, hipStream_t st);
 // Latency mode of the cooperative kernels (rows of `lanes` lanes, `rpw` rows per wave): a launch too small to give every SIMD a wave lets 1 << shift rows of a wave
 // compute the same rollout -- the copies run the same arithmetic, only the first writes -- so that a wave no longer waits for the slowest of `rpw` different Newton
 // solves in every step.  Returns the largest shift (<= log2 rpw) that still leaves every wave of the launch a SIMD of its own; JUDO_AMD_LATENCY_SHIFT=0..2 overrides.
 int jh_latency_shift(int N, int rpw);
-int jh_simple_max_knots(const jh_model* m, int H);  // largest fused K at horizon H (LDS staging budget of the launcher)
-int jh_simple_one_launch_max_knots(const jh_model* m, int H);  // largest K of the one-launch plan step at horizon H (its 48 KiB LDS staging)
 int jh_engine_max_knots(const jh_model* m, int H);
-int jh_simple_materialize(const jh_model* m, const float* x0, int x0_batched, const float* controls, int N, int H, float* states,
-                          float* sensors, hipStream_t st);
-// jh_simple_materialize on a plant axis (jh_rollout_materialize_plants): G blocks of n rollouts, block g on image p's table entry g of `images`, `image_stride` floats apart
-int jh_simple_materialize_plants(const jh_model* m, const float* images, long long image_stride, const jh_plant_axis& p, int G, const float* x0, int x0_batched, const float* controls,
-                                 int controls_shared, int n, int H, float* states, float* sensors, hipStream_t st);
-int jh_simple_reward(const jh_model* m, const float* states, const float* controls, const float* tp, int N, int H, float* rewards, hipStream_t st);
+int jh_simple_reward(const jh_model* m, const float* states, const float* controls, const float* tp, int N, int H, float* rewards, hipStream_t st);  // (jh_task_reward: the one closed-form launcher outside the row)
 
 int jh_engine_rollout_cost(const jh_model* m, const float* x0, const float* nominal, const float* noise, int ldn, const float* sigma,
                            const float* W, const float* lohi, const float* tp, int phase, int N, int n_offset, int H, int K, float* costs,

@@ -406,51 +406,59 @@ int launch_plan_step(const jh_model* m, const float* x0, const float* W, const f
   return JH_OK;
 }
 
+// (`P`: the float section of problem 0's model image, s.image floats to the next problem's -- m->d_f with s.image = 0 where the problems share the model.  The kernel's
+// plant axis stays at its default, 0 and the identity: B independent problems.)
 template <class T>
-int launch_plan_step_batch(const float* P, const float* x0, const float* W, const float* tp, int H, int K, const jh_upd::TailArgs& a, const jh_upd::BatchArgs& s, const jh_plant_axis& p, hipStream_t st) {
+int launch_plan_step_batch(const float* P, const float* x0, const float* W, const float* tp, int H, int K, const jh_upd::TailArgs& a, const jh_upd::BatchArgs& s, hipStream_t st) {
   constexpr int BS = jh_upd::kUB;
   size_t lds = sizeof(float) * ((size_t)H * K + (size_t)K * T::NU * BS + T::NP + T::NTP + T::NX);
   JH_REQUIRE(lds <= 48 * 1024, "plan_step_batch: H*K too large for the LDS staging of the one-launch plan step (%zu bytes)", lds);
-  hipLaunchKernelGGL(k_plan_step_batch<T>, dim3((a.N + BS - 1) / BS, s.B), dim3(BS), lds, st, P, x0, W, tp, H, K, a, s, p);
+  hipLaunchKernelGGL(k_plan_step_batch<T>, dim3((a.N + BS - 1) / BS, s.B), dim3(BS), lds, st, P, x0, W, tp, H, K, a, s, jh_plant_axis{});
   JH_HIP(hipGetLastError());
   return JH_OK;
 }
 
+// The batched rollout launch on the engines' two records, grid (workgroups of a problem, s.B, s.C).  k_rollout_cost_batch takes the update tail's records because it derives
+// a problem's pointers with the tail's batch_problem / batch_controller; they are filled here, with what the kernel reads of them: the costs, the knot source, N, the rollout
+// offset and the trace buffer of problem 0, and the strides -- a problem's block, noise and image from `s`, its N costs and N * H * NS trace floats from the launch's own shape
+// (the (controller, problem) pair c * gridDim.y + b owns a row of each).  Everything else of the two records is the tail's and stays zero.
 template <class T>
-int launch_cost_batch(const float* P, const float* x0, const float* W, const float* tp, int H, int K, const jh_upd::TailArgs& a, const jh_upd::BatchArgs& s, const jh_upd::ControllerAxis& z, const jh_plant_axis& p, hipStream_t st) {
-  size_t lds = sizeof(float) * ((size_t)H * K + (size_t)K * T::NU * kBlock + T::NP + T::NTP + T::NX);
+int launch_cost_batch(const jh_rollout_args& a, const jh_rollout_batch& s, hipStream_t st) {
+  size_t lds = sizeof(float) * ((size_t)a.H * a.K + (size_t)a.K * T::NU * kBlock + T::NP + T::NTP + T::NX);
   JH_REQUIRE(lds <= 64 * 1024, "plan_step_batch: H*K too large for the LDS staging (%zu bytes)", lds);
-  hipLaunchKernelGGL(k_rollout_cost_batch<T>, dim3((a.N + kBlock - 1) / kBlock, s.B, z.C), dim3(kBlock), lds, st, P, x0, W, tp, H, K, a, s, z, p);
+  jh_upd::TailArgs t = {};
+  t.costs = a.costs; t.src.nominal = a.nominal; t.src.noise = a.noise; t.src.sigma = a.sigma; t.src.lohi = a.lohi; t.src.ldn = a.ldn; t.N = a.N; t.n_offset = a.n_offset; t.trace = a.trace;
+  jh_upd::BatchArgs b = {};
+  b.B = s.B; b.blk = s.blk_stride; b.noise = s.noise_stride; b.costs = a.N; b.trace = (long long)a.N * a.H * T::NS; b.image = s.image_stride;
+  jh_upd::ControllerAxis z;
+  z.C = s.C; z.blk = s.blk_stride_c; z.noise = s.noise_stride_c; z.image = s.image_stride_c;
+  hipLaunchKernelGGL(k_rollout_cost_batch<T>, dim3((a.N + kBlock - 1) / kBlock, s.B, s.C), dim3(kBlock), lds, st, s.images, a.x0, a.W, a.tp, a.H, a.K, t, b, z, s.plants);
   JH_HIP(hipGetLastError());
   return JH_OK;
 }
 
 }  // namespace
 
-int jh_simple_plan_step_batch(const jh_model* m, const float* P, const float* x0, const float* W, const float* tp, int H, int K, const jh_upd::TailArgs& a, const jh_upd::BatchArgs& s, hipStream_t st,
-                              const jh_plant_axis& p) {
-  if (m->kind == JH_TASK_CARTPOLE) return launch_plan_step_batch<Cartpole>(P, x0, W, tp, H, K, a, s, p, st);
-  return launch_plan_step_batch<CylinderPush>(P, x0, W, tp, H, K, a, s, p, st);
+// ---- the launchers of the closed-form row (jh_simple_build, last in the file): one row for both models, the dispatch on the kind stays here
+// ([[maybe_unused]]: the row that names them exists in the host pass alone)
+[[maybe_unused]] static int jh_simple_plan_step_batch(const jh_model* m, const float* P, const float* x0, const float* W, const float* tp, int H, int K, const jh_upd::TailArgs& a, const jh_upd::BatchArgs& s, hipStream_t st) {
+  if (m->kind == JH_TASK_CARTPOLE) return launch_plan_step_batch<Cartpole>(P, x0, W, tp, H, K, a, s, st);
+  return launch_plan_step_batch<CylinderPush>(P, x0, W, tp, H, K, a, s, st);
 }
-int jh_simple_rollout_cost_batch(const jh_model* m, const float* P, const float* x0, const float* tp, const float* W, int H, int K, const jh_upd::TailArgs& a, const jh_upd::BatchArgs& s, hipStream_t st,
-                                 const jh_upd::ControllerAxis& z, const jh_plant_axis& p) {
-  if (m->kind == JH_TASK_CARTPOLE) return launch_cost_batch<Cartpole>(P, x0, W, tp, H, K, a, s, z, p, st);
-  return launch_cost_batch<CylinderPush>(P, x0, W, tp, H, K, a, s, z, p, st);
+[[maybe_unused]] static int jh_simple_rollout_cost_batch(const jh_model* m, const jh_rollout_args& a, const jh_rollout_batch& s, hipStream_t st) {
+  if (m->kind == JH_TASK_CARTPOLE) return launch_cost_batch<Cartpole>(a, s, st);
+  return launch_cost_batch<CylinderPush>(a, s, st);
 }
 
-// can the plan step of this model run as one launch?  (closed-form models; the knots of a workgroup of 256 rollouts must fit the LDS staging next to the update's own 9 KB)
+// can the plan step of this model run as one launch?  (the knots of a workgroup of 256 rollouts must fit the LDS staging next to the update's own 9 KB)
 template <class T>
 static int one_launch_max_knots(int H) { return (int)((12 * 1024 - T::NP - T::NTP - T::NX) / ((size_t)H + (size_t)T::NU * jh_upd::kUB)); }  // launch_plan_step's 48 KiB, in floats
-int jh_simple_one_launch_max_knots(const jh_model* m, int H) {
-  if (m->kind != JH_TASK_CARTPOLE && m->kind != JH_TASK_CYLINDER_PUSH) return 0;
-  return m->kind == JH_TASK_CARTPOLE ? one_launch_max_knots<Cartpole>(H) : one_launch_max_knots<CylinderPush>(H);
-}
-bool jh_simple_plan_step_fits(const jh_model* m, int H, int K) { return K <= jh_simple_one_launch_max_knots(m, H); }
+[[maybe_unused]] static int jh_simple_one_launch_max_knots(const jh_model* m, int H) { return m->kind == JH_TASK_CARTPOLE ? one_launch_max_knots<Cartpole>(H) : one_launch_max_knots<CylinderPush>(H); }
 
 #ifdef JH_TAIL_TICKS
 extern "C" int jh_debug_tail_ticks(long long* out) { return hipMemcpyFromSymbol(out, HIP_SYMBOL(jh_upd::g_tail_ticks), 16 * sizeof(long long)) == hipSuccess ? 0 : -2; }
 #endif
-int jh_simple_plan_step(const jh_model* m, const float* x0, const float* W, const float* tp, int H, int K, const jh_upd::TailArgs& a, hipStream_t st) {
+[[maybe_unused]] static int jh_simple_plan_step(const jh_model* m, const float* x0, const float* W, const float* tp, int H, int K, const jh_upd::TailArgs& a, hipStream_t st) {
   if (m->kind == JH_TASK_CARTPOLE) return launch_plan_step<Cartpole>(m, x0, W, tp, H, K, a, st);
   return launch_plan_step<CylinderPush>(m, x0, W, tp, H, K, a, st);
 }
@@ -458,15 +466,15 @@ int jh_simple_plan_step(const jh_model* m, const float* x0, const float* W, cons
 // largest K for which launch_cost's LDS staging (W, the lanes' knots, model / task constants, x0) fits the 64 KiB it may ask for
 template <class T>
 static int max_knots(int H) { return (int)((16 * 1024 - T::NP - T::NTP - T::NX) / ((size_t)H + (size_t)T::NU * kBlock)); }
-int jh_simple_max_knots(const jh_model* m, int H) { return m->kind == JH_TASK_CARTPOLE ? max_knots<Cartpole>(H) : max_knots<CylinderPush>(H); }
+[[maybe_unused]] static int jh_simple_max_knots(const jh_model* m, int H) { return m->kind == JH_TASK_CARTPOLE ? max_knots<Cartpole>(H) : max_knots<CylinderPush>(H); }
 
-int jh_simple_rollout_cost(const jh_model* m, const jh_rollout_args& a, hipStream_t st) {
+[[maybe_unused]] static int jh_simple_rollout_cost(const jh_model* m, const jh_rollout_args& a, hipStream_t st) {
   if (m->kind == JH_TASK_CARTPOLE) return launch_cost<Cartpole>(m, a, st);
   return launch_cost<CylinderPush>(m, a, st);
 }
 
-int jh_simple_materialize(const jh_model* m, const float* x0, int x0_batched, const float* controls, int N, int H, float* states,
-                          float* sensors, hipStream_t st) {
+[[maybe_unused]] static int jh_simple_materialize(const jh_model* m, const float* x0, int x0_batched, const float* controls, int N, int H, float* states,
+                                 float* sensors, hipStream_t st) {
   int grid = (N + kBlock - 1) / kBlock;
   // float4 tile moves need 16-byte aligned rows: aligned base pointers and H a multiple of the tile length
   const int vec_ok = (H % JH_MAT_TS == 0) && ((reinterpret_cast<uintptr_t>(controls) | reinterpret_cast<uintptr_t>(states) | reinterpret_cast<uintptr_t>(sensors)) & 15) == 0;
@@ -502,8 +510,17 @@ static int launch_materialize_plants(const float* images, long long image_stride
   JH_HIP(hipGetLastError());
   return JH_OK;
 }
-int jh_simple_materialize_plants(const jh_model* m, const float* images, long long image_stride, const jh_plant_axis& p, int G, const float* x0, int x0_batched, const float* controls,
-                                 int controls_shared, int n, int H, float* states, float* sensors, hipStream_t st) {
-  if (m->kind == JH_TASK_CARTPOLE) return launch_materialize_plants<Cartpole>(images, image_stride, p, G, x0, x0_batched, controls, controls_shared, n, H, states, sensors, st);
-  return launch_materialize_plants<CylinderPush>(images, image_stride, p, G, x0, x0_batched, controls, controls_shared, n, H, states, sensors, st);
+// (of `s` the launch reads images, image_stride, B -- the G blocks -- and plants)
+[[maybe_unused]] static int jh_simple_materialize_plants(const jh_model* m, const jh_rollout_batch& s, const float* x0, int x0_batched, const float* controls, int controls_shared, int n, int H, float* states,
+                                        float* sensors, hipStream_t st) {
+  if (m->kind == JH_TASK_CARTPOLE) return launch_materialize_plants<Cartpole>(s.images, s.image_stride, s.plants, s.B, x0, x0_batched, controls, controls_shared, n, H, states, sensors, st);
+  return launch_materialize_plants<CylinderPush>(s.images, s.image_stride, s.plants, s.B, x0, x0_batched, controls, controls_shared, n, H, states, sensors, st);
 }
+
+// The closed-form models' row of the table (jh_internal.h), whatever jh_model::kernel_gen holds: both models' six sensors are their two trace sites, one lane per rollout
+// writes them column-major; no contact pool.  Host pass only: a const object with a constant initialiser would be emitted into the code object as well.
+#ifndef __HIP_DEVICE_COMPILE__
+const jh_engine_build jh_simple_build = {"closed form", [](const jh_model* m) { return m->kind == JH_TASK_CARTPOLE || m->kind == JH_TASK_CYLINDER_PUSH; }, jh_simple_rollout_cost,
+                                         jh_simple_rollout_cost_batch, jh_simple_materialize, 0, jh_simple_materialize_plants, jh_simple_max_knots,
+                                         [](const jh_model*) { return jh_trace_layout{0, 6, 1}; }, jh_simple_one_launch_max_knots, jh_simple_plan_step, jh_simple_plan_step_batch};
+#endif

@@ -498,21 +498,11 @@ __device__ __forceinline__ float ensemble_cost_risk(const float* __restrict__ me
 int jh_update_tail_args(const char* who, const float* costs, const float* knots_nku, const float* nominal, const float* noise, int ldn, const float* sigma, const float* lohi, int N,
                         int n_offset, int K, int nu, int mode, float lambda, int k, int tie_high, int E, const float* trace, int row_floats, int colmajor, float* scratch,
                         float* nominal_out, float* sigma_out, float* trace_out, float* rec_out, jh_upd::TailArgs* a);
-// jh_simple.hip: rollout + cost + update tail of a closed-form model in one launch
 int jh_update_tail_launch(const jh_upd::TailArgs& a, hipStream_t st);  // k_update_tail on its own (the articulated models' plan step)
-bool jh_simple_plan_step_fits(const jh_model* m, int H, int K);
-int jh_simple_plan_step(const jh_model* m, const float* x0, const float* W, const float* tp, int H, int K, const jh_upd::TailArgs& a, hipStream_t st);
 // the batched forms (jh_plan_step_batch): `a` is problem 0's record, `s` the strides; grid (workgroups of a problem, B)
 int jh_update_tail_batch_launch(const jh_upd::TailArgs& a, const jh_upd::BatchArgs& s, hipStream_t st);
 // the ensemble form (jh_plan_step_ensemble): the aggregation of e.member_costs into e.costs == a.costs, then the tail, in one launch
 int jh_update_tail_ensemble_launch(const jh_upd::TailArgs& a, const jh_upd::EnsembleArgs& e, hipStream_t st);
-// (`P`: the float section of problem 0's model image, s.image floats to the next problem's -- m->d_f with s.image = 0 where the problems share the model)
-// (`p`: the plant axis of jh_internal.h, the rollout-index stride and the table from a problem to its image; the default, 0 and the identity, is B independent problems)
-int jh_simple_plan_step_batch(const jh_model* m, const float* P, const float* x0, const float* W, const float* tp, int H, int K, const jh_upd::TailArgs& a, const jh_upd::BatchArgs& s, hipStream_t st,
-                              const jh_plant_axis& p = {});
-// (`z`: the controller axis of jh_plan_step_ensemble_batch, grid (workgroups, s.B, z.C); the default is the launch without one)
-int jh_simple_rollout_cost_batch(const jh_model* m, const float* P, const float* x0, const float* tp, const float* W, int H, int K, const jh_upd::TailArgs& a, const jh_upd::BatchArgs& s, hipStream_t st,
-                                 const jh_upd::ControllerAxis& z = {}, const jh_plant_axis& p = {});
 // the ensemble fleet's tail (jh_plan_step_ensemble_batch): `a` is controller 0's record, `s` the controllers' strides and the two-level ticket; grid (tail workgroups, s.B)
 int jh_update_tail_ensemble_batch_launch(const jh_upd::TailArgs& a, const jh_upd::BatchArgs& s, const jh_upd::EnsembleBatchArgs& e, hipStream_t st);
 // the plant-weighted ensemble form (jh_plan_step_ensemble_weighted): jh_update_tail_ensemble_launch with the weighted aggregation in front of the tail.
