@@ -1,6 +1,9 @@
 // jh_coop.h -- building blocks of the cooperative (16 lanes per rollout) engine kernels on gfx950: row-local DPP reductions and
 // the buffer-free box-box / box-sphere narrow phase that feeds a caller-supplied contact sink.
 #pragma once
+#include <type_traits>
+#include <utility>
+
 #include "jh_engine_common.h"
 
 namespace jh_coop {
@@ -73,7 +76,9 @@ __device__ __forceinline__ float quad_get(float v, int j) {
   switch (j) { case 0: return dppf<0x00>(v); case 1: return dppf<0x55>(v); case 2: return dppf<0xAA>(v); default: return dppf<0xFF>(v); }
 }
 
-__device__ __forceinline__ float gmin(float v) {  // min over the 16 lanes of a rollout
+// min over the 16 lanes of a rollout.  fminf IGNORES a NaN lane: the result is the minimum of the lanes that hold numbers, and a NaN only when all 16 lanes are NaN --
+// a caller that must see a NaN has to test for it itself
+__device__ __forceinline__ float gmin(float v) {
   v = fminf(v, dppf<DPP_XOR1>(v)); v = fminf(v, dppf<DPP_XOR2>(v)); v = fminf(v, dppf<DPP_HALF_MIRROR>(v)); v = fminf(v, dppf<DPP_MIRROR>(v));
   return v;
 }
@@ -122,6 +127,93 @@ __device__ __forceinline__ void bwd_packed(float* v, const float* L) {
     for (int q = m + 1; q < N; q++) s -= L[tri4(q, m)] * v[q];
     v[m] = s * L[tri4(m, m)];
   }
+}
+
+// 4x4 Cholesky (packed lower) + triangular solves on registers; the diagonal is kept as its reciprocal (one v_rsq per pivot, no divisions in the solves)
+__device__ __forceinline__ void chol4(float* L, float* inv) {
+#pragma unroll
+  for (int i = 0; i < 4; i++)
+#pragma unroll
+    for (int j = 0; j <= i; j++) {
+      float s = L[tri(i, j)];
+#pragma unroll
+      for (int k = 0; k < j; k++) s -= L[tri(i, k)] * L[tri(j, k)];
+      if (i == j) { float r = __frsqrt_rn(fmaxf(s, 1e-30f)); inv[i] = r; L[tri(i, i)] = s * r; }
+      else L[tri(i, j)] = s * inv[j];
+    }
+}
+__device__ __forceinline__ void fwd4(const float* L, const float* inv, float* x) {
+#pragma unroll
+  for (int i = 0; i < 4; i++) { float s = x[i];
+#pragma unroll
+    for (int k = 0; k < i; k++) s -= L[tri(i, k)] * x[k];
+    x[i] = s * inv[i]; }
+}
+__device__ __forceinline__ void bwd4(const float* L, const float* inv, float* x) {
+#pragma unroll
+  for (int i = 3; i >= 0; i--) { float s = x[i];
+#pragma unroll
+    for (int k = i + 1; k < 4; k++) s -= L[tri(k, i)] * x[k];
+    x[i] = s * inv[i]; }
+}
+
+// dense Cholesky + solve of an n x n system held in registers (packed lower L, reciprocal diagonal), redundantly per lane
+template <int N_>
+__device__ __forceinline__ void chol_solve(float* L, float* x) {
+  float inv[N_];
+#pragma unroll
+  for (int i = 0; i < N_; i++)
+#pragma unroll
+    for (int j = 0; j <= i; j++) {
+      float s = L[tri(i, j)];
+#pragma unroll
+      for (int k = 0; k < j; k++) s -= L[tri(i, k)] * L[tri(j, k)];
+      if (i == j) { float rr = __frsqrt_rn(fmaxf(s, 1e-30f)); inv[i] = rr; L[tri(i, i)] = s * rr; }
+      else L[tri(i, j)] = s * inv[j];
+    }
+#pragma unroll
+  for (int i = 0; i < N_; i++) { float s = x[i];
+#pragma unroll
+    for (int k = 0; k < i; k++) s -= L[tri(i, k)] * x[k];
+    x[i] = s * inv[i]; }
+#pragma unroll
+  for (int i = N_ - 1; i >= 0; i--) { float s = x[i];
+#pragma unroll
+    for (int k = i + 1; k < N_; k++) s -= L[tri(k, i)] * x[k];
+    x[i] = s * inv[i]; }
+}
+
+template <int N, class F, int... I>
+__device__ __forceinline__ void static_for_impl(F&& f, std::integer_sequence<int, I...>) { (f(std::integral_constant<int, I>{}), ...); }
+template <int N, class F>
+__device__ __forceinline__ void static_for(F&& f) { static_for_impl<N>(f, std::make_integer_sequence<int, N>{}); }  // f(integral_constant<int, 0>) ... f(<N - 1>): compile-time indices for DPP controls
+
+// The arm's 9 x 9 system with its rows spread over the arm's lanes (lane 6 + a holds row a, entries b <= a; lane 15 the right-hand side as a tenth row): right-looking
+// Cholesky and both triangular solves with DPP row broadcasts, every entry receiving its subtractions in the order of chol_solve<9>; every lane gets x, bit for bit the
+// same.  Not chol_solve<9>'s bits, though: the subtractions here are explicit fma, chol_solve's `s -= a * b` are contracted as the compiler sees fit (where it packs the
+// multiplies in pairs the subtractions stay apart), so the two agree to rounding only (tests/test_gpu_solver_blocks.py holds both to the same residual).
+// Replaces the factorisation every lane did redundantly on its own copy of the 45 entries.
+template <int NA = 9>
+__device__ __forceinline__ void arm_chol_solve(float* R, float* x, int l) {
+  static_for<NA>([&](auto kc) {
+    constexpr int k = decltype(kc)::value;
+    const float rinv = __frsqrt_rn(fmaxf(row_bcast<6 + k>(R[k]), 1e-30f));
+    const float lk = R[k] * rinv;
+    R[k] = l == 6 + k ? rinv : lk;
+    static_for<NA - 1 - k>([&](auto jc) {
+      constexpr int j = k + 1 + decltype(jc)::value;
+      R[j] = __builtin_fmaf(-lk, row_bcast<6 + j>(lk), R[j]);
+    });
+  });
+  static_for<NA>([&](auto kc) {
+    constexpr int k = NA - 1 - decltype(kc)::value;
+    float s = row_bcast<15>(R[k]);
+    static_for<NA - 1 - k>([&](auto jc) {
+      constexpr int j = k + 1 + decltype(jc)::value;
+      s = __builtin_fmaf(-row_bcast<6 + j>(R[k]), x[j], s);
+    });
+    x[k] = s * row_bcast<6 + k>(R[k]);
+  });
 }
 
 // box-box contacts, normal from box 1 to box 2 (same algorithm as jh_engine.hip / the oracle); every contact goes to sk.push(pos, normal, dist)

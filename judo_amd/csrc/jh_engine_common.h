@@ -92,11 +92,15 @@ __device__ __forceinline__ void inertia_mul(float* r, const float* Rk, const flo
   float t[3]; mulMTV(t, Rk, v); t[0] *= di[0]; t[1] *= di[1]; t[2] *= di[2]; mulMV(r, Rk, t);
 }
 
+// The smallest squared tangential part that counts as one: the smallest normal fp32 number.  v_rsq_f32 flushes a denormal input to zero and returns infinity, which
+// T = T2 * iT turned into an infinite T and a NaN force; a T2 below this (a tangential part under 1.1e-19) is the T == 0 case, as a T2 that underflowed to 0 always was.
+constexpr float CONE_T2_MIN = 1.17549435e-38f;
+
 // elliptic-cone contact: force = -ds/djar, cost s, Hessian block W (sym 3x3: 00,10,11,20,21,22)
 __device__ __forceinline__ float cone_eval(const float* jar, const float* D, float Dm, float mu, float fri, float* f, float* W) {
   float U0 = jar[0] * mu, U1 = jar[1] * fri, U2 = jar[2] * fri;
   float N = U0, T2 = U1 * U1 + U2 * U2;
-  float iT = T2 > 0.f ? __frsqrt_rn(T2) : 0.f, T = T2 * iT;
+  float iT = T2 >= CONE_T2_MIN ? __frsqrt_rn(T2) : 0.f, T = T2 * iT;
   // (T >= 0 and mu > 0: the degenerate cases T == 0 of MuJoCo's zone tests -- top if N >= 0, bottom if N < 0 -- are the same two comparisons; spelled out as `||` of a second
   // clause they cost two exec-mask round trips each)
   if (N >= mu * T) { f[0] = f[1] = f[2] = 0.f; for (int k = 0; k < 6; k++) W[k] = 0.f; return 0.f; }
@@ -116,12 +120,13 @@ __device__ __forceinline__ float cone_eval(const float* jar, const float* D, flo
 }
 
 // cone_eval in two steps, for callers that skip a separated contact (the top zone) before anything else: cone_top returns the zone test and keeps the quantities the
-// other two zones need; cone_below is cone_eval's bottom / middle part, expression for expression (same bits)
+// other two zones need; cone_below is cone_eval's bottom / middle part, expression for expression.  The same values up to rounding, NOT the same bits: the compiler
+// contracts each inlined copy into fma on its own (the test kernel's two copies differ in W's last bit on two cases of three, tests/test_gpu_solver_blocks.py)
 struct ConeZ { float U1, U2, N, iT, T; };
 __device__ __forceinline__ bool cone_top(const float* jar, float mu, float fri, ConeZ& z) {
   float U0 = jar[0] * mu, U1 = jar[1] * fri, U2 = jar[2] * fri;
   float N = U0, T2 = U1 * U1 + U2 * U2;
-  float iT = T2 > 0.f ? __frsqrt_rn(T2) : 0.f, T = T2 * iT;
+  float iT = T2 >= CONE_T2_MIN ? __frsqrt_rn(T2) : 0.f, T = T2 * iT;
   z.U1 = U1; z.U2 = U2; z.N = N; z.iT = iT; z.T = T;
   return N >= mu * T;
 }
@@ -146,7 +151,7 @@ __device__ __forceinline__ void cone_below(const float* jar, const float* D, flo
 // Dm = D0 / (mu^2 (1 + mu^2)) is a per-contact constant supplied by the caller.
 __device__ __forceinline__ void cone_dir(const float* jar, const float* jp, const float* D, float Dm, float mu, float fri, float* d1, float* d2) {
   const float U1 = jar[1] * fri, U2 = jar[2] * fri, N = jar[0] * mu, T2 = U1 * U1 + U2 * U2;
-  const float iT = T2 > 0.f ? __frsqrt_rn(T2) : 0.f, T = T2 * iT;
+  const float iT = T2 >= CONE_T2_MIN ? __frsqrt_rn(T2) : 0.f, T = T2 * iT;
   const bool top = N >= mu * T;             // (T == 0: N >= 0, MuJoCo's degenerate top case)
   const bool bottom = mu * N + T <= 0.f;    // (T == 0: N <= 0; N == 0 is `top`, which the selects below test first)
   const float b1 = D[0] * jar[0] * jp[0] + D[1] * jar[1] * jp[1] + D[2] * jar[2] * jp[2];

@@ -146,35 +146,6 @@ __device__ __forceinline__ void lane_rows_dir(const Slot* sl, const DofRows& dr,
   *d1 = g1; *d2 = g2;
 }
 
-// 4x4 Cholesky (packed lower) + triangular solves on registers; the diagonal is kept as its reciprocal (one v_rsq per
-// pivot, no divisions in the solves)
-__device__ __forceinline__ void chol4(float* L, float* inv) {
-#pragma unroll
-  for (int i = 0; i < 4; i++)
-#pragma unroll
-    for (int j = 0; j <= i; j++) {
-      float s = L[tri(i, j)];
-#pragma unroll
-      for (int k = 0; k < j; k++) s -= L[tri(i, k)] * L[tri(j, k)];
-      if (i == j) { float r = __frsqrt_rn(fmaxf(s, 1e-30f)); inv[i] = r; L[tri(i, i)] = s * r; }
-      else L[tri(i, j)] = s * inv[j];
-    }
-}
-__device__ __forceinline__ void fwd4(const float* L, const float* inv, float* x) {
-#pragma unroll
-  for (int i = 0; i < 4; i++) { float s = x[i];
-#pragma unroll
-    for (int k = 0; k < i; k++) s -= L[tri(i, k)] * x[k];
-    x[i] = s * inv[i]; }
-}
-__device__ __forceinline__ void bwd4(const float* L, const float* inv, float* x) {
-#pragma unroll
-  for (int i = 3; i >= 0; i--) { float s = x[i];
-#pragma unroll
-    for (int k = i + 1; k < 4; k++) s -= L[tri(k, i)] * x[k];
-    x[i] = s * inv[i]; }
-}
-
 struct LaneConst {  // per-lane model constants (own joint / actuator / dof rows), loaded once
   float damp, kvd, kp, kv, clo, chi, clim, fl, fB, fD, invw, limited, lo, hi, lK, lB, si[5];
 };

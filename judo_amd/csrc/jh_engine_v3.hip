@@ -151,32 +151,6 @@ __device__ __forceinline__ void lane_rows_dir(const Slot3* sl, const SlotF* sf, 
   *d1 = g1; *d2 = g2;
 }
 
-// dense Cholesky + solve of an n x n system held in registers (packed lower L, reciprocal diagonal), redundantly per lane
-template <int N_>
-__device__ __forceinline__ void chol_solve(float* L, float* x) {
-  float inv[N_];
-#pragma unroll
-  for (int i = 0; i < N_; i++)
-#pragma unroll
-    for (int j = 0; j <= i; j++) {
-      float s = L[tri(i, j)];
-#pragma unroll
-      for (int k = 0; k < j; k++) s -= L[tri(i, k)] * L[tri(j, k)];
-      if (i == j) { float rr = __frsqrt_rn(fmaxf(s, 1e-30f)); inv[i] = rr; L[tri(i, i)] = s * rr; }
-      else L[tri(i, j)] = s * inv[j];
-    }
-#pragma unroll
-  for (int i = 0; i < N_; i++) { float s = x[i];
-#pragma unroll
-    for (int k = 0; k < i; k++) s -= L[tri(i, k)] * x[k];
-    x[i] = s * inv[i]; }
-#pragma unroll
-  for (int i = N_ - 1; i >= 0; i--) { float s = x[i];
-#pragma unroll
-    for (int k = i + 1; k < N_; k++) s -= L[tri(k, i)] * x[k];
-    x[i] = s * inv[i]; }
-}
-
 __device__ __forceinline__ void rodrigues(float* Rq, const float* al, float sn, float cs) {
   float t = 1.f - cs, x = al[0], y = al[1], z = al[2];
   Rq[0] = t * x * x + cs; Rq[1] = t * x * y - sn * z; Rq[2] = t * x * z + sn * y;

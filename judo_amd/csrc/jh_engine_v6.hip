@@ -20,12 +20,6 @@ using namespace jh_coop;
 #include <utility>
 
 namespace {
-template <int N, class F, int... I>
-__device__ __forceinline__ void static_for_impl(F&& f, std::integer_sequence<int, I...>) { (f(std::integral_constant<int, I>{}), ...); }
-template <int N, class F>
-__device__ __forceinline__ void static_for(F&& f) { static_for_impl<N>(f, std::make_integer_sequence<int, N>{}); }  // f(integral_constant<int, 0>) ... f(<N - 1>): compile-time indices for DPP controls
-
-
 #ifndef JH_V6_SELF
 #define JH_V6_SELF 0  // 1 (jh_engine_v6_self.hip): the build for an image with every pair the MJCF leaves (engine_model.pack_engine_model on a description with "self_collision"):
                       // arm bodies against each other -- link capsule against link capsule, hand / finger box against link capsule -- as general contacts whose two sides
@@ -310,57 +304,6 @@ __device__ __forceinline__ void lane_rows_dir(const Slot6* sl, const SlotF* sf, 
   if (dr.lims != 0.f) { float jp = dr.pl, x = fmaf(al, jp, dr.jl); if (x < 0.f) { g1 += dr.lD * x * jp; g2 += dr.lD * jp * jp; } }
   if (eq_lane) { float x = fmaf(al, ejp, ejar); g1 += eD * x * ejp; g2 += eD * ejp * ejp; }
   *d1 = g1; *d2 = g2;
-}
-
-// dense Cholesky + solve of an n x n system held in registers (packed lower L, reciprocal diagonal), redundantly per lane
-template <int N_>
-__device__ __forceinline__ void chol_solve(float* L, float* x) {
-  float inv[N_];
-#pragma unroll
-  for (int i = 0; i < N_; i++)
-#pragma unroll
-    for (int j = 0; j <= i; j++) {
-      float s = L[tri(i, j)];
-#pragma unroll
-      for (int k = 0; k < j; k++) s -= L[tri(i, k)] * L[tri(j, k)];
-      if (i == j) { float rr = __frsqrt_rn(fmaxf(s, 1e-30f)); inv[i] = rr; L[tri(i, i)] = s * rr; }
-      else L[tri(i, j)] = s * inv[j];
-    }
-#pragma unroll
-  for (int i = 0; i < N_; i++) { float s = x[i];
-#pragma unroll
-    for (int k = 0; k < i; k++) s -= L[tri(i, k)] * x[k];
-    x[i] = s * inv[i]; }
-#pragma unroll
-  for (int i = N_ - 1; i >= 0; i--) { float s = x[i];
-#pragma unroll
-    for (int k = i + 1; k < N_; k++) s -= L[tri(k, i)] * x[k];
-    x[i] = s * inv[i]; }
-}
-
-// The arm's 9 x 9 system with its rows spread over the arm's lanes (lane 6 + a holds row a, entries b <= a; lane 15 the right-hand side as a tenth row): right-looking
-// Cholesky and both triangular solves with DPP row broadcasts, every entry receiving its subtractions in the order of chol_solve<9> (the same bits); every lane gets x.
-// Replaces the factorisation every lane did redundantly on its own copy of the 45 entries.
-__device__ __forceinline__ void arm_chol_solve(float* R, float* x, int l) {
-  static_for<NA>([&](auto kc) {
-    constexpr int k = decltype(kc)::value;
-    const float rinv = __frsqrt_rn(fmaxf(row_bcast<6 + k>(R[k]), 1e-30f));
-    const float lk = R[k] * rinv;
-    R[k] = l == 6 + k ? rinv : lk;
-    static_for<NA - 1 - k>([&](auto jc) {
-      constexpr int j = k + 1 + decltype(jc)::value;
-      R[j] = __builtin_fmaf(-lk, row_bcast<6 + j>(lk), R[j]);
-    });
-  });
-  static_for<NA>([&](auto kc) {
-    constexpr int k = NA - 1 - decltype(kc)::value;
-    float s = row_bcast<15>(R[k]);
-    static_for<NA - 1 - k>([&](auto jc) {
-      constexpr int j = k + 1 + decltype(jc)::value;
-      s = __builtin_fmaf(-row_bcast<6 + j>(R[k]), x[j], s);
-    });
-    x[k] = s * row_bcast<6 + k>(R[k]);
-  });
 }
 
 __device__ __forceinline__ void rodrigues(float* Rq, const float* al, float sn, float cs) {

@@ -18,6 +18,7 @@ import numpy as np
 import pytest
 
 from oracle import oracle as O
+from tests.blocks import impedance as _impedance
 
 G = 9.81
 
@@ -35,18 +36,6 @@ def _sphere_on_plane(cone="elliptic", impratio=1.0, mu=0.5, gravity=(0.0, 0.0, -
     desc = dict(task="ball", source="tests", option=dict(timestep=dt, integrator="implicitfast", cone=cone, impratio=impratio, gravity=list(gravity), contact=True),
                 bodies=[world, cube], joints=[jnt], geoms=[plane, ball], sites=[], actuators=[], sensors=[], excludes=[], equalities=[], nsensordata=0)
     return O.Model("ball", desc), r, m
-
-
-def _impedance(si, dist):
-    d0, d1, width, mid, power = si
-    x = min(abs(dist) / width, 1.0)
-    if power == 1:
-        y = x
-    elif x <= mid:
-        y = x**power / mid ** (power - 1)
-    else:
-        y = 1 - (1 - x) ** power / (1 - mid) ** (power - 1)
-    return d0 + y * (d1 - d0)
 
 
 @pytest.mark.parametrize("cone", ["elliptic", "pyramidal"])
