@@ -763,6 +763,33 @@ int jh_plant_residuals(const float* pred /* DEVICE, (M * W, H, nx) */, const flo
                        const int* quat_adr /* HOST, nquat offsets, or NULL with nquat = 0 */, int nquat, int M, int W, int H, int nx, int nq, float* err /* DEVICE, M x ld */,
                        int ld, void* stream);
 
+/* ---- jh_plant_residuals_reports: jh_plant_residuals for a robot's reports.  An entry of obs or obs_sens that is NaN was NOT REPORTED: it is no evidence for or against
+ * any plant.  One rule covers reports slower than the model's step (whole step rows are NaN), partial reports (the velocity columns are NaN) and dropped readings.
+ * Sensor readings can be evidence beside the states, and the predictions may lie plant-major or window-major.
+ * Layout: the prediction of plant m on window w is window-row m * plant_stride + w * window_stride of pred, a window-row being (H, nx), contiguous; the same window-row
+ * index addresses pred_sens, whose rows are (H, ns) -- states and sensors come out of one launch in the same rollout order.  The plants launch of a model set is
+ * plant-major (plant_stride = W, window_stride = 1); jh_policy_rollout_plants with a problem per window is window-major (plant_stride = 1, window_stride = M).  Both
+ * strides are at least 1.  obs is (W, H, nx), obs_sens (W, H, ns); weight (nx) and weight_sens (ns) are 1 / sigma^2.  ns = 0 with three null sensor pointers: no sensor
+ * evidence.  quat_adr, nquat, nq, H, ld: as for jh_plant_residuals.
+ * The arithmetic is fixed, all of it in fp32 with every product and sum rounded on its own (no fused multiply-add); judo_amd/reports.py plant_residuals_reports_host
+ * restates it bit for bit:
+ *   per step and quaternion   dot = ((p0 * o0 + p1 * o1) + p2 * o2) + p3 * o3 as in jh_plant_residuals; a NaN among the four observed coordinates makes dot NaN, hence
+ *                             no flip;
+ *   per state coordinate d    if obs[d] is NaN -- on the bits: (bits & 0x7fffffff) > 0x7f800000 -- t_d = +0.0, and neither pred[d] nor weight[d] enters; otherwise
+ *                             e = p - o', t_d = (weight[d] * e) * e;
+ *   per step h                s_h = t_0, then s_h = s_h + t_d, d ascending; the ns sensor coordinates continue the same sum in ascending order under the same NaN rule
+ *                             with weight_sens (they have no quaternions);
+ *   per window                the 64-slot halving of jh_plant_residuals.
+ * With no NaN in obs, ns = 0 and plant-major strides the result is bit for bit that of jh_plant_residuals: a skipped term adds +0.0 to a non-negative sum, which is
+ * exact.  A window with nothing reported has error exactly +0.0 for every plant.  A NaN prediction under a reported entry gives NaN out (the estimators count it as
+ * +inf); under an unreported one it is not read into the sum.  Observed infinities are outside the contract.
+ * JH_ERR_INVALID before anything is enqueued, jh_last_error naming the argument: everything jh_plant_residuals refuses; ns < 0; ns > 0 with a null pred_sens, obs_sens
+ * or weight_sens; ns = 0 with one of them not null; a stride of 0. */
+int jh_plant_residuals_reports(const float* pred /* DEVICE, window-rows of (H, nx) */, const float* obs /* DEVICE, (W, H, nx) */, const float* weight /* DEVICE, nx */,
+                               const int* quat_adr /* HOST, nquat offsets, or NULL with nquat = 0 */, int nquat, const float* pred_sens /* DEVICE, window-rows of (H, ns), or NULL */,
+                               const float* obs_sens /* DEVICE, (W, H, ns), or NULL */, const float* weight_sens /* DEVICE, ns, or NULL */, int ns, size_t plant_stride,
+                               size_t window_stride, int M, int W, int H, int nx, int nq, float* err /* DEVICE, M x ld */, int ld, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -52,6 +52,8 @@ _SIGNATURES = {
     "jh_rollout_materialize_plants": (C.c_int, [C.c_void_p, C.POINTER(C.c_int), C.c_int, C.c_int, f32p, C.c_int, f32p, C.c_int, C.c_int, f32p, f32p, C.c_void_p]),
     "jh_fr3_rollout_materialize_plants": (C.c_int, [C.c_void_p, C.POINTER(C.c_int), C.c_int, C.c_int, f32p, C.c_int, f32p, C.c_int, C.c_int, f32p, f32p, C.c_void_p]),
     "jh_plant_residuals": (C.c_int, [f32p, f32p, f32p, C.POINTER(C.c_int), C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, f32p, C.c_int, C.c_void_p]),
+    "jh_plant_residuals_reports": (C.c_int, [f32p, f32p, f32p, C.POINTER(C.c_int), C.c_int, f32p, f32p, f32p, C.c_int, C.c_size_t, C.c_size_t, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, f32p,
+                                             C.c_int, C.c_void_p]),
     "jh_task_reward": (C.c_int, [C.c_void_p, f32p, f32p, f32p, f32p, C.c_int, C.c_int, C.c_int, f32p, C.c_void_p]),
     "jh_noise_normal": (C.c_int, [C.c_ulonglong, C.c_uint, C.c_int, C.c_int, C.c_int, f32p, C.c_int, C.c_void_p]),
     "jh_sample_knots": (C.c_int, [f32p, f32p, C.c_int, f32p, f32p, C.c_int, C.c_int, C.c_int, C.c_int, f32p, C.c_void_p]),

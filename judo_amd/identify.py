@@ -132,7 +132,96 @@ def _refuse_spot(what) -> None:
                          "to include, which a PlantEstimator does not record; it identifies the plants of a GpuModelSet")
 
 
-class PlantEstimator:
+class PlantBelief:
+    """What every estimator of the plant shares (`PlantEstimator` here, `ReportEstimator` and `SpotReportEstimator` of judo_amd/reports.py): the count of windows in a ring
+    buffer of `windows` slots, the posterior arithmetic on the (M, filled windows) errors a subclass's `_score` returns, and the hand-over to a controller.  A subclass
+    sets `num_plants` and calls `_init_belief`, owns the ring buffer's tensors, and advances `_pushed` when it records a window."""
+
+    def _init_belief(self, horizon, windows, prior, temperature: float, discount: float) -> None:
+        if int(horizon) != horizon or not 1 <= int(horizon) <= MAX_ID_HORIZON:
+            raise ValueError(f"horizon = {horizon} outside [1, {MAX_ID_HORIZON}] (include/judo_amd.h JH_MAX_ID_HORIZON)")
+        if int(windows) != windows or int(windows) < 1:
+            raise ValueError(f"windows = {windows} must be at least 1")
+        self.horizon, self.windows = int(horizon), int(windows)
+        if not temperature > 0:
+            raise ValueError(f"temperature = {temperature} must be positive")
+        if not 0 < discount <= 1:
+            raise ValueError(f"discount = {discount} outside (0, 1]")
+        self.temperature, self.discount = float(temperature), float(discount)
+        self._prior0 = self.prior = check_prior(prior, self.num_plants)
+
+    def reset(self, prior=None) -> None:
+        """Empty the ring buffer and the pending window; `prior` replaces the prior (None: the one of construction)."""
+        self.prior = self._prior0 if prior is None else check_prior(prior, self.num_plants)
+        self._pushed = 0  # windows pushed since the reset: window i lives in slot i % windows
+        self._pending: list[tuple[np.ndarray, np.ndarray, np.ndarray]] = []
+        self._posterior = None
+        self.errors = np.zeros((self.num_plants, 0), dtype=np.float32)
+        self.log_likelihood = np.zeros(self.num_plants)
+        self.degenerate = False
+
+    def __len__(self) -> int:
+        return min(self._pushed, self.windows)
+
+    def _slots(self) -> list[int]:
+        """The filled slots of the ring buffer, oldest window first."""
+        return [i % self.windows for i in range(max(0, self._pushed - self.windows), self._pushed)]
+
+    def update(self) -> np.ndarray:
+        """The posterior over the M plants, (M,) fp64, from the filled windows (the prior with none).  Leaves `errors` (M, filled windows; oldest first), `log_likelihood`
+        (M,: -0.5 * the discounted sum of a plant's errors, before the temperature), `map` and `degenerate` behind."""
+        self.errors = self._score() if len(self) else np.zeros((self.num_plants, 0), dtype=np.float32)
+        self._posterior, self.log_likelihood, self.degenerate = posterior_from_errors(self.errors, self.prior, self.temperature, self.discount)
+        return self._posterior.copy()
+
+    @property
+    def posterior(self) -> np.ndarray:
+        """The posterior of the windows recorded so far (`update()` if a window arrived since the last one)."""
+        if self._posterior is None:
+            self.update()
+        return self._posterior.copy()
+
+    @property
+    def map(self) -> int:
+        """The plant of largest posterior, ties to the lower index."""
+        return int(np.argmax(self.posterior))
+
+    # ---- the hand-over -------------------------------------------------------------------------------------------------------------------------------------------
+    def apply(self, ctrl, floor: float = 0.25) -> np.ndarray:
+        """A randomised controller's next assignment from the posterior: `ctrl.set_weights((1 - floor) * posterior + floor / M)`, returned.  With `floor` > 0 every plant
+        keeps a remainder in the apportionment (`plants.blocks_from_weights`), so evidence against the current belief can still arrive.  `ctrl` is a controller with an
+        `Assignment`: `RandomizedController`, `MaterializedRandomizedController` and their fr3 forms.  An ensemble controller is refused here: it has no assignment; `apply_risk`
+        hands it the posterior as the weights of its plant-weighted risk measure."""
+        if not 0 <= floor <= 1:
+            raise ValueError(f"floor = {floor} outside [0, 1]")
+        if isinstance(ctrl, WorstCase):
+            raise ValueError(f"ctrl is a {type(ctrl).__name__}, an ensemble controller: its risk measure has no plant weights (a plant-weighted risk measure is out of "
+                             f"scope).  Follow the belief with ctrl.set_member on the MAP plant's neighbours, or prune the set")
+        if not isinstance(ctrl, Assignment):
+            raise ValueError(f"ctrl is a {type(ctrl).__name__}, which has no assignment of rollout blocks to plants: apply needs a RandomizedController, a "
+                             f"MaterializedRandomizedController or one of their fr3 forms")
+        w = (1.0 - float(floor)) * self.posterior + float(floor) / self.num_plants
+        ctrl.set_weights(w)
+        return w
+
+    def apply_risk(self, ctrl, floor: float = 0.0, tail: float | None = None) -> np.ndarray:
+        """An ensemble controller's plant-weighted risk measure from the posterior: `ctrl.set_weights((1 - floor) * posterior + floor / M, tail)`, the weights returned.
+        From the next plan step on a candidate's cost is the tail mean of its member costs under these weights (`plants.WorstCase.set_weights`), so a plant the
+        observed steps have ruled out no longer drives the plan.  `floor` > 0 keeps every plant at a positive weight; `tail` None keeps the controller's tail mass.
+        `ctrl` is a controller with a `WorstCase`: `EnsembleController`, `MaterializedEnsembleController`, their fr3 forms and `SpotEnsembleController`; a randomised
+        controller follows the belief with `apply`."""
+        if not 0 <= floor <= 1:
+            raise ValueError(f"floor = {floor} outside [0, 1]")
+        if not isinstance(ctrl, WorstCase):
+            raise ValueError(f"ctrl is a {type(ctrl).__name__}, which has no risk measure over its plants: apply_risk needs an EnsembleController, a "
+                             f"MaterializedEnsembleController, one of their fr3 forms or a SpotEnsembleController"
+                             + ("; a randomised controller follows the belief with apply" if isinstance(ctrl, Assignment) else ""))
+        w = (1.0 - float(floor)) * self.posterior + float(floor) / self.num_plants
+        ctrl.set_weights(w, tail)
+        return w
+
+
+class PlantEstimator(PlantBelief):
     """A posterior over the M plants of a `GpuModelSet` (cartpole, cylinder_push, the leap family, fr3_pick) from recorded windows of `horizon` model steps.
 
         est = PlantEstimator(model_set, horizon=8, windows=16)   # or PlantEstimator.for_controller(ctrl), which reads ctrl.model_set on every update()
@@ -156,17 +245,7 @@ class PlantEstimator:
         self._ctrl, self._set = _controller, model_set
         first = model_set.models[0]
         self.num_plants, self.nx, self.nu, self.nq = len(model_set.models), int(first.nx), int(first.nu), int(first.nq)
-        if int(horizon) != horizon or not 1 <= int(horizon) <= MAX_ID_HORIZON:
-            raise ValueError(f"horizon = {horizon} outside [1, {MAX_ID_HORIZON}] (include/judo_amd.h JH_MAX_ID_HORIZON)")
-        if int(windows) != windows or int(windows) < 1:
-            raise ValueError(f"windows = {windows} must be at least 1")
-        self.horizon, self.windows = int(horizon), int(windows)
-        if not temperature > 0:
-            raise ValueError(f"temperature = {temperature} must be positive")
-        if not 0 < discount <= 1:
-            raise ValueError(f"discount = {discount} outside (0, 1]")
-        self.temperature, self.discount = float(temperature), float(discount)
-        self._prior0 = self.prior = check_prior(prior, self.num_plants)
+        self._init_belief(horizon, windows, prior, temperature, discount)
         sigma = np.ones(self.nx) if state_sigma is None else np.asarray(state_sigma, dtype=np.float64)
         if sigma.ndim == 0:
             sigma = np.full(self.nx, float(sigma))
@@ -198,23 +277,6 @@ class PlantEstimator:
         return self._ctrl.model_set if self._ctrl is not None else self._set
 
     # ---- recording -----------------------------------------------------------------------------------------------------------------------------------------------
-    def reset(self, prior=None) -> None:
-        """Empty the ring buffer and the pending window; `prior` replaces the prior (None: the one of construction)."""
-        self.prior = self._prior0 if prior is None else check_prior(prior, self.num_plants)
-        self._pushed = 0  # windows pushed since the reset: window i lives in slot i % windows
-        self._pending: list[tuple[np.ndarray, np.ndarray, np.ndarray]] = []
-        self._posterior = None
-        self.errors = np.zeros((self.num_plants, 0), dtype=np.float32)
-        self.log_likelihood = np.zeros(self.num_plants)
-        self.degenerate = False
-
-    def __len__(self) -> int:
-        return min(self._pushed, self.windows)
-
-    def _slots(self) -> list[int]:
-        """The filled slots of the ring buffer, oldest window first."""
-        return [i % self.windows for i in range(max(0, self._pushed - self.windows), self._pushed)]
-
     def _recorded_device(self) -> tuple[torch.Tensor, torch.Tensor, torch.Tensor]:
         """(x0, controls, states) of the filled windows on the device, oldest first."""
         W = len(self)
@@ -301,58 +363,5 @@ class PlantEstimator:
     def _score(self) -> np.ndarray:
         return self._residuals(*self._predict())
 
-    def update(self) -> np.ndarray:
-        """The posterior over the M plants, (M,) fp64, from the filled windows (the prior with none).  Leaves `errors` (M, filled windows; oldest first), `log_likelihood`
-        (M,: -0.5 * the discounted sum of a plant's errors, before the temperature), `map` and `degenerate` behind."""
-        self.errors = self._score() if len(self) else np.zeros((self.num_plants, 0), dtype=np.float32)
-        self._posterior, self.log_likelihood, self.degenerate = posterior_from_errors(self.errors, self.prior, self.temperature, self.discount)
-        return self._posterior.copy()
 
-    @property
-    def posterior(self) -> np.ndarray:
-        """The posterior of the windows recorded so far (`update()` if a window arrived since the last one)."""
-        if self._posterior is None:
-            self.update()
-        return self._posterior.copy()
-
-    @property
-    def map(self) -> int:
-        """The plant of largest posterior, ties to the lower index."""
-        return int(np.argmax(self.posterior))
-
-    # ---- the hand-over -------------------------------------------------------------------------------------------------------------------------------------------
-    def apply(self, ctrl, floor: float = 0.25) -> np.ndarray:
-        """A randomised controller's next assignment from the posterior: `ctrl.set_weights((1 - floor) * posterior + floor / M)`, returned.  With `floor` > 0 every plant
-        keeps a remainder in the apportionment (`plants.blocks_from_weights`), so evidence against the current belief can still arrive.  `ctrl` is a controller with an
-        `Assignment`: `RandomizedController`, `MaterializedRandomizedController` and their fr3 forms.  An ensemble controller is refused here: it has no assignment; `apply_risk`
-        hands it the posterior as the weights of its plant-weighted risk measure."""
-        if not 0 <= floor <= 1:
-            raise ValueError(f"floor = {floor} outside [0, 1]")
-        if isinstance(ctrl, WorstCase):
-            raise ValueError(f"ctrl is a {type(ctrl).__name__}, an ensemble controller: its risk measure has no plant weights (a plant-weighted risk measure is out of "
-                             f"scope).  Follow the belief with ctrl.set_member on the MAP plant's neighbours, or prune the set")
-        if not isinstance(ctrl, Assignment):
-            raise ValueError(f"ctrl is a {type(ctrl).__name__}, which has no assignment of rollout blocks to plants: apply needs a RandomizedController, a "
-                             f"MaterializedRandomizedController or one of their fr3 forms")
-        w = (1.0 - float(floor)) * self.posterior + float(floor) / self.num_plants
-        ctrl.set_weights(w)
-        return w
-
-    def apply_risk(self, ctrl, floor: float = 0.0, tail: float | None = None) -> np.ndarray:
-        """An ensemble controller's plant-weighted risk measure from the posterior: `ctrl.set_weights((1 - floor) * posterior + floor / M, tail)`, the weights returned.
-        From the next plan step on a candidate's cost is the tail mean of its member costs under these weights (`plants.WorstCase.set_weights`), so a plant the
-        observed steps have ruled out no longer drives the plan.  `floor` > 0 keeps every plant at a positive weight; `tail` None keeps the controller's tail mass.
-        `ctrl` is a controller with a `WorstCase`: `EnsembleController`, `MaterializedEnsembleController`, their fr3 forms and `SpotEnsembleController`; a randomised
-        controller follows the belief with `apply`."""
-        if not 0 <= floor <= 1:
-            raise ValueError(f"floor = {floor} outside [0, 1]")
-        if not isinstance(ctrl, WorstCase):
-            raise ValueError(f"ctrl is a {type(ctrl).__name__}, which has no risk measure over its plants: apply_risk needs an EnsembleController, a "
-                             f"MaterializedEnsembleController, one of their fr3 forms or a SpotEnsembleController"
-                             + ("; a randomised controller follows the belief with apply" if isinstance(ctrl, Assignment) else ""))
-        w = (1.0 - float(floor)) * self.posterior + float(floor) / self.num_plants
-        ctrl.set_weights(w, tail)
-        return w
-
-
-__all__ = ["MAX_ID_HORIZON", "MAX_ID_QUATS", "PlantEstimator", "check_prior", "check_quat_adr", "plant_residuals_host", "posterior_from_errors"]
+__all__ = ["MAX_ID_HORIZON", "MAX_ID_QUATS", "PlantBelief", "PlantEstimator", "check_prior", "check_quat_adr", "plant_residuals_host", "posterior_from_errors"]
