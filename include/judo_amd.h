@@ -790,6 +790,54 @@ int jh_plant_residuals_reports(const float* pred /* DEVICE, window-rows of (H, n
                                const float* obs_sens /* DEVICE, (W, H, ns), or NULL */, const float* weight_sens /* DEVICE, ns, or NULL */, int ns, size_t plant_stride,
                                size_t window_stride, int M, int W, int H, int nx, int nq, float* err /* DEVICE, M x ld */, int ld, void* stream);
 
+/* ---- The plant side of the closed loop (judo/app/dora/simulation.py:52-82, judo/simulation/mj_simulation.py:33-46, for B plants at once): B device-resident plants
+ * advance S physics steps on the splines their controllers planned.  judo_amd/simulation.py restates the two kernels' arithmetic (plant_controls_host,
+ * plant_reports_host) and holds the plants (PlantFleet).  All arithmetic in fp32, every product and sum rounded on its own (no fused multiply-add).
+ *
+ * jh_plant_controls: B splines at their plants' own clocks.  controls[b, step0 + s, u] = sum_k W[b, s, k] * knots[b, k, u] for s < S: acc = W[b,s,0] * knots[b,0,u],
+ * then acc = acc + W[b,s,k] * knots[b,k,u], k ascending; then, where ctrl_lo_hi (nu lower bounds, then nu upper bounds) is given, acc < lo -> lo and acc > hi -> hi in
+ * the order of the values' bits (-0.0 below +0.0; a NaN passes through).  W is (B, S, K), plant b's rows built on the host by spline_weights for its knot times and its
+ * clock; knots are (K, nu) per plant, knot_stride floats from one plant's to the next; controls is (B, ld_steps, nu), so a call fills steps step0 .. step0 + S - 1 of a
+ * longer segment and writes no other word.  Grid (workgroups over S * nu, B).
+ * JH_ERR_INVALID before anything is enqueued, jh_last_error naming the argument: a null W, knots or controls; B outside 1..JH_MAX_FLEET_PLANT_BLOCKS; S, K or nu < 1;
+ * K * nu > JH_MAX_KNOT_DIM; B > 1 with knot_stride < K * nu; step0 < 0; ld_steps < step0 + S. */
+int jh_plant_controls(const float* W /* DEVICE, (B, S, K) */, const float* knots /* DEVICE */, size_t knot_stride, const float* ctrl_lo_hi /* DEVICE, 2 * nu, or NULL */, int B,
+                      int S, int K, int nu, int step0, int ld_steps, float* controls /* DEVICE, (B, ld_steps, nu) */, void* stream);
+
+/* jh_plant_reports: what a robot reports of a segment, and the carry.  states is (B, S, nx) and sensors (B, S, ns) as a materialise launch wrote them.
+ *   reports[b, s, j] = states[b, s, j] + sigma[j] * noise[b, s, j] (the product, then the sum) where step s of plant b and column j are reported; just states[b, s, j]
+ *   where sigma or noise is NULL; NaN (0x7fc00000) where the step or the column is not reported.  noise is (B, S, nx), what jh_noise_normal(seed, draw, B * S, 0, nx,
+ *   noise, nx) draws.  Step s of plant b is reported when (count[b] + s + 1) % every == 0, count[b] being the steps plant b has taken before the segment: a stride that
+ *   does not divide S carries across segments.  Column j is reported when column_mask[j] != 0 (nx bytes on the device), or always with a NULL mask.
+ *   reports_sens likewise from sensors with noise_sens (B, S, ns), sigma_sens and column_mask_sens (ns); NULL: no sensor reports.
+ *   x[b, :] = states[b, S - 1, :]: the exact state, never the noisy one.
+ * With sigma NULL, every == 1 and no mask the reports are the states bit for bit.  With reports and reports_sens NULL the launch only carries.
+ * JH_ERR_INVALID before anything is enqueued: a null states, x or count; B outside 1..JH_MAX_FLEET_PLANT_BLOCKS; S or nx < 1; ns < 0; every < 1; a negative count,
+ * named with its plant; reports_sens with ns = 0 or a null sensors. */
+int jh_plant_reports(const float* states, const float* sensors /* or NULL */, int B, int S, int nx, int ns, const int* count /* HOST, B */, int every, const float* noise,
+                     const float* sigma, const unsigned char* column_mask, float* reports /* DEVICE, (B, S, nx), or NULL */, const float* noise_sens, const float* sigma_sens,
+                     const unsigned char* column_mask_sens, float* reports_sens /* DEVICE, (B, S, ns), or NULL */, float* x /* DEVICE, (B, nx) */, void* stream);
+
+/* jh_plants_advance: the whole chain in one call, three launches on `stream`:
+ *   1. k_plant_controls for steps step0 .. S - 1 of controls (B, S, nu) from W (B, S - step0, K) -- with step0 > 0 the caller has filled steps 0 .. step0 - 1 with a
+ *      jh_plant_controls call of its own: a plan that takes effect step0 steps after the state it was planned from;
+ *   2. the materialise launch on plants -- the launcher behind jh_rollout_materialize_plants, or behind jh_fr3_rollout_materialize_plants for an fr3_pick set --
+ *      with G = B blocks of n = 1 row, block b on plant truth[b], x0 batched from x (B, nq + nv), a row of controls per plant, H = S;
+ *   3. k_plant_reports, which also carries x.
+ * Contract: rows b of states (B, S, nq + nv) and sensors (B, S, nsensordata; may be NULL) are bit for bit what jh_rollout_materialize writes on plant truth[b]'s own
+ * jh_model from x[b] with those S controls.  x stays on the device between calls.
+ * The leap and fr3 kernels start their contact solver cold at the top of a launch: a plant carries the solver's warm start within a segment and not across segments
+ * (a MuJoCo plant carries qacc_warmstart from step to step).  DESIGN.md section 4.21.
+ * JH_ERR_INVALID before the first enqueue, jh_last_error naming the argument: everything the two entries above refuse; a null set or truth; step0 outside [0, S); a set
+ * of more than JH_MAX_ENSEMBLE members; a truth entry outside [0, M), named with its plant.  JH_ERR_UNSUPPORTED: a set whose member 0 runs another kernel generation
+ * than 3.  The set is a jh_model_set: a Spot tree set (jh_tree_set) is another type, its plant carries policy state and a solver warm start, and
+ * judo_amd.simulation.PlantFleet refuses it by name. */
+int jh_plants_advance(const jh_model_set* set, const int* truth /* HOST, B */, int B, float* x /* DEVICE, (B, nq + nv) */, const float* W /* DEVICE, (B, S - step0, K) */,
+                      const float* knots /* DEVICE */, size_t knot_stride, int K, const float* ctrl_lo_hi /* DEVICE, 2 * nu, or NULL */, int step0, int S,
+                      float* controls /* DEVICE, (B, S, nu) */, float* states /* DEVICE, (B, S, nq + nv) */, float* sensors /* DEVICE, (B, S, nsensordata), or NULL */,
+                      const int* count /* HOST, B */, int every, const float* noise, const float* sigma, const unsigned char* column_mask, float* reports, const float* noise_sens,
+                      const float* sigma_sens, const unsigned char* column_mask_sens, float* reports_sens, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -54,6 +54,10 @@ _SIGNATURES = {
     "jh_plant_residuals": (C.c_int, [f32p, f32p, f32p, C.POINTER(C.c_int), C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, f32p, C.c_int, C.c_void_p]),
     "jh_plant_residuals_reports": (C.c_int, [f32p, f32p, f32p, C.POINTER(C.c_int), C.c_int, f32p, f32p, f32p, C.c_int, C.c_size_t, C.c_size_t, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, f32p,
                                              C.c_int, C.c_void_p]),
+    "jh_plant_controls": (C.c_int, [f32p, f32p, C.c_size_t, f32p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, f32p, C.c_void_p]),
+    "jh_plant_reports": (C.c_int, [f32p, f32p, C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_int), C.c_int, f32p, f32p, C.c_void_p, f32p, f32p, f32p, C.c_void_p, f32p, f32p, C.c_void_p]),
+    "jh_plants_advance": (C.c_int, [C.c_void_p, C.POINTER(C.c_int), C.c_int, f32p, f32p, f32p, C.c_size_t, C.c_int, f32p, C.c_int, C.c_int, f32p, f32p, f32p, C.POINTER(C.c_int), C.c_int,
+                                    f32p, f32p, C.c_void_p, f32p, f32p, f32p, C.c_void_p, f32p, C.c_void_p]),
     "jh_task_reward": (C.c_int, [C.c_void_p, f32p, f32p, f32p, f32p, C.c_int, C.c_int, C.c_int, f32p, C.c_void_p]),
     "jh_noise_normal": (C.c_int, [C.c_ulonglong, C.c_uint, C.c_int, C.c_int, C.c_int, f32p, C.c_int, C.c_void_p]),
     "jh_sample_knots": (C.c_int, [f32p, f32p, C.c_int, f32p, f32p, C.c_int, C.c_int, C.c_int, C.c_int, f32p, C.c_void_p]),

@@ -799,6 +799,10 @@ extern "C" int jh_model_set_info(const jh_model_set* s, int* out) {
   return JH_OK;
 }
 
+// The set's member 0 and its members, for jh_plants.hip: jh_plants_advance checks the kind and the dimensions in front of its first enqueue (jh_internal.h).
+const jh_model* jh_model_set_member0(const jh_model_set* s) { return s->m0; }
+int jh_model_set_members(const jh_model_set* s) { return s->B; }
+
 extern "C" void jh_model_set_destroy(jh_model_set* s) {
   if (!s) return;
   if (s->d_images) (void)hipFree(s->d_images);

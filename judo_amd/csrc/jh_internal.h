@@ -187,6 +187,10 @@ extern __attribute__((visibility("hidden"))) const jh_engine_build jh_simple_bui
 extern __attribute__((visibility("hidden"))) const jh_engine_build jh_engine5_build, jh_engine5_build_cap64, jh_engine5_build_cyl;  // jh_engine_v5.hip: the leap kernel for 48 and 64 contacts, and with cylinders
 extern __attribute__((visibility("hidden"))) const jh_engine_build jh_engine6_build, jh_engine6_build_self;  // jh_engine_v6.hip: the fr3 kernel, and with the arm's own pairs (jh_model::arm_pairs > 0)
 
+// jh_api.hip: what jh_plants.hip reads of a model set (the structure is that file's own): member 0, whose kind and dimensions are the set's, and the members
+__attribute__((visibility("hidden"))) const jh_model* jh_model_set_member0(const jh_model_set* set);
+__attribute__((visibility("hidden"))) int jh_model_set_members(const jh_model_set* set);
+
 // The words of jh_model::d_stats that every product build writes and the host reads (jh_model_stats, jh_model_recomputed_units): contact-cap overflows, Newton iteration-cap
 // hits, Newton iterations, steps; wave-level iterations, steps; leap queue units whose hand-off was missed and which recomputed their group up to their slice.  The rest
 // belongs to diagnostic builds.
