@@ -175,9 +175,113 @@ def test_library_limits_agree_with_the_header():
     from judo_amd import _lib
 
     header = open(os.path.join(ROOT, "include", "judo_amd.h")).read()
-    for name, val in (("JH_MAX_KNOT_DIM", _lib.MAX_KNOT_DIM), ("JH_MAX_ELITES", _lib.MAX_ELITES), ("JH_MAX_TASK_PARAMS", _lib.MAX_TASK_PARAMS)):
+    limits = (("JH_MAX_KNOT_DIM", _lib.MAX_KNOT_DIM), ("JH_MAX_ELITES", _lib.MAX_ELITES), ("JH_MAX_TASK_PARAMS", _lib.MAX_TASK_PARAMS), ("JH_MAX_ENSEMBLE", _lib.MAX_ENSEMBLE),
+              ("JH_MAX_ENSEMBLE_FLEET", _lib.MAX_ENSEMBLE_FLEET), ("JH_MAX_PLANT_BLOCKS", _lib.MAX_PLANT_BLOCKS), ("JH_MAX_FLEET_PLANT_BLOCKS", _lib.MAX_FLEET_PLANT_BLOCKS),
+              ("JH_MAX_ID_HORIZON", _lib.MAX_ID_HORIZON), ("JH_MAX_ID_QUATS", _lib.MAX_ID_QUATS))
+    for name, val in limits:
         m = re.search(rf"#define\s+{name}\s+(\d+)", header)
-        assert m and int(m.group(1)) == val, name
+        assert m and int(m.group(1)) == val and type(val) is int, name
+    assert {name for name, _ in limits} == set(re.findall(r"#define\s+(JH_MAX_\w+)", header))  # every limit of the header has its name in the binding
+
+
+HEADER_SAMPLE = r"""
+/* thing.h -- a comment that holds a call, f(a, b); and a prototype, int jh_ghost(int n); neither is an entry */
+#ifndef THING_H
+#define THING_H
+#include <stddef.h>
+#ifdef __cplusplus
+extern "C" {
+#endif
+#define JH_MAX_THINGS 7 /* things (a, b) */
+#define JH_MAX_WIDE 512
+#define JH_BOTH(a, b) \
+  ((a) + (b))
+typedef struct jh_thing jh_thing;
+enum jh_kind { JH_A = 0, JH_B = 1 };
+const char* jh_name(void);
+int jh_count();
+void jh_thing_destroy(jh_thing* t);
+size_t jh_thing_floats(int n, unsigned int draw, unsigned long long seed, float scale, double tol, size_t stride);
+int jh_thing_create(const void* blob, jh_thing** out); // a line comment, g(a, b);
+int jh_thing_run(const jh_thing* t, const float* x /* DEVICE, (n, 3) */, float* y, void* stream,
+                 const int* plan /* HOST, (a, b) */, int* stats, const unsigned int* draws,
+                 const unsigned long long *seeds, const unsigned char* plant_of_block);
+int jh_thing_set(const jh_thing* const* members, const float* const* rows, void** outs, int lut[4]);
+int jh_thing_weighted(const float* weights, float* ms, const unsigned char* column_mask, const unsigned char* column_mask_sens, void* const* timing);
+typedef struct jh_hooks {
+  int (*run)(const jh_thing* t, int n, float* y);
+  int (*max)(const jh_thing* t);
+} jh_hooks;
+int jh_register(const jh_hooks* hooks);
+#ifdef __cplusplus
+}
+#endif
+#endif
+"""
+
+
+def test_header_reader_maps_every_rule_and_exception():
+    """The reader of judo_amd._lib on a header written here: one declaration per type rule and per named exception, in the shapes the real headers hold."""
+    from judo_amd._lib import read_header
+
+    P, void_p, i = ctypes.POINTER, ctypes.c_void_p, ctypes.c_int
+    table, limits = read_header(HEADER_SAMPLE)
+    assert limits == {"MAX_THINGS": 7, "MAX_WIDE": 512}
+    assert table == {
+        "jh_name": (ctypes.c_char_p, []),
+        "jh_count": (i, []),
+        "jh_thing_destroy": (None, [void_p]),
+        "jh_thing_floats": (ctypes.c_size_t, [i, ctypes.c_uint, ctypes.c_ulonglong, ctypes.c_float, ctypes.c_double, ctypes.c_size_t]),
+        "jh_thing_create": (i, [void_p, P(void_p)]),
+        "jh_thing_run": (i, [void_p, void_p, void_p, void_p, P(i), P(i), P(ctypes.c_uint), P(ctypes.c_ulonglong), P(ctypes.c_ubyte)]),
+        "jh_thing_set": (i, [P(void_p), P(void_p), P(void_p), P(i)]),
+        "jh_thing_weighted": (i, [P(ctypes.c_float), P(ctypes.c_float), void_p, void_p, void_p]),
+        "jh_register": (i, [void_p]),
+    }
+    assert list(table) == ["jh_name", "jh_count", "jh_thing_destroy", "jh_thing_floats", "jh_thing_create", "jh_thing_run", "jh_thing_set", "jh_thing_weighted", "jh_register"]
+    # an exception may name its entry: it holds there and nowhere else
+    table, _ = read_header("int jh_a(const float* x);\nint jh_b(const float* x);", {("const float*", "x", "jh_b"): P(ctypes.c_float)})
+    assert table == {"jh_a": (i, [void_p]), "jh_b": (i, [P(ctypes.c_float)])}
+    # it refuses what it cannot map, and names the entry and the parameter
+    with pytest.raises(TypeError, match=r"jh_bad.*short\* codes"):
+        read_header("int jh_ok(int n);\nint jh_bad(int n,\n           const short* codes /* HOST */);")
+    with pytest.raises(TypeError, match=r"jh_bad.*double\* tol"):
+        read_header("int jh_bad(double* tol);")
+    with pytest.raises(TypeError, match=r"jh_bad.*float\*\*\* rows"):
+        read_header("int jh_bad(float*** rows);")
+    with pytest.raises(TypeError, match=r"jh_bad.*cb"):
+        read_header("int jh_bad(int (*cb)(int, int));")
+    with pytest.raises(TypeError, match=r"jh_bad.*return type `float\*`"):
+        read_header("float* jh_bad(int n);")
+    with pytest.raises(TypeError, match=r"jh_twice"):
+        read_header("int jh_twice(int n);\nint jh_twice(int n);")
+    with pytest.raises(TypeError, match=r"cannot read the declaration `int jh_open\(int n`"):
+        read_header("int jh_open(int n;")
+
+
+def test_ctypes_table_is_the_headers():
+    """Every prototype of the two headers, and nothing else, is bound: the loaded function carries the derived restype and argtypes, and as many parameters as an
+    independent split of the prototype's text counts."""
+    from judo_amd import _lib
+
+    text = "".join(open(os.path.join(ROOT, "include", h)).read() for h in ("judo_amd.h", "judo_amd_xcheck.h"))
+    protos = re.findall(r"\b(jh_\w+)\s*\(([^;()]*)\)\s*;", re.sub(r"/\*.*?\*/", "", text, flags=re.S))
+    counts = {name: 0 if params.strip() in ("", "void") else params.count(",") + 1 for name, params in protos}
+    assert len(protos) == len(counts) == len(_lib.EXPORTED_SYMBOLS) and set(counts) == set(_lib.EXPORTED_SYMBOLS) == set(_lib._SIGNATURES), set(counts) ^ set(_lib.EXPORTED_SYMBOLS)
+    L = _lib.lib()
+    for name, (restype, argtypes) in _lib._SIGNATURES.items():
+        fn = getattr(L, name)
+        assert fn.restype is restype and len(fn.argtypes) == len(argtypes) == counts[name], name
+        assert all(a is b for a, b in zip(fn.argtypes, argtypes)), name
+        assert restype in (None, ctypes.c_int, ctypes.c_size_t, ctypes.c_char_p), name
+
+
+def test_missing_header_is_an_import_error_with_its_path(monkeypatch, tmp_path):
+    from judo_amd import _lib
+
+    monkeypatch.setattr(_lib, "_INCLUDE", str(tmp_path))
+    with pytest.raises(ImportError, match=re.escape(os.path.join(str(tmp_path), "judo_amd.h"))):
+        _lib._read_headers()
 
 
 def test_bench_refuses_a_world_size_that_contradicts_gpus():
